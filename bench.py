@@ -7,7 +7,7 @@ actions (SURVEY.md section 8d recipe: VELOCITY mode, throttle~U[0,100), steer~U[
 next step).  A "step" is one Environment::step() over the whole population.  State is resident in HBM before
 the timed region starts; nothing crosses PCIe inside it.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Multi-GPU: one process per GPU; every rank owns its own shard of `--agents` agents (weak scaling: the global
@@ -15,7 +15,9 @@ population is N x 4096, agent ids are global so the Philox streams do not repeat
 interact, so there is NO data-path collective; torch.distributed (RCCL) is used for the barriers around the
 timed region and for the max-over-ranks of the elapsed time.
 
-The single JSON line printed by rank 0 carries, besides the contract's keys:
+A plain run sets up, runs W warm-up steps, times exactly K steps (`ms_per_step` = that time / K), writes the state the
+last step left with --dump-outputs, and prints the line.  With --full the timed region is repeated 30 times (`value`
+from the median) and the single JSON line printed by rank 0 carries, besides the contract's keys:
   roofline     -- HBM roofline of the step kernel from ALGORITHMIC bytes (354 B per agent-step for C2,
                   SURVEY.md section 8d) divided by the kernel's average duration measured with HIP events on
                   the stream the kernel runs on.  The path is VALU/LDS-bound, not HBM-bound (BASELINE.md
@@ -446,6 +448,14 @@ def emit(args, result):
     os.write(args.json_fd, (json.dumps(result) + "\n").encode())
 
 
+def dump_outputs(state, out_dir):
+    """--dump-outputs: every field of the population's state (BatchedEnvironment.snapshot()) as <out_dir>/<field>.npy, float32
+    fields as they are, the integer flags and counters widened to float64 (exact).  For C2 this is 5.5 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in state.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 def dist_record(args, dist, world):
     """What the line says about the process group its collectives ran on (None: no group, every collective was skipped)."""
     if not (args.dist_on and dist.is_initialized()):
@@ -503,8 +513,9 @@ def main():
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4", "c5"],
                     help="c2: headline (random actions); c3/c4: EvolutionaryRacer generations (population 8192 x 32 rays per GPU, "
                          "Monza / Spa, fused MLP policy, score, select, mate; c4 adds the per-generation RCCL fitness all-gather)")
-    ap.add_argument("--repeats", type=int, default=30,
-                    help="the K-step timed region is run this many times back to back (state continues); `value` is from the median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K-step timed region is run this many times back to back (state continues); `value` is from the median "
+                         "(default: 1, so that the run times exactly --steps steps; 30 with --full)")
     ap.add_argument("--generations", type=int, default=5)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, default).  gloo + --single-device rehearses the multi-process path on a one-GPU box")
@@ -513,9 +524,20 @@ def main():
                     help="create the process group at world size 1 too (RANK 0 of 1, 127.0.0.1): the barriers, the max-over-ranks "
                          "all-reduce and C4's fitness all-gather then run on a real one-rank RCCL communicator instead of being skipped")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the secondary one-launch-per-step and host-boundary loops (used under rocprofv3 so that the "
-                         "kernel trace holds only the timed region's launches)")
+                    help="with --full: skip the secondary one-launch-per-step and host-boundary loops (used under rocprofv3 so that "
+                         "the kernel trace holds only the timed region's launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="C2: besides the headline, measure everything else the line can carry -- 30 timed regions by default, HIP-event "
+                         "kernel times and the roofline, broad-phase work, one launch per step, the host boundary, the callers, "
+                         "configs 3 / 4 / 5, the CPU baseline.  Without it the run sets up, warms up, times --steps steps and prints "
+                         "the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="C2: after the timed steps, write the population's state as the last timed step left it (poses, flags, "
+                         "per-ray hits and distances: what a caller of the step receives) as DIR/<field>.npy, float32 / float64; "
+                         "rank 0's agents when --gpus > 1")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.config != "c2":
+        ap.error("--dump-outputs writes the C2 step's outputs; --config %s has none" % args.config)
 
     # ---- --gpus N is a promise: the line printed at the end says n_gpus = N or the run fails ----
     # Under torchrun (the driver's way of starting N > 1) WORLD_SIZE is set and must equal --gpus.  Started plainly with
@@ -610,10 +632,12 @@ def main():
     run_steps(args.warmup, 0)
     fence()
     # ---- timed region: exactly K steps between two fences, repeated `repeats` times back to back (the state simply
-    # continues).  One region at the driver's --steps 20 is a single 0.3 ms launch, so a single sample says little: the
-    # headline is the MEDIAN region, min / max / spread are reported beside it.  Every region's time is the max over ranks.
-    repeats = max(1, args.repeats)
-    env.set_timing(True)
+    # continues).  One region at the driver's --steps 20 is a single 0.3 ms launch, so a single sample says little: with
+    # --full the headline is the MEDIAN of 30 regions, min / max / spread are reported beside it.  Every region's time is the
+    # max over ranks.
+    repeats = max(1, args.repeats if args.repeats is not None else (30 if args.full else 1))
+    if args.full:
+        env.set_timing(True)
     region_s = []
     for rep in range(repeats):
         fence()
@@ -623,11 +647,56 @@ def main():
         torch.cuda.synchronize()
         region_s.append(time.perf_counter() - t0)
     sharding.barrier(device_ids=[local_rank])
-    kernel_ms, launches = env.get_timing()
-    env.set_timing(False)
+    if args.full:
+        kernel_ms, launches = env.get_timing()
+        env.set_timing(False)
     region_s = sharding.max_over_ranks_list(region_s, device=args.tensor_dev)
     elapsed_max = float(np.median(region_s))
     steps_done = args.warmup + repeats * args.steps
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(env.snapshot(), args.dump_outputs)
+
+    result = None
+    if rank == 0:
+        total_agents = N * world
+        value = total_agents * args.steps / elapsed_max
+        result = {
+            "metric": "agent-steps/sec",
+            "value": value,
+            "unit": "agent-steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed_max / args.steps * 1e3,
+            "repeats": repeats,
+            "ms_per_step_min": min(region_s) / args.steps * 1e3,
+            "ms_per_step_max": max(region_s) / args.steps * 1e3,
+            "spread": (max(region_s) - min(region_s)) / elapsed_max if elapsed_max > 0 else None,
+            "spread_p10_p90": float(np.percentile(region_s, 90) - np.percentile(region_s, 10)) / elapsed_max if elapsed_max > 0 else None,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": "C2: %d agents x %d rays per GPU, %s.csv (S=%d segments), Philox random actions + auto reset, "
+                                   "HIP fused kinematics+raycast+collision" % (N, R, args.track, track.S),
+                       "agents_per_gpu": N, "rays": R, "track": args.track, "segments": track.S,
+                       "global_agents": total_agents, "agent_base_per_rank": [r * N for r in range(world)],
+                       "steps_per_launch": spl, "parallelism": "dp%d (agent shards, no collective)" % world,
+                       "grid_cell": info["grid_cell"], "lds_bytes": info["front_back_bytes"] or info["lds_bytes"]},
+            "rays_per_sec": value * R,
+            # what the reference's sweep would have to evaluate for the same result: every ray against all S segments
+            "brute_force_equivalent_ray_segment_tests_per_sec": value * R * track.S,
+            "dist": dist_record(args, dist, world),
+        }
+    if not args.full:
+        if rank == 0:
+            emit(args, result)
+        env.close()
+        if args.dist_on:
+            sharding.barrier(device_ids=[local_rank])
+            dist.destroy_process_group()
+        return
 
     # ---- secondary figure: one launch per step (what a host-side policy between steps would see) ----
     one_steps = 0 if args.headline_only else min(args.steps, 500)
@@ -674,8 +743,6 @@ def main():
             log("callers benchmark failed: %s" % callers["error"])
 
     if rank == 0:
-        total_agents = N * world
-        value = total_agents * args.steps / elapsed_max
         b_alg = algorithmic_bytes_per_agent_step(N, R, track.S)
         avg_launch_s = (kernel_ms * 1e-3) / max(launches, 1)
         steps_per_launch_avg = repeats * args.steps / max(launches, 1)
@@ -740,33 +807,7 @@ def main():
                              "valu_issue_frac": valu["simd_valu_issue_frac"], "valu_lane_utilisation": valu["valu_lane_utilisation"]})
         else:
             roofline.update({"achieved": hbm["achieved"], "peak": hbm["peak"], "unit": hbm["unit"], "frac": hbm["frac"]})
-        result = {
-            "metric": "agent-steps/sec",
-            "value": value,
-            "unit": "agent-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed_max / args.steps * 1e3,
-            "repeats": repeats,
-            "ms_per_step_min": min(region_s) / args.steps * 1e3,
-            "ms_per_step_max": max(region_s) / args.steps * 1e3,
-            "spread": (max(region_s) - min(region_s)) / elapsed_max if elapsed_max > 0 else None,
-            "spread_p10_p90": float(np.percentile(region_s, 90) - np.percentile(region_s, 10)) / elapsed_max if elapsed_max > 0 else None,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": "C2: %d agents x %d rays per GPU, %s.csv (S=%d segments), Philox random actions + auto reset, "
-                                   "HIP fused kinematics+raycast+collision" % (N, R, args.track, track.S),
-                       "agents_per_gpu": N, "rays": R, "track": args.track, "segments": track.S,
-                       "global_agents": total_agents, "agent_base_per_rank": [r * N for r in range(world)],
-                       "steps_per_launch": spl, "parallelism": "dp%d (agent shards, no collective)" % world,
-                       "grid_cell": info["grid_cell"], "lds_bytes": info["front_back_bytes"] or info["lds_bytes"]},
-            "rays_per_sec": value * R,
-            # what the reference's sweep would have to evaluate for the same result: every ray against all S segments
-            "brute_force_equivalent_ray_segment_tests_per_sec": value * R * track.S,
+        result.update({
             "valu_roofline": valu,
             "counter_profile_note": profile_note,
             # S_tested = exact ray-segment tests per ray (one whole-ray walk per ray at the final poses; the
@@ -787,10 +828,9 @@ def main():
             "value_one_launch_per_step": (N * one_steps / one_elapsed) if one_steps else None,
             "value_host_boundary_pcie_inclusive": (N * pcie_steps / pcie_elapsed) if pcie_steps else None,
             "crashed_fraction_at_end": crashed_frac,
-            "dist": dist_record(args, dist, world),
             "callers": callers,
             "roofline": roofline,
-        }
+        })
         result["cpu_baseline"] = None
         if world == 1 and not args.no_cpu_baseline:
             try:

@@ -9,6 +9,9 @@ reference-derived part):   python tests/golden/make_golden.py
   ref_kinematics.npz  -- FROM THE REFERENCE's compiled Agent.cpp: Agent::move trajectories (VELOCITY and
                          ACCELERATION) under seeded actions, 400 steps each; plus the default sensor fan and the
                          Agent::reset probe.
+  ref_answers.npz     -- FROM THE REFERENCE's compiled Agent.cpp and RaceTrack.cpp: its answers to the inputs of
+                         tests/test_oracle_vs_ref.py (track geometry, nearest indices, boundary / lane distances for
+                         3000 probes, 3000-step Agent::move trajectories, layout facts, the Agent::reset probe).
   c1_trajectory.npz   -- from the ORACLE (parity definition, ok_sincosf trig): BASELINE config 1 shape (64 agents x
                          16 rays, Austin), bench driver loop, 450 steps: full state every 50 steps and at the end.
                          A regression pin for oracle and GPU path alike (the reference cannot produce it: its
@@ -88,7 +91,9 @@ def main():
         for k in ("pos_x", "pos_y", "rot", "speed", "crashed", "timed_out", "disp_ctr", "dist", "rel_x", "rel_y"):
             traj["s%03d_%s" % ((chunk + 1) * 50, k)] = s[k]
     np.savez_compressed(os.path.join(HERE, "c1_trajectory.npz"), **traj)
-    for f in ("ref_tracks.npz", "ref_kinematics.npz", "c1_trajectory.npz"):
+    import test_oracle_vs_ref as T  # the inputs tests/test_oracle_vs_ref.py puts to the reference, and its answers
+    np.savez_compressed(os.path.join(HERE, "ref_answers.npz"), **T.ref_answers())
+    for f in ("ref_tracks.npz", "ref_kinematics.npz", "c1_trajectory.npz", "ref_answers.npz"):
         print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
 
 

@@ -38,3 +38,9 @@ def test_plain_start_with_two_gpus_spawns_two_ranks_and_relays_their_exit_code()
     assert r.returncode != 0
     assert r.stderr.count("bench.py needs a GPU") >= 1
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_is_refused_where_there_is_no_c2_step():
+    r = run_bench(["--config", "c5", "--dump-outputs", "out"])
+    assert r.returncode == 2 and "--dump-outputs writes the C2 step's outputs" in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,10 +1,12 @@
-"""The line the driver reads: `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON object with the contract's keys, the
-roofline and cpu_baseline objects, and -- this round -- BASELINE configs 3 and 5 and the broad-phase figures."""
+"""The line the driver reads: `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON object with the contract's keys after
+timing exactly K steps, and writes the state the last step left with --dump-outputs; with --full the line also carries the roofline
+and cpu_baseline objects, BASELINE configs 3 and 5 and the broad-phase figures."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,8 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_default_run_prints_the_contract_line(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--repeats", "4"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--repeats", "4",
+                        "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -56,3 +58,38 @@ def test_default_run_prints_the_contract_line(gpu):
     for steps, alive, off_alive in zip(isl["steps"], isl["alive_at_end"], isl["off_grid_alive"]):
         assert (steps == 4000) == (alive > 0) and off_alive <= alive
     assert [l for l in r.stdout.splitlines() if l.strip()] == lines  # stdout is the line and nothing else
+
+
+def test_plain_run_times_k_steps_and_dumps_the_same_outputs_every_time(gpu, tmp_path):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "250", "--warmup", "7",
+                            "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1  # stdout is the line and nothing else
+        runs.append(json.loads(lines[0]))
+    for j in runs:
+        assert j["metric"] == "agent-steps/sec" and j["unit"] == "agent-steps/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert j["n_gpus"] == 1 and j["steps"] == 250 and j["warmup"] == 7 and j["repeats"] == 1
+        assert j["value"] > 1e8 and abs(j["value"] - 4096 / (j["ms_per_step"] * 1e-3)) / j["value"] < 1e-6
+        for k in ("roofline", "cpu_baseline", "configs", "callers", "broad_phase"):  # measured with --full only
+            assert k not in j, k
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "dist.npy" in files and "pos_x.npy" in files and "crashed.npy" in files
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a.view(np.uint8), b.view(np.uint8)), f
+    assert np.load(tmp_path / "a" / "dist.npy").shape == (4096, 64)
+    # the state is the one 7 + 250 steps of the recipe leave: what the product's own driver loop computes for them
+    import openkitchen_amd as ok
+    e = ok.BatchedEnvironment.from_track(ok.Track("Silverstone"), 4096, 64, device=0)
+    e.init_bench_state(0, ok.capi.MODE_VELOCITY)
+    for step0, n in ((0, 7), (7, 100), (107, 100), (207, 50)):  # bench.py's launches: --steps-per-launch 100
+        e.rollout_random(n, 1234, 0, step0)
+    want = e.snapshot()
+    e.close()
+    for k, v in want.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert np.array_equal(got, v.astype(got.dtype)), k

@@ -62,7 +62,7 @@ def test_wrong_world_size_fails_loudly(gpu):
 
 
 def test_headline_config_on_two_ranks(gpu):
-    j = torchrun_bench("--steps", "20", "--warmup", "5", "--repeats", "5", "--no-cpu-baseline", "--headline-only")
+    j = torchrun_bench("--steps", "20", "--warmup", "5", "--repeats", "5", "--no-cpu-baseline", "--headline-only", "--full")
     assert j["n_gpus"] == 2 and j["scaling"] == "weak" and j["steps"] == 20 and j["repeats"] == 5
     assert j["config"]["global_agents"] == 2 * j["config"]["agents_per_gpu"] == 8192
     assert j["config"]["agent_base_per_rank"] == [0, 4096]

@@ -4,13 +4,14 @@
 # (FETCH_SIZE and WRITE_SIZE in separate --pmc passes, as MI355X_MICROARCH.md prescribes), SQ instruction mix.
 set -e
 TAG=$1
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profile_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $GRAFT_REPO_ROOT/bench.py --steps 1000 --warmup 100 --steps-per-launch 100 --repeats 3 --no-cpu-baseline --headline-only"
+BENCH="python3 $ROOT/bench.py --steps 1000 --warmup 100 --steps-per-launch 100 --repeats 3 --no-cpu-baseline --headline-only --full"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/stats_bench.json 2> $OUT/stats.log
-# the command the driver runs (one 20-step launch per timed region, 30 regions)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_k20 -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --headline-only > $OUT/stats_k20_bench.json 2> $OUT/stats_k20.log
+# the driver's command with --full (one 20-step launch per timed region, 30 regions)
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_k20 -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --headline-only --full > $OUT/stats_k20_bench.json 2> $OUT/stats_k20.log
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" \
            "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM" \
