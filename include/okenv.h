@@ -438,6 +438,47 @@ OKENV_API int okenv_debug_sincos(int32_t device, const float *x, float *s, float
 /* First-hit parameter t for n arbitrary rays (origin, angle [rad]) through the handle's grid (host pointers). */
 OKENV_API int okenv_debug_cast_rays(okenv_t h, const float *ox, const float *oy, const float *angle_rad, int32_t n, float *out_t);
 
+/* The step-kernel launch sites of openkitchen_amd/csrc/okenv_capi.hip (launchStep, startResident), one per instantiation the
+ * launcher can pick.  The tests use them to check which form a call ran. */
+enum okenv_step_form {
+    OKENV_FORM_TAIL_Q,             /* okStepTailKernel<kPolicyQ, 0>: a short Q-learning episode list, one agent per workgroup */
+    OKENV_FORM_TAIL_MLP32,         /* okStepTailKernel<kPolicyMlp, 32> */
+    OKENV_FORM_TAIL_MLP15,         /* okStepTailKernel<kPolicyMlp, 15> */
+    OKENV_FORM_TAIL_MLP,           /* okStepTailKernel<kPolicyMlp, 0>: any other fan */
+    OKENV_FORM_COOP_Q,             /* okStepCoopKernel<kPolicyQ> */
+    OKENV_FORM_COOP_CTRL,          /* okStepCoopKernel<kPolicyCtrl> */
+    OKENV_FORM_COOP_MLP32,         /* okStepCoopKernel<kPolicyMlp, false, false, false, 32>: 32 rays in 32-lane groups */
+    OKENV_FORM_COOP_MLP,           /* okStepCoopKernel<kPolicyMlp> */
+    OKENV_FORM_COOP_PACKED_DIRECT, /* okStepCoopKernel<kPolicyNone, true, false, true>: okenv_step_packed, direct intervals */
+    OKENV_FORM_COOP_PACKED,        /* okStepCoopKernel<kPolicyNone, true> */
+    OKENV_FORM_COOP_DIRECT,        /* okStepCoopKernel<kPolicyNone, false, false, true> */
+    OKENV_FORM_COOP_G64_RANDOM,    /* okStepCoopKernel<kPolicyNone, false, false, false, 64, true>: okenv_rollout_random */
+    OKENV_FORM_COOP_G64,           /* okStepCoopKernel<kPolicyNone, false, false, false, 64> */
+    OKENV_FORM_COOP,               /* okStepCoopKernel<kPolicyNone> */
+    OKENV_FORM_RESIDENT_DIRECT,    /* okStepCoopKernel<kPolicyNone, true, true, true>: the resident packed step */
+    OKENV_FORM_RESIDENT,           /* okStepCoopKernel<kPolicyNone, true, true> */
+    OKENV_FORM_LDS,                /* okStepKernel<kGridLds, kPolicyNone>: every lane walks its own rays (OKENV_COOP=0, or > 64 rays) */
+    OKENV_FORM_LDS_MLP,            /* okStepKernel<kGridLds, kPolicyMlp> */
+    OKENV_FORM_GLOBAL,             /* okStepKernel<kGridGlobal, kPolicyNone> */
+    OKENV_FORM_GLOBAL_MLP,         /* okStepKernel<kGridGlobal, kPolicyMlp> */
+    OKENV_FORM_BRUTE,              /* okStepKernel<kGridBrute, kPolicyNone> */
+    OKENV_FORM_BRUTE_MLP,          /* okStepKernel<kGridBrute, kPolicyMlp> */
+    OKENV_NUM_STEP_FORMS
+};
+/* Attributes of a launch, counted beside its form. */
+enum okenv_step_form_attr {
+    OKENV_FORM_ATTR_FRONT_BACK,       /* walked the front / back images */
+    OKENV_FORM_ATTR_LIST,             /* stepped an episode list */
+    OKENV_FORM_ATTR_WIDENED,          /* Q-learning list launched with wider lane groups than the handle's */
+    OKENV_FORM_ATTR_CTRL_LDS,         /* controller parameters staged in LDS */
+    OKENV_FORM_ATTR_AGENTS_PER_BLOCK, /* a fixed number of agents per workgroup (okenv_info.agents_per_block > 0) */
+    OKENV_NUM_STEP_FORM_ATTRS
+};
+/* Step-kernel launches of the handle since it was created (or last cleared), by form: out[f * (1 + OKENV_NUM_STEP_FORM_ATTRS)]
+ * counts the launches of form f, the OKENV_NUM_STEP_FORM_ATTRS words after it those of them with each attribute.  n_words must
+ * be at least OKENV_NUM_STEP_FORMS * (1 + OKENV_NUM_STEP_FORM_ATTRS); clear != 0 zeroes the counts after copying them. */
+OKENV_API int okenv_debug_step_forms(okenv_t h, uint64_t *out, int32_t n_words, int32_t clear);
+
 #ifdef __cplusplus
 }
 #endif

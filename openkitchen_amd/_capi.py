@@ -47,8 +47,14 @@ SYMBOLS = [
     "okenv_tracker_update", "okenv_step_packed",
     "okenv_controller_create", "okenv_controller_num_params", "okenv_controller_set_params", "okenv_controller_act", "okenv_rollout_controller",
     "okenv_episode_begin", "okenv_episode_compact", "okenv_episode_end", "okenv_episode_tail_limit", "okenv_work_stats",
-    "okenv_ga_scores_device", "okenv_get_stream", "okenv_off_grid_count", "okenv_work_stats_split",
+    "okenv_ga_scores_device", "okenv_get_stream", "okenv_off_grid_count", "okenv_work_stats_split", "okenv_debug_step_forms",
 ]
+
+# enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
+STEP_FORMS = ["tail_q", "tail_mlp32", "tail_mlp15", "tail_mlp", "coop_q", "coop_ctrl", "coop_mlp32", "coop_mlp",
+              "coop_packed_direct", "coop_packed", "coop_direct", "coop_g64_random", "coop_g64", "coop", "resident_direct", "resident",
+              "lds", "lds_mlp", "global", "global_mlp", "brute", "brute_mlp"]
+STEP_FORM_ATTRS = ["front_back", "list", "widened", "ctrl_lds", "agents_per_block"]
 
 
 class OkenvInfo(C.Structure):
@@ -128,6 +134,7 @@ def load(build_if_missing=True):
     L.okenv_track_queries.argtypes = [vp, vp, vp, i32, vp, vp]
     L.okenv_debug_sincos.argtypes = [i32, vp, vp, vp, i32]
     L.okenv_debug_cast_rays.argtypes = [vp, vp, vp, vp, i32, vp]
+    L.okenv_debug_step_forms.argtypes = [vp, vp, i32, i32]
     L.okenv_policy_mlp_create.argtypes = [vp, i32, u32, u32]
     L.okenv_policy_mlp_weights_per_agent.argtypes = [vp]
     L.okenv_policy_mlp_get_weights.argtypes = [vp, vp]

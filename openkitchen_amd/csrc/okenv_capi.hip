@@ -142,6 +142,9 @@ struct okenv
     std::chrono::steady_clock::time_point packed_last_end{};
     size_t      stage_slots_off{0}; // where the agents' slots lie in h_stage
     float       phase1_range{48.F}; // T1 of the cooperative kernel [px]
+    bool        ep_prelist{false};  // okenv_episode_begin has run, the episode's first rollout has not: it decides the pre-listing
+    // step-kernel launches by form and attribute (okenv_debug_step_forms)
+    uint64_t    form_counts[OKENV_NUM_STEP_FORMS][1 + OKENV_NUM_STEP_FORM_ATTRS]{};
     std::string last_error;
     bool        timing{false};
     std::vector<EventPair> events;      // recorded pairs awaiting resolution
@@ -332,9 +335,31 @@ OkStepParams baseParams(okenv *h)
 // An episode ends without its end-of-episode corrections when agent state is changed from outside the policy rollouts.
 void dropEpisode(okenv *h)
 {
-    h->episode  = false;
-    h->n_active = -1;
-    h->ep_kind  = 0;
+    h->episode    = false;
+    h->n_active   = -1;
+    h->ep_kind    = 0;
+    h->ep_prelist = false;
+}
+
+long tailLimit(const okenv *h, bool q_launch);
+
+// The first rollout of an episode (kind: kPolicyMlp / kPolicyQ / kPolicyCtrl): a population that fits the tail kernel (the
+// reference's 50 agents, say) is listed from the start.  Nobody is settled yet, so the list is 0 ... N-1 and its length is known
+// without asking the device -- the very first rollout then already runs one agent per workgroup, each leaving with its agent,
+// instead of the cooperative kernel that okenv_episode_compact would only replace after the first launch.  Decided here and not in
+// okenv_episode_begin because it depends on the rollout's policy (the Q-learning kernel's tail limit is lower; the controller
+// rollout has no tail form), and a handle may have several policies attached.
+int prelistEpisode(okenv *h, const int kind)
+{
+    if (!h->ep_prelist)
+        return OKENV_OK;
+    h->ep_prelist = false;
+    if (kind == kPolicyCtrl || h->n_active >= 0 || static_cast<long>(h->N) > tailLimit(h, kind == kPolicyQ))
+        return OKENV_OK;
+    hipLaunchKernelGGL(okEpisodeCompactKernel, dim3(1), dim3(1024), 0, h->stream, h->d_settled, h->st.crashed, h->N, h->d_active, h->d_ep_counts);
+    OK_HIP(h, hipGetLastError());
+    h->n_active = h->N;
+    return OKENV_OK;
 }
 
 int beginTiming(okenv *h, EventPair *ev)
@@ -496,6 +521,19 @@ bool directIntervals(const okenv *h)
 
 void useFrontBack(const okenv *h, OkStepParams &p);
 
+// One step-kernel launch of form `form` (enum okenv_step_form) with parameters `p`: counted next to every hipLaunchKernelGGL of a
+// step kernel, so that the tests can tell which instantiation a call ran (okenv_debug_step_forms).  Host-side only.
+void countForm(okenv *h, const int form, const OkStepParams &p)
+{
+    uint64_t *c = h->form_counts[form];
+    c[0] += 1U;
+    c[1 + OKENV_FORM_ATTR_FRONT_BACK] += p.fb != 0U ? 1U : 0U;
+    c[1 + OKENV_FORM_ATTR_LIST] += p.active != nullptr ? 1U : 0U;
+    c[1 + OKENV_FORM_ATTR_WIDENED] += p.G > h->G ? 1U : 0U;
+    c[1 + OKENV_FORM_ATTR_CTRL_LDS] += p.ctrl_lds_off != 0U ? 1U : 0U;
+    c[1 + OKENV_FORM_ATTR_AGENTS_PER_BLOCK] += p.agents_per_block > 0 ? 1U : 0U;
+}
+
 // Starts the resident kernel on a stream of its own; `p` carries the exchange pointers of okenv_step_packed.
 int startResident(okenv *h, OkStepParams p, volatile uint32_t *slots)
 {
@@ -515,11 +553,17 @@ int startResident(okenv *h, OkStepParams p, volatile uint32_t *slots)
         lds = h->fb_bytes + kCoopLdsExtra;
     }
     if (directIntervals(h))
+    {
+        countForm(h, OKENV_FORM_RESIDENT_DIRECT, p);
         hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true, true, true>), dim3(h->grid_blocks), dim3(h->block_threads), lds, h->resident_stream, p, off,
                            h->phase1_range);
+    }
     else
+    {
+        countForm(h, OKENV_FORM_RESIDENT, p);
         hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true, true>), dim3(h->grid_blocks), dim3(h->block_threads), lds, h->resident_stream, p, off,
                            h->phase1_range);
+    }
     OK_HIP(h, hipGetLastError());
     h->resident = true;
     return OKENV_OK;
@@ -626,8 +670,6 @@ int waitPackedDone(okenv *h, const volatile uint32_t *word, const uint32_t seq)
     }
 }
 
-long tailLimit(const okenv *h, bool q_launch);
-
 // Points a launch at the [front | back] images instead of the combined one (ok_grid.h: okClassifyFrontBack).
 void useFrontBack(const okenv *h, OkStepParams &p)
 {
@@ -733,25 +775,29 @@ int launchStep(okenv *h, OkStepParams p) // (by value: the diagnostic build adds
             }
 #endif
             if (q_launch)
+            {
+                countForm(h, OKENV_FORM_TAIL_Q, p);
                 hipLaunchKernelGGL((okStepTailKernel<kPolicyQ, 0>), tgrid, tblock, lds, h->stream, p, off);
+            }
             else if (h->R == 32)
+            {
+                countForm(h, OKENV_FORM_TAIL_MLP32, p);
                 hipLaunchKernelGGL((okStepTailKernel<kPolicyMlp, 32>), tgrid, tblock, lds, h->stream, p, off);
+            }
             else if (h->R == 15) // the reference's own fan (Agent.cpp:13-17; EvolutionaryRacer's 17-30-6 network): weights in registers as well
+            {
+                countForm(h, OKENV_FORM_TAIL_MLP15, p);
                 hipLaunchKernelGGL((okStepTailKernel<kPolicyMlp, 15>), tgrid, tblock, lds, h->stream, p, off);
+            }
             else
+            {
+                countForm(h, OKENV_FORM_TAIL_MLP, p);
                 hipLaunchKernelGGL((okStepTailKernel<kPolicyMlp, 0>), tgrid, tblock, lds, h->stream, p, off);
+            }
             OK_HIP(h, hipGetLastError());
             return endTiming(h, ev);
         }
     }
-#define OK_LAUNCH_GENERIC(MODE, LDS)                                                                                   \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        if (policy == kPolicyMlp)                                                                                      \
-            hipLaunchKernelGGL((okStepKernel<MODE, kPolicyMlp>), grid, block, LDS, h->stream, p);                      \
-        else                                                                                                           \
-            hipLaunchKernelGGL((okStepKernel<MODE, kPolicyNone>), grid, block, LDS, h->stream, p);                     \
-    } while (0)
     switch (h->grid_mode)
     {
     case kGridLds:
@@ -768,7 +814,10 @@ int launchStep(okenv *h, OkStepParams p) // (by value: the diagnostic build adds
                 lds = h->fb_bytes + kCoopLdsExtra;
             }
             if (p.action_source == kActionsQLearning)
+            {
+                countForm(h, OKENV_FORM_COOP_Q, p);
                 hipLaunchKernelGGL(okStepCoopKernel<kPolicyQ>, grid, block, lds + qLdsBytes(h), h->stream, p, off, phase1);
+            }
             else if (p.action_source == kActionsController)
             { // the controllers' parameters of a workgroup's agents go into its LDS when they fit behind the centre line
                 const size_t base  = ((lds + qLdsBytes(h) + 15U) / 16U) * 16U;
@@ -779,37 +828,86 @@ int launchStep(okenv *h, OkStepParams p) // (by value: the diagnostic build adds
                     p.ctrl_lds_off = static_cast<uint32_t>(base);
                     total          = base + stage;
                 }
+                countForm(h, OKENV_FORM_COOP_CTRL, p);
                 hipLaunchKernelGGL(okStepCoopKernel<kPolicyCtrl>, grid, block, total, h->stream, p, off, phase1);
             }
             else if (policy == kPolicyMlp && h->G == 32 && h->R == 32) // C3 / C4's fan: group and fan width compile-time constants
+            {
+                countForm(h, OKENV_FORM_COOP_MLP32, p);
                 hipLaunchKernelGGL((okStepCoopKernel<kPolicyMlp, false, false, false, 32>), grid, block, lds, h->stream, p, off, h->phase1_range);
+            }
             else if (policy == kPolicyMlp)
+            {
+                countForm(h, OKENV_FORM_COOP_MLP, p);
                 hipLaunchKernelGGL(okStepCoopKernel<kPolicyMlp>, grid, block, lds, h->stream, p, off, h->phase1_range);
+            }
             else if (p.rec_in != nullptr && directIntervals(h))
+            {
+                countForm(h, OKENV_FORM_COOP_PACKED_DIRECT, p);
                 hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true, false, true>), grid, block, lds, h->stream, p, off, h->phase1_range);
+            }
             else if (p.rec_in != nullptr)
+            {
+                countForm(h, OKENV_FORM_COOP_PACKED, p);
                 hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true>), grid, block, lds, h->stream, p, off, h->phase1_range);
+            }
             else if (directIntervals(h))
+            {
+                countForm(h, OKENV_FORM_COOP_DIRECT, p);
                 hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, false, false, true>), grid, block, lds, h->stream, p, off, h->phase1_range);
+            }
             else if (h->G == 64 && p.action_source == kActionsPhiloxReset && p.do_move != 0 && p.reset_flags == 0U)
-                // okenv_rollout_random without device-side resetAgent: its launch-time switches as constants (-1 %)
+            { // okenv_rollout_random without device-side resetAgent: its launch-time switches as constants (-1 %)
+                countForm(h, OKENV_FORM_COOP_G64_RANDOM, p);
                 hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, false, false, false, 64, true>), grid, block, lds, h->stream, p, off, h->phase1_range);
+            }
             else if (h->G == 64) // one agent per wave, the group width a compile-time constant (-1 % on 20-step launches)
+            {
+                countForm(h, OKENV_FORM_COOP_G64, p);
                 hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, false, false, false, 64>), grid, block, lds, h->stream, p, off, h->phase1_range);
+            }
             else
+            {
+                countForm(h, OKENV_FORM_COOP, p);
                 hipLaunchKernelGGL(okStepCoopKernel<kPolicyNone>, grid, block, lds, h->stream, p, off, h->phase1_range);
+            }
+        }
+        else if (policy == kPolicyMlp)
+        {
+            countForm(h, OKENV_FORM_LDS_MLP, p);
+            hipLaunchKernelGGL((okStepKernel<kGridLds, kPolicyMlp>), grid, block, h->image_bytes, h->stream, p);
         }
         else
-            OK_LAUNCH_GENERIC(kGridLds, h->image_bytes);
+        {
+            countForm(h, OKENV_FORM_LDS, p);
+            hipLaunchKernelGGL((okStepKernel<kGridLds, kPolicyNone>), grid, block, h->image_bytes, h->stream, p);
+        }
         break;
     case kGridGlobal:
-        OK_LAUNCH_GENERIC(kGridGlobal, 0);
+        if (policy == kPolicyMlp)
+        {
+            countForm(h, OKENV_FORM_GLOBAL_MLP, p);
+            hipLaunchKernelGGL((okStepKernel<kGridGlobal, kPolicyMlp>), grid, block, 0, h->stream, p);
+        }
+        else
+        {
+            countForm(h, OKENV_FORM_GLOBAL, p);
+            hipLaunchKernelGGL((okStepKernel<kGridGlobal, kPolicyNone>), grid, block, 0, h->stream, p);
+        }
         break;
     default:
-        OK_LAUNCH_GENERIC(kGridBrute, 0);
+        if (policy == kPolicyMlp)
+        {
+            countForm(h, OKENV_FORM_BRUTE_MLP, p);
+            hipLaunchKernelGGL((okStepKernel<kGridBrute, kPolicyMlp>), grid, block, 0, h->stream, p);
+        }
+        else
+        {
+            countForm(h, OKENV_FORM_BRUTE, p);
+            hipLaunchKernelGGL((okStepKernel<kGridBrute, kPolicyNone>), grid, block, 0, h->stream, p);
+        }
         break;
     }
-#undef OK_LAUNCH_GENERIC
     OK_HIP(h, hipGetLastError());
     return endTiming(h, ev);
 }
@@ -1971,6 +2069,9 @@ extern "C"
             // for crashed agents, so its bookkeeping would fall behind the per-step loop's)
             if (h->tracker_kind != kRewardProgress)
                 return fail(h, OKENV_ERR_STATE, "okenv_rollout_controller: inside an episode the bookkeeping must be OKENV_REWARD_PROGRESS");
+            const int prc = prelistEpisode(h, kPolicyCtrl);
+            if (prc != OKENV_OK)
+                return prc;
             h->ep_kind = kPolicyCtrl;
         }
         OkStepParams p     = baseParams(h);
@@ -2056,6 +2157,9 @@ extern "C"
                 return fail(h, OKENV_ERR_STATE, "okenv_rollout_policy: the running episode belongs to another rollout (okenv_rollout_q / _controller)");
             if ((h->reset_flags & kAutoResetOn) != 0U)
                 return fail(h, OKENV_ERR_STATE, "okenv_rollout_policy: episodes need auto-reset off");
+            const int prc = prelistEpisode(h, kPolicyMlp);
+            if (prc != OKENV_OK)
+                return prc;
             h->ep_kind = kPolicyMlp;
         }
         OkStepParams p  = baseParams(h);
@@ -2086,22 +2190,11 @@ extern "C"
         hipLaunchKernelGGL(okEpisodeBeginKernel, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->st.crashed, h->d_settled, h->d_crash_step,
                            h->d_live, h->N);
         OK_HIP(h, hipGetLastError());
-        h->episode  = true;
-        h->n_active = -1;
-        h->ep_kind  = 0;
-        h->ep_steps = 0U;
-        // A population that fits the tail kernel (the reference's 50 agents, say) is listed from the start: nobody is settled yet,
-        // so the list is 0 ... N-1 and its length is known without asking the device -- the very first rollout then already runs
-        // one agent per workgroup, each leaving with its agent, instead of the cooperative kernel that okenv_episode_compact would
-        // only replace after the first launch.
-        const bool q    = h->d_q_table != nullptr && h->d_mlp_w == nullptr;
-        const bool ctrl = h->d_ctrl_params != nullptr && h->d_mlp_w == nullptr && h->d_q_table == nullptr;
-        if (!ctrl && static_cast<long>(h->N) <= tailLimit(h, q))
-        {
-            hipLaunchKernelGGL(okEpisodeCompactKernel, dim3(1), dim3(1024), 0, h->stream, h->d_settled, h->st.crashed, h->N, h->d_active, h->d_ep_counts);
-            OK_HIP(h, hipGetLastError());
-            h->n_active = h->N;
-        }
+        h->episode    = true;
+        h->n_active   = -1;
+        h->ep_kind    = 0;
+        h->ep_steps   = 0U;
+        h->ep_prelist = true; // (the first rollout lists the population when it fits the tail kernel: prelistEpisode)
         return OKENV_OK;
     }
 
@@ -2116,7 +2209,8 @@ extern "C"
         int32_t counts[2] = {0, 0};
         OK_HIP(h, hipMemcpyAsync(counts, h->d_ep_counts, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
         OK_HIP(h, hipStreamSynchronize(h->stream));
-        h->n_active = counts[1];
+        h->n_active   = counts[1];
+        h->ep_prelist = false;
         if (alive_out)
             *alive_out = counts[0];
         if (listed_out)
@@ -2386,6 +2480,9 @@ extern "C"
                 return fail(h, OKENV_ERR_STATE, "okenv_rollout_q: the running episode belongs to another rollout (okenv_rollout_policy / _controller)");
             if (h->ep_kind == 0)
             {
+                const int prc = prelistEpisode(h, kPolicyQ);
+                if (prc != OKENV_OK)
+                    return prc;
                 h->ep_kind         = kPolicyQ;
                 h->ep_q_seed       = seed;
                 h->ep_q_agent_base = agent_base;
@@ -2783,6 +2880,18 @@ extern "C"
         OK_HIP(h, hipGetLastError());
         OK_HIP(h, hipMemcpyAsync(out_t, dt, 4U * static_cast<size_t>(n), hipMemcpyDeviceToHost, h->stream));
         OK_HIP(h, hipStreamSynchronize(h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_debug_step_forms(okenv_t h, uint64_t *out, int32_t n_words, int32_t clear)
+    {
+        OK_QUIESCE(h);
+        constexpr int32_t kWords = OKENV_NUM_STEP_FORMS * (1 + OKENV_NUM_STEP_FORM_ATTRS);
+        if (!h || !out || n_words < kWords)
+            return fail(h, OKENV_ERR_INVALID, "okenv_debug_step_forms: bad argument (out needs OKENV_NUM_STEP_FORMS * (1 + OKENV_NUM_STEP_FORM_ATTRS) words)");
+        std::memcpy(out, h->form_counts, sizeof(h->form_counts));
+        if (clear != 0)
+            std::memset(h->form_counts, 0, sizeof(h->form_counts));
         return OKENV_OK;
     }
 }

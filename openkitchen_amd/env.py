@@ -408,6 +408,20 @@ class BatchedEnvironment:
         capi.check(self._L.okenv_get_timing(self._h, C.byref(ms), C.byref(n)), self._h)
         return ms.value, n.value
 
+    def step_forms(self, clear=False):
+        """Step-kernel launches since the handle was created (or last cleared), by form (capi.STEP_FORMS, enum okenv_step_form):
+        {"forms": {form: launches}, "attrs": {form: {attribute: launches with it}}}, forms that never ran left out."""
+        width = 1 + len(capi.STEP_FORM_ATTRS)
+        out = np.zeros(len(capi.STEP_FORMS) * width, dtype=np.uint64)
+        capi.check(self._L.okenv_debug_step_forms(self._h, capi.ptr(out), out.size, 1 if clear else 0), self._h)
+        out = out.reshape(len(capi.STEP_FORMS), width)
+        forms, attrs = {}, {}
+        for name, row in zip(capi.STEP_FORMS, out):
+            if row[0]:
+                forms[name] = int(row[0])
+                attrs[name] = {a: int(v) for a, v in zip(capi.STEP_FORM_ATTRS, row[1:])}
+        return {"forms": forms, "attrs": attrs}
+
     def debug_cast_rays(self, ox, oy, angle_rad):
         ox, oy, ang = [np.ascontiguousarray(a, dtype=np.float32) for a in (ox, oy, angle_rad)]
         out = np.zeros(ox.size, dtype=np.float32)

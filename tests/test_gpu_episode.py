@@ -93,6 +93,9 @@ def test_ga_episode_lists_on_the_cooperative_kernel(gpu, oracle, monkeypatch, ta
         assert (steps, live) == want
         assert_same_state(dev.snapshot(), orc.snapshot(), "generation %d" % generation)
         assert np.array_equal(dev.ga_select_mate(5, generation), ga.select_mate(5, generation))
+    forms = dev.step_forms()["forms"]
+    # (okenv_step: the initial observation of each generation)
+    assert set(forms) == ({"coop_direct", "coop_mlp"} if tail == "0" else {"coop_direct", "coop_mlp", "tail_mlp32"}), forms
     dev.close()
 
 
@@ -108,7 +111,7 @@ def test_one_launch_for_the_whole_tail(gpu, oracle):
     want = oracle_ga_loop(orc, ga, 2500)
     dev.episode_begin()
     tail = dev.episode_tail_limit()
-    assert tail >= 256   # (Spa's image leaves room for one workgroup per CU)
+    assert tail >= dev.info()["compute_units"]   # (Spa's image leaves room for one workgroup per CU)
     taken, listed, calls = 0, dev.N, 0
     while taken < 2500:
         n = 2500 - taken if listed <= tail else min(40, 2500 - taken)
@@ -121,6 +124,8 @@ def test_one_launch_for_the_whole_tail(gpu, oracle):
     steps, live = dev.episode_end()
     assert (steps, live) == want and calls == 1
     assert_same_state(dev.snapshot(), orc.snapshot(), "one launch for the tail")
+    forms = dev.step_forms()["forms"]
+    assert forms.get("tail_mlp32") == 1 and set(forms) <= {"coop_direct", "tail_mlp32", "coop_mlp"}, forms
     dev.close()
 
 
@@ -160,6 +165,8 @@ def test_ga_episode_generic_kernel(gpu, oracle):
     steps, live, _ = device_ga_loop(dev, 40, 1200)
     assert (steps, live) == want
     assert_same_state(dev.snapshot(), orc.snapshot(), "generic kernel")
+    forms = dev.step_forms()["forms"]
+    assert set(forms) == {"global", "global_mlp"} and forms["global"] == 1, forms   # (okenv_step: the initial observation)
     dev.close()
 
 
@@ -271,11 +278,14 @@ def test_q_episode_with_agents_crashed_in_earlier_steps_outside_an_episode(gpu, 
 
 def test_q_episode_short_list_gets_wider_lane_groups(gpu, oracle, monkeypatch):
     monkeypatch.setenv("OKENV_TAIL_MAX_AGENTS", "0")   # (the cooperative kernel's treatment of short lists; the tail kernel is the default)
-    _q_short_list(gpu, oracle, monkeypatch)
+    sf = _q_short_list(gpu, oracle, monkeypatch)
+    # (okenv_q_begin_episode's initial observation: one launch of the handle's own form per episode)
+    assert set(sf["forms"]) == {"coop", "coop_q"} and sf["forms"]["coop"] == 2 and sf["attrs"]["coop_q"]["widened"] > 0, sf
 
 
 def test_q_episode_short_list_on_the_tail_kernel(gpu, oracle, monkeypatch):
-    _q_short_list(gpu, oracle, monkeypatch)
+    sf = _q_short_list(gpu, oracle, monkeypatch)
+    assert "tail_q" in sf["forms"] and set(sf["forms"]) <= {"coop", "coop_q", "tail_q"} and sf["forms"]["coop"] == 2, sf
 
 
 def _q_short_list(gpu, oracle, monkeypatch):
@@ -311,7 +321,9 @@ def _q_short_list(gpu, oracle, monkeypatch):
         assert_same_state(dev.snapshot(), orc.snapshot(), "episode %d" % episode)
         assert np.array_equal(bits(dev.q_table()), bits(oq.table()))
         eps = eps - np.float32(0.05)
+    sf = dev.step_forms()
     dev.close()
+    return sf
 
 
 def test_q_episode_arguments_must_stay_consistent(gpu, oracle):

@@ -126,6 +126,7 @@ def test_c2_full_size_equals_oracle(gpu, oracle):
         orc.rollout_random(n, seed, 0, done, threads=threads)
         done += n
         assert_same_state(dev.snapshot(), orc.snapshot(), "C2 full size after %d steps" % done)
+    assert set(dev.step_forms()["forms"]) == {"coop_g64_random"}
     dev.close()
 
 
@@ -282,4 +283,5 @@ def test_populations_beyond_one_round_of_workgroups_equal_oracle_windows(gpu, or
             for k in FIELDS_EXACT:
                 assert np.array_equal(bits(snap[k][b:b + W]), bits(want[k])), (k, b, done)
     assert (snap["crashed"] == 1).any() and snap["disp_ctr"].max() > 0
+    assert set(dev.step_forms()["forms"]) == {"coop_g64_random" if info["lanes_per_agent"] == 64 else "coop"}
     dev.close()

@@ -178,6 +178,7 @@ def test_grid_forms_agree(gpu, oracle, flags):
     dev.rollout_random(120, 99, 0, 0)
     orc.rollout_random(120, 99, 0, 0, threads=8)
     assert_same_state(dev.snapshot(), orc.snapshot(), "flags %d" % flags)
+    assert set(dev.step_forms()["forms"]) == {"global" if flags == 1 else "brute"}
 
 
 @pytest.mark.parametrize("cell", [6.0, 11.0, 37.0, 400.0])

@@ -80,12 +80,18 @@ class Run:
 def test_resident_steps_match_oracle(gpu, oracle, monkeypatch, N, R):
     monkeypatch.setenv("OKENV_RESIDENT", "1")
     run = Run(gpu, oracle, *make(gpu, oracle, N, R, seed=N))
-    assert run.dev.info()["agents_per_block"] == 1
+    resident = N <= run.dev.info()["compute_units"]   # one agent per workgroup, i.e. per CU (every SPX-mode shape here)
+    assert run.dev.info()["agents_per_block"] == (1 if resident else 0)
     run.steps(300)
     info = run.dev.info()
-    assert info["packed_resident_steps"] == 300 and 0 <= info["packed_fallbacks"] <= 300
+    assert info["packed_resident_steps"] == (300 if resident else 0) and 0 <= info["packed_fallbacks"] <= 300
     assert run.dev.step_count == 300
     assert run.check() == 300
+    forms = run.dev.step_forms()["forms"]
+    direct = "_direct" if info["lanes_per_agent"] >= 2 * R else ""   # (spare lanes and no phase 1: intervals dealt directly)
+    if resident:
+        assert forms.get("resident" + direct, 0) >= 1, forms
+    assert set(forms) <= {"resident" + direct, "coop_packed" + direct}, forms
     run.dev.close()
 
 
@@ -108,6 +114,8 @@ def test_resident_yields_to_other_calls_and_comes_back(gpu, oracle, monkeypatch)
     run.steps(5, pause=0.001)
     assert dev.info()["packed_resident_steps"] == 346
     assert run.check() == 106
+    forms = dev.step_forms()["forms"]
+    assert forms.get("resident_direct", 0) >= 3 and set(forms) <= {"resident_direct", "coop_packed_direct"}, forms
     dev.close()
 
 
@@ -136,6 +144,7 @@ def test_resident_never_when_switched_off(gpu, oracle, monkeypatch):
     run.steps(60)
     assert run.dev.info()["packed_resident"] == 0 and run.dev.info()["packed_resident_steps"] == 0
     run.check()
+    assert run.dev.step_forms()["forms"] == {"coop_packed_direct": 60}
     run.dev.close()
 
 
@@ -148,6 +157,8 @@ def test_step_handed_over_too_late_is_redone(gpu, oracle, monkeypatch):
     assert info["packed_fallbacks"] >= 5 and info["packed_resident_steps"] > info["packed_fallbacks"]
     assert run.dev.step_count == 80
     assert run.check() == 80
+    forms = run.dev.step_forms()["forms"]   # every late hand-over is redone by a packed launch of its own
+    assert forms.get("coop_packed_direct", 0) >= info["packed_fallbacks"] and forms.get("resident_direct", 0) >= 1, forms
     run.dev.close()
 
 

@@ -76,6 +76,16 @@ def read_trace(path):
     return out
 
 
+def traced_agent_steps(path):
+    """(calls, agent-steps) complete in the facade's step trace so far: every record of one application has the same size"""
+    raw = np.fromfile(path, dtype=np.uint8, count=16) if os.path.exists(path) else np.zeros(0, dtype=np.uint8)
+    if raw.size < 16:
+        return 0, 0
+    _, n, r, _ = (int(v) for v in raw.view(np.uint32))
+    calls = os.path.getsize(path) // (20 + 4 * r + 2 * n * RECORD.itemsize + 8 * n * r)
+    return calls, calls * n
+
+
 def replay_on_oracle(oracle, track_name, trace, limit):
     """Every traced call again on the CPU oracle, from the state the application handed in: what came back must be the
     oracle's result bit for bit (pose, speed, flags, DisplacementStats, sensor_hits_).  World hit points of crashed agents
@@ -219,7 +229,14 @@ def test_reference_policy_gradient_apps_run_on_the_device_environment(gpu, oracl
     unchanged: 15 agents (PPO) / one agent (REINFORCE), resetAgent to random points, +1 reward per step, a libtorch update per
     episode."""
     trace = str(tmp_path / (app + ".trace"))
-    out = run_app(app, gpu.track_path("Austin"), lambda text: text.count("EPISODE") >= 2, trace=trace)
+
+    def enough(text):
+        # two episodes -- and, however short the policy's random start makes them, steps enough for the moves asserted below
+        # (REINFORCE's single agent can crash twice within 200 steps)
+        calls, agent_steps = traced_agent_steps(trace)
+        return text.count("EPISODE") >= 2 and calls >= 60 and agent_steps >= 400
+
+    out = run_app(app, gpu.track_path("Austin"), enough, trace=trace)
     assert out.count("EPISODE") >= 2, out[-1500:]
     stats = replay_on_oracle(oracle, "Austin", read_trace(trace), 600)
     assert stats["calls"] >= 50 and stats["agents"] == (15 if app == "ppo_sim" else 1) and stats["moved"] > 200, stats
