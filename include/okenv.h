@@ -395,6 +395,76 @@ OKENV_API int okenv_q_table_sums(okenv_t h, float *sum, float *count);
 OKENV_API int okenv_q_assign_mean(okenv_t h, const float *sum, const float *count);
 OKENV_API int okenv_q_share_knowledge(okenv_t h);
 
+/* ---- bird's-eye camera views of every agent ----------------------------------------------------
+ * The frame the reference's image-based applications pull from the window every step (Visualizer::render with the camera
+ * following one agent at zoom 15, Environment/Visualizer.cpp:75-80,159-223, read back by ScreenGrabber::getRenderTargetDevice
+ * and flipped), rendered for ALL N agents at once by one kernel into a device buffer.  The rule, exactly (it is our own; raylib's
+ * rasteriser bits are not claimed):
+ *
+ * Geometry: the reference's draw list, six shadeAreaBetweenCurves calls (Visualizer.cpp:99-138,176-194): ordinal 0 right_bound_inner_ /
+ *   right_bound_outer_ (blue 0,0,255), 1 left_bound_inner_ / left_bound_outer_ (red 255,0,0), 2 left_bound_inner_ / right_bound_inner_
+ *   (green 0,255,0), 3 start_line_ / finish_line_ = {ro.front, ro.back} / {lo.front, lo.back} (green), 4 {ri.front, ri.back} /
+ *   {ro.front, ro.back} (blue), 5 {li.front, li.back} / {lo.front, lo.back} (red): 6P triangles, each in the vertex order the
+ *   reference hands to DrawTriangle after its cross-product reorder (okenv_track_band_triangles lists them).
+ * Inside test, fp32 without contraction, for a triangle (a, b, c) and a sample p: e0 = (b.x-a.x)*(p.y-a.y) - (b.y-a.y)*(p.x-a.x),
+ *   e1 and e2 the same for the edges (b, c) and (c, a); inside iff all three >= 0 or all three <= 0.  A triangle whose
+ *   area (b.x-a.x)*(c.y-a.y) - (b.y-a.y)*(c.x-a.x) is exactly 0 covers nothing.  A sample's band is the LARGEST ordinal among the
+ *   triangles containing it (later draws paint over earlier ones); none: background (0,0,0).
+ * Camera: step_x = view_w / (width*samples), half_x = view_w * 0.5f (fp32, host; y alike).  Sample column col = u*samples + j:
+ *   ox = ((float)col + 0.5f) * step_x - half_x; oy from the row alike.  Row 0 is the smallest world y (the frame after the
+ *   applications' flip({0})).  World-aligned (the reference's camera): wx = pos_x + ox, wy = pos_y + oy.  OKENV_VIEW_HEADING_UP:
+ *   (cs, sn) = cos, sin of OK_DEG2RAD * rot from ok_sincosf, wx = pos_x + (ox*(-sn) - oy*cs), wy = pos_y + (ox*cs - oy*sn).
+ * Agent (drawAgent, Visualizer.cpp:48-64; only the view's own agent): dx = wx - pos_x, dy = wy - pos_y; in the disc iff
+ *   dx*dx + dy*dy <= radius*radius; with OKENV_VIEW_DRAW_HEADING, in the white heading half iff dx*cs + dy*sn >= 0.  The disc has
+ *   the agent colour, or if crashed_ (253,249,0) at alpha 150 over the band: (253*150 + under*105 + 127) / 255 per channel.
+ * Formats, destination contiguous [N, H, W, C] uint8: OKENV_VIEW_RGBA8 (C = 4, alpha 255; samples > 1: per channel the box filter
+ *   (sum + s*s/2) / (s*s) over the s*s samples -- the applications' bilinear resize of a 1600x1400 frame differs from it at
+ *   edges), OKENV_VIEW_CLASS8 (C = 1, samples 1 only): 0 background, 1 right shoulder (ordinals 0, 4), 2 left shoulder (1, 5),
+ *   3 driving surface (2, 3), 4 agent, 5 heading half, 6 crashed agent.
+ */
+#define OKENV_VIEW_RGBA8 0
+#define OKENV_VIEW_CLASS8 1
+#define OKENV_VIEW_DRAW_AGENT 1u
+#define OKENV_VIEW_DRAW_HEADING 2u
+#define OKENV_VIEW_HEADING_UP 4u
+/* the reference's follow camera: a 1600 x 1400 window at zoom 15 (Visualizer.cpp:75-80) */
+#define OKENV_VIEW_FOLLOW_W (1600.0f / 15.0f)
+#define OKENV_VIEW_FOLLOW_H (1400.0f / 15.0f)
+
+typedef struct okenv_view_desc {
+    int32_t  width, height;   /* output pixels, 1..1024 each                                                  */
+    int32_t  samples;         /* per axis: 1, 2 or 4                                                          */
+    int32_t  format;          /* OKENV_VIEW_RGBA8 / OKENV_VIEW_CLASS8                                         */
+    float    view_w, view_h;  /* world extent [px], finite and > 0 (OKENV_VIEW_FOLLOW_W / _H)                  */
+    uint32_t flags;           /* OKENV_VIEW_DRAW_AGENT | OKENV_VIEW_DRAW_HEADING | OKENV_VIEW_HEADING_UP      */
+    float    radius;          /* Agent::radius_ (Agent.h:60: 9), finite and > 0                               */
+    uint8_t  agent_rgb[3];    /* Agent::color_ (Agent.h:63: 80, 80, 80)                                       */
+    uint8_t  reserved;
+} okenv_view_desc;
+
+typedef struct okenv_render_info {
+    int32_t  triangles;       /* of the draw list, zero-area ones left out                                    */
+    int32_t  grid_nx, grid_ny;
+    float    grid_cell;       /* cell edge [px]                                                               */
+    int32_t  registrations;   /* triangle copies over all cells                                               */
+    int32_t  solid_cells;     /* cells whose samples skip the tests (0: not used)                             */
+    int32_t  width, height, samples, channels;
+    uint64_t bytes_per_call;  /* N * H * W * C                                                                */
+} okenv_render_info;
+
+/* Builds the draw list from the four boundary polylines (xy pairs, num_points >= 2 each, host pointers), its grid, and uploads
+ * them; replaces an earlier render setup of the handle.  Synchronises. */
+OKENV_API int okenv_render_create(okenv_t h, const float *left_inner_xy, const float *left_outer_xy, const float *right_inner_xy,
+                                  const float *right_outer_xy, int32_t num_points, const okenv_view_desc *desc);
+/* Renders every agent's view into `dst` (device memory of the handle's device, >= N*H*W*C bytes) from the current pos_x, pos_y,
+ * rot, crashed_ (read only).  One kernel on the handle's stream, no synchronisation: it can be captured into a HIP graph next to
+ * okenv_step.  OKENV_ERR_STATE before okenv_render_create. */
+OKENV_API int okenv_render_views(okenv_t h, void *dst, uint64_t dst_bytes);
+OKENV_API int okenv_render_get_info(okenv_t h, okenv_render_info *out);
+/* The draw list of a track (host only, no GPU): 6P triangles as (a.x, a.y, b.x, b.y, c.x, c.y) in DrawTriangle's order and their
+ * draw ordinals; returns the count (6P), or < 0 on error, and writes min(count, cap) entries (either output may be NULL). */
+OKENV_API int okenv_track_band_triangles(okenv_track_t t, float *xy6, uint8_t *ordinal, int32_t cap);
+
 /* ---- measurement --------------------------------------------------------------------------------- */
 
 /* When enabled, every step/collide/rollout launch is bracketed by HIP events on the handle's stream. */

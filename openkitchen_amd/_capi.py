@@ -28,6 +28,10 @@ F_REWARD, F_FITNESS, F_TRACK_IDX, F_EPISODE_STEPS, F_EPISODE_RETURN, F_PREV_CRAS
 FIELD_NAMES += ["reward", "fitness", "track_idx", "episode_steps", "episode_return", "prev_crashed"]
 FIELD_DTYPE += [np.float32, np.float32, np.int32, np.uint32, np.float32, np.uint8]
 REWARD_STEP, REWARD_PROGRESS = 0, 1
+# bird's-eye camera views (include/okenv.h)
+VIEW_RGBA8, VIEW_CLASS8 = 0, 1
+VIEW_DRAW_AGENT, VIEW_DRAW_HEADING, VIEW_HEADING_UP = 1, 2, 4
+VIEW_FOLLOW_W, VIEW_FOLLOW_H = 1600.0 / 15.0, 1400.0 / 15.0  # as fp32 these equal OKENV_VIEW_FOLLOW_W / _H
 
 # every symbol include/okenv.h declares (tests/test_capi_symbols.py checks the library exports them all)
 SYMBOLS = [
@@ -48,6 +52,7 @@ SYMBOLS = [
     "okenv_controller_create", "okenv_controller_num_params", "okenv_controller_set_params", "okenv_controller_act", "okenv_rollout_controller",
     "okenv_episode_begin", "okenv_episode_compact", "okenv_episode_end", "okenv_episode_tail_limit", "okenv_work_stats",
     "okenv_ga_scores_device", "okenv_get_stream", "okenv_off_grid_count", "okenv_work_stats_split", "okenv_debug_step_forms",
+    "okenv_render_create", "okenv_render_views", "okenv_render_get_info", "okenv_track_band_triangles",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -65,6 +70,18 @@ class OkenvInfo(C.Structure):
                 ("agents_per_block", C.c_int32), ("packed_resident", C.c_int32), ("packed_resident_steps", C.c_int32),
                 ("packed_fallbacks", C.c_int32), ("compute_units", C.c_int32), ("front_back_bytes", C.c_int32),
                 ("back_segments", C.c_int32)]
+
+
+class OkenvViewDesc(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("format", C.c_int32),
+                ("view_w", C.c_float), ("view_h", C.c_float), ("flags", C.c_uint32), ("radius", C.c_float),
+                ("agent_rgb", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class OkenvRenderInfo(C.Structure):
+    _fields_ = [("triangles", C.c_int32), ("grid_nx", C.c_int32), ("grid_ny", C.c_int32), ("grid_cell", C.c_float),
+                ("registrations", C.c_int32), ("solid_cells", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("samples", C.c_int32), ("channels", C.c_int32), ("bytes_per_call", C.c_uint64)]
 
 
 class OkenvError(RuntimeError):
@@ -177,6 +194,10 @@ def load(build_if_missing=True):
     L.okenv_ga_scores_device.argtypes = [vp, C.POINTER(vp)]
     L.okenv_get_stream.argtypes = [vp, C.POINTER(vp)]
     L.okenv_off_grid_count.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.okenv_render_create.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(OkenvViewDesc)]
+    L.okenv_render_views.argtypes = [vp, vp, C.c_uint64]
+    L.okenv_render_get_info.argtypes = [vp, C.POINTER(OkenvRenderInfo)]
+    L.okenv_track_band_triangles.argtypes = [vp, vp, vp, i32]
     _lib = L
     return L
 

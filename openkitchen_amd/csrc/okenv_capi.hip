@@ -20,6 +20,7 @@
 #include "../../include/okenv.h"
 #include "Environment/RaceTrack.h"
 #include "ok_grid.h"
+#include "ok_render.h"
 #include "okenv_kernels.h"
 
 namespace
@@ -151,6 +152,13 @@ struct okenv
     double      timing_carry_ms{0.0};    // pairs resolved early (before a stream switch), not yet reported
     uint64_t    timing_carry_n{0};
     std::vector<EventPair> event_pool;  // reusable pairs
+    // bird's-eye views (okenv_render_create): the validated descriptor, the draw list's grid on the device and its sizes
+    bool            render_ok{false};
+    okenv_view_desc render_desc{};
+    OkRenderGeom    render_geom;        // scalars only: the CSR arrays are released after the upload
+    size_t          render_refs{0};
+    OkRenderTri    *d_render_tris{nullptr};
+    uint32_t       *d_render_start{nullptr};
 };
 
 struct okenv_track
@@ -2761,6 +2769,196 @@ extern "C"
         if (!t || !out_xyxy)
             return OKENV_ERR_INVALID;
         std::memcpy(out_xyxy, t->segments.data(), t->segments.size() * sizeof(Segment2d));
+        return OKENV_OK;
+    }
+
+    // ---- bird's-eye camera views (ok_render.h) ------------------------------------------------------------------------------
+
+    int okenv_track_band_triangles(okenv_track_t t, float *xy6, uint8_t *ordinal, int32_t cap)
+    {
+        if (!t || cap < 0)
+            return OKENV_ERR_INVALID;
+        const RaceTrack &rt = *t->track;
+        const size_t     P  = rt.left_bound_inner_.size();
+        if (P < 2 || rt.left_bound_outer_.size() != P || rt.right_bound_inner_.size() != P || rt.right_bound_outer_.size() != P)
+            return OKENV_ERR_STATE;
+        auto xy = [](const std::vector<Vec2d> &v) {
+            std::vector<float> o(2 * v.size());
+            for (size_t i = 0; i < v.size(); ++i)
+                o[2 * i] = v[i].x, o[2 * i + 1] = v[i].y;
+            return o;
+        };
+        const std::vector<float> li = xy(rt.left_bound_inner_), lo = xy(rt.left_bound_outer_), ri = xy(rt.right_bound_inner_),
+                                 ro = xy(rt.right_bound_outer_);
+        const std::vector<OkRenderTri> list = okRenderDrawList(li.data(), lo.data(), ri.data(), ro.data(), static_cast<int>(P));
+        const size_t                   n    = std::min(list.size(), static_cast<size_t>(cap));
+        for (size_t i = 0; i < n; ++i)
+        {
+            if (xy6)
+            {
+                const OkRenderTri &q = list[i];
+                const float        v[6] = {q.ax, q.ay, q.bx, q.by, q.cx, q.cy};
+                std::memcpy(xy6 + 6 * i, v, sizeof(v));
+            }
+            if (ordinal)
+                ordinal[i] = static_cast<uint8_t>(list[i].ord);
+        }
+        return static_cast<int>(list.size());
+    }
+
+    int okenv_render_create(okenv_t h, const float *left_inner_xy, const float *left_outer_xy, const float *right_inner_xy,
+                            const float *right_outer_xy, int32_t num_points, const okenv_view_desc *desc)
+    {
+        OK_QUIESCE(h);
+        if (!h || !desc || !left_inner_xy || !left_outer_xy || !right_inner_xy || !right_outer_xy)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: NULL argument");
+        if (num_points < 2)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: need at least two points per boundary");
+        const okenv_view_desc &d = *desc;
+        if (d.width < 1 || d.width > 1024 || d.height < 1 || d.height > 1024)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: width and height must be 1..1024");
+        if (d.samples != 1 && d.samples != 2 && d.samples != 4)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: samples must be 1, 2 or 4");
+        if (d.format != OKENV_VIEW_RGBA8 && d.format != OKENV_VIEW_CLASS8)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: unknown format");
+        if (d.format == OKENV_VIEW_CLASS8 && d.samples != 1)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: OKENV_VIEW_CLASS8 takes one sample per pixel");
+        if (!(std::isfinite(d.view_w) && d.view_w > 0.F && std::isfinite(d.view_h) && d.view_h > 0.F))
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: the view extent must be finite and > 0");
+        if (!(std::isfinite(d.radius) && d.radius > 0.F))
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: the radius must be finite and > 0");
+        if ((d.flags & ~(OKENV_VIEW_DRAW_AGENT | OKENV_VIEW_DRAW_HEADING | OKENV_VIEW_HEADING_UP)) != 0U)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: unknown flag");
+        const std::vector<OkRenderTri> list =
+            okRenderDrawList(left_inner_xy, left_outer_xy, right_inner_xy, right_outer_xy, num_points);
+        float cell = kRenderCell;
+        if (const char *e = std::getenv("OKENV_RENDER_CELL"))
+            cell = static_cast<float>(std::atof(e));
+        OkRenderGeom g;
+        if (!okRenderBuildGrid(list, cell, g))
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_create: non-finite boundary coordinate");
+        OK_HIP(h, hipSetDevice(h->device));
+        // the buffers of an earlier setup go: nothing on the stream may still read them
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        for (void *old : {static_cast<void *>(h->d_render_tris), static_cast<void *>(h->d_render_start)})
+        {
+            if (!old)
+                continue;
+            h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), old), h->allocations.end());
+            OK_HIP(h, hipFree(old));
+        }
+        h->render_ok      = false;
+        h->d_render_tris  = nullptr;
+        h->d_render_start = nullptr;
+        int rc;
+        if ((rc = devAlloc(h, &h->d_render_tris, g.cell_tris.size())) || (rc = devAlloc(h, &h->d_render_start, g.cell_start.size())))
+            return rc;
+        if (!g.cell_tris.empty())
+            OK_HIP(h, hipMemcpyAsync(h->d_render_tris, g.cell_tris.data(), sizeof(OkRenderTri) * g.cell_tris.size(), hipMemcpyHostToDevice,
+                                     h->stream));
+        OK_HIP(h, hipMemcpyAsync(h->d_render_start, g.cell_start.data(), sizeof(uint32_t) * g.cell_start.size(), hipMemcpyHostToDevice,
+                                 h->stream));
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        h->render_refs = g.cell_tris.size();
+        g.cell_tris    = {};
+        g.cell_start   = {};
+        h->render_geom = std::move(g);
+        h->render_desc = d;
+        h->render_ok   = true;
+        return OKENV_OK;
+    }
+
+    int okenv_render_get_info(okenv_t h, okenv_render_info *out)
+    {
+        OK_QUIESCE(h);
+        if (!h || !out)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_get_info: NULL argument");
+        if (!h->render_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_render_get_info: call okenv_render_create first");
+        const okenv_view_desc &d = h->render_desc;
+        const OkRenderGeom    &g = h->render_geom;
+        out->triangles      = g.triangles;
+        out->grid_nx        = g.nx;
+        out->grid_ny        = g.ny;
+        out->grid_cell      = g.cell;
+        out->registrations  = static_cast<int32_t>(h->render_refs);
+        out->solid_cells    = 0;
+        out->width          = d.width;
+        out->height         = d.height;
+        out->samples        = d.samples;
+        out->channels       = d.format == OKENV_VIEW_RGBA8 ? 4 : 1;
+        out->bytes_per_call = static_cast<uint64_t>(h->N) * static_cast<uint64_t>(d.width) * static_cast<uint64_t>(d.height) *
+                              static_cast<uint64_t>(out->channels);
+        return OKENV_OK;
+    }
+
+    int okenv_render_views(okenv_t h, void *dst, uint64_t dst_bytes)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_views: NULL handle");
+        if (!h->render_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_render_views: call okenv_render_create first");
+        const okenv_view_desc &d  = h->render_desc;
+        const uint64_t         C  = d.format == OKENV_VIEW_RGBA8 ? 4U : 1U;
+        const uint64_t         hw = static_cast<uint64_t>(d.width) * static_cast<uint64_t>(d.height);
+        if (!dst || dst_bytes < static_cast<uint64_t>(h->N) * hw * C)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_views: dst is NULL or smaller than N * H * W * C bytes");
+        OK_HIP(h, hipSetDevice(h->device));
+        hipPointerAttribute_t attr{};
+        const hipError_t      pe = hipPointerGetAttributes(&attr, dst);
+        if (pe != hipSuccess)
+            (void)hipGetLastError(); // an unknown (host) pointer: clear the sticky error before the launch checks for one
+        if (pe != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged) || attr.device != h->device)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_views: dst must be device memory of the handle's device");
+        const OkRenderGeom &g = h->render_geom;
+        OkRenderParams      p{};
+        p.pos_x      = h->st.pos_x;
+        p.pos_y      = h->st.pos_y;
+        p.rot        = h->st.rot;
+        p.crashed    = h->st.crashed;
+        p.tris       = h->d_render_tris;
+        p.cell_start = h->d_render_start;
+        p.dst        = static_cast<uint8_t *>(dst);
+        p.x0         = g.x0;
+        p.y0         = g.y0;
+        p.inv_cell   = g.inv_cell;
+        p.fnx        = static_cast<float>(g.nx);
+        p.fny        = static_cast<float>(g.ny);
+        p.nx         = g.nx;
+        p.W          = static_cast<uint32_t>(d.width);
+        p.hw         = static_cast<uint32_t>(hw);
+        p.step_x     = d.view_w / static_cast<float>(d.width * d.samples);
+        p.step_y     = d.view_h / static_cast<float>(d.height * d.samples);
+        p.half_x     = d.view_w * 0.5F;
+        p.half_y     = d.view_h * 0.5F;
+        p.r2         = d.radius * d.radius;
+        p.flags      = d.flags;
+        p.agent_rgb  = d.agent_rgb[0] | static_cast<uint32_t>(d.agent_rgb[1]) << 8 | static_cast<uint32_t>(d.agent_rgb[2]) << 16;
+        const uint32_t pix_per_block = kRenderThreads * (d.format == OKENV_VIEW_RGBA8 ? 4U : 16U);
+        p.chunks                     = static_cast<uint32_t>((hw + pix_per_block - 1U) / pix_per_block);
+        if (static_cast<uint64_t>(h->N) * p.chunks > 0x7FFFFFFFULL)
+            return fail(h, OKENV_ERR_INVALID, "okenv_render_views: too many workgroups for one launch (N * H * W too large)");
+        const dim3 grid(static_cast<uint32_t>(h->N) * p.chunks), block(kRenderThreads);
+        const bool up = (d.flags & OKENV_VIEW_HEADING_UP) != 0U;
+#define OK_RENDER_LAUNCH(F, S)                                                                                                 \
+    do                                                                                                                         \
+    {                                                                                                                          \
+        if (up)                                                                                                                \
+            hipLaunchKernelGGL((okRenderViewsKernel<F, S, true>), grid, block, 0, h->stream, p);                               \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((okRenderViewsKernel<F, S, false>), grid, block, 0, h->stream, p);                              \
+    } while (0)
+        if (d.format == OKENV_VIEW_CLASS8)
+            OK_RENDER_LAUNCH(kRenderClass, 1);
+        else if (d.samples == 1)
+            OK_RENDER_LAUNCH(kRenderRgba, 1);
+        else if (d.samples == 2)
+            OK_RENDER_LAUNCH(kRenderRgba, 2);
+        else
+            OK_RENDER_LAUNCH(kRenderRgba, 4);
+#undef OK_RENDER_LAUNCH
+        OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
 

@@ -71,6 +71,22 @@ class Track:
         finally:
             L.okenv_track_free(h)
 
+    def band_triangles(self):
+        """The draw list of the track bands (okenv_track_band_triangles, host only): (xy [6P, 3, 2] float32 in DrawTriangle's vertex
+        order, draw ordinal [6P] uint8)."""
+        L = capi.load()
+        h = C.c_void_p()
+        capi.check(L.okenv_track_load(C.byref(h), self.path.encode()))
+        try:
+            n = L.okenv_track_band_triangles(h, None, None, 0)
+            if n < 0:
+                capi.check(n)
+            xy, ordinal = np.zeros((n, 3, 2), dtype=np.float32), np.zeros(n, dtype=np.uint8)
+            assert L.okenv_track_band_triangles(h, capi.ptr(xy), capi.ptr(ordinal), n) == n
+        finally:
+            L.okenv_track_free(h)
+        return xy, ordinal
+
 
 class BatchedEnvironment:
     """N agents x R rays on one GPU.  State lives on the device; see include/okenv.h for field semantics."""
@@ -385,6 +401,32 @@ class BatchedEnvironment:
 
     def q_share_knowledge(self):
         capi.check(self._L.okenv_q_share_knowledge(self._h), self._h)
+
+    # ---- bird's-eye camera views (include/okenv.h) ------------------------------------------------
+    def render_create(self, track, width=96, height=96, samples=1, fmt=capi.VIEW_RGBA8,
+                      flags=capi.VIEW_DRAW_AGENT | capi.VIEW_DRAW_HEADING, view=None, radius=9.0, agent_rgb=(80, 80, 80)):
+        """Set up okenv_render_views for the bands of `track` (a Track): every agent's view, width x height pixels of
+        samples x samples samples each, over `view` = (view_w, view_h) world px (default: the reference's follow camera)."""
+        d = capi.OkenvViewDesc()
+        d.width, d.height, d.samples, d.format, d.flags = int(width), int(height), int(samples), int(fmt), int(flags)
+        d.view_w, d.view_h = (capi.VIEW_FOLLOW_W, capi.VIEW_FOLLOW_H) if view is None else (float(view[0]), float(view[1]))
+        d.radius = float(radius)
+        d.agent_rgb[:] = [int(c) for c in agent_rgb]
+        bounds = [np.ascontiguousarray(b, dtype=np.float32) for b in (track.li, track.lo, track.ri, track.ro)]
+        capi.check(self._L.okenv_render_create(self._h, *(capi.ptr(b) for b in bounds), bounds[0].size // 2, C.byref(d)), self._h)
+        self.render_shape = (self.N, int(height), int(width)) + ((4,) if fmt == capi.VIEW_RGBA8 else ())
+
+    def render_views(self, dst):
+        """Every agent's view into the device tensor `dst` (contiguous uint8, >= N*H*W*C bytes), enqueued on the handle's
+        stream without a synchronisation."""
+        assert dst.is_contiguous()
+        capi.check(self._L.okenv_render_views(self._h, C.c_void_p(dst.data_ptr()), dst.numel() * dst.element_size()), self._h)
+        return dst
+
+    def render_info(self):
+        i = capi.OkenvRenderInfo()
+        capi.check(self._L.okenv_render_get_info(self._h, C.byref(i)), self._h)
+        return {k: getattr(i, k) for k, _ in capi.OkenvRenderInfo._fields_}
 
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):

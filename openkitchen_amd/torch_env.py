@@ -52,7 +52,8 @@ class VectorEnvironment:
     def __init__(self, race_track_path, num_envs, num_rays=15, ray_angles_deg=None, device=0,
                  movement_mode=capi.MODE_VELOCITY, auto_reset=True, pick_random_point=True, randomize_lane=False,
                  randomize_heading=False, seed=0, agent_base=0, reward=None, draw_rays=False, hidden_window=True):
-        # draw_rays / hidden_window: accepted for signature compatibility; there is no window (rendering is out of scope)
+        # draw_rays / hidden_window: accepted for signature compatibility; there is no window (image observations come from
+        # enable_camera / camera: every agent's bird's-eye view rendered on the device)
         del draw_rays, hidden_window
         if not torch.cuda.is_available():
             raise capi.OkenvError(-3, "VectorEnvironment needs a GPU; there is no CPU path")
@@ -174,6 +175,28 @@ class VectorEnvironment:
             else:
                 self.env.tracker_update()  # re-placed agents restart their episode, the others take a normal step
         return self.distances, self.done
+
+    # ---- bird's-eye camera views (include/okenv.h) ---------------------------------------------------
+    def enable_camera(self, width=96, height=96, samples=1, fmt="rgba", heading_up=False, draw_agent=True, draw_heading=True,
+                      view=None):
+        """Sets up `camera()`: each agent's follow-camera frame of the track bands and its own disc, width x height pixels
+        (samples x samples box-filtered samples each), `view` = (view_w, view_h) world px, default the reference's follow
+        camera (1600 x 1400 at zoom 15).  fmt "rgba" gives [N, H, W, 4] uint8, "class" [N, H, W] band / agent classes."""
+        fmt_code = {"rgba": capi.VIEW_RGBA8, "class": capi.VIEW_CLASS8}[fmt]
+        flags = ((capi.VIEW_DRAW_AGENT if draw_agent else 0) | (capi.VIEW_DRAW_HEADING if draw_heading else 0) |
+                 (capi.VIEW_HEADING_UP if heading_up else 0))
+        self.env.render_create(self.track, width, height, samples, fmt_code, flags, view)
+        self.camera_shape = self.env.render_shape
+
+    def camera(self, out=None):
+        """Every agent's view of the current state, rendered by one kernel on the environment's stream (torch's current stream
+        unless use_stream chose another), without a synchronisation.
+        `out`: a contiguous uint8 tensor of camera_shape on this device to fill in place; otherwise a new tensor."""
+        if out is None:
+            out = torch.empty(self.camera_shape, dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != self.camera_shape or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("camera(out=...) needs a contiguous uint8 tensor of shape %s on %s" % (self.camera_shape, self.device))
+        return self.env.render_views(out)
 
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
