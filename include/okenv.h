@@ -233,6 +233,54 @@ OKENV_API int okenv_controller_act(okenv_t h, float throttle, float steering_sca
  * reward keeps counting for crashed agents, which an episode no longer steps).  hidden <= 4 x the handle's lanes per agent. */
 OKENV_API int okenv_rollout_controller(okenv_t h, int32_t n_steps, float throttle, float steering_scale);
 
+/* ---- expert drivers: FieldNavigators/ on the device -------------------
+ * PotFieldAgent::updateAction (FieldNavigators/PotentialFieldAgent.hpp:52-84) with DataCollectorAgent's steering clamp
+ * (FieldNavigators/collect_data/collect_data_random.cpp:59-65), or VFHAgent::updateAction (FieldNavigators/VFHAgent.hpp:53-123), for
+ * every agent, towards the goal point of their callers: nearest centre-line index of the agent's position + lookahead, wrapped
+ * modulo P (FieldNavigators/main.cpp:20-25) or clamped to P - 1 (collect_data_random.cpp:108-120).  The rule is restated in
+ * include/okenv_math.h (ok_potfield_action, ok_vfh_action; the two spots where the reference is undefined are written there). */
+#define OKENV_EXPERT_POTFIELD 0
+#define OKENV_EXPERT_VFH 1
+
+typedef struct okenv_expert_params {
+    int32_t kind;          /* OKENV_EXPERT_POTFIELD | OKENV_EXPERT_VFH                                                    */
+    int32_t lookahead;     /* kLookAheadIdx (PotentialFieldAgent.hpp:22, VFHAgent.hpp:21: 2), >= 0                        */
+    int32_t goal_wrap;     /* != 0: (nearest + lookahead) % P (main.cpp:23); 0: min(nearest + lookahead, P - 1)           */
+    float   k_att;         /* kAttractiveConstant  (PotentialFieldAgent.hpp:23: 100)                                      */
+    float   k_rep;         /* kRepulsiveConstant   (:24: 10)                                                              */
+    float   effect_range;  /* kObstacleEffectRange (:25: 5)                                                               */
+    float   clamp_deg;     /* kSteeringAngleClampDeg (collect_data_random.cpp:45: 10); <= 0: no clamp (PotFieldAgent)     */
+    float   vfh_throttle;  /* VFHAgent.hpp:120: 100                                                                       */
+    int32_t vfh_threshold; /* kObstacleDistThreshold (VFHAgent.hpp:20: 1): a sector is occupied when count > threshold    */
+} okenv_expert_params;
+
+/* Where okenv_expert_act leaves this step's sample, besides the action fields: device pointers of the handle's device, each may
+ * be NULL (skipped).  The observation is the one the action was computed from (what saveMeasurement writes,
+ * collect_data_random.cpp:67-100). */
+typedef struct okenv_expert_record {
+    float   *action; /* [N][2]    throttle_delta, steering_delta                      */
+    float   *dist;   /* [N][R]    OKENV_F_DIST                                         */
+    float   *rel_xy; /* [N][R][2] OKENV_F_REL_X, OKENV_F_REL_Y interleaved             */
+    uint8_t *alive;  /* [N]       !crashed_                                           */
+} okenv_expert_record;
+
+/* Attaches an expert to the handle (replaces an earlier one): validates, computes the per-ray cos / sin table in fp64 on the host
+ * and uploads it.  Any fan for the potential field; 2 <= R <= 64 for VFH (num_sectors_ = R, fov_ = |last - first|).
+ * OKENV_ERR_STATE without okenv_set_centerline; OKENV_ERR_INVALID for a NULL params pointer, an unknown kind, lookahead < 0 or
+ * a VFH fan outside 2 .. 64 rays.  Synchronises. */
+OKENV_API int okenv_expert_create(okenv_t h, const okenv_expert_params *params);
+/* updateAction for every agent, crashed ones included (FieldNavigators/main.cpp:78-84 asks every agent): reads pos_, rot_ and the
+ * last step's distances, writes OKENV_F_THROTTLE / OKENV_F_STEER and, when `rec` is given, the record slots.  One kernel on the
+ * handle's stream, no synchronisation, no allocation: it can be captured into a HIP graph next to okenv_step (the contract of
+ * okenv_controller_act; like it, it ends a running episode without the end-of-episode corrections).  OKENV_ERR_STATE before
+ * okenv_expert_create or without a centre line. */
+OKENV_API int okenv_expert_act(okenv_t h, const okenv_expert_record *rec);
+/* The same rule on host arrays, no GPU needed: n agents, ray fan [num_rays], dist [n][num_rays]; the goal points come from the
+ * centre line (cx, cy [num_points]) as above or, when goal_x / goal_y are not NULL, are given (cx / cy may then be NULL). */
+OKENV_API int okenv_expert_act_host(const okenv_expert_params *params, const float *ray_angles_deg, int32_t num_rays, const float *cx,
+                                    const float *cy, int32_t num_points, int32_t n, const float *pos_x, const float *pos_y, const float *rot_deg,
+                                    const float *dist, const float *goal_x, const float *goal_y, float *throttle, float *steer);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.
@@ -503,6 +551,9 @@ OKENV_API int okenv_work_stats_split(okenv_t h, uint64_t out[8]);
 
 /* ---- device self-checks used by the parity tests --------------------------------------------------- */
 
+/* ok_atan2f (include/okenv_math.h) and the experts' bounded normalizeAngleDeg on host arrays; host only, no GPU. */
+OKENV_API int okenv_debug_atan2f(const float *y, const float *x, float *out, int32_t n);
+OKENV_API int okenv_debug_expert_normalize_angle(const float *angle_deg, float *out, int32_t n);
 /* ok_sincosf evaluated on the GPU (n values, host pointers). */
 OKENV_API int okenv_debug_sincos(int32_t device, const float *x, float *s, float *c, int32_t n);
 /* First-hit parameter t for n arbitrary rays (origin, angle [rad]) through the handle's grid (host pointers). */

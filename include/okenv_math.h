@@ -252,6 +252,161 @@ OK_HD float ok_normalize_angle_deg(float angle)
     return angle;
 }
 
+/* ---- FieldNavigators: the two expert drivers ------------------------------
+ * PotFieldAgent::updateAction (FieldNavigators/PotentialFieldAgent.hpp:52-84), DataCollectorAgent::updateAction
+ * (FieldNavigators/collect_data/collect_data_random.cpp:59-65), VFHAgent::updateHistograms / findBestSector / updateAction
+ * (FieldNavigators/VFHAgent.hpp:53-123) and the goal point of their callers (FieldNavigators/main.cpp:20-25,
+ * collect_data_random.cpp:108-120), restated operation by operation in the reference's precisions.  One source for the device
+ * kernel (csrc/ok_expert.h) and for okenv_expert_act_host, so the two agree bit for bit; against the reference itself the only
+ * licensed difference is the last bit of atan2f (ok_atan2f below is ours, glibc's is not pinned).
+ *
+ * Two places where the reference is undefined or degenerate are restated, not "fixed":
+ *  1. findBestSector indexes binary_histogram_[(goal_sector + i) % num_sectors_] (VFHAgent.hpp:84-88) with a NEGATIVE
+ *     goal_sector whenever the goal lies more than 90 deg + one sector to the right: C's remainder is then negative and the
+ *     reference reads out of bounds.  Here the index (and the sector returned from it) is the non-negative remainder.
+ *  2. With kObstacleDistThreshold = 1 and one ray per sector, `count > threshold` marks a sector occupied only where the fp32
+ *     sector index (i / (float)R) * (float)num_sectors, truncated, puts two rays into one sector (it is not always i).  The
+ *     threshold is therefore a parameter; 1 is the reference.
+ * normalizeAngleDeg (Environment/Utils.h:3-14) spins for ever on an infinite rot_; here both loops are capped (below).
+ */
+
+/* atan2f for the experts, evaluated in fp64 with IEEE operations and explicit FMAs only and rounded once to fp32: same bits on
+ * host and device (the idea of ok_sincosf / ok_tanhf).  a = min(|x|,|y|) / max(|x|,|y|) in [0, 1]; above tan(pi/8) one
+ * reduction t = (a - 1) / (a + 1), atan a = pi/4 + atan t, so |t| <= 0.4143; atan t = t + t z A(z), z = t^2, A of degree 9
+ * (interpolant at the Chebyshev nodes of [0, 0.4143^2], tools/fit_math.py: relative error 2^-52.7); then the octant is undone:
+ * pi/2 - r where |y| > |x|, pi - r where x is negative (sign bit: -0 counts), the sign of y last.  Zeros, infinities and NaN
+ * follow C99 F.9.1.4.  tests/test_expert_rule.py: <= 1 ulp from the rounded fp64 arctan2 and from glibc's atan2f. */
+OK_HD float ok_atan2f(const float y, const float x)
+{
+    const double ay = __builtin_fabs((double)y), ax = __builtin_fabs((double)x);
+    if (!(ay == ay) || !(ax == ax)) return x + y; /* NaN in, NaN out */
+    const int swap = ay > ax;
+    const double hi = swap ? ay : ax, lo = swap ? ax : ay;
+    double r;
+    if (hi == 0.0) {
+        r = 0.0; /* atan2(+-0, +-0) */
+    } else {
+        const double a = (lo == hi) ? 1.0 : lo / hi; /* (inf / inf: the diagonal) */
+        const int fold = a > 0x1.a827999fcef32p-2;   /* tan(pi/8) = 0.41421356237309503 */
+        const double t = fold ? (a - 1.0) / (a + 1.0) : a;
+        const double z = t * t;
+        double p = ok_konst(0x1.74a2d785d5a9fp-6);             /*  0.022743902656055522 */
+        p = OK_FMA(p, z, ok_konst(-0x1.6f3c3017cb4e7p-5));     /* -0.04482850449708469  */
+        p = OK_FMA(p, z, ok_konst(0x1.d5e885b7ee229p-5));      /*  0.05736185185327642  */
+        p = OK_FMA(p, z, ok_konst(-0x1.105e007ccd67cp-4));     /* -0.06649589720185561  */
+        p = OK_FMA(p, z, ok_konst(0x1.3b0688e46275ap-4));      /*  0.07691052888381247  */
+        p = OK_FMA(p, z, ok_konst(-0x1.745c7f2dc5c2dp-4));     /* -0.09090852431505488  */
+        p = OK_FMA(p, z, ok_konst(0x1.c71c6dcf1e479p-4));      /*  0.11111109632646955  */
+        p = OK_FMA(p, z, ok_konst(-0x1.2492491dcf6e7p-3));     /* -0.1428571426603675   */
+        p = OK_FMA(p, z, ok_konst(0x1.9999999990a20p-3));      /*  0.19999999999898055  */
+        p = OK_FMA(p, z, ok_konst(-0x1.5555555555546p-2));     /* -0.3333333333333325   */
+        r = OK_FMA(t * z, p, t);
+        if (fold) r = ok_konst(0x1.921fb54442d18p-1) + r;      /* pi/4 */
+    }
+    if (swap) r = ok_konst(0x1.921fb54442d18p+0) - r;          /* pi/2 */
+    if (__builtin_signbit(x)) r = ok_konst(0x1.921fb54442d18p+1) - r; /* pi */
+    return (float)(__builtin_signbit(y) ? -r : r);
+}
+
+/* normalizeAngleDeg (Environment/Utils.h:3-14) for the experts: the two loops of repeated += 360 / -= 360 in fp32 (the rounding of
+ * the repeated additions is part of the result), each capped at OK_EXPERT_NORM_TURNS turns -- 4096 turns cover |angle| up to
+ * 1.47 million degrees, where the reference's loops and these agree bit for bit.  Beyond that, and for infinities and NaN (where the
+ * reference would spin for ever or return NaN), the result is DEFINED as 0: a wave never waits on an absurd rot_. */
+#define OK_EXPERT_NORM_TURNS 4096
+OK_HD float ok_expert_normalize_angle_deg(float angle)
+{
+    for (int i = 0; i < OK_EXPERT_NORM_TURNS && angle < 360.0f; ++i) angle += 360.0f;
+    for (int i = 0; i < OK_EXPERT_NORM_TURNS && angle >= 360.0f; ++i) angle -= 360.0f;
+    return (angle >= 0.0f && angle < 360.0f) ? angle : 0.0f;
+}
+
+/* Index of the goal point: nearest centre-line index + lookahead, wrapped modulo P (main.cpp:23) or clamped to P - 1
+ * (collect_data_random.cpp:111-112). */
+OK_HD int ok_expert_goal_index(const int nearest, const int lookahead, const int P, const int wrap)
+{
+    const long g = (long)nearest + (long)lookahead;
+    return wrap ? (int)(g % (long)P) : (int)(g < (long)P - 1 ? g : (long)P - 1);
+}
+
+/* PotFieldAgent::updateAction followed by DataCollectorAgent's clamp (off when clamp_deg <= 0).  dist[i] = sensor_hits_[i].norm();
+ * ray_cos / ray_sin [R]: cos / sin (angle_i * M_PI / 180.f) in fp64, made once on the host (they depend on the fan only). */
+OK_HD void ok_potfield_action(const float px, const float py, const float rot, const float gx, const float gy, const float *dist,
+                              const double *ray_cos, const double *ray_sin, const int R, const float k_att, const float k_rep,
+                              const float effect_range, const float clamp_deg, float *throttle, float *steer)
+{
+    float ax = gx - px, ay = gy - py; /* :54 */
+    const float distance_to_goal = __builtin_sqrtf(ax * ax + ay * ay);
+    ax = ax / distance_to_goal * k_att; /* :57: Vec2d / float, then Vec2d * float */
+    ay = ay / distance_to_goal * k_att;
+    float rx = 0.0f, ry = 0.0f;
+    for (int i = 0; i < R; ++i) { /* :60-73, ascending ray order */
+        const float n = dist[i];
+        if (n < effect_range) {
+            const float mag = k_rep * (1.0f / n - 1.0f / effect_range);
+            rx = (float)((double)rx + ray_cos[i] * (double)mag); /* float += double * float */
+            ry = (float)((double)ry + ray_sin[i] * (double)mag);
+        }
+    }
+    const float tx = ax - rx, ty = ay - ry; /* :75 */
+    /* :78  atan2(float, float) is the fp32 overload; * 180.F in fp32; / M_PI in fp64 */
+    const double goal_rotation = (double)(ok_atan2f(ty, tx) * 180.0f) / 3.14159265358979323846;
+    const float len = __builtin_sqrtf(tx * tx + ty * ty);
+    *throttle = len < 100.0f ? len : 100.0f; /* std::min(length, 100.F): NaN stays NaN */
+    float s = (float)(goal_rotation - (double)rot); /* :81 */
+    s = ok_expert_normalize_angle_deg(s);
+    if (s > 180.0f) s -= 360.0f;
+    if (clamp_deg > 0.0f) s = s < -clamp_deg ? -clamp_deg : (clamp_deg < s ? clamp_deg : s); /* std::clamp */
+    *steer = s;
+}
+
+/* VFHAgent::updateAction.  first / last: sensor_ray_angles_.front() / .back(); num_sectors_ = R, fov_ = |last - first|,
+ * sector_width_ = fov_ / num_sectors_ as in the constructor (VFHAgent.hpp:40-44).  2 <= R <= OK_VFH_MAX_RAYS: the occupancy of the
+ * sectors is one 64-bit word (the fp32 sector index is non-decreasing in i, so the rays of a sector are consecutive). */
+#define OK_VFH_MAX_RAYS 64
+OK_HD void ok_vfh_action(const float px, const float py, const float rot, const float gx, const float gy, const float *dist, const int R,
+                         const float first, const float last, const int threshold, const float vfh_throttle, float *throttle, float *steer)
+{
+    const int ns = R;
+    const float fov = __builtin_fabsf(last - first);
+    const float sector_width = fov / (float)ns;
+    /* updateHistograms (:53-72) */
+    uint64_t occupied = 0u;
+    int cur = -1, count = 0;
+    for (int i = 0; i < R; ++i) {
+        if (dist[i] < OK_SENSOR_RANGE) {
+            const int sector = (int)(((float)i / (float)R) * (float)ns);
+            if (sector != cur) {
+                if (cur >= 0 && count > threshold) occupied |= (uint64_t)1 << cur;
+                cur = sector;
+                count = 0;
+            }
+            ++count;
+        }
+    }
+    if (cur >= 0 && count > threshold) occupied |= (uint64_t)1 << cur;
+    /* updateAction (:97-110): atan2f, / M_PI and * 180.f in fp64, narrowed */
+    const float world = (float)((double)ok_atan2f(gy - py, gx - px) / 3.14159265358979323846 * (double)180.0f);
+    float a = world - rot;
+    a = (float)__builtin_fmod((double)a, 360.0); /* exact, so the same in either precision */
+    if (a > 180.0f) a -= 360.0f;
+    else if (a <= -180.0f) a += 360.0f;
+    /* findBestSector (:74-93) */
+    const float gs_f = (a - first) / fov * (float)ns;
+    /* the cast of a value outside int's range (or NaN) is undefined in the reference: 0 here */
+    const int goal_sector = (gs_f > -2147483000.0f && gs_f < 2147483000.0f) ? (int)gs_f : 0;
+    int best = goal_sector; /* fallback :92 */
+    for (int i = 0; i < ns; ++i) {
+        int s = (int)(((long)goal_sector + i) % ns);
+        if (s < 0) s += ns; /* undefined spot 1: the non-negative remainder */
+        if (!((occupied >> s) & 1u)) { best = s; break; }
+        s = (int)(((long)goal_sector - i + ns) % ns);
+        if (s < 0) s += ns;
+        if (!((occupied >> s) & 1u)) { best = s; break; }
+    }
+    *throttle = vfh_throttle;
+    *steer = sector_width * (float)best + first; /* :115 */
+}
+
 /* tanh for the CMA-ES controller (CovarianceMatrixAdaptationEvolution/Controller.cpp:16-23), evaluated in fp64 with IEEE operations
  * and explicit FMAs only (no library call), so that the device and the CPU oracle produce the same bits -- the same idea as
  * ok_sincosf.  tanh|x| = (1 - e) / (1 + e), e = exp(-2|x|) = 2^n (1 + m), n = rint(-2|x| / ln 2), m = expm1(r), |r| <= ln 2 / 2,

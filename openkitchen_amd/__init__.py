@@ -7,6 +7,8 @@ in its place.
 """
 from . import _capi as capi  # noqa: F401
 from .buildlib import build  # noqa: F401
-from .env import BatchedEnvironment, Track, debug_sincos, default_ray_fan, track_path  # noqa: F401
+from .env import (BatchedEnvironment, Track, debug_atan2f, debug_expert_normalize_angle, debug_sincos, default_ray_fan,  # noqa: F401
+                  expert_act_host, track_path)
 
-__all__ = ["BatchedEnvironment", "Track", "build", "capi", "debug_sincos", "default_ray_fan", "track_path"]
+__all__ = ["BatchedEnvironment", "Track", "build", "capi", "debug_atan2f", "debug_expert_normalize_angle", "debug_sincos",
+           "default_ray_fan", "expert_act_host", "track_path"]

@@ -32,6 +32,9 @@ REWARD_STEP, REWARD_PROGRESS = 0, 1
 VIEW_RGBA8, VIEW_CLASS8 = 0, 1
 VIEW_DRAW_AGENT, VIEW_DRAW_HEADING, VIEW_HEADING_UP = 1, 2, 4
 VIEW_FOLLOW_W, VIEW_FOLLOW_H = 1600.0 / 15.0, 1400.0 / 15.0  # as fp32 these equal OKENV_VIEW_FOLLOW_W / _H
+# expert drivers (include/okenv.h)
+EXPERT_POTFIELD, EXPERT_VFH = 0, 1
+EXPERT_KINDS = {"potfield": EXPERT_POTFIELD, "vfh": EXPERT_VFH}
 
 # every symbol include/okenv.h declares (tests/test_capi_symbols.py checks the library exports them all)
 SYMBOLS = [
@@ -53,6 +56,7 @@ SYMBOLS = [
     "okenv_episode_begin", "okenv_episode_compact", "okenv_episode_end", "okenv_episode_tail_limit", "okenv_work_stats",
     "okenv_ga_scores_device", "okenv_get_stream", "okenv_off_grid_count", "okenv_work_stats_split", "okenv_debug_step_forms",
     "okenv_render_create", "okenv_render_views", "okenv_render_get_info", "okenv_track_band_triangles",
+    "okenv_expert_create", "okenv_expert_act", "okenv_expert_act_host", "okenv_debug_atan2f", "okenv_debug_expert_normalize_angle",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -82,6 +86,23 @@ class OkenvRenderInfo(C.Structure):
     _fields_ = [("triangles", C.c_int32), ("grid_nx", C.c_int32), ("grid_ny", C.c_int32), ("grid_cell", C.c_float),
                 ("registrations", C.c_int32), ("solid_cells", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("samples", C.c_int32), ("channels", C.c_int32), ("bytes_per_call", C.c_uint64)]
+
+
+class OkenvExpertParams(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("lookahead", C.c_int32), ("goal_wrap", C.c_int32), ("k_att", C.c_float), ("k_rep", C.c_float),
+                ("effect_range", C.c_float), ("clamp_deg", C.c_float), ("vfh_throttle", C.c_float), ("vfh_threshold", C.c_int32)]
+
+
+class OkenvExpertRecord(C.Structure):
+    _fields_ = [("action", C.c_void_p), ("dist", C.c_void_p), ("rel_xy", C.c_void_p), ("alive", C.c_void_p)]
+
+
+def expert_params(kind, lookahead=2, goal_wrap=False, k_att=100.0, k_rep=10.0, effect_range=5.0, clamp_deg=0.0, vfh_throttle=100.0,
+                  vfh_threshold=1):
+    """okenv_expert_params with the reference's constants as defaults (PotentialFieldAgent.hpp:22-25, VFHAgent.hpp:20-21);
+    kind: "potfield" / "vfh" or the integer."""
+    k = EXPERT_KINDS[kind] if isinstance(kind, str) else int(kind)
+    return OkenvExpertParams(k, int(lookahead), 1 if goal_wrap else 0, k_att, k_rep, effect_range, clamp_deg, vfh_throttle, int(vfh_threshold))
 
 
 class OkenvError(RuntimeError):
@@ -198,6 +219,11 @@ def load(build_if_missing=True):
     L.okenv_render_views.argtypes = [vp, vp, C.c_uint64]
     L.okenv_render_get_info.argtypes = [vp, C.POINTER(OkenvRenderInfo)]
     L.okenv_track_band_triangles.argtypes = [vp, vp, vp, i32]
+    L.okenv_expert_create.argtypes = [vp, C.POINTER(OkenvExpertParams)]
+    L.okenv_expert_act.argtypes = [vp, C.POINTER(OkenvExpertRecord)]
+    L.okenv_expert_act_host.argtypes = [C.POINTER(OkenvExpertParams), vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.okenv_debug_atan2f.argtypes = [vp, vp, vp, i32]
+    L.okenv_debug_expert_normalize_angle.argtypes = [vp, vp, i32]
     _lib = L
     return L
 

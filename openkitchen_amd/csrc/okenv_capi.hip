@@ -22,6 +22,7 @@
 #include "ok_grid.h"
 #include "ok_render.h"
 #include "okenv_kernels.h"
+#include "ok_expert.h"
 
 namespace
 {
@@ -159,6 +160,10 @@ struct okenv
     size_t          render_refs{0};
     OkRenderTri    *d_render_tris{nullptr};
     uint32_t       *d_render_start{nullptr};
+    // expert drivers (okenv_expert_create): parameters and the per-ray cos / sin table [cos R | sin R]
+    bool                expert_ok{false};
+    okenv_expert_params expert{};
+    double             *d_expert_tab{nullptr};
 };
 
 struct okenv_track
@@ -2041,6 +2046,98 @@ extern "C"
             hipLaunchKernelGGL(okControllerKernel<64>, dim3(blocks), dim3(256), 0, h->stream, h->st, h->d_ctrl_params, h->ctrl_num_params, h->N,
                                h->R, h->ctrl_hidden, throttle, steering_scale);
         OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    // ---- expert drivers (FieldNavigators/) ---------------------------------------------------------------------------------
+
+    int okenv_expert_create(okenv_t h, const okenv_expert_params *params)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_expert_create: NULL handle");
+        if (const char *why = okExpertCheckParams(params, h->R))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_expert_create: ") + why);
+        if (h->P <= 0)
+            return fail(h, OKENV_ERR_STATE, "okenv_expert_create: call okenv_set_centerline first");
+        OK_HIP(h, hipSetDevice(h->device));
+        int rc = devEnsure(h, &h->d_expert_tab, 2U * static_cast<size_t>(h->R));
+        if (rc != OKENV_OK || (rc = buildCenterlineBuckets(h)) != OKENV_OK)
+            return rc;
+        std::vector<double> c, s;
+        okExpertRayTables(h->host_ray_deg.data(), h->R, c, s);
+        OK_HIP(h, hipMemcpyAsync(h->d_expert_tab, c.data(), 8U * static_cast<size_t>(h->R), hipMemcpyHostToDevice, h->stream));
+        OK_HIP(h, hipMemcpyAsync(h->d_expert_tab + h->R, s.data(), 8U * static_cast<size_t>(h->R), hipMemcpyHostToDevice, h->stream));
+        OK_HIP(h, hipStreamSynchronize(h->stream)); // the tables are locals
+        h->expert    = *params;
+        h->expert_ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_expert_act(okenv_t h, const okenv_expert_record *rec)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_expert_act: NULL handle");
+        if (!h->expert_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_expert_act: call okenv_expert_create first");
+        if (h->P <= 0)
+            return fail(h, OKENV_ERR_STATE, "okenv_expert_act: call okenv_set_centerline first");
+        dropEpisode(h);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkExpertParams p{};
+        p.st       = h->st;
+        p.N        = h->N;
+        p.R        = h->R;
+        p.P        = h->P;
+        p.cx       = h->d_cx;
+        p.cy       = h->d_cy;
+        p.cl_start = h->cl_dirty ? nullptr : h->d_cl_start;
+        p.cl_idx   = h->cl_dirty ? nullptr : h->d_cl_idx;
+        p.geom     = h->grid.g;
+        p.ray_cos  = h->d_expert_tab;
+        p.ray_sin  = h->d_expert_tab + h->R;
+        p.first    = h->host_ray_deg.front();
+        p.last     = h->host_ray_deg.back();
+        p.ep       = h->expert;
+        if (rec != nullptr)
+            p.rec = *rec;
+        const unsigned blocks = static_cast<unsigned>((static_cast<long>(h->N) * kExpertLanes + 255) / 256);
+        hipLaunchKernelGGL(okExpertKernel, dim3(blocks), dim3(256), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_expert_act_host(const okenv_expert_params *params, const float *ray_angles_deg, int32_t num_rays, const float *cx, const float *cy,
+                              int32_t num_points, int32_t n, const float *pos_x, const float *pos_y, const float *rot_deg, const float *dist,
+                              const float *goal_x, const float *goal_y, float *throttle, float *steer)
+    {
+        if (!ray_angles_deg || num_rays <= 0 || n < 0 || !pos_x || !pos_y || !rot_deg || !dist || !throttle || !steer)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_expert_act_host: bad argument");
+        if (const char *why = okExpertCheckParams(params, num_rays))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_expert_act_host: ") + why);
+        const bool given = goal_x != nullptr || goal_y != nullptr;
+        if (given ? (!goal_x || !goal_y) : (!cx || !cy || num_points <= 0))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_expert_act_host: needs a centre line or both goal arrays");
+        okExpertActHost(*params, ray_angles_deg, num_rays, cx, cy, num_points, n, pos_x, pos_y, rot_deg, dist, goal_x, goal_y, throttle, steer);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_atan2f(const float *y, const float *x, float *out, int32_t n)
+    {
+        if (!y || !x || !out || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_atan2f: bad argument");
+        for (int32_t i = 0; i < n; ++i)
+            out[i] = ok_atan2f(y[i], x[i]);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_expert_normalize_angle(const float *angle_deg, float *out, int32_t n)
+    {
+        if (!angle_deg || !out || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_expert_normalize_angle: bad argument");
+        for (int32_t i = 0; i < n; ++i)
+            out[i] = ok_expert_normalize_angle_deg(angle_deg[i]);
         return OKENV_OK;
     }
 

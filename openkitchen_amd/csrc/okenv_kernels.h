@@ -941,7 +941,8 @@ struct OkQCarry
 // outside can beat or tie it and the result is the brute-force argmin (strict '<' per lane over ascending indices, (distance,
 // index) order across lanes: "lowest index wins").  Otherwise -- a position far from the track -- the lanes stride over the
 // whole centre line.
-__device__ __forceinline__ int okNearestBucketed(const OkStepParams &p, const float *lds_cx, const float *lds_cy, const uint16_t *lds_cstart,
+template <class ParamsT> // OkStepParams, or any struct with its cl_start / geom / P members (ok_expert.h)
+__device__ __forceinline__ int okNearestBucketed(const ParamsT &p, const float *lds_cx, const float *lds_cy, const uint16_t *lds_cstart,
                                                  const uint16_t *lds_cidx, const float px, const float py, const int r, const int G)
 {
     float best = 3.402823466e+38F;

@@ -428,6 +428,34 @@ class BatchedEnvironment:
         capi.check(self._L.okenv_render_get_info(self._h, C.byref(i)), self._h)
         return {k: getattr(i, k) for k, _ in capi.OkenvRenderInfo._fields_}
 
+    # ---- expert drivers (include/okenv.h) ---------------------------------------------------------
+    def expert_create(self, kind="potfield", **params):
+        """Attaches the reference's potential-field ("potfield") or vector-field-histogram ("vfh") driver to the handle;
+        params: the members of okenv_expert_params (capi.expert_params lists them with the reference's defaults)."""
+        ep = capi.expert_params(kind, **params)
+        capi.check(self._L.okenv_expert_create(self._h, C.byref(ep)), self._h)
+        return ep
+
+    def expert_act(self, record=None):
+        """updateAction for every agent, enqueued on the handle's stream without a synchronisation.  record: None, or a dict of
+        device tensors / addresses under "action" [N,2], "dist" [N,R], "rel_xy" [N,R,2] (float32) and "alive" [N] (uint8), each
+        optional, that receive this step's sample."""
+        if record is None:
+            capi.check(self._L.okenv_expert_act(self._h, None), self._h)
+            return
+        rec = capi.OkenvExpertRecord()
+        sizes = {"action": self.N * 8, "dist": self.N * self.R * 4, "rel_xy": self.N * self.R * 8, "alive": self.N}
+        for k, v in record.items():
+            if k not in sizes:
+                raise KeyError("unknown record slot %r" % k)
+            if v is None:
+                continue
+            if hasattr(v, "data_ptr"):
+                assert v.is_contiguous() and v.numel() * v.element_size() >= sizes[k], "record slot %r is too small" % k
+                v = v.data_ptr()
+            setattr(rec, k, int(v))
+        capi.check(self._L.okenv_expert_act(self._h, C.byref(rec)), self._h)
+
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):
         """{rays, tests, cells, points} the broad phase leaves for the current poses (okenv_work_stats)."""
@@ -477,3 +505,41 @@ def debug_sincos(x, device=0):
     s, c = np.zeros_like(x), np.zeros_like(x)
     capi.check(capi.load().okenv_debug_sincos(int(device), capi.ptr(x), capi.ptr(s), capi.ptr(c), x.size))
     return s, c
+
+
+def expert_act_host(params, ray_angles_deg, pos_x, pos_y, rot, dist, centerline=None, goals=None):
+    """The experts' rule on host arrays, no GPU needed (okenv_expert_act_host): returns (throttle, steer) for n agents.  params:
+    capi.expert_params(...); dist [n, R]; centerline = (x, y) of the track's centre line, or goals = (x, y) per agent."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+    fan, pos_x, pos_y, rot, dist = f(ray_angles_deg), f(pos_x), f(pos_y), f(rot), f(dist)
+    n = pos_x.size
+    assert dist.size == n * fan.size and pos_y.size == n and rot.size == n
+    cx = cy = gx = gy = None
+    P = 0
+    if goals is not None:
+        gx, gy = f(goals[0]), f(goals[1])
+        assert gx.size == n and gy.size == n
+    if centerline is not None:
+        cx, cy = f(centerline[0]), f(centerline[1])
+        P = cx.size
+    thr, steer = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    capi.check(capi.load().okenv_expert_act_host(C.byref(params) if params is not None else None, capi.ptr(fan), fan.size, capi.ptr(cx),
+                                                 capi.ptr(cy), P, n, capi.ptr(pos_x), capi.ptr(pos_y), capi.ptr(rot), capi.ptr(dist), capi.ptr(gx),
+                                                 capi.ptr(gy), capi.ptr(thr), capi.ptr(steer)))
+    return thr, steer
+
+
+def debug_atan2f(y, x):
+    """ok_atan2f of include/okenv_math.h on host arrays (no GPU)."""
+    y, x = np.ascontiguousarray(y, dtype=np.float32), np.ascontiguousarray(x, dtype=np.float32)
+    out = np.zeros_like(y)
+    capi.check(capi.load().okenv_debug_atan2f(capi.ptr(y), capi.ptr(x), capi.ptr(out), y.size))
+    return out
+
+
+def debug_expert_normalize_angle(angle_deg):
+    """The experts' bounded normalizeAngleDeg on a host array (no GPU)."""
+    a = np.ascontiguousarray(angle_deg, dtype=np.float32)
+    out = np.zeros_like(a)
+    capi.check(capi.load().okenv_debug_expert_normalize_angle(capi.ptr(a), capi.ptr(out), a.size))
+    return out

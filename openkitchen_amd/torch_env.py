@@ -198,6 +198,18 @@ class VectorEnvironment:
             raise ValueError("camera(out=...) needs a contiguous uint8 tensor of shape %s on %s" % (self.camera_shape, self.device))
         return self.env.render_views(out)
 
+    # ---- expert drivers (include/okenv.h) --------------------------------------------------------------
+    def enable_expert(self, kind="potfield", **params):
+        """Attaches the reference's potential-field ("potfield") or vector-field-histogram ("vfh") driver
+        (FieldNavigators/); params as in capi.expert_params (lookahead, goal_wrap, clamp_deg, ...)."""
+        self.expert_params = self.env.expert_create(kind, **params)
+
+    def expert_act(self, record=None):
+        """The expert's updateAction for every agent from the last observation, written into `throttle` / `steering`: one
+        kernel on the environment's stream, no synchronisation, usable inside capture(body).  record: optional dict of
+        device tensors ("action" [N,2], "dist" [N,R], "rel_xy" [N,R,2] float32, "alive" [N] uint8) that receive the sample."""
+        self.env.expert_act(record)
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)

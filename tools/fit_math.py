@@ -8,6 +8,7 @@ ROUNDED polynomial, evaluated exactly, is reported relative to the function valu
   sin r = r + (r z) S(z),  S(z) = s1 + s2 z + ... + s5 z^4,        z = r^2, |r| <= 0.79 (pi/4 = 0.7854 plus the reduction's slack)
   cos r = 1 + z C(z),      C(z) = c1 + c2 z + ... + c6 z^5
   exp r - 1 = r + r^2 E(r), E(r) = e2 + e3 r + ... ,                |r| <= 0.3470 (ln 2 / 2 = 0.34657 plus slack)
+  atan t = t + (t z) A(z), A(z) = a1 + a2 z + ... + a10 z^9,        z = t^2, |t| <= 0.4143 (tan(pi/8) = 0.41421 plus slack; ok_atan2f)
 """
 import sys
 
@@ -71,6 +72,15 @@ def main():
     print("expm1: %d coefficients, max relative error on [-%s, %s]: %s = 2^%.1f" % (n, L, L, mp.nstr(err, 3), float(mp.log(err, 2))))
     for i, v in enumerate(c):
         print("    e%d = %s  /* %s */" % (i + 2, v.hex(), repr(v)))
+    T = mp.mpf("0.4143")
+    A = lambda z: (mp.atan(mp.sqrt(z)) / mp.sqrt(z) - 1) / z if z > 0 else mp.mpf(-1) / 3  # noqa: E731
+    n = int(sys.argv[4]) if len(sys.argv) > 4 else 10
+    c = to_double(cheb_fit(A, mp.mpf("1e-30"), T * T, n))
+    err = max_rel_err(lambda t: t + t * t * t * horner(c, t * t), mp.atan, mp.mpf("1e-6"), T)
+    print("atan: %d coefficients, max relative error of the rounded polynomial on (0, %s]: %s = 2^%.1f" % (n, T, mp.nstr(err, 3), float(mp.log(err, 2))))
+    for i, v in enumerate(c):
+        print("    a%d = %s  /* %s */" % (i + 1, v.hex(), repr(v)))
+    print("tan(pi/8) = %s; pi/4 = %s, pi/2 = %s, pi = %s" % (float(mp.tan(mp.pi / 8)).hex(), float(mp.pi / 4).hex(), float(mp.pi / 2).hex(), float(mp.pi).hex()))
     # pi/2 = P1 + P2 (double-double), 2/pi; ln 2 = L1 + L2, 1/ln 2
     p1 = float(mp.pi / 2)
     p2 = float(mp.pi / 2 - mp.mpf(p1))
