@@ -559,7 +559,7 @@ OKENV_API int okenv_debug_sincos(int32_t device, const float *x, float *s, float
 /* First-hit parameter t for n arbitrary rays (origin, angle [rad]) through the handle's grid (host pointers). */
 OKENV_API int okenv_debug_cast_rays(okenv_t h, const float *ox, const float *oy, const float *angle_rad, int32_t n, float *out_t);
 
-/* The step-kernel launch sites of openkitchen_amd/csrc/okenv_capi.hip (launchStep, startResident), one per instantiation the
+/* The step-kernel launches of openkitchen_amd/csrc/okenv_capi.hip (the cases of launchStep), one per instantiation the
  * launcher can pick.  The tests use them to check which form a call ran. */
 enum okenv_step_form {
     OKENV_FORM_TAIL_Q,             /* okStepTailKernel<kPolicyQ, 0>: a short Q-learning episode list, one agent per workgroup */
@@ -599,6 +599,49 @@ enum okenv_step_form_attr {
  * counts the launches of form f, the OKENV_NUM_STEP_FORM_ATTRS words after it those of them with each attribute.  n_words must
  * be at least OKENV_NUM_STEP_FORMS * (1 + OKENV_NUM_STEP_FORM_ATTRS); clear != 0 zeroes the counts after copying them. */
 OKENV_API int okenv_debug_step_forms(okenv_t h, uint64_t *out, int32_t n_words, int32_t clear);
+
+/* The launch policy of openkitchen_amd/csrc/okenv_capi.hip on plain numbers, no handle and no GPU needed (as okenv_expert_act_host):
+ * what okenv_create would decide for a population, and what the launcher would do with one call on it.  For the tests, which run
+ * the rules this way for compute-unit counts and image sizes no device at hand shows. */
+#define OKENV_PLAN_FIRST_ROLLOUT (-2)
+typedef struct okenv_plan_query {
+    int32_t  num_agents, num_rays, compute_units;
+    uint32_t flags;            /* okenv_create's */
+    int32_t  image_fits_lds;   /* what the grid builder says of the track */
+    /* the OKENV_* launch variables as numbers; the value that stands for "unset" in brackets */
+    int32_t  lanes_per_agent;  /* [0] */
+    int32_t  block_threads;    /* [0] */
+    int32_t  coop;             /* [1] */
+    int32_t  agents_per_block; /* [-1] */
+    int32_t  tail_max_agents;  /* [-1] */
+    int32_t  resident;         /* [-1] */
+    int32_t  front_back;       /* [1] */
+    float    phase1_range;     /* [-1] */
+    /* bytes of the track image, of the front / back images (0: the track has no split), of the centre line in LDS */
+    int32_t  image_bytes, front_back_bytes, q_bytes;
+    /* the call */
+    int32_t  action_source;    /* 0 stored actions, 1 okenv_rollout_random, 2 MLP policy, 3 Q-learning, 4 controller */
+    int32_t  n_listed;         /* agents on the episode's list, -1: no list, OKENV_PLAN_FIRST_ROLLOUT: an episode's first rollout */
+    int32_t  packed;           /* okenv_step_packed */
+    int32_t  resident_launch;  /* ... starting its resident kernel */
+    int32_t  do_move;
+    uint32_t reset_flags;
+    int32_t  ctrl_num_params;
+} okenv_plan_query;
+typedef struct okenv_plan_result {
+    /* the handle's shape */
+    int32_t lanes_per_agent, natural_lanes, rays_per_lane;
+    float   phase1_range, grid_cell; /* grid_cell: the default cell edge */
+    int32_t grid_mode;               /* 0 LDS image, 1 global grid, 2 brute force */
+    int32_t front_back_built, block_threads, grid_blocks, coop, agents_per_block, tail_max_agents, resident_mode, resident_eligible;
+    int32_t tail_limit;              /* for this call's policy (okenv_episode_tail_limit) */
+    /* the launch */
+    int32_t form;                    /* enum okenv_step_form */
+    int32_t launch_grid, launch_block, launch_lds_bytes, launch_image_off;
+    float   launch_phase1;
+    int32_t launch_lanes, launch_front_back, launch_ctrl_lds_off, launch_waves;
+} okenv_plan_result;
+OKENV_API int okenv_debug_plan_step(const okenv_plan_query *query, okenv_plan_result *out);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,7 @@ SYMBOLS = [
     "okenv_ga_scores_device", "okenv_get_stream", "okenv_off_grid_count", "okenv_work_stats_split", "okenv_debug_step_forms",
     "okenv_render_create", "okenv_render_views", "okenv_render_get_info", "okenv_track_band_triangles",
     "okenv_expert_create", "okenv_expert_act", "okenv_expert_act_host", "okenv_debug_atan2f", "okenv_debug_expert_normalize_angle",
+    "okenv_debug_plan_step",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -103,6 +104,41 @@ def expert_params(kind, lookahead=2, goal_wrap=False, k_att=100.0, k_rep=10.0, e
     kind: "potfield" / "vfh" or the integer."""
     k = EXPERT_KINDS[kind] if isinstance(kind, str) else int(kind)
     return OkenvExpertParams(k, int(lookahead), 1 if goal_wrap else 0, k_att, k_rep, effect_range, clamp_deg, vfh_throttle, int(vfh_threshold))
+
+
+PLAN_FIRST_ROLLOUT = -2
+
+
+class OkenvPlanQuery(C.Structure):
+    """okenv_plan_query; the defaults are a stored-action okenv_step with every launch variable unset."""
+    _fields_ = [("num_agents", C.c_int32), ("num_rays", C.c_int32), ("compute_units", C.c_int32), ("flags", C.c_uint32),
+                ("image_fits_lds", C.c_int32), ("lanes_per_agent", C.c_int32), ("block_threads", C.c_int32), ("coop", C.c_int32),
+                ("agents_per_block", C.c_int32), ("tail_max_agents", C.c_int32), ("resident", C.c_int32), ("front_back", C.c_int32),
+                ("phase1_range", C.c_float), ("image_bytes", C.c_int32), ("front_back_bytes", C.c_int32), ("q_bytes", C.c_int32),
+                ("action_source", C.c_int32), ("n_listed", C.c_int32), ("packed", C.c_int32), ("resident_launch", C.c_int32),
+                ("do_move", C.c_int32), ("reset_flags", C.c_uint32), ("ctrl_num_params", C.c_int32)]
+    DEFAULTS = dict(compute_units=256, image_fits_lds=1, coop=1, agents_per_block=-1, tail_max_agents=-1, resident=-1, front_back=1,
+                    phase1_range=-1.0, n_listed=-1, do_move=1)
+
+
+class OkenvPlanResult(C.Structure):
+    _fields_ = [("lanes_per_agent", C.c_int32), ("natural_lanes", C.c_int32), ("rays_per_lane", C.c_int32), ("phase1_range", C.c_float),
+                ("grid_cell", C.c_float), ("grid_mode", C.c_int32), ("front_back_built", C.c_int32), ("block_threads", C.c_int32),
+                ("grid_blocks", C.c_int32), ("coop", C.c_int32), ("agents_per_block", C.c_int32), ("tail_max_agents", C.c_int32),
+                ("resident_mode", C.c_int32), ("resident_eligible", C.c_int32), ("tail_limit", C.c_int32), ("form", C.c_int32),
+                ("launch_grid", C.c_int32), ("launch_block", C.c_int32), ("launch_lds_bytes", C.c_int32), ("launch_image_off", C.c_int32),
+                ("launch_phase1", C.c_float), ("launch_lanes", C.c_int32), ("launch_front_back", C.c_int32),
+                ("launch_ctrl_lds_off", C.c_int32), ("launch_waves", C.c_int32)]
+
+
+def plan_step(**query):
+    """okenv_debug_plan_step: the library's launch policy for a shape and a call, as a dict (form by name).  No GPU needed."""
+    q = OkenvPlanQuery(**dict(OkenvPlanQuery.DEFAULTS, **query))
+    r = OkenvPlanResult()
+    check(load().okenv_debug_plan_step(C.byref(q), C.byref(r)))
+    out = {name: getattr(r, name) for name, _ in r._fields_}
+    out["form"] = STEP_FORMS[r.form]
+    return out
 
 
 class OkenvError(RuntimeError):
@@ -224,6 +260,7 @@ def load(build_if_missing=True):
     L.okenv_expert_act_host.argtypes = [C.POINTER(OkenvExpertParams), vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.okenv_debug_atan2f.argtypes = [vp, vp, vp, i32]
     L.okenv_debug_expert_normalize_angle.argtypes = [vp, vp, i32]
+    L.okenv_debug_plan_step.argtypes = [C.POINTER(OkenvPlanQuery), C.POINTER(OkenvPlanResult)]
     _lib = L
     return L
 

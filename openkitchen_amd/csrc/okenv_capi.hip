@@ -50,17 +50,324 @@ inline void okCpuRelax()
 }
 } // namespace
 
+// ---- launch policy -------------------------------------------------------------------------------------------------------
+// Which step kernel a call runs (enum okenv_step_form) and with what grid, workgroup, LDS and lane-group width.  Everything from
+// here to the end of this namespace is plain arithmetic on the structs below -- no HIP call, no environment, no handle -- so that
+// okenv_debug_plan_step can run it on a machine without a device for any shape, knob and compute-unit count
+// (tests/test_step_form_table.py).  okenv_create fills the shape once, launchStep asks for a plan per launch.
+namespace
+{
+constexpr size_t kCoopLdsExtra      = 16U; // LDS every cooperative launch needs behind the image (the per-SIMD progress words)
+constexpr int    kResidentMaxAgents = 64;
+
+// The OKENV_* tuning / ablation variables that bear on launches, as parsed (readKnobs).  The default of each is its "unset" state;
+// a value outside the stated range is ignored like an unset one.
+struct OkKnobs
+{
+    int   lanes_per_agent{0};   // a power of two up to 64: fold the fan over fewer lanes (ray r, r+G, ... share one) or spread it over more
+    long  block_threads{0};     // a multiple of 64 and of G up to 1024: smaller workgroups (two per CU when the LDS image allows)
+    int   coop{1};              // 0: every lane walks its own ray to the end
+    int   agents_per_block{-1}; // >= 0 and within the workgroup; 0 = dense
+    int   tail_max_agents{-1};  // 0: never use the tail kernel; > 0: caps the rule
+    float phase1_range{-1.F};   // >= 0 [px]; 0: no phase 1.  Overrides the 16-ray and spare-lane rules
+    int   resident{-1};         // 0: never keep the packed-step kernel resident, 1: from the first eligible step on
+    int   front_back{1};        // 0: every launch stays on the combined image (same results)
+};
+
+// What okenv_create decides once for a handle.
+struct OkLaunchShape
+{
+    int    N{0}, R{0}, cus{256}; // agents, rays, compute units of the device (an MI355X in CPX / DPX partition mode shows 32 / 128 of its 256)
+    int    G{1}, natural_g{1}, rays_per_lane{1};
+    float  phase1_range{48.F};   // T1 of the cooperative kernel [px]
+    float  cell_default{OKGRID_DEFAULT_CELL};
+    int    grid_mode{kGridLds};
+    bool   front_back{false};    // the front / back split of the segment set is to be built (ok_grid.h)
+    int    block_threads{1024}, grid_blocks{1};
+    bool   coop{false};          // cooperative two-phase kernel (LDS form, one ray per lane)
+    int    agents_per_block{0};  // coop, tiny populations: agents per workgroup (the other lanes only stage); 0 = dense
+    int    tail_max_agents{-1};  // episode lists up to this long are stepped by okStepTailKernel: -1 = what one round of workgroups holds, 0 = never
+    int    resident_mode{-1};    // 0 never, 1 from the first eligible step on, default: after a run of quick steps
+    // known once the grid is built and uploaded: the combined image, the [front | back] blob; fb_ok: launches may use the latter
+    size_t image_bytes{0}, fb_bytes{0};
+    bool   fb_ok{false};
+};
+
+int pow2ceil(int v)
+{
+    int p = 1;
+    while (p < v)
+        p <<= 1;
+    return p;
+}
+
+// Widest lane group (up to 64) with which `agents` agents still take at most half of the machine's lanes (compute units x 1024),
+// so that the waves of a CU do not start competing for issue.
+int okWidenLanes(int G, const long agents, const int cus)
+{
+    while (G < 64 && agents * (2L * G) <= 512L * cus)
+        G *= 2;
+    return G;
+}
+
+// Workgroup size and count for `lanes` lanes: spread over the CUs (a workgroup on every CU before they grow to 1024 lanes), but at
+// least four waves each: with a handful of agents the launch is dominated by staging the ~70-90 KB track image into LDS, which a
+// single wave does four times slower (waves without an agent leave right after it).
+void okSpread(const long lanes, const int cus, long *per_block, long *blocks)
+{
+    const long per = ((((lanes + cus - 1) / cus) + 63) / 64) * 64;
+    *per_block     = per < 256 ? 256 : (per > 1024 ? 1024 : per);
+    *blocks        = (lanes + *per_block - 1) / *per_block;
+}
+
+// First stage, before the grid exists: lanes per agent, phase 1 and the cell edge the grid is built with by default.
+OkLaunchShape okPlanLanes(const int N, const int R, const int cus, const OkKnobs &k)
+{
+    OkLaunchShape s;
+    s.N   = N;
+    s.R   = R;
+    s.cus = cus;
+    // lanes per agent: the fan's width rounded up to a power of two -- and more when the population is far too small to fill the
+    // machine: the spare lanes of an agent's group take intervals of its rays in phase 2, which shortens the dependent chain of a
+    // step (11.5-13 us instead of 15.6 us per step for RL-sized populations).
+    s.natural_g = pow2ceil(R) > 64 ? 64 : pow2ceil(R);
+    s.G         = okWidenLanes(s.natural_g, N, cus);
+    if (k.lanes_per_agent >= 1 && k.lanes_per_agent <= 64 && (k.lanes_per_agent & (k.lanes_per_agent - 1)) == 0)
+        s.G = k.lanes_per_agent;
+    // with spare lanes there is no phase 1: phase 2 cuts every ray into intervals from its origin on (a 4 px phase 1 in
+    // front of it cost a second walk set-up per step: 6.5 -> 5.2 us for one five-ray agent, 8.4 -> 7.0 us at 4096 x 5)
+    if (s.G > s.natural_g)
+        s.phase1_range = 0.F;
+    s.rays_per_lane = (R + s.G - 1) / s.G;
+    // cell edge: 24 px when a wave holds one agent (all 64 rays leave one origin), 20 px when it holds several (measured:
+    // Silverstone / Spa x 64 rays 4 % faster at 24, Monza x 32 rays 6 % faster at 20)
+    // (round 3: 16-ray fans four to a wave -- BASELINE config 5 -- 24 px cells with a 32 px phase 1: 15.6 against 16.4 us per step)
+    const bool narrow16 = s.G == 16 && s.rays_per_lane == 1;
+    // (wide fans, one agent per wave: 28 px since the front / back split halved the points per cell -- 9.5-10.0 us per C2 step at
+    // 28-30 px against 10.4 at 24 and 10.7 at 20, profiles/r4/front_back_ab.txt; 16-ray fans stay at 24, 32-ray fans at 20)
+    const bool wide64 = s.G == 64 && s.rays_per_lane == 1 && R > 32;
+    s.cell_default    = wide64 ? 28.F : (narrow16 ? 24.F : OKGRID_DEFAULT_CELL);
+    if (narrow16)
+        s.phase1_range = 32.F;
+    if (k.phase1_range >= 0.F)
+        s.phase1_range = k.phase1_range;
+    return s;
+}
+
+// Second stage, once the grid builder has said whether the track image fits the LDS: the grid form and the launch geometry.
+void okPlanGeometry(OkLaunchShape &s, const uint32_t flags, const bool image_fits_lds, const OkKnobs &k)
+{
+    if (flags & OKENV_FLAG_BRUTE_FORCE)
+        s.grid_mode = kGridBrute;
+    else if (!image_fits_lds || (flags & OKENV_FLAG_FORCE_GLOBAL_GRID))
+        s.grid_mode = kGridGlobal;
+    else
+        s.grid_mode = kGridLds;
+    s.front_back = s.grid_mode == kGridLds && k.front_back != 0;
+    const long total_lanes = static_cast<long>(s.N) * s.G;
+    long       per_block, blocks;
+    okSpread(total_lanes, s.cus, &per_block, &blocks);
+    if (k.block_threads >= 64 && k.block_threads <= 1024 && k.block_threads % 64 == 0 && k.block_threads % s.G == 0)
+        per_block = k.block_threads;
+    s.block_threads = static_cast<int>(per_block);
+    s.grid_blocks   = static_cast<int>((total_lanes + per_block - 1) / per_block);
+    s.coop          = s.grid_mode == kGridLds && s.rays_per_lane == 1 && k.coop != 0;
+    // up to one agent per CU with a wave each (the populations of the reference's applications: 1, 15, 30, 50): one agent per
+    // workgroup, i.e. per CU -- four such waves on one CU take 7.8 us for a step, one alone 6.0 us -- and three more waves
+    // that only help with the staging
+    s.agents_per_block = 0;
+    if (s.coop && s.G == 64 && s.N <= s.cus && per_block == 256)
+        s.agents_per_block = 1;
+    if (s.coop && k.agents_per_block >= 0 && static_cast<long>(k.agents_per_block) * s.G <= per_block)
+        s.agents_per_block = k.agents_per_block;
+    if (s.agents_per_block > 0)
+        s.grid_blocks = (s.N + s.agents_per_block - 1) / s.agents_per_block;
+    s.resident_mode   = k.resident;
+    s.tail_max_agents = k.tail_max_agents;
+}
+
+// okenv_step_packed may keep its kernel resident on handles of this shape (the call and the handle's state decide the rest)
+bool okResidentShape(const OkLaunchShape &s)
+{
+    return s.resident_mode != 0 && s.agents_per_block == 1 && s.N <= kResidentMaxAgents;
+}
+
+size_t okCoopLdsBytes(const size_t image_bytes)
+{
+    return image_bytes + kCoopLdsExtra;
+}
+
+// The tail kernel's workgroup (okStepTailKernel: one agent, every ray cut into kTailSplit intervals): lanes that walk, and LDS
+// behind an image of `image_bytes`.  Q-learning: the centre line and its buckets (q_bytes) and the agent's table in LDS too.
+unsigned okTailLanes(const OkLaunchShape &s)
+{
+    return static_cast<unsigned>(((s.R * kTailSplit + 63) / 64) * 64);
+}
+
+size_t okTailLdsBytes(const size_t image_bytes, const bool q_launch, const size_t q_bytes)
+{
+    return image_bytes + 16U + sizeof(float) * kTailLdsFloats + (q_launch ? q_bytes + sizeof(float) * kTailQFloats : 0U);
+}
+
+// Longest episode list the tail kernel takes on this shape: one round of workgroups -- as many per CU as the LDS holds, times the
+// device's compute units (256 on an MI355X in SPX mode; measured there, 32-ray MLP agents: 8.1 us per step up to 256 agents, 9.2 at
+// 512 with two per CU, against 11.2-11.8 for the cooperative kernel; a second round loses: 17 us) -- or OKENV_TAIL_MAX_AGENTS;
+// 0: the tail kernel does not apply.
+long okTailLimit(const OkLaunchShape &s, const bool q_launch, const size_t q_bytes)
+{
+    if (s.grid_mode != kGridLds || !s.coop || s.tail_max_agents == 0)
+        return 0;
+    const size_t lds = okTailLdsBytes(s.image_bytes, q_launch, q_bytes);
+    if (okTailLanes(s) > 512U || lds > kLdsBudget)
+        return 0;
+    const long fit = static_cast<long>(kLdsBudget / lds) * s.cus;
+    return s.tail_max_agents > 0 ? std::min<long>(s.tail_max_agents, fit) : fit;
+}
+
+// The first rollout of an episode lists the whole population when it fits the tail kernel (prelistEpisode).  The controller
+// rollout has no tail form.
+bool okPrelist(const OkLaunchShape &s, const int action_source, const size_t q_bytes)
+{
+    return action_source != kActionsController && static_cast<long>(s.N) <= okTailLimit(s, action_source == kActionsQLearning, q_bytes);
+}
+
+// What differs from one step launch to the next.
+struct OkStepRequest
+{
+    int      action_source{kActionsStored};
+    int      n_listed{-1};       // agents on the episode's list; -1: no list, the whole population
+    bool     packed{false};      // okenv_step_packed's exchange records
+    bool     resident{false};    // ... served by the kernel that stays (startResident)
+    int      do_move{1};
+    uint32_t reset_flags{0};
+    int      ctrl_num_params{0};
+    size_t   q_bytes{0};         // LDS of the centre line and its cell buckets (qLdsBytes; it changes with okenv_set_centerline)
+};
+
+struct OkStepPlan
+{
+    int      form{OKENV_FORM_COOP};
+    unsigned grid{1}, block{64};
+    size_t   lds{0};            // dynamic LDS bytes
+    uint32_t image_off{0};      // where the image ends in LDS (tail and cooperative kernels)
+    float    phase1{0.F};
+    int      G{1};              // lane-group width of this launch
+    bool     front_back{false}; // the launch walks the [front | back] images
+    uint32_t ctrl_lds_off{0};   // controller parameters staged in LDS from here; 0: read from global memory
+    size_t   waves() const { return static_cast<size_t>(grid) * (block / 64U); }
+};
+
+OkStepPlan okPlanStep(const OkLaunchShape &s, const OkStepRequest &q)
+{
+    OkStepPlan pl;
+    pl.grid         = static_cast<unsigned>(s.grid_blocks);
+    pl.block        = static_cast<unsigned>(s.block_threads);
+    pl.G            = s.G;
+    pl.phase1       = s.phase1_range;
+    const bool mlp  = q.action_source == kActionsMlpPolicy;
+    const bool qlrn = q.action_source == kActionsQLearning;
+    if (q.n_listed >= 0)
+    { // an episode's list: the grid covers the listed agents, spread over the CUs like a population of that size
+        if (qlrn)
+        { // ... and a list that has become short gets what a population that small gets from okPlanLanes: wider lane groups
+          // whose spare lanes take intervals of the agent's rays, no phase 1 (16 rays, 64 listed agents: 9.3 against 11.8 us
+          // per step; the fused MLP's steps gain nothing from it and keep their width)
+            pl.G = okWidenLanes(s.G, q.n_listed, s.cus);
+            if (pl.G > s.G)
+                pl.phase1 = 0.F;
+        }
+        long per, blocks;
+        okSpread(static_cast<long>(q.n_listed) * pl.G, s.cus, &per, &blocks);
+        pl.block = static_cast<unsigned>(per);
+        pl.grid  = static_cast<unsigned>(blocks);
+    }
+    // The tail of an episode: a short list is stepped one agent per workgroup, every ray cut into eight intervals
+    // (okStepTailKernel).  Two such workgroups fit a CU's LDS; beyond about two rounds of them the cooperative kernel's shared
+    // waves win again.
+    if (q.n_listed > 0 && (mlp || qlrn) && q.n_listed <= okTailLimit(s, qlrn, q.q_bytes))
+    {
+        pl.G      = s.G; // (unused by the tail kernel; undoes the widening above)
+        pl.grid   = static_cast<unsigned>(q.n_listed);
+        // (Q-learning: one more wave, without rays -- it looks up the nearest centre-line index while the others walk)
+        pl.block  = okTailLanes(s) + (qlrn ? 64U : 0U);
+        pl.lds    = okTailLdsBytes(s.image_bytes, qlrn, q.q_bytes);
+        // the front / back split while the list fits one round of workgroups with the larger image (fewer of them share a CU);
+        // longer lists keep the combined image and their two workgroups per CU
+        const size_t lds_fb = okTailLdsBytes(s.fb_bytes, qlrn, q.q_bytes);
+        pl.front_back       = s.fb_ok && lds_fb <= kLdsBudget && static_cast<long>(q.n_listed) <= static_cast<long>(kLdsBudget / lds_fb) * s.cus;
+        if (pl.front_back)
+            pl.lds = lds_fb;
+        pl.image_off = static_cast<uint32_t>(pl.front_back ? s.fb_bytes : s.image_bytes);
+        // (15 rays: the reference's own fan -- Agent.cpp:13-17; EvolutionaryRacer's 17-30-6 network --, weights in registers as well)
+        pl.form = qlrn ? OKENV_FORM_TAIL_Q : (s.R == 32 ? OKENV_FORM_TAIL_MLP32 : (s.R == 15 ? OKENV_FORM_TAIL_MLP15 : OKENV_FORM_TAIL_MLP));
+        return pl;
+    }
+    if (s.grid_mode != kGridLds)
+    {
+        const bool global = s.grid_mode == kGridGlobal;
+        pl.form = mlp ? (global ? OKENV_FORM_GLOBAL_MLP : OKENV_FORM_BRUTE_MLP) : (global ? OKENV_FORM_GLOBAL : OKENV_FORM_BRUTE);
+        return pl;
+    }
+    if (!s.coop)
+    {
+        pl.lds  = s.image_bytes;
+        pl.form = mlp ? OKENV_FORM_LDS_MLP : OKENV_FORM_LDS;
+        return pl;
+    }
+    // the front / back split, when everything else the launch stages still fits behind it
+    const bool ctrl  = q.action_source == kActionsController;
+    pl.front_back    = s.fb_ok && okCoopLdsBytes(s.fb_bytes) + (qlrn || ctrl ? q.q_bytes : 0U) <= kLdsBudget;
+    const size_t img = pl.front_back ? s.fb_bytes : s.image_bytes;
+    pl.image_off     = static_cast<uint32_t>(img);
+    pl.lds           = okCoopLdsBytes(img);
+    // policy-free launches of a population with spare lanes and no phase 1 use the kernel's direct dealing of intervals to lanes
+    // (okStepCoopKernel's kDirect)
+    const bool direct = s.phase1_range <= 0.F && s.G >= 2 * s.R;
+    if (qlrn)
+    {
+        pl.lds += q.q_bytes;
+        pl.form = OKENV_FORM_COOP_Q;
+    }
+    else if (ctrl)
+    { // the controllers' parameters of a workgroup's agents go into its LDS when they fit behind the centre line
+        pl.lds += q.q_bytes;
+        const size_t base  = ((pl.lds + 15U) / 16U) * 16U;
+        const size_t stage = static_cast<size_t>(pl.block / static_cast<unsigned>(pl.G)) * static_cast<size_t>(q.ctrl_num_params) * sizeof(float);
+        if (base + stage <= kLdsBudget)
+        {
+            pl.ctrl_lds_off = static_cast<uint32_t>(base);
+            pl.lds          = base + stage;
+        }
+        pl.form = OKENV_FORM_COOP_CTRL;
+    }
+    else if (mlp) // (32 rays in 32-lane groups, C3 / C4's fan: group and fan width compile-time constants)
+        pl.form = s.G == 32 && s.R == 32 ? OKENV_FORM_COOP_MLP32 : OKENV_FORM_COOP_MLP;
+    else if (q.resident)
+        pl.form = direct ? OKENV_FORM_RESIDENT_DIRECT : OKENV_FORM_RESIDENT;
+    else if (q.packed)
+        pl.form = direct ? OKENV_FORM_COOP_PACKED_DIRECT : OKENV_FORM_COOP_PACKED;
+    else if (direct)
+        pl.form = OKENV_FORM_COOP_DIRECT;
+    else if (s.G == 64 && q.action_source == kActionsPhiloxReset && q.do_move != 0 && q.reset_flags == 0U)
+        pl.form = OKENV_FORM_COOP_G64_RANDOM; // okenv_rollout_random without device-side resetAgent: its launch-time switches as constants (-1 %)
+    else if (s.G == 64)
+        pl.form = OKENV_FORM_COOP_G64; // one agent per wave, the group width a compile-time constant (-1 % on 20-step launches)
+    else
+        pl.form = OKENV_FORM_COOP;
+    return pl;
+}
+} // namespace
+
 struct okenv
 {
     int         device{0};
     hipStream_t stream{nullptr};
     bool        own_stream{true};
-    int         N{0}, R{0}, S{0}, G{1}, rays_per_lane{1};
+    OkLaunchShape shape; // population, fan and every launch decision taken once (okPlanLanes, okPlanGeometry)
+    int         S{0};
     uint32_t    flags{0};
-    int         grid_mode{kGridLds};
     OkGridHost  grid;
     OkPolyImage poly;
-    size_t      image_bytes{0};
     void       *d_image{nullptr};
     OkSeg      *d_segs{nullptr};
     uint32_t   *d_refs32{nullptr}, *d_start{nullptr};
@@ -83,17 +390,14 @@ struct okenv
     uint32_t   *d_step_count{nullptr};
     OkDeviceState st{};
     std::vector<void *> allocations;
-    int         block_threads{1024}, grid_blocks{1};
     // EvolutionaryRacer state
     int      mlp_hidden{0};
     // front / back split of the segment set (ok_grid.h): classification, the two images, and their copy on the device as one blob
-    // [front | back]; fb_ok: the cooperative kernel's non-packed launches use it
+    // [front | back] (shape.fb_bytes of it, usable when shape.fb_ok)
     OkFrontBack       fbc;
     OkFrontBackImages fbi;
-    bool              fb_ok{false};
     uint8_t          *d_image_fb{nullptr};
-    size_t            fb_bytes{0}, fb_back_off{0};
-    int      cus{256}; // compute units of the device (hipDeviceAttributeMultiprocessorCount), asked once in okenv_create
+    size_t            fb_back_off{0};
     float   *d_mlp_w{nullptr}, *d_mlp_w_new{nullptr}, *d_score{nullptr}, *d_parent_score{nullptr};
     int32_t *d_nearest{nullptr}, *d_parents{nullptr}, *d_alive{nullptr};
     // Q-learning state
@@ -113,8 +417,6 @@ struct okenv
     float    q_epsilon{0.F};
     unsigned long long *d_stamps{nullptr}; // -DOKENV_STAMPS builds: per-wave stamps of the last launch
     size_t    stamp_waves{0}, stamp_waves_cap{0};
-    int       tail_max_agents{-1}; // episode lists up to this long are stepped by okStepTailKernel: -1 = what one round of
-                                   // workgroups holds, 0 = never (OKENV_TAIL_MAX_AGENTS)
     // episodes (okenv_episode_begin / _compact / _end)
     bool      episode{false};
     int       n_active{-1};       // agents listed for the policy rollouts (-1: everybody, no list)
@@ -128,13 +430,10 @@ struct okenv
     float    *d_crash_thr{nullptr}, *d_crash_steer{nullptr};
     unsigned long long *d_live{nullptr};
     std::vector<float> host_cx, host_cy, host_chead, host_ray_deg;
-    bool        coop{false};        // cooperative two-phase kernel (LDS form, one ray per lane)
-    int         agents_per_block{0}; // coop, tiny populations: agents per workgroup (the other lanes only stage); 0 = dense
     uint32_t    packed_seq{0};      // okenv_step_packed: sequence number of the last launch's completion word
     // resident step kernel (okenv_step_packed called in quick succession, see startResident)
     hipStream_t resident_stream{nullptr};
     bool        resident{false};
-    int         resident_mode{-1};  // OKENV_RESIDENT: 0 never, 1 from the first eligible step on, default: after a run of quick steps
     int         resident_steps{0}, resident_fallbacks{0}; // statistics (okenv_get_info)
     int         resident_stall_us{0}; // OKENV_RESIDENT_STALL_US, fault injection for the tests: the host dawdles this long before
                                       // it hands a step to the resident kernel, which has left by then
@@ -143,7 +442,6 @@ struct okenv
     int         packed_streak{0};   // packed steps in a row that came within kResidentGapUs of the one before
     std::chrono::steady_clock::time_point packed_last_end{};
     size_t      stage_slots_off{0}; // where the agents' slots lie in h_stage
-    float       phase1_range{48.F}; // T1 of the cooperative kernel [px]
     bool        ep_prelist{false};  // okenv_episode_begin has run, the episode's first rollout has not: it decides the pre-listing
     // step-kernel launches by form and attribute (okenv_debug_step_forms)
     uint64_t    form_counts[OKENV_NUM_STEP_FORMS][1 + OKENV_NUM_STEP_FORM_ATTRS]{};
@@ -229,14 +527,6 @@ int deviceScratch(okenv *h, const size_t bytes, void **out)
     return OKENV_OK;
 }
 
-int pow2ceil(int v)
-{
-    int p = 1;
-    while (p < v)
-        p <<= 1;
-    return p;
-}
-
 struct FieldDesc
 {
     void  *ptr;
@@ -245,7 +535,7 @@ struct FieldDesc
 
 FieldDesc fieldOf(okenv *h, const int f)
 {
-    const size_t N = h->N, NR = static_cast<size_t>(h->N) * h->R;
+    const size_t N = h->shape.N, NR = static_cast<size_t>(h->shape.N) * h->shape.R;
     auto        &s = h->st;
     switch (f)
     {
@@ -282,14 +572,14 @@ OkStepParams baseParams(okenv *h)
 {
     OkStepParams p{};
     p.st            = h->st;
-    p.N             = h->N;
-    p.R             = h->R;
-    p.G             = h->G;
-    p.rays_per_lane = h->rays_per_lane;
+    p.N             = h->shape.N;
+    p.R             = h->shape.R;
+    p.G             = h->shape.G;
+    p.rays_per_lane = h->shape.rays_per_lane;
     p.ray_deg       = h->d_ray_deg;
     p.sensor_offset = h->sensor_offset;
     p.image         = static_cast<const uint8_t *>(h->d_image);
-    p.image_bytes   = static_cast<uint32_t>(h->image_bytes);
+    p.image_bytes   = static_cast<uint32_t>(h->shape.image_bytes);
     p.off_hdr       = static_cast<uint32_t>(h->poly.off_hdr);
     p.side_tol      = h->poly.side_tol;
     p.geom          = h->grid.g;
@@ -308,7 +598,7 @@ OkStepParams baseParams(okenv *h)
     p.reset_seed    = h->reset_seed;
     p.agent_base    = h->reset_agent_base;
     p.step_counter  = h->d_step_count;
-    p.agents_per_block = h->coop ? h->agents_per_block : 0;
+    p.agents_per_block = h->shape.coop ? h->shape.agents_per_block : 0;
     p.lane_l        = h->d_lane_l;
     p.lane_r        = h->d_lane_r;
     p.mlp_w         = h->d_mlp_w;
@@ -354,24 +644,29 @@ void dropEpisode(okenv *h)
     h->ep_prelist = false;
 }
 
-long tailLimit(const okenv *h, bool q_launch);
+// LDS the Q-learning kernel needs behind the track image: the centre line (8 B per point) and its cell buckets
+size_t qLdsBytes(const okenv *h)
+{
+    const size_t cells = static_cast<size_t>(h->grid.g.nx) * h->grid.g.ny;
+    return 8U * static_cast<size_t>(h->P) + 2U * (cells + 1U) + 2U * static_cast<size_t>(h->P) + 16U;
+}
 
-// The first rollout of an episode (kind: kPolicyMlp / kPolicyQ / kPolicyCtrl): a population that fits the tail kernel (the
+// The first rollout of an episode (action_source: kActionsMlpPolicy / kActionsQLearning / kActionsController): a population that fits the tail kernel (the
 // reference's 50 agents, say) is listed from the start.  Nobody is settled yet, so the list is 0 ... N-1 and its length is known
 // without asking the device -- the very first rollout then already runs one agent per workgroup, each leaving with its agent,
 // instead of the cooperative kernel that okenv_episode_compact would only replace after the first launch.  Decided here and not in
 // okenv_episode_begin because it depends on the rollout's policy (the Q-learning kernel's tail limit is lower; the controller
 // rollout has no tail form), and a handle may have several policies attached.
-int prelistEpisode(okenv *h, const int kind)
+int prelistEpisode(okenv *h, const int action_source)
 {
     if (!h->ep_prelist)
         return OKENV_OK;
     h->ep_prelist = false;
-    if (kind == kPolicyCtrl || h->n_active >= 0 || static_cast<long>(h->N) > tailLimit(h, kind == kPolicyQ))
+    if (h->n_active >= 0 || !okPrelist(h->shape, action_source, qLdsBytes(h)))
         return OKENV_OK;
-    hipLaunchKernelGGL(okEpisodeCompactKernel, dim3(1), dim3(1024), 0, h->stream, h->d_settled, h->st.crashed, h->N, h->d_active, h->d_ep_counts);
+    hipLaunchKernelGGL(okEpisodeCompactKernel, dim3(1), dim3(1024), 0, h->stream, h->d_settled, h->st.crashed, h->shape.N, h->d_active, h->d_ep_counts);
     OK_HIP(h, hipGetLastError());
-    h->n_active = h->N;
+    h->n_active = h->shape.N;
     return OKENV_OK;
 }
 
@@ -400,20 +695,6 @@ int endTiming(okenv *h, const EventPair &ev)
     OK_HIP(h, hipEventRecord(ev.stop, h->stream));
     h->events.push_back(ev);
     return OKENV_OK;
-}
-
-// LDS the Q-learning kernel needs behind the track image: the centre line (8 B per point) and its cell buckets
-size_t qLdsBytes(const okenv *h)
-{
-    const size_t cells = static_cast<size_t>(h->grid.g.nx) * h->grid.g.ny;
-    return 8U * static_cast<size_t>(h->P) + 2U * (cells + 1U) + 2U * static_cast<size_t>(h->P) + 16U;
-}
-
-// LDS every cooperative launch needs behind the image (the per-SIMD progress words)
-constexpr size_t kCoopLdsExtra = 16U;
-size_t coopLdsBytes(const okenv *h)
-{
-    return h->image_bytes + kCoopLdsExtra;
 }
 
 // Buckets the centre-line points by the cells of the raycast grid (CSR, indices ascending inside a cell) and uploads
@@ -481,14 +762,13 @@ constexpr double   kResidentGapUs     = 100.0;  // the host treats the kernel as
 constexpr int      kResidentStreak    = 16;     // quick steps in a row before the kernel is made resident
 constexpr int      kResidentShort     = 32;     // a residency that served fewer steps than this quadruples that number
 constexpr uint32_t kResidentExit      = 0xFFFFFFFFU;
-constexpr int      kResidentMaxAgents = 64;
 
 int stopResident(okenv *h)
 {
     if (!h->resident)
         return OKENV_OK;
     volatile uint32_t *slots = reinterpret_cast<volatile uint32_t *>(static_cast<uint8_t *>(h->h_stage) + h->stage_slots_off);
-    for (int i = 0; i < h->N; ++i)
+    for (int i = 0; i < h->shape.N; ++i)
         for (int q = 3; q < 16; q += 4)
             slots[16 * i + q] = kResidentExit;
     std::atomic_thread_fence(std::memory_order_seq_cst);
@@ -523,16 +803,22 @@ uint32_t nextPackedSeq(okenv *h)
     return h->packed_seq;
 }
 
-size_t coopLdsBytes(const okenv *h);
-
-// Policy-free launches of a population with spare lanes and no phase 1 use the kernel's direct dealing of intervals to lanes
-// (okStepCoopKernel's kDirect).
-bool directIntervals(const okenv *h)
+// Points a launch at the [front | back] images instead of the combined one (ok_grid.h: okClassifyFrontBack).
+void useFrontBack(const okenv *h, OkStepParams &p)
 {
-    return h->phase1_range <= 0.F && h->G >= 2 * h->R;
+    p.image            = h->d_image_fb;
+    p.image_bytes      = static_cast<uint32_t>(h->shape.fb_bytes);
+    p.off_hdr          = static_cast<uint32_t>(h->fbi.front.off_hdr);
+    p.side_tol         = h->fbi.front.side_tol;
+    p.fb               = 1U;
+    p.fb_back_off      = static_cast<uint32_t>(h->fb_back_off);
+    p.fb_back_off_hdr  = static_cast<uint32_t>(h->fb_back_off + h->fbi.back.off_hdr);
+    p.fb_back_side_tol = h->fbi.back.side_tol;
+    p.fb_e_s           = h->fbc.e_s;
+    p.fb_e_t           = h->fbc.e_t;
+    p.fb_t12           = h->fbc.t12;
+    p.fb_t34           = h->fbc.t34;
 }
-
-void useFrontBack(const okenv *h, OkStepParams &p);
 
 // One step-kernel launch of form `form` (enum okenv_step_form) with parameters `p`: counted next to every hipLaunchKernelGGL of a
 // step kernel, so that the tests can tell which instantiation a call ran (okenv_debug_step_forms).  Host-side only.
@@ -542,9 +828,127 @@ void countForm(okenv *h, const int form, const OkStepParams &p)
     c[0] += 1U;
     c[1 + OKENV_FORM_ATTR_FRONT_BACK] += p.fb != 0U ? 1U : 0U;
     c[1 + OKENV_FORM_ATTR_LIST] += p.active != nullptr ? 1U : 0U;
-    c[1 + OKENV_FORM_ATTR_WIDENED] += p.G > h->G ? 1U : 0U;
+    c[1 + OKENV_FORM_ATTR_WIDENED] += p.G > h->shape.G ? 1U : 0U;
     c[1 + OKENV_FORM_ATTR_CTRL_LDS] += p.ctrl_lds_off != 0U ? 1U : 0U;
     c[1 + OKENV_FORM_ATTR_AGENTS_PER_BLOCK] += p.agents_per_block > 0 ? 1U : 0U;
+}
+
+// Every step-kernel launch of the library: asks the launch policy (okPlanStep) for a plan, applies it to `p` and launches the
+// plan's form -- the one hipLaunchKernelGGL under its case label below.
+int launchStep(okenv *h, OkStepParams p) // (by value: the plan is applied to it)
+{
+    OK_HIP(h, hipSetDevice(h->device));
+    EventPair ev{};
+    int       rc = beginTiming(h, &ev);
+    if (rc != OKENV_OK)
+        return rc;
+    OkStepRequest rq;
+    rq.action_source   = p.action_source;
+    rq.n_listed        = p.active != nullptr ? p.n_active : -1;
+    rq.packed          = p.rec_in != nullptr;
+    rq.resident        = p.slots != nullptr;
+    rq.do_move         = p.do_move;
+    rq.reset_flags     = p.reset_flags;
+    rq.ctrl_num_params = h->ctrl_num_params;
+    rq.q_bytes         = qLdsBytes(h);
+    const OkStepPlan plan = okPlanStep(h->shape, rq);
+    if (plan.front_back)
+        useFrontBack(h, p);
+    p.G            = plan.G;
+    p.ctrl_lds_off = plan.ctrl_lds_off;
+#if defined(OKENV_STAMPS)
+    { // diagnostic build: stamp space for every wave of THIS launch (the grid differs between populations, lists and forms).  Tail
+      // kernel: [0] policy, [1] pre-step, [3] interval walk + min, [5] epilogue, [6] barrier, [7] crash test + Q-learning; [2] / [4] start / end
+        if (plan.waves() > h->stamp_waves_cap)
+        {
+            unsigned long long *d = nullptr;
+            const int           src = devAlloc(h, &d, plan.waves() * kStampWords);
+            if (src != OKENV_OK)
+                return src;
+            h->d_stamps        = d;
+            h->stamp_waves_cap = plan.waves();
+        }
+        h->stamp_waves = plan.waves();
+        p.stamps       = h->d_stamps;
+    }
+#endif
+    countForm(h, plan.form, p);
+    const dim3        grid(plan.grid), block(plan.block);
+    const size_t      lds    = plan.lds;
+    const uint32_t    off    = plan.image_off;
+    const float       phase1 = plan.phase1;
+    const hipStream_t stream = rq.resident ? h->resident_stream : h->stream;
+    switch (plan.form)
+    { // (the kernels lie in the code object in the order of these cases)
+    case OKENV_FORM_RESIDENT_DIRECT: // (the image is staged once for the kernel's whole residency)
+        hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true, true, true>), grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_RESIDENT:
+        hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true, true>), grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_TAIL_Q:
+        hipLaunchKernelGGL((okStepTailKernel<kPolicyQ, 0>), grid, block, lds, stream, p, off);
+        break;
+    case OKENV_FORM_TAIL_MLP32:
+        hipLaunchKernelGGL((okStepTailKernel<kPolicyMlp, 32>), grid, block, lds, stream, p, off);
+        break;
+    case OKENV_FORM_TAIL_MLP15:
+        hipLaunchKernelGGL((okStepTailKernel<kPolicyMlp, 15>), grid, block, lds, stream, p, off);
+        break;
+    case OKENV_FORM_TAIL_MLP:
+        hipLaunchKernelGGL((okStepTailKernel<kPolicyMlp, 0>), grid, block, lds, stream, p, off);
+        break;
+    case OKENV_FORM_COOP_Q:
+        hipLaunchKernelGGL(okStepCoopKernel<kPolicyQ>, grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_COOP_CTRL:
+        hipLaunchKernelGGL(okStepCoopKernel<kPolicyCtrl>, grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_COOP_MLP32:
+        hipLaunchKernelGGL((okStepCoopKernel<kPolicyMlp, false, false, false, 32>), grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_COOP_MLP:
+        hipLaunchKernelGGL(okStepCoopKernel<kPolicyMlp>, grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_COOP_PACKED_DIRECT:
+        hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true, false, true>), grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_COOP_PACKED:
+        hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true>), grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_COOP_DIRECT:
+        hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, false, false, true>), grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_COOP_G64_RANDOM:
+        hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, false, false, false, 64, true>), grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_COOP_G64:
+        hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, false, false, false, 64>), grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_COOP:
+        hipLaunchKernelGGL(okStepCoopKernel<kPolicyNone>, grid, block, lds, stream, p, off, phase1);
+        break;
+    case OKENV_FORM_LDS_MLP:
+        hipLaunchKernelGGL((okStepKernel<kGridLds, kPolicyMlp>), grid, block, lds, stream, p);
+        break;
+    case OKENV_FORM_LDS:
+        hipLaunchKernelGGL((okStepKernel<kGridLds, kPolicyNone>), grid, block, lds, stream, p);
+        break;
+    case OKENV_FORM_GLOBAL_MLP:
+        hipLaunchKernelGGL((okStepKernel<kGridGlobal, kPolicyMlp>), grid, block, lds, stream, p);
+        break;
+    case OKENV_FORM_GLOBAL:
+        hipLaunchKernelGGL((okStepKernel<kGridGlobal, kPolicyNone>), grid, block, lds, stream, p);
+        break;
+    case OKENV_FORM_BRUTE_MLP:
+        hipLaunchKernelGGL((okStepKernel<kGridBrute, kPolicyMlp>), grid, block, lds, stream, p);
+        break;
+    case OKENV_FORM_BRUTE:
+        hipLaunchKernelGGL((okStepKernel<kGridBrute, kPolicyNone>), grid, block, lds, stream, p);
+        break;
+    }
+    OK_HIP(h, hipGetLastError());
+    return endTiming(h, ev);
 }
 
 // Starts the resident kernel on a stream of its own; `p` carries the exchange pointers of okenv_step_packed.
@@ -553,31 +957,13 @@ int startResident(okenv *h, OkStepParams p, volatile uint32_t *slots)
     OK_HIP(h, hipStreamSynchronize(h->stream)); // whatever was enqueued against the state comes first
     if (!h->resident_stream)
         OK_HIP(h, hipStreamCreateWithFlags(&h->resident_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 16 * h->N; ++i)
+    for (int i = 0; i < 16 * h->shape.N; ++i)
         slots[i] = 0U;
     std::atomic_thread_fence(std::memory_order_seq_cst);
     p.done_seq = okNextPackedSeq(h->packed_seq); // the first number the kernel waits for
-    size_t   lds = coopLdsBytes(h);
-    uint32_t off = static_cast<uint32_t>(h->image_bytes);
-    if (h->fb_ok && h->fb_bytes + kCoopLdsExtra <= kLdsBudget)
-    { // the front / back split (staged once for the kernel's whole residency)
-        useFrontBack(h, p);
-        off = static_cast<uint32_t>(h->fb_bytes);
-        lds = h->fb_bytes + kCoopLdsExtra;
-    }
-    if (directIntervals(h))
-    {
-        countForm(h, OKENV_FORM_RESIDENT_DIRECT, p);
-        hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true, true, true>), dim3(h->grid_blocks), dim3(h->block_threads), lds, h->resident_stream, p, off,
-                           h->phase1_range);
-    }
-    else
-    {
-        countForm(h, OKENV_FORM_RESIDENT, p);
-        hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true, true>), dim3(h->grid_blocks), dim3(h->block_threads), lds, h->resident_stream, p, off,
-                           h->phase1_range);
-    }
-    OK_HIP(h, hipGetLastError());
+    const int rc = launchStep(h, p); // (p.slots makes it the resident form)
+    if (rc != OKENV_OK)
+        return rc;
     h->resident = true;
     return OKENV_OK;
 }
@@ -597,7 +983,7 @@ int stepResident(okenv *h, const okenv_agent_record *in, volatile uint32_t *slot
         }
     }
     const uint32_t seq = nextPackedSeq(h);
-    const size_t   N   = static_cast<size_t>(h->N);
+    const size_t   N   = static_cast<size_t>(h->shape.N);
     for (size_t i = 0; i < N; ++i)
     { // record word j goes to slot word j + j / 3: words 3, 7, 11, 15 of a slot carry the sequence number
         uint32_t w[sizeof(okenv_agent_record) / 4U];
@@ -683,263 +1069,6 @@ int waitPackedDone(okenv *h, const volatile uint32_t *word, const uint32_t seq)
     }
 }
 
-// Points a launch at the [front | back] images instead of the combined one (ok_grid.h: okClassifyFrontBack).
-void useFrontBack(const okenv *h, OkStepParams &p)
-{
-    p.image            = h->d_image_fb;
-    p.image_bytes      = static_cast<uint32_t>(h->fb_bytes);
-    p.off_hdr          = static_cast<uint32_t>(h->fbi.front.off_hdr);
-    p.side_tol         = h->fbi.front.side_tol;
-    p.fb               = 1U;
-    p.fb_back_off      = static_cast<uint32_t>(h->fb_back_off);
-    p.fb_back_off_hdr  = static_cast<uint32_t>(h->fb_back_off + h->fbi.back.off_hdr);
-    p.fb_back_side_tol = h->fbi.back.side_tol;
-    p.fb_e_s           = h->fbc.e_s;
-    p.fb_e_t           = h->fbc.e_t;
-    p.fb_t12           = h->fbc.t12;
-    p.fb_t34           = h->fbc.t34;
-}
-
-int launchStep(okenv *h, OkStepParams p) // (by value: the diagnostic build adds its stamp buffer)
-{
-    OK_HIP(h, hipSetDevice(h->device));
-    EventPair ev{};
-    int       rc = beginTiming(h, &ev);
-    if (rc != OKENV_OK)
-        return rc;
-    dim3      grid(h->grid_blocks), block(h->block_threads);
-    const int policy = p.action_source == kActionsMlpPolicy ? kPolicyMlp : kPolicyNone;
-    float phase1 = h->phase1_range;
-    if (p.active != nullptr)
-    { // an episode's list: the grid covers the listed agents, spread over the CUs like a population of that size
-        if (p.action_source == kActionsQLearning)
-        { // ... and a list that has become short gets what a population that small gets from okenv_create: wider lane groups
-          // whose spare lanes take intervals of the agent's rays, no phase 1 (16 rays, 64 listed agents: 9.3 against 11.8 us
-          // per step; the fused MLP's steps gain nothing from it and keep their width)
-            int G = h->G;
-            while (G < 64 && static_cast<long>(p.n_active) * (2L * G) <= 512L * h->cus) // half of the machine's lanes, as in okenv_create
-                G *= 2;
-            if (G > h->G)
-            {
-                p.G    = G;
-                phase1 = 0.F;
-            }
-        }
-        const long lanes = static_cast<long>(p.n_active) * p.G;
-        long       per   = ((((lanes + h->cus - 1) / h->cus) + 63) / 64) * 64;
-        per              = per < 256 ? 256 : (per > 1024 ? 1024 : per);
-        block            = dim3(static_cast<unsigned>(per));
-        grid             = dim3(static_cast<unsigned>((lanes + per - 1) / per));
-    }
-#if defined(OKENV_STAMPS)
-    { // diagnostic build: stamp space for every wave of THIS launch (the grid differs between populations, lists and forms)
-        const size_t waves = static_cast<size_t>(grid.x) * (block.x / 64U);
-        if (waves > h->stamp_waves_cap)
-        {
-            unsigned long long *d = nullptr;
-            const int           src = devAlloc(h, &d, waves * kStampWords);
-            if (src != OKENV_OK)
-                return src;
-            h->d_stamps        = d;
-            h->stamp_waves_cap = waves;
-        }
-        h->stamp_waves = waves;
-        p.stamps       = h->d_stamps;
-    }
-#endif
-    // The tail of an episode: a short list is stepped one agent per workgroup, every ray cut into eight intervals
-    // (okStepTailKernel).  Two such workgroups fit a CU's LDS; beyond about two rounds of them the cooperative kernel's shared
-    // waves win again.
-    const bool q_launch = p.action_source == kActionsQLearning;
-    if (p.active != nullptr && (policy == kPolicyMlp || q_launch) && p.n_active > 0)
-    {
-        // (Q-learning: one more wave, without rays -- it looks up the nearest centre-line index while the others walk -- and the
-        // agent's table in LDS)
-        const unsigned lanes = static_cast<unsigned>(((h->R * kTailSplit + 63) / 64) * 64) + (q_launch ? 64U : 0U);
-        size_t         lds   = h->image_bytes + 16U + sizeof(float) * kTailLdsFloats + (q_launch ? qLdsBytes(h) + sizeof(float) * kTailQFloats : 0U);
-        if (p.n_active <= tailLimit(h, q_launch))
-        {
-            p.G = h->G; // (unused by the tail kernel; undo the widening above)
-            const dim3 tgrid(static_cast<unsigned>(p.n_active)), tblock(lanes);
-            uint32_t   off = static_cast<uint32_t>(h->image_bytes);
-            // the front / back split while the list fits one round of workgroups with the larger image (fewer of them share a CU);
-            // longer lists keep the combined image and their two workgroups per CU
-            const size_t lds_fb = lds - h->image_bytes + h->fb_bytes;
-            if (h->fb_ok && lds_fb <= kLdsBudget && static_cast<long>(p.n_active) <= static_cast<long>(kLdsBudget / lds_fb) * h->cus)
-            {
-                useFrontBack(h, p);
-                off = static_cast<uint32_t>(h->fb_bytes);
-                lds = lds_fb;
-            }
-#if defined(OKENV_STAMPS)
-            { // [0] policy, [1] pre-step, [3] interval walk + min, [5] epilogue, [6] barrier, [7] crash test + Q-learning; [2] / [4] start / end
-                const size_t waves = static_cast<size_t>(p.n_active) * (lanes / 64U);
-                if (waves > h->stamp_waves_cap)
-                {
-                    unsigned long long *d = nullptr;
-                    const int           src = devAlloc(h, &d, waves * kStampWords);
-                    if (src != OKENV_OK)
-                        return src;
-                    h->d_stamps        = d;
-                    h->stamp_waves_cap = waves;
-                }
-                h->stamp_waves = waves;
-                p.stamps       = h->d_stamps;
-            }
-#endif
-            if (q_launch)
-            {
-                countForm(h, OKENV_FORM_TAIL_Q, p);
-                hipLaunchKernelGGL((okStepTailKernel<kPolicyQ, 0>), tgrid, tblock, lds, h->stream, p, off);
-            }
-            else if (h->R == 32)
-            {
-                countForm(h, OKENV_FORM_TAIL_MLP32, p);
-                hipLaunchKernelGGL((okStepTailKernel<kPolicyMlp, 32>), tgrid, tblock, lds, h->stream, p, off);
-            }
-            else if (h->R == 15) // the reference's own fan (Agent.cpp:13-17; EvolutionaryRacer's 17-30-6 network): weights in registers as well
-            {
-                countForm(h, OKENV_FORM_TAIL_MLP15, p);
-                hipLaunchKernelGGL((okStepTailKernel<kPolicyMlp, 15>), tgrid, tblock, lds, h->stream, p, off);
-            }
-            else
-            {
-                countForm(h, OKENV_FORM_TAIL_MLP, p);
-                hipLaunchKernelGGL((okStepTailKernel<kPolicyMlp, 0>), tgrid, tblock, lds, h->stream, p, off);
-            }
-            OK_HIP(h, hipGetLastError());
-            return endTiming(h, ev);
-        }
-    }
-    switch (h->grid_mode)
-    {
-    case kGridLds:
-        if (h->coop)
-        {
-            size_t   lds = coopLdsBytes(h);
-            uint32_t off = static_cast<uint32_t>(h->image_bytes);
-            // the front / back split, when everything else the launch stages still fits behind it
-            const bool has_extra = p.action_source == kActionsQLearning || p.action_source == kActionsController;
-            if (h->fb_ok && h->fb_bytes + kCoopLdsExtra + (has_extra ? qLdsBytes(h) : 0U) <= kLdsBudget)
-            {
-                useFrontBack(h, p);
-                off = static_cast<uint32_t>(h->fb_bytes);
-                lds = h->fb_bytes + kCoopLdsExtra;
-            }
-            if (p.action_source == kActionsQLearning)
-            {
-                countForm(h, OKENV_FORM_COOP_Q, p);
-                hipLaunchKernelGGL(okStepCoopKernel<kPolicyQ>, grid, block, lds + qLdsBytes(h), h->stream, p, off, phase1);
-            }
-            else if (p.action_source == kActionsController)
-            { // the controllers' parameters of a workgroup's agents go into its LDS when they fit behind the centre line
-                const size_t base  = ((lds + qLdsBytes(h) + 15U) / 16U) * 16U;
-                const size_t stage = static_cast<size_t>(block.x / static_cast<unsigned>(p.G)) * static_cast<size_t>(h->ctrl_num_params) * sizeof(float);
-                size_t       total = lds + qLdsBytes(h);
-                if (base + stage <= kLdsBudget)
-                {
-                    p.ctrl_lds_off = static_cast<uint32_t>(base);
-                    total          = base + stage;
-                }
-                countForm(h, OKENV_FORM_COOP_CTRL, p);
-                hipLaunchKernelGGL(okStepCoopKernel<kPolicyCtrl>, grid, block, total, h->stream, p, off, phase1);
-            }
-            else if (policy == kPolicyMlp && h->G == 32 && h->R == 32) // C3 / C4's fan: group and fan width compile-time constants
-            {
-                countForm(h, OKENV_FORM_COOP_MLP32, p);
-                hipLaunchKernelGGL((okStepCoopKernel<kPolicyMlp, false, false, false, 32>), grid, block, lds, h->stream, p, off, h->phase1_range);
-            }
-            else if (policy == kPolicyMlp)
-            {
-                countForm(h, OKENV_FORM_COOP_MLP, p);
-                hipLaunchKernelGGL(okStepCoopKernel<kPolicyMlp>, grid, block, lds, h->stream, p, off, h->phase1_range);
-            }
-            else if (p.rec_in != nullptr && directIntervals(h))
-            {
-                countForm(h, OKENV_FORM_COOP_PACKED_DIRECT, p);
-                hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true, false, true>), grid, block, lds, h->stream, p, off, h->phase1_range);
-            }
-            else if (p.rec_in != nullptr)
-            {
-                countForm(h, OKENV_FORM_COOP_PACKED, p);
-                hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, true>), grid, block, lds, h->stream, p, off, h->phase1_range);
-            }
-            else if (directIntervals(h))
-            {
-                countForm(h, OKENV_FORM_COOP_DIRECT, p);
-                hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, false, false, true>), grid, block, lds, h->stream, p, off, h->phase1_range);
-            }
-            else if (h->G == 64 && p.action_source == kActionsPhiloxReset && p.do_move != 0 && p.reset_flags == 0U)
-            { // okenv_rollout_random without device-side resetAgent: its launch-time switches as constants (-1 %)
-                countForm(h, OKENV_FORM_COOP_G64_RANDOM, p);
-                hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, false, false, false, 64, true>), grid, block, lds, h->stream, p, off, h->phase1_range);
-            }
-            else if (h->G == 64) // one agent per wave, the group width a compile-time constant (-1 % on 20-step launches)
-            {
-                countForm(h, OKENV_FORM_COOP_G64, p);
-                hipLaunchKernelGGL((okStepCoopKernel<kPolicyNone, false, false, false, 64>), grid, block, lds, h->stream, p, off, h->phase1_range);
-            }
-            else
-            {
-                countForm(h, OKENV_FORM_COOP, p);
-                hipLaunchKernelGGL(okStepCoopKernel<kPolicyNone>, grid, block, lds, h->stream, p, off, h->phase1_range);
-            }
-        }
-        else if (policy == kPolicyMlp)
-        {
-            countForm(h, OKENV_FORM_LDS_MLP, p);
-            hipLaunchKernelGGL((okStepKernel<kGridLds, kPolicyMlp>), grid, block, h->image_bytes, h->stream, p);
-        }
-        else
-        {
-            countForm(h, OKENV_FORM_LDS, p);
-            hipLaunchKernelGGL((okStepKernel<kGridLds, kPolicyNone>), grid, block, h->image_bytes, h->stream, p);
-        }
-        break;
-    case kGridGlobal:
-        if (policy == kPolicyMlp)
-        {
-            countForm(h, OKENV_FORM_GLOBAL_MLP, p);
-            hipLaunchKernelGGL((okStepKernel<kGridGlobal, kPolicyMlp>), grid, block, 0, h->stream, p);
-        }
-        else
-        {
-            countForm(h, OKENV_FORM_GLOBAL, p);
-            hipLaunchKernelGGL((okStepKernel<kGridGlobal, kPolicyNone>), grid, block, 0, h->stream, p);
-        }
-        break;
-    default:
-        if (policy == kPolicyMlp)
-        {
-            countForm(h, OKENV_FORM_BRUTE_MLP, p);
-            hipLaunchKernelGGL((okStepKernel<kGridBrute, kPolicyMlp>), grid, block, 0, h->stream, p);
-        }
-        else
-        {
-            countForm(h, OKENV_FORM_BRUTE, p);
-            hipLaunchKernelGGL((okStepKernel<kGridBrute, kPolicyNone>), grid, block, 0, h->stream, p);
-        }
-        break;
-    }
-    OK_HIP(h, hipGetLastError());
-    return endTiming(h, ev);
-}
-
-// Longest episode list the tail kernel (okStepTailKernel) takes on this handle: one round of workgroups -- as many per CU as
-// the LDS holds, times the device's compute units (256 on an MI355X in SPX mode; measured there, 32-ray MLP agents: 8.1 us per step up to 256 agents, 9.2 at 512 with two per CU, against
-// 11.2-11.8 for the cooperative kernel; a second round loses: 17 us) -- or OKENV_TAIL_MAX_AGENTS; 0: the tail kernel does not apply.
-long tailLimit(const okenv *h, const bool q_launch)
-{
-    if (h->grid_mode != kGridLds || !h->coop || h->tail_max_agents == 0)
-        return 0;
-    const unsigned lanes = static_cast<unsigned>(((h->R * kTailSplit + 63) / 64) * 64);
-    const size_t   lds   = h->image_bytes + 16U + sizeof(float) * kTailLdsFloats + (q_launch ? qLdsBytes(h) + sizeof(float) * kTailQFloats : 0U);
-    if (lanes > 512U || lds > kLdsBudget)
-        return 0;
-    const long fit = static_cast<long>(kLdsBudget / lds) * h->cus;
-    return h->tail_max_agents > 0 ? std::min<long>(h->tail_max_agents, fit) : fit;
-}
-
 // The step counter also lives on the device (it is the epoch of the auto-reset draws and must advance when a captured
 // graph of the step is replayed): okFinishLaunch at the end of the step kernels.
 int advanceStepCount(okenv *h, const int n_steps)
@@ -954,6 +1083,29 @@ int copyAny(okenv *h, void *dst, const void *src, const size_t bytes)
         return OKENV_OK;
     OK_HIP(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, h->stream));
     return OKENV_OK;
+}
+
+// The launch knobs as the environment sets them: the one place that reads them.
+OkKnobs readKnobs()
+{
+    OkKnobs k;
+    if (const char *e = std::getenv("OKENV_LANES_PER_AGENT"))
+        k.lanes_per_agent = std::atoi(e);
+    if (const char *e = std::getenv("OKENV_BLOCK_THREADS"))
+        k.block_threads = std::atol(e);
+    if (const char *e = std::getenv("OKENV_COOP"))
+        k.coop = std::atoi(e);
+    if (const char *e = std::getenv("OKENV_AGENTS_PER_BLOCK"))
+        k.agents_per_block = std::atoi(e);
+    if (const char *e = std::getenv("OKENV_TAIL_MAX_AGENTS"))
+        k.tail_max_agents = std::atoi(e);
+    if (const char *e = std::getenv("OKENV_PHASE1_RANGE"))
+        k.phase1_range = static_cast<float>(std::atof(e));
+    if (const char *e = std::getenv("OKENV_RESIDENT"))
+        k.resident = std::atoi(e);
+    if (const char *e = std::getenv("OKENV_FRONT_BACK"))
+        k.front_back = std::atoi(e);
+    return k;
 }
 } // namespace
 
@@ -996,64 +1148,27 @@ extern "C"
         std::unique_ptr<okenv, Destroy> hp(new okenv);
         okenv                          *h = hp.get();
         h->device                = device;
-        h->N                     = num_agents;
-        h->R                     = num_rays;
         h->S                     = num_segments;
         h->flags                 = flags;
         OK_HIP(nullptr, hipSetDevice(device));
         OK_HIP(nullptr, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
 
-        // lanes per agent: the fan's width rounded up to a power of two -- and more when the population is far too
-        // small to fill the machine: the spare lanes of an agent's group take intervals of its rays in phase 2, which
-        // shortens the dependent chain of a step (11.5-13 us instead of 15.6 us per step for RL-sized populations).
-        // Kept to half of the machine's lanes (compute units x 1024; the device is asked, an MI355X in CPX / DPX partition mode
-        // shows 32 / 128 of its 256 CUs) so that the waves of a CU do not start competing for issue.
-        {
-            int cus = 0;
-            OK_HIP(nullptr, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-            h->cus = cus > 0 ? cus : 256;
-        }
-        h->G = pow2ceil(num_rays) > 64 ? 64 : pow2ceil(num_rays);
-        const int natural_g = h->G;
-        while (h->G < 64 && static_cast<long>(num_agents) * (2L * h->G) <= 512L * h->cus)
-            h->G *= 2;
-        if (const char *env_g = std::getenv("OKENV_LANES_PER_AGENT"))
-        { // tuning knob: fold the fan over fewer lanes (ray r, r+G, r+2G, ... share a lane) or spread it over more
-            const int g = std::atoi(env_g);
-            if (g >= 1 && g <= 64 && (g & (g - 1)) == 0)
-                h->G = g;
-        }
-        // with spare lanes there is no phase 1: phase 2 cuts every ray into intervals from its origin on (a 4 px phase 1 in
-        // front of it cost a second walk set-up per step: 6.5 -> 5.2 us for one five-ray agent, 8.4 -> 7.0 us at 4096 x 5)
-        if (h->G > natural_g)
-            h->phase1_range = 0.F;
-        h->rays_per_lane = (num_rays + h->G - 1) / h->G;
+        // lanes per agent, phase 1 and the default cell edge; the device is asked for its compute units (an MI355X in CPX / DPX
+        // partition mode shows 32 / 128 of its 256 CUs)
+        const OkKnobs knobs = readKnobs();
+        int           cus   = 0;
+        OK_HIP(nullptr, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+        h->shape = okPlanLanes(num_agents, num_rays, cus > 0 ? cus : 256, knobs);
 
         // ---- grid ------------------------------------------------------------------------------------
         const OkSeg *segs = reinterpret_cast<const OkSeg *>(segments_xyxy);
         bool         fits = false;
-        // cell edge: 24 px when a wave holds one agent (all 64 rays leave one origin), 20 px when it holds several (measured:
-        // Silverstone / Spa x 64 rays 4 % faster at 24, Monza x 32 rays 6 % faster at 20)
-        // (round 3: 16-ray fans four to a wave -- BASELINE config 5 -- 24 px cells with a 32 px phase 1: 15.6 against 16.4 us per step)
-        const bool  narrow16     = h->G == 16 && h->rays_per_lane == 1;
-        // (wide fans, one agent per wave: 28 px since the front / back split halved the points per cell -- 9.5-10.0 us per C2 step at
-        // 28-30 px against 10.4 at 24 and 10.7 at 20, profiles/r4/front_back_ab.txt; 16-ray fans stay at 24, 32-ray fans at 20)
-        const bool  wide64       = h->G == 64 && h->rays_per_lane == 1 && num_rays > 32;
-        const float cell_default = wide64 ? 28.F : (narrow16 ? 24.F : OKGRID_DEFAULT_CELL);
-        if (narrow16)
-            h->phase1_range = 32.F;
-        h->grid = okBuildGridAuto(segs, static_cast<size_t>(num_segments), grid_cell > 0.F ? grid_cell : cell_default, kLdsBudget - kLdsReserve,
-                                  &fits, &h->poly);
-        if (flags & OKENV_FLAG_BRUTE_FORCE)
-            h->grid_mode = kGridBrute;
-        else if (!fits || (flags & OKENV_FLAG_FORCE_GLOBAL_GRID))
-            h->grid_mode = kGridGlobal;
-        else
-            h->grid_mode = kGridLds;
+        h->grid = okBuildGridAuto(segs, static_cast<size_t>(num_segments), grid_cell > 0.F ? grid_cell : h->shape.cell_default,
+                                  kLdsBudget - kLdsReserve, &fits, &h->poly);
+        okPlanGeometry(h->shape, flags, fits, knobs);
         // The front / back split (ok_grid.h): the outer boundary polylines in an image of their own, walked only by the rays that
         // need it.  OKENV_FRONT_BACK=0 keeps every launch on the combined image (ablation; same results).
-        const char *env_fb = std::getenv("OKENV_FRONT_BACK");
-        if (h->grid_mode == kGridLds && (env_fb == nullptr || std::atoi(env_fb) != 0))
+        if (h->shape.front_back)
         {
             auto classify = [&]() {
                 h->fbc = okClassifyFrontBack(segs, static_cast<size_t>(num_segments), h->grid, h->poly.max_seg_len);
@@ -1064,9 +1179,8 @@ extern "C"
             // workgroup, and the drivers hand a list over to it at up to two workgroups per CU -- which the two images allow only when
             // they fit the CU's LDS twice.  With a default cell edge the smallest of 20 / 24 / 28 / 32 px that manages it is taken
             // (larger cells, smaller images; the cooperative kernel's step time is flat over that range: profiles/r4/front_back_ab.txt).
-            const size_t tail_extra = 16U + sizeof(float) * kTailLdsFloats;
-            auto twice = [&]() { return 2U * (h->fbi.front.bytes.size() + h->fbi.back.bytes.size() + tail_extra) <= kLdsBudget; };
-            if (grid_cell <= 0.F && h->G == 32 && h->fbi.ok && !twice())
+            auto twice = [&]() { return 2U * okTailLdsBytes(h->fbi.front.bytes.size() + h->fbi.back.bytes.size(), false, 0U) <= kLdsBudget; };
+            if (grid_cell <= 0.F && h->shape.G == 32 && h->fbi.ok && !twice())
             {
                 const OkGridHost       grid0 = h->grid;
                 const OkPolyImage      poly0 = h->poly;
@@ -1103,29 +1217,29 @@ extern "C"
         if ((rc = devAlloc(h, &h->d_segs, static_cast<size_t>(num_segments))) != OKENV_OK)
             return fail(nullptr, rc, h->last_error);
         OK_HIP(nullptr, hipMemcpyAsync(h->d_segs, segs, sizeof(OkSeg) * num_segments, hipMemcpyHostToDevice, h->stream));
-        if (h->grid_mode == kGridLds)
+        if (h->shape.grid_mode == kGridLds)
         {
-            h->image_bytes                  = h->poly.bytes.size();
+            h->shape.image_bytes            = h->poly.bytes.size();
             const std::vector<uint8_t> &img = h->poly.bytes;
             uint8_t *dimg = nullptr;
-            if ((rc = devAlloc(h, &dimg, h->image_bytes)) != OKENV_OK)
+            if ((rc = devAlloc(h, &dimg, h->shape.image_bytes)) != OKENV_OK)
                 return fail(nullptr, rc, h->last_error);
             h->d_image = dimg;
-            OK_HIP(nullptr, hipMemcpyAsync(dimg, img.data(), h->image_bytes, hipMemcpyHostToDevice, h->stream));
+            OK_HIP(nullptr, hipMemcpyAsync(dimg, img.data(), h->shape.image_bytes, hipMemcpyHostToDevice, h->stream));
             // The front / back split (ok_grid.h; classified before the images were uploaded, above): its two images as one blob.
             if (h->fbi.ok && h->fbi.front.bytes.size() + h->fbi.back.bytes.size() <= kLdsBudget - kLdsReserve)
             {
-                h->fb_back_off = h->fbi.front.bytes.size(); // (a multiple of 16: both parts of an image are 16-byte aligned)
-                h->fb_bytes    = h->fb_back_off + h->fbi.back.bytes.size();
-                if ((rc = devAlloc(h, &h->d_image_fb, h->fb_bytes)) != OKENV_OK)
+                h->fb_back_off    = h->fbi.front.bytes.size(); // (a multiple of 16: both parts of an image are 16-byte aligned)
+                h->shape.fb_bytes = h->fb_back_off + h->fbi.back.bytes.size();
+                if ((rc = devAlloc(h, &h->d_image_fb, h->shape.fb_bytes)) != OKENV_OK)
                     return fail(nullptr, rc, h->last_error);
                 OK_HIP(nullptr, hipMemcpyAsync(h->d_image_fb, h->fbi.front.bytes.data(), h->fb_back_off, hipMemcpyHostToDevice, h->stream));
                 OK_HIP(nullptr, hipMemcpyAsync(h->d_image_fb + h->fb_back_off, h->fbi.back.bytes.data(), h->fbi.back.bytes.size(), hipMemcpyHostToDevice,
                                                h->stream));
-                h->fb_ok = true;
+                h->shape.fb_ok = true;
             }
             OK_HIP(nullptr, hipStreamSynchronize(h->stream));
-            const int lds_plain = static_cast<int>(h->image_bytes);
+            const int lds_plain = static_cast<int>(h->shape.image_bytes);
             OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepKernel<kGridLds, kPolicyNone>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds_plain));
             OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepKernel<kGridLds, kPolicyMlp>),
@@ -1163,9 +1277,9 @@ extern "C"
             OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepTailKernel<kPolicyQ, 0>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
             OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDebugCastKernel<kGridLds>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(h->image_bytes)));
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(h->shape.image_bytes)));
         }
-        else if (h->grid_mode == kGridGlobal)
+        else if (h->shape.grid_mode == kGridGlobal)
         {
             if ((rc = devAlloc(h, &h->d_refs32, h->grid.refs.size())) != OKENV_OK ||
                 (rc = devAlloc(h, &h->d_start, h->grid.start.size())) != OKENV_OK)
@@ -1189,54 +1303,8 @@ extern "C"
         OK_HIP(nullptr, hipMemcpyAsync(h->d_ray_deg, ray_angles_deg, 4U * num_rays, hipMemcpyHostToDevice, h->stream));
         h->host_ray_deg.assign(ray_angles_deg, ray_angles_deg + num_rays);
 
-        // ---- launch geometry -------------------------------------------------------------------------
-        // Spread small populations over the CUs: aim for a workgroup on every CU before growing them to 1024 lanes.
-        const long total_lanes = static_cast<long>(num_agents) * h->G;
-        long       per_block   = (total_lanes + h->cus - 1) / h->cus;
-        per_block              = ((per_block + 63) / 64) * 64;
-        // at least four waves per workgroup: with a handful of agents the launch is dominated by staging the ~70-90 KB track
-        // image into LDS, which a single wave does four times slower (waves without an agent leave right after it)
-        if (per_block < 256)
-            per_block = 256;
-        if (per_block > 1024)
-            per_block = 1024;
-        if (const char *env_bt = std::getenv("OKENV_BLOCK_THREADS"))
-        { // tuning knob: smaller workgroups (two per CU when the LDS image allows)
-            const long bt = std::atol(env_bt);
-            if (bt >= 64 && bt <= 1024 && bt % 64 == 0 && bt % h->G == 0)
-                per_block = bt;
-        }
-        h->block_threads = static_cast<int>(per_block);
-        h->grid_blocks   = static_cast<int>((total_lanes + per_block - 1) / per_block);
-        h->coop          = h->grid_mode == kGridLds && h->rays_per_lane == 1;
-        if (const char *env_coop = std::getenv("OKENV_COOP")) // tuning/ablation knob: 0 = every lane walks its own ray to the end
-            h->coop = h->coop && std::atoi(env_coop) != 0;
-        // up to one agent per CU with a wave each (the populations of the reference's applications: 1, 15, 30, 50): one agent per
-        // workgroup, i.e. per CU -- four such waves on one CU take 7.8 us for a step, one alone 6.0 us -- and three more waves
-        // that only help with the staging
-        h->agents_per_block = 0;
-        if (h->coop && h->G == 64 && num_agents <= h->cus && per_block == 256)
-            h->agents_per_block = 1;
-        if (const char *env_apb = std::getenv("OKENV_AGENTS_PER_BLOCK"))
-        { // tuning knob; 0 = dense
-            const int apb = std::atoi(env_apb);
-            if (h->coop && apb >= 0 && static_cast<long>(apb) * h->G <= per_block)
-                h->agents_per_block = apb;
-        }
-        if (h->agents_per_block > 0)
-            h->grid_blocks = (num_agents + h->agents_per_block - 1) / h->agents_per_block;
         if (const char *env_stall = std::getenv("OKENV_RESIDENT_STALL_US"))
             h->resident_stall_us = std::atoi(env_stall);
-        if (const char *env_res = std::getenv("OKENV_RESIDENT")) // 0: never keep the packed-step kernel resident, 1: from the first step on
-            h->resident_mode = std::atoi(env_res);
-        if (const char *env_tail = std::getenv("OKENV_TAIL_MAX_AGENTS")) // tuning / ablation knob; 0: never use the tail kernel
-            h->tail_max_agents = std::atoi(env_tail);
-        if (const char *env_t1 = std::getenv("OKENV_PHASE1_RANGE"))
-        {
-            const float t1 = static_cast<float>(std::atof(env_t1));
-            if (t1 >= 0.F) // 0: no phase 1
-                h->phase1_range = t1;
-        }
         OK_HIP(nullptr, hipStreamSynchronize(h->stream));
         *out = hp.release();
         return OKENV_OK;
@@ -1280,25 +1348,25 @@ extern "C"
     {
         if (!h || !out)
             return fail(h, OKENV_ERR_INVALID, "okenv_get_info: NULL argument");
-        out->num_agents      = h->N;
-        out->num_rays        = h->R;
+        out->num_agents      = h->shape.N;
+        out->num_rays        = h->shape.R;
         out->num_segments    = h->S;
-        out->compute_units   = h->cus;
-        out->front_back_bytes = h->fb_ok ? static_cast<int32_t>(h->fb_bytes) : 0;
-        out->back_segments    = h->fb_ok ? static_cast<int32_t>(h->fbc.n_back) : 0;
+        out->compute_units   = h->shape.cus;
+        out->front_back_bytes = h->shape.fb_ok ? static_cast<int32_t>(h->shape.fb_bytes) : 0;
+        out->back_segments    = h->shape.fb_ok ? static_cast<int32_t>(h->fbc.n_back) : 0;
         out->grid_nx         = h->grid.g.nx;
         out->grid_ny         = h->grid.g.ny;
         out->grid_cell       = h->grid.g.cell;
         out->grid_refs       = static_cast<int32_t>(h->grid.refs.size());
-        out->grid_in_lds     = h->grid_mode == kGridLds ? 1 : 0;
-        out->lds_bytes       = h->grid_mode == kGridLds ? static_cast<int32_t>(h->image_bytes) : 0;
-        out->block_threads   = h->block_threads;
-        out->grid_blocks     = h->grid_blocks;
-        out->agents_per_block      = h->coop ? h->agents_per_block : 0;
+        out->grid_in_lds     = h->shape.grid_mode == kGridLds ? 1 : 0;
+        out->lds_bytes       = h->shape.grid_mode == kGridLds ? static_cast<int32_t>(h->shape.image_bytes) : 0;
+        out->block_threads   = h->shape.block_threads;
+        out->grid_blocks     = h->shape.grid_blocks;
+        out->agents_per_block      = h->shape.coop ? h->shape.agents_per_block : 0;
         out->packed_resident       = h->resident ? 1 : 0;
         out->packed_resident_steps = h->resident_steps;
         out->packed_fallbacks      = h->resident_fallbacks;
-        out->lanes_per_agent = h->G;
+        out->lanes_per_agent = h->shape.G;
         out->device          = h->device;
         return OKENV_OK;
     }
@@ -1415,7 +1483,7 @@ extern "C"
     {
         if (!h || !v)
             return fail(h, OKENV_ERR_INVALID, "state view is NULL");
-        const size_t N = h->N;
+        const size_t N = h->shape.N;
         auto        &s = h->st;
         struct Item
         {
@@ -1462,7 +1530,7 @@ extern "C"
         if (!h || !throttle || !steer)
             return fail(h, OKENV_ERR_INVALID, "okenv_set_actions: NULL argument");
         int rc;
-        if ((rc = copyAny(h, h->st.thr, throttle, 4U * h->N)) || (rc = copyAny(h, h->st.steer, steer, 4U * h->N)))
+        if ((rc = copyAny(h, h->st.thr, throttle, 4U * h->shape.N)) || (rc = copyAny(h, h->st.steer, steer, 4U * h->shape.N)))
             return rc;
         OK_HIP(h, hipStreamSynchronize(h->stream));
         return OKENV_OK;
@@ -1491,7 +1559,7 @@ extern "C"
         OK_HIP(h, hipMemcpyAsync(b + 12U * n, rot_deg, 4U * n, hipMemcpyHostToDevice, h->stream));
         hipLaunchKernelGGL(okResetKernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->st, reinterpret_cast<const int32_t *>(b),
                            reinterpret_cast<const float *>(b + 4U * n), reinterpret_cast<const float *>(b + 8U * n),
-                           reinterpret_cast<const float *>(b + 12U * n), n, h->N);
+                           reinterpret_cast<const float *>(b + 12U * n), n, h->shape.N);
         OK_HIP(h, hipGetLastError());
         OK_HIP(h, hipStreamSynchronize(h->stream));
         return OKENV_OK;
@@ -1538,7 +1606,7 @@ extern "C"
         if (!h || n < 0)
             return fail(h, OKENV_ERR_INVALID, "okenv_reset_random: bad argument");
         if (!idx)
-            n = h->N;
+            n = h->shape.N;
         if (n == 0)
             return OKENV_OK;
         int rc = checkResetInputs(h, flags, "okenv_reset_random");
@@ -1555,7 +1623,7 @@ extern "C"
             didx = static_cast<int32_t *>(sp);
             OK_HIP(h, hipMemcpyAsync(didx, idx, 4U * static_cast<size_t>(n), hipMemcpyDefault, h->stream));
         }
-        hipLaunchKernelGGL(okResetRandomKernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->st, didx, n, h->N, flags, seed, epoch,
+        hipLaunchKernelGGL(okResetRandomKernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->st, didx, n, h->shape.N, flags, seed, epoch,
                            agent_base, h->d_cx, h->d_cy, h->d_chead, h->d_lane_l, h->d_lane_r, h->P);
         OK_HIP(h, hipGetLastError());
         if (didx)
@@ -1637,7 +1705,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || !out_xy)
             return fail(h, OKENV_ERR_INVALID, "okenv_get_hits: NULL argument");
-        const size_t       NR = static_cast<size_t>(h->N) * h->R;
+        const size_t       NR = static_cast<size_t>(h->shape.N) * h->shape.R;
         std::vector<float> rx(NR), ry(NR);
         int                rc;
         if ((rc = copyAny(h, rx.data(), h->st.rel_x, 4U * NR)) || (rc = copyAny(h, ry.data(), h->st.rel_y, 4U * NR)))
@@ -1662,12 +1730,12 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || !out)
             return fail(h, OKENV_ERR_INVALID, "okenv_get_flags: NULL argument");
-        std::vector<uint8_t> c(h->N), t(h->N);
+        std::vector<uint8_t> c(h->shape.N), t(h->shape.N);
         int                  rc;
-        if ((rc = copyAny(h, c.data(), h->st.crashed, h->N)) || (rc = copyAny(h, t.data(), h->st.timed_out, h->N)))
+        if ((rc = copyAny(h, c.data(), h->st.crashed, h->shape.N)) || (rc = copyAny(h, t.data(), h->st.timed_out, h->shape.N)))
             return rc;
         OK_HIP(h, hipStreamSynchronize(h->stream));
-        for (int i = 0; i < h->N; ++i)
+        for (int i = 0; i < h->shape.N; ++i)
             out[i] = static_cast<uint8_t>((c[i] ? 1 : 0) | (t[i] ? 2 : 0));
         return OKENV_OK;
     }
@@ -1694,7 +1762,7 @@ extern "C"
         if (!h || !in || !out || !sensor_hits_xy)
             return fail(h, OKENV_ERR_INVALID, "okenv_step_packed: NULL argument");
         OK_HIP(h, hipSetDevice(h->device));
-        const size_t N = static_cast<size_t>(h->N), NR = N * static_cast<size_t>(h->R);
+        const size_t N = static_cast<size_t>(h->shape.N), NR = N * static_cast<size_t>(h->shape.R);
         const size_t rec_bytes = N * sizeof(okenv_agent_record), hit_bytes = NR * 2U * sizeof(float);
         // mapped host memory: [ in records | out records | hits | completion word | one 64-byte slot per agent (resident kernel) ]
         const size_t out_off   = (rec_bytes + 255U) & ~static_cast<size_t>(255U);
@@ -1720,7 +1788,7 @@ extern "C"
             h->stage_slots_off = slots_off;
         }
         uint8_t *hs = static_cast<uint8_t *>(h->h_stage), *ds = static_cast<uint8_t *>(h->d_stage);
-        if (h->grid_mode == kGridLds && h->coop)
+        if (h->shape.grid_mode == kGridLds && h->shape.coop)
         { // ONE kernel: it reads the records from, and writes records and sensor_hits_ to, the mapped host buffer
             uint8_t     *hm = static_cast<uint8_t *>(h->h_stage_device);
             OkStepParams p  = baseParams(h);
@@ -1734,7 +1802,7 @@ extern "C"
             // steps that follow each other closely are served by a resident kernel (see startResident)
             const auto   t_in  = std::chrono::steady_clock::now();
             const bool   quick = h->packed_seq != 0U && std::chrono::duration<double, std::micro>(t_in - h->packed_last_end).count() < kResidentGapUs;
-            const bool eligible = h->resident_mode != 0 && h->agents_per_block == 1 && h->N <= kResidentMaxAgents && h->own_stream && !h->timing &&
+            const bool eligible = okResidentShape(h->shape) && h->own_stream && !h->timing &&
                                   (h->reset_flags & kAutoResetOn) == 0U && flags == OKENV_PACKED_WITH_STATS;
             // (a run of quick steps counts only while every one of them is of the kind the resident kernel serves: a caller that
             // alternates step() and checkCollision() must not start and stop a kernel on every other call)
@@ -1746,7 +1814,7 @@ extern "C"
                     return src;
             }
             const bool was_resident = h->resident;
-            if (!h->resident && eligible && (h->resident_mode == 1 || h->packed_streak >= h->resident_need))
+            if (!h->resident && eligible && (h->shape.resident_mode == 1 || h->packed_streak >= h->resident_need))
             {
                 p.slots          = reinterpret_cast<const uint32_t *>(hm + slots_off);
                 p.idle_ticks     = kResidentIdleTicks;
@@ -1801,7 +1869,7 @@ extern "C"
         OK_HIP(h, hipMemcpyAsync(ds, hs, rec_bytes, hipMemcpyHostToDevice, h->stream));
         const unsigned blocks_n = static_cast<unsigned>((N + 255U) / 256U);
         hipLaunchKernelGGL(okUnpackRecordsKernel, dim3(blocks_n), dim3(256), 0, h->stream, h->st,
-                           reinterpret_cast<const okenv_agent_record *>(ds), h->N, (flags & OKENV_PACKED_WITH_STATS) ? 1 : 0);
+                           reinterpret_cast<const okenv_agent_record *>(ds), h->shape.N, (flags & OKENV_PACKED_WITH_STATS) ? 1 : 0);
         OkStepParams p = baseParams(h);
         if (flags & OKENV_PACKED_COLLIDE_ONLY)
         {
@@ -1815,7 +1883,7 @@ extern "C"
             advanceStepCount(h, 1);
         const size_t threads = NR > N ? NR : N;
         hipLaunchKernelGGL(okPackRecordsKernel, dim3(static_cast<unsigned>((threads + 255U) / 256U)), dim3(256), 0, h->stream, h->st,
-                           reinterpret_cast<okenv_agent_record *>(ds + out_off), reinterpret_cast<float *>(ds + hit_off), h->N, h->R);
+                           reinterpret_cast<okenv_agent_record *>(ds + out_off), reinterpret_cast<float *>(ds + hit_off), h->shape.N, h->shape.R);
         OK_HIP(h, hipGetLastError());
         OK_HIP(h, hipMemcpyAsync(hs + out_off, ds + out_off, (hit_off - out_off) + hit_bytes, hipMemcpyDeviceToHost, h->stream));
         OK_HIP(h, hipStreamSynchronize(h->stream));
@@ -1882,8 +1950,8 @@ extern "C"
         if (h->P <= 0)
             return fail(h, OKENV_ERR_STATE, "okenv_init_bench_state: call okenv_set_centerline first");
         OK_HIP(h, hipSetDevice(h->device));
-        hipLaunchKernelGGL(okInitBenchKernel, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->st, h->d_cx, h->d_cy, h->d_chead,
-                           h->P, h->N, h->R, agent_base, mode);
+        hipLaunchKernelGGL(okInitBenchKernel, dim3((h->shape.N + 255) / 256), dim3(256), 0, h->stream, h->st, h->d_cx, h->d_cy, h->d_chead,
+                           h->P, h->shape.N, h->shape.R, agent_base, mode);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -1900,7 +1968,7 @@ extern "C"
         if (!agents && !qy) // every argument is validated before anything is allocated
             return fail(h, OKENV_ERR_INVALID, "okenv_nearest_track_idx: qy is NULL");
         if (agents)
-            n = h->N;
+            n = h->shape.N;
         if (n <= 0)
             return OKENV_OK;
         void     *sp  = nullptr; // [ out: n x i32 | queries: 2n x f32 ]
@@ -1936,7 +2004,7 @@ extern "C"
             return fail(h, OKENV_ERR_STATE, "okenv_tracker_create: call okenv_set_centerline first");
         OK_HIP(h, hipSetDevice(h->device));
         {
-            const size_t N = static_cast<size_t>(h->N);
+            const size_t N = static_cast<size_t>(h->shape.N);
             int          rc;
             if ((rc = devEnsure(h, &h->tracker.prev_idx, N)) || (rc = devEnsure(h, &h->tracker.fitness, N)) ||
                 (rc = devEnsure(h, &h->tracker.reward, N)) || (rc = devEnsure(h, &h->tracker.ep_steps, N)) ||
@@ -1954,9 +2022,9 @@ extern "C"
         if (h->tracker_kind < 0)
             return fail(h, OKENV_ERR_STATE, std::string(who) + ": call okenv_tracker_create first");
         OK_HIP(h, hipSetDevice(h->device));
-        const long threads = static_cast<long>(h->N) * (h->tracker_kind == kRewardProgress ? kNearestLanes : 1);
+        const long threads = static_cast<long>(h->shape.N) * (h->tracker_kind == kRewardProgress ? kNearestLanes : 1);
         hipLaunchKernelGGL(okTrackerKernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, h->stream, h->st, h->d_cx, h->d_cy,
-                           h->P, h->tracker, h->N, h->tracker_kind, begin);
+                           h->P, h->tracker, h->shape.N, h->tracker_kind, begin);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -1991,13 +2059,13 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || hidden < 2 || hidden > OK_CTRL_MAX_HIDDEN || (hidden & 1) != 0)
             return fail(h, OKENV_ERR_INVALID, "okenv_controller_create: hidden width must be even and in [2, 64]");
-        if (h->R > 64)
+        if (h->shape.R > 64)
             return fail(h, OKENV_ERR_INVALID, "okenv_controller_create: at most 64 rays");
         OK_HIP(h, hipSetDevice(h->device));
-        const int np = ok_controller_num_params(h->R, hidden, 2);
+        const int np = ok_controller_num_params(h->shape.R, hidden, 2);
         if (!h->d_ctrl_params || np != h->ctrl_num_params)
         {
-            const int rc = devAlloc(h, &h->d_ctrl_params, static_cast<size_t>(h->N) * np);
+            const int rc = devAlloc(h, &h->d_ctrl_params, static_cast<size_t>(h->shape.N) * np);
             if (rc != OKENV_OK)
                 return rc;
         }
@@ -2023,7 +2091,7 @@ extern "C"
         if (ctrlEpisodeRunning(h))
             return fail(h, OKENV_ERR_STATE, "okenv_controller_set_params: a controller episode is running; okenv_episode_end first");
         OK_HIP(h, hipSetDevice(h->device));
-        return copyAny(h, h->d_ctrl_params, params, sizeof(float) * static_cast<size_t>(h->N) * h->ctrl_num_params);
+        return copyAny(h, h->d_ctrl_params, params, sizeof(float) * static_cast<size_t>(h->shape.N) * h->ctrl_num_params);
     }
 
     int okenv_controller_act(okenv_t h, float throttle, float steering_scale)
@@ -2035,16 +2103,16 @@ extern "C"
             return fail(h, OKENV_ERR_STATE, "okenv_controller_act: call okenv_controller_create first");
         OK_HIP(h, hipSetDevice(h->device));
         const int      lanes  = h->ctrl_hidden <= 16 ? 16 : (h->ctrl_hidden <= 32 ? 32 : 64);
-        const unsigned blocks = static_cast<unsigned>((static_cast<long>(h->N) * lanes + 255) / 256);
+        const unsigned blocks = static_cast<unsigned>((static_cast<long>(h->shape.N) * lanes + 255) / 256);
         if (lanes == 16)
-            hipLaunchKernelGGL(okControllerKernel<16>, dim3(blocks), dim3(256), 0, h->stream, h->st, h->d_ctrl_params, h->ctrl_num_params, h->N,
-                               h->R, h->ctrl_hidden, throttle, steering_scale);
+            hipLaunchKernelGGL(okControllerKernel<16>, dim3(blocks), dim3(256), 0, h->stream, h->st, h->d_ctrl_params, h->ctrl_num_params, h->shape.N,
+                               h->shape.R, h->ctrl_hidden, throttle, steering_scale);
         else if (lanes == 32)
-            hipLaunchKernelGGL(okControllerKernel<32>, dim3(blocks), dim3(256), 0, h->stream, h->st, h->d_ctrl_params, h->ctrl_num_params, h->N,
-                               h->R, h->ctrl_hidden, throttle, steering_scale);
+            hipLaunchKernelGGL(okControllerKernel<32>, dim3(blocks), dim3(256), 0, h->stream, h->st, h->d_ctrl_params, h->ctrl_num_params, h->shape.N,
+                               h->shape.R, h->ctrl_hidden, throttle, steering_scale);
         else
-            hipLaunchKernelGGL(okControllerKernel<64>, dim3(blocks), dim3(256), 0, h->stream, h->st, h->d_ctrl_params, h->ctrl_num_params, h->N,
-                               h->R, h->ctrl_hidden, throttle, steering_scale);
+            hipLaunchKernelGGL(okControllerKernel<64>, dim3(blocks), dim3(256), 0, h->stream, h->st, h->d_ctrl_params, h->ctrl_num_params, h->shape.N,
+                               h->shape.R, h->ctrl_hidden, throttle, steering_scale);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -2056,18 +2124,18 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_expert_create: NULL handle");
-        if (const char *why = okExpertCheckParams(params, h->R))
+        if (const char *why = okExpertCheckParams(params, h->shape.R))
             return fail(h, OKENV_ERR_INVALID, std::string("okenv_expert_create: ") + why);
         if (h->P <= 0)
             return fail(h, OKENV_ERR_STATE, "okenv_expert_create: call okenv_set_centerline first");
         OK_HIP(h, hipSetDevice(h->device));
-        int rc = devEnsure(h, &h->d_expert_tab, 2U * static_cast<size_t>(h->R));
+        int rc = devEnsure(h, &h->d_expert_tab, 2U * static_cast<size_t>(h->shape.R));
         if (rc != OKENV_OK || (rc = buildCenterlineBuckets(h)) != OKENV_OK)
             return rc;
         std::vector<double> c, s;
-        okExpertRayTables(h->host_ray_deg.data(), h->R, c, s);
-        OK_HIP(h, hipMemcpyAsync(h->d_expert_tab, c.data(), 8U * static_cast<size_t>(h->R), hipMemcpyHostToDevice, h->stream));
-        OK_HIP(h, hipMemcpyAsync(h->d_expert_tab + h->R, s.data(), 8U * static_cast<size_t>(h->R), hipMemcpyHostToDevice, h->stream));
+        okExpertRayTables(h->host_ray_deg.data(), h->shape.R, c, s);
+        OK_HIP(h, hipMemcpyAsync(h->d_expert_tab, c.data(), 8U * static_cast<size_t>(h->shape.R), hipMemcpyHostToDevice, h->stream));
+        OK_HIP(h, hipMemcpyAsync(h->d_expert_tab + h->shape.R, s.data(), 8U * static_cast<size_t>(h->shape.R), hipMemcpyHostToDevice, h->stream));
         OK_HIP(h, hipStreamSynchronize(h->stream)); // the tables are locals
         h->expert    = *params;
         h->expert_ok = true;
@@ -2087,8 +2155,8 @@ extern "C"
         OK_HIP(h, hipSetDevice(h->device));
         OkExpertParams p{};
         p.st       = h->st;
-        p.N        = h->N;
-        p.R        = h->R;
+        p.N        = h->shape.N;
+        p.R        = h->shape.R;
         p.P        = h->P;
         p.cx       = h->d_cx;
         p.cy       = h->d_cy;
@@ -2096,13 +2164,13 @@ extern "C"
         p.cl_idx   = h->cl_dirty ? nullptr : h->d_cl_idx;
         p.geom     = h->grid.g;
         p.ray_cos  = h->d_expert_tab;
-        p.ray_sin  = h->d_expert_tab + h->R;
+        p.ray_sin  = h->d_expert_tab + h->shape.R;
         p.first    = h->host_ray_deg.front();
         p.last     = h->host_ray_deg.back();
         p.ep       = h->expert;
         if (rec != nullptr)
             p.rec = *rec;
-        const unsigned blocks = static_cast<unsigned>((static_cast<long>(h->N) * kExpertLanes + 255) / 256);
+        const unsigned blocks = static_cast<unsigned>((static_cast<long>(h->shape.N) * kExpertLanes + 255) / 256);
         hipLaunchKernelGGL(okExpertKernel, dim3(blocks), dim3(256), 0, h->stream, p);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
@@ -2150,13 +2218,13 @@ extern "C"
             return fail(h, OKENV_ERR_STATE, "okenv_rollout_controller: call okenv_controller_create first");
         if (h->tracker_kind < 0)
             return fail(h, OKENV_ERR_STATE, "okenv_rollout_controller: call okenv_tracker_create first");
-        if (h->grid_mode != kGridLds || !h->coop || h->rays_per_lane != 1 || h->G < 8)
+        if (h->shape.grid_mode != kGridLds || !h->shape.coop || h->shape.rays_per_lane != 1 || h->shape.G < 8)
             return fail(h, OKENV_ERR_STATE, "okenv_rollout_controller: needs the LDS form of the step kernel with at most 64 rays "
                                             "(use okenv_controller_act + okenv_step + okenv_tracker_update)");
-        if (h->ctrl_hidden > kCtrlUnitsPerLane * h->G)
+        if (h->ctrl_hidden > kCtrlUnitsPerLane * h->shape.G)
             return fail(h, OKENV_ERR_STATE, "okenv_rollout_controller: the hidden layer is too wide for this fan's lane groups (hidden <= 4 x lanes per agent); "
                                             "use okenv_controller_act + okenv_step + okenv_tracker_update");
-        if (coopLdsBytes(h) + qLdsBytes(h) > kLdsBudget)
+        if (okCoopLdsBytes(h->shape.image_bytes) + qLdsBytes(h) > kLdsBudget)
             return fail(h, OKENV_ERR_STATE, "okenv_rollout_controller: track image + centre line do not fit the CU's LDS");
         if (n_steps == 0)
             return OKENV_OK;
@@ -2174,7 +2242,7 @@ extern "C"
             // for crashed agents, so its bookkeeping would fall behind the per-step loop's)
             if (h->tracker_kind != kRewardProgress)
                 return fail(h, OKENV_ERR_STATE, "okenv_rollout_controller: inside an episode the bookkeeping must be OKENV_REWARD_PROGRESS");
-            const int prc = prelistEpisode(h, kPolicyCtrl);
+            const int prc = prelistEpisode(h, kActionsController);
             if (prc != OKENV_OK)
                 return prc;
             h->ep_kind = kPolicyCtrl;
@@ -2199,26 +2267,26 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || hidden < 1 || hidden > OK_MLP_HID_PAD)
             return fail(h, OKENV_ERR_INVALID, "okenv_policy_mlp_create: hidden width must be in [1, 32]");
-        if (h->rays_per_lane != 1 || h->R < 5 || h->G < 8)
+        if (h->shape.rays_per_lane != 1 || h->shape.R < 5 || h->shape.G < 8)
             return fail(h, OKENV_ERR_INVALID, "okenv_policy_mlp_create: the fused policy needs 5 <= rays <= 64");
         OK_HIP(h, hipSetDevice(h->device));
-        const size_t total = static_cast<size_t>(h->N) * OK_MLP_WEIGHTS(h->R);
+        const size_t total = static_cast<size_t>(h->shape.N) * OK_MLP_WEIGHTS(h->shape.R);
         int          rc;
         // (d_mlp_w, which the other entry points take as "a policy exists", comes last)
-        if ((rc = devEnsure(h, &h->d_mlp_w_new, total)) || (rc = devEnsure(h, &h->d_score, static_cast<size_t>(h->N))) ||
-            (rc = devEnsure(h, &h->d_nearest, static_cast<size_t>(h->N))) || (rc = devEnsure(h, &h->d_parents, 16U)) ||
+        if ((rc = devEnsure(h, &h->d_mlp_w_new, total)) || (rc = devEnsure(h, &h->d_score, static_cast<size_t>(h->shape.N))) ||
+            (rc = devEnsure(h, &h->d_nearest, static_cast<size_t>(h->shape.N))) || (rc = devEnsure(h, &h->d_parents, 16U)) ||
             (rc = devEnsure(h, &h->d_parent_score, 16U)) || (rc = devEnsure(h, &h->d_alive, 4U)) || (rc = devEnsure(h, &h->d_mlp_w, total)))
             return rc;
         h->mlp_hidden = hidden;
-        hipLaunchKernelGGL(okGaInitWeightsKernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, h->stream, h->d_mlp_w, h->N,
-                           h->R, hidden, seed, agent_base);
+        hipLaunchKernelGGL(okGaInitWeightsKernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, h->stream, h->d_mlp_w, h->shape.N,
+                           h->shape.R, hidden, seed, agent_base);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
 
     int32_t okenv_policy_mlp_weights_per_agent(okenv_t h)
     {
-        return h ? OK_MLP_WEIGHTS(h->R) : 0;
+        return h ? OK_MLP_WEIGHTS(h->shape.R) : 0;
     }
 
     int okenv_policy_mlp_get_weights(okenv_t h, float *out)
@@ -2226,7 +2294,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || !out || !h->d_mlp_w)
             return fail(h, OKENV_ERR_STATE, "okenv_policy_mlp_get_weights: no policy");
-        int rc = copyAny(h, out, h->d_mlp_w, sizeof(float) * static_cast<size_t>(h->N) * OK_MLP_WEIGHTS(h->R));
+        int rc = copyAny(h, out, h->d_mlp_w, sizeof(float) * static_cast<size_t>(h->shape.N) * OK_MLP_WEIGHTS(h->shape.R));
         if (rc != OKENV_OK)
             return rc;
         OK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2240,7 +2308,7 @@ extern "C"
             dropEpisode(h);
         if (!h || !in || !h->d_mlp_w)
             return fail(h, OKENV_ERR_STATE, "okenv_policy_mlp_set_weights: no policy");
-        int rc = copyAny(h, h->d_mlp_w, in, sizeof(float) * static_cast<size_t>(h->N) * OK_MLP_WEIGHTS(h->R));
+        int rc = copyAny(h, h->d_mlp_w, in, sizeof(float) * static_cast<size_t>(h->shape.N) * OK_MLP_WEIGHTS(h->shape.R));
         if (rc != OKENV_OK)
             return rc;
         OK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2262,7 +2330,7 @@ extern "C"
                 return fail(h, OKENV_ERR_STATE, "okenv_rollout_policy: the running episode belongs to another rollout (okenv_rollout_q / _controller)");
             if ((h->reset_flags & kAutoResetOn) != 0U)
                 return fail(h, OKENV_ERR_STATE, "okenv_rollout_policy: episodes need auto-reset off");
-            const int prc = prelistEpisode(h, kPolicyMlp);
+            const int prc = prelistEpisode(h, kActionsMlpPolicy);
             if (prc != OKENV_OK)
                 return prc;
             h->ep_kind = kPolicyMlp;
@@ -2286,14 +2354,14 @@ extern "C"
         if ((h->reset_flags & kAutoResetOn) != 0U)
             return fail(h, OKENV_ERR_STATE, "okenv_episode_begin: episodes need auto-reset off (a crashed agent stays crashed until the caller resets it)");
         OK_HIP(h, hipSetDevice(h->device));
-        const size_t N = static_cast<size_t>(h->N);
+        const size_t N = static_cast<size_t>(h->shape.N);
         int          rc;
         if ((rc = devEnsure(h, &h->d_settled, N)) || (rc = devEnsure(h, &h->d_crash_step, N)) || (rc = devEnsure(h, &h->d_crash_thr, N)) ||
             (rc = devEnsure(h, &h->d_crash_steer, N)) || (rc = devEnsure(h, &h->d_active, N)) || (rc = devEnsure(h, &h->d_ep_counts, 2U)) ||
             (rc = devEnsure(h, &h->d_ep_out, 2U)) || (rc = devEnsure(h, &h->d_live, 1U)) || (rc = devEnsure(h, &h->d_q_next_state, N)))
             return rc;
-        hipLaunchKernelGGL(okEpisodeBeginKernel, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->st.crashed, h->d_settled, h->d_crash_step,
-                           h->d_live, h->N);
+        hipLaunchKernelGGL(okEpisodeBeginKernel, dim3((h->shape.N + 255) / 256), dim3(256), 0, h->stream, h->st.crashed, h->d_settled, h->d_crash_step,
+                           h->d_live, h->shape.N);
         OK_HIP(h, hipGetLastError());
         h->episode    = true;
         h->n_active   = -1;
@@ -2309,7 +2377,7 @@ extern "C"
         if (!h || !h->episode)
             return fail(h, OKENV_ERR_STATE, "okenv_episode_compact: no episode is running (okenv_episode_begin)");
         OK_HIP(h, hipSetDevice(h->device));
-        hipLaunchKernelGGL(okEpisodeCompactKernel, dim3(1), dim3(1024), 0, h->stream, h->d_settled, h->st.crashed, h->N, h->d_active, h->d_ep_counts);
+        hipLaunchKernelGGL(okEpisodeCompactKernel, dim3(1), dim3(1024), 0, h->stream, h->d_settled, h->st.crashed, h->shape.N, h->d_active, h->d_ep_counts);
         OK_HIP(h, hipGetLastError());
         int32_t counts[2] = {0, 0};
         OK_HIP(h, hipMemcpyAsync(counts, h->d_ep_counts, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
@@ -2330,7 +2398,7 @@ extern "C"
             return fail(h, OKENV_ERR_INVALID, "okenv_episode_tail_limit: NULL argument");
         const bool q    = h->ep_kind == kPolicyQ || (h->ep_kind == 0 && h->d_q_table != nullptr && h->d_mlp_w == nullptr);
         const bool ctrl = h->ep_kind == kPolicyCtrl || (h->ep_kind == 0 && h->d_ctrl_params != nullptr && h->d_mlp_w == nullptr && h->d_q_table == nullptr);
-        *out            = ctrl ? 0 : static_cast<int32_t>(tailLimit(h, q)); // (the controller rollout has no one-agent-per-workgroup form)
+        *out            = ctrl ? 0 : static_cast<int32_t>(okTailLimit(h->shape, q, qLdsBytes(h))); // (the controller rollout has no one-agent-per-workgroup form)
         return OKENV_OK;
     }
 
@@ -2340,16 +2408,16 @@ extern "C"
         if (!h || !h->episode)
             return fail(h, OKENV_ERR_STATE, "okenv_episode_end: no episode is running (okenv_episode_begin)");
         OK_HIP(h, hipSetDevice(h->device));
-        const unsigned blocks = static_cast<unsigned>((h->N + 255) / 256);
-        hipLaunchKernelGGL(okEpisodeEndKernel, dim3(1), dim3(1024), 0, h->stream, h->st.crashed, h->d_crash_step, h->N, h->ep_steps, h->d_ep_out);
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + 255) / 256);
+        hipLaunchKernelGGL(okEpisodeEndKernel, dim3(1), dim3(1024), 0, h->stream, h->st.crashed, h->d_crash_step, h->shape.N, h->ep_steps, h->d_ep_out);
         if (h->ep_kind == kPolicyMlp || h->ep_kind == kPolicyCtrl)
             hipLaunchKernelGGL(okEpisodeFixupKernel, dim3(blocks), dim3(256), 0, h->stream, h->st, h->d_crash_step, h->d_crash_thr, h->d_crash_steer,
-                               h->d_ep_out, h->N);
+                               h->d_ep_out, h->shape.N);
         else if (h->ep_kind == kPolicyQ)
-            hipLaunchKernelGGL(okQSettleKernel, dim3(static_cast<unsigned>((static_cast<long>(h->N) * kSettleLanes + 255) / 256)), dim3(256), 0,
+            hipLaunchKernelGGL(okQSettleKernel, dim3(static_cast<unsigned>((static_cast<long>(h->shape.N) * kSettleLanes + 255) / 256)), dim3(256), 0,
                                h->stream, h->st, h->d_q_table, h->d_q_state, h->d_q_action,
-                               h->d_q_next_state, h->d_crash_step, h->d_ep_out, h->N, h->ep_q_seed, h->ep_q_agent_base, h->ep_q_step_base,
-                               h->ep_q_epsilon, h->R, h->q_ray[0], h->q_ray[1], h->q_ray[2], h->q_ray[3], h->q_ray[4]);
+                               h->d_q_next_state, h->d_crash_step, h->d_ep_out, h->shape.N, h->ep_q_seed, h->ep_q_agent_base, h->ep_q_step_base,
+                               h->ep_q_epsilon, h->shape.R, h->q_ray[0], h->q_ray[1], h->q_ray[2], h->q_ray[3], h->q_ray[4]);
         OK_HIP(h, hipGetLastError());
         uint32_t           out[2] = {0U, 0U};
         unsigned long long live   = 0ULL;
@@ -2382,7 +2450,7 @@ extern "C"
             d = h->d_alive;
         }
         OK_HIP(h, hipMemsetAsync(d, 0, sizeof(int), h->stream));
-        hipLaunchKernelGGL(okAliveCountKernel, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->st.crashed, h->N, d);
+        hipLaunchKernelGGL(okAliveCountKernel, dim3((h->shape.N + 255) / 256), dim3(256), 0, h->stream, h->st.crashed, h->shape.N, d);
         OK_HIP(h, hipGetLastError());
         OK_HIP(h, hipMemcpyAsync(out, d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         OK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2402,7 +2470,7 @@ extern "C"
         int *d = static_cast<int *>(sp);
         OK_HIP(h, hipMemsetAsync(d, 0, 2U * sizeof(int), h->stream));
         const OkGridGeom &g = h->grid.g;
-        hipLaunchKernelGGL(okOffGridCountKernel, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->st.pos_x, h->st.pos_y, h->st.crashed, h->N,
+        hipLaunchKernelGGL(okOffGridCountKernel, dim3((h->shape.N + 255) / 256), dim3(256), 0, h->stream, h->st.pos_x, h->st.pos_y, h->st.crashed, h->shape.N,
                            g.x0, g.y0, g.x1, g.y1, d);
         OK_HIP(h, hipGetLastError());
         int host[2] = {0, 0};
@@ -2423,7 +2491,7 @@ extern "C"
         if (!h)
             return OKENV_ERR_INVALID;
         OK_HIP(h, hipSetDevice(h->device));
-        hipLaunchKernelGGL(okResetAllKernel, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->st, x, y, rot_deg, h->N);
+        hipLaunchKernelGGL(okResetAllKernel, dim3((h->shape.N + 255) / 256), dim3(256), 0, h->stream, h->st, x, y, rot_deg, h->shape.N);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -2436,13 +2504,13 @@ extern "C"
         if (!h->d_mlp_w || h->P <= 0)
             return fail(h, OKENV_ERR_STATE, "okenv_ga_scores: needs okenv_policy_mlp_create and okenv_set_centerline");
         OK_HIP(h, hipSetDevice(h->device));
-        hipLaunchKernelGGL(okNearestIdxKernel, dim3((h->N * kNearestLanes + 255) / 256), dim3(256), 0, h->stream, h->d_cx, h->d_cy, h->P,
-                           h->st.pos_x, h->st.pos_y, h->N, h->d_nearest);
-        hipLaunchKernelGGL(okGaScoreKernel, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->d_nearest, h->d_score, h->N);
+        hipLaunchKernelGGL(okNearestIdxKernel, dim3((h->shape.N * kNearestLanes + 255) / 256), dim3(256), 0, h->stream, h->d_cx, h->d_cy, h->P,
+                           h->st.pos_x, h->st.pos_y, h->shape.N, h->d_nearest);
+        hipLaunchKernelGGL(okGaScoreKernel, dim3((h->shape.N + 255) / 256), dim3(256), 0, h->stream, h->d_nearest, h->d_score, h->shape.N);
         OK_HIP(h, hipGetLastError());
         if (out)
         {
-            int rc = copyAny(h, out, h->d_score, sizeof(float) * static_cast<size_t>(h->N));
+            int rc = copyAny(h, out, h->d_score, sizeof(float) * static_cast<size_t>(h->shape.N));
             if (rc != OKENV_OK)
                 return rc;
             OK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2480,11 +2548,11 @@ extern "C"
         if (!h->d_mlp_w)
             return fail(h, OKENV_ERR_STATE, "okenv_ga_select_mate: call okenv_policy_mlp_create first");
         OK_HIP(h, hipSetDevice(h->device));
-        const int    K     = h->N < 5 ? h->N : 5; // kNumParents (Mating.hpp:118)
-        const size_t total = static_cast<size_t>(h->N) * OK_MLP_WEIGHTS(h->R);
-        hipLaunchKernelGGL(okGaTopKernel, dim3(1), dim3(1024), 0, h->stream, h->d_score, h->N, h->d_parents, h->d_parent_score, K);
+        const int    K     = h->shape.N < 5 ? h->shape.N : 5; // kNumParents (Mating.hpp:118)
+        const size_t total = static_cast<size_t>(h->shape.N) * OK_MLP_WEIGHTS(h->shape.R);
+        hipLaunchKernelGGL(okGaTopKernel, dim3(1), dim3(1024), 0, h->stream, h->d_score, h->shape.N, h->d_parents, h->d_parent_score, K);
         hipLaunchKernelGGL(okGaMateKernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, h->stream, h->d_mlp_w, h->d_mlp_w_new,
-                           h->d_parents, h->d_parent_score, K, h->N, h->R, h->mlp_hidden, seed, generation, agent_base);
+                           h->d_parents, h->d_parent_score, K, h->shape.N, h->shape.R, h->mlp_hidden, seed, generation, agent_base);
         OK_HIP(h, hipGetLastError());
         std::swap(h->d_mlp_w, h->d_mlp_w_new);
         if (parents_out)
@@ -2502,14 +2570,14 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return OKENV_ERR_INVALID;
-        if (!h->coop || h->R < 5)
+        if (!h->shape.coop || h->shape.R < 5)
             return fail(h, OKENV_ERR_INVALID, "okenv_q_create: needs the LDS form with 5 <= rays <= 64");
         OK_HIP(h, hipSetDevice(h->device));
-        const size_t n = static_cast<size_t>(h->N) * OK_Q_STATES * OK_Q_ACTIONS;
+        const size_t n = static_cast<size_t>(h->shape.N) * OK_Q_STATES * OK_Q_ACTIONS;
         int          rc;
         // (d_q_table, which the other entry points take as "the tables exist", comes last)
-        if ((rc = devEnsure(h, &h->d_q_state, static_cast<size_t>(h->N))) || (rc = devEnsure(h, &h->d_q_action, static_cast<size_t>(h->N))) ||
-            (rc = devEnsure(h, &h->d_q_prev, static_cast<size_t>(h->N))) || (rc = devEnsure(h, &h->d_q_reset_nearest, 4U)) ||
+        if ((rc = devEnsure(h, &h->d_q_state, static_cast<size_t>(h->shape.N))) || (rc = devEnsure(h, &h->d_q_action, static_cast<size_t>(h->shape.N))) ||
+            (rc = devEnsure(h, &h->d_q_prev, static_cast<size_t>(h->shape.N))) || (rc = devEnsure(h, &h->d_q_reset_nearest, 4U)) ||
             (rc = devEnsure(h, &h->d_q_reset_query, 4U)) || (rc = devEnsure(h, &h->d_q_table, n)))
             return rc;
         hipLaunchKernelGGL(okQInitTableKernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, h->stream, h->d_q_table,
@@ -2521,7 +2589,7 @@ extern "C"
         {
             int   arg  = 0;
             float best = std::fabs(h->host_ray_deg[0] - target[t]);
-            for (int r = 1; r < h->R; ++r)
+            for (int r = 1; r < h->shape.R; ++r)
             {
                 const float d = std::fabs(h->host_ray_deg[r] - target[t]);
                 if (d < best)
@@ -2557,8 +2625,8 @@ extern "C"
         OK_HIP(h, hipGetLastError());
         if ((rc = okenv_step(h, 1)) != OKENV_OK) // initial observation with the zero action Agent::reset leaves behind
             return rc;
-        hipLaunchKernelGGL(okQBeginEpisodeKernel, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->st.dist, h->R, h->q_ray[0], h->q_ray[1],
-                           h->q_ray[2], h->q_ray[3], h->q_ray[4], h->d_q_state, h->d_q_prev, h->d_q_reset_nearest, h->N);
+        hipLaunchKernelGGL(okQBeginEpisodeKernel, dim3((h->shape.N + 255) / 256), dim3(256), 0, h->stream, h->st.dist, h->shape.R, h->q_ray[0], h->q_ray[1],
+                           h->q_ray[2], h->q_ray[3], h->q_ray[4], h->d_q_state, h->d_q_prev, h->d_q_reset_nearest, h->shape.N);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -2572,7 +2640,7 @@ extern "C"
             return fail(h, OKENV_ERR_STATE, "okenv_rollout_q: call okenv_q_create first");
         if (n_steps == 0)
             return OKENV_OK;
-        if (coopLdsBytes(h) + qLdsBytes(h) > kLdsBudget)
+        if (okCoopLdsBytes(h->shape.image_bytes) + qLdsBytes(h) > kLdsBudget)
             return fail(h, OKENV_ERR_STATE, "okenv_rollout_q: track image + centre line do not fit the CU's LDS");
         OK_HIP(h, hipSetDevice(h->device));
         const int brc = buildCenterlineBuckets(h);
@@ -2585,7 +2653,7 @@ extern "C"
                 return fail(h, OKENV_ERR_STATE, "okenv_rollout_q: the running episode belongs to another rollout (okenv_rollout_policy / _controller)");
             if (h->ep_kind == 0)
             {
-                const int prc = prelistEpisode(h, kPolicyQ);
+                const int prc = prelistEpisode(h, kActionsQLearning);
                 if (prc != OKENV_OK)
                     return prc;
                 h->ep_kind         = kPolicyQ;
@@ -2619,7 +2687,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || !out || !h->d_q_table)
             return fail(h, OKENV_ERR_STATE, "okenv_q_get_table: no table");
-        int rc = copyAny(h, out, h->d_q_table, sizeof(float) * static_cast<size_t>(h->N) * OK_Q_STATES * OK_Q_ACTIONS);
+        int rc = copyAny(h, out, h->d_q_table, sizeof(float) * static_cast<size_t>(h->shape.N) * OK_Q_STATES * OK_Q_ACTIONS);
         if (rc != OKENV_OK)
             return rc;
         OK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2633,7 +2701,7 @@ extern "C"
             dropEpisode(h);
         if (!h || !in || !h->d_q_table)
             return fail(h, OKENV_ERR_STATE, "okenv_q_set_table: no table");
-        int rc = copyAny(h, h->d_q_table, in, sizeof(float) * static_cast<size_t>(h->N) * OK_Q_STATES * OK_Q_ACTIONS);
+        int rc = copyAny(h, h->d_q_table, in, sizeof(float) * static_cast<size_t>(h->shape.N) * OK_Q_STATES * OK_Q_ACTIONS);
         if (rc != OKENV_OK)
             return rc;
         OK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2646,8 +2714,8 @@ extern "C"
         if (!h || !h->d_q_table)
             return fail(h, OKENV_ERR_STATE, "okenv_q_get_state: no table");
         int rc;
-        if ((state && (rc = copyAny(h, state, h->d_q_state, 4U * h->N))) || (action && (rc = copyAny(h, action, h->d_q_action, 4U * h->N))) ||
-            (prev_idx && (rc = copyAny(h, prev_idx, h->d_q_prev, 4U * h->N))))
+        if ((state && (rc = copyAny(h, state, h->d_q_state, 4U * h->shape.N))) || (action && (rc = copyAny(h, action, h->d_q_action, 4U * h->shape.N))) ||
+            (prev_idx && (rc = copyAny(h, prev_idx, h->d_q_prev, 4U * h->shape.N))))
             return rc;
         OK_HIP(h, hipStreamSynchronize(h->stream));
         return OKENV_OK;
@@ -2665,7 +2733,7 @@ extern "C"
                 return rc;
         }
         constexpr int kEntries = OK_Q_STATES * OK_Q_ACTIONS;
-        hipLaunchKernelGGL(okQTableSumsKernel, dim3((kEntries + 63) / 64), dim3(64), 0, h->stream, h->d_q_table, h->N, h->d_q_sums,
+        hipLaunchKernelGGL(okQTableSumsKernel, dim3((kEntries + 63) / 64), dim3(64), 0, h->stream, h->d_q_table, h->shape.N, h->d_q_sums,
                            h->d_q_sums + kEntries);
         OK_HIP(h, hipGetLastError());
         *d_out = h->d_q_sums;
@@ -2708,8 +2776,8 @@ extern "C"
         if ((sum != h->d_q_sums && (rc = copyAny(h, h->d_q_sums, sum, kBytes))) ||
             (count != h->d_q_sums + kEntries && (rc = copyAny(h, h->d_q_sums + kEntries, count, kBytes))))
             return rc;
-        const long total = static_cast<long>(h->N) * kEntries;
-        hipLaunchKernelGGL(okQAssignAllKernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, h->stream, h->d_q_table, h->N,
+        const long total = static_cast<long>(h->shape.N) * kEntries;
+        hipLaunchKernelGGL(okQAssignAllKernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, h->stream, h->d_q_table, h->shape.N,
                            h->d_q_sums, h->d_q_sums + kEntries);
         OK_HIP(h, hipGetLastError());
         OK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2984,7 +3052,7 @@ extern "C"
         out->height         = d.height;
         out->samples        = d.samples;
         out->channels       = d.format == OKENV_VIEW_RGBA8 ? 4 : 1;
-        out->bytes_per_call = static_cast<uint64_t>(h->N) * static_cast<uint64_t>(d.width) * static_cast<uint64_t>(d.height) *
+        out->bytes_per_call = static_cast<uint64_t>(h->shape.N) * static_cast<uint64_t>(d.width) * static_cast<uint64_t>(d.height) *
                               static_cast<uint64_t>(out->channels);
         return OKENV_OK;
     }
@@ -2999,7 +3067,7 @@ extern "C"
         const okenv_view_desc &d  = h->render_desc;
         const uint64_t         C  = d.format == OKENV_VIEW_RGBA8 ? 4U : 1U;
         const uint64_t         hw = static_cast<uint64_t>(d.width) * static_cast<uint64_t>(d.height);
-        if (!dst || dst_bytes < static_cast<uint64_t>(h->N) * hw * C)
+        if (!dst || dst_bytes < static_cast<uint64_t>(h->shape.N) * hw * C)
             return fail(h, OKENV_ERR_INVALID, "okenv_render_views: dst is NULL or smaller than N * H * W * C bytes");
         OK_HIP(h, hipSetDevice(h->device));
         hipPointerAttribute_t attr{};
@@ -3034,9 +3102,9 @@ extern "C"
         p.agent_rgb  = d.agent_rgb[0] | static_cast<uint32_t>(d.agent_rgb[1]) << 8 | static_cast<uint32_t>(d.agent_rgb[2]) << 16;
         const uint32_t pix_per_block = kRenderThreads * (d.format == OKENV_VIEW_RGBA8 ? 4U : 16U);
         p.chunks                     = static_cast<uint32_t>((hw + pix_per_block - 1U) / pix_per_block);
-        if (static_cast<uint64_t>(h->N) * p.chunks > 0x7FFFFFFFULL)
+        if (static_cast<uint64_t>(h->shape.N) * p.chunks > 0x7FFFFFFFULL)
             return fail(h, OKENV_ERR_INVALID, "okenv_render_views: too many workgroups for one launch (N * H * W too large)");
-        const dim3 grid(static_cast<uint32_t>(h->N) * p.chunks), block(kRenderThreads);
+        const dim3 grid(static_cast<uint32_t>(h->shape.N) * p.chunks), block(kRenderThreads);
         const bool up = (d.flags & OKENV_VIEW_HEADING_UP) != 0U;
 #define OK_RENDER_LAUNCH(F, S)                                                                                                 \
     do                                                                                                                         \
@@ -3099,9 +3167,9 @@ extern "C"
     {
         if (!h || !out)
             return fail(h, OKENV_ERR_INVALID, std::string(who) + ": NULL argument");
-        if (h->grid_mode != kGridLds)
+        if (h->shape.grid_mode != kGridLds)
             return fail(h, OKENV_ERR_STATE, std::string(who) + ": needs the LDS form of the grid");
-        if (split && !h->fb_ok)
+        if (split && !h->shape.fb_ok)
             return fail(h, OKENV_ERR_STATE, std::string(who) + ": the segment set has no front / back split (okenv_info.front_back_bytes == 0)");
         OK_HIP(h, hipSetDevice(h->device));
         void     *sp  = nullptr;
@@ -3114,7 +3182,7 @@ extern "C"
             useFrontBack(h, p);
         OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okWorkStatsKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       static_cast<int>(kLdsBudget)));
-        const long total  = static_cast<long>(h->N) * h->R;
+        const long total  = static_cast<long>(h->shape.N) * h->shape.R;
         const int  blocks = static_cast<int>(std::min<long>(256, (total + 1023) / 1024));
         hipLaunchKernelGGL(okWorkStatsKernel, dim3(blocks), dim3(1024), p.image_bytes, h->stream, p, static_cast<unsigned long long *>(sp));
         OK_HIP(h, hipGetLastError());
@@ -3157,10 +3225,10 @@ extern "C"
         const OkStepParams p      = baseParams(h);
         const int          blocks = std::min(1024, (n + 1023) / 1024);
         float             *dt     = d + 3 * static_cast<size_t>(n);
-        switch (h->grid_mode)
+        switch (h->shape.grid_mode)
         {
         case kGridLds:
-            hipLaunchKernelGGL(okDebugCastKernel<kGridLds>, dim3(blocks), dim3(1024), h->image_bytes, h->stream, p, d, d + n,
+            hipLaunchKernelGGL(okDebugCastKernel<kGridLds>, dim3(blocks), dim3(1024), h->shape.image_bytes, h->stream, p, d, d + n,
                                d + 2 * static_cast<size_t>(n), n, dt);
             break;
         case kGridGlobal:
@@ -3187,6 +3255,69 @@ extern "C"
         std::memcpy(out, h->form_counts, sizeof(h->form_counts));
         if (clear != 0)
             std::memset(h->form_counts, 0, sizeof(h->form_counts));
+        return OKENV_OK;
+    }
+
+    // The launch policy on plain numbers: the same okPlanLanes / okPlanGeometry / okPlanStep a handle goes through, without one.
+    int okenv_debug_plan_step(const okenv_plan_query *q, okenv_plan_result *out)
+    {
+        if (!q || !out || q->num_agents <= 0 || q->num_rays <= 0 || q->compute_units <= 0 || q->image_bytes < 0 || q->front_back_bytes < 0 ||
+            q->q_bytes < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_plan_step: bad argument");
+        OkKnobs k;
+        k.lanes_per_agent  = q->lanes_per_agent;
+        k.block_threads    = q->block_threads;
+        k.coop             = q->coop;
+        k.agents_per_block = q->agents_per_block;
+        k.tail_max_agents  = q->tail_max_agents;
+        k.phase1_range     = q->phase1_range;
+        k.resident         = q->resident;
+        k.front_back       = q->front_back;
+        OkLaunchShape s = okPlanLanes(q->num_agents, q->num_rays, q->compute_units, k);
+        okPlanGeometry(s, q->flags, q->image_fits_lds != 0, k);
+        if (s.grid_mode == kGridLds)
+        { // (what okenv_create learns from the grid builder and the front / back classification)
+            s.image_bytes = static_cast<size_t>(q->image_bytes);
+            s.fb_ok       = s.front_back && q->front_back_bytes > 0;
+            s.fb_bytes    = s.fb_ok ? static_cast<size_t>(q->front_back_bytes) : 0U;
+        }
+        OkStepRequest rq;
+        rq.action_source   = q->action_source;
+        rq.n_listed        = q->n_listed;
+        rq.packed          = q->packed != 0;
+        rq.resident        = q->resident_launch != 0;
+        rq.do_move         = q->do_move;
+        rq.reset_flags     = q->reset_flags;
+        rq.ctrl_num_params = q->ctrl_num_params;
+        rq.q_bytes         = static_cast<size_t>(q->q_bytes);
+        if (q->n_listed == OKENV_PLAN_FIRST_ROLLOUT)
+            rq.n_listed = okPrelist(s, rq.action_source, rq.q_bytes) ? s.N : -1;
+        const OkStepPlan pl    = okPlanStep(s, rq);
+        out->lanes_per_agent   = s.G;
+        out->natural_lanes     = s.natural_g;
+        out->rays_per_lane     = s.rays_per_lane;
+        out->phase1_range      = s.phase1_range;
+        out->grid_cell         = s.cell_default;
+        out->grid_mode         = s.grid_mode;
+        out->front_back_built  = s.front_back ? 1 : 0;
+        out->block_threads     = s.block_threads;
+        out->grid_blocks       = s.grid_blocks;
+        out->coop              = s.coop ? 1 : 0;
+        out->agents_per_block  = s.agents_per_block;
+        out->tail_max_agents   = s.tail_max_agents;
+        out->resident_mode     = s.resident_mode;
+        out->resident_eligible = okResidentShape(s) ? 1 : 0;
+        out->tail_limit        = static_cast<int32_t>(okTailLimit(s, rq.action_source == kActionsQLearning, rq.q_bytes));
+        out->form              = pl.form;
+        out->launch_grid       = static_cast<int32_t>(pl.grid);
+        out->launch_block      = static_cast<int32_t>(pl.block);
+        out->launch_lds_bytes  = static_cast<int32_t>(pl.lds);
+        out->launch_image_off  = static_cast<int32_t>(pl.image_off);
+        out->launch_phase1     = pl.phase1;
+        out->launch_lanes      = pl.G;
+        out->launch_front_back = pl.front_back ? 1 : 0;
+        out->launch_ctrl_lds_off = static_cast<int32_t>(pl.ctrl_lds_off);
+        out->launch_waves        = static_cast<int32_t>(pl.waves());
         return OKENV_OK;
     }
 }

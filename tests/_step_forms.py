@@ -1,5 +1,5 @@
-"""The step-form table: one row per step-kernel launch site of openkitchen_amd/csrc/okenv_capi.hip (enum okenv_step_form in
-include/okenv.h), plus rows for the variants of a site (front / back images on and off, episode list or none, controller
+"""The step-form table: one row per step-kernel launch of openkitchen_amd/csrc/okenv_capi.hip (launchStep's switch over enum
+okenv_step_form of include/okenv.h), plus rows for the variants of a site (front / back images on and off, episode list or none, controller
 parameters in LDS or in global memory) and for a handle with several policies attached.  Plain data: tests/test_step_form_table.py
 imports it without a GPU, tests/test_gpu_step_forms.py runs every row against the oracle.
 
@@ -123,9 +123,9 @@ def pow2ceil(v):
 
 
 def handle_shape(N, R, C, env=None, flags=0):
-    """okenv_create's launch geometry (openkitchen_amd/csrc/okenv_capi.hip, okenv_create): lanes per agent G (:1003-1012), phase 1
-    (:1015-1016, :1030-1031, :1221-1226), the grid form (:1034-1039, assuming the track image fits the LDS, as the four tracks' do at
-    the default cell), workgroup size (:1181-1196), the cooperative kernel (:1198-1200), agents per workgroup (:1204-1214)."""
+    """A handle's launch shape (openkitchen_amd/csrc/okenv_capi.hip): okPlanLanes' lanes per agent G and phase 1, okPlanGeometry's
+    grid form (assuming the track image fits the LDS, as the four tracks' do at the default cell), workgroup size, cooperative
+    kernel and agents per workgroup.  env: the OKENV_* knobs as readKnobs finds them."""
     env = env or {}
     G = min(64, pow2ceil(R))
     natural = G
@@ -156,7 +156,7 @@ def handle_shape(N, R, C, env=None, flags=0):
 
 
 def tail_limit(shape, fit):
-    """tailLimit (okenv_capi.hip:918-928) for a track image of which `fit` tail workgroups share a CU's LDS (1 or 2 for the four
+    """okTailLimit (okenv_capi.hip) for a track image of which `fit` tail workgroups share a CU's LDS (1 or 2 for the four
     tracks; the exact figure needs the image, which only okenv_create builds): 0 without the cooperative kernel."""
     if shape["grid"] != "lds" or not shape["coop"] or shape["tail_max"] == 0:
         return 0
@@ -167,9 +167,9 @@ def tail_limit(shape, fit):
 
 
 def first_form(shape, call, fit):
-    """The form of a call's first step launch (launchStep, okenv_capi.hip:690-913; startResident :538-570; okenv_step_packed's
-    choice of the resident kernel :1724-1743).  call: step, random, packed, resident, ga_plain, ga_episode, q_plain, q_episode,
-    ctrl, ctrl_episode.  An episode's first launch is listed when the population fits the tail kernel (prelistEpisode)."""
+    """The form of a call's first step launch (okPlanStep of okenv_capi.hip; okResidentShape and okenv_step_packed for the choice of
+    the resident kernel).  call: step, random, packed, resident, ga_plain, ga_episode, q_plain, q_episode,
+    ctrl, ctrl_episode.  An episode's first launch is listed when the population fits the tail kernel (okPrelist)."""
     mlp = call.startswith("ga")
     episode = call.endswith("episode")
     if shape["grid"] != "lds" or not shape["coop"]:
