@@ -1,7 +1,10 @@
 """PPO racers on the device environment: the reference's RLRacers/PPO app (ppo_sim.cpp + PPOAgent.hpp) for thousands of
 agents, with the environment, resets and reward bookkeeping on the GPU and the learner in PyTorch-ROCm.
 
-    python examples/ppo_racer.py [--agents 1024] [--episodes 20] [--track Silverstone]
+    python examples/ppo_racer.py [--agents 1024] [--episodes 20] [--track Silverstone] [--device-actor [--graph-chunk 32]]
+
+--device-actor: the agents act on the device too (okenv_actor_act): one kernel per step evaluates actor and
+critic, samples and records the step, and --graph-chunk K replays K such iterations as one HIP graph.
 
 Per episode (ppo_sim.cpp:49-89): resetAgent to random centre-line points, one observation step, then act / step until
 every agent has crashed; then PPOAgent::updatePolicy (PPOAgent.hpp:106-160): discounted returns (gamma 0.99,
@@ -18,7 +21,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from openkitchen_amd.rollout import collect_episode, discounted_returns  # noqa: E402
+from openkitchen_amd.rollout import collect_episode, collect_episode_device, discounted_returns  # noqa: E402
 from openkitchen_amd.torch_env import VectorEnvironment  # noqa: E402
 
 
@@ -29,6 +32,8 @@ def main():
     ap.add_argument("--track", default="Silverstone")
     ap.add_argument("--max-steps", type=int, default=3000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device-actor", action="store_true", help="act with the device actor kernel instead of the PyTorch forward")
+    ap.add_argument("--graph-chunk", type=int, default=32, help="with --device-actor: iterations per replayed HIP graph (0: eager)")
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     rays = np.array([-70, -30, 0, 30, 70], dtype=np.float32)          # PPOAgent.hpp:56-61
@@ -38,9 +43,15 @@ def main():
     opt_a = torch.optim.Adam(actor.parameters(), lr=3e-4)             # kLearningRate
     opt_c = torch.optim.Adam(critic.parameters(), lr=3e-4)
     clip, epochs, batch = 0.2, 5, 4096
+    if args.device_actor:
+        venv.enable_actor(actor, critic)
     for episode in range(args.episodes):
         t0 = time.perf_counter()
-        ep = collect_episode(venv, actor, max_steps=args.max_steps)
+        if args.device_actor:
+            venv.sync_actor()  # the parameters the last update left
+            ep = collect_episode_device(venv, max_steps=args.max_steps, graph_chunk=args.graph_chunk)
+        else:
+            ep = collect_episode(venv, actor, max_steps=args.max_steps)
         alive = ep["alive"]
         lengths = alive.sum(dim=0).float()
         returns = discounted_returns(ep["rewards"] * alive)          # reward only while the agent is driving

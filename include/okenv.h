@@ -281,6 +281,70 @@ OKENV_API int okenv_expert_act_host(const okenv_expert_params *params, const flo
                                     const float *cy, int32_t num_points, int32_t n, const float *pos_x, const float *pos_y, const float *rot_deg,
                                     const float *dist, const float *goal_x, const float *goal_y, float *throttle, float *steer);
 
+/* ---- shared-network actors: RLRacers' PPO, REINFORCE and Deep-Q agents on the device (DESIGN.md
+ * section 14) ----------------------------------------------------------------------------------------------------------------
+ * updateAction of the agents that share ONE network (RLRacers/PPO/PPOAgent.hpp:68-102, Reinforce/Policy.hpp:22-29,
+ * Deep_Q_Learning/DQAgent.hpp:85-104) for every agent of the handle: x = dist / kSensorRange, a policy network R -> H -> A and an
+ * optional value network R -> Hv -> 1 (ReLU after the hidden layer), softmax + clamp + categorical sampling, arg-max, or
+ * epsilon-greedy, and the action table from index to (throttle_delta, steering_delta).  The rule, with its summation order, its
+ * exp and its Philox stream, is written out in include/okenv_math.h (ok_actor_*). */
+#define OKENV_ACTOR_SAMPLE 0     /* PPO, REINFORCE: one categorical draw from the clamped softmax */
+#define OKENV_ACTOR_GREEDY 1     /* evaluation: arg-max of the logits                             */
+#define OKENV_ACTOR_EPS_GREEDY 2 /* Deep-Q: a uniform action with probability epsilon, else arg-max */
+
+typedef struct okenv_actor_params {
+    int32_t  hidden;             /* H, 1 .. 256                                                     */
+    int32_t  num_actions;        /* A, 2 .. 8                                                       */
+    int32_t  value_hidden;       /* Hv, 0 .. 256; 0: no value network                               */
+    int32_t  mode;               /* OKENV_ACTOR_SAMPLE | _GREEDY | _EPS_GREEDY                      */
+    float    epsilon;            /* [0, 1]; read by OKENV_ACTOR_EPS_GREEDY only                     */
+    uint32_t seed, agent_base;   /* key of the draws; global id of the handle's agent 0             */
+    float    action_table[8][2]; /* (throttle_delta, steering_delta) per action index (kActionMap)  */
+} okenv_actor_params;
+
+/* Where okenv_actor_act leaves this step's sample, besides the action fields: device pointers, each may be NULL (skipped). */
+typedef struct okenv_actor_record {
+    float   *state;  /* [N][R]  x, the networks' input (dist / kSensorRange)                                  */
+    int64_t *action; /* [N]     the chosen index (what torch.gather wants)                                    */
+    float   *prob;   /* [N]     the clamped probability of that action; in OKENV_ACTOR_EPS_GREEDY its logit   */
+    float   *value;  /* [N]     the value network's output (left alone without a value network)               */
+    uint8_t *alive;  /* [N]     !crashed_                                                                     */
+} okenv_actor_record;
+
+/* Attaches an actor to the handle (replaces an earlier one, whose parameters are forgotten).  The fan has at most 64 rays.
+ * OKENV_ERR_INVALID for NULL arguments, a width or action count outside the limits above, an unknown mode, epsilon outside [0, 1]
+ * (or NaN), more than 64 rays. */
+OKENV_API int okenv_actor_create(okenv_t h, const okenv_actor_params *params);
+/* Floats of the two parameter vectors, in the order of torch's parameters(): l1.weight [H][R] row-major, l1.bias [H], l2.weight
+ * [A][H], l2.bias [A]; the value network's likewise with one output (0 floats without one).  Either pointer may be NULL. */
+OKENV_API int okenv_actor_num_params(okenv_t h, int32_t *policy, int32_t *value);
+/* New parameters from host or device pointers (a device pointer is a device-to-device copy on the handle's stream: the flattened
+ * parameters of a torch module can be handed over after every optimiser step without a host hop).  A NULL pointer leaves that
+ * network as it is.  No synchronisation: a host buffer must stay valid until the stream has passed the copy. */
+OKENV_API int okenv_actor_set_params(okenv_t h, const float *policy, const float *value);
+OKENV_API int okenv_actor_set_epsilon(okenv_t h, float epsilon);
+/* A device word that is added to the draw index of every later okenv_actor_act (NULL: none).  For replayed HIP graphs of a handle
+ * WITHOUT auto-reset, see okenv_actor_act. */
+OKENV_API int okenv_actor_set_draw_offset(okenv_t h, const uint32_t *device_word);
+/* updateAction for every agent, crashed ones included (ppo_sim.cpp:63-69 asks every agent): reads OKENV_F_DIST and crashed_, writes
+ * OKENV_F_THROTTLE / OKENV_F_STEER and, when `rec` is given, the record slots.  One kernel on the handle's stream, no
+ * synchronisation, no allocation: it can be captured into a HIP graph next to okenv_step (the contract of okenv_expert_act; like it,
+ * it ends a running episode without the end-of-episode corrections).
+ * The draw index is the handle's step count (okenv_get_step_count), which the call reads and does not advance: the agents draw
+ * afresh after every step, and a population sharded over handles (agent_base) draws what the unsharded one draws.  While
+ * auto-reset is on, the step count lives on the device (the step kernels advance it; it is the epoch of the reset draws) and the
+ * kernel reads it there, so replays of a captured graph keep drawing fresh numbers.  Without auto-reset the step kernels leave the
+ * device word alone and the host's count is passed by value: a captured launch then repeats its draw index on every replay, unless
+ * the caller advances a word of its own inside the graph and registers it with okenv_actor_set_draw_offset.
+ * OKENV_ERR_STATE before okenv_actor_create, or before okenv_actor_set_params has given every attached network its parameters. */
+OKENV_API int okenv_actor_act(okenv_t h, const okenv_actor_record *rec);
+/* The same rule on host arrays, no GPU needed: n agents (global ids params->agent_base + i), dist [n][num_rays], crashed [n] or
+ * NULL.  Outputs, each may be NULL: throttle, steer, action, prob [n], value_out [n] (needs a value network), state [n][num_rays],
+ * alive [n]. */
+OKENV_API int okenv_actor_act_host(const okenv_actor_params *params, const float *policy, const float *value, int32_t num_rays, int32_t n,
+                                   const float *dist, const uint8_t *crashed, uint32_t draw_index, float *throttle, float *steer,
+                                   int64_t *action, float *prob, float *value_out, float *state, uint8_t *alive);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.
@@ -554,6 +618,8 @@ OKENV_API int okenv_work_stats_split(okenv_t h, uint64_t out[8]);
 /* ok_atan2f (include/okenv_math.h) and the experts' bounded normalizeAngleDeg on host arrays; host only, no GPU. */
 OKENV_API int okenv_debug_atan2f(const float *y, const float *x, float *out, int32_t n);
 OKENV_API int okenv_debug_expert_normalize_angle(const float *angle_deg, float *out, int32_t n);
+/* ok_expf (the actors' softmax) on a host array; host only, no GPU. */
+OKENV_API int okenv_debug_expf(const float *x, float *out, int32_t n);
 /* ok_sincosf evaluated on the GPU (n values, host pointers). */
 OKENV_API int okenv_debug_sincos(int32_t device, const float *x, float *s, float *c, int32_t n);
 /* First-hit parameter t for n arbitrary rays (origin, angle [rad]) through the handle's grid (host pointers). */

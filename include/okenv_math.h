@@ -28,6 +28,8 @@
 #else
 #define OK_HD static inline
 #endif
+/* For functions that take small arrays the kernels keep in registers: inlined always, so that the array never needs an address. */
+#define OK_HDI OK_HD __attribute__((always_inline))
 
 /* Environment/Typedefs.h:10  kDeg2Rad = float(M_PI / 180.0F)  (bit pattern 0x3C8EFA35) */
 #define OK_DEG2RAD 0.01745329238474369049072265625f
@@ -441,6 +443,223 @@ OK_HD float ok_tanhf(const float x)
     const double den = OK_FMA(two_n.d, m, 1.0 + two_n.d);
     const double t = num / den;
     return (float)(x < 0.0f ? -t : t);
+}
+
+/* exp for the shared-network actors' softmax (below), for arguments <= 0: the pieces of ok_tanhf.  n = rint(x / ln 2),
+ * r = x - n ln 2 by two FMAs against ln 2 = L1 + L2, |r| <= ln 2 / 2, m = expm1(r) = r + r^2 E(r) with ok_tanhf's E (relative
+ * error 2^-48), exp x = 2^n (1 + m): the sum is one fp64 rounding, the scaling by 2^n is exact (n >= -289: a normal double), and the
+ * conversion to fp32 is the single rounding into fp32 -- subnormal results included, the conversion rounds those correctly too.
+ * Arguments below -200 count as -200 (the result is 0 from -104 on), so -inf gives 0; NaN stays NaN.  Arguments above 0 are not
+ * the softmax's business: they are evaluated by the same formula up to +200 (inf from 88.73 on) and nothing tests them.
+ * tests/test_actor_rule.py: equal to the rounded fp64 exp on all but a few of a million arguments in [-104, 0], never more than
+ * one ulp away. */
+OK_HD float ok_expf(const float x)
+{
+    if (!(x == x)) return x;
+    const double xd = (double)x;
+    const double y = xd < -200.0 ? -200.0 : (xd > 200.0 ? 200.0 : xd);
+    const double n = OK_RINT(y * ok_konst(0x1.71547652b82fep+0)); /* 1 / ln 2 */
+    double r = OK_FMA(-n, ok_konst(0x1.62e42fefa39efp-1), y);     /* L1 = 0.6931471805599453     */
+    r = OK_FMA(-n, ok_konst(0x1.abc9e3b39803fp-56), r);           /* L2 = 2.3190468138462996e-17 */
+    double p = ok_konst(0x1.28809b1a1156ep-22);           /* E: the coefficients of ok_tanhf */
+    p = OK_FMA(p, r, ok_konst(0x1.72c7b3ac3a215p-19));
+    p = OK_FMA(p, r, ok_konst(0x1.a019c964743c8p-16));
+    p = OK_FMA(p, r, ok_konst(0x1.a019ad41ef162p-13));
+    p = OK_FMA(p, r, ok_konst(0x1.6c16c1739cf9cp-10));
+    p = OK_FMA(p, r, ok_konst(0x1.1111111c5b16fp-7));
+    p = OK_FMA(p, r, ok_konst(0x1.5555555554ca3p-5));
+    p = OK_FMA(p, r, ok_konst(0x1.5555555553b3cp-3));
+    p = OK_FMA(p, r, 0.5);
+    const double m = OK_FMA(r * r, p, r); /* expm1(r) */
+    union { uint64_t u; double d; } two_n; /* 2^n, n in [-289, 289] */
+    two_n.u = (uint64_t)(1023 + (int)n) << 52;
+    return (float)(two_n.d * (1.0 + m));
+}
+
+/* ---- RLRacers: the shared-network actors -----------------------------------
+ * updateAction of PPOAgent (RLRacers/PPO/PPOAgent.hpp:68-102 with Actor.hpp:20-27 and Critic.hpp), of the REINFORCE agent
+ * (Reinforce/Policy.hpp:22-29, without its Dropout) and of DQAgent (Deep_Q_Learning/DQAgent.hpp:85-104, with one hidden layer): ONE
+ * network for all agents, an action index per agent, a table from index to (throttle_delta, steering_delta).  libtorch's summation
+ * order, its softmax and its multinomial are not pinned, so the rule is written out here; csrc/ok_actor.h's kernel and
+ * okenv_actor_act_host both evaluate THESE functions, so they agree bit for bit.
+ *
+ *   input     x[i] = dist[i] / 200.0f (OK_SENSOR_RANGE), one IEEE fp32 division: what sensor_hits_[i].norm() / kSensorRange is in
+ *             the reference's C++ (PPOAgent.hpp:66-74) and what torch computes on the CPU.  (On the GPU torch divides a tensor
+ *             by a scalar as a multiplication by the rounded reciprocal, so VectorEnvironment.observation() can differ from this
+ *             in the last place or two; the recorded state is the division's.)
+ *   networks  policy R -> H -> A and, optionally, value R -> Hv -> 1, ReLU after the hidden layer (relu(s) = s > 0 ? s : 0, so a
+ *             NaN sum gives 0).  Parameters in the order of torch's parameters(): l1.weight [H][R] row-major, l1.bias [H],
+ *             l2.weight [A][H], l2.bias [A].  1 <= R <= 64, 1 <= H <= 256, 2 <= A <= 8, 0 <= Hv <= 256 (0: no value network).
+ *   sums      fp32, a separate multiplication and addition per term, nothing fused.
+ *             hidden unit j:  s = b1[j]; s = s + w1[j][i] * x[i] for i = 0 .. R-1 ascending; h[j] = relu(s).
+ *             output k: OK_ACTOR_LANES = 8 interleaved partial sums joined by a fixed tree (the choice the kernel's lane groups
+ *             want; it does not depend on the launch shape or on N):
+ *               part_l = 0.0f; part_l = part_l + w2[k][j] * h[j] for j = l, l + 8, l + 16, ... < H ascending      (l = 0 .. 7)
+ *               z_k = b2[k] + (((part_0 + part_4) + (part_2 + part_6)) + ((part_1 + part_5) + (part_3 + part_7)))
+ *             (the butterfly over lane distances 4, 2, 1; IEEE addition commutes, so every lane of a group holds these bits).
+ *   softmax   m = max z (the lowest index wins ties), e_k = ok_expf(z_k - m), s = e_0 + e_1 + ... ascending, p_k = e_k / s (IEEE
+ *             division), then p_k clamped to [1e-8f, 1.0f]: kProbClamp (PPOAgent.hpp:27,88) is clamp(probs, 1e-8, 1.0 - 1e-8),
+ *             and the upper limit 1.0 - 1e-8 is 1.0f once it is an fp32 number, which is what torch compares a float tensor with.
+ *             A NaN p_k stays NaN (both comparisons are false).
+ *   draws     one Philox block per (seed, global agent id, draw index): counter = (agent, draw, 6, 0), key = (seed, "oken").
+ *             Stream 6 is used by nothing else (0: C2 actions, 1: resets and GA weights, 2 / 3: GA mating, 4: Q-learning, 5:
+ *             q_racer_sim's episode draws).
+ *   modes     OK_ACTOR_SAMPLE (PPO, REINFORCE): u = ok_u01(word 0); the action is the first k with u < p_0 + ... + p_k (fp32
+ *             sums of the clamped p, ascending), A - 1 if there is none.  Recorded: the clamped p of the action.
+ *             OK_ACTOR_GREEDY (evaluation): the arg-max of z, lowest index on ties.  Recorded: the clamped p of the action.
+ *             OK_ACTOR_EPS_GREEDY (DQAgent.hpp:89-99): ok_u01(word 0) < epsilon picks ok_index_from_word(word 1, A), otherwise the
+ *             arg-max of z.  No softmax; recorded: z of the action.
+ * The logarithm is the learner's: torch.log over the recorded [T, N] probabilities gives log_probs once per episode. */
+#define OK_ACTOR_SAMPLE 0
+#define OK_ACTOR_GREEDY 1
+#define OK_ACTOR_EPS_GREEDY 2
+#define OK_ACTOR_MAX_RAYS 64
+#define OK_ACTOR_MAX_HIDDEN 256
+#define OK_ACTOR_MAX_ACTIONS 8
+#define OK_ACTOR_LANES 8
+#define OK_ACTOR_PROB_MIN 1e-8f
+#define OK_ACTOR_PROB_MAX 1.0f /* (float)(1.0 - 1e-8) */
+
+OK_HDI int ok_actor_num_params(const int in, const int hidden, const int out)
+{
+    return hidden * in + hidden + out * hidden + out;
+}
+
+/* The partial sums of interleave lane l for every output: part[k] over the hidden units j = l, l + 8, ... of a network whose first
+ * layer's rows lie `w1_stride` floats apart (R in a parameter vector; the kernel pads its copy).  part has OK_ACTOR_MAX_ACTIONS
+ * entries; those from `out` on are left alone. */
+OK_HDI void ok_actor_partial(const float *w1, const int w1_stride, const float *b1, const float *w2, const int in, const int hidden, const int out,
+                            const float *x, const int l, float *part)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+        if (k < out) part[k] = 0.0f;
+    for (int j = l; j < hidden; j += OK_ACTOR_LANES) {
+        const float *row = w1 + j * w1_stride;
+        float s = b1[j];
+        for (int i = 0; i < in; ++i) s = s + row[i] * x[i];
+        const float h = s > 0.0f ? s : 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+            if (k < out) part[k] = part[k] + w2[k * hidden + j] * h;
+    }
+}
+
+/* The fixed tree over the eight partial sums, then the bias */
+OK_HDI float ok_actor_join(const float *p, const float bias)
+{
+    return bias + (((p[0] + p[4]) + (p[2] + p[6])) + ((p[1] + p[5]) + (p[3] + p[7])));
+}
+
+/* index of the largest of z[0 .. n-1], the lowest index on ties (NaN never wins) */
+OK_HDI int ok_actor_argmax(const float *z, const int n)
+{
+    int best = 0;
+    float m = z[0];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 1; k < OK_ACTOR_MAX_ACTIONS; ++k)
+        if (k < n && z[k] > m) { m = z[k]; best = k; }
+    return best;
+}
+
+OK_HDI float ok_actor_clamp_prob(const float p)
+{
+    return p < OK_ACTOR_PROB_MIN ? OK_ACTOR_PROB_MIN : (p > OK_ACTOR_PROB_MAX ? OK_ACTOR_PROB_MAX : p);
+}
+
+/* From the exponentials e_k = ok_expf(z_k - max z) to the action and the recorded probability of OK_ACTOR_SAMPLE (u given) and
+ * OK_ACTOR_GREEDY (`greedy` = the arg-max of z, or -1 to sample). */
+OK_HDI int ok_actor_pick(const float *e, const int n, const float u, const int greedy, float *prob)
+{
+    float s = e[0];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 1; k < OK_ACTOR_MAX_ACTIONS; ++k)
+        if (k < n) s = s + e[k];
+    int action = greedy >= 0 ? greedy : n - 1;
+    int found = greedy >= 0;
+    float cum = 0.0f, pa = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+        if (k < n) {
+            const float pk = ok_actor_clamp_prob(e[k] / s);
+            cum = k == 0 ? pk : cum + pk;
+            if (!found && u < cum) { action = k; found = 1; }
+            if (k == action) pa = pk; /* (k never passes a later `action`: it is either fixed or n - 1 until found) */
+        }
+    *prob = pa;
+    return action;
+}
+
+/* The two words of the action draw */
+OK_HDI ok_u32x4 ok_actor_draw(const uint32_t seed, const uint32_t agent, const uint32_t draw)
+{
+    return ok_philox4x32(agent, draw, 6u, 0u, seed, 0x6F6B656Eu);
+}
+
+/* OK_ACTOR_EPS_GREEDY: the action from the arg-max of the logits (its recorded value is z[action], the caller's to look up) */
+OK_HDI int ok_actor_eps_greedy(const float epsilon, const uint32_t seed, const uint32_t agent, const uint32_t draw, const int n, const int best)
+{
+    const ok_u32x4 r = ok_actor_draw(seed, agent, draw);
+    return ok_u01(r.v[0]) < epsilon ? (int)ok_index_from_word(r.v[1], (uint32_t)n) : best;
+}
+
+/* From the logits to the action: every mode.  z has OK_ACTOR_MAX_ACTIONS entries, n of them used. */
+OK_HDI int ok_actor_choose(const int mode, const float epsilon, const uint32_t seed, const uint32_t agent, const uint32_t draw, const float *z,
+                          const int n, float *prob)
+{
+    const int best = ok_actor_argmax(z, n);
+    if (mode == OK_ACTOR_EPS_GREEDY) {
+        const int action = ok_actor_eps_greedy(epsilon, seed, agent, draw, n, best);
+        *prob = z[action];
+        return action;
+    }
+    float e[OK_ACTOR_MAX_ACTIONS];
+    float m = z[0]; /* = z[best], without an indexed read of a register array */
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 1; k < OK_ACTOR_MAX_ACTIONS; ++k)
+        if (k < n && z[k] > m) m = z[k];
+    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+        e[k] = k < n ? ok_expf(z[k] - m) : 0.0f;
+    float u = 0.0f;
+    if (mode == OK_ACTOR_SAMPLE) u = ok_u01(ok_actor_draw(seed, agent, draw).v[0]);
+    return ok_actor_pick(e, n, u, mode == OK_ACTOR_GREEDY ? best : -1, prob);
+}
+
+/* One agent on the host (and the reading the kernel's lane groups split up): x from dist, both networks, the choice.
+ * `value_out` is written only when value_hidden > 0. */
+OK_HD int ok_actor_agent(const float *policy, const float *value, const int in, const int hidden, const int n_actions, const int value_hidden,
+                         const int mode, const float epsilon, const uint32_t seed, const uint32_t agent, const uint32_t draw, const float *dist,
+                         float *x, float *prob, float *value_out)
+{
+    for (int i = 0; i < in; ++i) x[i] = dist[i] / OK_SENSOR_RANGE;
+    float part[OK_ACTOR_LANES][OK_ACTOR_MAX_ACTIONS], col[OK_ACTOR_LANES], z[OK_ACTOR_MAX_ACTIONS];
+    const float *b1 = policy + hidden * in, *w2 = b1 + hidden, *b2 = w2 + n_actions * hidden;
+    for (int l = 0; l < OK_ACTOR_LANES; ++l) ok_actor_partial(policy, in, b1, w2, in, hidden, n_actions, x, l, part[l]);
+    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k) {
+        for (int l = 0; l < OK_ACTOR_LANES; ++l) col[l] = k < n_actions ? part[l][k] : 0.0f;
+        z[k] = k < n_actions ? ok_actor_join(col, b2[k]) : 0.0f;
+    }
+    if (value_hidden > 0) {
+        const float *vb1 = value + value_hidden * in, *vw2 = vb1 + value_hidden, *vb2 = vw2 + value_hidden;
+        for (int l = 0; l < OK_ACTOR_LANES; ++l) {
+            ok_actor_partial(value, in, vb1, vw2, in, value_hidden, 1, x, l, part[l]);
+            col[l] = part[l][0];
+        }
+        *value_out = ok_actor_join(col, vb2[0]);
+    }
+    return ok_actor_choose(mode, epsilon, seed, agent, draw, z, n_actions, prob);
 }
 
 /* One candidate's controller (Controller.cpp:3-23: fc1 in->h, fc2 h->h/2, fc3 h/2->out, tanh after each) on the input

@@ -35,6 +35,10 @@ VIEW_FOLLOW_W, VIEW_FOLLOW_H = 1600.0 / 15.0, 1400.0 / 15.0  # as fp32 these equ
 # expert drivers (include/okenv.h)
 EXPERT_POTFIELD, EXPERT_VFH = 0, 1
 EXPERT_KINDS = {"potfield": EXPERT_POTFIELD, "vfh": EXPERT_VFH}
+# shared-network actors (include/okenv.h)
+ACTOR_SAMPLE, ACTOR_GREEDY, ACTOR_EPS_GREEDY = 0, 1, 2
+ACTOR_MODES = {"sample": ACTOR_SAMPLE, "greedy": ACTOR_GREEDY, "eps_greedy": ACTOR_EPS_GREEDY}
+ACTOR_MAX_RAYS, ACTOR_MAX_HIDDEN, ACTOR_MAX_ACTIONS = 64, 256, 8
 
 # every symbol include/okenv.h declares (tests/test_capi_symbols.py checks the library exports them all)
 SYMBOLS = [
@@ -58,6 +62,8 @@ SYMBOLS = [
     "okenv_render_create", "okenv_render_views", "okenv_render_get_info", "okenv_track_band_triangles",
     "okenv_expert_create", "okenv_expert_act", "okenv_expert_act_host", "okenv_debug_atan2f", "okenv_debug_expert_normalize_angle",
     "okenv_debug_plan_step",
+    "okenv_actor_create", "okenv_actor_num_params", "okenv_actor_set_params", "okenv_actor_set_epsilon", "okenv_actor_set_draw_offset",
+    "okenv_actor_act", "okenv_actor_act_host", "okenv_debug_expf",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -104,6 +110,25 @@ def expert_params(kind, lookahead=2, goal_wrap=False, k_att=100.0, k_rep=10.0, e
     kind: "potfield" / "vfh" or the integer."""
     k = EXPERT_KINDS[kind] if isinstance(kind, str) else int(kind)
     return OkenvExpertParams(k, int(lookahead), 1 if goal_wrap else 0, k_att, k_rep, effect_range, clamp_deg, vfh_throttle, int(vfh_threshold))
+
+
+class OkenvActorParams(C.Structure):
+    _fields_ = [("hidden", C.c_int32), ("num_actions", C.c_int32), ("value_hidden", C.c_int32), ("mode", C.c_int32), ("epsilon", C.c_float),
+                ("seed", C.c_uint32), ("agent_base", C.c_uint32), ("action_table", (C.c_float * 2) * 8)]
+
+
+class OkenvActorRecord(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("action", C.c_void_p), ("prob", C.c_void_p), ("value", C.c_void_p), ("alive", C.c_void_p)]
+
+
+def actor_params(hidden, actions, value_hidden=0, mode="sample", epsilon=0.0, seed=0, agent_base=0):
+    """okenv_actor_params; actions: the table [(throttle_delta, steering_delta), ...] (2 .. 8 rows), mode: "sample" / "greedy" /
+    "eps_greedy" or the integer."""
+    ap = OkenvActorParams(int(hidden), len(actions), int(value_hidden), ACTOR_MODES[mode] if isinstance(mode, str) else int(mode),
+                          float(epsilon), int(seed) & 0xFFFFFFFF, int(agent_base) & 0xFFFFFFFF)
+    for k, (thr, steer) in enumerate(list(actions)[:ACTOR_MAX_ACTIONS]):
+        ap.action_table[k][0], ap.action_table[k][1] = float(thr), float(steer)
+    return ap
 
 
 PLAN_FIRST_ROLLOUT = -2
@@ -261,6 +286,14 @@ def load(build_if_missing=True):
     L.okenv_debug_atan2f.argtypes = [vp, vp, vp, i32]
     L.okenv_debug_expert_normalize_angle.argtypes = [vp, vp, i32]
     L.okenv_debug_plan_step.argtypes = [C.POINTER(OkenvPlanQuery), C.POINTER(OkenvPlanResult)]
+    L.okenv_actor_create.argtypes = [vp, C.POINTER(OkenvActorParams)]
+    L.okenv_actor_num_params.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.okenv_actor_set_params.argtypes = [vp, vp, vp]
+    L.okenv_actor_set_epsilon.argtypes = [vp, f32]
+    L.okenv_actor_set_draw_offset.argtypes = [vp, vp]
+    L.okenv_actor_act.argtypes = [vp, C.POINTER(OkenvActorRecord)]
+    L.okenv_actor_act_host.argtypes = [C.POINTER(OkenvActorParams), vp, vp, i32, i32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.okenv_debug_expf.argtypes = [vp, vp, i32]
     _lib = L
     return L
 

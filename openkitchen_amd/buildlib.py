@@ -23,6 +23,7 @@ CXX_SOURCES = [
 ]
 HEADERS = [
     os.path.join(CSRC, "ok_raycast.h"), os.path.join(CSRC, "ok_grid.h"), os.path.join(CSRC, "ok_render.h"), os.path.join(CSRC, "ok_expert.h"),
+    os.path.join(CSRC, "ok_actor.h"),
     os.path.join(CSRC, "okenv_kernels.h"),
     os.path.join(ROOT, "include", "okenv.h"), os.path.join(ROOT, "include", "okenv_math.h"),
 ]

@@ -1,0 +1,232 @@
+// ok_actor.h -- the reference's shared-network agents (RLRacers/PPO/PPOAgent.hpp, Reinforce/Policy.hpp, Deep_Q_Learning/DQAgent.hpp):
+// updateAction for every agent of a handle as one action kernel beside the step.  The rule itself lives in
+// include/okenv_math.h (ok_actor_partial, ok_actor_join, ok_expf, ok_actor_pick, ok_actor_eps_greedy) and is shared with
+// okActorActHost below, so the device and the host entry agree bit for bit.
+//
+// This is NOT a step kernel and adds no step-kernel launch site: it reads what the last step left (dist, crashed) and writes the
+// action the next step consumes, plus the learner's record of the step.
+#ifndef OK_ACTOR_H
+#define OK_ACTOR_H
+
+#include <vector>
+
+#include "../../include/okenv.h"
+#include "okenv_kernels.h"
+
+// What the kernel needs, by value
+struct OkActorParams
+{
+    OkDeviceState      st;
+    int                N, R;
+    const float       *policy, *value;  // parameter vectors on the device, each padded to a multiple of four floats
+    const uint32_t    *step_word;       // the handle's device-side step count (auto-reset on), or nullptr: host_steps
+    uint32_t           host_steps;
+    const uint32_t    *draw_offset;     // okenv_actor_set_draw_offset, or nullptr
+    okenv_actor_params ap;
+    okenv_actor_record rec;
+};
+
+// Lanes per agent = the rule's interleave (OK_ACTOR_LANES): lane l of a group owns the hidden units l, l + 8, ... of both networks
+// and carries one partial sum per output, so no hidden value ever leaves its lane; the partial sums meet in a butterfly of three
+// shuffles per output.  A wave holds 8 consecutive agents, a workgroup 32.
+constexpr int kActorLanes   = OK_ACTOR_LANES;
+constexpr int kActorThreads = 256;
+constexpr int kActorAgents  = kActorThreads / kActorLanes;
+
+// Row stride of the first layer's weights in LDS: odd, so that the 8 lanes of a group, which read 8 consecutive rows at the same
+// column, hit 8 different banks for every fan (the 4 groups of a 32-lane half read the same addresses: a broadcast).
+__host__ __device__ inline int okActorRowStride(const int R)
+{
+    return R | 1;
+}
+
+// LDS floats of one network's copy / of the whole launch
+__host__ __device__ inline int okActorNetFloats(const int R, const int hidden, const int out)
+{
+    return hidden > 0 ? hidden * okActorRowStride(R) + hidden + out * hidden + out : 0;
+}
+
+inline size_t okActorLdsBytes(const int R, const okenv_actor_params &ap)
+{
+    return sizeof(float) * static_cast<size_t>(okActorNetFloats(R, ap.hidden, ap.num_actions) + okActorNetFloats(R, ap.value_hidden, 1) + kActorAgents * okActorRowStride(R));
+}
+
+__device__ __forceinline__ int okActorLdsIndex(const int i, const int R, const int rp, const int n1, const int shift)
+{
+    return i < n1 ? (i / R) * rp + i % R : i + shift;
+}
+
+// One network from global memory into LDS: 16-byte loads (the vector is padded to a multiple of four floats), the first layer's
+// rows spread to the odd stride, the rest moved up behind them.
+__device__ __forceinline__ void okActorStage(float *dst, const float *src, const int R, const int hidden, const int n_params)
+{
+    const int rp = okActorRowStride(R), n1 = hidden * R, shift = hidden * (rp - R);
+    const float4 *src4 = reinterpret_cast<const float4 *>(src);
+    for (int c = static_cast<int>(threadIdx.x); 4 * c < n_params; c += kActorThreads)
+    {
+        const float4 v = src4[c];
+        const int    i = 4 * c;
+        if (i < n_params)
+            dst[okActorLdsIndex(i, R, rp, n1, shift)] = v.x;
+        if (i + 1 < n_params)
+            dst[okActorLdsIndex(i + 1, R, rp, n1, shift)] = v.y;
+        if (i + 2 < n_params)
+            dst[okActorLdsIndex(i + 2, R, rp, n1, shift)] = v.z;
+        if (i + 3 < n_params)
+            dst[okActorLdsIndex(i + 3, R, rp, n1, shift)] = v.w;
+    }
+}
+
+extern __shared__ float ok_actor_lds[];
+
+__global__ __launch_bounds__(kActorThreads) void okActorKernel(const OkActorParams p)
+{
+    const int R = p.R, H = p.ap.hidden, A = p.ap.num_actions, Hv = p.ap.value_hidden, rp = okActorRowStride(R);
+    float    *pol = ok_actor_lds, *val = pol + okActorNetFloats(R, H, A), *xs = val + okActorNetFloats(R, Hv, 1);
+    okActorStage(pol, p.policy, R, H, ok_actor_num_params(R, H, A));
+    if (Hv > 0)
+        okActorStage(val, p.value, R, Hv, ok_actor_num_params(R, Hv, 1));
+    const int  g     = static_cast<int>(threadIdx.x) / kActorLanes;
+    const int  lane  = static_cast<int>(threadIdx.x) & (kActorLanes - 1);
+    const long a_raw = static_cast<long>(blockIdx.x) * kActorAgents + g;
+    const bool valid = a_raw < p.N;
+    const long a     = valid ? a_raw : static_cast<long>(p.N) - 1; // (spare lanes of the last wave take part in the shuffles)
+    // the input, and its record slot: the group copies its row, consecutive lanes on consecutive addresses
+    float *x = xs + g * rp; // (the odd stride again: the 4 groups of a half read 4 different banks)
+    for (int i = lane; i < R; i += kActorLanes)
+    {
+        const float v = p.st.dist[a * R + i] / OK_SENSOR_RANGE;
+        x[i]          = v;
+        if (valid && p.rec.state != nullptr)
+            p.rec.state[a * R + i] = v;
+    }
+    __syncthreads();
+    float part[OK_ACTOR_MAX_ACTIONS], z[OK_ACTOR_MAX_ACTIONS];
+    ok_actor_partial(pol, rp, pol + H * rp, pol + H * rp + H, R, H, A, x, lane, part);
+    const float *b2 = pol + H * rp + H + A * H;
+#pragma unroll
+    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+    {
+        z[k] = 0.F;
+        if (k < A)
+        { // ok_actor_join's tree: lane distances 4, 2, 1
+            float v = part[k];
+            v       = v + __shfl_xor(v, 4);
+            v       = v + __shfl_xor(v, 2);
+            v       = v + __shfl_xor(v, 1);
+            z[k]    = b2[k] + v;
+        }
+    }
+    float value = 0.F;
+    if (Hv > 0)
+    {
+        ok_actor_partial(val, rp, val + Hv * rp, val + Hv * rp + Hv, R, Hv, 1, x, lane, part);
+        float v = part[0];
+        v       = v + __shfl_xor(v, 4);
+        v       = v + __shfl_xor(v, 2);
+        v       = v + __shfl_xor(v, 1);
+        value   = val[Hv * rp + Hv + Hv] + v;
+    }
+    const int      best  = ok_actor_argmax(z, A);
+    const uint32_t draw  = (p.step_word != nullptr ? p.step_word[0] : p.host_steps) + (p.draw_offset != nullptr ? p.draw_offset[0] : 0U);
+    const uint32_t agent = p.ap.agent_base + static_cast<uint32_t>(a);
+    float          mine  = z[0]; // lane k holds z_k
+#pragma unroll
+    for (int k = 1; k < OK_ACTOR_MAX_ACTIONS; ++k)
+        if (k == lane)
+            mine = z[k];
+    float prob;
+    int   action;
+    if (p.ap.mode == OKENV_ACTOR_EPS_GREEDY)
+    { // every lane of the group draws the same action; z of that action comes from the lane that holds it
+        action = ok_actor_eps_greedy(p.ap.epsilon, p.ap.seed, agent, draw, A, best);
+        prob   = __shfl(mine, action, kActorLanes);
+    }
+    else
+    { // the exponentials: lane k takes e_k (an fp64 evaluation each), every lane collects them
+        float m = z[0];
+#pragma unroll
+        for (int k = 1; k < OK_ACTOR_MAX_ACTIONS; ++k)
+            if (k < A && z[k] > m)
+                m = z[k];
+        const float el = lane < A ? ok_expf(mine - m) : 0.F;
+        float       e[OK_ACTOR_MAX_ACTIONS];
+#pragma unroll
+        for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+            e[k] = __shfl(el, k, kActorLanes);
+        const float u = p.ap.mode == OKENV_ACTOR_SAMPLE ? ok_u01(ok_actor_draw(p.ap.seed, agent, draw).v[0]) : 0.F;
+        action        = ok_actor_pick(e, A, u, p.ap.mode == OKENV_ACTOR_GREEDY ? best : -1, &prob);
+    }
+    if (lane != 0 || !valid)
+        return;
+    float thr = p.ap.action_table[0][0], steer = p.ap.action_table[0][1];
+#pragma unroll
+    for (int k = 1; k < OK_ACTOR_MAX_ACTIONS; ++k)
+        if (k == action)
+        {
+            thr   = p.ap.action_table[k][0];
+            steer = p.ap.action_table[k][1];
+        }
+    p.st.thr[a]   = thr;
+    p.st.steer[a] = steer;
+    if (p.rec.action != nullptr)
+        p.rec.action[a] = action;
+    if (p.rec.prob != nullptr)
+        p.rec.prob[a] = prob;
+    if (p.rec.value != nullptr && Hv > 0)
+        p.rec.value[a] = value;
+    if (p.rec.alive != nullptr)
+        p.rec.alive[a] = p.st.crashed[a] ? 0 : 1;
+}
+
+// ---- host side (no GPU) ------------------------------------------------------------------------------------------------------
+
+inline const char *okActorCheckParams(const okenv_actor_params *ap, const int R)
+{
+    if (ap == nullptr)
+        return "params is NULL";
+    if (R < 1 || R > OK_ACTOR_MAX_RAYS)
+        return "the fan needs 1 .. 64 rays";
+    if (ap->hidden < 1 || ap->hidden > OK_ACTOR_MAX_HIDDEN)
+        return "hidden width outside 1 .. 256";
+    if (ap->num_actions < 2 || ap->num_actions > OK_ACTOR_MAX_ACTIONS)
+        return "number of actions outside 2 .. 8";
+    if (ap->value_hidden < 0 || ap->value_hidden > OK_ACTOR_MAX_HIDDEN)
+        return "value network's hidden width outside 0 .. 256";
+    if (ap->mode != OKENV_ACTOR_SAMPLE && ap->mode != OKENV_ACTOR_GREEDY && ap->mode != OKENV_ACTOR_EPS_GREEDY)
+        return "unknown mode (OKENV_ACTOR_SAMPLE / _GREEDY / _EPS_GREEDY)";
+    if (!(ap->epsilon >= 0.F && ap->epsilon <= 1.F))
+        return "epsilon outside [0, 1]";
+    return nullptr;
+}
+
+// updateAction for n agents on host arrays; every output may be nullptr
+inline void okActorActHost(const okenv_actor_params &ap, const float *policy, const float *value, const int R, const int n, const float *dist,
+                           const uint8_t *crashed, const uint32_t draw_index, float *throttle, float *steer, int64_t *action, float *prob,
+                           float *value_out, float *state, uint8_t *alive)
+{
+    std::vector<float> x(static_cast<size_t>(R));
+    for (int a = 0; a < n; ++a)
+    {
+        float     pr = 0.F, v = 0.F;
+        const int act = ok_actor_agent(policy, value, R, ap.hidden, ap.num_actions, ap.value_hidden, ap.mode, ap.epsilon, ap.seed,
+                                       ap.agent_base + static_cast<uint32_t>(a), draw_index, dist + static_cast<size_t>(a) * R, x.data(), &pr, &v);
+        if (throttle != nullptr)
+            throttle[a] = ap.action_table[act][0];
+        if (steer != nullptr)
+            steer[a] = ap.action_table[act][1];
+        if (action != nullptr)
+            action[a] = act;
+        if (prob != nullptr)
+            prob[a] = pr;
+        if (value_out != nullptr && ap.value_hidden > 0)
+            value_out[a] = v;
+        if (state != nullptr)
+            for (int i = 0; i < R; ++i)
+                state[static_cast<size_t>(a) * R + i] = x[static_cast<size_t>(i)];
+        if (alive != nullptr)
+            alive[a] = (crashed != nullptr && crashed[a]) ? 0 : 1;
+    }
+}
+
+#endif // OK_ACTOR_H

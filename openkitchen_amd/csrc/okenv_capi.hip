@@ -22,6 +22,7 @@
 #include "ok_grid.h"
 #include "ok_render.h"
 #include "okenv_kernels.h"
+#include "ok_actor.h"
 #include "ok_expert.h"
 
 namespace
@@ -462,6 +463,11 @@ struct okenv
     bool                expert_ok{false};
     okenv_expert_params expert{};
     double             *d_expert_tab{nullptr};
+    // shared-network actors (okenv_actor_create): parameters, the two networks' vectors (padded to four floats) and what has been set
+    bool               actor_ok{false}, actor_policy_set{false}, actor_value_set{false};
+    okenv_actor_params actor{};
+    float             *d_actor_policy{nullptr}, *d_actor_value{nullptr};
+    const uint32_t    *actor_draw_offset{nullptr};
 };
 
 struct okenv_track
@@ -2206,6 +2212,138 @@ extern "C"
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_expert_normalize_angle: bad argument");
         for (int32_t i = 0; i < n; ++i)
             out[i] = ok_expert_normalize_angle_deg(angle_deg[i]);
+        return OKENV_OK;
+    }
+
+    // ---- shared-network actors (RLRacers/PPO, Reinforce, Deep_Q_Learning) --------------------------------------------------
+
+    int okenv_actor_create(okenv_t h, const okenv_actor_params *params)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_actor_create: NULL handle");
+        if (const char *why = okActorCheckParams(params, h->shape.R))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_actor_create: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        // room for the widest networks of this fan, so that a later create with other widths allocates nothing
+        const size_t cap = static_cast<size_t>(ok_actor_num_params(h->shape.R, OK_ACTOR_MAX_HIDDEN, OK_ACTOR_MAX_ACTIONS)) + 4U;
+        int          rc  = devEnsure(h, &h->d_actor_policy, cap);
+        if (rc != OKENV_OK || (rc = devEnsure(h, &h->d_actor_value, cap)) != OKENV_OK)
+            return rc;
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okActorKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(kLdsBudget)));
+        h->actor            = *params;
+        h->actor_ok         = true;
+        h->actor_policy_set = false;
+        h->actor_value_set  = false;
+        return OKENV_OK;
+    }
+
+    int okenv_actor_num_params(okenv_t h, int32_t *policy, int32_t *value)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_num_params: call okenv_actor_create first");
+        if (policy)
+            *policy = ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions);
+        if (value)
+            *value = h->actor.value_hidden > 0 ? ok_actor_num_params(h->shape.R, h->actor.value_hidden, 1) : 0;
+        return OKENV_OK;
+    }
+
+    int okenv_actor_set_params(okenv_t h, const float *policy, const float *value)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_set_params: call okenv_actor_create first");
+        if (value != nullptr && h->actor.value_hidden == 0)
+            return fail(h, OKENV_ERR_INVALID, "okenv_actor_set_params: the actor has no value network");
+        OK_HIP(h, hipSetDevice(h->device));
+        int rc = OKENV_OK;
+        if (policy != nullptr)
+        {
+            rc = copyAny(h, h->d_actor_policy, policy, sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions)));
+            if (rc != OKENV_OK)
+                return rc;
+            h->actor_policy_set = true;
+        }
+        if (value != nullptr)
+        {
+            rc = copyAny(h, h->d_actor_value, value, sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.value_hidden, 1)));
+            if (rc != OKENV_OK)
+                return rc;
+            h->actor_value_set = true;
+        }
+        return OKENV_OK;
+    }
+
+    int okenv_actor_set_epsilon(okenv_t h, float epsilon)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_set_epsilon: call okenv_actor_create first");
+        if (!(epsilon >= 0.F && epsilon <= 1.F))
+            return fail(h, OKENV_ERR_INVALID, "okenv_actor_set_epsilon: epsilon outside [0, 1]");
+        h->actor.epsilon = epsilon;
+        return OKENV_OK;
+    }
+
+    int okenv_actor_set_draw_offset(okenv_t h, const uint32_t *device_word)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_set_draw_offset: call okenv_actor_create first");
+        h->actor_draw_offset = device_word;
+        return OKENV_OK;
+    }
+
+    int okenv_actor_act(okenv_t h, const okenv_actor_record *rec)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_actor_act: NULL handle");
+        if (!h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_act: call okenv_actor_create first");
+        if (!h->actor_policy_set || (h->actor.value_hidden > 0 && !h->actor_value_set))
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_act: call okenv_actor_set_params first (every attached network needs its parameters)");
+        dropEpisode(h);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkActorParams p{};
+        p.st          = h->st;
+        p.N           = h->shape.N;
+        p.R           = h->shape.R;
+        p.policy      = h->d_actor_policy;
+        p.value       = h->d_actor_value;
+        p.step_word   = (h->reset_flags & kAutoResetOn) != 0U ? h->d_step_count : nullptr; // (the step kernels advance it only then)
+        p.host_steps  = h->step_count;
+        p.draw_offset = h->actor_draw_offset;
+        p.ap          = h->actor;
+        if (rec != nullptr)
+            p.rec = *rec;
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
+        hipLaunchKernelGGL(okActorKernel, dim3(blocks), dim3(kActorThreads), okActorLdsBytes(h->shape.R, h->actor), h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_actor_act_host(const okenv_actor_params *params, const float *policy, const float *value, int32_t num_rays, int32_t n, const float *dist,
+                             const uint8_t *crashed, uint32_t draw_index, float *throttle, float *steer, int64_t *action, float *prob,
+                             float *value_out, float *state, uint8_t *alive)
+    {
+        if (const char *why = okActorCheckParams(params, num_rays))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_actor_act_host: ") + why);
+        if (!policy || n < 0 || !dist || (params->value_hidden > 0 && !value))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_actor_act_host: bad argument");
+        okActorActHost(*params, policy, value, num_rays, n, dist, crashed, draw_index, throttle, steer, action, prob, value_out, state, alive);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_expf(const float *x, float *out, int32_t n)
+    {
+        if (!x || !out || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_expf: bad argument");
+        for (int32_t i = 0; i < n; ++i)
+            out[i] = ok_expf(x[i]);
         return OKENV_OK;
     }
 

@@ -456,6 +456,66 @@ class BatchedEnvironment:
             setattr(rec, k, int(v))
         capi.check(self._L.okenv_expert_act(self._h, C.byref(rec)), self._h)
 
+    # ---- shared-network actors (include/okenv.h) ---------------------------------------------------
+    def actor_create(self, hidden, actions, value_hidden=0, mode="sample", epsilon=0.0, seed=0, agent_base=0):
+        """Attaches a shared-network actor (policy R -> hidden -> len(actions), optional value network R -> value_hidden -> 1)
+        to the handle; actions: the table [(throttle_delta, steering_delta), ...].  Returns (policy floats, value floats)."""
+        ap = capi.actor_params(hidden, actions, value_hidden, mode, epsilon, seed, agent_base)
+        capi.check(self._L.okenv_actor_create(self._h, C.byref(ap)), self._h)
+        self.actor_params = ap
+        return self.actor_num_params()
+
+    def actor_num_params(self):
+        a, b = C.c_int32(), C.c_int32()
+        capi.check(self._L.okenv_actor_num_params(self._h, C.byref(a), C.byref(b)), self._h)
+        return a.value, b.value
+
+    def actor_set_params(self, policy=None, value=None):
+        """New parameter vectors (torch's parameters() order, flattened) from float32 numpy arrays or device tensors; None
+        leaves a network as it is.  Enqueued on the handle's stream, no synchronisation for device tensors."""
+        n_policy, n_value = self.actor_num_params()
+        keep = []
+        for v, n in ((policy, n_policy), (value, n_value)):
+            if v is None:
+                keep.append(None)
+                continue
+            if isinstance(v, np.ndarray):
+                v = np.ascontiguousarray(v, dtype=np.float32).ravel()
+                assert v.size == n, "expected %d parameters, got %d" % (n, v.size)
+            else:
+                assert v.is_contiguous() and v.numel() == n and v.element_size() == 4, "expected %d float32 parameters" % n
+            keep.append(v)
+        capi.check(self._L.okenv_actor_set_params(self._h, capi.ptr(keep[0]), capi.ptr(keep[1])), self._h)
+        if any(isinstance(v, np.ndarray) for v in keep):
+            self.sync()  # the host arrays are temporaries
+
+    def actor_set_epsilon(self, epsilon):
+        capi.check(self._L.okenv_actor_set_epsilon(self._h, float(epsilon)), self._h)
+
+    def actor_set_draw_offset(self, word=None):
+        """A device uint32 word (tensor or address) added to the draw index of every later actor_act; None removes it."""
+        capi.check(self._L.okenv_actor_set_draw_offset(self._h, capi.ptr(word)), self._h)
+
+    def actor_act(self, record=None):
+        """updateAction of the shared-network agents for every agent, enqueued on the handle's stream without a synchronisation.
+        record: None, or a dict of device tensors / addresses under "state" [N,R] float32, "action" [N] int64, "prob" [N] float32,
+        "value" [N] float32 and "alive" [N] uint8, each optional, that receive this step's sample."""
+        if record is None:
+            capi.check(self._L.okenv_actor_act(self._h, None), self._h)
+            return
+        rec = capi.OkenvActorRecord()
+        sizes = {"state": self.N * self.R * 4, "action": self.N * 8, "prob": self.N * 4, "value": self.N * 4, "alive": self.N}
+        for k, v in record.items():
+            if k not in sizes:
+                raise KeyError("unknown record slot %r" % k)
+            if v is None:
+                continue
+            if hasattr(v, "data_ptr"):
+                assert v.is_contiguous() and v.numel() * v.element_size() >= sizes[k], "record slot %r is too small" % k
+                v = v.data_ptr()
+            setattr(rec, k, int(v))
+        capi.check(self._L.okenv_actor_act(self._h, C.byref(rec)), self._h)
+
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):
         """{rays, tests, cells, points} the broad phase leaves for the current poses (okenv_work_stats)."""
@@ -527,6 +587,38 @@ def expert_act_host(params, ray_angles_deg, pos_x, pos_y, rot, dist, centerline=
                                                  capi.ptr(cy), P, n, capi.ptr(pos_x), capi.ptr(pos_y), capi.ptr(rot), capi.ptr(dist), capi.ptr(gx),
                                                  capi.ptr(gy), capi.ptr(thr), capi.ptr(steer)))
     return thr, steer
+
+
+def actor_act_host(params, policy, value, dist, crashed=None, draw_index=0):
+    """The shared-network actors' rule on host arrays, no GPU needed (okenv_actor_act_host).  params: capi.actor_params(...);
+    policy / value: flattened float32 parameter vectors (value None without a value network); dist [n, R].  Returns a dict:
+    throttle, steer, prob [n] float32, action [n] int64, state [n, R] float32, alive [n] uint8 and, with a value network, value."""
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    n, R = dist.shape
+    policy = None if policy is None else np.ascontiguousarray(policy, dtype=np.float32).ravel()
+    value = None if value is None else np.ascontiguousarray(value, dtype=np.float32).ravel()
+    if params is not None and policy is not None:
+        assert policy.size == params.hidden * R + params.hidden + params.num_actions * params.hidden + params.num_actions
+        assert value is None or value.size == params.value_hidden * R + 2 * params.value_hidden + 1
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, dtype=np.uint8)
+    out = {"throttle": np.zeros(n, np.float32), "steer": np.zeros(n, np.float32), "action": np.zeros(n, np.int64),
+           "prob": np.zeros(n, np.float32), "value": np.zeros(n, np.float32), "state": np.zeros((n, R), np.float32),
+           "alive": np.zeros(n, np.uint8)}
+    capi.check(capi.load().okenv_actor_act_host(C.byref(params) if params is not None else None, capi.ptr(policy), capi.ptr(value), R, n,
+                                                capi.ptr(dist), capi.ptr(crashed), int(draw_index) & 0xFFFFFFFF, capi.ptr(out["throttle"]),
+                                                capi.ptr(out["steer"]), capi.ptr(out["action"]), capi.ptr(out["prob"]), capi.ptr(out["value"]),
+                                                capi.ptr(out["state"]), capi.ptr(out["alive"])))
+    if params.value_hidden == 0:
+        del out["value"]
+    return out
+
+
+def debug_expf(x):
+    """ok_expf (the actors' softmax) on a host array (no GPU)."""
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.zeros_like(a)
+    capi.check(capi.load().okenv_debug_expf(capi.ptr(a), capi.ptr(out), a.size))
+    return out
 
 
 def debug_atan2f(y, x):

@@ -210,6 +210,72 @@ class VectorEnvironment:
         device tensors ("action" [N,2], "dist" [N,R], "rel_xy" [N,R,2] float32, "alive" [N] uint8) that receive the sample."""
         self.env.expert_act(record)
 
+    # ---- shared-network actors (include/okenv.h, DESIGN.md section 14) -------------------------------------------------------
+    @staticmethod
+    def _network_tensors(net, what):
+        """[l1.weight, l1.bias, l2.weight, l2.bias] of Sequential(Linear, ReLU, Linear[, Softmax]) or of four raw tensors."""
+        if isinstance(net, torch.nn.Module):
+            mods = list(net.children()) if isinstance(net, torch.nn.Sequential) else None
+            if mods is not None and len(mods) == 4 and isinstance(mods[3], torch.nn.Softmax):
+                mods = mods[:3]
+            if (mods is None or len(mods) != 3 or not isinstance(mods[0], torch.nn.Linear) or not isinstance(mods[1], torch.nn.ReLU)
+                    or not isinstance(mods[2], torch.nn.Linear) or mods[0].bias is None or mods[2].bias is None):
+                raise ValueError("%s: expected torch.nn.Sequential(Linear, ReLU, Linear[, Softmax]) with biases" % what)
+            return [mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias]
+        t = list(net)
+        if len(t) != 4 or not all(torch.is_tensor(x) for x in t):
+            raise ValueError("%s: expected a module or the four tensors l1.weight, l1.bias, l2.weight, l2.bias" % what)
+        return t
+
+    def _check_network(self, t, what, outputs=None):
+        w1, b1, w2, b2 = t
+        hidden = w1.shape[0] if w1.dim() == 2 else -1
+        out = w2.shape[0] if w2.dim() == 2 else -1
+        if (tuple(w1.shape) != (hidden, self.num_rays) or tuple(b1.shape) != (hidden,) or tuple(w2.shape) != (out, hidden)
+                or tuple(b2.shape) != (out,) or (outputs is not None and out != outputs)):
+            raise ValueError("%s: shapes %s do not form a %d -> H -> %s network" % (what, [tuple(x.shape) for x in t], self.num_rays,
+                                                                                 "A" if outputs is None else outputs))
+        if not 1 <= hidden <= capi.ACTOR_MAX_HIDDEN:
+            raise ValueError("%s: hidden width %d outside 1 .. %d" % (what, hidden, capi.ACTOR_MAX_HIDDEN))
+        return hidden, out
+
+    def enable_actor(self, actor, critic=None, mode="sample", actions=None, epsilon=0.0):
+        """Attaches the reference's shared-network agent (RLRacers/PPO, Reinforce, Deep_Q_Learning): `actor` is
+        torch.nn.Sequential(Linear(R, H), ReLU, Linear(H, A)[, Softmax]) or its four parameter tensors, `critic` optionally the
+        same with one output; mode "sample" (PPO, REINFORCE), "greedy" or "eps_greedy" (Deep-Q, with `epsilon`); `actions` the
+        table [(throttle, steering), ...] of A rows, default PPOAgent::kActionMap.  The modules are remembered: sync_actor() hands
+        their current parameters to the device actor (call it after every optimiser step)."""
+        from .rollout import PPO_ACTIONS
+        actions = PPO_ACTIONS if actions is None else actions
+        self._actor_nets = (self._network_tensors(actor, "actor"), None if critic is None else self._network_tensors(critic, "critic"))
+        hidden, n_actions = self._check_network(self._actor_nets[0], "actor")
+        if n_actions != len(actions) or not 2 <= n_actions <= capi.ACTOR_MAX_ACTIONS:
+            raise ValueError("actor: %d outputs for a table of %d actions (2 .. %d)" % (n_actions, len(actions), capi.ACTOR_MAX_ACTIONS))
+        value_hidden = 0 if critic is None else self._check_network(self._actor_nets[1], "critic", outputs=1)[0]
+        self.env.actor_create(hidden, actions, value_hidden, mode, epsilon, self.seed, self.agent_base)
+        self.actor_has_value = critic is not None
+        self._actor_graphs = {}
+        self.sync_actor()
+
+    def sync_actor(self):
+        """The current parameters of the networks given to enable_actor, flattened in parameters() order and copied device to
+        device on the environment's stream: no host hop, no synchronisation."""
+        flat = [None if t is None else torch.cat([x.detach().reshape(-1) for x in t]).to(device=self.device, dtype=torch.float32).contiguous()
+                for t in self._actor_nets]
+        self.env.actor_set_params(flat[0], flat[1])
+        self._actor_flat = flat  # alive until the next hand-over: the copy is asynchronous
+
+    def set_actor_epsilon(self, epsilon):
+        self.env.actor_set_epsilon(epsilon)
+        self._actor_graphs = {}  # a captured launch carries the old value
+
+    def actor_act(self, record=None):
+        """updateAction of the shared-network agents for every agent from the last observation, written into `throttle` /
+        `steering`: one kernel on the environment's stream, no synchronisation, usable inside capture(body).  record: optional
+        dict of device tensors ("state" [N,R] float32, "action" [N] int64, "prob" [N] float32, "value" [N] float32, "alive" [N]
+        uint8 or bool) that receive the sample."""
+        self.env.actor_act(record)
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
