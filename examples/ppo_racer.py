@@ -1,10 +1,14 @@
 """PPO racers on the device environment: the reference's RLRacers/PPO app (ppo_sim.cpp + PPOAgent.hpp) for thousands of
 agents, with the environment, resets and reward bookkeeping on the GPU and the learner in PyTorch-ROCm.
 
-    python examples/ppo_racer.py [--agents 1024] [--episodes 20] [--track Silverstone] [--device-actor [--graph-chunk 32]]
+    python examples/ppo_racer.py [--agents 1024] [--episodes 20] [--track Silverstone] [--device-actor [--graph-chunk 32]] [--device-batch]
 
 --device-actor: the agents act on the device too (okenv_actor_act): one kernel per step evaluates actor and
 critic, samples and records the step, and --graph-chunk K replays K such iterations as one HIP graph.
+
+--device-batch: the episode becomes the training set on the device (rollout.prepare_batch): returns, their
+normalisation over the alive samples and the packing of those samples in five kernels instead of a Python loop over the rows and
+five masked selections; the time of that stage is printed on its own.
 
 Per episode (ppo_sim.cpp:49-89): resetAgent to random centre-line points, one observation step, then act / step until
 every agent has crashed; then PPOAgent::updatePolicy (PPOAgent.hpp:106-160): discounted returns (gamma 0.99,
@@ -21,7 +25,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from openkitchen_amd.rollout import collect_episode, collect_episode_device, discounted_returns  # noqa: E402
+from openkitchen_amd.rollout import collect_episode, collect_episode_device, discounted_returns, prepare_batch  # noqa: E402
 from openkitchen_amd.torch_env import VectorEnvironment  # noqa: E402
 
 
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device-actor", action="store_true", help="act with the device actor kernel instead of the PyTorch forward")
     ap.add_argument("--graph-chunk", type=int, default=32, help="with --device-actor: iterations per replayed HIP graph (0: eager)")
+    ap.add_argument("--device-batch", action="store_true", help="build the training set with the device kernels (rollout.prepare_batch)")
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     rays = np.array([-70, -30, 0, 30, 70], dtype=np.float32)          # PPOAgent.hpp:56-61
@@ -54,12 +59,20 @@ def main():
             ep = collect_episode(venv, actor, max_steps=args.max_steps)
         alive = ep["alive"]
         lengths = alive.sum(dim=0).float()
-        returns = discounted_returns(ep["rewards"] * alive)          # reward only while the agent is driving
-        mask = alive.reshape(-1)
-        states = ep["states"].reshape(-1, 5)[mask]
-        actions = ep["actions"].reshape(-1, 1)[mask]
-        old_logp = ep["log_probs"].reshape(-1, 1)[mask]
-        ret = returns.reshape(-1, 1)[mask]
+        if args.device_batch:
+            torch.cuda.synchronize()
+            tb = time.perf_counter()
+            data = prepare_batch(venv, ep, gamma=0.99, normalize="returns")  # returns normalised over the alive samples
+            states, actions, old_logp, ret = data["states"], data["actions"].unsqueeze(1), data["log_probs"].unsqueeze(1), data["returns"].unsqueeze(1)
+            torch.cuda.synchronize()
+            t_batch = time.perf_counter() - tb
+        else:
+            returns = discounted_returns(ep["rewards"] * alive)          # reward only while the agent is driving
+            mask = alive.reshape(-1)
+            states = ep["states"].reshape(-1, 5)[mask]
+            actions = ep["actions"].reshape(-1, 1)[mask]
+            old_logp = ep["log_probs"].reshape(-1, 1)[mask]
+            ret = returns.reshape(-1, 1)[mask]
         t1 = time.perf_counter()
         for _ in range(epochs):
             perm = torch.randperm(states.shape[0], device=states.device)
@@ -79,8 +92,9 @@ def main():
                 opt_c.step()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-        print("episode %3d: %5d steps, mean episode length %7.1f (max %5d), %7d samples, rollout %.2f s, update %.2f s" % (
-            episode, ep["states"].shape[0], float(lengths.mean()), int(lengths.max()), states.shape[0], t1 - t0, t2 - t1), flush=True)
+        print("episode %3d: %5d steps, mean episode length %7.1f (max %5d), %7d samples, rollout %.2f s, update %.2f s%s" % (
+            episode, ep["states"].shape[0], float(lengths.mean()), int(lengths.max()), states.shape[0], t1 - t0, t2 - t1,
+            ", of the rollout the batch %.4f s" % t_batch if args.device_batch else ""), flush=True)
     return float(lengths.mean())
 
 

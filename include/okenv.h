@@ -345,6 +345,75 @@ OKENV_API int okenv_actor_act_host(const okenv_actor_params *params, const float
                                    const float *dist, const uint8_t *crashed, uint32_t draw_index, float *throttle, float *steer,
                                    int64_t *action, float *prob, float *value_out, float *state, uint8_t *alive);
 
+/* ---- from a recorded episode to the learner's batch ------------------------------------------------------
+ * The data side of the reference's updatePolicy (RLRacers/PPO/ExperienceBuffer.hpp:15-68, ReinforceAgent.hpp:94-106,
+ * GCLAgent.hpp:75-84,137-148) for a record of T step rows and N agent columns, as okenv_actor_act leaves it: discounted returns per
+ * agent column with `alive` as the episode boundary, optionally GAE(lambda) advantages from the recorded values, their statistics
+ * over the alive samples in an order no launch shape can change, the normalisation, and the alive samples packed densely in
+ * step-major, agent-minor order.  The rule is written out in include/okenv_batch.h (ok_batch_*). */
+#define OKENV_BATCH_NORMALIZE_RETURN 1u    /* the dense `ret` is (G - mean) / (std + FLT_EPSILON) */
+#define OKENV_BATCH_NORMALIZE_ADVANTAGE 2u /* the dense `adv` likewise                            */
+
+typedef struct okenv_batch_params {
+    int32_t  num_steps;     /* T >= 1                                                                              */
+    int32_t  num_agents;    /* N >= 1, T * N < 2^31 (not necessarily the handle's population)                     */
+    int32_t  state_width;   /* R: floats per row of `state` (>= 1 when state is gathered)                          */
+    int32_t  record_stride; /* agent slots between two rows of reward / alive / value; 0: N, else >= N             */
+    int32_t  field_stride;  /* the same for state / action / prob                                                  */
+    float    gamma;         /* [0, 1]                                                                              */
+    float    lambda;        /* [0, 1]; read only with a value plane                                                */
+    uint32_t normalize;     /* OKENV_BATCH_NORMALIZE_* bits                                                        */
+    int32_t  block_threads; /* workgroup size of the column walk: 0 (the default, 64) or 64 / 128 / 256 / 512 / 1024;
+                               no output depends on it                                                             */
+} okenv_batch_params;
+
+/* The record: device pointers (host pointers for okenv_batch_prepare_host).  reward and alive are required. */
+typedef struct okenv_batch_input {
+    const float   *reward;     /* [T][stride]      */
+    const uint8_t *alive;      /* [T][stride]      non-zero: the agent produced this sample while driving */
+    const float   *value;      /* [T][stride]      or NULL: no advantages */
+    const float   *last_value; /* [N]              or NULL: the value after the last row, for columns still alive there */
+    const float   *state;      /* [T][stride][R]   or NULL */
+    const int64_t *action;     /* [T][stride]      or NULL */
+    const float   *prob;       /* [T][stride]      or NULL: any per-sample fp32 field (the probability, or its logarithm) */
+} okenv_batch_input;
+
+/* Over the alive samples; sums in fp64, the order fixed by the rule.  The *_adv members are 0 without a value plane. */
+typedef struct okenv_batch_stats {
+    double  sum_ret, sumsq_ret, sum_adv, sumsq_adv;
+    float   mean_ret, std_ret, mean_adv, std_adv; /* fp64 results rounded once; std is the unbiased estimate, 0 for M < 2 */
+    int32_t count;                                /* M */
+    int32_t reserved;
+} okenv_batch_stats;
+
+/* Where the batch goes: device pointers (host pointers for okenv_batch_prepare_host), each may be NULL (skipped).  The dense
+ * outputs need room for T * N samples; their first M entries are written. */
+typedef struct okenv_batch_output {
+    float             *state;     /* [M][R]  needs input state                                               */
+    int64_t           *action;    /* [M]     needs input action                                              */
+    float             *prob;      /* [M]     needs input prob                                                */
+    float             *ret;       /* [M]     G, normalised with OKENV_BATCH_NORMALIZE_RETURN                 */
+    float             *adv;       /* [M]     A, normalised with OKENV_BATCH_NORMALIZE_ADVANTAGE; needs value */
+    int32_t           *index;     /* [M]     t * N + i of sample k                                           */
+    float             *ret_plane; /* [T][N]  G, never normalised, 0 where not alive                          */
+    float             *adv_plane; /* [T][N]  A likewise; needs value                                         */
+    okenv_batch_stats *stats;
+    int32_t           *count;     /* M as a device word                                                      */
+} okenv_batch_output;
+
+/* Enqueues the whole preparation on the handle's stream: five kernels, no synchronisation, and no allocation after the first
+ * call of a given T and N (the scratch belongs to the handle).  The handle lends its device, stream and scratch; the record is the
+ * caller's.  OKENV_ERR_INVALID for a NULL handle, struct, reward or alive, T or N < 1, T * N >= 2^31, gamma or lambda NaN or
+ * outside [0, 1], a stride smaller than N, unknown normalize bits, a block_threads not listed above, an output whose input is
+ * missing (adv / adv_plane without value, state / action / prob without theirs, state with state_width < 1), last_value without
+ * value. */
+OKENV_API int okenv_batch_prepare(okenv_t h, const okenv_batch_params *params, const okenv_batch_input *in, const okenv_batch_output *out);
+/* M of the handle's latest okenv_batch_prepare: waits for the stream and reads the one word the caller needs to size its views.
+ * OKENV_ERR_STATE before the first okenv_batch_prepare. */
+OKENV_API int okenv_batch_count(okenv_t h, int32_t *count);
+/* The same rule on host arrays, no GPU needed; *count (may be NULL) receives M. */
+OKENV_API int okenv_batch_prepare_host(const okenv_batch_params *params, const okenv_batch_input *in, const okenv_batch_output *out, int32_t *count);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.
@@ -620,6 +689,9 @@ OKENV_API int okenv_debug_atan2f(const float *y, const float *x, float *out, int
 OKENV_API int okenv_debug_expert_normalize_angle(const float *angle_deg, float *out, int32_t n);
 /* ok_expf (the actors' softmax) on a host array; host only, no GPU. */
 OKENV_API int okenv_debug_expf(const float *x, float *out, int32_t n);
+/* Device milliseconds of the five kernels of the handle's latest okenv_batch_prepare (walk, tree, count, scan, gather), from events
+ * it records between them while okenv_set_timing is on; waits for the last one.  OKENV_ERR_STATE when that call ran untimed. */
+OKENV_API int okenv_debug_batch_timing(okenv_t h, double *ms5);
 /* ok_sincosf evaluated on the GPU (n values, host pointers). */
 OKENV_API int okenv_debug_sincos(int32_t device, const float *x, float *s, float *c, int32_t n);
 /* First-hit parameter t for n arbitrary rays (origin, angle [rad]) through the handle's grid (host pointers). */

@@ -39,6 +39,9 @@ EXPERT_KINDS = {"potfield": EXPERT_POTFIELD, "vfh": EXPERT_VFH}
 ACTOR_SAMPLE, ACTOR_GREEDY, ACTOR_EPS_GREEDY = 0, 1, 2
 ACTOR_MODES = {"sample": ACTOR_SAMPLE, "greedy": ACTOR_GREEDY, "eps_greedy": ACTOR_EPS_GREEDY}
 ACTOR_MAX_RAYS, ACTOR_MAX_HIDDEN, ACTOR_MAX_ACTIONS = 64, 256, 8
+# episode -> batch (include/okenv.h)
+BATCH_NORMALIZE_RETURN, BATCH_NORMALIZE_ADVANTAGE = 1, 2
+BATCH_KERNELS = ("walk", "tree", "count", "scan", "gather")
 
 # every symbol include/okenv.h declares (tests/test_capi_symbols.py checks the library exports them all)
 SYMBOLS = [
@@ -64,6 +67,7 @@ SYMBOLS = [
     "okenv_debug_plan_step",
     "okenv_actor_create", "okenv_actor_num_params", "okenv_actor_set_params", "okenv_actor_set_epsilon", "okenv_actor_set_draw_offset",
     "okenv_actor_act", "okenv_actor_act_host", "okenv_debug_expf",
+    "okenv_batch_prepare", "okenv_batch_count", "okenv_batch_prepare_host", "okenv_debug_batch_timing",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -129,6 +133,36 @@ def actor_params(hidden, actions, value_hidden=0, mode="sample", epsilon=0.0, se
     for k, (thr, steer) in enumerate(list(actions)[:ACTOR_MAX_ACTIONS]):
         ap.action_table[k][0], ap.action_table[k][1] = float(thr), float(steer)
     return ap
+
+
+class OkenvBatchParams(C.Structure):
+    _fields_ = [("num_steps", C.c_int32), ("num_agents", C.c_int32), ("state_width", C.c_int32), ("record_stride", C.c_int32),
+                ("field_stride", C.c_int32), ("gamma", C.c_float), ("lam", C.c_float), ("normalize", C.c_uint32), ("block_threads", C.c_int32)]
+
+
+class OkenvBatchInput(C.Structure):
+    _fields_ = [("reward", C.c_void_p), ("alive", C.c_void_p), ("value", C.c_void_p), ("last_value", C.c_void_p), ("state", C.c_void_p),
+                ("action", C.c_void_p), ("prob", C.c_void_p)]
+
+
+class OkenvBatchStats(C.Structure):
+    _fields_ = [("sum_ret", C.c_double), ("sumsq_ret", C.c_double), ("sum_adv", C.c_double), ("sumsq_adv", C.c_double),
+                ("mean_ret", C.c_float), ("std_ret", C.c_float), ("mean_adv", C.c_float), ("std_adv", C.c_float),
+                ("count", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OkenvBatchOutput(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("action", C.c_void_p), ("prob", C.c_void_p), ("ret", C.c_void_p), ("adv", C.c_void_p),
+                ("index", C.c_void_p), ("ret_plane", C.c_void_p), ("adv_plane", C.c_void_p), ("stats", C.c_void_p), ("count", C.c_void_p)]
+
+
+BATCH_STATS_BYTES = C.sizeof(OkenvBatchStats)  # 56
+
+
+def batch_stats_dict(raw):
+    """okenv_batch_stats from its 56 bytes (a numpy uint8 array, or anything np.frombuffer takes) as a dict."""
+    s = OkenvBatchStats.from_buffer_copy(np.ascontiguousarray(raw).tobytes()[:BATCH_STATS_BYTES])
+    return {name: getattr(s, name) for name, _ in s._fields_ if name != "reserved"}
 
 
 PLAN_FIRST_ROLLOUT = -2
@@ -294,6 +328,10 @@ def load(build_if_missing=True):
     L.okenv_actor_act.argtypes = [vp, C.POINTER(OkenvActorRecord)]
     L.okenv_actor_act_host.argtypes = [C.POINTER(OkenvActorParams), vp, vp, i32, i32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     L.okenv_debug_expf.argtypes = [vp, vp, i32]
+    L.okenv_batch_prepare.argtypes = [vp, C.POINTER(OkenvBatchParams), C.POINTER(OkenvBatchInput), C.POINTER(OkenvBatchOutput)]
+    L.okenv_batch_count.argtypes = [vp, C.POINTER(i32)]
+    L.okenv_batch_prepare_host.argtypes = [C.POINTER(OkenvBatchParams), C.POINTER(OkenvBatchInput), C.POINTER(OkenvBatchOutput), C.POINTER(i32)]
+    L.okenv_debug_batch_timing.argtypes = [vp, vp]
     _lib = L
     return L
 

@@ -23,6 +23,7 @@
 #include "ok_render.h"
 #include "okenv_kernels.h"
 #include "ok_actor.h"
+#include "ok_batch.h"
 #include "ok_expert.h"
 
 namespace
@@ -468,6 +469,13 @@ struct okenv
     okenv_actor_params actor{};
     float             *d_actor_policy{nullptr}, *d_actor_value{nullptr};
     const uint32_t    *actor_draw_offset{nullptr};
+    // episode -> batch (okenv_batch_prepare): scratch for the planes, column partials, group counts, statistics and M; grown, never
+    // shrunk; the events exist only while okenv_set_timing is on
+    uint8_t   *d_batch{nullptr};
+    size_t     batch_bytes{0};
+    int32_t   *d_batch_count{nullptr};
+    bool       batch_timed{false};
+    hipEvent_t batch_events[6]{};
 };
 
 struct okenv_track
@@ -1344,6 +1352,9 @@ extern "C"
             (void)hipEventDestroy(e.start);
             (void)hipEventDestroy(e.stop);
         }
+        for (hipEvent_t e : h->batch_events)
+            if (e != nullptr)
+                (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
             (void)hipStreamDestroy(h->stream);
         delete h;
@@ -2335,6 +2346,133 @@ extern "C"
         if (!policy || n < 0 || !dist || (params->value_hidden > 0 && !value))
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_actor_act_host: bad argument");
         okActorActHost(*params, policy, value, num_rays, n, dist, crashed, draw_index, throttle, steer, action, prob, value_out, state, alive);
+        return OKENV_OK;
+    }
+
+    // ---- from a recorded episode to the learner's batch (ok_batch.h) ---------------------------------------------------------
+
+    int okenv_batch_prepare(okenv_t h, const okenv_batch_params *params, const okenv_batch_input *in, const okenv_batch_output *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_batch_prepare: NULL handle");
+        if (const char *why = okBatchCheck(params, in, out))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_batch_prepare: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkBatchParams p{};
+        p.T         = params->num_steps;
+        p.N         = params->num_agents;
+        p.R         = params->state_width;
+        p.W         = (p.N + kBatchWave - 1) / kBatchWave;
+        p.rs        = params->record_stride != 0 ? params->record_stride : p.N;
+        p.fs        = params->field_stride != 0 ? params->field_stride : p.N;
+        p.L         = static_cast<long>(p.T) * p.W;
+        p.groups    = (p.L + kBatchGroupChunks - 1) / kBatchGroupChunks;
+        p.gamma     = params->gamma;
+        p.gl        = static_cast<float>(static_cast<double>(params->gamma) * static_cast<double>(params->lambda));
+        p.normalize = params->normalize;
+        p.in        = *in;
+        p.out       = *out;
+        // the scratch: [G plane | A plane | column partials | their counts | group counts | statistics | M], each piece 256-aligned
+        const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
+        const size_t plane = up(sizeof(float) * static_cast<size_t>(p.T) * static_cast<size_t>(p.N));
+        const size_t parts = up(4U * sizeof(double) * static_cast<size_t>(p.N)), part_m = up(sizeof(uint32_t) * static_cast<size_t>(p.N));
+        const size_t group = up(sizeof(uint32_t) * static_cast<size_t>(p.groups));
+        const size_t bytes = 2U * plane + parts + part_m + group + 256U + 256U;
+        if (bytes > h->batch_bytes)
+        {
+            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in the old one
+            if (h->d_batch != nullptr)
+            {
+                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_batch)), h->allocations.end());
+                (void)hipFree(h->d_batch);
+                h->d_batch     = nullptr;
+                h->batch_bytes = 0;
+            }
+            uint8_t  *fresh = nullptr;
+            const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
+            if (rc != OKENV_OK)
+                return rc;
+            h->d_batch     = fresh;
+            h->batch_bytes = bytes + bytes / 2U;
+        }
+        uint8_t *at = h->d_batch;
+        p.g_plane   = out->ret_plane != nullptr ? out->ret_plane : reinterpret_cast<float *>(at);
+        p.a_plane   = out->adv_plane != nullptr ? out->adv_plane : reinterpret_cast<float *>(at + plane);
+        at += 2U * plane;
+        p.part = reinterpret_cast<double *>(at);
+        at += parts;
+        p.part_m = reinterpret_cast<uint32_t *>(at);
+        at += part_m;
+        p.group = reinterpret_cast<uint32_t *>(at);
+        at += group;
+        p.stats = reinterpret_cast<okenv_batch_stats *>(at);
+        at += 256U;
+        p.count          = reinterpret_cast<int32_t *>(at);
+        h->d_batch_count = p.count;
+        h->batch_timed   = h->timing;
+        if (h->timing)
+            for (hipEvent_t &e : h->batch_events)
+                if (e == nullptr)
+                    OK_HIP(h, hipEventCreate(&e));
+        const auto mark = [&](const int k) { return h->timing ? hipEventRecord(h->batch_events[k], h->stream) : hipSuccess; };
+        const unsigned bt   = static_cast<unsigned>(params->block_threads != 0 ? params->block_threads : kBatchWalkThreads);
+        const unsigned wide = static_cast<unsigned>(p.groups);
+        OK_HIP(h, mark(0));
+        if (in->value != nullptr)
+            hipLaunchKernelGGL(okBatchWalkKernel<true>, dim3((static_cast<unsigned>(p.N) + bt - 1U) / bt), dim3(bt), 0, h->stream, p);
+        else
+            hipLaunchKernelGGL(okBatchWalkKernel<false>, dim3((static_cast<unsigned>(p.N) + bt - 1U) / bt), dim3(bt), 0, h->stream, p);
+        OK_HIP(h, mark(1));
+        hipLaunchKernelGGL(okBatchTreeKernel, dim3(1), dim3(1024), 0, h->stream, p);
+        OK_HIP(h, mark(2));
+        hipLaunchKernelGGL(okBatchCountKernel, dim3(wide), dim3(kBatchWideThreads), 0, h->stream, p);
+        OK_HIP(h, mark(3));
+        hipLaunchKernelGGL(okBatchScanKernel, dim3(1), dim3(1024), 0, h->stream, p);
+        OK_HIP(h, mark(4));
+        hipLaunchKernelGGL(okBatchGatherKernel, dim3(wide), dim3(kBatchWideThreads), 0, h->stream, p);
+        OK_HIP(h, mark(5));
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_batch_count(okenv_t h, int32_t *count)
+    {
+        OK_QUIESCE(h);
+        if (!h || !count)
+            return fail(h, OKENV_ERR_INVALID, "okenv_batch_count: NULL argument");
+        if (h->d_batch_count == nullptr)
+            return fail(h, OKENV_ERR_STATE, "okenv_batch_count: call okenv_batch_prepare first");
+        OK_HIP(h, hipSetDevice(h->device));
+        OK_HIP(h, hipMemcpyAsync(count, h->d_batch_count, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_debug_batch_timing(okenv_t h, double *ms5)
+    {
+        OK_QUIESCE(h);
+        if (!h || !ms5)
+            return fail(h, OKENV_ERR_INVALID, "okenv_debug_batch_timing: NULL argument");
+        if (h->d_batch_count == nullptr || !h->batch_timed)
+            return fail(h, OKENV_ERR_STATE, "okenv_debug_batch_timing: no okenv_batch_prepare has run with okenv_set_timing on");
+        OK_HIP(h, hipEventSynchronize(h->batch_events[5]));
+        for (int k = 0; k < 5; ++k)
+        {
+            float ms = 0.F;
+            OK_HIP(h, hipEventElapsedTime(&ms, h->batch_events[k], h->batch_events[k + 1]));
+            ms5[k] = ms;
+        }
+        return OKENV_OK;
+    }
+
+    int okenv_batch_prepare_host(const okenv_batch_params *params, const okenv_batch_input *in, const okenv_batch_output *out, int32_t *count)
+    {
+        if (const char *why = okBatchCheck(params, in, out))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_batch_prepare_host: ") + why);
+        const int32_t m = okBatchPrepareHost(*params, *in, *out);
+        if (count != nullptr)
+            *count = m;
         return OKENV_OK;
     }
 

@@ -516,6 +516,37 @@ class BatchedEnvironment:
             setattr(rec, k, int(v))
         capi.check(self._L.okenv_actor_act(self._h, C.byref(rec)), self._h)
 
+    # ---- from a recorded episode to the learner's batch (include/okenv.h) ---------------------------
+    def batch_prepare(self, num_steps, num_agents, inputs, outputs, state_width=0, record_stride=0, field_stride=0, gamma=0.99, lam=1.0,
+                      normalize=0, block_threads=0):
+        """okenv_batch_prepare: enqueues the five kernels on the handle's stream, no synchronisation.  inputs: dict of device tensors
+        / addresses under "reward", "alive" (required), "value", "last_value", "state", "action", "prob"; outputs: likewise under
+        "state", "action", "prob", "ret", "adv", "index", "ret_plane", "adv_plane", "stats" (capi.BATCH_STATS_BYTES bytes), "count".
+        Strided views are passed by their first element: the strides are the caller's to state."""
+        bp = capi.OkenvBatchParams(int(num_steps), int(num_agents), int(state_width), int(record_stride), int(field_stride), float(gamma),
+                                   float(lam), int(normalize), int(block_threads))
+        bi, bo = capi.OkenvBatchInput(), capi.OkenvBatchOutput()
+        for struct, given in ((bi, inputs), (bo, outputs)):
+            names = {name for name, _ in struct._fields_}
+            for k, v in given.items():
+                if k not in names:
+                    raise KeyError("unknown batch slot %r" % k)
+                if v is not None:
+                    setattr(struct, k, int(v.data_ptr() if hasattr(v, "data_ptr") else v))
+        capi.check(self._L.okenv_batch_prepare(self._h, C.byref(bp), C.byref(bi), C.byref(bo)), self._h)
+
+    def batch_count(self):
+        """M of the latest batch_prepare; waits for the stream (the one 4-byte read the caller needs to size its views)."""
+        m = C.c_int32()
+        capi.check(self._L.okenv_batch_count(self._h, C.byref(m)), self._h)
+        return m.value
+
+    def batch_timing(self):
+        """Device microseconds of the five kernels of the latest batch_prepare that ran with set_timing(True), by capi.BATCH_KERNELS."""
+        ms = (C.c_double * 5)()
+        capi.check(self._L.okenv_debug_batch_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
+        return {k: 1000.0 * v for k, v in zip(capi.BATCH_KERNELS, ms)}
+
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):
         """{rays, tests, cells, points} the broad phase leaves for the current poses (okenv_work_stats)."""
@@ -611,6 +642,60 @@ def actor_act_host(params, policy, value, dist, crashed=None, draw_index=0):
     if params.value_hidden == 0:
         del out["value"]
     return out
+
+
+def batch_prepare_host(reward, alive, value=None, last_value=None, state=None, action=None, prob=None, num_agents=None, gamma=0.99, lam=1.0,
+                       normalize=0, want=None, block_threads=0):
+    """The episode-to-batch rule on host arrays, no GPU needed (okenv_batch_prepare_host).  reward / alive / value: [T, S] with
+    S >= num_agents (default S) agent slots per row, the rest padding; state [T, S', R], action [T, S'] int64, prob [T, S'] share
+    their own S'.  want: the outputs to ask for (default: every one the inputs allow) out of "state", "action", "prob", "ret", "adv",
+    "index", "ret_plane", "adv_plane", "stats", "count"; the others are passed as NULL.  Returns a dict: the dense outputs cut to M
+    rows, the planes [T, N], "stats" as a dict, "count" (the word) and "M" (the out-parameter)."""
+    reward = np.ascontiguousarray(reward, dtype=np.float32)
+    alive = np.ascontiguousarray(alive).view(np.uint8) if np.asarray(alive).dtype == np.bool_ else np.ascontiguousarray(alive, dtype=np.uint8)
+    T, S = reward.shape
+    N = S if num_agents is None else int(num_agents)
+    assert alive.shape == (T, S)
+    value = None if value is None else np.ascontiguousarray(value, dtype=np.float32)
+    last_value = None if last_value is None else np.ascontiguousarray(last_value, dtype=np.float32)
+    state = None if state is None else np.ascontiguousarray(state, dtype=np.float32)
+    action = None if action is None else np.ascontiguousarray(action, dtype=np.int64)
+    prob = None if prob is None else np.ascontiguousarray(prob, dtype=np.float32)
+    fields = [a for a in (state, action, prob) if a is not None]
+    Sf = fields[0].shape[1] if fields else S
+    assert all(a.shape[:2] == (T, Sf) for a in fields) and (value is None or value.shape == (T, S))
+    R = state.shape[2] if state is not None else 0
+    cap = max(T * N, 1)
+    possible = {"ret": np.zeros(cap, np.float32), "index": np.zeros(cap, np.int32), "ret_plane": np.zeros((max(T, 1), max(N, 1)), np.float32),
+                "stats": np.zeros(capi.BATCH_STATS_BYTES, np.uint8), "count": np.zeros(1, np.int32)}
+    if value is not None:
+        possible.update(adv=np.zeros(cap, np.float32), adv_plane=np.zeros((max(T, 1), max(N, 1)), np.float32))
+    if state is not None:
+        possible["state"] = np.zeros((cap, R), np.float32)
+    if action is not None:
+        possible["action"] = np.zeros(cap, np.int64)
+    if prob is not None:
+        possible["prob"] = np.zeros(cap, np.float32)
+    out = possible if want is None else {k: (possible[k] if k in possible else np.zeros(cap, np.float32)) for k in want}
+    bp = capi.OkenvBatchParams(T, N, R, S if S != N else 0, Sf if Sf != N else 0, float(gamma), float(lam), int(normalize), int(block_threads))
+    bi, bo = capi.OkenvBatchInput(), capi.OkenvBatchOutput()
+    for k, v in (("reward", reward), ("alive", alive), ("value", value), ("last_value", last_value), ("state", state), ("action", action),
+                 ("prob", prob)):
+        if v is not None:
+            setattr(bi, k, v.ctypes.data)
+    for k, v in out.items():
+        setattr(bo, k, v.ctypes.data)
+    m = C.c_int32(-1)
+    capi.check(capi.load().okenv_batch_prepare_host(C.byref(bp), C.byref(bi), C.byref(bo), C.byref(m)))
+    res = {"M": m.value}
+    for k, v in out.items():
+        if k == "stats":
+            res[k] = capi.batch_stats_dict(v)
+        elif k in ("ret_plane", "adv_plane", "count"):
+            res[k] = v
+        else:
+            res[k] = v[:m.value]
+    return res
 
 
 def debug_expf(x):

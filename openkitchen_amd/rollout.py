@@ -183,6 +183,75 @@ def _chunk_graph(venv, K):
     return venv._actor_graphs[K]
 
 
+def _rows_of(x, width):
+    """(tensor to hand over, its row stride in agent slots) of a [T, N] / [T, N, width] tensor: a view whose rows are dense and a
+    whole number of slots apart is passed as it is (the block buffers of _EpisodeBuffers), anything else is made contiguous."""
+    T, N = x.shape[0], x.shape[1]
+    dense = x.stride(1) == width and (x.dim() == 2 or x.stride(2) == 1)
+    if dense and (T == 1 or (x.stride(0) % width == 0 and x.stride(0) // width >= N)):
+        return x, (N if T == 1 else x.stride(0) // width)
+    return x.contiguous(), N
+
+
+_NORMALIZE = {True: capi.BATCH_NORMALIZE_RETURN | capi.BATCH_NORMALIZE_ADVANTAGE, False: 0, None: 0, "returns": capi.BATCH_NORMALIZE_RETURN,
+              "advantages": capi.BATCH_NORMALIZE_ADVANTAGE}
+
+
+def prepare_batch(venv, ep, gamma=0.99, lam=None, normalize=True, last_value=None, block_threads=0):
+    """From a recorded episode to the learner's batch on the device (okenv_batch_prepare): what
+    ExperienceBuffer::calculateDiscountedRewards + ::sample do in the reference (RLRacers/PPO/ExperienceBuffer.hpp:15-68), for the
+    dict `ep` that collect_episode_device or collect_episode returns.
+
+    Returns per agent along time with `alive` as the episode boundary (a dead row ends an episode: with auto-reset on a column holds
+    several), GAE(lam) advantages when `lam` is given and the episode has values (`last_value` [N]: the critic's value after the last
+    row, for episodes cut by max_steps), normalised over the M alive samples ((x - mean) / (std + eps), unbiased std; normalize:
+    True / False / "returns" / "advantages"), and the alive samples packed in step-major, agent-minor order -- the order of
+    x.reshape(-1)[alive.reshape(-1)].
+
+    Returns a dict of device tensors: states [M, R], actions [M] i64, log_probs [M], returns [M], advantages [M] (with values), index
+    [M] i32 (t * N + i), count (M, an int: the call waits for the stream once to read it), stats (the okenv_batch_stats words on
+    the device; batch_stats(batch) reads them)."""
+    rewards, alive = ep["rewards"], ep["alive"]
+    T, N = rewards.shape
+    R = ep["states"].shape[2]
+    dev = rewards.device
+    use_value = lam is not None and "values" in ep
+    if alive.dtype not in (torch.bool, torch.uint8):
+        alive = alive != 0
+    record = [_rows_of(rewards.float(), 1), _rows_of(alive, 1)] + ([_rows_of(ep["values"].float(), 1)] if use_value else [])
+    if len({s for _, s in record}) > 1:
+        record = [(x.contiguous(), N) for x, _ in record]
+    fields = [_rows_of(ep["states"].float(), R), _rows_of(ep["actions"], 1), _rows_of(ep["log_probs"].float(), 1)]
+    if len({s for _, s in fields}) > 1:
+        fields = [(x.contiguous(), N) for x, _ in fields]
+    assert fields[1][0].dtype == torch.int64, "actions must be int64"
+    inputs = {"reward": record[0][0], "alive": record[1][0], "state": fields[0][0], "action": fields[1][0], "prob": fields[2][0]}
+    cap = T * N
+    out = {"state": torch.empty((cap, R), dtype=torch.float32, device=dev), "action": torch.empty(cap, dtype=torch.int64, device=dev),
+           "prob": torch.empty(cap, dtype=torch.float32, device=dev), "ret": torch.empty(cap, dtype=torch.float32, device=dev),
+           "index": torch.empty(cap, dtype=torch.int32, device=dev), "stats": torch.empty(capi.BATCH_STATS_BYTES // 8, dtype=torch.float64, device=dev)}
+    if use_value:
+        inputs["value"] = record[2][0]
+        out["adv"] = torch.empty(cap, dtype=torch.float32, device=dev)
+        if last_value is not None:
+            inputs["last_value"] = last_value.to(device=dev, dtype=torch.float32).contiguous()
+            assert inputs["last_value"].numel() == N
+    venv.env.batch_prepare(T, N, inputs, out, state_width=R, record_stride=record[0][1], field_stride=fields[0][1], gamma=gamma,
+                           lam=lam if use_value else 1.0, normalize=_NORMALIZE[normalize], block_threads=block_threads)
+    M = venv.env.batch_count()  # waits for the stream: the inputs above may go now
+    res = {"states": out["state"][:M], "actions": out["action"][:M], "log_probs": out["prob"][:M], "returns": out["ret"][:M],
+           "index": out["index"][:M], "count": M, "stats": out["stats"]}
+    if use_value:
+        res["advantages"] = out["adv"][:M]
+    return res
+
+
+def batch_stats(batch):
+    """The statistics of a prepare_batch result as a dict (one small copy to the host): sum_ret, sumsq_ret, sum_adv, sumsq_adv (fp64, in
+    the rule's order), mean_ret, std_ret, mean_adv, std_adv, count."""
+    return capi.batch_stats_dict(batch["stats"].cpu().numpy().view("uint8"))
+
+
 def discounted_returns(rewards, gamma=0.99, normalize=True):
     """Reward-to-go along the time axis of a [T, N] reward tensor, then (optionally) the whole-buffer normalisation of
     ExperienceBuffer::calculateDiscountedRewards (RLRacers/PPO/ExperienceBuffer.hpp:47-71).  The reference discounts
