@@ -414,6 +414,70 @@ OKENV_API int okenv_batch_count(okenv_t h, int32_t *count);
 /* The same rule on host arrays, no GPU needed; *count (may be NULL) receives M. */
 OKENV_API int okenv_batch_prepare_host(const okenv_batch_params *params, const okenv_batch_input *in, const okenv_batch_output *out, int32_t *count);
 
+/* ---- PPO's update: losses, gradients and Adam ------------------------------------------------------------
+ * The minibatch loop of PPOAgent::updatePolicy (RLRacers/PPO/PPOAgent.hpp:109-151) on the batch okenv_batch_prepare leaves: per
+ * minibatch the clipped-surrogate actor loss and the critic's squared error, their gradients through both networks, and one Adam
+ * step on each, in place in the parameters okenv_actor_act reads.  The rule, with its summation order and torch autograd's
+ * conventions, is written out in include/okenv_learn.h (ok_learn_*). */
+typedef struct okenv_learner_params {
+    float lr;    /* > 0 (kLearningRate 3e-4)  */
+    float clip;  /* [0, 1) (kClip 0.2)        */
+    float beta1; /* [0, 1), torch: 0.9        */
+    float beta2; /* [0, 1), torch: 0.999      */
+    float eps;   /* > 0, torch: 1e-8          */
+} okenv_learner_params;
+
+/* The training set: device pointers (host pointers for okenv_ppo_update_host). */
+typedef struct okenv_ppo_batch {
+    const float   *state;  /* [M][R]                                                                          */
+    const int64_t *action; /* [M]                                                                             */
+    const float   *prob;   /* [M]  the recorded clamped probability of the action (not its logarithm)         */
+    const float   *ret;    /* [M]                                                                             */
+    const float   *adv;    /* [M]  or NULL: ret - v(s), v from before the minibatch's steps (needs a critic)  */
+} okenv_ppo_batch;
+
+/* Where the update reports: device pointers (host pointers for okenv_ppo_update_host), each may be NULL (skipped). */
+typedef struct okenv_ppo_output {
+    float   *actor_loss;  /* [epochs * ceil(M / B)]  per minibatch                                            */
+    float   *critic_loss; /* [epochs * ceil(M / B)]  0 without a critic                                       */
+    int32_t *clipped;     /* [epochs * ceil(M / B)]  samples whose ratio left [1 - clip, 1 + clip]            */
+    float   *grad_policy; /* the last minibatch's gradient of the actor loss, in parameter order              */
+    float   *grad_value;  /* the last minibatch's gradient of the critic loss (left alone without a critic)   */
+} okenv_ppo_output;
+
+/* Parameters and Adam state on the host, read and written by okenv_ppo_update_host; the value_* members may be NULL without a
+ * critic.  t: optimiser steps taken so far (one per minibatch, shared by both networks). */
+typedef struct okenv_learner_state {
+    float  *policy, *policy_m, *policy_v;
+    float  *value, *value_m, *value_v;
+    int64_t t;
+} okenv_learner_state;
+
+/* Attaches Adam state (m = v = 0, t = 0) for the networks of the handle's actor.  OKENV_ERR_STATE without an actor whose networks
+ * all have their parameters; OKENV_ERR_INVALID for NULL arguments, lr <= 0, clip outside [0, 1), a beta outside [0, 1), eps <= 0
+ * (or NaN). */
+OKENV_API int okenv_learner_create(okenv_t h, const okenv_learner_params *params);
+/* m = v = 0, t = 0 again.  (okenv_actor_set_params leaves the moments alone.) */
+OKENV_API int okenv_learner_reset(okenv_t h);
+/* Enqueues every minibatch of every epoch on the handle's stream, two kernels each (gradient partials per chunk; join + Adam on both
+ * networks): no synchronisation, and no allocation after the first call of a given min(B, M).  `order` is a device array
+ * [epochs][M] of int32 sample indices or NULL (sequential).  The next okenv_actor_act uses the new parameters.  The step number
+ * advances per enqueued minibatch; if the call returns an error part of the way, call okenv_learner_reset or carry on from
+ * okenv_learner_get_state's t, which counts the minibatches that were enqueued.
+ * OKENV_ERR_STATE before okenv_learner_create; OKENV_ERR_INVALID for a NULL handle, batch, state, action, prob or ret, M, B or
+ * epochs < 1, epochs * M >= 2^31, adv NULL without a critic. */
+OKENV_API int okenv_ppo_update(okenv_t h, const okenv_ppo_batch *batch, int32_t M, int32_t B, int32_t epochs, const int32_t *order,
+                               const okenv_ppo_output *out);
+/* The same rule on host arrays, no GPU needed: networks num_rays -> hidden -> num_actions and num_rays -> value_hidden -> 1
+ * (value_hidden 0: none). */
+OKENV_API int okenv_ppo_update_host(const okenv_learner_params *params, int32_t num_rays, int32_t hidden, int32_t num_actions, int32_t value_hidden,
+                                    okenv_learner_state *state, const okenv_ppo_batch *batch, int32_t M, int32_t B, int32_t epochs,
+                                    const int32_t *order, const okenv_ppo_output *out);
+/* The actor's parameters to host or device pointers (either may be NULL); synchronises.  OKENV_ERR_STATE before they were set. */
+OKENV_API int okenv_actor_get_params(okenv_t h, float *policy, float *value);
+/* The learner's moments to host or device pointers (each may be NULL) and its step number; synchronises. */
+OKENV_API int okenv_learner_get_state(okenv_t h, float *policy_m, float *policy_v, float *value_m, float *value_v, int64_t *t);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.
@@ -692,6 +756,13 @@ OKENV_API int okenv_debug_expf(const float *x, float *out, int32_t n);
 /* Device milliseconds of the five kernels of the handle's latest okenv_batch_prepare (walk, tree, count, scan, gather), from events
  * it records between them while okenv_set_timing is on; waits for the last one.  OKENV_ERR_STATE when that call ran untimed. */
 OKENV_API int okenv_debug_batch_timing(okenv_t h, double *ms5);
+/* Device milliseconds of the handle's latest okenv_ppo_update, summed over its minibatches per kernel (gradient partials, join +
+ * Adam), from events it records between them while okenv_set_timing is on; waits for the last one.  OKENV_ERR_STATE when that call
+ * ran untimed. */
+OKENV_API int okenv_debug_update_timing(okenv_t h, double *ms2);
+/* ok_learn_adam (include/okenv_learn.h) on host arrays: step number t >= 1 of n parameters p with moments m, v and gradients g, all
+ * updated in place; host only, no GPU. */
+OKENV_API int okenv_debug_adam(const okenv_learner_params *params, int64_t t, float *p, float *m, float *v, const float *g, int32_t n);
 /* ok_sincosf evaluated on the GPU (n values, host pointers). */
 OKENV_API int okenv_debug_sincos(int32_t device, const float *x, float *s, float *c, int32_t n);
 /* First-hit parameter t for n arbitrary rays (origin, angle [rad]) through the handle's grid (host pointers). */

@@ -42,6 +42,9 @@ ACTOR_MAX_RAYS, ACTOR_MAX_HIDDEN, ACTOR_MAX_ACTIONS = 64, 256, 8
 # episode -> batch (include/okenv.h)
 BATCH_NORMALIZE_RETURN, BATCH_NORMALIZE_ADVANTAGE = 1, 2
 BATCH_KERNELS = ("walk", "tree", "count", "scan", "gather")
+# PPO's update (include/okenv.h)
+UPDATE_KERNELS = ("grad", "step")
+LEARN_CHUNK = 32
 
 # every symbol include/okenv.h declares (tests/test_capi_symbols.py checks the library exports them all)
 SYMBOLS = [
@@ -68,6 +71,8 @@ SYMBOLS = [
     "okenv_actor_create", "okenv_actor_num_params", "okenv_actor_set_params", "okenv_actor_set_epsilon", "okenv_actor_set_draw_offset",
     "okenv_actor_act", "okenv_actor_act_host", "okenv_debug_expf",
     "okenv_batch_prepare", "okenv_batch_count", "okenv_batch_prepare_host", "okenv_debug_batch_timing",
+    "okenv_learner_create", "okenv_learner_reset", "okenv_ppo_update", "okenv_ppo_update_host", "okenv_actor_get_params",
+    "okenv_learner_get_state", "okenv_debug_update_timing", "okenv_debug_adam",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -157,6 +162,40 @@ class OkenvBatchOutput(C.Structure):
 
 
 BATCH_STATS_BYTES = C.sizeof(OkenvBatchStats)  # 56
+
+
+class OkenvLearnerParams(C.Structure):
+    _fields_ = [("lr", C.c_float), ("clip", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
+
+
+class OkenvPpoBatch(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("action", C.c_void_p), ("prob", C.c_void_p), ("ret", C.c_void_p), ("adv", C.c_void_p)]
+
+
+class OkenvPpoOutput(C.Structure):
+    _fields_ = [("actor_loss", C.c_void_p), ("critic_loss", C.c_void_p), ("clipped", C.c_void_p), ("grad_policy", C.c_void_p),
+                ("grad_value", C.c_void_p)]
+
+
+class OkenvLearnerState(C.Structure):
+    _fields_ = [("policy", C.c_void_p), ("policy_m", C.c_void_p), ("policy_v", C.c_void_p), ("value", C.c_void_p), ("value_m", C.c_void_p),
+                ("value_v", C.c_void_p), ("t", C.c_int64)]
+
+
+def learner_params(lr=3e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8):
+    """okenv_learner_params with the reference's learning rate and clip (PPOAgent.hpp:24-26) and torch.optim.Adam's defaults."""
+    return OkenvLearnerParams(float(lr), float(clip), float(beta1), float(beta2), float(eps))
+
+
+def fill_pointers(struct, given, what):
+    """Sets the pointer members of a ctypes struct from a dict of tensors / arrays / addresses (None: left NULL)."""
+    names = {name for name, _ in struct._fields_}
+    for k, v in given.items():
+        if k not in names:
+            raise KeyError("unknown %s slot %r" % (what, k))
+        if v is not None:
+            setattr(struct, k, ptr(v).value)
+    return struct
 
 
 def batch_stats_dict(raw):
@@ -332,6 +371,15 @@ def load(build_if_missing=True):
     L.okenv_batch_count.argtypes = [vp, C.POINTER(i32)]
     L.okenv_batch_prepare_host.argtypes = [C.POINTER(OkenvBatchParams), C.POINTER(OkenvBatchInput), C.POINTER(OkenvBatchOutput), C.POINTER(i32)]
     L.okenv_debug_batch_timing.argtypes = [vp, vp]
+    L.okenv_learner_create.argtypes = [vp, C.POINTER(OkenvLearnerParams)]
+    L.okenv_learner_reset.argtypes = [vp]
+    L.okenv_ppo_update.argtypes = [vp, C.POINTER(OkenvPpoBatch), i32, i32, i32, vp, C.POINTER(OkenvPpoOutput)]
+    L.okenv_ppo_update_host.argtypes = [C.POINTER(OkenvLearnerParams), i32, i32, i32, i32, C.POINTER(OkenvLearnerState), C.POINTER(OkenvPpoBatch),
+                                        i32, i32, i32, vp, C.POINTER(OkenvPpoOutput)]
+    L.okenv_actor_get_params.argtypes = [vp, vp, vp]
+    L.okenv_learner_get_state.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int64)]
+    L.okenv_debug_update_timing.argtypes = [vp, vp]
+    L.okenv_debug_adam.argtypes = [C.POINTER(OkenvLearnerParams), C.c_int64, vp, vp, vp, vp, i32]
     _lib = L
     return L
 

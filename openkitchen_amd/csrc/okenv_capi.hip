@@ -24,6 +24,7 @@
 #include "okenv_kernels.h"
 #include "ok_actor.h"
 #include "ok_batch.h"
+#include "ok_learn.h"
 #include "ok_expert.h"
 
 namespace
@@ -476,6 +477,17 @@ struct okenv
     int32_t   *d_batch_count{nullptr};
     bool       batch_timed{false};
     hipEvent_t batch_events[6]{};
+    // PPO's update (okenv_learner_create): Adam's moments beside the actor's parameters, the step number, the chunk partials (grown,
+    // never shrunk) and, while okenv_set_timing is on, the events around every kernel of the latest okenv_ppo_update
+    bool                    learner_ok{false};
+    okenv_learner_params    learner{};
+    int64_t                 learn_t{0};
+    float                  *d_learn_moments{nullptr}; // [4][cap]: policy m, policy v, value m, value v
+    size_t                  learn_cap{0};
+    uint8_t                *d_learn_part{nullptr};
+    size_t                  learn_part_bytes{0};
+    std::vector<hipEvent_t> learn_events;
+    size_t                  learn_timed{0};           // events of the latest timed update (0: it ran untimed)
 };
 
 struct okenv_track
@@ -1355,6 +1367,8 @@ extern "C"
         for (hipEvent_t e : h->batch_events)
             if (e != nullptr)
                 (void)hipEventDestroy(e);
+        for (hipEvent_t e : h->learn_events)
+            (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
             (void)hipStreamDestroy(h->stream);
         delete h;
@@ -2247,6 +2261,7 @@ extern "C"
         h->actor_ok         = true;
         h->actor_policy_set = false;
         h->actor_value_set  = false;
+        h->learner_ok       = false; // (Adam's moments belong to the networks that were just replaced)
         return OKENV_OK;
     }
 
@@ -2473,6 +2488,232 @@ extern "C"
         const int32_t m = okBatchPrepareHost(*params, *in, *out);
         if (count != nullptr)
             *count = m;
+        return OKENV_OK;
+    }
+
+    // ---- PPO's update: losses, gradients and Adam (ok_learn.h) --------------------------------------------------------------
+
+    int okenv_learner_create(okenv_t h, const okenv_learner_params *params)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_learner_create: NULL handle");
+        if (const char *why = okLearnCheckParams(params))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_learner_create: ") + why);
+        if (!h->actor_ok || !h->actor_policy_set || (h->actor.value_hidden > 0 && !h->actor_value_set))
+            return fail(h, OKENV_ERR_STATE, "okenv_learner_create: needs an actor whose networks have their parameters (okenv_actor_create, okenv_actor_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        h->learn_cap = static_cast<size_t>(ok_actor_num_params(h->shape.R, OK_ACTOR_MAX_HIDDEN, OK_ACTOR_MAX_ACTIONS)) + 4U;
+        const int rc = devEnsure(h, &h->d_learn_moments, 4U * h->learn_cap);
+        if (rc != OKENV_OK)
+            return rc;
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okLearnGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipMemsetAsync(h->d_learn_moments, 0, 4U * h->learn_cap * sizeof(float), h->stream));
+        h->learner    = *params;
+        h->learn_t    = 0;
+        h->learner_ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_learner_reset(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->learner_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_learner_reset: call okenv_learner_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        OK_HIP(h, hipMemsetAsync(h->d_learn_moments, 0, 4U * h->learn_cap * sizeof(float), h->stream));
+        h->learn_t = 0;
+        return OKENV_OK;
+    }
+
+    int okenv_ppo_update(okenv_t h, const okenv_ppo_batch *batch, int32_t M, int32_t B, int32_t epochs, const int32_t *order, const okenv_ppo_output *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ppo_update: NULL handle");
+        if (!h->learner_ok || !h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ppo_update: call okenv_learner_create first");
+        if (const char *why = okLearnCheckCall(batch, M, B, epochs, h->actor.value_hidden))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_ppo_update: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkLearnParams p{};
+        p.R    = h->shape.R;
+        p.H    = h->actor.hidden;
+        p.A    = h->actor.num_actions;
+        p.Hv   = h->actor.value_hidden;
+        p.M    = M;
+        p.Pp   = ok_actor_num_params(p.R, p.H, p.A);
+        p.Pv   = p.Hv > 0 ? ok_actor_num_params(p.R, p.Hv, 1) : 0;
+        p.cols = p.Pp + p.Pv + 2;
+        p.in   = *batch;
+        p.lo   = okLearnClipLo(h->learner.clip);
+        p.hi   = okLearnClipHi(h->learner.clip);
+        p.policy = h->d_actor_policy;
+        p.value  = h->d_actor_value;
+        p.pol_m  = h->d_learn_moments;
+        p.pol_v  = h->d_learn_moments + h->learn_cap;
+        p.val_m  = h->d_learn_moments + 2U * h->learn_cap;
+        p.val_v  = h->d_learn_moments + 3U * h->learn_cap;
+        const okenv_ppo_output none{};
+        const okenv_ppo_output &o = out != nullptr ? *out : none;
+        p.grad_policy = o.grad_policy;
+        p.grad_value  = o.grad_value;
+        // the scratch: [chunk partials | clip counts], each piece 256-aligned
+        const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
+        const size_t c_max = (static_cast<size_t>(std::min(B, M)) + OK_LEARN_CHUNK - 1U) / OK_LEARN_CHUNK;
+        const size_t parts = up(sizeof(float) * c_max * static_cast<size_t>(p.cols)), bytes = parts + up(sizeof(uint32_t) * c_max);
+        if (bytes > h->learn_part_bytes)
+        {
+            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in the old one
+            if (h->d_learn_part != nullptr)
+            {
+                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_learn_part)), h->allocations.end());
+                (void)hipFree(h->d_learn_part);
+                h->d_learn_part     = nullptr;
+                h->learn_part_bytes = 0;
+            }
+            uint8_t  *fresh = nullptr;
+            const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
+            if (rc != OKENV_OK)
+                return rc;
+            h->d_learn_part     = fresh;
+            h->learn_part_bytes = bytes + bytes / 2U;
+        }
+        p.part      = reinterpret_cast<float *>(h->d_learn_part);
+        p.part_clip = reinterpret_cast<uint32_t *>(h->d_learn_part + parts);
+        const int    per_epoch = okLearnMinibatches(M, B);
+        const size_t launches  = 2U * static_cast<size_t>(epochs) * static_cast<size_t>(per_epoch);
+        h->learn_timed = 0;
+        if (h->timing)
+        {
+            while (h->learn_events.size() < launches + 1U)
+            {
+                hipEvent_t e = nullptr;
+                OK_HIP(h, hipEventCreate(&e));
+                h->learn_events.push_back(e);
+            }
+            OK_HIP(h, hipEventRecord(h->learn_events[0], h->stream));
+        }
+        const size_t lds = okLearnLdsBytes(p.R, p.H, p.A, p.Hv);
+        size_t       ev  = 0;
+        for (int e = 0; e < epochs; ++e)
+            for (int k = 0; k < per_epoch; ++k)
+            {
+                const size_t slot = static_cast<size_t>(e) * per_epoch + k;
+                p.base  = static_cast<long>(k) * B;
+                p.Bk    = static_cast<int>(std::min<long>(B, M - p.base));
+                p.C     = (p.Bk + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+                p.order = order != nullptr ? order + static_cast<size_t>(e) * M : nullptr;
+                p.adam        = okLearnAdamConsts(h->learner, h->learn_t + 1);
+                p.actor_loss  = o.actor_loss != nullptr ? o.actor_loss + slot : nullptr;
+                p.critic_loss = o.critic_loss != nullptr ? o.critic_loss + slot : nullptr;
+                p.clipped     = o.clipped != nullptr ? o.clipped + slot : nullptr;
+                // The step number advances only once both kernels of the minibatch are enqueued: after a failed launch the handle's t
+                // is the number of steps the device's moments have taken, and the call reports the error.
+                hipLaunchKernelGGL(okLearnGradKernel, dim3(static_cast<unsigned>(p.C)), dim3(kLearnThreads), lds, h->stream, p);
+                OK_HIP(h, hipGetLastError());
+                if (h->timing)
+                    OK_HIP(h, hipEventRecord(h->learn_events[++ev], h->stream));
+                hipLaunchKernelGGL(okLearnStepKernel, dim3(static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols)),
+                                   dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
+                OK_HIP(h, hipGetLastError());
+                h->learn_t += 1;
+                if (h->timing)
+                    OK_HIP(h, hipEventRecord(h->learn_events[++ev], h->stream));
+            }
+        h->learn_timed = h->timing ? launches + 1U : 0U;
+        return OKENV_OK;
+    }
+
+    int okenv_debug_update_timing(okenv_t h, double *ms2)
+    {
+        OK_QUIESCE(h);
+        if (!h || !ms2)
+            return fail(h, OKENV_ERR_INVALID, "okenv_debug_update_timing: NULL argument");
+        if (h->learn_timed < 3U)
+            return fail(h, OKENV_ERR_STATE, "okenv_debug_update_timing: no okenv_ppo_update has run with okenv_set_timing on");
+        OK_HIP(h, hipEventSynchronize(h->learn_events[h->learn_timed - 1U]));
+        ms2[0] = ms2[1] = 0.0;
+        for (size_t k = 0; k + 1U < h->learn_timed; ++k)
+        {
+            float ms = 0.F;
+            OK_HIP(h, hipEventElapsedTime(&ms, h->learn_events[k], h->learn_events[k + 1U]));
+            ms2[k & 1U] += ms;
+        }
+        return OKENV_OK;
+    }
+
+    int okenv_actor_get_params(okenv_t h, float *policy, float *value)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_get_params: call okenv_actor_create first");
+        if ((policy != nullptr && !h->actor_policy_set) || (value != nullptr && !h->actor_value_set))
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_get_params: the network has no parameters yet (okenv_actor_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        int rc = OKENV_OK;
+        if (policy != nullptr)
+            rc = copyAny(h, policy, h->d_actor_policy, sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions)));
+        if (rc == OKENV_OK && value != nullptr)
+            rc = copyAny(h, value, h->d_actor_value, sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.value_hidden, 1)));
+        if (rc != OKENV_OK)
+            return rc;
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_learner_get_state(okenv_t h, float *policy_m, float *policy_v, float *value_m, float *value_v, int64_t *t)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->learner_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_learner_get_state: call okenv_learner_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t np = sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions));
+        const size_t nv = h->actor.value_hidden > 0 ? sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.value_hidden, 1)) : 0U;
+        float *const dst[4]   = {policy_m, policy_v, value_m, value_v};
+        const size_t bytes[4] = {np, np, nv, nv};
+        for (int k = 0; k < 4; ++k)
+            if (dst[k] != nullptr)
+            {
+                const int rc = copyAny(h, dst[k], h->d_learn_moments + static_cast<size_t>(k) * h->learn_cap, bytes[k]);
+                if (rc != OKENV_OK)
+                    return rc;
+            }
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        if (t != nullptr)
+            *t = h->learn_t;
+        return OKENV_OK;
+    }
+
+    int okenv_ppo_update_host(const okenv_learner_params *params, int32_t num_rays, int32_t hidden, int32_t num_actions, int32_t value_hidden,
+                              okenv_learner_state *state, const okenv_ppo_batch *batch, int32_t M, int32_t B, int32_t epochs, const int32_t *order,
+                              const okenv_ppo_output *out)
+    {
+        if (const char *why = okLearnCheckParams(params))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_ppo_update_host: ") + why);
+        if (num_rays < 1 || num_rays > OK_ACTOR_MAX_RAYS || hidden < 1 || hidden > OK_ACTOR_MAX_HIDDEN || num_actions < 2 ||
+            num_actions > OK_ACTOR_MAX_ACTIONS || value_hidden < 0 || value_hidden > OK_ACTOR_MAX_HIDDEN)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ppo_update_host: a network width outside the actor's limits");
+        if (const char *why = okLearnCheckCall(batch, M, B, epochs, value_hidden))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_ppo_update_host: ") + why);
+        if (state == nullptr || state->policy == nullptr || state->policy_m == nullptr || state->policy_v == nullptr || state->t < 0 ||
+            (value_hidden > 0 && (state->value == nullptr || state->value_m == nullptr || state->value_v == nullptr)))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ppo_update_host: state lacks a parameter or moment vector, or t < 0");
+        const okenv_ppo_output none{};
+        okLearnUpdateHost(*params, num_rays, hidden, num_actions, value_hidden, *state, *batch, M, B, epochs, order, out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_adam(const okenv_learner_params *params, int64_t t, float *p, float *m, float *v, const float *g, int32_t n)
+    {
+        if (const char *why = okLearnCheckParams(params))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_debug_adam: ") + why);
+        if (t < 1 || !p || !m || !v || !g || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_adam: bad argument");
+        const ok_learn_adam_consts c = okLearnAdamConsts(*params, t);
+        for (int32_t i = 0; i < n; ++i)
+            ok_learn_adam(p + i, m + i, v + i, g[i], c);
         return OKENV_OK;
     }
 

@@ -547,6 +547,50 @@ class BatchedEnvironment:
         capi.check(self._L.okenv_debug_batch_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
         return {k: 1000.0 * v for k, v in zip(capi.BATCH_KERNELS, ms)}
 
+    # ---- PPO's update (include/okenv.h) -------------------------------------------------------------
+    def learner_create(self, lr=3e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8):
+        """Attaches Adam state (m = v = 0, t = 0) for the networks of the handle's actor, which must have their parameters."""
+        lp = capi.learner_params(lr, clip, beta1, beta2, eps)
+        capi.check(self._L.okenv_learner_create(self._h, C.byref(lp)), self._h)
+        self.learner_params = lp
+
+    def learner_reset(self):
+        capi.check(self._L.okenv_learner_reset(self._h), self._h)
+
+    def ppo_update(self, batch, M, B, epochs=1, order=None, out=None):
+        """okenv_ppo_update: enqueues every minibatch of every epoch on the handle's stream (two kernels each), no synchronisation.
+        batch: dict of device tensors / addresses under "state" [M,R] float32, "action" [M] int64, "prob" [M] float32 (the recorded
+        probability), "ret" [M] float32 and optionally "adv" [M]; order: None or a device int32 tensor [epochs, M]; out: None or a dict
+        under "actor_loss", "critic_loss" (float32), "clipped" (int32), each [epochs * ceil(M / B)], "grad_policy", "grad_value"."""
+        pb = capi.fill_pointers(capi.OkenvPpoBatch(), batch, "ppo batch")
+        po = capi.fill_pointers(capi.OkenvPpoOutput(), out or {}, "ppo output")
+        capi.check(self._L.okenv_ppo_update(self._h, C.byref(pb), int(M), int(B), int(epochs), capi.ptr(order), C.byref(po)), self._h)
+
+    def actor_get_params(self, policy=True, value=True, out=None):
+        """The actor's current parameter vectors as float32 numpy arrays (policy, value) -- None for one that is not asked for or not
+        there -- or, with out=(policy tensor or None, value tensor or None), copied into those device tensors.  Synchronises."""
+        n_policy, n_value = self.actor_num_params()
+        if out is None:
+            out = (np.empty(n_policy, dtype=np.float32) if policy else None, np.empty(n_value, dtype=np.float32) if value and n_value else None)
+        capi.check(self._L.okenv_actor_get_params(self._h, capi.ptr(out[0]), capi.ptr(out[1])), self._h)
+        return out
+
+    def learner_state(self):
+        """Adam's moments and step number: dict of float32 numpy arrays policy_m, policy_v, value_m, value_v (empty without a critic)
+        and the int t.  Synchronises."""
+        n_policy, n_value = self.actor_num_params()
+        arrs = [np.empty(n, dtype=np.float32) for n in (n_policy, n_policy, n_value, n_value)]
+        t = C.c_int64()
+        capi.check(self._L.okenv_learner_get_state(self._h, *[capi.ptr(a) if a.size else None for a in arrs], C.byref(t)), self._h)
+        return dict(zip(("policy_m", "policy_v", "value_m", "value_v"), arrs), t=t.value)
+
+    def update_timing(self):
+        """Device microseconds of the latest ppo_update that ran with set_timing(True), summed over its minibatches, by
+        capi.UPDATE_KERNELS."""
+        ms = (C.c_double * 2)()
+        capi.check(self._L.okenv_debug_update_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
+        return {k: 1000.0 * v for k, v in zip(capi.UPDATE_KERNELS, ms)}
+
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):
         """{rays, tests, cells, points} the broad phase leaves for the current poses (okenv_work_stats)."""
@@ -696,6 +740,43 @@ def batch_prepare_host(reward, alive, value=None, last_value=None, state=None, a
         else:
             res[k] = v[:m.value]
     return res
+
+
+def ppo_update_host(params, shape, state, batch, B, epochs=1, order=None, want=("actor_loss", "critic_loss", "clipped", "grad_policy", "grad_value")):
+    """PPO's update on host arrays, no GPU needed (okenv_ppo_update_host).  params: capi.learner_params(...); shape: (R, H, A, Hv);
+    state: dict of float32 numpy arrays "policy", "policy_m", "policy_v" (and "value", "value_m", "value_v" with a critic) and the int
+    "t" -- copied, the new state is returned; batch: dict of numpy arrays "state" [M,R], "action" [M] int64, "prob", "ret" and
+    optionally "adv"; order: None or int32 [epochs, M].  Returns (new state, outputs): outputs holds the arrays named in `want`."""
+    R, H, A, Hv = (int(v) for v in shape)
+    M = int(np.asarray(batch["ret"]).shape[0])
+    b = {"state": np.ascontiguousarray(batch["state"], dtype=np.float32), "action": np.ascontiguousarray(batch["action"], dtype=np.int64),
+         "prob": np.ascontiguousarray(batch["prob"], dtype=np.float32), "ret": np.ascontiguousarray(batch["ret"], dtype=np.float32)}
+    if batch.get("adv") is not None:
+        b["adv"] = np.ascontiguousarray(batch["adv"], dtype=np.float32)
+    new = {k: np.array(v, dtype=np.float32, copy=True).ravel() for k, v in state.items() if k != "t" and v is not None}
+    st = capi.fill_pointers(capi.OkenvLearnerState(), new, "learner state")
+    st.t = int(state.get("t", 0))
+    nmb = int(epochs) * ((M + int(B) - 1) // int(B)) if M > 0 and B > 0 and epochs > 0 else 0
+    n_policy = H * R + H + A * H + A
+    n_value = Hv * R + Hv + Hv + 1 if Hv > 0 else 0
+    sizes = {"actor_loss": (nmb, np.float32), "critic_loss": (nmb, np.float32), "clipped": (nmb, np.int32), "grad_policy": (n_policy, np.float32),
+             "grad_value": (n_value, np.float32)}
+    outs = {k: np.zeros(sizes[k][0], dtype=sizes[k][1]) for k in want}
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.int32)
+    capi.check(capi.load().okenv_ppo_update_host(C.byref(params) if params is not None else None, R, H, A, Hv, C.byref(st),
+                                                 C.byref(capi.fill_pointers(capi.OkenvPpoBatch(), b, "ppo batch")), M, int(B), int(epochs),
+                                                 capi.ptr(order), C.byref(capi.fill_pointers(capi.OkenvPpoOutput(), {k: v for k, v in outs.items() if v.size}, "ppo output"))))
+    new["t"] = int(st.t)
+    return new, outs
+
+
+def debug_adam(params, t, p, m, v, g):
+    """ok_learn_adam on host arrays (no GPU): step number t of float32 arrays p, m, v with gradients g; returns the new (p, m, v)."""
+    p, m, v = (np.array(a, dtype=np.float32, copy=True).ravel() for a in (p, m, v))
+    g = np.ascontiguousarray(g, dtype=np.float32).ravel()
+    capi.check(capi.load().okenv_debug_adam(C.byref(params), int(t), capi.ptr(p), capi.ptr(m), capi.ptr(v), capi.ptr(g), p.size))
+    return p, m, v
 
 
 def debug_expf(x):

@@ -6,6 +6,8 @@ into one shared buffer -- crashed agents keep contributing their frozen observat
 for N agents with everything kept on the GPU as [T, N, ...] tensors; `alive[t, i]` marks the entries an agent produced
 before it crashed, so a learner can mask the frozen tail (or keep it, as the reference does).
 """
+import warnings
+
 import torch
 
 from . import _capi as capi
@@ -147,6 +149,7 @@ def collect_episode_device(venv, max_steps=None, check_every=8, graph_chunk=0):
         T = min(T, max_steps)
     res = {"states": out["state"][:T], "actions": out["action"][:T], "log_probs": torch.log(out["prob"][:T]),
            "rewards": out["reward"][:T], "alive": out["alive"][:T]}
+    venv._episode_probs = (res["log_probs"], out["prob"][:T])  # the probabilities as recorded, for prepare_batch -> ppo_update
     if venv.actor_has_value:
         res["values"] = out["value"][:T]
     return res
@@ -243,7 +246,52 @@ def prepare_batch(venv, ep, gamma=0.99, lam=None, normalize=True, last_value=Non
            "index": out["index"][:M], "count": M, "stats": out["stats"]}
     if use_value:
         res["advantages"] = out["adv"][:M]
+    recorded = getattr(venv, "_episode_probs", None) if getattr(venv, "learner_enabled", False) else None
+    if recorded is not None and recorded[0] is ep["log_probs"]:
+        # the probabilities as the device actor recorded them (ppo_update's ratio divides by them), by the samples' flat indices
+        res["probs"] = recorded[1].reshape(-1)[res["index"].long()].contiguous()
     return res
+
+
+def ppo_update(venv, batch, epochs=5, minibatch=4096, shuffle=True, use_advantages=False, grads=False):
+    """PPOAgent::updatePolicy's minibatch loop on the device (okenv_ppo_update, DESIGN.md section 16) for the dict prepare_batch
+    returns: `epochs` passes over the M samples in minibatches of `minibatch`, per minibatch the clipped-surrogate actor loss and the
+    critic's squared error, their gradients and one Adam step on each network, in place in the parameters the device actor acts
+    with (venv.enable_learner first; no sync_actor afterwards, venv.pull_actor() brings them back to the modules).
+
+    shuffle: a fresh torch.randperm per epoch (False: the buffer's order, as the reference walks it).  The advantage is
+    returns - v(s) with the critic's value from before the minibatch's steps, or batch["advantages"] with use_advantages.  The old
+    probabilities are batch["probs"] (an episode recorded by collect_episode_device carries them), else exp(batch["log_probs"]).
+
+    Everything is enqueued on the environment's stream; nothing is read back.  Returns a dict of device tensors, one entry per
+    minibatch in the order they ran: actor_loss, critic_loss (float32), clipped (int32: samples whose ratio left
+    [1 - clip, 1 + clip]); with grads=True also grad_policy and grad_value of the last minibatch."""
+    M = int(batch["states"].shape[0])
+    dev = batch["states"].device
+    if "probs" in batch:
+        probs = batch["probs"]
+    else:
+        # exp(log p) is p only up to rounding: the ratio of the first minibatch is then no longer exactly 1
+        warnings.warn("ppo_update: the batch carries no recorded probabilities (\"probs\"); using exp(log_probs).  prepare_batch adds them "
+                      "for the episode dict collect_episode_device returned, unchanged, once venv.enable_learner has been called.", stacklevel=2)
+        probs = torch.exp(batch["log_probs"])
+    data = {"state": batch["states"].float().contiguous(), "action": batch["actions"].reshape(-1).contiguous(),
+            "prob": probs.reshape(-1).float().contiguous(), "ret": batch["returns"].reshape(-1).float().contiguous()}
+    assert data["action"].dtype == torch.int64, "actions must be int64"
+    if use_advantages:
+        data["adv"] = batch["advantages"].reshape(-1).float().contiguous()
+    order = torch.stack([torch.randperm(M, device=dev) for _ in range(epochs)]).to(torch.int32).contiguous() if shuffle else None
+    n = epochs * ((M + minibatch - 1) // minibatch)
+    out = {"actor_loss": torch.empty(n, dtype=torch.float32, device=dev), "critic_loss": torch.empty(n, dtype=torch.float32, device=dev),
+           "clipped": torch.empty(n, dtype=torch.int32, device=dev)}
+    if grads:
+        n_policy, n_value = venv.env.actor_num_params()
+        out["grad_policy"] = torch.empty(n_policy, dtype=torch.float32, device=dev)
+        if n_value:
+            out["grad_value"] = torch.empty(n_value, dtype=torch.float32, device=dev)
+    venv.env.ppo_update(data, M, minibatch, epochs, order, out)
+    venv._update_inputs = (data, order)  # alive until the next update: the kernels are only enqueued
+    return out
 
 
 def batch_stats(batch):

@@ -265,6 +265,27 @@ class VectorEnvironment:
         self.env.actor_set_params(flat[0], flat[1])
         self._actor_flat = flat  # alive until the next hand-over: the copy is asynchronous
 
+    def enable_learner(self, lr=3e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8):
+        """Attaches PPO's update to the device actor: Adam state for the networks given to enable_actor, with
+        the reference's learning rate and clip and torch.optim.Adam's defaults.  rollout.ppo_update then steps the DEVICE parameters in
+        place: the next actor_act uses them without sync_actor(), and pull_actor() copies them back into the modules."""
+        assert getattr(self, "_actor_nets", None) is not None, "call enable_actor(actor, critic) first"
+        self.env.learner_create(lr, clip, beta1, beta2, eps)
+        self.learner_enabled = True
+
+    def pull_actor(self):
+        """Copies the device actor's parameters back into the modules (or tensors) given to enable_actor."""
+        n_policy, n_value = self.env.actor_num_params()
+        flat = [torch.empty(n, dtype=torch.float32, device=self.device) if t is not None else None
+                for t, n in zip(self._actor_nets, (n_policy, n_value))]
+        self.env.actor_get_params(out=flat)
+        with torch.no_grad():
+            for tensors, vec in zip(self._actor_nets, flat):
+                at = 0
+                for x in tensors or ():
+                    x.copy_(vec[at:at + x.numel()].reshape(x.shape))
+                    at += x.numel()
+
     def set_actor_epsilon(self, epsilon):
         self.env.actor_set_epsilon(epsilon)
         self._actor_graphs = {}  # a captured launch carries the old value
