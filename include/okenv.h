@@ -478,6 +478,86 @@ OKENV_API int okenv_actor_get_params(okenv_t h, float *policy, float *value);
 /* The learner's moments to host or device pointers (each may be NULL) and its step number; synchronises. */
 OKENV_API int okenv_learner_get_state(okenv_t h, float *policy_m, float *policy_v, float *value_m, float *value_v, int64_t *t);
 
+/* ---- Deep-Q learning: replay ring, sampling and the temporal-difference update ---------------------------
+ * The learning side of RLRacers/Deep_Q_Learning (dq_racer_sim.cpp:81-132, DQAgent.hpp:106-181, common/ReplayBuffer.hpp) for the
+ * handle's OKENV_ACTOR_EPS_GREEDY actor: a ring of transitions that persists across episodes on the device, filled by one push per
+ * step, and updateDQN's iterations -- uniform samples, y = r + gamma max q'(s'), the mean squared error over B * A elements, its
+ * gradient and one Adam step -- in place in the parameters okenv_actor_act reads.  The rule is written out in include/okenv_dqn.h
+ * (ok_dqn_*).  The Q network is the actor's policy network R -> H -> A; a value network, if attached, is left alone. */
+#define OKENV_REPLAY_PUSH_ALL 1u /* push every agent (the reference's loop), not only those that entered the step alive */
+#define OKENV_DQN_MASK_DONE 1u   /* y = r + ((1 - done) * gamma) * max q' (DQAgent.hpp:134) instead of r + gamma * max q' (:133) */
+
+/* The ring's fields: device pointers, or host pointers where a call says so; [C] slots each. */
+typedef struct okenv_replay_ring {
+    float   *state;      /* [C][R]  the networks' input before the step  */
+    float   *next_state; /* [C][R]  dist / kSensorRange after the step   */
+    int64_t *action;     /* [C]     the chosen index                     */
+    float   *reward;     /* [C]                                          */
+    float   *done;       /* [C]     1.0f: crashed_ after the step, else 0.0f */
+} okenv_replay_ring;
+
+typedef struct okenv_dqn_config {
+    float    gamma;          /* [0, 1] (kGamma 0.99)                                                                        */
+    uint32_t flags;          /* OKENV_DQN_MASK_DONE                                                                         */
+    int32_t  target_network; /* 0: q' from the online parameters (the reference); 1: from the copy okenv_dqn_sync_target makes */
+    uint32_t seed;           /* key of the sampling draws                                                                   */
+} okenv_dqn_config;
+
+/* Where the update reports: device pointers (host pointers for okenv_dqn_update_host), each may be NULL (skipped). */
+typedef struct okenv_dqn_output {
+    float   *loss;        /* [iterations]  mse_loss of every iteration                    */
+    float   *grad_policy; /* the last iteration's gradient, in parameter order            */
+    int32_t *index;       /* [B]           the slots the last iteration sampled           */
+} okenv_dqn_output;
+
+/* Attaches a ring of `capacity` slots to the handle (replaces an earlier one, whose contents are forgotten): every field zero,
+ * pushed = 0.  All of the push's device memory is allocated here.  OKENV_ERR_INVALID for a NULL handle, capacity < 1, unknown flags,
+ * more than 64 rays.  Synchronises.  The earlier ring's memory is freed: a HIP graph that captured
+ * okenv_replay_push against it must not be replayed again. */
+OKENV_API int okenv_replay_create(okenv_t h, int32_t capacity, uint32_t flags);
+/* pushed = 0 again (the slots keep their bytes; nothing reads them).  OKENV_ERR_STATE before okenv_replay_create. */
+OKENV_API int okenv_replay_reset(okenv_t h);
+/* Appends the transitions of the step that has just run: `rec` is the record the preceding okenv_actor_act wrote (state and action are
+ * required, alive unless OKENV_REPLAY_PUSH_ALL); next_state, done and the clearance reward come from the handle's fields after the
+ * step; `reward` is NULL or a device array [N] that replaces the clearance reward.  Two short kernels on the handle's stream, no
+ * synchronisation, no allocation: it can be captured into a HIP graph beside okenv_actor_act and okenv_step.
+ * OKENV_ERR_STATE before okenv_replay_create; OKENV_ERR_INVALID for a NULL handle or record, or a record without state / action
+ * (/ alive). */
+OKENV_API int okenv_replay_push(okenv_t h, const okenv_actor_record *rec, const float *reward);
+/* Transitions in the ring, min(pushed, capacity), and every transition ever pushed (either pointer may be NULL): waits for the stream
+ * and reads the 8-byte word.  Nothing on the device path needs this. */
+OKENV_API int okenv_replay_size(okenv_t h, int64_t *size, int64_t *pushed);
+/* The ring's fields, all `capacity` slots of each, to host or device pointers (each may be NULL); synchronises. */
+OKENV_API int okenv_replay_get(okenv_t h, const okenv_replay_ring *out);
+/* The update's constants (before the first call: gamma 0.99, no flags, no target network, seed 0).  Turning the target network on
+ * (from off: a call that leaves it on keeps the copy) allocates its copy and, when the actor has its parameters, fills it as
+ * okenv_dqn_sync_target does; without parameters the update asks for okenv_dqn_sync_target.  A failed call changes nothing.  OKENV_ERR_INVALID for NULL
+ * arguments, gamma NaN or outside [0, 1], unknown flags, target_network other than 0 or 1. */
+OKENV_API int okenv_dqn_params(okenv_t h, const okenv_dqn_config *config);
+/* `iterations` gradient steps on batches of B uniform samples of the ring, two kernels each on the handle's stream (gradient
+ * partials per chunk of 32 positions, drawn and gathered straight from the ring; join + Adam): no synchronisation, and no allocation
+ * after the first call of a given B.  Iteration i samples draw number draw_base + i with `resample`, else draw_base every time.  The
+ * ring's size is read on the device.  The next okenv_actor_act uses the new parameters; the step number is the learner's.
+ * OKENV_ERR_STATE before okenv_learner_create or okenv_replay_create, or with a target network that was never synchronised;
+ * OKENV_ERR_INVALID for a NULL handle, B or iterations < 1, B * A >= 2^31. */
+OKENV_API int okenv_dqn_update(okenv_t h, int32_t B, int32_t iterations, int32_t resample, uint32_t draw_base, const okenv_dqn_output *out);
+/* Copies the online parameters into the target network, device to device on the handle's stream.  OKENV_ERR_STATE unless
+ * okenv_dqn_params turned the target network on and the actor has its parameters. */
+OKENV_API int okenv_dqn_sync_target(okenv_t h);
+/* One push on host arrays, no GPU needed: ring of `capacity` slots (every field required) and *pushed, read and advanced; n agents with
+ * the record's state [n][num_rays], action [n] and alive [n] (may be NULL with OKENV_REPLAY_PUSH_ALL), the distances [n][num_rays] and
+ * crashed [n] after the step, reward [n] or NULL. */
+OKENV_API int okenv_replay_push_host(const okenv_replay_ring *ring, int32_t capacity, int32_t num_rays, uint64_t *pushed, uint32_t flags, int32_t n,
+                                     const float *state, const int64_t *action, const uint8_t *alive, const float *dist, const uint8_t *crashed,
+                                     const float *reward);
+/* The update on host arrays, no GPU needed: network num_rays -> hidden -> num_actions in state->policy / policy_m / policy_v / t (the
+ * value members are not read), `target` the target network's parameters (required exactly when config->target_network is on), the
+ * ring's fields and its size = min(pushed, capacity). */
+OKENV_API int okenv_dqn_update_host(const okenv_learner_params *params, const okenv_dqn_config *config, int32_t num_rays, int32_t hidden,
+                                    int32_t num_actions, okenv_learner_state *state, const float *target, const okenv_replay_ring *ring,
+                                    int64_t size, int32_t B, int32_t iterations, int32_t resample, uint32_t draw_base,
+                                    const okenv_dqn_output *out);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.
@@ -760,6 +840,8 @@ OKENV_API int okenv_debug_batch_timing(okenv_t h, double *ms5);
  * Adam), from events it records between them while okenv_set_timing is on; waits for the last one.  OKENV_ERR_STATE when that call
  * ran untimed. */
 OKENV_API int okenv_debug_update_timing(okenv_t h, double *ms2);
+/* The same for the handle's latest okenv_dqn_update, summed over its iterations per kernel (gradient partials, join + Adam). */
+OKENV_API int okenv_debug_dqn_timing(okenv_t h, double *ms2);
 /* ok_learn_adam (include/okenv_learn.h) on host arrays: step number t >= 1 of n parameters p with moments m, v and gradients g, all
  * updated in place; host only, no GPU. */
 OKENV_API int okenv_debug_adam(const okenv_learner_params *params, int64_t t, float *p, float *m, float *v, const float *g, int32_t n);

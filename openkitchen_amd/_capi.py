@@ -73,6 +73,9 @@ SYMBOLS = [
     "okenv_batch_prepare", "okenv_batch_count", "okenv_batch_prepare_host", "okenv_debug_batch_timing",
     "okenv_learner_create", "okenv_learner_reset", "okenv_ppo_update", "okenv_ppo_update_host", "okenv_actor_get_params",
     "okenv_learner_get_state", "okenv_debug_update_timing", "okenv_debug_adam",
+    "okenv_replay_create", "okenv_replay_reset", "okenv_replay_push", "okenv_replay_size", "okenv_replay_get", "okenv_dqn_params",
+    "okenv_dqn_update", "okenv_dqn_sync_target", "okenv_replay_push_host", "okenv_dqn_update_host",
+    "okenv_debug_dqn_timing",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -185,6 +188,27 @@ class OkenvLearnerState(C.Structure):
 def learner_params(lr=3e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8):
     """okenv_learner_params with the reference's learning rate and clip (PPOAgent.hpp:24-26) and torch.optim.Adam's defaults."""
     return OkenvLearnerParams(float(lr), float(clip), float(beta1), float(beta2), float(eps))
+
+
+REPLAY_PUSH_ALL = 1  # OKENV_REPLAY_PUSH_ALL
+DQN_MASK_DONE = 1    # OKENV_DQN_MASK_DONE
+
+
+class OkenvReplayRing(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("next_state", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p)]
+
+
+class OkenvDqnConfig(C.Structure):
+    _fields_ = [("gamma", C.c_float), ("flags", C.c_uint32), ("target_network", C.c_int32), ("seed", C.c_uint32)]
+
+
+class OkenvDqnOutput(C.Structure):
+    _fields_ = [("loss", C.c_void_p), ("grad_policy", C.c_void_p), ("index", C.c_void_p)]
+
+
+def dqn_config(gamma=0.99, mask_done=False, target_network=False, seed=0):
+    """okenv_dqn_config with the reference's discount (DQAgent.hpp:33) and target (:133: no mask, no target network)."""
+    return OkenvDqnConfig(float(gamma), DQN_MASK_DONE if mask_done else 0, 1 if target_network else 0, int(seed) & 0xFFFFFFFF)
 
 
 def fill_pointers(struct, given, what):
@@ -380,6 +404,18 @@ def load(build_if_missing=True):
     L.okenv_learner_get_state.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int64)]
     L.okenv_debug_update_timing.argtypes = [vp, vp]
     L.okenv_debug_adam.argtypes = [C.POINTER(OkenvLearnerParams), C.c_int64, vp, vp, vp, vp, i32]
+    L.okenv_replay_create.argtypes = [vp, i32, u32]
+    L.okenv_replay_reset.argtypes = [vp]
+    L.okenv_replay_push.argtypes = [vp, C.POINTER(OkenvActorRecord), vp]
+    L.okenv_replay_size.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.okenv_replay_get.argtypes = [vp, C.POINTER(OkenvReplayRing)]
+    L.okenv_dqn_params.argtypes = [vp, C.POINTER(OkenvDqnConfig)]
+    L.okenv_dqn_update.argtypes = [vp, i32, i32, i32, u32, C.POINTER(OkenvDqnOutput)]
+    L.okenv_dqn_sync_target.argtypes = [vp]
+    L.okenv_replay_push_host.argtypes = [C.POINTER(OkenvReplayRing), i32, i32, C.POINTER(C.c_uint64), u32, i32, vp, vp, vp, vp, vp, vp]
+    L.okenv_dqn_update_host.argtypes = [C.POINTER(OkenvLearnerParams), C.POINTER(OkenvDqnConfig), i32, i32, i32, C.POINTER(OkenvLearnerState), vp,
+                                        C.POINTER(OkenvReplayRing), C.c_int64, i32, i32, i32, u32, C.POINTER(OkenvDqnOutput)]
+    L.okenv_debug_dqn_timing.argtypes = [vp, vp]
     _lib = L
     return L
 

@@ -209,18 +209,18 @@ __global__ __launch_bounds__(kLearnThreads) void okLearnGradKernel(const OkLearn
 // ok_learn_tree over the C chunk partials of every column, split so that no two threads ever touch the same partial: at the levels
 // h >= 16 the partials i and i + h have the same residue mod 16, so thread r of a column does all of them for its residue in place;
 // the 16 that remain meet in LDS, where thread 0 of the column takes the last four levels, the division by B_k and the Adam step.
-__global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okLearnStepKernel(const OkLearnParams p)
+// The whole workgroup calls it (there is a barrier inside); true for the one thread per live column that holds the column's sum.
+__device__ __forceinline__ bool okLearnColumnSum(float *part, const int cols, const int chunks, float (*last)[kLearnStepCols], int *column_out, float *sum_out)
 {
-    __shared__ float last[kLearnStepRows][kLearnStepCols];
     const int      c = static_cast<int>(threadIdx.x) % kLearnStepCols, r = static_cast<int>(threadIdx.x) / kLearnStepCols;
     const int      column = static_cast<int>(blockIdx.x) * kLearnStepCols + c;
-    const bool     live   = column < p.cols;
-    const uint32_t n      = static_cast<uint32_t>(p.C);
-    const size_t   stride = static_cast<size_t>(p.cols);
+    const bool     live   = column < cols;
+    const uint32_t n      = static_cast<uint32_t>(chunks);
+    const size_t   stride = static_cast<size_t>(cols);
     uint32_t       w      = 1U;
     while (w < n)
         w <<= 1;
-    float *x = p.part + (live ? column : 0);
+    float *x = part + (live ? column : 0);
     if (live)
     {
         for (uint32_t h = w >> 1; h >= static_cast<uint32_t>(kLearnStepRows); h >>= 1)
@@ -231,12 +231,25 @@ __global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okLearnStepKer
     }
     __syncthreads();
     if (!live || r != 0)
-        return;
+        return false;
     for (uint32_t h = (w >> 1) < kLearnStepRows / 2U ? (w >> 1) : kLearnStepRows / 2U; h >= 1U; h >>= 1)
         for (uint32_t i = 0; i < h; ++i)
             if (i + h < n)
                 last[i][c] = last[i][c] + last[i + h][c];
-    const float sum = last[0][c], bk = static_cast<float>(p.Bk);
+    *column_out = column;
+    *sum_out    = last[0][c];
+    return true;
+}
+
+__global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okLearnStepKernel(const OkLearnParams p)
+{
+    __shared__ float last[kLearnStepRows][kLearnStepCols];
+    int              column = 0;
+    float            sum    = 0.F;
+    if (!okLearnColumnSum(p.part, p.cols, p.C, last, &column, &sum))
+        return;
+    const uint32_t n  = static_cast<uint32_t>(p.C);
+    const float    bk = static_cast<float>(p.Bk);
     if (column < p.Pp)
     {
         const float g = sum / bk;

@@ -25,6 +25,7 @@
 #include "ok_actor.h"
 #include "ok_batch.h"
 #include "ok_learn.h"
+#include "ok_dqn.h"
 #include "ok_expert.h"
 
 namespace
@@ -488,6 +489,21 @@ struct okenv
     size_t                  learn_part_bytes{0};
     std::vector<hipEvent_t> learn_events;
     size_t                  learn_timed{0};           // events of the latest timed update (0: it ran untimed)
+    // Deep-Q (okenv_replay_create, okenv_dqn_params): the ring's fields and counter, the push's scratch [snapshot | counts], the update's
+    // constants, the target network's copy, the chunk partials (grown, never shrunk) and the events of the latest timed update
+    bool                    replay_ok{false};
+    uint32_t                replay_flags{0};
+    int32_t                 replay_capacity{0};
+    okenv_replay_ring       replay{};
+    uint64_t               *d_replay_words{nullptr};  // [0] pushed, [1] its value before the latest push
+    uint32_t               *d_replay_counts{nullptr};
+    okenv_dqn_config        dqn{0.99F, 0U, 0, 0U};
+    float                  *d_dqn_target{nullptr};
+    bool                    dqn_target_set{false};
+    uint8_t                *d_dqn_part{nullptr};
+    size_t                  dqn_part_bytes{0};
+    std::vector<hipEvent_t> dqn_events;
+    size_t                  dqn_timed{0};
 };
 
 struct okenv_track
@@ -1368,6 +1384,8 @@ extern "C"
             if (e != nullptr)
                 (void)hipEventDestroy(e);
         for (hipEvent_t e : h->learn_events)
+            (void)hipEventDestroy(e);
+        for (hipEvent_t e : h->dqn_events)
             (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
             (void)hipStreamDestroy(h->stream);
@@ -2262,6 +2280,7 @@ extern "C"
         h->actor_policy_set = false;
         h->actor_value_set  = false;
         h->learner_ok       = false; // (Adam's moments belong to the networks that were just replaced)
+        h->dqn_target_set   = false; // (and so does the target network's copy)
         return OKENV_OK;
     }
 
@@ -2702,6 +2721,326 @@ extern "C"
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_ppo_update_host: state lacks a parameter or moment vector, or t < 0");
         const okenv_ppo_output none{};
         okLearnUpdateHost(*params, num_rays, hidden, num_actions, value_hidden, *state, *batch, M, B, epochs, order, out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    // ---- Deep-Q learning: replay ring, sampling and the TD update (ok_dqn.h) ------------------------------------------------
+
+    int okenv_replay_create(okenv_t h, int32_t capacity, uint32_t flags)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_replay_create: NULL handle");
+        if (const char *why = okReplayCheckCreate(capacity, flags))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_replay_create: ") + why);
+        if (h->shape.R > OK_ACTOR_MAX_RAYS)
+            return fail(h, OKENV_ERR_INVALID, "okenv_replay_create: the fan needs 1 .. 64 rays");
+        OK_HIP(h, hipSetDevice(h->device));
+        OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in an earlier ring
+        h->replay_ok = false;
+        void *const old[5] = {h->replay.state, h->replay.next_state, h->replay.action, h->replay.reward, h->replay.done};
+        for (void *q : old)
+            if (q != nullptr)
+            {
+                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), q), h->allocations.end());
+                (void)hipFree(q);
+            }
+        h->replay = okenv_replay_ring{};
+        const size_t C = static_cast<size_t>(capacity), R = static_cast<size_t>(h->shape.R);
+        const size_t blocks = (static_cast<size_t>(h->shape.N) + kReplayThreads - 1U) / kReplayThreads;
+        int          rc = devAlloc(h, &h->replay.state, C * R);
+        if (rc != OKENV_OK || (rc = devAlloc(h, &h->replay.next_state, C * R)) != OKENV_OK || (rc = devAlloc(h, &h->replay.action, C)) != OKENV_OK ||
+            (rc = devAlloc(h, &h->replay.reward, C)) != OKENV_OK || (rc = devAlloc(h, &h->replay.done, C)) != OKENV_OK ||
+            (rc = devEnsure(h, &h->d_replay_words, 2)) != OKENV_OK || (rc = devEnsure(h, &h->d_replay_counts, blocks)) != OKENV_OK)
+            return rc;
+        OK_HIP(h, hipMemsetAsync(h->d_replay_words, 0, 2U * sizeof(uint64_t), h->stream));
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDqnGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        h->replay_capacity = capacity;
+        h->replay_flags    = flags;
+        h->replay_ok       = true;
+        return OKENV_OK;
+    }
+
+    int okenv_replay_reset(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_replay_reset: call okenv_replay_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        OK_HIP(h, hipMemsetAsync(h->d_replay_words, 0, 2U * sizeof(uint64_t), h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_replay_push(okenv_t h, const okenv_actor_record *rec, const float *reward)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_replay_push: NULL handle");
+        if (!h->replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_replay_push: call okenv_replay_create first");
+        if (!rec)
+            return fail(h, OKENV_ERR_INVALID, "okenv_replay_push: the record is NULL");
+        if (!rec->state || !rec->action)
+            return fail(h, OKENV_ERR_INVALID, "okenv_replay_push: the record needs state and action");
+        if (!rec->alive && (h->replay_flags & OKENV_REPLAY_PUSH_ALL) == 0U)
+            return fail(h, OKENV_ERR_INVALID, "okenv_replay_push: the record needs alive (or create the ring with OKENV_REPLAY_PUSH_ALL)");
+        OK_HIP(h, hipSetDevice(h->device));
+        OkReplayParams p{};
+        p.N        = h->shape.N;
+        p.R        = h->shape.R;
+        p.flags    = h->replay_flags;
+        p.capacity = static_cast<uint64_t>(h->replay_capacity);
+        p.ring     = h->replay;
+        p.pushed   = h->d_replay_words;
+        p.snapshot = h->d_replay_words + 1;
+        p.counts   = h->d_replay_counts;
+        p.rec      = *rec;
+        p.dist     = h->st.dist;
+        p.crashed  = h->st.crashed;
+        p.reward   = reward;
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + kReplayThreads - 1) / kReplayThreads);
+        hipLaunchKernelGGL(okReplayCountKernel, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        hipLaunchKernelGGL(okReplayScatterKernel, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_replay_size(okenv_t h, int64_t *size, int64_t *pushed)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_replay_size: call okenv_replay_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        uint64_t word = 0;
+        OK_HIP(h, hipMemcpyAsync(&word, h->d_replay_words, sizeof(word), hipMemcpyDeviceToHost, h->stream));
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        if (size)
+            *size = static_cast<int64_t>(ok_dqn_size(word, static_cast<uint64_t>(h->replay_capacity)));
+        if (pushed)
+            *pushed = static_cast<int64_t>(word);
+        return OKENV_OK;
+    }
+
+    int okenv_replay_get(okenv_t h, const okenv_replay_ring *out)
+    {
+        OK_QUIESCE(h);
+        if (!h || !out)
+            return fail(h, OKENV_ERR_INVALID, "okenv_replay_get: NULL argument");
+        if (!h->replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_replay_get: call okenv_replay_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t C = static_cast<size_t>(h->replay_capacity), R = static_cast<size_t>(h->shape.R);
+        void *const       dst[5]   = {out->state, out->next_state, out->action, out->reward, out->done};
+        const void *const src[5]   = {h->replay.state, h->replay.next_state, h->replay.action, h->replay.reward, h->replay.done};
+        const size_t      bytes[5] = {C * R * sizeof(float), C * R * sizeof(float), C * sizeof(int64_t), C * sizeof(float), C * sizeof(float)};
+        for (int k = 0; k < 5; ++k)
+            if (dst[k] != nullptr)
+            {
+                const int rc = copyAny(h, dst[k], src[k], bytes[k]);
+                if (rc != OKENV_OK)
+                    return rc;
+            }
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_dqn_sync_target(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_dqn_sync_target: NULL handle");
+        if (h->dqn.target_network == 0 || h->d_dqn_target == nullptr)
+            return fail(h, OKENV_ERR_STATE, "okenv_dqn_sync_target: okenv_dqn_params has not turned the target network on");
+        if (!h->actor_ok || !h->actor_policy_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_dqn_sync_target: the actor has no parameters yet (okenv_actor_create, okenv_actor_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        // (whole float4s: the kernels stage a network in 16-byte loads, and the actor's vector is padded the same way)
+        const size_t n = (static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions)) + 3U) & ~static_cast<size_t>(3U);
+        OK_HIP(h, hipMemcpyAsync(h->d_dqn_target, h->d_actor_policy, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        h->dqn_target_set = true;
+        return OKENV_OK;
+    }
+
+    int okenv_dqn_params(okenv_t h, const okenv_dqn_config *config)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_dqn_params: NULL handle");
+        if (const char *why = okDqnCheckConfig(config))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_dqn_params: ") + why);
+        if (config->target_network == 0)
+        {
+            h->dqn = *config;
+            return OKENV_OK;
+        }
+        OK_HIP(h, hipSetDevice(h->device));
+        const int rc = devEnsure(h, &h->d_dqn_target, static_cast<size_t>(ok_actor_num_params(OK_ACTOR_MAX_RAYS, OK_ACTOR_MAX_HIDDEN, OK_ACTOR_MAX_ACTIONS)) + 4U);
+        if (rc != OKENV_OK)
+            return rc;
+        const bool turned_on = h->dqn.target_network == 0;
+        h->dqn               = *config;
+        if (turned_on)
+        { // (an earlier copy is stale: the switch going on is a sync, or the wait for one)
+            h->dqn_target_set = false;
+            if (h->actor_ok && h->actor_policy_set)
+                return okenv_dqn_sync_target(h);
+        }
+        return OKENV_OK;
+    }
+
+    int okenv_dqn_update(okenv_t h, int32_t B, int32_t iterations, int32_t resample, uint32_t draw_base, const okenv_dqn_output *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_dqn_update: NULL handle");
+        if (!h->learner_ok || !h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: call okenv_learner_create first");
+        if (!h->replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: call okenv_replay_create first");
+        if (h->dqn.target_network != 0 && !h->dqn_target_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: the target network was never filled (okenv_dqn_sync_target)");
+        if (const char *why = okDqnCheckCall(B, iterations, h->actor.num_actions))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_dqn_update: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkDqnParams p{};
+        p.R        = h->shape.R;
+        p.H        = h->actor.hidden;
+        p.A        = h->actor.num_actions;
+        p.B        = B;
+        p.C        = (B + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+        p.Pp       = ok_actor_num_params(p.R, p.H, p.A);
+        p.cols     = p.Pp + 1;
+        p.capacity = static_cast<uint64_t>(h->replay_capacity);
+        p.pushed   = h->d_replay_words;
+        p.ring     = h->replay;
+        p.policy   = h->d_actor_policy;
+        p.pol_m    = h->d_learn_moments;
+        p.pol_v    = h->d_learn_moments + h->learn_cap;
+        p.target   = h->dqn.target_network != 0 ? h->d_dqn_target : h->d_actor_policy;
+        p.gamma    = h->dqn.gamma;
+        p.flags    = h->dqn.flags;
+        p.seed     = h->dqn.seed;
+        const okenv_dqn_output none{};
+        const okenv_dqn_output &o = out != nullptr ? *out : none;
+        p.grad_policy = o.grad_policy;
+        p.index       = o.index;
+        const size_t bytes = sizeof(float) * static_cast<size_t>(p.C) * static_cast<size_t>(p.cols);
+        if (bytes > h->dqn_part_bytes)
+        {
+            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in the old one
+            if (h->d_dqn_part != nullptr)
+            {
+                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_dqn_part)), h->allocations.end());
+                (void)hipFree(h->d_dqn_part);
+                h->d_dqn_part     = nullptr;
+                h->dqn_part_bytes = 0;
+            }
+            uint8_t  *fresh = nullptr;
+            const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
+            if (rc != OKENV_OK)
+                return rc;
+            h->d_dqn_part     = fresh;
+            h->dqn_part_bytes = bytes + bytes / 2U;
+        }
+        p.part = reinterpret_cast<float *>(h->d_dqn_part);
+        const size_t launches = 2U * static_cast<size_t>(iterations);
+        h->dqn_timed = 0;
+        if (h->timing)
+        {
+            while (h->dqn_events.size() < launches + 1U)
+            {
+                hipEvent_t e = nullptr;
+                OK_HIP(h, hipEventCreate(&e));
+                h->dqn_events.push_back(e);
+            }
+            OK_HIP(h, hipEventRecord(h->dqn_events[0], h->stream));
+        }
+        const size_t lds = okDqnLdsBytes(p.R, p.H, p.A);
+        size_t       ev  = 0;
+        for (int it = 0; it < iterations; ++it)
+        {
+            p.draw = draw_base + (resample != 0 ? static_cast<uint32_t>(it) : 0U);
+            p.adam = okLearnAdamConsts(h->learner, h->learn_t + 1);
+            p.loss = o.loss != nullptr ? o.loss + it : nullptr;
+            // (the step number advances once both kernels of the iteration are enqueued, as in okenv_ppo_update)
+            hipLaunchKernelGGL(okDqnGradKernel, dim3(static_cast<unsigned>(p.C)), dim3(kLearnThreads), lds, h->stream, p);
+            OK_HIP(h, hipGetLastError());
+            if (h->timing)
+                OK_HIP(h, hipEventRecord(h->dqn_events[++ev], h->stream));
+            hipLaunchKernelGGL(okDqnStepKernel, dim3(static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols)),
+                               dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
+            OK_HIP(h, hipGetLastError());
+            h->learn_t += 1;
+            if (h->timing)
+                OK_HIP(h, hipEventRecord(h->dqn_events[++ev], h->stream));
+        }
+        h->dqn_timed = h->timing ? launches + 1U : 0U;
+        return OKENV_OK;
+    }
+
+    int okenv_debug_dqn_timing(okenv_t h, double *ms2)
+    {
+        OK_QUIESCE(h);
+        if (!h || !ms2)
+            return fail(h, OKENV_ERR_INVALID, "okenv_debug_dqn_timing: NULL argument");
+        if (h->dqn_timed < 3U)
+            return fail(h, OKENV_ERR_STATE, "okenv_debug_dqn_timing: no okenv_dqn_update has run with okenv_set_timing on");
+        OK_HIP(h, hipEventSynchronize(h->dqn_events[h->dqn_timed - 1U]));
+        ms2[0] = ms2[1] = 0.0;
+        for (size_t k = 0; k + 1U < h->dqn_timed; ++k)
+        {
+            float ms = 0.F;
+            OK_HIP(h, hipEventElapsedTime(&ms, h->dqn_events[k], h->dqn_events[k + 1U]));
+            ms2[k & 1U] += ms;
+        }
+        return OKENV_OK;
+    }
+
+    int okenv_replay_push_host(const okenv_replay_ring *ring, int32_t capacity, int32_t num_rays, uint64_t *pushed, uint32_t flags, int32_t n,
+                               const float *state, const int64_t *action, const uint8_t *alive, const float *dist, const uint8_t *crashed,
+                               const float *reward)
+    {
+        if (const char *why = okReplayCheckCreate(capacity, flags))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_replay_push_host: ") + why);
+        if (!okReplayRingComplete(ring) || !pushed)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_replay_push_host: the ring needs every field and its counter");
+        if (num_rays < 1 || num_rays > OK_ACTOR_MAX_RAYS || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_replay_push_host: the fan needs 1 .. 64 rays and n >= 0");
+        if (!state || !action)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_replay_push_host: the record needs state and action");
+        if (!alive && (flags & OKENV_REPLAY_PUSH_ALL) == 0U)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_replay_push_host: the record needs alive (or pass OKENV_REPLAY_PUSH_ALL)");
+        if (!dist || !crashed)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_replay_push_host: dist and crashed are required");
+        okReplayPushHost(*ring, static_cast<uint64_t>(capacity), num_rays, pushed, flags, n, state, action, alive, dist, crashed, reward);
+        return OKENV_OK;
+    }
+
+    int okenv_dqn_update_host(const okenv_learner_params *params, const okenv_dqn_config *config, int32_t num_rays, int32_t hidden, int32_t num_actions,
+                              okenv_learner_state *state, const float *target, const okenv_replay_ring *ring, int64_t size, int32_t B,
+                              int32_t iterations, int32_t resample, uint32_t draw_base, const okenv_dqn_output *out)
+    {
+        if (const char *why = okLearnCheckParams(params))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_dqn_update_host: ") + why);
+        if (const char *why = okDqnCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_dqn_update_host: ") + why);
+        if (num_rays < 1 || num_rays > OK_ACTOR_MAX_RAYS || hidden < 1 || hidden > OK_ACTOR_MAX_HIDDEN || num_actions < 2 || num_actions > OK_ACTOR_MAX_ACTIONS)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_dqn_update_host: a network width outside the actor's limits");
+        if (const char *why = okDqnCheckCall(B, iterations, num_actions))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_dqn_update_host: ") + why);
+        if (state == nullptr || state->policy == nullptr || state->policy_m == nullptr || state->policy_v == nullptr || state->t < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_dqn_update_host: state lacks a parameter or moment vector, or t < 0");
+        if ((config->target_network != 0) != (target != nullptr))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_dqn_update_host: target is required exactly when the target network is on");
+        if (size < 0 || size >= (INT64_C(1) << 31) || (size > 0 && !okReplayRingComplete(ring)))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_dqn_update_host: size outside 0 .. 2^31 - 1, or a ring without every field");
+        const okenv_dqn_output  none{};
+        const okenv_replay_ring empty{};
+        okDqnUpdateHost(*params, *config, num_rays, hidden, num_actions, *state, target, ring != nullptr ? *ring : empty, static_cast<uint32_t>(size), B,
+                        iterations, resample != 0, draw_base, out != nullptr ? *out : none);
         return OKENV_OK;
     }
 

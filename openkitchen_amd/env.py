@@ -591,6 +591,63 @@ class BatchedEnvironment:
         capi.check(self._L.okenv_debug_update_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
         return {k: 1000.0 * v for k, v in zip(capi.UPDATE_KERNELS, ms)}
 
+    # ---- Deep-Q learning (include/okenv.h) ----------------------------------------------------------
+    def replay_create(self, capacity, push_all=False):
+        """Attaches a replay ring of `capacity` transitions (state, next_state [C,R], action, reward, done [C]) to the handle; an
+        earlier one is dropped and its memory freed: a HIP graph that captured replay_push before this call must not be replayed again
+        (VectorEnvironment.enable_replay drops the ones it keeps).  push_all: push every agent, not only those that entered the step
+        alive."""
+        capi.check(self._L.okenv_replay_create(self._h, int(capacity), capi.REPLAY_PUSH_ALL if push_all else 0), self._h)
+        self.replay_capacity = int(capacity)
+
+    def replay_reset(self):
+        capi.check(self._L.okenv_replay_reset(self._h), self._h)
+
+    def replay_push(self, record, reward=None):
+        """Appends the transitions of the step that has just run: `record` is the dict the preceding actor_act was given ("state",
+        "action" and, unless push_all, "alive"); reward: None (the clearance rule) or a device float32 tensor [N].  Two kernels on
+        the handle's stream, no synchronisation."""
+        rec = capi.fill_pointers(capi.OkenvActorRecord(), {k: v for k, v in record.items() if k in ("state", "action", "alive")}, "actor record")
+        capi.check(self._L.okenv_replay_push(self._h, C.byref(rec), capi.ptr(reward)), self._h)
+
+    def replay_size(self):
+        """(transitions in the ring, transitions ever pushed); waits for the stream."""
+        size, pushed = C.c_int64(), C.c_int64()
+        capi.check(self._L.okenv_replay_size(self._h, C.byref(size), C.byref(pushed)), self._h)
+        return size.value, pushed.value
+
+    def replay_get(self, out=None):
+        """The ring's fields, all `capacity` slots: numpy arrays, or copied into the device tensors of the dict `out`.  Synchronises."""
+        Cn, R = self.replay_capacity, self.R
+        if out is None:
+            out = {"state": np.empty((Cn, R), np.float32), "next_state": np.empty((Cn, R), np.float32), "action": np.empty(Cn, np.int64),
+                   "reward": np.empty(Cn, np.float32), "done": np.empty(Cn, np.float32)}
+        ring = capi.fill_pointers(capi.OkenvReplayRing(), out, "replay ring")
+        capi.check(self._L.okenv_replay_get(self._h, C.byref(ring)), self._h)
+        return out
+
+    def dqn_params(self, gamma=0.99, mask_done=False, target_network=False, seed=0):
+        cfg = capi.dqn_config(gamma, mask_done, target_network, seed)
+        capi.check(self._L.okenv_dqn_params(self._h, C.byref(cfg)), self._h)
+        self.dqn_config = cfg
+
+    def dqn_sync_target(self):
+        capi.check(self._L.okenv_dqn_sync_target(self._h), self._h)
+
+    def dqn_update(self, B, iterations, resample=False, draw_base=0, out=None):
+        """okenv_dqn_update: `iterations` gradient steps on batches of B uniform samples of the ring, two kernels each on the handle's
+        stream, no synchronisation.  out: None or a dict of device tensors under "loss" [iterations] float32, "grad_policy", "index"
+        [B] int32."""
+        po = capi.fill_pointers(capi.OkenvDqnOutput(), out or {}, "dqn output")
+        capi.check(self._L.okenv_dqn_update(self._h, int(B), int(iterations), 1 if resample else 0, int(draw_base) & 0xFFFFFFFF, C.byref(po)), self._h)
+
+    def dqn_timing(self):
+        """Device microseconds of the latest dqn_update that ran with set_timing(True), summed over its iterations, by
+        capi.UPDATE_KERNELS."""
+        ms = (C.c_double * 2)()
+        capi.check(self._L.okenv_debug_dqn_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
+        return {k: 1000.0 * v for k, v in zip(capi.UPDATE_KERNELS, ms)}
+
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):
         """{rays, tests, cells, points} the broad phase leaves for the current poses (okenv_work_stats)."""
@@ -767,6 +824,57 @@ def ppo_update_host(params, shape, state, batch, B, epochs=1, order=None, want=(
     capi.check(capi.load().okenv_ppo_update_host(C.byref(params) if params is not None else None, R, H, A, Hv, C.byref(st),
                                                  C.byref(capi.fill_pointers(capi.OkenvPpoBatch(), b, "ppo batch")), M, int(B), int(epochs),
                                                  capi.ptr(order), C.byref(capi.fill_pointers(capi.OkenvPpoOutput(), {k: v for k, v in outs.items() if v.size}, "ppo output"))))
+    new["t"] = int(st.t)
+    return new, outs
+
+
+def replay_ring(capacity, num_rays):
+    """An empty replay ring on the host: dict of zeroed numpy arrays and "pushed" = 0."""
+    return {"state": np.zeros((capacity, num_rays), np.float32), "next_state": np.zeros((capacity, num_rays), np.float32),
+            "action": np.zeros(capacity, np.int64), "reward": np.zeros(capacity, np.float32), "done": np.zeros(capacity, np.float32), "pushed": 0}
+
+
+def _ring_struct(ring):
+    return capi.fill_pointers(capi.OkenvReplayRing(), {k: v for k, v in ring.items() if k != "pushed"}, "replay ring")
+
+
+def replay_push_host(ring, state, action, alive, dist, crashed, reward=None, push_all=False):
+    """One push on host arrays, no GPU needed (okenv_replay_push_host): `ring` (replay_ring(...)) is updated in place, "pushed"
+    included.  state [n,R], action [n] int64 and alive [n] are the actor record, dist [n,R] and crashed [n] the fields after the step."""
+    Cn, R = ring["state"].shape
+    state = np.ascontiguousarray(state, dtype=np.float32)
+    action = np.ascontiguousarray(action, dtype=np.int64)
+    alive = None if alive is None else np.ascontiguousarray(alive).astype(np.uint8)
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    crashed = np.ascontiguousarray(crashed).astype(np.uint8)
+    reward = None if reward is None else np.ascontiguousarray(reward, dtype=np.float32)
+    n = action.shape[0]
+    assert state.shape == (n, R) and dist.shape == (n, R) and crashed.shape == (n,)
+    pushed = C.c_uint64(int(ring["pushed"]))
+    capi.check(capi.load().okenv_replay_push_host(C.byref(_ring_struct(ring)), Cn, R, C.byref(pushed), capi.REPLAY_PUSH_ALL if push_all else 0, n,
+                                                  capi.ptr(state), capi.ptr(action), capi.ptr(alive), capi.ptr(dist), capi.ptr(crashed), capi.ptr(reward)))
+    ring["pushed"] = int(pushed.value)
+    return ring
+
+
+def dqn_update_host(params, config, shape, state, ring, B, iterations=1, resample=False, draw_base=0, target=None, size=None,
+                    want=("loss", "grad_policy", "index")):
+    """Deep-Q's update on host arrays, no GPU needed (okenv_dqn_update_host).  params: capi.learner_params(...); config:
+    capi.dqn_config(...); shape: (R, H, A); state: dict of float32 arrays "policy", "policy_m", "policy_v" and the int "t" -- copied, the
+    new state is returned; ring: replay_ring(...) as the pushes left it; target: the target network's parameters when config turns it
+    on.  Returns (new state, outputs): outputs holds the arrays named in `want`."""
+    R, H, A = (int(v) for v in shape)
+    new = {k: np.array(state[k], dtype=np.float32, copy=True).ravel() for k in ("policy", "policy_m", "policy_v")}
+    st = capi.fill_pointers(capi.OkenvLearnerState(), new, "learner state")
+    st.t = int(state.get("t", 0))
+    size = min(int(ring["pushed"]), ring["state"].shape[0]) if size is None else int(size)
+    sizes = {"loss": (max(int(iterations), 0), np.float32), "grad_policy": (H * R + H + A * H + A, np.float32), "index": (max(int(B), 0), np.int32)}
+    outs = {k: np.zeros(sizes[k][0], dtype=sizes[k][1]) for k in want}
+    target = None if target is None else np.ascontiguousarray(target, dtype=np.float32).ravel()
+    capi.check(capi.load().okenv_dqn_update_host(C.byref(params) if params is not None else None, C.byref(config) if config is not None else None,
+                                                 R, H, A, C.byref(st), capi.ptr(target), C.byref(_ring_struct(ring)), size, int(B), int(iterations),
+                                                 1 if resample else 0, int(draw_base) & 0xFFFFFFFF,
+                                                 C.byref(capi.fill_pointers(capi.OkenvDqnOutput(), {k: v for k, v in outs.items() if v.size}, "dqn output"))))
     new["t"] = int(st.t)
     return new, outs
 

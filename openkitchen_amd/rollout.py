@@ -14,6 +14,8 @@ from . import _capi as capi
 
 # PPOAgent::kActionMap (RLRacers/PPO/PPOAgent.hpp:41-43): action index -> (throttle, steering)
 PPO_ACTIONS = ((60.0, 0.0), (30.0, 5.0), (30.0, -5.0))
+# DQLearnAgent::kActionMap (RLRacers/Deep_Q_Learning/DQAgent.hpp:40-45)
+DQN_ACTIONS = ((60.0, 0.0), (30.0, 5.0), (30.0, -5.0), (30.0, 2.5), (30.0, -2.5))
 
 
 def collect_episode(venv, policy, max_steps=None, check_every=8, actions=PPO_ACTIONS):
@@ -292,6 +294,118 @@ def ppo_update(venv, batch, epochs=5, minibatch=4096, shuffle=True, use_advantag
     venv.env.ppo_update(data, M, minibatch, epochs, order, out)
     venv._update_inputs = (data, order)  # alive until the next update: the kernels are only enqueued
     return out
+
+
+def _dqn_record(venv):
+    return {"state": torch.empty((venv.num_envs, venv.num_rays), dtype=torch.float32, device=venv.device),
+            "action": torch.empty(venv.num_envs, dtype=torch.int64, device=venv.device),
+            "alive": torch.empty(venv.num_envs, dtype=torch.uint8, device=venv.device)}
+
+
+def collect_episode_dqn(venv, max_steps=None, check_every=8, graph_chunk=0, reward=None):
+    """One episode of dq_racer_sim.cpp:61-130 on the device: reset, then `actor_act (eps-greedy) -> step -> replay_push` until every
+    agent has crashed (tested every `check_every` steps) or `max_steps` steps have run.  Nothing but that test crosses to the host:
+    the transitions go straight into the ring of venv.enable_replay, which keeps them for later episodes.  reward: None for the
+    reference's clearance reward (DQAgent.hpp:162-181), "tracker" for the environment's own `reward` tensor, or a device tensor [N]
+    that the caller keeps up to date.
+
+    graph_chunk = K > 0: K iterations are captured once into a HIP graph (kept on `venv` until set_actor_epsilon changes what it
+    carries) and replayed; the test runs once per chunk.  Without auto-reset the graph's last node advances the word the actor adds
+    to its draw index, so replays keep drawing fresh numbers; eager and chunked episodes fill the ring with the same bits.
+
+    Returns {"steps": steps taken}; a multiple of K with a graph (crashed agents stand still, and only agents that entered a step
+    alive are pushed unless the ring was created with push_all)."""
+    assert getattr(venv, "_actor_nets", None) is not None, "call venv.enable_actor(q_network, mode=\"eps_greedy\") first"
+    assert getattr(venv, "replay_push_all", None) is not None, "call venv.enable_replay(capacity) first"
+    assert not venv.auto_reset or max_steps is not None, "with auto-reset on the episode never ends: pass max_steps"
+    if isinstance(reward, str):
+        assert reward == "tracker" and venv.reward_kind is not None, 'reward="tracker" needs a VectorEnvironment with a reward'
+        reward = venv.reward
+    K = int(graph_chunk)
+    venv.reset()
+    steps = 0
+    start = venv.env.step_count
+    if K <= 0:
+        rec = getattr(venv, "_dqn_rec", None) or _dqn_record(venv)
+        venv._dqn_rec = rec
+        while True:
+            venv.actor_act(rec)
+            venv.step()
+            venv.replay_push(rec, reward)
+            steps += 1
+            if steps % check_every == 0 and venv.env.alive_count() == 0:
+                break
+            if max_steps is not None and steps >= max_steps:
+                break
+        return {"steps": steps}
+    graph, offset, base = _dqn_chunk_graph(venv, K, reward)
+    if offset is not None:  # the captured launches carry base + k as their draw index
+        offset.fill_(((start - base + 2 ** 31) % 2 ** 32) - 2 ** 31)
+    try:
+        while True:
+            graph.replay()
+            steps += K
+            if venv.env.alive_count() == 0:
+                break
+            if max_steps is not None and steps >= max_steps:
+                break
+    finally:
+        if offset is not None:
+            venv.env.step_count = start + steps  # (replays do not advance the host's count)
+    return {"steps": steps}
+
+
+def _dqn_chunk_graph(venv, K, reward):
+    """The captured chunk of K iterations of collect_episode_dqn: (graph, draw-offset word or None, the host step count the launches
+    were captured with); see _chunk_graph."""
+    key = ("dqn", K, None if reward is None else reward.data_ptr())
+    if key in venv._actor_graphs:
+        return venv._actor_graphs[key][:3]
+    rec = _dqn_record(venv)
+    offset = None if venv.auto_reset else torch.zeros(1, dtype=torch.int32, device=venv.device)
+
+    def body():
+        for _ in range(K):
+            venv.actor_act(rec)
+            venv.step()
+            venv.replay_push(rec, reward)
+        if offset is not None:
+            offset.add_(K)
+
+    base = venv.env.step_count
+    if offset is not None:
+        offset.add_(0)  # torch's own kernel is loaded before the capture; ours are already
+    venv.env.actor_set_draw_offset(offset)  # the captured launches keep the pointer; eager calls afterwards get none
+    try:
+        graph = venv.capture(body, warmup=0)  # no warm-up iterations: they would push into the ring and move the count
+    finally:
+        venv.env.actor_set_draw_offset(None)
+    venv._actor_graphs[key] = (graph, offset, base, rec, reward)  # (the record and the reward are the graph's: kept alive with it)
+    return graph, offset, base
+
+
+def dqn_update(venv, batch=100, iterations=200, resample=False, draw=None, grads=False):
+    """DQLearnAgent::updateDQN on the device (okenv_dqn_update, DESIGN.md section 17): `iterations` gradient steps of the mean squared
+    temporal-difference error on `batch` uniform samples of the ring, with Adam, in place in the parameters the device actor acts with
+    (venv.enable_actor, venv.enable_learner(lr=1e-4) and venv.enable_replay first; no sync_actor afterwards, venv.pull_actor() brings
+    them back to the module).  resample=False draws one batch for all iterations, as the reference does; True draws a fresh one per
+    iteration (its commented alternative).  draw: the number of the first draw; by default a count kept on `venv`, so that every call
+    samples afresh.
+
+    Everything is enqueued on the environment's stream; the ring's size is read on the device and nothing is read back.  Returns the
+    loss of every iteration as a device tensor [iterations]; with grads=True a dict with "loss", "grad_policy" and "index" (the slots
+    of the last iteration's batch)."""
+    used = int(iterations) if resample else 1
+    if draw is None:
+        draw = venv._dqn_draw
+        venv._dqn_draw = (draw + used) % 2 ** 32
+    out = {"loss": torch.empty(int(iterations), dtype=torch.float32, device=venv.device)}
+    if grads:
+        out["grad_policy"] = torch.empty(venv.env.actor_num_params()[0], dtype=torch.float32, device=venv.device)
+        out["index"] = torch.empty(int(batch), dtype=torch.int32, device=venv.device)
+    venv.env.dqn_update(batch, iterations, resample, draw, out)
+    venv._update_inputs = out  # alive until the next update: the kernels are only enqueued
+    return out if grads else out["loss"]
 
 
 def batch_stats(batch):

@@ -297,6 +297,28 @@ class VectorEnvironment:
         uint8 or bool) that receive the sample."""
         self.env.actor_act(record)
 
+    # ---- Deep-Q learning (include/okenv.h, DESIGN.md section 17) --------------------------------------------------------------
+    def enable_replay(self, capacity, push_all=False, gamma=0.99, mask_done=False, target_network=False, seed=None):
+        """Attaches a replay ring of `capacity` transitions that persists across episodes on the device, and sets the constants of
+        rollout.dqn_update: the reference's discount, its target r + gamma max q' (mask_done: (1 - done) in front of gamma), no
+        target network (target_network=True: q' comes from a copy that sync_target() refreshes).  push_all: push crashed agents' frozen
+        observations too, as the reference's loop does; the default pushes the agents that entered the step alive."""
+        self.env.replay_create(capacity, push_all)
+        self.env.dqn_params(gamma, mask_done, target_network, self.seed if seed is None else seed)
+        self.replay_push_all = bool(push_all)
+        self._dqn_draw = 0
+        self._actor_graphs = {}  # a captured push carries the old ring's pointers, capacity and flags
+
+    def replay_push(self, record, reward=None):
+        """Appends the transitions of the step that has just run to the ring: `record` is the dict the preceding actor_act filled
+        ("state", "action", "alive"); reward: None for the reference's clearance reward, or a device float32 tensor [N] (the tracker's
+        `reward`, say).  Two kernels on the environment's stream, no synchronisation, usable inside capture(body)."""
+        self.env.replay_push(record, reward)
+
+    def sync_target(self):
+        """Copies the online Q network into the target network (device to device, no synchronisation)."""
+        self.env.dqn_sync_target()
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
