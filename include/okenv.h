@@ -558,6 +558,105 @@ OKENV_API int okenv_dqn_update_host(const okenv_learner_params *params, const ok
                                     int64_t size, int32_t B, int32_t iterations, int32_t resample, uint32_t draw_base,
                                     const okenv_dqn_output *out);
 
+/* ---- DDPG: continuous actor, critic, replay ring and update -----------------------------------------------
+ * RLRacers/DDPG (ddpg_sim.cpp:55-95, DDPGAgent.hpp:60-170) for every agent of the handle: an actor R -> H -> 2 that ends in
+ * tanh * scale + bias and writes throttle_delta / steering_delta as real numbers, a critic (R + 2) -> Hc -> 1 on [state, action], two
+ * target networks with soft updates, a ring whose action is two floats, and the update's iterations.  The rule is written out in
+ * include/okenv_ddpg.h (ok_ddpg_*).  A DDPG object and a shared-network actor (okenv_actor_create) may live on one handle; neither
+ * reads the other's buffers. */
+typedef struct okenv_ddpg_config {
+    int32_t  hidden;           /* H, 1 .. 256                                                       */
+    int32_t  critic_hidden;    /* Hc, 1 .. 256                                                      */
+    float    scale[2];         /* a_k = tanh(z_k) * scale_k + bias_k  (Actor.hpp: 50, 5)            */
+    float    bias[2];          /*                                     (Actor.hpp: 50, 0)            */
+    float    noise[2];         /* >= 0; 0: no exploration (the reference)                           */
+    uint32_t seed, agent_base; /* key of the exploration draws; global id of the handle's agent 0   */
+    float    gamma;            /* [0, 1] (kGamma 0.99)                                              */
+    float    tau;              /* [0, 1] (kTau 0.005)                                               */
+    float    lr_actor;         /* > 0 (1e-4)                                                        */
+    float    lr_critic;        /* > 0 (1e-3)                                                        */
+    float    beta1, beta2;     /* [0, 1), torch: 0.9, 0.999                                         */
+    float    eps;              /* > 0, torch: 1e-8                                                  */
+    uint32_t sample_seed;      /* key of the sampling draws                                         */
+} okenv_ddpg_config;
+
+/* Where okenv_ddpg_act leaves this step's sample, besides the action fields: device pointers, each may be NULL (skipped). */
+typedef struct okenv_ddpg_record {
+    float   *state;  /* [N][R]  x, the actor's input (dist / kSensorRange)  */
+    float   *action; /* [N][2]  (throttle_delta, steering_delta)            */
+    uint8_t *alive;  /* [N]     !crashed_                                   */
+} okenv_ddpg_record;
+
+/* The ring's fields: device pointers, or host pointers where a call says so; [C] slots each. */
+typedef struct okenv_ddpg_ring {
+    float *state;      /* [C][R] */
+    float *next_state; /* [C][R] */
+    float *action;     /* [C][2] */
+    float *reward;     /* [C]    */
+    float *done;       /* [C]    1.0f: crashed_ after the step, else 0.0f */
+} okenv_ddpg_ring;
+
+/* Parameters, target networks and Adam state: host or device pointers where a call says so.  t: iterations so far (both networks
+ * step once per iteration). */
+typedef struct okenv_ddpg_state {
+    float  *actor, *critic, *actor_target, *critic_target;
+    float  *actor_m, *actor_v, *critic_m, *critic_v;
+    int64_t t;
+} okenv_ddpg_state;
+
+/* Where the update reports: device pointers (host pointers for okenv_ddpg_update_host), each may be NULL (skipped). */
+typedef struct okenv_ddpg_output {
+    float   *critic_loss; /* [iterations]  mse_loss of every iteration                  */
+    float   *actor_loss;  /* [iterations]  -mean q of every iteration                   */
+    float   *grad_critic; /* the last iteration's gradient, in parameter order          */
+    float   *grad_actor;  /* the last iteration's gradient, in parameter order          */
+    int32_t *index;       /* [B]           the slots the last iteration sampled         */
+} okenv_ddpg_output;
+
+/* Attaches a DDPG object to the handle (replaces an earlier one: parameters, moments and t are forgotten; a ring stays).  All device
+ * memory of acting and of the networks is allocated here.  OKENV_ERR_INVALID for NULL arguments, a width outside 1 .. 256, more than
+ * 62 rays, gamma or tau outside [0, 1] (or NaN), negative (or NaN) noise, lr or eps <= 0, a beta outside [0, 1). */
+OKENV_API int okenv_ddpg_create(okenv_t h, const okenv_ddpg_config *config);
+/* Floats of the two parameter vectors: actor [H][R], [H], [2][H], [2]; critic [Hc][R + 2], [Hc], [1][Hc], [1]. */
+OKENV_API int okenv_ddpg_num_params(okenv_t h, int32_t *actor, int32_t *critic);
+/* New online parameters from host or device pointers (NULL: left alone).  Each network that arrives also replaces its target network
+ * (DDPGAgent.hpp:65-74).  Moments and t are left alone.  No synchronisation. */
+OKENV_API int okenv_ddpg_set_params(okenv_t h, const float *actor, const float *critic);
+/* Every non-NULL member of `out` is filled from the device (host or device pointers); out->t is set; synchronises.
+ * OKENV_ERR_STATE before both networks have their parameters. */
+OKENV_API int okenv_ddpg_get_state(okenv_t h, okenv_ddpg_state *out);
+/* A device word added to the draw index of every later okenv_ddpg_act (NULL: none): okenv_actor_set_draw_offset's contract. */
+OKENV_API int okenv_ddpg_set_draw_offset(okenv_t h, const uint32_t *device_word);
+/* The action of every agent, crashed ones included: reads OKENV_F_DIST and crashed_, writes OKENV_F_THROTTLE / OKENV_F_STEER and the
+ * record.  One kernel on the handle's stream, no synchronisation, no allocation: capturable beside okenv_step; ends a running
+ * episode as okenv_actor_act does.  The draw index is okenv_actor_act's.  OKENV_ERR_STATE before the actor has its parameters. */
+OKENV_API int okenv_ddpg_act(okenv_t h, const okenv_ddpg_record *rec);
+/* The ring: okenv_replay_create / _reset / _push / _size / _get's contracts with a two-float action.  `reward` is NULL (1.0f per
+ * transition, ddpg_sim.cpp:73) or a device array [N].  Needs 1 .. 62 rays. */
+OKENV_API int okenv_ddpg_replay_create(okenv_t h, int32_t capacity, uint32_t flags);
+OKENV_API int okenv_ddpg_replay_reset(okenv_t h);
+OKENV_API int okenv_ddpg_replay_push(okenv_t h, const okenv_ddpg_record *rec, const float *reward);
+OKENV_API int okenv_ddpg_replay_size(okenv_t h, int64_t *size, int64_t *pushed);
+OKENV_API int okenv_ddpg_replay_get(okenv_t h, const okenv_ddpg_ring *out);
+/* `iterations` iterations on batches of B uniform samples of the ring, four kernels each on the handle's stream (critic gradient
+ * partials; join + Adam + soft update of the critic; actor gradient partials through the stepped critic; join + Adam + soft update
+ * of the actor): no synchronisation, and no allocation after the first call of a given B.  The next okenv_ddpg_act uses the new
+ * parameters.  OKENV_ERR_STATE before okenv_ddpg_create, before both networks have parameters, or before okenv_ddpg_replay_create;
+ * OKENV_ERR_INVALID for a NULL handle, B or iterations < 1. */
+OKENV_API int okenv_ddpg_update(okenv_t h, int32_t B, int32_t iterations, int32_t resample, uint32_t draw_base, const okenv_ddpg_output *out);
+/* The same rules on host arrays, no GPU needed.  Act: n agents (global ids config->agent_base + i), dist [n][num_rays], crashed [n]
+ * or NULL; outputs, each may be NULL: throttle, steer [n], action [n][2], state [n][num_rays], alive [n]. */
+OKENV_API int okenv_ddpg_act_host(const okenv_ddpg_config *config, const float *actor, int32_t num_rays, int32_t n, const float *dist,
+                                  const uint8_t *crashed, uint32_t draw_index, float *throttle, float *steer, float *action, float *state,
+                                  uint8_t *alive);
+OKENV_API int okenv_ddpg_replay_push_host(const okenv_ddpg_ring *ring, int32_t capacity, int32_t num_rays, uint64_t *pushed, uint32_t flags,
+                                          int32_t n, const float *state, const float *action, const uint8_t *alive, const float *dist,
+                                          const uint8_t *crashed, const float *reward);
+/* Every member of `state` is required; size = min(pushed, capacity). */
+OKENV_API int okenv_ddpg_update_host(const okenv_ddpg_config *config, int32_t num_rays, okenv_ddpg_state *state, const okenv_ddpg_ring *ring,
+                                     int64_t size, int32_t B, int32_t iterations, int32_t resample, uint32_t draw_base,
+                                     const okenv_ddpg_output *out);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.
@@ -842,6 +941,8 @@ OKENV_API int okenv_debug_batch_timing(okenv_t h, double *ms5);
 OKENV_API int okenv_debug_update_timing(okenv_t h, double *ms2);
 /* The same for the handle's latest okenv_dqn_update, summed over its iterations per kernel (gradient partials, join + Adam). */
 OKENV_API int okenv_debug_dqn_timing(okenv_t h, double *ms2);
+/* The same for the handle's latest okenv_ddpg_update: critic gradient, critic step, actor gradient, actor step. */
+OKENV_API int okenv_debug_ddpg_timing(okenv_t h, double *ms4);
 /* ok_learn_adam (include/okenv_learn.h) on host arrays: step number t >= 1 of n parameters p with moments m, v and gradients g, all
  * updated in place; host only, no GPU. */
 OKENV_API int okenv_debug_adam(const okenv_learner_params *params, int64_t t, float *p, float *m, float *v, const float *g, int32_t n);

@@ -76,6 +76,10 @@ SYMBOLS = [
     "okenv_replay_create", "okenv_replay_reset", "okenv_replay_push", "okenv_replay_size", "okenv_replay_get", "okenv_dqn_params",
     "okenv_dqn_update", "okenv_dqn_sync_target", "okenv_replay_push_host", "okenv_dqn_update_host",
     "okenv_debug_dqn_timing",
+    "okenv_ddpg_create", "okenv_ddpg_num_params", "okenv_ddpg_set_params", "okenv_ddpg_get_state", "okenv_ddpg_set_draw_offset",
+    "okenv_ddpg_act", "okenv_ddpg_replay_create", "okenv_ddpg_replay_reset", "okenv_ddpg_replay_push", "okenv_ddpg_replay_size",
+    "okenv_ddpg_replay_get", "okenv_ddpg_update", "okenv_debug_ddpg_timing", "okenv_ddpg_act_host", "okenv_ddpg_replay_push_host",
+    "okenv_ddpg_update_host",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -209,6 +213,47 @@ class OkenvDqnOutput(C.Structure):
 def dqn_config(gamma=0.99, mask_done=False, target_network=False, seed=0):
     """okenv_dqn_config with the reference's discount (DQAgent.hpp:33) and target (:133: no mask, no target network)."""
     return OkenvDqnConfig(float(gamma), DQN_MASK_DONE if mask_done else 0, 1 if target_network else 0, int(seed) & 0xFFFFFFFF)
+
+
+# DDPG (include/okenv.h)
+DDPG_MAX_RAYS = 62
+DDPG_KERNELS = ("critic_grad", "critic_step", "actor_grad", "actor_step")
+
+
+class OkenvDdpgConfig(C.Structure):
+    _fields_ = [("hidden", C.c_int32), ("critic_hidden", C.c_int32), ("scale", C.c_float * 2), ("bias", C.c_float * 2), ("noise", C.c_float * 2),
+                ("seed", C.c_uint32), ("agent_base", C.c_uint32), ("gamma", C.c_float), ("tau", C.c_float), ("lr_actor", C.c_float),
+                ("lr_critic", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("sample_seed", C.c_uint32)]
+
+
+class OkenvDdpgRecord(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("action", C.c_void_p), ("alive", C.c_void_p)]
+
+
+class OkenvDdpgRing(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("next_state", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p)]
+
+
+class OkenvDdpgState(C.Structure):
+    _fields_ = [("actor", C.c_void_p), ("critic", C.c_void_p), ("actor_target", C.c_void_p), ("critic_target", C.c_void_p),
+                ("actor_m", C.c_void_p), ("actor_v", C.c_void_p), ("critic_m", C.c_void_p), ("critic_v", C.c_void_p), ("t", C.c_int64)]
+
+
+DDPG_STATE_VECTORS = [name for name, _ in OkenvDdpgState._fields_ if name != "t"]
+
+
+class OkenvDdpgOutput(C.Structure):
+    _fields_ = [("critic_loss", C.c_void_p), ("actor_loss", C.c_void_p), ("grad_critic", C.c_void_p), ("grad_actor", C.c_void_p),
+                ("index", C.c_void_p)]
+
+
+def ddpg_config(hidden, critic_hidden, scale=(50.0, 5.0), bias=(50.0, 0.0), noise=(0.0, 0.0), seed=0, agent_base=0, gamma=0.99, tau=0.005,
+                lr_actor=1e-4, lr_critic=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, sample_seed=0):
+    """okenv_ddpg_config with the reference's constants as defaults (Actor.hpp:14-17, DDPGAgent.hpp:27-33: no exploration noise) and
+    torch.optim.Adam's."""
+    return OkenvDdpgConfig(int(hidden), int(critic_hidden), (C.c_float * 2)(*map(float, scale)), (C.c_float * 2)(*map(float, bias)),
+                           (C.c_float * 2)(*map(float, noise)), int(seed) & 0xFFFFFFFF, int(agent_base) & 0xFFFFFFFF, float(gamma), float(tau),
+                           float(lr_actor), float(lr_critic), float(beta1), float(beta2), float(eps), int(sample_seed) & 0xFFFFFFFF)
 
 
 def fill_pointers(struct, given, what):
@@ -416,6 +461,23 @@ def load(build_if_missing=True):
     L.okenv_dqn_update_host.argtypes = [C.POINTER(OkenvLearnerParams), C.POINTER(OkenvDqnConfig), i32, i32, i32, C.POINTER(OkenvLearnerState), vp,
                                         C.POINTER(OkenvReplayRing), C.c_int64, i32, i32, i32, u32, C.POINTER(OkenvDqnOutput)]
     L.okenv_debug_dqn_timing.argtypes = [vp, vp]
+    L.okenv_ddpg_create.argtypes = [vp, C.POINTER(OkenvDdpgConfig)]
+    L.okenv_ddpg_num_params.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.okenv_ddpg_set_params.argtypes = [vp, vp, vp]
+    L.okenv_ddpg_get_state.argtypes = [vp, C.POINTER(OkenvDdpgState)]
+    L.okenv_ddpg_set_draw_offset.argtypes = [vp, vp]
+    L.okenv_ddpg_act.argtypes = [vp, C.POINTER(OkenvDdpgRecord)]
+    L.okenv_ddpg_replay_create.argtypes = [vp, i32, u32]
+    L.okenv_ddpg_replay_reset.argtypes = [vp]
+    L.okenv_ddpg_replay_push.argtypes = [vp, C.POINTER(OkenvDdpgRecord), vp]
+    L.okenv_ddpg_replay_size.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.okenv_ddpg_replay_get.argtypes = [vp, C.POINTER(OkenvDdpgRing)]
+    L.okenv_ddpg_update.argtypes = [vp, i32, i32, i32, u32, C.POINTER(OkenvDdpgOutput)]
+    L.okenv_debug_ddpg_timing.argtypes = [vp, vp]
+    L.okenv_ddpg_act_host.argtypes = [C.POINTER(OkenvDdpgConfig), vp, i32, i32, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.okenv_ddpg_replay_push_host.argtypes = [C.POINTER(OkenvDdpgRing), i32, i32, C.POINTER(C.c_uint64), u32, i32, vp, vp, vp, vp, vp, vp]
+    L.okenv_ddpg_update_host.argtypes = [C.POINTER(OkenvDdpgConfig), i32, C.POINTER(OkenvDdpgState), C.POINTER(OkenvDdpgRing), C.c_int64, i32, i32, i32,
+                                         u32, C.POINTER(OkenvDdpgOutput)]
     _lib = L
     return L
 

@@ -45,12 +45,26 @@ constexpr int kReplayWave    = 64;
 constexpr int kReplayWaves   = kReplayThreads / kReplayWave;
 constexpr int kReplayLanes   = kActorLanes; // the group-copy pattern: 8 lanes per row
 
-__device__ __forceinline__ bool okReplaySelected(const OkReplayParams &p, const long a)
+// (The kernels of the push are templates over the parameter struct: ok_ddpg.h shares them with a ring whose action is two floats.
+// A struct brings its fields under the names used here and an okReplayStoreAction / okReplayReward of its own.)
+template <class P>
+__device__ __forceinline__ bool okReplaySelected(const P &p, const long a)
 {
     return a < p.N && ((p.flags & OK_REPLAY_PUSH_ALL) != 0U || p.rec.alive[a] != 0);
 }
 
-__global__ __launch_bounds__(kReplayThreads) void okReplayCountKernel(const OkReplayParams p)
+__device__ __forceinline__ void okReplayStoreAction(const OkReplayParams &p, const long long slot, const long a)
+{
+    p.ring.action[slot] = p.rec.action[a];
+}
+
+__device__ __forceinline__ float okReplayReward(const OkReplayParams &p, const int crash, const long a)
+{
+    return p.reward != nullptr ? p.reward[a] : ok_dqn_reward(crash, p.dist + a * p.R, p.R);
+}
+
+template <class P>
+__global__ __launch_bounds__(kReplayThreads) void okReplayCountKernel(const P p)
 {
     __shared__ uint32_t wave_count[kReplayWaves];
     const int           wv = static_cast<int>(threadIdx.x) / kReplayWave, lane = static_cast<int>(threadIdx.x) % kReplayWave;
@@ -69,7 +83,8 @@ __global__ __launch_bounds__(kReplayThreads) void okReplayCountKernel(const OkRe
     }
 }
 
-__global__ __launch_bounds__(kReplayThreads) void okReplayScatterKernel(const OkReplayParams p)
+template <class P>
+__global__ __launch_bounds__(kReplayThreads) void okReplayScatterKernel(const P p)
 {
     __shared__ uint32_t      wave_count[kReplayWaves];
     __shared__ uint32_t      before_part[kReplayThreads], total_part[kReplayThreads];
@@ -111,9 +126,9 @@ __global__ __launch_bounds__(kReplayThreads) void okReplayScatterKernel(const Ok
     {
         slot            = static_cast<long long>(ok_dqn_slot(start + k, p.capacity));
         const int crash = p.crashed[a] != 0;
-        p.ring.action[slot] = p.rec.action[a];
+        okReplayStoreAction(p, slot, a);
         p.ring.done[slot]   = crash ? 1.F : 0.F;
-        p.ring.reward[slot] = p.reward != nullptr ? p.reward[a] : ok_dqn_reward(crash, p.dist + a * p.R, p.R);
+        p.ring.reward[slot] = okReplayReward(p, crash, a);
     }
     slot_of[threadIdx.x] = slot;
     __syncthreads();

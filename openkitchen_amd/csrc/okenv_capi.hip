@@ -26,6 +26,7 @@
 #include "ok_batch.h"
 #include "ok_learn.h"
 #include "ok_dqn.h"
+#include "ok_ddpg.h"
 #include "ok_expert.h"
 
 namespace
@@ -504,6 +505,26 @@ struct okenv
     size_t                  dqn_part_bytes{0};
     std::vector<hipEvent_t> dqn_events;
     size_t                  dqn_timed{0};
+    // DDPG (okenv_ddpg_create, okenv_ddpg_replay_create): the four networks [actor | critic | actor target | critic target] and the four
+    // moments [actor m | actor v | critic m | critic v], each ddpg_cap floats; the ring's fields and counter, the push's scratch, the
+    // update's chunk partials (grown, never shrunk) and timing events.  Nothing here is shared with the actor, the learner or the
+    // Deep-Q ring above.
+    bool                    ddpg_ok{false}, ddpg_actor_set{false}, ddpg_critic_set{false};
+    okenv_ddpg_config       ddpg{};
+    size_t                  ddpg_cap{0};
+    float                  *d_ddpg_nets{nullptr}, *d_ddpg_moments{nullptr};
+    int64_t                 ddpg_t{0};
+    const uint32_t         *ddpg_draw_offset{nullptr};
+    bool                    ddpg_replay_ok{false};
+    uint32_t                ddpg_replay_flags{0};
+    int32_t                 ddpg_replay_capacity{0};
+    okenv_ddpg_ring         ddpg_ring{};
+    uint64_t               *d_ddpg_words{nullptr}; // [0] pushed, [1] its value before the latest push
+    uint32_t               *d_ddpg_counts{nullptr};
+    uint8_t                *d_ddpg_part{nullptr};
+    size_t                  ddpg_part_bytes{0};
+    std::vector<hipEvent_t> ddpg_events;
+    size_t                  ddpg_timed{0};
 };
 
 struct okenv_track
@@ -1386,6 +1407,8 @@ extern "C"
         for (hipEvent_t e : h->learn_events)
             (void)hipEventDestroy(e);
         for (hipEvent_t e : h->dqn_events)
+            (void)hipEventDestroy(e);
+        for (hipEvent_t e : h->ddpg_events)
             (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
             (void)hipStreamDestroy(h->stream);
@@ -2801,9 +2824,9 @@ extern "C"
         p.crashed  = h->st.crashed;
         p.reward   = reward;
         const unsigned blocks = static_cast<unsigned>((h->shape.N + kReplayThreads - 1) / kReplayThreads);
-        hipLaunchKernelGGL(okReplayCountKernel, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+        hipLaunchKernelGGL(okReplayCountKernel<OkReplayParams>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
         OK_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(okReplayScatterKernel, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+        hipLaunchKernelGGL(okReplayScatterKernel<OkReplayParams>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -3041,6 +3064,437 @@ extern "C"
         const okenv_replay_ring empty{};
         okDqnUpdateHost(*params, *config, num_rays, hidden, num_actions, *state, target, ring != nullptr ? *ring : empty, static_cast<uint32_t>(size), B,
                         iterations, resample != 0, draw_base, out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    // ---- DDPG: continuous actor, critic, replay ring and update (ok_ddpg.h) ---------------------------------------------------
+
+    int okenv_ddpg_create(okenv_t h, const okenv_ddpg_config *config)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_create: NULL handle");
+        if (const char *why = okDdpgCheckConfig(config, h->shape.R))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_ddpg_create: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        // room for the widest networks, so that a later create with other widths allocates nothing
+        // (a multiple of four floats, with room for the last 16-byte load: okActorStage reads whole float4s from each vector)
+        h->ddpg_cap = ((static_cast<size_t>(ok_actor_num_params(OK_ACTOR_MAX_RAYS, OK_ACTOR_MAX_HIDDEN, 2)) + 3U) & ~static_cast<size_t>(3U)) + 4U;
+        int rc      = devEnsure(h, &h->d_ddpg_nets, 4U * h->ddpg_cap);
+        if (rc != OKENV_OK || (rc = devEnsure(h, &h->d_ddpg_moments, 4U * h->ddpg_cap)) != OKENV_OK)
+            return rc;
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDdpgActKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDdpgCriticGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDdpgActorGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipMemsetAsync(h->d_ddpg_nets, 0, 4U * h->ddpg_cap * sizeof(float), h->stream));
+        OK_HIP(h, hipMemsetAsync(h->d_ddpg_moments, 0, 4U * h->ddpg_cap * sizeof(float), h->stream));
+        h->ddpg            = *config;
+        h->ddpg_t          = 0;
+        h->ddpg_actor_set  = false;
+        h->ddpg_critic_set = false;
+        h->ddpg_ok         = true;
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_num_params(okenv_t h, int32_t *actor, int32_t *critic)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->ddpg_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_num_params: call okenv_ddpg_create first");
+        if (actor)
+            *actor = ok_actor_num_params(h->shape.R, h->ddpg.hidden, 2);
+        if (critic)
+            *critic = ok_ddpg_critic_params(h->shape.R, h->ddpg.critic_hidden);
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_set_params(okenv_t h, const float *actor, const float *critic)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->ddpg_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_set_params: call okenv_ddpg_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        const float *const src[2]   = {actor, critic};
+        const size_t       bytes[2] = {sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->ddpg.hidden, 2)),
+                                       sizeof(float) * static_cast<size_t>(ok_ddpg_critic_params(h->shape.R, h->ddpg.critic_hidden))};
+        for (size_t k = 0; k < 2U; ++k)
+            if (src[k] != nullptr)
+            { // the online network, then its target from it (DDPGAgent.hpp:65-74)
+                float    *online = h->d_ddpg_nets + k * h->ddpg_cap;
+                const int rc     = copyAny(h, online, src[k], bytes[k]);
+                if (rc != OKENV_OK)
+                    return rc;
+                OK_HIP(h, hipMemcpyAsync(online + 2U * h->ddpg_cap, online, bytes[k], hipMemcpyDeviceToDevice, h->stream));
+                (k == 0U ? h->ddpg_actor_set : h->ddpg_critic_set) = true;
+            }
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_get_state(okenv_t h, okenv_ddpg_state *out)
+    {
+        OK_QUIESCE(h);
+        if (!h || !out)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_get_state: NULL argument");
+        if (!h->ddpg_ok || !h->ddpg_actor_set || !h->ddpg_critic_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_get_state: both networks need their parameters first (okenv_ddpg_create, okenv_ddpg_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t na = sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->ddpg.hidden, 2));
+        const size_t nc = sizeof(float) * static_cast<size_t>(ok_ddpg_critic_params(h->shape.R, h->ddpg.critic_hidden));
+        float *const       dst[8]   = {out->actor, out->critic, out->actor_target, out->critic_target, out->actor_m, out->actor_v, out->critic_m, out->critic_v};
+        const float *const base[8]  = {h->d_ddpg_nets, h->d_ddpg_nets, h->d_ddpg_nets, h->d_ddpg_nets, h->d_ddpg_moments, h->d_ddpg_moments, h->d_ddpg_moments, h->d_ddpg_moments};
+        const size_t       bytes[8] = {na, nc, na, nc, na, na, nc, nc};
+        for (size_t k = 0; k < 8U; ++k)
+            if (dst[k] != nullptr)
+            {
+                const int rc = copyAny(h, dst[k], base[k] + (k & 3U) * h->ddpg_cap, bytes[k]);
+                if (rc != OKENV_OK)
+                    return rc;
+            }
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        out->t = h->ddpg_t;
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_set_draw_offset(okenv_t h, const uint32_t *device_word)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->ddpg_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_set_draw_offset: call okenv_ddpg_create first");
+        h->ddpg_draw_offset = device_word;
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_act(okenv_t h, const okenv_ddpg_record *rec)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_act: NULL handle");
+        if (!h->ddpg_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_act: call okenv_ddpg_create first");
+        if (!h->ddpg_actor_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_act: call okenv_ddpg_set_params first (the actor needs its parameters)");
+        dropEpisode(h);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkDdpgActParams p{};
+        p.st          = h->st;
+        p.N           = h->shape.N;
+        p.R           = h->shape.R;
+        p.H           = h->ddpg.hidden;
+        p.actor       = h->d_ddpg_nets;
+        p.step_word   = (h->reset_flags & kAutoResetOn) != 0U ? h->d_step_count : nullptr; // (the step kernels advance it only then)
+        p.host_steps  = h->step_count;
+        p.draw_offset = h->ddpg_draw_offset;
+        for (int k = 0; k < 2; ++k)
+        {
+            p.scale[k] = h->ddpg.scale[k];
+            p.bias[k]  = h->ddpg.bias[k];
+            p.noise[k] = h->ddpg.noise[k];
+        }
+        p.seed       = h->ddpg.seed;
+        p.agent_base = h->ddpg.agent_base;
+        if (rec != nullptr)
+            p.rec = *rec;
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
+        hipLaunchKernelGGL(okDdpgActKernel, dim3(blocks), dim3(kActorThreads), okDdpgActLdsBytes(p.R, p.H), h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_replay_create(okenv_t h, int32_t capacity, uint32_t flags)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_create: NULL handle");
+        if (const char *why = okReplayCheckCreate(capacity, flags))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_ddpg_replay_create: ") + why);
+        if (h->shape.R > OK_DDPG_MAX_RAYS)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_create: the fan needs 1 .. 62 rays");
+        OK_HIP(h, hipSetDevice(h->device));
+        OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in an earlier ring
+        h->ddpg_replay_ok = false;
+        void *const old[5] = {h->ddpg_ring.state, h->ddpg_ring.next_state, h->ddpg_ring.action, h->ddpg_ring.reward, h->ddpg_ring.done};
+        for (void *q : old)
+            if (q != nullptr)
+            {
+                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), q), h->allocations.end());
+                (void)hipFree(q);
+            }
+        h->ddpg_ring = okenv_ddpg_ring{};
+        const size_t C = static_cast<size_t>(capacity), R = static_cast<size_t>(h->shape.R);
+        const size_t blocks = (static_cast<size_t>(h->shape.N) + kReplayThreads - 1U) / kReplayThreads;
+        int          rc = devAlloc(h, &h->ddpg_ring.state, C * R);
+        if (rc != OKENV_OK || (rc = devAlloc(h, &h->ddpg_ring.next_state, C * R)) != OKENV_OK || (rc = devAlloc(h, &h->ddpg_ring.action, 2U * C)) != OKENV_OK ||
+            (rc = devAlloc(h, &h->ddpg_ring.reward, C)) != OKENV_OK || (rc = devAlloc(h, &h->ddpg_ring.done, C)) != OKENV_OK ||
+            (rc = devEnsure(h, &h->d_ddpg_words, 2)) != OKENV_OK || (rc = devEnsure(h, &h->d_ddpg_counts, blocks)) != OKENV_OK)
+            return rc;
+        OK_HIP(h, hipMemsetAsync(h->d_ddpg_words, 0, 2U * sizeof(uint64_t), h->stream));
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        h->ddpg_replay_capacity = capacity;
+        h->ddpg_replay_flags    = flags;
+        h->ddpg_replay_ok       = true;
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_replay_reset(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->ddpg_replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_replay_reset: call okenv_ddpg_replay_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        OK_HIP(h, hipMemsetAsync(h->d_ddpg_words, 0, 2U * sizeof(uint64_t), h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_replay_push(okenv_t h, const okenv_ddpg_record *rec, const float *reward)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_push: NULL handle");
+        if (!h->ddpg_replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_replay_push: call okenv_ddpg_replay_create first");
+        if (!rec)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_push: the record is NULL");
+        if (!rec->state || !rec->action)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_push: the record needs state and action");
+        if (!rec->alive && (h->ddpg_replay_flags & OKENV_REPLAY_PUSH_ALL) == 0U)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_push: the record needs alive (or create the ring with OKENV_REPLAY_PUSH_ALL)");
+        OK_HIP(h, hipSetDevice(h->device));
+        OkDdpgReplayParams p{};
+        p.N        = h->shape.N;
+        p.R        = h->shape.R;
+        p.flags    = h->ddpg_replay_flags;
+        p.capacity = static_cast<uint64_t>(h->ddpg_replay_capacity);
+        p.ring     = h->ddpg_ring;
+        p.pushed   = h->d_ddpg_words;
+        p.snapshot = h->d_ddpg_words + 1;
+        p.counts   = h->d_ddpg_counts;
+        p.rec      = *rec;
+        p.dist     = h->st.dist;
+        p.crashed  = h->st.crashed;
+        p.reward   = reward;
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + kReplayThreads - 1) / kReplayThreads);
+        hipLaunchKernelGGL(okReplayCountKernel<OkDdpgReplayParams>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        hipLaunchKernelGGL(okReplayScatterKernel<OkDdpgReplayParams>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_replay_size(okenv_t h, int64_t *size, int64_t *pushed)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->ddpg_replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_replay_size: call okenv_ddpg_replay_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        uint64_t word = 0;
+        OK_HIP(h, hipMemcpyAsync(&word, h->d_ddpg_words, sizeof(word), hipMemcpyDeviceToHost, h->stream));
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        if (size)
+            *size = static_cast<int64_t>(ok_dqn_size(word, static_cast<uint64_t>(h->ddpg_replay_capacity)));
+        if (pushed)
+            *pushed = static_cast<int64_t>(word);
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_replay_get(okenv_t h, const okenv_ddpg_ring *out)
+    {
+        OK_QUIESCE(h);
+        if (!h || !out)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_get: NULL argument");
+        if (!h->ddpg_replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_replay_get: call okenv_ddpg_replay_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t C = static_cast<size_t>(h->ddpg_replay_capacity), R = static_cast<size_t>(h->shape.R);
+        void *const       dst[5]   = {out->state, out->next_state, out->action, out->reward, out->done};
+        const void *const src[5]   = {h->ddpg_ring.state, h->ddpg_ring.next_state, h->ddpg_ring.action, h->ddpg_ring.reward, h->ddpg_ring.done};
+        const size_t      bytes[5] = {C * R * sizeof(float), C * R * sizeof(float), 2U * C * sizeof(float), C * sizeof(float), C * sizeof(float)};
+        for (int k = 0; k < 5; ++k)
+            if (dst[k] != nullptr)
+            {
+                const int rc = copyAny(h, dst[k], src[k], bytes[k]);
+                if (rc != OKENV_OK)
+                    return rc;
+            }
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_update(okenv_t h, int32_t B, int32_t iterations, int32_t resample, uint32_t draw_base, const okenv_ddpg_output *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_update: NULL handle");
+        if (!h->ddpg_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_update: call okenv_ddpg_create first");
+        if (!h->ddpg_actor_set || !h->ddpg_critic_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_update: both networks need their parameters first (okenv_ddpg_set_params)");
+        if (!h->ddpg_replay_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_update: call okenv_ddpg_replay_create first");
+        if (B < 1 || iterations < 1)
+            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_update: B and iterations must be at least 1");
+        OK_HIP(h, hipSetDevice(h->device));
+        OkDdpgParams p{};
+        p.R        = h->shape.R;
+        p.H        = h->ddpg.hidden;
+        p.Hc       = h->ddpg.critic_hidden;
+        p.B        = B;
+        p.C        = (B + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+        p.Pa       = ok_actor_num_params(p.R, p.H, 2);
+        p.Pc       = ok_ddpg_critic_params(p.R, p.Hc);
+        p.capacity = static_cast<uint64_t>(h->ddpg_replay_capacity);
+        p.pushed   = h->d_ddpg_words;
+        p.ring     = h->ddpg_ring;
+        p.actor    = h->d_ddpg_nets;
+        p.critic   = h->d_ddpg_nets + h->ddpg_cap;
+        p.actor_t  = h->d_ddpg_nets + 2U * h->ddpg_cap;
+        p.critic_t = h->d_ddpg_nets + 3U * h->ddpg_cap;
+        p.act_m    = h->d_ddpg_moments;
+        p.act_v    = h->d_ddpg_moments + h->ddpg_cap;
+        p.cri_m    = h->d_ddpg_moments + 2U * h->ddpg_cap;
+        p.cri_v    = h->d_ddpg_moments + 3U * h->ddpg_cap;
+        for (int k = 0; k < 2; ++k)
+        {
+            p.scale[k] = h->ddpg.scale[k];
+            p.bias[k]  = h->ddpg.bias[k];
+        }
+        p.gamma = h->ddpg.gamma;
+        p.tau   = h->ddpg.tau;
+        p.omt   = 1.F - h->ddpg.tau;
+        p.seed  = h->ddpg.sample_seed;
+        const okenv_ddpg_output none{};
+        const okenv_ddpg_output &o = out != nullptr ? *out : none;
+        p.grad_critic = o.grad_critic;
+        p.grad_actor  = o.grad_actor;
+        p.index       = o.index;
+        const size_t bytes = sizeof(float) * static_cast<size_t>(p.C) * (static_cast<size_t>(std::max(p.Pa, p.Pc)) + 1U);
+        if (bytes > h->ddpg_part_bytes)
+        {
+            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in the old one
+            if (h->d_ddpg_part != nullptr)
+            {
+                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_ddpg_part)), h->allocations.end());
+                (void)hipFree(h->d_ddpg_part);
+                h->d_ddpg_part     = nullptr;
+                h->ddpg_part_bytes = 0;
+            }
+            uint8_t  *fresh = nullptr;
+            const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
+            if (rc != OKENV_OK)
+                return rc;
+            h->d_ddpg_part     = fresh;
+            h->ddpg_part_bytes = bytes + bytes / 2U;
+        }
+        p.part = reinterpret_cast<float *>(h->d_ddpg_part);
+        const size_t launches = 4U * static_cast<size_t>(iterations);
+        h->ddpg_timed = 0;
+        if (h->timing)
+        {
+            while (h->ddpg_events.size() < launches + 1U)
+            {
+                hipEvent_t e = nullptr;
+                OK_HIP(h, hipEventCreate(&e));
+                h->ddpg_events.push_back(e);
+            }
+            OK_HIP(h, hipEventRecord(h->ddpg_events[0], h->stream));
+        }
+        const size_t   lds = okDdpgLdsBytes(p.R, p.H, p.Hc);
+        const unsigned chunks = static_cast<unsigned>(p.C), step_threads = kLearnStepCols * kLearnStepRows;
+        const unsigned cols_c = static_cast<unsigned>((p.Pc + 1 + kLearnStepCols - 1) / kLearnStepCols), cols_a = static_cast<unsigned>((p.Pa + 1 + kLearnStepCols - 1) / kLearnStepCols);
+        size_t         ev  = 0;
+        const auto     mark = [&]() { return h->timing ? hipEventRecord(h->ddpg_events[++ev], h->stream) : hipSuccess; };
+        for (int it = 0; it < iterations; ++it)
+        {
+            p.draw        = draw_base + (resample != 0 ? static_cast<uint32_t>(it) : 0U);
+            p.adam_actor  = okDdpgAdamConsts(h->ddpg, h->ddpg.lr_actor, h->ddpg_t + 1);
+            p.adam_critic = okDdpgAdamConsts(h->ddpg, h->ddpg.lr_critic, h->ddpg_t + 1);
+            p.critic_loss = o.critic_loss != nullptr ? o.critic_loss + it : nullptr;
+            p.actor_loss  = o.actor_loss != nullptr ? o.actor_loss + it : nullptr;
+            // (the step number advances once all four kernels of the iteration are enqueued, as in okenv_ppo_update)
+            hipLaunchKernelGGL(okDdpgCriticGradKernel, dim3(chunks), dim3(kLearnThreads), lds, h->stream, p);
+            OK_HIP(h, hipGetLastError());
+            OK_HIP(h, mark());
+            hipLaunchKernelGGL(okDdpgStepKernel<false>, dim3(cols_c), dim3(step_threads), 0, h->stream, p);
+            OK_HIP(h, hipGetLastError());
+            OK_HIP(h, mark());
+            hipLaunchKernelGGL(okDdpgActorGradKernel, dim3(chunks), dim3(kLearnThreads), lds, h->stream, p);
+            OK_HIP(h, hipGetLastError());
+            OK_HIP(h, mark());
+            hipLaunchKernelGGL(okDdpgStepKernel<true>, dim3(cols_a), dim3(step_threads), 0, h->stream, p);
+            OK_HIP(h, hipGetLastError());
+            OK_HIP(h, mark());
+            h->ddpg_t += 1;
+        }
+        h->ddpg_timed = h->timing ? launches + 1U : 0U;
+        return OKENV_OK;
+    }
+
+    int okenv_debug_ddpg_timing(okenv_t h, double *ms4)
+    {
+        OK_QUIESCE(h);
+        if (!h || !ms4)
+            return fail(h, OKENV_ERR_INVALID, "okenv_debug_ddpg_timing: NULL argument");
+        if (h->ddpg_timed < 5U)
+            return fail(h, OKENV_ERR_STATE, "okenv_debug_ddpg_timing: no okenv_ddpg_update has run with okenv_set_timing on");
+        OK_HIP(h, hipEventSynchronize(h->ddpg_events[h->ddpg_timed - 1U]));
+        ms4[0] = ms4[1] = ms4[2] = ms4[3] = 0.0;
+        for (size_t k = 0; k + 1U < h->ddpg_timed; ++k)
+        {
+            float ms = 0.F;
+            OK_HIP(h, hipEventElapsedTime(&ms, h->ddpg_events[k], h->ddpg_events[k + 1U]));
+            ms4[k & 3U] += ms;
+        }
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_act_host(const okenv_ddpg_config *config, const float *actor, int32_t num_rays, int32_t n, const float *dist, const uint8_t *crashed,
+                            uint32_t draw_index, float *throttle, float *steer, float *action, float *state, uint8_t *alive)
+    {
+        if (const char *why = okDdpgCheckConfig(config, num_rays))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_ddpg_act_host: ") + why);
+        if (!actor || n < 0 || !dist)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_act_host: bad argument");
+        okDdpgActHost(*config, actor, num_rays, n, dist, crashed, draw_index, throttle, steer, action, state, alive);
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_replay_push_host(const okenv_ddpg_ring *ring, int32_t capacity, int32_t num_rays, uint64_t *pushed, uint32_t flags, int32_t n,
+                                    const float *state, const float *action, const uint8_t *alive, const float *dist, const uint8_t *crashed,
+                                    const float *reward)
+    {
+        if (const char *why = okReplayCheckCreate(capacity, flags))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_ddpg_replay_push_host: ") + why);
+        if (!okDdpgRingComplete(ring) || !pushed)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_replay_push_host: the ring needs every field and its counter");
+        if (num_rays < 1 || num_rays > OK_DDPG_MAX_RAYS || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_replay_push_host: the fan needs 1 .. 62 rays and n >= 0");
+        if (!state || !action)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_replay_push_host: the record needs state and action");
+        if (!alive && (flags & OKENV_REPLAY_PUSH_ALL) == 0U)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_replay_push_host: the record needs alive (or pass OKENV_REPLAY_PUSH_ALL)");
+        if (!dist || !crashed)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_replay_push_host: dist and crashed are required");
+        okDdpgPushHost(*ring, static_cast<uint64_t>(capacity), num_rays, pushed, flags, n, state, action, alive, dist, crashed, reward);
+        return OKENV_OK;
+    }
+
+    int okenv_ddpg_update_host(const okenv_ddpg_config *config, int32_t num_rays, okenv_ddpg_state *state, const okenv_ddpg_ring *ring, int64_t size, int32_t B,
+                               int32_t iterations, int32_t resample, uint32_t draw_base, const okenv_ddpg_output *out)
+    {
+        if (const char *why = okDdpgCheckConfig(config, num_rays))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_ddpg_update_host: ") + why);
+        if (B < 1 || iterations < 1)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_update_host: B and iterations must be at least 1");
+        if (state == nullptr || state->actor == nullptr || state->critic == nullptr || state->actor_target == nullptr || state->critic_target == nullptr ||
+            state->actor_m == nullptr || state->actor_v == nullptr || state->critic_m == nullptr || state->critic_v == nullptr || state->t < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_update_host: state lacks a parameter or moment vector, or t < 0");
+        if (size < 0 || size >= (INT64_C(1) << 31) || (size > 0 && !okDdpgRingComplete(ring)))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_update_host: size outside 0 .. 2^31 - 1, or a ring without every field");
+        const okenv_ddpg_output none{};
+        const okenv_ddpg_ring   empty{};
+        okDdpgUpdateHost(*config, num_rays, *state, ring != nullptr ? *ring : empty, static_cast<uint32_t>(size), B, iterations, resample != 0, draw_base,
+                         out != nullptr ? *out : none);
         return OKENV_OK;
     }
 

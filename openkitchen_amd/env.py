@@ -648,6 +648,110 @@ class BatchedEnvironment:
         capi.check(self._L.okenv_debug_dqn_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
         return {k: 1000.0 * v for k, v in zip(capi.UPDATE_KERNELS, ms)}
 
+    # ---- DDPG (include/okenv.h) ----------------------------------------------------------------------
+    def ddpg_create(self, hidden, critic_hidden, **config):
+        """Attaches a DDPG object (actor R -> hidden -> 2 ending in tanh * scale + bias, critic (R + 2) -> critic_hidden -> 1, their
+        target networks and Adam state) to the handle; config: the members of okenv_ddpg_config (capi.ddpg_config lists them with the
+        reference's defaults).  Returns (actor floats, critic floats)."""
+        cfg = capi.ddpg_config(hidden, critic_hidden, **config)
+        capi.check(self._L.okenv_ddpg_create(self._h, C.byref(cfg)), self._h)
+        self.ddpg_config = cfg
+        return self.ddpg_num_params()
+
+    def ddpg_num_params(self):
+        a, b = C.c_int32(), C.c_int32()
+        capi.check(self._L.okenv_ddpg_num_params(self._h, C.byref(a), C.byref(b)), self._h)
+        return a.value, b.value
+
+    def ddpg_set_params(self, actor=None, critic=None):
+        """New online parameters (torch's parameters() order, flattened) from float32 numpy arrays or device tensors; each network
+        that arrives also replaces its target network.  None leaves a network as it is."""
+        keep = []
+        for v, n in zip((actor, critic), self.ddpg_num_params()):
+            if v is None:
+                keep.append(None)
+                continue
+            if isinstance(v, np.ndarray):
+                v = np.ascontiguousarray(v, dtype=np.float32).ravel()
+                assert v.size == n, "expected %d parameters, got %d" % (n, v.size)
+            else:
+                assert v.is_contiguous() and v.numel() == n and v.element_size() == 4, "expected %d float32 parameters" % n
+            keep.append(v)
+        capi.check(self._L.okenv_ddpg_set_params(self._h, capi.ptr(keep[0]), capi.ptr(keep[1])), self._h)
+        if any(isinstance(v, np.ndarray) for v in keep):
+            self.sync()  # the host arrays are temporaries
+
+    def ddpg_state(self, out=None):
+        """The four parameter vectors, the four Adam moments (capi.DDPG_STATE_VECTORS) and the int t: float32 numpy arrays, or copied
+        into the device tensors of the dict `out` (any subset).  Synchronises."""
+        na, nc = self.ddpg_num_params()
+        if out is None:
+            out = {k: np.empty(nc if "critic" in k else na, dtype=np.float32) for k in capi.DDPG_STATE_VECTORS}
+        st = capi.fill_pointers(capi.OkenvDdpgState(), out, "ddpg state")
+        capi.check(self._L.okenv_ddpg_get_state(self._h, C.byref(st)), self._h)
+        return dict(out, t=int(st.t))
+
+    def ddpg_set_draw_offset(self, word=None):
+        """A device uint32 word (tensor or address) added to the draw index of every later ddpg_act; None removes it."""
+        capi.check(self._L.okenv_ddpg_set_draw_offset(self._h, capi.ptr(word)), self._h)
+
+    def ddpg_act(self, record=None):
+        """The continuous action of every agent, enqueued on the handle's stream without a synchronisation.  record: None, or a dict
+        of device tensors / addresses under "state" [N,R] float32, "action" [N,2] float32 and "alive" [N] uint8, each optional."""
+        if record is None:
+            capi.check(self._L.okenv_ddpg_act(self._h, None), self._h)
+            return
+        sizes = {"state": self.N * self.R * 4, "action": self.N * 8, "alive": self.N}
+        for k, v in record.items():
+            if k not in sizes:
+                raise KeyError("unknown record slot %r" % k)
+            if v is not None and hasattr(v, "data_ptr"):
+                assert v.is_contiguous() and v.numel() * v.element_size() >= sizes[k], "record slot %r is too small" % k
+        rec = capi.fill_pointers(capi.OkenvDdpgRecord(), record, "ddpg record")
+        capi.check(self._L.okenv_ddpg_act(self._h, C.byref(rec)), self._h)
+
+    def ddpg_replay_create(self, capacity, push_all=False):
+        """Attaches DDPG's replay ring of `capacity` transitions (action [C,2] float32); replay_create's contract."""
+        capi.check(self._L.okenv_ddpg_replay_create(self._h, int(capacity), capi.REPLAY_PUSH_ALL if push_all else 0), self._h)
+        self.ddpg_replay_capacity = int(capacity)
+
+    def ddpg_replay_reset(self):
+        capi.check(self._L.okenv_ddpg_replay_reset(self._h), self._h)
+
+    def ddpg_replay_push(self, record, reward=None):
+        """Appends the transitions of the step that has just run: `record` is the dict the preceding ddpg_act was given; reward:
+        None (1.0 per transition) or a device float32 tensor [N].  Two kernels on the handle's stream, no synchronisation."""
+        rec = capi.fill_pointers(capi.OkenvDdpgRecord(), {k: v for k, v in record.items() if k in ("state", "action", "alive")}, "ddpg record")
+        capi.check(self._L.okenv_ddpg_replay_push(self._h, C.byref(rec), capi.ptr(reward)), self._h)
+
+    def ddpg_replay_size(self):
+        """(transitions in the ring, transitions ever pushed); waits for the stream."""
+        size, pushed = C.c_int64(), C.c_int64()
+        capi.check(self._L.okenv_ddpg_replay_size(self._h, C.byref(size), C.byref(pushed)), self._h)
+        return size.value, pushed.value
+
+    def ddpg_replay_get(self, out=None):
+        """The ring's fields, all `capacity` slots: numpy arrays, or copied into the device tensors of the dict `out`.  Synchronises."""
+        if out is None:
+            out = {k: v for k, v in ddpg_ring(self.ddpg_replay_capacity, self.R).items() if k != "pushed"}
+        ring = capi.fill_pointers(capi.OkenvDdpgRing(), out, "ddpg ring")
+        capi.check(self._L.okenv_ddpg_replay_get(self._h, C.byref(ring)), self._h)
+        return out
+
+    def ddpg_update(self, B, iterations, resample=False, draw_base=0, out=None):
+        """okenv_ddpg_update: `iterations` iterations on batches of B uniform samples of the ring, four kernels each on the handle's
+        stream, no synchronisation.  out: None or a dict of device tensors under "critic_loss", "actor_loss" [iterations] float32,
+        "grad_critic", "grad_actor", "index" [B] int32."""
+        po = capi.fill_pointers(capi.OkenvDdpgOutput(), out or {}, "ddpg output")
+        capi.check(self._L.okenv_ddpg_update(self._h, int(B), int(iterations), 1 if resample else 0, int(draw_base) & 0xFFFFFFFF, C.byref(po)), self._h)
+
+    def ddpg_timing(self):
+        """Device microseconds of the latest ddpg_update that ran with set_timing(True), summed over its iterations, by
+        capi.DDPG_KERNELS."""
+        ms = (C.c_double * 4)()
+        capi.check(self._L.okenv_debug_ddpg_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
+        return {k: 1000.0 * v for k, v in zip(capi.DDPG_KERNELS, ms)}
+
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):
         """{rays, tests, cells, points} the broad phase leaves for the current poses (okenv_work_stats)."""
@@ -875,6 +979,74 @@ def dqn_update_host(params, config, shape, state, ring, B, iterations=1, resampl
                                                  R, H, A, C.byref(st), capi.ptr(target), C.byref(_ring_struct(ring)), size, int(B), int(iterations),
                                                  1 if resample else 0, int(draw_base) & 0xFFFFFFFF,
                                                  C.byref(capi.fill_pointers(capi.OkenvDqnOutput(), {k: v for k, v in outs.items() if v.size}, "dqn output"))))
+    new["t"] = int(st.t)
+    return new, outs
+
+
+def ddpg_act_host(config, actor, dist, crashed=None, draw_index=0):
+    """DDPG's action on host arrays, no GPU needed (okenv_ddpg_act_host).  config: capi.ddpg_config(...); actor: the flattened float32
+    parameters; dist [n, R].  Returns a dict: throttle, steer [n], action [n, 2], state [n, R] float32 and alive [n] uint8."""
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    n, R = dist.shape
+    actor = None if actor is None else np.ascontiguousarray(actor, dtype=np.float32).ravel()
+    if config is not None and actor is not None:
+        assert actor.size == config.hidden * R + config.hidden + 2 * config.hidden + 2
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, dtype=np.uint8)
+    out = {"throttle": np.zeros(n, np.float32), "steer": np.zeros(n, np.float32), "action": np.zeros((n, 2), np.float32),
+           "state": np.zeros((n, R), np.float32), "alive": np.zeros(n, np.uint8)}
+    capi.check(capi.load().okenv_ddpg_act_host(C.byref(config) if config is not None else None, capi.ptr(actor), R, n, capi.ptr(dist), capi.ptr(crashed),
+                                               int(draw_index) & 0xFFFFFFFF, capi.ptr(out["throttle"]), capi.ptr(out["steer"]), capi.ptr(out["action"]),
+                                               capi.ptr(out["state"]), capi.ptr(out["alive"])))
+    return out
+
+
+def ddpg_ring(capacity, num_rays):
+    """An empty DDPG replay ring on the host: dict of zeroed numpy arrays (action [C, 2] float32) and "pushed" = 0."""
+    return {"state": np.zeros((capacity, num_rays), np.float32), "next_state": np.zeros((capacity, num_rays), np.float32),
+            "action": np.zeros((capacity, 2), np.float32), "reward": np.zeros(capacity, np.float32), "done": np.zeros(capacity, np.float32), "pushed": 0}
+
+
+def _ddpg_ring_struct(ring):
+    return capi.fill_pointers(capi.OkenvDdpgRing(), {k: v for k, v in ring.items() if k != "pushed"}, "ddpg ring")
+
+
+def ddpg_replay_push_host(ring, state, action, alive, dist, crashed, reward=None, push_all=False):
+    """One push on host arrays, no GPU needed (okenv_ddpg_replay_push_host): `ring` (ddpg_ring(...)) is updated in place, "pushed"
+    included.  state [n,R], action [n,2] and alive [n] are the record, dist [n,R] and crashed [n] the fields after the step."""
+    Cn, R = ring["state"].shape
+    state = np.ascontiguousarray(state, dtype=np.float32)
+    action = np.ascontiguousarray(action, dtype=np.float32)
+    alive = None if alive is None else np.ascontiguousarray(alive).astype(np.uint8)
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    crashed = np.ascontiguousarray(crashed).astype(np.uint8)
+    reward = None if reward is None else np.ascontiguousarray(reward, dtype=np.float32)
+    n = action.shape[0]
+    assert state.shape == (n, R) and action.shape == (n, 2) and dist.shape == (n, R) and crashed.shape == (n,)
+    pushed = C.c_uint64(int(ring["pushed"]))
+    capi.check(capi.load().okenv_ddpg_replay_push_host(C.byref(_ddpg_ring_struct(ring)), Cn, R, C.byref(pushed), capi.REPLAY_PUSH_ALL if push_all else 0, n,
+                                                       capi.ptr(state), capi.ptr(action), capi.ptr(alive), capi.ptr(dist), capi.ptr(crashed), capi.ptr(reward)))
+    ring["pushed"] = int(pushed.value)
+    return ring
+
+
+def ddpg_update_host(config, num_rays, state, ring, B, iterations=1, resample=False, draw_base=0, size=None,
+                     want=("critic_loss", "actor_loss", "grad_critic", "grad_actor", "index")):
+    """DDPG's update on host arrays, no GPU needed (okenv_ddpg_update_host).  config: capi.ddpg_config(...); state: dict of the float32
+    arrays capi.DDPG_STATE_VECTORS and the int "t" -- copied, the new state is returned; ring: ddpg_ring(...) as the pushes left it.
+    Returns (new state, outputs): outputs holds the arrays named in `want`."""
+    R = int(num_rays)
+    new = {k: np.array(state[k], dtype=np.float32, copy=True).ravel() for k in capi.DDPG_STATE_VECTORS if state.get(k) is not None}
+    st = capi.fill_pointers(capi.OkenvDdpgState(), new, "ddpg state")
+    st.t = int(state.get("t", 0))
+    size = min(int(ring["pushed"]), ring["state"].shape[0]) if size is None else int(size)
+    H, Hc = (config.hidden, config.critic_hidden) if config is not None else (0, 0)
+    sizes = {"critic_loss": (max(int(iterations), 0), np.float32), "actor_loss": (max(int(iterations), 0), np.float32),
+             "grad_critic": (max(Hc * (R + 2) + 2 * Hc + 1, 0), np.float32), "grad_actor": (max(H * R + 3 * H + 2, 0), np.float32),
+             "index": (max(int(B), 0), np.int32)}
+    outs = {k: np.zeros(sizes[k][0], dtype=sizes[k][1]) for k in want}
+    capi.check(capi.load().okenv_ddpg_update_host(C.byref(config) if config is not None else None, R, C.byref(st), C.byref(_ddpg_ring_struct(ring)), size,
+                                                  int(B), int(iterations), 1 if resample else 0, int(draw_base) & 0xFFFFFFFF,
+                                                  C.byref(capi.fill_pointers(capi.OkenvDdpgOutput(), {k: v for k, v in outs.items() if v.size}, "ddpg output"))))
     new["t"] = int(st.t)
     return new, outs
 

@@ -408,6 +408,117 @@ def dqn_update(venv, batch=100, iterations=200, resample=False, draw=None, grads
     return out if grads else out["loss"]
 
 
+def _ddpg_record(venv):
+    return {"state": torch.empty((venv.num_envs, venv.num_rays), dtype=torch.float32, device=venv.device),
+            "action": torch.empty((venv.num_envs, 2), dtype=torch.float32, device=venv.device),
+            "alive": torch.empty(venv.num_envs, dtype=torch.uint8, device=venv.device)}
+
+
+def collect_episode_ddpg(venv, max_steps=None, check_every=8, graph_chunk=0, reward=None):
+    """One episode of ddpg_sim.cpp:55-95 on the device: reset, then `ddpg_act -> step -> ddpg_replay_push` until every agent has
+    crashed (tested every `check_every` steps) or `max_steps` steps have run.  The transitions go straight into the ring of
+    venv.enable_ddpg_replay.  reward: None for the reference's +1 per step, "tracker" for the environment's own `reward` tensor, or a
+    device tensor [N] that the caller keeps up to date.
+
+    graph_chunk = K > 0: K iterations are captured once into a HIP graph (kept on `venv` until the ring is re-created) and replayed;
+    the test runs once per chunk.  Without auto-reset the graph's last node advances the word the actor adds to its draw index, so
+    replays keep drawing fresh exploration noise; eager and chunked episodes fill the ring with the same bits.
+
+    Returns {"steps": steps taken}; a multiple of K with a graph."""
+    assert getattr(venv, "_ddpg_nets", None) is not None, "call venv.enable_ddpg(actor, critic) first"
+    assert getattr(venv, "ddpg_push_all", None) is not None, "call venv.enable_ddpg_replay(capacity) first"
+    assert not venv.auto_reset or max_steps is not None, "with auto-reset on the episode never ends: pass max_steps"
+    if isinstance(reward, str):
+        assert reward == "tracker" and venv.reward_kind is not None, 'reward="tracker" needs a VectorEnvironment with a reward'
+        reward = venv.reward
+    K = int(graph_chunk)
+    venv.reset()
+    steps = 0
+    start = venv.env.step_count
+    if K <= 0:
+        rec = getattr(venv, "_ddpg_rec", None) or _ddpg_record(venv)
+        venv._ddpg_rec = rec
+        while True:
+            venv.ddpg_act(rec)
+            venv.step()
+            venv.ddpg_replay_push(rec, reward)
+            steps += 1
+            if steps % check_every == 0 and venv.env.alive_count() == 0:
+                break
+            if max_steps is not None and steps >= max_steps:
+                break
+        return {"steps": steps}
+    graph, offset, base = _ddpg_chunk_graph(venv, K, reward)
+    if offset is not None:  # the captured launches carry base + k as their draw index
+        offset.fill_(((start - base + 2 ** 31) % 2 ** 32) - 2 ** 31)
+    try:
+        while True:
+            graph.replay()
+            steps += K
+            if venv.env.alive_count() == 0:
+                break
+            if max_steps is not None and steps >= max_steps:
+                break
+    finally:
+        if offset is not None:
+            venv.env.step_count = start + steps  # (replays do not advance the host's count)
+    return {"steps": steps}
+
+
+def _ddpg_chunk_graph(venv, K, reward):
+    """The captured chunk of K iterations of collect_episode_ddpg: (graph, draw-offset word or None, the host step count the launches
+    were captured with); see _dqn_chunk_graph."""
+    key = (K, None if reward is None else reward.data_ptr())
+    if key in venv._ddpg_graphs:
+        return venv._ddpg_graphs[key][:3]
+    rec = _ddpg_record(venv)
+    offset = None if venv.auto_reset else torch.zeros(1, dtype=torch.int32, device=venv.device)
+
+    def body():
+        for _ in range(K):
+            venv.ddpg_act(rec)
+            venv.step()
+            venv.ddpg_replay_push(rec, reward)
+        if offset is not None:
+            offset.add_(K)
+
+    base = venv.env.step_count
+    if offset is not None:
+        offset.add_(0)  # torch's own kernel is loaded before the capture; ours are already
+    venv.env.ddpg_set_draw_offset(offset)  # the captured launches keep the pointer; eager calls afterwards get none
+    try:
+        graph = venv.capture(body, warmup=0)  # no warm-up iterations: they would push into the ring and move the count
+    finally:
+        venv.env.ddpg_set_draw_offset(None)
+    venv._ddpg_graphs[key] = (graph, offset, base, rec, reward)  # (the record and the reward are the graph's: kept alive with it)
+    return graph, offset, base
+
+
+def ddpg_update(venv, batch=250, iterations=50, resample=True, draw=None, grads=False):
+    """DDPGAgent::update on the device (okenv_ddpg_update, DESIGN.md section 18): `iterations` iterations of the critic's step, the
+    actor's step through the stepped critic and both soft updates on `batch` uniform samples of the ring, in place in the parameters
+    the device actor acts with (venv.enable_ddpg and venv.enable_ddpg_replay first; venv.pull_ddpg() brings them back to the
+    modules).  resample=True draws a fresh batch per iteration, as the reference does (one sample() per update() call).  draw: the
+    number of the first draw; by default a count kept on `venv`.
+
+    Everything is enqueued on the environment's stream and nothing is read back.  Returns (critic_loss, actor_loss), device tensors
+    [iterations]; with grads=True a dict that also holds "grad_critic", "grad_actor" and "index"."""
+    used = int(iterations) if resample else 1
+    if draw is None:
+        draw = venv._ddpg_draw
+        venv._ddpg_draw = (draw + used) % 2 ** 32
+    out = {"critic_loss": torch.empty(int(iterations), dtype=torch.float32, device=venv.device),
+           "actor_loss": torch.empty(int(iterations), dtype=torch.float32, device=venv.device)}
+    if grads:
+        na, nc = venv.env.ddpg_num_params()
+        out["grad_actor"] = torch.empty(na, dtype=torch.float32, device=venv.device)
+        out["grad_critic"] = torch.empty(nc, dtype=torch.float32, device=venv.device)
+        out["index"] = torch.empty(int(batch), dtype=torch.int32, device=venv.device)
+    venv.env.ddpg_update(batch, iterations, resample, draw, out)
+    venv._update_inputs = out  # alive until the next update: the kernels are only enqueued
+    return out if grads else (out["critic_loss"], out["actor_loss"])
+
+
 def batch_stats(batch):
     """The statistics of a prepare_batch result as a dict (one small copy to the host): sum_ret, sumsq_ret, sum_adv, sumsq_adv (fp64, in
     the rule's order), mean_ret, std_ret, mean_adv, std_adv, count."""

@@ -319,6 +319,60 @@ class VectorEnvironment:
         """Copies the online Q network into the target network (device to device, no synchronisation)."""
         self.env.dqn_sync_target()
 
+    # ---- DDPG (include/okenv.h, DESIGN.md section 18) ---------------------------------------------------------------------------
+    def enable_ddpg(self, actor, critic, **config):
+        """Attaches the reference's DDPG agent (RLRacers/DDPG) with one hidden layer per network: `actor` is
+        torch.nn.Sequential(Linear(R, H), ReLU, Linear(H, 2)) -- the device applies tanh * scale + bias to its output -- and `critic`
+        Sequential(Linear(R + 2, Hc), ReLU, Linear(Hc, 1)) on torch.cat([state, action], 1), or their four parameter tensors each.
+        config: the members of okenv_ddpg_config but the widths (capi.ddpg_config: scale, bias, noise, gamma, tau, lr_actor, lr_critic,
+        beta1, beta2, eps, sample_seed).  The online and the target networks on the device start from the modules' parameters;
+        rollout.ddpg_update steps them in place, and pull_ddpg() copies the online ones back into the modules."""
+        nets = (self._network_tensors(actor, "actor"), self._network_tensors(critic, "critic"))
+        widths = []
+        for t, what, n_in, n_out in ((nets[0], "actor", self.num_rays, 2), (nets[1], "critic", self.num_rays + 2, 1)):
+            hidden = t[0].shape[0] if t[0].dim() == 2 else -1
+            if [tuple(x.shape) for x in t] != [(hidden, n_in), (hidden,), (n_out, hidden), (n_out,)]:
+                raise ValueError("%s: shapes %s do not form a %d -> H -> %d network" % (what, [tuple(x.shape) for x in t], n_in, n_out))
+            widths.append(hidden)
+        config.setdefault("seed", self.seed)
+        config.setdefault("agent_base", self.agent_base)
+        config.setdefault("sample_seed", self.seed)
+        self.env.ddpg_create(widths[0], widths[1], **config)
+        self._ddpg_nets = nets
+        self._ddpg_graphs = {}
+        flat = [torch.cat([x.detach().reshape(-1) for x in t]).to(device=self.device, dtype=torch.float32).contiguous() for t in nets]
+        self.env.ddpg_set_params(flat[0], flat[1])
+        self._ddpg_flat = flat  # alive until the next hand-over: the copy is asynchronous
+
+    def pull_ddpg(self):
+        """Copies the device's online actor and critic back into the modules (or tensors) given to enable_ddpg."""
+        flat = {k: torch.empty(n, dtype=torch.float32, device=self.device) for k, n in zip(("actor", "critic"), self.env.ddpg_num_params())}
+        self.env.ddpg_state(out=flat)
+        with torch.no_grad():
+            for tensors, vec in zip(self._ddpg_nets, (flat["actor"], flat["critic"])):
+                at = 0
+                for x in tensors:
+                    x.copy_(vec[at:at + x.numel()].reshape(x.shape))
+                    at += x.numel()
+
+    def ddpg_act(self, record=None):
+        """The continuous action of every agent from the last observation, written into `throttle` / `steering`: one kernel on the
+        environment's stream, no synchronisation, usable inside capture(body).  record: optional dict of device tensors ("state"
+        [N,R] float32, "action" [N,2] float32, "alive" [N] uint8) that receive the sample."""
+        self.env.ddpg_act(record)
+
+    def enable_ddpg_replay(self, capacity, push_all=False):
+        """Attaches DDPG's replay ring of `capacity` transitions that persists across episodes on the device."""
+        self.env.ddpg_replay_create(capacity, push_all)
+        self.ddpg_push_all = bool(push_all)
+        self._ddpg_draw = 0
+        self._ddpg_graphs = {}  # a captured push carries the old ring's pointers, capacity and flags
+
+    def ddpg_replay_push(self, record, reward=None):
+        """Appends the transitions of the step that has just run to DDPG's ring: `record` is the dict the preceding ddpg_act filled;
+        reward: None for the reference's +1 per step, or a device float32 tensor [N].  Usable inside capture(body)."""
+        self.env.ddpg_replay_push(record, reward)
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
