@@ -77,7 +77,7 @@ def assert_same_update(got_state, got_out, want_state, want_out, what):
 
 # ---- acting --------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("R,H", [(1, 1), (5, 128), (7, 9), (62, 256)])
+@pytest.mark.parametrize("R,H", [(1, 1), (5, 128), (7, 9), (62, 256), (6, 9)])
 def test_act_host_equals_the_numpy_restatement(ok, tanhf, R, H):
     for n in (1, 63, 65):
         rng = np.random.default_rng(R * 1000 + n)
@@ -162,7 +162,7 @@ CASES = [(1, 1, 1, False, 0.005), (31, 32, 3, True, 0.005), (33, 33, 1, False, 1
          (31, 250, 1, False, 0.005)]
 
 
-@pytest.mark.parametrize("shape", [(1, 1, 1), (5, 128, 128), (7, 9, 13), (62, 256, 256)])
+@pytest.mark.parametrize("shape", [(1, 1, 1), (5, 128, 128), (7, 9, 13), (62, 256, 256), (6, 9, 131), (8, 131, 13), (5, 1, 256), (5, 256, 1)])
 def test_update_host_equals_the_numpy_restatement(ok, tanhf, shape):
     R, H, Hc = shape
     rng = np.random.default_rng(sum(shape))
@@ -182,6 +182,23 @@ def test_update_host_equals_the_numpy_restatement(ok, tanhf, shape):
             assert np.array_equal(bits(new["actor_target"]), bits(st["actor_target"])) and np.array_equal(bits(new["critic_target"]), bits(st["critic_target"])), what
         else:
             assert not np.array_equal(new["actor_target"], st["actor_target"]) and not np.array_equal(new["actor_target"], new["actor"]), what
+
+
+@pytest.mark.parametrize("B", [513, 1500, 4096])
+def test_update_host_equals_the_numpy_restatement_above_eight_chunks(ok, tanhf, B):
+    """ok_learn_tree in the host entry (okDdpgStepHost) at C = 17, 47 and 128 chunks (CASES stops at B = 250, eight chunks): padded
+    widths 32, 64 and 128, the guard `i + h < n` false at the first level for C = 17 and 47 and never for 128.  These are the B of
+    tests/test_gpu_update_geometry.py, whose device results are compared with this host entry."""
+    R, H, Hc = 7, 9, 13
+    rng = np.random.default_rng(B)
+    for iterations, resample, tau in ((1, False, 0.005), (3, True, 1.0)):
+        cfg = config(H, Hc, tau=tau, sample_seed=B)
+        rg = filled_ring(rng, R, 1000, 1000)
+        st = fresh_state(rng, R, H, Hc, moments=True)
+        got = ok.ddpg_update_host(cfg_of(ok, cfg), R, st, rg, B, iterations, resample, draw_base=7)
+        want = G_.update(cfg, R, st, rg, B, tanhf, iterations, resample, draw_base=7)
+        assert_same_update(*got, *want, ((R, H, Hc), B, iterations, resample, tau))
+        assert np.isfinite(got[1]["critic_loss"]).all() and got[1]["actor_loss"].size == iterations and got[1]["index"].size == B
 
 
 def test_two_calls_continue_one_run(ok):

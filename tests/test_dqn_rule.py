@@ -13,7 +13,7 @@ import _learn_numpy as L_
 f32 = np.float32
 U = 2.0 ** -24  # unit roundoff of fp32
 HP = dict(lr=1e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8)  # kLearningRate (DQAgent.hpp:34); clip is unread
-SHAPES = [(5, 128, 5), (7, 9, 4), (64, 256, 8), (1, 1, 2)]
+SHAPES = [(5, 128, 5), (7, 9, 4), (64, 256, 8), (1, 1, 2), (6, 9, 4), (10, 13, 5)]
 RING_FIELDS = ("state", "next_state", "action", "reward", "done")
 
 
@@ -179,6 +179,26 @@ def test_update_host_equals_the_numpy_restatement(ok, shape):
         want = D_.update(HP, cfg, shape, st, rg, B, iterations, resample, draw_base=7, target=target)
         assert_same_update(*got, *want, (shape, size, B, iterations, resample, mask_done, target_network))
         assert np.isfinite(got[1]["loss"]).all() and got[1]["loss"].size == iterations
+
+
+@pytest.mark.parametrize("B", [513, 1500, 4096])
+def test_update_host_equals_the_numpy_restatement_above_four_chunks(ok, B):
+    """ok_learn_tree in the host entry at C = 17, 47 and 128 chunks (CASES stops at B = 100, four chunks): padded widths 32, 64 and
+    128, the guard `i + h < n` false at the first level for C = 17 and 47 and never for 128.  These are the B of
+    tests/test_gpu_update_geometry.py, whose device results are compared with this host entry."""
+    shape = (7, 9, 4)
+    R, H, A = shape
+    rng = np.random.default_rng(B)
+    lp = ok.capi.learner_params(**HP)
+    for iterations, resample, mask_done, target_network in ((1, False, True, False), (3, True, False, True)):
+        rg = filled_ring(rng, R, A, 1000, 1000)
+        st = fresh_state(rng, shape)
+        target = (st["policy"] + rng.standard_normal(st["policy"].size).astype(f32) * f32(0.05)) if target_network else None
+        cfg = dict(gamma=0.99, mask_done=mask_done, target_network=target_network, seed=B)
+        got = ok.dqn_update_host(lp, cfg_of(ok, cfg), shape, st, rg, B, iterations, resample, draw_base=7, target=target)
+        want = D_.update(HP, cfg, shape, st, rg, B, iterations, resample, draw_base=7, target=target)
+        assert_same_update(*got, *want, (shape, B, iterations, resample, mask_done, target_network))
+        assert np.isfinite(got[1]["loss"]).all() and got[1]["loss"].size == iterations and got[1]["index"].size == B
 
 
 def test_two_calls_continue_one_run(ok):

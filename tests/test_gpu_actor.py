@@ -40,10 +40,13 @@ def make_env(gpu, track, N, fan, seed):
 
 @pytest.mark.parametrize("track,R,H,A,Hv,N", [
     ("Austin", 5, 128, 3, 128, 4096), ("Silverstone", 1, 1, 2, 0, 257), ("Monza", 15, 16, 5, 256, 4096), ("Austin", 64, 256, 8, 256, 257),
-    ("Silverstone", 64, 128, 8, 1, 1), ("Monza", 5, 256, 2, 16, 257), ("Silverstone", 15, 1, 3, 128, 4096), ("Austin", 1, 16, 5, 0, 1)])
+    ("Silverstone", 64, 128, 8, 1, 1), ("Monza", 5, 256, 2, 16, 257), ("Silverstone", 15, 1, 3, 128, 4096), ("Austin", 1, 16, 5, 0, 1),
+    ("Monza", 6, 9, 4, 13, 257)])
 def test_device_equals_host(gpu, track, R, H, A, Hv, N):
     """Every record slot and the two action fields, all modes, crashed agents among them, agent_base != 0, each record pointer
-    NULL in turn."""
+    NULL in turn.  The row (6, 9, 4, 13) is the first in okActorKernel whose first layers (54 and 78 floats) end inside a 16-byte
+    load of okActorStage while everything behind them is shifted (R even, so the LDS row stride is R + 1; the other even fan, 64
+    at widths 128 and 256, ends on a load), with widths that leave a lane a partial last round of hidden units."""
     fan = gpu.default_ray_fan(R) if R > 1 else np.zeros(1, dtype=f32)
     t, dev = make_env(gpu, track, N, fan, seed=R + N)
     rng = np.random.default_rng(N * 7 + R + H)

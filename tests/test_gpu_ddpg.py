@@ -61,9 +61,11 @@ def make_env(gpu, N, R, H, Hc, env_seed, **cfg):
 
 @pytest.mark.parametrize("N", [1, 257, 1025])
 def test_act_equals_host_entry(gpu, N):
-    """A partial workgroup, a partial wave and several workgroups; both shapes; noise off and on (one component only, too); a sharded
-    agent_base; crashed agents; each record pointer NULL in turn."""
-    for R, H in ((5, 128), (62, 256)):
+    """A partial workgroup, a partial wave and several workgroups; four shapes; noise off and on (one component only, too); a sharded
+    agent_base; crashed agents; each record pointer NULL in turn.  (6, 9) is the first even fan of okDdpgActKernel whose first
+    layer (54 floats) ends inside a 16-byte load of okActorStage while everything behind it is shifted (by 9 floats); (7, 9) is
+    the same width with the identity copy, and both leave lane 0 of a group a second, partial round of hidden units (j = 8)."""
+    for R, H in ((5, 128), (62, 256), (6, 9), (7, 9)):
         for noise, base in (((0.0, 0.0), 0), ((20.0, 2.0), 4000), ((0.0, 3.0), 7)):
             cfg = dict(CFG, noise=noise, seed=31, agent_base=base)
             dev, actor, _ = make_env(gpu, N, R, H, 8, env_seed=N + R, **cfg)
@@ -109,10 +111,11 @@ def act_step_push(gpu, dev, rec, host_ring, reward=None, push_all=False):
                               dev.get(gpu.capi.F_CRASHED), None if reward is None else reward.cpu().numpy(), push_all)
 
 
-@pytest.mark.parametrize("N", [1, 65, 257, 1025])
+@pytest.mark.parametrize("N", [1, 65, 256, 257, 512, 1025])
 def test_push_equals_host_entry(gpu, N):
     """Every ring field and the counter after ten consecutive act + step + push: capacities below one call's transitions (1, 7), below
-    ten calls' (100) and above (5000), every mask, push-all and a caller's reward in turn."""
+    ten calls' (100) and above (5000), every mask, push-all and a caller's reward in turn.  N = 256 and 512 are exact workgroup
+    edges of the push kernels: no thread of the last workgroup fails `a < p.N` in okReplaySelected."""
     R, H = 5, 16
     dev, _, _ = make_env(gpu, N, R, H, 8, env_seed=N, noise=(10.0, 1.0))
     rng = np.random.default_rng(N)
@@ -178,11 +181,21 @@ def assert_update_equal(dev, got, want_state, want, what):
         assert np.array_equal(bits(st[k]), bits(want_state[k])), (k,) + tuple(what)
 
 
-@pytest.mark.parametrize("shape", [(5, 128, 128), (1, 1, 1), (62, 256, 256)])
+UPDATE_SHAPES = [(5, 128, 128), (1, 1, 1), (62, 256, 256), (7, 9, 13), (6, 9, 131), (8, 131, 13), (5, 1, 256), (5, 256, 1)]
+
+
+@pytest.mark.parametrize("shape", UPDATE_SHAPES)
 def test_update_equals_host_entry(gpu, shape):
     """All four networks, all moments, both losses, both gradients and the slots: size in {1, 33, 1000} x B in {1, 32, 33, 250} with
     iterations, resample and tau rotating through the cases; then each output NULL in turn, a continuation across calls, and acting
-    with the new parameters without any sync call."""
+    with the new parameters without any sync call.  The shapes with H != Hc are the first on the device in which okDdpgNetFloats,
+    okLearnHiddenStride(H, Hc) and the strides rpa / rpc of the two gradient kernels are not the same for both networks:
+      (7, 9, 13)    odd fans (identity staging) and widths that are no multiple of 8: a lane's last round of hidden units is partial
+      (6, 9, 131)   R = 2 mod 4 with odd H: the actor's first layer (54 floats) ends inside a 16-byte load of okActorStage with a
+                    shift of 9; the critic's (8 x 131) ends on one; H < Hc
+      (8, 131, 13)  R = 0 mod 4: the actor's first layer ends on a load, the critic's (10 x 13 = 130 floats) inside one with a
+                    shift of 13; H > Hc
+      (5, 1, 256), (5, 256, 1)   the widest ratio either way: the staged region and the hidden rows are sized by the other network"""
     R, H, Hc = shape
     N = 257
     rng = np.random.default_rng(sum(shape) + 3)

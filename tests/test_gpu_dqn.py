@@ -18,7 +18,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 HP = dict(lr=1e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8)
-SHAPES = [(5, 128, 5), (7, 9, 4), (64, 256, 8), (1, 1, 2)]
+# (6, 9, 4) and (10, 13, 5): even fans with R = 2 mod 4 and odd widths, so okActorStage's first layer (54 / 130 floats) ends inside a
+# 16-byte load while everything behind it is shifted by H floats; the other even fan, 64 x 256, ends on a load
+SHAPES = [(5, 128, 5), (7, 9, 4), (64, 256, 8), (1, 1, 2), (6, 9, 4), (10, 13, 5)]
 TABLE8 = tuple((10.0 * k + 5.0, 2.5 * k - 9.0) for k in range(8))
 RING_FIELDS = ("state", "next_state", "action", "reward", "done")
 DQN_FAN = np.array([-70, -30, 0, 30, 70], dtype=f32)
@@ -66,12 +68,13 @@ def act_step_push(gpu, dev, rec, host_ring, reward=None, push_all=False):
                          dev.get(gpu.capi.F_CRASHED), None if reward is None else reward.cpu().numpy(), push_all)
 
 
-@pytest.mark.parametrize("N", [1, 65, 257, 1025])
+@pytest.mark.parametrize("N", [1, 65, 256, 257, 512, 1025])
 def test_push_equals_host_entry(gpu, N):
     """Every ring field and the counter after each of ten consecutive pushes' worth of act + step + push: capacities below one call's
     transitions (1, 7), below ten calls' (100) and above (5000: no wrap unless N = 1025), every mask (set through crashed_ before the
     act, so that `alive` is the actor's own byte and some agents crash during the step as well), push-all and a caller's reward in
-    turn.  N = 257 and 1025 span two and five workgroups of the push kernels."""
+    turn.  N = 257 and 1025 span two and five workgroups of the push kernels; N = 256 and 512 are exact workgroup edges (no thread
+    of the last workgroup fails `a < p.N` in okReplaySelected)."""
     R, H, A = 5, 16, 5
     dev, _ = make_env(gpu, N, R, H, A, seed=N)
     rng = np.random.default_rng(N)

@@ -16,7 +16,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 HP = dict(lr=3e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8)
-SHAPES = [(5, 128, 3, 128), (1, 1, 2, 1), (7, 9, 4, 16), (64, 256, 8, 256)]
+# (6, 9, 4, 13): R = 2 mod 4 with odd widths, so the first layer of both networks (54 / 78 floats) ends inside a 16-byte load of
+# okActorStage while everything behind it is shifted (by 9 / 13 floats).  (8, 131, 3, 9): R = 0 mod 4, both first layers end on a
+# load with a non-zero shift, H > Hv, and the value network is staged into a place sized by the policy's.
+SHAPES = [(5, 128, 3, 128), (1, 1, 2, 1), (7, 9, 4, 16), (64, 256, 8, 256), (6, 9, 4, 13), (8, 131, 3, 9)]
 TABLE8 = tuple((10.0 * k + 5.0, 2.5 * k - 9.0) for k in range(8))
 OUTS = ("actor_loss", "critic_loss", "clipped", "grad_policy", "grad_value")
 

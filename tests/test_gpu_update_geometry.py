@@ -1,0 +1,239 @@
+"""The learners' device kernels at the edges of their launch geometry (openkitchen_amd/csrc/ok_learn.h, ok_dqn.h, ok_ddpg.h): every
+chunk count 1 .. 130 of the tree the three step kernels share (okLearnColumnSum), the same tree at the widths the examples run,
+calls of different B on one handle (the partials' buffer grows and is reused while larger than needed), and pushes over more than
+256 workgroups (okReplayScatterKernel's count loop).  Everything is compared bit for bit with the host entries, whose own link to
+the numpy restatements at these B is in tests/test_learn_rule.py, test_dqn_rule.py and test_ddpg_rule.py."""
+import numpy as np
+import pytest
+import torch
+
+import _learn_numpy as L_
+import test_gpu_ddpg as G
+import test_gpu_dqn as Q
+import test_gpu_learn as P
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+LEARNERS = ("ppo", "dqn", "ddpg")
+SMALLEST = {"ppo": (1, 1, 2, 1), "dqn": (1, 1, 2), "ddpg": (1, 1, 1)}
+EXAMPLE = {"ppo": (5, 128, 3, 128), "dqn": (5, 128, 5), "ddpg": (5, 128, 128)}
+LARGEST = {"ppo": (64, 256, 8, 256), "dqn": (64, 256, 8), "ddpg": (62, 256, 256)}
+N_RING, RING = 257, 1000  # ring_on_device pushes 4 x 257 transitions of real steps: a full ring of 1000
+
+
+def sweep_batch(C):
+    """B of chunk count C: C - 1 full chunks and a last one of 1 + C mod 32 positions (every fill 1 .. 32 occurs in 1 .. 130)."""
+    return 32 * (C - 1) + 1 + C % 32
+
+
+class PpoCases:
+    """One handle; a case is a fresh random batch of M = B samples in one minibatch, fresh parameters and zeroed moments."""
+
+    def __init__(self, gpu, shape, seed):
+        self.gpu, self.shape, self.rng = gpu, shape, np.random.default_rng(seed)
+        self.lp = gpu.capi.learner_params(**P.HP)
+        self.dev = P.handle_for(gpu, shape, P.fresh_state(self.rng, shape))
+
+    def run(self, B, case, iterations=1, tail=0):
+        """`tail` > 0 adds a second, partial minibatch of that many positions to every epoch."""
+        shape, rng, M = self.shape, self.rng, B + tail
+        batch = P.random_batch(rng, shape, M, with_adv=case % 2 == 1)
+        order = np.stack([rng.permutation(M) for _ in range(iterations)]).astype(np.int32) if case % 3 != 0 else None
+        st = P.fresh_state(rng, shape, 0.3 if shape[0] < 64 else 0.05)
+        self.dev.actor_set_params(st["policy"], st.get("value"))
+        self.dev.learner_reset()
+        got = P.on_device(self.dev, batch, M, B, iterations, order, shape)
+        want_state, want = self.gpu.ppo_update_host(self.lp, shape, st, batch, B, iterations, order)
+        what = ("ppo", shape, B, case, iterations, tail)
+        assert set(got) == set(P.OUTS), what
+        P.assert_outputs_equal(got, want, what)
+        P.assert_state_equal(P.device_state(self.dev), want_state, what)
+
+    def close(self):
+        self.dev.close()
+
+
+class DqnCases:
+    """One handle and one ring of 1000 real transitions; a case is fresh parameters, a new learner (zeroed moments, t = 0) and the
+    mask-done / target-network switches of its number."""
+
+    def __init__(self, gpu, shape, seed):
+        R, H, A = shape
+        self.gpu, self.shape, self.rng = gpu, shape, np.random.default_rng(seed)
+        self.lp = gpu.capi.learner_params(**Q.HP)
+        self.dev, _ = Q.make_env(gpu, N_RING, R, H, A, seed=seed)
+        self.ring = Q.ring_on_device(gpu, self.dev, N_RING, R, RING, self.rng)
+
+    def run(self, B, case, iterations=1, tail=0):
+        gpu, dev, shape, rng = self.gpu, self.dev, self.shape, self.rng
+        R, H, A = shape
+        resample, mask_done, target_on = case % 2 == 1, case % 3 == 1, case % 4 >= 2
+        policy = (rng.standard_normal(L_.n_params(R, H, A)) * (0.3 if R < 64 else 0.05)).astype(f32)
+        target = (policy + rng.standard_normal(policy.size).astype(f32) * f32(0.05)) if target_on else None
+        st = {"policy": policy, "policy_m": np.zeros_like(policy), "policy_v": np.zeros_like(policy), "t": 0}
+        if target_on:  # the target network is a copy of what the actor holds at sync time
+            dev.actor_set_params(target, None)
+            dev.dqn_params(0.99, mask_done, True, seed=R + case)
+            dev.dqn_sync_target()
+        else:
+            dev.dqn_params(0.99, mask_done, False, seed=R + case)
+        dev.actor_set_params(policy, None)
+        dev.learner_create(**Q.HP)
+        cfg = gpu.capi.dqn_config(0.99, mask_done, target_on, R + case)
+        got = Q.device_update(dev, shape, B, iterations, resample, 5 + case)
+        want_state, want = gpu.dqn_update_host(self.lp, cfg, shape, st, self.ring, B, iterations, resample, 5 + case, target)
+        what = ("dqn", shape, B, case, iterations, resample, mask_done, target_on)
+        assert set(got) == {"loss", "grad_policy", "index"}, what
+        Q.assert_update_equal(dev, got, want_state, want, what)
+
+    def close(self):
+        self.dev.close()
+
+
+class DdpgCases:
+    """One handle and one ring of 1000 real transitions; a case is a new DDPG object on the same ring (fresh parameters, targets
+    equal to them, zeroed moments, t = 0) with the tau of its number."""
+
+    def __init__(self, gpu, shape, seed):
+        R, H, Hc = shape
+        self.gpu, self.shape, self.rng = gpu, shape, np.random.default_rng(seed)
+        self.dev, _, _ = G.make_env(gpu, N_RING, R, H, Hc, env_seed=seed, noise=(5.0, 0.5))
+        self.ring = G.ring_on_device(self.dev, N_RING, R, RING)
+
+    def run(self, B, case, iterations=1, tail=0):
+        gpu, dev, rng = self.gpu, self.dev, self.rng
+        R, H, Hc = self.shape
+        resample, tau = case % 2 == 1, (0.005, 1.0, 0.0, 0.005)[case % 4]
+        cfg = dict(G.CFG, tau=tau, sample_seed=R + case, noise=(5.0, 0.5))
+        dev.ddpg_create(H, Hc, **cfg)  # (the ring stays; parameters, moments and t are forgotten)
+        scale = 0.3 if R < 62 else 0.05
+        actor, critic = (rng.standard_normal(G.n_actor(R, H)) * scale).astype(f32), (rng.standard_normal(G.n_critic(R, Hc)) * scale).astype(f32)
+        dev.ddpg_set_params(actor, critic)
+        st = {"actor": actor, "critic": critic, "actor_target": actor, "critic_target": critic, "t": 0}
+        for net in ("actor", "critic"):
+            st[net + "_m"], st[net + "_v"] = np.zeros_like(st[net]), np.zeros_like(st[net])
+        got = G.device_update(dev, R, H, Hc, B, iterations, resample, 5 + case)
+        want_state, want = gpu.ddpg_update_host(gpu.capi.ddpg_config(H, Hc, **cfg), R, st, self.ring, B, iterations, resample, 5 + case)
+        what = ("ddpg", self.shape, B, case, iterations, resample, tau)
+        assert set(got) == set(G.OUTPUTS), what
+        G.assert_update_equal(dev, got, want_state, want, what)
+
+    def close(self):
+        self.dev.close()
+
+
+CASES = {"ppo": PpoCases, "dqn": DqnCases, "ddpg": DdpgCases}
+
+
+# ---- A: every chunk count, smallest network ----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("learner", LEARNERS)
+def test_every_chunk_count_1_to_130(gpu, learner):
+    """One update per C = 1 .. 130 with B = 32 (C - 1) + 1 + C mod 32, on the smallest shape of the ABI (one step workgroup,
+    7 live columns for Deep-Q and for each of DDPG's networks, 12 for PPO), one iteration each.  What okLearnColumnSum executes for the first time
+    on the device, by C (w is C padded to a power of two; "in place" are the levels h >= 16 of `for (h = w >> 1; h >= kLearnStepRows`):
+      C = 9 .. 16    the LDS level h = 8 of the last loop (`for (h = min(w >> 1, 8)`), its guard `i + h < n` false for C < 16 and
+                     never false at C = 16; C = 9, 10, ... also has a last chunk of 10, 11, ... positions, and C = 32 k (k = 1 .. 4)
+                     a last chunk of ONE position, whose 31 spare groups borrow its sample (with C = 9 .. 16 in the test below)
+      C = 17         the first in-place level (h = 16): only thread 0's partial passes the guard `i + h < n`
+      C = 18 .. 31   that guard true for the threads r < C - 16 and false for the others
+      C = 33 .. 64   two in-place levels (h = 32, 16); at h = 32 a thread owns two partials of one level (i = r and r + 16), the
+                     guard cutting the level after the first (C <= 48) or inside the second; no power of two above 32 ran before
+      C = 65 .. 128  three in-place levels; four partials per thread at h = 64
+      C = 129, 130   w = 256: four in-place levels, eight partials per thread at h = 128, of which only one or two pass the guard
+    (for PPO C = 32 was reached before, for Deep-Q nothing above C = 4, for DDPG nothing above C = 8)."""
+    cases = CASES[learner](gpu, SMALLEST[learner], seed=11)
+    fills = set()
+    for C in range(1, 131):
+        B = sweep_batch(C)
+        assert (B + 31) // 32 == C
+        fills.add(B - 32 * (C - 1))
+        cases.run(B, case=C)
+    assert fills == set(range(1, 33))
+    cases.close()
+
+
+@pytest.mark.parametrize("learner", LEARNERS)
+def test_the_lds_level_8_with_a_last_chunk_of_one_position(gpu, learner):
+    """C = 9 .. 16 with B = 32 (C - 1) + 1: the LDS level h = 8 of okLearnColumnSum with its guard `i + h < n` (false from i = C - 8
+    on), and in the same launch a last chunk of one position, whose 31 spare groups take part in the gradient kernel's shuffles with
+    that sample (`g < n ? g : n - 1`) and whose rows the chunk sums must not read.  Both on the smallest shape and on the example's,
+    where the last of the step workgroups is partly live."""
+    for shape in (SMALLEST[learner], EXAMPLE[learner]):
+        cases = CASES[learner](gpu, shape, seed=12)
+        for C in range(9, 17):
+            cases.run(32 * (C - 1) + 1, case=C)
+        cases.close()
+
+
+# ---- B: the tree at real widths ----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("learner", LEARNERS)
+def test_the_tree_at_the_examples_width(gpu, learner):
+    """The shape of the example and of the bench tool, (5, 128, 3, 128) / (5, 128, 5) / (5, 128, 128): 129, 89 and 73 + 65 step
+    workgroups of which the last is partly live (`live = column < cols`), on ONE handle in the order B = 257, 4096, 513, 1500, 1025:
+      B = 257   C = 9: the LDS level h = 8, a last chunk of one position
+      B = 4096  C = 128: three in-place levels with every guard true, the shape tools/ddpg_bench.py times; the partials' buffer
+                grows (the handle frees the old one behind a stream synchronisation)
+      B = 513   C = 17: the first in-place level with only thread 0's partial passing, in a buffer that is larger than needed
+                and still holds the partials of B = 4096 behind row 17
+      B = 1500  C = 47: two in-place levels, at h = 32 the guard passes only a thread's first partial, and not thread 15's (i + 32 < 47 for i < 15)
+      B = 1025  C = 33: w = 64 with a single partial beyond 32
+    Iterations in {1, 3}, resample, mask-done / the target network and tau in {0.005, 1, 0} rotate with the case number; PPO runs
+    M = B + 100, so every epoch has a second minibatch of 100 positions (C = 4) between two large ones."""
+    cases = CASES[learner](gpu, EXAMPLE[learner], seed=13)
+    for case, B in enumerate((257, 4096, 513, 1500, 1025)):
+        cases.run(B, case=case, iterations=(1, 3)[case % 2], tail=100 if learner == "ppo" else 0)
+    cases.close()
+
+
+@pytest.mark.parametrize("learner", LEARNERS)
+def test_the_tree_at_the_largest_shape(gpu, learner):
+    """(64, 256, 8, 256) / (64, 256, 8) / (62, 256, 256) at B = 1025 (C = 33: two in-place levels), three iterations with a new
+    draw each: 2225, 1169 and 1057 + 1041 step workgroups, each column's partials 35 595 / 18 697 / 16 898 and 16 643 floats apart (the stride
+    of `x[i * stride]`)."""
+    cases = CASES[learner](gpu, LARGEST[learner], seed=14)
+    cases.run(1025, case=1, iterations=3)
+    cases.close()
+
+
+# ---- D: pushes over more than 256 workgroups ---------------------------------------------------------------------------------------
+
+BIG_N = 257 * 256 + 1
+
+
+@pytest.mark.parametrize("learner", ["dqn", "ddpg"])
+def test_push_over_more_than_256_workgroups(gpu, learner):
+    """N = 65 793 agents, R = 1: 258 workgroups of the push kernels, so okReplayScatterKernel's count loop
+    `for (b = threadIdx.x; b < gridDim.x; b += kReplayThreads)` takes a second round in threads 0 and 1 (five workgroups was the
+    most before), and the last workgroup holds one agent.  Three consecutive act + step + push per case; capacity 1000 (fewer slots
+    than one call's transitions: whole workgroups of selected agents do not survive), 100 000 (wraps at the second call) and 300 000
+    (no wrap); masks "random" and "alternating", push-all and a caller's reward rotating as in test_push_equals_host_entry.  Every
+    ring field and (size, pushed) against the host entry's ring after each case."""
+    N, R = BIG_N, 1
+    M = Q if learner == "dqn" else G
+    if learner == "dqn":
+        dev, _ = Q.make_env(gpu, N, R, 16, 5, seed=9)
+        create, ring_of = dev.replay_create, gpu.replay_ring
+    else:
+        dev, _, _ = G.make_env(gpu, N, R, 16, 8, env_seed=9, noise=(10.0, 1.0))
+        create, ring_of = dev.ddpg_replay_create, gpu.ddpg_ring
+    rng = np.random.default_rng(N)
+    rec = M.record_tensors(N, R)
+    case = 1  # (so that push-all meets capacity 100 000: 2 N transitions wrap it at the second call)
+    for capacity in (1000, 100_000, 300_000):
+        for mask in ("random", "alternating"):
+            push_all, own_reward = case % 3 == 1, case % 3 == 2
+            case += 1
+            create(capacity, push_all)
+            host = ring_of(capacity, R)
+            reward = torch.from_numpy(rng.standard_normal(N).astype(f32)).cuda() if own_reward else None
+            for push in range(3):
+                if push == 0:  # (afterwards the flags are what the last step left: crashed agents stay crashed)
+                    crashed = (np.arange(N) % 2).astype(np.uint8) if mask == "alternating" else (rng.random(N) < 0.25).astype(np.uint8)
+                    dev.set(gpu.capi.F_CRASHED, crashed)
+                M.act_step_push(gpu, dev, rec, host, reward, push_all)
+            what = (learner, capacity, mask, push_all, own_reward)
+            assert host["pushed"] > max(65536, capacity if capacity == 100_000 else 0) and (not push_all or host["pushed"] == 3 * N), what
+            M.same_ring(dev, host, what)
+    dev.close()

@@ -13,7 +13,7 @@ import _learn_numpy as L_
 f32 = np.float32
 U = 2.0 ** -24  # unit roundoff of fp32
 HP = dict(lr=3e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8)
-SHAPES = [(5, 128, 3, 128), (1, 1, 2, 1), (7, 9, 4, 16), (64, 256, 8, 256)]
+SHAPES = [(5, 128, 3, 128), (1, 1, 2, 1), (7, 9, 4, 16), (64, 256, 8, 256), (6, 9, 4, 13), (8, 131, 3, 9)]
 TABLE8 = tuple((10.0 * k + 5.0, 2.5 * k - 9.0) for k in range(8))
 
 
@@ -68,6 +68,26 @@ def test_host_entry_equals_the_numpy_restatement(ok, shape):
         assert got_state["t"] == epochs * ((M + B - 1) // B)
         clipped_seen += int(got_out["clipped"].sum())
     assert clipped_seen > 0
+
+
+@pytest.mark.parametrize("B", [513, 1500, 4096])
+def test_host_entry_equals_the_numpy_restatement_above_seven_chunks(ok, B):
+    """ok_learn_tree in the host entry at C = 17, 47 and 128 chunks (the cases above stop at C = 7: M = 1000 in minibatches of 4096
+    is never run as one, B = 100 gives four): padded widths 32, 64 and 128, the guard `i + h < n` false at the first level for
+    C = 17 and 47 and never for 128.  M = B + 40 adds a partial second minibatch (two chunks) to each of the two epochs.  These are
+    the B of tests/test_gpu_update_geometry.py, whose device results are compared with this host entry."""
+    shape = (7, 9, 4, 16)
+    rng = np.random.default_rng(B)
+    lp = ok.capi.learner_params(**HP)
+    for permuted, with_adv in ((False, True), (True, False)):
+        M = B + 40
+        st = fresh_state(rng, shape)
+        batch = random_batch(rng, shape, M, with_adv)
+        order = np.stack([rng.permutation(M) for _ in range(2)]).astype(np.int32) if permuted else None
+        got_state, got_out = ok.ppo_update_host(lp, shape, st, batch, B, 2, order)
+        want_state, want_out = L_.update(ok.debug_expf, HP, shape, st, batch, B, 2, order)
+        assert_same(got_state, got_out, want_state, want_out, (shape, M, B, permuted, with_adv))
+        assert got_state["t"] == 4 and got_out["actor_loss"].size == 4
 
 
 def test_two_calls_continue_one_run(ok):
