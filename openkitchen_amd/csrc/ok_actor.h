@@ -77,6 +77,32 @@ __device__ __forceinline__ void okActorStage(float *dst, const float *src, const
     }
 }
 
+// ok_actor_join's tree over the 8 lanes of a group, lane distances 4, 2, 1: every lane gets the sum of the lanes' partial sums
+__device__ __forceinline__ float okActorJoinLanes(float v)
+{
+    v = v + __shfl_xor(v, 4);
+    v = v + __shfl_xor(v, 2);
+    v = v + __shfl_xor(v, 1);
+    return v;
+}
+
+// The outputs z[0 .. out) of the network staged at `net` (okActorStage, R inputs) for the group's row x, in every lane of the group:
+// the lanes' partial sums, their join, the output's bias.  z[k] = 0 for k >= out.
+__device__ __forceinline__ void okActorForward(const float *net, const int R, const int hidden, const int out, const float *x, const int lane, float *z)
+{
+    const int rp = okActorRowStride(R);
+    float     part[OK_ACTOR_MAX_ACTIONS];
+    ok_actor_partial(net, rp, net + hidden * rp, net + hidden * rp + hidden, R, hidden, out, x, lane, part);
+    const float *b2 = net + hidden * rp + hidden + out * hidden;
+#pragma unroll
+    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+    {
+        z[k] = 0.F;
+        if (k < out)
+            z[k] = b2[k] + okActorJoinLanes(part[k]);
+    }
+}
+
 extern __shared__ float ok_actor_lds[];
 
 __global__ __launch_bounds__(kActorThreads) void okActorKernel(const OkActorParams p)
@@ -101,31 +127,13 @@ __global__ __launch_bounds__(kActorThreads) void okActorKernel(const OkActorPara
             p.rec.state[a * R + i] = v;
     }
     __syncthreads();
-    float part[OK_ACTOR_MAX_ACTIONS], z[OK_ACTOR_MAX_ACTIONS];
-    ok_actor_partial(pol, rp, pol + H * rp, pol + H * rp + H, R, H, A, x, lane, part);
-    const float *b2 = pol + H * rp + H + A * H;
-#pragma unroll
-    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
-    {
-        z[k] = 0.F;
-        if (k < A)
-        { // ok_actor_join's tree: lane distances 4, 2, 1
-            float v = part[k];
-            v       = v + __shfl_xor(v, 4);
-            v       = v + __shfl_xor(v, 2);
-            v       = v + __shfl_xor(v, 1);
-            z[k]    = b2[k] + v;
-        }
-    }
+    float z[OK_ACTOR_MAX_ACTIONS], zv[OK_ACTOR_MAX_ACTIONS];
+    okActorForward(pol, R, H, A, x, lane, z);
     float value = 0.F;
     if (Hv > 0)
     {
-        ok_actor_partial(val, rp, val + Hv * rp, val + Hv * rp + Hv, R, Hv, 1, x, lane, part);
-        float v = part[0];
-        v       = v + __shfl_xor(v, 4);
-        v       = v + __shfl_xor(v, 2);
-        v       = v + __shfl_xor(v, 1);
-        value   = val[Hv * rp + Hv + Hv] + v;
+        okActorForward(val, R, Hv, 1, x, lane, zv);
+        value = zv[0];
     }
     const int      best  = ok_actor_argmax(z, A);
     const uint32_t draw  = (p.step_word != nullptr ? p.step_word[0] : p.host_steps) + (p.draw_offset != nullptr ? p.draw_offset[0] : 0U);

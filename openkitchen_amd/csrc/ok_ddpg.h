@@ -1,7 +1,7 @@
 // ok_ddpg.h -- DDPG on the device: the continuous actor's action kernel, the push of a ring whose action is
 // two floats, and DDPGAgent::update's iterations (RLRacers/DDPG/DDPGAgent.hpp:127-170) on uniform samples of it.  The rule lives in
 // include/okenv_ddpg.h (ok_ddpg_*) on top of the actor's forward, the learner's backward, sums and Adam, and the ring's rules, and is
-// shared with okDdpgActHost / okDdpgPushHost / okDdpgUpdateHost below, so the device and the host entries agree bit for bit.
+// shared with okDdpgActHost / okReplayPushHost (ok_dqn.h) / okDdpgUpdateHost below, so the device and the host entries agree bit for bit.
 //
 // These are NOT step kernels and add no step-kernel launch site.  On the handle's stream:
 //   okDdpgActKernel         32 agents x 8 lanes per workgroup: x = dist / 200, the actor, tanh * scale + bias, noise, the record
@@ -43,15 +43,6 @@ inline size_t okDdpgActLdsBytes(const int R, const int H)
     return sizeof(float) * static_cast<size_t>(okActorNetFloats(R, H, 2) + kActorAgents * okActorRowStride(R));
 }
 
-// The two outputs of a network with two outputs from the lanes' partial sums: ok_actor_join's tree over lane distances 4, 2, 1
-__device__ __forceinline__ float okDdpgJoinLanes(float v)
-{
-    v = v + __shfl_xor(v, 4);
-    v = v + __shfl_xor(v, 2);
-    v = v + __shfl_xor(v, 1);
-    return v;
-}
-
 // tanh * scale + bias of both outputs: lanes 0 and 1 of the group take one ok_tanhf each (an fp64 evaluation), every lane gets both
 __device__ __forceinline__ void okDdpgGroupAction(const float z0, const float z1, const float *scale, const float *bias, const int lane, float *a, float *t)
 {
@@ -82,12 +73,9 @@ __global__ __launch_bounds__(kActorThreads) void okDdpgActKernel(const OkDdpgAct
             p.rec.state[a * R + i] = v;
     }
     __syncthreads();
-    float part[OK_ACTOR_MAX_ACTIONS];
-    ok_actor_partial(net, rp, net + H * rp, net + H * rp + H, R, H, 2, x, lane, part);
-    const float *b2 = net + H * rp + H + 2 * H;
-    const float  z0 = b2[0] + okDdpgJoinLanes(part[0]), z1 = b2[1] + okDdpgJoinLanes(part[1]);
-    float        act[2], t[2];
-    okDdpgGroupAction(z0, z1, p.scale, p.bias, lane, act, t);
+    float z[OK_ACTOR_MAX_ACTIONS], act[2], t[2];
+    okActorForward(net, R, H, 2, x, lane, z);
+    okDdpgGroupAction(z[0], z[1], p.scale, p.bias, lane, act, t);
     if (lane != 0 || !valid)
         return;
     if (p.noise[0] > 0.F || p.noise[1] > 0.F)
@@ -166,125 +154,81 @@ __host__ __device__ inline int okDdpgNetFloats(const int R, const int H, const i
 
 inline size_t okDdpgLdsBytes(const int R, const int H, const int Hc)
 {
-    return sizeof(float) * static_cast<size_t>(okDdpgNetFloats(R, H, Hc) + OK_LEARN_CHUNK * (okActorRowStride(R + 2) + 2 * okLearnHiddenStride(H, Hc) + OK_ACTOR_MAX_ACTIONS + 1));
+    return sizeof(float) * static_cast<size_t>(okLearnPlaces(okDdpgNetFloats(R, H, Hc), R + 2, okLearnHiddenStride(H, Hc), 1).end);
 }
 
-// What both gradient kernels begin with: the LDS places, the group's sample and its slot in the ring
-struct OkDdpgSample
+// What both gradient kernels begin with: the chunk (its rows hold the critic's input [state, a_0, a_1]) and the group's ring draw
+__device__ __forceinline__ OkLearnChunk okDdpgBegin(const OkDdpgParams &p, size_t *idx, int *live)
 {
-    float *net, *xs, *hs, *dss, *dzs, *terms, *x;
-    int    g, lane, chunk, n, q, live, rpx, hp;
-    size_t idx;
-};
-
-__device__ __forceinline__ OkDdpgSample okDdpgBegin(const OkDdpgParams &p)
-{
-    OkDdpgSample s;
-    s.rpx   = okActorRowStride(p.R + 2);
-    s.hp    = okLearnHiddenStride(p.H, p.Hc);
-    s.net   = ok_learn_lds;
-    s.xs    = s.net + okDdpgNetFloats(p.R, p.H, p.Hc);
-    s.hs    = s.xs + OK_LEARN_CHUNK * s.rpx;
-    s.dss   = s.hs + OK_LEARN_CHUNK * s.hp;
-    s.dzs   = s.dss + OK_LEARN_CHUNK * s.hp;
-    s.terms = s.dzs + OK_LEARN_CHUNK * OK_ACTOR_MAX_ACTIONS;
-    s.g     = static_cast<int>(threadIdx.x) / kLearnLanes;
-    s.lane  = static_cast<int>(threadIdx.x) & (kLearnLanes - 1);
-    s.chunk = static_cast<int>(blockIdx.x);
-    const int left = p.B - s.chunk * OK_LEARN_CHUNK;
-    s.n            = left < OK_LEARN_CHUNK ? left : OK_LEARN_CHUNK;
-    // (the spare groups of the last chunk take part in the shuffles with its last sample; the sums never read their rows)
-    s.q = s.chunk * OK_LEARN_CHUNK + (s.g < s.n ? s.g : s.n - 1);
-    const uint32_t size = static_cast<uint32_t>(ok_dqn_size(p.pushed[0], p.capacity));
-    s.live              = size != 0U;
-    s.idx               = s.live ? ok_dqn_sample(p.seed, static_cast<uint32_t>(s.q), p.draw, size) : 0U;
-    s.x                 = s.xs + s.g * s.rpx;
+    const OkLearnChunk s = okLearnBegin(okDdpgNetFloats(p.R, p.H, p.Hc), p.R + 2, okLearnHiddenStride(p.H, p.Hc), 1, p.B);
+    *idx                 = okReplayDraw(p, s.q, live);
     return s;
-}
-
-// The actor's two pre-tanh outputs for the group's row x (the network staged at `net` with R inputs)
-__device__ __forceinline__ void okDdpgActorForward(const float *net, const int R, const int H, const float *x, const int lane, float *z0, float *z1)
-{
-    const int rp = okActorRowStride(R);
-    float     part[OK_ACTOR_MAX_ACTIONS];
-    ok_actor_partial(net, rp, net + H * rp, net + H * rp + H, R, H, 2, x, lane, part);
-    const float *b2 = net + H * rp + H + 2 * H;
-    *z0             = b2[0] + okDdpgJoinLanes(part[0]);
-    *z1             = b2[1] + okDdpgJoinLanes(part[1]);
 }
 
 __global__ __launch_bounds__(kLearnThreads) void okDdpgCriticGradKernel(const OkDdpgParams p)
 {
     const int          R = p.R, H = p.H, Hc = p.Hc, in = R + 2;
-    const OkDdpgSample s = okDdpgBegin(p);
-    const int          lane = s.lane, rpc = okActorRowStride(in);
+    size_t             idx;
+    int                live;
+    const OkLearnChunk s = okDdpgBegin(p, &idx, &live);
+    const int          lane = s.lane;
     float             *x = s.x;
     // a' = the target actor's action on s'
     okActorStage(s.net, p.actor_t, R, H, p.Pa);
-    for (int i = lane; i < R; i += kLearnLanes)
-        x[i] = s.live ? p.ring.next_state[s.idx * static_cast<size_t>(R) + i] : 0.F;
+    okReplayGatherRow(x, p.ring.next_state, idx, R, lane, live);
     __syncthreads();
-    float z0, z1, act[2], t[2];
-    okDdpgActorForward(s.net, R, H, x, lane, &z0, &z1);
-    okDdpgGroupAction(z0, z1, p.scale, p.bias, lane, act, t);
+    float z[OK_ACTOR_MAX_ACTIONS], dz[OK_ACTOR_MAX_ACTIONS], act[2], t[2];
+    okActorForward(s.net, R, H, 2, x, lane, z);
+    okDdpgGroupAction(z[0], z[1], p.scale, p.bias, lane, act, t);
     if (lane < 2)
         x[R + lane] = lane == 1 ? act[1] : act[0];
     __syncthreads(); // every group is done with the target actor: its place is free
     // q' = the target critic on [s', a'], to y
     okActorStage(s.net, p.critic_t, in, Hc, p.Pc);
     __syncthreads();
-    float part[OK_ACTOR_MAX_ACTIONS], dz[OK_ACTOR_MAX_ACTIONS];
-    ok_actor_partial(s.net, rpc, s.net + Hc * rpc, s.net + Hc * rpc + Hc, in, Hc, 1, x, lane, part);
-    const float qn = s.net[Hc * rpc + Hc + Hc] + okDdpgJoinLanes(part[0]);
-    const float y  = ok_dqn_target(s.live ? p.ring.reward[s.idx] : 0.F, s.live ? p.ring.done[s.idx] : 0.F, p.gamma, qn, OK_DQN_MASK_DONE);
+    okActorForward(s.net, in, Hc, 1, x, lane, z);
+    const float y = ok_dqn_target(live ? p.ring.reward[idx] : 0.F, live ? p.ring.done[idx] : 0.F, p.gamma, z[0], OK_DQN_MASK_DONE);
     __syncthreads(); // every group has read its row and the target critic: both places are free
     // the online critic on [s, a], in the same rows
     okActorStage(s.net, p.critic, in, Hc, p.Pc);
-    for (int i = lane; i < R; i += kLearnLanes)
-        x[i] = s.live ? p.ring.state[s.idx * static_cast<size_t>(R) + i] : 0.F;
+    okReplayGatherRow(x, p.ring.state, idx, R, lane, live);
     if (lane < 2)
-        x[R + lane] = s.live ? p.ring.action[2U * s.idx + static_cast<size_t>(lane)] : 0.F;
+        x[R + lane] = live ? p.ring.action[2U * idx + static_cast<size_t>(lane)] : 0.F;
     __syncthreads();
-    ok_actor_partial(s.net, rpc, s.net + Hc * rpc, s.net + Hc * rpc + Hc, in, Hc, 1, x, lane, part);
-    const float qv = s.net[Hc * rpc + Hc + Hc] + okDdpgJoinLanes(part[0]);
-    const float e  = s.live ? qv - y : 0.F;
+    okActorForward(s.net, in, Hc, 1, x, lane, z);
+    const float e = live ? z[0] - y : 0.F;
 #pragma unroll
     for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
         dz[k] = k == 0 ? e : 0.F;
-    okLearnHidden(s.net, rpc, in, Hc, 1, x, dz, lane, s.hs + s.g * s.hp, s.dss + s.g * s.hp);
+    okLearnHidden(s.net, s.rp, in, Hc, 1, x, dz, lane, s.hs + s.g * s.hp, s.dss + s.g * s.hp);
     if (lane == 0)
     {
         s.dzs[s.g * OK_ACTOR_MAX_ACTIONS] = e;
         s.terms[s.g]                      = e * e;
         if (s.g < s.n && p.index != nullptr)
-            p.index[s.q] = static_cast<int32_t>(s.idx);
+            p.index[s.q] = static_cast<int32_t>(idx);
     }
     __syncthreads();
     float *col = p.part + static_cast<size_t>(s.chunk) * static_cast<size_t>(p.Pc + 1);
-    okLearnChunkSums(p.Pc, in, Hc, 1, s.xs, s.hs, s.dss, s.dzs, s.rpx, s.hp, s.n, col);
-    if (threadIdx.x == 0)
-    {
-        float acc = 0.F;
-        for (int k = 0; k < s.n; ++k)
-            acc = acc + s.terms[k];
-        col[p.Pc] = acc;
-    }
+    okLearnChunkSums(p.Pc, in, Hc, 1, s.xs, s.hs, s.dss, s.dzs, s.rp, s.hp, s.n, col);
+    okLearnSumTerms(s.terms, s.n, col + p.Pc);
 }
 
 __global__ __launch_bounds__(kLearnThreads) void okDdpgActorGradKernel(const OkDdpgParams p)
 {
     const int          R = p.R, H = p.H, Hc = p.Hc, in = R + 2;
-    const OkDdpgSample s = okDdpgBegin(p);
-    const int          lane = s.lane, rpa = okActorRowStride(R), rpc = okActorRowStride(in);
+    size_t             idx;
+    int                live;
+    const OkLearnChunk s = okDdpgBegin(p, &idx, &live);
+    const int          lane = s.lane, rpa = okActorRowStride(R), rpc = s.rp;
     float             *x = s.x;
     // a = the online actor's action on s
     okActorStage(s.net, p.actor, R, H, p.Pa);
-    for (int i = lane; i < R; i += kLearnLanes)
-        x[i] = s.live ? p.ring.state[s.idx * static_cast<size_t>(R) + i] : 0.F;
+    okReplayGatherRow(x, p.ring.state, idx, R, lane, live);
     __syncthreads();
-    float z0, z1, act[2], t[2];
-    okDdpgActorForward(s.net, R, H, x, lane, &z0, &z1);
-    okDdpgGroupAction(z0, z1, p.scale, p.bias, lane, act, t);
+    float z[OK_ACTOR_MAX_ACTIONS], act[2], t[2];
+    okActorForward(s.net, R, H, 2, x, lane, z);
+    okDdpgGroupAction(z[0], z[1], p.scale, p.bias, lane, act, t);
     if (lane < 2)
         x[R + lane] = lane == 1 ? act[1] : act[0];
     __syncthreads(); // every group is done with the actor: its place is free
@@ -292,9 +236,9 @@ __global__ __launch_bounds__(kLearnThreads) void okDdpgActorGradKernel(const OkD
     okActorStage(s.net, p.critic, in, Hc, p.Pc);
     __syncthreads();
     float pq, pda[2];
-    ok_ddpg_critic_lane(s.net, rpc, s.net + Hc * rpc, s.net + Hc * rpc + Hc, in, Hc, x, lane, s.live ? 1.F : 0.F, &pq, pda);
-    const float qv  = s.net[Hc * rpc + Hc + Hc] + okDdpgJoinLanes(pq);
-    const float da0 = okDdpgJoinLanes(pda[0]), da1 = okDdpgJoinLanes(pda[1]);
+    ok_ddpg_critic_lane(s.net, rpc, s.net + Hc * rpc, s.net + Hc * rpc + Hc, in, Hc, x, lane, live ? 1.F : 0.F, &pq, pda);
+    const float qv  = s.net[Hc * rpc + Hc + Hc] + okActorJoinLanes(pq);
+    const float da0 = okActorJoinLanes(pda[0]), da1 = okActorJoinLanes(pda[1]);
     float       dz[OK_ACTOR_MAX_ACTIONS];
 #pragma unroll
     for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
@@ -309,17 +253,11 @@ __global__ __launch_bounds__(kLearnThreads) void okDdpgActorGradKernel(const OkD
     if (lane < 2)
         s.dzs[s.g * OK_ACTOR_MAX_ACTIONS + lane] = lane == 1 ? dz[1] : dz[0];
     if (lane == 0)
-        s.terms[s.g] = s.live ? qv : 0.F;
+        s.terms[s.g] = live ? qv : 0.F;
     __syncthreads();
     float *col = p.part + static_cast<size_t>(s.chunk) * static_cast<size_t>(p.Pa + 1);
-    okLearnChunkSums(p.Pa, R, H, 2, s.xs, s.hs, s.dss, s.dzs, s.rpx, s.hp, s.n, col);
-    if (threadIdx.x == 0)
-    {
-        float acc = 0.F;
-        for (int k = 0; k < s.n; ++k)
-            acc = acc + s.terms[k];
-        col[p.Pa] = acc;
-    }
+    okLearnChunkSums(p.Pa, R, H, 2, s.xs, s.hs, s.dss, s.dzs, s.rp, s.hp, s.n, col);
+    okLearnSumTerms(s.terms, s.n, col + p.Pa);
 }
 
 // The step of one network (kActor: the actor's, else the critic's) and the soft update of its target in the thread that owns the
@@ -336,13 +274,10 @@ __global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okDdpgStepKern
     const float count = static_cast<float>(p.B);
     if (column < P)
     {
-        float *par = (kActor ? p.actor : p.critic) + column, *tgt = (kActor ? p.actor_t : p.critic_t) + column;
-        float *out = kActor ? p.grad_actor : p.grad_critic;
-        const float g = ok_ddpg_scale_grad(sum, count, kActor ? 1 : 0);
-        if (out != nullptr)
-            out[column] = g;
-        ok_learn_adam(par, (kActor ? p.act_m : p.cri_m) + column, (kActor ? p.act_v : p.cri_v) + column, g, kActor ? p.adam_actor : p.adam_critic);
-        *tgt = ok_ddpg_soft(*par, *tgt, p.tau, p.omt);
+        float *par = kActor ? p.actor : p.critic, *tgt = (kActor ? p.actor_t : p.critic_t) + column;
+        okLearnStepParam(par, kActor ? p.act_m : p.cri_m, kActor ? p.act_v : p.cri_v, kActor ? p.grad_actor : p.grad_critic, column,
+                         ok_ddpg_scale_grad(sum, count, kActor ? 1 : 0), kActor ? p.adam_actor : p.adam_critic);
+        *tgt = ok_ddpg_soft(par[column], *tgt, p.tau, p.omt);
     }
     else
     {
@@ -375,11 +310,6 @@ inline const char *okDdpgCheckConfig(const okenv_ddpg_config *c, const int R)
     if (!(c->eps > 0.F) || !(c->eps < 3.0e38F))
         return "eps must be positive and finite";
     return nullptr;
-}
-
-inline bool okDdpgRingComplete(const okenv_ddpg_ring *r)
-{
-    return r != nullptr && r->state != nullptr && r->next_state != nullptr && r->action != nullptr && r->reward != nullptr && r->done != nullptr;
 }
 
 inline ok_learn_adam_consts okDdpgAdamConsts(const okenv_ddpg_config &c, const float lr, const int64_t t)
@@ -424,35 +354,16 @@ inline void okDdpgActHost(const okenv_ddpg_config &c, const float *actor, const 
     }
 }
 
-// One push, agent by agent
-inline void okDdpgPushHost(const okenv_ddpg_ring &ring, const uint64_t capacity, const int R, uint64_t *pushed, const uint32_t flags, const int n_agents,
-                           const float *state, const float *action, const uint8_t *alive, const float *dist, const uint8_t *crashed, const float *reward)
+// okReplayPushHost's two pieces (ok_dqn.h) for a ring whose action is two floats
+inline void okReplayStoreActionHost(const okenv_ddpg_ring &ring, const size_t slot, const float *action, const size_t a)
 {
-    const bool all = (flags & OK_REPLAY_PUSH_ALL) != 0U;
-    uint64_t   n   = 0;
-    for (int a = 0; a < n_agents; ++a)
-        n += (all || alive[a] != 0) ? 1U : 0U;
-    uint64_t k = 0;
-    for (int a = 0; a < n_agents; ++a)
-    {
-        if (!(all || alive[a] != 0))
-            continue;
-        if (ok_dqn_survives(k, n, capacity))
-        {
-            const size_t slot = static_cast<size_t>(ok_dqn_slot(*pushed + k, capacity)), src = static_cast<size_t>(a) * R;
-            for (int i = 0; i < R; ++i)
-            {
-                ring.state[slot * R + i]      = state[src + i];
-                ring.next_state[slot * R + i] = dist[src + i] / OK_SENSOR_RANGE;
-            }
-            ring.action[2 * slot]     = action[2 * static_cast<size_t>(a)];
-            ring.action[2 * slot + 1] = action[2 * static_cast<size_t>(a) + 1];
-            ring.done[slot]           = crashed[a] != 0 ? 1.F : 0.F;
-            ring.reward[slot]         = reward != nullptr ? reward[a] : 1.F;
-        }
-        ++k;
-    }
-    *pushed += n;
+    ring.action[2 * slot]     = action[2 * a];
+    ring.action[2 * slot + 1] = action[2 * a + 1];
+}
+
+inline float okReplayRewardHost(const okenv_ddpg_ring &, const int, const float *, const int)
+{
+    return 1.F;
 }
 
 // The join, the scale, Adam and the soft update of one network on the host: okDdpgStepKernel
@@ -465,10 +376,7 @@ inline void okDdpgStepHost(std::vector<float> &part, const int P, const int C, c
         const float sum = ok_learn_tree(part.data() + column, cols, static_cast<uint32_t>(C));
         if (column < P)
         {
-            const float g = ok_ddpg_scale_grad(sum, count, is_actor ? 1 : 0);
-            if (grad != nullptr)
-                grad[column] = g;
-            ok_learn_adam(par + column, m + column, v + column, g, adam);
+            okLearnStepParam(par, m, v, grad, column, ok_ddpg_scale_grad(sum, count, is_actor ? 1 : 0), adam);
             tgt[column] = ok_ddpg_soft(par[column], tgt[column], tau, omt);
         }
         else if (loss != nullptr)
@@ -529,10 +437,7 @@ inline void okDdpgUpdateHost(const okenv_ddpg_config &cfg, const int R, okenv_dd
                     out.index[q] = static_cast<int32_t>(idx);
             }
             okLearnHostChunkSums(Pc, in, Hc, 1, xs.data(), rows, n, col);
-            float acc = 0.F;
-            for (int s = 0; s < n; ++s)
-                acc = acc + terms[static_cast<size_t>(s)];
-            col[Pc] = acc;
+            col[Pc] = okLearnHostSumTerms(terms.data(), n);
         }
         okDdpgStepHost(part, Pc, C, count, false, st.critic, st.critic_m, st.critic_v, st.critic_target, okDdpgAdamConsts(cfg, cfg.lr_critic, st.t), cfg.tau, omt,
                        out.grad_critic, out.critic_loss != nullptr ? out.critic_loss + it : nullptr);
@@ -570,10 +475,7 @@ inline void okDdpgUpdateHost(const okenv_ddpg_config &cfg, const int R, okenv_dd
                     rows.dz[static_cast<size_t>(s) * OK_ACTOR_MAX_ACTIONS + a] = dz[a];
             }
             okLearnHostChunkSums(Pa, R, H, 2, xa.data(), rows, n, col);
-            float acc = 0.F;
-            for (int s = 0; s < n; ++s)
-                acc = acc + terms[static_cast<size_t>(s)];
-            col[Pa] = acc;
+            col[Pa] = okLearnHostSumTerms(terms.data(), n);
         }
         okDdpgStepHost(part, Pa, C, count, true, st.actor, st.actor_m, st.actor_v, st.actor_target, okDdpgAdamConsts(cfg, cfg.lr_actor, st.t), cfg.tau, omt,
                        out.grad_actor, out.actor_loss != nullptr ? out.actor_loss + it : nullptr);

@@ -174,66 +174,48 @@ struct OkDqnParams
 
 inline size_t okDqnLdsBytes(const int R, const int H, const int A)
 {
-    return sizeof(float) * static_cast<size_t>(okActorNetFloats(R, H, A) + OK_LEARN_CHUNK * (okActorRowStride(R) + 2 * okLearnHiddenStride(H, 0) + OK_ACTOR_MAX_ACTIONS + 1));
+    return sizeof(float) * static_cast<size_t>(okLearnPlaces(okActorNetFloats(R, H, A), R, okLearnHiddenStride(H, 0), 1).end);
+}
+
+// The ring draw of the sampling learners (P: OkDqnParams, ok_ddpg.h's OkDdpgParams) for position q of the batch: the slot, and
+// whether the ring holds anything (an empty ring gives zeros everywhere and a zero gradient)
+template <class P>
+__device__ __forceinline__ size_t okReplayDraw(const P &p, const int q, int *live)
+{
+    const uint32_t size = static_cast<uint32_t>(ok_dqn_size(p.pushed[0], p.capacity));
+    *live               = size != 0U;
+    return *live ? ok_dqn_sample(p.seed, static_cast<uint32_t>(q), p.draw, size) : 0U;
+}
+
+// Row idx of the ring's `state` or `next_state` into the group's LDS row, consecutive lanes on consecutive addresses
+__device__ __forceinline__ void okReplayGatherRow(float *x, const float *rows, const size_t idx, const int R, const int lane, const int live)
+{
+    for (int i = lane; i < R; i += kLearnLanes)
+        x[i] = live ? rows[idx * static_cast<size_t>(R) + i] : 0.F;
 }
 
 __global__ __launch_bounds__(kLearnThreads) void okDqnGradKernel(const OkDqnParams p)
 {
-    const int R = p.R, H = p.H, A = p.A, rp = okActorRowStride(R), hp = okLearnHiddenStride(H, 0);
-    float    *net = ok_learn_lds, *xs = net + okActorNetFloats(R, H, A), *hs = xs + OK_LEARN_CHUNK * rp, *dss = hs + OK_LEARN_CHUNK * hp;
-    float    *dzs = dss + OK_LEARN_CHUNK * hp, *sqs = dzs + OK_LEARN_CHUNK * OK_ACTOR_MAX_ACTIONS;
-    const int g = static_cast<int>(threadIdx.x) / kLearnLanes, lane = static_cast<int>(threadIdx.x) & (kLearnLanes - 1);
-    const int chunk = static_cast<int>(blockIdx.x);
-    const int left = p.B - chunk * OK_LEARN_CHUNK, n = left < OK_LEARN_CHUNK ? left : OK_LEARN_CHUNK;
-    // (the spare groups of the last chunk take part in the shuffles with its last sample; the sums never read their rows)
-    const int      q    = chunk * OK_LEARN_CHUNK + (g < n ? g : n - 1);
-    const uint32_t size = static_cast<uint32_t>(ok_dqn_size(p.pushed[0], p.capacity));
-    const int      live = size != 0U;
-    const size_t   idx  = live ? ok_dqn_sample(p.seed, static_cast<uint32_t>(q), p.draw, size) : 0U;
-    float         *x    = xs + g * rp;
+    const int          R = p.R, H = p.H, A = p.A;
+    const OkLearnChunk s = okLearnBegin(okActorNetFloats(R, H, A), R, okLearnHiddenStride(H, 0), 1, p.B);
+    const int          g = s.g, lane = s.lane;
+    int                live;
+    const size_t       idx = okReplayDraw(p, s.q, &live);
+    float             *net = s.net, *x = s.x;
     // s' through the target's network, to y
     okActorStage(net, p.target, R, H, p.Pp);
-    for (int i = lane; i < R; i += kLearnLanes)
-        x[i] = live ? p.ring.next_state[idx * static_cast<size_t>(R) + i] : 0.F;
+    okReplayGatherRow(x, p.ring.next_state, idx, R, lane, live);
     __syncthreads();
-    float        part[OK_ACTOR_MAX_ACTIONS], z[OK_ACTOR_MAX_ACTIONS], dz[OK_ACTOR_MAX_ACTIONS];
-    const float *b2 = net + H * rp + H + A * H;
-    ok_actor_partial(net, rp, net + H * rp, net + H * rp + H, R, H, A, x, lane, part);
-#pragma unroll
-    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
-    {
-        z[k] = 0.F;
-        if (k < A)
-        { // ok_actor_join's tree: lane distances 4, 2, 1
-            float v = part[k];
-            v       = v + __shfl_xor(v, 4);
-            v       = v + __shfl_xor(v, 2);
-            v       = v + __shfl_xor(v, 1);
-            z[k]    = b2[k] + v;
-        }
-    }
+    float z[OK_ACTOR_MAX_ACTIONS], dz[OK_ACTOR_MAX_ACTIONS];
+    okActorForward(net, R, H, A, x, lane, z);
     const float y = ok_dqn_target(live ? p.ring.reward[idx] : 0.F, live ? p.ring.done[idx] : 0.F, p.gamma, ok_dqn_max(z, A), p.flags);
     __syncthreads(); // every group has read its s' row and the target's network: both places are free
     // s through the online network, in the same rows
     if (p.target != p.policy)
         okActorStage(net, p.policy, R, H, p.Pp);
-    for (int i = lane; i < R; i += kLearnLanes)
-        x[i] = live ? p.ring.state[idx * static_cast<size_t>(R) + i] : 0.F;
+    okReplayGatherRow(x, p.ring.state, idx, R, lane, live);
     __syncthreads();
-    ok_actor_partial(net, rp, net + H * rp, net + H * rp + H, R, H, A, x, lane, part);
-#pragma unroll
-    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
-    {
-        z[k] = 0.F;
-        if (k < A)
-        { // ok_actor_join's tree: lane distances 4, 2, 1
-            float v = part[k];
-            v       = v + __shfl_xor(v, 4);
-            v       = v + __shfl_xor(v, 2);
-            v       = v + __shfl_xor(v, 1);
-            z[k]    = b2[k] + v;
-        }
-    }
+    okActorForward(net, R, H, A, x, lane, z);
     const int action = live ? ok_learn_clamp_index(static_cast<long long>(p.ring.action[idx]), A) : 0;
     float     mine = z[0], sq; // lane k holds q_k
 #pragma unroll
@@ -241,27 +223,21 @@ __global__ __launch_bounds__(kLearnThreads) void okDqnGradKernel(const OkDqnPara
         if (k == lane)
             mine = z[k];
     ok_dqn_seed(__shfl(mine, action, kLearnLanes), action, y, live, dz, &sq);
-    okLearnHidden(net, rp, R, H, A, x, dz, lane, hs + g * hp, dss + g * hp);
+    okLearnHidden(net, s.rp, R, H, A, x, dz, lane, s.hs + g * s.hp, s.dss + g * s.hp);
 #pragma unroll
     for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
         if (k == lane)
-            dzs[g * OK_ACTOR_MAX_ACTIONS + k] = dz[k];
+            s.dzs[g * OK_ACTOR_MAX_ACTIONS + k] = dz[k];
     if (lane == 0)
     {
-        sqs[g] = sq;
-        if (g < n && p.index != nullptr)
-            p.index[q] = static_cast<int32_t>(idx);
+        s.terms[g] = sq;
+        if (g < s.n && p.index != nullptr)
+            p.index[s.q] = static_cast<int32_t>(idx);
     }
     __syncthreads();
-    float *col = p.part + static_cast<size_t>(chunk) * static_cast<size_t>(p.cols);
-    okLearnChunkSums(p.Pp, R, H, A, xs, hs, dss, dzs, rp, hp, n, col);
-    if (threadIdx.x == 0)
-    {
-        float acc = 0.F;
-        for (int s = 0; s < n; ++s)
-            acc = acc + sqs[s];
-        col[p.Pp] = acc;
-    }
+    float *col = p.part + static_cast<size_t>(s.chunk) * static_cast<size_t>(p.cols);
+    okLearnChunkSums(p.Pp, R, H, A, s.xs, s.hs, s.dss, s.dzs, s.rp, s.hp, s.n, col);
+    okLearnSumTerms(s.terms, s.n, col + p.Pp);
 }
 
 __global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okDqnStepKernel(const OkDqnParams p)
@@ -273,12 +249,7 @@ __global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okDqnStepKerne
         return;
     const float count = ok_dqn_count(p.B, p.A);
     if (column < p.Pp)
-    {
-        const float g = ok_dqn_scale_grad(sum, count);
-        if (p.grad_policy != nullptr)
-            p.grad_policy[column] = g;
-        ok_learn_adam(p.policy + column, p.pol_m + column, p.pol_v + column, g, p.adam);
-    }
+        okLearnStepParam(p.policy, p.pol_m, p.pol_v, p.grad_policy, column, ok_dqn_scale_grad(sum, count), p.adam);
     else if (p.loss != nullptr)
         *p.loss = ok_dqn_scale_loss(sum, count);
 }
@@ -316,14 +287,29 @@ inline const char *okReplayCheckCreate(const int32_t capacity, const uint32_t fl
     return nullptr;
 }
 
-inline bool okReplayRingComplete(const okenv_replay_ring *r)
+// (okenv_replay_ring or okenv_ddpg_ring)
+template <class Ring>
+inline bool okReplayRingComplete(const Ring *r)
 {
     return r != nullptr && r->state != nullptr && r->next_state != nullptr && r->action != nullptr && r->reward != nullptr && r->done != nullptr;
 }
 
+// What the two rings differ in on the host, as okReplayStoreAction / okReplayReward above on the device: the action's row and the
+// reward of a push without one (ok_ddpg.h has the pair for a ring whose action is two floats)
+inline void okReplayStoreActionHost(const okenv_replay_ring &ring, const size_t slot, const int64_t *action, const size_t a)
+{
+    ring.action[slot] = action[a];
+}
+
+inline float okReplayRewardHost(const okenv_replay_ring &, const int crash, const float *dist_row, const int R)
+{
+    return ok_dqn_reward(crash, dist_row, R);
+}
+
 // One push, agent by agent
-inline void okReplayPushHost(const okenv_replay_ring &ring, const uint64_t capacity, const int R, uint64_t *pushed, const uint32_t flags, const int n_agents,
-                             const float *state, const int64_t *action, const uint8_t *alive, const float *dist, const uint8_t *crashed, const float *reward)
+template <class Ring, class Action>
+inline void okReplayPushHost(const Ring &ring, const uint64_t capacity, const int R, uint64_t *pushed, const uint32_t flags, const int n_agents,
+                             const float *state, const Action *action, const uint8_t *alive, const float *dist, const uint8_t *crashed, const float *reward)
 {
     const bool all = (flags & OK_REPLAY_PUSH_ALL) != 0U;
     uint64_t   n   = 0;
@@ -343,9 +329,9 @@ inline void okReplayPushHost(const okenv_replay_ring &ring, const uint64_t capac
                 ring.state[slot * R + i]      = state[src + i];
                 ring.next_state[slot * R + i] = dist[src + i] / OK_SENSOR_RANGE;
             }
-            ring.action[slot] = action[a];
+            okReplayStoreActionHost(ring, slot, action, static_cast<size_t>(a));
             ring.done[slot]   = crash ? 1.F : 0.F;
-            ring.reward[slot] = reward != nullptr ? reward[a] : ok_dqn_reward(crash, dist + src, R);
+            ring.reward[slot] = reward != nullptr ? reward[a] : okReplayRewardHost(ring, crash, dist + src, R);
         }
         ++k;
     }
@@ -396,10 +382,7 @@ inline void okDqnUpdateHost(const okenv_learner_params &lp, const okenv_dqn_conf
                     out.index[q] = static_cast<int32_t>(idx);
             }
             okLearnHostChunkSums(Pp, R, H, A, xs.data(), rows, n, col);
-            float acc = 0.F;
-            for (int s = 0; s < n; ++s)
-                acc = acc + sqs[static_cast<size_t>(s)];
-            col[Pp] = acc;
+            col[Pp] = okLearnHostSumTerms(sqs.data(), n);
         }
         st.t += 1;
         const ok_learn_adam_consts adam = okLearnAdamConsts(lp, st.t);
@@ -407,12 +390,7 @@ inline void okDqnUpdateHost(const okenv_learner_params &lp, const okenv_dqn_conf
         {
             const float sum = ok_learn_tree(part.data() + column, cols, static_cast<uint32_t>(C));
             if (column < Pp)
-            {
-                const float g = ok_dqn_scale_grad(sum, count);
-                if (out.grad_policy != nullptr)
-                    out.grad_policy[column] = g;
-                ok_learn_adam(st.policy + column, st.policy_m + column, st.policy_v + column, g, adam);
-            }
+                okLearnStepParam(st.policy, st.policy_m, st.policy_v, out.grad_policy, column, ok_dqn_scale_grad(sum, count), adam);
             else if (out.loss != nullptr)
                 out.loss[it] = ok_dqn_scale_loss(sum, count);
         }

@@ -52,20 +52,99 @@ __host__ __device__ inline int okLearnHiddenStride(const int H, const int Hv)
     return (H > Hv ? H : Hv) + 8;
 }
 
-// LDS floats: one network at a time (the value network first, then the policy network in the same place), the chunk's inputs,
-// hidden values and hidden seeds, output seeds, loss terms and clip flags
+// One network at a time in LDS (the value network first, then the policy network in the same place): the larger of the two
 __host__ __device__ inline int okLearnNetFloats(const int R, const int H, const int A, const int Hv)
 {
     const int a = okActorNetFloats(R, H, A), b = okActorNetFloats(R, Hv, 1);
     return a > b ? a : b;
 }
 
+// ---- shared pieces of the learners' kernels (PPO here, Deep-Q in ok_dqn.h, DDPG in ok_ddpg.h) ---------------
+
+// The LDS of a gradient kernel, in floats from its start: [net | xs | hs | dss | dzs | terms], that is the staged network, then for
+// the chunk's 32 samples the input rows (`in` wide), the hidden values and hidden seeds (stride hp), the output seeds and `terms`
+// rows of per-sample terms (a loss term; PPO has three: surrogate, squared error, clip flag).  `end` is the launch's size.
+struct OkLearnPlaces
+{
+    int xs, hs, dss, dzs, terms, end;
+};
+
+__host__ __device__ inline OkLearnPlaces okLearnPlaces(const int net_floats, const int in, const int hp, const int terms)
+{
+    OkLearnPlaces at;
+    at.xs    = net_floats;
+    at.hs    = at.xs + OK_LEARN_CHUNK * okActorRowStride(in);
+    at.dss   = at.hs + OK_LEARN_CHUNK * hp;
+    at.dzs   = at.dss + OK_LEARN_CHUNK * hp;
+    at.terms = at.dzs + OK_LEARN_CHUNK * OK_ACTOR_MAX_ACTIONS;
+    at.end   = at.terms + OK_LEARN_CHUNK * terms;
+    return at;
+}
+
 inline size_t okLearnLdsBytes(const int R, const int H, const int A, const int Hv)
 {
-    return sizeof(float) * static_cast<size_t>(okLearnNetFloats(R, H, A, Hv) + OK_LEARN_CHUNK * (okActorRowStride(R) + 2 * okLearnHiddenStride(H, Hv) + OK_ACTOR_MAX_ACTIONS + 3));
+    return sizeof(float) * static_cast<size_t>(okLearnPlaces(okLearnNetFloats(R, H, A, Hv), R, okLearnHiddenStride(H, Hv), 3).end);
 }
 
 extern __shared__ float ok_learn_lds[];
+
+// What every gradient kernel begins with: the LDS places, the group's lane, the chunk and the group's sample
+struct OkLearnChunk
+{
+    float *net, *xs, *hs, *dss, *dzs, *terms, *x; // x: the group's input row
+    int    g, lane, chunk, n, q, rp, hp;          // n: samples of this chunk; q: the group's position in the batch of B
+};
+
+__device__ __forceinline__ OkLearnChunk okLearnBegin(const int net_floats, const int in, const int hp, const int terms, const int B)
+{
+    const OkLearnPlaces at = okLearnPlaces(net_floats, in, hp, terms);
+    OkLearnChunk        s;
+    s.rp    = okActorRowStride(in);
+    s.hp    = hp;
+    s.net   = ok_learn_lds;
+    s.xs    = s.net + at.xs;
+    s.hs    = s.net + at.hs;
+    s.dss   = s.net + at.dss;
+    s.dzs   = s.net + at.dzs;
+    s.terms = s.net + at.terms;
+    s.g     = static_cast<int>(threadIdx.x) / kLearnLanes;
+    s.lane  = static_cast<int>(threadIdx.x) & (kLearnLanes - 1);
+    s.chunk = static_cast<int>(blockIdx.x);
+    const int left = B - s.chunk * OK_LEARN_CHUNK;
+    s.n            = left < OK_LEARN_CHUNK ? left : OK_LEARN_CHUNK;
+    // (the spare groups of the last chunk take part in the shuffles with its last sample; the sums never read their rows)
+    s.q = s.chunk * OK_LEARN_CHUNK + (s.g < s.n ? s.g : s.n - 1);
+    s.x = s.xs + s.g * s.rp;
+    return s;
+}
+
+// Thread 0 sums the chunk's n terms in ascending order into the column behind the parameters
+__device__ __forceinline__ void okLearnSumTerms(const float *terms, const int n, float *dst)
+{
+    if (threadIdx.x != 0)
+        return;
+    float acc = 0.F;
+    for (int q = 0; q < n; ++q)
+        acc = acc + terms[q];
+    *dst = acc;
+}
+
+// The same sum in a host entry
+inline float okLearnHostSumTerms(const float *terms, const int n)
+{
+    float acc = 0.F;
+    for (int q = 0; q < n; ++q)
+        acc = acc + terms[q];
+    return acc;
+}
+
+// A column that is parameter k of a network, in a step kernel and in a host entry's loop: the gradient's output, Adam in place
+__host__ __device__ inline void okLearnStepParam(float *par, float *m, float *v, float *grad_out, const int k, const float g, const ok_learn_adam_consts &adam)
+{
+    if (grad_out != nullptr)
+        grad_out[k] = g;
+    ok_learn_adam(par + k, m + k, v + k, g, adam);
+}
 
 // Phase B: threads own parameters and walk the chunk's samples in ascending position.  ok_learn_term's four kinds, the choice hoisted
 // out of the walk.
@@ -105,33 +184,25 @@ __device__ __forceinline__ void okLearnHidden(const float *net, const int rp, co
 
 __global__ __launch_bounds__(kLearnThreads) void okLearnGradKernel(const OkLearnParams p)
 {
-    const int R = p.R, H = p.H, A = p.A, Hv = p.Hv, rp = okActorRowStride(R), hp = okLearnHiddenStride(H, Hv);
-    float    *net = ok_learn_lds, *xs = net + okLearnNetFloats(R, H, A, Hv), *hs = xs + OK_LEARN_CHUNK * rp, *dss = hs + OK_LEARN_CHUNK * hp;
-    float    *dzs = dss + OK_LEARN_CHUNK * hp, *surrs = dzs + OK_LEARN_CHUNK * OK_ACTOR_MAX_ACTIONS, *sqs = surrs + OK_LEARN_CHUNK;
-    int      *clips = reinterpret_cast<int *>(sqs + OK_LEARN_CHUNK);
-    const int g = static_cast<int>(threadIdx.x) / kLearnLanes, lane = static_cast<int>(threadIdx.x) & (kLearnLanes - 1);
-    const int chunk = static_cast<int>(blockIdx.x);
-    const int left = p.Bk - chunk * OK_LEARN_CHUNK, n = left < OK_LEARN_CHUNK ? left : OK_LEARN_CHUNK;
-    // (the spare groups of the last chunk take part in the shuffles with its last sample; phase B never reads their rows)
-    const long pos = p.base + chunk * OK_LEARN_CHUNK + (g < n ? g : n - 1);
+    const int          R = p.R, H = p.H, A = p.A, Hv = p.Hv;
+    const OkLearnChunk s = okLearnBegin(okLearnNetFloats(R, H, A, Hv), R, okLearnHiddenStride(H, Hv), 3, p.Bk);
+    const int          g = s.g, lane = s.lane, rp = s.rp, hp = s.hp, n = s.n;
+    float             *net = s.net, *x = s.x, *surrs = s.terms, *sqs = surrs + OK_LEARN_CHUNK;
+    int               *clips = reinterpret_cast<int *>(sqs + OK_LEARN_CHUNK);
+    const long         pos = p.base + s.q;
     const int  idx = ok_learn_clamp_index(p.order != nullptr ? static_cast<long long>(p.order[pos]) : static_cast<long long>(pos), p.M);
-    float     *x   = xs + g * rp;
     for (int i = lane; i < R; i += kLearnLanes)
         x[i] = p.in.state[static_cast<size_t>(idx) * static_cast<size_t>(R) + i];
     const float ret = p.in.ret[idx];
     float       adv = p.in.adv != nullptr ? p.in.adv[idx] : 0.F;
-    float      *col = p.part + static_cast<size_t>(chunk) * static_cast<size_t>(p.cols);
-    float       part[OK_ACTOR_MAX_ACTIONS], dz[OK_ACTOR_MAX_ACTIONS];
+    float      *col = p.part + static_cast<size_t>(s.chunk) * static_cast<size_t>(p.cols);
+    float       z[OK_ACTOR_MAX_ACTIONS], dz[OK_ACTOR_MAX_ACTIONS];
     if (Hv > 0)
     { // the critic: its value is also the advantage's, from before either step
         okActorStage(net, p.value, R, Hv, p.Pv);
         __syncthreads();
-        ok_actor_partial(net, rp, net + Hv * rp, net + Hv * rp + Hv, R, Hv, 1, x, lane, part);
-        float v = part[0]; // ok_actor_join's tree: lane distances 4, 2, 1
-        v       = v + __shfl_xor(v, 4);
-        v       = v + __shfl_xor(v, 2);
-        v       = v + __shfl_xor(v, 1);
-        const float value = net[Hv * rp + Hv + Hv] + v;
+        okActorForward(net, R, Hv, 1, x, lane, z);
+        const float value = z[0];
         float       sq;
 #pragma unroll
         for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
@@ -139,70 +210,45 @@ __global__ __launch_bounds__(kLearnThreads) void okLearnGradKernel(const OkLearn
         ok_learn_value_seed(value, ret, &dz[0], &sq);
         if (p.in.adv == nullptr)
             adv = ret - value;
-        okLearnHidden(net, rp, R, Hv, 1, x, dz, lane, hs + g * hp, dss + g * hp);
+        okLearnHidden(net, rp, R, Hv, 1, x, dz, lane, s.hs + g * hp, s.dss + g * hp);
         if (lane == 0)
         {
-            dzs[g * OK_ACTOR_MAX_ACTIONS] = dz[0];
-            sqs[g]                        = sq;
+            s.dzs[g * OK_ACTOR_MAX_ACTIONS] = dz[0];
+            sqs[g]                          = sq;
         }
         __syncthreads();
-        okLearnChunkSums(p.Pv, R, Hv, 1, xs, hs, dss, dzs, rp, hp, n, col + p.Pp);
-        if (threadIdx.x == 0)
-        {
-            float acc = 0.F;
-            for (int q = 0; q < n; ++q)
-                acc = acc + sqs[q];
-            col[p.Pp + p.Pv + 1] = acc;
-        }
+        okLearnChunkSums(p.Pv, R, Hv, 1, s.xs, s.hs, s.dss, s.dzs, rp, hp, n, col + p.Pp);
+        okLearnSumTerms(sqs, n, col + p.Pp + p.Pv + 1);
         __syncthreads(); // the network's place and the rows are free again
     }
     else if (threadIdx.x == 0)
         col[p.Pp + p.Pv + 1] = 0.F;
     okActorStage(net, p.policy, R, H, p.Pp);
     __syncthreads();
-    ok_actor_partial(net, rp, net + H * rp, net + H * rp + H, R, H, A, x, lane, part);
-    const float *b2 = net + H * rp + H + A * H;
-    float        z[OK_ACTOR_MAX_ACTIONS];
-#pragma unroll
-    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
-    {
-        z[k] = 0.F;
-        if (k < A)
-        {
-            float v = part[k];
-            v       = v + __shfl_xor(v, 4);
-            v       = v + __shfl_xor(v, 2);
-            v       = v + __shfl_xor(v, 1);
-            z[k]    = b2[k] + v;
-        }
-    }
+    okActorForward(net, R, H, A, x, lane, z);
     const int action = ok_learn_clamp_index(static_cast<long long>(p.in.action[idx]), A);
     float     surr;
     int       clipped;
     ok_learn_policy_seed(z, A, action, p.in.prob[idx], adv, p.lo, p.hi, dz, &surr, &clipped);
-    okLearnHidden(net, rp, R, H, A, x, dz, lane, hs + g * hp, dss + g * hp);
+    okLearnHidden(net, rp, R, H, A, x, dz, lane, s.hs + g * hp, s.dss + g * hp);
 #pragma unroll
     for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
         if (k == lane)
-            dzs[g * OK_ACTOR_MAX_ACTIONS + k] = dz[k];
+            s.dzs[g * OK_ACTOR_MAX_ACTIONS + k] = dz[k];
     if (lane == 0)
     {
         surrs[g] = surr;
         clips[g] = clipped;
     }
     __syncthreads();
-    okLearnChunkSums(p.Pp, R, H, A, xs, hs, dss, dzs, rp, hp, n, col);
+    okLearnChunkSums(p.Pp, R, H, A, s.xs, s.hs, s.dss, s.dzs, rp, hp, n, col);
+    okLearnSumTerms(surrs, n, col + p.Pp + p.Pv);
     if (threadIdx.x == 0)
     {
-        float    acc = 0.F;
         uint32_t cnt = 0U;
         for (int q = 0; q < n; ++q)
-        {
-            acc = acc + surrs[q];
             cnt += static_cast<uint32_t>(clips[q]);
-        }
-        col[p.Pp + p.Pv] = acc;
-        p.part_clip[chunk] = cnt;
+        p.part_clip[s.chunk] = cnt;
     }
 }
 
@@ -251,20 +297,9 @@ __global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okLearnStepKer
     const uint32_t n  = static_cast<uint32_t>(p.C);
     const float    bk = static_cast<float>(p.Bk);
     if (column < p.Pp)
-    {
-        const float g = sum / bk;
-        if (p.grad_policy != nullptr)
-            p.grad_policy[column] = g;
-        ok_learn_adam(p.policy + column, p.pol_m + column, p.pol_v + column, g, p.adam);
-    }
+        okLearnStepParam(p.policy, p.pol_m, p.pol_v, p.grad_policy, column, sum / bk, p.adam);
     else if (column < p.Pp + p.Pv)
-    {
-        const int   k = column - p.Pp;
-        const float g = sum / bk;
-        if (p.grad_value != nullptr)
-            p.grad_value[k] = g;
-        ok_learn_adam(p.value + k, p.val_m + k, p.val_v + k, g, p.adam);
-    }
+        okLearnStepParam(p.value, p.val_m, p.val_v, p.grad_value, column - p.Pp, sum / bk, p.adam);
     else if (column == p.Pp + p.Pv)
     {
         if (p.actor_loss != nullptr)
@@ -441,10 +476,7 @@ inline void okLearnUpdateHost(const okenv_learner_params &lp, const int R, const
                             rows.dz[static_cast<size_t>(q) * OK_ACTOR_MAX_ACTIONS + a] = dz[a];
                     }
                     okLearnHostChunkSums(Pv, R, Hv, 1, xs.data(), rows, n, col + Pp);
-                    float acc = 0.F;
-                    for (int q = 0; q < n; ++q)
-                        acc = acc + sqs[q];
-                    col[Pp + Pv + 1] = acc;
+                    col[Pp + Pv + 1] = okLearnHostSumTerms(sqs.data(), n);
                 }
                 else
                     col[Pp + Pv + 1] = 0.F;
@@ -459,14 +491,10 @@ inline void okLearnUpdateHost(const okenv_learner_params &lp, const int R, const
                         rows.dz[static_cast<size_t>(q) * OK_ACTOR_MAX_ACTIONS + a] = dz[a];
                 }
                 okLearnHostChunkSums(Pp, R, H, A, xs.data(), rows, n, col);
-                float    acc = 0.F;
                 uint32_t cnt = 0U;
                 for (int q = 0; q < n; ++q)
-                {
-                    acc = acc + surrs[q];
                     cnt += static_cast<uint32_t>(clips[q]);
-                }
-                col[Pp + Pv]     = acc;
+                col[Pp + Pv]     = okLearnHostSumTerms(surrs.data(), n);
                 part_clip[chunk] = cnt;
             }
             st.t += 1;
@@ -477,20 +505,9 @@ inline void okLearnUpdateHost(const okenv_learner_params &lp, const int R, const
             {
                 const float sum = ok_learn_tree(part.data() + column, cols, static_cast<uint32_t>(C));
                 if (column < Pp)
-                {
-                    const float g = sum / bk;
-                    if (out.grad_policy != nullptr)
-                        out.grad_policy[column] = g;
-                    ok_learn_adam(st.policy + column, st.policy_m + column, st.policy_v + column, g, adam);
-                }
+                    okLearnStepParam(st.policy, st.policy_m, st.policy_v, out.grad_policy, column, sum / bk, adam);
                 else if (column < Pp + Pv)
-                {
-                    const int   j = column - Pp;
-                    const float g = sum / bk;
-                    if (out.grad_value != nullptr)
-                        out.grad_value[j] = g;
-                    ok_learn_adam(st.value + j, st.value_m + j, st.value_v + j, g, adam);
-                }
+                    okLearnStepParam(st.value, st.value_m, st.value_v, out.grad_value, column - Pp, sum / bk, adam);
                 else if (column == Pp + Pv)
                 {
                     if (out.actor_loss != nullptr)

@@ -363,6 +363,29 @@ OkStepPlan okPlanStep(const OkLaunchShape &s, const OkStepRequest &q)
 }
 } // namespace
 
+// A replay ring as the handle keeps it, Deep-Q's or DDPG's (both may live on one handle): the fields on the device, the counter words
+// and the push's count scratch.  The two differ in the action's row only.
+struct OkRing
+{
+    size_t    action_bytes;        // of one slot's action: an int64 index, or two floats
+    bool      ok{false};
+    uint32_t  flags{0};
+    int32_t   capacity{0};
+    float    *state{nullptr}, *next_state{nullptr};
+    uint8_t  *action{nullptr};
+    float    *reward{nullptr}, *done{nullptr};
+    uint64_t *d_words{nullptr};    // [0] pushed, [1] its value before the latest push
+    uint32_t *d_counts{nullptr};   // [workgroups of the push]
+    explicit OkRing(const size_t action_bytes_) : action_bytes(action_bytes_) {}
+};
+
+// The events around every kernel of an update's latest timed call (okenv_set_timing on): created on demand, kept for the next call
+struct OkEventLog
+{
+    std::vector<hipEvent_t> events;
+    size_t                  want{0}, at{0}, timed{0}; // events of the call under way, the last one recorded, events of the latest complete timed call
+};
+
 struct okenv
 {
     int         device{0};
@@ -473,14 +496,13 @@ struct okenv
     float             *d_actor_policy{nullptr}, *d_actor_value{nullptr};
     const uint32_t    *actor_draw_offset{nullptr};
     // episode -> batch (okenv_batch_prepare): scratch for the planes, column partials, group counts, statistics and M; grown, never
-    // shrunk; the events exist only while okenv_set_timing is on
+    // shrunk; the events of the latest timed call
     uint8_t   *d_batch{nullptr};
     size_t     batch_bytes{0};
     int32_t   *d_batch_count{nullptr};
-    bool       batch_timed{false};
-    hipEvent_t batch_events[6]{};
+    OkEventLog batch_log;
     // PPO's update (okenv_learner_create): Adam's moments beside the actor's parameters, the step number, the chunk partials (grown,
-    // never shrunk) and, while okenv_set_timing is on, the events around every kernel of the latest okenv_ppo_update
+    // never shrunk) and the events of the latest timed okenv_ppo_update
     bool                    learner_ok{false};
     okenv_learner_params    learner{};
     int64_t                 learn_t{0};
@@ -488,25 +510,18 @@ struct okenv
     size_t                  learn_cap{0};
     uint8_t                *d_learn_part{nullptr};
     size_t                  learn_part_bytes{0};
-    std::vector<hipEvent_t> learn_events;
-    size_t                  learn_timed{0};           // events of the latest timed update (0: it ran untimed)
-    // Deep-Q (okenv_replay_create, okenv_dqn_params): the ring's fields and counter, the push's scratch [snapshot | counts], the update's
-    // constants, the target network's copy, the chunk partials (grown, never shrunk) and the events of the latest timed update
-    bool                    replay_ok{false};
-    uint32_t                replay_flags{0};
-    int32_t                 replay_capacity{0};
-    okenv_replay_ring       replay{};
-    uint64_t               *d_replay_words{nullptr};  // [0] pushed, [1] its value before the latest push
-    uint32_t               *d_replay_counts{nullptr};
+    OkEventLog              learn_log;
+    // Deep-Q (okenv_replay_create, okenv_dqn_params): the ring, the update's constants, the target network's copy, the chunk partials
+    // (grown, never shrunk) and the events of the latest timed update
+    OkRing                  replay{sizeof(int64_t)};
     okenv_dqn_config        dqn{0.99F, 0U, 0, 0U};
     float                  *d_dqn_target{nullptr};
     bool                    dqn_target_set{false};
     uint8_t                *d_dqn_part{nullptr};
     size_t                  dqn_part_bytes{0};
-    std::vector<hipEvent_t> dqn_events;
-    size_t                  dqn_timed{0};
+    OkEventLog              dqn_log;
     // DDPG (okenv_ddpg_create, okenv_ddpg_replay_create): the four networks [actor | critic | actor target | critic target] and the four
-    // moments [actor m | actor v | critic m | critic v], each ddpg_cap floats; the ring's fields and counter, the push's scratch, the
+    // moments [actor m | actor v | critic m | critic v], each ddpg_cap floats; the ring, the
     // update's chunk partials (grown, never shrunk) and timing events.  Nothing here is shared with the actor, the learner or the
     // Deep-Q ring above.
     bool                    ddpg_ok{false}, ddpg_actor_set{false}, ddpg_critic_set{false};
@@ -515,16 +530,10 @@ struct okenv
     float                  *d_ddpg_nets{nullptr}, *d_ddpg_moments{nullptr};
     int64_t                 ddpg_t{0};
     const uint32_t         *ddpg_draw_offset{nullptr};
-    bool                    ddpg_replay_ok{false};
-    uint32_t                ddpg_replay_flags{0};
-    int32_t                 ddpg_replay_capacity{0};
-    okenv_ddpg_ring         ddpg_ring{};
-    uint64_t               *d_ddpg_words{nullptr}; // [0] pushed, [1] its value before the latest push
-    uint32_t               *d_ddpg_counts{nullptr};
+    OkRing                  ddpg_ring{2U * sizeof(float)};
     uint8_t                *d_ddpg_part{nullptr};
     size_t                  ddpg_part_bytes{0};
-    std::vector<hipEvent_t> ddpg_events;
-    size_t                  ddpg_timed{0};
+    OkEventLog              ddpg_log;
 };
 
 struct okenv_track
@@ -1148,6 +1157,231 @@ int copyAny(okenv *h, void *dst, const void *src, const size_t bytes)
     return OKENV_OK;
 }
 
+// A scratch buffer of the handle that grows to 1.5 x what a call needs and never shrinks (the updates' chunk partials, the batch's
+// planes): the old one is freed behind a wait for the stream, since an earlier call may still be working in it.
+int growScratch(okenv *h, uint8_t **ptr, size_t *have, const size_t bytes)
+{
+    if (bytes <= *have)
+        return OKENV_OK;
+    OK_HIP(h, hipStreamSynchronize(h->stream));
+    if (*ptr != nullptr)
+    {
+        h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(*ptr)), h->allocations.end());
+        (void)hipFree(*ptr);
+        *ptr  = nullptr;
+        *have = 0;
+    }
+    uint8_t  *fresh = nullptr;
+    const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
+    if (rc != OKENV_OK)
+        return rc;
+    *ptr  = fresh;
+    *have = bytes + bytes / 2U;
+    return OKENV_OK;
+}
+
+// ---- the event log of an update or a batch: eventsBegin before the first launch, eventsMark behind every launch, eventsSums afterwards ----------
+
+// (With okenv_set_timing off the call runs untimed, and the log says so.)
+int eventsBegin(okenv *h, OkEventLog &log, const size_t launches)
+{
+    log.timed = log.at = 0;
+    log.want  = h->timing ? launches + 1U : 0U;
+    if (log.want == 0U)
+        return OKENV_OK;
+    while (log.events.size() < log.want)
+    {
+        hipEvent_t e = nullptr;
+        OK_HIP(h, hipEventCreate(&e));
+        log.events.push_back(e);
+    }
+    OK_HIP(h, hipEventRecord(log.events[0], h->stream));
+    return OKENV_OK;
+}
+
+// (The log is complete, and eventsSums has something to answer, only once the call's last launch has its event.)
+int eventsMark(okenv *h, OkEventLog &log)
+{
+    if (log.want == 0U)
+        return OKENV_OK;
+    OK_HIP(h, hipEventRecord(log.events[++log.at], h->stream));
+    if (log.at + 1U == log.want)
+        log.timed = log.want;
+    return OKENV_OK;
+}
+
+// out[k]: the device time, in milliseconds, of the launches number k mod period of the latest timed call
+int eventsSums(okenv *h, OkEventLog &log, double *out, const size_t period)
+{
+    OK_HIP(h, hipEventSynchronize(log.events[log.timed - 1U]));
+    for (size_t k = 0; k < period; ++k)
+        out[k] = 0.0;
+    for (size_t k = 0; k + 1U < log.timed; ++k)
+    {
+        float ms = 0.F;
+        OK_HIP(h, hipEventElapsedTime(&ms, log.events[k], log.events[k + 1U]));
+        out[k % period] += ms;
+    }
+    return OKENV_OK;
+}
+
+// ---- the replay rings' entries, behind the exported functions' OK_QUIESCE ---------------------------------------------------------
+
+// Which ring an exported entry works on: its record in the handle, the prefix of its entries' names (for the messages) and the widest
+// fan its learner takes
+struct RingKind
+{
+    OkRing okenv::*ring;
+    const char    *prefix;
+    int            max_rays;
+};
+const RingKind kDqnRing{&okenv::replay, "okenv_replay_", OK_ACTOR_MAX_RAYS}, kDdpgRing{&okenv::ddpg_ring, "okenv_ddpg_replay_", OK_DDPG_MAX_RAYS};
+
+// The record's fields as the public struct of its kind (okenv_replay_ring, okenv_ddpg_ring)
+template <class Ring>
+Ring ringFields(const OkRing &r)
+{
+    Ring o{};
+    o.state      = r.state;
+    o.next_state = r.next_state;
+    o.action     = reinterpret_cast<decltype(o.action)>(r.action);
+    o.reward     = r.reward;
+    o.done       = r.done;
+    return o;
+}
+
+int ringMissing(okenv *h, const RingKind &k, const char *entry)
+{
+    return fail(h, OKENV_ERR_STATE, std::string(k.prefix) + entry + ": call " + k.prefix + "create first");
+}
+
+// lds_kernel: the update's gradient kernel whose dynamic-LDS limit is raised with the ring, or nullptr
+int ringCreate(okenv *h, const RingKind &k, const int32_t capacity, const uint32_t flags, const void *lds_kernel)
+{
+    const std::string name = std::string(k.prefix) + "create: ";
+    if (!h)
+        return fail(h, OKENV_ERR_INVALID, name + "NULL handle");
+    if (const char *why = okReplayCheckCreate(capacity, flags))
+        return fail(h, OKENV_ERR_INVALID, name + why);
+    if (h->shape.R > k.max_rays)
+        return fail(h, OKENV_ERR_INVALID, name + "the fan needs 1 .. " + std::to_string(k.max_rays) + " rays");
+    OkRing &r = h->*k.ring;
+    OK_HIP(h, hipSetDevice(h->device));
+    OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in an earlier ring
+    r.ok = false;
+    void *const old[5] = {r.state, r.next_state, r.action, r.reward, r.done};
+    for (void *q : old)
+        if (q != nullptr)
+        {
+            h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), q), h->allocations.end());
+            (void)hipFree(q);
+        }
+    r.state = r.next_state = r.reward = r.done = nullptr;
+    r.action                                   = nullptr;
+    const size_t C = static_cast<size_t>(capacity), R = static_cast<size_t>(h->shape.R);
+    const size_t blocks = (static_cast<size_t>(h->shape.N) + kReplayThreads - 1U) / kReplayThreads;
+    int          rc = devAlloc(h, &r.state, C * R);
+    if (rc != OKENV_OK || (rc = devAlloc(h, &r.next_state, C * R)) != OKENV_OK || (rc = devAlloc(h, &r.action, C * r.action_bytes)) != OKENV_OK ||
+        (rc = devAlloc(h, &r.reward, C)) != OKENV_OK || (rc = devAlloc(h, &r.done, C)) != OKENV_OK ||
+        (rc = devEnsure(h, &r.d_words, 2)) != OKENV_OK || (rc = devEnsure(h, &r.d_counts, blocks)) != OKENV_OK)
+        return rc;
+    OK_HIP(h, hipMemsetAsync(r.d_words, 0, 2U * sizeof(uint64_t), h->stream));
+    if (lds_kernel != nullptr)
+        OK_HIP(h, hipFuncSetAttribute(lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+    OK_HIP(h, hipStreamSynchronize(h->stream));
+    r.capacity = capacity;
+    r.flags    = flags;
+    r.ok       = true;
+    return OKENV_OK;
+}
+
+int ringReset(okenv *h, const RingKind &k)
+{
+    if (!h || !(h->*k.ring).ok)
+        return ringMissing(h, k, "reset");
+    OK_HIP(h, hipSetDevice(h->device));
+    OK_HIP(h, hipMemsetAsync((h->*k.ring).d_words, 0, 2U * sizeof(uint64_t), h->stream));
+    return OKENV_OK;
+}
+
+// Params: the push kernels' parameter struct of the ring's kind (OkReplayParams, OkDdpgReplayParams); Rec: its record
+template <class Params, class Rec>
+int ringPush(okenv *h, const RingKind &k, const Rec *rec, const float *reward)
+{
+    const std::string name = std::string(k.prefix) + "push: ";
+    if (!h)
+        return fail(h, OKENV_ERR_INVALID, name + "NULL handle");
+    const OkRing &r = h->*k.ring;
+    if (!r.ok)
+        return ringMissing(h, k, "push");
+    if (!rec)
+        return fail(h, OKENV_ERR_INVALID, name + "the record is NULL");
+    if (!rec->state || !rec->action)
+        return fail(h, OKENV_ERR_INVALID, name + "the record needs state and action");
+    if (!rec->alive && (r.flags & OKENV_REPLAY_PUSH_ALL) == 0U)
+        return fail(h, OKENV_ERR_INVALID, name + "the record needs alive (or create the ring with OKENV_REPLAY_PUSH_ALL)");
+    OK_HIP(h, hipSetDevice(h->device));
+    Params p{};
+    p.N        = h->shape.N;
+    p.R        = h->shape.R;
+    p.flags    = r.flags;
+    p.capacity = static_cast<uint64_t>(r.capacity);
+    p.ring     = ringFields<decltype(p.ring)>(r);
+    p.pushed   = r.d_words;
+    p.snapshot = r.d_words + 1;
+    p.counts   = r.d_counts;
+    p.rec      = *rec;
+    p.dist     = h->st.dist;
+    p.crashed  = h->st.crashed;
+    p.reward   = reward;
+    const unsigned blocks = static_cast<unsigned>((h->shape.N + kReplayThreads - 1) / kReplayThreads);
+    hipLaunchKernelGGL(okReplayCountKernel<Params>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+    OK_HIP(h, hipGetLastError());
+    hipLaunchKernelGGL(okReplayScatterKernel<Params>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+    OK_HIP(h, hipGetLastError());
+    return OKENV_OK;
+}
+
+int ringSize(okenv *h, const RingKind &k, int64_t *size, int64_t *pushed)
+{
+    if (!h || !(h->*k.ring).ok)
+        return ringMissing(h, k, "size");
+    const OkRing &r = h->*k.ring;
+    OK_HIP(h, hipSetDevice(h->device));
+    uint64_t word = 0;
+    OK_HIP(h, hipMemcpyAsync(&word, r.d_words, sizeof(word), hipMemcpyDeviceToHost, h->stream));
+    OK_HIP(h, hipStreamSynchronize(h->stream));
+    if (size)
+        *size = static_cast<int64_t>(ok_dqn_size(word, static_cast<uint64_t>(r.capacity)));
+    if (pushed)
+        *pushed = static_cast<int64_t>(word);
+    return OKENV_OK;
+}
+
+template <class Ring>
+int ringGet(okenv *h, const RingKind &k, const Ring *out)
+{
+    if (!h || !out)
+        return fail(h, OKENV_ERR_INVALID, std::string(k.prefix) + "get: NULL argument");
+    const OkRing &r = h->*k.ring;
+    if (!r.ok)
+        return ringMissing(h, k, "get");
+    OK_HIP(h, hipSetDevice(h->device));
+    const size_t C = static_cast<size_t>(r.capacity), R = static_cast<size_t>(h->shape.R);
+    void *const       dst[5]   = {out->state, out->next_state, out->action, out->reward, out->done};
+    const void *const src[5]   = {r.state, r.next_state, r.action, r.reward, r.done};
+    const size_t      bytes[5] = {C * R * sizeof(float), C * R * sizeof(float), C * r.action_bytes, C * sizeof(float), C * sizeof(float)};
+    for (int i = 0; i < 5; ++i)
+        if (dst[i] != nullptr)
+        {
+            const int rc = copyAny(h, dst[i], src[i], bytes[i]);
+            if (rc != OKENV_OK)
+                return rc;
+        }
+    OK_HIP(h, hipStreamSynchronize(h->stream));
+    return OKENV_OK;
+}
+
 // The launch knobs as the environment sets them: the one place that reads them.
 OkKnobs readKnobs()
 {
@@ -1401,15 +1635,9 @@ extern "C"
             (void)hipEventDestroy(e.start);
             (void)hipEventDestroy(e.stop);
         }
-        for (hipEvent_t e : h->batch_events)
-            if (e != nullptr)
+        for (OkEventLog *log : {&h->batch_log, &h->learn_log, &h->dqn_log, &h->ddpg_log})
+            for (hipEvent_t e : log->events)
                 (void)hipEventDestroy(e);
-        for (hipEvent_t e : h->learn_events)
-            (void)hipEventDestroy(e);
-        for (hipEvent_t e : h->dqn_events)
-            (void)hipEventDestroy(e);
-        for (hipEvent_t e : h->ddpg_events)
-            (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
             (void)hipStreamDestroy(h->stream);
         delete h;
@@ -2436,23 +2664,8 @@ extern "C"
         const size_t parts = up(4U * sizeof(double) * static_cast<size_t>(p.N)), part_m = up(sizeof(uint32_t) * static_cast<size_t>(p.N));
         const size_t group = up(sizeof(uint32_t) * static_cast<size_t>(p.groups));
         const size_t bytes = 2U * plane + parts + part_m + group + 256U + 256U;
-        if (bytes > h->batch_bytes)
-        {
-            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in the old one
-            if (h->d_batch != nullptr)
-            {
-                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_batch)), h->allocations.end());
-                (void)hipFree(h->d_batch);
-                h->d_batch     = nullptr;
-                h->batch_bytes = 0;
-            }
-            uint8_t  *fresh = nullptr;
-            const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
-            if (rc != OKENV_OK)
-                return rc;
-            h->d_batch     = fresh;
-            h->batch_bytes = bytes + bytes / 2U;
-        }
+        if (const int rc = growScratch(h, &h->d_batch, &h->batch_bytes, bytes))
+            return rc;
         uint8_t *at = h->d_batch;
         p.g_plane   = out->ret_plane != nullptr ? out->ret_plane : reinterpret_cast<float *>(at);
         p.a_plane   = out->adv_plane != nullptr ? out->adv_plane : reinterpret_cast<float *>(at + plane);
@@ -2467,28 +2680,28 @@ extern "C"
         at += 256U;
         p.count          = reinterpret_cast<int32_t *>(at);
         h->d_batch_count = p.count;
-        h->batch_timed   = h->timing;
-        if (h->timing)
-            for (hipEvent_t &e : h->batch_events)
-                if (e == nullptr)
-                    OK_HIP(h, hipEventCreate(&e));
-        const auto mark = [&](const int k) { return h->timing ? hipEventRecord(h->batch_events[k], h->stream) : hipSuccess; };
         const unsigned bt   = static_cast<unsigned>(params->block_threads != 0 ? params->block_threads : kBatchWalkThreads);
         const unsigned wide = static_cast<unsigned>(p.groups);
-        OK_HIP(h, mark(0));
+        if (const int rc = eventsBegin(h, h->batch_log, 5))
+            return rc;
         if (in->value != nullptr)
             hipLaunchKernelGGL(okBatchWalkKernel<true>, dim3((static_cast<unsigned>(p.N) + bt - 1U) / bt), dim3(bt), 0, h->stream, p);
         else
             hipLaunchKernelGGL(okBatchWalkKernel<false>, dim3((static_cast<unsigned>(p.N) + bt - 1U) / bt), dim3(bt), 0, h->stream, p);
-        OK_HIP(h, mark(1));
+        if (const int rc = eventsMark(h, h->batch_log))
+            return rc;
         hipLaunchKernelGGL(okBatchTreeKernel, dim3(1), dim3(1024), 0, h->stream, p);
-        OK_HIP(h, mark(2));
+        if (const int rc = eventsMark(h, h->batch_log))
+            return rc;
         hipLaunchKernelGGL(okBatchCountKernel, dim3(wide), dim3(kBatchWideThreads), 0, h->stream, p);
-        OK_HIP(h, mark(3));
+        if (const int rc = eventsMark(h, h->batch_log))
+            return rc;
         hipLaunchKernelGGL(okBatchScanKernel, dim3(1), dim3(1024), 0, h->stream, p);
-        OK_HIP(h, mark(4));
+        if (const int rc = eventsMark(h, h->batch_log))
+            return rc;
         hipLaunchKernelGGL(okBatchGatherKernel, dim3(wide), dim3(kBatchWideThreads), 0, h->stream, p);
-        OK_HIP(h, mark(5));
+        if (const int rc = eventsMark(h, h->batch_log))
+            return rc;
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -2511,16 +2724,9 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || !ms5)
             return fail(h, OKENV_ERR_INVALID, "okenv_debug_batch_timing: NULL argument");
-        if (h->d_batch_count == nullptr || !h->batch_timed)
+        if (h->batch_log.timed < 6U)
             return fail(h, OKENV_ERR_STATE, "okenv_debug_batch_timing: no okenv_batch_prepare has run with okenv_set_timing on");
-        OK_HIP(h, hipEventSynchronize(h->batch_events[5]));
-        for (int k = 0; k < 5; ++k)
-        {
-            float ms = 0.F;
-            OK_HIP(h, hipEventElapsedTime(&ms, h->batch_events[k], h->batch_events[k + 1]));
-            ms5[k] = ms;
-        }
-        return OKENV_OK;
+        return eventsSums(h, h->batch_log, ms5, 5);
     }
 
     int okenv_batch_prepare_host(const okenv_batch_params *params, const okenv_batch_input *in, const okenv_batch_output *out, int32_t *count)
@@ -2605,40 +2811,15 @@ extern "C"
         const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
         const size_t c_max = (static_cast<size_t>(std::min(B, M)) + OK_LEARN_CHUNK - 1U) / OK_LEARN_CHUNK;
         const size_t parts = up(sizeof(float) * c_max * static_cast<size_t>(p.cols)), bytes = parts + up(sizeof(uint32_t) * c_max);
-        if (bytes > h->learn_part_bytes)
-        {
-            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in the old one
-            if (h->d_learn_part != nullptr)
-            {
-                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_learn_part)), h->allocations.end());
-                (void)hipFree(h->d_learn_part);
-                h->d_learn_part     = nullptr;
-                h->learn_part_bytes = 0;
-            }
-            uint8_t  *fresh = nullptr;
-            const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
-            if (rc != OKENV_OK)
-                return rc;
-            h->d_learn_part     = fresh;
-            h->learn_part_bytes = bytes + bytes / 2U;
-        }
+        if (const int rc = growScratch(h, &h->d_learn_part, &h->learn_part_bytes, bytes))
+            return rc;
         p.part      = reinterpret_cast<float *>(h->d_learn_part);
         p.part_clip = reinterpret_cast<uint32_t *>(h->d_learn_part + parts);
         const int    per_epoch = okLearnMinibatches(M, B);
         const size_t launches  = 2U * static_cast<size_t>(epochs) * static_cast<size_t>(per_epoch);
-        h->learn_timed = 0;
-        if (h->timing)
-        {
-            while (h->learn_events.size() < launches + 1U)
-            {
-                hipEvent_t e = nullptr;
-                OK_HIP(h, hipEventCreate(&e));
-                h->learn_events.push_back(e);
-            }
-            OK_HIP(h, hipEventRecord(h->learn_events[0], h->stream));
-        }
+        if (const int rc = eventsBegin(h, h->learn_log, launches))
+            return rc;
         const size_t lds = okLearnLdsBytes(p.R, p.H, p.A, p.Hv);
-        size_t       ev  = 0;
         for (int e = 0; e < epochs; ++e)
             for (int k = 0; k < per_epoch; ++k)
             {
@@ -2655,16 +2836,15 @@ extern "C"
                 // is the number of steps the device's moments have taken, and the call reports the error.
                 hipLaunchKernelGGL(okLearnGradKernel, dim3(static_cast<unsigned>(p.C)), dim3(kLearnThreads), lds, h->stream, p);
                 OK_HIP(h, hipGetLastError());
-                if (h->timing)
-                    OK_HIP(h, hipEventRecord(h->learn_events[++ev], h->stream));
+                if (const int rc = eventsMark(h, h->learn_log))
+                    return rc;
                 hipLaunchKernelGGL(okLearnStepKernel, dim3(static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols)),
                                    dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
                 OK_HIP(h, hipGetLastError());
                 h->learn_t += 1;
-                if (h->timing)
-                    OK_HIP(h, hipEventRecord(h->learn_events[++ev], h->stream));
+                if (const int rc = eventsMark(h, h->learn_log))
+                    return rc;
             }
-        h->learn_timed = h->timing ? launches + 1U : 0U;
         return OKENV_OK;
     }
 
@@ -2673,17 +2853,9 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || !ms2)
             return fail(h, OKENV_ERR_INVALID, "okenv_debug_update_timing: NULL argument");
-        if (h->learn_timed < 3U)
+        if (h->learn_log.timed < 3U)
             return fail(h, OKENV_ERR_STATE, "okenv_debug_update_timing: no okenv_ppo_update has run with okenv_set_timing on");
-        OK_HIP(h, hipEventSynchronize(h->learn_events[h->learn_timed - 1U]));
-        ms2[0] = ms2[1] = 0.0;
-        for (size_t k = 0; k + 1U < h->learn_timed; ++k)
-        {
-            float ms = 0.F;
-            OK_HIP(h, hipEventElapsedTime(&ms, h->learn_events[k], h->learn_events[k + 1U]));
-            ms2[k & 1U] += ms;
-        }
-        return OKENV_OK;
+        return eventsSums(h, h->learn_log, ms2, 2);
     }
 
     int okenv_actor_get_params(okenv_t h, float *policy, float *value)
@@ -2752,122 +2924,31 @@ extern "C"
     int okenv_replay_create(okenv_t h, int32_t capacity, uint32_t flags)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_replay_create: NULL handle");
-        if (const char *why = okReplayCheckCreate(capacity, flags))
-            return fail(h, OKENV_ERR_INVALID, std::string("okenv_replay_create: ") + why);
-        if (h->shape.R > OK_ACTOR_MAX_RAYS)
-            return fail(h, OKENV_ERR_INVALID, "okenv_replay_create: the fan needs 1 .. 64 rays");
-        OK_HIP(h, hipSetDevice(h->device));
-        OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in an earlier ring
-        h->replay_ok = false;
-        void *const old[5] = {h->replay.state, h->replay.next_state, h->replay.action, h->replay.reward, h->replay.done};
-        for (void *q : old)
-            if (q != nullptr)
-            {
-                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), q), h->allocations.end());
-                (void)hipFree(q);
-            }
-        h->replay = okenv_replay_ring{};
-        const size_t C = static_cast<size_t>(capacity), R = static_cast<size_t>(h->shape.R);
-        const size_t blocks = (static_cast<size_t>(h->shape.N) + kReplayThreads - 1U) / kReplayThreads;
-        int          rc = devAlloc(h, &h->replay.state, C * R);
-        if (rc != OKENV_OK || (rc = devAlloc(h, &h->replay.next_state, C * R)) != OKENV_OK || (rc = devAlloc(h, &h->replay.action, C)) != OKENV_OK ||
-            (rc = devAlloc(h, &h->replay.reward, C)) != OKENV_OK || (rc = devAlloc(h, &h->replay.done, C)) != OKENV_OK ||
-            (rc = devEnsure(h, &h->d_replay_words, 2)) != OKENV_OK || (rc = devEnsure(h, &h->d_replay_counts, blocks)) != OKENV_OK)
-            return rc;
-        OK_HIP(h, hipMemsetAsync(h->d_replay_words, 0, 2U * sizeof(uint64_t), h->stream));
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDqnGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(kLdsBudget)));
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        h->replay_capacity = capacity;
-        h->replay_flags    = flags;
-        h->replay_ok       = true;
-        return OKENV_OK;
+        return ringCreate(h, kDqnRing, capacity, flags, reinterpret_cast<const void *>(&okDqnGradKernel));
     }
 
     int okenv_replay_reset(okenv_t h)
     {
         OK_QUIESCE(h);
-        if (!h || !h->replay_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_replay_reset: call okenv_replay_create first");
-        OK_HIP(h, hipSetDevice(h->device));
-        OK_HIP(h, hipMemsetAsync(h->d_replay_words, 0, 2U * sizeof(uint64_t), h->stream));
-        return OKENV_OK;
+        return ringReset(h, kDqnRing);
     }
 
     int okenv_replay_push(okenv_t h, const okenv_actor_record *rec, const float *reward)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_replay_push: NULL handle");
-        if (!h->replay_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_replay_push: call okenv_replay_create first");
-        if (!rec)
-            return fail(h, OKENV_ERR_INVALID, "okenv_replay_push: the record is NULL");
-        if (!rec->state || !rec->action)
-            return fail(h, OKENV_ERR_INVALID, "okenv_replay_push: the record needs state and action");
-        if (!rec->alive && (h->replay_flags & OKENV_REPLAY_PUSH_ALL) == 0U)
-            return fail(h, OKENV_ERR_INVALID, "okenv_replay_push: the record needs alive (or create the ring with OKENV_REPLAY_PUSH_ALL)");
-        OK_HIP(h, hipSetDevice(h->device));
-        OkReplayParams p{};
-        p.N        = h->shape.N;
-        p.R        = h->shape.R;
-        p.flags    = h->replay_flags;
-        p.capacity = static_cast<uint64_t>(h->replay_capacity);
-        p.ring     = h->replay;
-        p.pushed   = h->d_replay_words;
-        p.snapshot = h->d_replay_words + 1;
-        p.counts   = h->d_replay_counts;
-        p.rec      = *rec;
-        p.dist     = h->st.dist;
-        p.crashed  = h->st.crashed;
-        p.reward   = reward;
-        const unsigned blocks = static_cast<unsigned>((h->shape.N + kReplayThreads - 1) / kReplayThreads);
-        hipLaunchKernelGGL(okReplayCountKernel<OkReplayParams>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(okReplayScatterKernel<OkReplayParams>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return ringPush<OkReplayParams>(h, kDqnRing, rec, reward);
     }
 
     int okenv_replay_size(okenv_t h, int64_t *size, int64_t *pushed)
     {
         OK_QUIESCE(h);
-        if (!h || !h->replay_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_replay_size: call okenv_replay_create first");
-        OK_HIP(h, hipSetDevice(h->device));
-        uint64_t word = 0;
-        OK_HIP(h, hipMemcpyAsync(&word, h->d_replay_words, sizeof(word), hipMemcpyDeviceToHost, h->stream));
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        if (size)
-            *size = static_cast<int64_t>(ok_dqn_size(word, static_cast<uint64_t>(h->replay_capacity)));
-        if (pushed)
-            *pushed = static_cast<int64_t>(word);
-        return OKENV_OK;
+        return ringSize(h, kDqnRing, size, pushed);
     }
 
     int okenv_replay_get(okenv_t h, const okenv_replay_ring *out)
     {
         OK_QUIESCE(h);
-        if (!h || !out)
-            return fail(h, OKENV_ERR_INVALID, "okenv_replay_get: NULL argument");
-        if (!h->replay_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_replay_get: call okenv_replay_create first");
-        OK_HIP(h, hipSetDevice(h->device));
-        const size_t C = static_cast<size_t>(h->replay_capacity), R = static_cast<size_t>(h->shape.R);
-        void *const       dst[5]   = {out->state, out->next_state, out->action, out->reward, out->done};
-        const void *const src[5]   = {h->replay.state, h->replay.next_state, h->replay.action, h->replay.reward, h->replay.done};
-        const size_t      bytes[5] = {C * R * sizeof(float), C * R * sizeof(float), C * sizeof(int64_t), C * sizeof(float), C * sizeof(float)};
-        for (int k = 0; k < 5; ++k)
-            if (dst[k] != nullptr)
-            {
-                const int rc = copyAny(h, dst[k], src[k], bytes[k]);
-                if (rc != OKENV_OK)
-                    return rc;
-            }
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        return OKENV_OK;
+        return ringGet(h, kDqnRing, out);
     }
 
     int okenv_dqn_sync_target(okenv_t h)
@@ -2921,7 +3002,7 @@ extern "C"
             return fail(h, OKENV_ERR_INVALID, "okenv_dqn_update: NULL handle");
         if (!h->learner_ok || !h->actor_ok)
             return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: call okenv_learner_create first");
-        if (!h->replay_ok)
+        if (!h->replay.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: call okenv_replay_create first");
         if (h->dqn.target_network != 0 && !h->dqn_target_set)
             return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: the target network was never filled (okenv_dqn_sync_target)");
@@ -2936,9 +3017,9 @@ extern "C"
         p.C        = (B + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
         p.Pp       = ok_actor_num_params(p.R, p.H, p.A);
         p.cols     = p.Pp + 1;
-        p.capacity = static_cast<uint64_t>(h->replay_capacity);
-        p.pushed   = h->d_replay_words;
-        p.ring     = h->replay;
+        p.capacity = static_cast<uint64_t>(h->replay.capacity);
+        p.pushed   = h->replay.d_words;
+        p.ring     = ringFields<okenv_replay_ring>(h->replay);
         p.policy   = h->d_actor_policy;
         p.pol_m    = h->d_learn_moments;
         p.pol_v    = h->d_learn_moments + h->learn_cap;
@@ -2951,38 +3032,13 @@ extern "C"
         p.grad_policy = o.grad_policy;
         p.index       = o.index;
         const size_t bytes = sizeof(float) * static_cast<size_t>(p.C) * static_cast<size_t>(p.cols);
-        if (bytes > h->dqn_part_bytes)
-        {
-            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in the old one
-            if (h->d_dqn_part != nullptr)
-            {
-                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_dqn_part)), h->allocations.end());
-                (void)hipFree(h->d_dqn_part);
-                h->d_dqn_part     = nullptr;
-                h->dqn_part_bytes = 0;
-            }
-            uint8_t  *fresh = nullptr;
-            const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
-            if (rc != OKENV_OK)
-                return rc;
-            h->d_dqn_part     = fresh;
-            h->dqn_part_bytes = bytes + bytes / 2U;
-        }
+        if (const int rc = growScratch(h, &h->d_dqn_part, &h->dqn_part_bytes, bytes))
+            return rc;
         p.part = reinterpret_cast<float *>(h->d_dqn_part);
         const size_t launches = 2U * static_cast<size_t>(iterations);
-        h->dqn_timed = 0;
-        if (h->timing)
-        {
-            while (h->dqn_events.size() < launches + 1U)
-            {
-                hipEvent_t e = nullptr;
-                OK_HIP(h, hipEventCreate(&e));
-                h->dqn_events.push_back(e);
-            }
-            OK_HIP(h, hipEventRecord(h->dqn_events[0], h->stream));
-        }
+        if (const int rc = eventsBegin(h, h->dqn_log, launches))
+            return rc;
         const size_t lds = okDqnLdsBytes(p.R, p.H, p.A);
-        size_t       ev  = 0;
         for (int it = 0; it < iterations; ++it)
         {
             p.draw = draw_base + (resample != 0 ? static_cast<uint32_t>(it) : 0U);
@@ -2991,16 +3047,15 @@ extern "C"
             // (the step number advances once both kernels of the iteration are enqueued, as in okenv_ppo_update)
             hipLaunchKernelGGL(okDqnGradKernel, dim3(static_cast<unsigned>(p.C)), dim3(kLearnThreads), lds, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            if (h->timing)
-                OK_HIP(h, hipEventRecord(h->dqn_events[++ev], h->stream));
+            if (const int rc = eventsMark(h, h->dqn_log))
+                return rc;
             hipLaunchKernelGGL(okDqnStepKernel, dim3(static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols)),
                                dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
             OK_HIP(h, hipGetLastError());
             h->learn_t += 1;
-            if (h->timing)
-                OK_HIP(h, hipEventRecord(h->dqn_events[++ev], h->stream));
+            if (const int rc = eventsMark(h, h->dqn_log))
+                return rc;
         }
-        h->dqn_timed = h->timing ? launches + 1U : 0U;
         return OKENV_OK;
     }
 
@@ -3009,17 +3064,9 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || !ms2)
             return fail(h, OKENV_ERR_INVALID, "okenv_debug_dqn_timing: NULL argument");
-        if (h->dqn_timed < 3U)
+        if (h->dqn_log.timed < 3U)
             return fail(h, OKENV_ERR_STATE, "okenv_debug_dqn_timing: no okenv_dqn_update has run with okenv_set_timing on");
-        OK_HIP(h, hipEventSynchronize(h->dqn_events[h->dqn_timed - 1U]));
-        ms2[0] = ms2[1] = 0.0;
-        for (size_t k = 0; k + 1U < h->dqn_timed; ++k)
-        {
-            float ms = 0.F;
-            OK_HIP(h, hipEventElapsedTime(&ms, h->dqn_events[k], h->dqn_events[k + 1U]));
-            ms2[k & 1U] += ms;
-        }
-        return OKENV_OK;
+        return eventsSums(h, h->dqn_log, ms2, 2);
     }
 
     int okenv_replay_push_host(const okenv_replay_ring *ring, int32_t capacity, int32_t num_rays, uint64_t *pushed, uint32_t flags, int32_t n,
@@ -3205,120 +3252,31 @@ extern "C"
     int okenv_ddpg_replay_create(okenv_t h, int32_t capacity, uint32_t flags)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_create: NULL handle");
-        if (const char *why = okReplayCheckCreate(capacity, flags))
-            return fail(h, OKENV_ERR_INVALID, std::string("okenv_ddpg_replay_create: ") + why);
-        if (h->shape.R > OK_DDPG_MAX_RAYS)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_create: the fan needs 1 .. 62 rays");
-        OK_HIP(h, hipSetDevice(h->device));
-        OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in an earlier ring
-        h->ddpg_replay_ok = false;
-        void *const old[5] = {h->ddpg_ring.state, h->ddpg_ring.next_state, h->ddpg_ring.action, h->ddpg_ring.reward, h->ddpg_ring.done};
-        for (void *q : old)
-            if (q != nullptr)
-            {
-                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), q), h->allocations.end());
-                (void)hipFree(q);
-            }
-        h->ddpg_ring = okenv_ddpg_ring{};
-        const size_t C = static_cast<size_t>(capacity), R = static_cast<size_t>(h->shape.R);
-        const size_t blocks = (static_cast<size_t>(h->shape.N) + kReplayThreads - 1U) / kReplayThreads;
-        int          rc = devAlloc(h, &h->ddpg_ring.state, C * R);
-        if (rc != OKENV_OK || (rc = devAlloc(h, &h->ddpg_ring.next_state, C * R)) != OKENV_OK || (rc = devAlloc(h, &h->ddpg_ring.action, 2U * C)) != OKENV_OK ||
-            (rc = devAlloc(h, &h->ddpg_ring.reward, C)) != OKENV_OK || (rc = devAlloc(h, &h->ddpg_ring.done, C)) != OKENV_OK ||
-            (rc = devEnsure(h, &h->d_ddpg_words, 2)) != OKENV_OK || (rc = devEnsure(h, &h->d_ddpg_counts, blocks)) != OKENV_OK)
-            return rc;
-        OK_HIP(h, hipMemsetAsync(h->d_ddpg_words, 0, 2U * sizeof(uint64_t), h->stream));
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        h->ddpg_replay_capacity = capacity;
-        h->ddpg_replay_flags    = flags;
-        h->ddpg_replay_ok       = true;
-        return OKENV_OK;
+        return ringCreate(h, kDdpgRing, capacity, flags, nullptr);
     }
 
     int okenv_ddpg_replay_reset(okenv_t h)
     {
         OK_QUIESCE(h);
-        if (!h || !h->ddpg_replay_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_replay_reset: call okenv_ddpg_replay_create first");
-        OK_HIP(h, hipSetDevice(h->device));
-        OK_HIP(h, hipMemsetAsync(h->d_ddpg_words, 0, 2U * sizeof(uint64_t), h->stream));
-        return OKENV_OK;
+        return ringReset(h, kDdpgRing);
     }
 
     int okenv_ddpg_replay_push(okenv_t h, const okenv_ddpg_record *rec, const float *reward)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_push: NULL handle");
-        if (!h->ddpg_replay_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_replay_push: call okenv_ddpg_replay_create first");
-        if (!rec)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_push: the record is NULL");
-        if (!rec->state || !rec->action)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_push: the record needs state and action");
-        if (!rec->alive && (h->ddpg_replay_flags & OKENV_REPLAY_PUSH_ALL) == 0U)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_push: the record needs alive (or create the ring with OKENV_REPLAY_PUSH_ALL)");
-        OK_HIP(h, hipSetDevice(h->device));
-        OkDdpgReplayParams p{};
-        p.N        = h->shape.N;
-        p.R        = h->shape.R;
-        p.flags    = h->ddpg_replay_flags;
-        p.capacity = static_cast<uint64_t>(h->ddpg_replay_capacity);
-        p.ring     = h->ddpg_ring;
-        p.pushed   = h->d_ddpg_words;
-        p.snapshot = h->d_ddpg_words + 1;
-        p.counts   = h->d_ddpg_counts;
-        p.rec      = *rec;
-        p.dist     = h->st.dist;
-        p.crashed  = h->st.crashed;
-        p.reward   = reward;
-        const unsigned blocks = static_cast<unsigned>((h->shape.N + kReplayThreads - 1) / kReplayThreads);
-        hipLaunchKernelGGL(okReplayCountKernel<OkDdpgReplayParams>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(okReplayScatterKernel<OkDdpgReplayParams>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return ringPush<OkDdpgReplayParams>(h, kDdpgRing, rec, reward);
     }
 
     int okenv_ddpg_replay_size(okenv_t h, int64_t *size, int64_t *pushed)
     {
         OK_QUIESCE(h);
-        if (!h || !h->ddpg_replay_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_replay_size: call okenv_ddpg_replay_create first");
-        OK_HIP(h, hipSetDevice(h->device));
-        uint64_t word = 0;
-        OK_HIP(h, hipMemcpyAsync(&word, h->d_ddpg_words, sizeof(word), hipMemcpyDeviceToHost, h->stream));
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        if (size)
-            *size = static_cast<int64_t>(ok_dqn_size(word, static_cast<uint64_t>(h->ddpg_replay_capacity)));
-        if (pushed)
-            *pushed = static_cast<int64_t>(word);
-        return OKENV_OK;
+        return ringSize(h, kDdpgRing, size, pushed);
     }
 
     int okenv_ddpg_replay_get(okenv_t h, const okenv_ddpg_ring *out)
     {
         OK_QUIESCE(h);
-        if (!h || !out)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_replay_get: NULL argument");
-        if (!h->ddpg_replay_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_replay_get: call okenv_ddpg_replay_create first");
-        OK_HIP(h, hipSetDevice(h->device));
-        const size_t C = static_cast<size_t>(h->ddpg_replay_capacity), R = static_cast<size_t>(h->shape.R);
-        void *const       dst[5]   = {out->state, out->next_state, out->action, out->reward, out->done};
-        const void *const src[5]   = {h->ddpg_ring.state, h->ddpg_ring.next_state, h->ddpg_ring.action, h->ddpg_ring.reward, h->ddpg_ring.done};
-        const size_t      bytes[5] = {C * R * sizeof(float), C * R * sizeof(float), 2U * C * sizeof(float), C * sizeof(float), C * sizeof(float)};
-        for (int k = 0; k < 5; ++k)
-            if (dst[k] != nullptr)
-            {
-                const int rc = copyAny(h, dst[k], src[k], bytes[k]);
-                if (rc != OKENV_OK)
-                    return rc;
-            }
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        return OKENV_OK;
+        return ringGet(h, kDdpgRing, out);
     }
 
     int okenv_ddpg_update(okenv_t h, int32_t B, int32_t iterations, int32_t resample, uint32_t draw_base, const okenv_ddpg_output *out)
@@ -3330,7 +3288,7 @@ extern "C"
             return fail(h, OKENV_ERR_STATE, "okenv_ddpg_update: call okenv_ddpg_create first");
         if (!h->ddpg_actor_set || !h->ddpg_critic_set)
             return fail(h, OKENV_ERR_STATE, "okenv_ddpg_update: both networks need their parameters first (okenv_ddpg_set_params)");
-        if (!h->ddpg_replay_ok)
+        if (!h->ddpg_ring.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_ddpg_update: call okenv_ddpg_replay_create first");
         if (B < 1 || iterations < 1)
             return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_update: B and iterations must be at least 1");
@@ -3343,9 +3301,9 @@ extern "C"
         p.C        = (B + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
         p.Pa       = ok_actor_num_params(p.R, p.H, 2);
         p.Pc       = ok_ddpg_critic_params(p.R, p.Hc);
-        p.capacity = static_cast<uint64_t>(h->ddpg_replay_capacity);
-        p.pushed   = h->d_ddpg_words;
-        p.ring     = h->ddpg_ring;
+        p.capacity = static_cast<uint64_t>(h->ddpg_ring.capacity);
+        p.pushed   = h->ddpg_ring.d_words;
+        p.ring     = ringFields<okenv_ddpg_ring>(h->ddpg_ring);
         p.actor    = h->d_ddpg_nets;
         p.critic   = h->d_ddpg_nets + h->ddpg_cap;
         p.actor_t  = h->d_ddpg_nets + 2U * h->ddpg_cap;
@@ -3369,41 +3327,15 @@ extern "C"
         p.grad_actor  = o.grad_actor;
         p.index       = o.index;
         const size_t bytes = sizeof(float) * static_cast<size_t>(p.C) * (static_cast<size_t>(std::max(p.Pa, p.Pc)) + 1U);
-        if (bytes > h->ddpg_part_bytes)
-        {
-            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in the old one
-            if (h->d_ddpg_part != nullptr)
-            {
-                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_ddpg_part)), h->allocations.end());
-                (void)hipFree(h->d_ddpg_part);
-                h->d_ddpg_part     = nullptr;
-                h->ddpg_part_bytes = 0;
-            }
-            uint8_t  *fresh = nullptr;
-            const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
-            if (rc != OKENV_OK)
-                return rc;
-            h->d_ddpg_part     = fresh;
-            h->ddpg_part_bytes = bytes + bytes / 2U;
-        }
+        if (const int rc = growScratch(h, &h->d_ddpg_part, &h->ddpg_part_bytes, bytes))
+            return rc;
         p.part = reinterpret_cast<float *>(h->d_ddpg_part);
         const size_t launches = 4U * static_cast<size_t>(iterations);
-        h->ddpg_timed = 0;
-        if (h->timing)
-        {
-            while (h->ddpg_events.size() < launches + 1U)
-            {
-                hipEvent_t e = nullptr;
-                OK_HIP(h, hipEventCreate(&e));
-                h->ddpg_events.push_back(e);
-            }
-            OK_HIP(h, hipEventRecord(h->ddpg_events[0], h->stream));
-        }
+        if (const int rc = eventsBegin(h, h->ddpg_log, launches))
+            return rc;
         const size_t   lds = okDdpgLdsBytes(p.R, p.H, p.Hc);
         const unsigned chunks = static_cast<unsigned>(p.C), step_threads = kLearnStepCols * kLearnStepRows;
         const unsigned cols_c = static_cast<unsigned>((p.Pc + 1 + kLearnStepCols - 1) / kLearnStepCols), cols_a = static_cast<unsigned>((p.Pa + 1 + kLearnStepCols - 1) / kLearnStepCols);
-        size_t         ev  = 0;
-        const auto     mark = [&]() { return h->timing ? hipEventRecord(h->ddpg_events[++ev], h->stream) : hipSuccess; };
         for (int it = 0; it < iterations; ++it)
         {
             p.draw        = draw_base + (resample != 0 ? static_cast<uint32_t>(it) : 0U);
@@ -3414,19 +3346,22 @@ extern "C"
             // (the step number advances once all four kernels of the iteration are enqueued, as in okenv_ppo_update)
             hipLaunchKernelGGL(okDdpgCriticGradKernel, dim3(chunks), dim3(kLearnThreads), lds, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            OK_HIP(h, mark());
+            if (const int rc = eventsMark(h, h->ddpg_log))
+                return rc;
             hipLaunchKernelGGL(okDdpgStepKernel<false>, dim3(cols_c), dim3(step_threads), 0, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            OK_HIP(h, mark());
+            if (const int rc = eventsMark(h, h->ddpg_log))
+                return rc;
             hipLaunchKernelGGL(okDdpgActorGradKernel, dim3(chunks), dim3(kLearnThreads), lds, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            OK_HIP(h, mark());
+            if (const int rc = eventsMark(h, h->ddpg_log))
+                return rc;
             hipLaunchKernelGGL(okDdpgStepKernel<true>, dim3(cols_a), dim3(step_threads), 0, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            OK_HIP(h, mark());
+            if (const int rc = eventsMark(h, h->ddpg_log))
+                return rc;
             h->ddpg_t += 1;
         }
-        h->ddpg_timed = h->timing ? launches + 1U : 0U;
         return OKENV_OK;
     }
 
@@ -3435,17 +3370,9 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || !ms4)
             return fail(h, OKENV_ERR_INVALID, "okenv_debug_ddpg_timing: NULL argument");
-        if (h->ddpg_timed < 5U)
+        if (h->ddpg_log.timed < 5U)
             return fail(h, OKENV_ERR_STATE, "okenv_debug_ddpg_timing: no okenv_ddpg_update has run with okenv_set_timing on");
-        OK_HIP(h, hipEventSynchronize(h->ddpg_events[h->ddpg_timed - 1U]));
-        ms4[0] = ms4[1] = ms4[2] = ms4[3] = 0.0;
-        for (size_t k = 0; k + 1U < h->ddpg_timed; ++k)
-        {
-            float ms = 0.F;
-            OK_HIP(h, hipEventElapsedTime(&ms, h->ddpg_events[k], h->ddpg_events[k + 1U]));
-            ms4[k & 3U] += ms;
-        }
-        return OKENV_OK;
+        return eventsSums(h, h->ddpg_log, ms4, 4);
     }
 
     int okenv_ddpg_act_host(const okenv_ddpg_config *config, const float *actor, int32_t num_rays, int32_t n, const float *dist, const uint8_t *crashed,
@@ -3465,7 +3392,7 @@ extern "C"
     {
         if (const char *why = okReplayCheckCreate(capacity, flags))
             return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_ddpg_replay_push_host: ") + why);
-        if (!okDdpgRingComplete(ring) || !pushed)
+        if (!okReplayRingComplete(ring) || !pushed)
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_replay_push_host: the ring needs every field and its counter");
         if (num_rays < 1 || num_rays > OK_DDPG_MAX_RAYS || n < 0)
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_replay_push_host: the fan needs 1 .. 62 rays and n >= 0");
@@ -3475,7 +3402,7 @@ extern "C"
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_replay_push_host: the record needs alive (or pass OKENV_REPLAY_PUSH_ALL)");
         if (!dist || !crashed)
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_replay_push_host: dist and crashed are required");
-        okDdpgPushHost(*ring, static_cast<uint64_t>(capacity), num_rays, pushed, flags, n, state, action, alive, dist, crashed, reward);
+        okReplayPushHost(*ring, static_cast<uint64_t>(capacity), num_rays, pushed, flags, n, state, action, alive, dist, crashed, reward);
         return OKENV_OK;
     }
 
@@ -3489,7 +3416,7 @@ extern "C"
         if (state == nullptr || state->actor == nullptr || state->critic == nullptr || state->actor_target == nullptr || state->critic_target == nullptr ||
             state->actor_m == nullptr || state->actor_v == nullptr || state->critic_m == nullptr || state->critic_v == nullptr || state->t < 0)
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_update_host: state lacks a parameter or moment vector, or t < 0");
-        if (size < 0 || size >= (INT64_C(1) << 31) || (size > 0 && !okDdpgRingComplete(ring)))
+        if (size < 0 || size >= (INT64_C(1) << 31) || (size > 0 && !okReplayRingComplete(ring)))
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_ddpg_update_host: size outside 0 .. 2^31 - 1, or a ring without every field");
         const okenv_ddpg_output none{};
         const okenv_ddpg_ring   empty{};

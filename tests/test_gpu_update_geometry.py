@@ -1,7 +1,7 @@
 """The learners' device kernels at the edges of their launch geometry (openkitchen_amd/csrc/ok_learn.h, ok_dqn.h, ok_ddpg.h): every
 chunk count 1 .. 130 of the tree the three step kernels share (okLearnColumnSum), the same tree at the widths the examples run,
-calls of different B on one handle (the partials' buffer grows and is reused while larger than needed), and pushes over more than
-256 workgroups (okReplayScatterKernel's count loop).  Everything is compared bit for bit with the host entries, whose own link to
+calls of different B on one handle (the partials' buffer grows and is reused while larger than needed), pushes over more than
+256 workgroups (okReplayScatterKernel's count loop), and Deep-Q's ring and DDPG's on one handle.  Everything is compared bit for bit with the host entries, whose own link to
 the numpy restatements at these B is in tests/test_learn_rule.py, test_dqn_rule.py and test_ddpg_rule.py."""
 import numpy as np
 import pytest
@@ -236,4 +236,40 @@ def test_push_over_more_than_256_workgroups(gpu, learner):
             what = (learner, capacity, mask, push_all, own_reward)
             assert host["pushed"] > max(65536, capacity if capacity == 100_000 else 0) and (not push_all or host["pushed"] == 3 * N), what
             M.same_ring(dev, host, what)
+    dev.close()
+
+
+# ---- E: both rings on one handle ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("push_all", [False, True])
+def test_both_rings_on_one_handle(gpu, push_all):
+    """Deep-Q's ring and DDPG's on ONE handle, each with its own counter words and count scratch: N = 300 agents (two workgroups of
+    the push kernels, the second partly live), R = 5, both rings of capacity 257, so that the second push of each wraps (with
+    push-all the first one already drops its 43 oldest transitions).  The pushes alternate Deep-Q, DDPG, Deep-Q, DDPG, each after
+    an act of its own learner and a step, so the recorded actions differ (an index / two floats) and so do the states of the four
+    pushes.  Without push-all `alive` selects about half the agents (crashed_ is set to a fresh mask of 45 % before every act, so
+    two pushes of about 165 transitions pass 257 with room for the agents that crash in the step between).  Every field and (size, pushed) of both rings against the host entries' rings after every push: a ring that took the
+    other's counter, snapshot or counts shows in its slots at once."""
+    N, R, capacity = 300, 5, 257
+    dev, _ = Q.make_env(gpu, N, R, 16, 5, seed=21)
+    assert dev.ddpg_create(16, 8, **dict(G.CFG, noise=(10.0, 1.0))) == (G.n_actor(R, 16), G.n_critic(R, 8))
+    rng = np.random.default_rng(21)
+    dev.ddpg_set_params((rng.standard_normal(G.n_actor(R, 16)) * 0.3).astype(f32), (rng.standard_normal(G.n_critic(R, 8)) * 0.3).astype(f32))
+    dev.replay_create(capacity, push_all)
+    dev.ddpg_replay_create(capacity, push_all)
+    host_q, host_g = gpu.replay_ring(capacity, R), gpu.ddpg_ring(capacity, R)
+    rec_q, rec_g = Q.record_tensors(N, R), G.record_tensors(N, R)
+    for push in range(2):
+        dev.set(gpu.capi.F_CRASHED, (rng.random(N) < 0.45).astype(np.uint8))
+        Q.act_step_push(gpu, dev, rec_q, host_q, None, push_all)
+        Q.same_ring(dev, host_q, ("dqn", push, push_all))
+        G.same_ring(dev, host_g, ("ddpg before its push", push, push_all))
+        dev.set(gpu.capi.F_CRASHED, (rng.random(N) < 0.45).astype(np.uint8))
+        G.act_step_push(gpu, dev, rec_g, host_g, None, push_all)
+        G.same_ring(dev, host_g, ("ddpg", push, push_all))
+        Q.same_ring(dev, host_q, ("dqn after ddpg's push", push, push_all))
+    for host in (host_q, host_g):
+        assert host["pushed"] > capacity and (not push_all or host["pushed"] == 2 * N), (host["pushed"], push_all)
+    if not push_all:  # about half: neither nobody nor everybody
+        assert N // 2 < host_q["pushed"] < 2 * N - N // 2, host_q["pushed"]
     dev.close()
