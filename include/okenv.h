@@ -478,6 +478,66 @@ OKENV_API int okenv_actor_get_params(okenv_t h, float *policy, float *value);
 /* The learner's moments to host or device pointers (each may be NULL) and its step number; synchronises. */
 OKENV_API int okenv_learner_get_state(okenv_t h, float *policy_m, float *policy_v, float *value_m, float *value_v, int64_t *t);
 
+/* ---- REINFORCE: the dropout actor and the whole-episode update --------------------------------------------
+ * The reference's REINFORCE network as it is (RLRacers/Reinforce/Policy.hpp:22-29: Dropout between the first affine layer and the
+ * ReLU, active while acting and in the update) and updatePolicy of ReinforceAgent.hpp:91-123 on the batch okenv_batch_prepare leaves:
+ * loss = sum of -log p(a) * G over the episode's samples, its gradient through the masked network, one Adam step, in place in the
+ * parameters okenv_actor_act reads.  The rule, with its Philox layout and summation order, is written out in
+ * include/okenv_reinforce.h (ok_reinforce_*). */
+#define OKENV_REINFORCE_SUM 0  /* loss and gradient are sums over the samples (the reference's loss +=) */
+#define OKENV_REINFORCE_MEAN 1 /* each divided once by the number of samples of the step                */
+
+/* Dropout with probability p on the hidden layer of the handle's POLICY network (never the value network), masks keyed by `seed`,
+ * the global agent id and the draw index: okenv_actor_act then runs its dropout instantiation, and okenv_reinforce_update
+ * regenerates every sample's mask.  The default is off (p = 0), and okenv_actor_create switches it off again.  While p > 0
+ * okenv_ppo_update and okenv_dqn_update return OKENV_ERR_STATE: their forwards know no mask.  A captured okenv_actor_act carries p
+ * and the seed by value.  OKENV_ERR_INVALID for a NULL handle, p outside [0, 1) or NaN, OKENV_ERR_STATE before
+ * okenv_actor_create. */
+OKENV_API int okenv_actor_set_dropout(okenv_t h, float p, uint32_t seed);
+/* okenv_actor_act_host with dropout (p, dropout_seed); p == 0 is okenv_actor_act_host, bit for bit.  No GPU needed. */
+OKENV_API int okenv_actor_act_dropout_host(const okenv_actor_params *params, float p, uint32_t dropout_seed, const float *policy, const float *value,
+                                           int32_t num_rays, int32_t n, const float *dist, const uint8_t *crashed, uint32_t draw_index,
+                                           float *throttle, float *steer, int64_t *action, float *prob, float *value_out, float *state,
+                                           uint8_t *alive);
+
+typedef struct okenv_reinforce_config {
+    int32_t  accumulate; /* non-zero: ONE optimiser step per call, on the gradient of all M samples (the reference);
+                            0: one step per slice of B samples (minibatch REINFORCE)                                   */
+    int32_t  reduce;     /* OKENV_REINFORCE_SUM | _MEAN                                                                */
+    int32_t  num_agents; /* N of the record the batch was cut from: sample index = row * N + agent (read with dropout) */
+    uint32_t draw_first; /* the actor's draw index of the record's row 0 (read with dropout)                           */
+} okenv_reinforce_config;
+
+/* The training set: device pointers (host pointers for okenv_reinforce_update_host). */
+typedef struct okenv_reinforce_batch {
+    const float   *state;  /* [M][R]                                                                               */
+    const int64_t *action; /* [M]                                                                                  */
+    const float   *ret;    /* [M]  the (normalised) return G                                                       */
+    const int32_t *index;  /* [M]  row * N + agent, as okenv_batch_prepare writes it; may be NULL while dropout is off */
+} okenv_reinforce_batch;
+
+/* Where the update reports: device pointers (host pointers for okenv_reinforce_update_host), each may be NULL (skipped). */
+typedef struct okenv_reinforce_output {
+    float *loss;        /* one value per optimiser step: 1 when accumulating, else ceil(M / B) */
+    float *grad_policy; /* the last step's gradient, in parameter order                        */
+} okenv_reinforce_output;
+
+/* Enqueues the update on the handle's stream: the M samples in ceil(M / B) slices of B, two kernels per slice (gradient partials per
+ * chunk; join + accumulate, or join + Adam), no synchronisation, and no allocation after the first call of a given min(B, M).  B only
+ * bounds the scratch when accumulating: the sums' order, and so the result's bits, depend on it.  `order` is a device array [M] of
+ * int32 sample indices or NULL (sequential).  The learner is the handle's (okenv_learner_create: lr, the betas and eps are read, clip
+ * is not; t, m and v continue); the next okenv_actor_act uses the new parameters.
+ * OKENV_ERR_STATE before okenv_learner_create; OKENV_ERR_INVALID for a NULL handle, config, batch, state, action or ret, M or B < 1, an
+ * unknown reduce and, with dropout on, a NULL index or num_agents < 1. */
+OKENV_API int okenv_reinforce_update(okenv_t h, const okenv_reinforce_config *config, const okenv_reinforce_batch *batch, int32_t M, int32_t B,
+                                     const int32_t *order, const okenv_reinforce_output *out);
+/* The same rule on host arrays, no GPU needed: network num_rays -> hidden -> num_actions, dropout (p, dropout_seed) with global agent
+ * ids agent_base + index mod num_agents; of `state` the policy's members and t are read and written. */
+OKENV_API int okenv_reinforce_update_host(const okenv_learner_params *params, const okenv_reinforce_config *config, float p, uint32_t dropout_seed,
+                                          uint32_t agent_base, int32_t num_rays, int32_t hidden, int32_t num_actions, okenv_learner_state *state,
+                                          const okenv_reinforce_batch *batch, int32_t M, int32_t B, const int32_t *order,
+                                          const okenv_reinforce_output *out);
+
 /* ---- Deep-Q learning: replay ring, sampling and the temporal-difference update ---------------------------
  * The learning side of RLRacers/Deep_Q_Learning (dq_racer_sim.cpp:81-132, DQAgent.hpp:106-181, common/ReplayBuffer.hpp) for the
  * handle's OKENV_ACTOR_EPS_GREEDY actor: a ring of transitions that persists across episodes on the device, filled by one push per
@@ -932,6 +992,10 @@ OKENV_API int okenv_debug_atan2f(const float *y, const float *x, float *out, int
 OKENV_API int okenv_debug_expert_normalize_angle(const float *angle_deg, float *out, int32_t n);
 /* ok_expf (the actors' softmax) on a host array; host only, no GPU. */
 OKENV_API int okenv_debug_expf(const float *x, float *out, int32_t n);
+/* ok_logf of okenv_math.h for n positive finite arguments (host evaluation) */
+OKENV_API int okenv_debug_logf(const float *x, float *out, int32_t n);
+/* REINFORCE's dropout mask of hidden units 0 .. hidden-1 for (p, seed, global agent id, draw index): 1 kept, 0 dropped (host) */
+OKENV_API int okenv_debug_reinforce_mask(float p, uint32_t seed, uint32_t agent, uint32_t draw, int32_t hidden, uint8_t *out);
 /* Device milliseconds of the five kernels of the handle's latest okenv_batch_prepare (walk, tree, count, scan, gather), from events
  * it records between them while okenv_set_timing is on; waits for the last one.  OKENV_ERR_STATE when that call ran untimed. */
 OKENV_API int okenv_debug_batch_timing(okenv_t h, double *ms5);
@@ -943,6 +1007,8 @@ OKENV_API int okenv_debug_update_timing(okenv_t h, double *ms2);
 OKENV_API int okenv_debug_dqn_timing(okenv_t h, double *ms2);
 /* The same for the handle's latest okenv_ddpg_update: critic gradient, critic step, actor gradient, actor step. */
 OKENV_API int okenv_debug_ddpg_timing(okenv_t h, double *ms4);
+/* of the latest okenv_reinforce_update likewise: [0] gradient kernels, [1] join kernels (accumulate and Adam), summed over the slices */
+OKENV_API int okenv_debug_reinforce_timing(okenv_t h, double *ms2);
 /* ok_learn_adam (include/okenv_learn.h) on host arrays: step number t >= 1 of n parameters p with moments m, v and gradients g, all
  * updated in place; host only, no GPU. */
 OKENV_API int okenv_debug_adam(const okenv_learner_params *params, int64_t t, float *p, float *m, float *v, const float *g, int32_t n);

@@ -476,9 +476,47 @@ OK_HD float ok_expf(const float x)
     return (float)(two_n.d * (1.0 + m));
 }
 
+/* log for REINFORCE's loss column (okenv_reinforce.h), for positive finite fp32 arguments, subnormal ones included: evaluated in fp64
+ * and rounded once to fp32.  x = 2^e m with m in [sqrt(1/2), sqrt(2)) (the double's own exponent and mantissa, halved once where the
+ * mantissa reaches sqrt 2), u = (m - 1) / (m + 1), |u| <= 0.1716, log m = 2 atanh u = 2 (u + u^3/3 + u^5/5 + ...): the series' own
+ * coefficients 1/(2k + 1), each the correctly rounded quotient of two small integers, up to u^23 (the first term left out is below
+ * 2^-59 of the sum), by Horner's rule in FMAs in z = u^2.  Then e ln 2 with ok_expf's split ln 2 = L1 + L2, the small part first.
+ * Zero, negative, infinite and NaN arguments are not the loss's business (the probability is clamped to [1e-8, 1]) and nothing
+ * tests them.  tests/test_reinforce_rule.py: equal to the rounded fp64 log on all but a few of a million arguments in [1e-8, 1] and
+ * on every binade of the positive normal floats, never more than one ulp away.  No gradient depends on it. */
+OK_HD float ok_logf(const float x)
+{
+    union { uint64_t u; double d; } b;
+    b.d = (double)x; /* exact, and a normal double for every positive fp32 number */
+    double e = (double)((int)(b.u >> 52) - 1023);
+    b.u = (b.u & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull; /* the mantissa as a double in [1, 2) */
+    double m = b.d;
+    if (m >= 0x1.6a09e667f3bcdp+0) { /* sqrt 2 */
+        m = m * 0.5;
+        e = e + 1.0;
+    }
+    const double u = (m - 1.0) / (m + 1.0);
+    const double z = u * u;
+    double p = ok_konst(1.0 / 23.0);
+    p = OK_FMA(p, z, ok_konst(1.0 / 21.0));
+    p = OK_FMA(p, z, ok_konst(1.0 / 19.0));
+    p = OK_FMA(p, z, ok_konst(1.0 / 17.0));
+    p = OK_FMA(p, z, ok_konst(1.0 / 15.0));
+    p = OK_FMA(p, z, ok_konst(1.0 / 13.0));
+    p = OK_FMA(p, z, ok_konst(1.0 / 11.0));
+    p = OK_FMA(p, z, ok_konst(1.0 / 9.0));
+    p = OK_FMA(p, z, ok_konst(1.0 / 7.0));
+    p = OK_FMA(p, z, ok_konst(1.0 / 5.0));
+    p = OK_FMA(p, z, ok_konst(1.0 / 3.0));
+    const double log_m = 2.0 * OK_FMA(u * z, p, u);
+    double r = OK_FMA(e, ok_konst(0x1.abc9e3b39803fp-56), log_m); /* L2 = 2.3190468138462996e-17 */
+    r = OK_FMA(e, ok_konst(0x1.62e42fefa39efp-1), r);             /* L1 = 0.6931471805599453     */
+    return (float)r;
+}
+
 /* ---- RLRacers: the shared-network actors -----------------------------------
  * updateAction of PPOAgent (RLRacers/PPO/PPOAgent.hpp:68-102 with Actor.hpp:20-27 and Critic.hpp), of the REINFORCE agent
- * (Reinforce/Policy.hpp:22-29, without its Dropout) and of DQAgent (Deep_Q_Learning/DQAgent.hpp:85-104, with one hidden layer): ONE
+ * (Reinforce/Policy.hpp:22-29; its Dropout is okenv_reinforce.h's, on top of this rule) and of DQAgent (Deep_Q_Learning/DQAgent.hpp:85-104, with one hidden layer): ONE
  * network for all agents, an action index per agent, a table from index to (throttle_delta, steering_delta).  libtorch's summation
  * order, its softmax and its multinomial are not pinned, so the rule is written out here; csrc/ok_actor.h's kernel and
  * okenv_actor_act_host both evaluate THESE functions, so they agree bit for bit.
@@ -503,7 +541,8 @@ OK_HD float ok_expf(const float x)
  *             A NaN p_k stays NaN (both comparisons are false).
  *   draws     one Philox block per (seed, global agent id, draw index): counter = (agent, draw, 6, 0), key = (seed, "oken").
  *             Stream 6 is used by nothing else (0: C2 actions, 1: resets and GA weights, 2 / 3: GA mating, 4: Q-learning, 5:
- *             q_racer_sim's episode draws; 7: Deep-Q's sampling, okenv_dqn.h; 8: DDPG's exploration, okenv_ddpg.h).
+ *             q_racer_sim's episode draws; 7: Deep-Q's sampling, okenv_dqn.h; 8: DDPG's exploration, okenv_ddpg.h; 9: REINFORCE's
+ *             dropout masks, okenv_reinforce.h).
  *   modes     OK_ACTOR_SAMPLE (PPO, REINFORCE): u = ok_u01(word 0); the action is the first k with u < p_0 + ... + p_k (fp32
  *             sums of the clamped p, ascending), A - 1 if there is none.  Recorded: the clamped p of the action.
  *             OK_ACTOR_GREEDY (evaluation): the arg-max of z, lowest index on ties.  Recorded: the clamped p of the action.

@@ -45,6 +45,10 @@ BATCH_KERNELS = ("walk", "tree", "count", "scan", "gather")
 # PPO's update (include/okenv.h)
 UPDATE_KERNELS = ("grad", "step")
 LEARN_CHUNK = 32
+# REINFORCE (include/okenv.h)
+REINFORCE_SUM, REINFORCE_MEAN = 0, 1
+REINFORCE_REDUCE = {"sum": REINFORCE_SUM, "mean": REINFORCE_MEAN}
+REINFORCE_KERNELS = ("grad", "step")
 
 # every symbol include/okenv.h declares (tests/test_capi_symbols.py checks the library exports them all)
 SYMBOLS = [
@@ -80,6 +84,8 @@ SYMBOLS = [
     "okenv_ddpg_act", "okenv_ddpg_replay_create", "okenv_ddpg_replay_reset", "okenv_ddpg_replay_push", "okenv_ddpg_replay_size",
     "okenv_ddpg_replay_get", "okenv_ddpg_update", "okenv_debug_ddpg_timing", "okenv_ddpg_act_host", "okenv_ddpg_replay_push_host",
     "okenv_ddpg_update_host",
+    "okenv_actor_set_dropout", "okenv_actor_act_dropout_host", "okenv_reinforce_update", "okenv_reinforce_update_host",
+    "okenv_debug_reinforce_timing", "okenv_debug_logf", "okenv_debug_reinforce_mask",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -192,6 +198,25 @@ class OkenvLearnerState(C.Structure):
 def learner_params(lr=3e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8):
     """okenv_learner_params with the reference's learning rate and clip (PPOAgent.hpp:24-26) and torch.optim.Adam's defaults."""
     return OkenvLearnerParams(float(lr), float(clip), float(beta1), float(beta2), float(eps))
+
+
+class OkenvReinforceConfig(C.Structure):
+    _fields_ = [("accumulate", C.c_int32), ("reduce", C.c_int32), ("num_agents", C.c_int32), ("draw_first", C.c_uint32)]
+
+
+class OkenvReinforceBatch(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("action", C.c_void_p), ("ret", C.c_void_p), ("index", C.c_void_p)]
+
+
+class OkenvReinforceOutput(C.Structure):
+    _fields_ = [("loss", C.c_void_p), ("grad_policy", C.c_void_p)]
+
+
+def reinforce_config(accumulate=True, reduce="sum", num_agents=0, draw_first=0):
+    """okenv_reinforce_config with the reference's choices as defaults (ReinforceAgent.hpp:109-118: one step on the summed loss);
+    reduce: "sum" / "mean" or the integer."""
+    return OkenvReinforceConfig(1 if accumulate else 0, REINFORCE_REDUCE[reduce] if isinstance(reduce, str) else int(reduce), int(num_agents),
+                                int(draw_first) & 0xFFFFFFFF)
 
 
 REPLAY_PUSH_ALL = 1  # OKENV_REPLAY_PUSH_ALL
@@ -478,6 +503,16 @@ def load(build_if_missing=True):
     L.okenv_ddpg_replay_push_host.argtypes = [C.POINTER(OkenvDdpgRing), i32, i32, C.POINTER(C.c_uint64), u32, i32, vp, vp, vp, vp, vp, vp]
     L.okenv_ddpg_update_host.argtypes = [C.POINTER(OkenvDdpgConfig), i32, C.POINTER(OkenvDdpgState), C.POINTER(OkenvDdpgRing), C.c_int64, i32, i32, i32,
                                          u32, C.POINTER(OkenvDdpgOutput)]
+    L.okenv_actor_set_dropout.argtypes = [vp, f32, u32]
+    L.okenv_actor_act_dropout_host.argtypes = [C.POINTER(OkenvActorParams), f32, u32, vp, vp, i32, i32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.okenv_reinforce_update.argtypes = [vp, C.POINTER(OkenvReinforceConfig), C.POINTER(OkenvReinforceBatch), i32, i32, vp,
+                                         C.POINTER(OkenvReinforceOutput)]
+    L.okenv_reinforce_update_host.argtypes = [C.POINTER(OkenvLearnerParams), C.POINTER(OkenvReinforceConfig), f32, u32, u32, i32, i32, i32,
+                                              C.POINTER(OkenvLearnerState), C.POINTER(OkenvReinforceBatch), i32, i32, vp,
+                                              C.POINTER(OkenvReinforceOutput)]
+    L.okenv_debug_reinforce_timing.argtypes = [vp, vp]
+    L.okenv_debug_logf.argtypes = [vp, vp, i32]
+    L.okenv_debug_reinforce_mask.argtypes = [f32, u32, u32, u32, i32, vp]
     _lib = L
     return L
 

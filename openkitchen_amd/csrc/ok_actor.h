@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/okenv.h"
+#include "../../include/okenv_reinforce.h"
 #include "okenv_kernels.h"
 
 // What the kernel needs, by value
@@ -24,6 +25,7 @@ struct OkActorParams
     const uint32_t    *draw_offset;     // okenv_actor_set_draw_offset, or nullptr
     okenv_actor_params ap;
     okenv_actor_record rec;
+    ok_reinforce_mask  drop; // okenv_actor_set_dropout: p, its scale and the seed (agent and draw are the kernel's to fill in)
 };
 
 // Lanes per agent = the rule's interleave (OK_ACTOR_LANES): lane l of a group owns the hidden units l, l + 8, ... of both networks
@@ -103,8 +105,28 @@ __device__ __forceinline__ void okActorForward(const float *net, const int R, co
     }
 }
 
+// okActorForward with REINFORCE's dropout mask `m` on the hidden layer (okenv_reinforce.h): every lane evaluates the Philox blocks of
+// its own units
+__device__ __forceinline__ void okActorForwardDropout(const float *net, const int R, const int hidden, const int out, const float *x, const int lane,
+                                                      const ok_reinforce_mask m, float *z)
+{
+    const int rp = okActorRowStride(R);
+    float     part[OK_ACTOR_MAX_ACTIONS];
+    ok_reinforce_partial(net, rp, net + hidden * rp, net + hidden * rp + hidden, R, hidden, out, x, lane, m, part);
+    const float *b2 = net + hidden * rp + hidden + out * hidden;
+#pragma unroll
+    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+    {
+        z[k] = 0.F;
+        if (k < out)
+            z[k] = b2[k] + okActorJoinLanes(part[k]);
+    }
+}
+
 extern __shared__ float ok_actor_lds[];
 
+// Dropout: the policy network's hidden layer is masked (okenv_actor_set_dropout with p > 0); false is section 14's kernel as it was
+template <bool Dropout>
 __global__ __launch_bounds__(kActorThreads) void okActorKernel(const OkActorParams p)
 {
     const int R = p.R, H = p.ap.hidden, A = p.ap.num_actions, Hv = p.ap.value_hidden, rp = okActorRowStride(R);
@@ -128,7 +150,15 @@ __global__ __launch_bounds__(kActorThreads) void okActorKernel(const OkActorPara
     }
     __syncthreads();
     float z[OK_ACTOR_MAX_ACTIONS], zv[OK_ACTOR_MAX_ACTIONS];
-    okActorForward(pol, R, H, A, x, lane, z);
+    if constexpr (Dropout)
+    { // the mask belongs to the agent and the draw index the action draw below uses
+        ok_reinforce_mask m = p.drop;
+        m.agent             = p.ap.agent_base + static_cast<uint32_t>(a);
+        m.draw              = (p.step_word != nullptr ? p.step_word[0] : p.host_steps) + (p.draw_offset != nullptr ? p.draw_offset[0] : 0U);
+        okActorForwardDropout(pol, R, H, A, x, lane, m, z);
+    }
+    else
+        okActorForward(pol, R, H, A, x, lane, z);
     float value = 0.F;
     if (Hv > 0)
     {
@@ -228,6 +258,62 @@ inline void okActorActHost(const okenv_actor_params &ap, const float *policy, co
         if (prob != nullptr)
             prob[a] = pr;
         if (value_out != nullptr && ap.value_hidden > 0)
+            value_out[a] = v;
+        if (state != nullptr)
+            for (int i = 0; i < R; ++i)
+                state[static_cast<size_t>(a) * R + i] = x[static_cast<size_t>(i)];
+        if (alive != nullptr)
+            alive[a] = (crashed != nullptr && crashed[a]) ? 0 : 1;
+    }
+}
+
+// The same with REINFORCE's dropout on the policy network's hidden layer (okenv_reinforce.h); p == 0 is okActorActHost
+inline void okActorActDropoutHost(const okenv_actor_params &ap, const float p, const uint32_t dropout_seed, const float *policy, const float *value,
+                                  const int R, const int n, const float *dist, const uint8_t *crashed, const uint32_t draw_index, float *throttle,
+                                  float *steer, int64_t *action, float *prob, float *value_out, float *state, uint8_t *alive)
+{
+    if (!(p > 0.F))
+        return okActorActHost(ap, policy, value, R, n, dist, crashed, draw_index, throttle, steer, action, prob, value_out, state, alive);
+    const int          H = ap.hidden, A = ap.num_actions, Hv = ap.value_hidden;
+    std::vector<float> x(static_cast<size_t>(R));
+    ok_reinforce_mask  m{p, ok_reinforce_scale(p), dropout_seed, 0U, draw_index};
+    const float       *b1 = policy + H * R, *w2 = b1 + H, *b2 = w2 + A * H;
+    for (int a = 0; a < n; ++a)
+    {
+        m.agent = ap.agent_base + static_cast<uint32_t>(a);
+        for (int i = 0; i < R; ++i)
+            x[static_cast<size_t>(i)] = dist[static_cast<size_t>(a) * R + i] / OK_SENSOR_RANGE;
+        float part[OK_ACTOR_LANES][OK_ACTOR_MAX_ACTIONS], col[OK_ACTOR_LANES], z[OK_ACTOR_MAX_ACTIONS];
+        for (int l = 0; l < OK_ACTOR_LANES; ++l)
+            ok_reinforce_partial(policy, R, b1, w2, R, H, A, x.data(), l, m, part[l]);
+        for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+        {
+            for (int l = 0; l < OK_ACTOR_LANES; ++l)
+                col[l] = k < A ? part[l][k] : 0.F;
+            z[k] = k < A ? ok_actor_join(col, b2[k]) : 0.F;
+        }
+        float v = 0.F;
+        if (Hv > 0)
+        {
+            const float *vb1 = value + Hv * R, *vw2 = vb1 + Hv, *vb2 = vw2 + Hv;
+            for (int l = 0; l < OK_ACTOR_LANES; ++l)
+            {
+                ok_actor_partial(value, R, vb1, vw2, R, Hv, 1, x.data(), l, part[l]);
+                col[l] = part[l][0];
+            }
+            v = ok_actor_join(col, vb2[0]);
+        }
+        float     pr  = 0.F;
+        const int act = ok_actor_choose(ap.mode, ap.epsilon, ap.seed, m.agent, draw_index, z, A, &pr);
+        if (throttle != nullptr)
+            throttle[a] = ap.action_table[act][0];
+        if (steer != nullptr)
+            steer[a] = ap.action_table[act][1];
+        if (action != nullptr)
+            action[a] = act;
+        if (prob != nullptr)
+            prob[a] = pr;
+        if (value_out != nullptr && Hv > 0)
             value_out[a] = v;
         if (state != nullptr)
             for (int i = 0; i < R; ++i)

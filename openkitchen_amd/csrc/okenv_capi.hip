@@ -27,6 +27,7 @@
 #include "ok_learn.h"
 #include "ok_dqn.h"
 #include "ok_ddpg.h"
+#include "ok_reinforce.h"
 #include "ok_expert.h"
 
 namespace
@@ -534,6 +535,13 @@ struct okenv
     uint8_t                *d_ddpg_part{nullptr};
     size_t                  ddpg_part_bytes{0};
     OkEventLog              ddpg_log;
+    // REINFORCE (okenv_actor_set_dropout, okenv_reinforce_update): the policy network's dropout, the update's scratch
+    // [chunk partials | accumulator] (grown, never shrunk) and timing events.  The learner is the one above.
+    float                   actor_dropout{0.F};
+    uint32_t                actor_dropout_seed{0};
+    uint8_t                *d_reinforce_part{nullptr};
+    size_t                  reinforce_part_bytes{0};
+    OkEventLog              reinforce_log;
 };
 
 struct okenv_track
@@ -1635,7 +1643,7 @@ extern "C"
             (void)hipEventDestroy(e.start);
             (void)hipEventDestroy(e.stop);
         }
-        for (OkEventLog *log : {&h->batch_log, &h->learn_log, &h->dqn_log, &h->ddpg_log})
+        for (OkEventLog *log : {&h->batch_log, &h->learn_log, &h->dqn_log, &h->ddpg_log, &h->reinforce_log})
             for (hipEvent_t e : log->events)
                 (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
@@ -2524,9 +2532,12 @@ extern "C"
         int          rc  = devEnsure(h, &h->d_actor_policy, cap);
         if (rc != OKENV_OK || (rc = devEnsure(h, &h->d_actor_value, cap)) != OKENV_OK)
             return rc;
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okActorKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okActorKernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okActorKernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       static_cast<int>(kLdsBudget)));
         h->actor            = *params;
+        h->actor_dropout    = 0.F; // (okenv_actor_set_dropout is per actor)
         h->actor_ok         = true;
         h->actor_policy_set = false;
         h->actor_value_set  = false;
@@ -2617,7 +2628,13 @@ extern "C"
         if (rec != nullptr)
             p.rec = *rec;
         const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
-        hipLaunchKernelGGL(okActorKernel, dim3(blocks), dim3(kActorThreads), okActorLdsBytes(h->shape.R, h->actor), h->stream, p);
+        if (h->actor_dropout > 0.F)
+        {
+            p.drop = ok_reinforce_mask{h->actor_dropout, ok_reinforce_scale(h->actor_dropout), h->actor_dropout_seed, 0U, 0U};
+            hipLaunchKernelGGL(okActorKernel<true>, dim3(blocks), dim3(kActorThreads), okActorLdsBytes(h->shape.R, h->actor), h->stream, p);
+        }
+        else
+            hipLaunchKernelGGL(okActorKernel<false>, dim3(blocks), dim3(kActorThreads), okActorLdsBytes(h->shape.R, h->actor), h->stream, p);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -2757,6 +2774,8 @@ extern "C"
             return rc;
         OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okLearnGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okReinforceGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(kLdsBudget)));
         OK_HIP(h, hipMemsetAsync(h->d_learn_moments, 0, 4U * h->learn_cap * sizeof(float), h->stream));
         h->learner    = *params;
         h->learn_t    = 0;
@@ -2782,6 +2801,8 @@ extern "C"
             return fail(h, OKENV_ERR_INVALID, "okenv_ppo_update: NULL handle");
         if (!h->learner_ok || !h->actor_ok)
             return fail(h, OKENV_ERR_STATE, "okenv_ppo_update: call okenv_learner_create first");
+        if (h->actor_dropout > 0.F)
+            return fail(h, OKENV_ERR_STATE, "okenv_ppo_update: the actor's dropout is on (okenv_actor_set_dropout) and this update's forward knows no mask");
         if (const char *why = okLearnCheckCall(batch, M, B, epochs, h->actor.value_hidden))
             return fail(h, OKENV_ERR_INVALID, std::string("okenv_ppo_update: ") + why);
         OK_HIP(h, hipSetDevice(h->device));
@@ -2919,6 +2940,168 @@ extern "C"
         return OKENV_OK;
     }
 
+    // ---- REINFORCE: the dropout actor and the whole-episode update (ok_reinforce.h) -------------------------------------------
+
+    int okenv_actor_set_dropout(okenv_t h, float p, uint32_t seed)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_actor_set_dropout: NULL handle");
+        if (!h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_set_dropout: call okenv_actor_create first");
+        if (!(p >= 0.F && p < 1.F))
+            return fail(h, OKENV_ERR_INVALID, "okenv_actor_set_dropout: p outside [0, 1)");
+        h->actor_dropout      = p;
+        h->actor_dropout_seed = seed;
+        return OKENV_OK;
+    }
+
+    int okenv_actor_act_dropout_host(const okenv_actor_params *params, float p, uint32_t dropout_seed, const float *policy, const float *value,
+                                     int32_t num_rays, int32_t n, const float *dist, const uint8_t *crashed, uint32_t draw_index, float *throttle,
+                                     float *steer, int64_t *action, float *prob, float *value_out, float *state, uint8_t *alive)
+    {
+        if (const char *why = okActorCheckParams(params, num_rays))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_actor_act_dropout_host: ") + why);
+        if (!(p >= 0.F && p < 1.F))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_actor_act_dropout_host: p outside [0, 1)");
+        if (!policy || n < 0 || !dist || (params->value_hidden > 0 && !value))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_actor_act_dropout_host: bad argument");
+        okActorActDropoutHost(*params, p, dropout_seed, policy, value, num_rays, n, dist, crashed, draw_index, throttle, steer, action, prob, value_out,
+                              state, alive);
+        return OKENV_OK;
+    }
+
+    int okenv_reinforce_update(okenv_t h, const okenv_reinforce_config *config, const okenv_reinforce_batch *batch, int32_t M, int32_t B,
+                               const int32_t *order, const okenv_reinforce_output *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_reinforce_update: NULL handle");
+        if (!h->learner_ok || !h->actor_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_reinforce_update: call okenv_learner_create first");
+        if (const char *why = okReinforceCheckCall(config, batch, M, B, h->actor_dropout > 0.F))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_reinforce_update: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkReinforceParams p{};
+        p.R          = h->shape.R;
+        p.H          = h->actor.hidden;
+        p.A          = h->actor.num_actions;
+        p.M          = M;
+        p.Pp         = ok_actor_num_params(p.R, p.H, p.A);
+        p.cols       = p.Pp + 1;
+        p.in         = *batch;
+        p.drop       = ok_reinforce_mask{h->actor_dropout, ok_reinforce_scale(h->actor_dropout), h->actor_dropout_seed, 0U, 0U};
+        p.agent_base = h->actor.agent_base;
+        p.draw_first = config->draw_first;
+        p.N          = config->num_agents;
+        p.order      = order;
+        p.policy     = h->d_actor_policy;
+        p.pol_m      = h->d_learn_moments;
+        p.pol_v      = h->d_learn_moments + h->learn_cap;
+        p.reduce     = config->reduce;
+        const okenv_reinforce_output none{};
+        const okenv_reinforce_output &o = out != nullptr ? *out : none;
+        p.grad_policy = o.grad_policy;
+        // the scratch: [chunk partials | accumulator], each piece 256-aligned
+        const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
+        const size_t c_max = (static_cast<size_t>(std::min(B, M)) + OK_LEARN_CHUNK - 1U) / OK_LEARN_CHUNK;
+        const size_t parts = up(sizeof(float) * c_max * static_cast<size_t>(p.cols)), acc_bytes = sizeof(float) * static_cast<size_t>(p.cols);
+        if (const int rc = growScratch(h, &h->d_reinforce_part, &h->reinforce_part_bytes, parts + up(acc_bytes)))
+            return rc;
+        p.part = reinterpret_cast<float *>(h->d_reinforce_part);
+        const bool accumulate = config->accumulate != 0;
+        if (accumulate)
+        {
+            p.acc = reinterpret_cast<float *>(h->d_reinforce_part + parts);
+            OK_HIP(h, hipMemsetAsync(p.acc, 0, acc_bytes, h->stream));
+        }
+        const int slices = okLearnMinibatches(M, B);
+        if (const int rc = eventsBegin(h, h->reinforce_log, 2U * static_cast<size_t>(slices)))
+            return rc;
+        const size_t   lds       = okReinforceLdsBytes(p.R, p.H, p.A);
+        const unsigned step_grid = static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols);
+        int            slot      = 0;
+        for (int k = 0; k < slices; ++k)
+        {
+            p.base = static_cast<long>(k) * B;
+            p.Bk   = static_cast<int>(std::min<long>(B, M - p.base));
+            p.C    = (p.Bk + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+            hipLaunchKernelGGL(okReinforceGradKernel, dim3(static_cast<unsigned>(p.C)), dim3(kLearnThreads), lds, h->stream, p);
+            OK_HIP(h, hipGetLastError());
+            if (const int rc = eventsMark(h, h->reinforce_log))
+                return rc;
+            if (accumulate && k + 1 < slices)
+            {
+                hipLaunchKernelGGL(okReinforceStepKernel<false>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
+                OK_HIP(h, hipGetLastError());
+            }
+            else
+            {
+                p.count = static_cast<float>(accumulate ? M : p.Bk);
+                p.adam  = okLearnAdamConsts(h->learner, h->learn_t + 1);
+                p.loss  = o.loss != nullptr ? o.loss + slot : nullptr;
+                hipLaunchKernelGGL(okReinforceStepKernel<true>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
+                OK_HIP(h, hipGetLastError());
+                // (the step number advances once the step's kernels are enqueued, as in okenv_ppo_update)
+                h->learn_t += 1;
+                ++slot;
+            }
+            if (const int rc = eventsMark(h, h->reinforce_log))
+                return rc;
+        }
+        return OKENV_OK;
+    }
+
+    int okenv_debug_reinforce_timing(okenv_t h, double *ms2)
+    {
+        OK_QUIESCE(h);
+        if (!h || !ms2)
+            return fail(h, OKENV_ERR_INVALID, "okenv_debug_reinforce_timing: NULL argument");
+        if (h->reinforce_log.timed < 3U)
+            return fail(h, OKENV_ERR_STATE, "okenv_debug_reinforce_timing: no okenv_reinforce_update has run with okenv_set_timing on");
+        return eventsSums(h, h->reinforce_log, ms2, 2);
+    }
+
+    int okenv_reinforce_update_host(const okenv_learner_params *params, const okenv_reinforce_config *config, float p, uint32_t dropout_seed,
+                                    uint32_t agent_base, int32_t num_rays, int32_t hidden, int32_t num_actions, okenv_learner_state *state,
+                                    const okenv_reinforce_batch *batch, int32_t M, int32_t B, const int32_t *order, const okenv_reinforce_output *out)
+    {
+        if (const char *why = okLearnCheckParams(params))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_reinforce_update_host: ") + why);
+        if (num_rays < 1 || num_rays > OK_ACTOR_MAX_RAYS || hidden < 1 || hidden > OK_ACTOR_MAX_HIDDEN || num_actions < 2 ||
+            num_actions > OK_ACTOR_MAX_ACTIONS)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_reinforce_update_host: a network width outside the actor's limits");
+        if (!(p >= 0.F && p < 1.F))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_reinforce_update_host: p outside [0, 1)");
+        if (const char *why = okReinforceCheckCall(config, batch, M, B, p > 0.F))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_reinforce_update_host: ") + why);
+        if (state == nullptr || state->policy == nullptr || state->policy_m == nullptr || state->policy_v == nullptr || state->t < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_reinforce_update_host: state lacks a parameter or moment vector, or t < 0");
+        const okenv_reinforce_output none{};
+        okReinforceUpdateHost(*params, *config, p, dropout_seed, agent_base, num_rays, hidden, num_actions, *state, *batch, M, B, order,
+                              out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_logf(const float *x, float *out, int32_t n)
+    {
+        if (!x || !out || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_logf: bad argument");
+        for (int32_t i = 0; i < n; ++i)
+            out[i] = ok_logf(x[i]);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_reinforce_mask(float p, uint32_t seed, uint32_t agent, uint32_t draw, int32_t hidden, uint8_t *out)
+    {
+        if (!(p >= 0.F && p < 1.F) || hidden < 0 || !out)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_reinforce_mask: bad argument");
+        const ok_reinforce_mask m{p, ok_reinforce_scale(p), seed, agent, draw};
+        for (int32_t j = 0; j < hidden; ++j)
+            out[j] = ok_reinforce_kept(m, j) ? 1 : 0;
+        return OKENV_OK;
+    }
+
     // ---- Deep-Q learning: replay ring, sampling and the TD update (ok_dqn.h) ------------------------------------------------
 
     int okenv_replay_create(okenv_t h, int32_t capacity, uint32_t flags)
@@ -3002,6 +3185,8 @@ extern "C"
             return fail(h, OKENV_ERR_INVALID, "okenv_dqn_update: NULL handle");
         if (!h->learner_ok || !h->actor_ok)
             return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: call okenv_learner_create first");
+        if (h->actor_dropout > 0.F)
+            return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: the actor's dropout is on (okenv_actor_set_dropout) and this update's forward knows no mask");
         if (!h->replay.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: call okenv_replay_create first");
         if (h->dqn.target_network != 0 && !h->dqn_target_set)

@@ -591,6 +591,29 @@ class BatchedEnvironment:
         capi.check(self._L.okenv_debug_update_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
         return {k: 1000.0 * v for k, v in zip(capi.UPDATE_KERNELS, ms)}
 
+    # ---- REINFORCE (include/okenv.h) ----------------------------------------------------------------
+    def actor_set_dropout(self, p, seed=0):
+        """Dropout with probability p in [0, 1) on the hidden layer of the actor's policy network, masks keyed by `seed`; 0 switches it
+        off, and so does a new actor_create.  While it is on, ppo_update and dqn_update refuse."""
+        capi.check(self._L.okenv_actor_set_dropout(self._h, float(p), int(seed) & 0xFFFFFFFF), self._h)
+
+    def reinforce_update(self, batch, M, B, accumulate=True, reduce="sum", num_agents=0, draw_first=0, order=None, out=None):
+        """okenv_reinforce_update: enqueues every slice on the handle's stream (two kernels each), no synchronisation.  batch: dict of
+        device tensors / addresses under "state" [M,R] float32, "action" [M] int64, "ret" [M] float32 and "index" [M] int32 (needed
+        with dropout on, together with num_agents and draw_first); order: None or a device int32 tensor [M]; out: None or a dict under
+        "loss" (float32, one per optimiser step) and "grad_policy"."""
+        cfg = capi.reinforce_config(accumulate, reduce, num_agents, draw_first)
+        rb = capi.fill_pointers(capi.OkenvReinforceBatch(), batch, "reinforce batch")
+        ro = capi.fill_pointers(capi.OkenvReinforceOutput(), out or {}, "reinforce output")
+        capi.check(self._L.okenv_reinforce_update(self._h, C.byref(cfg), C.byref(rb), int(M), int(B), capi.ptr(order), C.byref(ro)), self._h)
+
+    def reinforce_timing(self):
+        """Device microseconds of the latest reinforce_update that ran with set_timing(True), summed over its slices, by
+        capi.REINFORCE_KERNELS."""
+        ms = (C.c_double * 2)()
+        capi.check(self._L.okenv_debug_reinforce_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
+        return {k: 1000.0 * v for k, v in zip(capi.REINFORCE_KERNELS, ms)}
+
     # ---- Deep-Q learning (include/okenv.h, DESIGN.md section 17) ----------------------------------------------------------
     def replay_create(self, capacity, push_all=False):
         """Attaches a replay ring of `capacity` transitions (state, next_state [C,R], action, reward, done [C]) to the handle; an
@@ -849,6 +872,59 @@ def actor_act_host(params, policy, value, dist, crashed=None, draw_index=0):
     return out
 
 
+def actor_act_dropout_host(params, p, dropout_seed, policy, value, dist, crashed=None, draw_index=0):
+    """actor_act_host with REINFORCE's dropout (p, dropout_seed) on the policy network's hidden layer (okenv_actor_act_dropout_host);
+    the same arguments and the same dict."""
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    n, R = dist.shape
+    policy = None if policy is None else np.ascontiguousarray(policy, dtype=np.float32).ravel()
+    value = None if value is None else np.ascontiguousarray(value, dtype=np.float32).ravel()
+    if params is not None and policy is not None:
+        assert policy.size == params.hidden * R + params.hidden + params.num_actions * params.hidden + params.num_actions
+        assert value is None or value.size == params.value_hidden * R + 2 * params.value_hidden + 1
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, dtype=np.uint8)
+    out = {"throttle": np.zeros(n, np.float32), "steer": np.zeros(n, np.float32), "action": np.zeros(n, np.int64),
+           "prob": np.zeros(n, np.float32), "value": np.zeros(n, np.float32), "state": np.zeros((n, R), np.float32),
+           "alive": np.zeros(n, np.uint8)}
+    capi.check(capi.load().okenv_actor_act_dropout_host(C.byref(params) if params is not None else None, float(p), int(dropout_seed) & 0xFFFFFFFF,
+                                                        capi.ptr(policy), capi.ptr(value), R, n, capi.ptr(dist), capi.ptr(crashed),
+                                                        int(draw_index) & 0xFFFFFFFF, capi.ptr(out["throttle"]), capi.ptr(out["steer"]),
+                                                        capi.ptr(out["action"]), capi.ptr(out["prob"]), capi.ptr(out["value"]),
+                                                        capi.ptr(out["state"]), capi.ptr(out["alive"])))
+    if params.value_hidden == 0:
+        del out["value"]
+    return out
+
+
+def reinforce_update_host(params, shape, state, batch, B, accumulate=True, reduce="sum", p=0.0, dropout_seed=0, agent_base=0, num_agents=0,
+                          draw_first=0, order=None, want=("loss", "grad_policy")):
+    """REINFORCE's update on host arrays, no GPU needed (okenv_reinforce_update_host).  params: capi.learner_params(...); shape:
+    (R, H, A); state: dict of float32 numpy arrays "policy", "policy_m", "policy_v" and the int "t" -- copied, the new state is
+    returned; batch: dict of numpy arrays "state" [M,R], "action" [M] int64, "ret" [M] and, with p > 0, "index" [M] int32; order: None
+    or int32 [M].  Returns (new state, outputs): outputs holds the arrays named in `want` ("loss": one value per optimiser step)."""
+    R, H, A = (int(v) for v in shape)
+    M = int(np.asarray(batch["ret"]).shape[0])
+    b = {"state": np.ascontiguousarray(batch["state"], dtype=np.float32), "action": np.ascontiguousarray(batch["action"], dtype=np.int64),
+         "ret": np.ascontiguousarray(batch["ret"], dtype=np.float32)}
+    if batch.get("index") is not None:
+        b["index"] = np.ascontiguousarray(batch["index"], dtype=np.int32)
+    new = {k: np.array(v, dtype=np.float32, copy=True).ravel() for k, v in state.items() if k != "t" and v is not None}
+    st = capi.fill_pointers(capi.OkenvLearnerState(), new, "learner state")
+    st.t = int(state.get("t", 0))
+    steps = (1 if accumulate else (M + int(B) - 1) // int(B)) if M > 0 and B > 0 else 0
+    sizes = {"loss": steps, "grad_policy": H * R + H + A * H + A}
+    outs = {k: np.zeros(sizes[k], dtype=np.float32) for k in want}
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.int32)
+    cfg = capi.reinforce_config(accumulate, reduce, num_agents, draw_first) if reduce is not None else None
+    capi.check(capi.load().okenv_reinforce_update_host(
+        C.byref(params) if params is not None else None, C.byref(cfg) if cfg is not None else None, float(p), int(dropout_seed) & 0xFFFFFFFF,
+        int(agent_base) & 0xFFFFFFFF, R, H, A, C.byref(st), C.byref(capi.fill_pointers(capi.OkenvReinforceBatch(), b, "reinforce batch")), M, int(B),
+        capi.ptr(order), C.byref(capi.fill_pointers(capi.OkenvReinforceOutput(), {k: v for k, v in outs.items() if v.size}, "reinforce output"))))
+    new["t"] = int(st.t)
+    return new, outs
+
+
 def batch_prepare_host(reward, alive, value=None, last_value=None, state=None, action=None, prob=None, num_agents=None, gamma=0.99, lam=1.0,
                        normalize=0, want=None, block_threads=0):
     """The episode-to-batch rule on host arrays, no GPU needed (okenv_batch_prepare_host).  reward / alive / value: [T, S] with
@@ -1064,6 +1140,22 @@ def debug_expf(x):
     a = np.ascontiguousarray(x, dtype=np.float32)
     out = np.zeros_like(a)
     capi.check(capi.load().okenv_debug_expf(capi.ptr(a), capi.ptr(out), a.size))
+    return out
+
+
+def debug_logf(x):
+    """ok_logf of include/okenv_math.h (the logarithm of REINFORCE's loss column) for an array of positive float32 arguments."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    capi.check(capi.load().okenv_debug_logf(capi.ptr(x), capi.ptr(out), x.size))
+    return out
+
+
+def debug_reinforce_mask(p, seed, agent, draw, hidden):
+    """REINFORCE's dropout mask of hidden units 0 .. hidden-1 for one (global agent id, draw index): uint8, 1 kept."""
+    out = np.zeros(int(hidden), dtype=np.uint8)
+    capi.check(capi.load().okenv_debug_reinforce_mask(float(p), int(seed) & 0xFFFFFFFF, int(agent) & 0xFFFFFFFF, int(draw) & 0xFFFFFFFF, int(hidden),
+                                                      capi.ptr(out)))
     return out
 
 

@@ -152,6 +152,7 @@ def collect_episode_device(venv, max_steps=None, check_every=8, graph_chunk=0):
     res = {"states": out["state"][:T], "actions": out["action"][:T], "log_probs": torch.log(out["prob"][:T]),
            "rewards": out["reward"][:T], "alive": out["alive"][:T]}
     venv._episode_probs = (res["log_probs"], out["prob"][:T])  # the probabilities as recorded, for prepare_batch -> ppo_update
+    venv._episode_draw_first = (res["log_probs"], start)  # row 0's draw index, for prepare_batch -> reinforce_update's dropout masks
     if venv.actor_has_value:
         res["values"] = out["value"][:T]
     return res
@@ -215,7 +216,8 @@ def prepare_batch(venv, ep, gamma=0.99, lam=None, normalize=True, last_value=Non
 
     Returns a dict of device tensors: states [M, R], actions [M] i64, log_probs [M], returns [M], advantages [M] (with values), index
     [M] i32 (t * N + i), count (M, an int: the call waits for the stream once to read it), stats (the okenv_batch_stats words on
-    the device; batch_stats(batch) reads them)."""
+    the device; batch_stats(batch) reads them) and, for an episode dict collect_episode_device returned, draw_first (an int: the
+    device actor's draw index of row 0)."""
     rewards, alive = ep["rewards"], ep["alive"]
     T, N = rewards.shape
     R = ep["states"].shape[2]
@@ -248,6 +250,9 @@ def prepare_batch(venv, ep, gamma=0.99, lam=None, normalize=True, last_value=Non
            "index": out["index"][:M], "count": M, "stats": out["stats"]}
     if use_value:
         res["advantages"] = out["adv"][:M]
+    drawn = getattr(venv, "_episode_draw_first", None)
+    if drawn is not None and drawn[0] is ep["log_probs"]:
+        res["draw_first"] = drawn[1]  # the device actor's draw index of the episode's row 0 (reinforce_update's masks)
     recorded = getattr(venv, "_episode_probs", None) if getattr(venv, "learner_enabled", False) else None
     if recorded is not None and recorded[0] is ep["log_probs"]:
         # the probabilities as the device actor recorded them (ppo_update's ratio divides by them), by the samples' flat indices
@@ -292,6 +297,41 @@ def ppo_update(venv, batch, epochs=5, minibatch=4096, shuffle=True, use_advantag
         if n_value:
             out["grad_value"] = torch.empty(n_value, dtype=torch.float32, device=dev)
     venv.env.ppo_update(data, M, minibatch, epochs, order, out)
+    venv._update_inputs = (data, order)  # alive until the next update: the kernels are only enqueued
+    return out
+
+
+def reinforce_update(venv, batch, slice=16384, accumulate=True, reduce="sum", shuffle=False, grads=False):
+    """ReinforceAgent::updatePolicy on the device (okenv_reinforce_update, DESIGN.md section 19) for the dict prepare_batch returns:
+    loss = sum of -log p(a) * return over the M samples, its gradient through the policy network -- with the dropout masks the device
+    actor drew while acting, regenerated from batch["index"] and the draw index collect_episode_device kept -- and one Adam step, in
+    place in the parameters the device actor acts with (venv.enable_actor, venv.enable_learner(lr=0.01) first; no sync_actor
+    afterwards, venv.pull_actor() brings them back to the module).
+
+    slice: samples per pair of launches; it bounds the scratch, and the sums' order (so the last bits) depends on it.
+    accumulate=False steps after every slice instead (minibatch REINFORCE); reduce "sum" (the reference) or "mean"; shuffle: a
+    torch.randperm over the samples.  While dropout is on the batch must carry "draw_first", which prepare_batch adds for the episode dict
+    collect_episode_device returned: a batch of an older episode keeps its own draw index.
+
+    Everything is enqueued on the environment's stream; nothing is read back.  Returns a dict of device tensors: loss [steps]
+    (float32, one per optimiser step) and, with grads=True, grad_policy of the last step."""
+    M = int(batch["states"].shape[0])
+    dev = batch["states"].device
+    data = {"state": batch["states"].float().contiguous(), "action": batch["actions"].reshape(-1).contiguous(),
+            "ret": batch["returns"].reshape(-1).float().contiguous()}
+    assert data["action"].dtype == torch.int64, "actions must be int64"
+    draw_first = 0
+    if getattr(venv, "actor_dropout", 0.0) > 0.0:
+        # the masks are those of the episode the batch was cut from: prepare_batch puts its draw index beside the samples' indices
+        assert "draw_first" in batch, ("with dropout on, the batch must be prepare_batch's of the episode dict collect_episode_device returned, "
+                                       "unchanged: it carries that episode's draw index")
+        data["index"] = batch["index"].reshape(-1).to(torch.int32).contiguous()
+        draw_first = batch["draw_first"]
+    order = torch.randperm(M, device=dev).to(torch.int32).contiguous() if shuffle else None
+    out = {"loss": torch.empty(1 if accumulate else (M + slice - 1) // slice, dtype=torch.float32, device=dev)}
+    if grads:
+        out["grad_policy"] = torch.empty(venv.env.actor_num_params()[0], dtype=torch.float32, device=dev)
+    venv.env.reinforce_update(data, M, slice, accumulate, reduce, venv.num_envs, draw_first, order, out)
     venv._update_inputs = (data, order)  # alive until the next update: the kernels are only enqueued
     return out
 

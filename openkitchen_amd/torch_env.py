@@ -254,6 +254,7 @@ class VectorEnvironment:
         value_hidden = 0 if critic is None else self._check_network(self._actor_nets[1], "critic", outputs=1)[0]
         self.env.actor_create(hidden, actions, value_hidden, mode, epsilon, self.seed, self.agent_base)
         self.actor_has_value = critic is not None
+        self.actor_dropout = 0.0  # (a new device actor starts without dropout)
         self._actor_graphs = {}
         self.sync_actor()
 
@@ -288,6 +289,15 @@ class VectorEnvironment:
 
     def set_actor_epsilon(self, epsilon):
         self.env.actor_set_epsilon(epsilon)
+        self._actor_graphs = {}  # a captured launch carries the old value
+
+    def set_actor_dropout(self, p, seed=None):
+        """Dropout with probability p in [0, 1) on the hidden layer of the device actor's policy network, as the reference's REINFORCE
+        network has it while acting and in the update (Reinforce/Policy.hpp:22-29); 0 switches it off.  The masks
+        are keyed by `seed` (default: the environment's), the global agent id and the draw index, so rollout.reinforce_update regenerates
+        them.  While it is on, rollout.ppo_update and rollout.dqn_update refuse."""
+        self.env.actor_set_dropout(p, self.seed if seed is None else seed)
+        self.actor_dropout = float(p)
         self._actor_graphs = {}  # a captured launch carries the old value
 
     def actor_act(self, record=None):
