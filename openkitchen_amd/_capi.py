@@ -4,6 +4,7 @@ Fails loudly if the shared object is missing or cannot be loaded: there is no Py
 the hot path.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -281,13 +282,27 @@ def ddpg_config(hidden, critic_hidden, scale=(50.0, 5.0), bias=(50.0, 0.0), nois
                            float(lr_actor), float(lr_critic), float(beta1), float(beta2), float(eps), int(sample_seed) & 0xFFFFFFFF)
 
 
-def fill_pointers(struct, given, what):
-    """Sets the pointer members of a ctypes struct from a dict of tensors / arrays / addresses (None: left NULL)."""
-    names = {name for name, _ in struct._fields_}
+@functools.lru_cache(maxsize=None)
+def _members(struct_type):
+    return frozenset(name for name, _ in struct_type._fields_)
+
+
+def fill_pointers(struct, given, what, sizes=None, strided=False):
+    """Sets the pointer members of a ctypes struct from a dict of tensors / arrays / addresses (None: left NULL): the one way a dict
+    of slots becomes a struct of the C ABI.  A key that is no member raises KeyError; arrays and tensors must be contiguous.
+    sizes: {slot: bytes}, the least a tensor under that slot may hold.  strided=True hands tensors over by their first element without
+    the contiguity check, for callers that state the strides themselves (batch_prepare)."""
+    names = _members(type(struct))
     for k, v in given.items():
         if k not in names:
             raise KeyError("unknown %s slot %r" % (what, k))
-        if v is not None:
+        if v is None:
+            continue
+        if hasattr(v, "data_ptr"):  # torch tensor: on the act -> step -> push path, so without the detour through ptr()
+            assert strided or v.is_contiguous(), "%s slot %r is not contiguous" % (what, k)
+            assert sizes is None or v.numel() * v.element_size() >= sizes[k], "%s slot %r is too small" % (what, k)
+            setattr(struct, k, v.data_ptr())
+        else:
             setattr(struct, k, ptr(v).value)
     return struct
 

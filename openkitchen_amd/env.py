@@ -5,6 +5,7 @@
 once with device-resident state.  bench.py, the parity tests and the Python callers use these; the C++
 callers use the classes in include/Environment/.  All compute happens in libokenv.so on the GPU.
 """
+import collections
 import ctypes as C
 import os
 
@@ -13,6 +14,12 @@ import numpy as np
 from . import _capi as capi
 
 TRACK_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tracks")
+
+# What tells Deep-Q's replay ring from DDPG's (ringCreate ... ringGet serve both on the C side): the symbols' prefix, the two structs, the
+# attribute that remembers the capacity, and the action's shape and dtype per transition.
+_Ring = collections.namedtuple("_Ring", "prefix ring_struct record_struct capacity_attr action_shape action_dtype")
+_DQN_RING = _Ring("okenv_replay", capi.OkenvReplayRing, capi.OkenvActorRecord, "replay_capacity", (), np.int64)
+_DDPG_RING = _Ring("okenv_ddpg_replay", capi.OkenvDdpgRing, capi.OkenvDdpgRecord, "ddpg_replay_capacity", (2,), np.float32)
 
 
 def track_path(name):
@@ -86,6 +93,19 @@ class Track:
         finally:
             L.okenv_track_free(h)
         return xy, ordinal
+
+
+def _flat_params(v, n):
+    """A network's n parameters as the C ABI takes them: a float32 numpy array made flat and contiguous, or a device tensor that must be
+    so already; None stays None (the network is left as it is)."""
+    if v is None:
+        return None
+    if isinstance(v, np.ndarray):
+        v = np.ascontiguousarray(v, dtype=np.float32).ravel()
+        assert v.size == n, "expected %d parameters, got %d" % (n, v.size)
+    else:
+        assert v.is_contiguous() and v.numel() == n and v.element_size() == 4, "expected %d float32 parameters" % n
+    return v
 
 
 class BatchedEnvironment:
@@ -443,17 +463,8 @@ class BatchedEnvironment:
         if record is None:
             capi.check(self._L.okenv_expert_act(self._h, None), self._h)
             return
-        rec = capi.OkenvExpertRecord()
         sizes = {"action": self.N * 8, "dist": self.N * self.R * 4, "rel_xy": self.N * self.R * 8, "alive": self.N}
-        for k, v in record.items():
-            if k not in sizes:
-                raise KeyError("unknown record slot %r" % k)
-            if v is None:
-                continue
-            if hasattr(v, "data_ptr"):
-                assert v.is_contiguous() and v.numel() * v.element_size() >= sizes[k], "record slot %r is too small" % k
-                v = v.data_ptr()
-            setattr(rec, k, int(v))
+        rec = capi.fill_pointers(capi.OkenvExpertRecord(), record, "record", sizes)
         capi.check(self._L.okenv_expert_act(self._h, C.byref(rec)), self._h)
 
     # ---- shared-network actors (include/okenv.h) ---------------------------------------------------
@@ -473,19 +484,12 @@ class BatchedEnvironment:
     def actor_set_params(self, policy=None, value=None):
         """New parameter vectors (torch's parameters() order, flattened) from float32 numpy arrays or device tensors; None
         leaves a network as it is.  Enqueued on the handle's stream, no synchronisation for device tensors."""
-        n_policy, n_value = self.actor_num_params()
-        keep = []
-        for v, n in ((policy, n_policy), (value, n_value)):
-            if v is None:
-                keep.append(None)
-                continue
-            if isinstance(v, np.ndarray):
-                v = np.ascontiguousarray(v, dtype=np.float32).ravel()
-                assert v.size == n, "expected %d parameters, got %d" % (n, v.size)
-            else:
-                assert v.is_contiguous() and v.numel() == n and v.element_size() == 4, "expected %d float32 parameters" % n
-            keep.append(v)
-        capi.check(self._L.okenv_actor_set_params(self._h, capi.ptr(keep[0]), capi.ptr(keep[1])), self._h)
+        self._set_params(self._L.okenv_actor_set_params, (policy, value), self.actor_num_params())
+
+    def _set_params(self, entry, vectors, counts):
+        """Two parameter vectors to an okenv_*_set_params entry, each checked by _flat_params."""
+        keep = [_flat_params(v, n) for v, n in zip(vectors, counts)]
+        capi.check(entry(self._h, capi.ptr(keep[0]), capi.ptr(keep[1])), self._h)
         if any(isinstance(v, np.ndarray) for v in keep):
             self.sync()  # the host arrays are temporaries
 
@@ -503,17 +507,8 @@ class BatchedEnvironment:
         if record is None:
             capi.check(self._L.okenv_actor_act(self._h, None), self._h)
             return
-        rec = capi.OkenvActorRecord()
         sizes = {"state": self.N * self.R * 4, "action": self.N * 8, "prob": self.N * 4, "value": self.N * 4, "alive": self.N}
-        for k, v in record.items():
-            if k not in sizes:
-                raise KeyError("unknown record slot %r" % k)
-            if v is None:
-                continue
-            if hasattr(v, "data_ptr"):
-                assert v.is_contiguous() and v.numel() * v.element_size() >= sizes[k], "record slot %r is too small" % k
-                v = v.data_ptr()
-            setattr(rec, k, int(v))
+        rec = capi.fill_pointers(capi.OkenvActorRecord(), record, "record", sizes)
         capi.check(self._L.okenv_actor_act(self._h, C.byref(rec)), self._h)
 
     # ---- from a recorded episode to the learner's batch (include/okenv.h) ---------------------------
@@ -522,17 +517,12 @@ class BatchedEnvironment:
         """okenv_batch_prepare: enqueues the five kernels on the handle's stream, no synchronisation.  inputs: dict of device tensors
         / addresses under "reward", "alive" (required), "value", "last_value", "state", "action", "prob"; outputs: likewise under
         "state", "action", "prob", "ret", "adv", "index", "ret_plane", "adv_plane", "stats" (capi.BATCH_STATS_BYTES bytes), "count".
-        Strided views are passed by their first element: the strides are the caller's to state."""
+        Strided views are passed by their first element: the strides are the caller's to state, so the slots go through the shared
+        packer (capi.fill_pointers) with strided=True, which skips its contiguity check."""
         bp = capi.OkenvBatchParams(int(num_steps), int(num_agents), int(state_width), int(record_stride), int(field_stride), float(gamma),
                                    float(lam), int(normalize), int(block_threads))
-        bi, bo = capi.OkenvBatchInput(), capi.OkenvBatchOutput()
-        for struct, given in ((bi, inputs), (bo, outputs)):
-            names = {name for name, _ in struct._fields_}
-            for k, v in given.items():
-                if k not in names:
-                    raise KeyError("unknown batch slot %r" % k)
-                if v is not None:
-                    setattr(struct, k, int(v.data_ptr() if hasattr(v, "data_ptr") else v))
+        bi = capi.fill_pointers(capi.OkenvBatchInput(), inputs, "batch", strided=True)
+        bo = capi.fill_pointers(capi.OkenvBatchOutput(), outputs, "batch", strided=True)
         capi.check(self._L.okenv_batch_prepare(self._h, C.byref(bp), C.byref(bi), C.byref(bo)), self._h)
 
     def batch_count(self):
@@ -543,9 +533,13 @@ class BatchedEnvironment:
 
     def batch_timing(self):
         """Device microseconds of the five kernels of the latest batch_prepare that ran with set_timing(True), by capi.BATCH_KERNELS."""
-        ms = (C.c_double * 5)()
-        capi.check(self._L.okenv_debug_batch_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
-        return {k: 1000.0 * v for k, v in zip(capi.BATCH_KERNELS, ms)}
+        return self._timing("okenv_debug_batch_timing", capi.BATCH_KERNELS)
+
+    def _timing(self, symbol, names):
+        """One device time in microseconds per name from an okenv_debug_*_timing entry (which gives milliseconds)."""
+        ms = (C.c_double * len(names))()
+        capi.check(getattr(self._L, symbol)(self._h, C.cast(ms, C.c_void_p)), self._h)
+        return {k: 1000.0 * v for k, v in zip(names, ms)}
 
     # ---- PPO's update (include/okenv.h, DESIGN.md section 16) -------------------------------------------------------------
     def learner_create(self, lr=3e-4, clip=0.2, beta1=0.9, beta2=0.999, eps=1e-8):
@@ -587,9 +581,7 @@ class BatchedEnvironment:
     def update_timing(self):
         """Device microseconds of the latest ppo_update that ran with set_timing(True), summed over its minibatches, by
         capi.UPDATE_KERNELS."""
-        ms = (C.c_double * 2)()
-        capi.check(self._L.okenv_debug_update_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
-        return {k: 1000.0 * v for k, v in zip(capi.UPDATE_KERNELS, ms)}
+        return self._timing("okenv_debug_update_timing", capi.UPDATE_KERNELS)
 
     # ---- REINFORCE (include/okenv.h, DESIGN.md section 19) ----------------------------------------------------------------
     def actor_set_dropout(self, p, seed=0):
@@ -610,9 +602,7 @@ class BatchedEnvironment:
     def reinforce_timing(self):
         """Device microseconds of the latest reinforce_update that ran with set_timing(True), summed over its slices, by
         capi.REINFORCE_KERNELS."""
-        ms = (C.c_double * 2)()
-        capi.check(self._L.okenv_debug_reinforce_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
-        return {k: 1000.0 * v for k, v in zip(capi.REINFORCE_KERNELS, ms)}
+        return self._timing("okenv_debug_reinforce_timing", capi.REINFORCE_KERNELS)
 
     # ---- Deep-Q learning (include/okenv.h, DESIGN.md section 17) ----------------------------------------------------------
     def replay_create(self, capacity, push_all=False):
@@ -620,33 +610,46 @@ class BatchedEnvironment:
         earlier one is dropped and its memory freed: a HIP graph that captured replay_push before this call must not be replayed again
         (VectorEnvironment.enable_replay drops the ones it keeps).  push_all: push every agent, not only those that entered the step
         alive."""
-        capi.check(self._L.okenv_replay_create(self._h, int(capacity), capi.REPLAY_PUSH_ALL if push_all else 0), self._h)
-        self.replay_capacity = int(capacity)
+        self._ring_create(_DQN_RING, capacity, push_all)
 
     def replay_reset(self):
-        capi.check(self._L.okenv_replay_reset(self._h), self._h)
+        self._ring_call(_DQN_RING, "reset")
 
     def replay_push(self, record, reward=None):
         """Appends the transitions of the step that has just run: `record` is the dict the preceding actor_act was given ("state",
         "action" and, unless push_all, "alive"); reward: None (the clearance rule) or a device float32 tensor [N].  Two kernels on
         the handle's stream, no synchronisation."""
-        rec = capi.fill_pointers(capi.OkenvActorRecord(), {k: v for k, v in record.items() if k in ("state", "action", "alive")}, "actor record")
-        capi.check(self._L.okenv_replay_push(self._h, C.byref(rec), capi.ptr(reward)), self._h)
+        self._ring_push(_DQN_RING, record, reward)
 
     def replay_size(self):
         """(transitions in the ring, transitions ever pushed); waits for the stream."""
-        size, pushed = C.c_int64(), C.c_int64()
-        capi.check(self._L.okenv_replay_size(self._h, C.byref(size), C.byref(pushed)), self._h)
-        return size.value, pushed.value
+        return self._ring_size(_DQN_RING)
 
     def replay_get(self, out=None):
         """The ring's fields, all `capacity` slots: numpy arrays, or copied into the device tensors of the dict `out`.  Synchronises."""
-        Cn, R = self.replay_capacity, self.R
+        return self._ring_get(_DQN_RING, out)
+
+    # (one implementation for Deep-Q's ring and DDPG's: `kind` is _DQN_RING or _DDPG_RING)
+    def _ring_call(self, kind, op, *args):
+        capi.check(getattr(self._L, "%s_%s" % (kind.prefix, op))(self._h, *args), self._h)
+
+    def _ring_create(self, kind, capacity, push_all):
+        self._ring_call(kind, "create", int(capacity), capi.REPLAY_PUSH_ALL if push_all else 0)
+        setattr(self, kind.capacity_attr, int(capacity))
+
+    def _ring_push(self, kind, record, reward):
+        rec = capi.fill_pointers(kind.record_struct(), {k: v for k, v in record.items() if k in ("state", "action", "alive")}, "record")
+        self._ring_call(kind, "push", C.byref(rec), capi.ptr(reward))
+
+    def _ring_size(self, kind):
+        size, pushed = C.c_int64(), C.c_int64()
+        self._ring_call(kind, "size", C.byref(size), C.byref(pushed))
+        return size.value, pushed.value
+
+    def _ring_get(self, kind, out):
         if out is None:
-            out = {"state": np.empty((Cn, R), np.float32), "next_state": np.empty((Cn, R), np.float32), "action": np.empty(Cn, np.int64),
-                   "reward": np.empty(Cn, np.float32), "done": np.empty(Cn, np.float32)}
-        ring = capi.fill_pointers(capi.OkenvReplayRing(), out, "replay ring")
-        capi.check(self._L.okenv_replay_get(self._h, C.byref(ring)), self._h)
+            out = {k: v for k, v in _host_ring(kind, getattr(self, kind.capacity_attr), self.R, np.empty).items() if k != "pushed"}
+        self._ring_call(kind, "get", C.byref(_ring_struct(kind, out)))
         return out
 
     def dqn_params(self, gamma=0.99, mask_done=False, target_network=False, seed=0):
@@ -667,9 +670,7 @@ class BatchedEnvironment:
     def dqn_timing(self):
         """Device microseconds of the latest dqn_update that ran with set_timing(True), summed over its iterations, by
         capi.UPDATE_KERNELS."""
-        ms = (C.c_double * 2)()
-        capi.check(self._L.okenv_debug_dqn_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
-        return {k: 1000.0 * v for k, v in zip(capi.UPDATE_KERNELS, ms)}
+        return self._timing("okenv_debug_dqn_timing", capi.UPDATE_KERNELS)
 
     # ---- DDPG (include/okenv.h, DESIGN.md section 18) ----------------------------------------------------------------------
     def ddpg_create(self, hidden, critic_hidden, **config):
@@ -689,20 +690,7 @@ class BatchedEnvironment:
     def ddpg_set_params(self, actor=None, critic=None):
         """New online parameters (torch's parameters() order, flattened) from float32 numpy arrays or device tensors; each network
         that arrives also replaces its target network.  None leaves a network as it is."""
-        keep = []
-        for v, n in zip((actor, critic), self.ddpg_num_params()):
-            if v is None:
-                keep.append(None)
-                continue
-            if isinstance(v, np.ndarray):
-                v = np.ascontiguousarray(v, dtype=np.float32).ravel()
-                assert v.size == n, "expected %d parameters, got %d" % (n, v.size)
-            else:
-                assert v.is_contiguous() and v.numel() == n and v.element_size() == 4, "expected %d float32 parameters" % n
-            keep.append(v)
-        capi.check(self._L.okenv_ddpg_set_params(self._h, capi.ptr(keep[0]), capi.ptr(keep[1])), self._h)
-        if any(isinstance(v, np.ndarray) for v in keep):
-            self.sync()  # the host arrays are temporaries
+        self._set_params(self._L.okenv_ddpg_set_params, (actor, critic), self.ddpg_num_params())
 
     def ddpg_state(self, out=None):
         """The four parameter vectors, the four Adam moments (capi.DDPG_STATE_VECTORS) and the int t: float32 numpy arrays, or copied
@@ -725,41 +713,28 @@ class BatchedEnvironment:
             capi.check(self._L.okenv_ddpg_act(self._h, None), self._h)
             return
         sizes = {"state": self.N * self.R * 4, "action": self.N * 8, "alive": self.N}
-        for k, v in record.items():
-            if k not in sizes:
-                raise KeyError("unknown record slot %r" % k)
-            if v is not None and hasattr(v, "data_ptr"):
-                assert v.is_contiguous() and v.numel() * v.element_size() >= sizes[k], "record slot %r is too small" % k
-        rec = capi.fill_pointers(capi.OkenvDdpgRecord(), record, "ddpg record")
+        rec = capi.fill_pointers(capi.OkenvDdpgRecord(), record, "record", sizes)
         capi.check(self._L.okenv_ddpg_act(self._h, C.byref(rec)), self._h)
 
     def ddpg_replay_create(self, capacity, push_all=False):
         """Attaches DDPG's replay ring of `capacity` transitions (action [C,2] float32); replay_create's contract."""
-        capi.check(self._L.okenv_ddpg_replay_create(self._h, int(capacity), capi.REPLAY_PUSH_ALL if push_all else 0), self._h)
-        self.ddpg_replay_capacity = int(capacity)
+        self._ring_create(_DDPG_RING, capacity, push_all)
 
     def ddpg_replay_reset(self):
-        capi.check(self._L.okenv_ddpg_replay_reset(self._h), self._h)
+        self._ring_call(_DDPG_RING, "reset")
 
     def ddpg_replay_push(self, record, reward=None):
         """Appends the transitions of the step that has just run: `record` is the dict the preceding ddpg_act was given; reward:
         None (1.0 per transition) or a device float32 tensor [N].  Two kernels on the handle's stream, no synchronisation."""
-        rec = capi.fill_pointers(capi.OkenvDdpgRecord(), {k: v for k, v in record.items() if k in ("state", "action", "alive")}, "ddpg record")
-        capi.check(self._L.okenv_ddpg_replay_push(self._h, C.byref(rec), capi.ptr(reward)), self._h)
+        self._ring_push(_DDPG_RING, record, reward)
 
     def ddpg_replay_size(self):
         """(transitions in the ring, transitions ever pushed); waits for the stream."""
-        size, pushed = C.c_int64(), C.c_int64()
-        capi.check(self._L.okenv_ddpg_replay_size(self._h, C.byref(size), C.byref(pushed)), self._h)
-        return size.value, pushed.value
+        return self._ring_size(_DDPG_RING)
 
     def ddpg_replay_get(self, out=None):
         """The ring's fields, all `capacity` slots: numpy arrays, or copied into the device tensors of the dict `out`.  Synchronises."""
-        if out is None:
-            out = {k: v for k, v in ddpg_ring(self.ddpg_replay_capacity, self.R).items() if k != "pushed"}
-        ring = capi.fill_pointers(capi.OkenvDdpgRing(), out, "ddpg ring")
-        capi.check(self._L.okenv_ddpg_replay_get(self._h, C.byref(ring)), self._h)
-        return out
+        return self._ring_get(_DDPG_RING, out)
 
     def ddpg_update(self, B, iterations, resample=False, draw_base=0, out=None):
         """okenv_ddpg_update: `iterations` iterations on batches of B uniform samples of the ring, four kernels each on the handle's
@@ -771,9 +746,7 @@ class BatchedEnvironment:
     def ddpg_timing(self):
         """Device microseconds of the latest ddpg_update that ran with set_timing(True), summed over its iterations, by
         capi.DDPG_KERNELS."""
-        ms = (C.c_double * 4)()
-        capi.check(self._L.okenv_debug_ddpg_timing(self._h, C.cast(ms, C.c_void_p)), self._h)
-        return {k: 1000.0 * v for k, v in zip(capi.DDPG_KERNELS, ms)}
+        return self._timing("okenv_debug_ddpg_timing", capi.DDPG_KERNELS)
 
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):
@@ -1008,33 +981,44 @@ def ppo_update_host(params, shape, state, batch, B, epochs=1, order=None, want=(
     return new, outs
 
 
-def replay_ring(capacity, num_rays):
-    """An empty replay ring on the host: dict of zeroed numpy arrays and "pushed" = 0."""
-    return {"state": np.zeros((capacity, num_rays), np.float32), "next_state": np.zeros((capacity, num_rays), np.float32),
-            "action": np.zeros(capacity, np.int64), "reward": np.zeros(capacity, np.float32), "done": np.zeros(capacity, np.float32), "pushed": 0}
+def _host_ring(kind, capacity, num_rays, new=np.zeros):
+    return {"state": new((capacity, num_rays), np.float32), "next_state": new((capacity, num_rays), np.float32),
+            "action": new((capacity,) + kind.action_shape, kind.action_dtype), "reward": new(capacity, np.float32),
+            "done": new(capacity, np.float32), "pushed": 0}
 
 
-def _ring_struct(ring):
-    return capi.fill_pointers(capi.OkenvReplayRing(), {k: v for k, v in ring.items() if k != "pushed"}, "replay ring")
+def _ring_struct(kind, ring):
+    return capi.fill_pointers(kind.ring_struct(), {k: v for k, v in ring.items() if k != "pushed"}, "replay ring")
 
 
-def replay_push_host(ring, state, action, alive, dist, crashed, reward=None, push_all=False):
-    """One push on host arrays, no GPU needed (okenv_replay_push_host): `ring` (replay_ring(...)) is updated in place, "pushed"
-    included.  state [n,R], action [n] int64 and alive [n] are the actor record, dist [n,R] and crashed [n] the fields after the step."""
+def _push_host(kind, ring, state, action, alive, dist, crashed, reward, push_all):
     Cn, R = ring["state"].shape
     state = np.ascontiguousarray(state, dtype=np.float32)
-    action = np.ascontiguousarray(action, dtype=np.int64)
+    action = np.ascontiguousarray(action, dtype=kind.action_dtype)
     alive = None if alive is None else np.ascontiguousarray(alive).astype(np.uint8)
     dist = np.ascontiguousarray(dist, dtype=np.float32)
     crashed = np.ascontiguousarray(crashed).astype(np.uint8)
     reward = None if reward is None else np.ascontiguousarray(reward, dtype=np.float32)
     n = action.shape[0]
     assert state.shape == (n, R) and dist.shape == (n, R) and crashed.shape == (n,)
+    assert not kind.action_shape or action.shape == (n,) + kind.action_shape  # (Deep-Q's one index per agent was never checked)
     pushed = C.c_uint64(int(ring["pushed"]))
-    capi.check(capi.load().okenv_replay_push_host(C.byref(_ring_struct(ring)), Cn, R, C.byref(pushed), capi.REPLAY_PUSH_ALL if push_all else 0, n,
-                                                  capi.ptr(state), capi.ptr(action), capi.ptr(alive), capi.ptr(dist), capi.ptr(crashed), capi.ptr(reward)))
+    entry = getattr(capi.load(), kind.prefix + "_push_host")
+    capi.check(entry(C.byref(_ring_struct(kind, ring)), Cn, R, C.byref(pushed), capi.REPLAY_PUSH_ALL if push_all else 0, n, capi.ptr(state),
+                     capi.ptr(action), capi.ptr(alive), capi.ptr(dist), capi.ptr(crashed), capi.ptr(reward)))
     ring["pushed"] = int(pushed.value)
     return ring
+
+
+def replay_ring(capacity, num_rays):
+    """An empty replay ring on the host: dict of zeroed numpy arrays and "pushed" = 0."""
+    return _host_ring(_DQN_RING, capacity, num_rays)
+
+
+def replay_push_host(ring, state, action, alive, dist, crashed, reward=None, push_all=False):
+    """One push on host arrays, no GPU needed (okenv_replay_push_host): `ring` (replay_ring(...)) is updated in place, "pushed"
+    included.  state [n,R], action [n] int64 and alive [n] are the actor record, dist [n,R] and crashed [n] the fields after the step."""
+    return _push_host(_DQN_RING, ring, state, action, alive, dist, crashed, reward, push_all)
 
 
 def dqn_update_host(params, config, shape, state, ring, B, iterations=1, resample=False, draw_base=0, target=None, size=None,
@@ -1052,7 +1036,7 @@ def dqn_update_host(params, config, shape, state, ring, B, iterations=1, resampl
     outs = {k: np.zeros(sizes[k][0], dtype=sizes[k][1]) for k in want}
     target = None if target is None else np.ascontiguousarray(target, dtype=np.float32).ravel()
     capi.check(capi.load().okenv_dqn_update_host(C.byref(params) if params is not None else None, C.byref(config) if config is not None else None,
-                                                 R, H, A, C.byref(st), capi.ptr(target), C.byref(_ring_struct(ring)), size, int(B), int(iterations),
+                                                 R, H, A, C.byref(st), capi.ptr(target), C.byref(_ring_struct(_DQN_RING, ring)), size, int(B), int(iterations),
                                                  1 if resample else 0, int(draw_base) & 0xFFFFFFFF,
                                                  C.byref(capi.fill_pointers(capi.OkenvDqnOutput(), {k: v for k, v in outs.items() if v.size}, "dqn output"))))
     new["t"] = int(st.t)
@@ -1078,31 +1062,13 @@ def ddpg_act_host(config, actor, dist, crashed=None, draw_index=0):
 
 def ddpg_ring(capacity, num_rays):
     """An empty DDPG replay ring on the host: dict of zeroed numpy arrays (action [C, 2] float32) and "pushed" = 0."""
-    return {"state": np.zeros((capacity, num_rays), np.float32), "next_state": np.zeros((capacity, num_rays), np.float32),
-            "action": np.zeros((capacity, 2), np.float32), "reward": np.zeros(capacity, np.float32), "done": np.zeros(capacity, np.float32), "pushed": 0}
-
-
-def _ddpg_ring_struct(ring):
-    return capi.fill_pointers(capi.OkenvDdpgRing(), {k: v for k, v in ring.items() if k != "pushed"}, "ddpg ring")
+    return _host_ring(_DDPG_RING, capacity, num_rays)
 
 
 def ddpg_replay_push_host(ring, state, action, alive, dist, crashed, reward=None, push_all=False):
     """One push on host arrays, no GPU needed (okenv_ddpg_replay_push_host): `ring` (ddpg_ring(...)) is updated in place, "pushed"
     included.  state [n,R], action [n,2] and alive [n] are the record, dist [n,R] and crashed [n] the fields after the step."""
-    Cn, R = ring["state"].shape
-    state = np.ascontiguousarray(state, dtype=np.float32)
-    action = np.ascontiguousarray(action, dtype=np.float32)
-    alive = None if alive is None else np.ascontiguousarray(alive).astype(np.uint8)
-    dist = np.ascontiguousarray(dist, dtype=np.float32)
-    crashed = np.ascontiguousarray(crashed).astype(np.uint8)
-    reward = None if reward is None else np.ascontiguousarray(reward, dtype=np.float32)
-    n = action.shape[0]
-    assert state.shape == (n, R) and action.shape == (n, 2) and dist.shape == (n, R) and crashed.shape == (n,)
-    pushed = C.c_uint64(int(ring["pushed"]))
-    capi.check(capi.load().okenv_ddpg_replay_push_host(C.byref(_ddpg_ring_struct(ring)), Cn, R, C.byref(pushed), capi.REPLAY_PUSH_ALL if push_all else 0, n,
-                                                       capi.ptr(state), capi.ptr(action), capi.ptr(alive), capi.ptr(dist), capi.ptr(crashed), capi.ptr(reward)))
-    ring["pushed"] = int(pushed.value)
-    return ring
+    return _push_host(_DDPG_RING, ring, state, action, alive, dist, crashed, reward, push_all)
 
 
 def ddpg_update_host(config, num_rays, state, ring, B, iterations=1, resample=False, draw_base=0, size=None,
@@ -1120,7 +1086,7 @@ def ddpg_update_host(config, num_rays, state, ring, B, iterations=1, resample=Fa
              "grad_critic": (max(Hc * (R + 2) + 2 * Hc + 1, 0), np.float32), "grad_actor": (max(H * R + 3 * H + 2, 0), np.float32),
              "index": (max(int(B), 0), np.int32)}
     outs = {k: np.zeros(sizes[k][0], dtype=sizes[k][1]) for k in want}
-    capi.check(capi.load().okenv_ddpg_update_host(C.byref(config) if config is not None else None, R, C.byref(st), C.byref(_ddpg_ring_struct(ring)), size,
+    capi.check(capi.load().okenv_ddpg_update_host(C.byref(config) if config is not None else None, R, C.byref(st), C.byref(_ring_struct(_DDPG_RING, ring)), size,
                                                   int(B), int(iterations), 1 if resample else 0, int(draw_base) & 0xFFFFFFFF,
                                                   C.byref(capi.fill_pointers(capi.OkenvDdpgOutput(), {k: v for k, v in outs.items() if v.size}, "ddpg output"))))
     new["t"] = int(st.t)

@@ -6,6 +6,7 @@ into one shared buffer -- crashed agents keep contributing their frozen observat
 for N agents with everything kept on the GPU as [T, N, ...] tensors; `alive[t, i]` marks the entries an agent produced
 before it crashed, so a learner can mask the frozen tail (or keep it, as the reference does).
 """
+import collections
 import warnings
 
 import torch
@@ -18,6 +19,71 @@ PPO_ACTIONS = ((60.0, 0.0), (30.0, 5.0), (30.0, -5.0))
 DQN_ACTIONS = ((60.0, 0.0), (30.0, 5.0), (30.0, -5.0), (30.0, 2.5), (30.0, -2.5))
 
 
+# What a collector hands _run_episode for graph_chunk = K > 0: the cache `graphs` and the `key` of its captured chunk in it; the acting
+# object's actor_set_draw_offset / ddpg_set_draw_offset; build() -> (iteration(k) for the chunk's k-th iteration, the tensors the graph
+# reads and writes), called when the chunk has to be captured; after_replay(steps, tensors), or None, called after every replay.
+_Chunk = collections.namedtuple("_Chunk", "K graphs key set_draw_offset build after_replay")
+
+
+def _run_episode(venv, iteration, max_steps, check_every, chunk=None):
+    """The episode loop of every collector: reset, then iteration(t) for t = 0, 1, ... until nobody is alive -- tested with
+    alive_count(), which synchronises, on the multiples of `check_every` only -- or `max_steps` steps have run.  Returns (the host's
+    step count after the reset, steps taken).
+
+    chunk (a _Chunk) with K > 0: the loop replays a HIP graph of K iterations instead and tests once per replay, so the steps are a
+    multiple of K.  The graph is chunk.graphs[chunk.key]; when it is not there, it is captured from chunk.build() and kept there with
+    the tensors it reads and writes."""
+    venv.reset()  # resetAgent for every agent + the initial-observation step (ppo_sim.cpp:53-60)
+    start = venv.env.step_count
+    steps, stride, offset = 0, 1, None
+    K = 0 if chunk is None else chunk.K
+    if K > 0:
+        graphs, key, set_draw_offset = chunk.graphs, chunk.key, chunk.set_draw_offset
+        if key not in graphs:
+            chunk_iteration, kept = chunk.build()
+            # Without auto-reset the step kernels do not advance the device-side step count, and a captured act carries the host's
+            # count of the moment of capture: the graph's last node advances a word of ours by K instead (the act kernels add it).
+            offset = None if venv.auto_reset else torch.zeros(1, dtype=torch.int32, device=venv.device)
+
+            def body():
+                for k in range(K):
+                    chunk_iteration(k)
+                if offset is not None:
+                    offset.add_(K)
+
+            base = venv.env.step_count
+            if offset is not None:
+                offset.add_(0)  # torch's own kernel is loaded before the capture; ours are already
+            set_draw_offset(offset)  # the captured launches keep the pointer; eager calls afterwards get none
+            try:
+                # no warm-up iterations: they would push into a ring and move the count the launches are captured with
+                graph = venv.capture(body, warmup=0)
+            finally:
+                set_draw_offset(None)
+            graphs[key] = (graph, offset, base, kept)  # (the tensors are the graph's: kept alive with it)
+        graph, offset, base, kept = graphs[key]
+        if offset is not None:  # the captured launches carry base + k as their draw index
+            offset.fill_(((start - base + 2 ** 31) % 2 ** 32) - 2 ** 31)
+        stride = check_every = K  # one test per replay
+    try:
+        while True:
+            if K > 0:
+                graph.replay()
+                if chunk.after_replay is not None:
+                    chunk.after_replay(steps, kept)
+            else:
+                iteration(steps)
+            steps += stride
+            if steps % check_every == 0 and venv.env.alive_count() == 0:
+                break
+            if max_steps is not None and steps >= max_steps:
+                break
+    finally:
+        if offset is not None:
+            venv.env.step_count = start + steps  # (replays do not advance the host's count)
+    return start, steps
+
+
 def collect_episode(venv, policy, max_steps=None, check_every=8, actions=PPO_ACTIONS):
     """One pass of the episode loop (ppo_sim.cpp:49-89).
 
@@ -28,11 +94,9 @@ def collect_episode(venv, policy, max_steps=None, check_every=8, actions=PPO_ACT
     assert venv.reward_kind == capi.REWARD_STEP, 'create the VectorEnvironment with reward="step"'
     assert not venv.auto_reset or max_steps is not None, "with auto-reset on the episode never ends: pass max_steps"
     table = torch.tensor(actions, dtype=torch.float32, device=venv.device)
-    # resetAgent for every agent + the initial-observation step (ppo_sim.cpp:53-60)
-    venv.reset()
     states, acts, logps, rewards, alive = [], [], [], [], []
-    steps = 0
-    while True:
+
+    def iteration(_):
         state = venv.observation()
         with torch.no_grad():
             probs = torch.clamp(policy(state), 1e-8, 1.0 - 1e-8)        # kProbClamp (PPOAgent.hpp:27,83)
@@ -44,11 +108,8 @@ def collect_episode(venv, policy, max_steps=None, check_every=8, actions=PPO_ACT
         logps.append(logp)
         venv.step(table[action])
         rewards.append(venv.reward.clone())
-        steps += 1
-        if steps % check_every == 0 and venv.env.alive_count() == 0:
-            break
-        if max_steps is not None and steps >= max_steps:
-            break
+
+    _run_episode(venv, iteration, max_steps, check_every)
     return {"states": torch.stack(states), "actions": torch.stack(acts), "log_probs": torch.stack(logps),
             "rewards": torch.stack(rewards), "alive": torch.stack(alive)}
 
@@ -87,8 +148,11 @@ class _EpisodeBuffers:
         return {k: torch.cat([b[k] for b in self.blocks])[:steps] for k in self.fields}
 
 
-def _record_of(slot):
-    return {k: v for k, v in slot.items() if k != "reward"}
+def _act_step_record(venv, slot):
+    """One iteration of collect_episode_device into the row `slot` of the episode's (or a chunk's) tensors."""
+    venv.actor_act({k: v for k, v in slot.items() if k != "reward"})
+    venv.step()
+    slot["reward"].copy_(venv.reward)
 
 
 def collect_episode_device(venv, max_steps=None, check_every=8, graph_chunk=0):
@@ -108,41 +172,22 @@ def collect_episode_device(venv, max_steps=None, check_every=8, graph_chunk=0):
     assert not venv.auto_reset or max_steps is not None, "with auto-reset on the episode never ends: pass max_steps"
     assert getattr(venv, "_actor_nets", None) is not None, "call venv.enable_actor(actor, critic) first"
     K = int(graph_chunk)
-    venv.reset()
     block = 256 if K <= 0 else K * max(1, 256 // K)
     if max_steps is not None:  # everything in one block: the result is a view
         block = max_steps if K <= 0 else K * ((max_steps + K - 1) // K)
     buf = _EpisodeBuffers(venv, block, venv.actor_has_value)
-    steps = 0
-    start = venv.env.step_count
-    if K <= 0:
-        while True:
-            slot = buf.slot(steps)
-            venv.actor_act(_record_of(slot))
-            venv.step()
-            slot["reward"].copy_(venv.reward)
-            steps += 1
-            if steps % check_every == 0 and venv.env.alive_count() == 0:
-                break
-            if max_steps is not None and steps >= max_steps:
-                break
-    else:
-        graph, chunk, offset, base = _chunk_graph(venv, K)
-        if offset is not None:  # the captured launches carry base + k as their draw index
-            offset.fill_(((start - base + 2 ** 31) % 2 ** 32) - 2 ** 31)
-        try:
-            while True:
-                graph.replay()
-                for k, dst in buf.rows(steps, K).items():
-                    dst.copy_(chunk[k])
-                steps += K
-                if venv.env.alive_count() == 0:
-                    break
-                if max_steps is not None and steps >= max_steps:
-                    break
-        finally:
-            if offset is not None:
-                venv.env.step_count = start + steps  # (replays do not advance the host's count)
+
+    def build():
+        chunk = _EpisodeBuffers(venv, K, venv.actor_has_value).rows(0, K)
+        chunk["reward"][0].copy_(venv.reward)  # torch's own kernels are loaded before the capture; ours are already
+        return (lambda k: _act_step_record(venv, {name: t[k] for name, t in chunk.items()})), chunk
+
+    def copy_rows(steps, chunk):  # one device-to-device copy per field into the episode's tensors
+        for name, dst in buf.rows(steps, K).items():
+            dst.copy_(chunk[name])
+
+    captured = _Chunk(K=K, graphs=venv._actor_graphs, key=K, set_draw_offset=venv.env.actor_set_draw_offset, build=build, after_replay=copy_rows)
+    start, steps = _run_episode(venv, lambda t: _act_step_record(venv, buf.slot(t)), max_steps, check_every, captured)
     out = buf.finish(steps)
     T = steps
     if not venv.auto_reset:  # the reference loop's length: the rows in which somebody was still driving
@@ -156,37 +201,6 @@ def collect_episode_device(venv, max_steps=None, check_every=8, graph_chunk=0):
     if venv.actor_has_value:
         res["values"] = out["value"][:T]
     return res
-
-
-def _chunk_graph(venv, K):
-    """The captured chunk of K iterations for this environment: (graph, chunk tensors, draw-offset word or None, the host step
-    count the launches were captured with)."""
-    if K in venv._actor_graphs:
-        return venv._actor_graphs[K]
-    chunk = _EpisodeBuffers(venv, K, venv.actor_has_value).rows(0, K)
-    # Without auto-reset the step kernels do not advance the device-side step count, and a captured okenv_actor_act carries the
-    # host's count of the moment of capture: the graph's last node advances a word of ours by K instead (okenv_actor_act adds it).
-    offset = None if venv.auto_reset else torch.zeros(1, dtype=torch.int32, device=venv.device)
-
-    def body():
-        for k in range(K):
-            venv.actor_act({name: t[k] for name, t in chunk.items() if name != "reward"})
-            venv.step()
-            chunk["reward"][k].copy_(venv.reward)
-        if offset is not None:
-            offset.add_(K)
-
-    base = venv.env.step_count
-    chunk["reward"][0].copy_(venv.reward)  # torch's own kernels are loaded before the capture; ours are already
-    if offset is not None:
-        offset.add_(0)
-    venv.env.actor_set_draw_offset(offset)  # the captured launches keep the pointer; eager calls afterwards get none
-    try:
-        graph = venv.capture(body, warmup=0)  # no warm-up iterations: they would move the count the launches are captured with
-    finally:
-        venv.env.actor_set_draw_offset(None)
-    venv._actor_graphs[K] = (graph, chunk, offset, base)
-    return venv._actor_graphs[K]
 
 
 def _rows_of(x, width):
@@ -336,10 +350,40 @@ def reinforce_update(venv, batch, slice=16384, accumulate=True, reduce="sum", sh
     return out
 
 
-def _dqn_record(venv):
+def _ring_record(venv, action_shape, action_dtype):
+    """The record an act kernel fills and a push reads: "state" [N, R], "action" [N, *action_shape] and "alive" [N]."""
     return {"state": torch.empty((venv.num_envs, venv.num_rays), dtype=torch.float32, device=venv.device),
-            "action": torch.empty(venv.num_envs, dtype=torch.int64, device=venv.device),
+            "action": torch.empty((venv.num_envs,) + action_shape, dtype=action_dtype, device=venv.device),
             "alive": torch.empty(venv.num_envs, dtype=torch.uint8, device=venv.device)}
+
+
+# What tells the Deep-Q collector from the DDPG collector: the act and push methods, the action's shape and dtype in the record, the
+# attribute of venv that keeps the eager episodes' record, the cache of captured chunks with the key's prefix in it, and the setter
+# of the acting object's draw-offset word.
+_RingCollector = collections.namedtuple("_RingCollector", "act push action_shape action_dtype eager_record graphs key set_draw_offset")
+
+
+def _collect_into_ring(venv, kind, max_steps, check_every, K, reward):
+    """What collect_episode_dqn and collect_episode_ddpg share (`kind`: a _RingCollector): `act -> step -> push` on one record, the one
+    kept on venv for eager episodes and one of its own for every captured chunk, which also keeps `reward`."""
+    def iteration_on(rec):
+        def iteration(_):
+            kind.act(rec)
+            venv.step()
+            kind.push(rec, reward)
+        return iteration
+
+    def build():
+        rec = _ring_record(venv, kind.action_shape, kind.action_dtype)
+        return iteration_on(rec), (rec, reward)
+
+    rec = None
+    if K <= 0:
+        rec = getattr(venv, kind.eager_record, None) or _ring_record(venv, kind.action_shape, kind.action_dtype)
+        setattr(venv, kind.eager_record, rec)
+    chunk = _Chunk(K=K, graphs=kind.graphs, key=kind.key + (K, None if reward is None else reward.data_ptr()),
+                   set_draw_offset=kind.set_draw_offset, build=build, after_replay=None)
+    return {"steps": _run_episode(venv, iteration_on(rec), max_steps, check_every, chunk)[1]}
 
 
 def collect_episode_dqn(venv, max_steps=None, check_every=8, graph_chunk=0, reward=None):
@@ -361,67 +405,9 @@ def collect_episode_dqn(venv, max_steps=None, check_every=8, graph_chunk=0, rewa
     if isinstance(reward, str):
         assert reward == "tracker" and venv.reward_kind is not None, 'reward="tracker" needs a VectorEnvironment with a reward'
         reward = venv.reward
-    K = int(graph_chunk)
-    venv.reset()
-    steps = 0
-    start = venv.env.step_count
-    if K <= 0:
-        rec = getattr(venv, "_dqn_rec", None) or _dqn_record(venv)
-        venv._dqn_rec = rec
-        while True:
-            venv.actor_act(rec)
-            venv.step()
-            venv.replay_push(rec, reward)
-            steps += 1
-            if steps % check_every == 0 and venv.env.alive_count() == 0:
-                break
-            if max_steps is not None and steps >= max_steps:
-                break
-        return {"steps": steps}
-    graph, offset, base = _dqn_chunk_graph(venv, K, reward)
-    if offset is not None:  # the captured launches carry base + k as their draw index
-        offset.fill_(((start - base + 2 ** 31) % 2 ** 32) - 2 ** 31)
-    try:
-        while True:
-            graph.replay()
-            steps += K
-            if venv.env.alive_count() == 0:
-                break
-            if max_steps is not None and steps >= max_steps:
-                break
-    finally:
-        if offset is not None:
-            venv.env.step_count = start + steps  # (replays do not advance the host's count)
-    return {"steps": steps}
-
-
-def _dqn_chunk_graph(venv, K, reward):
-    """The captured chunk of K iterations of collect_episode_dqn: (graph, draw-offset word or None, the host step count the launches
-    were captured with); see _chunk_graph."""
-    key = ("dqn", K, None if reward is None else reward.data_ptr())
-    if key in venv._actor_graphs:
-        return venv._actor_graphs[key][:3]
-    rec = _dqn_record(venv)
-    offset = None if venv.auto_reset else torch.zeros(1, dtype=torch.int32, device=venv.device)
-
-    def body():
-        for _ in range(K):
-            venv.actor_act(rec)
-            venv.step()
-            venv.replay_push(rec, reward)
-        if offset is not None:
-            offset.add_(K)
-
-    base = venv.env.step_count
-    if offset is not None:
-        offset.add_(0)  # torch's own kernel is loaded before the capture; ours are already
-    venv.env.actor_set_draw_offset(offset)  # the captured launches keep the pointer; eager calls afterwards get none
-    try:
-        graph = venv.capture(body, warmup=0)  # no warm-up iterations: they would push into the ring and move the count
-    finally:
-        venv.env.actor_set_draw_offset(None)
-    venv._actor_graphs[key] = (graph, offset, base, rec, reward)  # (the record and the reward are the graph's: kept alive with it)
-    return graph, offset, base
+    kind = _RingCollector(act=venv.actor_act, push=venv.replay_push, action_shape=(), action_dtype=torch.int64, eager_record="_dqn_rec",
+                          graphs=venv._actor_graphs, key=("dqn",), set_draw_offset=venv.env.actor_set_draw_offset)
+    return _collect_into_ring(venv, kind, max_steps, check_every, int(graph_chunk), reward)
 
 
 def dqn_update(venv, batch=100, iterations=200, resample=False, draw=None, grads=False):
@@ -448,12 +434,6 @@ def dqn_update(venv, batch=100, iterations=200, resample=False, draw=None, grads
     return out if grads else out["loss"]
 
 
-def _ddpg_record(venv):
-    return {"state": torch.empty((venv.num_envs, venv.num_rays), dtype=torch.float32, device=venv.device),
-            "action": torch.empty((venv.num_envs, 2), dtype=torch.float32, device=venv.device),
-            "alive": torch.empty(venv.num_envs, dtype=torch.uint8, device=venv.device)}
-
-
 def collect_episode_ddpg(venv, max_steps=None, check_every=8, graph_chunk=0, reward=None):
     """One episode of ddpg_sim.cpp:55-95 on the device: reset, then `ddpg_act -> step -> ddpg_replay_push` until every agent has
     crashed (tested every `check_every` steps) or `max_steps` steps have run.  The transitions go straight into the ring of
@@ -471,67 +451,9 @@ def collect_episode_ddpg(venv, max_steps=None, check_every=8, graph_chunk=0, rew
     if isinstance(reward, str):
         assert reward == "tracker" and venv.reward_kind is not None, 'reward="tracker" needs a VectorEnvironment with a reward'
         reward = venv.reward
-    K = int(graph_chunk)
-    venv.reset()
-    steps = 0
-    start = venv.env.step_count
-    if K <= 0:
-        rec = getattr(venv, "_ddpg_rec", None) or _ddpg_record(venv)
-        venv._ddpg_rec = rec
-        while True:
-            venv.ddpg_act(rec)
-            venv.step()
-            venv.ddpg_replay_push(rec, reward)
-            steps += 1
-            if steps % check_every == 0 and venv.env.alive_count() == 0:
-                break
-            if max_steps is not None and steps >= max_steps:
-                break
-        return {"steps": steps}
-    graph, offset, base = _ddpg_chunk_graph(venv, K, reward)
-    if offset is not None:  # the captured launches carry base + k as their draw index
-        offset.fill_(((start - base + 2 ** 31) % 2 ** 32) - 2 ** 31)
-    try:
-        while True:
-            graph.replay()
-            steps += K
-            if venv.env.alive_count() == 0:
-                break
-            if max_steps is not None and steps >= max_steps:
-                break
-    finally:
-        if offset is not None:
-            venv.env.step_count = start + steps  # (replays do not advance the host's count)
-    return {"steps": steps}
-
-
-def _ddpg_chunk_graph(venv, K, reward):
-    """The captured chunk of K iterations of collect_episode_ddpg: (graph, draw-offset word or None, the host step count the launches
-    were captured with); see _dqn_chunk_graph."""
-    key = (K, None if reward is None else reward.data_ptr())
-    if key in venv._ddpg_graphs:
-        return venv._ddpg_graphs[key][:3]
-    rec = _ddpg_record(venv)
-    offset = None if venv.auto_reset else torch.zeros(1, dtype=torch.int32, device=venv.device)
-
-    def body():
-        for _ in range(K):
-            venv.ddpg_act(rec)
-            venv.step()
-            venv.ddpg_replay_push(rec, reward)
-        if offset is not None:
-            offset.add_(K)
-
-    base = venv.env.step_count
-    if offset is not None:
-        offset.add_(0)  # torch's own kernel is loaded before the capture; ours are already
-    venv.env.ddpg_set_draw_offset(offset)  # the captured launches keep the pointer; eager calls afterwards get none
-    try:
-        graph = venv.capture(body, warmup=0)  # no warm-up iterations: they would push into the ring and move the count
-    finally:
-        venv.env.ddpg_set_draw_offset(None)
-    venv._ddpg_graphs[key] = (graph, offset, base, rec, reward)  # (the record and the reward are the graph's: kept alive with it)
-    return graph, offset, base
+    kind = _RingCollector(act=venv.ddpg_act, push=venv.ddpg_replay_push, action_shape=(2,), action_dtype=torch.float32, eager_record="_ddpg_rec",
+                          graphs=venv._ddpg_graphs, key=(), set_draw_offset=venv.env.ddpg_set_draw_offset)
+    return _collect_into_ring(venv, kind, max_steps, check_every, int(graph_chunk), reward)
 
 
 def ddpg_update(venv, batch=250, iterations=50, resample=True, draw=None, grads=False):

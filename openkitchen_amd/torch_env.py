@@ -227,17 +227,34 @@ class VectorEnvironment:
             raise ValueError("%s: expected a module or the four tensors l1.weight, l1.bias, l2.weight, l2.bias" % what)
         return t
 
-    def _check_network(self, t, what, outputs=None):
+    @staticmethod
+    def _check_network(t, what, inputs, outputs=None, max_hidden=None):
+        """(hidden width, outputs) of the four tensors of an inputs -> H -> outputs network (outputs None: any); ValueError otherwise."""
         w1, b1, w2, b2 = t
         hidden = w1.shape[0] if w1.dim() == 2 else -1
         out = w2.shape[0] if w2.dim() == 2 else -1
-        if (tuple(w1.shape) != (hidden, self.num_rays) or tuple(b1.shape) != (hidden,) or tuple(w2.shape) != (out, hidden)
+        if (tuple(w1.shape) != (hidden, inputs) or tuple(b1.shape) != (hidden,) or tuple(w2.shape) != (out, hidden)
                 or tuple(b2.shape) != (out,) or (outputs is not None and out != outputs)):
-            raise ValueError("%s: shapes %s do not form a %d -> H -> %s network" % (what, [tuple(x.shape) for x in t], self.num_rays,
+            raise ValueError("%s: shapes %s do not form a %d -> H -> %s network" % (what, [tuple(x.shape) for x in t], inputs,
                                                                                  "A" if outputs is None else outputs))
-        if not 1 <= hidden <= capi.ACTOR_MAX_HIDDEN:
-            raise ValueError("%s: hidden width %d outside 1 .. %d" % (what, hidden, capi.ACTOR_MAX_HIDDEN))
+        if max_hidden is not None and not 1 <= hidden <= max_hidden:
+            raise ValueError("%s: hidden width %d outside 1 .. %d" % (what, hidden, max_hidden))
         return hidden, out
+
+    def _flatten(self, tensors):
+        """The tensors of one network as one float32 vector on the device, in parameters() order; None stays None."""
+        if tensors is None:
+            return None
+        return torch.cat([x.detach().reshape(-1) for x in tensors]).to(device=self.device, dtype=torch.float32).contiguous()
+
+    @staticmethod
+    def _unflatten(tensors, vec):
+        """_flatten's inverse: copies the vector's pieces back into the tensors."""
+        at = 0
+        with torch.no_grad():
+            for x in tensors or ():
+                x.copy_(vec[at:at + x.numel()].reshape(x.shape))
+                at += x.numel()
 
     def enable_actor(self, actor, critic=None, mode="sample", actions=None, epsilon=0.0):
         """Attaches the reference's shared-network agent (RLRacers/PPO, Reinforce, Deep_Q_Learning): `actor` is
@@ -248,10 +265,10 @@ class VectorEnvironment:
         from .rollout import PPO_ACTIONS
         actions = PPO_ACTIONS if actions is None else actions
         self._actor_nets = (self._network_tensors(actor, "actor"), None if critic is None else self._network_tensors(critic, "critic"))
-        hidden, n_actions = self._check_network(self._actor_nets[0], "actor")
+        hidden, n_actions = self._check_network(self._actor_nets[0], "actor", self.num_rays, max_hidden=capi.ACTOR_MAX_HIDDEN)
         if n_actions != len(actions) or not 2 <= n_actions <= capi.ACTOR_MAX_ACTIONS:
             raise ValueError("actor: %d outputs for a table of %d actions (2 .. %d)" % (n_actions, len(actions), capi.ACTOR_MAX_ACTIONS))
-        value_hidden = 0 if critic is None else self._check_network(self._actor_nets[1], "critic", outputs=1)[0]
+        value_hidden = 0 if critic is None else self._check_network(self._actor_nets[1], "critic", self.num_rays, 1, capi.ACTOR_MAX_HIDDEN)[0]
         self.env.actor_create(hidden, actions, value_hidden, mode, epsilon, self.seed, self.agent_base)
         self.actor_has_value = critic is not None
         self.actor_dropout = 0.0  # (a new device actor starts without dropout)
@@ -261,8 +278,7 @@ class VectorEnvironment:
     def sync_actor(self):
         """The current parameters of the networks given to enable_actor, flattened in parameters() order and copied device to
         device on the environment's stream: no host hop, no synchronisation."""
-        flat = [None if t is None else torch.cat([x.detach().reshape(-1) for x in t]).to(device=self.device, dtype=torch.float32).contiguous()
-                for t in self._actor_nets]
+        flat = [self._flatten(t) for t in self._actor_nets]
         self.env.actor_set_params(flat[0], flat[1])
         self._actor_flat = flat  # alive until the next hand-over: the copy is asynchronous
 
@@ -280,12 +296,8 @@ class VectorEnvironment:
         flat = [torch.empty(n, dtype=torch.float32, device=self.device) if t is not None else None
                 for t, n in zip(self._actor_nets, (n_policy, n_value))]
         self.env.actor_get_params(out=flat)
-        with torch.no_grad():
-            for tensors, vec in zip(self._actor_nets, flat):
-                at = 0
-                for x in tensors or ():
-                    x.copy_(vec[at:at + x.numel()].reshape(x.shape))
-                    at += x.numel()
+        for tensors, vec in zip(self._actor_nets, flat):
+            self._unflatten(tensors, vec)
 
     def set_actor_epsilon(self, epsilon):
         self.env.actor_set_epsilon(epsilon)
@@ -338,19 +350,14 @@ class VectorEnvironment:
         beta1, beta2, eps, sample_seed).  The online and the target networks on the device start from the modules' parameters;
         rollout.ddpg_update steps them in place, and pull_ddpg() copies the online ones back into the modules."""
         nets = (self._network_tensors(actor, "actor"), self._network_tensors(critic, "critic"))
-        widths = []
-        for t, what, n_in, n_out in ((nets[0], "actor", self.num_rays, 2), (nets[1], "critic", self.num_rays + 2, 1)):
-            hidden = t[0].shape[0] if t[0].dim() == 2 else -1
-            if [tuple(x.shape) for x in t] != [(hidden, n_in), (hidden,), (n_out, hidden), (n_out,)]:
-                raise ValueError("%s: shapes %s do not form a %d -> H -> %d network" % (what, [tuple(x.shape) for x in t], n_in, n_out))
-            widths.append(hidden)
+        widths = (self._check_network(nets[0], "actor", self.num_rays, 2)[0], self._check_network(nets[1], "critic", self.num_rays + 2, 1)[0])
         config.setdefault("seed", self.seed)
         config.setdefault("agent_base", self.agent_base)
         config.setdefault("sample_seed", self.seed)
         self.env.ddpg_create(widths[0], widths[1], **config)
         self._ddpg_nets = nets
         self._ddpg_graphs = {}
-        flat = [torch.cat([x.detach().reshape(-1) for x in t]).to(device=self.device, dtype=torch.float32).contiguous() for t in nets]
+        flat = [self._flatten(t) for t in nets]
         self.env.ddpg_set_params(flat[0], flat[1])
         self._ddpg_flat = flat  # alive until the next hand-over: the copy is asynchronous
 
@@ -358,12 +365,8 @@ class VectorEnvironment:
         """Copies the device's online actor and critic back into the modules (or tensors) given to enable_ddpg."""
         flat = {k: torch.empty(n, dtype=torch.float32, device=self.device) for k, n in zip(("actor", "critic"), self.env.ddpg_num_params())}
         self.env.ddpg_state(out=flat)
-        with torch.no_grad():
-            for tensors, vec in zip(self._ddpg_nets, (flat["actor"], flat["critic"])):
-                at = 0
-                for x in tensors:
-                    x.copy_(vec[at:at + x.numel()].reshape(x.shape))
-                    at += x.numel()
+        for tensors, vec in zip(self._ddpg_nets, (flat["actor"], flat["critic"])):
+            self._unflatten(tensors, vec)
 
     def ddpg_act(self, record=None):
         """The continuous action of every agent from the last observation, written into `throttle` / `steering`: one kernel on the
