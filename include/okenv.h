@@ -1014,6 +1014,27 @@ OKENV_API int okenv_debug_reinforce_timing(okenv_t h, double *ms2);
 OKENV_API int okenv_debug_adam(const okenv_learner_params *params, int64_t t, float *p, float *m, float *v, const float *g, int32_t n);
 /* ok_sincosf evaluated on the GPU (n values, host pointers). */
 OKENV_API int okenv_debug_sincos(int32_t device, const float *x, float *s, float *c, int32_t n);
+/* One leaf function of include/okenv_math.h on n values (host pointers), evaluated on GPU `device` by one elementwise kernel, or,
+ * with device == OKENV_DEBUG_ON_HOST, by the host compilation of the same header inside the library (no GPU needed).  The two must
+ * agree bit for bit: tests/test_gpu_math.py runs both over the whole argument range.  `b` is read by OKENV_FN_ATAN2 only (a = y,
+ * b = x); `out1` is written by OKENV_FN_SINCOS only (out0 = sine, out1 = cosine); both may be NULL otherwise. */
+enum okenv_debug_fn {
+    OKENV_FN_SINCOS,                 /* ok_sincosf */
+    OKENV_FN_TANH,                   /* ok_tanhf */
+    OKENV_FN_EXP,                    /* ok_expf */
+    OKENV_FN_LOG,                    /* ok_logf */
+    OKENV_FN_ATAN2,                  /* ok_atan2f(a, b) */
+    OKENV_FN_NORMALIZE_ANGLE,        /* ok_normalize_angle_deg */
+    OKENV_FN_EXPERT_NORMALIZE_ANGLE, /* ok_expert_normalize_angle_deg */
+    OKENV_NUM_DEBUG_FNS
+};
+#define OKENV_DEBUG_ON_HOST (-1)
+OKENV_API int okenv_debug_math(int32_t device, int32_t fn, const float *a, const float *b, float *out0, float *out1, int32_t n);
+/* okenv_debug_adam with ok_learn_adam evaluated per element on GPU `device` (ok_learn_factors on the host, as in every learner); the
+ * arrays are host pointers and are updated in place.  device == OKENV_DEBUG_ON_HOST evaluates on the host.  Unlike the learners'
+ * entries this one accepts eps == 0, so that the division's zero and infinite denominators can be compared too. */
+OKENV_API int okenv_debug_adam_device(int32_t device, const okenv_learner_params *params, int64_t t, float *p, float *m, float *v, const float *g,
+                                      int32_t n);
 /* First-hit parameter t for n arbitrary rays (origin, angle [rad]) through the handle's grid (host pointers). */
 OKENV_API int okenv_debug_cast_rays(okenv_t h, const float *ox, const float *oy, const float *angle_rad, int32_t n, float *out_t);
 

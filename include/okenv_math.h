@@ -450,7 +450,9 @@ OK_HD float ok_tanhf(const float x)
  * error 2^-48), exp x = 2^n (1 + m): the sum is one fp64 rounding, the scaling by 2^n is exact (n >= -289: a normal double), and the
  * conversion to fp32 is the single rounding into fp32 -- subnormal results included, the conversion rounds those correctly too.
  * Arguments below -200 count as -200 (the result is 0 from -104 on), so -inf gives 0; NaN stays NaN.  Arguments above 0 are not
- * the softmax's business: they are evaluated by the same formula up to +200 (inf from 88.73 on) and nothing tests them.
+ * the softmax's business: they are evaluated by the same formula up to +200 (inf from 88.73 on); tests/test_math_cases.py (host) and tests/test_gpu_math.py (device)
+ * run every 256th float and the neighbourhoods of 0, of both clamps, of the first subnormal, the first normal and the first infinite
+ * result and of every tie of rint: equal to the rounded fp64 exp on all of [-200, 88.7], same bits on host and device everywhere.
  * tests/test_actor_rule.py: equal to the rounded fp64 exp on all but a few of a million arguments in [-104, 0], never more than
  * one ulp away. */
 OK_HD float ok_expf(const float x)
@@ -481,8 +483,10 @@ OK_HD float ok_expf(const float x)
  * mantissa reaches sqrt 2), u = (m - 1) / (m + 1), |u| <= 0.1716, log m = 2 atanh u = 2 (u + u^3/3 + u^5/5 + ...): the series' own
  * coefficients 1/(2k + 1), each the correctly rounded quotient of two small integers, up to u^23 (the first term left out is below
  * 2^-59 of the sum), by Horner's rule in FMAs in z = u^2.  Then e ln 2 with ok_expf's split ln 2 = L1 + L2, the small part first.
- * Zero, negative, infinite and NaN arguments are not the loss's business (the probability is clamped to [1e-8, 1]) and nothing
- * tests them.  tests/test_reinforce_rule.py: equal to the rounded fp64 log on all but a few of a million arguments in [1e-8, 1] and
+ * Zero, negative, infinite and NaN arguments are not the loss's business (the probability is clamped to [1e-8, 1]): what they give is
+ * whatever the formula gives, and tests/test_gpu_math.py holds the device to the host's bits for them too.  tests/test_math_cases.py
+ * (host) and tests/test_gpu_math.py (device): equal to the rounded fp64 log on every 256th positive finite float and around 2^k and
+ * sqrt 2 * 2^k for every k, subnormal arguments included.  tests/test_reinforce_rule.py: equal to the rounded fp64 log on all but a few of a million arguments in [1e-8, 1] and
  * on every binade of the positive normal floats, never more than one ulp away.  No gradient depends on it. */
 OK_HD float ok_logf(const float x)
 {

@@ -50,6 +50,9 @@ LEARN_CHUNK = 32
 REINFORCE_SUM, REINFORCE_MEAN = 0, 1
 REINFORCE_REDUCE = {"sum": REINFORCE_SUM, "mean": REINFORCE_MEAN}
 REINFORCE_KERNELS = ("grad", "step")
+# okenv_debug_math (include/okenv.h): enum okenv_debug_fn in order, and the device number that means "evaluate on the host"
+DEBUG_FNS = ("sincos", "tanh", "exp", "log", "atan2", "normalize_angle", "expert_normalize_angle")
+DEBUG_ON_HOST = -1
 
 # every symbol include/okenv.h declares (tests/test_capi_symbols.py checks the library exports them all)
 SYMBOLS = [
@@ -87,6 +90,7 @@ SYMBOLS = [
     "okenv_ddpg_update_host",
     "okenv_actor_set_dropout", "okenv_actor_act_dropout_host", "okenv_reinforce_update", "okenv_reinforce_update_host",
     "okenv_debug_reinforce_timing", "okenv_debug_logf", "okenv_debug_reinforce_mask",
+    "okenv_debug_math", "okenv_debug_adam_device",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -414,6 +418,8 @@ def load(build_if_missing=True):
     L.okenv_track_segments.argtypes = [vp, vp]
     L.okenv_track_queries.argtypes = [vp, vp, vp, i32, vp, vp]
     L.okenv_debug_sincos.argtypes = [i32, vp, vp, vp, i32]
+    L.okenv_debug_math.argtypes = [i32, i32, vp, vp, vp, vp, i32]
+    L.okenv_debug_adam_device.argtypes = [i32, C.POINTER(OkenvLearnerParams), C.c_int64, vp, vp, vp, vp, i32]
     L.okenv_debug_cast_rays.argtypes = [vp, vp, vp, vp, i32, vp]
     L.okenv_debug_step_forms.argtypes = [vp, vp, i32, i32]
     L.okenv_policy_mlp_create.argtypes = [vp, i32, u32, u32]

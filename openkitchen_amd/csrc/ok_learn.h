@@ -319,6 +319,14 @@ __global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okLearnStepKer
     }
 }
 
+// ok_learn_adam alone, one parameter per thread (okenv_debug_adam_device): the Adam of every join kernel above without the join
+__global__ void __launch_bounds__(256) okDebugAdamKernel(float *p, float *m, float *v, const float *g, const ok_learn_adam_consts adam, const unsigned n)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n)
+        ok_learn_adam(p + i, m + i, v + i, g[i], adam);
+}
+
 // ---- host side (no GPU) ------------------------------------------------------------------------------------------------------
 
 inline const char *okLearnCheckParams(const okenv_learner_params *lp)

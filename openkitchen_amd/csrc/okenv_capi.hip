@@ -15,6 +15,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/okenv.h"
@@ -1411,6 +1412,66 @@ OkKnobs readKnobs()
     if (const char *e = std::getenv("OKENV_FRONT_BACK"))
         k.front_back = std::atoi(e);
     return k;
+}
+
+// ---- okenv_debug_math / okenv_debug_adam_device ----
+
+// their device buffer: freed on every way out
+struct DebugBuffer
+{
+    float *d = nullptr;
+    ~DebugBuffer()
+    {
+        if (d != nullptr)
+            (void)hipFree(d);
+    }
+};
+
+int debugNeedsDevice(const char *who)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, OKENV_ERR_NO_DEVICE, std::string(who) + ": no HIP device");
+    return OKENV_OK;
+}
+
+template <int kFn>
+int debugMath(const int32_t device, const float *a, const float *b, float *out0, float *out1, const int32_t n)
+{
+    const size_t count = static_cast<size_t>(n);
+    if (device == OKENV_DEBUG_ON_HOST)
+    {
+        // elements are independent: up to eight host threads share them (ok_sincosf's fmod and the normalisers' loops are slow)
+        const size_t        workers = std::min<size_t>(8, count / 65536 + 1);
+        std::vector<std::thread> pool;
+        for (size_t w = 0; w < workers; ++w)
+            pool.emplace_back([=] {
+                for (size_t i = count * w / workers; i < count * (w + 1) / workers; ++i)
+                    okDebugMathElement<kFn>(a, b, out0, out1, i);
+            });
+        for (std::thread &t : pool)
+            t.join();
+        return OKENV_OK;
+    }
+    if (const int rc = debugNeedsDevice("okenv_debug_math"))
+        return rc;
+    if (n == 0)
+        return OKENV_OK;
+    OK_HIP(nullptr, hipSetDevice(device));
+    // four arrays of n floats: a, b (OKENV_FN_ATAN2 only), out0, out1 (OKENV_FN_SINCOS only)
+    DebugBuffer buf;
+    OK_HIP(nullptr, hipMalloc(reinterpret_cast<void **>(&buf.d), 16U * count));
+    float *da = buf.d, *db = buf.d + count, *d0 = buf.d + 2U * count, *d1 = buf.d + 3U * count;
+    OK_HIP(nullptr, hipMemcpy(da, a, 4U * count, hipMemcpyHostToDevice));
+    if (kFn == OKENV_FN_ATAN2)
+        OK_HIP(nullptr, hipMemcpy(db, b, 4U * count, hipMemcpyHostToDevice));
+    const unsigned un = static_cast<unsigned>(n);
+    hipLaunchKernelGGL(okDebugMathKernel<kFn>, dim3((un + 255U) / 256U), dim3(256), 0, nullptr, da, db, d0, d1, un);
+    OK_HIP(nullptr, hipGetLastError());
+    OK_HIP(nullptr, hipMemcpy(out0, d0, 4U * count, hipMemcpyDeviceToHost));
+    if (kFn == OKENV_FN_SINCOS)
+        OK_HIP(nullptr, hipMemcpy(out1, d1, 4U * count, hipMemcpyDeviceToHost));
+    return OKENV_OK;
 }
 } // namespace
 
@@ -4582,6 +4643,65 @@ extern "C"
         OK_HIP(nullptr, hipMemcpy(s, d + n, 4U * static_cast<size_t>(n), hipMemcpyDeviceToHost));
         OK_HIP(nullptr, hipMemcpy(c, d + 2 * static_cast<size_t>(n), 4U * static_cast<size_t>(n), hipMemcpyDeviceToHost));
         OK_HIP(nullptr, hipFree(d));
+        return OKENV_OK;
+    }
+
+    int okenv_debug_math(int32_t device, int32_t fn, const float *a, const float *b, float *out0, float *out1, int32_t n)
+    {
+        if (fn < 0 || fn >= OKENV_NUM_DEBUG_FNS || !a || !out0 || n < 0 || (fn == OKENV_FN_ATAN2 && !b) || (fn == OKENV_FN_SINCOS && !out1))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_math: bad argument");
+        switch (fn)
+        {
+        case OKENV_FN_SINCOS: return debugMath<OKENV_FN_SINCOS>(device, a, b, out0, out1, n);
+        case OKENV_FN_TANH: return debugMath<OKENV_FN_TANH>(device, a, b, out0, out1, n);
+        case OKENV_FN_EXP: return debugMath<OKENV_FN_EXP>(device, a, b, out0, out1, n);
+        case OKENV_FN_LOG: return debugMath<OKENV_FN_LOG>(device, a, b, out0, out1, n);
+        case OKENV_FN_ATAN2: return debugMath<OKENV_FN_ATAN2>(device, a, b, out0, out1, n);
+        case OKENV_FN_NORMALIZE_ANGLE: return debugMath<OKENV_FN_NORMALIZE_ANGLE>(device, a, b, out0, out1, n);
+        default: return debugMath<OKENV_FN_EXPERT_NORMALIZE_ANGLE>(device, a, b, out0, out1, n);
+        }
+    }
+
+    int okenv_debug_adam_device(int32_t device, const okenv_learner_params *params, int64_t t, float *p, float *m, float *v, const float *g, int32_t n)
+    {
+        // okLearnCheckParams but for eps, which may be 0 here (include/okenv.h)
+        okenv_learner_params checked{};
+        if (params != nullptr)
+        {
+            checked = *params;
+            if (checked.eps == 0.F)
+                checked.eps = 1.F;
+        }
+        if (const char *why = okLearnCheckParams(params != nullptr ? &checked : nullptr))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_debug_adam_device: ") + why);
+        if (t < 1 || !p || !m || !v || !g || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_adam_device: bad argument");
+        const ok_learn_adam_consts c     = okLearnAdamConsts(*params, t);
+        const size_t               count = static_cast<size_t>(n);
+        if (device == OKENV_DEBUG_ON_HOST)
+        {
+            for (size_t i = 0; i < count; ++i)
+                ok_learn_adam(p + i, m + i, v + i, g[i], c);
+            return OKENV_OK;
+        }
+        if (const int rc = debugNeedsDevice("okenv_debug_adam_device"))
+            return rc;
+        if (n == 0)
+            return OKENV_OK;
+        OK_HIP(nullptr, hipSetDevice(device));
+        DebugBuffer buf;
+        OK_HIP(nullptr, hipMalloc(reinterpret_cast<void **>(&buf.d), 16U * count));
+        float *dp = buf.d, *dm = buf.d + count, *dv = buf.d + 2U * count, *dg = buf.d + 3U * count;
+        OK_HIP(nullptr, hipMemcpy(dp, p, 4U * count, hipMemcpyHostToDevice));
+        OK_HIP(nullptr, hipMemcpy(dm, m, 4U * count, hipMemcpyHostToDevice));
+        OK_HIP(nullptr, hipMemcpy(dv, v, 4U * count, hipMemcpyHostToDevice));
+        OK_HIP(nullptr, hipMemcpy(dg, g, 4U * count, hipMemcpyHostToDevice));
+        const unsigned un = static_cast<unsigned>(n);
+        hipLaunchKernelGGL(okDebugAdamKernel, dim3((un + 255U) / 256U), dim3(256), 0, nullptr, dp, dm, dv, dg, c, un);
+        OK_HIP(nullptr, hipGetLastError());
+        OK_HIP(nullptr, hipMemcpy(p, dp, 4U * count, hipMemcpyDeviceToHost));
+        OK_HIP(nullptr, hipMemcpy(m, dm, 4U * count, hipMemcpyDeviceToHost));
+        OK_HIP(nullptr, hipMemcpy(v, dv, 4U * count, hipMemcpyDeviceToHost));
         return OKENV_OK;
     }
 

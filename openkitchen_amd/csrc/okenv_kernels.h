@@ -2930,6 +2930,35 @@ __global__ void okDebugSincosKernel(const float *x, float *s, float *c, int n)
         ok_sincosf(x[i], &s[i], &c[i]);
 }
 
+// Element i of okenv_debug_math: one leaf function of okenv_math.h, chosen at compile time.  The kernel below and the entry's host
+// path both call THIS, so the two differ in nothing but the compiler that translated the header.
+template <int kFn>
+__host__ __device__ inline void okDebugMathElement(const float *a, const float *b, float *out0, float *out1, const size_t i)
+{
+    if (kFn == OKENV_FN_SINCOS)
+        ok_sincosf(a[i], &out0[i], &out1[i]);
+    else if (kFn == OKENV_FN_TANH)
+        out0[i] = ok_tanhf(a[i]);
+    else if (kFn == OKENV_FN_EXP)
+        out0[i] = ok_expf(a[i]);
+    else if (kFn == OKENV_FN_LOG)
+        out0[i] = ok_logf(a[i]);
+    else if (kFn == OKENV_FN_ATAN2)
+        out0[i] = ok_atan2f(a[i], b[i]);
+    else if (kFn == OKENV_FN_NORMALIZE_ANGLE)
+        out0[i] = ok_normalize_angle_deg(a[i]);
+    else
+        out0[i] = ok_expert_normalize_angle_deg(a[i]);
+}
+
+template <int kFn>
+__global__ void __launch_bounds__(256) okDebugMathKernel(const float *a, const float *b, float *out0, float *out1, const unsigned n)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x; // n < 2^31 and the grid is ceil(n / 256) blocks: no wrap
+    if (i < n)
+        okDebugMathElement<kFn>(a, b, out0, out1, i);
+}
+
 template <int kMode>
 __global__ void __launch_bounds__(1024)
 okDebugCastKernel(const OkStepParams p, const float *ox, const float *oy, const float *ang, int n, float *out_t)

@@ -799,6 +799,32 @@ def debug_sincos(x, device=0):
     return s, c
 
 
+def debug_math(fn, a, b=None, device=0):
+    """One leaf function of include/okenv_math.h on a float32 array (okenv_debug_math), on GPU `device` or, with
+    device=capi.DEBUG_ON_HOST, by the library's host compilation of the same header (no GPU needed).  fn: a name of capi.DEBUG_FNS or
+    the integer.  b is the second argument of "atan2" (a = y, b = x).  Returns the result; (sine, cosine) for "sincos"."""
+    k = capi.DEBUG_FNS.index(fn) if isinstance(fn, str) else int(fn)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = None if b is None else np.ascontiguousarray(b, dtype=np.float32)
+    if b is not None and b.shape != a.shape:
+        raise ValueError("debug_math: a and b differ in shape")
+    out0 = np.zeros_like(a)
+    out1 = np.zeros_like(a) if k == capi.DEBUG_FNS.index("sincos") else None
+    capi.check(capi.load().okenv_debug_math(int(device), k, capi.ptr(a), capi.ptr(b), capi.ptr(out0), capi.ptr(out1), a.size))
+    return out0 if out1 is None else (out0, out1)
+
+
+def debug_adam_device(params, t, p, m, v, g, device=0):
+    """debug_adam with ok_learn_adam evaluated per element on GPU `device` (okenv_debug_adam_device), or on the host with
+    device=capi.DEBUG_ON_HOST; params.eps may be 0 here.  Returns the new (p, m, v)."""
+    p, m, v = (np.array(a, dtype=np.float32, copy=True).ravel() for a in (p, m, v))
+    g = np.ascontiguousarray(g, dtype=np.float32).ravel()
+    if not p.size == m.size == v.size == g.size:
+        raise ValueError("debug_adam_device: p, m, v and g differ in size")
+    capi.check(capi.load().okenv_debug_adam_device(int(device), C.byref(params), int(t), capi.ptr(p), capi.ptr(m), capi.ptr(v), capi.ptr(g), p.size))
+    return p, m, v
+
+
 def expert_act_host(params, ray_angles_deg, pos_x, pos_y, rot, dist, centerline=None, goals=None):
     """The experts' rule on host arrays, no GPU needed (okenv_expert_act_host): returns (throttle, steer) for n agents.  params:
     capi.expert_params(...); dist [n, R]; centerline = (x, y) of the track's centre line, or goals = (x, y) per agent."""

@@ -36,6 +36,10 @@ def test_fails_loudly_without_gpu(ok):
     assert e.value.code == -3 and "no CPU fallback" in str(e.value)
     with pytest.raises(ok.capi.OkenvError):
         ok.debug_sincos(np.zeros(4, dtype=np.float32))
+    with pytest.raises(ok.capi.OkenvError):
+        ok.debug_math("tanh", np.zeros(4, dtype=np.float32), device=0)
+    with pytest.raises(ok.capi.OkenvError):
+        ok.debug_adam_device(ok.capi.learner_params(), 1, *(np.zeros(4, dtype=np.float32) for _ in range(4)), device=0)
 
 
 def test_invalid_arguments_are_reported(ok):
