@@ -717,6 +717,103 @@ OKENV_API int okenv_ddpg_update_host(const okenv_ddpg_config *config, int32_t nu
                                      int64_t size, int32_t B, int32_t iterations, int32_t resample, uint32_t draw_base,
                                      const okenv_ddpg_output *out);
 
+/* ---- Continuous REINFORCE: two-hidden-layer Gaussian actor and whole-episode update ---------------------------
+ * RLRacers/ReinforceContinuous (Policy.hpp:17-53, ReinforceAgent.hpp:49-146) for every agent of the handle: a network
+ * R -> H1 -> H2 -> 2 with a free log_std [2], the action tanh(mu + exp(log_std) * eps) * scale + bias with eps a Box-Muller normal, its
+ * log-probability, and updatePolicy on the batch okenv_batch_prepare leaves.  The rule is written out in include/okenv_gauss.h
+ * (ok_gauss_*).  A Gaussian actor, a shared-network actor (okenv_actor_create) and a DDPG object may live on one handle; they share no
+ * buffer.  The parameter vector is [log_std | fc1.weight | fc1.bias | fc2.weight | fc2.bias | mean.weight | mean.bias]: torch's
+ * parameters() order for the reference's module. */
+#define OKENV_GAUSS_GRAD_REFERENCE 0 /* the gradient autograd gives for the reference's graph (pre not detached) */
+#define OKENV_GAUSS_GRAD_SCORE 1     /* the score-function estimator (pre detached)                              */
+
+typedef struct okenv_gauss_config {
+    int32_t  hidden1, hidden2; /* H1, H2: 1 .. 128; the gradient kernel's LDS (okenv_gauss_lds_bytes) must fit 160 KB */
+    float    scale[2];         /* a_k = tanh(pre_k) * scale_k + bias_k  (the reference: 50, 10)                       */
+    float    bias[2];          /*                                       (the reference: 50, 0)                        */
+    int32_t  greedy;           /* 0: sample; 1: tanh(mu), no draw (ReinforceAgent.hpp:137-146)                        */
+    uint32_t seed, agent_base; /* key of the normal draws; global id of the handle's agent 0                          */
+} okenv_gauss_config;
+
+/* Where okenv_gauss_act leaves this step's sample, besides the action fields: device pointers, each may be NULL (skipped). */
+typedef struct okenv_gauss_record {
+    float   *state;  /* [N][R]  x, the network's input (dist / kSensorRange)       */
+    float   *eps;    /* [N][2]  the normal draws (not written when acting greedily) */
+    float   *pre;    /* [N][2]  mu + std * eps (greedy: mu)                        */
+    float   *action; /* [N][2]  (throttle_delta, steering_delta)                   */
+    float   *logp;   /* [N]     the sample's log-probability                       */
+    uint8_t *alive;  /* [N]     !crashed_                                          */
+} okenv_gauss_record;
+
+/* Parameters and Adam state: host or device pointers where a call says so; t: optimiser steps so far. */
+typedef struct okenv_gauss_state {
+    float  *params, *m, *v;
+    int64_t t;
+} okenv_gauss_state;
+
+typedef struct okenv_gauss_update_config {
+    int32_t accumulate; /* okenv_reinforce_config's: != 0 one Adam step per call on the slices' sum; 0 one step per slice */
+    int32_t reduce;     /* OKENV_REINFORCE_SUM | _MEAN                                                               */
+    int32_t grad_mode;  /* OKENV_GAUSS_GRAD_REFERENCE | _SCORE                                                        */
+} okenv_gauss_update_config;
+
+/* The batch: device pointers (host pointers for okenv_gauss_update_host).  eps is required in REFERENCE mode, pre in SCORE mode; the
+ * other may be NULL. */
+typedef struct okenv_gauss_batch {
+    const float *state; /* [M][R] */
+    const float *eps;   /* [M][2] */
+    const float *pre;   /* [M][2] */
+    const float *ret;   /* [M]    */
+} okenv_gauss_batch;
+
+/* Where the update reports: device pointers (host pointers for okenv_gauss_update_host), each may be NULL (skipped). */
+typedef struct okenv_gauss_output {
+    float *loss; /* [steps]  the loss of every optimiser step of the call */
+    float *grad; /* the last step's gradient, in parameter order          */
+} okenv_gauss_output;
+
+/* LDS bytes of the gradient kernel for a network R -> H1 -> H2 -> A with chunks of 32 samples: a pure host function.  A shape is
+ * accepted by okenv_gauss_create (and the host entries) only if this fits 160 KB; the chunk is never shrunk, because it is part of
+ * the summation order.  0 for a width outside the rule's limits. */
+OKENV_API int64_t okenv_gauss_lds_bytes(int32_t num_rays, int32_t hidden1, int32_t hidden2, int32_t num_actions);
+/* Attaches a Gaussian actor to the handle (replaces an earlier one: parameters, moments and t are forgotten).  All device memory of
+ * acting and of the network is allocated here.  OKENV_ERR_INVALID for NULL arguments, a width outside 1 .. 128, a shape whose gradient
+ * kernel does not fit the LDS, greedy other than 0 or 1, a scale or bias that is not finite. */
+OKENV_API int okenv_gauss_create(okenv_t h, const okenv_gauss_config *config);
+OKENV_API int okenv_gauss_num_params(okenv_t h, int32_t *num_params);
+/* New parameters from a host or device pointer; moments and t are left alone.  No synchronisation. */
+OKENV_API int okenv_gauss_set_params(okenv_t h, const float *params);
+/* The parameters to a host or device pointer; synchronises. */
+OKENV_API int okenv_gauss_get_params(okenv_t h, float *params);
+/* Every non-NULL member of `out` is filled from the device (host or device pointers); out->t is set; synchronises.  The moments exist
+ * after okenv_gauss_learner_create (zeros before). */
+OKENV_API int okenv_gauss_get_state(okenv_t h, okenv_gauss_state *out);
+/* A device word added to the draw index of every later okenv_gauss_act (NULL: none): okenv_actor_set_draw_offset's contract. */
+OKENV_API int okenv_gauss_set_draw_offset(okenv_t h, const uint32_t *device_word);
+OKENV_API int okenv_gauss_set_greedy(okenv_t h, int32_t greedy);
+/* The action of every agent, crashed ones included (okenv_ddpg_act's contract): reads OKENV_F_DIST and crashed_, writes
+ * OKENV_F_THROTTLE / OKENV_F_STEER and the record.  One kernel on the handle's stream, no synchronisation, no allocation: capturable
+ * beside okenv_step.  The draw index is okenv_actor_act's.  OKENV_ERR_STATE before the actor has its parameters. */
+OKENV_API int okenv_gauss_act(okenv_t h, const okenv_gauss_record *rec);
+/* The optimiser of the Gaussian actor: Adam's moments zeroed, t = 0.  `clip` is not read.  OKENV_ERR_STATE before the actor has its
+ * parameters. */
+OKENV_API int okenv_gauss_learner_create(okenv_t h, const okenv_learner_params *params);
+/* okenv_reinforce_update's contract for this network: two kernels per slice on the handle's stream, no synchronisation, no allocation
+ * after the first call of a given B; `order` [M] int32 on the device or NULL.  OKENV_ERR_STATE before okenv_gauss_learner_create;
+ * OKENV_ERR_INVALID for NULL arguments, M or B < 1, an unknown reduce or grad_mode, a batch without state, ret or the mode's field. */
+OKENV_API int okenv_gauss_update(okenv_t h, const okenv_gauss_update_config *config, const okenv_gauss_batch *batch, int32_t M, int32_t B,
+                                 const int32_t *order, const okenv_gauss_output *out);
+/* The same rules on host arrays, no GPU needed.  Act: n agents (global ids config->agent_base + i), dist [n][num_rays], crashed [n] or
+ * NULL; outputs, each may be NULL: throttle, steer [n], eps, pre, action [n][2], logp [n], state [n][num_rays], alive [n]. */
+OKENV_API int okenv_gauss_act_host(const okenv_gauss_config *config, const float *params, int32_t num_rays, int32_t n, const float *dist,
+                                   const uint8_t *crashed, uint32_t draw_index, float *throttle, float *steer, float *eps, float *pre, float *action,
+                                   float *logp, float *state, uint8_t *alive);
+/* Network num_rays -> hidden1 -> hidden2 -> num_actions (1 .. 8 here: eps and pre are [M][num_actions]); every member of `state` is
+ * required. */
+OKENV_API int okenv_gauss_update_host(const okenv_learner_params *params, const okenv_gauss_update_config *config, int32_t num_rays, int32_t hidden1,
+                                      int32_t hidden2, int32_t num_actions, okenv_gauss_state *state, const okenv_gauss_batch *batch, int32_t M,
+                                      int32_t B, const int32_t *order, const okenv_gauss_output *out);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.
@@ -1009,6 +1106,11 @@ OKENV_API int okenv_debug_dqn_timing(okenv_t h, double *ms2);
 OKENV_API int okenv_debug_ddpg_timing(okenv_t h, double *ms4);
 /* of the latest okenv_reinforce_update likewise: [0] gradient kernels, [1] join kernels (accumulate and Adam), summed over the slices */
 OKENV_API int okenv_debug_reinforce_timing(okenv_t h, double *ms2);
+/* of the latest okenv_gauss_update likewise: [0] gradient kernels, [1] join kernels */
+OKENV_API int okenv_debug_gauss_timing(okenv_t h, double *ms2);
+/* ok_gauss_normal_pair (include/okenv_gauss.h) on n word pairs (host pointers): out0 = r cos, out1 = r sin; on GPU `device`, or on the
+ * host with device == OKENV_DEBUG_ON_HOST. */
+OKENV_API int okenv_debug_normal(int32_t device, const uint32_t *w0, const uint32_t *w1, float *out0, float *out1, int32_t n);
 /* ok_learn_adam (include/okenv_learn.h) on host arrays: step number t >= 1 of n parameters p with moments m, v and gradients g, all
  * updated in place; host only, no GPU. */
 OKENV_API int okenv_debug_adam(const okenv_learner_params *params, int64_t t, float *p, float *m, float *v, const float *g, int32_t n);

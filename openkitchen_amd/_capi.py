@@ -91,6 +91,9 @@ SYMBOLS = [
     "okenv_actor_set_dropout", "okenv_actor_act_dropout_host", "okenv_reinforce_update", "okenv_reinforce_update_host",
     "okenv_debug_reinforce_timing", "okenv_debug_logf", "okenv_debug_reinforce_mask",
     "okenv_debug_math", "okenv_debug_adam_device",
+    "okenv_gauss_lds_bytes", "okenv_gauss_create", "okenv_gauss_num_params", "okenv_gauss_set_params", "okenv_gauss_get_params",
+    "okenv_gauss_get_state", "okenv_gauss_set_draw_offset", "okenv_gauss_set_greedy", "okenv_gauss_act", "okenv_gauss_learner_create",
+    "okenv_gauss_update", "okenv_gauss_act_host", "okenv_gauss_update_host", "okenv_debug_gauss_timing", "okenv_debug_normal",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -284,6 +287,63 @@ def ddpg_config(hidden, critic_hidden, scale=(50.0, 5.0), bias=(50.0, 0.0), nois
     return OkenvDdpgConfig(int(hidden), int(critic_hidden), (C.c_float * 2)(*map(float, scale)), (C.c_float * 2)(*map(float, bias)),
                            (C.c_float * 2)(*map(float, noise)), int(seed) & 0xFFFFFFFF, int(agent_base) & 0xFFFFFFFF, float(gamma), float(tau),
                            float(lr_actor), float(lr_critic), float(beta1), float(beta2), float(eps), int(sample_seed) & 0xFFFFFFFF)
+
+
+# continuous REINFORCE (include/okenv.h)
+GAUSS_GRAD_REFERENCE, GAUSS_GRAD_SCORE = 0, 1
+GAUSS_GRAD = {"reference": GAUSS_GRAD_REFERENCE, "score": GAUSS_GRAD_SCORE}
+GAUSS_KERNELS = ("grad", "step")
+GAUSS_MAX_HIDDEN = 128
+GAUSS_LDS_BUDGET = 160 * 1024
+
+
+class OkenvGaussConfig(C.Structure):
+    _fields_ = [("hidden1", C.c_int32), ("hidden2", C.c_int32), ("scale", C.c_float * 2), ("bias", C.c_float * 2), ("greedy", C.c_int32),
+                ("seed", C.c_uint32), ("agent_base", C.c_uint32)]
+
+
+class OkenvGaussRecord(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("eps", C.c_void_p), ("pre", C.c_void_p), ("action", C.c_void_p), ("logp", C.c_void_p),
+                ("alive", C.c_void_p)]
+
+
+class OkenvGaussState(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("t", C.c_int64)]
+
+
+class OkenvGaussUpdateConfig(C.Structure):
+    _fields_ = [("accumulate", C.c_int32), ("reduce", C.c_int32), ("grad_mode", C.c_int32)]
+
+
+class OkenvGaussBatch(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("eps", C.c_void_p), ("pre", C.c_void_p), ("ret", C.c_void_p)]
+
+
+class OkenvGaussOutput(C.Structure):
+    _fields_ = [("loss", C.c_void_p), ("grad", C.c_void_p)]
+
+
+def gauss_config(hidden1=128, hidden2=128, scale=(50.0, 10.0), bias=(50.0, 0.0), greedy=False, seed=0, agent_base=0):
+    """okenv_gauss_config with the reference's widths and action ranges as defaults (Policy.hpp:17-24, ReinforceAgent.hpp:85-88)."""
+    return OkenvGaussConfig(int(hidden1), int(hidden2), (C.c_float * 2)(*map(float, scale)), (C.c_float * 2)(*map(float, bias)),
+                            int(greedy), int(seed) & 0xFFFFFFFF, int(agent_base) & 0xFFFFFFFF)
+
+
+def gauss_update_config(accumulate=True, reduce="sum", grad="reference"):
+    """okenv_gauss_update_config with the reference's choices as defaults; reduce: "sum" / "mean", grad: "reference" / "score", or
+    the integers."""
+    return OkenvGaussUpdateConfig(1 if accumulate else 0, REINFORCE_REDUCE[reduce] if isinstance(reduce, str) else int(reduce),
+                                  GAUSS_GRAD[grad] if isinstance(grad, str) else int(grad))
+
+
+def gauss_num_params(R, H1, H2, A=2):
+    """Floats of the parameter vector [log_std | fc1.weight | fc1.bias | fc2.weight | fc2.bias | mean.weight | mean.bias]."""
+    return A + H1 * R + H1 + H2 * H1 + H2 + A * H2 + A
+
+
+def gauss_lds_bytes(R, H1, H2, A=2):
+    """okenv_gauss_lds_bytes: the gradient kernel's LDS for the shape, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_gauss_lds_bytes(int(R), int(H1), int(H2), int(A)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -534,6 +594,23 @@ def load(build_if_missing=True):
     L.okenv_debug_reinforce_timing.argtypes = [vp, vp]
     L.okenv_debug_logf.argtypes = [vp, vp, i32]
     L.okenv_debug_reinforce_mask.argtypes = [f32, u32, u32, u32, i32, vp]
+    L.okenv_gauss_lds_bytes.argtypes = [i32, i32, i32, i32]
+    L.okenv_gauss_lds_bytes.restype = C.c_int64
+    L.okenv_gauss_create.argtypes = [vp, C.POINTER(OkenvGaussConfig)]
+    L.okenv_gauss_num_params.argtypes = [vp, C.POINTER(i32)]
+    L.okenv_gauss_set_params.argtypes = [vp, vp]
+    L.okenv_gauss_get_params.argtypes = [vp, vp]
+    L.okenv_gauss_get_state.argtypes = [vp, C.POINTER(OkenvGaussState)]
+    L.okenv_gauss_set_draw_offset.argtypes = [vp, vp]
+    L.okenv_gauss_set_greedy.argtypes = [vp, i32]
+    L.okenv_gauss_act.argtypes = [vp, C.POINTER(OkenvGaussRecord)]
+    L.okenv_gauss_learner_create.argtypes = [vp, C.POINTER(OkenvLearnerParams)]
+    L.okenv_gauss_update.argtypes = [vp, C.POINTER(OkenvGaussUpdateConfig), C.POINTER(OkenvGaussBatch), i32, i32, vp, C.POINTER(OkenvGaussOutput)]
+    L.okenv_gauss_act_host.argtypes = [C.POINTER(OkenvGaussConfig), vp, i32, i32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.okenv_gauss_update_host.argtypes = [C.POINTER(OkenvLearnerParams), C.POINTER(OkenvGaussUpdateConfig), i32, i32, i32, i32,
+                                          C.POINTER(OkenvGaussState), C.POINTER(OkenvGaussBatch), i32, i32, vp, C.POINTER(OkenvGaussOutput)]
+    L.okenv_debug_gauss_timing.argtypes = [vp, vp]
+    L.okenv_debug_normal.argtypes = [i32, vp, vp, vp, vp, i32]
     _lib = L
     return L
 

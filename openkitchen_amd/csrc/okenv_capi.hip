@@ -29,6 +29,7 @@
 #include "ok_dqn.h"
 #include "ok_ddpg.h"
 #include "ok_reinforce.h"
+#include "ok_gauss.h"
 #include "ok_expert.h"
 
 namespace
@@ -543,6 +544,19 @@ struct okenv
     uint8_t                *d_reinforce_part{nullptr};
     size_t                  reinforce_part_bytes{0};
     OkEventLog              reinforce_log;
+    // Continuous REINFORCE (okenv_gauss_create, okenv_gauss_learner_create): the parameter vector and Adam's two moments
+    // [params | m | v], each gauss_cap floats, the update's scratch [chunk partials | accumulator] (grown, never shrunk) and timing
+    // events.  Nothing here is shared with the actor, the learner or the DDPG object above.
+    bool                    gauss_ok{false}, gauss_set{false}, gauss_learner_ok{false};
+    okenv_gauss_config      gauss{};
+    okenv_learner_params    gauss_learner{};
+    size_t                  gauss_cap{0};
+    float                  *d_gauss{nullptr};
+    int64_t                 gauss_t{0};
+    const uint32_t         *gauss_draw_offset{nullptr};
+    uint8_t                *d_gauss_part{nullptr};
+    size_t                  gauss_part_bytes{0};
+    OkEventLog              gauss_log;
 };
 
 struct okenv_track
@@ -1704,7 +1718,7 @@ extern "C"
             (void)hipEventDestroy(e.start);
             (void)hipEventDestroy(e.stop);
         }
-        for (OkEventLog *log : {&h->batch_log, &h->learn_log, &h->dqn_log, &h->ddpg_log, &h->reinforce_log})
+        for (OkEventLog *log : {&h->batch_log, &h->learn_log, &h->dqn_log, &h->ddpg_log, &h->reinforce_log, &h->gauss_log})
             for (hipEvent_t e : log->events)
                 (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
@@ -3357,6 +3371,315 @@ extern "C"
         const okenv_replay_ring empty{};
         okDqnUpdateHost(*params, *config, num_rays, hidden, num_actions, *state, target, ring != nullptr ? *ring : empty, static_cast<uint32_t>(size), B,
                         iterations, resample != 0, draw_base, out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    // ---- Continuous REINFORCE: two-hidden-layer Gaussian actor and whole-episode update (ok_gauss.h) ---------------------------
+
+    int64_t okenv_gauss_lds_bytes(int32_t num_rays, int32_t hidden1, int32_t hidden2, int32_t num_actions)
+    {
+        return static_cast<int64_t>(okGaussLdsBytes(num_rays, hidden1, hidden2, num_actions));
+    }
+
+    int okenv_gauss_create(okenv_t h, const okenv_gauss_config *config)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_create: NULL handle");
+        if (const char *why = okGaussCheckConfig(config, h->shape.R))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_gauss_create: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        // room for the widest network, so that a later create with other widths allocates nothing
+        h->gauss_cap = (static_cast<size_t>(ok_gauss_num_params(OK_ACTOR_MAX_RAYS, OK_GAUSS_MAX_HIDDEN, OK_GAUSS_MAX_HIDDEN, 2)) + 3U) & ~static_cast<size_t>(3U);
+        if (const int rc = devEnsure(h, &h->d_gauss, 3U * h->gauss_cap))
+            return rc;
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okGaussActKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okGaussGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipMemsetAsync(h->d_gauss, 0, 3U * h->gauss_cap * sizeof(float), h->stream));
+        h->gauss            = *config;
+        h->gauss_t          = 0;
+        h->gauss_set        = false;
+        h->gauss_learner_ok = false;
+        h->gauss_ok         = true;
+        return OKENV_OK;
+    }
+
+    int okenv_gauss_num_params(okenv_t h, int32_t *num_params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->gauss_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gauss_num_params: call okenv_gauss_create first");
+        if (num_params)
+            *num_params = ok_gauss_num_params(h->shape.R, h->gauss.hidden1, h->gauss.hidden2, 2);
+        return OKENV_OK;
+    }
+
+    int okenv_gauss_set_params(okenv_t h, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->gauss_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gauss_set_params: call okenv_gauss_create first");
+        if (!params)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_set_params: NULL argument");
+        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = copyAny(h, h->d_gauss, params, sizeof(float) * static_cast<size_t>(ok_gauss_num_params(h->shape.R, h->gauss.hidden1, h->gauss.hidden2, 2))))
+            return rc;
+        h->gauss_set = true;
+        return OKENV_OK;
+    }
+
+    int okenv_gauss_get_state(okenv_t h, okenv_gauss_state *out)
+    {
+        OK_QUIESCE(h);
+        if (!h || !out)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_get_state: NULL argument");
+        if (!h->gauss_ok || !h->gauss_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_gauss_get_state: the actor needs its parameters first (okenv_gauss_create, okenv_gauss_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t bytes  = sizeof(float) * static_cast<size_t>(ok_gauss_num_params(h->shape.R, h->gauss.hidden1, h->gauss.hidden2, 2));
+        float *const dst[3] = {out->params, out->m, out->v};
+        for (size_t k = 0; k < 3U; ++k)
+            if (dst[k] != nullptr)
+                if (const int rc = copyAny(h, dst[k], h->d_gauss + k * h->gauss_cap, bytes))
+                    return rc;
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        out->t = h->gauss_t;
+        return OKENV_OK;
+    }
+
+    int okenv_gauss_get_params(okenv_t h, float *params)
+    {
+        OK_QUIESCE(h);
+        if (!params)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_get_params: NULL argument");
+        okenv_gauss_state st{params, nullptr, nullptr, 0};
+        return okenv_gauss_get_state(h, &st);
+    }
+
+    int okenv_gauss_set_draw_offset(okenv_t h, const uint32_t *device_word)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->gauss_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gauss_set_draw_offset: call okenv_gauss_create first");
+        h->gauss_draw_offset = device_word;
+        return OKENV_OK;
+    }
+
+    int okenv_gauss_set_greedy(okenv_t h, int32_t greedy)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->gauss_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gauss_set_greedy: call okenv_gauss_create first");
+        if (greedy != 0 && greedy != 1)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_set_greedy: greedy must be 0 or 1");
+        h->gauss.greedy = greedy;
+        return OKENV_OK;
+    }
+
+    int okenv_gauss_act(okenv_t h, const okenv_gauss_record *rec)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_act: NULL handle");
+        if (!h->gauss_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gauss_act: call okenv_gauss_create first");
+        if (!h->gauss_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_gauss_act: call okenv_gauss_set_params first (the actor needs its parameters)");
+        dropEpisode(h);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkGaussActParams p{};
+        p.st          = h->st;
+        p.N           = h->shape.N;
+        p.R           = h->shape.R;
+        p.H1          = h->gauss.hidden1;
+        p.H2          = h->gauss.hidden2;
+        p.params      = h->d_gauss;
+        p.step_word   = (h->reset_flags & kAutoResetOn) != 0U ? h->d_step_count : nullptr; // (the step kernels advance it only then)
+        p.host_steps  = h->step_count;
+        p.draw_offset = h->gauss_draw_offset;
+        for (int k = 0; k < 2; ++k)
+        {
+            p.scale[k] = h->gauss.scale[k];
+            p.bias[k]  = h->gauss.bias[k];
+        }
+        p.greedy     = h->gauss.greedy;
+        p.seed       = h->gauss.seed;
+        p.agent_base = h->gauss.agent_base;
+        if (rec != nullptr)
+            p.rec = *rec;
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
+        hipLaunchKernelGGL(okGaussActKernel, dim3(blocks), dim3(kActorThreads), okGaussActLdsBytes(p.R, p.H1, p.H2), h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_gauss_learner_create(okenv_t h, const okenv_learner_params *params)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_learner_create: NULL handle");
+        if (const char *why = okLearnCheckParams(params))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_gauss_learner_create: ") + why);
+        if (!h->gauss_ok || !h->gauss_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_gauss_learner_create: needs a Gaussian actor with its parameters (okenv_gauss_create, okenv_gauss_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        OK_HIP(h, hipMemsetAsync(h->d_gauss + h->gauss_cap, 0, 2U * h->gauss_cap * sizeof(float), h->stream));
+        h->gauss_learner    = *params;
+        h->gauss_t          = 0;
+        h->gauss_learner_ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_gauss_update(okenv_t h, const okenv_gauss_update_config *config, const okenv_gauss_batch *batch, int32_t M, int32_t B, const int32_t *order,
+                           const okenv_gauss_output *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_update: NULL handle");
+        if (!h->gauss_ok || !h->gauss_learner_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gauss_update: call okenv_gauss_learner_create first");
+        if (const char *why = okGaussCheckCall(config, batch, M, B))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_gauss_update: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkGaussParams p{};
+        p.R      = h->shape.R;
+        p.H1     = h->gauss.hidden1;
+        p.H2     = h->gauss.hidden2;
+        p.A      = 2;
+        p.M      = M;
+        p.P      = ok_gauss_num_params(p.R, p.H1, p.H2, p.A);
+        p.cols   = p.P + 1;
+        p.in     = *batch;
+        p.mode   = config->grad_mode;
+        p.order  = order;
+        p.params = h->d_gauss;
+        // the join kernels are section 19's, on this parameter vector
+        OkReinforceParams s{};
+        s.Pp     = p.P;
+        s.cols   = p.cols;
+        s.policy = h->d_gauss;
+        s.pol_m  = h->d_gauss + h->gauss_cap;
+        s.pol_v  = h->d_gauss + 2U * h->gauss_cap;
+        s.reduce = config->reduce;
+        const okenv_gauss_output none{};
+        const okenv_gauss_output &o = out != nullptr ? *out : none;
+        s.grad_policy = o.grad;
+        // the scratch: [chunk partials | accumulator], each piece 256-aligned
+        const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
+        const size_t c_max = (static_cast<size_t>(std::min(B, M)) + OK_LEARN_CHUNK - 1U) / OK_LEARN_CHUNK;
+        const size_t parts = up(sizeof(float) * c_max * static_cast<size_t>(p.cols)), acc_bytes = sizeof(float) * static_cast<size_t>(p.cols);
+        if (const int rc = growScratch(h, &h->d_gauss_part, &h->gauss_part_bytes, parts + up(acc_bytes)))
+            return rc;
+        p.part = s.part = reinterpret_cast<float *>(h->d_gauss_part);
+        const bool accumulate = config->accumulate != 0;
+        if (accumulate)
+        {
+            s.acc = reinterpret_cast<float *>(h->d_gauss_part + parts);
+            OK_HIP(h, hipMemsetAsync(s.acc, 0, acc_bytes, h->stream));
+        }
+        const int slices = okLearnMinibatches(M, B);
+        if (const int rc = eventsBegin(h, h->gauss_log, 2U * static_cast<size_t>(slices)))
+            return rc;
+        const size_t   lds       = okGaussLdsBytes(p.R, p.H1, p.H2, p.A);
+        const unsigned step_grid = static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols);
+        int            slot      = 0;
+        for (int k = 0; k < slices; ++k)
+        {
+            p.base = static_cast<long>(k) * B;
+            p.Bk   = static_cast<int>(std::min<long>(B, M - p.base));
+            s.C    = (p.Bk + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+            hipLaunchKernelGGL(okGaussGradKernel, dim3(static_cast<unsigned>(s.C)), dim3(kLearnThreads), lds, h->stream, p);
+            OK_HIP(h, hipGetLastError());
+            if (const int rc = eventsMark(h, h->gauss_log))
+                return rc;
+            if (accumulate && k + 1 < slices)
+            {
+                hipLaunchKernelGGL(okReinforceStepKernel<false>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, s);
+                OK_HIP(h, hipGetLastError());
+            }
+            else
+            {
+                s.count = static_cast<float>(accumulate ? M : p.Bk);
+                s.adam  = okLearnAdamConsts(h->gauss_learner, h->gauss_t + 1);
+                s.loss  = o.loss != nullptr ? o.loss + slot : nullptr;
+                hipLaunchKernelGGL(okReinforceStepKernel<true>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, s);
+                OK_HIP(h, hipGetLastError());
+                h->gauss_t += 1;
+                ++slot;
+            }
+            if (const int rc = eventsMark(h, h->gauss_log))
+                return rc;
+        }
+        return OKENV_OK;
+    }
+
+    int okenv_debug_gauss_timing(okenv_t h, double *ms2)
+    {
+        OK_QUIESCE(h);
+        if (!h || !ms2)
+            return fail(h, OKENV_ERR_INVALID, "okenv_debug_gauss_timing: NULL argument");
+        if (h->gauss_log.timed < 3U)
+            return fail(h, OKENV_ERR_STATE, "okenv_debug_gauss_timing: no okenv_gauss_update has run with okenv_set_timing on");
+        return eventsSums(h, h->gauss_log, ms2, 2);
+    }
+
+    int okenv_gauss_act_host(const okenv_gauss_config *config, const float *params, int32_t num_rays, int32_t n, const float *dist, const uint8_t *crashed,
+                             uint32_t draw_index, float *throttle, float *steer, float *eps, float *pre, float *action, float *logp, float *state,
+                             uint8_t *alive)
+    {
+        if (const char *why = okGaussCheckConfig(config, num_rays))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gauss_act_host: ") + why);
+        if (!params || n < 0 || !dist)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_gauss_act_host: bad argument");
+        okGaussActHost(*config, params, num_rays, n, dist, crashed, draw_index, throttle, steer, eps, pre, action, logp, state, alive);
+        return OKENV_OK;
+    }
+
+    int okenv_gauss_update_host(const okenv_learner_params *params, const okenv_gauss_update_config *config, int32_t num_rays, int32_t hidden1,
+                                int32_t hidden2, int32_t num_actions, okenv_gauss_state *state, const okenv_gauss_batch *batch, int32_t M, int32_t B,
+                                const int32_t *order, const okenv_gauss_output *out)
+    {
+        if (const char *why = okLearnCheckParams(params))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gauss_update_host: ") + why);
+        if (const char *why = okGaussCheckShape(num_rays, hidden1, hidden2, num_actions))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gauss_update_host: ") + why);
+        if (const char *why = okGaussCheckCall(config, batch, M, B))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gauss_update_host: ") + why);
+        if (state == nullptr || state->params == nullptr || state->m == nullptr || state->v == nullptr || state->t < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_gauss_update_host: state lacks a parameter or moment vector, or t < 0");
+        const okenv_gauss_output none{};
+        okGaussUpdateHost(*params, *config, num_rays, hidden1, hidden2, num_actions, *state, *batch, M, B, order, out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_normal(int32_t device, const uint32_t *w0, const uint32_t *w1, float *out0, float *out1, int32_t n)
+    {
+        if (!w0 || !w1 || !out0 || !out1 || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_normal: bad argument");
+        const size_t count = static_cast<size_t>(n);
+        if (device == OKENV_DEBUG_ON_HOST)
+        {
+            for (size_t i = 0; i < count; ++i)
+                ok_gauss_normal_pair(w0[i], w1[i], out0 + i, out1 + i);
+            return OKENV_OK;
+        }
+        if (const int rc = debugNeedsDevice("okenv_debug_normal"))
+            return rc;
+        if (n == 0)
+            return OKENV_OK;
+        OK_HIP(nullptr, hipSetDevice(device));
+        // four arrays of n words: w0, w1, out0, out1
+        DebugBuffer buf;
+        OK_HIP(nullptr, hipMalloc(reinterpret_cast<void **>(&buf.d), 16U * count));
+        uint32_t *d0 = reinterpret_cast<uint32_t *>(buf.d), *d1 = d0 + count;
+        float    *o0 = buf.d + 2U * count, *o1 = buf.d + 3U * count;
+        OK_HIP(nullptr, hipMemcpy(d0, w0, 4U * count, hipMemcpyHostToDevice));
+        OK_HIP(nullptr, hipMemcpy(d1, w1, 4U * count, hipMemcpyHostToDevice));
+        const unsigned un = static_cast<unsigned>(n);
+        hipLaunchKernelGGL(okDebugNormalKernel, dim3((un + 255U) / 256U), dim3(256), 0, nullptr, d0, d1, o0, o1, un);
+        OK_HIP(nullptr, hipGetLastError());
+        OK_HIP(nullptr, hipMemcpy(out0, o0, 4U * count, hipMemcpyDeviceToHost));
+        OK_HIP(nullptr, hipMemcpy(out1, o1, 4U * count, hipMemcpyDeviceToHost));
         return OKENV_OK;
     }
 

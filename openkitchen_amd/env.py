@@ -748,6 +748,74 @@ class BatchedEnvironment:
         capi.DDPG_KERNELS."""
         return self._timing("okenv_debug_ddpg_timing", capi.DDPG_KERNELS)
 
+    # ---- continuous REINFORCE (include/okenv.h, DESIGN.md section 20) -------------------------------------------------------
+    def gauss_create(self, hidden1=128, hidden2=128, **config):
+        """Attaches a Gaussian actor (R -> hidden1 -> hidden2 -> 2 with a free log_std [2]) to the handle; config: the members of
+        okenv_gauss_config (capi.gauss_config lists them with the reference's defaults).  Returns the floats of its parameter vector."""
+        cfg = capi.gauss_config(hidden1, hidden2, **config)
+        capi.check(self._L.okenv_gauss_create(self._h, C.byref(cfg)), self._h)
+        self.gauss_config = cfg
+        return self.gauss_num_params()
+
+    def gauss_num_params(self):
+        n = C.c_int32()
+        capi.check(self._L.okenv_gauss_num_params(self._h, C.byref(n)), self._h)
+        return n.value
+
+    def gauss_set_params(self, params):
+        """New parameters [log_std | fc1 | fc2 | mean] (torch's parameters() order, flattened) from a float32 numpy array or a device
+        tensor.  No synchronisation."""
+        if hasattr(params, "data_ptr"):
+            assert params.is_contiguous() and params.numel() == self.gauss_num_params()
+        else:
+            params = _flat_params(params, self.gauss_num_params())
+        capi.check(self._L.okenv_gauss_set_params(self._h, capi.ptr(params)), self._h)
+
+    def gauss_state(self, out=None):
+        """The parameter vector, Adam's two moments ("params", "m", "v") and the int t: float32 numpy arrays, or copied into the
+        device tensors of the dict `out` (any subset).  Synchronises."""
+        if out is None:
+            out = {k: np.empty(self.gauss_num_params(), dtype=np.float32) for k in ("params", "m", "v")}
+        st = capi.fill_pointers(capi.OkenvGaussState(), out, "gauss state")
+        capi.check(self._L.okenv_gauss_get_state(self._h, C.byref(st)), self._h)
+        return dict(out, t=int(st.t))
+
+    def gauss_set_draw_offset(self, word=None):
+        """A device uint32 word (tensor or address) added to the draw index of every later gauss_act; None removes it."""
+        capi.check(self._L.okenv_gauss_set_draw_offset(self._h, capi.ptr(word)), self._h)
+
+    def gauss_set_greedy(self, greedy):
+        capi.check(self._L.okenv_gauss_set_greedy(self._h, 1 if greedy else 0), self._h)
+
+    def gauss_act(self, record=None):
+        """The sampled (or greedy) action of every agent, enqueued on the handle's stream without a synchronisation.  record: None,
+        or a dict of device tensors / addresses under "state" [N,R], "eps", "pre", "action" [N,2], "logp" [N] float32 and "alive" [N]
+        uint8, each optional."""
+        if record is None:
+            capi.check(self._L.okenv_gauss_act(self._h, None), self._h)
+            return
+        sizes = {"state": self.N * self.R * 4, "eps": self.N * 8, "pre": self.N * 8, "action": self.N * 8, "logp": self.N * 4, "alive": self.N}
+        rec = capi.fill_pointers(capi.OkenvGaussRecord(), record, "record", sizes)
+        capi.check(self._L.okenv_gauss_act(self._h, C.byref(rec)), self._h)
+
+    def gauss_learner_create(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
+        """Adam for the Gaussian actor (the reference's learning rate, ReinforceAgent.hpp:52): moments zeroed, t = 0."""
+        lp = capi.learner_params(lr, 0.0, beta1, beta2, eps)
+        capi.check(self._L.okenv_gauss_learner_create(self._h, C.byref(lp)), self._h)
+
+    def gauss_update(self, batch, M, B, accumulate=True, reduce="sum", grad="reference", order=None, out=None):
+        """okenv_gauss_update: enqueues every slice on the handle's stream (two kernels each), no synchronisation.  batch: dict of device
+        tensors / addresses under "state" [M,R], "eps" [M,2] (grad="reference"), "pre" [M,2] (grad="score") and "ret" [M], float32;
+        order: None or a device int32 tensor [M]; out: None or a dict under "loss" (float32, one per optimiser step) and "grad"."""
+        cfg = capi.gauss_update_config(accumulate, reduce, grad)
+        gb = capi.fill_pointers(capi.OkenvGaussBatch(), batch, "gauss batch")
+        go = capi.fill_pointers(capi.OkenvGaussOutput(), out or {}, "gauss output")
+        capi.check(self._L.okenv_gauss_update(self._h, C.byref(cfg), C.byref(gb), int(M), int(B), capi.ptr(order), C.byref(go)), self._h)
+
+    def gauss_timing(self):
+        """Device microseconds of the latest gauss_update that ran with set_timing(True), summed over its slices, by capi.GAUSS_KERNELS."""
+        return self._timing("okenv_debug_gauss_timing", capi.GAUSS_KERNELS)
+
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):
         """{rays, tests, cells, points} the broad phase leaves for the current poses (okenv_work_stats)."""
@@ -1165,3 +1233,59 @@ def debug_expert_normalize_angle(angle_deg):
     out = np.zeros_like(a)
     capi.check(capi.load().okenv_debug_expert_normalize_angle(capi.ptr(a), capi.ptr(out), a.size))
     return out
+
+
+def debug_normal(w0, w1, device=0):
+    """ok_gauss_normal_pair of include/okenv_gauss.h on uint32 word pairs (okenv_debug_normal), on GPU `device` or, with
+    device=capi.DEBUG_ON_HOST, on the host (no GPU needed).  Returns (r cos, r sin): the even and the odd component of a block."""
+    w0, w1 = np.ascontiguousarray(w0, dtype=np.uint32), np.ascontiguousarray(w1, dtype=np.uint32)
+    if w0.shape != w1.shape:
+        raise ValueError("debug_normal: w0 and w1 differ in shape")
+    out0, out1 = np.zeros(w0.shape, np.float32), np.zeros(w0.shape, np.float32)
+    capi.check(capi.load().okenv_debug_normal(int(device), capi.ptr(w0), capi.ptr(w1), capi.ptr(out0), capi.ptr(out1), w0.size))
+    return out0, out1
+
+
+def gauss_act_host(config, params, dist, crashed=None, draw_index=0):
+    """The Gaussian actor's action on host arrays, no GPU needed (okenv_gauss_act_host).  config: capi.gauss_config(...); params: the
+    flattened float32 parameter vector; dist [n, R].  Returns a dict: throttle, steer [n], eps, pre, action [n, 2], logp [n], state
+    [n, R] float32 and alive [n] uint8 (eps stays NaN when acting greedily: nothing is drawn)."""
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    n, R = dist.shape
+    params = None if params is None else np.ascontiguousarray(params, dtype=np.float32).ravel()
+    if config is not None and params is not None:
+        assert params.size == capi.gauss_num_params(R, config.hidden1, config.hidden2)
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, dtype=np.uint8)
+    out = {"throttle": np.zeros(n, np.float32), "steer": np.zeros(n, np.float32), "eps": np.full((n, 2), np.nan, np.float32),
+           "pre": np.zeros((n, 2), np.float32), "action": np.zeros((n, 2), np.float32), "logp": np.zeros(n, np.float32),
+           "state": np.zeros((n, R), np.float32), "alive": np.zeros(n, np.uint8)}
+    capi.check(capi.load().okenv_gauss_act_host(C.byref(config) if config is not None else None, capi.ptr(params), R, n, capi.ptr(dist),
+                                                capi.ptr(crashed), int(draw_index) & 0xFFFFFFFF, capi.ptr(out["throttle"]), capi.ptr(out["steer"]),
+                                                capi.ptr(out["eps"]), capi.ptr(out["pre"]), capi.ptr(out["action"]), capi.ptr(out["logp"]),
+                                                capi.ptr(out["state"]), capi.ptr(out["alive"])))
+    return out
+
+
+def gauss_update_host(params, shape, state, batch, B, accumulate=True, reduce="sum", grad="reference", order=None, want=("loss", "grad")):
+    """The continuous REINFORCE update on host arrays, no GPU needed (okenv_gauss_update_host).  params: capi.learner_params(...); shape:
+    (R, H1, H2) or (R, H1, H2, A); state: dict of float32 numpy arrays "params", "m", "v" and the int "t" -- copied, the new state is
+    returned; batch: dict of numpy arrays "state" [M,R], "ret" [M] and "eps" / "pre" [M,A]; order: None or int32 [M].  Returns
+    (new state, outputs): outputs holds the arrays named in `want` ("loss": one value per optimiser step)."""
+    R, H1, H2, A = (tuple(int(v) for v in shape) + (2,))[:4]
+    M = int(np.asarray(batch["ret"]).shape[0])
+    b = {k: np.ascontiguousarray(batch[k], dtype=np.float32) for k in ("state", "eps", "pre", "ret") if batch.get(k) is not None}
+    new = {k: np.array(v, dtype=np.float32, copy=True).ravel() for k, v in state.items() if k != "t" and v is not None}
+    st = capi.fill_pointers(capi.OkenvGaussState(), new, "gauss state")
+    st.t = int(state.get("t", 0))
+    steps = (1 if accumulate else (M + int(B) - 1) // int(B)) if M > 0 and B > 0 else 0
+    sizes = {"loss": steps, "grad": capi.gauss_num_params(R, H1, H2, A)}
+    outs = {k: np.zeros(sizes[k], dtype=np.float32) for k in want}
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.int32)
+    cfg = capi.gauss_update_config(accumulate, reduce, grad) if reduce is not None else None
+    capi.check(capi.load().okenv_gauss_update_host(
+        C.byref(params) if params is not None else None, C.byref(cfg) if cfg is not None else None, R, H1, H2, A, C.byref(st),
+        C.byref(capi.fill_pointers(capi.OkenvGaussBatch(), b, "gauss batch")), M, int(B), capi.ptr(order),
+        C.byref(capi.fill_pointers(capi.OkenvGaussOutput(), {k: v for k, v in outs.items() if v.size}, "gauss output"))))
+    new["t"] = int(st.t)
+    return new, outs

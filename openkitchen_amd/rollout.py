@@ -117,10 +117,10 @@ def collect_episode(venv, policy, max_steps=None, check_every=8, actions=PPO_ACT
 class _EpisodeBuffers:
     """[T, N, ...] tensors of an episode, preallocated in blocks of `block` steps; slot(t) gives step t's record pointers."""
 
-    def __init__(self, venv, block, with_value):
+    def __init__(self, venv, block, with_value, fields=None):
         self.venv, self.block, self.blocks = venv, block, []
         self.fields = {"state": ((venv.num_rays,), torch.float32), "action": ((), torch.int64), "prob": ((), torch.float32),
-                       "alive": ((), torch.bool), "reward": ((), torch.float32)}
+                       "alive": ((), torch.bool), "reward": ((), torch.float32)} if fields is None else dict(fields)
         if with_value:
             self.fields["value"] = ((), torch.float32)
 
@@ -479,6 +479,123 @@ def ddpg_update(venv, batch=250, iterations=50, resample=True, draw=None, grads=
     venv.env.ddpg_update(batch, iterations, resample, draw, out)
     venv._update_inputs = out  # alive until the next update: the kernels are only enqueued
     return out if grads else (out["critic_loss"], out["actor_loss"])
+
+
+# ---- continuous REINFORCE --------------------------------------------------------------------------------
+
+def _gauss_fields(venv):
+    return {"state": ((venv.num_rays,), torch.float32), "eps": ((2,), torch.float32), "pre": ((2,), torch.float32), "action": ((2,), torch.float32),
+            "logp": ((), torch.float32), "alive": ((), torch.bool), "reward": ((), torch.float32)}
+
+
+def _gauss_act_step_record(venv, slot, prev, crash_reward):
+    """One iteration of collect_episode_gauss into the row `slot`: gauss_act -> step -> reward.  The reward is the distance moved in
+    the step, |pos - prev_pos| with prev_pos refreshed every step, and `crash_reward` on the crashing step (reinforce_sim.cpp:67-73)."""
+    venv.gauss_act({k: v for k, v in slot.items() if k != "reward"})
+    prev[0].copy_(venv.pos_x)
+    prev[1].copy_(venv.pos_y)
+    venv.step()
+    dx, dy = venv.pos_x - prev[0], venv.pos_y - prev[1]
+    moved = torch.sqrt(dx * dx + dy * dy)
+    slot["reward"].copy_(moved.masked_fill_(venv.done, crash_reward))
+
+
+def collect_episode_gauss(venv, max_steps=None, check_every=8, graph_chunk=0, crash_reward=-5.0):
+    """The episode loop of RLRacers/ReinforceContinuous (reinforce_sim.cpp:46-108) with the acting on the device: `gauss_act -> step
+    -> reward` for the actor given to venv.enable_gauss_actor, eagerly or, with graph_chunk = K > 0, as a replayed HIP graph of K
+    iterations (collect_episode_device's contract: rows past the step in which the last agent crashed are trimmed).  The reward comes
+    from torch elementwise operations on the position fields.  Returns a dict of device tensors: states [T, N, R], eps, pre, actions
+    [T, N, 2], log_probs, rewards [T, N], alive [T, N] bool.  (While acting greedily nothing is drawn and eps is left as allocated.)"""
+    assert not venv.auto_reset or max_steps is not None, "with auto-reset on the episode never ends: pass max_steps"
+    assert getattr(venv, "_gauss_nets", None) is not None, "call venv.enable_gauss_actor(policy) first"
+    K = int(graph_chunk)
+    block = 256 if K <= 0 else K * max(1, 256 // K)
+    if max_steps is not None:
+        block = max_steps if K <= 0 else K * ((max_steps + K - 1) // K)
+    buf = _EpisodeBuffers(venv, block, False, _gauss_fields(venv))
+    crash_reward = float(crash_reward)
+
+    def scratch():
+        prev = torch.empty((2, venv.num_envs), dtype=torch.float32, device=venv.device)
+        prev[0].copy_(venv.pos_x)
+        dx = venv.pos_x - prev[0]
+        torch.sqrt(dx * dx + dx).masked_fill_(venv.done, crash_reward)  # torch's own kernels are loaded before a capture
+        return prev
+
+    def build():
+        chunk = _EpisodeBuffers(venv, K, False, _gauss_fields(venv)).rows(0, K)
+        prev = scratch()
+        chunk["reward"][0].copy_(prev[0])
+        return (lambda k: _gauss_act_step_record(venv, {name: t[k] for name, t in chunk.items()}, prev, crash_reward)), chunk
+
+    def copy_rows(steps, chunk):
+        for name, dst in buf.rows(steps, K).items():
+            dst.copy_(chunk[name])
+
+    eager_prev = scratch() if K <= 0 else None
+    captured = _Chunk(K=K, graphs=venv._gauss_graphs, key=(K, crash_reward), set_draw_offset=venv.env.gauss_set_draw_offset, build=build,
+                      after_replay=copy_rows)
+    _, steps = _run_episode(venv, lambda t: _gauss_act_step_record(venv, buf.slot(t), eager_prev, crash_reward), max_steps, check_every, captured)
+    out = buf.finish(steps)
+    T = steps
+    if not venv.auto_reset:
+        T = int(out["alive"].any(dim=1).sum())
+    if max_steps is not None:
+        T = min(T, max_steps)
+    return {"states": out["state"][:T], "eps": out["eps"][:T], "pre": out["pre"][:T], "actions": out["action"][:T], "log_probs": out["logp"][:T],
+            "rewards": out["reward"][:T], "alive": out["alive"][:T]}
+
+
+def prepare_gauss_batch(venv, ep, gamma=0.99, normalize="returns"):
+    """From the dict collect_episode_gauss returns to the continuous learner's batch on the device: okenv_batch_prepare without action
+    and prob (discounted returns per agent with `alive` as the episode boundary, normalised over the M alive samples -- the
+    reference's (G - mean) / (std + eps) -- and the alive samples packed in step-major order), then eps and pre gathered by the
+    samples' flat indices.  Returns a dict of device tensors: states [M, R], eps, pre [M, 2], returns [M], index [M] i32, count (an
+    int: the call waits for the stream once to read it) and stats."""
+    rewards, alive = ep["rewards"], ep["alive"]
+    T, N = rewards.shape
+    R = ep["states"].shape[2]
+    dev = rewards.device
+    if alive.dtype not in (torch.bool, torch.uint8):
+        alive = alive != 0
+    record = [_rows_of(rewards.float(), 1), _rows_of(alive, 1)]
+    if len({s for _, s in record}) > 1:
+        record = [(x.contiguous(), N) for x, _ in record]
+    state, field_stride = _rows_of(ep["states"].float(), R)
+    cap = T * N
+    out = {"state": torch.empty((cap, R), dtype=torch.float32, device=dev), "ret": torch.empty(cap, dtype=torch.float32, device=dev),
+           "index": torch.empty(cap, dtype=torch.int32, device=dev), "stats": torch.empty(capi.BATCH_STATS_BYTES // 8, dtype=torch.float64, device=dev)}
+    venv.env.batch_prepare(T, N, {"reward": record[0][0], "alive": record[1][0], "state": state}, out, state_width=R, record_stride=record[0][1],
+                           field_stride=field_stride, gamma=gamma, lam=1.0, normalize=_NORMALIZE[normalize])
+    M = venv.env.batch_count()  # waits for the stream: the inputs above may go now
+    index = out["index"][:M]
+    flat = index.long()
+    return {"states": out["state"][:M], "eps": ep["eps"].reshape(-1, 2)[flat].contiguous(), "pre": ep["pre"].reshape(-1, 2)[flat].contiguous(),
+            "returns": out["ret"][:M], "index": index, "count": M, "stats": out["stats"]}
+
+
+def reinforce_continuous_update(venv, batch, slice=16384, accumulate=True, reduce="sum", grad="reference", shuffle=False, grads=False):
+    """ReinforceAgent::updatePolicy of RLRacers/ReinforceContinuous on the device (okenv_gauss_update, DESIGN.md section 20) for the
+    dict prepare_gauss_batch returns: loss = sum of -log_prob * return over the M samples, its gradient through the two-hidden-layer
+    network and log_std, one Adam step, in place in the parameters the device actor acts with (venv.enable_gauss_actor,
+    venv.enable_gauss_learner first; venv.pull_gauss() brings them back to the module).
+
+    grad "reference": the gradient autograd gives for the reference's graph, in which the pre-tanh sample is not detached (all of it
+    flows through the tanh correction); "score": the score-function estimator.  slice, accumulate, reduce and shuffle are
+    reinforce_update's.  Everything is enqueued on the environment's stream; nothing is read back.  Returns a dict of device tensors:
+    loss [steps] and, with grads=True, grad of the last step."""
+    assert getattr(venv, "gauss_learner_enabled", False), "call venv.enable_gauss_learner() first"
+    M = int(batch["states"].shape[0])
+    dev = batch["states"].device
+    data = {"state": batch["states"].float().contiguous(), "eps": batch["eps"].float().contiguous(), "pre": batch["pre"].float().contiguous(),
+            "ret": batch["returns"].reshape(-1).float().contiguous()}
+    order = torch.randperm(M, device=dev).to(torch.int32).contiguous() if shuffle else None
+    out = {"loss": torch.empty(1 if accumulate else (M + slice - 1) // slice, dtype=torch.float32, device=dev)}
+    if grads:
+        out["grad"] = torch.empty(venv.env.gauss_num_params(), dtype=torch.float32, device=dev)
+    venv.env.gauss_update(data, M, slice, accumulate, reduce, grad, order, out)
+    venv._update_inputs = (data, order)  # alive until the next update: the kernels are only enqueued
+    return out
 
 
 def batch_stats(batch):

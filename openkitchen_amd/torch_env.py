@@ -386,6 +386,65 @@ class VectorEnvironment:
         reward: None for the reference's +1 per step, or a device float32 tensor [N].  Usable inside capture(body)."""
         self.env.ddpg_replay_push(record, reward)
 
+    # ---- continuous REINFORCE (include/okenv.h, DESIGN.md section 20) --------------------------------------------------------
+    @staticmethod
+    def _gauss_tensors(policy):
+        """[log_std, fc1.weight, fc1.bias, fc2.weight, fc2.bias, mean.weight, mean.bias] of a module built like the reference's
+        Policy (RLRacers/ReinforceContinuous/Policy.hpp:17-30): parameters() order, the module's own log_std first."""
+        try:
+            t = [policy.log_std, policy.fc1.weight, policy.fc1.bias, policy.fc2.weight, policy.fc2.bias, policy.mean.weight, policy.mean.bias]
+        except AttributeError:
+            raise ValueError("policy: expected a module with log_std, fc1, fc2 and mean (Linear layers with biases)")
+        if any(x is None for x in t):
+            raise ValueError("policy: fc1, fc2 and mean need their biases")
+        return t
+
+    def enable_gauss_actor(self, policy_module, **config):
+        """Attaches the reference's continuous REINFORCE agent (RLRacers/ReinforceContinuous): `policy_module` has log_std [2],
+        fc1 = Linear(R, H1), fc2 = Linear(H1, H2) and mean = Linear(H2, 2); the device applies ReLU behind fc1 and fc2 and samples
+        tanh(mu + exp(log_std) * eps) * scale + bias.  config: the members of okenv_gauss_config but the widths (capi.gauss_config:
+        scale, bias, greedy, seed, agent_base).  The device's parameters start from the module's; rollout's update steps them in
+        place, and pull_gauss() copies them back."""
+        t = self._gauss_tensors(policy_module)
+        H1, H2 = t[1].shape[0], t[3].shape[0]
+        shapes = [(2,), (H1, self.num_rays), (H1,), (H2, H1), (H2,), (2, H2), (2,)]
+        if [tuple(x.shape) for x in t] != shapes:
+            raise ValueError("policy: shapes %s do not form a %d -> H1 -> H2 -> 2 network with log_std [2]" % ([tuple(x.shape) for x in t], self.num_rays))
+        config.setdefault("seed", self.seed)
+        config.setdefault("agent_base", self.agent_base)
+        self.env.gauss_create(H1, H2, **config)
+        self._gauss_nets = t
+        self._gauss_graphs = {}
+        self.gauss_learner_enabled = False
+        self.sync_gauss()
+
+    def sync_gauss(self):
+        """The module's current parameters to the device actor, device to device on the environment's stream."""
+        self._gauss_flat = self._flatten(self._gauss_nets)  # alive until the next hand-over: the copy is asynchronous
+        self.env.gauss_set_params(self._gauss_flat)
+
+    def enable_gauss_learner(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
+        """Adam for the device's Gaussian actor (the reference's learning rate, torch.optim.Adam's defaults)."""
+        assert getattr(self, "_gauss_nets", None) is not None, "call enable_gauss_actor(policy) first"
+        self.env.gauss_learner_create(lr, beta1, beta2, eps)
+        self.gauss_learner_enabled = True
+
+    def pull_gauss(self):
+        """Copies the device's parameters back into the module given to enable_gauss_actor."""
+        flat = torch.empty(self.env.gauss_num_params(), dtype=torch.float32, device=self.device)
+        self.env.gauss_state(out={"params": flat})
+        self._unflatten(self._gauss_nets, flat)
+
+    def set_gauss_greedy(self, greedy):
+        self.env.gauss_set_greedy(greedy)
+        self._gauss_graphs = {}  # a captured launch carries the old value
+
+    def gauss_act(self, record=None):
+        """The sampled (or greedy) action of every agent from the last observation, written into `throttle` / `steering`: one kernel
+        on the environment's stream, no synchronisation, usable inside capture(body).  record: optional dict of device tensors
+        ("state" [N,R], "eps", "pre", "action" [N,2], "logp" [N] float32, "alive" [N] uint8) that receive the sample."""
+        self.env.gauss_act(record)
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
