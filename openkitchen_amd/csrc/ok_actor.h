@@ -14,15 +14,28 @@
 #include "../../include/okenv_reinforce.h"
 #include "okenv_kernels.h"
 
+// What the three act kernels share (okActorKernel here, okDdpgActKernel, okGaussActKernel), in two pieces, so that every kernel's
+// parameter struct keeps the place its widths and vectors had between them (the kernel-argument layout decides how the loads group,
+// docs/HISTORY.md section 29): the step's state with the population, and the words of the draw index
+struct OkActFrame
+{
+    OkDeviceState st;
+    int           N, R;
+};
+
+struct OkActDrawWords
+{
+    const uint32_t *step_word;   // the handle's device-side step count (auto-reset on), or nullptr: host_steps
+    uint32_t        host_steps;
+    const uint32_t *draw_offset; // okenv_actor_ / okenv_ddpg_ / okenv_gauss_set_draw_offset, or nullptr
+};
+
 // What the kernel needs, by value
 struct OkActorParams
 {
-    OkDeviceState      st;
-    int                N, R;
-    const float       *policy, *value;  // parameter vectors on the device, each padded to a multiple of four floats
-    const uint32_t    *step_word;       // the handle's device-side step count (auto-reset on), or nullptr: host_steps
-    uint32_t           host_steps;
-    const uint32_t    *draw_offset;     // okenv_actor_set_draw_offset, or nullptr
+    OkActFrame         f;
+    const float       *policy, *value; // parameter vectors on the device, each padded to a multiple of four floats
+    OkActDrawWords     draw;
     okenv_actor_params ap;
     okenv_actor_record rec;
     ok_reinforce_mask  drop; // okenv_actor_set_dropout: p, its scale and the seed (agent and draw are the kernel's to fill in)
@@ -125,25 +138,70 @@ __device__ __forceinline__ void okActorForwardDropout(const float *net, const in
 
 extern __shared__ float ok_actor_lds[];
 
+// ---- shared pieces of the act kernels: the counterpart of ok_learn.h's okLearnBegin -------------------------------------------------
+
+// The index of this act's draws: the steps taken so far plus the caller's offset
+__device__ __forceinline__ uint32_t okActDraw(const OkActDrawWords &w)
+{
+    return (w.step_word != nullptr ? w.step_word[0] : w.host_steps) + (w.draw_offset != nullptr ? w.draw_offset[0] : 0U);
+}
+
+// What every act kernel begins with: the group, its lane, its agent and its input row
+struct OkActGroup
+{
+    int    g, lane;
+    long   a;     // the group's agent; a spare group of the last workgroup takes the last agent and part in shuffles and barriers
+    bool   valid; // false for such a spare group: it stores nothing
+    float *x;     // the group's row of xs
+};
+
+// The group copies its row x = dist / 200 into xs (rows `row_stride` apart) and into the record's state (or nullptr), consecutive
+// lanes on consecutive addresses.  The kernel's __syncthreads() follows.
+__device__ __forceinline__ OkActGroup okActBegin(const float *dist, const int N, const int R, float *xs, const int row_stride, float *rec_state)
+{
+    OkActGroup s;
+    s.g              = static_cast<int>(threadIdx.x) / kActorLanes;
+    s.lane           = static_cast<int>(threadIdx.x) & (kActorLanes - 1);
+    const long a_raw = static_cast<long>(blockIdx.x) * kActorAgents + s.g;
+    s.valid          = a_raw < N;
+    s.a              = s.valid ? a_raw : static_cast<long>(N) - 1;
+    s.x              = xs + s.g * row_stride;
+    for (int i = s.lane; i < R; i += kActorLanes)
+    {
+        const float v = dist[s.a * R + i] / OK_SENSOR_RANGE;
+        s.x[i]        = v;
+        if (s.valid && rec_state != nullptr)
+            rec_state[s.a * R + i] = v;
+    }
+    return s;
+}
+
+// The record's last field, by the group's first lane
+__device__ __forceinline__ void okActAlive(const uint8_t *crashed, uint8_t *rec_alive, const long a)
+{
+    if (rec_alive != nullptr)
+        rec_alive[a] = crashed[a] ? 0 : 1;
+}
+
 // Dropout: the policy network's hidden layer is masked (okenv_actor_set_dropout with p > 0); false is section 14's kernel as it was
 template <bool Dropout>
 __global__ __launch_bounds__(kActorThreads) void okActorKernel(const OkActorParams p)
 {
-    const int R = p.R, H = p.ap.hidden, A = p.ap.num_actions, Hv = p.ap.value_hidden, rp = okActorRowStride(R);
+    const int R = p.f.R, H = p.ap.hidden, A = p.ap.num_actions, Hv = p.ap.value_hidden, rp = okActorRowStride(R);
     float    *pol = ok_actor_lds, *val = pol + okActorNetFloats(R, H, A), *xs = val + okActorNetFloats(R, Hv, 1);
     okActorStage(pol, p.policy, R, H, ok_actor_num_params(R, H, A));
     if (Hv > 0)
         okActorStage(val, p.value, R, Hv, ok_actor_num_params(R, Hv, 1));
+    // (okActBegin and okActDraw written out: with them this kernel's schedule differs from the one it had, docs/HISTORY.md section 29)
     const int  g     = static_cast<int>(threadIdx.x) / kActorLanes;
     const int  lane  = static_cast<int>(threadIdx.x) & (kActorLanes - 1);
     const long a_raw = static_cast<long>(blockIdx.x) * kActorAgents + g;
-    const bool valid = a_raw < p.N;
-    const long a     = valid ? a_raw : static_cast<long>(p.N) - 1; // (spare lanes of the last wave take part in the shuffles)
-    // the input, and its record slot: the group copies its row, consecutive lanes on consecutive addresses
-    float *x = xs + g * rp; // (the odd stride again: the 4 groups of a half read 4 different banks)
+    const bool valid = a_raw < p.f.N;
+    const long a     = valid ? a_raw : static_cast<long>(p.f.N) - 1; // (spare lanes of the last wave take part in the shuffles)
+    float     *x     = xs + g * rp; // (the odd stride again: the 4 groups of a half read 4 different banks)
     for (int i = lane; i < R; i += kActorLanes)
     {
-        const float v = p.st.dist[a * R + i] / OK_SENSOR_RANGE;
+        const float v = p.f.st.dist[a * R + i] / OK_SENSOR_RANGE;
         x[i]          = v;
         if (valid && p.rec.state != nullptr)
             p.rec.state[a * R + i] = v;
@@ -154,7 +212,7 @@ __global__ __launch_bounds__(kActorThreads) void okActorKernel(const OkActorPara
     { // the mask belongs to the agent and the draw index the action draw below uses
         ok_reinforce_mask m = p.drop;
         m.agent             = p.ap.agent_base + static_cast<uint32_t>(a);
-        m.draw              = (p.step_word != nullptr ? p.step_word[0] : p.host_steps) + (p.draw_offset != nullptr ? p.draw_offset[0] : 0U);
+        m.draw              = (p.draw.step_word != nullptr ? p.draw.step_word[0] : p.draw.host_steps) + (p.draw.draw_offset != nullptr ? p.draw.draw_offset[0] : 0U);
         okActorForwardDropout(pol, R, H, A, x, lane, m, z);
     }
     else
@@ -166,7 +224,7 @@ __global__ __launch_bounds__(kActorThreads) void okActorKernel(const OkActorPara
         value = zv[0];
     }
     const int      best  = ok_actor_argmax(z, A);
-    const uint32_t draw  = (p.step_word != nullptr ? p.step_word[0] : p.host_steps) + (p.draw_offset != nullptr ? p.draw_offset[0] : 0U);
+    const uint32_t draw  = (p.draw.step_word != nullptr ? p.draw.step_word[0] : p.draw.host_steps) + (p.draw.draw_offset != nullptr ? p.draw.draw_offset[0] : 0U);
     const uint32_t agent = p.ap.agent_base + static_cast<uint32_t>(a);
     float          mine  = z[0]; // lane k holds z_k
 #pragma unroll
@@ -205,16 +263,15 @@ __global__ __launch_bounds__(kActorThreads) void okActorKernel(const OkActorPara
             thr   = p.ap.action_table[k][0];
             steer = p.ap.action_table[k][1];
         }
-    p.st.thr[a]   = thr;
-    p.st.steer[a] = steer;
+    p.f.st.thr[a]   = thr;
+    p.f.st.steer[a] = steer;
     if (p.rec.action != nullptr)
         p.rec.action[a] = action;
     if (p.rec.prob != nullptr)
         p.rec.prob[a] = prob;
     if (p.rec.value != nullptr && Hv > 0)
         p.rec.value[a] = value;
-    if (p.rec.alive != nullptr)
-        p.rec.alive[a] = p.st.crashed[a] ? 0 : 1;
+    okActAlive(p.f.st.crashed, p.rec.alive, a);
 }
 
 // ---- host side (no GPU) ------------------------------------------------------------------------------------------------------

@@ -27,12 +27,10 @@
 
 struct OkDdpgActParams
 {
-    OkDeviceState     st;
-    int               N, R, H;
-    const float      *actor;       // padded to a multiple of four floats
-    const uint32_t   *step_word;   // the handle's device-side step count (auto-reset on), or nullptr: host_steps
-    uint32_t          host_steps;
-    const uint32_t   *draw_offset; // okenv_ddpg_set_draw_offset, or nullptr
+    OkActFrame        f; // (ok_actor.h)
+    int               H;
+    const float      *actor; // padded to a multiple of four floats
+    OkActDrawWords    draw;
     float             scale[2], bias[2], noise[2];
     uint32_t          seed, agent_base;
     okenv_ddpg_record rec;
@@ -56,44 +54,32 @@ __device__ __forceinline__ void okDdpgGroupAction(const float z0, const float z1
 
 __global__ __launch_bounds__(kActorThreads) void okDdpgActKernel(const OkDdpgActParams p)
 {
-    const int R = p.R, H = p.H, rp = okActorRowStride(R);
+    const int R = p.f.R, H = p.H;
     float    *net = ok_actor_lds, *xs = net + okActorNetFloats(R, H, 2);
     okActorStage(net, p.actor, R, H, ok_actor_num_params(R, H, 2));
-    const int  g     = static_cast<int>(threadIdx.x) / kActorLanes;
-    const int  lane  = static_cast<int>(threadIdx.x) & (kActorLanes - 1);
-    const long a_raw = static_cast<long>(blockIdx.x) * kActorAgents + g;
-    const bool valid = a_raw < p.N;
-    const long a     = valid ? a_raw : static_cast<long>(p.N) - 1; // (spare lanes of the last wave take part in the shuffles)
-    float     *x     = xs + g * rp;
-    for (int i = lane; i < R; i += kActorLanes)
-    { // the group copies its row, consecutive lanes on consecutive addresses
-        const float v = p.st.dist[a * R + i] / OK_SENSOR_RANGE;
-        x[i]          = v;
-        if (valid && p.rec.state != nullptr)
-            p.rec.state[a * R + i] = v;
-    }
+    const OkActGroup s    = okActBegin(p.f.st.dist, p.f.N, R, xs, okActorRowStride(R), p.rec.state);
+    const int        lane = s.lane;
+    const long       a    = s.a;
     __syncthreads();
     float z[OK_ACTOR_MAX_ACTIONS], act[2], t[2];
-    okActorForward(net, R, H, 2, x, lane, z);
+    okActorForward(net, R, H, 2, s.x, lane, z);
     okDdpgGroupAction(z[0], z[1], p.scale, p.bias, lane, act, t);
-    if (lane != 0 || !valid)
+    if (lane != 0 || !s.valid)
         return;
     if (p.noise[0] > 0.F || p.noise[1] > 0.F)
     {
-        const uint32_t draw = (p.step_word != nullptr ? p.step_word[0] : p.host_steps) + (p.draw_offset != nullptr ? p.draw_offset[0] : 0U);
-        const ok_u32x4 r    = ok_ddpg_draw(p.seed, p.agent_base + static_cast<uint32_t>(a), draw);
-        act[0]              = ok_ddpg_explore(act[0], p.noise[0], r.v[0], p.scale[0], p.bias[0]);
-        act[1]              = ok_ddpg_explore(act[1], p.noise[1], r.v[1], p.scale[1], p.bias[1]);
+        const ok_u32x4 r = ok_ddpg_draw(p.seed, p.agent_base + static_cast<uint32_t>(a), okActDraw(p.draw));
+        act[0]           = ok_ddpg_explore(act[0], p.noise[0], r.v[0], p.scale[0], p.bias[0]);
+        act[1]           = ok_ddpg_explore(act[1], p.noise[1], r.v[1], p.scale[1], p.bias[1]);
     }
-    p.st.thr[a]   = act[0];
-    p.st.steer[a] = act[1];
+    p.f.st.thr[a]   = act[0];
+    p.f.st.steer[a] = act[1];
     if (p.rec.action != nullptr)
     {
         p.rec.action[2 * a]     = act[0];
         p.rec.action[2 * a + 1] = act[1];
     }
-    if (p.rec.alive != nullptr)
-        p.rec.alive[a] = p.st.crashed[a] ? 0 : 1;
+    okActAlive(p.f.st.crashed, p.rec.alive, a);
 }
 
 // ---- the push: section 17's kernels with a two-float action row -----------------------------------------------------------------------

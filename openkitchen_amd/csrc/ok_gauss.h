@@ -8,7 +8,7 @@
 //   okGaussActKernel       32 agents x 8 lanes per workgroup: x = dist / 200, the network, the draw, tanh * scale + bias, the record
 //   okGaussGradKernel      one workgroup per chunk of 32 positions: forward, seed and backward into the samples' LDS rows, then the
 //                          chunk's partial of every parameter's gradient (register tiles over the weight matrices) and of the loss
-//   okReinforceStepKernel  section 19's join kernels on this parameter vector (ok_reinforce.h)
+//   okReinforceStepKernel  section 19's join kernels on this parameter vector (ok_reinforce.h: OkJoinParams)
 // No atomics anywhere: the sums' order is the rule's.
 #ifndef OK_GAUSS_H
 #define OK_GAUSS_H
@@ -181,12 +181,10 @@ __device__ __forceinline__ float okGaussGroupLogp(const float nk, const float lk
 
 struct OkGaussActParams
 {
-    OkDeviceState      st;
-    int                N, R, H1, H2;
+    OkActFrame         f; // (ok_actor.h)
+    int                H1, H2;
     const float       *params;
-    const uint32_t    *step_word;   // the handle's device-side step count (auto-reset on), or nullptr: host_steps
-    uint32_t           host_steps;
-    const uint32_t    *draw_offset; // okenv_gauss_set_draw_offset, or nullptr
+    OkActDrawWords     draw;
     float              scale[2], bias[2];
     int                greedy;
     uint32_t           seed, agent_base;
@@ -195,43 +193,30 @@ struct OkGaussActParams
 
 __global__ __launch_bounds__(kActorThreads) void okGaussActKernel(const OkGaussActParams p)
 {
-    const int        R = p.R, H1 = p.H1, H2 = p.H2;
+    const int        R = p.f.R, H1 = p.H1, H2 = p.H2;
     const OkGaussNet ln  = okGaussNet(R, H1, H2, 2);
     float           *net = ok_actor_lds, *xs = net + ln.floats, *h1s = xs + kActorAgents * ln.rp, *h2s = h1s + kActorAgents * okGaussHiddenStride(H1);
     okGaussStage(net, p.params, ln, R, H1, H2, 2);
-    const int  g     = static_cast<int>(threadIdx.x) / kActorLanes;
-    const int  lane  = static_cast<int>(threadIdx.x) & (kActorLanes - 1);
-    const long a_raw = static_cast<long>(blockIdx.x) * kActorAgents + g;
-    const bool valid = a_raw < p.N;
-    const long a     = valid ? a_raw : static_cast<long>(p.N) - 1; // (the spare groups of the last workgroup take part in the barriers)
-    float     *x     = xs + g * ln.rp;
-    for (int i = lane; i < R; i += kActorLanes)
-    { // the group copies its row, consecutive lanes on consecutive addresses
-        const float v = p.st.dist[a * R + i] / OK_SENSOR_RANGE;
-        x[i]          = v;
-        if (valid && p.rec.state != nullptr)
-            p.rec.state[a * R + i] = v;
-    }
+    const OkActGroup s = okActBegin(p.f.st.dist, p.f.N, R, xs, ln.rp, p.rec.state);
+    const int        g = s.g, lane = s.lane;
+    const long       a = s.a;
     __syncthreads();
-    const float mu = okGaussForward(net, ln, R, H1, H2, 2, x, h1s + g * okGaussHiddenStride(H1), h2s + g * okGaussHiddenStride(H2), lane);
+    const float mu = okGaussForward(net, ln, R, H1, H2, 2, s.x, h1s + g * okGaussHiddenStride(H1), h2s + g * okGaussHiddenStride(H2), lane);
     // lanes 0 and 1 take one component each: the draw, exp, tanh and log (fp64 evaluations)
     const int   k  = lane & 1;
     const float ls = net[ln.ls + k];
     float       eps = 0.F;
     if (p.greedy == 0 && lane < 2)
-    {
-        const uint32_t draw = (p.step_word != nullptr ? p.step_word[0] : p.host_steps) + (p.draw_offset != nullptr ? p.draw_offset[0] : 0U);
-        eps                 = ok_gauss_eps(p.seed, p.agent_base + static_cast<uint32_t>(a), draw, k);
-    }
+        eps = ok_gauss_eps(p.seed, p.agent_base + static_cast<uint32_t>(a), okActDraw(p.draw), k);
     float               z;
     const ok_gauss_comp c    = ok_gauss_component(mu, ls, eps, 0.F, 0, p.greedy, &z);
     const float         act  = ok_gauss_action(c.t, k == 1 ? p.scale[1] : p.scale[0], k == 1 ? p.bias[1] : p.bias[0]);
     const float         logp = okGaussGroupLogp(c.n, c.l, 2);
     const float         act1 = __shfl(act, 1, kActorLanes), eps1 = __shfl(eps, 1, kActorLanes), pre1 = __shfl(c.pre, 1, kActorLanes);
-    if (lane != 0 || !valid)
+    if (lane != 0 || !s.valid)
         return;
-    p.st.thr[a]   = act;
-    p.st.steer[a] = act1;
+    p.f.st.thr[a]   = act;
+    p.f.st.steer[a] = act1;
     if (p.rec.eps != nullptr && p.greedy == 0)
     {
         p.rec.eps[2 * a]     = eps;
@@ -249,8 +234,7 @@ __global__ __launch_bounds__(kActorThreads) void okGaussActKernel(const OkGaussA
     }
     if (p.rec.logp != nullptr)
         p.rec.logp[a] = logp;
-    if (p.rec.alive != nullptr)
-        p.rec.alive[a] = p.st.crashed[a] ? 0 : 1;
+    okActAlive(p.f.st.crashed, p.rec.alive, a);
 }
 
 // ok_gauss_normal_pair alone, one word pair per thread (okenv_debug_normal)
@@ -263,7 +247,7 @@ __global__ void __launch_bounds__(256) okDebugNormalKernel(const uint32_t *w0, c
 
 // ---- the update -----------------------------------------------------------------------------------------------------------------
 
-// What the gradient kernel needs for one slice, by value (the join kernels take section 19's OkReinforceParams)
+// What the gradient kernel needs for one slice, by value (the join kernels take section 19's OkJoinParams)
 struct OkGaussParams
 {
     int               R, H1, H2, A;
@@ -511,107 +495,69 @@ inline void okGaussActHost(const okenv_gauss_config &c, const float *par, const 
     }
 }
 
-// Optimiser steps of one call
-inline int okGaussSteps(const okenv_gauss_update_config &cfg, const int32_t M, const int32_t B)
-{
-    return cfg.accumulate != 0 ? 1 : okLearnMinibatches(M, B);
-}
-
 // The rule on host arrays; every output may be nullptr
 inline void okGaussUpdateHost(const okenv_learner_params &lp, const okenv_gauss_update_config &cfg, const int R, const int H1, const int H2, const int A,
                               okenv_gauss_state &st, const okenv_gauss_batch &in, const int M, const int B, const int32_t *order,
                               const okenv_gauss_output &out)
 {
-    const int          P = ok_gauss_num_params(R, H1, H2, A), cols = P + 1;
-    const int          slices = okLearnMinibatches(M, B), c_max = (std::min(B, M) + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+    const int          P = ok_gauss_num_params(R, H1, H2, A);
     const size_t       W = OK_ACTOR_MAX_ACTIONS;
-    std::vector<float> part(static_cast<size_t>(c_max) * cols), acc(static_cast<size_t>(cols), 0.F), terms(OK_LEARN_CHUNK);
+    std::vector<float> terms(OK_LEARN_CHUNK);
     std::vector<float> xs(static_cast<size_t>(OK_LEARN_CHUNK) * R), h1s(static_cast<size_t>(OK_LEARN_CHUNK) * H1), d1s(h1s.size());
     std::vector<float> h2s(static_cast<size_t>(OK_LEARN_CHUNK) * H2), d2s(h2s.size()), dzs(OK_LEARN_CHUNK * W), dlss(OK_LEARN_CHUNK * W);
-    const bool         score = cfg.grad_mode == OK_GAUSS_GRAD_SCORE;
-    int                slot  = 0;
-    for (int k = 0; k < slices; ++k)
+    const bool            score = cfg.grad_mode == OK_GAUSS_GRAD_SCORE;
+    const ok_gauss_layout pv    = ok_gauss_offsets(R, H1, H2, A);
+    const float          *par   = st.params;
+    // the per-sample mathematics of one chunk
+    const auto chunk_sums = [&](const long first, const int n, float *col)
     {
-        const long            base = static_cast<long>(k) * B;
-        const int             Bk = static_cast<int>(std::min<long>(B, M - base)), C = (Bk + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
-        const ok_gauss_layout pv = ok_gauss_offsets(R, H1, H2, A);
-        const float          *par = st.params;
-        for (int chunk = 0; chunk < C; ++chunk)
+        for (int q = 0; q < n; ++q)
         {
-            const int n   = std::min(OK_LEARN_CHUNK, Bk - chunk * OK_LEARN_CHUNK);
-            float    *col = part.data() + static_cast<size_t>(chunk) * cols;
+            const long   pos = first + q;
+            const int    idx = ok_learn_clamp_index(order != nullptr ? static_cast<long long>(order[pos]) : static_cast<long long>(pos), M);
+            const size_t sq = static_cast<size_t>(q), si = static_cast<size_t>(idx);
+            float       *x = xs.data() + sq * R, *h1 = h1s.data() + sq * H1, *d1 = d1s.data() + sq * H1, *h2 = h2s.data() + sq * H2, *d2 = d2s.data() + sq * H2;
+            float       *dz = dzs.data() + sq * W, *dls = dlss.data() + sq * W;
+            for (int i = 0; i < R; ++i)
+                x[i] = in.state[si * R + i];
+            float mu[OK_ACTOR_MAX_ACTIONS], nn[OK_ACTOR_MAX_ACTIONS] = {0.F}, ll[OK_ACTOR_MAX_ACTIONS] = {0.F};
+            okGaussHostForward(par, R, H1, H2, A, x, h1, h2, mu);
+            const float G = in.ret[idx];
+            for (int a = 0; a < OK_ACTOR_MAX_ACTIONS; ++a)
+            {
+                dz[a] = dls[a] = 0.F;
+                if (a >= A)
+                    continue;
+                float               z;
+                const ok_gauss_comp c = ok_gauss_component(mu[a], par[a], score ? 0.F : in.eps[si * A + a], score ? in.pre[si * A + a] : 0.F, score ? 1 : 0, 0, &z);
+                ok_gauss_seed(cfg.grad_mode, c, z, G, &dz[a], &dls[a]);
+                nn[a] = c.n;
+                ll[a] = c.l;
+            }
+            terms[sq] = -(ok_gauss_logp(nn, ll, A) * G);
+            for (int j = 0; j < H2; ++j)
+                d2[j] = ok_learn_back_hidden(par + pv.w3, H2, A, dz, j, h2[j]);
+            for (int i = 0; i < H1; ++i)
+            {
+                const float dh = ok_gauss_back(par + pv.w2, H1, H2, d2, i);
+                d1[i]          = h1[i] > 0.F ? dh : 0.F;
+            }
+        }
+        for (int pi = 0; pi < P; ++pi)
+        {
+            const ok_learn_slot s = ok_gauss_decode(pi, R, H1, H2, A);
+            float               a = 0.F;
             for (int q = 0; q < n; ++q)
             {
-                const long   pos = base + chunk * OK_LEARN_CHUNK + q;
-                const int    idx = ok_learn_clamp_index(order != nullptr ? static_cast<long long>(order[pos]) : static_cast<long long>(pos), M);
-                const size_t sq = static_cast<size_t>(q), si = static_cast<size_t>(idx);
-                float       *x = xs.data() + sq * R, *h1 = h1s.data() + sq * H1, *d1 = d1s.data() + sq * H1, *h2 = h2s.data() + sq * H2, *d2 = d2s.data() + sq * H2;
-                float       *dz = dzs.data() + sq * W, *dls = dlss.data() + sq * W;
-                for (int i = 0; i < R; ++i)
-                    x[i] = in.state[si * R + i];
-                float mu[OK_ACTOR_MAX_ACTIONS], nn[OK_ACTOR_MAX_ACTIONS] = {0.F}, ll[OK_ACTOR_MAX_ACTIONS] = {0.F};
-                okGaussHostForward(par, R, H1, H2, A, x, h1, h2, mu);
-                const float G = in.ret[idx];
-                for (int a = 0; a < OK_ACTOR_MAX_ACTIONS; ++a)
-                {
-                    dz[a] = dls[a] = 0.F;
-                    if (a >= A)
-                        continue;
-                    float               z;
-                    const ok_gauss_comp c = ok_gauss_component(mu[a], par[a], score ? 0.F : in.eps[si * A + a], score ? in.pre[si * A + a] : 0.F, score ? 1 : 0, 0, &z);
-                    ok_gauss_seed(cfg.grad_mode, c, z, G, &dz[a], &dls[a]);
-                    nn[a] = c.n;
-                    ll[a] = c.l;
-                }
-                terms[sq] = -(ok_gauss_logp(nn, ll, A) * G);
-                for (int j = 0; j < H2; ++j)
-                    d2[j] = ok_learn_back_hidden(par + pv.w3, H2, A, dz, j, h2[j]);
-                for (int i = 0; i < H1; ++i)
-                {
-                    const float dh = ok_gauss_back(par + pv.w2, H1, H2, d2, i);
-                    d1[i]          = h1[i] > 0.F ? dh : 0.F;
-                }
+                const size_t sq = static_cast<size_t>(q);
+                a = a + ok_gauss_term(s, xs.data() + sq * R, h1s.data() + sq * H1, h2s.data() + sq * H2, d1s.data() + sq * H1, d2s.data() + sq * H2,
+                                      dzs.data() + sq * W, dlss.data() + sq * W);
             }
-            for (int pi = 0; pi < P; ++pi)
-            {
-                const ok_learn_slot s = ok_gauss_decode(pi, R, H1, H2, A);
-                float               a = 0.F;
-                for (int q = 0; q < n; ++q)
-                {
-                    const size_t sq = static_cast<size_t>(q);
-                    a = a + ok_gauss_term(s, xs.data() + sq * R, h1s.data() + sq * H1, h2s.data() + sq * H2, d1s.data() + sq * H1, d2s.data() + sq * H2,
-                                          dzs.data() + sq * W, dlss.data() + sq * W);
-                }
-                col[pi] = a;
-            }
-            col[P] = okLearnHostSumTerms(terms.data(), n);
+            col[pi] = a;
         }
-        const bool           step = cfg.accumulate == 0 || k + 1 == slices;
-        ok_learn_adam_consts adam{};
-        if (step)
-        {
-            st.t += 1;
-            adam = okLearnAdamConsts(lp, st.t);
-        }
-        const float count = static_cast<float>(cfg.accumulate != 0 ? M : Bk);
-        for (int column = 0; column < cols; ++column)
-        {
-            const float sum = ok_learn_tree(part.data() + column, cols, static_cast<uint32_t>(C));
-            if (!step)
-            {
-                acc[static_cast<size_t>(column)] = acc[static_cast<size_t>(column)] + sum;
-                continue;
-            }
-            const float total = cfg.accumulate != 0 ? acc[static_cast<size_t>(column)] + sum : sum;
-            const float gr    = ok_reinforce_reduce(total, cfg.reduce, count);
-            if (column < P)
-                okLearnStepParam(st.params, st.m, st.v, out.grad, column, gr, adam);
-            else if (out.loss != nullptr)
-                out.loss[slot] = gr;
-        }
-        if (step)
-            ++slot;
-    }
+        col[P] = okLearnHostSumTerms(terms.data(), n);
+    };
+    okSliceUpdateHost(lp, cfg.accumulate != 0, okJoinOn(P, st.params, st.m, st.v, cfg.reduce, out.grad), st.t, M, B, out.loss, chunk_sums);
 }
 
 #endif // OK_GAUSS_H

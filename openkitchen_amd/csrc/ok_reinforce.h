@@ -21,11 +21,50 @@
 #include "../../include/okenv_reinforce.h"
 #include "ok_learn.h"
 
-// What the kernels need for one slice, by value
+// What the join kernel okReinforceStepKernel<Step> reads, by value: the whole-episode updates (this one, ok_gauss.h's) share it
+struct OkJoinParams
+{
+    int                  Pp, cols, C; // parameters; columns of the partials: [parameters | loss]; chunks of this slice
+    float               *policy, *pol_m, *pol_v;
+    float               *part;        // [C][cols] (the tree works in place)
+    float               *acc;         // [cols], or nullptr when every slice steps
+    int                  reduce;
+    float                count;
+    ok_learn_adam_consts adam;
+    float               *loss;        // this step's slot, or nullptr
+    float               *grad_policy;
+};
+
+// The join of a parameter vector of P floats with its moments; C, part, acc, count, adam and loss are the slice loop's to fill in
+inline OkJoinParams okJoinOn(const int P, float *par, float *par_m, float *par_v, const int reduce, float *grad)
+{
+    OkJoinParams j{};
+    j.Pp          = P;
+    j.cols        = P + 1;
+    j.policy      = par;
+    j.pol_m       = par_m;
+    j.pol_v       = par_v;
+    j.reduce      = reduce;
+    j.grad_policy = grad;
+    return j;
+}
+
+// A column's total behind the last join of a step, in the join kernel and in the host frame: `reduce`, then the parameter's gradient
+// output and Adam in place, or the step's loss slot
+__host__ __device__ inline void okJoinStep(const OkJoinParams &p, const int column, const float total)
+{
+    const float g = ok_reinforce_reduce(total, p.reduce, p.count);
+    if (column < p.Pp)
+        okLearnStepParam(p.policy, p.pol_m, p.pol_v, p.grad_policy, column, g, p.adam);
+    else if (p.loss != nullptr)
+        *p.loss = g;
+}
+
+// What the gradient kernel needs for one slice, by value
 struct OkReinforceParams
 {
     int                   R, H, A;
-    int                   M, Bk, C; // samples, positions of this slice, its chunks
+    int                   M, Bk;    // samples, positions of this slice
     int                   Pp, cols; // parameters of the network; columns of the partials: [policy | loss]
     long                  base;     // first position of the slice: k * B
     const int32_t        *order;    // or nullptr
@@ -33,14 +72,8 @@ struct OkReinforceParams
     ok_reinforce_mask     drop;     // p, s and the seed; agent and draw come from the sample's index
     uint32_t              agent_base, draw_first;
     int                   N;        // agents per recorded row: index = row * N + agent
-    float                *policy, *pol_m, *pol_v;
-    float                *part;     // [C][cols]
-    float                *acc;      // [cols], or nullptr when every slice steps
-    int                   reduce;
-    float                 count;
-    ok_learn_adam_consts  adam;
-    float                *loss;     // this step's slot, or nullptr
-    float                *grad_policy;
+    const float          *policy;
+    float                *part;     // [chunks][cols]
 };
 
 inline size_t okReinforceLdsBytes(const int R, const int H, const int A)
@@ -104,7 +137,7 @@ __global__ __launch_bounds__(kLearnThreads) void okReinforceGradKernel(const OkR
 // Step: false adds the slice's column sums into the accumulator; true joins the accumulator in (when there is one), applies `reduce`
 // and takes the Adam step in place
 template <bool Step>
-__global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okReinforceStepKernel(const OkReinforceParams p)
+__global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okReinforceStepKernel(const OkJoinParams p)
 {
     __shared__ float last[kLearnStepRows][kLearnStepCols];
     int              column = 0;
@@ -114,14 +147,7 @@ __global__ __launch_bounds__(kLearnStepCols *kLearnStepRows) void okReinforceSte
     if constexpr (!Step)
         p.acc[column] = p.acc[column] + sum;
     else
-    {
-        const float total = p.acc != nullptr ? p.acc[column] + sum : sum;
-        const float g     = ok_reinforce_reduce(total, p.reduce, p.count);
-        if (column < p.Pp)
-            okLearnStepParam(p.policy, p.pol_m, p.pol_v, p.grad_policy, column, g, p.adam);
-        else if (p.loss != nullptr)
-            *p.loss = g;
-    }
+        okJoinStep(p, column, p.acc != nullptr ? p.acc[column] + sum : sum);
 }
 
 // ---- host side (no GPU) ------------------------------------------------------------------------------------------------------
@@ -146,10 +172,40 @@ inline const char *okReinforceCheckCall(const okenv_reinforce_config *cfg, const
     return nullptr;
 }
 
-// Optimiser steps of one call
-inline int okReinforceSteps(const okenv_reinforce_config &cfg, const int32_t M, const int32_t B)
+// The frame of a whole-episode update on host arrays: slices of B positions, chunks of OK_LEARN_CHUNK, and behind every slice the join
+// (the fixed tree over the chunk partials of every column, then the accumulator or okJoinStep).  j: okJoinOn's; loss: one value per
+// step, or nullptr.  chunk_sums(first, n, col) writes the columns [parameters | loss] of the chunk of n positions from `first` on.
+template <class ChunkSums>
+inline void okSliceUpdateHost(const okenv_learner_params &lp, const bool accumulate, OkJoinParams j, int64_t &t, const int M, const int B, float *loss,
+                              const ChunkSums &chunk_sums)
 {
-    return cfg.accumulate != 0 ? 1 : okLearnMinibatches(M, B);
+    const int          cols = j.cols, slices = okLearnMinibatches(M, B), c_max = (std::min(B, M) + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+    std::vector<float> part(static_cast<size_t>(c_max) * cols), acc(static_cast<size_t>(cols), 0.F);
+    int                slot = 0;
+    for (int k = 0; k < slices; ++k)
+    {
+        const long base = static_cast<long>(k) * B;
+        const int  Bk = static_cast<int>(std::min<long>(B, M - base)), C = (Bk + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+        for (int chunk = 0; chunk < C; ++chunk)
+            chunk_sums(base + chunk * OK_LEARN_CHUNK, std::min(OK_LEARN_CHUNK, Bk - chunk * OK_LEARN_CHUNK), part.data() + static_cast<size_t>(chunk) * cols);
+        const bool step = !accumulate || k + 1 == slices;
+        if (step)
+        {
+            t += 1;
+            j.count = static_cast<float>(accumulate ? M : Bk);
+            j.adam  = okLearnAdamConsts(lp, t);
+            j.loss  = loss != nullptr ? loss + slot : nullptr;
+            ++slot;
+        }
+        for (int column = 0; column < cols; ++column)
+        {
+            const float sum = ok_learn_tree(part.data() + column, cols, static_cast<uint32_t>(C));
+            if (step)
+                okJoinStep(j, column, accumulate ? acc[static_cast<size_t>(column)] + sum : sum);
+            else
+                acc[static_cast<size_t>(column)] = acc[static_cast<size_t>(column)] + sum;
+        }
+    }
 }
 
 // The rule on host arrays; every output may be nullptr
@@ -157,89 +213,57 @@ inline void okReinforceUpdateHost(const okenv_learner_params &lp, const okenv_re
                                   const uint32_t agent_base, const int R, const int H, const int A, okenv_learner_state &st,
                                   const okenv_reinforce_batch &in, const int M, const int B, const int32_t *order, const okenv_reinforce_output &out)
 {
-    const int          Pp = ok_actor_num_params(R, H, A), cols = Pp + 1;
-    const int          slices = okLearnMinibatches(M, B), c_max = (std::min(B, M) + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
-    std::vector<float> part(static_cast<size_t>(c_max) * cols), xs(static_cast<size_t>(OK_LEARN_CHUNK) * R), terms(OK_LEARN_CHUNK), acc(static_cast<size_t>(cols), 0.F);
+    const int          Pp = ok_actor_num_params(R, H, A);
+    std::vector<float> xs(static_cast<size_t>(OK_LEARN_CHUNK) * R), terms(OK_LEARN_CHUNK);
     OkLearnHostRows    rows;
     rows.h.resize(static_cast<size_t>(OK_LEARN_CHUNK) * H);
     rows.ds.resize(static_cast<size_t>(OK_LEARN_CHUNK) * H);
     rows.dz.resize(static_cast<size_t>(OK_LEARN_CHUNK) * OK_ACTOR_MAX_ACTIONS);
     ok_reinforce_mask m{p_drop > 0.F ? p_drop : 0.F, ok_reinforce_scale(p_drop > 0.F ? p_drop : 0.F), dropout_seed, 0U, 0U};
-    int               slot = 0;
-    for (int k = 0; k < slices; ++k)
+    const float      *b1 = st.policy + H * R, *w2 = b1 + H, *b2 = w2 + A * H;
+    // the per-sample mathematics of one chunk
+    const auto chunk_sums = [&](const long first, const int n, float *col)
     {
-        const long   base = static_cast<long>(k) * B;
-        const int    Bk = static_cast<int>(std::min<long>(B, M - base)), C = (Bk + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
-        const float *b1 = st.policy + H * R, *w2 = b1 + H, *b2 = w2 + A * H;
-        for (int chunk = 0; chunk < C; ++chunk)
+        for (int q = 0; q < n; ++q)
         {
-            const int n   = std::min(OK_LEARN_CHUNK, Bk - chunk * OK_LEARN_CHUNK);
-            float    *col = part.data() + static_cast<size_t>(chunk) * cols;
-            for (int q = 0; q < n; ++q)
+            const long pos = first + q;
+            const int  idx = ok_learn_clamp_index(order != nullptr ? static_cast<long long>(order[pos]) : static_cast<long long>(pos), M);
+            float     *x   = xs.data() + static_cast<size_t>(q) * R;
+            for (int i = 0; i < R; ++i)
+                x[i] = in.state[static_cast<size_t>(idx) * R + i];
+            if (m.p > 0.F)
             {
-                const long pos = base + chunk * OK_LEARN_CHUNK + q;
-                const int  idx = ok_learn_clamp_index(order != nullptr ? static_cast<long long>(order[pos]) : static_cast<long long>(pos), M);
-                float     *x   = xs.data() + static_cast<size_t>(q) * R;
-                for (int i = 0; i < R; ++i)
-                    x[i] = in.state[static_cast<size_t>(idx) * R + i];
-                if (m.p > 0.F)
-                {
-                    const int32_t  raw  = in.index[idx];
-                    const uint32_t flat = raw < 0 ? 0U : static_cast<uint32_t>(raw);
-                    m.agent             = agent_base + flat % static_cast<uint32_t>(cfg.num_agents);
-                    m.draw              = cfg.draw_first + flat / static_cast<uint32_t>(cfg.num_agents);
-                }
-                float part_l[OK_ACTOR_LANES][OK_ACTOR_MAX_ACTIONS], colv[OK_ACTOR_LANES], z[OK_ACTOR_MAX_ACTIONS], dz[OK_ACTOR_MAX_ACTIONS];
+                const int32_t  raw  = in.index[idx];
+                const uint32_t flat = raw < 0 ? 0U : static_cast<uint32_t>(raw);
+                m.agent             = agent_base + flat % static_cast<uint32_t>(cfg.num_agents);
+                m.draw              = cfg.draw_first + flat / static_cast<uint32_t>(cfg.num_agents);
+            }
+            float part_l[OK_ACTOR_LANES][OK_ACTOR_MAX_ACTIONS], colv[OK_ACTOR_LANES], z[OK_ACTOR_MAX_ACTIONS], dz[OK_ACTOR_MAX_ACTIONS];
+            for (int l = 0; l < OK_ACTOR_LANES; ++l)
+                ok_reinforce_partial(st.policy, R, b1, w2, R, H, A, x, l, m, part_l[l]);
+            for (int a = 0; a < OK_ACTOR_MAX_ACTIONS; ++a)
+            {
                 for (int l = 0; l < OK_ACTOR_LANES; ++l)
-                    ok_reinforce_partial(st.policy, R, b1, w2, R, H, A, x, l, m, part_l[l]);
-                for (int a = 0; a < OK_ACTOR_MAX_ACTIONS; ++a)
-                {
-                    for (int l = 0; l < OK_ACTOR_LANES; ++l)
-                        colv[l] = a < A ? part_l[l][a] : 0.F;
-                    z[a] = a < A ? ok_actor_join(colv, b2[a]) : 0.F;
-                }
-                const int action = ok_learn_clamp_index(static_cast<long long>(in.action[idx]), A);
-                ok_reinforce_seed(z, A, action, in.ret[idx], dz, &terms[static_cast<size_t>(q)]);
-                float *h_row = rows.h.data() + static_cast<size_t>(q) * H, *ds_row = rows.ds.data() + static_cast<size_t>(q) * H;
-                for (int j = 0; j < H; ++j)
-                {
-                    const int   kept = ok_reinforce_kept(m, j);
-                    const float pre  = ok_learn_pre(st.policy, R, b1, R, x, j);
-                    h_row[j]         = ok_reinforce_hidden(pre, kept, m.s);
-                    ds_row[j]        = ok_reinforce_back_hidden(w2, H, A, dz, j, pre, kept, m.s);
-                }
-                for (int a = 0; a < OK_ACTOR_MAX_ACTIONS; ++a)
-                    rows.dz[static_cast<size_t>(q) * OK_ACTOR_MAX_ACTIONS + a] = dz[a];
+                    colv[l] = a < A ? part_l[l][a] : 0.F;
+                z[a] = a < A ? ok_actor_join(colv, b2[a]) : 0.F;
             }
-            okLearnHostChunkSums(Pp, R, H, A, xs.data(), rows, n, col);
-            col[Pp] = okLearnHostSumTerms(terms.data(), n);
-        }
-        const bool step = cfg.accumulate == 0 || k + 1 == slices;
-        ok_learn_adam_consts adam{};
-        if (step)
-        {
-            st.t += 1;
-            adam = okLearnAdamConsts(lp, st.t);
-        }
-        const float count = static_cast<float>(cfg.accumulate != 0 ? M : Bk);
-        for (int column = 0; column < cols; ++column)
-        {
-            const float sum = ok_learn_tree(part.data() + column, cols, static_cast<uint32_t>(C));
-            if (!step)
+            const int action = ok_learn_clamp_index(static_cast<long long>(in.action[idx]), A);
+            ok_reinforce_seed(z, A, action, in.ret[idx], dz, &terms[static_cast<size_t>(q)]);
+            float *h_row = rows.h.data() + static_cast<size_t>(q) * H, *ds_row = rows.ds.data() + static_cast<size_t>(q) * H;
+            for (int j = 0; j < H; ++j)
             {
-                acc[static_cast<size_t>(column)] = acc[static_cast<size_t>(column)] + sum;
-                continue;
+                const int   kept = ok_reinforce_kept(m, j);
+                const float pre  = ok_learn_pre(st.policy, R, b1, R, x, j);
+                h_row[j]         = ok_reinforce_hidden(pre, kept, m.s);
+                ds_row[j]        = ok_reinforce_back_hidden(w2, H, A, dz, j, pre, kept, m.s);
             }
-            const float total = cfg.accumulate != 0 ? acc[static_cast<size_t>(column)] + sum : sum;
-            const float g     = ok_reinforce_reduce(total, cfg.reduce, count);
-            if (column < Pp)
-                okLearnStepParam(st.policy, st.policy_m, st.policy_v, out.grad_policy, column, g, adam);
-            else if (out.loss != nullptr)
-                out.loss[slot] = g;
+            for (int a = 0; a < OK_ACTOR_MAX_ACTIONS; ++a)
+                rows.dz[static_cast<size_t>(q) * OK_ACTOR_MAX_ACTIONS + a] = dz[a];
         }
-        if (step)
-            ++slot;
-    }
+        okLearnHostChunkSums(Pp, R, H, A, xs.data(), rows, n, col);
+        col[Pp] = okLearnHostSumTerms(terms.data(), n);
+    };
+    okSliceUpdateHost(lp, cfg.accumulate != 0, okJoinOn(Pp, st.policy, st.policy_m, st.policy_v, cfg.reduce, out.grad_policy), st.t, M, B, out.loss, chunk_sums);
 }
 
 #endif // OK_REINFORCE_H

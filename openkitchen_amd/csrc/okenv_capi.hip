@@ -389,6 +389,14 @@ struct OkEventLog
     size_t                  want{0}, at{0}, timed{0}; // events of the call under way, the last one recorded, events of the latest complete timed call
 };
 
+// The device scratch of an update or a batch (grown, never shrunk: growScratch) and the events of its latest timed call
+struct OkUpdateScratch
+{
+    uint8_t   *part{nullptr};
+    size_t     bytes{0};
+    OkEventLog log;
+};
+
 struct okenv
 {
     int         device{0};
@@ -500,10 +508,8 @@ struct okenv
     const uint32_t    *actor_draw_offset{nullptr};
     // episode -> batch (okenv_batch_prepare): scratch for the planes, column partials, group counts, statistics and M; grown, never
     // shrunk; the events of the latest timed call
-    uint8_t   *d_batch{nullptr};
-    size_t     batch_bytes{0};
-    int32_t   *d_batch_count{nullptr};
-    OkEventLog batch_log;
+    OkUpdateScratch batch_scratch;
+    int32_t        *d_batch_count{nullptr};
     // PPO's update (okenv_learner_create): Adam's moments beside the actor's parameters, the step number, the chunk partials (grown,
     // never shrunk) and the events of the latest timed okenv_ppo_update
     bool                    learner_ok{false};
@@ -511,18 +517,14 @@ struct okenv
     int64_t                 learn_t{0};
     float                  *d_learn_moments{nullptr}; // [4][cap]: policy m, policy v, value m, value v
     size_t                  learn_cap{0};
-    uint8_t                *d_learn_part{nullptr};
-    size_t                  learn_part_bytes{0};
-    OkEventLog              learn_log;
+    OkUpdateScratch         learn_scratch;
     // Deep-Q (okenv_replay_create, okenv_dqn_params): the ring, the update's constants, the target network's copy, the chunk partials
     // (grown, never shrunk) and the events of the latest timed update
     OkRing                  replay{sizeof(int64_t)};
     okenv_dqn_config        dqn{0.99F, 0U, 0, 0U};
     float                  *d_dqn_target{nullptr};
     bool                    dqn_target_set{false};
-    uint8_t                *d_dqn_part{nullptr};
-    size_t                  dqn_part_bytes{0};
-    OkEventLog              dqn_log;
+    OkUpdateScratch         dqn_scratch;
     // DDPG (okenv_ddpg_create, okenv_ddpg_replay_create): the four networks [actor | critic | actor target | critic target] and the four
     // moments [actor m | actor v | critic m | critic v], each ddpg_cap floats; the ring, the
     // update's chunk partials (grown, never shrunk) and timing events.  Nothing here is shared with the actor, the learner or the
@@ -534,16 +536,12 @@ struct okenv
     int64_t                 ddpg_t{0};
     const uint32_t         *ddpg_draw_offset{nullptr};
     OkRing                  ddpg_ring{2U * sizeof(float)};
-    uint8_t                *d_ddpg_part{nullptr};
-    size_t                  ddpg_part_bytes{0};
-    OkEventLog              ddpg_log;
+    OkUpdateScratch         ddpg_scratch;
     // REINFORCE (okenv_actor_set_dropout, okenv_reinforce_update): the policy network's dropout, the update's scratch
     // [chunk partials | accumulator] (grown, never shrunk) and timing events.  The learner is the one above.
     float                   actor_dropout{0.F};
     uint32_t                actor_dropout_seed{0};
-    uint8_t                *d_reinforce_part{nullptr};
-    size_t                  reinforce_part_bytes{0};
-    OkEventLog              reinforce_log;
+    OkUpdateScratch         reinforce_scratch;
     // Continuous REINFORCE (okenv_gauss_create, okenv_gauss_learner_create): the parameter vector and Adam's two moments
     // [params | m | v], each gauss_cap floats, the update's scratch [chunk partials | accumulator] (grown, never shrunk) and timing
     // events.  Nothing here is shared with the actor, the learner or the DDPG object above.
@@ -554,9 +552,7 @@ struct okenv
     float                  *d_gauss{nullptr};
     int64_t                 gauss_t{0};
     const uint32_t         *gauss_draw_offset{nullptr};
-    uint8_t                *d_gauss_part{nullptr};
-    size_t                  gauss_part_bytes{0};
-    OkEventLog              gauss_log;
+    OkUpdateScratch         gauss_scratch;
 };
 
 struct okenv_track
@@ -1182,24 +1178,24 @@ int copyAny(okenv *h, void *dst, const void *src, const size_t bytes)
 
 // A scratch buffer of the handle that grows to 1.5 x what a call needs and never shrinks (the updates' chunk partials, the batch's
 // planes): the old one is freed behind a wait for the stream, since an earlier call may still be working in it.
-int growScratch(okenv *h, uint8_t **ptr, size_t *have, const size_t bytes)
+int growScratch(okenv *h, OkUpdateScratch &u, const size_t bytes)
 {
-    if (bytes <= *have)
+    if (bytes <= u.bytes)
         return OKENV_OK;
     OK_HIP(h, hipStreamSynchronize(h->stream));
-    if (*ptr != nullptr)
+    if (u.part != nullptr)
     {
-        h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(*ptr)), h->allocations.end());
-        (void)hipFree(*ptr);
-        *ptr  = nullptr;
-        *have = 0;
+        h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(u.part)), h->allocations.end());
+        (void)hipFree(u.part);
+        u.part  = nullptr;
+        u.bytes = 0;
     }
     uint8_t  *fresh = nullptr;
     const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
     if (rc != OKENV_OK)
         return rc;
-    *ptr  = fresh;
-    *have = bytes + bytes / 2U;
+    u.part  = fresh;
+    u.bytes = bytes + bytes / 2U;
     return OKENV_OK;
 }
 
@@ -1244,6 +1240,93 @@ int eventsSums(okenv *h, OkEventLog &log, double *out, const size_t period)
         float ms = 0.F;
         OK_HIP(h, hipEventElapsedTime(&ms, log.events[k], log.events[k + 1U]));
         out[k % period] += ms;
+    }
+    return OKENV_OK;
+}
+
+// The okenv_debug_*_timing entries, behind the exported functions' OK_QUIESCE: out[period] of the latest timed call of `update`
+int updateTiming(okenv *h, OkUpdateScratch okenv::*scratch, const char *entry, const char *update, double *out, const size_t period)
+{
+    if (!h || !out)
+        return fail(h, OKENV_ERR_INVALID, std::string(entry) + ": NULL argument");
+    if ((h->*scratch).log.timed < period + 1U)
+        return fail(h, OKENV_ERR_STATE, std::string(entry) + ": no " + update + " has run with okenv_set_timing on");
+    return eventsSums(h, (h->*scratch).log, out, period);
+}
+
+// ---- the act kernels' frame and the whole-episode updates' loop, behind the exported functions' OK_QUIESCE ------------------------------------
+
+// What okenv_actor_act, okenv_ddpg_act and okenv_gauss_act hand their kernels alike (ok_actor.h); draw_offset: the learner's own word
+OkActFrame actFrame(const okenv *h)
+{
+    OkActFrame f{};
+    f.st = h->st;
+    f.N  = h->shape.N;
+    f.R  = h->shape.R;
+    return f;
+}
+
+OkActDrawWords actDrawWords(const okenv *h, const uint32_t *draw_offset)
+{
+    OkActDrawWords w{};
+    w.step_word   = (h->reset_flags & kAutoResetOn) != 0U ? h->d_step_count : nullptr; // (the step kernels advance it only then)
+    w.host_steps  = h->step_count;
+    w.draw_offset = draw_offset;
+    return w;
+}
+
+// okenv_reinforce_update's and okenv_gauss_update's slices: two launches each, the learner's gradient kernel and the join kernel
+// (ok_reinforce.h).  j is okJoinOn's (the parameter vector, its moments, reduce and the gradient's output); t is the learner's step number,
+// lp its Adam; loss takes one value per step, or is nullptr.  launch_grad(base, Bk, C) enqueues the gradient kernel of the slice of Bk
+// positions from `base` on, C workgroups writing to u.part.
+template <class LaunchGrad>
+int sliceUpdate(okenv *h, OkUpdateScratch &u, const int32_t M, const int32_t B, const bool accumulate, OkJoinParams j, int64_t &t,
+                const okenv_learner_params &lp, float *loss, const LaunchGrad &launch_grad)
+{
+    // the scratch: [chunk partials | accumulator], each piece 256-aligned
+    const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
+    const size_t c_max = (static_cast<size_t>(std::min(B, M)) + OK_LEARN_CHUNK - 1U) / OK_LEARN_CHUNK;
+    const size_t parts = up(sizeof(float) * c_max * static_cast<size_t>(j.cols)), acc_bytes = sizeof(float) * static_cast<size_t>(j.cols);
+    if (const int rc = growScratch(h, u, parts + up(acc_bytes)))
+        return rc;
+    j.part = reinterpret_cast<float *>(u.part);
+    if (accumulate)
+    {
+        j.acc = reinterpret_cast<float *>(u.part + parts);
+        OK_HIP(h, hipMemsetAsync(j.acc, 0, acc_bytes, h->stream));
+    }
+    const int slices = okLearnMinibatches(M, B);
+    if (const int rc = eventsBegin(h, u.log, 2U * static_cast<size_t>(slices)))
+        return rc;
+    const unsigned step_grid = static_cast<unsigned>((j.cols + kLearnStepCols - 1) / kLearnStepCols);
+    int            slot      = 0;
+    for (int k = 0; k < slices; ++k)
+    {
+        const long base = static_cast<long>(k) * B;
+        const int  Bk   = static_cast<int>(std::min<long>(B, M - base));
+        j.C             = (Bk + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+        launch_grad(base, Bk, j.C);
+        OK_HIP(h, hipGetLastError());
+        if (const int rc = eventsMark(h, u.log))
+            return rc;
+        if (accumulate && k + 1 < slices)
+        {
+            hipLaunchKernelGGL(okReinforceStepKernel<false>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, j);
+            OK_HIP(h, hipGetLastError());
+        }
+        else
+        {
+            j.count = static_cast<float>(accumulate ? M : Bk);
+            j.adam  = okLearnAdamConsts(lp, t + 1);
+            j.loss  = loss != nullptr ? loss + slot : nullptr;
+            hipLaunchKernelGGL(okReinforceStepKernel<true>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, j);
+            OK_HIP(h, hipGetLastError());
+            // (the step number advances once the step's kernels are enqueued, as in okenv_ppo_update)
+            t += 1;
+            ++slot;
+        }
+        if (const int rc = eventsMark(h, u.log))
+            return rc;
     }
     return OKENV_OK;
 }
@@ -1718,8 +1801,8 @@ extern "C"
             (void)hipEventDestroy(e.start);
             (void)hipEventDestroy(e.stop);
         }
-        for (OkEventLog *log : {&h->batch_log, &h->learn_log, &h->dqn_log, &h->ddpg_log, &h->reinforce_log, &h->gauss_log})
-            for (hipEvent_t e : log->events)
+        for (OkUpdateScratch *u : {&h->batch_scratch, &h->learn_scratch, &h->dqn_scratch, &h->ddpg_scratch, &h->reinforce_scratch, &h->gauss_scratch})
+            for (hipEvent_t e : u->log.events)
                 (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
             (void)hipStreamDestroy(h->stream);
@@ -2691,15 +2774,11 @@ extern "C"
         dropEpisode(h);
         OK_HIP(h, hipSetDevice(h->device));
         OkActorParams p{};
-        p.st          = h->st;
-        p.N           = h->shape.N;
-        p.R           = h->shape.R;
-        p.policy      = h->d_actor_policy;
-        p.value       = h->d_actor_value;
-        p.step_word   = (h->reset_flags & kAutoResetOn) != 0U ? h->d_step_count : nullptr; // (the step kernels advance it only then)
-        p.host_steps  = h->step_count;
-        p.draw_offset = h->actor_draw_offset;
-        p.ap          = h->actor;
+        p.f      = actFrame(h);
+        p.draw   = actDrawWords(h, h->actor_draw_offset);
+        p.policy = h->d_actor_policy;
+        p.value  = h->d_actor_value;
+        p.ap     = h->actor;
         if (rec != nullptr)
             p.rec = *rec;
         const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
@@ -2756,9 +2835,9 @@ extern "C"
         const size_t parts = up(4U * sizeof(double) * static_cast<size_t>(p.N)), part_m = up(sizeof(uint32_t) * static_cast<size_t>(p.N));
         const size_t group = up(sizeof(uint32_t) * static_cast<size_t>(p.groups));
         const size_t bytes = 2U * plane + parts + part_m + group + 256U + 256U;
-        if (const int rc = growScratch(h, &h->d_batch, &h->batch_bytes, bytes))
+        if (const int rc = growScratch(h, h->batch_scratch, bytes))
             return rc;
-        uint8_t *at = h->d_batch;
+        uint8_t *at = h->batch_scratch.part;
         p.g_plane   = out->ret_plane != nullptr ? out->ret_plane : reinterpret_cast<float *>(at);
         p.a_plane   = out->adv_plane != nullptr ? out->adv_plane : reinterpret_cast<float *>(at + plane);
         at += 2U * plane;
@@ -2774,25 +2853,25 @@ extern "C"
         h->d_batch_count = p.count;
         const unsigned bt   = static_cast<unsigned>(params->block_threads != 0 ? params->block_threads : kBatchWalkThreads);
         const unsigned wide = static_cast<unsigned>(p.groups);
-        if (const int rc = eventsBegin(h, h->batch_log, 5))
+        if (const int rc = eventsBegin(h, h->batch_scratch.log, 5))
             return rc;
         if (in->value != nullptr)
             hipLaunchKernelGGL(okBatchWalkKernel<true>, dim3((static_cast<unsigned>(p.N) + bt - 1U) / bt), dim3(bt), 0, h->stream, p);
         else
             hipLaunchKernelGGL(okBatchWalkKernel<false>, dim3((static_cast<unsigned>(p.N) + bt - 1U) / bt), dim3(bt), 0, h->stream, p);
-        if (const int rc = eventsMark(h, h->batch_log))
+        if (const int rc = eventsMark(h, h->batch_scratch.log))
             return rc;
         hipLaunchKernelGGL(okBatchTreeKernel, dim3(1), dim3(1024), 0, h->stream, p);
-        if (const int rc = eventsMark(h, h->batch_log))
+        if (const int rc = eventsMark(h, h->batch_scratch.log))
             return rc;
         hipLaunchKernelGGL(okBatchCountKernel, dim3(wide), dim3(kBatchWideThreads), 0, h->stream, p);
-        if (const int rc = eventsMark(h, h->batch_log))
+        if (const int rc = eventsMark(h, h->batch_scratch.log))
             return rc;
         hipLaunchKernelGGL(okBatchScanKernel, dim3(1), dim3(1024), 0, h->stream, p);
-        if (const int rc = eventsMark(h, h->batch_log))
+        if (const int rc = eventsMark(h, h->batch_scratch.log))
             return rc;
         hipLaunchKernelGGL(okBatchGatherKernel, dim3(wide), dim3(kBatchWideThreads), 0, h->stream, p);
-        if (const int rc = eventsMark(h, h->batch_log))
+        if (const int rc = eventsMark(h, h->batch_scratch.log))
             return rc;
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
@@ -2814,11 +2893,7 @@ extern "C"
     int okenv_debug_batch_timing(okenv_t h, double *ms5)
     {
         OK_QUIESCE(h);
-        if (!h || !ms5)
-            return fail(h, OKENV_ERR_INVALID, "okenv_debug_batch_timing: NULL argument");
-        if (h->batch_log.timed < 6U)
-            return fail(h, OKENV_ERR_STATE, "okenv_debug_batch_timing: no okenv_batch_prepare has run with okenv_set_timing on");
-        return eventsSums(h, h->batch_log, ms5, 5);
+        return updateTiming(h, &okenv::batch_scratch, "okenv_debug_batch_timing", "okenv_batch_prepare", ms5, 5);
     }
 
     int okenv_batch_prepare_host(const okenv_batch_params *params, const okenv_batch_input *in, const okenv_batch_output *out, int32_t *count)
@@ -2907,13 +2982,13 @@ extern "C"
         const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
         const size_t c_max = (static_cast<size_t>(std::min(B, M)) + OK_LEARN_CHUNK - 1U) / OK_LEARN_CHUNK;
         const size_t parts = up(sizeof(float) * c_max * static_cast<size_t>(p.cols)), bytes = parts + up(sizeof(uint32_t) * c_max);
-        if (const int rc = growScratch(h, &h->d_learn_part, &h->learn_part_bytes, bytes))
+        if (const int rc = growScratch(h, h->learn_scratch, bytes))
             return rc;
-        p.part      = reinterpret_cast<float *>(h->d_learn_part);
-        p.part_clip = reinterpret_cast<uint32_t *>(h->d_learn_part + parts);
+        p.part      = reinterpret_cast<float *>(h->learn_scratch.part);
+        p.part_clip = reinterpret_cast<uint32_t *>(h->learn_scratch.part + parts);
         const int    per_epoch = okLearnMinibatches(M, B);
         const size_t launches  = 2U * static_cast<size_t>(epochs) * static_cast<size_t>(per_epoch);
-        if (const int rc = eventsBegin(h, h->learn_log, launches))
+        if (const int rc = eventsBegin(h, h->learn_scratch.log, launches))
             return rc;
         const size_t lds = okLearnLdsBytes(p.R, p.H, p.A, p.Hv);
         for (int e = 0; e < epochs; ++e)
@@ -2932,13 +3007,13 @@ extern "C"
                 // is the number of steps the device's moments have taken, and the call reports the error.
                 hipLaunchKernelGGL(okLearnGradKernel, dim3(static_cast<unsigned>(p.C)), dim3(kLearnThreads), lds, h->stream, p);
                 OK_HIP(h, hipGetLastError());
-                if (const int rc = eventsMark(h, h->learn_log))
+                if (const int rc = eventsMark(h, h->learn_scratch.log))
                     return rc;
                 hipLaunchKernelGGL(okLearnStepKernel, dim3(static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols)),
                                    dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
                 OK_HIP(h, hipGetLastError());
                 h->learn_t += 1;
-                if (const int rc = eventsMark(h, h->learn_log))
+                if (const int rc = eventsMark(h, h->learn_scratch.log))
                     return rc;
             }
         return OKENV_OK;
@@ -2947,11 +3022,7 @@ extern "C"
     int okenv_debug_update_timing(okenv_t h, double *ms2)
     {
         OK_QUIESCE(h);
-        if (!h || !ms2)
-            return fail(h, OKENV_ERR_INVALID, "okenv_debug_update_timing: NULL argument");
-        if (h->learn_log.timed < 3U)
-            return fail(h, OKENV_ERR_STATE, "okenv_debug_update_timing: no okenv_ppo_update has run with okenv_set_timing on");
-        return eventsSums(h, h->learn_log, ms2, 2);
+        return updateTiming(h, &okenv::learn_scratch, "okenv_debug_update_timing", "okenv_ppo_update", ms2, 2);
     }
 
     int okenv_actor_get_params(okenv_t h, float *policy, float *value)
@@ -3071,70 +3142,24 @@ extern "C"
         p.N          = config->num_agents;
         p.order      = order;
         p.policy     = h->d_actor_policy;
-        p.pol_m      = h->d_learn_moments;
-        p.pol_v      = h->d_learn_moments + h->learn_cap;
-        p.reduce     = config->reduce;
         const okenv_reinforce_output none{};
         const okenv_reinforce_output &o = out != nullptr ? *out : none;
-        p.grad_policy = o.grad_policy;
-        // the scratch: [chunk partials | accumulator], each piece 256-aligned
-        const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
-        const size_t c_max = (static_cast<size_t>(std::min(B, M)) + OK_LEARN_CHUNK - 1U) / OK_LEARN_CHUNK;
-        const size_t parts = up(sizeof(float) * c_max * static_cast<size_t>(p.cols)), acc_bytes = sizeof(float) * static_cast<size_t>(p.cols);
-        if (const int rc = growScratch(h, &h->d_reinforce_part, &h->reinforce_part_bytes, parts + up(acc_bytes)))
-            return rc;
-        p.part = reinterpret_cast<float *>(h->d_reinforce_part);
-        const bool accumulate = config->accumulate != 0;
-        if (accumulate)
-        {
-            p.acc = reinterpret_cast<float *>(h->d_reinforce_part + parts);
-            OK_HIP(h, hipMemsetAsync(p.acc, 0, acc_bytes, h->stream));
-        }
-        const int slices = okLearnMinibatches(M, B);
-        if (const int rc = eventsBegin(h, h->reinforce_log, 2U * static_cast<size_t>(slices)))
-            return rc;
-        const size_t   lds       = okReinforceLdsBytes(p.R, p.H, p.A);
-        const unsigned step_grid = static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols);
-        int            slot      = 0;
-        for (int k = 0; k < slices; ++k)
-        {
-            p.base = static_cast<long>(k) * B;
-            p.Bk   = static_cast<int>(std::min<long>(B, M - p.base));
-            p.C    = (p.Bk + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
-            hipLaunchKernelGGL(okReinforceGradKernel, dim3(static_cast<unsigned>(p.C)), dim3(kLearnThreads), lds, h->stream, p);
-            OK_HIP(h, hipGetLastError());
-            if (const int rc = eventsMark(h, h->reinforce_log))
-                return rc;
-            if (accumulate && k + 1 < slices)
-            {
-                hipLaunchKernelGGL(okReinforceStepKernel<false>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
-                OK_HIP(h, hipGetLastError());
-            }
-            else
-            {
-                p.count = static_cast<float>(accumulate ? M : p.Bk);
-                p.adam  = okLearnAdamConsts(h->learner, h->learn_t + 1);
-                p.loss  = o.loss != nullptr ? o.loss + slot : nullptr;
-                hipLaunchKernelGGL(okReinforceStepKernel<true>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
-                OK_HIP(h, hipGetLastError());
-                // (the step number advances once the step's kernels are enqueued, as in okenv_ppo_update)
-                h->learn_t += 1;
-                ++slot;
-            }
-            if (const int rc = eventsMark(h, h->reinforce_log))
-                return rc;
-        }
-        return OKENV_OK;
+        const OkJoinParams j   = okJoinOn(p.Pp, h->d_actor_policy, h->d_learn_moments, h->d_learn_moments + h->learn_cap, config->reduce, o.grad_policy);
+        const size_t       lds = okReinforceLdsBytes(p.R, p.H, p.A);
+        return sliceUpdate(h, h->reinforce_scratch, M, B, config->accumulate != 0, j, h->learn_t, h->learner, o.loss,
+                           [&](const long base, const int Bk, const int C)
+                           {
+                               p.base = base;
+                               p.Bk   = Bk;
+                               p.part = reinterpret_cast<float *>(h->reinforce_scratch.part);
+                               hipLaunchKernelGGL(okReinforceGradKernel, dim3(static_cast<unsigned>(C)), dim3(kLearnThreads), lds, h->stream, p);
+                           });
     }
 
     int okenv_debug_reinforce_timing(okenv_t h, double *ms2)
     {
         OK_QUIESCE(h);
-        if (!h || !ms2)
-            return fail(h, OKENV_ERR_INVALID, "okenv_debug_reinforce_timing: NULL argument");
-        if (h->reinforce_log.timed < 3U)
-            return fail(h, OKENV_ERR_STATE, "okenv_debug_reinforce_timing: no okenv_reinforce_update has run with okenv_set_timing on");
-        return eventsSums(h, h->reinforce_log, ms2, 2);
+        return updateTiming(h, &okenv::reinforce_scratch, "okenv_debug_reinforce_timing", "okenv_reinforce_update", ms2, 2);
     }
 
     int okenv_reinforce_update_host(const okenv_learner_params *params, const okenv_reinforce_config *config, float p, uint32_t dropout_seed,
@@ -3292,11 +3317,11 @@ extern "C"
         p.grad_policy = o.grad_policy;
         p.index       = o.index;
         const size_t bytes = sizeof(float) * static_cast<size_t>(p.C) * static_cast<size_t>(p.cols);
-        if (const int rc = growScratch(h, &h->d_dqn_part, &h->dqn_part_bytes, bytes))
+        if (const int rc = growScratch(h, h->dqn_scratch, bytes))
             return rc;
-        p.part = reinterpret_cast<float *>(h->d_dqn_part);
+        p.part = reinterpret_cast<float *>(h->dqn_scratch.part);
         const size_t launches = 2U * static_cast<size_t>(iterations);
-        if (const int rc = eventsBegin(h, h->dqn_log, launches))
+        if (const int rc = eventsBegin(h, h->dqn_scratch.log, launches))
             return rc;
         const size_t lds = okDqnLdsBytes(p.R, p.H, p.A);
         for (int it = 0; it < iterations; ++it)
@@ -3307,13 +3332,13 @@ extern "C"
             // (the step number advances once both kernels of the iteration are enqueued, as in okenv_ppo_update)
             hipLaunchKernelGGL(okDqnGradKernel, dim3(static_cast<unsigned>(p.C)), dim3(kLearnThreads), lds, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            if (const int rc = eventsMark(h, h->dqn_log))
+            if (const int rc = eventsMark(h, h->dqn_scratch.log))
                 return rc;
             hipLaunchKernelGGL(okDqnStepKernel, dim3(static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols)),
                                dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, p);
             OK_HIP(h, hipGetLastError());
             h->learn_t += 1;
-            if (const int rc = eventsMark(h, h->dqn_log))
+            if (const int rc = eventsMark(h, h->dqn_scratch.log))
                 return rc;
         }
         return OKENV_OK;
@@ -3322,11 +3347,7 @@ extern "C"
     int okenv_debug_dqn_timing(okenv_t h, double *ms2)
     {
         OK_QUIESCE(h);
-        if (!h || !ms2)
-            return fail(h, OKENV_ERR_INVALID, "okenv_debug_dqn_timing: NULL argument");
-        if (h->dqn_log.timed < 3U)
-            return fail(h, OKENV_ERR_STATE, "okenv_debug_dqn_timing: no okenv_dqn_update has run with okenv_set_timing on");
-        return eventsSums(h, h->dqn_log, ms2, 2);
+        return updateTiming(h, &okenv::dqn_scratch, "okenv_debug_dqn_timing", "okenv_dqn_update", ms2, 2);
     }
 
     int okenv_replay_push_host(const okenv_replay_ring *ring, int32_t capacity, int32_t num_rays, uint64_t *pushed, uint32_t flags, int32_t n,
@@ -3488,15 +3509,11 @@ extern "C"
         dropEpisode(h);
         OK_HIP(h, hipSetDevice(h->device));
         OkGaussActParams p{};
-        p.st          = h->st;
-        p.N           = h->shape.N;
-        p.R           = h->shape.R;
-        p.H1          = h->gauss.hidden1;
-        p.H2          = h->gauss.hidden2;
-        p.params      = h->d_gauss;
-        p.step_word   = (h->reset_flags & kAutoResetOn) != 0U ? h->d_step_count : nullptr; // (the step kernels advance it only then)
-        p.host_steps  = h->step_count;
-        p.draw_offset = h->gauss_draw_offset;
+        p.f      = actFrame(h);
+        p.draw   = actDrawWords(h, h->gauss_draw_offset);
+        p.H1     = h->gauss.hidden1;
+        p.H2     = h->gauss.hidden2;
+        p.params = h->d_gauss;
         for (int k = 0; k < 2; ++k)
         {
             p.scale[k] = h->gauss.scale[k];
@@ -3508,7 +3525,7 @@ extern "C"
         if (rec != nullptr)
             p.rec = *rec;
         const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
-        hipLaunchKernelGGL(okGaussActKernel, dim3(blocks), dim3(kActorThreads), okGaussActLdsBytes(p.R, p.H1, p.H2), h->stream, p);
+        hipLaunchKernelGGL(okGaussActKernel, dim3(blocks), dim3(kActorThreads), okGaussActLdsBytes(p.f.R, p.H1, p.H2), h->stream, p);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -3554,73 +3571,24 @@ extern "C"
         p.order  = order;
         p.params = h->d_gauss;
         // the join kernels are section 19's, on this parameter vector
-        OkReinforceParams s{};
-        s.Pp     = p.P;
-        s.cols   = p.cols;
-        s.policy = h->d_gauss;
-        s.pol_m  = h->d_gauss + h->gauss_cap;
-        s.pol_v  = h->d_gauss + 2U * h->gauss_cap;
-        s.reduce = config->reduce;
         const okenv_gauss_output none{};
         const okenv_gauss_output &o = out != nullptr ? *out : none;
-        s.grad_policy = o.grad;
-        // the scratch: [chunk partials | accumulator], each piece 256-aligned
-        const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
-        const size_t c_max = (static_cast<size_t>(std::min(B, M)) + OK_LEARN_CHUNK - 1U) / OK_LEARN_CHUNK;
-        const size_t parts = up(sizeof(float) * c_max * static_cast<size_t>(p.cols)), acc_bytes = sizeof(float) * static_cast<size_t>(p.cols);
-        if (const int rc = growScratch(h, &h->d_gauss_part, &h->gauss_part_bytes, parts + up(acc_bytes)))
-            return rc;
-        p.part = s.part = reinterpret_cast<float *>(h->d_gauss_part);
-        const bool accumulate = config->accumulate != 0;
-        if (accumulate)
-        {
-            s.acc = reinterpret_cast<float *>(h->d_gauss_part + parts);
-            OK_HIP(h, hipMemsetAsync(s.acc, 0, acc_bytes, h->stream));
-        }
-        const int slices = okLearnMinibatches(M, B);
-        if (const int rc = eventsBegin(h, h->gauss_log, 2U * static_cast<size_t>(slices)))
-            return rc;
-        const size_t   lds       = okGaussLdsBytes(p.R, p.H1, p.H2, p.A);
-        const unsigned step_grid = static_cast<unsigned>((p.cols + kLearnStepCols - 1) / kLearnStepCols);
-        int            slot      = 0;
-        for (int k = 0; k < slices; ++k)
-        {
-            p.base = static_cast<long>(k) * B;
-            p.Bk   = static_cast<int>(std::min<long>(B, M - p.base));
-            s.C    = (p.Bk + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
-            hipLaunchKernelGGL(okGaussGradKernel, dim3(static_cast<unsigned>(s.C)), dim3(kLearnThreads), lds, h->stream, p);
-            OK_HIP(h, hipGetLastError());
-            if (const int rc = eventsMark(h, h->gauss_log))
-                return rc;
-            if (accumulate && k + 1 < slices)
-            {
-                hipLaunchKernelGGL(okReinforceStepKernel<false>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, s);
-                OK_HIP(h, hipGetLastError());
-            }
-            else
-            {
-                s.count = static_cast<float>(accumulate ? M : p.Bk);
-                s.adam  = okLearnAdamConsts(h->gauss_learner, h->gauss_t + 1);
-                s.loss  = o.loss != nullptr ? o.loss + slot : nullptr;
-                hipLaunchKernelGGL(okReinforceStepKernel<true>, dim3(step_grid), dim3(kLearnStepCols * kLearnStepRows), 0, h->stream, s);
-                OK_HIP(h, hipGetLastError());
-                h->gauss_t += 1;
-                ++slot;
-            }
-            if (const int rc = eventsMark(h, h->gauss_log))
-                return rc;
-        }
-        return OKENV_OK;
+        const OkJoinParams j   = okJoinOn(p.P, h->d_gauss, h->d_gauss + h->gauss_cap, h->d_gauss + 2U * h->gauss_cap, config->reduce, o.grad);
+        const size_t       lds = okGaussLdsBytes(p.R, p.H1, p.H2, p.A);
+        return sliceUpdate(h, h->gauss_scratch, M, B, config->accumulate != 0, j, h->gauss_t, h->gauss_learner, o.loss,
+                           [&](const long base, const int Bk, const int C)
+                           {
+                               p.base = base;
+                               p.Bk   = Bk;
+                               p.part = reinterpret_cast<float *>(h->gauss_scratch.part);
+                               hipLaunchKernelGGL(okGaussGradKernel, dim3(static_cast<unsigned>(C)), dim3(kLearnThreads), lds, h->stream, p);
+                           });
     }
 
     int okenv_debug_gauss_timing(okenv_t h, double *ms2)
     {
         OK_QUIESCE(h);
-        if (!h || !ms2)
-            return fail(h, OKENV_ERR_INVALID, "okenv_debug_gauss_timing: NULL argument");
-        if (h->gauss_log.timed < 3U)
-            return fail(h, OKENV_ERR_STATE, "okenv_debug_gauss_timing: no okenv_gauss_update has run with okenv_set_timing on");
-        return eventsSums(h, h->gauss_log, ms2, 2);
+        return updateTiming(h, &okenv::gauss_scratch, "okenv_debug_gauss_timing", "okenv_gauss_update", ms2, 2);
     }
 
     int okenv_gauss_act_host(const okenv_gauss_config *config, const float *params, int32_t num_rays, int32_t n, const float *dist, const uint8_t *crashed,
@@ -3794,14 +3762,10 @@ extern "C"
         dropEpisode(h);
         OK_HIP(h, hipSetDevice(h->device));
         OkDdpgActParams p{};
-        p.st          = h->st;
-        p.N           = h->shape.N;
-        p.R           = h->shape.R;
-        p.H           = h->ddpg.hidden;
-        p.actor       = h->d_ddpg_nets;
-        p.step_word   = (h->reset_flags & kAutoResetOn) != 0U ? h->d_step_count : nullptr; // (the step kernels advance it only then)
-        p.host_steps  = h->step_count;
-        p.draw_offset = h->ddpg_draw_offset;
+        p.f     = actFrame(h);
+        p.draw  = actDrawWords(h, h->ddpg_draw_offset);
+        p.H     = h->ddpg.hidden;
+        p.actor = h->d_ddpg_nets;
         for (int k = 0; k < 2; ++k)
         {
             p.scale[k] = h->ddpg.scale[k];
@@ -3813,7 +3777,7 @@ extern "C"
         if (rec != nullptr)
             p.rec = *rec;
         const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
-        hipLaunchKernelGGL(okDdpgActKernel, dim3(blocks), dim3(kActorThreads), okDdpgActLdsBytes(p.R, p.H), h->stream, p);
+        hipLaunchKernelGGL(okDdpgActKernel, dim3(blocks), dim3(kActorThreads), okDdpgActLdsBytes(p.f.R, p.H), h->stream, p);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -3896,11 +3860,11 @@ extern "C"
         p.grad_actor  = o.grad_actor;
         p.index       = o.index;
         const size_t bytes = sizeof(float) * static_cast<size_t>(p.C) * (static_cast<size_t>(std::max(p.Pa, p.Pc)) + 1U);
-        if (const int rc = growScratch(h, &h->d_ddpg_part, &h->ddpg_part_bytes, bytes))
+        if (const int rc = growScratch(h, h->ddpg_scratch, bytes))
             return rc;
-        p.part = reinterpret_cast<float *>(h->d_ddpg_part);
+        p.part = reinterpret_cast<float *>(h->ddpg_scratch.part);
         const size_t launches = 4U * static_cast<size_t>(iterations);
-        if (const int rc = eventsBegin(h, h->ddpg_log, launches))
+        if (const int rc = eventsBegin(h, h->ddpg_scratch.log, launches))
             return rc;
         const size_t   lds = okDdpgLdsBytes(p.R, p.H, p.Hc);
         const unsigned chunks = static_cast<unsigned>(p.C), step_threads = kLearnStepCols * kLearnStepRows;
@@ -3915,19 +3879,19 @@ extern "C"
             // (the step number advances once all four kernels of the iteration are enqueued, as in okenv_ppo_update)
             hipLaunchKernelGGL(okDdpgCriticGradKernel, dim3(chunks), dim3(kLearnThreads), lds, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            if (const int rc = eventsMark(h, h->ddpg_log))
+            if (const int rc = eventsMark(h, h->ddpg_scratch.log))
                 return rc;
             hipLaunchKernelGGL(okDdpgStepKernel<false>, dim3(cols_c), dim3(step_threads), 0, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            if (const int rc = eventsMark(h, h->ddpg_log))
+            if (const int rc = eventsMark(h, h->ddpg_scratch.log))
                 return rc;
             hipLaunchKernelGGL(okDdpgActorGradKernel, dim3(chunks), dim3(kLearnThreads), lds, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            if (const int rc = eventsMark(h, h->ddpg_log))
+            if (const int rc = eventsMark(h, h->ddpg_scratch.log))
                 return rc;
             hipLaunchKernelGGL(okDdpgStepKernel<true>, dim3(cols_a), dim3(step_threads), 0, h->stream, p);
             OK_HIP(h, hipGetLastError());
-            if (const int rc = eventsMark(h, h->ddpg_log))
+            if (const int rc = eventsMark(h, h->ddpg_scratch.log))
                 return rc;
             h->ddpg_t += 1;
         }
@@ -3937,11 +3901,7 @@ extern "C"
     int okenv_debug_ddpg_timing(okenv_t h, double *ms4)
     {
         OK_QUIESCE(h);
-        if (!h || !ms4)
-            return fail(h, OKENV_ERR_INVALID, "okenv_debug_ddpg_timing: NULL argument");
-        if (h->ddpg_log.timed < 5U)
-            return fail(h, OKENV_ERR_STATE, "okenv_debug_ddpg_timing: no okenv_ddpg_update has run with okenv_set_timing on");
-        return eventsSums(h, h->ddpg_log, ms4, 4);
+        return updateTiming(h, &okenv::ddpg_scratch, "okenv_debug_ddpg_timing", "okenv_ddpg_update", ms4, 4);
     }
 
     int okenv_ddpg_act_host(const okenv_ddpg_config *config, const float *actor, int32_t num_rays, int32_t n, const float *dist, const uint8_t *crashed,

@@ -1,7 +1,8 @@
 """The learners' device kernels at the edges of their launch geometry (openkitchen_amd/csrc/ok_learn.h, ok_dqn.h, ok_ddpg.h): every
 chunk count 1 .. 130 of the tree the three step kernels share (okLearnColumnSum), the same tree at the widths the examples run,
 calls of different B on one handle (the partials' buffer grows and is reused while larger than needed), pushes over more than
-256 workgroups (okReplayScatterKernel's count loop), and Deep-Q's ring and DDPG's on one handle.  Everything is compared bit for bit with the host entries, whose own link to
+256 workgroups (okReplayScatterKernel's count loop), Deep-Q's ring and DDPG's on one handle, and the two whole-episode updates
+(REINFORCE's and the Gaussian actor's) on one handle.  Everything is compared bit for bit with the host entries, whose own link to
 the numpy restatements at these B is in tests/test_learn_rule.py, test_dqn_rule.py and test_ddpg_rule.py."""
 import numpy as np
 import pytest
@@ -10,7 +11,9 @@ import torch
 import _learn_numpy as L_
 import test_gpu_ddpg as G
 import test_gpu_dqn as Q
+import test_gpu_gauss as C
 import test_gpu_learn as P
+import test_gpu_reinforce as F
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -272,4 +275,56 @@ def test_both_rings_on_one_handle(gpu, push_all):
         assert host["pushed"] > capacity and (not push_all or host["pushed"] == 2 * N), (host["pushed"], push_all)
     if not push_all:  # about half: neither nobody nor everybody
         assert N // 2 < host_q["pushed"] < 2 * N - N // 2, host_q["pushed"]
+    dev.close()
+
+
+# ---- F: both whole-episode updates on one handle -------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("accumulate", [True, False])
+def test_both_sliced_updates_on_one_handle(gpu, accumulate):
+    """REINFORCE's update and the Gaussian actor's on ONE handle of 33 agents, R = 5: a shared-network actor (H = 8, A = 3, no value
+    network, dropout p = 0.25) with its learner, and a Gaussian actor (H1 = H2 = 8) with a learner of another lr.  They share the loop
+    over slices and the join kernel, and must keep their own t, moments, scratch and event log.  M = 70, B = 33: three slices of 33, 33
+    and 4 positions, that is 2, 2 and 1 chunks, the last with a fill of 4; a random order; REINFORCE's flat indices from [0, 33 * 3)
+    with num_agents = 33 and draw_first = 5.  accumulate on is one step per call, off three.  The calls alternate REINFORCE, Gauss,
+    REINFORCE, Gauss, each on a fresh batch; after every call loss, gradient, parameters, both moments and t of the learner just
+    updated equal its host entry continued from its own previous state, bit for bit, and the other learner's parameters, moments
+    and t are what they were.  The second round runs timed: each timing entry answers two finite positive numbers after its own
+    update, and REINFORCE's still does after the Gaussian update that followed it."""
+    N, R, M, B = 33, 5, 70, 33
+    r_shape, g_shape, p_drop, steps = (R, 8, 3), (R, 8, 8), 0.25, 1 if accumulate else 3
+    rng = np.random.default_rng(31 + accumulate)
+    r_st, g_st = F.fresh_state(rng, r_shape), C.fresh_state(gpu, rng, g_shape)
+    r_hp, g_hp = F.HP, dict(C.HP, lr=0.003)
+    dev = F.handle_for(gpu, r_shape, r_st, n_agents=N)
+    dev.actor_set_dropout(p_drop, 21)
+    assert dev.gauss_create(8, 8, seed=11) == C.n_params(gpu, g_shape)
+    dev.gauss_set_params(g_st["params"])
+    dev.gauss_learner_create(**g_hp)
+    r_cfg = dict(accumulate=accumulate, reduce="mean", num_agents=N, draw_first=5)
+    g_cfg = dict(accumulate=accumulate, reduce="sum", grad="reference")
+
+    def timing_ok(times, names):
+        return set(times) == set(names) and len(times) == 2 and all(np.isfinite(v) and v > 0.0 for v in times.values())
+
+    for rnd in range(2):
+        dev.set_timing(rnd == 1)
+        what = ("reinforce", accumulate, rnd)
+        batch, order = F.random_batch(rng, r_shape, M, N), rng.permutation(M).astype(np.int32)
+        batch["index"] = np.sort(rng.choice(N * 3, M, replace=False)).astype(np.int32)
+        got = F.on_device(dev, r_shape, batch, M, B, order=order, **r_cfg)
+        r_st, want = gpu.reinforce_update_host(gpu.capi.learner_params(**r_hp), r_shape, r_st, batch, B, p=p_drop, dropout_seed=21, agent_base=0,
+                                               order=order, **r_cfg)
+        assert set(got) == {"loss", "grad_policy"} and got["loss"].size == steps and r_st["t"] == (rnd + 1) * steps, what
+        F.assert_equal(got, F.device_state(dev), want, r_st, what)
+        C.assert_equal({}, dev.gauss_state(), {}, g_st, ("gauss after reinforce's update", accumulate, rnd))
+        assert rnd == 0 or timing_ok(dev.reinforce_timing(), gpu.capi.REINFORCE_KERNELS), what
+        what = ("gauss", accumulate, rnd)
+        batch, order = dict(C.random_batch(rng, M), state=rng.random((M, R)).astype(f32)), rng.permutation(M).astype(np.int32)
+        got = C.on_device(gpu, dev, g_shape, batch, M, B, order=order, **g_cfg)
+        g_st, want = gpu.gauss_update_host(gpu.capi.learner_params(clip=0.0, **g_hp), g_shape, g_st, batch, B, order=order, **g_cfg)
+        assert set(got) == {"loss", "grad"} and got["loss"].size == steps and g_st["t"] == (rnd + 1) * steps, what
+        C.assert_equal(got, dev.gauss_state(), want, g_st, what)
+        F.assert_equal({}, F.device_state(dev), {}, r_st, ("reinforce after gauss's update", accumulate, rnd))
+        assert rnd == 0 or (timing_ok(dev.gauss_timing(), gpu.capi.GAUSS_KERNELS) and timing_ok(dev.reinforce_timing(), gpu.capi.REINFORCE_KERNELS)), what
     dev.close()
