@@ -814,6 +814,135 @@ OKENV_API int okenv_gauss_update_host(const okenv_learner_params *params, const 
                                       int32_t hidden2, int32_t num_actions, okenv_gauss_state *state, const okenv_gauss_batch *batch, int32_t M,
                                       int32_t B, const int32_t *order, const okenv_gauss_output *out);
 
+/* ---- Guided cost learning: cost, policy and value networks ---------------------------------------------------
+ * RLRacers/GuidedCostLearning (Networks.hpp, GCLAgent.hpp, main.cpp:114-187, ReadExpertData.hpp) for every agent of the handle: a
+ * Gaussian actor R -> H1 -> H2 -> 2 whose mean is squashed, a value network R -> H1 -> H2 -> 1 and a tanh cost network
+ * (R + 2) -> C1 -> C2 -> 1 on [state | squashed action], with the state x_k = |sensor_hits_[k]|^2 / 200^2.  The rule is written out in
+ * include/okenv_gcl.h (ok_gcl_*).  A GCL object, a shared-network actor, a Gaussian actor and a DDPG object may live on one handle;
+ * they share no buffer.  Parameter vectors in torch's parameters() order: policy [log_std | fc1 | fc2 | fc3], value and cost
+ * [fc1 | fc2 | fc3]. */
+#define OKENV_GCL_POLICY 0
+#define OKENV_GCL_VALUE 1
+#define OKENV_GCL_COST 2
+
+typedef struct okenv_gcl_config {
+    int32_t  hidden1, hidden2;           /* H1, H2 of the policy and the value network: 1 .. 128                      */
+    int32_t  cost_hidden1, cost_hidden2; /* C1, C2 of the cost network: 1 .. 128; its input R + 2 must not exceed 64  */
+    float    scale[2];                   /* action_k = tanh(pre_k) * scale_k + bias_k  (the reference: 50, 10)        */
+    float    bias[2];                    /*                                            (the reference: 50, 0)         */
+    int32_t  greedy;                     /* 0: sample; 1: pre = mu, no draw                                           */
+    uint32_t seed, agent_base;           /* key of the normal draws and of the expert draws; global id of agent 0     */
+} okenv_gcl_config;
+
+/* Where okenv_gcl_act leaves this step's sample, besides the action fields: device pointers, each may be NULL (skipped). */
+typedef struct okenv_gcl_record {
+    float   *state;    /* [N][R]  x_k = (rel_x^2 + rel_y^2) / 40000                    */
+    float   *eps;      /* [N][2]  the normal draws (not written when acting greedily)  */
+    float   *pre;      /* [N][2]  mu + std * eps (greedy: mu), before the squash       */
+    float   *squashed; /* [N][2]  tanh(pre): the action the cost network reads         */
+    float   *action;   /* [N][2]  (throttle_delta, steering_delta)                     */
+    float   *logp;     /* [N]     the sample's log-probability, no tanh correction     */
+    uint8_t *alive;    /* [N]     !crashed_                                            */
+} okenv_gcl_record;
+
+/* Parameters and Adam state of one network: host or device pointers where a call says so; t: optimiser steps so far. */
+typedef struct okenv_gcl_state {
+    float  *params, *m, *v;
+    int64_t t;
+} okenv_gcl_state;
+
+/* The policy rows of a cost update: device pointers (host pointers for the host entry). */
+typedef struct okenv_gcl_cost_batch {
+    const float *state;    /* [Mp][R] */
+    const float *squashed; /* [Mp][2] */
+} okenv_gcl_cost_batch;
+
+typedef struct okenv_gcl_cost_output {
+    float *loss; /* [1]  BCEWithLogits(c_expert, 0) + BCEWithLogits(c_policy, 1) */
+    float *grad; /* the step's gradient, in parameter order                      */
+} okenv_gcl_cost_output;
+
+typedef struct okenv_gcl_update_config {
+    int32_t accumulate; /* okenv_reinforce_config's: != 0 one Adam step per call on the slices' sum; 0 one step per slice */
+    int32_t reduce;     /* OKENV_REINFORCE_SUM | _MEAN                                                               */
+} okenv_gcl_update_config;
+
+/* The batch of a policy / value update: device pointers (host pointers for the host entry), all required. */
+typedef struct okenv_gcl_batch {
+    const float *state; /* [M][R] */
+    const float *pre;   /* [M][2]  the recorded pre-squash sample */
+    const float *logp;  /* [M]     the recorded log-probability   */
+    const float *ret;   /* [M]     discounted returns G           */
+} okenv_gcl_batch;
+
+/* Where the update reports: device pointers (host pointers for the host entry), each may be NULL (skipped). */
+typedef struct okenv_gcl_output {
+    float   *policy_loss; /* [steps]  -mean (or -sum) of the clipped surrogate, per optimiser step */
+    float   *value_loss;  /* [steps]  mean (or sum) of (v - G)^2                                   */
+    int32_t *clipped;     /* [steps]  samples whose ratio left [1 - clip, 1 + clip]               */
+    float   *grad_policy, *grad_value; /* the last step's gradients, in parameter order           */
+    float   *adv;         /* [M]      the normalised advantages of the call                        */
+} okenv_gcl_output;
+
+/* LDS bytes of the largest of the three gradient kernels with chunks of 32 samples: a pure host function.  A shape is accepted only
+ * if this fits 160 KB; the chunk is never shrunk, because it is part of the summation order.  0 for a width outside the rule's limits
+ * (num_rays + 2 > 64 included). */
+OKENV_API int64_t okenv_gcl_lds_bytes(int32_t num_rays, int32_t hidden1, int32_t hidden2, int32_t cost_hidden1, int32_t cost_hidden2);
+/* Attaches a GCL object to the handle (replaces an earlier one: parameters, moments, step counts and the expert bank are forgotten).
+ * OKENV_ERR_INVALID for NULL arguments, a width outside 1 .. 128, num_rays + 2 > 64, a shape that does not fit the LDS, greedy other
+ * than 0 or 1, a scale or bias that is not finite. */
+OKENV_API int okenv_gcl_create(okenv_t h, const okenv_gcl_config *config);
+OKENV_API int okenv_gcl_num_params(okenv_t h, int32_t which, int32_t *num_params);
+/* New parameters of network `which` (OKENV_GCL_POLICY | _VALUE | _COST) from a host or device pointer; moments and step counts are
+ * left alone.  No synchronisation. */
+OKENV_API int okenv_gcl_set_params(okenv_t h, int32_t which, const float *params);
+/* The parameters to a host or device pointer; synchronises. */
+OKENV_API int okenv_gcl_get_params(okenv_t h, int32_t which, float *params);
+/* Every non-NULL member of `out` is filled from the device; out->t is the network's step count (policy and value share one);
+ * synchronises. */
+OKENV_API int okenv_gcl_get_state(okenv_t h, int32_t which, okenv_gcl_state *out);
+/* A device word added to the draw index of every later okenv_gcl_act (NULL: none): okenv_actor_set_draw_offset's contract. */
+OKENV_API int okenv_gcl_set_draw_offset(okenv_t h, const uint32_t *device_word);
+OKENV_API int okenv_gcl_set_greedy(okenv_t h, int32_t greedy);
+/* The action of every agent, crashed ones included: reads OKENV_F_REL_X / _REL_Y and crashed_, writes OKENV_F_THROTTLE /
+ * OKENV_F_STEER and the record.  One kernel on the handle's stream, no synchronisation, no allocation: capturable beside okenv_step.
+ * OKENV_ERR_STATE before the policy has its parameters. */
+OKENV_API int okenv_gcl_act(okenv_t h, const okenv_gcl_record *rec);
+/* The expert bank: E rows state [E][R] and action [E][2] (already in the network's units: ReadExpertData.hpp:98,111), copied from
+ * device pointers on the handle's stream.  Allocates when E exceeds every earlier bank.  OKENV_ERR_INVALID for E < 1 or NULL. */
+OKENV_API int okenv_gcl_set_expert(okenv_t h, const float *state, const float *action, int32_t E);
+/* out[s] = cost([state_s | squashed_s]) for M rows, device pointers: one forward-only kernel, no synchronisation.  OKENV_ERR_STATE
+ * before the cost network has its parameters. */
+OKENV_API int okenv_gcl_cost(okenv_t h, const float *state, const float *squashed, int32_t M, float *out);
+/* The optimisers: `policy_value` for the policy and the value network (its clip is the ratio's), `cost` for the cost network (its
+ * clip is not read).  Moments zeroed, step counts 0.  OKENV_ERR_STATE before all three networks have their parameters. */
+OKENV_API int okenv_gcl_learner_create(okenv_t h, const okenv_learner_params *policy_value, const okenv_learner_params *cost);
+/* One Adam step of the cost network on Me expert positions drawn from the bank and the Mp policy rows of `batch`: a gradient kernel
+ * and a join kernel on the handle's stream, no synchronisation, no allocation after the first call of a given size.
+ * OKENV_ERR_STATE before okenv_gcl_learner_create or okenv_gcl_set_expert; OKENV_ERR_INVALID for NULL fields, Mp < 1 or Me < 1. */
+OKENV_API int okenv_gcl_cost_update(okenv_t h, const okenv_gcl_cost_batch *batch, int32_t Mp, int32_t Me, const okenv_gcl_cost_output *out);
+/* The advantages of the call (a forward-only sweep of the value network, their statistics, the normalisation), then the policy's
+ * slices and the value's slices, two kernels each (okenv_reinforce_update's contract): no synchronisation, no allocation after the
+ * first call of a given M and B; `order` [M] int32 on the device or NULL. */
+OKENV_API int okenv_gcl_policy_update(okenv_t h, const okenv_gcl_update_config *config, const okenv_gcl_batch *batch, int32_t M, int32_t B,
+                                      const int32_t *order, const okenv_gcl_output *out);
+/* The same rules on host arrays, no GPU needed.  Act: n agents (global ids config->agent_base + i), rel_x, rel_y [n][num_rays],
+ * crashed [n] or NULL; outputs, each may be NULL: throttle, steer [n], eps, pre, squashed, action [n][2], logp [n], state
+ * [n][num_rays], alive [n]. */
+OKENV_API int okenv_gcl_act_host(const okenv_gcl_config *config, const float *policy, int32_t num_rays, int32_t n, const float *rel_x,
+                                 const float *rel_y, const uint8_t *crashed, uint32_t draw_index, float *throttle, float *steer, float *eps, float *pre,
+                                 float *squashed, float *action, float *logp, float *state, uint8_t *alive);
+OKENV_API int okenv_gcl_cost_host(const float *cost, int32_t num_rays, int32_t cost_hidden1, int32_t cost_hidden2, const float *state,
+                                  const float *squashed, int32_t M, float *out);
+/* Every member of `state` is required; state->t is the update number of the expert draws and advances by one. */
+OKENV_API int okenv_gcl_cost_update_host(const okenv_learner_params *params, uint32_t seed, int32_t num_rays, int32_t cost_hidden1,
+                                         int32_t cost_hidden2, okenv_gcl_state *state, const float *bank_state, const float *bank_action, int32_t E,
+                                         const okenv_gcl_cost_batch *batch, int32_t Mp, int32_t Me, const okenv_gcl_cost_output *out);
+/* Every member of both states is required; the step count is policy->t (value->t is set to it afterwards). */
+OKENV_API int okenv_gcl_policy_update_host(const okenv_learner_params *params, const okenv_gcl_update_config *config, int32_t num_rays,
+                                           int32_t hidden1, int32_t hidden2, okenv_gcl_state *policy, okenv_gcl_state *value,
+                                           const okenv_gcl_batch *batch, int32_t M, int32_t B, const int32_t *order, const okenv_gcl_output *out);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.
@@ -1108,6 +1237,9 @@ OKENV_API int okenv_debug_ddpg_timing(okenv_t h, double *ms4);
 OKENV_API int okenv_debug_reinforce_timing(okenv_t h, double *ms2);
 /* of the latest okenv_gauss_update likewise: [0] gradient kernels, [1] join kernels */
 OKENV_API int okenv_debug_gauss_timing(okenv_t h, double *ms2);
+/* of the latest okenv_gcl_cost_update (which = OKENV_GCL_COST) or of network `which`'s slices in the latest okenv_gcl_policy_update
+ * likewise: [0] gradient kernels, [1] join kernels */
+OKENV_API int okenv_debug_gcl_timing(okenv_t h, int32_t which, double *ms2);
 /* ok_gauss_normal_pair (include/okenv_gauss.h) on n word pairs (host pointers): out0 = r cos, out1 = r sin; on GPU `device`, or on the
  * host with device == OKENV_DEBUG_ON_HOST. */
 OKENV_API int okenv_debug_normal(int32_t device, const uint32_t *w0, const uint32_t *w1, float *out0, float *out1, int32_t n);

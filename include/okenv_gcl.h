@@ -1,0 +1,257 @@
+/*
+ * okenv_gcl.h -- the rule of guided cost learning (RLRacers/GuidedCostLearning: Networks.hpp, GCLAgent.hpp:52-180, main.cpp:150-187,
+ * ReadExpertData.hpp:98,111): a tanh cost network on [state | action], a Gaussian actor with a squashed mean and a clipped-ratio update,
+ * and a value network with a squared-error update, shared bit for bit by the HIP kernels (openkitchen_amd/csrc/ok_gcl.h) and the host
+ * entries okenv_gcl_act_host, okenv_gcl_cost_host, okenv_gcl_cost_update_host and okenv_gcl_policy_update_host.
+ * It stands on the actor's rule (okenv_math.h), the learner's (okenv_learn.h), the batch's statistics (okenv_batch.h) and the Gaussian
+ * machinery (okenv_gauss.h).
+ *
+ * THE RULE
+ *
+ * State (GCLAgent.hpp:52-61).  x_k = (rel_x_k * rel_x_k + rel_y_k * rel_y_k) / 40000.0f: one multiplication each, one addition, one
+ * IEEE division (ok_gcl_state).  NOT the other actors' dist / 200.
+ *
+ * Networks.  Three, each in -> H1 -> H2 -> out with the parameter vector in torch's parameters() order (ok_gcl_offsets):
+ *     policy  R -> H1 -> H2 -> 2, ReLU twice, one free log_std [2] FIRST (a module's own parameters come before its children's):
+ *             [log_std | fc1.weight | fc1.bias | fc2.weight | fc2.bias | fc3.weight | fc3.bias] = ok_gauss_layout
+ *     value   R -> H1 -> H2 -> 1, ReLU twice, no log_std: [fc1 | fc2 | fc3]
+ *     cost    (R + 2) -> C1 -> C2 -> 1 on [x | a] with the squashed a, tanh behind both hidden layers, no log_std; R + 2 <= 64
+ * Sums and layers are okenv_gauss.h's, unchanged: ok_learn_pre for layer 1, ok_gauss_pre (8 interleaved partials and ok_actor_join's
+ * tree) for layers 2 and 3, ok_learn_back_hidden and ok_gauss_back backward, ok_gauss_term for a parameter's term.  New here:
+ *     a tanh hidden layer    h = ok_tanhf(pre);   backward  dpre = dh * (1.0f - h * h)     the product h * h first, then the difference,
+ *                                                                                           then the product with dh (ok_gcl_tanh_back)
+ *     the policy's mean      mu_k = ok_tanhf(z3_k), z3 the third layer's output;   dz3_k = dmu_k * (1.0f - mu_k * mu_k)   the same way
+ * With ReLU, dpre = pre > 0 ? dh : 0 (tested as relu(pre) > 0), as in okenv_gauss.h.
+ *
+ * Acting (ok_gcl_sample).  eps is ok_gauss_normal_pair on Philox stream 11: counter = (global agent id g, draw index d, 11, n),
+ * key = (seed, "oken"), words 0 and 1 of block n give components 2 n and 2 n + 1 (ok_gcl_eps).  The draw index and the draw-offset word
+ * are section 14's.  For component k:
+ *     std_k = ok_expf(log_std_k)
+ *     pre_k = mu_k + std_k * eps_k                       greedy: pre_k = mu_k, nothing is drawn
+ *     z_k   = (pre_k - mu_k) / std_k                     greedy: z_k = 0.0f
+ *     a_k   = ok_tanhf(pre_k)                            `squashed`: what the cost network reads
+ *     act_k = a_k * scale_k + bias_k                     section 20's form; (50, 50) and (10, 0).  The reference writes
+ *                                                        (a_0 + 1) / 2 * 100 and a_1 * 10: the throttle differs by rounding only
+ *     n_k   = ((-0.5f * z_k) * z_k - log_std_k) - 0.9189385f
+ *     logp  = n_0 + n_1                                  there is no tanh correction (GCLAgent.hpp:127-129)
+ * z is formed from the rounded pre, NOT taken to be eps: (fl(mu + fl(std * eps)) - mu) / std differs from eps by rounding, and the update
+ * below can only form the former.  The reference records the logp of eps and recomputes the logp of (a_raw - mu) / std (GCLAgent.hpp:127,
+ * 154), so its first ratio is 1 up to rounding; here the recorded logp is the recomputable one, so before any optimiser step the
+ * recomputed logp equals the recorded one bit for bit and r is exactly 1.  The recorded eps is the draw itself.  Every agent is acted
+ * for, crashed ones included.
+ *
+ * Policy seed (ok_gcl_policy_seed), with the current parameters and the recorded pre, logp_old and the advantage adv:
+ *     z_k, n_k, logp as above;   r = ok_expf(logp - logp_old)
+ *     lo, hi, rc, s1, s2, surr, clipped and the min / clamp / tie conventions: okenv_learn.h:25-32, word for word
+ *     g_r = w1 * adv + w2 * (lo <= r <= hi ? adv : 0);   g = (-g_r) * r          d loss / d logp: loss = -mean(surr), d r / d logp = r
+ *     dmu_k = g * (z_k / std_k);   dls_k = g * (z_k * z_k - 1.0f)                 pre is a constant (detached)
+ * The sample's loss term is -surr (the negation is exact).
+ *
+ * Advantages (ok_gcl_adv).  One forward-only sweep of the value network over all M samples with the parameters the call starts with:
+ * raw_s = G_s - v_s.  Their mean and unbiased standard deviation by section 15's rule: the samples are cut into chunks of OK_LEARN_CHUNK
+ * consecutive SAMPLE indices (not positions: `order` plays no part); a chunk's fp64 partials are S = S + raw, Q = Q + raw * raw
+ * ascending from 0.0; the chunk partials are joined by ok_batch_tree over the chunk index; ok_batch_finish gives mean and std.
+ *     adv_s = (raw_s - mean) / (std + 1e-8f)
+ * In fp32 the + 1e-8f only matters at std = 0: that is the reference (GCLAgent.hpp:149).  M = 1 gives (raw - raw) / 1e-8f = 0, never
+ * NaN.  With accumulate = 0 the later slices keep these advantages although the value network has stepped in between: they are the
+ * call's, not the slice's.
+ *
+ * Value seed.  ok_learn_value_seed: e = v - G, term e * e, dz = 2.0f * e.
+ *
+ * Cost seed (ok_gcl_cost_seed), safe for any finite logit c:
+ *     e = ok_expf(-|c|);   l = ok_logf(1.0f + e)
+ *     softplus(c) = (c > 0 ? c : 0.0f) + l;   softplus(-c) = (c < 0 ? -c : 0.0f) + l
+ *     sigmoid(c)  = c >= 0 ? 1.0f / (1.0f + e) : e / (1.0f + e)
+ *     expert row:  term softplus(c),  seed sigmoid(c)                  BCEWithLogits(c, 0)
+ *     policy row:  term softplus(-c), seed sigmoid(c) - 1.0f           BCEWithLogits(c, 1)
+ * The update reads Me expert positions and Mp policy rows.  Expert position q of update number d (the cost network's step count before
+ * the update) reads bank row ok_gcl_expert_row(seed, q, d, E): ok_index_from_word on word 0 of Philox stream 12, counter (q, d, 12, 0).
+ * Each set is cut into its own chunks of OK_LEARN_CHUNK positions and summed in its own partial columns [parameters | loss], each
+ * joined by ok_learn_tree; each joined sum is divided ONCE by its own count, then the two are added, expert first:
+ *     gradient = sum_e / (float)Me + sum_p / (float)Mp,  and the loss likewise;  then ok_learn_adam.
+ *
+ * Slices, accumulate, reduce, order, Adam for the policy / value update: okenv_reinforce.h's, unchanged.  Policy and value share the
+ * step count t and each has its own moments (section 16); the two networks do not read each other once the advantages stand, so the
+ * policy's slices and the value's slices are independent.  The cost network has its own t.  The reference is accumulate = 1,
+ * reduce = MEAN.
+ *
+ * Only +, -, *, /, comparisons, the correctly rounded square root, ok_expf, ok_logf, ok_tanhf and ok_sincosf are used; compile with
+ * -ffp-contract=off.  Plain C99 / C++ / HIP.
+ */
+#ifndef OKENV_GCL_H
+#define OKENV_GCL_H
+
+#include "okenv_batch.h"
+#include "okenv_gauss.h"
+
+#define OK_GCL_ACT_STREAM 11u
+#define OK_GCL_EXPERT_STREAM 12u
+#define OK_GCL_POLICY 0
+#define OK_GCL_VALUE 1
+#define OK_GCL_COST 2
+#define OK_GCL_RANGE_SQUARED 40000.0f /* kSensorRange * kSensorRange */
+#define OK_GCL_ADV_EPS 1e-8f
+
+OK_HDI float ok_gcl_state(const float rel_x, const float rel_y)
+{
+    const float xx = rel_x * rel_x, yy = rel_y * rel_y;
+    return (xx + yy) / OK_GCL_RANGE_SQUARED;
+}
+
+/* Where the pieces of a network's parameter vector begin: ok_gauss_offsets with `nls` floats of log_std in front (2 for the policy,
+ * 0 for the value and the cost network).  at.log_std = 0 and at.w1 = nls. */
+OK_HDI ok_gauss_layout ok_gcl_offsets(const int in, const int h1, const int h2, const int out, const int nls)
+{
+    ok_gauss_layout at;
+    at.log_std = 0;
+    at.w1 = nls;
+    at.b1 = at.w1 + h1 * in;
+    at.w2 = at.b1 + h1;
+    at.b2 = at.w2 + h2 * h1;
+    at.w3 = at.b2 + h2;
+    at.b3 = at.w3 + out * h2;
+    at.total = at.b3 + out;
+    return at;
+}
+
+/* Inputs, outputs and log_std floats of network `which` for a fan of R rays */
+OK_HDI int ok_gcl_in(const int which, const int R) { return which == OK_GCL_COST ? R + 2 : R; }
+OK_HDI int ok_gcl_out(const int which) { return which == OK_GCL_POLICY ? 2 : 1; }
+OK_HDI int ok_gcl_nls(const int which) { return which == OK_GCL_POLICY ? 2 : 0; }
+
+OK_HDI int ok_gcl_num_params(const int which, const int R, const int h1, const int h2)
+{
+    return ok_gcl_offsets(ok_gcl_in(which, R), h1, h2, ok_gcl_out(which), ok_gcl_nls(which)).total;
+}
+
+/* Parameter index p as the term it sums: ok_gauss_decode behind `nls` log_std entries */
+OK_HDI ok_learn_slot ok_gcl_decode(const int p, const int in, const int h1, const int h2, const int out, const int nls)
+{
+    if (p < nls) {
+        ok_learn_slot s;
+        s.kind = 0;
+        s.a = p;
+        s.b = 0;
+        return s;
+    }
+    return ok_gauss_decode(p - nls + out, in, h1, h2, out);
+}
+
+OK_HDI float ok_gcl_tanh_back(const float dh, const float h)
+{
+    const float hh = h * h;
+    const float u = 1.0f - hh;
+    return dh * u;
+}
+
+/* A hidden unit's value from its pre-activation, and its seed from dh and that value: tanh (the cost network) or ReLU */
+OK_HDI float ok_gcl_hidden(const float pre, const int tanh_layer)
+{
+    if (tanh_layer) return ok_tanhf(pre);
+    return pre > 0.0f ? pre : 0.0f;
+}
+
+OK_HDI float ok_gcl_back(const float dh, const float h, const int tanh_layer)
+{
+    if (tanh_layer) return ok_gcl_tanh_back(dh, h);
+    return h > 0.0f ? dh : 0.0f;
+}
+
+/* eps_k of (seed, global agent id, draw index) */
+OK_HD float ok_gcl_eps(const uint32_t seed, const uint32_t agent, const uint32_t draw, const int k)
+{
+    const ok_u32x4 b = ok_philox4x32(agent, draw, OK_GCL_ACT_STREAM, (uint32_t)(k >> 1), seed, 0x6F6B656Eu);
+    float e0, e1;
+    ok_gauss_normal_pair(b.v[0], b.v[1], &e0, &e1);
+    return (k & 1) ? e1 : e0;
+}
+
+/* The bank row of expert position q of update number d */
+OK_HDI uint32_t ok_gcl_expert_row(const uint32_t seed, const uint32_t q, const uint32_t d, const uint32_t rows)
+{
+    const ok_u32x4 r = ok_philox4x32(q, d, OK_GCL_EXPERT_STREAM, 0u, seed, 0x6F6B656Eu);
+    return ok_index_from_word(r.v[0], rows);
+}
+
+/* One component's normal term from its z */
+OK_HDI float ok_gcl_normal_term(const float z, const float log_std)
+{
+    return ((-0.5f * z) * z - log_std) - 0.9189385f;
+}
+
+/* One component of the acted sample from mu_k = ok_tanhf(z3_k) */
+typedef struct ok_gcl_comp {
+    float pre, squashed, z, n;
+} ok_gcl_comp;
+
+OK_HD ok_gcl_comp ok_gcl_sample(const float mu, const float log_std, const float eps, const int greedy)
+{
+    ok_gcl_comp c;
+    if (greedy) {
+        c.pre = mu;
+        c.z = 0.0f;
+    } else {
+        const float std = ok_expf(log_std);
+        const float se = std * eps;
+        c.pre = mu + se;
+        c.z = (c.pre - mu) / std;
+    }
+    c.squashed = ok_tanhf(c.pre);
+    c.n = ok_gcl_normal_term(c.z, log_std);
+    return c;
+}
+
+/* z_k and std_k of a recorded pre under the current mu and log_std */
+OK_HD float ok_gcl_z(const float pre, const float mu, const float log_std, float *std_out)
+{
+    const float std = ok_expf(log_std);
+    *std_out = std;
+    return (pre - mu) / std;
+}
+
+/* From logp and the recorded logp_old to the surrogate, the clip flag and g = d loss / d logp of the sample */
+OK_HD float ok_gcl_ratio_seed(const float logp, const float logp_old, const float adv, const float lo, const float hi, float *surr, int *clipped)
+{
+    const float r = ok_expf(logp - logp_old);
+    const float rc = r < lo ? lo : (r > hi ? hi : r);
+    const float s1 = r * adv, s2 = rc * adv;
+    *surr = s1 < s2 ? s1 : s2;
+    *clipped = (r < lo || r > hi) ? 1 : 0;
+    const float w1 = s1 < s2 ? 1.0f : (s2 < s1 ? 0.0f : 0.5f);
+    const float w2 = 1.0f - w1;
+    const float in_range = (r >= lo && r <= hi) ? adv : 0.0f;
+    const float g_r = w1 * adv + w2 * in_range;
+    return (-g_r) * r;
+}
+
+/* The seeds of one component on mu_k and log_std_k */
+OK_HDI void ok_gcl_policy_seed(const float g, const float z, const float std, float *dmu, float *dls)
+{
+    *dmu = g * (z / std);
+    *dls = g * (z * z - 1.0f);
+}
+
+OK_HDI float ok_gcl_adv(const float raw, const float mean, const float sd)
+{
+    const float den = sd + OK_GCL_ADV_EPS;
+    return (raw - mean) / den;
+}
+
+/* The term and the seed of a cost row with logit c; policy != 0: a policy row (label 1), else an expert row (label 0) */
+OK_HD void ok_gcl_cost_seed(const float c, const int policy, float *term, float *seed)
+{
+    const float ac = c < 0.0f ? -c : c;
+    const float e = ok_expf(-ac);
+    const float ope = 1.0f + e;
+    const float l = ok_logf(ope);
+    const float sig = c >= 0.0f ? 1.0f / ope : e / ope;
+    if (policy) {
+        *term = (c < 0.0f ? -c : 0.0f) + l;
+        *seed = sig - 1.0f;
+    } else {
+        *term = (c > 0.0f ? c : 0.0f) + l;
+        *seed = sig;
+    }
+}
+
+#endif /* OKENV_GCL_H */

@@ -94,6 +94,10 @@ SYMBOLS = [
     "okenv_gauss_lds_bytes", "okenv_gauss_create", "okenv_gauss_num_params", "okenv_gauss_set_params", "okenv_gauss_get_params",
     "okenv_gauss_get_state", "okenv_gauss_set_draw_offset", "okenv_gauss_set_greedy", "okenv_gauss_act", "okenv_gauss_learner_create",
     "okenv_gauss_update", "okenv_gauss_act_host", "okenv_gauss_update_host", "okenv_debug_gauss_timing", "okenv_debug_normal",
+    "okenv_gcl_lds_bytes", "okenv_gcl_create", "okenv_gcl_num_params", "okenv_gcl_set_params", "okenv_gcl_get_params", "okenv_gcl_get_state",
+    "okenv_gcl_set_draw_offset", "okenv_gcl_set_greedy", "okenv_gcl_act", "okenv_gcl_set_expert", "okenv_gcl_cost", "okenv_gcl_learner_create",
+    "okenv_gcl_cost_update", "okenv_gcl_policy_update", "okenv_debug_gcl_timing", "okenv_gcl_act_host", "okenv_gcl_cost_host",
+    "okenv_gcl_cost_update_host", "okenv_gcl_policy_update_host",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -344,6 +348,72 @@ def gauss_num_params(R, H1, H2, A=2):
 def gauss_lds_bytes(R, H1, H2, A=2):
     """okenv_gauss_lds_bytes: the gradient kernel's LDS for the shape, 0 outside the rule's limits.  No GPU needed."""
     return int(load().okenv_gauss_lds_bytes(int(R), int(H1), int(H2), int(A)))
+
+
+# guided cost learning (include/okenv.h)
+GCL_POLICY, GCL_VALUE, GCL_COST = 0, 1, 2
+GCL_NETWORKS = {"policy": GCL_POLICY, "value": GCL_VALUE, "cost": GCL_COST}
+GCL_KERNELS = ("grad", "step")
+GCL_LDS_BUDGET = 160 * 1024
+
+
+class OkenvGclConfig(C.Structure):
+    _fields_ = [("hidden1", C.c_int32), ("hidden2", C.c_int32), ("cost_hidden1", C.c_int32), ("cost_hidden2", C.c_int32), ("scale", C.c_float * 2),
+                ("bias", C.c_float * 2), ("greedy", C.c_int32), ("seed", C.c_uint32), ("agent_base", C.c_uint32)]
+
+
+class OkenvGclRecord(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("eps", C.c_void_p), ("pre", C.c_void_p), ("squashed", C.c_void_p), ("action", C.c_void_p),
+                ("logp", C.c_void_p), ("alive", C.c_void_p)]
+
+
+class OkenvGclState(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("t", C.c_int64)]
+
+
+class OkenvGclCostBatch(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("squashed", C.c_void_p)]
+
+
+class OkenvGclCostOutput(C.Structure):
+    _fields_ = [("loss", C.c_void_p), ("grad", C.c_void_p)]
+
+
+class OkenvGclUpdateConfig(C.Structure):
+    _fields_ = [("accumulate", C.c_int32), ("reduce", C.c_int32)]
+
+
+class OkenvGclBatch(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("pre", C.c_void_p), ("logp", C.c_void_p), ("ret", C.c_void_p)]
+
+
+class OkenvGclOutput(C.Structure):
+    _fields_ = [("policy_loss", C.c_void_p), ("value_loss", C.c_void_p), ("clipped", C.c_void_p), ("grad_policy", C.c_void_p),
+                ("grad_value", C.c_void_p), ("adv", C.c_void_p)]
+
+
+def gcl_config(hidden1=64, hidden2=64, cost_hidden1=64, cost_hidden2=64, scale=(50.0, 10.0), bias=(50.0, 0.0), greedy=False, seed=0, agent_base=0):
+    """okenv_gcl_config with the reference's widths and action ranges as defaults (Networks.hpp, GCLAgent.hpp:64-72)."""
+    return OkenvGclConfig(int(hidden1), int(hidden2), int(cost_hidden1), int(cost_hidden2), (C.c_float * 2)(*map(float, scale)),
+                          (C.c_float * 2)(*map(float, bias)), int(greedy), int(seed) & 0xFFFFFFFF, int(agent_base) & 0xFFFFFFFF)
+
+
+def gcl_update_config(accumulate=True, reduce="mean"):
+    """okenv_gcl_update_config with the reference's choices as defaults (one step on the mean); reduce: "sum" / "mean" or the integer."""
+    return OkenvGclUpdateConfig(1 if accumulate else 0, REINFORCE_REDUCE[reduce] if isinstance(reduce, str) else int(reduce))
+
+
+def gcl_num_params(which, R, H1, H2):
+    """Floats of a network's parameter vector; which: "policy" [log_std | fc1 | fc2 | fc3] (R -> H1 -> H2 -> 2), "value" [fc1 | fc2 | fc3]
+    (R -> H1 -> H2 -> 1) or "cost" (R + 2 -> H1 -> H2 -> 1), or the integer."""
+    which = GCL_NETWORKS[which] if isinstance(which, str) else int(which)
+    n_in, out, nls = (R + 2 if which == GCL_COST else R), (2 if which == GCL_POLICY else 1), (2 if which == GCL_POLICY else 0)
+    return nls + H1 * n_in + H1 + H2 * H1 + H2 + out * H2 + out
+
+
+def gcl_lds_bytes(R, H1, H2, C1, C2):
+    """okenv_gcl_lds_bytes: the largest gradient kernel's LDS for the shapes, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_gcl_lds_bytes(int(R), int(H1), int(H2), int(C1), int(C2)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -610,6 +680,28 @@ def load(build_if_missing=True):
     L.okenv_gauss_update_host.argtypes = [C.POINTER(OkenvLearnerParams), C.POINTER(OkenvGaussUpdateConfig), i32, i32, i32, i32,
                                           C.POINTER(OkenvGaussState), C.POINTER(OkenvGaussBatch), i32, i32, vp, C.POINTER(OkenvGaussOutput)]
     L.okenv_debug_gauss_timing.argtypes = [vp, vp]
+    L.okenv_gcl_lds_bytes.argtypes = [i32, i32, i32, i32, i32]
+    L.okenv_gcl_lds_bytes.restype = C.c_int64
+    L.okenv_gcl_create.argtypes = [vp, C.POINTER(OkenvGclConfig)]
+    L.okenv_gcl_num_params.argtypes = [vp, i32, C.POINTER(i32)]
+    L.okenv_gcl_set_params.argtypes = [vp, i32, vp]
+    L.okenv_gcl_get_params.argtypes = [vp, i32, vp]
+    L.okenv_gcl_get_state.argtypes = [vp, i32, C.POINTER(OkenvGclState)]
+    L.okenv_gcl_set_draw_offset.argtypes = [vp, vp]
+    L.okenv_gcl_set_greedy.argtypes = [vp, i32]
+    L.okenv_gcl_act.argtypes = [vp, C.POINTER(OkenvGclRecord)]
+    L.okenv_gcl_set_expert.argtypes = [vp, vp, vp, i32]
+    L.okenv_gcl_cost.argtypes = [vp, vp, vp, i32, vp]
+    L.okenv_gcl_learner_create.argtypes = [vp, C.POINTER(OkenvLearnerParams), C.POINTER(OkenvLearnerParams)]
+    L.okenv_gcl_cost_update.argtypes = [vp, C.POINTER(OkenvGclCostBatch), i32, i32, C.POINTER(OkenvGclCostOutput)]
+    L.okenv_gcl_policy_update.argtypes = [vp, C.POINTER(OkenvGclUpdateConfig), C.POINTER(OkenvGclBatch), i32, i32, vp, C.POINTER(OkenvGclOutput)]
+    L.okenv_debug_gcl_timing.argtypes = [vp, i32, vp]
+    L.okenv_gcl_act_host.argtypes = [C.POINTER(OkenvGclConfig), vp, i32, i32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.okenv_gcl_cost_host.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp]
+    L.okenv_gcl_cost_update_host.argtypes = [C.POINTER(OkenvLearnerParams), u32, i32, i32, i32, C.POINTER(OkenvGclState), vp, vp, i32,
+                                             C.POINTER(OkenvGclCostBatch), i32, i32, C.POINTER(OkenvGclCostOutput)]
+    L.okenv_gcl_policy_update_host.argtypes = [C.POINTER(OkenvLearnerParams), C.POINTER(OkenvGclUpdateConfig), i32, i32, i32, C.POINTER(OkenvGclState),
+                                               C.POINTER(OkenvGclState), C.POINTER(OkenvGclBatch), i32, i32, vp, C.POINTER(OkenvGclOutput)]
     L.okenv_debug_normal.argtypes = [i32, vp, vp, vp, vp, i32]
     _lib = L
     return L

@@ -30,6 +30,7 @@
 #include "ok_ddpg.h"
 #include "ok_reinforce.h"
 #include "ok_gauss.h"
+#include "ok_gcl.h"
 #include "ok_expert.h"
 
 namespace
@@ -553,6 +554,19 @@ struct okenv
     int64_t                 gauss_t{0};
     const uint32_t         *gauss_draw_offset{nullptr};
     OkUpdateScratch         gauss_scratch;
+    // Guided cost learning (okenv_gcl_create, okenv_gcl_learner_create): the three networks [policy | value | cost], each
+    // [params | m | v] of gcl_cap floats; the expert bank (grown, never shrunk); per network the update's scratch [chunk partials |
+    // accumulator] (the policy's also holds its chunks' clip counts) and timing; the advantages' scratch [adv | S, Q partials | mean, std]
+    bool                    gcl_ok{false}, gcl_set[3]{false, false, false}, gcl_learner_ok{false};
+    okenv_gcl_config        gcl{};
+    okenv_learner_params    gcl_learner{}, gcl_cost_learner{};
+    size_t                  gcl_cap{0};
+    float                  *d_gcl{nullptr};
+    int64_t                 gcl_t{0}, gcl_cost_t{0};
+    const uint32_t         *gcl_draw_offset{nullptr};
+    float                  *d_gcl_bank{nullptr}; // [state rows | action rows]
+    int32_t                 gcl_bank_rows{0}, gcl_bank_cap{0};
+    OkUpdateScratch         gcl_scratch[3], gcl_adv_scratch;
 };
 
 struct okenv_track
@@ -1331,6 +1345,18 @@ int sliceUpdate(okenv *h, OkUpdateScratch &u, const int32_t M, const int32_t B, 
     return OKENV_OK;
 }
 
+// Guided cost learning's vectors in d_gcl: network `which` (OKENV_GCL_POLICY / _VALUE / _COST), vector k (0 params, 1 m, 2 v)
+float *gclVector(const okenv *h, const int which, const int k)
+{
+    return h->d_gcl + (static_cast<size_t>(which) * 3U + static_cast<size_t>(k)) * h->gcl_cap;
+}
+
+int gclNumParams(const okenv *h, const int which)
+{
+    const bool cost = which == OKENV_GCL_COST;
+    return ok_gcl_num_params(which, h->shape.R, cost ? h->gcl.cost_hidden1 : h->gcl.hidden1, cost ? h->gcl.cost_hidden2 : h->gcl.hidden2);
+}
+
 // ---- the replay rings' entries, behind the exported functions' OK_QUIESCE ---------------------------------------------------------
 
 // Which ring an exported entry works on: its record in the handle, the prefix of its entries' names (for the messages) and the widest
@@ -1801,7 +1827,8 @@ extern "C"
             (void)hipEventDestroy(e.start);
             (void)hipEventDestroy(e.stop);
         }
-        for (OkUpdateScratch *u : {&h->batch_scratch, &h->learn_scratch, &h->dqn_scratch, &h->ddpg_scratch, &h->reinforce_scratch, &h->gauss_scratch})
+        for (OkUpdateScratch *u : {&h->batch_scratch, &h->learn_scratch, &h->dqn_scratch, &h->ddpg_scratch, &h->reinforce_scratch, &h->gauss_scratch, &h->gcl_scratch[0],
+                                   &h->gcl_scratch[1], &h->gcl_scratch[2], &h->gcl_adv_scratch})
             for (hipEvent_t e : u->log.events)
                 (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
@@ -3648,6 +3675,462 @@ extern "C"
         OK_HIP(nullptr, hipGetLastError());
         OK_HIP(nullptr, hipMemcpy(out0, o0, 4U * count, hipMemcpyDeviceToHost));
         OK_HIP(nullptr, hipMemcpy(out1, o1, 4U * count, hipMemcpyDeviceToHost));
+        return OKENV_OK;
+    }
+
+    // ---- Guided cost learning: cost, policy and value networks (ok_gcl.h) --------------------------------------------------------
+
+    int64_t okenv_gcl_lds_bytes(int32_t num_rays, int32_t hidden1, int32_t hidden2, int32_t cost_hidden1, int32_t cost_hidden2)
+    {
+        return static_cast<int64_t>(okGclLdsBytes(num_rays, hidden1, hidden2, cost_hidden1, cost_hidden2));
+    }
+
+    int okenv_gcl_create(okenv_t h, const okenv_gcl_config *config)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_create: NULL handle");
+        if (const char *why = okGclCheckConfig(config, h->shape.R))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_gcl_create: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        // room for the widest network, so that a later create with other widths allocates nothing
+        h->gcl_cap = (static_cast<size_t>(ok_gauss_num_params(OK_ACTOR_MAX_RAYS, OK_GAUSS_MAX_HIDDEN, OK_GAUSS_MAX_HIDDEN, 2)) + 3U) & ~static_cast<size_t>(3U);
+        if (const int rc = devEnsure(h, &h->d_gcl, 9U * h->gcl_cap))
+            return rc;
+        const void *const kernels[] = {reinterpret_cast<const void *>(&okGclActKernel),
+                                       reinterpret_cast<const void *>(&okGclForwardKernel<false>),
+                                       reinterpret_cast<const void *>(&okGclForwardKernel<true>),
+                                       reinterpret_cast<const void *>(&okGclGradKernel<OK_GCL_POLICY>),
+                                       reinterpret_cast<const void *>(&okGclGradKernel<OK_GCL_VALUE>),
+                                       reinterpret_cast<const void *>(&okGclGradKernel<OK_GCL_COST>)};
+        for (const void *k : kernels)
+            OK_HIP(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+        OK_HIP(h, hipMemsetAsync(h->d_gcl, 0, 9U * h->gcl_cap * sizeof(float), h->stream));
+        h->gcl = *config;
+        h->gcl_t = h->gcl_cost_t = 0;
+        for (bool &set : h->gcl_set)
+            set = false;
+        h->gcl_learner_ok = false;
+        h->gcl_bank_rows  = 0;
+        h->gcl_ok         = true;
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_num_params(okenv_t h, int32_t which, int32_t *num_params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->gcl_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_num_params: call okenv_gcl_create first");
+        if (which < OKENV_GCL_POLICY || which > OKENV_GCL_COST)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_num_params: unknown network (OKENV_GCL_POLICY / _VALUE / _COST)");
+        if (num_params)
+            *num_params = gclNumParams(h, which);
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_set_params(okenv_t h, int32_t which, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->gcl_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_set_params: call okenv_gcl_create first");
+        if (!params || which < OKENV_GCL_POLICY || which > OKENV_GCL_COST)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_set_params: NULL argument or unknown network");
+        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = copyAny(h, gclVector(h, which, 0), params, sizeof(float) * static_cast<size_t>(gclNumParams(h, which))))
+            return rc;
+        h->gcl_set[which] = true;
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_get_state(okenv_t h, int32_t which, okenv_gcl_state *out)
+    {
+        OK_QUIESCE(h);
+        if (!h || !out || which < OKENV_GCL_POLICY || which > OKENV_GCL_COST)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_get_state: NULL argument or unknown network");
+        if (!h->gcl_ok || !h->gcl_set[which])
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_get_state: the network needs its parameters first (okenv_gcl_create, okenv_gcl_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t bytes  = sizeof(float) * static_cast<size_t>(gclNumParams(h, which));
+        float *const dst[3] = {out->params, out->m, out->v};
+        for (int k = 0; k < 3; ++k)
+            if (dst[k] != nullptr)
+                if (const int rc = copyAny(h, dst[k], gclVector(h, which, k), bytes))
+                    return rc;
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        out->t = which == OKENV_GCL_COST ? h->gcl_cost_t : h->gcl_t;
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_get_params(okenv_t h, int32_t which, float *params)
+    {
+        OK_QUIESCE(h);
+        if (!params)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_get_params: NULL argument");
+        okenv_gcl_state st{params, nullptr, nullptr, 0};
+        return okenv_gcl_get_state(h, which, &st);
+    }
+
+    int okenv_gcl_set_draw_offset(okenv_t h, const uint32_t *device_word)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->gcl_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_set_draw_offset: call okenv_gcl_create first");
+        h->gcl_draw_offset = device_word;
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_set_greedy(okenv_t h, int32_t greedy)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->gcl_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_set_greedy: call okenv_gcl_create first");
+        if (greedy != 0 && greedy != 1)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_set_greedy: greedy must be 0 or 1");
+        h->gcl.greedy = greedy;
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_act(okenv_t h, const okenv_gcl_record *rec)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_act: NULL handle");
+        if (!h->gcl_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_act: call okenv_gcl_create first");
+        if (!h->gcl_set[OKENV_GCL_POLICY])
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_act: call okenv_gcl_set_params first (the policy needs its parameters)");
+        dropEpisode(h);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkGclActParams p{};
+        p.f      = actFrame(h);
+        p.draw   = actDrawWords(h, h->gcl_draw_offset);
+        p.H1     = h->gcl.hidden1;
+        p.H2     = h->gcl.hidden2;
+        p.params = gclVector(h, OKENV_GCL_POLICY, 0);
+        for (int k = 0; k < 2; ++k)
+        {
+            p.scale[k] = h->gcl.scale[k];
+            p.bias[k]  = h->gcl.bias[k];
+        }
+        p.greedy     = h->gcl.greedy;
+        p.seed       = h->gcl.seed;
+        p.agent_base = h->gcl.agent_base;
+        if (rec != nullptr)
+            p.rec = *rec;
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
+        hipLaunchKernelGGL(okGclActKernel, dim3(blocks), dim3(kActorThreads), okGaussActLdsBytes(p.f.R, p.H1, p.H2), h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_set_expert(okenv_t h, const float *state, const float *action, int32_t E)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->gcl_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_set_expert: call okenv_gcl_create first");
+        if (!state || !action || E < 1)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_set_expert: NULL argument or an empty bank");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t R = static_cast<size_t>(h->shape.R), rows = static_cast<size_t>(E);
+        if (E > h->gcl_bank_cap)
+        {
+            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still reading the old one
+            if (h->d_gcl_bank != nullptr)
+            {
+                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_gcl_bank)), h->allocations.end());
+                (void)hipFree(h->d_gcl_bank);
+                h->d_gcl_bank   = nullptr;
+                h->gcl_bank_cap = h->gcl_bank_rows = 0;
+            }
+            if (const int rc = devAlloc(h, &h->d_gcl_bank, rows * (R + 2U)))
+                return rc;
+            h->gcl_bank_cap = E;
+        }
+        if (const int rc = copyAny(h, h->d_gcl_bank, state, sizeof(float) * rows * R))
+            return rc;
+        if (const int rc = copyAny(h, h->d_gcl_bank + rows * R, action, sizeof(float) * rows * 2U))
+            return rc;
+        h->gcl_bank_rows = E;
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_cost(okenv_t h, const float *state, const float *squashed, int32_t M, float *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_cost: NULL handle");
+        if (!h->gcl_ok || !h->gcl_set[OKENV_GCL_COST])
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_cost: the cost network needs its parameters first (okenv_gcl_create, okenv_gcl_set_params)");
+        if (!state || !squashed || !out || M < 1)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_cost: NULL argument or M < 1");
+        OK_HIP(h, hipSetDevice(h->device));
+        OkGclForwardParams p{};
+        p.R        = h->shape.R;
+        p.in       = p.R + 2;
+        p.H1       = h->gcl.cost_hidden1;
+        p.H2       = h->gcl.cost_hidden2;
+        p.M        = M;
+        p.state    = state;
+        p.squashed = squashed;
+        p.params   = gclVector(h, OKENV_GCL_COST, 0);
+        p.out      = out;
+        p.C        = (M + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+        hipLaunchKernelGGL(okGclForwardKernel<true>, dim3(static_cast<unsigned>(p.C)), dim3(kLearnThreads), okGclForwardLdsBytes(p.in, p.H1, p.H2), h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_learner_create(okenv_t h, const okenv_learner_params *policy_value, const okenv_learner_params *cost)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_learner_create: NULL handle");
+        for (const okenv_learner_params *lp : {policy_value, cost})
+            if (const char *why = okLearnCheckParams(lp))
+                return fail(h, OKENV_ERR_INVALID, std::string("okenv_gcl_learner_create: ") + why);
+        if (!h->gcl_ok || !h->gcl_set[0] || !h->gcl_set[1] || !h->gcl_set[2])
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_learner_create: needs a GCL object whose three networks have their parameters (okenv_gcl_create, okenv_gcl_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        for (int which = 0; which < 3; ++which)
+            OK_HIP(h, hipMemsetAsync(gclVector(h, which, 1), 0, 2U * h->gcl_cap * sizeof(float), h->stream));
+        h->gcl_learner      = *policy_value;
+        h->gcl_cost_learner = *cost;
+        h->gcl_t = h->gcl_cost_t = 0;
+        h->gcl_learner_ok        = true;
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_cost_update(okenv_t h, const okenv_gcl_cost_batch *batch, int32_t Mp, int32_t Me, const okenv_gcl_cost_output *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_cost_update: NULL handle");
+        if (!h->gcl_ok || !h->gcl_learner_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_cost_update: call okenv_gcl_learner_create first");
+        if (h->gcl_bank_rows < 1)
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_cost_update: call okenv_gcl_set_expert first (the bank is empty)");
+        if (const char *why = okGclCheckCostCall(batch, Mp, Me))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_gcl_cost_update: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkUpdateScratch &u = h->gcl_scratch[OKENV_GCL_COST];
+        OkGclGradParams  p{};
+        p.R           = h->shape.R;
+        p.in          = p.R + 2;
+        p.H1          = h->gcl.cost_hidden1;
+        p.H2          = h->gcl.cost_hidden2;
+        p.Bk          = Mp;
+        p.P           = gclNumParams(h, OKENV_GCL_COST);
+        p.cols        = p.P + 1;
+        p.state       = batch->state;
+        p.squashed    = batch->squashed;
+        p.bank_state  = h->d_gcl_bank;
+        p.bank_action = h->d_gcl_bank + static_cast<size_t>(h->gcl_bank_rows) * static_cast<size_t>(p.R);
+        p.E           = h->gcl_bank_rows;
+        p.Me          = Me;
+        p.Ce          = (Me + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+        p.seed        = h->gcl.seed;
+        p.draw        = static_cast<uint32_t>(h->gcl_cost_t);
+        p.params      = gclVector(h, OKENV_GCL_COST, 0);
+        const int Cp  = (Mp + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+        if (const int rc = growScratch(h, u, sizeof(float) * static_cast<size_t>(p.Ce + Cp) * static_cast<size_t>(p.cols)))
+            return rc;
+        p.part = reinterpret_cast<float *>(u.part);
+        if (const int rc = eventsBegin(h, u.log, 2U))
+            return rc;
+        hipLaunchKernelGGL(okGclGradKernel<OK_GCL_COST>, dim3(static_cast<unsigned>(p.Ce + Cp)), dim3(kLearnThreads), okGclGradLdsBytes(p.in, p.H1, p.H2, 1),
+                           h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        if (const int rc = eventsMark(h, u.log))
+            return rc;
+        OkGclCostJoinParams j{};
+        j.P      = p.P;
+        j.cols   = p.cols;
+        j.Ce     = p.Ce;
+        j.Cp     = Cp;
+        j.part   = p.part;
+        j.me     = static_cast<float>(Me);
+        j.mp     = static_cast<float>(Mp);
+        j.params = gclVector(h, OKENV_GCL_COST, 0);
+        j.m      = gclVector(h, OKENV_GCL_COST, 1);
+        j.v      = gclVector(h, OKENV_GCL_COST, 2);
+        j.adam   = okLearnAdamConsts(h->gcl_cost_learner, h->gcl_cost_t + 1);
+        j.loss   = out != nullptr ? out->loss : nullptr;
+        j.grad   = out != nullptr ? out->grad : nullptr;
+        hipLaunchKernelGGL(okGclCostStepKernel, dim3(static_cast<unsigned>((j.cols + kLearnStepCols - 1) / kLearnStepCols)), dim3(kLearnStepCols * kLearnStepRows), 0,
+                           h->stream, j);
+        OK_HIP(h, hipGetLastError());
+        h->gcl_cost_t += 1;
+        return eventsMark(h, u.log);
+    }
+
+    int okenv_gcl_policy_update(okenv_t h, const okenv_gcl_update_config *config, const okenv_gcl_batch *batch, int32_t M, int32_t B, const int32_t *order,
+                                const okenv_gcl_output *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_policy_update: NULL handle");
+        if (!h->gcl_ok || !h->gcl_learner_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_gcl_policy_update: call okenv_gcl_learner_create first");
+        if (const char *why = okGclCheckCall(config, batch, M, B))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_gcl_policy_update: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        const okenv_gcl_output  none{};
+        const okenv_gcl_output &o = out != nullptr ? *out : none;
+        const bool              accumulate = config->accumulate != 0;
+        const int               R = h->shape.R, H1 = h->gcl.hidden1, H2 = h->gcl.hidden2;
+        // the advantages' scratch: [S, Q partials | adv | mean, std | the policy chunks' clip counts], each piece 256-aligned
+        const auto   up    = [](const size_t b) { return (b + 255U) & ~static_cast<size_t>(255U); };
+        const int    Cm    = (M + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
+        const size_t c_max = (static_cast<size_t>(std::min(B, M)) + OK_LEARN_CHUNK - 1U) / OK_LEARN_CHUNK;
+        const size_t stat_bytes = up(sizeof(double) * 2U * static_cast<size_t>(Cm)), adv_bytes = up(sizeof(float) * static_cast<size_t>(M));
+        if (const int rc = growScratch(h, h->gcl_adv_scratch, stat_bytes + adv_bytes + 256U + up(sizeof(uint32_t) * c_max)))
+            return rc;
+        double   *stat = reinterpret_cast<double *>(h->gcl_adv_scratch.part);
+        float    *adv = reinterpret_cast<float *>(h->gcl_adv_scratch.part + stat_bytes), *ms = reinterpret_cast<float *>(h->gcl_adv_scratch.part + stat_bytes + adv_bytes);
+        uint32_t *part_clip = reinterpret_cast<uint32_t *>(h->gcl_adv_scratch.part + stat_bytes + adv_bytes + 256U);
+        // the value sweep with the parameters the call starts with, the statistics, the normalisation
+        OkGclForwardParams f{};
+        f.R      = R;
+        f.in     = R;
+        f.H1     = H1;
+        f.H2     = H2;
+        f.M      = M;
+        f.state  = batch->state;
+        f.ret    = batch->ret;
+        f.params = gclVector(h, OKENV_GCL_VALUE, 0);
+        f.out    = adv;
+        f.stat   = stat;
+        f.C      = Cm;
+        hipLaunchKernelGGL(okGclForwardKernel<false>, dim3(static_cast<unsigned>(Cm)), dim3(kLearnThreads), okGclForwardLdsBytes(R, H1, H2), h->stream, f);
+        OK_HIP(h, hipGetLastError());
+        hipLaunchKernelGGL(okGclAdvStatsKernel, dim3(1), dim3(kGclStatsThreads), 0, h->stream, stat, Cm, M, ms);
+        OK_HIP(h, hipGetLastError());
+        hipLaunchKernelGGL(okGclAdvNormKernel, dim3(static_cast<unsigned>((M + 255) / 256)), dim3(256), 0, h->stream, adv, ms, M, o.adv);
+        OK_HIP(h, hipGetLastError());
+        if (o.clipped != nullptr)
+            OK_HIP(h, hipMemsetAsync(o.clipped, 0, sizeof(int32_t) * static_cast<size_t>(accumulate ? 1 : okLearnMinibatches(M, B)), h->stream));
+        OkGclGradParams p{};
+        p.R     = R;
+        p.in    = R;
+        p.H1    = H1;
+        p.H2    = H2;
+        p.M     = M;
+        p.order = order;
+        p.state = batch->state;
+        p.pre   = batch->pre;
+        p.logp  = batch->logp;
+        p.ret   = batch->ret;
+        p.adv   = adv;
+        p.lo    = okLearnClipLo(h->gcl_learner.clip);
+        p.hi    = okLearnClipHi(h->gcl_learner.clip);
+        // the policy's slices, then the value's: the join kernels are section 19's, on either parameter vector; both count the same steps
+        int64_t t_policy = h->gcl_t, t_value = h->gcl_t;
+        p.P         = gclNumParams(h, OKENV_GCL_POLICY);
+        p.cols      = p.P + 1;
+        p.params    = gclVector(h, OKENV_GCL_POLICY, 0);
+        p.part_clip = o.clipped != nullptr ? part_clip : nullptr;
+        if (const int rc = sliceUpdate(h, h->gcl_scratch[OKENV_GCL_POLICY], M, B, accumulate,
+                                       okJoinOn(p.P, gclVector(h, OKENV_GCL_POLICY, 0), gclVector(h, OKENV_GCL_POLICY, 1), gclVector(h, OKENV_GCL_POLICY, 2), config->reduce,
+                                                o.grad_policy),
+                                       t_policy, h->gcl_learner, o.policy_loss,
+                                       [&](const long base, const int Bk, const int C)
+                                       {
+                                           p.base = base;
+                                           p.Bk   = Bk;
+                                           p.part = reinterpret_cast<float *>(h->gcl_scratch[OKENV_GCL_POLICY].part);
+                                           hipLaunchKernelGGL(okGclGradKernel<OK_GCL_POLICY>, dim3(static_cast<unsigned>(C)), dim3(kLearnThreads),
+                                                              okGclGradLdsBytes(R, H1, H2, 2), h->stream, p);
+                                           if (o.clipped != nullptr)
+                                               hipLaunchKernelGGL(okGclClipCountKernel, dim3(1), dim3(256), 0, h->stream, part_clip, C, o.clipped + (accumulate ? 0 : base / B));
+                                       }))
+            return rc;
+        p.P         = gclNumParams(h, OKENV_GCL_VALUE);
+        p.cols      = p.P + 1;
+        p.params    = gclVector(h, OKENV_GCL_VALUE, 0);
+        p.part_clip = nullptr;
+        if (const int rc = sliceUpdate(h, h->gcl_scratch[OKENV_GCL_VALUE], M, B, accumulate,
+                                       okJoinOn(p.P, gclVector(h, OKENV_GCL_VALUE, 0), gclVector(h, OKENV_GCL_VALUE, 1), gclVector(h, OKENV_GCL_VALUE, 2), config->reduce,
+                                                o.grad_value),
+                                       t_value, h->gcl_learner, o.value_loss,
+                                       [&](const long base, const int Bk, const int C)
+                                       {
+                                           p.base = base;
+                                           p.Bk   = Bk;
+                                           p.part = reinterpret_cast<float *>(h->gcl_scratch[OKENV_GCL_VALUE].part);
+                                           hipLaunchKernelGGL(okGclGradKernel<OK_GCL_VALUE>, dim3(static_cast<unsigned>(C)), dim3(kLearnThreads),
+                                                              okGclGradLdsBytes(R, H1, H2, 1), h->stream, p);
+                                       }))
+            return rc;
+        h->gcl_t = t_policy;
+        return OKENV_OK;
+    }
+
+    int okenv_debug_gcl_timing(okenv_t h, int32_t which, double *ms2)
+    {
+        OK_QUIESCE(h);
+        if (!h || !ms2 || which < OKENV_GCL_POLICY || which > OKENV_GCL_COST)
+            return fail(h, OKENV_ERR_INVALID, "okenv_debug_gcl_timing: NULL argument or unknown network");
+        if (h->gcl_scratch[which].log.timed < 3U)
+            return fail(h, OKENV_ERR_STATE, "okenv_debug_gcl_timing: no update of this network has run with okenv_set_timing on");
+        return eventsSums(h, h->gcl_scratch[which].log, ms2, 2);
+    }
+
+    int okenv_gcl_act_host(const okenv_gcl_config *config, const float *policy, int32_t num_rays, int32_t n, const float *rel_x, const float *rel_y,
+                           const uint8_t *crashed, uint32_t draw_index, float *throttle, float *steer, float *eps, float *pre, float *squashed, float *action,
+                           float *logp, float *state, uint8_t *alive)
+    {
+        if (const char *why = okGclCheckConfig(config, num_rays))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gcl_act_host: ") + why);
+        if (!policy || n < 0 || !rel_x || !rel_y)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_gcl_act_host: bad argument");
+        okGclActHost(*config, policy, num_rays, n, rel_x, rel_y, crashed, draw_index, throttle, steer, eps, pre, squashed, action, logp, state, alive);
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_cost_host(const float *cost, int32_t num_rays, int32_t cost_hidden1, int32_t cost_hidden2, const float *state, const float *squashed,
+                            int32_t M, float *out)
+    {
+        if (const char *why = okGclCheckShape(num_rays, 1, 1, cost_hidden1, cost_hidden2))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gcl_cost_host: ") + why);
+        if (!cost || !state || !squashed || !out || M < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_gcl_cost_host: bad argument");
+        okGclForwardHost(okGclHostNet(OK_GCL_COST, num_rays, cost_hidden1, cost_hidden2, cost), num_rays, state, squashed, M, out);
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_cost_update_host(const okenv_learner_params *params, uint32_t seed, int32_t num_rays, int32_t cost_hidden1, int32_t cost_hidden2,
+                                   okenv_gcl_state *state, const float *bank_state, const float *bank_action, int32_t E, const okenv_gcl_cost_batch *batch,
+                                   int32_t Mp, int32_t Me, const okenv_gcl_cost_output *out)
+    {
+        if (const char *why = okLearnCheckParams(params))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gcl_cost_update_host: ") + why);
+        if (const char *why = okGclCheckShape(num_rays, 1, 1, cost_hidden1, cost_hidden2))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gcl_cost_update_host: ") + why);
+        if (const char *why = okGclCheckCostCall(batch, Mp, Me))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gcl_cost_update_host: ") + why);
+        if (!bank_state || !bank_action || E < 1)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_gcl_cost_update_host: the expert bank is NULL or empty");
+        if (!okGclStateComplete(state))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_gcl_cost_update_host: state lacks a parameter or moment vector, or t < 0");
+        const okenv_gcl_cost_output none{};
+        okGclCostUpdateHost(*params, seed, num_rays, cost_hidden1, cost_hidden2, *state, bank_state, bank_action, E, *batch, Mp, Me, out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    int okenv_gcl_policy_update_host(const okenv_learner_params *params, const okenv_gcl_update_config *config, int32_t num_rays, int32_t hidden1,
+                                     int32_t hidden2, okenv_gcl_state *policy, okenv_gcl_state *value, const okenv_gcl_batch *batch, int32_t M, int32_t B,
+                                     const int32_t *order, const okenv_gcl_output *out)
+    {
+        if (const char *why = okLearnCheckParams(params))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gcl_policy_update_host: ") + why);
+        if (const char *why = okGclCheckShape(num_rays, hidden1, hidden2, 1, 1))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gcl_policy_update_host: ") + why);
+        if (const char *why = okGclCheckCall(config, batch, M, B))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_gcl_policy_update_host: ") + why);
+        if (!okGclStateComplete(policy) || !okGclStateComplete(value))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_gcl_policy_update_host: a state lacks a parameter or moment vector, or t < 0");
+        const okenv_gcl_output none{};
+        okGclPolicyUpdateHost(*params, *config, num_rays, hidden1, hidden2, *policy, *value, *batch, M, B, order, out != nullptr ? *out : none);
         return OKENV_OK;
     }
 

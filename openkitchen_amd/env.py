@@ -816,6 +816,98 @@ class BatchedEnvironment:
         """Device microseconds of the latest gauss_update that ran with set_timing(True), summed over its slices, by capi.GAUSS_KERNELS."""
         return self._timing("okenv_debug_gauss_timing", capi.GAUSS_KERNELS)
 
+    # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) -------------------------------------------------------
+    def gcl_create(self, **config):
+        """Attaches a GCL object (policy R -> H1 -> H2 -> 2 with log_std, value R -> H1 -> H2 -> 1, cost R + 2 -> C1 -> C2 -> 1) to the
+        handle; config: the members of okenv_gcl_config (capi.gcl_config lists them with the reference's defaults).  Returns the floats
+        of the three parameter vectors as a dict."""
+        cfg = capi.gcl_config(**config)
+        capi.check(self._L.okenv_gcl_create(self._h, C.byref(cfg)), self._h)
+        self.gcl_config = cfg
+        return {name: self.gcl_num_params(name) for name in capi.GCL_NETWORKS}
+
+    def gcl_num_params(self, which):
+        n = C.c_int32()
+        capi.check(self._L.okenv_gcl_num_params(self._h, _gcl_which(which), C.byref(n)), self._h)
+        return n.value
+
+    def gcl_set_params(self, which, params):
+        """New parameters of network `which` ("policy" / "value" / "cost"; torch's parameters() order, flattened) from a float32 numpy
+        array or a device tensor.  No synchronisation."""
+        if hasattr(params, "data_ptr"):
+            assert params.is_contiguous() and params.numel() == self.gcl_num_params(which)
+        else:
+            params = _flat_params(params, self.gcl_num_params(which))
+        capi.check(self._L.okenv_gcl_set_params(self._h, _gcl_which(which), capi.ptr(params)), self._h)
+
+    def gcl_state(self, which, out=None):
+        """Network `which`'s parameter vector, Adam's two moments ("params", "m", "v") and the int t: float32 numpy arrays, or copied
+        into the device tensors of the dict `out` (any subset).  Synchronises."""
+        if out is None:
+            out = {k: np.empty(self.gcl_num_params(which), dtype=np.float32) for k in ("params", "m", "v")}
+        st = capi.fill_pointers(capi.OkenvGclState(), out, "gcl state")
+        capi.check(self._L.okenv_gcl_get_state(self._h, _gcl_which(which), C.byref(st)), self._h)
+        return dict(out, t=int(st.t))
+
+    def gcl_set_draw_offset(self, word=None):
+        """A device uint32 word (tensor or address) added to the draw index of every later gcl_act; None removes it."""
+        capi.check(self._L.okenv_gcl_set_draw_offset(self._h, capi.ptr(word)), self._h)
+
+    def gcl_set_greedy(self, greedy):
+        capi.check(self._L.okenv_gcl_set_greedy(self._h, 1 if greedy else 0), self._h)
+
+    def gcl_act(self, record=None):
+        """The sampled (or greedy) action of every agent, enqueued on the handle's stream without a synchronisation.  record: None,
+        or a dict of device tensors / addresses under "state" [N,R], "eps", "pre", "squashed", "action" [N,2], "logp" [N] float32 and
+        "alive" [N] uint8, each optional."""
+        if record is None:
+            capi.check(self._L.okenv_gcl_act(self._h, None), self._h)
+            return
+        sizes = {"state": self.N * self.R * 4, "eps": self.N * 8, "pre": self.N * 8, "squashed": self.N * 8, "action": self.N * 8,
+                 "logp": self.N * 4, "alive": self.N}
+        rec = capi.fill_pointers(capi.OkenvGclRecord(), record, "record", sizes)
+        capi.check(self._L.okenv_gcl_act(self._h, C.byref(rec)), self._h)
+
+    def gcl_set_expert(self, state, action):
+        """The expert bank from device tensors state [E,R] and action [E,2] (float32, contiguous), copied on the handle's stream."""
+        E = int(state.shape[0])
+        assert state.is_contiguous() and action.is_contiguous() and state.numel() == E * self.R and action.numel() == E * 2
+        capi.check(self._L.okenv_gcl_set_expert(self._h, capi.ptr(state), capi.ptr(action), E), self._h)
+
+    def gcl_cost(self, state, squashed, out):
+        """out[s] = cost([state_s | squashed_s]) for the M rows of device tensors state [M,R], squashed [M,2]; out [M] float32."""
+        M = int(out.numel())
+        assert state.is_contiguous() and squashed.is_contiguous() and out.is_contiguous() and state.numel() == M * self.R and squashed.numel() == M * 2
+        capi.check(self._L.okenv_gcl_cost(self._h, capi.ptr(state), capi.ptr(squashed), M, capi.ptr(out)), self._h)
+
+    def gcl_learner_create(self, lr=3e-4, clip=0.2, cost_lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8):
+        """Adam for the three networks (the reference's learning rate and clip, GCLAgent.hpp:30-32,92): moments zeroed, t = 0."""
+        lp, lc = capi.learner_params(lr, clip, beta1, beta2, eps), capi.learner_params(cost_lr, 0.0, beta1, beta2, eps)
+        capi.check(self._L.okenv_gcl_learner_create(self._h, C.byref(lp), C.byref(lc)), self._h)
+
+    def gcl_cost_update(self, batch, Mp, Me, out=None):
+        """okenv_gcl_cost_update: one Adam step of the cost network on Me expert draws and the Mp policy rows of `batch` (device tensors
+        "state" [Mp,R], "squashed" [Mp,2]); out: None or a dict under "loss" [1] and "grad".  No synchronisation."""
+        cb = capi.fill_pointers(capi.OkenvGclCostBatch(), batch, "gcl cost batch")
+        co = capi.fill_pointers(capi.OkenvGclCostOutput(), out or {}, "gcl cost output")
+        capi.check(self._L.okenv_gcl_cost_update(self._h, C.byref(cb), int(Mp), int(Me), C.byref(co)), self._h)
+
+    def gcl_policy_update(self, batch, M, B, accumulate=True, reduce="mean", order=None, out=None):
+        """okenv_gcl_policy_update: the advantages, then the policy's and the value's slices on the handle's stream, no synchronisation.
+        batch: dict of device tensors "state" [M,R], "pre" [M,2], "logp" [M], "ret" [M], float32; order: None or a device int32 tensor
+        [M]; out: None or a dict under "policy_loss", "value_loss" (float32, one per optimiser step), "clipped" (int32 likewise),
+        "grad_policy", "grad_value" and "adv" [M]."""
+        cfg = capi.gcl_update_config(accumulate, reduce)
+        gb = capi.fill_pointers(capi.OkenvGclBatch(), batch, "gcl batch")
+        go = capi.fill_pointers(capi.OkenvGclOutput(), out or {}, "gcl output")
+        capi.check(self._L.okenv_gcl_policy_update(self._h, C.byref(cfg), C.byref(gb), int(M), int(B), capi.ptr(order), C.byref(go)), self._h)
+
+    def gcl_timing(self, which):
+        """Device microseconds of network `which`'s kernels in the latest update that ran with set_timing(True), by capi.GCL_KERNELS."""
+        out = (C.c_double * 2)()
+        capi.check(self._L.okenv_debug_gcl_timing(self._h, _gcl_which(which), out), self._h)
+        return {name: out[k] * 1e3 for k, name in enumerate(capi.GCL_KERNELS)}
+
     # ---- measurement / self-checks ------------------------------------------------------------------
     def work_stats(self):
         """{rays, tests, cells, points} the broad phase leaves for the current poses (okenv_work_stats)."""
@@ -1289,3 +1381,91 @@ def gauss_update_host(params, shape, state, batch, B, accumulate=True, reduce="s
         C.byref(capi.fill_pointers(capi.OkenvGaussOutput(), {k: v for k, v in outs.items() if v.size}, "gauss output"))))
     new["t"] = int(st.t)
     return new, outs
+
+
+def _gcl_which(which):
+    return capi.GCL_NETWORKS[which] if isinstance(which, str) else int(which)
+
+
+def gcl_act_host(config, policy, rel_xy, crashed=None, draw_index=0):
+    """Guided cost learning's action on host arrays, no GPU needed (okenv_gcl_act_host).  config: capi.gcl_config(...); policy: the
+    flattened float32 parameter vector; rel_xy [n, R, 2]: the hits relative to the agent.  Returns a dict: throttle, steer [n], eps, pre,
+    squashed, action [n, 2], logp [n], state [n, R] float32 and alive [n] uint8 (eps stays NaN when acting greedily)."""
+    rel_xy = np.asarray(rel_xy, dtype=np.float32)
+    n, R = rel_xy.shape[:2]
+    rel_x, rel_y = np.ascontiguousarray(rel_xy[..., 0]), np.ascontiguousarray(rel_xy[..., 1])
+    policy = None if policy is None else np.ascontiguousarray(policy, dtype=np.float32).ravel()
+    if config is not None and policy is not None:
+        assert policy.size == capi.gcl_num_params("policy", R, config.hidden1, config.hidden2)
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, dtype=np.uint8)
+    out = {"throttle": np.zeros(n, np.float32), "steer": np.zeros(n, np.float32), "eps": np.full((n, 2), np.nan, np.float32),
+           "pre": np.zeros((n, 2), np.float32), "squashed": np.zeros((n, 2), np.float32), "action": np.zeros((n, 2), np.float32),
+           "logp": np.zeros(n, np.float32), "state": np.zeros((n, R), np.float32), "alive": np.zeros(n, np.uint8)}
+    capi.check(capi.load().okenv_gcl_act_host(C.byref(config) if config is not None else None, capi.ptr(policy), R, n, capi.ptr(rel_x), capi.ptr(rel_y),
+                                              capi.ptr(crashed), int(draw_index) & 0xFFFFFFFF, capi.ptr(out["throttle"]), capi.ptr(out["steer"]),
+                                              capi.ptr(out["eps"]), capi.ptr(out["pre"]), capi.ptr(out["squashed"]), capi.ptr(out["action"]),
+                                              capi.ptr(out["logp"]), capi.ptr(out["state"]), capi.ptr(out["alive"])))
+    return out
+
+
+def gcl_cost_host(cost, shape, state, squashed):
+    """The cost of M rows on host arrays (okenv_gcl_cost_host).  shape: (R, C1, C2); state [M, R], squashed [M, 2].  Returns [M]."""
+    R, C1, C2 = (int(v) for v in shape)
+    state, squashed = np.ascontiguousarray(state, dtype=np.float32), np.ascontiguousarray(squashed, dtype=np.float32)
+    out = np.zeros(state.shape[0], np.float32)
+    cost = None if cost is None else np.ascontiguousarray(cost, dtype=np.float32).ravel()
+    capi.check(capi.load().okenv_gcl_cost_host(capi.ptr(cost), R, C1, C2, capi.ptr(state), capi.ptr(squashed), out.size, capi.ptr(out)))
+    return out
+
+
+def _gcl_host_state(state):
+    new = {k: np.array(v, dtype=np.float32, copy=True).ravel() for k, v in state.items() if k != "t" and v is not None}
+    st = capi.fill_pointers(capi.OkenvGclState(), new, "gcl state")
+    st.t = int(state.get("t", 0))
+    return new, st
+
+
+def gcl_cost_update_host(params, seed, shape, state, bank, batch, Me, want=("loss", "grad")):
+    """One step of the cost network on host arrays (okenv_gcl_cost_update_host).  params: capi.learner_params(...); shape: (R, C1, C2);
+    state: dict "params", "m", "v", "t" (copied; the new state is returned); bank: dict "state" [E, R], "action" [E, 2]; batch: dict
+    "state" [Mp, R], "squashed" [Mp, 2].  Returns (new state, outputs)."""
+    R, C1, C2 = (int(v) for v in shape)
+    new, st = _gcl_host_state(state)
+    bs = None if bank.get("state") is None else np.ascontiguousarray(bank["state"], dtype=np.float32)
+    ba = None if bank.get("action") is None else np.ascontiguousarray(bank["action"], dtype=np.float32)
+    E = 0 if bs is None else bs.shape[0]
+    b = {k: np.ascontiguousarray(batch[k], dtype=np.float32) for k in ("state", "squashed") if batch.get(k) is not None}
+    Mp = int(np.asarray(batch["squashed"]).shape[0]) if batch.get("squashed") is not None else int(np.asarray(batch["state"]).shape[0])
+    sizes = {"loss": 1, "grad": capi.gcl_num_params("cost", R, C1, C2)}
+    outs = {k: np.zeros(sizes[k], dtype=np.float32) for k in want}
+    capi.check(capi.load().okenv_gcl_cost_update_host(
+        C.byref(params) if params is not None else None, int(seed) & 0xFFFFFFFF, R, C1, C2, C.byref(st), capi.ptr(bs), capi.ptr(ba), E,
+        C.byref(capi.fill_pointers(capi.OkenvGclCostBatch(), b, "gcl cost batch")), Mp, int(Me),
+        C.byref(capi.fill_pointers(capi.OkenvGclCostOutput(), outs, "gcl cost output"))))
+    new["t"] = int(st.t)
+    return new, outs
+
+
+def gcl_policy_update_host(params, shape, policy, value, batch, B, accumulate=True, reduce="mean", order=None,
+                           want=("policy_loss", "value_loss", "clipped", "grad_policy", "grad_value", "adv")):
+    """The policy / value update on host arrays (okenv_gcl_policy_update_host).  params: capi.learner_params(...); shape: (R, H1, H2);
+    policy, value: dicts "params", "m", "v" (and "t" in policy), copied; batch: dict "state" [M, R], "pre" [M, 2], "logp" [M], "ret" [M];
+    order: None or int32 [M].  Returns (new policy state, new value state, outputs)."""
+    R, H1, H2 = (int(v) for v in shape)
+    M = int(np.asarray(batch["ret"]).shape[0])
+    b = {k: np.ascontiguousarray(batch[k], dtype=np.float32) for k in ("state", "pre", "logp", "ret") if batch.get(k) is not None}
+    newp, sp = _gcl_host_state(policy)
+    newv, sv = _gcl_host_state(dict(value, t=policy.get("t", 0)))
+    steps = (1 if accumulate else (M + int(B) - 1) // int(B)) if M > 0 and B > 0 else 0
+    sizes = {"policy_loss": steps, "value_loss": steps, "clipped": steps, "grad_policy": capi.gcl_num_params("policy", R, H1, H2),
+             "grad_value": capi.gcl_num_params("value", R, H1, H2), "adv": M}
+    outs = {k: np.zeros(sizes[k], dtype=np.int32 if k == "clipped" else np.float32) for k in want}
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.int32)
+    cfg = capi.gcl_update_config(accumulate, reduce) if reduce is not None else None
+    capi.check(capi.load().okenv_gcl_policy_update_host(
+        C.byref(params) if params is not None else None, C.byref(cfg) if cfg is not None else None, R, H1, H2, C.byref(sp), C.byref(sv),
+        C.byref(capi.fill_pointers(capi.OkenvGclBatch(), b, "gcl batch")), M, int(B), capi.ptr(order),
+        C.byref(capi.fill_pointers(capi.OkenvGclOutput(), {k: v for k, v in outs.items() if v.size}, "gcl output"))))
+    newp["t"] = newv["t"] = int(sp.t)
+    return newp, newv, outs

@@ -598,6 +598,132 @@ def reinforce_continuous_update(venv, batch, slice=16384, accumulate=True, reduc
     return out
 
 
+# ---- guided cost learning --------------------------------------------------------------------------------
+
+def gcl_expert_rows(demonstrations):
+    """The expert bank's rows from the dict demonstrations.collect_demonstrations returns (ReadExpertData.hpp:98,111), alive rows only:
+    state [E, R] = (rel_x^2 + rel_y^2) / 200^2 and action [E, 2] = (((throttle / 100) - 0.5) * 2, steering / 10).  Every operation is
+    one torch kernel and the divisions are tensor by tensor, so the state is the device actor's own, bit for bit (torch divides a tensor
+    by a Python number as a multiplication by the reciprocal)."""
+    rel, actions, alive = demonstrations["rel_xy"].float(), demonstrations["actions"].float(), demonstrations["alive"]
+    keep = (alive != 0).reshape(-1)
+    rel = rel.reshape(-1, rel.shape[-2], 2)[keep]
+    actions = actions.reshape(-1, 2)[keep]
+    xx, yy = rel[..., 0] * rel[..., 0], rel[..., 1] * rel[..., 1]
+    total = xx + yy
+    state = total / torch.full_like(total, 40000.0)
+    thr = actions[:, 0] / torch.full_like(actions[:, 0], 100.0)
+    thr = (thr - 0.5) * 2.0
+    steer = actions[:, 1] / torch.full_like(actions[:, 1], 10.0)
+    return state.contiguous(), torch.stack([thr, steer], dim=1).contiguous()
+
+
+def _gcl_fields(venv):
+    pair = ((2,), torch.float32)
+    return {"state": ((venv.num_rays,), torch.float32), "eps": pair, "pre": pair, "squashed": pair, "action": pair, "logp": ((), torch.float32),
+            "alive": ((), torch.bool)}
+
+
+def _gcl_act_step_record(venv, slot):
+    """One iteration of collect_episode_gcl into the row `slot`: gcl_act -> step.  The reward is the cost network's (gcl_rewards)."""
+    venv.gcl_act(slot)
+    venv.step()
+
+
+def collect_episode_gcl(venv, max_steps, check_every=8, graph_chunk=0):
+    """A rollout of `max_steps` steps of the reference's guided-cost-learning agent (GCLAgent.hpp:102-135, main.cpp:84-112) with the
+    acting on the device: `gcl_act -> step` for the policy given to venv.enable_gcl, eagerly or, with graph_chunk = K > 0, as a replayed
+    HIP graph of K iterations (then max_steps is rounded up to a multiple of K and trimmed afterwards).  Auto-reset must be on: the
+    reference re-places a crashed agent and goes on, and a row recorded while an agent stands crashed is marked dead.  Returns a dict of
+    device tensors: states [T, N, R], eps, pre, squashed, actions [T, N, 2], log_probs [T, N], alive [T, N] bool."""
+    assert venv.auto_reset, "create the VectorEnvironment with auto_reset=True: the reference re-places crashed agents and goes on"
+    assert getattr(venv, "_gcl_nets", None) is not None, "call venv.enable_gcl(policy, value, cost) first"
+    K = int(graph_chunk)
+    block = max_steps if K <= 0 else K * ((max_steps + K - 1) // K)
+    buf = _EpisodeBuffers(venv, block, False, _gcl_fields(venv))
+
+    def build():
+        chunk = _EpisodeBuffers(venv, K, False, _gcl_fields(venv)).rows(0, K)
+        return (lambda k: _gcl_act_step_record(venv, {name: t[k] for name, t in chunk.items()})), chunk
+
+    def copy_rows(steps, chunk):
+        for name, dst in buf.rows(steps, K).items():
+            dst.copy_(chunk[name])
+
+    captured = _Chunk(K=K, graphs=venv._gcl_graphs, key=K, set_draw_offset=venv.env.gcl_set_draw_offset, build=build, after_replay=copy_rows)
+    _, steps = _run_episode(venv, lambda t: _gcl_act_step_record(venv, buf.slot(t)), max_steps, check_every, captured)
+    out = buf.finish(steps)
+    T = min(steps, max_steps)
+    return {"states": out["state"][:T], "eps": out["eps"][:T], "pre": out["pre"][:T], "squashed": out["squashed"][:T], "actions": out["action"][:T],
+            "log_probs": out["logp"][:T], "alive": out["alive"][:T]}
+
+
+def gcl_rewards(venv, ep):
+    """rewards [T, N] = -cost(state, squashed action) of every row of the dict collect_episode_gcl returns, with the device's cost
+    network as it stands (okenv_gcl_cost): one kernel, no synchronisation."""
+    T, N = ep["alive"].shape
+    states, squashed = ep["states"].reshape(T * N, -1).contiguous(), ep["squashed"].reshape(T * N, 2).contiguous()
+    cost = torch.empty(T * N, dtype=torch.float32, device=states.device)
+    venv.env.gcl_cost(states, squashed, cost)
+    venv._gcl_cost_inputs = (states, squashed)  # alive until the next call: the kernel is only enqueued
+    return (-cost).reshape(T, N)
+
+
+def gcl_cost_update(venv, ep, expert_samples=None, grads=False):
+    """One step of the cost network on the device (okenv_gcl_cost_update, main.cpp:150-176): BCEWithLogits(c_expert, 0) +
+    BCEWithLogits(c_policy, 1), the policy samples being the alive rows of the dict collect_episode_gcl returns and the expert samples
+    `expert_samples` uniform draws with replacement from the bank (default: as many as policy samples).  The call reads the number of
+    alive rows (one synchronisation).  Returns a dict of device tensors: loss [1] and, with grads=True, grad."""
+    assert getattr(venv, "gcl_learner_enabled", False), "call venv.enable_gcl_learner() first"
+    keep = ep["alive"].reshape(-1)
+    data = {"state": ep["states"].reshape(keep.numel(), -1)[keep].contiguous(), "squashed": ep["squashed"].reshape(-1, 2)[keep].contiguous()}
+    Mp = int(data["state"].shape[0])
+    out = {"loss": torch.empty(1, dtype=torch.float32, device=keep.device)}
+    if grads:
+        out["grad"] = torch.empty(venv.env.gcl_num_params("cost"), dtype=torch.float32, device=keep.device)
+    venv.env.gcl_cost_update(data, Mp, Mp if expert_samples is None else int(expert_samples), out)
+    venv._gcl_cost_update_inputs = data  # alive until the next update: the kernels are only enqueued
+    return out
+
+
+def prepare_gcl_batch(venv, ep, rewards, gamma=0.99):
+    """From the dict collect_episode_gcl returns and its rewards [T, N] to the policy / value update's batch: prepare_batch without a
+    value plane and without normalisation (discounted returns per agent, a dead row an episode boundary, the alive samples packed in
+    step-major order; the recorded log-probabilities ride in its probability plane), then pre gathered by the samples' flat indices.
+    Returns a dict of device tensors: states [M, R], pre [M, 2], log_probs [M], returns [M], index [M] i32, count and stats."""
+    T, N = rewards.shape
+    plain = {"states": ep["states"], "actions": torch.zeros((T, N), dtype=torch.int64, device=rewards.device), "log_probs": ep["log_probs"],
+             "rewards": rewards, "alive": ep["alive"]}
+    batch = prepare_batch(venv, plain, gamma=gamma, lam=None, normalize=False)
+    return {"states": batch["states"], "pre": ep["pre"].reshape(-1, 2)[batch["index"].long()].contiguous(), "log_probs": batch["log_probs"],
+            "returns": batch["returns"], "index": batch["index"], "count": batch["count"], "stats": batch["stats"]}
+
+
+def gcl_policy_update(venv, batch, slice=16384, accumulate=True, reduce="mean", shuffle=False, grads=False):
+    """updatePolicy of RLRacers/GuidedCostLearning on the device (okenv_gcl_policy_update, GCLAgent.hpp:146-177) for the dict
+    prepare_gcl_batch returns: advantages returns - V(state), normalised over the batch; the clipped surrogate on the ratio of the
+    recomputed to the recorded log-probability of the recorded pre-squash sample; the value network's squared error; one Adam step on
+    each, in place in the parameters the device acts with (venv.pull_gcl() brings them back to the modules).  slice, accumulate, reduce
+    and shuffle are reinforce_update's; the reference is one step on the mean.  Everything is enqueued on the environment's stream.
+    Returns a dict of device tensors: policy_loss, value_loss (float32), clipped (int32), one per optimiser step, adv [M] and, with
+    grads=True, grad_policy and grad_value of the last step."""
+    assert getattr(venv, "gcl_learner_enabled", False), "call venv.enable_gcl_learner() first"
+    M = int(batch["states"].shape[0])
+    dev = batch["states"].device
+    data = {"state": batch["states"].float().contiguous(), "pre": batch["pre"].float().contiguous(), "logp": batch["log_probs"].reshape(-1).float().contiguous(),
+            "ret": batch["returns"].reshape(-1).float().contiguous()}
+    order = torch.randperm(M, device=dev).to(torch.int32).contiguous() if shuffle else None
+    steps = 1 if accumulate else (M + slice - 1) // slice
+    out = {"policy_loss": torch.empty(steps, dtype=torch.float32, device=dev), "value_loss": torch.empty(steps, dtype=torch.float32, device=dev),
+           "clipped": torch.empty(steps, dtype=torch.int32, device=dev), "adv": torch.empty(M, dtype=torch.float32, device=dev)}
+    if grads:
+        out["grad_policy"] = torch.empty(venv.env.gcl_num_params("policy"), dtype=torch.float32, device=dev)
+        out["grad_value"] = torch.empty(venv.env.gcl_num_params("value"), dtype=torch.float32, device=dev)
+    venv.env.gcl_policy_update(data, M, slice, accumulate, reduce, order, out)
+    venv._update_inputs = (data, order)  # alive until the next update: the kernels are only enqueued
+    return out
+
+
 def batch_stats(batch):
     """The statistics of a prepare_batch result as a dict (one small copy to the host): sum_ret, sumsq_ret, sum_adv, sumsq_adv (fp64, in
     the rule's order), mean_ret, std_ret, mean_adv, std_adv, count."""

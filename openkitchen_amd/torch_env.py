@@ -445,6 +445,86 @@ class VectorEnvironment:
         ("state" [N,R], "eps", "pre", "action" [N,2], "logp" [N] float32, "alive" [N] uint8) that receive the sample."""
         self.env.gauss_act(record)
 
+    # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) ----------------------------------------------------------
+    @staticmethod
+    def _gcl_tensors(module, what, log_std):
+        """[log_std,] fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc3.weight, fc3.bias of a module built like the reference's
+        (RLRacers/GuidedCostLearning/Networks.hpp): parameters() order, the policy's own log_std first."""
+        try:
+            t = ([module.log_std] if log_std else []) + [module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.fc3.weight,
+                                                        module.fc3.bias]
+        except AttributeError:
+            raise ValueError("%s: expected a module with %sfc1, fc2 and fc3 (Linear layers with biases)" % (what, "log_std, " if log_std else ""))
+        if any(x is None for x in t):
+            raise ValueError("%s: fc1, fc2 and fc3 need their biases" % what)
+        return t
+
+    def enable_gcl(self, policy_module, value_module, cost_module, **config):
+        """Attaches the reference's guided-cost-learning agent (RLRacers/GuidedCostLearning): `policy_module` has log_std [2] and
+        fc1 = Linear(R, H1), fc2 = Linear(H1, H2), fc3 = Linear(H2, 2) -- the device applies ReLU twice, tanh to the mean and samples
+        tanh(mu + exp(log_std) * eps) * scale + bias; `value_module` has fc1, fc2, fc3 = Linear(H2, 1) of the same widths;
+        `cost_module` fc1 = Linear(R + 2, C1), fc2 = Linear(C1, C2), fc3 = Linear(C2, 1), tanh twice, on torch.cat([state, action], 1).
+        The state is the squared hit distance over the squared sensor range, not observation().  config: the members of okenv_gcl_config
+        but the widths (capi.gcl_config: scale, bias, greedy, seed, agent_base).  The device's parameters start from the modules';
+        rollout's updates step them in place, and pull_gcl() copies them back."""
+        nets = {"policy": self._gcl_tensors(policy_module, "policy", True), "value": self._gcl_tensors(value_module, "value", False),
+                "cost": self._gcl_tensors(cost_module, "cost", False)}
+        R = self.num_rays
+        H1, H2 = nets["policy"][1].shape[0], nets["policy"][3].shape[0]
+        C1, C2 = nets["cost"][0].shape[0], nets["cost"][2].shape[0]
+
+        def shapes(n_in, a, b, out):
+            return [(a, n_in), (a,), (b, a), (b,), (out, b), (out,)]
+
+        want = {"policy": [(2,)] + shapes(R, H1, H2, 2), "value": shapes(R, H1, H2, 1), "cost": shapes(R + 2, C1, C2, 1)}
+        for name, t in nets.items():
+            if [tuple(x.shape) for x in t] != want[name]:
+                raise ValueError("%s: shapes %s, expected %s" % (name, [tuple(x.shape) for x in t], want[name]))
+        config.setdefault("seed", self.seed)
+        config.setdefault("agent_base", self.agent_base)
+        self.env.gcl_create(hidden1=H1, hidden2=H2, cost_hidden1=C1, cost_hidden2=C2, **config)
+        self._gcl_nets = nets
+        self._gcl_graphs = {}
+        self.gcl_learner_enabled = False
+        self.sync_gcl()
+
+    def sync_gcl(self):
+        """The modules' current parameters to the device's three networks, device to device on the environment's stream."""
+        self._gcl_flat = {name: self._flatten(t) for name, t in self._gcl_nets.items()}  # alive until the next hand-over
+        for name, flat in self._gcl_flat.items():
+            self.env.gcl_set_params(name, flat)
+
+    def enable_gcl_learner(self, lr=3e-4, clip=0.2, cost_lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8):
+        """Adam for the device's three networks (the reference's learning rate and clip, torch.optim.Adam's defaults)."""
+        assert getattr(self, "_gcl_nets", None) is not None, "call enable_gcl(policy, value, cost) first"
+        self.env.gcl_learner_create(lr, clip, cost_lr, beta1, beta2, eps)
+        self.gcl_learner_enabled = True
+
+    def set_gcl_expert(self, demonstrations):
+        """The expert bank from the dict demonstrations.collect_demonstrations returns: the alive rows, as rollout.gcl_expert_rows
+        makes them.  Returns the number of rows."""
+        from .rollout import gcl_expert_rows
+        self._gcl_bank = gcl_expert_rows(demonstrations)  # alive until the next bank: the copy is asynchronous
+        self.env.gcl_set_expert(*self._gcl_bank)
+        return int(self._gcl_bank[0].shape[0])
+
+    def pull_gcl(self):
+        """Copies the device's parameters back into the modules given to enable_gcl."""
+        for name, tensors in self._gcl_nets.items():
+            flat = torch.empty(self.env.gcl_num_params(name), dtype=torch.float32, device=self.device)
+            self.env.gcl_state(name, out={"params": flat})
+            self._unflatten(tensors, flat)
+
+    def set_gcl_greedy(self, greedy):
+        self.env.gcl_set_greedy(greedy)
+        self._gcl_graphs = {}  # a captured launch carries the old value
+
+    def gcl_act(self, record=None):
+        """The sampled (or greedy) action of every agent from the last observation, written into `throttle` / `steering`: one kernel
+        on the environment's stream, no synchronisation, usable inside capture(body).  record: optional dict of device tensors
+        ("state" [N,R], "eps", "pre", "squashed", "action" [N,2], "logp" [N] float32, "alive" [N] uint8) that receive the sample."""
+        self.env.gcl_act(record)
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
