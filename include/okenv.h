@@ -943,6 +943,59 @@ OKENV_API int okenv_gcl_policy_update_host(const okenv_learner_params *params, c
                                            int32_t hidden1, int32_t hidden2, okenv_gcl_state *policy, okenv_gcl_state *value,
                                            const okenv_gcl_batch *batch, int32_t M, int32_t B, const int32_t *order, const okenv_gcl_output *out);
 
+/* ---- Lidar transformer driver -----------------------------------------------------------------------------
+ * ImitationLearningTransformer (laser_transformer.py: LidarTransformer; infer_torch_traced_main.cpp) for every agent of the handle:
+ * the hit points of the handle's rays, normalised, through a point embedding, post-norm transformer encoder layers and a control
+ * head, to (throttle_delta, steering_delta).  Inference only.  The rule is written out in include/okenv_lidar.h (ok_lidar_*); the
+ * linear layers run on the f32-input matrix cores.  The parameter vector is torch's parameters() order for the reference module
+ * followed by a positional table pos [R][d_model] (ok_lidar_offsets). */
+typedef struct okenv_lidar_config {
+    int32_t num_points;      /* R: must equal the handle's ray count, 1 .. 16                                      */
+    int32_t d_model;         /* multiple of 16, 16 .. 512        (the reference: 128)                              */
+    int32_t nhead;           /* divides d_model                  (8)                                               */
+    int32_t num_layers;      /* 1 .. 8                           (3)                                               */
+    int32_t dim_feedforward; /* multiple of 16, 16 .. 4096       (512)                                             */
+    int32_t head_hidden1;    /* multiple of 16, 16 .. 2048       (256)                                             */
+    int32_t head_hidden2;    /* multiple of 16, 16 .. 2048       (64)                                              */
+    float   action_lo[2];    /* a_k = (o_k + 1) / 2 * (hi_k - lo_k) + lo_k   (the reference: 0, -2)                */
+    float   action_hi[2];    /*                                              (the reference: 100, 2)               */
+    float   sensor_range;    /* points are normalised from [-sensor_range, sensor_range] to [-1, 1]  (200)          */
+} okenv_lidar_config;
+
+/* Where okenv_lidar_act leaves this step's sample, besides the action fields: device pointers, each may be NULL (skipped). */
+typedef struct okenv_lidar_record {
+    float   *action; /* [N][2]     (throttle_delta, steering_delta) */
+    float   *input;  /* [N][R][2]  the normalised points            */
+    uint8_t *alive;  /* [N]        !crashed_                        */
+} okenv_lidar_record;
+
+/* LDS bytes of the act kernel (16 agents per workgroup) for the shape: a pure host function.  A shape is accepted only if this fits
+ * 160 KB.  0 for a NULL config or a shape outside the rule's limits. */
+OKENV_API int64_t okenv_lidar_lds_bytes(const okenv_lidar_config *config);
+/* Attaches a lidar policy to the handle (replaces an earlier one: its parameters are forgotten).  All device memory is allocated
+ * here.  OKENV_ERR_INVALID for NULL arguments, num_points other than the handle's ray count, a width outside the limits above, a
+ * shape that does not fit the LDS, ranges that are not finite or sensor_range <= 0. */
+OKENV_API int okenv_lidar_create(okenv_t h, const okenv_lidar_config *config);
+/* Floats of the parameter vector, the positional table included. */
+OKENV_API int okenv_lidar_num_params(okenv_t h, int32_t *num_params);
+/* New parameters from a host or device pointer.  No synchronisation. */
+OKENV_API int okenv_lidar_set_params(okenv_t h, const float *params);
+/* The parameters, in the same order, to a host or device pointer; synchronises. */
+OKENV_API int okenv_lidar_get_params(okenv_t h, float *params);
+/* The action of every agent, crashed ones included (okenv_expert_act's contract): reads OKENV_F_REL_X / _REL_Y and crashed_, writes
+ * OKENV_F_THROTTLE / OKENV_F_STEER and the record.  One kernel on the handle's stream, no synchronisation, no allocation: capturable
+ * beside okenv_step.  OKENV_ERR_STATE before okenv_lidar_create or okenv_lidar_set_params. */
+OKENV_API int okenv_lidar_act(okenv_t h, const okenv_lidar_record *rec);
+/* The same rule on host arrays, no GPU needed: n agents, rel_xy [n][R][2] (x, y interleaved), crashed [n] or NULL; outputs, each
+ * may be NULL: throttle, steer [n], input [n][R][2], alive [n]. */
+OKENV_API int okenv_lidar_act_host(const okenv_lidar_config *config, const float *params, int32_t n, const float *rel_xy, const uint8_t *crashed,
+                                   float *throttle, float *steer, float *input, uint8_t *alive);
+/* out [M][N] = x [M][K] w^T [N][K] + bias [N] (relu != 0: relu of it), the rule's linear layer alone.  On device `device` it runs
+ * through the act kernel's own device function, 16 rows per workgroup; device < 0 (OKENV_DEBUG_ON_HOST) evaluates ok_lidar_dot on
+ * the host.  Host pointers.  K and N multiples of 16, K <= 4096, N <= 4096; synchronises. */
+OKENV_API int okenv_debug_lidar_linear(int32_t device, int32_t M, int32_t K, int32_t N, const float *x, const float *w, const float *bias,
+                                       int32_t relu, float *out);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.

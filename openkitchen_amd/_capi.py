@@ -98,6 +98,8 @@ SYMBOLS = [
     "okenv_gcl_set_draw_offset", "okenv_gcl_set_greedy", "okenv_gcl_act", "okenv_gcl_set_expert", "okenv_gcl_cost", "okenv_gcl_learner_create",
     "okenv_gcl_cost_update", "okenv_gcl_policy_update", "okenv_debug_gcl_timing", "okenv_gcl_act_host", "okenv_gcl_cost_host",
     "okenv_gcl_cost_update_host", "okenv_gcl_policy_update_host",
+    "okenv_lidar_lds_bytes", "okenv_lidar_create", "okenv_lidar_num_params", "okenv_lidar_set_params", "okenv_lidar_get_params", "okenv_lidar_act",
+    "okenv_lidar_act_host", "okenv_debug_lidar_linear",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -348,6 +350,83 @@ def gauss_num_params(R, H1, H2, A=2):
 def gauss_lds_bytes(R, H1, H2, A=2):
     """okenv_gauss_lds_bytes: the gradient kernel's LDS for the shape, 0 outside the rule's limits.  No GPU needed."""
     return int(load().okenv_gauss_lds_bytes(int(R), int(H1), int(H2), int(A)))
+
+
+# lidar transformer driver (include/okenv.h)
+LIDAR_LDS_BUDGET = 160 * 1024
+
+
+class OkenvLidarConfig(C.Structure):
+    _fields_ = [("num_points", C.c_int32), ("d_model", C.c_int32), ("nhead", C.c_int32), ("num_layers", C.c_int32),
+                ("dim_feedforward", C.c_int32), ("head_hidden1", C.c_int32), ("head_hidden2", C.c_int32), ("action_lo", C.c_float * 2),
+                ("action_hi", C.c_float * 2), ("sensor_range", C.c_float)]
+
+
+class OkenvLidarRecord(C.Structure):
+    _fields_ = [("action", C.c_void_p), ("input", C.c_void_p), ("alive", C.c_void_p)]
+
+
+def lidar_config(num_points=7, d_model=128, nhead=8, num_layers=3, dim_feedforward=512, head_hidden1=256, head_hidden2=64,
+                 action_lo=(0.0, -2.0), action_hi=(100.0, 2.0), sensor_range=200.0):
+    """okenv_lidar_config with the reference's shape and ranges as defaults (laser_transformer.py, infer_torch_traced_main.cpp:19-43)."""
+    return OkenvLidarConfig(int(num_points), int(d_model), int(nhead), int(num_layers), int(dim_feedforward), int(head_hidden1),
+                            int(head_hidden2), (C.c_float * 2)(*map(float, action_lo)), (C.c_float * 2)(*map(float, action_hi)),
+                            float(sensor_range))
+
+
+def lidar_layout(cfg):
+    """ok_lidar_offsets: where every piece of the parameter vector begins, as (name, offset, shape) in order; the names are the
+    reference module's state-dict keys, the last piece is the positional table "pos".  The last entry's end is the vector's length."""
+    R, d, F, H1, H2 = cfg.num_points, cfg.d_model, cfg.dim_feedforward, cfg.head_hidden1, cfg.head_hidden2
+    pieces = [("point_embedding.weight", (d, 2)), ("point_embedding.bias", (d,))]
+    for i in range(cfg.num_layers):
+        pre = "transformer_encoder.layers.%d." % i
+        pieces += [(pre + "self_attn.in_proj_weight", (3 * d, d)), (pre + "self_attn.in_proj_bias", (3 * d,)),
+                   (pre + "self_attn.out_proj.weight", (d, d)), (pre + "self_attn.out_proj.bias", (d,)),
+                   (pre + "linear1.weight", (F, d)), (pre + "linear1.bias", (F,)), (pre + "linear2.weight", (d, F)), (pre + "linear2.bias", (d,)),
+                   (pre + "norm1.weight", (d,)), (pre + "norm1.bias", (d,)), (pre + "norm2.weight", (d,)), (pre + "norm2.bias", (d,))]
+    pieces += [("control_head.0.weight", (H1, R * d)), ("control_head.0.bias", (H1,)), ("control_head.2.weight", (H2, H1)),
+               ("control_head.2.bias", (H2,)), ("control_head.4.weight", (2, H2)), ("control_head.4.bias", (2,)), ("pos", (R, d))]
+    out, at = [], 0
+    for name, shape in pieces:
+        out.append((name, at, shape))
+        at += int(np.prod(shape))
+    return out
+
+
+def lidar_num_params(cfg):
+    """Floats of the parameter vector, the positional table included."""
+    name, at, shape = lidar_layout(cfg)[-1]
+    return at + int(np.prod(shape))
+
+
+def lidar_lds_bytes(cfg):
+    """okenv_lidar_lds_bytes: the act kernel's LDS for the shape, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_lidar_lds_bytes(C.byref(cfg)))
+
+
+def lidar_act_host(cfg, params, rel_xy, crashed=None):
+    """okenv_lidar_act_host on numpy arrays: rel_xy [n][R][2] -> dict(throttle, steer [n], input [n][R][2], alive [n]).  No GPU needed."""
+    rel_xy = np.ascontiguousarray(rel_xy, np.float32)
+    params = np.ascontiguousarray(params, np.float32)
+    n = rel_xy.shape[0]
+    assert rel_xy.shape == (n, cfg.num_points, 2) and params.size == lidar_num_params(cfg)
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, np.uint8)
+    out = dict(throttle=np.empty(n, np.float32), steer=np.empty(n, np.float32), input=np.empty((n, cfg.num_points, 2), np.float32),
+               alive=np.empty(n, np.uint8))
+    check(load().okenv_lidar_act_host(C.byref(cfg), ptr(params), n, ptr(rel_xy), ptr(crashed), ptr(out["throttle"]), ptr(out["steer"]),
+                                      ptr(out["input"]), ptr(out["alive"])))
+    return out
+
+
+def debug_lidar_linear(x, w, bias, relu=False, device=DEBUG_ON_HOST):
+    """okenv_debug_lidar_linear: x [M][K], w [N][K], bias [N] -> [M][N]; device < 0 evaluates the rule on the host."""
+    x, w, bias = (np.ascontiguousarray(a, np.float32) for a in (x, w, bias))
+    (M, K), N = x.shape, w.shape[0]
+    assert w.shape == (N, K) and bias.shape == (N,)
+    out = np.empty((M, N), np.float32)
+    check(load().okenv_debug_lidar_linear(int(device), M, K, N, ptr(x), ptr(w), ptr(bias), 1 if relu else 0, ptr(out)))
+    return out
 
 
 # guided cost learning (include/okenv.h)
@@ -703,6 +782,15 @@ def load(build_if_missing=True):
     L.okenv_gcl_policy_update_host.argtypes = [C.POINTER(OkenvLearnerParams), C.POINTER(OkenvGclUpdateConfig), i32, i32, i32, C.POINTER(OkenvGclState),
                                                C.POINTER(OkenvGclState), C.POINTER(OkenvGclBatch), i32, i32, vp, C.POINTER(OkenvGclOutput)]
     L.okenv_debug_normal.argtypes = [i32, vp, vp, vp, vp, i32]
+    L.okenv_lidar_lds_bytes.argtypes = [C.POINTER(OkenvLidarConfig)]
+    L.okenv_lidar_lds_bytes.restype = C.c_int64
+    L.okenv_lidar_create.argtypes = [vp, C.POINTER(OkenvLidarConfig)]
+    L.okenv_lidar_num_params.argtypes = [vp, C.POINTER(i32)]
+    L.okenv_lidar_set_params.argtypes = [vp, vp]
+    L.okenv_lidar_get_params.argtypes = [vp, vp]
+    L.okenv_lidar_act.argtypes = [vp, C.POINTER(OkenvLidarRecord)]
+    L.okenv_lidar_act_host.argtypes = [C.POINTER(OkenvLidarConfig), vp, i32, vp, vp, vp, vp, vp, vp]
+    L.okenv_debug_lidar_linear.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, vp]
     _lib = L
     return L
 

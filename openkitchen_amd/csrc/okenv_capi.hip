@@ -31,6 +31,7 @@
 #include "ok_reinforce.h"
 #include "ok_gauss.h"
 #include "ok_gcl.h"
+#include "ok_lidar.h"
 #include "ok_expert.h"
 
 namespace
@@ -567,6 +568,11 @@ struct okenv
     float                  *d_gcl_bank{nullptr}; // [state rows | action rows]
     int32_t                 gcl_bank_rows{0}, gcl_bank_cap{0};
     OkUpdateScratch         gcl_scratch[3], gcl_adv_scratch;
+    // Lidar transformer driver (okenv_lidar_create): the parameter vector in torch's order with the positional table behind it
+    bool                    lidar_ok{false}, lidar_set{false};
+    okenv_lidar_config      lidar{};
+    size_t                  lidar_cap{0};
+    float                  *d_lidar{nullptr};
 };
 
 struct okenv_track
@@ -4131,6 +4137,164 @@ extern "C"
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_gcl_policy_update_host: a state lacks a parameter or moment vector, or t < 0");
         const okenv_gcl_output none{};
         okGclPolicyUpdateHost(*params, *config, num_rays, hidden1, hidden2, *policy, *value, *batch, M, B, order, out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    // ---- Lidar transformer driver (ok_lidar.h) -----------------------------------------------------------------------------------
+
+    int64_t okenv_lidar_lds_bytes(const okenv_lidar_config *config)
+    {
+        return config != nullptr ? static_cast<int64_t>(okLidarLdsBytes(okLidarShape(*config))) : 0;
+    }
+
+    int okenv_lidar_create(okenv_t h, const okenv_lidar_config *config)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_create: NULL handle");
+        if (const char *why = okLidarCheckConfig(config))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_lidar_create: ") + why);
+        if (config->num_points != h->shape.R)
+            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_create: num_points must equal the handle's ray count");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t total = static_cast<size_t>(ok_lidar_offsets(okLidarShape(*config)).total);
+        h->lidar_ok        = false;
+        h->lidar_set       = false;
+        if (total > h->lidar_cap)
+        {
+            // the old vector is freed behind a wait for the stream: an earlier act may still be reading it
+            OK_HIP(h, hipStreamSynchronize(h->stream));
+            if (h->d_lidar != nullptr)
+            {
+                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_lidar)), h->allocations.end());
+                (void)hipFree(h->d_lidar);
+                h->d_lidar   = nullptr;
+                h->lidar_cap = 0;
+            }
+            float *fresh = nullptr;
+            if (const int rc = devAlloc(h, &fresh, total))
+                return rc;
+            h->d_lidar   = fresh;
+            h->lidar_cap = total;
+        }
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okLidarActKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+        h->lidar    = *config;
+        h->lidar_ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_lidar_num_params(okenv_t h, int32_t *num_params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !num_params)
+            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_num_params: NULL argument");
+        if (!h->lidar_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_lidar_num_params: call okenv_lidar_create first");
+        *num_params = ok_lidar_offsets(okLidarShape(h->lidar)).total;
+        return OKENV_OK;
+    }
+
+    int okenv_lidar_set_params(okenv_t h, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !params)
+            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_set_params: NULL argument");
+        if (!h->lidar_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_lidar_set_params: call okenv_lidar_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = copyAny(h, h->d_lidar, params, sizeof(float) * static_cast<size_t>(ok_lidar_offsets(okLidarShape(h->lidar)).total)))
+            return rc;
+        h->lidar_set = true;
+        return OKENV_OK;
+    }
+
+    int okenv_lidar_get_params(okenv_t h, float *params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !params)
+            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_get_params: NULL argument");
+        if (!h->lidar_ok || !h->lidar_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_lidar_get_params: the policy needs its parameters first (okenv_lidar_create, okenv_lidar_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = copyAny(h, params, h->d_lidar, sizeof(float) * static_cast<size_t>(ok_lidar_offsets(okLidarShape(h->lidar)).total)))
+            return rc;
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_lidar_act(okenv_t h, const okenv_lidar_record *rec)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_act: NULL handle");
+        if (!h->lidar_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_lidar_act: call okenv_lidar_create first");
+        if (!h->lidar_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_lidar_act: call okenv_lidar_set_params first (the policy needs its parameters)");
+        dropEpisode(h);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkLidarActParams p{};
+        p.st     = h->st;
+        p.N      = h->shape.N;
+        p.s      = okLidarShape(h->lidar);
+        p.params = h->d_lidar;
+        for (int k = 0; k < 2; ++k)
+        {
+            p.lo[k] = h->lidar.action_lo[k];
+            p.hi[k] = h->lidar.action_hi[k];
+        }
+        p.range = h->lidar.sensor_range;
+        p.scale = ok_lidar_scale(p.s.d / p.s.nhead);
+        if (rec != nullptr)
+            p.rec = *rec;
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + kLidarAgents - 1) / kLidarAgents);
+        hipLaunchKernelGGL(okLidarActKernel, dim3(blocks), dim3(kLidarThreads), okLidarLdsBytes(p.s), h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_lidar_act_host(const okenv_lidar_config *config, const float *params, int32_t n, const float *rel_xy, const uint8_t *crashed, float *throttle,
+                             float *steer, float *input, uint8_t *alive)
+    {
+        if (const char *why = okLidarCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_lidar_act_host: ") + why);
+        if (!params || n < 0 || !rel_xy)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_lidar_act_host: bad argument");
+        okLidarActHost(*config, params, n, rel_xy, crashed, throttle, steer, input, alive);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_lidar_linear(int32_t device, int32_t M, int32_t K, int32_t N, const float *x, const float *w, const float *bias, int32_t relu, float *out)
+    {
+        if (!x || !w || !bias || !out || M < 0 || K < 16 || K > 4096 || K % 16 != 0 || N < 16 || N > 4096 || N % 16 != 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_lidar_linear: bad argument (K and N multiples of 16 up to 4096)");
+        if (device < 0)
+        {
+            okLidarLinearHost(M, K, N, x, w, bias, relu, out);
+            return OKENV_OK;
+        }
+        const size_t lds = okDebugLidarLinearLdsBytes(K, N);
+        if (lds > kLdsBudget)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_lidar_linear: 16 rows of x and out do not fit the LDS");
+        if (const int rc = debugNeedsDevice("okenv_debug_lidar_linear"))
+            return rc;
+        if (M == 0)
+            return OKENV_OK;
+        OK_HIP(nullptr, hipSetDevice(device));
+        // [x M K | w N K | bias N | out M N]
+        const size_t nx = static_cast<size_t>(M) * K, nw = static_cast<size_t>(N) * K, nb = static_cast<size_t>(N), no = static_cast<size_t>(M) * N;
+        DebugBuffer  buf;
+        OK_HIP(nullptr, hipMalloc(reinterpret_cast<void **>(&buf.d), 4U * (nx + nw + nb + no)));
+        float *dx = buf.d, *dw = dx + nx, *db = dw + nw, *dout = db + nb;
+        OK_HIP(nullptr, hipMemcpy(dx, x, 4U * nx, hipMemcpyHostToDevice));
+        OK_HIP(nullptr, hipMemcpy(dw, w, 4U * nw, hipMemcpyHostToDevice));
+        OK_HIP(nullptr, hipMemcpy(db, bias, 4U * nb, hipMemcpyHostToDevice));
+        OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDebugLidarLinearKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            static_cast<int>(kLdsBudget)));
+        hipLaunchKernelGGL(okDebugLidarLinearKernel, dim3(static_cast<unsigned>((M + kLidarAgents - 1) / kLidarAgents)), dim3(kLidarThreads), lds, nullptr, M, K, N,
+                           dx, dw, db, relu, dout);
+        OK_HIP(nullptr, hipGetLastError());
+        OK_HIP(nullptr, hipMemcpy(out, dout, 4U * no, hipMemcpyDeviceToHost));
         return OKENV_OK;
     }
 

@@ -816,6 +816,48 @@ class BatchedEnvironment:
         """Device microseconds of the latest gauss_update that ran with set_timing(True), summed over its slices, by capi.GAUSS_KERNELS."""
         return self._timing("okenv_debug_gauss_timing", capi.GAUSS_KERNELS)
 
+    # ---- lidar transformer driver (include/okenv.h, DESIGN.md section 22) -------------------------------------------------------
+    def lidar_create(self, config=None, **members):
+        """Attaches a lidar transformer policy to the handle; config: a capi.lidar_config(...), or its members by name (num_points
+        defaults to the handle's ray count, the rest to the reference's shape).  Returns the floats of its parameter vector."""
+        if config is None:
+            members.setdefault("num_points", self.R)
+            config = capi.lidar_config(**members)
+        capi.check(self._L.okenv_lidar_create(self._h, C.byref(config)), self._h)
+        self.lidar_config = config
+        return self.lidar_num_params()
+
+    def lidar_num_params(self):
+        n = C.c_int32()
+        capi.check(self._L.okenv_lidar_num_params(self._h, C.byref(n)), self._h)
+        return n.value
+
+    def lidar_set_params(self, params):
+        """New parameters (torch's parameters() order, then the positional table: capi.lidar_layout) from a float32 numpy array or a
+        device tensor.  No synchronisation."""
+        if hasattr(params, "data_ptr"):
+            assert params.is_contiguous() and params.numel() == self.lidar_num_params()
+        else:
+            params = _flat_params(params, self.lidar_num_params())
+        capi.check(self._L.okenv_lidar_set_params(self._h, capi.ptr(params)), self._h)
+
+    def lidar_get_params(self, out=None):
+        """The parameter vector as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
+        if out is None:
+            out = np.empty(self.lidar_num_params(), dtype=np.float32)
+        capi.check(self._L.okenv_lidar_get_params(self._h, capi.ptr(out)), self._h)
+        return out
+
+    def lidar_act(self, record=None):
+        """The policy's action for every agent, enqueued on the handle's stream without a synchronisation.  record: None, or a dict
+        of device tensors / addresses under "action" [N,2], "input" [N,R,2] float32 and "alive" [N] uint8, each optional."""
+        if record is None:
+            capi.check(self._L.okenv_lidar_act(self._h, None), self._h)
+            return
+        sizes = {"action": self.N * 8, "input": self.N * self.R * 8, "alive": self.N}
+        rec = capi.fill_pointers(capi.OkenvLidarRecord(), record, "record", sizes)
+        capi.check(self._L.okenv_lidar_act(self._h, C.byref(rec)), self._h)
+
     # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) -------------------------------------------------------
     def gcl_create(self, **config):
         """Attaches a GCL object (policy R -> H1 -> H2 -> 2 with log_std, value R -> H1 -> H2 -> 1, cost R + 2 -> C1 -> C2 -> 1) to the

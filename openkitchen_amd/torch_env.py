@@ -525,6 +525,28 @@ class VectorEnvironment:
         ("state" [N,R], "eps", "pre", "squashed", "action" [N,2], "logp" [N] float32, "alive" [N] uint8) that receive the sample."""
         self.env.gcl_act(record)
 
+    # ---- lidar transformer driver (include/okenv.h, DESIGN.md section 22) ----------------------------------------------------------
+    def enable_lidar_policy(self, config, params):
+        """Attaches the reference's imitation policy (ImitationLearningTransformer: LidarTransformer) as a device driver.  config:
+        a capi.lidar_config(...) or a dict of its members (num_points defaults to the environment's ray count); params: the flat
+        vector imitation.lidar_params_from_state_dict makes, a float32 numpy array or a tensor.  Call it again with new params after
+        training on."""
+        if isinstance(config, dict):
+            config = capi.lidar_config(**dict({"num_points": self.num_rays}, **config))
+        self.env.lidar_create(config)
+        if torch.is_tensor(params):
+            params = params.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        self._lidar_flat = params  # alive until the next hand-over: the copy is asynchronous
+        self.env.lidar_set_params(params)
+        self.lidar_config = config
+        self._lidar_graphs = {}  # a captured launch carries the old shape and vector
+
+    def lidar_act(self, record=None):
+        """The policy's action of every agent from the last observation's hit points, written into `throttle` / `steering`: one
+        kernel on the environment's stream, no synchronisation, usable inside capture(body).  record: optional dict of device tensors
+        ("action" [N,2], "input" [N,R,2] float32, "alive" [N] uint8) that receive the sample."""
+        self.env.lidar_act(record)
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
