@@ -1,0 +1,106 @@
+"""The reference's flow-matching driver (FlowMatching/) for a whole population: demonstrations with bird's-eye frames from the
+device's potential-field expert, the conditional flow-matching policy trained on them in PyTorch with the reference's recipe, and N
+agents driven by it -- the conv encoder once per step in PyTorch, the 32 evaluations of the trunk in the device's one act kernel.
+
+    python examples/flow_racer.py [--agents 256] [--frame-size 64] [--demo-steps 128] [--epochs 3] [--steps 256] [--episodes 2]
+                                  [--flow-steps 32] [--graph-chunk 8] [--torch-sampler] [--track Austin]
+
+1. record: every living agent's frame and the expert's action (demonstrations.collect_demonstrations(images=True));
+2. train: x_t on the straight path from noise to the normalised action, MSE on the velocity, Adam 1e-3 (train_flow_matching.py);
+3. hand over: the trunk's weights as one flat vector (flow.flow_params_from_state_dict -> enable_flow_policy);
+4. drive: `step`, `camera()`, the encoder, `flow_act(cond)` (flow.drive), and the share of agents that survive every episode.
+--torch-sampler drives with the PyTorch loop over the trunk instead (flow.sample), for comparison.
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from openkitchen_amd import flow  # noqa: E402
+from openkitchen_amd.demonstrations import collect_demonstrations  # noqa: E402
+from openkitchen_amd.torch_env import VectorEnvironment  # noqa: E402
+
+
+def torch_drive(venv, model, steps, flow_steps, gen):
+    """The same loop with the PyTorch sampler between single-step launches."""
+    venv.reset()
+    lo, hi = (venv.throttle.new_tensor(v) for v in (flow.ACTION_LO, flow.ACTION_HI))
+    with torch.no_grad():
+        for _ in range(steps):
+            venv.step()
+            cond = model.bev_encoder(flow.frames_to_input(venv.camera()))
+            x0 = torch.randn((venv.num_envs, 2), device=venv.device, generator=gen)
+            action = flow.denormalize_controls(flow.sample(model, cond, x0, flow_steps), flow.ACTION_LO, flow.ACTION_HI)
+            action = torch.minimum(torch.maximum(action, lo), hi)
+            venv.set_action(action[:, 0], action[:, 1])
+    return steps
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--agents", type=int, default=256)
+    ap.add_argument("--frame-size", type=int, default=64)
+    ap.add_argument("--demo-steps", type=int, default=128)
+    ap.add_argument("--epochs", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=256)
+    ap.add_argument("--episodes", type=int, default=2)
+    ap.add_argument("--flow-steps", type=int, default=32)
+    ap.add_argument("--graph-chunk", type=int, default=8)
+    ap.add_argument("--track", default="Austin")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--torch-sampler", action="store_true")
+    a = ap.parse_args(argv)
+    torch.manual_seed(a.seed)
+    venv = VectorEnvironment(a.track, a.agents, auto_reset=False, randomize_lane=True, randomize_heading=True, seed=a.seed)
+    venv.enable_camera(width=a.frame_size, height=a.frame_size, fmt="rgba")
+    # 1. demonstrations (the steering clamp keeps the expert inside the controls' range of +-10 degrees)
+    venv.enable_expert("potfield", lookahead=2, goal_wrap=False, clamp_deg=flow.ACTION_HI[1])
+    demos = collect_demonstrations(venv, a.demo_steps, images=True, seed=a.seed)
+    frames, actions = flow.demonstration_rows(demos)
+    print("recorded %d frames of living agents out of %d" % (frames.shape[0], a.agents * a.demo_steps))
+    # 2. training
+    model = flow.ConditionalFlowMatchingPolicy().to(venv.device)
+    t0 = time.perf_counter()
+    losses = flow.train(model, frames, actions, epochs=a.epochs, seed=a.seed)
+    print("trained %d epochs in %.1f s: loss %s" % (a.epochs, time.perf_counter() - t0, " ".join("%.4g" % v for v in losses)))
+    # 3. hand-over
+    sd = model.action_flow_trunk.state_dict()
+    cfg = flow.flow_config_from_state_dict(sd, steps=a.flow_steps, seed=a.seed, agent_base=venv.agent_base)
+    venv.enable_flow_policy(cfg, flow.flow_params_from_state_dict(sd))
+    # the first driven step, recorded: what the device sampled, from which noise and which condition
+    venv.reset()
+    venv.step()
+    with torch.no_grad():
+        cond = model.bev_encoder(flow.frames_to_input(venv.camera())).contiguous()
+    first = {"x0": torch.empty((a.agents, 2), device=venv.device), "x": torch.empty((a.agents, 2), device=venv.device),
+             "action": torch.empty((a.agents, 2), device=venv.device)}
+    venv.flow_act(cond, first)
+    want = flow.sample(model, cond, first["x0"], a.flow_steps)
+    print("first step: max |device - PyTorch sampler| = %.4g on the normalised sample" % float((first["x"] - want).abs().max()))
+    first["cond"] = cond
+    # 4. driving
+    gen = torch.Generator(device=venv.device).manual_seed(a.seed)
+    survival = []
+    for episode in range(a.episodes):
+        t0 = time.perf_counter()
+        if a.torch_sampler:
+            steps = torch_drive(venv, model, a.steps, a.flow_steps, gen)
+        else:
+            steps = flow.drive(venv, model, a.steps, graph_chunk=a.graph_chunk)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        survival.append(float((~venv.done).float().mean()))
+        print("episode %d: %d agents, %d steps with the %s in %.3f s (%.3g agent-steps/s); survival %.3f"
+              % (episode, a.agents, steps, "PyTorch sampler" if a.torch_sampler else "device act", dt, a.agents * steps / dt, survival[-1]))
+    out = {"model": model, "config": cfg, "first": first, "survival": survival, "losses": losses,
+           "throttle": venv.throttle.clone(), "steering": venv.steering.clone()}
+    print("actions finite %s" % bool(torch.isfinite(out["throttle"]).all() and torch.isfinite(out["steering"]).all()))
+    venv.close()
+    return out
+
+
+if __name__ == "__main__":
+    main()

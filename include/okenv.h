@@ -996,6 +996,54 @@ OKENV_API int okenv_lidar_act_host(const okenv_lidar_config *config, const float
 OKENV_API int okenv_debug_lidar_linear(int32_t device, int32_t M, int32_t K, int32_t N, const float *x, const float *w, const float *bias,
                                        int32_t relu, float *out);
 
+/* ---- Flow-matching driver ----------------------------------------------------------------------------------
+ * FlowMatching (flow_matching_model.py: ActionFlowTrunk; main_flow_control.cpp:68-102) for every agent of the handle: from noise
+ * x ~ N(0, I), `steps` Euler steps x += dt * trunk(x, t, cond) in one kernel, clamped to [-1, 1] and denormalised to
+ * (throttle_delta, steering_delta).  cond is the image encoder's output for the agent; the encoder is the caller's.  Inference only.
+ * The rule is written out in include/okenv_flow.h (ok_flow_*); the two wide linear layers run on the f32-input matrix cores.  The
+ * parameter vector is torch's parameters() order for the reference's trunk (ok_flow_offsets). */
+typedef struct okenv_flow_config {
+    int32_t  cond_dim;         /* C: multiple of 16, 16 .. 512     (the reference: 128)                               */
+    int32_t  hidden;           /* H: multiple of 16, 16 .. 512     (256)                                              */
+    int32_t  steps;            /* S: Euler steps, 1 .. 256         (32)                                               */
+    int32_t  noise;            /* 1: x starts from the normal draw; 0: from (0, 0), nothing is drawn                  */
+    float    action_lo[2];     /* a_k = (x_k + 1) / 2 * (hi_k - lo_k) + lo_k, clamped to [lo_k, hi_k]  (0, -10)       */
+    float    action_hi[2];     /*                                                                      (100, 10)      */
+    uint32_t seed, agent_base; /* key of the normal draws; global id of the handle's agent 0                          */
+} okenv_flow_config;
+
+/* Where okenv_flow_act leaves this step's sample, besides the action fields: device pointers, each may be NULL (skipped). */
+typedef struct okenv_flow_record {
+    float   *x0;     /* [N][2]  the noise the sampler started from (zeros with noise == 0) */
+    float   *x;      /* [N][2]  the clamped normalised sample                            */
+    float   *action; /* [N][2]  (throttle_delta, steering_delta)                         */
+    uint8_t *alive;  /* [N]     !crashed_                                                */
+} okenv_flow_record;
+
+/* LDS bytes of the act kernel for the shape: a pure host function.  A shape is accepted only if this fits 160 KB.  0 for a NULL
+ * config or a shape outside the rule's limits. */
+OKENV_API int64_t okenv_flow_lds_bytes(const okenv_flow_config *config);
+/* Attaches a flow policy to the handle (replaces an earlier one: its parameters are forgotten).  All device memory is allocated
+ * here.  OKENV_ERR_INVALID for NULL arguments, a width or step count outside the limits above, a shape that does not fit the LDS,
+ * noise other than 0 or 1, ranges that are not finite. */
+OKENV_API int okenv_flow_create(okenv_t h, const okenv_flow_config *config);
+OKENV_API int okenv_flow_num_params(okenv_t h, int32_t *num_params);
+/* New parameters from a host or device pointer.  No synchronisation. */
+OKENV_API int okenv_flow_set_params(okenv_t h, const float *params);
+/* The parameters, in the same order, to a host or device pointer; synchronises. */
+OKENV_API int okenv_flow_get_params(okenv_t h, float *params);
+/* A device word added to the draw index of every later okenv_flow_act (NULL: none): okenv_actor_set_draw_offset's contract. */
+OKENV_API int okenv_flow_set_draw_offset(okenv_t h, const uint32_t *device_word);
+/* The action of every agent, crashed ones included, from cond (device, [N][cond_dim]): reads crashed_, writes OKENV_F_THROTTLE /
+ * OKENV_F_STEER and the record.  One kernel on the handle's stream, no synchronisation, no allocation: capturable beside okenv_step.
+ * The draw index is okenv_actor_act's.  OKENV_ERR_STATE before okenv_flow_create or okenv_flow_set_params; OKENV_ERR_INVALID for a
+ * NULL cond. */
+OKENV_API int okenv_flow_act(okenv_t h, const float *cond, const okenv_flow_record *rec);
+/* The same rule on host arrays, no GPU needed: n agents (global ids config->agent_base + i), cond [n][cond_dim], crashed [n] or NULL;
+ * outputs, each may be NULL: throttle, steer [n], x0, x [n][2], alive [n]. */
+OKENV_API int okenv_flow_act_host(const okenv_flow_config *config, const float *params, int32_t n, const float *cond, const uint8_t *crashed,
+                                  uint32_t draw_index, float *throttle, float *steer, float *x0, float *x, uint8_t *alive);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.

@@ -547,7 +547,7 @@ OK_HD float ok_logf(const float x)
  *             Stream 6 is used by nothing else (0: C2 actions, 1: resets and GA weights, 2 / 3: GA mating, 4: Q-learning, 5:
  *             q_racer_sim's episode draws; 7: Deep-Q's sampling, okenv_dqn.h; 8: DDPG's exploration, okenv_ddpg.h; 9: REINFORCE's
  *             dropout masks, okenv_reinforce.h; 10: the Gaussian actor's normal draws, okenv_gauss.h; 11: guided cost learning's
- *             normal draws and 12: its expert rows, okenv_gcl.h).
+ *             normal draws and 12: its expert rows, okenv_gcl.h; 13: the flow-matching driver's noise, okenv_flow.h).
  *   modes     OK_ACTOR_SAMPLE (PPO, REINFORCE): u = ok_u01(word 0); the action is the first k with u < p_0 + ... + p_k (fp32
  *             sums of the clamped p, ascending), A - 1 if there is none.  Recorded: the clamped p of the action.
  *             OK_ACTOR_GREEDY (evaluation): the arg-max of z, lowest index on ties.  Recorded: the clamped p of the action.

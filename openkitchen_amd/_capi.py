@@ -100,6 +100,8 @@ SYMBOLS = [
     "okenv_gcl_cost_update_host", "okenv_gcl_policy_update_host",
     "okenv_lidar_lds_bytes", "okenv_lidar_create", "okenv_lidar_num_params", "okenv_lidar_set_params", "okenv_lidar_get_params", "okenv_lidar_act",
     "okenv_lidar_act_host", "okenv_debug_lidar_linear",
+    "okenv_flow_lds_bytes", "okenv_flow_create", "okenv_flow_num_params", "okenv_flow_set_params", "okenv_flow_get_params",
+    "okenv_flow_set_draw_offset", "okenv_flow_act", "okenv_flow_act_host",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -426,6 +428,64 @@ def debug_lidar_linear(x, w, bias, relu=False, device=DEBUG_ON_HOST):
     assert w.shape == (N, K) and bias.shape == (N,)
     out = np.empty((M, N), np.float32)
     check(load().okenv_debug_lidar_linear(int(device), M, K, N, ptr(x), ptr(w), ptr(bias), 1 if relu else 0, ptr(out)))
+    return out
+
+
+# flow-matching driver (include/okenv.h)
+FLOW_LDS_BUDGET = 160 * 1024
+FLOW_AGENTS = 16  # agents per workgroup of the act kernel (ok_flow.h: kFlowAgents); tests/test_flow_rule.py keeps the two in step
+
+
+class OkenvFlowConfig(C.Structure):
+    _fields_ = [("cond_dim", C.c_int32), ("hidden", C.c_int32), ("steps", C.c_int32), ("noise", C.c_int32), ("action_lo", C.c_float * 2),
+                ("action_hi", C.c_float * 2), ("seed", C.c_uint32), ("agent_base", C.c_uint32)]
+
+
+class OkenvFlowRecord(C.Structure):
+    _fields_ = [("x0", C.c_void_p), ("x", C.c_void_p), ("action", C.c_void_p), ("alive", C.c_void_p)]
+
+
+def flow_config(cond_dim=128, hidden=256, steps=32, noise=True, action_lo=(0.0, -10.0), action_hi=(100.0, 10.0), seed=0, agent_base=0):
+    """okenv_flow_config with the reference's shape and ranges as defaults (flow_matching_model.py, main_flow_control.cpp:19, 97-101)."""
+    return OkenvFlowConfig(int(cond_dim), int(hidden), int(steps), int(noise), (C.c_float * 2)(*map(float, action_lo)),
+                           (C.c_float * 2)(*map(float, action_hi)), int(seed) & 0xFFFFFFFF, int(agent_base) & 0xFFFFFFFF)
+
+
+def flow_layout(cfg):
+    """ok_flow_offsets: where every piece of the parameter vector begins, as (name, offset, shape) in order; the names are the
+    state-dict keys of the reference's ActionFlowTrunk.  The last entry's end is the vector's length."""
+    Cd, H = cfg.cond_dim, cfg.hidden
+    pieces = [("net.0.weight", (H, 3 + Cd)), ("net.0.bias", (H,)), ("net.2.weight", (H, H)), ("net.2.bias", (H,)), ("net.4.weight", (2, H)),
+              ("net.4.bias", (2,))]
+    out, at = [], 0
+    for name, shape in pieces:
+        out.append((name, at, shape))
+        at += int(np.prod(shape))
+    return out
+
+
+def flow_num_params(cfg):
+    """Floats of the trunk's parameter vector."""
+    name, at, shape = flow_layout(cfg)[-1]
+    return at + int(np.prod(shape))
+
+
+def flow_lds_bytes(cfg):
+    """okenv_flow_lds_bytes: the act kernel's LDS for the shape, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_flow_lds_bytes(C.byref(cfg)))
+
+
+def flow_act_host(cfg, params, cond, crashed=None, draw_index=0):
+    """okenv_flow_act_host on numpy arrays: cond [n][cond_dim] -> dict(throttle, steer [n], x0, x [n][2], alive [n]).  No GPU needed."""
+    cond = np.ascontiguousarray(cond, np.float32)
+    params = np.ascontiguousarray(params, np.float32)
+    n = cond.shape[0]
+    assert cond.shape == (n, cfg.cond_dim) and params.size == flow_num_params(cfg)
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, np.uint8)
+    out = dict(throttle=np.empty(n, np.float32), steer=np.empty(n, np.float32), x0=np.empty((n, 2), np.float32), x=np.empty((n, 2), np.float32),
+               alive=np.empty(n, np.uint8))
+    check(load().okenv_flow_act_host(C.byref(cfg), ptr(params), n, ptr(cond), ptr(crashed), int(draw_index) & 0xFFFFFFFF, ptr(out["throttle"]),
+                                     ptr(out["steer"]), ptr(out["x0"]), ptr(out["x"]), ptr(out["alive"])))
     return out
 
 
@@ -791,6 +851,15 @@ def load(build_if_missing=True):
     L.okenv_lidar_act.argtypes = [vp, C.POINTER(OkenvLidarRecord)]
     L.okenv_lidar_act_host.argtypes = [C.POINTER(OkenvLidarConfig), vp, i32, vp, vp, vp, vp, vp, vp]
     L.okenv_debug_lidar_linear.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, vp]
+    L.okenv_flow_lds_bytes.argtypes = [C.POINTER(OkenvFlowConfig)]
+    L.okenv_flow_lds_bytes.restype = C.c_int64
+    L.okenv_flow_create.argtypes = [vp, C.POINTER(OkenvFlowConfig)]
+    L.okenv_flow_num_params.argtypes = [vp, C.POINTER(i32)]
+    L.okenv_flow_set_params.argtypes = [vp, vp]
+    L.okenv_flow_get_params.argtypes = [vp, vp]
+    L.okenv_flow_set_draw_offset.argtypes = [vp, vp]
+    L.okenv_flow_act.argtypes = [vp, vp, C.POINTER(OkenvFlowRecord)]
+    L.okenv_flow_act_host.argtypes = [C.POINTER(OkenvFlowConfig), vp, i32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -32,6 +32,7 @@
 #include "ok_gauss.h"
 #include "ok_gcl.h"
 #include "ok_lidar.h"
+#include "ok_flow.h"
 #include "ok_expert.h"
 
 namespace
@@ -573,6 +574,12 @@ struct okenv
     okenv_lidar_config      lidar{};
     size_t                  lidar_cap{0};
     float                  *d_lidar{nullptr};
+    // Flow-matching driver (okenv_flow_create): the trunk's parameter vector in torch's order
+    bool                    flow_ok{false}, flow_set{false};
+    okenv_flow_config       flow{};
+    size_t                  flow_cap{0};
+    float                  *d_flow{nullptr};
+    const uint32_t         *flow_draw_offset{nullptr};
 };
 
 struct okenv_track
@@ -4295,6 +4302,142 @@ extern "C"
                            dx, dw, db, relu, dout);
         OK_HIP(nullptr, hipGetLastError());
         OK_HIP(nullptr, hipMemcpy(out, dout, 4U * no, hipMemcpyDeviceToHost));
+        return OKENV_OK;
+    }
+
+    // ---- Flow-matching driver (ok_flow.h) ----------------------------------------------------------------------------------------
+
+    int64_t okenv_flow_lds_bytes(const okenv_flow_config *config)
+    {
+        return config != nullptr ? static_cast<int64_t>(okFlowLdsBytes(okFlowShape(*config))) : 0;
+    }
+
+    int okenv_flow_create(okenv_t h, const okenv_flow_config *config)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_flow_create: NULL handle");
+        if (const char *why = okFlowCheckConfig(config))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_flow_create: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t total = static_cast<size_t>(ok_flow_offsets(okFlowShape(*config)).total);
+        h->flow_ok         = false;
+        h->flow_set        = false;
+        if (total > h->flow_cap)
+        {
+            // the old vector is freed behind a wait for the stream: an earlier act may still be reading it
+            OK_HIP(h, hipStreamSynchronize(h->stream));
+            if (h->d_flow != nullptr)
+            {
+                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_flow)), h->allocations.end());
+                (void)hipFree(h->d_flow);
+                h->d_flow   = nullptr;
+                h->flow_cap = 0;
+            }
+            float *fresh = nullptr;
+            if (const int rc = devAlloc(h, &fresh, total))
+                return rc;
+            h->d_flow   = fresh;
+            h->flow_cap = total;
+        }
+        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okFlowActKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+        h->flow    = *config;
+        h->flow_ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_flow_num_params(okenv_t h, int32_t *num_params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !num_params)
+            return fail(h, OKENV_ERR_INVALID, "okenv_flow_num_params: NULL argument");
+        if (!h->flow_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_flow_num_params: call okenv_flow_create first");
+        *num_params = ok_flow_offsets(okFlowShape(h->flow)).total;
+        return OKENV_OK;
+    }
+
+    int okenv_flow_set_params(okenv_t h, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !params)
+            return fail(h, OKENV_ERR_INVALID, "okenv_flow_set_params: NULL argument");
+        if (!h->flow_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_flow_set_params: call okenv_flow_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = copyAny(h, h->d_flow, params, sizeof(float) * static_cast<size_t>(ok_flow_offsets(okFlowShape(h->flow)).total)))
+            return rc;
+        h->flow_set = true;
+        return OKENV_OK;
+    }
+
+    int okenv_flow_get_params(okenv_t h, float *params)
+    {
+        OK_QUIESCE(h);
+        if (!h || !params)
+            return fail(h, OKENV_ERR_INVALID, "okenv_flow_get_params: NULL argument");
+        if (!h->flow_ok || !h->flow_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_flow_get_params: the policy needs its parameters first (okenv_flow_create, okenv_flow_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = copyAny(h, params, h->d_flow, sizeof(float) * static_cast<size_t>(ok_flow_offsets(okFlowShape(h->flow)).total)))
+            return rc;
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_flow_set_draw_offset(okenv_t h, const uint32_t *device_word)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->flow_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_flow_set_draw_offset: call okenv_flow_create first");
+        h->flow_draw_offset = device_word;
+        return OKENV_OK;
+    }
+
+    int okenv_flow_act(okenv_t h, const float *cond, const okenv_flow_record *rec)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_flow_act: NULL handle");
+        if (!h->flow_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_flow_act: call okenv_flow_create first");
+        if (!h->flow_set)
+            return fail(h, OKENV_ERR_STATE, "okenv_flow_act: call okenv_flow_set_params first (the policy needs its parameters)");
+        if (!cond)
+            return fail(h, OKENV_ERR_INVALID, "okenv_flow_act: cond is NULL");
+        dropEpisode(h);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkFlowActParams p{};
+        p.st     = h->st;
+        p.N      = h->shape.N;
+        p.s      = okFlowShape(h->flow);
+        p.params = h->d_flow;
+        p.cond   = cond;
+        p.draw   = actDrawWords(h, h->flow_draw_offset);
+        for (int k = 0; k < 2; ++k)
+        {
+            p.lo[k] = h->flow.action_lo[k];
+            p.hi[k] = h->flow.action_hi[k];
+        }
+        p.noise      = h->flow.noise;
+        p.seed       = h->flow.seed;
+        p.agent_base = h->flow.agent_base;
+        if (rec != nullptr)
+            p.rec = *rec;
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + kFlowAgents - 1) / kFlowAgents);
+        hipLaunchKernelGGL(okFlowActKernel, dim3(blocks), dim3(kLidarThreads), okFlowLdsBytes(p.s), h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_flow_act_host(const okenv_flow_config *config, const float *params, int32_t n, const float *cond, const uint8_t *crashed,
+                            uint32_t draw_index, float *throttle, float *steer, float *x0, float *x, uint8_t *alive)
+    {
+        if (const char *why = okFlowCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_flow_act_host: ") + why);
+        if (!params || n < 0 || !cond)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_flow_act_host: bad argument");
+        okFlowActHost(*config, params, n, cond, crashed, draw_index, throttle, steer, x0, x, alive);
         return OKENV_OK;
     }
 

@@ -858,6 +858,53 @@ class BatchedEnvironment:
         rec = capi.fill_pointers(capi.OkenvLidarRecord(), record, "record", sizes)
         capi.check(self._L.okenv_lidar_act(self._h, C.byref(rec)), self._h)
 
+    # ---- flow-matching driver (include/okenv.h) --------------------------------------------------------
+    def flow_create(self, config=None, **members):
+        """Attaches a flow-matching policy (the Euler sampler of the reference's ActionFlowTrunk) to the handle; config: a
+        capi.flow_config(...), or its members by name (the reference's shape and ranges by default).  Returns the floats of its
+        parameter vector."""
+        if config is None:
+            config = capi.flow_config(**members)
+        capi.check(self._L.okenv_flow_create(self._h, C.byref(config)), self._h)
+        self.flow_config = config
+        return self.flow_num_params()
+
+    def flow_num_params(self):
+        n = C.c_int32()
+        capi.check(self._L.okenv_flow_num_params(self._h, C.byref(n)), self._h)
+        return n.value
+
+    def flow_set_params(self, params):
+        """New parameters (the trunk's, in torch's parameters() order: capi.flow_layout) from a float32 numpy array or a device
+        tensor.  No synchronisation."""
+        if hasattr(params, "data_ptr"):
+            assert params.is_contiguous() and params.numel() == self.flow_num_params()
+        else:
+            params = _flat_params(params, self.flow_num_params())
+        capi.check(self._L.okenv_flow_set_params(self._h, capi.ptr(params)), self._h)
+
+    def flow_get_params(self, out=None):
+        """The parameter vector as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
+        if out is None:
+            out = np.empty(self.flow_num_params(), dtype=np.float32)
+        capi.check(self._L.okenv_flow_get_params(self._h, capi.ptr(out)), self._h)
+        return out
+
+    def flow_set_draw_offset(self, word=None):
+        """A device uint32 word (tensor or address) added to the draw index of every later flow_act; None removes it."""
+        capi.check(self._L.okenv_flow_set_draw_offset(self._h, capi.ptr(word)), self._h)
+
+    def flow_act(self, cond, record=None):
+        """The sampled action of every agent from its condition vector, enqueued on the handle's stream without a synchronisation.
+        cond: a device tensor / address of [N, cond_dim] float32.  record: None, or a dict of device tensors / addresses under "x0",
+        "x", "action" [N,2] float32 and "alive" [N] uint8, each optional."""
+        if record is None:
+            capi.check(self._L.okenv_flow_act(self._h, capi.ptr(cond), None), self._h)
+            return
+        sizes = {"x0": self.N * 8, "x": self.N * 8, "action": self.N * 8, "alive": self.N}
+        rec = capi.fill_pointers(capi.OkenvFlowRecord(), record, "record", sizes)
+        capi.check(self._L.okenv_flow_act(self._h, capi.ptr(cond), C.byref(rec)), self._h)
+
     # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) -------------------------------------------------------
     def gcl_create(self, **config):
         """Attaches a GCL object (policy R -> H1 -> H2 -> 2 with log_std, value R -> H1 -> H2 -> 1, cost R + 2 -> C1 -> C2 -> 1) to the

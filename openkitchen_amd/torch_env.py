@@ -547,6 +547,32 @@ class VectorEnvironment:
         ("action" [N,2], "input" [N,R,2] float32, "alive" [N] uint8) that receive the sample."""
         self.env.lidar_act(record)
 
+    # ---- flow-matching driver (include/okenv.h, DESIGN.md section 23) -------------------------------------------------------------
+    def enable_flow_policy(self, config, params):
+        """Attaches the reference's flow-matching policy (FlowMatching: the Euler sampler of ActionFlowTrunk) as a device driver.
+        config: a capi.flow_config(...) or a dict of its members (seed and agent_base default to the environment's); params: the flat
+        vector flow.flow_params_from_state_dict makes, a float32 numpy array or a tensor.  Call it again with new params after
+        training on."""
+        if isinstance(config, dict):
+            config = capi.flow_config(**dict({"seed": self.seed, "agent_base": self.agent_base}, **config))
+        self.env.flow_create(config)
+        if torch.is_tensor(params):
+            params = params.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        self._flow_flat = params  # alive until the next hand-over: the copy is asynchronous
+        self.env.flow_set_params(params)
+        self.flow_config = config
+        self._flow_graphs = {}  # a captured launch carries the old shape and vector
+
+    def flow_act(self, cond, record=None):
+        """The policy's action of every agent from `cond`, a contiguous float32 tensor [N, cond_dim] on this device (the image
+        encoder's output), written into `throttle` / `steering`: one kernel on the environment's stream, no synchronisation, usable
+        inside capture(body).  record: optional dict of device tensors ("x0", "x", "action" [N,2] float32, "alive" [N] uint8) that
+        receive the sample."""
+        if (not torch.is_tensor(cond) or cond.dtype != torch.float32 or not cond.is_contiguous() or cond.device != self.device
+                or tuple(cond.shape) != (self.num_envs, self.flow_config.cond_dim)):
+            raise ValueError("flow_act(cond) needs a contiguous float32 tensor of shape (%d, %d) on %s" % (self.num_envs, self.flow_config.cond_dim, self.device))
+        self.env.flow_act(cond, record)
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
