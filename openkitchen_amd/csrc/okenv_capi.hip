@@ -400,6 +400,17 @@ struct OkUpdateScratch
     OkEventLog log;
 };
 
+// What a family that attaches a network keeps in the handle beside its configuration ("The drivers' life cycle on the host"):
+// the shared entries reach it through the family's DriverKind
+struct OkDriver
+{
+    bool            ok{false};                   // okenv_*_create has run
+    bool            set[3]{false, false, false}; // per parameter vector: okenv_*_set_params has filled it
+    size_t          cap{0};                      // floats of one vector's room
+    float          *d{nullptr}, *d2{nullptr};    // the vectors on the device, [vectors][cap] (d2: a second block, the actor's and DDPG's)
+    const uint32_t *draw_offset{nullptr};        // okenv_*_set_draw_offset's device word
+};
+
 struct okenv
 {
     int         device{0};
@@ -505,10 +516,9 @@ struct okenv
     okenv_expert_params expert{};
     double             *d_expert_tab{nullptr};
     // shared-network actors (okenv_actor_create): parameters, the two networks' vectors (padded to four floats) and what has been set
-    bool               actor_ok{false}, actor_policy_set{false}, actor_value_set{false};
+    // (actor_drv: d the policy's vector, d2 the value's; set[0], set[1] likewise)
+    OkDriver           actor_drv;
     okenv_actor_params actor{};
-    float             *d_actor_policy{nullptr}, *d_actor_value{nullptr};
-    const uint32_t    *actor_draw_offset{nullptr};
     // episode -> batch (okenv_batch_prepare): scratch for the planes, column partials, group counts, statistics and M; grown, never
     // shrunk; the events of the latest timed call
     OkUpdateScratch batch_scratch;
@@ -529,15 +539,13 @@ struct okenv
     bool                    dqn_target_set{false};
     OkUpdateScratch         dqn_scratch;
     // DDPG (okenv_ddpg_create, okenv_ddpg_replay_create): the four networks [actor | critic | actor target | critic target] and the four
-    // moments [actor m | actor v | critic m | critic v], each ddpg_cap floats; the ring, the
+    // moments [actor m | actor v | critic m | critic v], each ddpg_drv.cap floats (ddpg_drv: d the networks, d2 the moments; set[0] the
+    // actor, set[1] the critic); the ring, the
     // update's chunk partials (grown, never shrunk) and timing events.  Nothing here is shared with the actor, the learner or the
     // Deep-Q ring above.
-    bool                    ddpg_ok{false}, ddpg_actor_set{false}, ddpg_critic_set{false};
+    OkDriver                ddpg_drv;
     okenv_ddpg_config       ddpg{};
-    size_t                  ddpg_cap{0};
-    float                  *d_ddpg_nets{nullptr}, *d_ddpg_moments{nullptr};
     int64_t                 ddpg_t{0};
-    const uint32_t         *ddpg_draw_offset{nullptr};
     OkRing                  ddpg_ring{2U * sizeof(float)};
     OkUpdateScratch         ddpg_scratch;
     // REINFORCE (okenv_actor_set_dropout, okenv_reinforce_update): the policy network's dropout, the update's scratch
@@ -546,40 +554,31 @@ struct okenv
     uint32_t                actor_dropout_seed{0};
     OkUpdateScratch         reinforce_scratch;
     // Continuous REINFORCE (okenv_gauss_create, okenv_gauss_learner_create): the parameter vector and Adam's two moments
-    // [params | m | v], each gauss_cap floats, the update's scratch [chunk partials | accumulator] (grown, never shrunk) and timing
+    // [params | m | v], each gauss_drv.cap floats, the update's scratch [chunk partials | accumulator] (grown, never shrunk) and timing
     // events.  Nothing here is shared with the actor, the learner or the DDPG object above.
-    bool                    gauss_ok{false}, gauss_set{false}, gauss_learner_ok{false};
+    OkDriver                gauss_drv;
+    bool                    gauss_learner_ok{false};
     okenv_gauss_config      gauss{};
     okenv_learner_params    gauss_learner{};
-    size_t                  gauss_cap{0};
-    float                  *d_gauss{nullptr};
     int64_t                 gauss_t{0};
-    const uint32_t         *gauss_draw_offset{nullptr};
     OkUpdateScratch         gauss_scratch;
     // Guided cost learning (okenv_gcl_create, okenv_gcl_learner_create): the three networks [policy | value | cost], each
-    // [params | m | v] of gcl_cap floats; the expert bank (grown, never shrunk); per network the update's scratch [chunk partials |
+    // [params | m | v] of gcl_drv.cap floats (gcl_drv.set[which]: the network has its parameters); the expert bank (grown, never shrunk); per network the update's scratch [chunk partials |
     // accumulator] (the policy's also holds its chunks' clip counts) and timing; the advantages' scratch [adv | S, Q partials | mean, std]
-    bool                    gcl_ok{false}, gcl_set[3]{false, false, false}, gcl_learner_ok{false};
+    OkDriver                gcl_drv;
+    bool                    gcl_learner_ok{false};
     okenv_gcl_config        gcl{};
     okenv_learner_params    gcl_learner{}, gcl_cost_learner{};
-    size_t                  gcl_cap{0};
-    float                  *d_gcl{nullptr};
     int64_t                 gcl_t{0}, gcl_cost_t{0};
-    const uint32_t         *gcl_draw_offset{nullptr};
     float                  *d_gcl_bank{nullptr}; // [state rows | action rows]
     int32_t                 gcl_bank_rows{0}, gcl_bank_cap{0};
     OkUpdateScratch         gcl_scratch[3], gcl_adv_scratch;
     // Lidar transformer driver (okenv_lidar_create): the parameter vector in torch's order with the positional table behind it
-    bool                    lidar_ok{false}, lidar_set{false};
+    OkDriver                lidar_drv;
     okenv_lidar_config      lidar{};
-    size_t                  lidar_cap{0};
-    float                  *d_lidar{nullptr};
     // Flow-matching driver (okenv_flow_create): the trunk's parameter vector in torch's order
-    bool                    flow_ok{false}, flow_set{false};
+    OkDriver                flow_drv;
     okenv_flow_config       flow{};
-    size_t                  flow_cap{0};
-    float                  *d_flow{nullptr};
-    const uint32_t         *flow_draw_offset{nullptr};
 };
 
 struct okenv_track
@@ -1203,26 +1202,65 @@ int copyAny(okenv *h, void *dst, const void *src, const size_t bytes)
     return OKENV_OK;
 }
 
+// Buffers of the handle replaced by fresh, zeroed ones (every buffer that is allocated anew on a live handle goes through here): waits
+// for the stream, since an earlier call may still be working in the old ones; releases those from `allocations` and frees them; then
+// allocates each anew.  After a failure the slots that were not reached are nullptr, and the caller's sizes and flags say so already.
+struct OkFresh
+{
+    void **slot;
+    size_t bytes;
+};
+
+template <class T>
+OkFresh fresh(T *&slot, const size_t count)
+{
+    return OkFresh{reinterpret_cast<void **>(&slot), std::max<size_t>(count, 1) * sizeof(T)};
+}
+
+int regrow(okenv *h, const std::initializer_list<OkFresh> buffers)
+{
+    OK_HIP(h, hipStreamSynchronize(h->stream));
+    for (const OkFresh &b : buffers)
+        if (*b.slot != nullptr)
+        {
+            h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), *b.slot), h->allocations.end());
+            (void)hipFree(*b.slot);
+            *b.slot = nullptr;
+        }
+    for (const OkFresh &b : buffers)
+    {
+        uint8_t *p = nullptr;
+        if (const int rc = devAlloc(h, &p, b.bytes))
+            return rc;
+        *b.slot = p;
+    }
+    return OKENV_OK;
+}
+
 // A scratch buffer of the handle that grows to 1.5 x what a call needs and never shrinks (the updates' chunk partials, the batch's
-// planes): the old one is freed behind a wait for the stream, since an earlier call may still be working in it.
+// planes)
 int growScratch(okenv *h, OkUpdateScratch &u, const size_t bytes)
 {
     if (bytes <= u.bytes)
         return OKENV_OK;
-    OK_HIP(h, hipStreamSynchronize(h->stream));
-    if (u.part != nullptr)
-    {
-        h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(u.part)), h->allocations.end());
-        (void)hipFree(u.part);
-        u.part  = nullptr;
-        u.bytes = 0;
-    }
-    uint8_t  *fresh = nullptr;
-    const int rc    = devAlloc(h, &fresh, bytes + bytes / 2U);
-    if (rc != OKENV_OK)
+    u.bytes = 0;
+    if (const int rc = regrow(h, {fresh(u.part, bytes + bytes / 2U)}))
         return rc;
-    u.part  = fresh;
     u.bytes = bytes + bytes / 2U;
+    return OKENV_OK;
+}
+
+// The dynamic-LDS limit of each kernel raised, to the whole budget unless the site knows its need
+template <class Kernel>
+const void *kernelOf(Kernel *kernel)
+{
+    return reinterpret_cast<const void *>(kernel);
+}
+
+int raiseLdsLimit(okenv *h, const std::initializer_list<const void *> kernels, const size_t bytes = kLdsBudget)
+{
+    for (const void *k : kernels)
+        OK_HIP(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
     return OKENV_OK;
 }
 
@@ -1358,16 +1396,228 @@ int sliceUpdate(okenv *h, OkUpdateScratch &u, const int32_t M, const int32_t B, 
     return OKENV_OK;
 }
 
-// Guided cost learning's vectors in d_gcl: network `which` (OKENV_GCL_POLICY / _VALUE / _COST), vector k (0 params, 1 m, 2 v)
+// Guided cost learning's vectors in gcl_drv.d: network `which` (OKENV_GCL_POLICY / _VALUE / _COST), vector k (0 params, 1 m, 2 v)
 float *gclVector(const okenv *h, const int which, const int k)
 {
-    return h->d_gcl + (static_cast<size_t>(which) * 3U + static_cast<size_t>(k)) * h->gcl_cap;
+    return h->gcl_drv.d + (static_cast<size_t>(which) * 3U + static_cast<size_t>(k)) * h->gcl_drv.cap;
+}
+
+// floats of the handle's networks as their configs stand
+int actorPolicyParams(const okenv *h)
+{
+    return ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions);
+}
+
+int actorValueParams(const okenv *h)
+{
+    return h->actor.value_hidden > 0 ? ok_actor_num_params(h->shape.R, h->actor.value_hidden, 1) : 0;
+}
+
+int ddpgActorParams(const okenv *h)
+{
+    return ok_actor_num_params(h->shape.R, h->ddpg.hidden, 2);
+}
+
+int ddpgCriticParams(const okenv *h)
+{
+    return ok_ddpg_critic_params(h->shape.R, h->ddpg.critic_hidden);
+}
+
+int gaussNumParams(const okenv *h)
+{
+    return ok_gauss_num_params(h->shape.R, h->gauss.hidden1, h->gauss.hidden2, 2);
 }
 
 int gclNumParams(const okenv *h, const int which)
 {
     const bool cost = which == OKENV_GCL_COST;
     return ok_gcl_num_params(which, h->shape.R, cost ? h->gcl.cost_hidden1 : h->gcl.hidden1, cost ? h->gcl.cost_hidden2 : h->gcl.hidden2);
+}
+
+// ---- the drivers' life cycle, behind the exported functions' OK_QUIESCE ("The drivers' life cycle on the host") ---------------
+
+// Which family an exported entry works on: its record in the handle, the prefix of its entries' names (for the messages), who "needs its
+// parameters" in act's refusal and in get's, and whether num_params and set_params look at their pointer before the state (the two
+// families that came last do, and refuse a NULL out pointer of num_params; the others write nothing through one)
+struct DriverKind
+{
+    OkDriver okenv::*drv;
+    const char      *prefix;
+    const char      *act_needs, *get_needs;
+    bool             argument_first;
+};
+const DriverKind kActorDriver{&okenv::actor_drv, "okenv_actor_", "every attached network needs its parameters", nullptr, false},
+    kDdpgDriver{&okenv::ddpg_drv, "okenv_ddpg_", "the actor needs its parameters", "both networks need their parameters", false},
+    kGaussDriver{&okenv::gauss_drv, "okenv_gauss_", "the actor needs its parameters", "the actor needs its parameters", false},
+    kGclDriver{&okenv::gcl_drv, "okenv_gcl_", "the policy needs its parameters", "the network needs its parameters", false},
+    kLidarDriver{&okenv::lidar_drv, "okenv_lidar_", "the policy needs its parameters", "the policy needs its parameters", true},
+    kFlowDriver{&okenv::flow_drv, "okenv_flow_", "the policy needs its parameters", "the policy needs its parameters", true};
+
+int driverRefuses(okenv *h, const int code, const DriverKind &k, const char *entry, const std::string &why)
+{
+    return fail(h, code, std::string(k.prefix) + entry + ": " + why);
+}
+
+// The refusals an entry can have, in the order in which the gate looks at them
+enum : unsigned
+{
+    kGateHandle   = 1U,  // a NULL handle is INVALID "NULL handle" (create, act)
+    kGateArgFirst = 2U,  // a NULL handle or argument is INVALID "NULL argument", before the state
+    kGateCreated  = 4U,  // STATE "call ..create first"; also for a NULL handle, which none of the above caught
+    kGateStored   = 8U,  // get's: STATE "<who> needs its parameters first (..create, ..set_params)" unless created and set
+    kGateSet      = 16U, // act's: STATE "call ..set_params first (<who> needs its parameters)" unless set
+    kGateArgLast  = 32U, // a NULL argument is INVALID "NULL argument", behind the state
+};
+
+// need: the set flags (bit i for set[i]) that kGateStored / kGateSet ask for
+int driverGate(okenv *h, const DriverKind &k, const char *entry, const unsigned checks, const bool argument = true, const unsigned need = 0U)
+{
+    const auto prefix = [&k] { return std::string(k.prefix); }; // (only a refusal builds a string)
+    if ((checks & kGateHandle) != 0U && !h)
+        return driverRefuses(h, OKENV_ERR_INVALID, k, entry, "NULL handle");
+    if ((checks & kGateArgFirst) != 0U && (!h || !argument))
+        return driverRefuses(h, OKENV_ERR_INVALID, k, entry, "NULL argument");
+    const OkDriver *d = h != nullptr ? &(h->*k.drv) : nullptr;
+    const bool created = d != nullptr && d->ok;
+    bool       set     = created;
+    for (unsigned i = 0; set && i < 3U; ++i)
+        set = (need >> i & 1U) == 0U || d->set[i];
+    if ((checks & kGateStored) != 0U && !set)
+        return driverRefuses(h, OKENV_ERR_STATE, k, entry, std::string(k.get_needs) + " first (" + prefix() + "create, " + prefix() + "set_params)");
+    if ((checks & kGateCreated) != 0U && !created)
+        return driverRefuses(h, OKENV_ERR_STATE, k, entry, "call " + prefix() + "create first");
+    if ((checks & kGateSet) != 0U && !set)
+        return driverRefuses(h, OKENV_ERR_STATE, k, entry, "call " + prefix() + "set_params first (" + k.act_needs + ")");
+    if ((checks & kGateArgLast) != 0U && !argument)
+        return driverRefuses(h, OKENV_ERR_INVALID, k, entry, "NULL argument");
+    return OKENV_OK;
+}
+
+// okenv_*_create of the families of fixed capacity, behind their gate and config check: room for the widest network once (`vectors` of
+// `cap` floats in d, `vectors2` in d2), so that a later create with other widths allocates nothing; the kernels' LDS limit; the vectors
+// zeroed on the stream where the family keeps Adam's moments among them.  The caller stores its config and resets its own dependants.
+int driverCreateFixed(okenv *h, const DriverKind &k, const size_t cap, const size_t vectors, const size_t vectors2, const bool zero,
+                      const std::initializer_list<const void *> kernels)
+{
+    OkDriver &d = h->*k.drv;
+    d.cap       = cap;
+    int rc      = devEnsure(h, &d.d, vectors * cap);
+    if (rc != OKENV_OK || (vectors2 > 0U && (rc = devEnsure(h, &d.d2, vectors2 * cap)) != OKENV_OK) || (rc = raiseLdsLimit(h, kernels)) != OKENV_OK)
+        return rc;
+    if (zero)
+    {
+        OK_HIP(h, hipMemsetAsync(d.d, 0, vectors * cap * sizeof(float), h->stream));
+        if (vectors2 > 0U)
+            OK_HIP(h, hipMemsetAsync(d.d2, 0, vectors2 * cap * sizeof(float), h->stream));
+    }
+    d.ok = true;
+    for (bool &set : d.set)
+        set = false;
+    return OKENV_OK;
+}
+
+// okenv_*_create of the families whose one vector grows on demand, behind their gate and config check: detached before the allocation,
+// so that a failed one leaves the driver so; the room is kept when it suffices, and the parameters are forgotten either way
+int driverCreateFlat(okenv *h, const DriverKind &k, const size_t total, const void *kernel)
+{
+    OK_HIP(h, hipSetDevice(h->device));
+    OkDriver &d = h->*k.drv;
+    d.ok        = false;
+    d.set[0]    = false;
+    if (total > d.cap)
+    {
+        d.cap = 0;
+        if (const int rc = regrow(h, {fresh(d.d, total)}))
+            return rc;
+        d.cap = total;
+    }
+    if (const int rc = raiseLdsLimit(h, {kernel}))
+        return rc;
+    d.ok = true;
+    return OKENV_OK;
+}
+
+// One parameter vector of a set or get: where it lies on the device, the caller's pointer (host or device; nullptr: not this one), its
+// floats, and the set flag that a set raises
+struct OkVector
+{
+    float *device;
+    void  *other;
+    size_t floats;
+    int    flag;
+};
+
+OkVector vectorOf(float *device, const void *other, const int floats, const int flag = 0)
+{
+    return OkVector{device, const_cast<void *>(other), static_cast<size_t>(floats), flag};
+}
+
+// okenv_*_set_params behind the gate: copies on the stream, no synchronisation
+int driverSet(okenv *h, const DriverKind &k, const std::initializer_list<OkVector> vectors)
+{
+    OK_HIP(h, hipSetDevice(h->device));
+    for (const OkVector &v : vectors)
+        if (v.other != nullptr)
+        {
+            if (const int rc = copyAny(h, v.device, v.other, sizeof(float) * v.floats))
+                return rc;
+            (h->*k.drv).set[v.flag] = true;
+        }
+    return OKENV_OK;
+}
+
+// okenv_*_get_params / _get_state behind the gate: copies on the stream and waits for it
+int driverGet(okenv *h, const std::initializer_list<OkVector> vectors)
+{
+    OK_HIP(h, hipSetDevice(h->device));
+    for (const OkVector &v : vectors)
+        if (v.other != nullptr)
+            if (const int rc = copyAny(h, v.other, v.device, sizeof(float) * v.floats))
+                return rc;
+    OK_HIP(h, hipStreamSynchronize(h->stream));
+    return OKENV_OK;
+}
+
+int driverSetDrawOffset(okenv *h, const DriverKind &k, const uint32_t *device_word)
+{
+    if (const int rc = driverGate(h, k, "set_draw_offset", kGateCreated))
+        return rc;
+    (h->*k.drv).draw_offset = device_word;
+    return OKENV_OK;
+}
+
+// greedy_of: the family's config member
+template <class Config>
+int driverSetGreedy(okenv *h, const DriverKind &k, Config okenv::*config, const int32_t greedy)
+{
+    if (const int rc = driverGate(h, k, "set_greedy", kGateCreated))
+        return rc;
+    if (greedy != 0 && greedy != 1)
+        return driverRefuses(h, OKENV_ERR_INVALID, k, "set_greedy", "greedy must be 0 or 1");
+    (h->*config).greedy = greedy;
+    return OKENV_OK;
+}
+
+// How every okenv_*_act opens: the gate, then the entry's own last refusal (`missing`: nullptr or its text), the episode dropped, the device
+int actBegin(okenv *h, const DriverKind &k, const unsigned need, const char *missing = nullptr)
+{
+    if (const int rc = driverGate(h, k, "act", kGateHandle | kGateCreated | kGateSet, true, need))
+        return rc;
+    if (missing != nullptr)
+        return driverRefuses(h, OKENV_ERR_INVALID, k, "act", missing);
+    dropEpisode(h);
+    OK_HIP(h, hipSetDevice(h->device));
+    return OKENV_OK;
+}
+
+// ... and how it closes: one workgroup of `threads` per `agents` agents, on the stream
+template <class Params>
+int actLaunch(okenv *h, void (*kernel)(Params), const int agents, const unsigned threads, const size_t lds, const Params &p)
+{
+    const unsigned blocks = static_cast<unsigned>((h->shape.N + agents - 1) / agents);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, h->stream, p);
+    OK_HIP(h, hipGetLastError());
+    return OKENV_OK;
 }
 
 // ---- the replay rings' entries, behind the exported functions' OK_QUIESCE ---------------------------------------------------------
@@ -1412,27 +1662,16 @@ int ringCreate(okenv *h, const RingKind &k, const int32_t capacity, const uint32
         return fail(h, OKENV_ERR_INVALID, name + "the fan needs 1 .. " + std::to_string(k.max_rays) + " rays");
     OkRing &r = h->*k.ring;
     OK_HIP(h, hipSetDevice(h->device));
-    OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still working in an earlier ring
     r.ok = false;
-    void *const old[5] = {r.state, r.next_state, r.action, r.reward, r.done};
-    for (void *q : old)
-        if (q != nullptr)
-        {
-            h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), q), h->allocations.end());
-            (void)hipFree(q);
-        }
-    r.state = r.next_state = r.reward = r.done = nullptr;
-    r.action                                   = nullptr;
     const size_t C = static_cast<size_t>(capacity), R = static_cast<size_t>(h->shape.R);
     const size_t blocks = (static_cast<size_t>(h->shape.N) + kReplayThreads - 1U) / kReplayThreads;
-    int          rc = devAlloc(h, &r.state, C * R);
-    if (rc != OKENV_OK || (rc = devAlloc(h, &r.next_state, C * R)) != OKENV_OK || (rc = devAlloc(h, &r.action, C * r.action_bytes)) != OKENV_OK ||
-        (rc = devAlloc(h, &r.reward, C)) != OKENV_OK || (rc = devAlloc(h, &r.done, C)) != OKENV_OK ||
-        (rc = devEnsure(h, &r.d_words, 2)) != OKENV_OK || (rc = devEnsure(h, &r.d_counts, blocks)) != OKENV_OK)
+    // (the wait: nobody is still working in an earlier ring)
+    int rc = regrow(h, {fresh(r.state, C * R), fresh(r.next_state, C * R), fresh(r.action, C * r.action_bytes), fresh(r.reward, C), fresh(r.done, C)});
+    if (rc != OKENV_OK || (rc = devEnsure(h, &r.d_words, 2)) != OKENV_OK || (rc = devEnsure(h, &r.d_counts, blocks)) != OKENV_OK)
         return rc;
     OK_HIP(h, hipMemsetAsync(r.d_words, 0, 2U * sizeof(uint64_t), h->stream));
-    if (lds_kernel != nullptr)
-        OK_HIP(h, hipFuncSetAttribute(lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+    if (lds_kernel != nullptr && (rc = raiseLdsLimit(h, {lds_kernel})) != OKENV_OK)
+        return rc;
     OK_HIP(h, hipStreamSynchronize(h->stream));
     r.capacity = capacity;
     r.flags    = flags;
@@ -1741,45 +1980,20 @@ extern "C"
                 h->shape.fb_ok = true;
             }
             OK_HIP(nullptr, hipStreamSynchronize(h->stream));
-            const int lds_plain = static_cast<int>(h->shape.image_bytes);
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepKernel<kGridLds, kPolicyNone>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_plain));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepKernel<kGridLds, kPolicyMlp>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_plain));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyNone>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyNone, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyNone, true, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyNone, false, false, false, 64, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyNone, false, false, false, 64>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyNone, false, false, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyNone, true, false, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyNone, true, true, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyMlp>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyQ>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyCtrl>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepCoopKernel<kPolicyMlp, false, false, false, 32>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepTailKernel<kPolicyMlp, 32>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepTailKernel<kPolicyMlp, 15>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepTailKernel<kPolicyMlp, 0>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okStepTailKernel<kPolicyQ, 0>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-            OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDebugCastKernel<kGridLds>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(h->shape.image_bytes)));
+            if ((rc = raiseLdsLimit(nullptr, {kernelOf(okStepKernel<kGridLds, kPolicyNone>), kernelOf(okStepKernel<kGridLds, kPolicyMlp>),
+                                              kernelOf(okDebugCastKernel<kGridLds>)}, h->shape.image_bytes)) != OKENV_OK ||
+                (rc = raiseLdsLimit(nullptr, {kernelOf(okStepCoopKernel<kPolicyNone>), kernelOf(okStepCoopKernel<kPolicyNone, true>),
+                                              kernelOf(okStepCoopKernel<kPolicyNone, true, true>),
+                                              kernelOf(okStepCoopKernel<kPolicyNone, false, false, false, 64, true>),
+                                              kernelOf(okStepCoopKernel<kPolicyNone, false, false, false, 64>),
+                                              kernelOf(okStepCoopKernel<kPolicyNone, false, false, true>),
+                                              kernelOf(okStepCoopKernel<kPolicyNone, true, false, true>),
+                                              kernelOf(okStepCoopKernel<kPolicyNone, true, true, true>), kernelOf(okStepCoopKernel<kPolicyMlp>),
+                                              kernelOf(okStepCoopKernel<kPolicyQ>), kernelOf(okStepCoopKernel<kPolicyCtrl>),
+                                              kernelOf(okStepCoopKernel<kPolicyMlp, false, false, false, 32>),
+                                              kernelOf(okStepTailKernel<kPolicyMlp, 32>), kernelOf(okStepTailKernel<kPolicyMlp, 15>),
+                                              kernelOf(okStepTailKernel<kPolicyMlp, 0>), kernelOf(okStepTailKernel<kPolicyQ, 0>)})) != OKENV_OK)
+                return rc;
         }
         else if (h->shape.grid_mode == kGridGlobal)
         {
@@ -2720,72 +2934,48 @@ extern "C"
     int okenv_actor_create(okenv_t h, const okenv_actor_params *params)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_actor_create: NULL handle");
+        if (const int rc = driverGate(h, kActorDriver, "create", kGateHandle))
+            return rc;
         if (const char *why = okActorCheckParams(params, h->shape.R))
-            return fail(h, OKENV_ERR_INVALID, std::string("okenv_actor_create: ") + why);
+            return driverRefuses(h, OKENV_ERR_INVALID, kActorDriver, "create", why);
         OK_HIP(h, hipSetDevice(h->device));
         // room for the widest networks of this fan, so that a later create with other widths allocates nothing
         const size_t cap = static_cast<size_t>(ok_actor_num_params(h->shape.R, OK_ACTOR_MAX_HIDDEN, OK_ACTOR_MAX_ACTIONS)) + 4U;
-        int          rc  = devEnsure(h, &h->d_actor_policy, cap);
-        if (rc != OKENV_OK || (rc = devEnsure(h, &h->d_actor_value, cap)) != OKENV_OK)
+        if (const int rc = driverCreateFixed(h, kActorDriver, cap, 1, 1, false, {kernelOf(okActorKernel<false>), kernelOf(okActorKernel<true>)}))
             return rc;
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okActorKernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(kLdsBudget)));
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okActorKernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(kLdsBudget)));
-        h->actor            = *params;
-        h->actor_dropout    = 0.F; // (okenv_actor_set_dropout is per actor)
-        h->actor_ok         = true;
-        h->actor_policy_set = false;
-        h->actor_value_set  = false;
-        h->learner_ok       = false; // (Adam's moments belong to the networks that were just replaced)
-        h->dqn_target_set   = false; // (and so does the target network's copy)
+        h->actor          = *params;
+        h->actor_dropout  = 0.F;   // (okenv_actor_set_dropout is per actor)
+        h->learner_ok     = false; // (Adam's moments belong to the networks that were just replaced)
+        h->dqn_target_set = false; // (and so does the target network's copy)
         return OKENV_OK;
     }
 
     int okenv_actor_num_params(okenv_t h, int32_t *policy, int32_t *value)
     {
         OK_QUIESCE(h);
-        if (!h || !h->actor_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_actor_num_params: call okenv_actor_create first");
+        if (const int rc = driverGate(h, kActorDriver, "num_params", kGateCreated))
+            return rc;
         if (policy)
-            *policy = ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions);
+            *policy = actorPolicyParams(h);
         if (value)
-            *value = h->actor.value_hidden > 0 ? ok_actor_num_params(h->shape.R, h->actor.value_hidden, 1) : 0;
+            *value = actorValueParams(h);
         return OKENV_OK;
     }
 
     int okenv_actor_set_params(okenv_t h, const float *policy, const float *value)
     {
         OK_QUIESCE(h);
-        if (!h || !h->actor_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_actor_set_params: call okenv_actor_create first");
+        if (const int rc = driverGate(h, kActorDriver, "set_params", kGateCreated))
+            return rc;
         if (value != nullptr && h->actor.value_hidden == 0)
             return fail(h, OKENV_ERR_INVALID, "okenv_actor_set_params: the actor has no value network");
-        OK_HIP(h, hipSetDevice(h->device));
-        int rc = OKENV_OK;
-        if (policy != nullptr)
-        {
-            rc = copyAny(h, h->d_actor_policy, policy, sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions)));
-            if (rc != OKENV_OK)
-                return rc;
-            h->actor_policy_set = true;
-        }
-        if (value != nullptr)
-        {
-            rc = copyAny(h, h->d_actor_value, value, sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.value_hidden, 1)));
-            if (rc != OKENV_OK)
-                return rc;
-            h->actor_value_set = true;
-        }
-        return OKENV_OK;
+        return driverSet(h, kActorDriver, {vectorOf(h->actor_drv.d, policy, actorPolicyParams(h), 0), vectorOf(h->actor_drv.d2, value, actorValueParams(h), 1)});
     }
 
     int okenv_actor_set_epsilon(okenv_t h, float epsilon)
     {
         OK_QUIESCE(h);
-        if (!h || !h->actor_ok)
+        if (!h || !h->actor_drv.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_actor_set_epsilon: call okenv_actor_create first");
         if (!(epsilon >= 0.F && epsilon <= 1.F))
             return fail(h, OKENV_ERR_INVALID, "okenv_actor_set_epsilon: epsilon outside [0, 1]");
@@ -2796,41 +2986,26 @@ extern "C"
     int okenv_actor_set_draw_offset(okenv_t h, const uint32_t *device_word)
     {
         OK_QUIESCE(h);
-        if (!h || !h->actor_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_actor_set_draw_offset: call okenv_actor_create first");
-        h->actor_draw_offset = device_word;
-        return OKENV_OK;
+        return driverSetDrawOffset(h, kActorDriver, device_word);
     }
 
     int okenv_actor_act(okenv_t h, const okenv_actor_record *rec)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_actor_act: NULL handle");
-        if (!h->actor_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_actor_act: call okenv_actor_create first");
-        if (!h->actor_policy_set || (h->actor.value_hidden > 0 && !h->actor_value_set))
-            return fail(h, OKENV_ERR_STATE, "okenv_actor_act: call okenv_actor_set_params first (every attached network needs its parameters)");
-        dropEpisode(h);
-        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = actBegin(h, kActorDriver, h != nullptr && h->actor.value_hidden > 0 ? 3U : 1U))
+            return rc;
         OkActorParams p{};
         p.f      = actFrame(h);
-        p.draw   = actDrawWords(h, h->actor_draw_offset);
-        p.policy = h->d_actor_policy;
-        p.value  = h->d_actor_value;
+        p.draw   = actDrawWords(h, h->actor_drv.draw_offset);
+        p.policy = h->actor_drv.d;
+        p.value  = h->actor_drv.d2;
         p.ap     = h->actor;
         if (rec != nullptr)
             p.rec = *rec;
-        const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
         if (h->actor_dropout > 0.F)
-        {
             p.drop = ok_reinforce_mask{h->actor_dropout, ok_reinforce_scale(h->actor_dropout), h->actor_dropout_seed, 0U, 0U};
-            hipLaunchKernelGGL(okActorKernel<true>, dim3(blocks), dim3(kActorThreads), okActorLdsBytes(h->shape.R, h->actor), h->stream, p);
-        }
-        else
-            hipLaunchKernelGGL(okActorKernel<false>, dim3(blocks), dim3(kActorThreads), okActorLdsBytes(h->shape.R, h->actor), h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return actLaunch(h, h->actor_dropout > 0.F ? okActorKernel<true> : okActorKernel<false>, kActorAgents, kActorThreads,
+                         okActorLdsBytes(h->shape.R, h->actor), p);
     }
 
     int okenv_actor_act_host(const okenv_actor_params *params, const float *policy, const float *value, int32_t num_rays, int32_t n, const float *dist,
@@ -2955,17 +3130,15 @@ extern "C"
             return fail(h, OKENV_ERR_INVALID, "okenv_learner_create: NULL handle");
         if (const char *why = okLearnCheckParams(params))
             return fail(h, OKENV_ERR_INVALID, std::string("okenv_learner_create: ") + why);
-        if (!h->actor_ok || !h->actor_policy_set || (h->actor.value_hidden > 0 && !h->actor_value_set))
+        if (!h->actor_drv.ok || !h->actor_drv.set[0] || (h->actor.value_hidden > 0 && !h->actor_drv.set[1]))
             return fail(h, OKENV_ERR_STATE, "okenv_learner_create: needs an actor whose networks have their parameters (okenv_actor_create, okenv_actor_set_params)");
         OK_HIP(h, hipSetDevice(h->device));
         h->learn_cap = static_cast<size_t>(ok_actor_num_params(h->shape.R, OK_ACTOR_MAX_HIDDEN, OK_ACTOR_MAX_ACTIONS)) + 4U;
         const int rc = devEnsure(h, &h->d_learn_moments, 4U * h->learn_cap);
         if (rc != OKENV_OK)
             return rc;
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okLearnGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(kLdsBudget)));
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okReinforceGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(kLdsBudget)));
+        if (const int lrc = raiseLdsLimit(h, {kernelOf(okLearnGradKernel), kernelOf(okReinforceGradKernel)}))
+            return lrc;
         OK_HIP(h, hipMemsetAsync(h->d_learn_moments, 0, 4U * h->learn_cap * sizeof(float), h->stream));
         h->learner    = *params;
         h->learn_t    = 0;
@@ -2989,7 +3162,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_ppo_update: NULL handle");
-        if (!h->learner_ok || !h->actor_ok)
+        if (!h->learner_ok || !h->actor_drv.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_ppo_update: call okenv_learner_create first");
         if (h->actor_dropout > 0.F)
             return fail(h, OKENV_ERR_STATE, "okenv_ppo_update: the actor's dropout is on (okenv_actor_set_dropout) and this update's forward knows no mask");
@@ -3008,8 +3181,8 @@ extern "C"
         p.in   = *batch;
         p.lo   = okLearnClipLo(h->learner.clip);
         p.hi   = okLearnClipHi(h->learner.clip);
-        p.policy = h->d_actor_policy;
-        p.value  = h->d_actor_value;
+        p.policy = h->actor_drv.d;
+        p.value  = h->actor_drv.d2;
         p.pol_m  = h->d_learn_moments;
         p.pol_v  = h->d_learn_moments + h->learn_cap;
         p.val_m  = h->d_learn_moments + 2U * h->learn_cap;
@@ -3068,20 +3241,11 @@ extern "C"
     int okenv_actor_get_params(okenv_t h, float *policy, float *value)
     {
         OK_QUIESCE(h);
-        if (!h || !h->actor_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_actor_get_params: call okenv_actor_create first");
-        if ((policy != nullptr && !h->actor_policy_set) || (value != nullptr && !h->actor_value_set))
-            return fail(h, OKENV_ERR_STATE, "okenv_actor_get_params: the network has no parameters yet (okenv_actor_set_params)");
-        OK_HIP(h, hipSetDevice(h->device));
-        int rc = OKENV_OK;
-        if (policy != nullptr)
-            rc = copyAny(h, policy, h->d_actor_policy, sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions)));
-        if (rc == OKENV_OK && value != nullptr)
-            rc = copyAny(h, value, h->d_actor_value, sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.value_hidden, 1)));
-        if (rc != OKENV_OK)
+        if (const int rc = driverGate(h, kActorDriver, "get_params", kGateCreated))
             return rc;
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        return OKENV_OK;
+        if ((policy != nullptr && !h->actor_drv.set[0]) || (value != nullptr && !h->actor_drv.set[1]))
+            return fail(h, OKENV_ERR_STATE, "okenv_actor_get_params: the network has no parameters yet (okenv_actor_set_params)");
+        return driverGet(h, {vectorOf(h->actor_drv.d, policy, actorPolicyParams(h)), vectorOf(h->actor_drv.d2, value, actorValueParams(h))});
     }
 
     int okenv_learner_get_state(okenv_t h, float *policy_m, float *policy_v, float *value_m, float *value_v, int64_t *t)
@@ -3133,7 +3297,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_actor_set_dropout: NULL handle");
-        if (!h->actor_ok)
+        if (!h->actor_drv.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_actor_set_dropout: call okenv_actor_create first");
         if (!(p >= 0.F && p < 1.F))
             return fail(h, OKENV_ERR_INVALID, "okenv_actor_set_dropout: p outside [0, 1)");
@@ -3163,7 +3327,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_reinforce_update: NULL handle");
-        if (!h->learner_ok || !h->actor_ok)
+        if (!h->learner_ok || !h->actor_drv.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_reinforce_update: call okenv_learner_create first");
         if (const char *why = okReinforceCheckCall(config, batch, M, B, h->actor_dropout > 0.F))
             return fail(h, OKENV_ERR_INVALID, std::string("okenv_reinforce_update: ") + why);
@@ -3181,10 +3345,10 @@ extern "C"
         p.draw_first = config->draw_first;
         p.N          = config->num_agents;
         p.order      = order;
-        p.policy     = h->d_actor_policy;
+        p.policy     = h->actor_drv.d;
         const okenv_reinforce_output none{};
         const okenv_reinforce_output &o = out != nullptr ? *out : none;
-        const OkJoinParams j   = okJoinOn(p.Pp, h->d_actor_policy, h->d_learn_moments, h->d_learn_moments + h->learn_cap, config->reduce, o.grad_policy);
+        const OkJoinParams j   = okJoinOn(p.Pp, h->actor_drv.d, h->d_learn_moments, h->d_learn_moments + h->learn_cap, config->reduce, o.grad_policy);
         const size_t       lds = okReinforceLdsBytes(p.R, p.H, p.A);
         return sliceUpdate(h, h->reinforce_scratch, M, B, config->accumulate != 0, j, h->learn_t, h->learner, o.loss,
                            [&](const long base, const int Bk, const int C)
@@ -3281,12 +3445,12 @@ extern "C"
             return fail(h, OKENV_ERR_INVALID, "okenv_dqn_sync_target: NULL handle");
         if (h->dqn.target_network == 0 || h->d_dqn_target == nullptr)
             return fail(h, OKENV_ERR_STATE, "okenv_dqn_sync_target: okenv_dqn_params has not turned the target network on");
-        if (!h->actor_ok || !h->actor_policy_set)
+        if (!h->actor_drv.ok || !h->actor_drv.set[0])
             return fail(h, OKENV_ERR_STATE, "okenv_dqn_sync_target: the actor has no parameters yet (okenv_actor_create, okenv_actor_set_params)");
         OK_HIP(h, hipSetDevice(h->device));
         // (whole float4s: the kernels stage a network in 16-byte loads, and the actor's vector is padded the same way)
         const size_t n = (static_cast<size_t>(ok_actor_num_params(h->shape.R, h->actor.hidden, h->actor.num_actions)) + 3U) & ~static_cast<size_t>(3U);
-        OK_HIP(h, hipMemcpyAsync(h->d_dqn_target, h->d_actor_policy, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        OK_HIP(h, hipMemcpyAsync(h->d_dqn_target, h->actor_drv.d, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         h->dqn_target_set = true;
         return OKENV_OK;
     }
@@ -3312,7 +3476,7 @@ extern "C"
         if (turned_on)
         { // (an earlier copy is stale: the switch going on is a sync, or the wait for one)
             h->dqn_target_set = false;
-            if (h->actor_ok && h->actor_policy_set)
+            if (h->actor_drv.ok && h->actor_drv.set[0])
                 return okenv_dqn_sync_target(h);
         }
         return OKENV_OK;
@@ -3323,7 +3487,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_dqn_update: NULL handle");
-        if (!h->learner_ok || !h->actor_ok)
+        if (!h->learner_ok || !h->actor_drv.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: call okenv_learner_create first");
         if (h->actor_dropout > 0.F)
             return fail(h, OKENV_ERR_STATE, "okenv_dqn_update: the actor's dropout is on (okenv_actor_set_dropout) and this update's forward knows no mask");
@@ -3345,10 +3509,10 @@ extern "C"
         p.capacity = static_cast<uint64_t>(h->replay.capacity);
         p.pushed   = h->replay.d_words;
         p.ring     = ringFields<okenv_replay_ring>(h->replay);
-        p.policy   = h->d_actor_policy;
+        p.policy   = h->actor_drv.d;
         p.pol_m    = h->d_learn_moments;
         p.pol_v    = h->d_learn_moments + h->learn_cap;
-        p.target   = h->dqn.target_network != 0 ? h->d_dqn_target : h->d_actor_policy;
+        p.target   = h->dqn.target_network != 0 ? h->d_dqn_target : h->actor_drv.d;
         p.gamma    = h->dqn.gamma;
         p.flags    = h->dqn.flags;
         p.seed     = h->dqn.seed;
@@ -3445,65 +3609,48 @@ extern "C"
     int okenv_gauss_create(okenv_t h, const okenv_gauss_config *config)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_create: NULL handle");
-        if (const char *why = okGaussCheckConfig(config, h->shape.R))
-            return fail(h, OKENV_ERR_INVALID, std::string("okenv_gauss_create: ") + why);
-        OK_HIP(h, hipSetDevice(h->device));
-        // room for the widest network, so that a later create with other widths allocates nothing
-        h->gauss_cap = (static_cast<size_t>(ok_gauss_num_params(OK_ACTOR_MAX_RAYS, OK_GAUSS_MAX_HIDDEN, OK_GAUSS_MAX_HIDDEN, 2)) + 3U) & ~static_cast<size_t>(3U);
-        if (const int rc = devEnsure(h, &h->d_gauss, 3U * h->gauss_cap))
+        if (const int rc = driverGate(h, kGaussDriver, "create", kGateHandle))
             return rc;
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okGaussActKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okGaussGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-        OK_HIP(h, hipMemsetAsync(h->d_gauss, 0, 3U * h->gauss_cap * sizeof(float), h->stream));
+        if (const char *why = okGaussCheckConfig(config, h->shape.R))
+            return driverRefuses(h, OKENV_ERR_INVALID, kGaussDriver, "create", why);
+        OK_HIP(h, hipSetDevice(h->device));
+        // room for the widest network, so that a later create with other widths allocates nothing: [params | m | v]
+        const size_t cap = (static_cast<size_t>(ok_gauss_num_params(OK_ACTOR_MAX_RAYS, OK_GAUSS_MAX_HIDDEN, OK_GAUSS_MAX_HIDDEN, 2)) + 3U) & ~static_cast<size_t>(3U);
+        if (const int rc = driverCreateFixed(h, kGaussDriver, cap, 3, 0, true, {kernelOf(okGaussActKernel), kernelOf(okGaussGradKernel)}))
+            return rc;
         h->gauss            = *config;
         h->gauss_t          = 0;
-        h->gauss_set        = false;
         h->gauss_learner_ok = false;
-        h->gauss_ok         = true;
         return OKENV_OK;
     }
 
     int okenv_gauss_num_params(okenv_t h, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (!h || !h->gauss_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gauss_num_params: call okenv_gauss_create first");
+        if (const int rc = driverGate(h, kGaussDriver, "num_params", kGateCreated))
+            return rc;
         if (num_params)
-            *num_params = ok_gauss_num_params(h->shape.R, h->gauss.hidden1, h->gauss.hidden2, 2);
+            *num_params = gaussNumParams(h);
         return OKENV_OK;
     }
 
     int okenv_gauss_set_params(okenv_t h, const float *params)
     {
         OK_QUIESCE(h);
-        if (!h || !h->gauss_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gauss_set_params: call okenv_gauss_create first");
-        if (!params)
-            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_set_params: NULL argument");
-        OK_HIP(h, hipSetDevice(h->device));
-        if (const int rc = copyAny(h, h->d_gauss, params, sizeof(float) * static_cast<size_t>(ok_gauss_num_params(h->shape.R, h->gauss.hidden1, h->gauss.hidden2, 2))))
+        if (const int rc = driverGate(h, kGaussDriver, "set_params", kGateCreated | kGateArgLast, params != nullptr))
             return rc;
-        h->gauss_set = true;
-        return OKENV_OK;
+        return driverSet(h, kGaussDriver, {vectorOf(h->gauss_drv.d, params, gaussNumParams(h))});
     }
 
     int okenv_gauss_get_state(okenv_t h, okenv_gauss_state *out)
     {
         OK_QUIESCE(h);
-        if (!h || !out)
-            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_get_state: NULL argument");
-        if (!h->gauss_ok || !h->gauss_set)
-            return fail(h, OKENV_ERR_STATE, "okenv_gauss_get_state: the actor needs its parameters first (okenv_gauss_create, okenv_gauss_set_params)");
-        OK_HIP(h, hipSetDevice(h->device));
-        const size_t bytes  = sizeof(float) * static_cast<size_t>(ok_gauss_num_params(h->shape.R, h->gauss.hidden1, h->gauss.hidden2, 2));
-        float *const dst[3] = {out->params, out->m, out->v};
-        for (size_t k = 0; k < 3U; ++k)
-            if (dst[k] != nullptr)
-                if (const int rc = copyAny(h, dst[k], h->d_gauss + k * h->gauss_cap, bytes))
-                    return rc;
-        OK_HIP(h, hipStreamSynchronize(h->stream));
+        if (const int rc = driverGate(h, kGaussDriver, "get_state", kGateArgFirst | kGateStored, out != nullptr, 1U))
+            return rc;
+        const OkDriver &d = h->gauss_drv;
+        const int       n = gaussNumParams(h);
+        if (const int rc = driverGet(h, {vectorOf(d.d, out->params, n), vectorOf(d.d + d.cap, out->m, n), vectorOf(d.d + 2U * d.cap, out->v, n)}))
+            return rc;
         out->t = h->gauss_t;
         return OKENV_OK;
     }
@@ -3520,40 +3667,26 @@ extern "C"
     int okenv_gauss_set_draw_offset(okenv_t h, const uint32_t *device_word)
     {
         OK_QUIESCE(h);
-        if (!h || !h->gauss_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gauss_set_draw_offset: call okenv_gauss_create first");
-        h->gauss_draw_offset = device_word;
-        return OKENV_OK;
+        return driverSetDrawOffset(h, kGaussDriver, device_word);
     }
 
     int okenv_gauss_set_greedy(okenv_t h, int32_t greedy)
     {
         OK_QUIESCE(h);
-        if (!h || !h->gauss_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gauss_set_greedy: call okenv_gauss_create first");
-        if (greedy != 0 && greedy != 1)
-            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_set_greedy: greedy must be 0 or 1");
-        h->gauss.greedy = greedy;
-        return OKENV_OK;
+        return driverSetGreedy(h, kGaussDriver, &okenv::gauss, greedy);
     }
 
     int okenv_gauss_act(okenv_t h, const okenv_gauss_record *rec)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_gauss_act: NULL handle");
-        if (!h->gauss_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gauss_act: call okenv_gauss_create first");
-        if (!h->gauss_set)
-            return fail(h, OKENV_ERR_STATE, "okenv_gauss_act: call okenv_gauss_set_params first (the actor needs its parameters)");
-        dropEpisode(h);
-        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = actBegin(h, kGaussDriver, 1U))
+            return rc;
         OkGaussActParams p{};
         p.f      = actFrame(h);
-        p.draw   = actDrawWords(h, h->gauss_draw_offset);
+        p.draw   = actDrawWords(h, h->gauss_drv.draw_offset);
         p.H1     = h->gauss.hidden1;
         p.H2     = h->gauss.hidden2;
-        p.params = h->d_gauss;
+        p.params = h->gauss_drv.d;
         for (int k = 0; k < 2; ++k)
         {
             p.scale[k] = h->gauss.scale[k];
@@ -3564,10 +3697,7 @@ extern "C"
         p.agent_base = h->gauss.agent_base;
         if (rec != nullptr)
             p.rec = *rec;
-        const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
-        hipLaunchKernelGGL(okGaussActKernel, dim3(blocks), dim3(kActorThreads), okGaussActLdsBytes(p.f.R, p.H1, p.H2), h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return actLaunch(h, okGaussActKernel, kActorAgents, kActorThreads, okGaussActLdsBytes(p.f.R, p.H1, p.H2), p);
     }
 
     int okenv_gauss_learner_create(okenv_t h, const okenv_learner_params *params)
@@ -3577,10 +3707,10 @@ extern "C"
             return fail(h, OKENV_ERR_INVALID, "okenv_gauss_learner_create: NULL handle");
         if (const char *why = okLearnCheckParams(params))
             return fail(h, OKENV_ERR_INVALID, std::string("okenv_gauss_learner_create: ") + why);
-        if (!h->gauss_ok || !h->gauss_set)
+        if (!h->gauss_drv.ok || !h->gauss_drv.set[0])
             return fail(h, OKENV_ERR_STATE, "okenv_gauss_learner_create: needs a Gaussian actor with its parameters (okenv_gauss_create, okenv_gauss_set_params)");
         OK_HIP(h, hipSetDevice(h->device));
-        OK_HIP(h, hipMemsetAsync(h->d_gauss + h->gauss_cap, 0, 2U * h->gauss_cap * sizeof(float), h->stream));
+        OK_HIP(h, hipMemsetAsync(h->gauss_drv.d + h->gauss_drv.cap, 0, 2U * h->gauss_drv.cap * sizeof(float), h->stream));
         h->gauss_learner    = *params;
         h->gauss_t          = 0;
         h->gauss_learner_ok = true;
@@ -3593,7 +3723,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_gauss_update: NULL handle");
-        if (!h->gauss_ok || !h->gauss_learner_ok)
+        if (!h->gauss_drv.ok || !h->gauss_learner_ok)
             return fail(h, OKENV_ERR_STATE, "okenv_gauss_update: call okenv_gauss_learner_create first");
         if (const char *why = okGaussCheckCall(config, batch, M, B))
             return fail(h, OKENV_ERR_INVALID, std::string("okenv_gauss_update: ") + why);
@@ -3609,11 +3739,11 @@ extern "C"
         p.in     = *batch;
         p.mode   = config->grad_mode;
         p.order  = order;
-        p.params = h->d_gauss;
+        p.params = h->gauss_drv.d;
         // the join kernels are section 19's, on this parameter vector
         const okenv_gauss_output none{};
         const okenv_gauss_output &o = out != nullptr ? *out : none;
-        const OkJoinParams j   = okJoinOn(p.P, h->d_gauss, h->d_gauss + h->gauss_cap, h->d_gauss + 2U * h->gauss_cap, config->reduce, o.grad);
+        const OkJoinParams j   = okJoinOn(p.P, h->gauss_drv.d, h->gauss_drv.d + h->gauss_drv.cap, h->gauss_drv.d + 2U * h->gauss_drv.cap, config->reduce, o.grad);
         const size_t       lds = okGaussLdsBytes(p.R, p.H1, p.H2, p.A);
         return sliceUpdate(h, h->gauss_scratch, M, B, config->accumulate != 0, j, h->gauss_t, h->gauss_learner, o.loss,
                            [&](const long base, const int Bk, const int C)
@@ -3701,39 +3831,30 @@ extern "C"
     int okenv_gcl_create(okenv_t h, const okenv_gcl_config *config)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_create: NULL handle");
-        if (const char *why = okGclCheckConfig(config, h->shape.R))
-            return fail(h, OKENV_ERR_INVALID, std::string("okenv_gcl_create: ") + why);
-        OK_HIP(h, hipSetDevice(h->device));
-        // room for the widest network, so that a later create with other widths allocates nothing
-        h->gcl_cap = (static_cast<size_t>(ok_gauss_num_params(OK_ACTOR_MAX_RAYS, OK_GAUSS_MAX_HIDDEN, OK_GAUSS_MAX_HIDDEN, 2)) + 3U) & ~static_cast<size_t>(3U);
-        if (const int rc = devEnsure(h, &h->d_gcl, 9U * h->gcl_cap))
+        if (const int rc = driverGate(h, kGclDriver, "create", kGateHandle))
             return rc;
-        const void *const kernels[] = {reinterpret_cast<const void *>(&okGclActKernel),
-                                       reinterpret_cast<const void *>(&okGclForwardKernel<false>),
-                                       reinterpret_cast<const void *>(&okGclForwardKernel<true>),
-                                       reinterpret_cast<const void *>(&okGclGradKernel<OK_GCL_POLICY>),
-                                       reinterpret_cast<const void *>(&okGclGradKernel<OK_GCL_VALUE>),
-                                       reinterpret_cast<const void *>(&okGclGradKernel<OK_GCL_COST>)};
-        for (const void *k : kernels)
-            OK_HIP(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-        OK_HIP(h, hipMemsetAsync(h->d_gcl, 0, 9U * h->gcl_cap * sizeof(float), h->stream));
+        if (const char *why = okGclCheckConfig(config, h->shape.R))
+            return driverRefuses(h, OKENV_ERR_INVALID, kGclDriver, "create", why);
+        OK_HIP(h, hipSetDevice(h->device));
+        // room for the widest network, so that a later create with other widths allocates nothing: three networks of [params | m | v]
+        const size_t cap = (static_cast<size_t>(ok_gauss_num_params(OK_ACTOR_MAX_RAYS, OK_GAUSS_MAX_HIDDEN, OK_GAUSS_MAX_HIDDEN, 2)) + 3U) & ~static_cast<size_t>(3U);
+        if (const int rc = driverCreateFixed(h, kGclDriver, cap, 9, 0, true,
+                                             {kernelOf(okGclActKernel), kernelOf(okGclForwardKernel<false>), kernelOf(okGclForwardKernel<true>),
+                                              kernelOf(okGclGradKernel<OK_GCL_POLICY>), kernelOf(okGclGradKernel<OK_GCL_VALUE>),
+                                              kernelOf(okGclGradKernel<OK_GCL_COST>)}))
+            return rc;
         h->gcl = *config;
         h->gcl_t = h->gcl_cost_t = 0;
-        for (bool &set : h->gcl_set)
-            set = false;
         h->gcl_learner_ok = false;
         h->gcl_bank_rows  = 0;
-        h->gcl_ok         = true;
         return OKENV_OK;
     }
 
     int okenv_gcl_num_params(okenv_t h, int32_t which, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (!h || !h->gcl_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gcl_num_params: call okenv_gcl_create first");
+        if (const int rc = driverGate(h, kGclDriver, "num_params", kGateCreated))
+            return rc;
         if (which < OKENV_GCL_POLICY || which > OKENV_GCL_COST)
             return fail(h, OKENV_ERR_INVALID, "okenv_gcl_num_params: unknown network (OKENV_GCL_POLICY / _VALUE / _COST)");
         if (num_params)
@@ -3744,15 +3865,11 @@ extern "C"
     int okenv_gcl_set_params(okenv_t h, int32_t which, const float *params)
     {
         OK_QUIESCE(h);
-        if (!h || !h->gcl_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gcl_set_params: call okenv_gcl_create first");
+        if (const int rc = driverGate(h, kGclDriver, "set_params", kGateCreated))
+            return rc;
         if (!params || which < OKENV_GCL_POLICY || which > OKENV_GCL_COST)
             return fail(h, OKENV_ERR_INVALID, "okenv_gcl_set_params: NULL argument or unknown network");
-        OK_HIP(h, hipSetDevice(h->device));
-        if (const int rc = copyAny(h, gclVector(h, which, 0), params, sizeof(float) * static_cast<size_t>(gclNumParams(h, which))))
-            return rc;
-        h->gcl_set[which] = true;
-        return OKENV_OK;
+        return driverSet(h, kGclDriver, {vectorOf(gclVector(h, which, 0), params, gclNumParams(h, which), which)});
     }
 
     int okenv_gcl_get_state(okenv_t h, int32_t which, okenv_gcl_state *out)
@@ -3760,16 +3877,12 @@ extern "C"
         OK_QUIESCE(h);
         if (!h || !out || which < OKENV_GCL_POLICY || which > OKENV_GCL_COST)
             return fail(h, OKENV_ERR_INVALID, "okenv_gcl_get_state: NULL argument or unknown network");
-        if (!h->gcl_ok || !h->gcl_set[which])
-            return fail(h, OKENV_ERR_STATE, "okenv_gcl_get_state: the network needs its parameters first (okenv_gcl_create, okenv_gcl_set_params)");
-        OK_HIP(h, hipSetDevice(h->device));
-        const size_t bytes  = sizeof(float) * static_cast<size_t>(gclNumParams(h, which));
-        float *const dst[3] = {out->params, out->m, out->v};
-        for (int k = 0; k < 3; ++k)
-            if (dst[k] != nullptr)
-                if (const int rc = copyAny(h, dst[k], gclVector(h, which, k), bytes))
-                    return rc;
-        OK_HIP(h, hipStreamSynchronize(h->stream));
+        if (const int rc = driverGate(h, kGclDriver, "get_state", kGateStored, true, 1U << which))
+            return rc;
+        const int n = gclNumParams(h, which);
+        if (const int rc = driverGet(h, {vectorOf(gclVector(h, which, 0), out->params, n), vectorOf(gclVector(h, which, 1), out->m, n),
+                                         vectorOf(gclVector(h, which, 2), out->v, n)}))
+            return rc;
         out->t = which == OKENV_GCL_COST ? h->gcl_cost_t : h->gcl_t;
         return OKENV_OK;
     }
@@ -3786,37 +3899,23 @@ extern "C"
     int okenv_gcl_set_draw_offset(okenv_t h, const uint32_t *device_word)
     {
         OK_QUIESCE(h);
-        if (!h || !h->gcl_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gcl_set_draw_offset: call okenv_gcl_create first");
-        h->gcl_draw_offset = device_word;
-        return OKENV_OK;
+        return driverSetDrawOffset(h, kGclDriver, device_word);
     }
 
     int okenv_gcl_set_greedy(okenv_t h, int32_t greedy)
     {
         OK_QUIESCE(h);
-        if (!h || !h->gcl_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gcl_set_greedy: call okenv_gcl_create first");
-        if (greedy != 0 && greedy != 1)
-            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_set_greedy: greedy must be 0 or 1");
-        h->gcl.greedy = greedy;
-        return OKENV_OK;
+        return driverSetGreedy(h, kGclDriver, &okenv::gcl, greedy);
     }
 
     int okenv_gcl_act(okenv_t h, const okenv_gcl_record *rec)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_gcl_act: NULL handle");
-        if (!h->gcl_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_gcl_act: call okenv_gcl_create first");
-        if (!h->gcl_set[OKENV_GCL_POLICY])
-            return fail(h, OKENV_ERR_STATE, "okenv_gcl_act: call okenv_gcl_set_params first (the policy needs its parameters)");
-        dropEpisode(h);
-        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = actBegin(h, kGclDriver, 1U << OKENV_GCL_POLICY))
+            return rc;
         OkGclActParams p{};
         p.f      = actFrame(h);
-        p.draw   = actDrawWords(h, h->gcl_draw_offset);
+        p.draw   = actDrawWords(h, h->gcl_drv.draw_offset);
         p.H1     = h->gcl.hidden1;
         p.H2     = h->gcl.hidden2;
         p.params = gclVector(h, OKENV_GCL_POLICY, 0);
@@ -3830,16 +3929,13 @@ extern "C"
         p.agent_base = h->gcl.agent_base;
         if (rec != nullptr)
             p.rec = *rec;
-        const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
-        hipLaunchKernelGGL(okGclActKernel, dim3(blocks), dim3(kActorThreads), okGaussActLdsBytes(p.f.R, p.H1, p.H2), h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return actLaunch(h, okGclActKernel, kActorAgents, kActorThreads, okGaussActLdsBytes(p.f.R, p.H1, p.H2), p);
     }
 
     int okenv_gcl_set_expert(okenv_t h, const float *state, const float *action, int32_t E)
     {
         OK_QUIESCE(h);
-        if (!h || !h->gcl_ok)
+        if (!h || !h->gcl_drv.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_gcl_set_expert: call okenv_gcl_create first");
         if (!state || !action || E < 1)
             return fail(h, OKENV_ERR_INVALID, "okenv_gcl_set_expert: NULL argument or an empty bank");
@@ -3847,15 +3943,8 @@ extern "C"
         const size_t R = static_cast<size_t>(h->shape.R), rows = static_cast<size_t>(E);
         if (E > h->gcl_bank_cap)
         {
-            OK_HIP(h, hipStreamSynchronize(h->stream)); // nobody is still reading the old one
-            if (h->d_gcl_bank != nullptr)
-            {
-                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_gcl_bank)), h->allocations.end());
-                (void)hipFree(h->d_gcl_bank);
-                h->d_gcl_bank   = nullptr;
-                h->gcl_bank_cap = h->gcl_bank_rows = 0;
-            }
-            if (const int rc = devAlloc(h, &h->d_gcl_bank, rows * (R + 2U)))
+            h->gcl_bank_cap = h->gcl_bank_rows = 0;
+            if (const int rc = regrow(h, {fresh(h->d_gcl_bank, rows * (R + 2U))}))
                 return rc;
             h->gcl_bank_cap = E;
         }
@@ -3872,7 +3961,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_gcl_cost: NULL handle");
-        if (!h->gcl_ok || !h->gcl_set[OKENV_GCL_COST])
+        if (!h->gcl_drv.ok || !h->gcl_drv.set[OKENV_GCL_COST])
             return fail(h, OKENV_ERR_STATE, "okenv_gcl_cost: the cost network needs its parameters first (okenv_gcl_create, okenv_gcl_set_params)");
         if (!state || !squashed || !out || M < 1)
             return fail(h, OKENV_ERR_INVALID, "okenv_gcl_cost: NULL argument or M < 1");
@@ -3901,11 +3990,11 @@ extern "C"
         for (const okenv_learner_params *lp : {policy_value, cost})
             if (const char *why = okLearnCheckParams(lp))
                 return fail(h, OKENV_ERR_INVALID, std::string("okenv_gcl_learner_create: ") + why);
-        if (!h->gcl_ok || !h->gcl_set[0] || !h->gcl_set[1] || !h->gcl_set[2])
+        if (!h->gcl_drv.ok || !h->gcl_drv.set[0] || !h->gcl_drv.set[1] || !h->gcl_drv.set[2])
             return fail(h, OKENV_ERR_STATE, "okenv_gcl_learner_create: needs a GCL object whose three networks have their parameters (okenv_gcl_create, okenv_gcl_set_params)");
         OK_HIP(h, hipSetDevice(h->device));
         for (int which = 0; which < 3; ++which)
-            OK_HIP(h, hipMemsetAsync(gclVector(h, which, 1), 0, 2U * h->gcl_cap * sizeof(float), h->stream));
+            OK_HIP(h, hipMemsetAsync(gclVector(h, which, 1), 0, 2U * h->gcl_drv.cap * sizeof(float), h->stream));
         h->gcl_learner      = *policy_value;
         h->gcl_cost_learner = *cost;
         h->gcl_t = h->gcl_cost_t = 0;
@@ -3918,7 +4007,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_gcl_cost_update: NULL handle");
-        if (!h->gcl_ok || !h->gcl_learner_ok)
+        if (!h->gcl_drv.ok || !h->gcl_learner_ok)
             return fail(h, OKENV_ERR_STATE, "okenv_gcl_cost_update: call okenv_gcl_learner_create first");
         if (h->gcl_bank_rows < 1)
             return fail(h, OKENV_ERR_STATE, "okenv_gcl_cost_update: call okenv_gcl_set_expert first (the bank is empty)");
@@ -3982,7 +4071,7 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_gcl_policy_update: NULL handle");
-        if (!h->gcl_ok || !h->gcl_learner_ok)
+        if (!h->gcl_drv.ok || !h->gcl_learner_ok)
             return fail(h, OKENV_ERR_STATE, "okenv_gcl_policy_update: call okenv_gcl_learner_create first");
         if (const char *why = okGclCheckCall(config, batch, M, B))
             return fail(h, OKENV_ERR_INVALID, std::string("okenv_gcl_policy_update: ") + why);
@@ -4157,46 +4246,23 @@ extern "C"
     int okenv_lidar_create(okenv_t h, const okenv_lidar_config *config)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_create: NULL handle");
+        if (const int rc = driverGate(h, kLidarDriver, "create", kGateHandle))
+            return rc;
         if (const char *why = okLidarCheckConfig(config))
-            return fail(h, OKENV_ERR_INVALID, std::string("okenv_lidar_create: ") + why);
+            return driverRefuses(h, OKENV_ERR_INVALID, kLidarDriver, "create", why);
         if (config->num_points != h->shape.R)
             return fail(h, OKENV_ERR_INVALID, "okenv_lidar_create: num_points must equal the handle's ray count");
-        OK_HIP(h, hipSetDevice(h->device));
-        const size_t total = static_cast<size_t>(ok_lidar_offsets(okLidarShape(*config)).total);
-        h->lidar_ok        = false;
-        h->lidar_set       = false;
-        if (total > h->lidar_cap)
-        {
-            // the old vector is freed behind a wait for the stream: an earlier act may still be reading it
-            OK_HIP(h, hipStreamSynchronize(h->stream));
-            if (h->d_lidar != nullptr)
-            {
-                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_lidar)), h->allocations.end());
-                (void)hipFree(h->d_lidar);
-                h->d_lidar   = nullptr;
-                h->lidar_cap = 0;
-            }
-            float *fresh = nullptr;
-            if (const int rc = devAlloc(h, &fresh, total))
-                return rc;
-            h->d_lidar   = fresh;
-            h->lidar_cap = total;
-        }
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okLidarActKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-        h->lidar    = *config;
-        h->lidar_ok = true;
+        if (const int rc = driverCreateFlat(h, kLidarDriver, static_cast<size_t>(ok_lidar_offsets(okLidarShape(*config)).total), kernelOf(okLidarActKernel)))
+            return rc;
+        h->lidar = *config;
         return OKENV_OK;
     }
 
     int okenv_lidar_num_params(okenv_t h, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (!h || !num_params)
-            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_num_params: NULL argument");
-        if (!h->lidar_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_lidar_num_params: call okenv_lidar_create first");
+        if (const int rc = driverGate(h, kLidarDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
+            return rc;
         *num_params = ok_lidar_offsets(okLidarShape(h->lidar)).total;
         return OKENV_OK;
     }
@@ -4204,47 +4270,29 @@ extern "C"
     int okenv_lidar_set_params(okenv_t h, const float *params)
     {
         OK_QUIESCE(h);
-        if (!h || !params)
-            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_set_params: NULL argument");
-        if (!h->lidar_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_lidar_set_params: call okenv_lidar_create first");
-        OK_HIP(h, hipSetDevice(h->device));
-        if (const int rc = copyAny(h, h->d_lidar, params, sizeof(float) * static_cast<size_t>(ok_lidar_offsets(okLidarShape(h->lidar)).total)))
+        if (const int rc = driverGate(h, kLidarDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
             return rc;
-        h->lidar_set = true;
-        return OKENV_OK;
+        return driverSet(h, kLidarDriver, {vectorOf(h->lidar_drv.d, params, ok_lidar_offsets(okLidarShape(h->lidar)).total)});
     }
 
     int okenv_lidar_get_params(okenv_t h, float *params)
     {
         OK_QUIESCE(h);
-        if (!h || !params)
-            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_get_params: NULL argument");
-        if (!h->lidar_ok || !h->lidar_set)
-            return fail(h, OKENV_ERR_STATE, "okenv_lidar_get_params: the policy needs its parameters first (okenv_lidar_create, okenv_lidar_set_params)");
-        OK_HIP(h, hipSetDevice(h->device));
-        if (const int rc = copyAny(h, params, h->d_lidar, sizeof(float) * static_cast<size_t>(ok_lidar_offsets(okLidarShape(h->lidar)).total)))
+        if (const int rc = driverGate(h, kLidarDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
             return rc;
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        return OKENV_OK;
+        return driverGet(h, {vectorOf(h->lidar_drv.d, params, ok_lidar_offsets(okLidarShape(h->lidar)).total)});
     }
 
     int okenv_lidar_act(okenv_t h, const okenv_lidar_record *rec)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_lidar_act: NULL handle");
-        if (!h->lidar_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_lidar_act: call okenv_lidar_create first");
-        if (!h->lidar_set)
-            return fail(h, OKENV_ERR_STATE, "okenv_lidar_act: call okenv_lidar_set_params first (the policy needs its parameters)");
-        dropEpisode(h);
-        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = actBegin(h, kLidarDriver, 1U))
+            return rc;
         OkLidarActParams p{};
         p.st     = h->st;
         p.N      = h->shape.N;
         p.s      = okLidarShape(h->lidar);
-        p.params = h->d_lidar;
+        p.params = h->lidar_drv.d;
         for (int k = 0; k < 2; ++k)
         {
             p.lo[k] = h->lidar.action_lo[k];
@@ -4254,10 +4302,7 @@ extern "C"
         p.scale = ok_lidar_scale(p.s.d / p.s.nhead);
         if (rec != nullptr)
             p.rec = *rec;
-        const unsigned blocks = static_cast<unsigned>((h->shape.N + kLidarAgents - 1) / kLidarAgents);
-        hipLaunchKernelGGL(okLidarActKernel, dim3(blocks), dim3(kLidarThreads), okLidarLdsBytes(p.s), h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return actLaunch(h, okLidarActKernel, kLidarAgents, kLidarThreads, okLidarLdsBytes(p.s), p);
     }
 
     int okenv_lidar_act_host(const okenv_lidar_config *config, const float *params, int32_t n, const float *rel_xy, const uint8_t *crashed, float *throttle,
@@ -4296,8 +4341,8 @@ extern "C"
         OK_HIP(nullptr, hipMemcpy(dx, x, 4U * nx, hipMemcpyHostToDevice));
         OK_HIP(nullptr, hipMemcpy(dw, w, 4U * nw, hipMemcpyHostToDevice));
         OK_HIP(nullptr, hipMemcpy(db, bias, 4U * nb, hipMemcpyHostToDevice));
-        OK_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDebugLidarLinearKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            static_cast<int>(kLdsBudget)));
+        if (const int rc = raiseLdsLimit(nullptr, {kernelOf(okDebugLidarLinearKernel)}))
+            return rc;
         hipLaunchKernelGGL(okDebugLidarLinearKernel, dim3(static_cast<unsigned>((M + kLidarAgents - 1) / kLidarAgents)), dim3(kLidarThreads), lds, nullptr, M, K, N,
                            dx, dw, db, relu, dout);
         OK_HIP(nullptr, hipGetLastError());
@@ -4315,44 +4360,21 @@ extern "C"
     int okenv_flow_create(okenv_t h, const okenv_flow_config *config)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_flow_create: NULL handle");
+        if (const int rc = driverGate(h, kFlowDriver, "create", kGateHandle))
+            return rc;
         if (const char *why = okFlowCheckConfig(config))
-            return fail(h, OKENV_ERR_INVALID, std::string("okenv_flow_create: ") + why);
-        OK_HIP(h, hipSetDevice(h->device));
-        const size_t total = static_cast<size_t>(ok_flow_offsets(okFlowShape(*config)).total);
-        h->flow_ok         = false;
-        h->flow_set        = false;
-        if (total > h->flow_cap)
-        {
-            // the old vector is freed behind a wait for the stream: an earlier act may still be reading it
-            OK_HIP(h, hipStreamSynchronize(h->stream));
-            if (h->d_flow != nullptr)
-            {
-                h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), static_cast<void *>(h->d_flow)), h->allocations.end());
-                (void)hipFree(h->d_flow);
-                h->d_flow   = nullptr;
-                h->flow_cap = 0;
-            }
-            float *fresh = nullptr;
-            if (const int rc = devAlloc(h, &fresh, total))
-                return rc;
-            h->d_flow   = fresh;
-            h->flow_cap = total;
-        }
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okFlowActKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-        h->flow    = *config;
-        h->flow_ok = true;
+            return driverRefuses(h, OKENV_ERR_INVALID, kFlowDriver, "create", why);
+        if (const int rc = driverCreateFlat(h, kFlowDriver, static_cast<size_t>(ok_flow_offsets(okFlowShape(*config)).total), kernelOf(okFlowActKernel)))
+            return rc;
+        h->flow = *config;
         return OKENV_OK;
     }
 
     int okenv_flow_num_params(okenv_t h, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (!h || !num_params)
-            return fail(h, OKENV_ERR_INVALID, "okenv_flow_num_params: NULL argument");
-        if (!h->flow_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_flow_num_params: call okenv_flow_create first");
+        if (const int rc = driverGate(h, kFlowDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
+            return rc;
         *num_params = ok_flow_offsets(okFlowShape(h->flow)).total;
         return OKENV_OK;
     }
@@ -4360,60 +4382,37 @@ extern "C"
     int okenv_flow_set_params(okenv_t h, const float *params)
     {
         OK_QUIESCE(h);
-        if (!h || !params)
-            return fail(h, OKENV_ERR_INVALID, "okenv_flow_set_params: NULL argument");
-        if (!h->flow_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_flow_set_params: call okenv_flow_create first");
-        OK_HIP(h, hipSetDevice(h->device));
-        if (const int rc = copyAny(h, h->d_flow, params, sizeof(float) * static_cast<size_t>(ok_flow_offsets(okFlowShape(h->flow)).total)))
+        if (const int rc = driverGate(h, kFlowDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
             return rc;
-        h->flow_set = true;
-        return OKENV_OK;
+        return driverSet(h, kFlowDriver, {vectorOf(h->flow_drv.d, params, ok_flow_offsets(okFlowShape(h->flow)).total)});
     }
 
     int okenv_flow_get_params(okenv_t h, float *params)
     {
         OK_QUIESCE(h);
-        if (!h || !params)
-            return fail(h, OKENV_ERR_INVALID, "okenv_flow_get_params: NULL argument");
-        if (!h->flow_ok || !h->flow_set)
-            return fail(h, OKENV_ERR_STATE, "okenv_flow_get_params: the policy needs its parameters first (okenv_flow_create, okenv_flow_set_params)");
-        OK_HIP(h, hipSetDevice(h->device));
-        if (const int rc = copyAny(h, params, h->d_flow, sizeof(float) * static_cast<size_t>(ok_flow_offsets(okFlowShape(h->flow)).total)))
+        if (const int rc = driverGate(h, kFlowDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
             return rc;
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        return OKENV_OK;
+        return driverGet(h, {vectorOf(h->flow_drv.d, params, ok_flow_offsets(okFlowShape(h->flow)).total)});
     }
 
     int okenv_flow_set_draw_offset(okenv_t h, const uint32_t *device_word)
     {
         OK_QUIESCE(h);
-        if (!h || !h->flow_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_flow_set_draw_offset: call okenv_flow_create first");
-        h->flow_draw_offset = device_word;
-        return OKENV_OK;
+        return driverSetDrawOffset(h, kFlowDriver, device_word);
     }
 
     int okenv_flow_act(okenv_t h, const float *cond, const okenv_flow_record *rec)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_flow_act: NULL handle");
-        if (!h->flow_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_flow_act: call okenv_flow_create first");
-        if (!h->flow_set)
-            return fail(h, OKENV_ERR_STATE, "okenv_flow_act: call okenv_flow_set_params first (the policy needs its parameters)");
-        if (!cond)
-            return fail(h, OKENV_ERR_INVALID, "okenv_flow_act: cond is NULL");
-        dropEpisode(h);
-        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = actBegin(h, kFlowDriver, 1U, cond != nullptr ? nullptr : "cond is NULL"))
+            return rc;
         OkFlowActParams p{};
         p.st     = h->st;
         p.N      = h->shape.N;
         p.s      = okFlowShape(h->flow);
-        p.params = h->d_flow;
+        p.params = h->flow_drv.d;
         p.cond   = cond;
-        p.draw   = actDrawWords(h, h->flow_draw_offset);
+        p.draw   = actDrawWords(h, h->flow_drv.draw_offset);
         for (int k = 0; k < 2; ++k)
         {
             p.lo[k] = h->flow.action_lo[k];
@@ -4424,10 +4423,7 @@ extern "C"
         p.agent_base = h->flow.agent_base;
         if (rec != nullptr)
             p.rec = *rec;
-        const unsigned blocks = static_cast<unsigned>((h->shape.N + kFlowAgents - 1) / kFlowAgents);
-        hipLaunchKernelGGL(okFlowActKernel, dim3(blocks), dim3(kLidarThreads), okFlowLdsBytes(p.s), h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return actLaunch(h, okFlowActKernel, kFlowAgents, kLidarThreads, okFlowLdsBytes(p.s), p);
     }
 
     int okenv_flow_act_host(const okenv_flow_config *config, const float *params, int32_t n, const float *cond, const uint8_t *crashed,
@@ -4446,87 +4442,63 @@ extern "C"
     int okenv_ddpg_create(okenv_t h, const okenv_ddpg_config *config)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_create: NULL handle");
+        if (const int rc = driverGate(h, kDdpgDriver, "create", kGateHandle))
+            return rc;
         if (const char *why = okDdpgCheckConfig(config, h->shape.R))
-            return fail(h, OKENV_ERR_INVALID, std::string("okenv_ddpg_create: ") + why);
+            return driverRefuses(h, OKENV_ERR_INVALID, kDdpgDriver, "create", why);
         OK_HIP(h, hipSetDevice(h->device));
         // room for the widest networks, so that a later create with other widths allocates nothing
         // (a multiple of four floats, with room for the last 16-byte load: okActorStage reads whole float4s from each vector)
-        h->ddpg_cap = ((static_cast<size_t>(ok_actor_num_params(OK_ACTOR_MAX_RAYS, OK_ACTOR_MAX_HIDDEN, 2)) + 3U) & ~static_cast<size_t>(3U)) + 4U;
-        int rc      = devEnsure(h, &h->d_ddpg_nets, 4U * h->ddpg_cap);
-        if (rc != OKENV_OK || (rc = devEnsure(h, &h->d_ddpg_moments, 4U * h->ddpg_cap)) != OKENV_OK)
+        const size_t cap = ((static_cast<size_t>(ok_actor_num_params(OK_ACTOR_MAX_RAYS, OK_ACTOR_MAX_HIDDEN, 2)) + 3U) & ~static_cast<size_t>(3U)) + 4U;
+        if (const int rc = driverCreateFixed(h, kDdpgDriver, cap, 4, 4, true,
+                                             {kernelOf(okDdpgActKernel), kernelOf(okDdpgCriticGradKernel), kernelOf(okDdpgActorGradKernel)}))
             return rc;
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDdpgActKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDdpgCriticGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(kLdsBudget)));
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okDdpgActorGradKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(kLdsBudget)));
-        OK_HIP(h, hipMemsetAsync(h->d_ddpg_nets, 0, 4U * h->ddpg_cap * sizeof(float), h->stream));
-        OK_HIP(h, hipMemsetAsync(h->d_ddpg_moments, 0, 4U * h->ddpg_cap * sizeof(float), h->stream));
-        h->ddpg            = *config;
-        h->ddpg_t          = 0;
-        h->ddpg_actor_set  = false;
-        h->ddpg_critic_set = false;
-        h->ddpg_ok         = true;
+        h->ddpg   = *config;
+        h->ddpg_t = 0;
         return OKENV_OK;
     }
 
     int okenv_ddpg_num_params(okenv_t h, int32_t *actor, int32_t *critic)
     {
         OK_QUIESCE(h);
-        if (!h || !h->ddpg_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_num_params: call okenv_ddpg_create first");
+        if (const int rc = driverGate(h, kDdpgDriver, "num_params", kGateCreated))
+            return rc;
         if (actor)
-            *actor = ok_actor_num_params(h->shape.R, h->ddpg.hidden, 2);
+            *actor = ddpgActorParams(h);
         if (critic)
-            *critic = ok_ddpg_critic_params(h->shape.R, h->ddpg.critic_hidden);
+            *critic = ddpgCriticParams(h);
         return OKENV_OK;
     }
 
     int okenv_ddpg_set_params(okenv_t h, const float *actor, const float *critic)
     {
         OK_QUIESCE(h);
-        if (!h || !h->ddpg_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_set_params: call okenv_ddpg_create first");
-        OK_HIP(h, hipSetDevice(h->device));
-        const float *const src[2]   = {actor, critic};
-        const size_t       bytes[2] = {sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->ddpg.hidden, 2)),
-                                       sizeof(float) * static_cast<size_t>(ok_ddpg_critic_params(h->shape.R, h->ddpg.critic_hidden))};
+        if (const int rc = driverGate(h, kDdpgDriver, "set_params", kGateCreated))
+            return rc;
+        const OkDriver    &d          = h->ddpg_drv;
+        const float *const src[2]     = {actor, critic};
+        const size_t       floats[2]  = {static_cast<size_t>(ddpgActorParams(h)), static_cast<size_t>(ddpgCriticParams(h))};
+        if (const int rc = driverSet(h, kDdpgDriver, {vectorOf(d.d, actor, ddpgActorParams(h), 0), vectorOf(d.d + d.cap, critic, ddpgCriticParams(h), 1)}))
+            return rc;
+        // each online network that arrived, into its target (DDPGAgent.hpp:65-74)
         for (size_t k = 0; k < 2U; ++k)
             if (src[k] != nullptr)
-            { // the online network, then its target from it (DDPGAgent.hpp:65-74)
-                float    *online = h->d_ddpg_nets + k * h->ddpg_cap;
-                const int rc     = copyAny(h, online, src[k], bytes[k]);
-                if (rc != OKENV_OK)
-                    return rc;
-                OK_HIP(h, hipMemcpyAsync(online + 2U * h->ddpg_cap, online, bytes[k], hipMemcpyDeviceToDevice, h->stream));
-                (k == 0U ? h->ddpg_actor_set : h->ddpg_critic_set) = true;
-            }
+                OK_HIP(h, hipMemcpyAsync(d.d + (k + 2U) * d.cap, d.d + k * d.cap, sizeof(float) * floats[k], hipMemcpyDeviceToDevice, h->stream));
         return OKENV_OK;
     }
 
     int okenv_ddpg_get_state(okenv_t h, okenv_ddpg_state *out)
     {
         OK_QUIESCE(h);
-        if (!h || !out)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_get_state: NULL argument");
-        if (!h->ddpg_ok || !h->ddpg_actor_set || !h->ddpg_critic_set)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_get_state: both networks need their parameters first (okenv_ddpg_create, okenv_ddpg_set_params)");
-        OK_HIP(h, hipSetDevice(h->device));
-        const size_t na = sizeof(float) * static_cast<size_t>(ok_actor_num_params(h->shape.R, h->ddpg.hidden, 2));
-        const size_t nc = sizeof(float) * static_cast<size_t>(ok_ddpg_critic_params(h->shape.R, h->ddpg.critic_hidden));
-        float *const       dst[8]   = {out->actor, out->critic, out->actor_target, out->critic_target, out->actor_m, out->actor_v, out->critic_m, out->critic_v};
-        const float *const base[8]  = {h->d_ddpg_nets, h->d_ddpg_nets, h->d_ddpg_nets, h->d_ddpg_nets, h->d_ddpg_moments, h->d_ddpg_moments, h->d_ddpg_moments, h->d_ddpg_moments};
-        const size_t       bytes[8] = {na, nc, na, nc, na, na, nc, nc};
-        for (size_t k = 0; k < 8U; ++k)
-            if (dst[k] != nullptr)
-            {
-                const int rc = copyAny(h, dst[k], base[k] + (k & 3U) * h->ddpg_cap, bytes[k]);
-                if (rc != OKENV_OK)
-                    return rc;
-            }
-        OK_HIP(h, hipStreamSynchronize(h->stream));
+        if (const int rc = driverGate(h, kDdpgDriver, "get_state", kGateArgFirst | kGateStored, out != nullptr, 3U))
+            return rc;
+        const OkDriver &d  = h->ddpg_drv;
+        const int       na = ddpgActorParams(h), nc = ddpgCriticParams(h);
+        if (const int rc = driverGet(h, {vectorOf(d.d, out->actor, na), vectorOf(d.d + d.cap, out->critic, nc), vectorOf(d.d + 2U * d.cap, out->actor_target, na),
+                                         vectorOf(d.d + 3U * d.cap, out->critic_target, nc), vectorOf(d.d2, out->actor_m, na),
+                                         vectorOf(d.d2 + d.cap, out->actor_v, na), vectorOf(d.d2 + 2U * d.cap, out->critic_m, nc),
+                                         vectorOf(d.d2 + 3U * d.cap, out->critic_v, nc)}))
+            return rc;
         out->t = h->ddpg_t;
         return OKENV_OK;
     }
@@ -4534,28 +4506,19 @@ extern "C"
     int okenv_ddpg_set_draw_offset(okenv_t h, const uint32_t *device_word)
     {
         OK_QUIESCE(h);
-        if (!h || !h->ddpg_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_set_draw_offset: call okenv_ddpg_create first");
-        h->ddpg_draw_offset = device_word;
-        return OKENV_OK;
+        return driverSetDrawOffset(h, kDdpgDriver, device_word);
     }
 
     int okenv_ddpg_act(okenv_t h, const okenv_ddpg_record *rec)
     {
         OK_QUIESCE(h);
-        if (!h)
-            return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_act: NULL handle");
-        if (!h->ddpg_ok)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_act: call okenv_ddpg_create first");
-        if (!h->ddpg_actor_set)
-            return fail(h, OKENV_ERR_STATE, "okenv_ddpg_act: call okenv_ddpg_set_params first (the actor needs its parameters)");
-        dropEpisode(h);
-        OK_HIP(h, hipSetDevice(h->device));
+        if (const int rc = actBegin(h, kDdpgDriver, 1U))
+            return rc;
         OkDdpgActParams p{};
         p.f     = actFrame(h);
-        p.draw  = actDrawWords(h, h->ddpg_draw_offset);
+        p.draw  = actDrawWords(h, h->ddpg_drv.draw_offset);
         p.H     = h->ddpg.hidden;
-        p.actor = h->d_ddpg_nets;
+        p.actor = h->ddpg_drv.d;
         for (int k = 0; k < 2; ++k)
         {
             p.scale[k] = h->ddpg.scale[k];
@@ -4566,10 +4529,7 @@ extern "C"
         p.agent_base = h->ddpg.agent_base;
         if (rec != nullptr)
             p.rec = *rec;
-        const unsigned blocks = static_cast<unsigned>((h->shape.N + kActorAgents - 1) / kActorAgents);
-        hipLaunchKernelGGL(okDdpgActKernel, dim3(blocks), dim3(kActorThreads), okDdpgActLdsBytes(p.f.R, p.H), h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return actLaunch(h, okDdpgActKernel, kActorAgents, kActorThreads, okDdpgActLdsBytes(p.f.R, p.H), p);
     }
 
     int okenv_ddpg_replay_create(okenv_t h, int32_t capacity, uint32_t flags)
@@ -4607,9 +4567,9 @@ extern "C"
         OK_QUIESCE(h);
         if (!h)
             return fail(h, OKENV_ERR_INVALID, "okenv_ddpg_update: NULL handle");
-        if (!h->ddpg_ok)
+        if (!h->ddpg_drv.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_ddpg_update: call okenv_ddpg_create first");
-        if (!h->ddpg_actor_set || !h->ddpg_critic_set)
+        if (!h->ddpg_drv.set[0] || !h->ddpg_drv.set[1])
             return fail(h, OKENV_ERR_STATE, "okenv_ddpg_update: both networks need their parameters first (okenv_ddpg_set_params)");
         if (!h->ddpg_ring.ok)
             return fail(h, OKENV_ERR_STATE, "okenv_ddpg_update: call okenv_ddpg_replay_create first");
@@ -4627,14 +4587,14 @@ extern "C"
         p.capacity = static_cast<uint64_t>(h->ddpg_ring.capacity);
         p.pushed   = h->ddpg_ring.d_words;
         p.ring     = ringFields<okenv_ddpg_ring>(h->ddpg_ring);
-        p.actor    = h->d_ddpg_nets;
-        p.critic   = h->d_ddpg_nets + h->ddpg_cap;
-        p.actor_t  = h->d_ddpg_nets + 2U * h->ddpg_cap;
-        p.critic_t = h->d_ddpg_nets + 3U * h->ddpg_cap;
-        p.act_m    = h->d_ddpg_moments;
-        p.act_v    = h->d_ddpg_moments + h->ddpg_cap;
-        p.cri_m    = h->d_ddpg_moments + 2U * h->ddpg_cap;
-        p.cri_v    = h->d_ddpg_moments + 3U * h->ddpg_cap;
+        p.actor    = h->ddpg_drv.d;
+        p.critic   = h->ddpg_drv.d + h->ddpg_drv.cap;
+        p.actor_t  = h->ddpg_drv.d + 2U * h->ddpg_drv.cap;
+        p.critic_t = h->ddpg_drv.d + 3U * h->ddpg_drv.cap;
+        p.act_m    = h->ddpg_drv.d2;
+        p.act_v    = h->ddpg_drv.d2 + h->ddpg_drv.cap;
+        p.cri_m    = h->ddpg_drv.d2 + 2U * h->ddpg_drv.cap;
+        p.cri_v    = h->ddpg_drv.d2 + 3U * h->ddpg_drv.cap;
         for (int k = 0; k < 2; ++k)
         {
             p.scale[k] = h->ddpg.scale[k];
@@ -5559,20 +5519,9 @@ extern "C"
         if (!okRenderBuildGrid(list, cell, g))
             return fail(h, OKENV_ERR_INVALID, "okenv_render_create: non-finite boundary coordinate");
         OK_HIP(h, hipSetDevice(h->device));
-        // the buffers of an earlier setup go: nothing on the stream may still read them
-        OK_HIP(h, hipStreamSynchronize(h->stream));
-        for (void *old : {static_cast<void *>(h->d_render_tris), static_cast<void *>(h->d_render_start)})
-        {
-            if (!old)
-                continue;
-            h->allocations.erase(std::remove(h->allocations.begin(), h->allocations.end(), old), h->allocations.end());
-            OK_HIP(h, hipFree(old));
-        }
-        h->render_ok      = false;
-        h->d_render_tris  = nullptr;
-        h->d_render_start = nullptr;
-        int rc;
-        if ((rc = devAlloc(h, &h->d_render_tris, g.cell_tris.size())) || (rc = devAlloc(h, &h->d_render_start, g.cell_start.size())))
+        // the buffers of an earlier setup go (behind the wait: nothing on the stream may still read them)
+        h->render_ok = false;
+        if (const int rc = regrow(h, {fresh(h->d_render_tris, g.cell_tris.size()), fresh(h->d_render_start, g.cell_start.size())}))
             return rc;
         if (!g.cell_tris.empty())
             OK_HIP(h, hipMemcpyAsync(h->d_render_tris, g.cell_tris.data(), sizeof(OkRenderTri) * g.cell_tris.size(), hipMemcpyHostToDevice,
@@ -5795,8 +5744,8 @@ extern "C"
         OkStepParams p = baseParams(h);
         if (split)
             useFrontBack(h, p);
-        OK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&okWorkStatsKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(kLdsBudget)));
+        if (const int lrc = raiseLdsLimit(h, {kernelOf(okWorkStatsKernel)}))
+            return lrc;
         const long total  = static_cast<long>(h->shape.N) * h->shape.R;
         const int  blocks = static_cast<int>(std::min<long>(256, (total + 1023) / 1024));
         hipLaunchKernelGGL(okWorkStatsKernel, dim3(blocks), dim3(1024), p.image_bytes, h->stream, p, static_cast<unsigned long long *>(sp));

@@ -460,12 +460,8 @@ class BatchedEnvironment:
         """updateAction for every agent, enqueued on the handle's stream without a synchronisation.  record: None, or a dict of
         device tensors / addresses under "action" [N,2], "dist" [N,R], "rel_xy" [N,R,2] (float32) and "alive" [N] (uint8), each
         optional, that receive this step's sample."""
-        if record is None:
-            capi.check(self._L.okenv_expert_act(self._h, None), self._h)
-            return
-        sizes = {"action": self.N * 8, "dist": self.N * self.R * 4, "rel_xy": self.N * self.R * 8, "alive": self.N}
-        rec = capi.fill_pointers(capi.OkenvExpertRecord(), record, "record", sizes)
-        capi.check(self._L.okenv_expert_act(self._h, C.byref(rec)), self._h)
+        self._act("okenv_expert_act", capi.OkenvExpertRecord, record,
+                  record and {"action": self.N * 8, "dist": self.N * self.R * 4, "rel_xy": self.N * self.R * 8, "alive": self.N})
 
     # ---- shared-network actors (include/okenv.h, DESIGN.md section 14) ---------------------------------------------------
     def actor_create(self, hidden, actions, value_hidden=0, mode="sample", epsilon=0.0, seed=0, agent_base=0):
@@ -477,39 +473,64 @@ class BatchedEnvironment:
         return self.actor_num_params()
 
     def actor_num_params(self):
-        a, b = C.c_int32(), C.c_int32()
-        capi.check(self._L.okenv_actor_num_params(self._h, C.byref(a), C.byref(b)), self._h)
-        return a.value, b.value
+        return self._count("okenv_actor_num_params", outs=2)
 
     def actor_set_params(self, policy=None, value=None):
         """New parameter vectors (torch's parameters() order, flattened) from float32 numpy arrays or device tensors; None
         leaves a network as it is.  Enqueued on the handle's stream, no synchronisation for device tensors."""
-        self._set_params(self._L.okenv_actor_set_params, (policy, value), self.actor_num_params())
+        self._set_params("okenv_actor_set_params", (policy, value), self.actor_num_params())
 
-    def _set_params(self, entry, vectors, counts):
-        """Two parameter vectors to an okenv_*_set_params entry, each checked by _flat_params."""
+    # (one implementation for the families that attach a network to the handle -- actor, ddpg, gauss, gcl, lidar, flow: `symbol` is
+    # the family's entry, `lead` what it takes between the handle and the arguments named here)
+    def _count(self, symbol, *lead, outs=1):
+        """The floats an okenv_*_num_params entry reports: an int, or a tuple of `outs` of them."""
+        n = [C.c_int32() for _ in range(outs)]
+        capi.check(getattr(self._L, symbol)(self._h, *lead, *(C.byref(v) for v in n)), self._h)
+        return n[0].value if outs == 1 else tuple(v.value for v in n)
+
+    def _set_params(self, symbol, vectors, counts, *lead):
+        """Parameter vectors to an okenv_*_set_params entry, each checked by _flat_params.  The entry only enqueues its copies and a host
+        buffer must stay valid until the stream has passed them, so a call that handed over a numpy array waits for the stream."""
         keep = [_flat_params(v, n) for v, n in zip(vectors, counts)]
-        capi.check(entry(self._h, capi.ptr(keep[0]), capi.ptr(keep[1])), self._h)
+        capi.check(getattr(self._L, symbol)(self._h, *lead, *(capi.ptr(v) for v in keep)), self._h)
         if any(isinstance(v, np.ndarray) for v in keep):
             self.sync()  # the host arrays are temporaries
+
+    def _get_state(self, symbol, counts, out=None, struct=None, lead=()):
+        """Vectors read back through an okenv_*_get_state / _get_params entry, which waits for the stream.  counts: {name: floats}, the
+        float32 numpy arrays made when `out` (a dict of device tensors, any subset) is None; struct: the entry's state struct, whose t the
+        result carries, or None for an entry that takes the pointer of the one vector "params"."""
+        if out is None:
+            out = {k: np.empty(n, dtype=np.float32) for k, n in counts.items()}
+        if struct is None:
+            capi.check(getattr(self._L, symbol)(self._h, *lead, capi.ptr(out["params"])), self._h)
+            return out
+        st = capi.fill_pointers(struct(), out, "state")
+        capi.check(getattr(self._L, symbol)(self._h, *lead, C.byref(st)), self._h)
+        return dict(out, t=int(st.t))
+
+    def _set_draw_offset(self, symbol, word):
+        capi.check(getattr(self._L, symbol)(self._h, capi.ptr(word)), self._h)
+
+    def _act(self, symbol, struct, record, sizes, *lead):
+        """An okenv_*_act entry, enqueued without a synchronisation.  record: None or the dict of device tensors / addresses that fills
+        `struct`; sizes: the bytes each slot must hold (callers pass `record and {...}`, which builds it only for a record)."""
+        rec = None if record is None else C.byref(capi.fill_pointers(struct(), record, "record", sizes))
+        capi.check(getattr(self._L, symbol)(self._h, *lead, rec), self._h)
 
     def actor_set_epsilon(self, epsilon):
         capi.check(self._L.okenv_actor_set_epsilon(self._h, float(epsilon)), self._h)
 
     def actor_set_draw_offset(self, word=None):
         """A device uint32 word (tensor or address) added to the draw index of every later actor_act; None removes it."""
-        capi.check(self._L.okenv_actor_set_draw_offset(self._h, capi.ptr(word)), self._h)
+        self._set_draw_offset("okenv_actor_set_draw_offset", word)
 
     def actor_act(self, record=None):
         """updateAction of the shared-network agents for every agent, enqueued on the handle's stream without a synchronisation.
         record: None, or a dict of device tensors / addresses under "state" [N,R] float32, "action" [N] int64, "prob" [N] float32,
         "value" [N] float32 and "alive" [N] uint8, each optional, that receive this step's sample."""
-        if record is None:
-            capi.check(self._L.okenv_actor_act(self._h, None), self._h)
-            return
-        sizes = {"state": self.N * self.R * 4, "action": self.N * 8, "prob": self.N * 4, "value": self.N * 4, "alive": self.N}
-        rec = capi.fill_pointers(capi.OkenvActorRecord(), record, "record", sizes)
-        capi.check(self._L.okenv_actor_act(self._h, C.byref(rec)), self._h)
+        self._act("okenv_actor_act", capi.OkenvActorRecord, record,
+                  record and {"state": self.N * self.R * 4, "action": self.N * 8, "prob": self.N * 4, "value": self.N * 4, "alive": self.N})
 
     # ---- from a recorded episode to the learner's batch (include/okenv.h, DESIGN.md section 15) ---------------------------
     def batch_prepare(self, num_steps, num_agents, inputs, outputs, state_width=0, record_stride=0, field_stride=0, gamma=0.99, lam=1.0,
@@ -683,38 +704,27 @@ class BatchedEnvironment:
         return self.ddpg_num_params()
 
     def ddpg_num_params(self):
-        a, b = C.c_int32(), C.c_int32()
-        capi.check(self._L.okenv_ddpg_num_params(self._h, C.byref(a), C.byref(b)), self._h)
-        return a.value, b.value
+        return self._count("okenv_ddpg_num_params", outs=2)
 
     def ddpg_set_params(self, actor=None, critic=None):
         """New online parameters (torch's parameters() order, flattened) from float32 numpy arrays or device tensors; each network
         that arrives also replaces its target network.  None leaves a network as it is."""
-        self._set_params(self._L.okenv_ddpg_set_params, (actor, critic), self.ddpg_num_params())
+        self._set_params("okenv_ddpg_set_params", (actor, critic), self.ddpg_num_params())
 
     def ddpg_state(self, out=None):
         """The four parameter vectors, the four Adam moments (capi.DDPG_STATE_VECTORS) and the int t: float32 numpy arrays, or copied
         into the device tensors of the dict `out` (any subset).  Synchronises."""
         na, nc = self.ddpg_num_params()
-        if out is None:
-            out = {k: np.empty(nc if "critic" in k else na, dtype=np.float32) for k in capi.DDPG_STATE_VECTORS}
-        st = capi.fill_pointers(capi.OkenvDdpgState(), out, "ddpg state")
-        capi.check(self._L.okenv_ddpg_get_state(self._h, C.byref(st)), self._h)
-        return dict(out, t=int(st.t))
+        return self._get_state("okenv_ddpg_get_state", {k: nc if "critic" in k else na for k in capi.DDPG_STATE_VECTORS}, out, capi.OkenvDdpgState)
 
     def ddpg_set_draw_offset(self, word=None):
         """A device uint32 word (tensor or address) added to the draw index of every later ddpg_act; None removes it."""
-        capi.check(self._L.okenv_ddpg_set_draw_offset(self._h, capi.ptr(word)), self._h)
+        self._set_draw_offset("okenv_ddpg_set_draw_offset", word)
 
     def ddpg_act(self, record=None):
         """The continuous action of every agent, enqueued on the handle's stream without a synchronisation.  record: None, or a dict
         of device tensors / addresses under "state" [N,R] float32, "action" [N,2] float32 and "alive" [N] uint8, each optional."""
-        if record is None:
-            capi.check(self._L.okenv_ddpg_act(self._h, None), self._h)
-            return
-        sizes = {"state": self.N * self.R * 4, "action": self.N * 8, "alive": self.N}
-        rec = capi.fill_pointers(capi.OkenvDdpgRecord(), record, "record", sizes)
-        capi.check(self._L.okenv_ddpg_act(self._h, C.byref(rec)), self._h)
+        self._act("okenv_ddpg_act", capi.OkenvDdpgRecord, record, record and {"state": self.N * self.R * 4, "action": self.N * 8, "alive": self.N})
 
     def ddpg_replay_create(self, capacity, push_all=False):
         """Attaches DDPG's replay ring of `capacity` transitions (action [C,2] float32); replay_create's contract."""
@@ -758,31 +768,22 @@ class BatchedEnvironment:
         return self.gauss_num_params()
 
     def gauss_num_params(self):
-        n = C.c_int32()
-        capi.check(self._L.okenv_gauss_num_params(self._h, C.byref(n)), self._h)
-        return n.value
+        return self._count("okenv_gauss_num_params")
 
     def gauss_set_params(self, params):
         """New parameters [log_std | fc1 | fc2 | mean] (torch's parameters() order, flattened) from a float32 numpy array or a device
-        tensor.  No synchronisation."""
-        if hasattr(params, "data_ptr"):
-            assert params.is_contiguous() and params.numel() == self.gauss_num_params()
-        else:
-            params = _flat_params(params, self.gauss_num_params())
-        capi.check(self._L.okenv_gauss_set_params(self._h, capi.ptr(params)), self._h)
+        tensor.  Enqueued on the handle's stream; the call waits for the stream when it was handed a numpy
+        array (which may be a temporary), not for a device tensor."""
+        self._set_params("okenv_gauss_set_params", (params,), (self.gauss_num_params(),))
 
     def gauss_state(self, out=None):
         """The parameter vector, Adam's two moments ("params", "m", "v") and the int t: float32 numpy arrays, or copied into the
         device tensors of the dict `out` (any subset).  Synchronises."""
-        if out is None:
-            out = {k: np.empty(self.gauss_num_params(), dtype=np.float32) for k in ("params", "m", "v")}
-        st = capi.fill_pointers(capi.OkenvGaussState(), out, "gauss state")
-        capi.check(self._L.okenv_gauss_get_state(self._h, C.byref(st)), self._h)
-        return dict(out, t=int(st.t))
+        return self._get_state("okenv_gauss_get_state", dict.fromkeys(("params", "m", "v"), self.gauss_num_params()), out, capi.OkenvGaussState)
 
     def gauss_set_draw_offset(self, word=None):
         """A device uint32 word (tensor or address) added to the draw index of every later gauss_act; None removes it."""
-        capi.check(self._L.okenv_gauss_set_draw_offset(self._h, capi.ptr(word)), self._h)
+        self._set_draw_offset("okenv_gauss_set_draw_offset", word)
 
     def gauss_set_greedy(self, greedy):
         capi.check(self._L.okenv_gauss_set_greedy(self._h, 1 if greedy else 0), self._h)
@@ -791,12 +792,8 @@ class BatchedEnvironment:
         """The sampled (or greedy) action of every agent, enqueued on the handle's stream without a synchronisation.  record: None,
         or a dict of device tensors / addresses under "state" [N,R], "eps", "pre", "action" [N,2], "logp" [N] float32 and "alive" [N]
         uint8, each optional."""
-        if record is None:
-            capi.check(self._L.okenv_gauss_act(self._h, None), self._h)
-            return
-        sizes = {"state": self.N * self.R * 4, "eps": self.N * 8, "pre": self.N * 8, "action": self.N * 8, "logp": self.N * 4, "alive": self.N}
-        rec = capi.fill_pointers(capi.OkenvGaussRecord(), record, "record", sizes)
-        capi.check(self._L.okenv_gauss_act(self._h, C.byref(rec)), self._h)
+        self._act("okenv_gauss_act", capi.OkenvGaussRecord, record, record and
+                  {"state": self.N * self.R * 4, "eps": self.N * 8, "pre": self.N * 8, "action": self.N * 8, "logp": self.N * 4, "alive": self.N})
 
     def gauss_learner_create(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
         """Adam for the Gaussian actor (the reference's learning rate, ReinforceAgent.hpp:52): moments zeroed, t = 0."""
@@ -828,35 +825,22 @@ class BatchedEnvironment:
         return self.lidar_num_params()
 
     def lidar_num_params(self):
-        n = C.c_int32()
-        capi.check(self._L.okenv_lidar_num_params(self._h, C.byref(n)), self._h)
-        return n.value
+        return self._count("okenv_lidar_num_params")
 
     def lidar_set_params(self, params):
         """New parameters (torch's parameters() order, then the positional table: capi.lidar_layout) from a float32 numpy array or a
-        device tensor.  No synchronisation."""
-        if hasattr(params, "data_ptr"):
-            assert params.is_contiguous() and params.numel() == self.lidar_num_params()
-        else:
-            params = _flat_params(params, self.lidar_num_params())
-        capi.check(self._L.okenv_lidar_set_params(self._h, capi.ptr(params)), self._h)
+        device tensor.  Enqueued on the handle's stream; the call waits for the stream when it was handed a numpy
+        array (which may be a temporary), not for a device tensor."""
+        self._set_params("okenv_lidar_set_params", (params,), (self.lidar_num_params(),))
 
     def lidar_get_params(self, out=None):
         """The parameter vector as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
-        if out is None:
-            out = np.empty(self.lidar_num_params(), dtype=np.float32)
-        capi.check(self._L.okenv_lidar_get_params(self._h, capi.ptr(out)), self._h)
-        return out
+        return self._get_state("okenv_lidar_get_params", {"params": self.lidar_num_params()}, None if out is None else {"params": out})["params"]
 
     def lidar_act(self, record=None):
         """The policy's action for every agent, enqueued on the handle's stream without a synchronisation.  record: None, or a dict
         of device tensors / addresses under "action" [N,2], "input" [N,R,2] float32 and "alive" [N] uint8, each optional."""
-        if record is None:
-            capi.check(self._L.okenv_lidar_act(self._h, None), self._h)
-            return
-        sizes = {"action": self.N * 8, "input": self.N * self.R * 8, "alive": self.N}
-        rec = capi.fill_pointers(capi.OkenvLidarRecord(), record, "record", sizes)
-        capi.check(self._L.okenv_lidar_act(self._h, C.byref(rec)), self._h)
+        self._act("okenv_lidar_act", capi.OkenvLidarRecord, record, record and {"action": self.N * 8, "input": self.N * self.R * 8, "alive": self.N})
 
     # ---- flow-matching driver (include/okenv.h, DESIGN.md section 23) --------------------------------------------------------
     def flow_create(self, config=None, **members):
@@ -870,40 +854,28 @@ class BatchedEnvironment:
         return self.flow_num_params()
 
     def flow_num_params(self):
-        n = C.c_int32()
-        capi.check(self._L.okenv_flow_num_params(self._h, C.byref(n)), self._h)
-        return n.value
+        return self._count("okenv_flow_num_params")
 
     def flow_set_params(self, params):
         """New parameters (the trunk's, in torch's parameters() order: capi.flow_layout) from a float32 numpy array or a device
-        tensor.  No synchronisation."""
-        if hasattr(params, "data_ptr"):
-            assert params.is_contiguous() and params.numel() == self.flow_num_params()
-        else:
-            params = _flat_params(params, self.flow_num_params())
-        capi.check(self._L.okenv_flow_set_params(self._h, capi.ptr(params)), self._h)
+        tensor.  Enqueued on the handle's stream; the call waits for the stream when it was handed a numpy
+        array (which may be a temporary), not for a device tensor."""
+        self._set_params("okenv_flow_set_params", (params,), (self.flow_num_params(),))
 
     def flow_get_params(self, out=None):
         """The parameter vector as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
-        if out is None:
-            out = np.empty(self.flow_num_params(), dtype=np.float32)
-        capi.check(self._L.okenv_flow_get_params(self._h, capi.ptr(out)), self._h)
-        return out
+        return self._get_state("okenv_flow_get_params", {"params": self.flow_num_params()}, None if out is None else {"params": out})["params"]
 
     def flow_set_draw_offset(self, word=None):
         """A device uint32 word (tensor or address) added to the draw index of every later flow_act; None removes it."""
-        capi.check(self._L.okenv_flow_set_draw_offset(self._h, capi.ptr(word)), self._h)
+        self._set_draw_offset("okenv_flow_set_draw_offset", word)
 
     def flow_act(self, cond, record=None):
         """The sampled action of every agent from its condition vector, enqueued on the handle's stream without a synchronisation.
         cond: a device tensor / address of [N, cond_dim] float32.  record: None, or a dict of device tensors / addresses under "x0",
         "x", "action" [N,2] float32 and "alive" [N] uint8, each optional."""
-        if record is None:
-            capi.check(self._L.okenv_flow_act(self._h, capi.ptr(cond), None), self._h)
-            return
-        sizes = {"x0": self.N * 8, "x": self.N * 8, "action": self.N * 8, "alive": self.N}
-        rec = capi.fill_pointers(capi.OkenvFlowRecord(), record, "record", sizes)
-        capi.check(self._L.okenv_flow_act(self._h, capi.ptr(cond), C.byref(rec)), self._h)
+        self._act("okenv_flow_act", capi.OkenvFlowRecord, record, record and {"x0": self.N * 8, "x": self.N * 8, "action": self.N * 8, "alive": self.N},
+                  capi.ptr(cond))
 
     # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) -------------------------------------------------------
     def gcl_create(self, **config):
@@ -916,31 +888,23 @@ class BatchedEnvironment:
         return {name: self.gcl_num_params(name) for name in capi.GCL_NETWORKS}
 
     def gcl_num_params(self, which):
-        n = C.c_int32()
-        capi.check(self._L.okenv_gcl_num_params(self._h, _gcl_which(which), C.byref(n)), self._h)
-        return n.value
+        return self._count("okenv_gcl_num_params", _gcl_which(which))
 
     def gcl_set_params(self, which, params):
         """New parameters of network `which` ("policy" / "value" / "cost"; torch's parameters() order, flattened) from a float32 numpy
-        array or a device tensor.  No synchronisation."""
-        if hasattr(params, "data_ptr"):
-            assert params.is_contiguous() and params.numel() == self.gcl_num_params(which)
-        else:
-            params = _flat_params(params, self.gcl_num_params(which))
-        capi.check(self._L.okenv_gcl_set_params(self._h, _gcl_which(which), capi.ptr(params)), self._h)
+        array or a device tensor.  Enqueued on the handle's stream; the call waits for the stream when it was handed a numpy
+        array (which may be a temporary), not for a device tensor."""
+        self._set_params("okenv_gcl_set_params", (params,), (self.gcl_num_params(which),), _gcl_which(which))
 
     def gcl_state(self, which, out=None):
         """Network `which`'s parameter vector, Adam's two moments ("params", "m", "v") and the int t: float32 numpy arrays, or copied
         into the device tensors of the dict `out` (any subset).  Synchronises."""
-        if out is None:
-            out = {k: np.empty(self.gcl_num_params(which), dtype=np.float32) for k in ("params", "m", "v")}
-        st = capi.fill_pointers(capi.OkenvGclState(), out, "gcl state")
-        capi.check(self._L.okenv_gcl_get_state(self._h, _gcl_which(which), C.byref(st)), self._h)
-        return dict(out, t=int(st.t))
+        return self._get_state("okenv_gcl_get_state", dict.fromkeys(("params", "m", "v"), self.gcl_num_params(which)), out, capi.OkenvGclState,
+                               (_gcl_which(which),))
 
     def gcl_set_draw_offset(self, word=None):
         """A device uint32 word (tensor or address) added to the draw index of every later gcl_act; None removes it."""
-        capi.check(self._L.okenv_gcl_set_draw_offset(self._h, capi.ptr(word)), self._h)
+        self._set_draw_offset("okenv_gcl_set_draw_offset", word)
 
     def gcl_set_greedy(self, greedy):
         capi.check(self._L.okenv_gcl_set_greedy(self._h, 1 if greedy else 0), self._h)
@@ -949,13 +913,9 @@ class BatchedEnvironment:
         """The sampled (or greedy) action of every agent, enqueued on the handle's stream without a synchronisation.  record: None,
         or a dict of device tensors / addresses under "state" [N,R], "eps", "pre", "squashed", "action" [N,2], "logp" [N] float32 and
         "alive" [N] uint8, each optional."""
-        if record is None:
-            capi.check(self._L.okenv_gcl_act(self._h, None), self._h)
-            return
-        sizes = {"state": self.N * self.R * 4, "eps": self.N * 8, "pre": self.N * 8, "squashed": self.N * 8, "action": self.N * 8,
-                 "logp": self.N * 4, "alive": self.N}
-        rec = capi.fill_pointers(capi.OkenvGclRecord(), record, "record", sizes)
-        capi.check(self._L.okenv_gcl_act(self._h, C.byref(rec)), self._h)
+        self._act("okenv_gcl_act", capi.OkenvGclRecord, record, record and
+                  {"state": self.N * self.R * 4, "eps": self.N * 8, "pre": self.N * 8, "squashed": self.N * 8, "action": self.N * 8,
+                   "logp": self.N * 4, "alive": self.N})
 
     def gcl_set_expert(self, state, action):
         """The expert bank from device tensors state [E,R] and action [E,2] (float32, contiguous), copied on the handle's stream."""

@@ -363,10 +363,8 @@ class VectorEnvironment:
 
     def pull_ddpg(self):
         """Copies the device's online actor and critic back into the modules (or tensors) given to enable_ddpg."""
-        flat = {k: torch.empty(n, dtype=torch.float32, device=self.device) for k, n in zip(("actor", "critic"), self.env.ddpg_num_params())}
-        self.env.ddpg_state(out=flat)
-        for tensors, vec in zip(self._ddpg_nets, (flat["actor"], flat["critic"])):
-            self._unflatten(tensors, vec)
+        names = ("actor", "critic")
+        self._pull(dict(zip(names, self._ddpg_nets)), dict(zip(names, self.env.ddpg_num_params())), lambda flat: self.env.ddpg_state(out=flat))
 
     def ddpg_act(self, record=None):
         """The continuous action of every agent from the last observation, written into `throttle` / `steering`: one kernel on the
@@ -388,16 +386,28 @@ class VectorEnvironment:
 
     # ---- continuous REINFORCE (include/okenv.h, DESIGN.md section 20) --------------------------------------------------------
     @staticmethod
-    def _gauss_tensors(policy):
-        """[log_std, fc1.weight, fc1.bias, fc2.weight, fc2.bias, mean.weight, mean.bias] of a module built like the reference's
-        Policy (RLRacers/ReinforceContinuous/Policy.hpp:17-30): parameters() order, the module's own log_std first."""
+    def _layer_tensors(module, what, layers, log_std):
+        """[log_std,] then weight and bias of each Linear layer named in `layers`, of a module built like the reference's
+        (RLRacers/ReinforceContinuous/Policy.hpp:17-30, RLRacers/GuidedCostLearning/Networks.hpp): parameters() order, a policy's own
+        log_std first."""
+        listed = "%s and %s" % (", ".join(layers[:-1]), layers[-1])
         try:
-            t = [policy.log_std, policy.fc1.weight, policy.fc1.bias, policy.fc2.weight, policy.fc2.bias, policy.mean.weight, policy.mean.bias]
+            t = [module.log_std] if log_std else []
+            for name in layers:
+                t += [getattr(module, name).weight, getattr(module, name).bias]
         except AttributeError:
-            raise ValueError("policy: expected a module with log_std, fc1, fc2 and mean (Linear layers with biases)")
+            raise ValueError("%s: expected a module with %s%s (Linear layers with biases)" % (what, "log_std, " if log_std else "", listed))
         if any(x is None for x in t):
-            raise ValueError("policy: fc1, fc2 and mean need their biases")
+            raise ValueError("%s: %s need their biases" % (what, listed))
         return t
+
+    def _pull(self, nets, counts, read):
+        """Copies vectors of the device back into the tensors they were flattened from.  nets: {name: tensors}; counts: {name: floats};
+        read(flat): fills the dict of device vectors `flat` (an env.*_state(out=flat))."""
+        flat = {k: torch.empty(counts[k], dtype=torch.float32, device=self.device) for k in nets}
+        read(flat)
+        for k, tensors in nets.items():
+            self._unflatten(tensors, flat[k])
 
     def enable_gauss_actor(self, policy_module, **config):
         """Attaches the reference's continuous REINFORCE agent (RLRacers/ReinforceContinuous): `policy_module` has log_std [2],
@@ -405,7 +415,7 @@ class VectorEnvironment:
         tanh(mu + exp(log_std) * eps) * scale + bias.  config: the members of okenv_gauss_config but the widths (capi.gauss_config:
         scale, bias, greedy, seed, agent_base).  The device's parameters start from the module's; rollout's update steps them in
         place, and pull_gauss() copies them back."""
-        t = self._gauss_tensors(policy_module)
+        t = self._layer_tensors(policy_module, "policy", ("fc1", "fc2", "mean"), True)
         H1, H2 = t[1].shape[0], t[3].shape[0]
         shapes = [(2,), (H1, self.num_rays), (H1,), (H2, H1), (H2,), (2, H2), (2,)]
         if [tuple(x.shape) for x in t] != shapes:
@@ -431,9 +441,7 @@ class VectorEnvironment:
 
     def pull_gauss(self):
         """Copies the device's parameters back into the module given to enable_gauss_actor."""
-        flat = torch.empty(self.env.gauss_num_params(), dtype=torch.float32, device=self.device)
-        self.env.gauss_state(out={"params": flat})
-        self._unflatten(self._gauss_nets, flat)
+        self._pull({"params": self._gauss_nets}, {"params": self.env.gauss_num_params()}, lambda flat: self.env.gauss_state(out=flat))
 
     def set_gauss_greedy(self, greedy):
         self.env.gauss_set_greedy(greedy)
@@ -446,19 +454,6 @@ class VectorEnvironment:
         self.env.gauss_act(record)
 
     # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) ----------------------------------------------------------
-    @staticmethod
-    def _gcl_tensors(module, what, log_std):
-        """[log_std,] fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc3.weight, fc3.bias of a module built like the reference's
-        (RLRacers/GuidedCostLearning/Networks.hpp): parameters() order, the policy's own log_std first."""
-        try:
-            t = ([module.log_std] if log_std else []) + [module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.fc3.weight,
-                                                        module.fc3.bias]
-        except AttributeError:
-            raise ValueError("%s: expected a module with %sfc1, fc2 and fc3 (Linear layers with biases)" % (what, "log_std, " if log_std else ""))
-        if any(x is None for x in t):
-            raise ValueError("%s: fc1, fc2 and fc3 need their biases" % what)
-        return t
-
     def enable_gcl(self, policy_module, value_module, cost_module, **config):
         """Attaches the reference's guided-cost-learning agent (RLRacers/GuidedCostLearning): `policy_module` has log_std [2] and
         fc1 = Linear(R, H1), fc2 = Linear(H1, H2), fc3 = Linear(H2, 2) -- the device applies ReLU twice, tanh to the mean and samples
@@ -467,8 +462,8 @@ class VectorEnvironment:
         The state is the squared hit distance over the squared sensor range, not observation().  config: the members of okenv_gcl_config
         but the widths (capi.gcl_config: scale, bias, greedy, seed, agent_base).  The device's parameters start from the modules';
         rollout's updates step them in place, and pull_gcl() copies them back."""
-        nets = {"policy": self._gcl_tensors(policy_module, "policy", True), "value": self._gcl_tensors(value_module, "value", False),
-                "cost": self._gcl_tensors(cost_module, "cost", False)}
+        nets = {name: self._layer_tensors(module, name, ("fc1", "fc2", "fc3"), name == "policy")
+                for name, module in (("policy", policy_module), ("value", value_module), ("cost", cost_module))}
         R = self.num_rays
         H1, H2 = nets["policy"][1].shape[0], nets["policy"][3].shape[0]
         C1, C2 = nets["cost"][0].shape[0], nets["cost"][2].shape[0]
@@ -511,9 +506,7 @@ class VectorEnvironment:
     def pull_gcl(self):
         """Copies the device's parameters back into the modules given to enable_gcl."""
         for name, tensors in self._gcl_nets.items():
-            flat = torch.empty(self.env.gcl_num_params(name), dtype=torch.float32, device=self.device)
-            self.env.gcl_state(name, out={"params": flat})
-            self._unflatten(tensors, flat)
+            self._pull({"params": tensors}, {"params": self.env.gcl_num_params(name)}, lambda flat: self.env.gcl_state(name, out=flat))
 
     def set_gcl_greedy(self, greedy):
         self.env.gcl_set_greedy(greedy)
@@ -526,6 +519,15 @@ class VectorEnvironment:
         self.env.gcl_act(record)
 
     # ---- lidar transformer driver (include/okenv.h) ----------------------------------------------------------
+    def _attach_flat(self, family, config, params):
+        """enable_lidar_policy's and enable_flow_policy's hand-over: env.<family>_create(config), then the flat vector `params` (a tensor
+        is brought to this device as float32).  Returns what was handed over, for the caller to keep until the next hand-over."""
+        getattr(self.env, family + "_create")(config)
+        if torch.is_tensor(params):
+            params = params.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        getattr(self.env, family + "_set_params")(params)
+        return params
+
     def enable_lidar_policy(self, config, params):
         """Attaches the reference's imitation policy (ImitationLearningTransformer: LidarTransformer) as a device driver.  config:
         a capi.lidar_config(...) or a dict of its members (num_points defaults to the environment's ray count); params: the flat
@@ -533,11 +535,7 @@ class VectorEnvironment:
         training on."""
         if isinstance(config, dict):
             config = capi.lidar_config(**dict({"num_points": self.num_rays}, **config))
-        self.env.lidar_create(config)
-        if torch.is_tensor(params):
-            params = params.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-        self._lidar_flat = params  # alive until the next hand-over: the copy is asynchronous
-        self.env.lidar_set_params(params)
+        self._lidar_flat = self._attach_flat("lidar", config, params)  # alive until the next hand-over: a tensor's copy is asynchronous
         self.lidar_config = config
         self._lidar_graphs = {}  # a captured launch carries the old shape and vector
 
@@ -555,11 +553,7 @@ class VectorEnvironment:
         training on."""
         if isinstance(config, dict):
             config = capi.flow_config(**dict({"seed": self.seed, "agent_base": self.agent_base}, **config))
-        self.env.flow_create(config)
-        if torch.is_tensor(params):
-            params = params.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-        self._flow_flat = params  # alive until the next hand-over: the copy is asynchronous
-        self.env.flow_set_params(params)
+        self._flow_flat = self._attach_flat("flow", config, params)  # alive until the next hand-over: a tensor's copy is asynchronous
         self.flow_config = config
         self._flow_graphs = {}  # a captured launch carries the old shape and vector
 
