@@ -208,10 +208,16 @@ OK_HD void ok_lidar_add_norm(float *x, const float *y, const int R, const int d,
     }
 }
 
-/* Floats of work space ok_lidar_forward needs */
+/* Floats of work space ok_lidar_forward needs: x, y, q, k, v [R][d]; h, first the attention's context [R][d], then the feed-forward's
+ * hidden layer [R][ff] (ff may be smaller than d); p [R]; the head's hidden layers */
+OK_HDI int ok_lidar_hidden_floats(const ok_lidar_shape s)
+{
+    return s.R * (s.ff > s.d ? s.ff : s.d);
+}
+
 OK_HDI int ok_lidar_work_floats(const ok_lidar_shape s)
 {
-    return 5 * s.R * s.d + s.R * s.ff + s.R + s.h1 + s.h2;
+    return 5 * s.R * s.d + ok_lidar_hidden_floats(s) + s.R + s.h1 + s.h2;
 }
 
 /* The whole forward of one agent on the host: in [R][2] (normalised points) -> o [2] (normalised controls) */
@@ -219,7 +225,7 @@ OK_HD void ok_lidar_forward(const ok_lidar_shape s, const float *params, const f
 {
     const ok_lidar_layout at = ok_lidar_offsets(s);
     const int R = s.R, d = s.d, dh = s.d / s.nhead;
-    float *x = work, *y = x + R * d, *q = y + R * d, *k = q + R * d, *v = k + R * d, *h = v + R * d, *p = h + R * s.ff, *g1 = p + R, *g2 = g1 + s.h1;
+    float *x = work, *y = x + R * d, *q = y + R * d, *k = q + R * d, *v = k + R * d, *h = v + R * d, *p = h + ok_lidar_hidden_floats(s), *g1 = p + R, *g2 = g1 + s.h1;
     const float scale = ok_lidar_scale(dh);
     for (int t = 0; t < R; ++t)
         for (int c = 0; c < d; ++c)

@@ -8,11 +8,51 @@ import _gauss_numpy as gauss
 
 STREAM = 13
 # the three shapes of the rule's tests: one tile wide in both widths and few steps; widths that are no power of two and an odd step
-# count; the reference's
+# count; the reference's.  Behind them the shapes at which the LDS's room, not kFlowStageCols, decides how many columns of W2 the act
+# kernel (openkitchen_amd/csrc/ok_flow.h) stages at a time; what each one reaches is in PATHS below and asserted by the tests that use it
 SHAPES = {
     "tiny": dict(cond_dim=16, hidden=16, steps=3),
     "small": dict(cond_dim=48, hidden=80, steps=5),
     "reference": dict(cond_dim=128, hidden=256, steps=32),
+    "stage48": dict(cond_dim=16, hidden=352, steps=2),
+    "stage32": dict(cond_dim=16, hidden=400, steps=2),
+    "stage16": dict(cond_dim=512, hidden=448, steps=2),
+    "stage16_full": dict(cond_dim=384, hidden=496, steps=2),
+    "largest_plan": dict(cond_dim=464, hidden=480, steps=2),
+}
+OLD_SHAPES = ("tiny", "small", "reference")
+NEW_SHAPES = tuple(name for name in SHAPES if name not in OLD_SHAPES)
+
+# ok_flow.h's and ok_lidar.h's constants; tests/test_flow_rule.py keeps them in step with the headers
+AGENTS, STAGE_COLS, PAD, LDS_BUDGET = 16, 64, 4, 160 * 1024
+
+
+def plan(shape):
+    """okFlowPlaces restated: the columns of W2 staged in LDS at a time (whole tiles that fit behind the rest, at most STAGE_COLS and at
+    most H; 0: layer 2 reads W2 from global memory), the blocks an Euler step takes, whether the room decided, and the plan's bytes."""
+    C, H = shape["cond_dim"], shape["hidden"]
+    ldc, ldh = C + PAD, H + PAD
+    w3s = AGENTS * ldc + 3 * AGENTS * ldh + 2 * AGENTS + 3 * H
+    w2s = (w3s + 2 * ldh + 3) & ~3
+    room = (LDS_BUDGET // 4 - w2s) // ldh
+    room = 0 if room < 0 else room & ~15
+    stage_cols = min(STAGE_COLS, H, room)
+    return dict(stage_cols=stage_cols, room_limited=room < min(STAGE_COLS, H),
+                blocks=[min(stage_cols, H - n0) for n0 in range(0, H, stage_cols)] if stage_cols else [], bytes=4 * (w2s + stage_cols * ldh))
+
+
+# What each new shape exists for, as a predicate on (shape, plan): a later change of a constant that takes the path away fails the
+# test that names the shape, before it compares anything
+PATHS = {
+    # three column tiles for four waves; a short block behind room-limited ones
+    "stage48": lambda s, p: p["stage_cols"] == 48 and p["room_limited"] and p["blocks"] == [48] * 7 + [16],
+    "stage32": lambda s, p: p["stage_cols"] == 32 and p["room_limited"] and s["hidden"] % 32 == 16 and p["blocks"] == [32] * 12 + [16],
+    # one tile at a time with H > 16: many blocks per Euler step
+    "stage16": lambda s, p: p["stage_cols"] == 16 and p["room_limited"] and s["hidden"] > 16 and p["blocks"] == [16] * 28,
+    # ... at the widest H that still stages, the plan within 1 KB of the budget
+    "stage16_full": lambda s, p: p["stage_cols"] == 16 and p["room_limited"] and p["blocks"] == [16] * 31 and LDS_BUDGET - 1024 < p["bytes"] <= LDS_BUDGET,
+    # the largest plan any allowed shape has (tests/test_flow_rule.py walks the grid): the staged block ends 224 bytes under the budget
+    "largest_plan": lambda s, p: p["stage_cols"] == 16 and p["room_limited"] and LDS_BUDGET - 256 < p["bytes"] <= LDS_BUDGET,
 }
 
 

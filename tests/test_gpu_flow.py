@@ -46,6 +46,10 @@ WIDE = dict(cond_dim=512, hidden=512, steps=2)
 def act_case(gpu, name, N):
     shape = WIDE if name == "wide" else mirror.SHAPES[name]
     capi = gpu.capi
+    # the staging of W2 the shape was chosen for is the one its plan selects (tests/_flow_numpy.py)
+    plan = mirror.plan(shape)
+    assert plan["bytes"] == capi.flow_lds_bytes(capi.flow_config(**shape)) <= capi.FLOW_LDS_BUDGET
+    assert (name in mirror.PATHS) == (name in mirror.NEW_SHAPES) and (name not in mirror.PATHS or mirror.PATHS[name](shape, plan)), plan
     rng = np.random.default_rng(7 * N + shape["hidden"])
     base = 2 ** 32 - 10  # the global ids wrap past 2^32 inside the larger populations
     cfgs = {noise: capi.flow_config(noise=noise, seed=13, agent_base=base, **shape) for noise in (0, 1)}
@@ -150,6 +154,18 @@ def test_act_device_equals_host_widest_shape(gpu):
     cfg = gpu.capi.flow_config(**WIDE)
     assert gpu.capi.flow_lds_bytes(cfg) <= gpu.capi.FLOW_LDS_BUDGET < gpu.capi.flow_lds_bytes(cfg) + 16 * (WIDE["hidden"] + 4) * 4
     act_case(gpu, "wide", T + 1)
+
+
+@pytest.mark.parametrize("name", mirror.NEW_SHAPES)
+def test_act_device_equals_host_room_limited_staging(gpu, name):
+    """The widths at which the LDS's room decides the staged block of W2 (mirror.PATHS names it, act_case asserts it first): 48
+    columns (three column tiles for four waves), 32 and 16 with many blocks an Euler step, a short last block behind them, the
+    plans that end next to the budget.  A full workgroup plus one agent."""
+    act_case(gpu, name, T + 1)
+
+
+def test_act_device_equals_host_three_column_tiles_one_agent(gpu):
+    act_case(gpu, "stage48", 1)
 
 
 def test_draw_index(gpu):

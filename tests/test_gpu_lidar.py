@@ -17,6 +17,9 @@ REC = {"action": lambda N, R: torch.full((N, 2), -7.0, device="cuda"), "input": 
 # Random-action steps on Austin after which the population holds crashed and alive agents alike, for 15 .. 33 agents and both ray fans
 # (found with the CPU oracle: 8 calls of rollout_random(25, seed 11) behind reset_random(seed 5) leave 1 .. 3 agents crashed)
 RANDOM_CHUNKS, RANDOM_CHUNK_STEPS = 8, 25
+# ... and so they do at 17 agents with fans of 2, 5, 6 and 16 rays (1 or 2 crashed; a crash depends on the fan).  A single ray leaves
+# nobody crashed behind the 8th call and one agent behind the 7th (the driver re-places crashed agents, so the count does not grow)
+CHUNKS_BY_RAYS = {1: 7}
 
 
 def same(a, b):
@@ -73,7 +76,7 @@ def driven_population(gpu, N, R):
     dev = gpu.BatchedEnvironment.from_track(gpu.Track("Austin"), N, ray_angles_deg=fan(R))
     dev.reset_random(None, 1, 5, 0, 0)
     dev.step(1)
-    for i in range(RANDOM_CHUNKS):
+    for i in range(CHUNKS_BY_RAYS.get(R, RANDOM_CHUNKS)):
         dev.rollout_random(RANDOM_CHUNK_STEPS, 11, 0, RANDOM_CHUNK_STEPS * i)
     return dev
 
@@ -82,6 +85,10 @@ def act_case(gpu, name, N):
     shape = mirror.SHAPES[name]
     R = shape["num_points"]
     cfg = gpu.capi.lidar_config(**shape)
+    # the path of the kernel the shape was chosen for is the one its plan selects (tests/_lidar_numpy.py)
+    plan = mirror.plan(shape)
+    assert plan["bytes"] == gpu.capi.lidar_lds_bytes(cfg) <= gpu.capi.LIDAR_LDS_BUDGET
+    assert (name in mirror.PATHS) == (name in mirror.NEW_SHAPES) and (name not in mirror.PATHS or mirror.PATHS[name](plan)), plan
     rng = np.random.default_rng(7 * N + R)
     params = mirror.random_params(gpu.capi, cfg, rng)
     dev = driven_population(gpu, N, R)
@@ -102,6 +109,9 @@ def act_case(gpu, name, N):
     rel = np.stack([dev.get(gpu.capi.F_REL_X), dev.get(gpu.capi.F_REL_Y)], axis=2)
     want = gpu.capi.lidar_act_host(cfg, params, rel, crashed)
     want["action"] = np.stack([want["throttle"], want["steer"]], axis=1)
+    if N >= 15:  # rays that all miss would feed every agent the same row, the ends of the range
+        rows = want["input"].reshape(N, -1)
+        assert len(np.unique(rows, axis=0)) > N // 2 and float((np.abs(rows) < 0.99).mean()) > 0.5
 
     def check(rec, label):
         dev.sync()
@@ -155,6 +165,16 @@ def test_act_device_equals_host(gpu, name, N):
 
 def test_act_device_equals_host_reference_shape(gpu):
     act_case(gpu, "reference", 33)
+
+
+@pytest.mark.parametrize("N", [1, 17])
+@pytest.mark.parametrize("name", mirror.NEW_SHAPES)
+def test_act_device_equals_host_on_every_path(gpu, name, N):
+    """The shapes that select what the three above never do (mirror.PATHS names it, act_case asserts it first): head groups of two
+    and three column tiles, a head that starts inside a tile, heads of one column and seven attention tasks a thread, an even point
+    count, one point and sixteen, every okLidarUnit<1 .. 4> as the tail of a row block, a short column block behind full ones in
+    out_proj and in the feed-forward, LDS regions sized by the head.  One agent, and a full workgroup plus one."""
+    act_case(gpu, name, N)
 
 
 def test_graph_of_act_and_step_equals_eager(gpu):

@@ -2,6 +2,9 @@
 stack through the exporter, the positional table's two readings, the host entry okenv_lidar_act_host against the mirror, the linear
 piece's fused bias-first chain, and the limits of the C ABI."""
 import ctypes as C
+import os
+import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -11,14 +14,29 @@ import _lidar_numpy as mirror
 
 f32 = np.float32
 INVALID, STATE = -1, -5
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # Item 3's bound on |host entry - float64 mirror| of the normalised outputs, from the same fp32 points, default action ranges.
 # Measured here over the seeds and agent counts below: the largest deviation was 2.07e-7 (reference shape 2.07e-7, tiny 1.51e-7,
 # small 2.01e-7) at outputs of magnitude up to 0.56; the bound is 4 x that, for seed-to-seed spread.  It covers the fp32 network AND
 # the rounding of the denormalised action (half an ulp of a throttle in 64 .. 100 is 3.8e-6, 7.6e-8 once normalised).
 HOST_VS_MIRROR_TOL = 4 * 2.07e-7
-SEEDS = {"reference": (0, 1), "tiny": (0, 1, 2, 3), "small": (0, 1, 2, 3)}
-AGENTS = {"reference": 8, "tiny": 33, "small": 33}  # (the host forward of the reference shape is 4.4 M fused operations per agent)
+# The shapes chosen for the act kernel's other paths (tests/_lidar_numpy.py: PATHS) have other depths and widths, so each has a bound
+# of its own, found the same way: the largest deviation measured over seeds 0 .. 3 and 33 agents, times 4.  random_params' scale
+# stays 1: the smallest of the outputs' maxima per seed is 0.098 (two_tiles_a_head, seed 0), above the guard of 0.05.  Measured, with
+# the largest output over the seeds (one_point's head is 256 and 512 wide behind a single token, hence its longer chains):
+MEASURED_DEVIATION = {
+    "unit_heads": 1.88e-7,        # outputs up to 0.41
+    "wide_group": 1.96e-7,        # 0.68
+    "short_blocks": 2.26e-7,      # 0.71
+    "two_tiles_a_head": 1.76e-7,  # 0.57
+    "sixteen_points": 2.01e-7,    # 0.81
+    "one_point": 5.08e-7,         # 0.58
+}
+TOL = dict({name: HOST_VS_MIRROR_TOL for name in mirror.OLD_SHAPES}, **{name: 4 * v for name, v in MEASURED_DEVIATION.items()})
+SEEDS = dict({"reference": (0, 1), "tiny": (0, 1, 2, 3), "small": (0, 1, 2, 3)}, **{name: (0, 1, 2, 3) for name in mirror.NEW_SHAPES})
+# (the host forward of the reference shape is 4.4 M fused operations per agent)
+AGENTS = dict({"reference": 8, "tiny": 33, "small": 33}, **{name: 33 for name in mirror.NEW_SHAPES})
 
 
 @pytest.fixture(scope="module")
@@ -38,21 +56,34 @@ def torch_model(shape, positional, seed):
     return model
 
 
-def test_mirror_equals_torch_stack(capi):
-    """Item 1: reference shape, 33 agents, a token-dependent positional table."""
+def mirror_vs_torch(capi, name, agents=33):
     from openkitchen_amd.imitation import lidar_params_from_state_dict
-    shape = mirror.SHAPES["reference"]
+    shape = mirror.SHAPES[name]
     model = torch_model(shape, "token", 0)
     cfg = capi.lidar_config(**shape)
     params = lidar_params_from_state_dict(model.state_dict(), positional="token", dtype=torch.float64).numpy()
-    assert params.size == capi.lidar_num_params(cfg) == 841410 + 896
-    x = torch.rand(33, 7, 2, dtype=torch.float64) * 2 - 1
+    assert params.size == capi.lidar_num_params(cfg)
+    x = torch.rand(agents, shape["num_points"], 2, dtype=torch.float64) * 2 - 1
     with torch.no_grad():
         want = model(x).numpy()
     got = mirror.forward(capi, cfg, params, x.numpy())
     err = np.abs(got - want).max()
-    print("mirror vs torch float64: max abs deviation %.3g, outputs up to %.3g" % (err, np.abs(want).max()))
+    print("%s: mirror vs torch float64: max abs deviation %.3g, outputs up to %.3g" % (name, err, np.abs(want).max()))
+    assert np.abs(want).max() > 0.05
     assert err <= 1e-9
+    return params
+
+
+def test_mirror_equals_torch_stack(capi):
+    """Item 1: reference shape, 33 agents, a token-dependent positional table."""
+    assert mirror_vs_torch(capi, "reference").size == 841410 + 896
+
+
+@pytest.mark.parametrize("name", ["wide_group", "unit_heads"])
+def test_mirror_equals_torch_stack_at_other_head_widths(capi, name):
+    """The mirror's head split and scale at heads of 24 columns (no multiple of a tile, scale no power of two) and of one column."""
+    assert mirror.PATHS[name](mirror.plan(mirror.SHAPES[name])) and mirror.SHAPES[name]["d_model"] // mirror.SHAPES[name]["nhead"] in (24, 1)
+    mirror_vs_torch(capi, name)
 
 
 @pytest.mark.parametrize("positional", ["reference", "token"])
@@ -101,14 +132,80 @@ def host_vs_mirror(capi, name, seed):
 
 @pytest.mark.parametrize("name", list(mirror.SHAPES))
 def test_host_entry_against_mirror(capi, name):
-    """Item 3."""
+    """Item 3; the shapes behind the first three reach, in the host entry too, the widths their names say."""
+    if name in mirror.PATHS:
+        assert mirror.PATHS[name](mirror.plan(mirror.SHAPES[name])), name
     worst = 0.0
     for seed in SEEDS[name]:
         err, size = host_vs_mirror(capi, name, seed)
         print("%s seed %d: max abs deviation %.3g, outputs up to %.3g" % (name, seed, err, size))
         assert size > 0.05, "the outputs are too small for an absolute bound to say anything"
         worst = max(worst, err)
-    assert worst <= HOST_VS_MIRROR_TOL
+    assert worst <= TOL[name]
+
+
+@pytest.mark.parametrize("name", list(mirror.SHAPES))
+def test_lds_plan_restated(capi, name):
+    """tests/_lidar_numpy.py's plan() is okLidarPlaces: the same bytes as okenv_lidar_lds_bytes, inside the budget; a new shape
+    reaches the path it was chosen for."""
+    shape = mirror.SHAPES[name]
+    plan = mirror.plan(shape)
+    print(name, plan)
+    assert plan["bytes"] == capi.lidar_lds_bytes(capi.lidar_config(**shape)) <= capi.LIDAR_LDS_BUDGET
+    assert (name in mirror.PATHS) == (name in mirror.NEW_SHAPES)
+    if name in mirror.PATHS:
+        assert mirror.PATHS[name](plan), plan
+    else:  # what the first three shapes have in common, and the others are for
+        assert plan["W"] == 16 and plan["tasks"] <= mirror.THREADS and plan["ldp"] == shape["num_points"] and plan["row_blocks"] in ([3], [4, 3])
+        assert all(b == mirror.COL_BLOCK for b in plan["d_blocks"][:-1] + plan["ff_blocks"][:-1]) and plan["c_by"] == "activations"
+        assert len(plan["d_blocks"]) == 1 or plan["d_blocks"][-1] == mirror.COL_BLOCK
+        assert len(plan["ff_blocks"]) == 1 or plan["ff_blocks"][-1] == mirror.COL_BLOCK
+
+
+def test_lds_plan_restated_over_a_grid(capi):
+    """The restatement against the library wherever the rule's limits allow a shape, the ones over the budget included."""
+    seen = set()
+    for R in (1, 2, 5, 8, 16):
+        for d, nhead in ((16, 1), (16, 16), (48, 2), (48, 3), (64, 2), (80, 5), (96, 4), (128, 8), (256, 8), (512, 1)):
+            for ff, h1, h2 in ((16, 16, 16), (80, 2048, 16), (4096, 16, 2048), (144, 256, 512)):
+                shape = dict(num_points=R, d_model=d, nhead=nhead, num_layers=1, dim_feedforward=ff, head_hidden1=h1, head_hidden2=h2)
+                plan = mirror.plan(shape)
+                assert plan["bytes"] == capi.lidar_lds_bytes(capi.lidar_config(**shape)), shape
+                seen.add((plan["c_by"], plan["s_by"], plan["bytes"] <= capi.LIDAR_LDS_BUDGET))
+    # (a column block never sizes s: 3 rows (W + 4) + 256 (R | 1) exceeds rows x 68 already at W = 16)
+    assert {c for c, s, fits in seen} == {"activations", "head1"} and {s for c, s, fits in seen} == {"attention", "head2"}
+    assert {fits for c, s, fits in seen} == {True, False}
+
+
+def test_mirror_constants_match_the_header():
+    kernel = open(os.path.join(ROOT, "openkitchen_amd", "csrc", "ok_lidar.h")).read()
+
+    def constant(name):
+        return int(re.search(r"constexpr int %s\s*=\s*(\d+);" % name, kernel).group(1))
+
+    assert (constant("kLidarAgents"), constant("kLidarThreads")) == (mirror.AGENTS, mirror.THREADS)
+    assert (constant("kLidarRowBlock"), constant("kLidarColBlock"), constant("kLidarPad")) == (mirror.ROW_BLOCK, mirror.COL_BLOCK, mirror.PAD)
+    budget = re.search(r"constexpr size_t kLidarLdsBudget\s*=\s*(\d+)U \* (\d+)U;", kernel)
+    assert int(budget.group(1)) * int(budget.group(2)) == 160 * 1024
+
+
+def test_host_forwards_stay_inside_their_work_space(tmp_path):
+    """The host forwards of both matrix-core drivers as a stand-alone program under AddressSanitizer and UBSan
+    (tests/cpp/lidar_host_check.cpp), on work spaces of exactly ok_*_work_floats floats: every shape of the two mirrors and the corners
+    of the limits -- a feed-forward narrower than d_model, which once let the attention's context run past the work space's end."""
+    import _flow_numpy as flow_mirror
+    exe = str(tmp_path / "lidar_host_check")
+    subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                    "-g", "-O1", "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tests", "cpp", "lidar_host_check.cpp")], check=True)
+    keys = ("num_points", "d_model", "dim_feedforward", "head_hidden1", "head_hidden2", "nhead", "num_layers")
+    lidar = [tuple(shape[k] for k in keys) for name, shape in mirror.SHAPES.items() if name != "reference"]
+    lidar += [(16, 512, 16, 16, 16, 1, 1), (16, 16, 16, 16, 16, 16, 8), (1, 16, 16, 2048, 16, 2, 1), (1, 16, 16, 16, 2048, 1, 1), (3, 64, 48, 32, 16, 4, 2)]
+    assert any(ff < d for R, d, ff, h1, h2, nhead, layers in lidar)
+    flow = [(shape["cond_dim"], shape["hidden"], 2) for shape in flow_mirror.SHAPES.values()] + [(512, 16, 1), (16, 512, 1)]
+    args = [str(v) for shape in lidar for v in ("lidar",) + shape] + [str(v) for shape in flow for v in ("flow",) + shape]
+    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
+    assert r.returncode == 0 and r.stdout.split() == ["ok", str(len(lidar) + len(flow))], r.stdout[-1000:] + r.stderr[-4000:]
 
 
 def test_host_entry_crashed_and_null_outputs(capi):
