@@ -83,11 +83,12 @@ typedef struct ok_gauss_layout {
     int log_std, w1, b1, w2, b2, w3, b3, total;
 } ok_gauss_layout;
 
-OK_HDI ok_gauss_layout ok_gauss_offsets(const int in, const int h1, const int h2, const int out)
+/* The layout of a vector with `nls` floats of log_std in front: at.log_std = 0 and at.w1 = nls */
+OK_HDI ok_gauss_layout ok_gauss_offsets_nls(const int in, const int h1, const int h2, const int out, const int nls)
 {
     ok_gauss_layout at;
     at.log_std = 0;
-    at.w1 = out;
+    at.w1 = nls;
     at.b1 = at.w1 + h1 * in;
     at.w2 = at.b1 + h1;
     at.b2 = at.w2 + h2 * h1;
@@ -96,6 +97,9 @@ OK_HDI ok_gauss_layout ok_gauss_offsets(const int in, const int h1, const int h2
     at.total = at.b3 + out;
     return at;
 }
+
+/* This learner's vector: one log_std per output */
+OK_HDI ok_gauss_layout ok_gauss_offsets(const int in, const int h1, const int h2, const int out) { return ok_gauss_offsets_nls(in, h1, h2, out, out); }
 
 OK_HDI int ok_gauss_num_params(const int in, const int h1, const int h2, const int out)
 {
@@ -244,13 +248,13 @@ OK_HD void ok_gauss_seed(const int mode, const ok_gauss_comp c, const float z, c
 }
 
 /* Parameter index p as the term it sums: kind 0: dls[a]; 1: dpre1[a] * x[b]; 2: dpre1[a]; 3: dpre2[a] * h1[b]; 4: dpre2[a];
- * 5: dz[a] * h2[b]; 6: dz[a] */
-OK_HDI ok_learn_slot ok_gauss_decode(int p, const int in, const int h1, const int h2, const int out)
+ * 5: dz[a] * h2[b]; 6: dz[a].  The vector begins with `nls` log_std entries. */
+OK_HDI ok_learn_slot ok_gauss_decode_nls(int p, const int in, const int h1, const int h2, const int out, const int nls)
 {
     ok_learn_slot s;
     s.b = 0;
-    if (p < out) { s.kind = 0; s.a = p; return s; }
-    p -= out;
+    if (p < nls) { s.kind = 0; s.a = p; return s; }
+    p -= nls;
     if (p < h1 * in) { s.kind = 1; s.a = p / in; s.b = p - s.a * in; return s; }
     p -= h1 * in;
     if (p < h1) { s.kind = 2; s.a = p; return s; }
@@ -264,6 +268,8 @@ OK_HDI ok_learn_slot ok_gauss_decode(int p, const int in, const int h1, const in
     s.a = p - out * h2;
     return s;
 }
+
+OK_HDI ok_learn_slot ok_gauss_decode(const int p, const int in, const int h1, const int h2, const int out) { return ok_gauss_decode_nls(p, in, h1, h2, out, out); }
 
 /* The term of one sample from its rows */
 OK_HDI float ok_gauss_term(const ok_learn_slot s, const float *x, const float *h1, const float *h2, const float *d1, const float *d2, const float *dz,

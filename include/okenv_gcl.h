@@ -100,19 +100,7 @@ OK_HDI float ok_gcl_state(const float rel_x, const float rel_y)
 
 /* Where the pieces of a network's parameter vector begin: ok_gauss_offsets with `nls` floats of log_std in front (2 for the policy,
  * 0 for the value and the cost network).  at.log_std = 0 and at.w1 = nls. */
-OK_HDI ok_gauss_layout ok_gcl_offsets(const int in, const int h1, const int h2, const int out, const int nls)
-{
-    ok_gauss_layout at;
-    at.log_std = 0;
-    at.w1 = nls;
-    at.b1 = at.w1 + h1 * in;
-    at.w2 = at.b1 + h1;
-    at.b2 = at.w2 + h2 * h1;
-    at.w3 = at.b2 + h2;
-    at.b3 = at.w3 + out * h2;
-    at.total = at.b3 + out;
-    return at;
-}
+OK_HDI ok_gauss_layout ok_gcl_offsets(const int in, const int h1, const int h2, const int out, const int nls) { return ok_gauss_offsets_nls(in, h1, h2, out, nls); }
 
 /* Inputs, outputs and log_std floats of network `which` for a fan of R rays */
 OK_HDI int ok_gcl_in(const int which, const int R) { return which == OK_GCL_COST ? R + 2 : R; }
@@ -125,17 +113,7 @@ OK_HDI int ok_gcl_num_params(const int which, const int R, const int h1, const i
 }
 
 /* Parameter index p as the term it sums: ok_gauss_decode behind `nls` log_std entries */
-OK_HDI ok_learn_slot ok_gcl_decode(const int p, const int in, const int h1, const int h2, const int out, const int nls)
-{
-    if (p < nls) {
-        ok_learn_slot s;
-        s.kind = 0;
-        s.a = p;
-        s.b = 0;
-        return s;
-    }
-    return ok_gauss_decode(p - nls + out, in, h1, h2, out);
-}
+OK_HDI ok_learn_slot ok_gcl_decode(const int p, const int in, const int h1, const int h2, const int out, const int nls) { return ok_gauss_decode_nls(p, in, h1, h2, out, nls); }
 
 OK_HDI float ok_gcl_tanh_back(const float dh, const float h)
 {

@@ -14,7 +14,7 @@
 #include "../../include/okenv_reinforce.h"
 #include "okenv_kernels.h"
 
-// What the three act kernels share (okActorKernel here, okDdpgActKernel, okGaussActKernel), in two pieces, so that every kernel's
+// What the act kernels share (okActorKernel here, okDdpgActKernel, okGaussActKernel, okGclActKernel), in two pieces, so that every kernel's
 // parameter struct keeps the place its widths and vectors had between them (the kernel-argument layout decides how the loads group,
 // docs/HISTORY.md section 29): the step's state with the population, and the words of the draw index
 struct OkActFrame
@@ -155,9 +155,10 @@ struct OkActGroup
     float *x;     // the group's row of xs
 };
 
-// The group copies its row x = dist / 200 into xs (rows `row_stride` apart) and into the record's state (or nullptr), consecutive
-// lanes on consecutive addresses.  The kernel's __syncthreads() follows.
-__device__ __forceinline__ OkActGroup okActBegin(const float *dist, const int N, const int R, float *xs, const int row_stride, float *rec_state)
+// The group copies its row x[i] = state(a * R + i) into xs (rows `row_stride` apart) and into the record's state (or nullptr),
+// consecutive lanes on consecutive addresses.  The kernel's __syncthreads() follows.
+template <class State>
+__device__ __forceinline__ OkActGroup okActBegin(const int N, const int R, float *xs, const int row_stride, float *rec_state, const State &state)
 {
     OkActGroup s;
     s.g              = static_cast<int>(threadIdx.x) / kActorLanes;
@@ -168,12 +169,18 @@ __device__ __forceinline__ OkActGroup okActBegin(const float *dist, const int N,
     s.x              = xs + s.g * row_stride;
     for (int i = s.lane; i < R; i += kActorLanes)
     {
-        const float v = dist[s.a * R + i] / OK_SENSOR_RANGE;
+        const float v = state(s.a * R + i);
         s.x[i]        = v;
         if (s.valid && rec_state != nullptr)
             rec_state[s.a * R + i] = v;
     }
     return s;
+}
+
+// ... with the state of the shared-network actors: x = dist / 200
+__device__ __forceinline__ OkActGroup okActBegin(const float *dist, const int N, const int R, float *xs, const int row_stride, float *rec_state)
+{
+    return okActBegin(N, R, xs, row_stride, rec_state, [dist](const long i) { return dist[i] / OK_SENSOR_RANGE; });
 }
 
 // The record's last field, by the group's first lane

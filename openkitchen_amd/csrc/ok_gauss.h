@@ -10,6 +10,12 @@
 //                          chunk's partial of every parameter's gradient (register tiles over the weight matrices) and of the loss
 //   okReinforceStepKernel  section 19's join kernels on this parameter vector (ok_reinforce.h: OkJoinParams)
 // No atomics anywhere: the sums' order is the rule's.
+//
+// The first section holds what every in -> H1 -> H2 -> out network of the library is built from (okMlp2*, OkGaussNet, OkGaussPlaces,
+// okGaussOuterSums, okGaussVecSums, and their host counterparts); guided cost learning's three networks (ok_gcl.h) use the same pieces.
+// The gradient kernels' frame (places, group rows, the chunk's n) and their eight walks stay written out in okGaussGradKernel and in
+// okGclGradKernel: every shared form of them compiled to other instructions, and the measured ones were slower (docs/HISTORY.md
+// section 35).
 #ifndef OK_GAUSS_H
 #define OK_GAUSS_H
 
@@ -17,8 +23,12 @@
 #include <vector>
 
 #include "../../include/okenv.h"
-#include "../../include/okenv_gauss.h"
+// (ok_gcl_hidden and ok_gcl_back, the hidden layers' activation with ReLU or tanh, are the shared network's and carry the later learner's
+// name only because they are part of the public rule header that the C programs and the numpy restatements read as it is)
+#include "../../include/okenv_gcl.h"
 #include "ok_reinforce.h"
+
+// ==== the two-hidden-layer network: what this learner and guided cost learning share ==================================================
 
 // The network's copy in LDS, in floats from its start: the weight rows of both hidden layers spread to odd strides (the 8 lanes of a
 // group read 8 consecutive rows at the same column: 8 different banks), the rest behind them, log_std last
@@ -115,14 +125,13 @@ __device__ __forceinline__ int okGaussLdsIndex(const int i, const ok_gauss_layou
     return ln.b2 + (i - pv.b2);
 }
 
-// The parameter vector from global memory into LDS (the vector begins with log_std, so its matrices are not 16-byte aligned: 4-byte
-// loads, consecutive threads on consecutive addresses).  A thread issues kGaussStageBatch loads before it stores the first of them, so
-// that their latencies overlap: one workgroup per CU has nobody else to hide them behind.
+// A parameter vector with the layout `pv` from global memory into LDS (a vector that begins with log_std has matrices that are not
+// 16-byte aligned: 4-byte loads, consecutive threads on consecutive addresses).  A thread issues kGaussStageBatch loads before it stores
+// the first of them, so that their latencies overlap: one workgroup per CU has nobody else to hide them behind.
 constexpr int kGaussStageBatch = 8;
-__device__ __forceinline__ void okGaussStage(float *__restrict__ dst, const float *__restrict__ src, const OkGaussNet ln, const int R, const int H1, const int H2,
-                                             const int A)
+__device__ __forceinline__ void okMlp2Stage(float *__restrict__ dst, const float *__restrict__ src, const OkGaussNet ln, const ok_gauss_layout pv, const int in,
+                                            const int H1)
 {
-    const ok_gauss_layout pv = ok_gauss_offsets(R, H1, H2, A);
     for (int base = static_cast<int>(threadIdx.x); base < pv.total; base += kActorThreads * kGaussStageBatch)
     {
         float v[kGaussStageBatch];
@@ -137,129 +146,49 @@ __device__ __forceinline__ void okGaussStage(float *__restrict__ dst, const floa
         {
             const int i = base + u * kActorThreads;
             if (i < pv.total)
-                dst[okGaussLdsIndex(i, pv, ln, R, H1)] = v[u];
+                dst[okGaussLdsIndex(i, pv, ln, in, H1)] = v[u];
         }
     }
 }
 
-// Both hidden layers of the group's sample into its LDS rows, then mu_k in lane k (0 in the lanes from A on).  Lane l owns the units
-// l, l + 8, ... of both layers; h1 passes through LDS between them.  The whole workgroup calls it (two barriers inside).
+// Both hidden layers of the group's sample into its LDS rows (tanh or ReLU), then the third layer's output k in lane k (0 in the lanes
+// from A on).  Lane l owns the units l, l + 8, ... of both layers; h1 passes through LDS between them.  The whole workgroup calls it
+// (two barriers inside).
 // (The rows do not overlap the network or each other: __restrict__ lets two units' loads be in flight at once.)
-__device__ __forceinline__ float okGaussForward(const float *__restrict__ net, const OkGaussNet ln, const int R, const int H1, const int H2, const int A,
-                                                const float *__restrict__ x, float *__restrict__ h1, float *__restrict__ h2, const int lane)
+template <bool Tanh>
+__device__ __forceinline__ float okMlp2Forward(const float *__restrict__ net, const OkGaussNet ln, const int in, const int H1, const int H2, const int A,
+                                               const float *__restrict__ x, float *__restrict__ h1, float *__restrict__ h2, const int lane)
 {
     for (int j = lane; j < H1; j += kActorLanes)
-    {
-        const float s = ok_learn_pre(net + ln.w1, ln.rp, net + ln.b1, R, x, j);
-        h1[j]         = s > 0.F ? s : 0.F;
-    }
+        h1[j] = ok_gcl_hidden(ok_learn_pre(net + ln.w1, ln.rp, net + ln.b1, in, x, j), Tanh ? 1 : 0);
     __syncthreads();
+    if constexpr (Tanh) // (the tanh layer's loop carries no pragma: the compiler chooses, as it did)
+        for (int j = lane; j < H2; j += kActorLanes)
+            h2[j] = ok_gcl_hidden(ok_gauss_pre(net + ln.w2, ln.hp, net + ln.b2, H1, h1, j), 1);
+    else
 #pragma unroll 2
-    for (int j = lane; j < H2; j += kActorLanes)
-    {
-        const float s = ok_gauss_pre(net + ln.w2, ln.hp, net + ln.b2, H1, h1, j);
-        h2[j]         = s > 0.F ? s : 0.F;
-    }
+        for (int j = lane; j < H2; j += kActorLanes)
+            h2[j] = ok_gcl_hidden(ok_gauss_pre(net + ln.w2, ln.hp, net + ln.b2, H1, h1, j), 0);
     __syncthreads();
     return lane < A ? ok_gauss_pre(net + ln.w3, H2, net + ln.b3, H2, h2, lane) : 0.F;
 }
 
-// logp in every lane of the group from the components' n and l, one per lane
-__device__ __forceinline__ float okGaussGroupLogp(const float nk, const float lk, const int A)
+// From the output seeds dz to the hidden seeds d2 and d1 of the group's sample (three barriers inside; the first orders dz, dlss and
+// terms before their readers)
+template <bool Tanh>
+__device__ __forceinline__ void okMlp2Backward(const float *__restrict__ net, const OkGaussNet ln, const int H1, const int H2, const int A,
+                                               const float *__restrict__ dz, const float *__restrict__ h1, const float *__restrict__ h2, float *__restrict__ d1,
+                                               float *__restrict__ d2, const int lane)
 {
-    float n[OK_ACTOR_MAX_ACTIONS], l[OK_ACTOR_MAX_ACTIONS];
-#pragma unroll
-    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
-    {
-        n[k] = __shfl(nk, k, kActorLanes);
-        l[k] = __shfl(lk, k, kActorLanes);
-    }
-    return ok_gauss_logp(n, l, A);
-}
-
-// ---- acting ---------------------------------------------------------------------------------------------------------------------
-
-struct OkGaussActParams
-{
-    OkActFrame         f; // (ok_actor.h)
-    int                H1, H2;
-    const float       *params;
-    OkActDrawWords     draw;
-    float              scale[2], bias[2];
-    int                greedy;
-    uint32_t           seed, agent_base;
-    okenv_gauss_record rec;
-};
-
-__global__ __launch_bounds__(kActorThreads) void okGaussActKernel(const OkGaussActParams p)
-{
-    const int        R = p.f.R, H1 = p.H1, H2 = p.H2;
-    const OkGaussNet ln  = okGaussNet(R, H1, H2, 2);
-    float           *net = ok_actor_lds, *xs = net + ln.floats, *h1s = xs + kActorAgents * ln.rp, *h2s = h1s + kActorAgents * okGaussHiddenStride(H1);
-    okGaussStage(net, p.params, ln, R, H1, H2, 2);
-    const OkActGroup s = okActBegin(p.f.st.dist, p.f.N, R, xs, ln.rp, p.rec.state);
-    const int        g = s.g, lane = s.lane;
-    const long       a = s.a;
     __syncthreads();
-    const float mu = okGaussForward(net, ln, R, H1, H2, 2, s.x, h1s + g * okGaussHiddenStride(H1), h2s + g * okGaussHiddenStride(H2), lane);
-    // lanes 0 and 1 take one component each: the draw, exp, tanh and log (fp64 evaluations)
-    const int   k  = lane & 1;
-    const float ls = net[ln.ls + k];
-    float       eps = 0.F;
-    if (p.greedy == 0 && lane < 2)
-        eps = ok_gauss_eps(p.seed, p.agent_base + static_cast<uint32_t>(a), okActDraw(p.draw), k);
-    float               z;
-    const ok_gauss_comp c    = ok_gauss_component(mu, ls, eps, 0.F, 0, p.greedy, &z);
-    const float         act  = ok_gauss_action(c.t, k == 1 ? p.scale[1] : p.scale[0], k == 1 ? p.bias[1] : p.bias[0]);
-    const float         logp = okGaussGroupLogp(c.n, c.l, 2);
-    const float         act1 = __shfl(act, 1, kActorLanes), eps1 = __shfl(eps, 1, kActorLanes), pre1 = __shfl(c.pre, 1, kActorLanes);
-    if (lane != 0 || !s.valid)
-        return;
-    p.f.st.thr[a]   = act;
-    p.f.st.steer[a] = act1;
-    if (p.rec.eps != nullptr && p.greedy == 0)
-    {
-        p.rec.eps[2 * a]     = eps;
-        p.rec.eps[2 * a + 1] = eps1;
-    }
-    if (p.rec.pre != nullptr)
-    {
-        p.rec.pre[2 * a]     = c.pre;
-        p.rec.pre[2 * a + 1] = pre1;
-    }
-    if (p.rec.action != nullptr)
-    {
-        p.rec.action[2 * a]     = act;
-        p.rec.action[2 * a + 1] = act1;
-    }
-    if (p.rec.logp != nullptr)
-        p.rec.logp[a] = logp;
-    okActAlive(p.f.st.crashed, p.rec.alive, a);
+    for (int j = lane; j < H2; j += kLearnLanes)
+        d2[j] = ok_gcl_back(ok_learn_back_hidden(net + ln.w3, H2, A, dz, j, 1.F), h2[j], Tanh ? 1 : 0);
+    __syncthreads();
+#pragma unroll 2
+    for (int i = lane; i < H1; i += kLearnLanes)
+        d1[i] = ok_gcl_back(ok_gauss_back(net + ln.w2, ln.hp, H2, d2, i), h1[i], Tanh ? 1 : 0);
+    __syncthreads();
 }
-
-// ok_gauss_normal_pair alone, one word pair per thread (okenv_debug_normal)
-__global__ void __launch_bounds__(256) okDebugNormalKernel(const uint32_t *w0, const uint32_t *w1, float *out0, float *out1, const unsigned n)
-{
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        ok_gauss_normal_pair(w0[i], w1[i], out0 + i, out1 + i);
-}
-
-// ---- the update -----------------------------------------------------------------------------------------------------------------
-
-// What the gradient kernel needs for one slice, by value (the join kernels take section 19's OkJoinParams)
-struct OkGaussParams
-{
-    int               R, H1, H2, A;
-    int               M, Bk;
-    int               P, cols; // parameters; columns of the partials: [params | loss]
-    long              base;    // first position of the slice: k * B
-    const int32_t    *order;   // or nullptr
-    okenv_gauss_batch in;
-    int               mode;
-    const float      *params;
-    float            *part; // [C][cols]
-};
 
 // Threads own parameters of a bias-like piece and walk the chunk's samples in ascending position
 __device__ __forceinline__ void okGaussVecSums(float *dst, const float *rows, const int stride, const int count, const int n)
@@ -320,6 +249,214 @@ __device__ __forceinline__ void okGaussOuterSums(float *dst, const float *a_rows
         }
 }
 
+// The end of a two-component act kernel: lanes 0 and 1 of the group hold one component's act, eps and pre (and squashed: only where the
+// record has that field) and every lane logp; the group's first lane stores the controls and the record `rec`
+// (a kernel whose record has no squashed passes none: the constant 0 makes its exchange below dead code, and the compiler drops it)
+template <class Rec>
+__device__ __forceinline__ void okMlp2ActStore(const OkActFrame &f, const OkActGroup &s, const Rec &rec, const int greedy, const float act, const float eps,
+                                               const float pre, const float logp, float *rec_squashed = nullptr, const float squashed = 0.F)
+{
+    const float act1 = __shfl(act, 1, kActorLanes), eps1 = __shfl(eps, 1, kActorLanes), pre1 = __shfl(pre, 1, kActorLanes);
+    const float sq1  = __shfl(squashed, 1, kActorLanes);
+    if (s.lane != 0 || !s.valid)
+        return;
+    const long a  = s.a;
+    f.st.thr[a]   = act;
+    f.st.steer[a] = act1;
+    if (rec.eps != nullptr && greedy == 0)
+    {
+        rec.eps[2 * a]     = eps;
+        rec.eps[2 * a + 1] = eps1;
+    }
+    if (rec.pre != nullptr)
+    {
+        rec.pre[2 * a]     = pre;
+        rec.pre[2 * a + 1] = pre1;
+    }
+    if (rec_squashed != nullptr)
+    {
+        rec_squashed[2 * a]     = squashed;
+        rec_squashed[2 * a + 1] = sq1;
+    }
+    if (rec.action != nullptr)
+    {
+        rec.action[2 * a]     = act;
+        rec.action[2 * a + 1] = act1;
+    }
+    if (rec.logp != nullptr)
+        rec.logp[a] = logp;
+    okActAlive(f.st.crashed, rec.alive, a);
+}
+
+// ---- the same on the host (no GPU) ----------------------------------------------------------------------------------------------
+
+// What the act configurations of both learners share
+inline const char *okMlp2CheckAct(const int greedy, const float *scale, const float *bias)
+{
+    if (greedy != 0 && greedy != 1)
+        return "greedy must be 0 or 1";
+    for (int k = 0; k < 2; ++k)
+        if (!(scale[k] - scale[k] == 0.F) || !(bias[k] - bias[k] == 0.F))
+            return "a scale or bias is not finite";
+    return nullptr;
+}
+
+// One network on the host: its shape, its hidden layers' activation and where its pieces begin
+struct OkMlp2HostNet
+{
+    int             in, H1, H2, A, nls, tanh;
+    ok_gauss_layout pv;
+    const float    *par;
+};
+
+inline OkMlp2HostNet okMlp2HostNet(const int in, const int H1, const int H2, const int A, const int nls, const int tanh, const float *par)
+{
+    return OkMlp2HostNet{in, H1, H2, A, nls, tanh, ok_gauss_offsets_nls(in, H1, H2, A, nls), par};
+}
+
+// Both hidden layers and the third layer's outputs of one sample
+inline void okMlp2HostForward(const OkMlp2HostNet &n, const float *x, float *h1, float *h2, float *z3)
+{
+    const float *par = n.par;
+    for (int j = 0; j < n.H1; ++j)
+        h1[j] = ok_gcl_hidden(ok_learn_pre(par + n.pv.w1, n.in, par + n.pv.b1, n.in, x, j), n.tanh);
+    for (int j = 0; j < n.H2; ++j)
+        h2[j] = ok_gcl_hidden(ok_gauss_pre(par + n.pv.w2, n.H1, par + n.pv.b2, n.H1, h1, j), n.tanh);
+    for (int k = 0; k < n.A; ++k)
+        z3[k] = ok_gauss_pre(par + n.pv.w3, n.H2, par + n.pv.b3, n.H2, h2, k);
+}
+
+// The rows of one chunk on the host: what a gradient kernel keeps in LDS
+struct OkMlp2HostRows
+{
+    std::vector<float> xs, h1s, d1s, h2s, d2s, dzs, dlss, terms;
+    std::vector<int>   clips;
+    explicit OkMlp2HostRows(const OkMlp2HostNet &n)
+        : xs(static_cast<size_t>(OK_LEARN_CHUNK) * n.in), h1s(static_cast<size_t>(OK_LEARN_CHUNK) * n.H1), d1s(h1s.size()),
+          h2s(static_cast<size_t>(OK_LEARN_CHUNK) * n.H2), d2s(h2s.size()), dzs(static_cast<size_t>(OK_LEARN_CHUNK) * OK_ACTOR_MAX_ACTIONS), dlss(dzs.size()),
+          terms(OK_LEARN_CHUNK), clips(OK_LEARN_CHUNK)
+    {
+    }
+};
+
+// A chunk of n samples: fill(q, x) writes sample q's input row; seed(q, z3, dz, dls, &term, &clipped) its output seeds from the third
+// layer's outputs.  Writes the columns [parameters | loss] and returns the chunk's clip count.
+template <class Fill, class Seed>
+inline uint32_t okMlp2HostChunk(const OkMlp2HostNet &net, OkMlp2HostRows &r, const int n, float *col, const Fill &fill, const Seed &seed)
+{
+    const size_t W = OK_ACTOR_MAX_ACTIONS;
+    const int    P = net.pv.total;
+    for (int q = 0; q < n; ++q)
+    {
+        const size_t sq = static_cast<size_t>(q);
+        float       *x = r.xs.data() + sq * net.in, *h1 = r.h1s.data() + sq * net.H1, *d1 = r.d1s.data() + sq * net.H1, *h2 = r.h2s.data() + sq * net.H2;
+        float       *d2 = r.d2s.data() + sq * net.H2, *dz = r.dzs.data() + sq * W, *dls = r.dlss.data() + sq * W;
+        float        z3[OK_ACTOR_MAX_ACTIONS] = {0.F};
+        fill(q, x);
+        okMlp2HostForward(net, x, h1, h2, z3);
+        for (size_t a = 0; a < W; ++a)
+            dz[a] = dls[a] = 0.F;
+        r.clips[sq] = 0;
+        seed(q, z3, dz, dls, &r.terms[sq], &r.clips[sq]);
+        for (int j = 0; j < net.H2; ++j)
+            d2[j] = ok_gcl_back(ok_learn_back_hidden(net.par + net.pv.w3, net.H2, net.A, dz, j, 1.F), h2[j], net.tanh);
+        for (int i = 0; i < net.H1; ++i)
+            d1[i] = ok_gcl_back(ok_gauss_back(net.par + net.pv.w2, net.H1, net.H2, d2, i), h1[i], net.tanh);
+    }
+    for (int pi = 0; pi < P; ++pi)
+    {
+        const ok_learn_slot s = ok_gauss_decode_nls(pi, net.in, net.H1, net.H2, net.A, net.nls);
+        float               a = 0.F;
+        for (int q = 0; q < n; ++q)
+        {
+            const size_t sq = static_cast<size_t>(q);
+            a = a + ok_gauss_term(s, r.xs.data() + sq * net.in, r.h1s.data() + sq * net.H1, r.h2s.data() + sq * net.H2, r.d1s.data() + sq * net.H1,
+                                  r.d2s.data() + sq * net.H2, r.dzs.data() + sq * W, r.dlss.data() + sq * W);
+        }
+        col[pi] = a;
+    }
+    col[P]       = okLearnHostSumTerms(r.terms.data(), n);
+    uint32_t cnt = 0U;
+    for (int q = 0; q < n; ++q)
+        cnt += static_cast<uint32_t>(r.clips[static_cast<size_t>(q)]);
+    return cnt;
+}
+
+// ==== the continuous REINFORCE learner =================================================================================================
+
+// logp in every lane of the group from the components' n and l, one per lane
+__device__ __forceinline__ float okGaussGroupLogp(const float nk, const float lk, const int A)
+{
+    float n[OK_ACTOR_MAX_ACTIONS], l[OK_ACTOR_MAX_ACTIONS];
+#pragma unroll
+    for (int k = 0; k < OK_ACTOR_MAX_ACTIONS; ++k)
+    {
+        n[k] = __shfl(nk, k, kActorLanes);
+        l[k] = __shfl(lk, k, kActorLanes);
+    }
+    return ok_gauss_logp(n, l, A);
+}
+
+// ---- acting ---------------------------------------------------------------------------------------------------------------------
+
+struct OkGaussActParams
+{
+    OkActFrame         f; // (ok_actor.h)
+    int                H1, H2;
+    const float       *params;
+    OkActDrawWords     draw;
+    float              scale[2], bias[2];
+    int                greedy;
+    uint32_t           seed, agent_base;
+    okenv_gauss_record rec;
+};
+
+__global__ __launch_bounds__(kActorThreads) void okGaussActKernel(const OkGaussActParams p)
+{
+    const int        R = p.f.R, H1 = p.H1, H2 = p.H2;
+    const OkGaussNet ln  = okGaussNet(R, H1, H2, 2);
+    float           *net = ok_actor_lds, *xs = net + ln.floats, *h1s = xs + kActorAgents * ln.rp, *h2s = h1s + kActorAgents * okGaussHiddenStride(H1);
+    okMlp2Stage(net, p.params, ln, ok_gauss_offsets(R, H1, H2, 2), R, H1);
+    const OkActGroup s = okActBegin(p.f.st.dist, p.f.N, R, xs, ln.rp, p.rec.state);
+    const int        g = s.g, lane = s.lane;
+    __syncthreads();
+    const float mu = okMlp2Forward<false>(net, ln, R, H1, H2, 2, s.x, h1s + g * okGaussHiddenStride(H1), h2s + g * okGaussHiddenStride(H2), lane);
+    // lanes 0 and 1 take one component each: the draw, exp, tanh and log (fp64 evaluations)
+    const int   k  = lane & 1;
+    const float ls = net[ln.ls + k];
+    float       eps = 0.F;
+    if (p.greedy == 0 && lane < 2)
+        eps = ok_gauss_eps(p.seed, p.agent_base + static_cast<uint32_t>(s.a), okActDraw(p.draw), k);
+    float               z;
+    const ok_gauss_comp c   = ok_gauss_component(mu, ls, eps, 0.F, 0, p.greedy, &z);
+    const float         act = ok_gauss_action(c.t, k == 1 ? p.scale[1] : p.scale[0], k == 1 ? p.bias[1] : p.bias[0]);
+    okMlp2ActStore(p.f, s, p.rec, p.greedy, act, eps, c.pre, okGaussGroupLogp(c.n, c.l, 2));
+}
+
+// ok_gauss_normal_pair alone, one word pair per thread (okenv_debug_normal)
+__global__ void __launch_bounds__(256) okDebugNormalKernel(const uint32_t *w0, const uint32_t *w1, float *out0, float *out1, const unsigned n)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n)
+        ok_gauss_normal_pair(w0[i], w1[i], out0 + i, out1 + i);
+}
+
+// ---- the update -----------------------------------------------------------------------------------------------------------------
+
+// What the gradient kernel needs for one slice, by value (the join kernels take section 19's OkJoinParams)
+struct OkGaussParams
+{
+    int               R, H1, H2, A;
+    int               M, Bk;
+    int               P, cols; // parameters; columns of the partials: [params | loss]
+    long              base;    // first position of the slice: k * B
+    const int32_t    *order;   // or nullptr
+    okenv_gauss_batch in;
+    int               mode;
+    const float      *params;
+    float            *part; // [C][cols]
+};
+
 __global__ __launch_bounds__(kLearnThreads) void okGaussGradKernel(const OkGaussParams p)
 {
     const int           R = p.R, H1 = p.H1, H2 = p.H2, A = p.A;
@@ -339,9 +476,10 @@ __global__ __launch_bounds__(kLearnThreads) void okGaussGradKernel(const OkGauss
     float *__restrict__ d2 = d2s + g * s2, *__restrict__ dz = dzs + g * OK_ACTOR_MAX_ACTIONS;
     for (int i = lane; i < R; i += kLearnLanes)
         x[i] = p.in.state[static_cast<size_t>(idx) * static_cast<size_t>(R) + i];
-    okGaussStage(net, p.params, ln, R, H1, H2, A);
+    const ok_gauss_layout pv = ok_gauss_offsets(R, H1, H2, A);
+    okMlp2Stage(net, p.params, ln, pv, R, H1);
     __syncthreads();
-    const float mu = okGaussForward(net, ln, R, H1, H2, A, x, h1, h2, lane);
+    const float mu = okMlp2Forward<false>(net, ln, R, H1, H2, A, x, h1, h2, lane);
     // lane k takes component k: exp, tanh, log and the two seeds
     const float G     = p.in.ret[idx];
     const bool  score = p.mode == OK_GAUSS_GRAD_SCORE, mine = lane < A;
@@ -356,20 +494,9 @@ __global__ __launch_bounds__(kLearnThreads) void okGaussGradKernel(const OkGauss
     dlss[g * OK_ACTOR_MAX_ACTIONS + lane] = mine ? dls : 0.F;
     if (lane == 0)
         terms[g] = -(logp * G);
-    __syncthreads();
-    for (int j = lane; j < H2; j += kLearnLanes)
-        d2[j] = ok_learn_back_hidden(net + ln.w3, H2, A, dz, j, h2[j]);
-    __syncthreads();
-#pragma unroll 2
-    for (int i = lane; i < H1; i += kLearnLanes)
-    {
-        const float dh = ok_gauss_back(net + ln.w2, ln.hp, H2, d2, i);
-        d1[i]          = h1[i] > 0.F ? dh : 0.F;
-    }
-    __syncthreads();
+    okMlp2Backward<false>(net, ln, H1, H2, A, dz, h1, h2, d1, d2, lane);
     // the per-parameter walks into the chunk's row [params | loss]
-    const ok_gauss_layout pv  = ok_gauss_offsets(R, H1, H2, A);
-    float                *col = p.part + static_cast<size_t>(chunk) * static_cast<size_t>(p.cols);
+    float *col = p.part + static_cast<size_t>(chunk) * static_cast<size_t>(p.cols);
     okGaussOuterSums(col + pv.w2, d2s, s2, H2, h1s, s1, H1, n);
     okGaussOuterSums(col + pv.w1, d1s, s1, H1, xs, ln.rp, R, n);
     okGaussOuterSums(col + pv.w3, dzs, OK_ACTOR_MAX_ACTIONS, A, h2s, s2, H2, n);
@@ -401,12 +528,7 @@ inline const char *okGaussCheckConfig(const okenv_gauss_config *c, const int R)
         return "config is NULL";
     if (const char *why = okGaussCheckShape(R, c->hidden1, c->hidden2, 2))
         return why;
-    if (c->greedy != 0 && c->greedy != 1)
-        return "greedy must be 0 or 1";
-    for (int k = 0; k < 2; ++k)
-        if (!(c->scale[k] - c->scale[k] == 0.F) || !(c->bias[k] - c->bias[k] == 0.F))
-            return "a scale or bias is not finite";
-    return nullptr;
+    return okMlp2CheckAct(c->greedy, c->scale, c->bias);
 }
 
 inline const char *okGaussCheckCall(const okenv_gauss_update_config *cfg, const okenv_gauss_batch *batch, const int32_t M, const int32_t B)
@@ -430,38 +552,20 @@ inline const char *okGaussCheckCall(const okenv_gauss_update_config *cfg, const 
     return nullptr;
 }
 
-// Both hidden layers and the means of one sample
-inline void okGaussHostForward(const float *par, const int R, const int H1, const int H2, const int A, const float *x, float *h1, float *h2, float *mu)
-{
-    const ok_gauss_layout pv = ok_gauss_offsets(R, H1, H2, A);
-    for (int j = 0; j < H1; ++j)
-    {
-        const float s = ok_learn_pre(par + pv.w1, R, par + pv.b1, R, x, j);
-        h1[j]         = s > 0.F ? s : 0.F;
-    }
-    for (int j = 0; j < H2; ++j)
-    {
-        const float s = ok_gauss_pre(par + pv.w2, H1, par + pv.b2, H1, h1, j);
-        h2[j]         = s > 0.F ? s : 0.F;
-    }
-    for (int k = 0; k < A; ++k)
-        mu[k] = ok_gauss_pre(par + pv.w3, H2, par + pv.b3, H2, h2, k);
-}
-
 // The action of n agents on host arrays; every output may be nullptr
 inline void okGaussActHost(const okenv_gauss_config &c, const float *par, const int R, const int n, const float *dist, const uint8_t *crashed,
                            const uint32_t draw_index, float *throttle, float *steer, float *eps_out, float *pre_out, float *action, float *logp,
                            float *state, uint8_t *alive)
 {
-    const int          H1 = c.hidden1, H2 = c.hidden2;
-    std::vector<float> x(static_cast<size_t>(R)), h1(static_cast<size_t>(H1)), h2(static_cast<size_t>(H2));
+    const OkMlp2HostNet net = okMlp2HostNet(R, c.hidden1, c.hidden2, 2, 2, 0, par);
+    std::vector<float>  x(static_cast<size_t>(R)), h1(static_cast<size_t>(net.H1)), h2(static_cast<size_t>(net.H2));
     for (int a = 0; a < n; ++a)
     {
         const size_t sa = static_cast<size_t>(a);
         for (int i = 0; i < R; ++i)
             x[static_cast<size_t>(i)] = dist[sa * R + i] / OK_SENSOR_RANGE;
         float mu[OK_ACTOR_MAX_ACTIONS], nn[OK_ACTOR_MAX_ACTIONS] = {0.F}, ll[OK_ACTOR_MAX_ACTIONS] = {0.F}, act[2], eps[2], pre[2];
-        okGaussHostForward(par, R, H1, H2, 2, x.data(), h1.data(), h2.data(), mu);
+        okMlp2HostForward(net, x.data(), h1.data(), h2.data(), mu);
         for (int k = 0; k < 2; ++k)
         {
             eps[k] = c.greedy != 0 ? 0.F : ok_gauss_eps(c.seed, c.agent_base + static_cast<uint32_t>(a), draw_index, k);
@@ -500,64 +604,41 @@ inline void okGaussUpdateHost(const okenv_learner_params &lp, const okenv_gauss_
                               okenv_gauss_state &st, const okenv_gauss_batch &in, const int M, const int B, const int32_t *order,
                               const okenv_gauss_output &out)
 {
-    const int          P = ok_gauss_num_params(R, H1, H2, A);
-    const size_t       W = OK_ACTOR_MAX_ACTIONS;
-    std::vector<float> terms(OK_LEARN_CHUNK);
-    std::vector<float> xs(static_cast<size_t>(OK_LEARN_CHUNK) * R), h1s(static_cast<size_t>(OK_LEARN_CHUNK) * H1), d1s(h1s.size());
-    std::vector<float> h2s(static_cast<size_t>(OK_LEARN_CHUNK) * H2), d2s(h2s.size()), dzs(OK_LEARN_CHUNK * W), dlss(OK_LEARN_CHUNK * W);
-    const bool            score = cfg.grad_mode == OK_GAUSS_GRAD_SCORE;
-    const ok_gauss_layout pv    = ok_gauss_offsets(R, H1, H2, A);
-    const float          *par   = st.params;
-    // the per-sample mathematics of one chunk
-    const auto chunk_sums = [&](const long first, const int n, float *col)
+    const OkMlp2HostNet net = okMlp2HostNet(R, H1, H2, A, A, 0, st.params);
+    OkMlp2HostRows      rows(net);
+    const bool          score  = cfg.grad_mode == OK_GAUSS_GRAD_SCORE;
+    const auto          sample = [&](const long pos)
+    { return static_cast<size_t>(ok_learn_clamp_index(order != nullptr ? static_cast<long long>(order[pos]) : static_cast<long long>(pos), M)); };
+    const auto fill_from = [&](const long first)
     {
-        for (int q = 0; q < n; ++q)
+        return [&, first](const int q, float *x)
         {
-            const long   pos = first + q;
-            const int    idx = ok_learn_clamp_index(order != nullptr ? static_cast<long long>(order[pos]) : static_cast<long long>(pos), M);
-            const size_t sq = static_cast<size_t>(q), si = static_cast<size_t>(idx);
-            float       *x = xs.data() + sq * R, *h1 = h1s.data() + sq * H1, *d1 = d1s.data() + sq * H1, *h2 = h2s.data() + sq * H2, *d2 = d2s.data() + sq * H2;
-            float       *dz = dzs.data() + sq * W, *dls = dlss.data() + sq * W;
+            const size_t si = sample(first + q);
             for (int i = 0; i < R; ++i)
                 x[i] = in.state[si * R + i];
-            float mu[OK_ACTOR_MAX_ACTIONS], nn[OK_ACTOR_MAX_ACTIONS] = {0.F}, ll[OK_ACTOR_MAX_ACTIONS] = {0.F};
-            okGaussHostForward(par, R, H1, H2, A, x, h1, h2, mu);
-            const float G = in.ret[idx];
-            for (int a = 0; a < OK_ACTOR_MAX_ACTIONS; ++a)
+        };
+    };
+    const auto seed_from = [&](const long first)
+    {
+        return [&, first](const int q, const float *mu, float *dz, float *dls, float *term, int *)
+        {
+            const size_t si = sample(first + q);
+            const float  G  = in.ret[si];
+            float        nn[OK_ACTOR_MAX_ACTIONS] = {0.F}, ll[OK_ACTOR_MAX_ACTIONS] = {0.F};
+            for (int a = 0; a < A; ++a)
             {
-                dz[a] = dls[a] = 0.F;
-                if (a >= A)
-                    continue;
                 float               z;
-                const ok_gauss_comp c = ok_gauss_component(mu[a], par[a], score ? 0.F : in.eps[si * A + a], score ? in.pre[si * A + a] : 0.F, score ? 1 : 0, 0, &z);
+                const ok_gauss_comp c =
+                    ok_gauss_component(mu[a], net.par[a], score ? 0.F : in.eps[si * A + a], score ? in.pre[si * A + a] : 0.F, score ? 1 : 0, 0, &z);
                 ok_gauss_seed(cfg.grad_mode, c, z, G, &dz[a], &dls[a]);
                 nn[a] = c.n;
                 ll[a] = c.l;
             }
-            terms[sq] = -(ok_gauss_logp(nn, ll, A) * G);
-            for (int j = 0; j < H2; ++j)
-                d2[j] = ok_learn_back_hidden(par + pv.w3, H2, A, dz, j, h2[j]);
-            for (int i = 0; i < H1; ++i)
-            {
-                const float dh = ok_gauss_back(par + pv.w2, H1, H2, d2, i);
-                d1[i]          = h1[i] > 0.F ? dh : 0.F;
-            }
-        }
-        for (int pi = 0; pi < P; ++pi)
-        {
-            const ok_learn_slot s = ok_gauss_decode(pi, R, H1, H2, A);
-            float               a = 0.F;
-            for (int q = 0; q < n; ++q)
-            {
-                const size_t sq = static_cast<size_t>(q);
-                a = a + ok_gauss_term(s, xs.data() + sq * R, h1s.data() + sq * H1, h2s.data() + sq * H2, d1s.data() + sq * H1, d2s.data() + sq * H2,
-                                      dzs.data() + sq * W, dlss.data() + sq * W);
-            }
-            col[pi] = a;
-        }
-        col[P] = okLearnHostSumTerms(terms.data(), n);
+            *term = -(ok_gauss_logp(nn, ll, A) * G);
+        };
     };
-    okSliceUpdateHost(lp, cfg.accumulate != 0, okJoinOn(P, st.params, st.m, st.v, cfg.reduce, out.grad), st.t, M, B, out.loss, chunk_sums);
+    okSliceUpdateHost(lp, cfg.accumulate != 0, okJoinOn(net.pv.total, st.params, st.m, st.v, cfg.reduce, out.grad), st.t, M, B, out.loss,
+                      [&](const long first, const int n, float *col) { (void)okMlp2HostChunk(net, rows, n, col, fill_from(first), seed_from(first)); });
 }
 
 #endif // OK_GAUSS_H

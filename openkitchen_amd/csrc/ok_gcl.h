@@ -10,9 +10,9 @@
 //                             advantages (raw = G - v and the chunk's fp64 partials of its statistics)
 //   okGclAdvStatsKernel       one workgroup: ok_batch_tree over the chunk partials, ok_batch_finish
 //   okGclAdvNormKernel        adv = (raw - mean) / (std + 1e-8f)
-//   okGclGradKernel<Head>     okGaussGradKernel's plan for the three heads (policy, value, cost): one workgroup per chunk of 32
-//                             positions, forward, seed and backward into the samples' LDS rows, then okGaussOuterSums / okGaussVecSums;
-//                             the heads differ in input assembly, activation, the output squash and the seed only
+//   okGclGradKernel<Head>     okGaussGradKernel's plan and pieces (ok_gauss.h: okMlp2Stage, okMlp2Forward, okMlp2Backward, okGaussOuterSums,
+//                             okGaussVecSums) for the three heads (policy, value, cost); the heads differ in input assembly, activation,
+//                             the output squash, the seed and the clip count only
 //   okGclClipCountKernel      the policy slices' clip counts into the step's slot
 //   okReinforceStepKernel     section 19's join kernels on the policy's and the value's parameter vector (OkJoinParams)
 //   okGclCostStepKernel       the cost update's join: two sets, each divided by its own count, then added, Adam in place
@@ -55,65 +55,6 @@ inline size_t okGclLdsBytes(const int R, const int H1, const int H2, const int C
     return std::max(std::max(okGclGradLdsBytes(R, H1, H2, 2), okGclGradLdsBytes(R, H1, H2, 1)), okGclGradLdsBytes(R + 2, C1, C2, 1));
 }
 
-// ---- device pieces -----------------------------------------------------------------------------------------------------------------
-
-// okGaussStage for a parameter vector with the layout `pv` (ok_gcl_offsets: the value and the cost network have no log_std in front)
-__device__ __forceinline__ void okGclStage(float *__restrict__ dst, const float *__restrict__ src, const OkGaussNet ln, const ok_gauss_layout pv, const int in,
-                                           const int H1)
-{
-    for (int base = static_cast<int>(threadIdx.x); base < pv.total; base += kActorThreads * kGaussStageBatch)
-    {
-        float v[kGaussStageBatch];
-#pragma unroll
-        for (int u = 0; u < kGaussStageBatch; ++u)
-        {
-            const int i = base + u * kActorThreads;
-            v[u]        = i < pv.total ? src[i] : 0.F;
-        }
-#pragma unroll
-        for (int u = 0; u < kGaussStageBatch; ++u)
-        {
-            const int i = base + u * kActorThreads;
-            if (i < pv.total)
-                dst[okGaussLdsIndex(i, pv, ln, in, H1)] = v[u];
-        }
-    }
-}
-
-// okGaussForward with the layers' activation chosen: both hidden layers of the group's sample into its LDS rows, then the third
-// layer's output k in lane k (0 in the lanes from A on).  The whole workgroup calls it (two barriers inside).
-template <bool Tanh>
-__device__ __forceinline__ float okGclForward(const float *__restrict__ net, const OkGaussNet ln, const int in, const int H1, const int H2, const int A,
-                                              const float *__restrict__ x, float *__restrict__ h1, float *__restrict__ h2, const int lane)
-{
-    if constexpr (!Tanh)
-        return okGaussForward(net, ln, in, H1, H2, A, x, h1, h2, lane);
-    for (int j = lane; j < H1; j += kActorLanes)
-        h1[j] = ok_gcl_hidden(ok_learn_pre(net + ln.w1, ln.rp, net + ln.b1, in, x, j), 1);
-    __syncthreads();
-    for (int j = lane; j < H2; j += kActorLanes)
-        h2[j] = ok_gcl_hidden(ok_gauss_pre(net + ln.w2, ln.hp, net + ln.b2, H1, h1, j), 1);
-    __syncthreads();
-    return lane < A ? ok_gauss_pre(net + ln.w3, H2, net + ln.b3, H2, h2, lane) : 0.F;
-}
-
-// From the output seeds dz to the hidden seeds d2 and d1 of the group's sample (two barriers inside; the first orders dz before its
-// readers)
-template <bool Tanh>
-__device__ __forceinline__ void okGclBackward(const float *__restrict__ net, const OkGaussNet ln, const int H1, const int H2, const int A,
-                                              const float *__restrict__ dz, const float *__restrict__ h1, const float *__restrict__ h2, float *__restrict__ d1,
-                                              float *__restrict__ d2, const int lane)
-{
-    __syncthreads();
-    for (int j = lane; j < H2; j += kLearnLanes)
-        d2[j] = ok_gcl_back(ok_learn_back_hidden(net + ln.w3, H2, A, dz, j, 1.F), h2[j], Tanh ? 1 : 0);
-    __syncthreads();
-#pragma unroll 2
-    for (int i = lane; i < H1; i += kLearnLanes)
-        d1[i] = ok_gcl_back(ok_gauss_back(net + ln.w2, ln.hp, H2, d2, i), h1[i], Tanh ? 1 : 0);
-    __syncthreads();
-}
-
 // ---- acting ------------------------------------------------------------------------------------------------------------------------
 
 struct OkGclActParams
@@ -133,60 +74,23 @@ __global__ __launch_bounds__(kActorThreads) void okGclActKernel(const OkGclActPa
     const int        R = p.f.R, H1 = p.H1, H2 = p.H2;
     const OkGaussNet ln  = okGaussNet(R, H1, H2, 2);
     float           *net = ok_actor_lds, *xs = net + ln.floats, *h1s = xs + kActorAgents * ln.rp, *h2s = h1s + kActorAgents * okGaussHiddenStride(H1);
-    okGaussStage(net, p.params, ln, R, H1, H2, 2);
-    // okActBegin with this learner's state: the squared norm of the hit over the squared range
-    const int  g = static_cast<int>(threadIdx.x) / kActorLanes, lane = static_cast<int>(threadIdx.x) & (kActorLanes - 1);
-    const long a_raw = static_cast<long>(blockIdx.x) * kActorAgents + g;
-    const bool valid = a_raw < p.f.N;
-    const long a     = valid ? a_raw : static_cast<long>(p.f.N) - 1; // (a spare group takes the last agent and stores nothing)
-    float     *x     = xs + g * ln.rp;
-    for (int i = lane; i < R; i += kActorLanes)
-    {
-        const float v = ok_gcl_state(p.f.st.rel_x[a * R + i], p.f.st.rel_y[a * R + i]);
-        x[i]          = v;
-        if (valid && p.rec.state != nullptr)
-            p.rec.state[a * R + i] = v;
-    }
+    okMlp2Stage(net, p.params, ln, ok_gauss_offsets(R, H1, H2, 2), R, H1);
+    // this learner's state: the squared norm of the hit over the squared range
+    const float     *rel_x = p.f.st.rel_x, *rel_y = p.f.st.rel_y;
+    const OkActGroup s = okActBegin(p.f.N, R, xs, ln.rp, p.rec.state, [rel_x, rel_y](const long i) { return ok_gcl_state(rel_x[i], rel_y[i]); });
+    const int        g = s.g, lane = s.lane;
     __syncthreads();
-    const float z3 = okGaussForward(net, ln, R, H1, H2, 2, x, h1s + g * okGaussHiddenStride(H1), h2s + g * okGaussHiddenStride(H2), lane);
+    const float z3 = okMlp2Forward<false>(net, ln, R, H1, H2, 2, s.x, h1s + g * okGaussHiddenStride(H1), h2s + g * okGaussHiddenStride(H2), lane);
     // lanes 0 and 1 take one component each
     const int   k   = lane & 1;
     const float ls  = net[ln.ls + k], mu = ok_tanhf(z3);
     float       eps = 0.F;
     if (p.greedy == 0 && lane < 2)
-        eps = ok_gcl_eps(p.seed, p.agent_base + static_cast<uint32_t>(a), okActDraw(p.draw), k);
+        eps = ok_gcl_eps(p.seed, p.agent_base + static_cast<uint32_t>(s.a), okActDraw(p.draw), k);
     const ok_gcl_comp c    = ok_gcl_sample(mu, ls, eps, p.greedy);
     const float       act  = ok_gauss_action(c.squashed, k == 1 ? p.scale[1] : p.scale[0], k == 1 ? p.bias[1] : p.bias[0]);
     const float       logp = __shfl(c.n, 0, kActorLanes) + __shfl(c.n, 1, kActorLanes);
-    const float       act1 = __shfl(act, 1, kActorLanes), eps1 = __shfl(eps, 1, kActorLanes), pre1 = __shfl(c.pre, 1, kActorLanes);
-    const float       sq1  = __shfl(c.squashed, 1, kActorLanes);
-    if (lane != 0 || !valid)
-        return;
-    p.f.st.thr[a]   = act;
-    p.f.st.steer[a] = act1;
-    if (p.rec.eps != nullptr && p.greedy == 0)
-    {
-        p.rec.eps[2 * a]     = eps;
-        p.rec.eps[2 * a + 1] = eps1;
-    }
-    if (p.rec.pre != nullptr)
-    {
-        p.rec.pre[2 * a]     = c.pre;
-        p.rec.pre[2 * a + 1] = pre1;
-    }
-    if (p.rec.squashed != nullptr)
-    {
-        p.rec.squashed[2 * a]     = c.squashed;
-        p.rec.squashed[2 * a + 1] = sq1;
-    }
-    if (p.rec.action != nullptr)
-    {
-        p.rec.action[2 * a]     = act;
-        p.rec.action[2 * a + 1] = act1;
-    }
-    if (p.rec.logp != nullptr)
-        p.rec.logp[a] = logp;
-    okActAlive(p.f.st.crashed, p.rec.alive, a);
+    okMlp2ActStore(p.f, s, p.rec, p.greedy, act, eps, c.pre, logp, p.rec.squashed, c.squashed);
 }
 
 // ---- forward only: the cost of rows, the value sweep -------------------------------------------------------------------------------
@@ -218,9 +122,9 @@ __global__ __launch_bounds__(kLearnThreads) void okGclForwardKernel(const OkGclF
     float *__restrict__ x = xs + g * ln.rp;
     for (int i = lane; i < in; i += kLearnLanes)
         x[i] = i < R ? p.state[idx * static_cast<size_t>(R) + i] : p.squashed[idx * 2U + (i - R)];
-    okGclStage(net, p.params, ln, ok_gcl_offsets(in, H1, H2, 1, 0), in, H1);
+    okMlp2Stage(net, p.params, ln, ok_gcl_offsets(in, H1, H2, 1, 0), in, H1);
     __syncthreads();
-    const float z = okGclForward<Tanh>(net, ln, in, H1, H2, 1, x, h1s + g * s1, h2s + g * s2, lane);
+    const float z = okMlp2Forward<Tanh>(net, ln, in, H1, H2, 1, x, h1s + g * s1, h2s + g * s2, lane);
     if (lane == 0 && g < n)
     {
         const float v = p.ret != nullptr ? p.ret[idx] - z : z;
@@ -343,9 +247,9 @@ __global__ __launch_bounds__(kLearnThreads) void okGclGradKernel(const OkGclGrad
             x[i] = p.state[idx * static_cast<size_t>(R) + i];
     }
     const ok_gauss_layout pv = ok_gcl_offsets(in, H1, H2, A, kNls);
-    okGclStage(net, p.params, ln, pv, in, H1);
+    okMlp2Stage(net, p.params, ln, pv, in, H1);
     __syncthreads();
-    const float z3 = okGclForward<kTanh>(net, ln, in, H1, H2, A, x, h1, h2, lane);
+    const float z3 = okMlp2Forward<kTanh>(net, ln, in, H1, H2, A, x, h1, h2, lane);
     float       seed = 0.F, dls = 0.F, term = 0.F;
     int         clipped = 0;
     if constexpr (Head == OK_GCL_POLICY)
@@ -373,7 +277,7 @@ __global__ __launch_bounds__(kLearnThreads) void okGclGradKernel(const OkGclGrad
         terms[g] = term;
         clips[g] = clipped;
     }
-    okGclBackward<kTanh>(net, ln, H1, H2, A, dz, h1, h2, d1, d2, lane);
+    okMlp2Backward<kTanh>(net, ln, H1, H2, A, dz, h1, h2, d1, d2, lane);
     // the per-parameter walks into the chunk's row [params | loss]
     float *col = p.part + static_cast<size_t>(chunk) * static_cast<size_t>(p.cols);
     okGaussOuterSums(col + pv.w2, d2s, s2, H2, h1s, s1, H1, n);
@@ -465,12 +369,7 @@ inline const char *okGclCheckConfig(const okenv_gcl_config *c, const int R)
         return "config is NULL";
     if (const char *why = okGclCheckShape(R, c->hidden1, c->hidden2, c->cost_hidden1, c->cost_hidden2))
         return why;
-    if (c->greedy != 0 && c->greedy != 1)
-        return "greedy must be 0 or 1";
-    for (int k = 0; k < 2; ++k)
-        if (!(c->scale[k] - c->scale[k] == 0.F) || !(c->bias[k] - c->bias[k] == 0.F))
-            return "a scale or bias is not finite";
-    return nullptr;
+    return okMlp2CheckAct(c->greedy, c->scale, c->bias);
 }
 
 inline const char *okGclCheckCostCall(const okenv_gcl_cost_batch *batch, const int32_t Mp, const int32_t Me)
@@ -504,87 +403,10 @@ inline bool okGclStateComplete(const okenv_gcl_state *s)
     return s != nullptr && s->params != nullptr && s->m != nullptr && s->v != nullptr && s->t >= 0;
 }
 
-// One network on the host: its shape and where its pieces begin
-struct OkGclHostNet
+// Network `which` of a fan of R rays on the host
+inline OkMlp2HostNet okGclHostNet(const int which, const int R, const int H1, const int H2, const float *par)
 {
-    int             in, H1, H2, A, nls, tanh;
-    ok_gauss_layout pv;
-    const float    *par;
-};
-
-inline OkGclHostNet okGclHostNet(const int which, const int R, const int H1, const int H2, const float *par)
-{
-    OkGclHostNet n{ok_gcl_in(which, R), H1, H2, ok_gcl_out(which), ok_gcl_nls(which), which == OK_GCL_COST ? 1 : 0, {}, par};
-    n.pv = ok_gcl_offsets(n.in, H1, H2, n.A, n.nls);
-    return n;
-}
-
-// Both hidden layers and the third layer's outputs of one sample
-inline void okGclHostForward(const OkGclHostNet &n, const float *x, float *h1, float *h2, float *z3)
-{
-    const float *par = n.par;
-    for (int j = 0; j < n.H1; ++j)
-        h1[j] = ok_gcl_hidden(ok_learn_pre(par + n.pv.w1, n.in, par + n.pv.b1, n.in, x, j), n.tanh);
-    for (int j = 0; j < n.H2; ++j)
-        h2[j] = ok_gcl_hidden(ok_gauss_pre(par + n.pv.w2, n.H1, par + n.pv.b2, n.H1, h1, j), n.tanh);
-    for (int k = 0; k < n.A; ++k)
-        z3[k] = ok_gauss_pre(par + n.pv.w3, n.H2, par + n.pv.b3, n.H2, h2, k);
-}
-
-// The rows of one chunk on the host: what a gradient kernel keeps in LDS
-struct OkGclHostRows
-{
-    std::vector<float> xs, h1s, d1s, h2s, d2s, dzs, dlss, terms;
-    std::vector<int>   clips;
-    explicit OkGclHostRows(const OkGclHostNet &n)
-        : xs(static_cast<size_t>(OK_LEARN_CHUNK) * n.in), h1s(static_cast<size_t>(OK_LEARN_CHUNK) * n.H1), d1s(h1s.size()),
-          h2s(static_cast<size_t>(OK_LEARN_CHUNK) * n.H2), d2s(h2s.size()), dzs(static_cast<size_t>(OK_LEARN_CHUNK) * OK_ACTOR_MAX_ACTIONS), dlss(dzs.size()),
-          terms(OK_LEARN_CHUNK), clips(OK_LEARN_CHUNK)
-    {
-    }
-};
-
-// A chunk of n samples: fill(q, x) writes sample q's input row; seed(q, z3, dz, dls, &term, &clipped) its output seeds from the third
-// layer's outputs.  Writes the columns [parameters | loss] and returns the chunk's clip count.
-template <class Fill, class Seed>
-inline uint32_t okGclHostChunk(const OkGclHostNet &net, OkGclHostRows &r, const int n, float *col, const Fill &fill, const Seed &seed)
-{
-    const size_t W = OK_ACTOR_MAX_ACTIONS;
-    const int    P = net.pv.total;
-    for (int q = 0; q < n; ++q)
-    {
-        const size_t sq = static_cast<size_t>(q);
-        float       *x = r.xs.data() + sq * net.in, *h1 = r.h1s.data() + sq * net.H1, *d1 = r.d1s.data() + sq * net.H1, *h2 = r.h2s.data() + sq * net.H2;
-        float       *d2 = r.d2s.data() + sq * net.H2, *dz = r.dzs.data() + sq * W, *dls = r.dlss.data() + sq * W;
-        float        z3[OK_ACTOR_MAX_ACTIONS] = {0.F};
-        fill(q, x);
-        okGclHostForward(net, x, h1, h2, z3);
-        for (size_t a = 0; a < W; ++a)
-            dz[a] = dls[a] = 0.F;
-        r.clips[sq] = 0;
-        seed(q, z3, dz, dls, &r.terms[sq], &r.clips[sq]);
-        for (int j = 0; j < net.H2; ++j)
-            d2[j] = ok_gcl_back(ok_learn_back_hidden(net.par + net.pv.w3, net.H2, net.A, dz, j, 1.F), h2[j], net.tanh);
-        for (int i = 0; i < net.H1; ++i)
-            d1[i] = ok_gcl_back(ok_gauss_back(net.par + net.pv.w2, net.H1, net.H2, d2, i), h1[i], net.tanh);
-    }
-    for (int pi = 0; pi < P; ++pi)
-    {
-        const ok_learn_slot s = ok_gcl_decode(pi, net.in, net.H1, net.H2, net.A, net.nls);
-        float               a = 0.F;
-        for (int q = 0; q < n; ++q)
-        {
-            const size_t sq = static_cast<size_t>(q);
-            a = a + ok_gauss_term(s, r.xs.data() + sq * net.in, r.h1s.data() + sq * net.H1, r.h2s.data() + sq * net.H2, r.d1s.data() + sq * net.H1,
-                                  r.d2s.data() + sq * net.H2, r.dzs.data() + sq * W, r.dlss.data() + sq * W);
-        }
-        col[pi] = a;
-    }
-    col[P]       = okLearnHostSumTerms(r.terms.data(), n);
-    uint32_t cnt = 0U;
-    for (int q = 0; q < n; ++q)
-        cnt += static_cast<uint32_t>(r.clips[static_cast<size_t>(q)]);
-    return cnt;
+    return okMlp2HostNet(ok_gcl_in(which, R), H1, H2, ok_gcl_out(which), ok_gcl_nls(which), which == OK_GCL_COST ? 1 : 0, par);
 }
 
 // The action of n agents on host arrays; every output may be nullptr
@@ -592,7 +414,7 @@ inline void okGclActHost(const okenv_gcl_config &c, const float *par, const int 
                          const uint32_t draw_index, float *throttle, float *steer, float *eps_out, float *pre_out, float *squashed, float *action,
                          float *logp, float *state, uint8_t *alive)
 {
-    const OkGclHostNet net = okGclHostNet(OK_GCL_POLICY, R, c.hidden1, c.hidden2, par);
+    const OkMlp2HostNet net = okGclHostNet(OK_GCL_POLICY, R, c.hidden1, c.hidden2, par);
     std::vector<float> x(static_cast<size_t>(R)), h1(static_cast<size_t>(net.H1)), h2(static_cast<size_t>(net.H2));
     for (int a = 0; a < n; ++a)
     {
@@ -600,7 +422,7 @@ inline void okGclActHost(const okenv_gcl_config &c, const float *par, const int 
         for (int i = 0; i < R; ++i)
             x[static_cast<size_t>(i)] = ok_gcl_state(rel_x[sa * R + i], rel_y[sa * R + i]);
         float z3[OK_ACTOR_MAX_ACTIONS] = {0.F}, eps[2], nn[2];
-        okGclHostForward(net, x.data(), h1.data(), h2.data(), z3);
+        okMlp2HostForward(net, x.data(), h1.data(), h2.data(), z3);
         for (int k = 0; k < 2; ++k)
         {
             eps[k]              = c.greedy != 0 ? 0.F : ok_gcl_eps(c.seed, c.agent_base + static_cast<uint32_t>(a), draw_index, k);
@@ -631,7 +453,7 @@ inline void okGclActHost(const okenv_gcl_config &c, const float *par, const int 
 }
 
 // out[s] = the output of network `which` (value or cost) for M rows; squashed: the cost network's input tail
-inline void okGclForwardHost(const OkGclHostNet &net, const int R, const float *state, const float *squashed, const int M, float *out)
+inline void okGclForwardHost(const OkMlp2HostNet &net, const int R, const float *state, const float *squashed, const int M, float *out)
 {
     std::vector<float> x(static_cast<size_t>(net.in)), h1(static_cast<size_t>(net.H1)), h2(static_cast<size_t>(net.H2));
     for (int s = 0; s < M; ++s)
@@ -639,7 +461,7 @@ inline void okGclForwardHost(const OkGclHostNet &net, const int R, const float *
         for (int i = 0; i < net.in; ++i)
             x[static_cast<size_t>(i)] = i < R ? state[static_cast<size_t>(s) * R + i] : squashed[static_cast<size_t>(s) * 2U + (i - R)];
         float z3[OK_ACTOR_MAX_ACTIONS] = {0.F};
-        okGclHostForward(net, x.data(), h1.data(), h2.data(), z3);
+        okMlp2HostForward(net, x.data(), h1.data(), h2.data(), z3);
         out[s] = z3[0];
     }
 }
@@ -649,8 +471,8 @@ inline void okGclCostUpdateHost(const okenv_learner_params &lp, const uint32_t s
                                 const float *bank_state, const float *bank_action, const int E, const okenv_gcl_cost_batch &in, const int Mp, const int Me,
                                 const okenv_gcl_cost_output &out)
 {
-    const OkGclHostNet net = okGclHostNet(OK_GCL_COST, R, C1, C2, st.params);
-    OkGclHostRows      rows(net);
+    const OkMlp2HostNet net = okGclHostNet(OK_GCL_COST, R, C1, C2, st.params);
+    OkMlp2HostRows      rows(net);
     const int          P = net.pv.total, cols = P + 1, Ce = (Me + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK, Cp = (Mp + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
     std::vector<float> part(static_cast<size_t>(Ce + Cp) * cols);
     const uint32_t     draw = static_cast<uint32_t>(st.t);
@@ -659,7 +481,7 @@ inline void okGclCostUpdateHost(const okenv_learner_params &lp, const uint32_t s
         const bool expert = chunk < Ce;
         const long first  = static_cast<long>(expert ? chunk : chunk - Ce) * OK_LEARN_CHUNK;
         const int  n      = static_cast<int>(std::min<long>(OK_LEARN_CHUNK, (expert ? Me : Mp) - first));
-        (void)okGclHostChunk(
+        (void)okMlp2HostChunk(
             net, rows, n, part.data() + static_cast<size_t>(chunk) * cols,
             [&](const int q, float *x)
             {
@@ -690,7 +512,7 @@ inline void okGclCostUpdateHost(const okenv_learner_params &lp, const uint32_t s
 }
 
 // The advantages of a call on host arrays: adv [M]
-inline void okGclAdvHost(const OkGclHostNet &value, const int R, const float *state, const float *ret, const int M, float *adv)
+inline void okGclAdvHost(const OkMlp2HostNet &value, const int R, const float *state, const float *ret, const int M, float *adv)
 {
     okGclForwardHost(value, R, state, nullptr, M, adv);
     const int           C = (M + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
@@ -719,7 +541,7 @@ inline void okGclPolicyUpdateHost(const okenv_learner_params &lp, const okenv_gc
                                   okenv_gcl_state &pol, okenv_gcl_state &val, const okenv_gcl_batch &in, const int M, const int B, const int32_t *order,
                                   const okenv_gcl_output &out)
 {
-    const OkGclHostNet pn = okGclHostNet(OK_GCL_POLICY, R, H1, H2, pol.params), vn = okGclHostNet(OK_GCL_VALUE, R, H1, H2, val.params);
+    const OkMlp2HostNet pn = okGclHostNet(OK_GCL_POLICY, R, H1, H2, pol.params), vn = okGclHostNet(OK_GCL_VALUE, R, H1, H2, val.params);
     std::vector<float> adv(static_cast<size_t>(M));
     okGclAdvHost(vn, R, in.state, in.ret, M, adv.data());
     if (out.adv != nullptr)
@@ -741,11 +563,11 @@ inline void okGclPolicyUpdateHost(const okenv_learner_params &lp, const okenv_gc
     if (out.clipped != nullptr)
         std::fill(out.clipped, out.clipped + (accumulate ? 1 : okLearnMinibatches(M, B)), 0);
     {
-        OkGclHostRows rows(pn);
+        OkMlp2HostRows rows(pn);
         okSliceUpdateHost(lp, accumulate, okJoinOn(pn.pv.total, pol.params, pol.m, pol.v, cfg.reduce, out.grad_policy), tp, M, B, out.policy_loss,
                           [&](const long first, const int n, float *col)
                           {
-                              const uint32_t cnt = okGclHostChunk(pn, rows, n, col, fill_from(first),
+                              const uint32_t cnt = okMlp2HostChunk(pn, rows, n, col, fill_from(first),
                                                                   [&](const int q, const float *z3, float *dz, float *dls, float *term, int *clipped)
                                                                   {
                                                                       const size_t idx = sample(first + q);
@@ -771,11 +593,11 @@ inline void okGclPolicyUpdateHost(const okenv_learner_params &lp, const okenv_gc
                           });
     }
     {
-        OkGclHostRows rows(vn);
+        OkMlp2HostRows rows(vn);
         okSliceUpdateHost(lp, accumulate, okJoinOn(vn.pv.total, val.params, val.m, val.v, cfg.reduce, out.grad_value), tv, M, B, out.value_loss,
                           [&](const long first, const int n, float *col)
                           {
-                              (void)okGclHostChunk(vn, rows, n, col, fill_from(first),
+                              (void)okMlp2HostChunk(vn, rows, n, col, fill_from(first),
                                                    [&](const int q, const float *z3, float *dz, float *, float *term, int *)
                                                    { ok_learn_value_seed(z3[0], in.ret[sample(first + q)], &dz[0], term); });
                           });
