@@ -1,15 +1,18 @@
 """The reference's flow-matching driver (FlowMatching/) for a whole population: demonstrations with bird's-eye frames from the
 device's potential-field expert, the conditional flow-matching policy trained on them in PyTorch with the reference's recipe, and N
-agents driven by it -- the conv encoder once per step in PyTorch, the 32 evaluations of the trunk in the device's one act kernel.
+agents driven by it -- the conv encoder once per step in PyTorch (or, with --device-encoder, in the device's conv kernels), the 32
+evaluations of the trunk in the device's one act kernel.
 
     python examples/flow_racer.py [--agents 256] [--frame-size 64] [--demo-steps 128] [--epochs 3] [--steps 256] [--episodes 2]
-                                  [--flow-steps 32] [--graph-chunk 8] [--torch-sampler] [--track Austin]
+                                  [--flow-steps 32] [--graph-chunk 8] [--torch-sampler] [--device-encoder] [--track Austin]
 
 1. record: every living agent's frame and the expert's action (demonstrations.collect_demonstrations(images=True));
 2. train: x_t on the straight path from noise to the normalised action, MSE on the velocity, Adam 1e-3 (train_flow_matching.py);
 3. hand over: the trunk's weights as one flat vector (flow.flow_params_from_state_dict -> enable_flow_policy);
 4. drive: `step`, `camera()`, the encoder, `flow_act(cond)` (flow.drive), and the share of agents that survive every episode.
 --torch-sampler drives with the PyTorch loop over the trunk instead (flow.sample), for comparison.
+--device-encoder hands the trained encoder over beside the trunk (flow.bev_params_from_state_dict -> enable_bev_encoder) and drives
+with no PyTorch op in the loop; --frame-size is then the encoder's image size (a multiple of 8 in 16 .. 128).
 """
 import argparse
 import os
@@ -52,7 +55,9 @@ def main(argv=None):
     ap.add_argument("--track", default="Austin")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--torch-sampler", action="store_true")
+    ap.add_argument("--device-encoder", action="store_true")
     a = ap.parse_args(argv)
+    assert not (a.torch_sampler and a.device_encoder), "--device-encoder feeds the device sampler"
     torch.manual_seed(a.seed)
     venv = VectorEnvironment(a.track, a.agents, auto_reset=False, randomize_lane=True, randomize_heading=True, seed=a.seed)
     venv.enable_camera(width=a.frame_size, height=a.frame_size, fmt="rgba")
@@ -70,17 +75,24 @@ def main(argv=None):
     sd = model.action_flow_trunk.state_dict()
     cfg = flow.flow_config_from_state_dict(sd, steps=a.flow_steps, seed=a.seed, agent_base=venv.agent_base)
     venv.enable_flow_policy(cfg, flow.flow_params_from_state_dict(sd))
+    if a.device_encoder:
+        sd = model.bev_encoder.state_dict()
+        venv.enable_bev_encoder(flow.bev_config_from_state_dict(sd, image_size=a.frame_size), flow.bev_params_from_state_dict(sd))
     # the first driven step, recorded: what the device sampled, from which noise and which condition
     venv.reset()
     venv.step()
+    frame = venv.camera()
     with torch.no_grad():
-        cond = model.bev_encoder(flow.frames_to_input(venv.camera())).contiguous()
+        cond = cond_torch = model.bev_encoder(flow.frames_to_input(frame)).contiguous()
+    if a.device_encoder:
+        cond = venv.bev_encode(frame)
+        print("first step: max |device - PyTorch encoder| = %.4g on the condition" % float((cond - cond_torch).abs().max()))
     first = {"x0": torch.empty((a.agents, 2), device=venv.device), "x": torch.empty((a.agents, 2), device=venv.device),
              "action": torch.empty((a.agents, 2), device=venv.device)}
     venv.flow_act(cond, first)
     want = flow.sample(model, cond, first["x0"], a.flow_steps)
     print("first step: max |device - PyTorch sampler| = %.4g on the normalised sample" % float((first["x"] - want).abs().max()))
-    first["cond"] = cond
+    first["cond"], first["cond_torch"] = cond, cond_torch
     # 4. driving
     gen = torch.Generator(device=venv.device).manual_seed(a.seed)
     survival = []
@@ -89,12 +101,12 @@ def main(argv=None):
         if a.torch_sampler:
             steps = torch_drive(venv, model, a.steps, a.flow_steps, gen)
         else:
-            steps = flow.drive(venv, model, a.steps, graph_chunk=a.graph_chunk)
+            steps = flow.drive(venv, model, a.steps, graph_chunk=a.graph_chunk, encoder="device" if a.device_encoder else "torch")
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         survival.append(float((~venv.done).float().mean()))
         print("episode %d: %d agents, %d steps with the %s in %.3f s (%.3g agent-steps/s); survival %.3f"
-              % (episode, a.agents, steps, "PyTorch sampler" if a.torch_sampler else "device act", dt, a.agents * steps / dt, survival[-1]))
+              % (episode, a.agents, steps, "PyTorch sampler" if a.torch_sampler else ("device encoder and act" if a.device_encoder else "device act"), dt, a.agents * steps / dt, survival[-1]))
     out = {"model": model, "config": cfg, "first": first, "survival": survival, "losses": losses,
            "throttle": venv.throttle.clone(), "steering": venv.steering.clone()}
     print("actions finite %s" % bool(torch.isfinite(out["throttle"]).all() and torch.isfinite(out["steering"]).all()))

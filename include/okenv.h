@@ -1044,6 +1044,48 @@ OKENV_API int okenv_flow_act(okenv_t h, const float *cond, const okenv_flow_reco
 OKENV_API int okenv_flow_act_host(const okenv_flow_config *config, const float *params, int32_t n, const float *cond, const uint8_t *crashed,
                                   uint32_t draw_index, float *throttle, float *steer, float *x0, float *x, uint8_t *alive);
 
+/* ---- The flow driver's image encoder -----------------------------------------------------------------------
+ * FlowMatching's BEVEncoder (flow_matching_model.py) for every agent of the handle: from the camera's RGBA8 frames
+ * (okenv_render_views, rendered at image_size x image_size) the /255 normalisation, three stride-2 convolutions with ReLU, the global
+ * average and the projection, to the [N][embed_dim] condition vectors okenv_flow_act takes.  Inference only.  The rule is written out
+ * in include/okenv_bev.h (ok_bev_*); the convolutions run on the f32-input matrix cores.  The parameter vector is torch's
+ * parameters() order for the reference's encoder (ok_bev_offsets); every weight must be finite. */
+typedef struct okenv_bev_config {
+    int32_t image_size;  /* S: multiple of 8, 16 .. 128                          (the reference: 128)         */
+    int32_t kernel[3];   /* 3 or 5; stride 2 and padding kernel / 2              (5, 3, 3)                    */
+    int32_t channels[3]; /* multiples of 16, 16 .. 128                           (32, 64, 128)                */
+    int32_t embed_dim;   /* E: multiple of 16, 16 .. 512                         (128)                        */
+} okenv_bev_config;
+
+/* LDS bytes of the larger of the two conv kernels for the shape: a pure host function.  A shape is accepted only if this fits 160 KB.
+ * 0 for a NULL config or a shape outside the rule's limits. */
+OKENV_API int64_t okenv_bev_lds_bytes(const okenv_bev_config *config);
+/* The sides (8 or 4) of the output tiles a workgroup of the first and of the second conv kernel owns for the shape: a pure host
+ * function, what the tests name the kernels' paths by.  tiles [2]. */
+OKENV_API int okenv_bev_tiles(const okenv_bev_config *config, int32_t *tiles);
+/* Attaches an encoder to the handle (replaces an earlier one: its parameters are forgotten).  All device memory, the layers'
+ * intermediate outputs included, is allocated here.  OKENV_ERR_INVALID for NULL arguments or a shape outside the limits above. */
+OKENV_API int okenv_bev_create(okenv_t h, const okenv_bev_config *config);
+OKENV_API int okenv_bev_num_params(okenv_t h, int32_t *num_params);
+/* New parameters from a host or device pointer; the kernels' own copy of the conv weights is made behind it on the stream.  No
+ * synchronisation. */
+OKENV_API int okenv_bev_set_params(okenv_t h, const float *params);
+/* The parameters, in the same order, to a host or device pointer; synchronises. */
+OKENV_API int okenv_bev_get_params(okenv_t h, float *params);
+/* out (device, [N][embed_dim]) from frames (device, 4-byte aligned, [N][S][S][4] uint8, frame_bytes = N S S 4 in all) for every
+ * agent, crashed ones included.  Three kernels on the handle's stream, no synchronisation, no allocation: capturable beside
+ * okenv_step, okenv_render_views and okenv_flow_act.  OKENV_ERR_STATE before okenv_bev_create or okenv_bev_set_params;
+ * OKENV_ERR_INVALID for NULL pointers or another frame_bytes. */
+OKENV_API int okenv_bev_encode(okenv_t h, const uint8_t *frames, int64_t frame_bytes, float *out);
+/* okenv_bev_encode's kernels one by one, for measurement: only those named in `stages`, in their order (each reads what the one in
+ * front of it left in the handle's buffers on an earlier call).  Refusals as okenv_bev_encode's. */
+#define OKENV_BEV_STAGE_FRONT 1u /* layers 0 and 1 */
+#define OKENV_BEV_STAGE_BACK 2u  /* layer 2 */
+#define OKENV_BEV_STAGE_HEAD 4u  /* pool and projection */
+OKENV_API int okenv_debug_bev_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, float *out, uint32_t stages);
+/* The same rule on host arrays, no GPU needed: frames [n][S][S][4] -> out [n][embed_dim]. */
+OKENV_API int okenv_bev_encode_host(const okenv_bev_config *config, const float *params, int32_t n, const uint8_t *frames, float *out);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.

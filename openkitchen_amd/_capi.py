@@ -102,6 +102,8 @@ SYMBOLS = [
     "okenv_lidar_act_host", "okenv_debug_lidar_linear",
     "okenv_flow_lds_bytes", "okenv_flow_create", "okenv_flow_num_params", "okenv_flow_set_params", "okenv_flow_get_params",
     "okenv_flow_set_draw_offset", "okenv_flow_act", "okenv_flow_act_host",
+    "okenv_bev_lds_bytes", "okenv_bev_tiles", "okenv_bev_create", "okenv_bev_num_params", "okenv_bev_set_params", "okenv_bev_get_params",
+    "okenv_bev_encode", "okenv_debug_bev_stages", "okenv_bev_encode_host",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -489,6 +491,64 @@ def flow_act_host(cfg, params, cond, crashed=None, draw_index=0):
     return out
 
 
+# the flow driver's image encoder (include/okenv.h)
+BEV_LDS_BUDGET = 160 * 1024
+BEV_STAGE_FRONT, BEV_STAGE_BACK, BEV_STAGE_HEAD = 1, 2, 4
+
+
+class OkenvBevConfig(C.Structure):
+    _fields_ = [("image_size", C.c_int32), ("kernel", C.c_int32 * 3), ("channels", C.c_int32 * 3), ("embed_dim", C.c_int32)]
+
+
+def bev_config(image_size=128, kernel=(5, 3, 3), channels=(32, 64, 128), embed_dim=128):
+    """okenv_bev_config with the reference's shape as defaults (flow_matching_model.py: BEVEncoder)."""
+    return OkenvBevConfig(int(image_size), (C.c_int32 * 3)(*map(int, kernel)), (C.c_int32 * 3)(*map(int, channels)), int(embed_dim))
+
+
+def bev_layout(cfg):
+    """ok_bev_offsets: where every piece of the parameter vector begins, as (name, offset, shape) in order; the names are the
+    state-dict keys of the reference's BEVEncoder.  The last entry's end is the vector's length."""
+    k, c = list(cfg.kernel), list(cfg.channels)
+    pieces = []
+    for l, cin in enumerate([3] + c[:2]):
+        pieces += [("conv.%d.weight" % (2 * l), (c[l], cin, k[l], k[l])), ("conv.%d.bias" % (2 * l), (c[l],))]
+    pieces += [("proj.weight", (cfg.embed_dim, c[2])), ("proj.bias", (cfg.embed_dim,))]
+    out, at = [], 0
+    for name, shape in pieces:
+        out.append((name, at, shape))
+        at += int(np.prod(shape))
+    return out
+
+
+def bev_num_params(cfg):
+    """Floats of the encoder's parameter vector."""
+    name, at, shape = bev_layout(cfg)[-1]
+    return at + int(np.prod(shape))
+
+
+def bev_lds_bytes(cfg):
+    """okenv_bev_lds_bytes: the larger conv kernel's LDS for the shape, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_bev_lds_bytes(C.byref(cfg)))
+
+
+def bev_tiles(cfg):
+    """okenv_bev_tiles: the sides of the output tiles of the two conv kernels, the kernels' paths.  No GPU needed."""
+    out = (C.c_int32 * 2)()
+    check(load().okenv_bev_tiles(C.byref(cfg), out))
+    return int(out[0]), int(out[1])
+
+
+def bev_encode_host(cfg, params, frames):
+    """okenv_bev_encode_host on numpy arrays: frames [n][S][S][4] uint8 -> [n][embed_dim] float32.  No GPU needed."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    params = np.ascontiguousarray(params, np.float32)
+    n = frames.shape[0]
+    assert frames.shape == (n, cfg.image_size, cfg.image_size, 4) and params.size == bev_num_params(cfg)
+    out = np.empty((n, cfg.embed_dim), np.float32)
+    check(load().okenv_bev_encode_host(C.byref(cfg), ptr(params), n, ptr(frames), ptr(out)))
+    return out
+
+
 # guided cost learning (include/okenv.h)
 GCL_POLICY, GCL_VALUE, GCL_COST = 0, 1, 2
 GCL_NETWORKS = {"policy": GCL_POLICY, "value": GCL_VALUE, "cost": GCL_COST}
@@ -860,6 +920,16 @@ def load(build_if_missing=True):
     L.okenv_flow_set_draw_offset.argtypes = [vp, vp]
     L.okenv_flow_act.argtypes = [vp, vp, C.POINTER(OkenvFlowRecord)]
     L.okenv_flow_act_host.argtypes = [C.POINTER(OkenvFlowConfig), vp, i32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.okenv_bev_lds_bytes.argtypes = [C.POINTER(OkenvBevConfig)]
+    L.okenv_bev_lds_bytes.restype = C.c_int64
+    L.okenv_bev_tiles.argtypes = [C.POINTER(OkenvBevConfig), vp]
+    L.okenv_bev_create.argtypes = [vp, C.POINTER(OkenvBevConfig)]
+    L.okenv_bev_num_params.argtypes = [vp, C.POINTER(i32)]
+    L.okenv_bev_set_params.argtypes = [vp, vp]
+    L.okenv_bev_get_params.argtypes = [vp, vp]
+    L.okenv_bev_encode.argtypes = [vp, vp, C.c_int64, vp]
+    L.okenv_debug_bev_stages.argtypes = [vp, vp, C.c_int64, vp, C.c_uint32]
+    L.okenv_bev_encode_host.argtypes = [C.POINTER(OkenvBevConfig), vp, i32, vp, vp]
     _lib = L
     return L
 

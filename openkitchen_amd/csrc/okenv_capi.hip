@@ -33,6 +33,7 @@
 #include "ok_gcl.h"
 #include "ok_lidar.h"
 #include "ok_flow.h"
+#include "ok_bev.h"
 #include "ok_expert.h"
 
 namespace
@@ -579,6 +580,12 @@ struct okenv
     // Flow-matching driver (okenv_flow_create): the trunk's parameter vector in torch's order
     OkDriver                flow_drv;
     okenv_flow_config       flow{};
+    // The flow driver's image encoder (okenv_bev_create): the parameter vector in torch's order; the conv kernels' copy of the weights
+    // and the two layers' outputs that pass through global memory, all allocated at create
+    OkDriver                bev_drv;
+    okenv_bev_config        bev{};
+    float                  *d_bev_pack{nullptr}, *d_bev_act1{nullptr}, *d_bev_act2{nullptr};
+    size_t                  bev_pack_cap{0}, bev_act1_cap{0}, bev_act2_cap{0};
 };
 
 struct okenv_track
@@ -1451,7 +1458,8 @@ const DriverKind kActorDriver{&okenv::actor_drv, "okenv_actor_", "every attached
     kGaussDriver{&okenv::gauss_drv, "okenv_gauss_", "the actor needs its parameters", "the actor needs its parameters", false},
     kGclDriver{&okenv::gcl_drv, "okenv_gcl_", "the policy needs its parameters", "the network needs its parameters", false},
     kLidarDriver{&okenv::lidar_drv, "okenv_lidar_", "the policy needs its parameters", "the policy needs its parameters", true},
-    kFlowDriver{&okenv::flow_drv, "okenv_flow_", "the policy needs its parameters", "the policy needs its parameters", true};
+    kFlowDriver{&okenv::flow_drv, "okenv_flow_", "the policy needs its parameters", "the policy needs its parameters", true},
+    kBevDriver{&okenv::bev_drv, "okenv_bev_", "the encoder needs its parameters", "the encoder needs its parameters", true};
 
 int driverRefuses(okenv *h, const int code, const DriverKind &k, const char *entry, const std::string &why)
 {
@@ -1616,6 +1624,44 @@ int actLaunch(okenv *h, void (*kernel)(Params), const int agents, const unsigned
 {
     const unsigned blocks = static_cast<unsigned>((h->shape.N + agents - 1) / agents);
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, h->stream, p);
+    OK_HIP(h, hipGetLastError());
+    return OKENV_OK;
+}
+
+// okenv_bev_encode behind its OK_QUIESCE: the kernels named in `stages` (OKENV_BEV_STAGE_*), in their order, on the stream
+int bevEncode(okenv *h, const uint8_t *frames, const int64_t frame_bytes, float *out, const unsigned stages)
+{
+    if (const int rc = driverGate(h, kBevDriver, "encode", kGateHandle | kGateCreated | kGateSet, true, 1U))
+        return rc;
+    const ok_bev_shape s = okBevShape(h->bev);
+    if (!frames || !out)
+        return driverRefuses(h, OKENV_ERR_INVALID, kBevDriver, "encode", "NULL argument");
+    if (frame_bytes != static_cast<int64_t>(h->shape.N) * s.S * s.S * 4)
+        return driverRefuses(h, OKENV_ERR_INVALID, kBevDriver, "encode", "frame_bytes is not num_agents x image_size x image_size x 4");
+    if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
+        return driverRefuses(h, OKENV_ERR_INVALID, kBevDriver, "encode", "frames must be 4-byte aligned");
+    OK_HIP(h, hipSetDevice(h->device));
+    const OkBevPlaces pl = okBevPlaces(s);
+    OkBevEncodeParams p{};
+    p.N      = h->shape.N;
+    p.s      = s;
+    p.frames = frames;
+    p.params = h->bev_drv.d;
+    p.pack   = h->d_bev_pack;
+    p.act1   = h->d_bev_act1;
+    p.act2   = h->d_bev_act2;
+    p.out    = out;
+    const auto tiles = [](const int side, const int t) { return static_cast<unsigned>((side + t - 1) / t); };
+    const unsigned N = static_cast<unsigned>(h->shape.N), ta = tiles(ok_bev_side(s, 1), pl.ta), tb = tiles(ok_bev_side(s, 2), pl.tb);
+    const size_t   front = sizeof(float) * static_cast<size_t>(pl.front_end), back = sizeof(float) * static_cast<size_t>(pl.back_end);
+    if ((stages & OKENV_BEV_STAGE_FRONT) != 0U)
+        hipLaunchKernelGGL(pl.ta == 8 ? okBevFrontKernel<8> : okBevFrontKernel<4>, dim3(N * ta * ta), dim3(kBevThreads), front, h->stream, p);
+    OK_HIP(h, hipGetLastError());
+    if ((stages & OKENV_BEV_STAGE_BACK) != 0U)
+        hipLaunchKernelGGL(pl.tb == 8 ? okBevBackKernel<8> : okBevBackKernel<4>, dim3(N * tb * tb), dim3(kBevThreads), back, h->stream, p);
+    OK_HIP(h, hipGetLastError());
+    if ((stages & OKENV_BEV_STAGE_HEAD) != 0U)
+        hipLaunchKernelGGL(okBevHeadKernel, dim3(N), dim3(kBevThreads), 0, h->stream, p);
     OK_HIP(h, hipGetLastError());
     return OKENV_OK;
 }
@@ -4434,6 +4480,111 @@ extern "C"
         if (!params || n < 0 || !cond)
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_flow_act_host: bad argument");
         okFlowActHost(*config, params, n, cond, crashed, draw_index, throttle, steer, x0, x, alive);
+        return OKENV_OK;
+    }
+
+    // ---- The flow driver's image encoder (ok_bev.h) ------------------------------------------------------------------------------
+
+    int64_t okenv_bev_lds_bytes(const okenv_bev_config *config)
+    {
+        return config != nullptr ? static_cast<int64_t>(okBevLdsBytes(okBevShape(*config))) : 0;
+    }
+
+    int okenv_bev_tiles(const okenv_bev_config *config, int32_t *tiles)
+    {
+        if (const char *why = okBevCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_bev_tiles: ") + why);
+        if (!tiles)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_bev_tiles: bad argument");
+        const OkBevPlaces pl = okBevPlaces(okBevShape(*config));
+        tiles[0] = pl.ta;
+        tiles[1] = pl.tb;
+        return OKENV_OK;
+    }
+
+    int okenv_bev_create(okenv_t h, const okenv_bev_config *config)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kBevDriver, "create", kGateHandle))
+            return rc;
+        if (const char *why = okBevCheckConfig(config))
+            return driverRefuses(h, OKENV_ERR_INVALID, kBevDriver, "create", why);
+        const ok_bev_shape s = okBevShape(*config);
+        if (const int rc = driverCreateFlat(h, kBevDriver, static_cast<size_t>(ok_bev_offsets(s).total), kernelOf(okBevFrontKernel<8>)))
+            return rc;
+        h->bev_drv.ok = false; // (until the kernels' own buffers stand)
+        if (const int rc = raiseLdsLimit(h, {kernelOf(okBevFrontKernel<4>), kernelOf(okBevBackKernel<8>), kernelOf(okBevBackKernel<4>)}))
+            return rc;
+        const size_t N = static_cast<size_t>(h->shape.N), side1 = static_cast<size_t>(ok_bev_side(s, 1)), side2 = static_cast<size_t>(ok_bev_side(s, 2));
+        const size_t pack = static_cast<size_t>(okBevPlaces(s).pack_total), act1 = N * side1 * side1 * s.c[1], act2 = N * side2 * side2 * s.c[2];
+        if (pack > h->bev_pack_cap || act1 > h->bev_act1_cap || act2 > h->bev_act2_cap)
+        {
+            const size_t np = std::max(pack, h->bev_pack_cap), n1 = std::max(act1, h->bev_act1_cap), n2 = std::max(act2, h->bev_act2_cap);
+            h->bev_pack_cap = h->bev_act1_cap = h->bev_act2_cap = 0; // (a failed allocation leaves none of them)
+            if (const int rc = regrow(h, {fresh(h->d_bev_pack, np), fresh(h->d_bev_act1, n1), fresh(h->d_bev_act2, n2)}))
+                return rc;
+            h->bev_pack_cap = np, h->bev_act1_cap = n1, h->bev_act2_cap = n2;
+        }
+        h->bev        = *config;
+        h->bev_drv.ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_bev_num_params(okenv_t h, int32_t *num_params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kBevDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
+            return rc;
+        *num_params = ok_bev_offsets(okBevShape(h->bev)).total;
+        return OKENV_OK;
+    }
+
+    int okenv_bev_set_params(okenv_t h, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kBevDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
+            return rc;
+        const ok_bev_shape s = okBevShape(h->bev);
+        if (const int rc = driverSet(h, kBevDriver, {vectorOf(h->bev_drv.d, params, ok_bev_offsets(s).total)}))
+            return rc;
+        // the conv kernels' copy of the weights, behind the upload on the stream
+        OkBevPackParams p{};
+        p.s      = s;
+        p.params = h->bev_drv.d;
+        p.pack   = h->d_bev_pack;
+        const unsigned blocks = static_cast<unsigned>((okBevPlaces(s).pack_total + kBevThreads - 1) / kBevThreads);
+        hipLaunchKernelGGL(okBevPackKernel, dim3(blocks), dim3(kBevThreads), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_bev_get_params(okenv_t h, float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kBevDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
+            return rc;
+        return driverGet(h, {vectorOf(h->bev_drv.d, params, ok_bev_offsets(okBevShape(h->bev)).total)});
+    }
+
+    int okenv_bev_encode(okenv_t h, const uint8_t *frames, int64_t frame_bytes, float *out)
+    {
+        OK_QUIESCE(h);
+        return bevEncode(h, frames, frame_bytes, out, OKENV_BEV_STAGE_FRONT | OKENV_BEV_STAGE_BACK | OKENV_BEV_STAGE_HEAD);
+    }
+
+    int okenv_debug_bev_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, float *out, uint32_t stages)
+    {
+        OK_QUIESCE(h);
+        return bevEncode(h, frames, frame_bytes, out, stages);
+    }
+
+    int okenv_bev_encode_host(const okenv_bev_config *config, const float *params, int32_t n, const uint8_t *frames, float *out)
+    {
+        if (const char *why = okBevCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_bev_encode_host: ") + why);
+        if (!params || n < 0 || !frames || !out)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_bev_encode_host: bad argument");
+        okBevEncodeHost(*config, params, n, frames, out);
         return OKENV_OK;
     }
 

@@ -480,7 +480,7 @@ class BatchedEnvironment:
         leaves a network as it is.  Enqueued on the handle's stream, no synchronisation for device tensors."""
         self._set_params("okenv_actor_set_params", (policy, value), self.actor_num_params())
 
-    # (one implementation for the families that attach a network to the handle -- actor, ddpg, gauss, gcl, lidar, flow: `symbol` is
+    # (one implementation for the families that attach a network to the handle -- actor, ddpg, gauss, gcl, lidar, flow, bev: `symbol` is
     # the family's entry, `lead` what it takes between the handle and the arguments named here)
     def _count(self, symbol, *lead, outs=1):
         """The floats an okenv_*_num_params entry reports: an int, or a tuple of `outs` of them."""
@@ -876,6 +876,39 @@ class BatchedEnvironment:
         "x", "action" [N,2] float32 and "alive" [N] uint8, each optional."""
         self._act("okenv_flow_act", capi.OkenvFlowRecord, record, record and {"x0": self.N * 8, "x": self.N * 8, "action": self.N * 8, "alive": self.N},
                   capi.ptr(cond))
+
+    # ---- the flow driver's image encoder (include/okenv.h, DESIGN.md section 25) ---------------------------------------------
+    def bev_create(self, config=None, **members):
+        """Attaches the flow driver's image encoder (the reference's BEVEncoder) to the handle; config: a capi.bev_config(...), or
+        its members by name (the reference's shape by default).  Returns the floats of its parameter vector."""
+        if config is None:
+            config = capi.bev_config(**members)
+        capi.check(self._L.okenv_bev_create(self._h, C.byref(config)), self._h)
+        self.bev_config = config
+        return self.bev_num_params()
+
+    def bev_num_params(self):
+        return self._count("okenv_bev_num_params")
+
+    def bev_set_params(self, params):
+        """New parameters (the encoder's, in torch's parameters() order: capi.bev_layout) from a float32 numpy array or a device
+        tensor.  Enqueued on the handle's stream; the call waits for the stream when it was handed a numpy array (which may be a
+        temporary), not for a device tensor."""
+        self._set_params("okenv_bev_set_params", (params,), (self.bev_num_params(),))
+
+    def bev_get_params(self, out=None):
+        """The parameter vector as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
+        return self._get_state("okenv_bev_get_params", {"params": self.bev_num_params()}, None if out is None else {"params": out})["params"]
+
+    def bev_encode(self, frames, out, stages=None):
+        """The embedding of every agent's frame, enqueued on the handle's stream without a synchronisation.  frames: a device tensor
+        / address of [N, S, S, 4] uint8; out: one of [N, embed_dim] float32.  stages: None, or a mask of capi.BEV_STAGE_* -- only those
+        kernels (okenv_debug_bev_stages, for measurement)."""
+        S = self.bev_config.image_size
+        if stages is None:
+            capi.check(self._L.okenv_bev_encode(self._h, capi.ptr(frames), self.N * S * S * 4, capi.ptr(out)), self._h)
+        else:
+            capi.check(self._L.okenv_debug_bev_stages(self._h, capi.ptr(frames), self.N * S * S * 4, capi.ptr(out), int(stages)), self._h)
 
     # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) -------------------------------------------------------
     def gcl_create(self, **config):

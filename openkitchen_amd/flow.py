@@ -2,8 +2,8 @@
 ActionFlowTrunk, ConditionalFlowMatchingPolicy) as PyTorch modules for training, the hand-over of the trunk's weights to the device
 sampler (okenv_flow_*) and the driving loop of main_flow_control.cpp:157-170 for N agents.
 
-Training and the conv encoder stay in PyTorch; the encoder runs once per environment step.  What runs as a HIP kernel is the part
-that is a loop in the reference: the 32 evaluations of the trunk per action.
+Training stays in PyTorch.  The 32 evaluations of the trunk per action run as one HIP kernel; the conv encoder, once per environment
+step, runs in PyTorch or, handed over like the trunk, as the device encoder (okenv_bev_*, DESIGN.md section 25: drive(encoder="device")).
 """
 import torch
 from torch import nn
@@ -15,6 +15,8 @@ from .rollout import _Chunk, _run_episode
 ACTION_LO, ACTION_HI = (0.0, -10.0), (100.0, 10.0)  # flow_matching_model.py: ActionNormalizer
 TRUNK_KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias")
 TRUNK_PREFIX = "action_flow_trunk."
+ENCODER_KEYS = ("conv.0.weight", "conv.0.bias", "conv.2.weight", "conv.2.bias", "conv.4.weight", "conv.4.bias", "proj.weight", "proj.bias")
+ENCODER_PREFIX = "bev_encoder."
 
 
 class BEVEncoder(nn.Module):
@@ -80,6 +82,29 @@ def flow_params_from_state_dict(sd, dtype=torch.float32):
     return torch.cat(pieces).contiguous()
 
 
+def _encoder_tensors(sd):
+    """The encoder's eight tensors from its own state dict or from the whole policy's."""
+    prefix = ENCODER_PREFIX if ENCODER_PREFIX + ENCODER_KEYS[0] in sd else ""
+    return [sd[prefix + k] for k in ENCODER_KEYS]
+
+
+def bev_config_from_state_dict(sd, image_size=128):
+    """The capi.bev_config of the shape a state dict of the encoder (or of the whole policy) has, for frames of image_size."""
+    t = _encoder_tensors(sd)
+    return capi.bev_config(image_size=image_size, kernel=[w.shape[2] for w in t[0:6:2]], channels=[w.shape[0] for w in t[0:6:2]],
+                           embed_dim=t[6].shape[0])
+
+
+def bev_params_from_state_dict(sd, dtype=torch.float32):
+    """The flat parameter vector of okenv_bev_set_params: the pieces of capi.bev_layout in order."""
+    cfg = bev_config_from_state_dict(sd)
+    pieces = []
+    for t, (name, _, shape) in zip(_encoder_tensors(sd), capi.bev_layout(cfg)):
+        assert tuple(t.shape) == tuple(shape), "%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape))
+        pieces.append(t.detach().to(dtype=dtype).reshape(-1))
+    return torch.cat(pieces).contiguous()
+
+
 def frames_to_input(frames, image_size=None):
     """venv.camera()'s RGBA frames [N, H, W, 4] uint8 -> the encoder's input [N, 3, S, S] float in 0 .. 1 (main_flow_control.cpp:40-66:
     drop alpha, to float, NCHW, bilinear resize with align_corners=False -- only when the size differs).  The camera's row 0 is already
@@ -137,38 +162,62 @@ def demonstration_rows(demonstrations):
     return frames.reshape((-1,) + tuple(frames.shape[2:]))[alive], demonstrations["actions"].reshape(-1, 2)[alive]
 
 
-def drive(venv, model, steps, graph_chunk=0, image_size=None):
-    """The loop of main_flow_control.cpp:157-170 for every agent: `step`, the agents' frames (venv.camera()), the encoder in PyTorch
-    and the device sampler from its output, `steps` times; the environment's auto-reset stands in for resetAgent (without it the loop
-    ends once nobody is alive).  The trunk is the one given to venv.enable_flow_policy, the encoder is model.bev_encoder.
+def drive(venv, model, steps, graph_chunk=0, image_size=None, encoder="torch"):
+    """The loop of main_flow_control.cpp:157-170 for every agent: `step`, the agents' frames (venv.camera()), the encoder and the
+    device sampler from its output, `steps` times; the environment's auto-reset stands in for resetAgent (without it the loop ends
+    once nobody is alive).  The trunk is the one given to venv.enable_flow_policy.  encoder="torch": model.bev_encoder in PyTorch
+    behind frames_to_input; encoder="device": the one given to venv.enable_bev_encoder, no PyTorch op in the iteration (model is not
+    used and may be None) -- the camera must render at the encoder's image_size, the device path does not resize.
     graph_chunk = K > 0 replays a HIP graph of K iterations.  Returns the steps taken."""
+    assert encoder in ("torch", "device"), 'encoder is "torch" or "device"'
     assert getattr(venv, "flow_config", None) is not None, "call venv.enable_flow_policy(config, params) first"
     assert hasattr(venv, "camera_shape") and len(venv.camera_shape) == 4, 'call venv.enable_camera(..., fmt="rgba") first'
-    encoder = model.bev_encoder
     frame = torch.empty(venv.camera_shape, dtype=torch.uint8, device=venv.device)
+    if encoder == "device":
+        assert getattr(venv, "bev_config", None) is not None, "call venv.enable_bev_encoder(config, params) first"
+        S = venv.bev_config.image_size
+        if tuple(venv.camera_shape[1:3]) != (S, S):
+            raise ValueError('drive(encoder="device") needs the camera at the encoder\'s size: venv.enable_camera(width=%d, height=%d, fmt="rgba"); '
+                             "it renders %dx%d (the device encoder does not resize; encoder=\"torch\" does)" % (S, S, venv.camera_shape[2], venv.camera_shape[1]))
+        assert venv.bev_config.embed_dim == venv.flow_config.cond_dim, "the encoder's embed_dim is not the trunk's cond_dim"
+        cond = torch.empty((venv.num_envs, venv.bev_config.embed_dim), dtype=torch.float32, device=venv.device)
 
-    def iteration(_):
-        venv.step()
-        venv.camera(out=frame)
-        with torch.no_grad():
-            cond = encoder(frames_to_input(frame, image_size))
-        venv.flow_act(cond.contiguous())
+        def iteration(_):
+            venv.step()
+            venv.camera(out=frame)
+            venv.bev_encode(frame, out=cond)
+            venv.flow_act(cond)
 
-    def build():
-        venv.camera(out=frame)
-        with torch.no_grad():  # the convolutions choose their kernels on the first call of a shape: not inside a capture
-            encoder(frames_to_input(frame, image_size))
-        return iteration, (frame, encoder)
+        def build():
+            return iteration, (frame, cond)
+
+        key = ("device",)
+    else:
+        module = model.bev_encoder
+
+        def iteration(_):
+            venv.step()
+            venv.camera(out=frame)
+            with torch.no_grad():
+                cond = module(frames_to_input(frame, image_size))
+            venv.flow_act(cond.contiguous())
+
+        def build():
+            venv.camera(out=frame)
+            with torch.no_grad():  # the convolutions choose their kernels on the first call of a shape: not inside a capture
+                module(frames_to_input(frame, image_size))
+            return iteration, (frame, module)
+
+        key = (id(module), image_size)
 
     K = int(graph_chunk)
     chunk = None
     if K > 0:
-        chunk = _Chunk(K=K, graphs=venv._flow_graphs, key=(K, id(encoder), image_size), set_draw_offset=venv.env.flow_set_draw_offset, build=build,
-                       after_replay=None)
+        chunk = _Chunk(K=K, graphs=venv._flow_graphs, key=(K,) + key, set_draw_offset=venv.env.flow_set_draw_offset, build=build, after_replay=None)
     _, taken = _run_episode(venv, iteration, int(steps), 8, chunk)
     return taken
 
 
 __all__ = ["BEVEncoder", "ActionFlowTrunk", "ConditionalFlowMatchingPolicy", "flow_config_from_state_dict", "flow_params_from_state_dict",
-           "frames_to_input", "sample", "train", "demonstration_rows", "drive", "normalize_controls", "denormalize_controls", "ACTION_LO",
+           "bev_config_from_state_dict", "bev_params_from_state_dict", "frames_to_input", "sample", "train", "demonstration_rows", "drive", "normalize_controls", "denormalize_controls", "ACTION_LO",
            "ACTION_HI"]

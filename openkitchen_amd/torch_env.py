@@ -520,7 +520,7 @@ class VectorEnvironment:
 
     # ---- lidar transformer driver (include/okenv.h) ----------------------------------------------------------
     def _attach_flat(self, family, config, params):
-        """enable_lidar_policy's and enable_flow_policy's hand-over: env.<family>_create(config), then the flat vector `params` (a tensor
+        """enable_lidar_policy's, enable_flow_policy's and enable_bev_encoder's hand-over: env.<family>_create(config), then the flat vector `params` (a tensor
         is brought to this device as float32).  Returns what was handed over, for the caller to keep until the next hand-over."""
         getattr(self.env, family + "_create")(config)
         if torch.is_tensor(params):
@@ -566,6 +566,32 @@ class VectorEnvironment:
                 or tuple(cond.shape) != (self.num_envs, self.flow_config.cond_dim)):
             raise ValueError("flow_act(cond) needs a contiguous float32 tensor of shape (%d, %d) on %s" % (self.num_envs, self.flow_config.cond_dim, self.device))
         self.env.flow_act(cond, record)
+
+    # ---- the flow driver's image encoder (include/okenv.h) --------------------------------------------------
+    def enable_bev_encoder(self, config, params):
+        """Attaches the reference's image encoder (FlowMatching: BEVEncoder) as a device driver.  config: a capi.bev_config(...) or a
+        dict of its members; params: the flat vector flow.bev_params_from_state_dict makes, a float32 numpy array or a tensor.  Call
+        it again with new params after training on."""
+        if isinstance(config, dict):
+            config = capi.bev_config(**config)
+        self._bev_flat = self._attach_flat("bev", config, params)  # alive until the next hand-over: a tensor's copy is asynchronous
+        self.bev_config = config
+        self._flow_graphs = {}  # a captured launch carries the old shape and vector
+
+    def bev_encode(self, frames, out=None):
+        """The embedding [N, embed_dim] float32 of every agent's frame: `frames` a contiguous uint8 tensor [N, S, S, 4] on this device
+        (camera()'s, rendered at the encoder's image_size).  Three kernels on the environment's stream, no synchronisation, usable
+        inside capture(body).  `out`: a contiguous float32 tensor to fill in place; otherwise a new tensor."""
+        S, E = self.bev_config.image_size, self.bev_config.embed_dim
+        if (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.device != self.device
+                or tuple(frames.shape) != (self.num_envs, S, S, 4)):
+            raise ValueError("bev_encode(frames) needs a contiguous uint8 tensor of shape (%d, %d, %d, 4) on %s" % (self.num_envs, S, S, self.device))
+        if out is None:
+            out = torch.empty((self.num_envs, E), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (self.num_envs, E) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("bev_encode(out=...) needs a contiguous float32 tensor of shape (%d, %d) on %s" % (self.num_envs, E, self.device))
+        self.env.bev_encode(frames, out)
+        return out
 
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
