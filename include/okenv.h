@@ -1086,6 +1086,59 @@ OKENV_API int okenv_debug_bev_stages(okenv_t h, const uint8_t *frames, int64_t f
 /* The same rule on host arrays, no GPU needed: frames [n][S][S][4] -> out [n][embed_dim]. */
 OKENV_API int okenv_bev_encode_host(const okenv_bev_config *config, const float *params, int32_t n, const uint8_t *frames, float *out);
 
+/* ---- Behavioural-cloning image policy ----------------------------------------------------------------------
+ * BehavioralCloning's PolicyCNN (env_train_bc.py) driven as main.cpp drives it, for every agent of the handle: from the camera's RGBA8
+ * frames (okenv_render_views, rendered at image_size x image_size) the /255 normalisation, three valid convolutions with ReLU, the
+ * flatten, a hidden layer with ReLU, one output and its tanh, to throttle_delta = throttle and steering_delta = steer_scale * output.
+ * Inference only.  The rule is written out in include/okenv_cnn.h (ok_cnn_*); all matrix work runs on the f32-input matrix cores.  The
+ * parameter vector is torch's parameters() order for the reference module (ok_cnn_offsets); every weight must be finite. */
+typedef struct okenv_cnn_config {
+    int32_t image_size;  /* S: 16 .. 128                                         (the reference: 96)          */
+    int32_t kernel[3];   /* 1 .. 8; no padding                                   (8, 4, 3)                    */
+    int32_t stride[3];   /* 1 .. 4, at most the kernel                           (4, 2, 1)                    */
+    int32_t channels[3]; /* multiples of 16, 16 .. 128                           (32, 64, 64)                 */
+    int32_t hidden;      /* H: multiple of 16, 16 .. 512                         (256)                        */
+    float   throttle;    /* the constant throttle_delta; finite                  (100)                        */
+    float   steer_scale; /* steering_delta per unit of the output; finite        (10)                         */
+} okenv_cnn_config;
+
+/* What an act can leave behind for the caller, device pointers, each may be NULL */
+typedef struct okenv_cnn_record {
+    float   *out;    /* [N]    the tanh output                         */
+    float   *action; /* [N][2] throttle_delta, steering_delta          */
+    uint8_t *alive;  /* [N]    1 where the agent was not crashed       */
+} okenv_cnn_record;
+
+/* LDS bytes of the larger of the two act kernels for the shape: a pure host function.  A shape is accepted only if this fits 160 KB.
+ * 0 for a NULL config or a shape outside the rule's limits. */
+OKENV_API int64_t okenv_cnn_lds_bytes(const okenv_cnn_config *config);
+/* What names the kernels' path for the shape: a pure host function.  plan [2]: the tiles of 16 hidden units a wave of the head kernel
+ * owns (1 .. 4: the head kernel's four forms), and what sizes the conv kernel's first LDS region (0: the frame, 1: layer 1's output). */
+OKENV_API int okenv_cnn_plan(const okenv_cnn_config *config, int32_t *plan);
+/* Attaches a policy to the handle (replaces an earlier one: its parameters are forgotten).  All device memory, the features between
+ * the two kernels included, is allocated here.  OKENV_ERR_INVALID for NULL arguments, a shape outside the limits above or a
+ * non-finite throttle or steer_scale. */
+OKENV_API int okenv_cnn_create(okenv_t h, const okenv_cnn_config *config);
+OKENV_API int okenv_cnn_num_params(okenv_t h, int32_t *num_params);
+/* New parameters from a host or device pointer; the kernels' own copy of the weights is made behind it on the stream.  No
+ * synchronisation. */
+OKENV_API int okenv_cnn_set_params(okenv_t h, const float *params);
+/* The parameters, in the same order, to a host or device pointer; synchronises. */
+OKENV_API int okenv_cnn_get_params(okenv_t h, float *params);
+/* Acts for every agent, crashed ones included, from frames (device, 4-byte aligned, [N][S][S][4] uint8, frame_bytes = N S S 4 in
+ * all): writes OKENV_F_THROTTLE, OKENV_F_STEER and the record (rec may be NULL).  Two kernels on the handle's stream, no
+ * synchronisation, no allocation: capturable beside okenv_step and okenv_render_views.  OKENV_ERR_STATE before okenv_cnn_create or
+ * okenv_cnn_set_params; OKENV_ERR_INVALID for NULL frames or another frame_bytes. */
+OKENV_API int okenv_cnn_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_cnn_record *rec);
+/* okenv_cnn_act's kernels one by one, for measurement: only those named in `stages`, in their order (the head reads what the conv
+ * kernel left in the handle's buffer on an earlier call).  Refusals as okenv_cnn_act's. */
+#define OKENV_CNN_STAGE_CONV 1u /* layers 0, 1 and 2 */
+#define OKENV_CNN_STAGE_HEAD 2u /* hidden layer, output and action */
+OKENV_API int okenv_debug_cnn_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_cnn_record *rec, uint32_t stages);
+/* The same rule on host arrays, no GPU needed: frames [n][S][S][4]; crashed [n] or NULL; every output [n] and may be NULL. */
+OKENV_API int okenv_cnn_act_host(const okenv_cnn_config *config, const float *params, int32_t n, const uint8_t *frames, const uint8_t *crashed,
+                                 float *throttle, float *steer, float *out, uint8_t *alive);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.

@@ -104,6 +104,8 @@ SYMBOLS = [
     "okenv_flow_set_draw_offset", "okenv_flow_act", "okenv_flow_act_host",
     "okenv_bev_lds_bytes", "okenv_bev_tiles", "okenv_bev_create", "okenv_bev_num_params", "okenv_bev_set_params", "okenv_bev_get_params",
     "okenv_bev_encode", "okenv_debug_bev_stages", "okenv_bev_encode_host",
+    "okenv_cnn_lds_bytes", "okenv_cnn_plan", "okenv_cnn_create", "okenv_cnn_num_params", "okenv_cnn_set_params", "okenv_cnn_get_params",
+    "okenv_cnn_act", "okenv_debug_cnn_stages", "okenv_cnn_act_host",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -549,8 +551,88 @@ def bev_encode_host(cfg, params, frames):
     return out
 
 
+# behavioural-cloning image policy (include/okenv.h)
+CNN_LDS_BUDGET = 160 * 1024
+CNN_STAGE_CONV, CNN_STAGE_HEAD = 1, 2
+CNN_AGENTS = 16  # agents per workgroup of the head kernel (ok_cnn.h: kCnnAgents)
+
+
+class OkenvCnnConfig(C.Structure):
+    _fields_ = [("image_size", C.c_int32), ("kernel", C.c_int32 * 3), ("stride", C.c_int32 * 3), ("channels", C.c_int32 * 3),
+                ("hidden", C.c_int32), ("throttle", C.c_float), ("steer_scale", C.c_float)]
+
+
+class OkenvCnnRecord(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("action", C.c_void_p), ("alive", C.c_void_p)]
+
+
+def cnn_config(image_size=96, kernel=(8, 4, 3), stride=(4, 2, 1), channels=(32, 64, 64), hidden=256, throttle=100.0, steer_scale=10.0):
+    """okenv_cnn_config with the reference's shape and controls as defaults (BehavioralCloning: env_train_bc.py PolicyCNN, main.cpp)."""
+    return OkenvCnnConfig(int(image_size), (C.c_int32 * 3)(*map(int, kernel)), (C.c_int32 * 3)(*map(int, stride)),
+                          (C.c_int32 * 3)(*map(int, channels)), int(hidden), float(throttle), float(steer_scale))
+
+
+def cnn_sides(cfg):
+    """ok_cnn_side: the sides of the three convolutions' outputs (a valid convolution floors; 0 where the kernel does not fit)."""
+    side, out = cfg.image_size, []
+    for k, s in zip(cfg.kernel, cfg.stride):
+        side = 0 if side < k or s < 1 else (side - k) // s + 1
+        out.append(side)
+    return tuple(out)
+
+
+def cnn_layout(cfg):
+    """ok_cnn_offsets: where every piece of the parameter vector begins, as (name, offset, shape) in order; the names are the
+    state-dict keys of the reference's PolicyCNN.  The last entry's end is the vector's length."""
+    k, c, H = list(cfg.kernel), list(cfg.channels), cfg.hidden
+    F = c[2] * cnn_sides(cfg)[2] ** 2
+    pieces = []
+    for l, cin in enumerate([3] + c[:2]):
+        pieces += [("encoder.%d.weight" % (2 * l), (c[l], cin, k[l], k[l])), ("encoder.%d.bias" % (2 * l), (c[l],))]
+    pieces += [("steering_head.0.weight", (H, F)), ("steering_head.0.bias", (H,)), ("steering_head.2.weight", (1, H)),
+               ("steering_head.2.bias", (1,))]
+    out, at = [], 0
+    for name, shape in pieces:
+        out.append((name, at, shape))
+        at += int(np.prod(shape))
+    return out
+
+
+def cnn_num_params(cfg):
+    """Floats of the policy's parameter vector."""
+    name, at, shape = cnn_layout(cfg)[-1]
+    return at + int(np.prod(shape))
+
+
+def cnn_lds_bytes(cfg):
+    """okenv_cnn_lds_bytes: the larger act kernel's LDS for the shape, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_cnn_lds_bytes(C.byref(cfg)))
+
+
+def cnn_plan(cfg):
+    """okenv_cnn_plan: (tiles of 16 hidden units per wave of the head kernel, what sizes the conv kernel's first LDS region), the
+    kernels' paths.  No GPU needed."""
+    out = (C.c_int32 * 2)()
+    check(load().okenv_cnn_plan(C.byref(cfg), out))
+    return int(out[0]), int(out[1])
+
+
+def cnn_act_host(cfg, params, frames, crashed=None):
+    """okenv_cnn_act_host on numpy arrays: frames [n][S][S][4] uint8 -> dict(throttle, steer, out [n] float32, alive [n]).  No GPU
+    needed."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    params = np.ascontiguousarray(params, np.float32)
+    n = frames.shape[0]
+    assert frames.shape == (n, cfg.image_size, cfg.image_size, 4) and params.size == cnn_num_params(cfg)
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, np.uint8)
+    out = dict(throttle=np.empty(n, np.float32), steer=np.empty(n, np.float32), out=np.empty(n, np.float32), alive=np.empty(n, np.uint8))
+    check(load().okenv_cnn_act_host(C.byref(cfg), ptr(params), n, ptr(frames), ptr(crashed), ptr(out["throttle"]), ptr(out["steer"]),
+                                    ptr(out["out"]), ptr(out["alive"])))
+    return out
+
+
 # guided cost learning (include/okenv.h)
-GCL_POLICY, GCL_VALUE, GCL_COST = 0, 1, 2
+GCL_POLICY,GCL_VALUE, GCL_COST = 0, 1, 2
 GCL_NETWORKS = {"policy": GCL_POLICY, "value": GCL_VALUE, "cost": GCL_COST}
 GCL_KERNELS = ("grad", "step")
 GCL_LDS_BUDGET = 160 * 1024
@@ -930,6 +1012,16 @@ def load(build_if_missing=True):
     L.okenv_bev_encode.argtypes = [vp, vp, C.c_int64, vp]
     L.okenv_debug_bev_stages.argtypes = [vp, vp, C.c_int64, vp, C.c_uint32]
     L.okenv_bev_encode_host.argtypes = [C.POINTER(OkenvBevConfig), vp, i32, vp, vp]
+    L.okenv_cnn_lds_bytes.argtypes = [C.POINTER(OkenvCnnConfig)]
+    L.okenv_cnn_lds_bytes.restype = C.c_int64
+    L.okenv_cnn_plan.argtypes = [C.POINTER(OkenvCnnConfig), vp]
+    L.okenv_cnn_create.argtypes = [vp, C.POINTER(OkenvCnnConfig)]
+    L.okenv_cnn_num_params.argtypes = [vp, C.POINTER(i32)]
+    L.okenv_cnn_set_params.argtypes = [vp, vp]
+    L.okenv_cnn_get_params.argtypes = [vp, vp]
+    L.okenv_cnn_act.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvCnnRecord)]
+    L.okenv_debug_cnn_stages.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvCnnRecord), C.c_uint32]
+    L.okenv_cnn_act_host.argtypes = [C.POINTER(OkenvCnnConfig), vp, i32, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

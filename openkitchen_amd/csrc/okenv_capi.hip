@@ -34,6 +34,7 @@
 #include "ok_lidar.h"
 #include "ok_flow.h"
 #include "ok_bev.h"
+#include "ok_cnn.h"
 #include "ok_expert.h"
 
 namespace
@@ -586,6 +587,12 @@ struct okenv
     okenv_bev_config        bev{};
     float                  *d_bev_pack{nullptr}, *d_bev_act1{nullptr}, *d_bev_act2{nullptr};
     size_t                  bev_pack_cap{0}, bev_act1_cap{0}, bev_act2_cap{0};
+    // Behavioural-cloning image policy (okenv_cnn_create): the parameter vector in torch's order; the kernels' copy of the weights and
+    // the features that pass from the conv kernel to the head, both allocated at create
+    OkDriver                cnn_drv;
+    okenv_cnn_config        cnn{};
+    float                  *d_cnn_pack{nullptr}, *d_cnn_feat{nullptr};
+    size_t                  cnn_pack_cap{0}, cnn_feat_cap{0};
 };
 
 struct okenv_track
@@ -1459,7 +1466,8 @@ const DriverKind kActorDriver{&okenv::actor_drv, "okenv_actor_", "every attached
     kGclDriver{&okenv::gcl_drv, "okenv_gcl_", "the policy needs its parameters", "the network needs its parameters", false},
     kLidarDriver{&okenv::lidar_drv, "okenv_lidar_", "the policy needs its parameters", "the policy needs its parameters", true},
     kFlowDriver{&okenv::flow_drv, "okenv_flow_", "the policy needs its parameters", "the policy needs its parameters", true},
-    kBevDriver{&okenv::bev_drv, "okenv_bev_", "the encoder needs its parameters", "the encoder needs its parameters", true};
+    kBevDriver{&okenv::bev_drv, "okenv_bev_", "the encoder needs its parameters", "the encoder needs its parameters", true},
+    kCnnDriver{&okenv::cnn_drv, "okenv_cnn_", "the policy needs its parameters", "the policy needs its parameters", true};
 
 int driverRefuses(okenv *h, const int code, const DriverKind &k, const char *entry, const std::string &why)
 {
@@ -1663,6 +1671,47 @@ int bevEncode(okenv *h, const uint8_t *frames, const int64_t frame_bytes, float 
     if ((stages & OKENV_BEV_STAGE_HEAD) != 0U)
         hipLaunchKernelGGL(okBevHeadKernel, dim3(N), dim3(kBevThreads), 0, h->stream, p);
     OK_HIP(h, hipGetLastError());
+    return OKENV_OK;
+}
+
+// okenv_cnn_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_CNN_STAGE_*), in their order, on the stream
+int cnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_cnn_record *rec, const unsigned stages)
+{
+    const char *missing = nullptr;
+    if (h != nullptr && h->cnn_drv.ok)
+    {
+        const int S = h->cnn.image_size;
+        if (!frames)
+            missing = "NULL argument";
+        else if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
+            missing = "frame_bytes is not num_agents x image_size x image_size x 4";
+        else if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
+            missing = "frames must be 4-byte aligned";
+    }
+    if (const int rc = actBegin(h, kCnnDriver, 1U, missing))
+        return rc;
+    const ok_cnn_shape s  = okCnnShape(h->cnn);
+    const OkCnnPlaces  pl = okCnnPlaces(s);
+    OkCnnActParams     p{};
+    p.st          = h->st;
+    p.N           = h->shape.N;
+    p.s           = s;
+    p.frames      = frames;
+    p.params      = h->cnn_drv.d;
+    p.pack        = h->d_cnn_pack;
+    p.feat        = h->d_cnn_feat;
+    p.throttle    = h->cnn.throttle;
+    p.steer_scale = h->cnn.steer_scale;
+    if (rec != nullptr)
+        p.rec = *rec;
+    if ((stages & OKENV_CNN_STAGE_CONV) != 0U)
+        if (const int rc = actLaunch(h, okCnnConvKernel, 1, kCnnThreads, sizeof(float) * static_cast<size_t>(pl.conv_end), p))
+            return rc;
+    if ((stages & OKENV_CNN_STAGE_HEAD) != 0U)
+    {
+        void (*const heads[kCnnMaxColTiles])(OkCnnActParams) = {okCnnHeadKernel<1>, okCnnHeadKernel<2>, okCnnHeadKernel<3>, okCnnHeadKernel<4>};
+        return actLaunch(h, heads[pl.ct - 1], kCnnAgents, kCnnThreads, sizeof(float) * static_cast<size_t>(pl.head_end), p);
+    }
     return OKENV_OK;
 }
 
@@ -4480,6 +4529,108 @@ extern "C"
         if (!params || n < 0 || !cond)
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_flow_act_host: bad argument");
         okFlowActHost(*config, params, n, cond, crashed, draw_index, throttle, steer, x0, x, alive);
+        return OKENV_OK;
+    }
+
+    // ---- Behavioural-cloning image policy (ok_cnn.h) -------------------------------------------------------------------------------
+
+    int64_t okenv_cnn_lds_bytes(const okenv_cnn_config *config)
+    {
+        return config != nullptr ? static_cast<int64_t>(okCnnLdsBytes(okCnnShape(*config))) : 0;
+    }
+
+    int okenv_cnn_plan(const okenv_cnn_config *config, int32_t *plan)
+    {
+        if (const char *why = okCnnCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_cnn_plan: ") + why);
+        if (!plan)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_cnn_plan: bad argument");
+        const OkCnnPlaces pl = okCnnPlaces(okCnnShape(*config));
+        plan[0] = pl.ct;
+        plan[1] = pl.region;
+        return OKENV_OK;
+    }
+
+    int okenv_cnn_create(okenv_t h, const okenv_cnn_config *config)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kCnnDriver, "create", kGateHandle))
+            return rc;
+        if (const char *why = okCnnCheckConfig(config))
+            return driverRefuses(h, OKENV_ERR_INVALID, kCnnDriver, "create", why);
+        const ok_cnn_shape s = okCnnShape(*config);
+        if (const int rc = driverCreateFlat(h, kCnnDriver, static_cast<size_t>(ok_cnn_offsets(s).total), kernelOf(okCnnConvKernel)))
+            return rc;
+        h->cnn_drv.ok = false; // (until the kernels' own buffers stand)
+        const size_t pack = static_cast<size_t>(okCnnPlaces(s).pack_total), feat = static_cast<size_t>(h->shape.N) * ok_cnn_features(s);
+        if (pack > h->cnn_pack_cap || feat > h->cnn_feat_cap)
+        {
+            const size_t np = std::max(pack, h->cnn_pack_cap), nf = std::max(feat, h->cnn_feat_cap);
+            h->cnn_pack_cap = h->cnn_feat_cap = 0; // (a failed allocation leaves none of them)
+            if (const int rc = regrow(h, {fresh(h->d_cnn_pack, np), fresh(h->d_cnn_feat, nf)}))
+                return rc;
+            h->cnn_pack_cap = np, h->cnn_feat_cap = nf;
+        }
+        h->cnn        = *config;
+        h->cnn_drv.ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_cnn_num_params(okenv_t h, int32_t *num_params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kCnnDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
+            return rc;
+        *num_params = ok_cnn_offsets(okCnnShape(h->cnn)).total;
+        return OKENV_OK;
+    }
+
+    int okenv_cnn_set_params(okenv_t h, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kCnnDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
+            return rc;
+        const ok_cnn_shape s = okCnnShape(h->cnn);
+        if (const int rc = driverSet(h, kCnnDriver, {vectorOf(h->cnn_drv.d, params, ok_cnn_offsets(s).total)}))
+            return rc;
+        OkCnnPackParams p{};
+        p.s      = s;
+        p.params = h->cnn_drv.d;
+        p.pack   = h->d_cnn_pack;
+        const unsigned blocks = static_cast<unsigned>((okCnnPlaces(s).pack_total + 255) / 256);
+        hipLaunchKernelGGL(okCnnPackKernel, dim3(blocks), dim3(256), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_cnn_get_params(okenv_t h, float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kCnnDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
+            return rc;
+        return driverGet(h, {vectorOf(h->cnn_drv.d, params, ok_cnn_offsets(okCnnShape(h->cnn)).total)});
+    }
+
+    int okenv_cnn_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_cnn_record *rec)
+    {
+        OK_QUIESCE(h);
+        return cnnAct(h, frames, frame_bytes, rec, OKENV_CNN_STAGE_CONV | OKENV_CNN_STAGE_HEAD);
+    }
+
+    int okenv_debug_cnn_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_cnn_record *rec, uint32_t stages)
+    {
+        OK_QUIESCE(h);
+        return cnnAct(h, frames, frame_bytes, rec, stages);
+    }
+
+    int okenv_cnn_act_host(const okenv_cnn_config *config, const float *params, int32_t n, const uint8_t *frames, const uint8_t *crashed,
+                           float *throttle, float *steer, float *out, uint8_t *alive)
+    {
+        if (const char *why = okCnnCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_cnn_act_host: ") + why);
+        if (!params || n < 0 || !frames)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_cnn_act_host: bad argument");
+        okCnnActHost(*config, params, n, frames, crashed, throttle, steer, out, alive);
         return OKENV_OK;
     }
 

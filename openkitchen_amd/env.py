@@ -910,6 +910,42 @@ class BatchedEnvironment:
         else:
             capi.check(self._L.okenv_debug_bev_stages(self._h, capi.ptr(frames), self.N * S * S * 4, capi.ptr(out), int(stages)), self._h)
 
+    # ---- behavioural-cloning image policy (include/okenv.h) ---------------------------------------------
+    def cnn_create(self, config=None, **members):
+        """Attaches the behavioural-cloning image policy (the reference's PolicyCNN) to the handle; config: a capi.cnn_config(...), or
+        its members by name (the reference's shape and controls by default).  Returns the floats of its parameter vector."""
+        if config is None:
+            config = capi.cnn_config(**members)
+        capi.check(self._L.okenv_cnn_create(self._h, C.byref(config)), self._h)
+        self.cnn_config = config
+        return self.cnn_num_params()
+
+    def cnn_num_params(self):
+        return self._count("okenv_cnn_num_params")
+
+    def cnn_set_params(self, params):
+        """New parameters (the policy's, in torch's parameters() order: capi.cnn_layout) from a float32 numpy array or a device
+        tensor.  Enqueued on the handle's stream; the call waits for the stream when it was handed a numpy array (which may be a
+        temporary), not for a device tensor."""
+        self._set_params("okenv_cnn_set_params", (params,), (self.cnn_num_params(),))
+
+    def cnn_get_params(self, out=None):
+        """The parameter vector as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
+        return self._get_state("okenv_cnn_get_params", {"params": self.cnn_num_params()}, None if out is None else {"params": out})["params"]
+
+    def cnn_act(self, frames, record=None, stages=None):
+        """The policy's action of every agent from its frame, enqueued on the handle's stream without a synchronisation.  frames: a
+        device tensor / address of [N, S, S, 4] uint8.  record: None, or a dict of device tensors / addresses under "out" [N],
+        "action" [N,2] float32 and "alive" [N] uint8, each optional.  stages: None, or a mask of capi.CNN_STAGE_* -- only those
+        kernels (okenv_debug_cnn_stages, for measurement)."""
+        S = self.cnn_config.image_size
+        sizes = record and {"out": self.N * 4, "action": self.N * 8, "alive": self.N}
+        if stages is None:
+            self._act("okenv_cnn_act", capi.OkenvCnnRecord, record, sizes, capi.ptr(frames), self.N * S * S * 4)
+        else:
+            rec = None if record is None else C.byref(capi.fill_pointers(capi.OkenvCnnRecord(), record, "record", sizes))
+            capi.check(self._L.okenv_debug_cnn_stages(self._h, capi.ptr(frames), self.N * S * S * 4, rec, int(stages)), self._h)
+
     # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) -------------------------------------------------------
     def gcl_create(self, **config):
         """Attaches a GCL object (policy R -> H1 -> H2 -> 2 with log_std, value R -> H1 -> H2 -> 1, cost R + 2 -> C1 -> C2 -> 1) to the

@@ -593,6 +593,28 @@ class VectorEnvironment:
         self.env.bev_encode(frames, out)
         return out
 
+    # ---- behavioural-cloning image policy (include/okenv.h) -------------------------------------------------
+    def enable_image_policy(self, config, params):
+        """Attaches the reference's behavioural-cloning policy (BehavioralCloning: PolicyCNN) as a device driver.  config: a
+        capi.cnn_config(...) or a dict of its members; params: the flat vector bc.cnn_params_from_state_dict makes, a float32 numpy
+        array or a tensor.  Call it again with new params after training on."""
+        if isinstance(config, dict):
+            config = capi.cnn_config(**config)
+        self._cnn_flat = self._attach_flat("cnn", config, params)  # alive until the next hand-over: a tensor's copy is asynchronous
+        self.cnn_config = config
+        self._cnn_graphs = {}  # a captured launch carries the old shape and vector
+
+    def image_act(self, frames, record=None):
+        """The policy's action of every agent from `frames`, a contiguous uint8 tensor [N, S, S, 4] on this device (camera()'s,
+        rendered at the policy's image_size), written into `throttle` / `steering`: two kernels on the environment's stream, no
+        synchronisation, usable inside capture(body).  record: optional dict of device tensors ("out" [N], "action" [N,2] float32,
+        "alive" [N] uint8) that receive the sample."""
+        S = self.cnn_config.image_size
+        if (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.device != self.device
+                or tuple(frames.shape) != (self.num_envs, S, S, 4)):
+            raise ValueError("image_act(frames) needs a contiguous uint8 tensor of shape (%d, %d, %d, 4) on %s" % (self.num_envs, S, S, self.device))
+        self.env.cnn_act(frames, record)
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
