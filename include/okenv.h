@@ -1447,7 +1447,8 @@ OKENV_API int okenv_debug_sincos(int32_t device, const float *x, float *s, float
 /* One leaf function of include/okenv_math.h on n values (host pointers), evaluated on GPU `device` by one elementwise kernel, or,
  * with device == OKENV_DEBUG_ON_HOST, by the host compilation of the same header inside the library (no GPU needed).  The two must
  * agree bit for bit: tests/test_gpu_math.py runs both over the whole argument range.  `b` is read by OKENV_FN_ATAN2 only (a = y,
- * b = x); `out1` is written by OKENV_FN_SINCOS only (out0 = sine, out1 = cosine); both may be NULL otherwise. */
+ * b = x) and OKENV_FN_SINCOS_PAIR; `out1` is written by OKENV_FN_SINCOS (out0 = sine, out1 = cosine) and OKENV_FN_SINCOS_PAIR only;
+ * both may be NULL otherwise. */
 enum okenv_debug_fn {
     OKENV_FN_SINCOS,                 /* ok_sincosf */
     OKENV_FN_TANH,                   /* ok_tanhf */
@@ -1456,6 +1457,8 @@ enum okenv_debug_fn {
     OKENV_FN_ATAN2,                  /* ok_atan2f(a, b) */
     OKENV_FN_NORMALIZE_ANGLE,        /* ok_normalize_angle_deg */
     OKENV_FN_EXPERT_NORMALIZE_ANGLE, /* ok_expert_normalize_angle_deg */
+    OKENV_FN_SINCOS_PAIR,            /* ok_sincosf_pair(a, b): out0 and out1 hold 2 n floats, the sine and cosine of a[i] in
+                                        out0[2 i], out0[2 i + 1], those of b[i] in out1[2 i], out1[2 i + 1] */
     OKENV_NUM_DEBUG_FNS
 };
 #define OKENV_DEBUG_ON_HOST (-1)

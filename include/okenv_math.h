@@ -121,6 +121,79 @@ OK_HD void ok_sincosf(float x, float *s_out, float *c_out)
     *c_out = (float)cv;
 }
 
+/* From sin r and cos r, already rounded to fp32, to the sine and cosine of quadrant n: ok_sincosf's four cases without a branch.
+ * Odd quadrants swap the two; the sine is negative in quadrants 2 and 3, the cosine in 1 and 2.  ok_sincosf negates the double and
+ * then rounds; rounding to nearest even is symmetric in the sign, so flipping the sign bit of the rounded value gives the same bits. */
+OK_HD void ok_sincos_quadrant(const int n, const float sr, const float cr, float *s_out, float *c_out)
+{
+    union { float f; uint32_t u; } s, c;
+    s.f = (n & 1) ? cr : sr;
+    c.f = (n & 1) ? sr : cr;
+    s.u ^= ((uint32_t)n & 2u) << 30;
+    c.u ^= (((uint32_t)n + 1u) & 2u) << 30;
+    *s_out = s.f;
+    *c_out = c.f;
+}
+
+/*
+ * ok_sincosf of two angles at once: by definition the bits that ok_sincosf(xa, sa, ca) and ok_sincosf(xb, sb, cb) return, for every
+ * pair of arguments, on host and device (tests/test_math_pair.py).  The step kernels need the sine and cosine of the agent's
+ * heading and of the lane's ray angle in every step; two calls of ok_sincosf compile to two blocks one after the other, each with
+ * its own range-reduction loop, its own non-finite exit, its own four-way quadrant branch and its own copy of the constants, and
+ * the two dependent fp64 chains run back to back.  Here, where both arguments are finite and below 2^31 in magnitude -- always,
+ * but for a heading that has run away -- both reductions and both pairs of polynomials stand in one basic block, operation by
+ * operation next to each other, so that one chain's latency is the other's work; every constant is named once; the quadrants are
+ * undone by selects and sign bits (ok_sincos_quadrant).  The same operations on the same values as ok_sincosf in every other
+ * respect.  Anything else takes the one rare branch to two plain calls.
+ */
+OK_HD void ok_sincosf_pair(const float xa, const float xb, float *sa_out, float *ca_out, float *sb_out, float *cb_out)
+{
+    /* (the comparison in fp32 decides what ok_sincosf's in fp64 decides: the conversion is exact) */
+    if (__builtin_expect(!((__builtin_fabsf(xa) < 2147483648.0f) & (__builtin_fabsf(xb) < 2147483648.0f)), 0)) {
+        ok_sincosf(xa, sa_out, ca_out);
+        ok_sincosf(xb, sb_out, cb_out);
+        return;
+    }
+    const double xda = (double)xa, xdb = (double)xb;
+    const double two_over_pi = ok_konst(0x1.45f306dc9c883p-1);
+    const double qa = OK_RINT(xda * two_over_pi), qb = OK_RINT(xdb * two_over_pi);
+    const double p1 = ok_konst(0x1.921fb54442d18p+0);
+    double ra = OK_FMA(-qa, p1, xda), rb = OK_FMA(-qb, p1, xdb);
+    const double p2 = ok_konst(0x1.1a62633145c07p-54);
+    ra = OK_FMA(-qa, p2, ra);
+    rb = OK_FMA(-qb, p2, rb);
+    const double za = ra * ra, zb = rb * rb;
+    /* the coefficients of ok_sincosf's S and C, highest degree first */
+    const double s5 = ok_konst(0x1.5e01d1798c2b3p-33), c5 = ok_konst(0x1.1bfd9695386eap-29);
+    const double s4 = ok_konst(-0x1.ae5ff116c8d06p-26), c4 = ok_konst(-0x1.27e0dd327adbcp-22);
+    double psa = OK_FMA(s5, za, s4), psb = OK_FMA(s5, zb, s4);
+    double pca = OK_FMA(c5, za, c4), pcb = OK_FMA(c5, zb, c4);
+    const double s3 = ok_konst(0x1.71de377d84985p-19), c3 = ok_konst(0x1.a019fc4c6ed87p-16);
+    psa = OK_FMA(psa, za, s3);
+    psb = OK_FMA(psb, zb, s3);
+    pca = OK_FMA(pca, za, c3);
+    pcb = OK_FMA(pcb, zb, c3);
+    const double s2 = ok_konst(-0x1.a01a019e70424p-13), c2 = ok_konst(-0x1.6c16c168f930cp-10);
+    psa = OK_FMA(psa, za, s2);
+    psb = OK_FMA(psb, zb, s2);
+    pca = OK_FMA(pca, za, c2);
+    pcb = OK_FMA(pcb, zb, c2);
+    const double s1 = ok_konst(0x1.1111111110b60p-7), c1 = ok_konst(0x1.5555555554001p-5);
+    psa = OK_FMA(psa, za, s1);
+    psb = OK_FMA(psb, zb, s1);
+    pca = OK_FMA(pca, za, c1);
+    pcb = OK_FMA(pcb, zb, c1);
+    const double s0 = ok_konst(-0x1.5555555555555p-3), c0 = ok_konst(-0x1.ffffffffffffap-2);
+    psa = OK_FMA(psa, za, s0);
+    psb = OK_FMA(psb, zb, s0);
+    pca = OK_FMA(pca, za, c0);
+    pcb = OK_FMA(pcb, zb, c0);
+    const double sra = OK_FMA(ra * za, psa, ra), srb = OK_FMA(rb * zb, psb, rb);
+    const double cra = OK_FMA(za, pca, 1.0), crb = OK_FMA(zb, pcb, 1.0);
+    ok_sincos_quadrant((int)qa, (float)sra, (float)cra, sa_out, ca_out); /* |q| < 1.4e9 fits an int */
+    ok_sincos_quadrant((int)qb, (float)srb, (float)crb, sb_out, cb_out);
+}
+
 /* ---- Philox4x32-10 -------------------------------------------------------------------------- */
 
 typedef struct ok_u32x4 { uint32_t v[4]; } ok_u32x4;

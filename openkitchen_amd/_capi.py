@@ -51,7 +51,7 @@ REINFORCE_SUM, REINFORCE_MEAN = 0, 1
 REINFORCE_REDUCE = {"sum": REINFORCE_SUM, "mean": REINFORCE_MEAN}
 REINFORCE_KERNELS = ("grad", "step")
 # okenv_debug_math (include/okenv.h): enum okenv_debug_fn in order, and the device number that means "evaluate on the host"
-DEBUG_FNS = ("sincos", "tanh", "exp", "log", "atan2", "normalize_angle", "expert_normalize_angle")
+DEBUG_FNS = ("sincos", "tanh", "exp", "log", "atan2", "normalize_angle", "expert_normalize_angle", "sincos_pair")
 DEBUG_ON_HOST = -1
 
 # every symbol include/okenv.h declares (tests/test_capi_symbols.py checks the library exports them all)

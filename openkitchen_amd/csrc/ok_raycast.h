@@ -41,6 +41,24 @@
 
 #define OKRC_INF __builtin_huge_valf()
 
+// A value barrier against the compiler's own packing of fp32 arithmetic.  Where the x and the y component of a point go through the
+// same operations, -O3 pairs them up into v_pk_add_f32 / v_pk_mul_f32 and builds the register pairs with extra moves; on gfx950 a
+// packed fp32 operation costs more than the two plain ones it stands for (docs/HISTORY.md section 38 has the measurement).  A value
+// that has passed through here is opaque to the vectoriser, so the operation that made it has no twin to be paired with.  No
+// instruction, same bits; nothing at all on the host.
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ float okUnpaired(float v)
+{
+    asm("" : "+v"(v));
+    return v;
+}
+#else
+OKRC_HD float okUnpaired(const float v)
+{
+    return v;
+}
+#endif
+
 // Segment2d of the reference (Environment/Typedefs.h:101-105): x1,y1,x2,y2, 16 bytes.
 struct OkSeg
 {
@@ -368,12 +386,12 @@ OKRC_HD float ok_first_hit_update(const float   ox,
     constexpr int32_t kBitsHi  = 0x501502F9; // 1e10f
     constexpr int32_t kBitsEps = 0x322BCC77; // 1e-8f = OK_PARALLEL_EPS
     const float    sdx   = b.x - a.x;
-    const float    sdy   = b.y - a.y;
-    const float    denom = rdx * sdy - rdy * sdx;
+    const float    sdy   = okUnpaired(b.y - a.y); // (okUnpaired: plain VALU, no packed pairs in the exact loop)
+    const float    denom = rdx * sdy - okUnpaired(rdy * sdx);
     const float    ex    = a.x - ox;
-    const float    ey    = a.y - oy;
-    const float    num_t = ex * sdy - ey * sdx;
-    const float    num_s = ex * rdy - ey * rdx;
+    const float    ey    = okUnpaired(a.y - oy);
+    const float    num_t = ex * sdy - okUnpaired(ey * sdx);
+    const float    num_s = ex * rdy - okUnpaired(ey * rdx);
     const uint32_t sg    = okBits(denom) & 0x80000000U;
     const uint32_t bd    = okBits(denom) ^ sg;       // bits of |denom|
     const uint32_t bfs   = okBits(num_s) ^ sg;       // bits of fs = num_s with denom's sign folded in

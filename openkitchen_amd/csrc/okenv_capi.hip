@@ -1928,19 +1928,22 @@ int debugMath(const int32_t device, const float *a, const float *b, float *out0,
     if (n == 0)
         return OKENV_OK;
     OK_HIP(nullptr, hipSetDevice(device));
-    // four arrays of n floats: a, b (OKENV_FN_ATAN2 only), out0, out1 (OKENV_FN_SINCOS only)
-    DebugBuffer buf;
-    OK_HIP(nullptr, hipMalloc(reinterpret_cast<void **>(&buf.d), 16U * count));
-    float *da = buf.d, *db = buf.d + count, *d0 = buf.d + 2U * count, *d1 = buf.d + 3U * count;
+    // four arrays: a, b (OKENV_FN_ATAN2 and OKENV_FN_SINCOS_PAIR only) of n floats, out0, out1 (OKENV_FN_SINCOS and
+    // OKENV_FN_SINCOS_PAIR only) of n floats, 2 n for OKENV_FN_SINCOS_PAIR
+    constexpr bool kPair = kFn == OKENV_FN_SINCOS_PAIR;
+    const size_t   wide  = kPair ? 2U * count : count;
+    DebugBuffer    buf;
+    OK_HIP(nullptr, hipMalloc(reinterpret_cast<void **>(&buf.d), 4U * (2U * count + 2U * wide)));
+    float *da = buf.d, *db = buf.d + count, *d0 = buf.d + 2U * count, *d1 = d0 + wide;
     OK_HIP(nullptr, hipMemcpy(da, a, 4U * count, hipMemcpyHostToDevice));
-    if (kFn == OKENV_FN_ATAN2)
+    if (kFn == OKENV_FN_ATAN2 || kPair)
         OK_HIP(nullptr, hipMemcpy(db, b, 4U * count, hipMemcpyHostToDevice));
     const unsigned un = static_cast<unsigned>(n);
     hipLaunchKernelGGL(okDebugMathKernel<kFn>, dim3((un + 255U) / 256U), dim3(256), 0, nullptr, da, db, d0, d1, un);
     OK_HIP(nullptr, hipGetLastError());
-    OK_HIP(nullptr, hipMemcpy(out0, d0, 4U * count, hipMemcpyDeviceToHost));
-    if (kFn == OKENV_FN_SINCOS)
-        OK_HIP(nullptr, hipMemcpy(out1, d1, 4U * count, hipMemcpyDeviceToHost));
+    OK_HIP(nullptr, hipMemcpy(out0, d0, 4U * wide, hipMemcpyDeviceToHost));
+    if (kFn == OKENV_FN_SINCOS || kPair)
+        OK_HIP(nullptr, hipMemcpy(out1, d1, 4U * wide, hipMemcpyDeviceToHost));
     return OKENV_OK;
 }
 } // namespace
@@ -5972,7 +5975,8 @@ extern "C"
 
     int okenv_debug_math(int32_t device, int32_t fn, const float *a, const float *b, float *out0, float *out1, int32_t n)
     {
-        if (fn < 0 || fn >= OKENV_NUM_DEBUG_FNS || !a || !out0 || n < 0 || (fn == OKENV_FN_ATAN2 && !b) || (fn == OKENV_FN_SINCOS && !out1))
+        if (fn < 0 || fn >= OKENV_NUM_DEBUG_FNS || !a || !out0 || n < 0 || ((fn == OKENV_FN_ATAN2 || fn == OKENV_FN_SINCOS_PAIR) && !b) ||
+            ((fn == OKENV_FN_SINCOS || fn == OKENV_FN_SINCOS_PAIR) && !out1))
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_math: bad argument");
         switch (fn)
         {
@@ -5982,6 +5986,7 @@ extern "C"
         case OKENV_FN_LOG: return debugMath<OKENV_FN_LOG>(device, a, b, out0, out1, n);
         case OKENV_FN_ATAN2: return debugMath<OKENV_FN_ATAN2>(device, a, b, out0, out1, n);
         case OKENV_FN_NORMALIZE_ANGLE: return debugMath<OKENV_FN_NORMALIZE_ANGLE>(device, a, b, out0, out1, n);
+        case OKENV_FN_SINCOS_PAIR: return debugMath<OKENV_FN_SINCOS_PAIR>(device, a, b, out0, out1, n);
         default: return debugMath<OKENV_FN_EXPERT_NORMALIZE_ANGLE>(device, a, b, out0, out1, n);
         }
     }

@@ -494,8 +494,9 @@ __device__ __forceinline__ void okAgentPreStep(const OkStepParams &p,
         }
     }
     // The lane's ray direction (CollisionChecker.cu:125, angle = kDeg2Rad * (rot_ + ray angle)) depends on nothing but
-    // the heading just updated: evaluated here, next to the agent's own sine/cosine, the two independent fp64 chains
-    // interleave instead of running back to back.
+    // the heading just updated: it is evaluated here, together with the agent's own sine/cosine, by ok_sincosf_pair, which
+    // puts the two independent fp64 chains into one basic block.  (Two calls of ok_sincosf side by side do NOT interleave:
+    // the compiler emits one block after the other, each behind its own branches and with its own copy of the constants.)
     // pair_split (the tail kernel, where lanes 2i and 2i + 1 hold the same agent AND the same ray): the even lane takes the
     // ray's angle, the odd lane the agent's, and they swap results -- one fp64 chain per lane instead of two.
     if (pair_split)
@@ -512,15 +513,17 @@ __device__ __forceinline__ void okAgentPreStep(const OkStepParams &p,
     else
     {
         if (ray_sn != nullptr)
-            ok_sincosf(OK_DEG2RAD * (r.rot + ray_deg), ray_sn, ray_cs);
-        ok_sincosf(OK_DEG2RAD * r.rot, &sn, &cs);
+            ok_sincosf_pair(OK_DEG2RAD * (r.rot + ray_deg), OK_DEG2RAD * r.rot, ray_sn, ray_cs, &sn, &cs);
+        else
+            ok_sincosf(OK_DEG2RAD * r.rot, &sn, &cs);
     }
     if (moves)
     {
+        // (okUnpaired, ok_raycast.h, here and below: the y component's operations stay plain VALU instead of being packed with x's)
         const float dx = cs * r.speed * OK_DT;
         r.pos_x += dx;
-        const float dy = sn * r.speed * OK_DT;
-        r.pos_y += dy;
+        const float dy = okUnpaired(okUnpaired(sn * r.speed) * OK_DT);
+        r.pos_y = okUnpaired(r.pos_y + dy);
     }
     if (p.do_move && !r.crashed)
     {
@@ -534,8 +537,8 @@ __device__ __forceinline__ void okAgentPreStep(const OkStepParams &p,
         }
         else if (r.disp_ctr >= OK_DISP_PERIOD)
         {
-            const float ddx = r.pos_x - r.disp_x, ddy = r.pos_y - r.disp_y;
-            const float d2  = ddx * ddx + ddy * ddy;
+            const float ddx = r.pos_x - r.disp_x, ddy = okUnpaired(r.pos_y - r.disp_y);
+            const float d2  = ddx * ddx + okUnpaired(ddy * ddy);
             if (d2 < OK_DISP_THRESH2)
                 r.disp_to = true;
             r.disp_ctr = 0U;
@@ -568,10 +571,10 @@ __device__ __forceinline__ float okRayEpilogue(const OkDeviceState &st,
                                                float               *rel_y_out = nullptr)
 {
     const float xt = hx - ox;
-    const float yt = hy - oy;
-    const float rx = xt * cr - yt * sr;
-    const float ry = xt * sr + yt * cr;
-    const float n2 = rx * rx + ry * ry;
+    const float yt = okUnpaired(hy - oy); // (okUnpaired: plain VALU, no packed pairs)
+    const float rx = xt * cr - okUnpaired(yt * sr);
+    const float ry = okUnpaired(okUnpaired(xt * sr) + okUnpaired(yt * cr));
+    const float n2 = rx * rx + okUnpaired(ry * ry);
     st.rel_x[k]    = rx;
     st.rel_y[k]    = ry;
     if (rel_x_out != nullptr)
@@ -1117,7 +1120,7 @@ __global__ void __launch_bounds__(1024) okStepKernel(const OkStepParams p)
                     ok_sincosf(OK_DEG2RAD * (ag.rot + p.ray_deg[r]), &rdy, &rdx);
                     const float min_t = okCastRay<kMode>(p, view, ox, oy, rdx, rdy);
                     hx                = ox + min_t * rdx;
-                    hy                = oy + min_t * rdy;
+                    hy                = okUnpaired(oy + okUnpaired(min_t * rdy));
                     p.st.hit_x[k]     = hx;
                     p.st.hit_y[k]     = hy;
                 }
@@ -1446,20 +1449,15 @@ __global__ void __launch_bounds__(1024) okStepCoopKernel(const OkStepParams p_in
             // A launch ends with its slowest wave, and a wave is slow for many steps in a row (its agent sits where rays are long).
             // Waves of one SIMD share its issue slots: the further a wave lags behind the leader of its SIMD, the higher its
             // issue priority.  Purely a scheduling hint: no effect on results.
+            // The progress word is asked for here and used after the pre-step (below): its LDS round trip runs under the trig.
+            // (An atomicMax whose value is used would be waited for on the spot: the compiler's single-lane form of a wave's atomic
+            // hands the value round with a readfirstlane right behind it.  So the update returns nothing and a load of the same
+            // lane, which the LDS serves after it, fetches max(old, s): behind >= k for the same k >= 1 as with the old value.)
+            uint32_t leader = 0U;
+            if ((threadIdx.x & 63U) == 0U)
             {
-                uint32_t leader = 0U;
-                if ((threadIdx.x & 63U) == 0U)
-                    leader = atomicMax(&lds_progress[my_simd], static_cast<uint32_t>(s));
-                leader          = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(leader)));
-                const int behind = static_cast<int>(leader) - s;
-                if (behind >= 3 * OKENV_PRIO_STEP)
-                    __builtin_amdgcn_s_setprio(3);
-                else if (behind >= 2 * OKENV_PRIO_STEP)
-                    __builtin_amdgcn_s_setprio(2);
-                else if (behind >= OKENV_PRIO_STEP)
-                    __builtin_amdgcn_s_setprio(1);
-                else
-                    __builtin_amdgcn_s_setprio(0);
+                (void)__hip_atomic_fetch_max(&lds_progress[my_simd], static_cast<uint32_t>(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                leader = __hip_atomic_load(&lds_progress[my_simd], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
 #endif
             if (kPolicy == kPolicyMlp)
@@ -1518,8 +1516,21 @@ __global__ void __launch_bounds__(1024) okStepCoopKernel(const OkStepParams p_in
             // (direct dealing with an even number of lanes per ray: lanes 2i and 2i + 1 hold the same ray and share the two fp64
             // evaluations, as in the tail kernel)
             okAgentPreStep(p, ag, a, s, sr, cr, ray_deg, &rdy, &rdx, have_drawn, ra_now, direct && (dm & 1) == 0);
+#if OKENV_PRIO == 2
+            { // the progress word asked for at the top of the step has arrived by now
+                const int behind = __builtin_amdgcn_readfirstlane(static_cast<int>(leader)) - s;
+                if (behind >= 3 * OKENV_PRIO_STEP)
+                    __builtin_amdgcn_s_setprio(3);
+                else if (behind >= 2 * OKENV_PRIO_STEP)
+                    __builtin_amdgcn_s_setprio(2);
+                else if (behind >= OKENV_PRIO_STEP)
+                    __builtin_amdgcn_s_setprio(1);
+                else
+                    __builtin_amdgcn_s_setprio(0);
+            }
+#endif
             const float ox     = ag.pos_x + p.sensor_offset * cr;
-            const float oy     = ag.pos_y + p.sensor_offset * sr;
+            const float oy     = okUnpaired(ag.pos_y + okUnpaired(p.sensor_offset * sr));
             const bool  casts  = ray_ok && !ag.crashed;
             // front / back split: is the agent's ray origin certainly on the side of the inner boundaries where no back segment can
             // be a ray's first hit?  (one answer per agent; its rays' front walks report ambiguous rejections in amb_ray)
@@ -1527,7 +1538,7 @@ __global__ void __launch_bounds__(1024) okStepCoopKernel(const OkStepParams p_in
             if (fb)
             { // (the answer of the last test stands while the origin stays inside the circle that test cleared; a re-placed agent
               // is far outside it, a NaN pose fails the comparison)
-                const float moved = __builtin_fabsf(ox - cert_ox) + __builtin_fabsf(oy - cert_oy);
+                const float moved = __builtin_fabsf(ox - cert_ox) + __builtin_fabsf(okUnpaired(oy - cert_oy));
                 if (!(moved < cert_clear))
                 {
                     cert_state = okOriginChiGroup(view, ox, oy, r, G, p.fb_t12, p.fb_t34, &cert_clear);
@@ -1701,7 +1712,7 @@ __global__ void __launch_bounds__(1024) okStepCoopKernel(const OkStepParams p_in
                 if (casts)
                 {
                     hx                = ox + min_t * rdx;
-                    hy                = oy + min_t * rdy;
+                    hy                = okUnpaired(oy + okUnpaired(min_t * rdy));
                     p.st.hit_x[ke]    = hx;
                     p.st.hit_y[ke]    = hy;
                 }
@@ -2122,7 +2133,7 @@ __global__ void __launch_bounds__(kPolicy == kPolicyQ ? 576 : 512) okStepTailKer
             if (casts)
             {
                 hx             = ox + found * rdx;
-                hy             = oy + found * rdy;
+                hy             = okUnpaired(oy + okUnpaired(found * rdy));
                 p.st.hit_x[ke] = hx;
                 p.st.hit_y[ke] = hy;
             }
@@ -2947,6 +2958,8 @@ __host__ __device__ inline void okDebugMathElement(const float *a, const float *
         out0[i] = ok_atan2f(a[i], b[i]);
     else if (kFn == OKENV_FN_NORMALIZE_ANGLE)
         out0[i] = ok_normalize_angle_deg(a[i]);
+    else if (kFn == OKENV_FN_SINCOS_PAIR) // (out0 and out1 hold two floats per element: sine, cosine)
+        ok_sincosf_pair(a[i], b[i], &out0[2U * i], &out0[2U * i + 1U], &out1[2U * i], &out1[2U * i + 1U]);
     else
         out0[i] = ok_expert_normalize_angle_deg(a[i]);
 }

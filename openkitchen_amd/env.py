@@ -1080,12 +1080,19 @@ def debug_sincos(x, device=0):
 def debug_math(fn, a, b=None, device=0):
     """One leaf function of include/okenv_math.h on a float32 array (okenv_debug_math), on GPU `device` or, with
     device=capi.DEBUG_ON_HOST, by the library's host compilation of the same header (no GPU needed).  fn: a name of capi.DEBUG_FNS or
-    the integer.  b is the second argument of "atan2" (a = y, b = x).  Returns the result; (sine, cosine) for "sincos"."""
+    the integer.  b is the second argument of "atan2" (a = y, b = x) and of "sincos_pair".  Returns the result; (sine, cosine) for
+    "sincos"; for "sincos_pair" two arrays of shape a.shape + (2,): (sine, cosine) of a and of b (ok_sincosf_pair)."""
     k = capi.DEBUG_FNS.index(fn) if isinstance(fn, str) else int(fn)
     a = np.ascontiguousarray(a, dtype=np.float32)
     b = None if b is None else np.ascontiguousarray(b, dtype=np.float32)
     if b is not None and b.shape != a.shape:
         raise ValueError("debug_math: a and b differ in shape")
+    if k == capi.DEBUG_FNS.index("sincos_pair"):
+        if b is None:
+            raise ValueError("debug_math: sincos_pair takes two arrays")
+        out0, out1 = np.zeros(a.shape + (2,), np.float32), np.zeros(a.shape + (2,), np.float32)
+        capi.check(capi.load().okenv_debug_math(int(device), k, capi.ptr(a), capi.ptr(b), capi.ptr(out0), capi.ptr(out1), a.size))
+        return out0, out1
     out0 = np.zeros_like(a)
     out1 = np.zeros_like(a) if k == capi.DEBUG_FNS.index("sincos") else None
     capi.check(capi.load().okenv_debug_math(int(device), k, capi.ptr(a), capi.ptr(b), capi.ptr(out0), capi.ptr(out1), a.size))
