@@ -1139,6 +1139,86 @@ OKENV_API int okenv_debug_cnn_stages(okenv_t h, const uint8_t *frames, int64_t f
 OKENV_API int okenv_cnn_act_host(const okenv_cnn_config *config, const float *params, int32_t n, const uint8_t *frames, const uint8_t *crashed,
                                  float *throttle, float *steer, float *out, uint8_t *alive);
 
+/* ---- World-model racers -------------------------------------------------------------------------------------
+ * WorldModelVaeRnn/main.cpp's CmaEsAgent for every agent of the handle, each agent one CMA-ES candidate: from the camera's RGBA8
+ * frames (okenv_render_views, rendered at image_size x image_size) the /255 normalisation, the conv-VAE encoder's four stride-2
+ * convolutions (kernel 4, padding 1, eval-mode BatchNorm folded in) with ReLU and fc_mu, the state [mu | sin(rot), cos(rot)], the
+ * agent's OWN controller (Z + 2 -> hidden -> hidden / 2 -> 1, tanh after each layer), to throttle_delta = throttle and
+ * steering_delta = steer_scale * output; and the fitness of main.cpp:329-342.  Inference only.  The rule is written out in
+ * include/okenv_world.h (ok_world_*); all matrix work runs on the f32-input matrix cores.  Two parameter vectors: the encoder's, shared
+ * (ok_world_offsets), and the controllers', [N][ok_controller_num_params(latent + 2, hidden, 1)]; every weight must be finite. */
+typedef struct okenv_world_config {
+    int32_t image_size;   /* S: multiple of 16, 16 .. 128                        (the reference: 128)         */
+    int32_t channels[4];  /* multiples of 16, 16 .. 512                          (64, 128, 256, 512)          */
+    int32_t latent;       /* Z: multiple of 16, 16 .. 128; channels[3] (S/16)^2 <= 32768      (32)            */
+    int32_t hidden;       /* the controller's: even, 2 .. 64                     (16)                         */
+    float   throttle;     /* the constant throttle_delta; finite                 (100)                        */
+    float   steer_scale;  /* steering_delta per unit of the output; finite       (5)                          */
+    int32_t skip_crashed; /* 1: an act writes nothing for agents crashed at its time and spends no work on their frames */
+} okenv_world_config;
+
+/* What an act can leave behind for the caller, device pointers, each may be NULL */
+typedef struct okenv_world_record {
+    float   *mu;     /* [N][Z]     the encoder's mu                        */
+    float   *state;  /* [N][Z + 2] mu, sin(rot), cos(rot)                  */
+    float   *out;    /* [N]        the controller's output                 */
+    float   *action; /* [N][2]     throttle_delta, steering_delta          */
+    uint8_t *alive;  /* [N]        1 where the agent was not crashed       */
+} okenv_world_record;
+
+/* LDS bytes of the largest act kernel for the shape: a pure host function.  A shape is accepted only if this fits 160 KB.  0 for a
+ * NULL config or a shape outside the rule's limits. */
+OKENV_API int64_t okenv_world_lds_bytes(const okenv_world_config *config);
+/* What names the kernels' path for the shape: a pure host function.  plan [12], three per convolution: the workgroups its output
+ * channels take (128 a workgroup; waves of the last one idle where the count is no multiple of 128), the K blocks per tap (chunks of
+ * up to 64 input channels; 0 for layer 0, whose whole chain is one block) and the channels of a tap's last block (16 .. 64). */
+OKENV_API int okenv_world_plan(const okenv_world_config *config, int32_t *plan);
+/* Device bytes okenv_world_create allocates for N agents (packed weights, controllers, the activations between the kernels, fitness). */
+OKENV_API int64_t okenv_world_workspace_bytes(const okenv_world_config *config, int32_t num_agents);
+/* Attaches the racers to the handle (replaces earlier ones: their parameters are forgotten; the fitness is zeroed).  All device memory
+ * is allocated here.  OKENV_ERR_INVALID for NULL arguments, a shape outside the limits, a non-finite throttle or steer_scale or a
+ * skip_crashed other than 0 or 1. */
+OKENV_API int okenv_world_create(okenv_t h, const okenv_world_config *config);
+/* Floats of the encoder vector and of ONE agent's controller. */
+OKENV_API int okenv_world_num_params(okenv_t h, int32_t *encoder, int32_t *controller);
+/* New parameters from a host or device pointer: `which` OKENV_WORLD_ENCODER (the kernels' own copy of the weights is made behind it on
+ * the stream) or OKENV_WORLD_CONTROLLERS ([N][controller], one copy on the stream: cheap, it is called every generation).  No
+ * synchronisation. */
+#define OKENV_WORLD_ENCODER 0
+#define OKENV_WORLD_CONTROLLERS 1
+OKENV_API int okenv_world_set_params(okenv_t h, int32_t which, const float *params);
+/* The parameters, in the same order, to a host or device pointer; synchronises. */
+OKENV_API int okenv_world_get_params(okenv_t h, int32_t which, float *params);
+/* Acts from frames (device, 4-byte aligned, [N][S][S][4] uint8, frame_bytes = N S S 4 in all): writes OKENV_F_THROTTLE, OKENV_F_STEER
+ * and the record (rec may be NULL), for every agent, or with skip_crashed for those not crashed.  Kernels on the handle's stream only,
+ * no synchronisation, no allocation: capturable beside okenv_step and okenv_render_views.  OKENV_ERR_STATE before okenv_world_create or
+ * before both okenv_world_set_params; OKENV_ERR_INVALID for NULL frames or another frame_bytes. */
+OKENV_API int okenv_world_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_world_record *rec);
+/* The lane widths RaceTrack::getDistanceToLaneCenter divides by, host or device [P]; P must equal the centre line's. */
+OKENV_API int okenv_world_set_lane_widths(okenv_t h, const float *w_left, const float *w_right, int32_t num_points);
+/* The fitness: _begin zeroes it; _score is one kernel on the stream (capturable): per agent, not crashed: += 1 - distance to the lane
+ * centre over the lane width; crashed and timed out: = 0.  OKENV_ERR_STATE before okenv_world_create (score: or set_lane_widths). */
+OKENV_API int okenv_world_score_begin(okenv_t h);
+OKENV_API int okenv_world_score(okenv_t h);
+/* The fitness [N] to a host or device pointer (synchronises), and where it lives on the device. */
+OKENV_API int okenv_world_fitness(okenv_t h, float *out);
+OKENV_API int okenv_world_fitness_device(okenv_t h, float **ptr);
+/* okenv_world_act's kernels one by one, for measurement: only those named in `stages`, in their order (each reads what the one before
+ * left in the handle's buffers on an earlier call).  Refusals as okenv_world_act's. */
+#define OKENV_WORLD_STAGE_LIST 1u
+#define OKENV_WORLD_STAGE_CONV0 2u /* CONV0 << l: layer l */
+#define OKENV_WORLD_STAGE_LATENT 32u
+#define OKENV_WORLD_STAGE_HEAD 64u
+OKENV_API int okenv_debug_world_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_world_record *rec, uint32_t stages);
+/* The same rules on host arrays, no GPU needed.  act: frames [n][S][S][4], rot [n] (degrees, as stored), crashed [n] or NULL; the
+ * outputs mu [n][Z], state [n][Z + 2], out, throttle, steer, alive [n], each may be NULL; with skip_crashed the entries of crashed
+ * agents are left as they are.  score: one okenv_world_score on fitness [n] in place. */
+OKENV_API int okenv_world_act_host(const okenv_world_config *config, const float *encoder, const float *controllers, int32_t n,
+                                   const uint8_t *frames, const float *rot, const uint8_t *crashed, float *mu, float *state, float *out,
+                                   float *throttle, float *steer, uint8_t *alive);
+OKENV_API int okenv_world_score_host(const float *cx, const float *cy, const float *w_left, const float *w_right, int32_t num_points, int32_t n,
+                                     const float *x, const float *y, const uint8_t *crashed, const uint8_t *timed_out, float *fitness);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.

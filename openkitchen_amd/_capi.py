@@ -106,6 +106,10 @@ SYMBOLS = [
     "okenv_bev_encode", "okenv_debug_bev_stages", "okenv_bev_encode_host",
     "okenv_cnn_lds_bytes", "okenv_cnn_plan", "okenv_cnn_create", "okenv_cnn_num_params", "okenv_cnn_set_params", "okenv_cnn_get_params",
     "okenv_cnn_act", "okenv_debug_cnn_stages", "okenv_cnn_act_host",
+    "okenv_world_lds_bytes", "okenv_world_plan", "okenv_world_workspace_bytes", "okenv_world_create", "okenv_world_num_params",
+    "okenv_world_set_params", "okenv_world_get_params", "okenv_world_act", "okenv_world_set_lane_widths", "okenv_world_score_begin",
+    "okenv_world_score", "okenv_world_fitness", "okenv_world_fitness_device", "okenv_debug_world_stages", "okenv_world_act_host",
+    "okenv_world_score_host",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -631,6 +635,104 @@ def cnn_act_host(cfg, params, frames, crashed=None):
     return out
 
 
+# world-model racers (include/okenv.h)
+WORLD_LDS_BUDGET = 160 * 1024
+WORLD_ENCODER, WORLD_CONTROLLERS = 0, 1
+WORLD_VECTORS = {"encoder": WORLD_ENCODER, "controllers": WORLD_CONTROLLERS}
+WORLD_STAGE_LIST, WORLD_STAGE_CONV0, WORLD_STAGE_LATENT, WORLD_STAGE_HEAD = 1, 2, 32, 64  # CONV0 << l: layer l
+WORLD_STAGES = (("list", 1), ("conv0", 2), ("conv1", 4), ("conv2", 8), ("conv3", 16), ("latent", 32), ("head", 64))
+WORLD_COLS, WORLD_CHUNK = 128, 64  # output channels per workgroup and input channels per K block (ok_world.h)
+
+
+class OkenvWorldConfig(C.Structure):
+    _fields_ = [("image_size", C.c_int32), ("channels", C.c_int32 * 4), ("latent", C.c_int32), ("hidden", C.c_int32),
+                ("throttle", C.c_float), ("steer_scale", C.c_float), ("skip_crashed", C.c_int32)]
+
+
+class OkenvWorldRecord(C.Structure):
+    _fields_ = [("mu", C.c_void_p), ("state", C.c_void_p), ("out", C.c_void_p), ("action", C.c_void_p), ("alive", C.c_void_p)]
+
+
+def world_config(image_size=128, channels=(64, 128, 256, 512), latent=32, hidden=16, throttle=100.0, steer_scale=5.0, skip_crashed=0):
+    """okenv_world_config with the reference's shape and controls as defaults (WorldModelVaeRnn: train_vae.py's defaults, main.cpp)."""
+    return OkenvWorldConfig(int(image_size), (C.c_int32 * 4)(*map(int, channels)), int(latent), int(hidden), float(throttle),
+                            float(steer_scale), int(skip_crashed))
+
+
+def world_layout(cfg):
+    """ok_world_offsets: where every piece of the encoder vector begins, as (name, offset, shape) in order; the names are the
+    state-dict keys of the reference's Encoder (the BatchNorm layers net.3 / net.6 / net.9 are folded into the convolutions in front
+    of them).  The last entry's end is the vector's length."""
+    c = list(cfg.channels)
+    F = c[3] * (cfg.image_size // 16) ** 2
+    pieces = []
+    for l, cin in enumerate([3] + c[:3]):
+        name = "net.%d" % (0, 2, 5, 8)[l]
+        pieces += [(name + ".weight", (c[l], cin, 4, 4)), (name + ".bias", (c[l],))]
+    pieces += [("fc_mu.weight", (cfg.latent, F)), ("fc_mu.bias", (cfg.latent,))]
+    out, at = [], 0
+    for name, shape in pieces:
+        out.append((name, at, shape))
+        at += int(np.prod(shape))
+    return out
+
+
+def world_num_params(cfg):
+    """(floats of the encoder vector, floats of one agent's controller: ok_controller_num_params(latent + 2, hidden, 1))."""
+    name, at, shape = world_layout(cfg)[-1]
+    i, h = cfg.latent + 2, cfg.hidden
+    return at + int(np.prod(shape)), h * i + h + (h // 2) * h + h // 2 + h // 2 + 1
+
+
+def world_lds_bytes(cfg):
+    """okenv_world_lds_bytes: the largest act kernel's LDS for the shape, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_world_lds_bytes(C.byref(cfg)))
+
+
+def world_plan(cfg):
+    """okenv_world_plan: per convolution (workgroups its output channels take, K blocks per tap -- 0 for layer 0 --, channels of a tap's
+    last block).  No GPU needed."""
+    out = (C.c_int32 * 12)()
+    check(load().okenv_world_plan(C.byref(cfg), out))
+    return tuple(tuple(int(v) for v in out[3 * l:3 * l + 3]) for l in range(4))
+
+
+def world_workspace_bytes(cfg, num_agents):
+    """okenv_world_workspace_bytes: device bytes okenv_world_create allocates for num_agents; 0 for a refused shape."""
+    return int(load().okenv_world_workspace_bytes(C.byref(cfg), int(num_agents)))
+
+
+def world_act_host(cfg, encoder, controllers, frames, rot, crashed=None, into=None):
+    """okenv_world_act_host on numpy arrays: frames [n][S][S][4] uint8, rot [n] (degrees, as stored), controllers [n][.] ->
+    dict(mu [n][Z], state [n][Z+2], out, throttle, steer [n] float32, alive [n] uint8).  into: such a dict to write into (with
+    skip_crashed the entries of crashed agents keep what it holds).  No GPU needed."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    encoder = np.ascontiguousarray(encoder, np.float32)
+    controllers = np.ascontiguousarray(controllers, np.float32)
+    rot = np.ascontiguousarray(rot, np.float32)
+    n, Z = frames.shape[0], cfg.latent
+    ne, nc = world_num_params(cfg)
+    assert frames.shape == (n, cfg.image_size, cfg.image_size, 4) and encoder.size == ne and controllers.size == n * nc and rot.size == n
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, np.uint8)
+    out = into if into is not None else dict(
+        mu=np.zeros((n, Z), np.float32), state=np.zeros((n, Z + 2), np.float32), out=np.zeros(n, np.float32),
+        throttle=np.zeros(n, np.float32), steer=np.zeros(n, np.float32), alive=np.zeros(n, np.uint8))
+    check(load().okenv_world_act_host(C.byref(cfg), ptr(encoder), ptr(controllers), n, ptr(frames), ptr(rot), ptr(crashed), ptr(out["mu"]),
+                                      ptr(out["state"]), ptr(out["out"]), ptr(out["throttle"]), ptr(out["steer"]), ptr(out["alive"])))
+    return out
+
+
+def world_score_host(cx, cy, w_left, w_right, x, y, crashed, timed_out, fitness):
+    """okenv_world_score_host: one okenv_world_score on host arrays; returns the new fitness [n].  No GPU needed."""
+    cx, cy, w_left, w_right, x, y = (np.ascontiguousarray(v, np.float32) for v in (cx, cy, w_left, w_right, x, y))
+    crashed, timed_out = np.ascontiguousarray(crashed, np.uint8), np.ascontiguousarray(timed_out, np.uint8)
+    fitness = np.array(fitness, np.float32)
+    assert cx.size == cy.size == w_left.size == w_right.size and x.size == y.size == crashed.size == timed_out.size == fitness.size
+    check(load().okenv_world_score_host(ptr(cx), ptr(cy), ptr(w_left), ptr(w_right), cx.size, x.size, ptr(x), ptr(y), ptr(crashed),
+                                        ptr(timed_out), ptr(fitness)))
+    return fitness
+
+
 # guided cost learning (include/okenv.h)
 GCL_POLICY,GCL_VALUE, GCL_COST = 0, 1, 2
 GCL_NETWORKS = {"policy": GCL_POLICY, "value": GCL_VALUE, "cost": GCL_COST}
@@ -1022,6 +1124,24 @@ def load(build_if_missing=True):
     L.okenv_cnn_act.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvCnnRecord)]
     L.okenv_debug_cnn_stages.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvCnnRecord), C.c_uint32]
     L.okenv_cnn_act_host.argtypes = [C.POINTER(OkenvCnnConfig), vp, i32, vp, vp, vp, vp, vp, vp]
+    L.okenv_world_lds_bytes.argtypes = [C.POINTER(OkenvWorldConfig)]
+    L.okenv_world_lds_bytes.restype = C.c_int64
+    L.okenv_world_plan.argtypes = [C.POINTER(OkenvWorldConfig), vp]
+    L.okenv_world_workspace_bytes.argtypes = [C.POINTER(OkenvWorldConfig), i32]
+    L.okenv_world_workspace_bytes.restype = C.c_int64
+    L.okenv_world_create.argtypes = [vp, C.POINTER(OkenvWorldConfig)]
+    L.okenv_world_num_params.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.okenv_world_set_params.argtypes = [vp, i32, vp]
+    L.okenv_world_get_params.argtypes = [vp, i32, vp]
+    L.okenv_world_act.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvWorldRecord)]
+    L.okenv_world_set_lane_widths.argtypes = [vp, vp, vp, i32]
+    L.okenv_world_score_begin.argtypes = [vp]
+    L.okenv_world_score.argtypes = [vp]
+    L.okenv_world_fitness.argtypes = [vp, vp]
+    L.okenv_world_fitness_device.argtypes = [vp, C.POINTER(vp)]
+    L.okenv_debug_world_stages.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvWorldRecord), C.c_uint32]
+    L.okenv_world_act_host.argtypes = [C.POINTER(OkenvWorldConfig), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.okenv_world_score_host.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

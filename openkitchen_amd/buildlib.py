@@ -24,7 +24,7 @@ CXX_SOURCES = [
 HEADERS = [
     os.path.join(CSRC, "ok_raycast.h"), os.path.join(CSRC, "ok_grid.h"), os.path.join(CSRC, "ok_render.h"), os.path.join(CSRC, "ok_expert.h"),
     os.path.join(CSRC, "ok_actor.h"), os.path.join(CSRC, "ok_batch.h"), os.path.join(CSRC, "ok_learn.h"),
-    os.path.join(CSRC, "ok_dqn.h"), os.path.join(CSRC, "ok_ddpg.h"), os.path.join(CSRC, "ok_reinforce.h"), os.path.join(CSRC, "ok_gauss.h"), os.path.join(CSRC, "ok_lidar.h"), os.path.join(CSRC, "ok_flow.h"), os.path.join(CSRC, "ok_bev.h"), os.path.join(CSRC, "ok_cnn.h"), os.path.join(CSRC, "okenv_kernels.h"),
+    os.path.join(CSRC, "ok_dqn.h"), os.path.join(CSRC, "ok_ddpg.h"), os.path.join(CSRC, "ok_reinforce.h"), os.path.join(CSRC, "ok_gauss.h"), os.path.join(CSRC, "ok_lidar.h"), os.path.join(CSRC, "ok_flow.h"), os.path.join(CSRC, "ok_bev.h"), os.path.join(CSRC, "ok_cnn.h"), os.path.join(CSRC, "ok_world.h"), os.path.join(CSRC, "okenv_kernels.h"),
     os.path.join(ROOT, "include", "okenv.h"), os.path.join(ROOT, "include", "okenv_math.h"),
     os.path.join(ROOT, "include", "okenv_batch.h"), os.path.join(ROOT, "include", "okenv_learn.h"),
     os.path.join(ROOT, "include", "okenv_dqn.h"), os.path.join(ROOT, "include", "okenv_ddpg.h"),
@@ -32,6 +32,7 @@ HEADERS = [
     os.path.join(ROOT, "include", "okenv_lidar.h"), os.path.join(ROOT, "include", "okenv_flow.h"),
     os.path.join(ROOT, "include", "okenv_bev.h"),
     os.path.join(ROOT, "include", "okenv_cnn.h"),
+    os.path.join(ROOT, "include", "okenv_world.h"),
 ]
 
 # -ffp-contract=off: crash/done flags must be bit-exact against the CPU oracle, and FMA contraction changes

@@ -35,6 +35,7 @@
 #include "ok_flow.h"
 #include "ok_bev.h"
 #include "ok_cnn.h"
+#include "ok_world.h"
 #include "ok_expert.h"
 
 namespace
@@ -593,6 +594,13 @@ struct okenv
     okenv_cnn_config        cnn{};
     float                  *d_cnn_pack{nullptr}, *d_cnn_feat{nullptr};
     size_t                  cnn_pack_cap{0}, cnn_feat_cap{0};
+    // World-model racers (okenv_world_create): the encoder vector in torch's order in world_drv.d; one workspace for everything else
+    // (okWorldPlaces: packed weights, controllers, activations, partial latents, fitness, list), allocated at create; the lane widths
+    OkDriver                world_drv;
+    okenv_world_config      world{};
+    float                  *d_world_ws{nullptr}, *d_world_widths{nullptr};
+    size_t                  world_ws_cap{0};
+    bool                    world_widths{false};
 };
 
 struct okenv_track
@@ -1467,7 +1475,8 @@ const DriverKind kActorDriver{&okenv::actor_drv, "okenv_actor_", "every attached
     kLidarDriver{&okenv::lidar_drv, "okenv_lidar_", "the policy needs its parameters", "the policy needs its parameters", true},
     kFlowDriver{&okenv::flow_drv, "okenv_flow_", "the policy needs its parameters", "the policy needs its parameters", true},
     kBevDriver{&okenv::bev_drv, "okenv_bev_", "the encoder needs its parameters", "the encoder needs its parameters", true},
-    kCnnDriver{&okenv::cnn_drv, "okenv_cnn_", "the policy needs its parameters", "the policy needs its parameters", true};
+    kCnnDriver{&okenv::cnn_drv, "okenv_cnn_", "the policy needs its parameters", "the policy needs its parameters", true},
+    kWorldDriver{&okenv::world_drv, "okenv_world_", "the encoder and the controllers need their parameters", "the vector needs its parameters", true};
 
 int driverRefuses(okenv *h, const int code, const DriverKind &k, const char *entry, const std::string &why)
 {
@@ -1711,6 +1720,93 @@ int cnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const oke
     {
         void (*const heads[kCnnMaxColTiles])(OkCnnActParams) = {okCnnHeadKernel<1>, okCnnHeadKernel<2>, okCnnHeadKernel<3>, okCnnHeadKernel<4>};
         return actLaunch(h, heads[pl.ct - 1], kCnnAgents, kCnnThreads, sizeof(float) * static_cast<size_t>(pl.head_end), p);
+    }
+    return OKENV_OK;
+}
+
+// okenv_world_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_WORLD_STAGE_*), in their order, on the stream.  Every
+// grid is sized for all N agents; workgroups past the list's end leave at once.
+int worldAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_world_record *rec, const unsigned stages)
+{
+    const char *missing = nullptr;
+    if (h != nullptr && h->world_drv.ok)
+    {
+        const int S = h->world.image_size;
+        if (!frames)
+            missing = "NULL argument";
+        else if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
+            missing = "frame_bytes is not num_agents x image_size x image_size x 4";
+        else if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
+            missing = "frames must be 4-byte aligned";
+    }
+    if (const int rc = actBegin(h, kWorldDriver, 3U, missing))
+        return rc;
+    const ok_world_shape  s  = okWorldShape(h->world);
+    const ok_world_layout at = ok_world_offsets(s);
+    const size_t          N  = static_cast<size_t>(h->shape.N);
+    const OkWorldPlaces   pl = okWorldPlaces(s, N);
+    float                *ws = h->d_world_ws;
+    int                  *list = reinterpret_cast<int *>(ws + pl.list), *count = reinterpret_cast<int *>(ws + pl.count);
+    if ((stages & OKENV_WORLD_STAGE_LIST) != 0U)
+    {
+        hipLaunchKernelGGL(okWorldListKernel, dim3(1), dim3(256), 0, h->stream, h->st.crashed, h->shape.N, h->world.skip_crashed, list, count);
+        OK_HIP(h, hipGetLastError());
+    }
+    for (int l = 0; l < 4; ++l)
+    {
+        if ((stages & (OKENV_WORLD_STAGE_CONV0 << l)) == 0U)
+            continue;
+        OkWorldConvJob j{};
+        j.frames = frames;
+        j.in     = l > 0 ? ws + pl.act[l - 1] : nullptr;
+        j.out    = ws + pl.act[l];
+        j.w      = ws + pl.pack[l];
+        j.bias   = h->world_drv.d + at.b[l];
+        j.list   = list;
+        j.count  = count;
+        j.S      = s.S >> l;
+        j.side   = ok_world_side(s, l);
+        j.Cin    = ok_world_cin(s, l);
+        j.Cout   = s.c[l];
+        const size_t rows = N * static_cast<size_t>(j.side) * j.side;
+        const dim3   grid(static_cast<unsigned>((rows + kWorldRows - 1) / kWorldRows), static_cast<unsigned>((j.Cout + kWorldCols - 1) / kWorldCols));
+        const size_t lds = sizeof(float) * kWorldRows * kWorldLda;
+        if (l == 0)
+            hipLaunchKernelGGL(okWorldConvKernel<true>, grid, dim3(kWorldThreads), lds, h->stream, j);
+        else
+            hipLaunchKernelGGL(okWorldConvKernel<false>, grid, dim3(kWorldThreads), lds, h->stream, j);
+        OK_HIP(h, hipGetLastError());
+    }
+    const int P = ok_world_side(s, 3) * ok_world_side(s, 3);
+    if ((stages & OKENV_WORLD_STAGE_LATENT) != 0U)
+    {
+        OkWorldLatentJob j{};
+        j.act3  = ws + pl.act[3];
+        j.w     = ws + pl.pack[4];
+        j.part  = ws + pl.part;
+        j.count = count;
+        j.P     = P;
+        j.C     = s.c[3];
+        j.Z     = s.Z;
+        const dim3 grid(static_cast<unsigned>((N + kWorldAgents - 1) / kWorldAgents), static_cast<unsigned>(P));
+        hipLaunchKernelGGL(okWorldLatentKernel, grid, dim3(64 * (s.Z / 16)), sizeof(float) * kWorldAgents * (s.c[3] + 2), h->stream, j);
+        OK_HIP(h, hipGetLastError());
+    }
+    if ((stages & OKENV_WORLD_STAGE_HEAD) != 0U)
+    {
+        OkWorldHeadParams p{};
+        p.st          = h->st;
+        p.s           = s;
+        p.enc         = h->world_drv.d;
+        p.ctrl        = ws + pl.ctrl;
+        p.part        = ws + pl.part;
+        p.list        = list;
+        p.count       = count;
+        p.throttle    = h->world.throttle;
+        p.steer_scale = h->world.steer_scale;
+        if (rec != nullptr)
+            p.rec = *rec;
+        return actLaunch(h, okWorldHeadKernel, kWorldHeadSlots, 64 * kWorldHeadSlots, 0, p);
     }
     return OKENV_OK;
 }
@@ -4634,6 +4730,200 @@ extern "C"
         if (!params || n < 0 || !frames)
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_cnn_act_host: bad argument");
         okCnnActHost(*config, params, n, frames, crashed, throttle, steer, out, alive);
+        return OKENV_OK;
+    }
+
+    // ---- World-model racers (ok_world.h) -------------------------------------------------------------------------------------------
+
+    int64_t okenv_world_lds_bytes(const okenv_world_config *config)
+    {
+        return config != nullptr ? static_cast<int64_t>(okWorldLdsBytes(okWorldShape(*config))) : 0;
+    }
+
+    int okenv_world_plan(const okenv_world_config *config, int32_t *plan)
+    {
+        if (const char *why = okWorldCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_world_plan: ") + why);
+        if (!plan)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_world_plan: bad argument");
+        okWorldPlan(okWorldShape(*config), plan);
+        return OKENV_OK;
+    }
+
+    int64_t okenv_world_workspace_bytes(const okenv_world_config *config, int32_t num_agents)
+    {
+        if (okWorldCheckConfig(config) != nullptr || num_agents < 1)
+            return 0;
+        const ok_world_shape s = okWorldShape(*config);
+        return static_cast<int64_t>(sizeof(float) * (okWorldPlaces(s, static_cast<size_t>(num_agents)).words + static_cast<size_t>(ok_world_offsets(s).total)));
+    }
+
+    int okenv_world_create(okenv_t h, const okenv_world_config *config)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kWorldDriver, "create", kGateHandle))
+            return rc;
+        if (const char *why = okWorldCheckConfig(config))
+            return driverRefuses(h, OKENV_ERR_INVALID, kWorldDriver, "create", why);
+        const ok_world_shape s = okWorldShape(*config);
+        // (the conv kernels' 16.5 KB and their row table fit the default limit; the latent kernel, up to 32.1 KB, has the limit raised)
+        if (const int rc = driverCreateFlat(h, kWorldDriver, static_cast<size_t>(ok_world_offsets(s).total), kernelOf(okWorldLatentKernel)))
+            return rc;
+        h->world_drv.ok     = false; // (until the workspace stands)
+        h->world_drv.set[1] = false;
+        const OkWorldPlaces pl = okWorldPlaces(s, static_cast<size_t>(h->shape.N));
+        if (pl.words > h->world_ws_cap)
+        {
+            h->world_ws_cap = 0; // (a failed allocation leaves none)
+            if (const int rc = regrow(h, {fresh(h->d_world_ws, pl.words)}))
+                return rc;
+            h->world_ws_cap = pl.words;
+        }
+        OK_HIP(h, hipMemsetAsync(h->d_world_ws + pl.fitness, 0, sizeof(float) * static_cast<size_t>(h->shape.N), h->stream));
+        h->world        = *config;
+        h->world_drv.ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_world_num_params(okenv_t h, int32_t *encoder, int32_t *controller)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kWorldDriver, "num_params", kGateArgFirst | kGateCreated, encoder != nullptr && controller != nullptr))
+            return rc;
+        const ok_world_shape s = okWorldShape(h->world);
+        *encoder               = ok_world_offsets(s).total;
+        *controller            = ok_world_controller_params(s);
+        return OKENV_OK;
+    }
+
+    int okenv_world_set_params(okenv_t h, int32_t which, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kWorldDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
+            return rc;
+        if (which != OKENV_WORLD_ENCODER && which != OKENV_WORLD_CONTROLLERS)
+            return driverRefuses(h, OKENV_ERR_INVALID, kWorldDriver, "set_params", "which must be OKENV_WORLD_ENCODER or OKENV_WORLD_CONTROLLERS");
+        const ok_world_shape s  = okWorldShape(h->world);
+        const OkWorldPlaces  pl = okWorldPlaces(s, static_cast<size_t>(h->shape.N));
+        if (which == OKENV_WORLD_CONTROLLERS)
+            return driverSet(h, kWorldDriver, {vectorOf(h->d_world_ws + pl.ctrl, params, h->shape.N * ok_world_controller_params(s), 1)});
+        if (const int rc = driverSet(h, kWorldDriver, {vectorOf(h->world_drv.d, params, ok_world_offsets(s).total)}))
+            return rc;
+        OkWorldPackParams p{};
+        p.s      = s;
+        p.params = h->world_drv.d;
+        p.pack   = h->d_world_ws;
+        hipLaunchKernelGGL(okWorldPackKernel, dim3(static_cast<unsigned>((pl.pack_total + 255) / 256)), dim3(256), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_world_get_params(okenv_t h, int32_t which, float *params)
+    {
+        OK_QUIESCE(h);
+        const bool controllers = which == OKENV_WORLD_CONTROLLERS;
+        if (const int rc = driverGate(h, kWorldDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, controllers ? 2U : 1U))
+            return rc;
+        if (which != OKENV_WORLD_ENCODER && !controllers)
+            return driverRefuses(h, OKENV_ERR_INVALID, kWorldDriver, "get_params", "which must be OKENV_WORLD_ENCODER or OKENV_WORLD_CONTROLLERS");
+        const ok_world_shape s = okWorldShape(h->world);
+        if (controllers)
+            return driverGet(h, {vectorOf(h->d_world_ws + okWorldPlaces(s, static_cast<size_t>(h->shape.N)).ctrl, params,
+                                          h->shape.N * ok_world_controller_params(s))});
+        return driverGet(h, {vectorOf(h->world_drv.d, params, ok_world_offsets(s).total)});
+    }
+
+    int okenv_world_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_world_record *rec)
+    {
+        OK_QUIESCE(h);
+        return worldAct(h, frames, frame_bytes, rec, ~0U);
+    }
+
+    int okenv_debug_world_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_world_record *rec, uint32_t stages)
+    {
+        OK_QUIESCE(h);
+        return worldAct(h, frames, frame_bytes, rec, stages);
+    }
+
+    int okenv_world_set_lane_widths(okenv_t h, const float *w_left, const float *w_right, int32_t num_points)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kWorldDriver, "set_lane_widths", kGateArgFirst | kGateCreated, w_left != nullptr && w_right != nullptr))
+            return rc;
+        if (num_points < 1 || num_points != h->P)
+            return driverRefuses(h, OKENV_ERR_INVALID, kWorldDriver, "set_lane_widths", "num_points is not the centre line's (okenv_set_centerline)");
+        h->world_widths = false;
+        if (const int rc = regrow(h, {fresh(h->d_world_widths, 2U * static_cast<size_t>(num_points))}))
+            return rc;
+        const size_t bytes = sizeof(float) * static_cast<size_t>(num_points);
+        int          rc    = copyAny(h, h->d_world_widths, w_left, bytes);
+        if (rc == OKENV_OK)
+            rc = copyAny(h, h->d_world_widths + num_points, w_right, bytes);
+        h->world_widths = rc == OKENV_OK;
+        return rc;
+    }
+
+    int okenv_world_score_begin(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kWorldDriver, "score_begin", kGateHandle | kGateCreated))
+            return rc;
+        const size_t at = okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).fitness;
+        OK_HIP(h, hipMemsetAsync(h->d_world_ws + at, 0, sizeof(float) * static_cast<size_t>(h->shape.N), h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_world_score(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kWorldDriver, "score", kGateHandle | kGateCreated))
+            return rc;
+        if (!h->world_widths || h->P < 1)
+            return driverRefuses(h, OKENV_ERR_STATE, kWorldDriver, "score", "call okenv_world_set_lane_widths first");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t at = okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).fitness;
+        hipLaunchKernelGGL(okWorldScoreKernel, dim3((h->shape.N + 255) / 256), dim3(256), 0, h->stream, h->st, h->shape.N, h->d_cx, h->d_cy,
+                           h->d_world_widths, h->d_world_widths + h->P, h->P, h->d_world_ws + at);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_world_fitness(okenv_t h, float *out)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kWorldDriver, "fitness", kGateArgFirst | kGateCreated, out != nullptr))
+            return rc;
+        const size_t at = okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).fitness;
+        return driverGet(h, {vectorOf(h->d_world_ws + at, out, h->shape.N)});
+    }
+
+    int okenv_world_fitness_device(okenv_t h, float **ptr)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kWorldDriver, "fitness_device", kGateArgFirst | kGateCreated, ptr != nullptr))
+            return rc;
+        *ptr = h->d_world_ws + okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).fitness;
+        return OKENV_OK;
+    }
+
+    int okenv_world_act_host(const okenv_world_config *config, const float *encoder, const float *controllers, int32_t n, const uint8_t *frames,
+                             const float *rot, const uint8_t *crashed, float *mu, float *state, float *out, float *throttle, float *steer,
+                             uint8_t *alive)
+    {
+        if (const char *why = okWorldCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_world_act_host: ") + why);
+        if (!encoder || !controllers || n < 0 || !frames || !rot)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_world_act_host: bad argument");
+        okWorldActHost(*config, encoder, controllers, n, frames, rot, crashed, mu, state, out, throttle, steer, alive);
+        return OKENV_OK;
+    }
+
+    int okenv_world_score_host(const float *cx, const float *cy, const float *w_left, const float *w_right, int32_t num_points, int32_t n,
+                               const float *x, const float *y, const uint8_t *crashed, const uint8_t *timed_out, float *fitness)
+    {
+        if (!cx || !cy || !w_left || !w_right || num_points < 1 || n < 0 || !x || !y || !crashed || !timed_out || !fitness)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_world_score_host: bad argument");
+        okWorldScoreHost(cx, cy, w_left, w_right, num_points, n, x, y, crashed, timed_out, fitness);
         return OKENV_OK;
     }
 

@@ -946,6 +946,75 @@ class BatchedEnvironment:
             rec = None if record is None else C.byref(capi.fill_pointers(capi.OkenvCnnRecord(), record, "record", sizes))
             capi.check(self._L.okenv_debug_cnn_stages(self._h, capi.ptr(frames), self.N * S * S * 4, rec, int(stages)), self._h)
 
+    # ---- world-model racers (include/okenv.h) --------------------------------------------------------------
+    def world_create(self, config=None, **members):
+        """Attaches the world-model racers (the reference's conv-VAE encoder and one controller per agent) to the handle; config: a
+        capi.world_config(...), or its members by name (the reference's shape and controls by default).  Returns (floats of the
+        encoder vector, floats of one agent's controller)."""
+        if config is None:
+            config = capi.world_config(**members)
+        capi.check(self._L.okenv_world_create(self._h, C.byref(config)), self._h)
+        self.world_config = config
+        return self.world_num_params()
+
+    def world_num_params(self):
+        return self._count("okenv_world_num_params", outs=2)
+
+    def _world_floats(self, which):
+        ne, nc = self.world_num_params()
+        return ne if capi.WORLD_VECTORS[which] == capi.WORLD_ENCODER else self.N * nc
+
+    def world_set_params(self, which, params):
+        """New parameters, which: "encoder" (the shared vector, capi.world_layout) or "controllers" ([N, controller], one row per
+        agent), from a float32 numpy array or a device tensor.  Enqueued on the handle's stream; the call waits for the stream when
+        it was handed a numpy array (which may be a temporary), not for a device tensor."""
+        self._set_params("okenv_world_set_params", (params,), (self._world_floats(which),), capi.WORLD_VECTORS[which])
+
+    def world_get_params(self, which, out=None):
+        """The vector `which` as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
+        return self._get_state("okenv_world_get_params", {"params": self._world_floats(which)}, None if out is None else {"params": out},
+                               lead=(capi.WORLD_VECTORS[which],))["params"]
+
+    def world_act(self, frames, record=None, stages=None):
+        """Every agent's action from its frame and its own controller, enqueued on the handle's stream without a synchronisation
+        (with skip_crashed: nothing is written for crashed agents).  frames: a device tensor / address of [N, S, S, 4] uint8.  record:
+        None, or a dict of device tensors / addresses under "mu" [N,Z], "state" [N,Z+2], "out" [N], "action" [N,2] float32 and "alive"
+        [N] uint8, each optional.  stages: None, or a mask of capi.WORLD_STAGE_* -- only those kernels (okenv_debug_world_stages)."""
+        S, Z = self.world_config.image_size, self.world_config.latent
+        sizes = record and {"mu": self.N * Z * 4, "state": self.N * (Z + 2) * 4, "out": self.N * 4, "action": self.N * 8, "alive": self.N}
+        if stages is None:
+            self._act("okenv_world_act", capi.OkenvWorldRecord, record, sizes, capi.ptr(frames), self.N * S * S * 4)
+        else:
+            rec = None if record is None else C.byref(capi.fill_pointers(capi.OkenvWorldRecord(), record, "record", sizes))
+            capi.check(self._L.okenv_debug_world_stages(self._h, capi.ptr(frames), self.N * S * S * 4, rec, int(stages)), self._h)
+
+    def world_set_lane_widths(self, w_left, w_right):
+        """The lane widths the score divides by (Track.wl / Track.wr), one pair per centre-line point."""
+        l, r = (np.ascontiguousarray(v, dtype=np.float32) for v in (w_left, w_right))
+        assert l.size == r.size
+        capi.check(self._L.okenv_world_set_lane_widths(self._h, capi.ptr(l), capi.ptr(r), l.size), self._h)
+        self.sync()  # the host arrays are temporaries
+
+    def world_score_begin(self):
+        capi.check(self._L.okenv_world_score_begin(self._h), self._h)
+
+    def world_score(self):
+        """One step of the reference's fitness (main.cpp:329-342) for every agent: one kernel on the handle's stream."""
+        capi.check(self._L.okenv_world_score(self._h), self._h)
+
+    def world_fitness(self, out=None):
+        """The fitness [N] as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
+        if out is None:
+            out = np.empty(self.N, dtype=np.float32)
+        capi.check(self._L.okenv_world_fitness(self._h, capi.ptr(out)), self._h)
+        return out
+
+    def world_fitness_device(self):
+        """The device address of the fitness [N] float32, valid until the next world_create."""
+        p = C.c_void_p()
+        capi.check(self._L.okenv_world_fitness_device(self._h, C.byref(p)), self._h)
+        return int(p.value)
+
     # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) -------------------------------------------------------
     def gcl_create(self, **config):
         """Attaches a GCL object (policy R -> H1 -> H2 -> 2 with log_std, value R -> H1 -> H2 -> 1, cost R + 2 -> C1 -> C2 -> 1) to the

@@ -615,6 +615,46 @@ class VectorEnvironment:
             raise ValueError("image_act(frames) needs a contiguous uint8 tensor of shape (%d, %d, %d, 4) on %s" % (self.num_envs, S, S, self.device))
         self.env.cnn_act(frames, record)
 
+    # ---- world-model racers (include/okenv.h) ------------------------------------------------------------------
+    def enable_world_racers(self, config, encoder_params, controllers=None):
+        """Attaches the reference's world-model racers (WorldModelVaeRnn: the conv-VAE encoder, one controller per agent) as a device
+        driver, with the track's lane widths for the score.  config: a capi.world_config(...) or a dict of its members; encoder_params:
+        the flat vector worldmodel.world_params_from_state_dict makes; controllers: [N, controller] or None (set_world_controllers
+        later, once per generation)."""
+        if isinstance(config, dict):
+            config = capi.world_config(**config)
+        self.env.world_create(config)
+        if torch.is_tensor(encoder_params):
+            encoder_params = encoder_params.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        self.env.world_set_params("encoder", encoder_params)
+        self._world_flat = encoder_params  # alive until the next hand-over: a tensor's copy is asynchronous
+        self.env.world_set_lane_widths(self.track.wl, self.track.wr)
+        self.world_config = config
+        if controllers is not None:
+            self.set_world_controllers(controllers)
+
+    def set_world_controllers(self, controllers):
+        """Every agent's controller, [N, controller] float32 (a numpy array or a tensor): one copy on the environment's stream."""
+        if torch.is_tensor(controllers):
+            controllers = controllers.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        self.env.world_set_params("controllers", controllers)
+        self._world_controllers = controllers
+
+    def world_act(self, frames, record=None):
+        """Every agent's action from `frames`, a contiguous uint8 tensor [N, S, S, 4] on this device (camera()'s, rendered at the
+        encoder's image_size), written into `throttle` / `steering` on the environment's stream, no synchronisation, usable inside
+        capture(body).  record: optional dict of device tensors ("mu" [N,Z], "state" [N,Z+2], "out" [N], "action" [N,2] float32,
+        "alive" [N] uint8)."""
+        S = self.world_config.image_size
+        if (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.device != self.device
+                or tuple(frames.shape) != (self.num_envs, S, S, 4)):
+            raise ValueError("world_act(frames) needs a contiguous uint8 tensor of shape (%d, %d, %d, 4) on %s" % (self.num_envs, S, S, self.device))
+        self.env.world_act(frames, record)
+
+    def world_fitness(self):
+        """The racers' fitness [N] as a float32 device tensor (a view of the handle's buffer; world_score() adds to it)."""
+        return torch.as_tensor(_DeviceArray(self.env.world_fitness_device(), (self.num_envs,), torch.float32, self.env), device=self.device)
+
     def nearest_track_idx(self):
         """RaceTrack::findNearestTrackIndexBruteForce for every agent, as a device tensor."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
