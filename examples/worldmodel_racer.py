@@ -6,12 +6,17 @@ to the lane centre -- with the encoder's forward once per step in PyTorch or, wi
     python examples/worldmodel_racer.py [--population 256] [--frame-size 128] [--base-ch 64] [--latent 32] [--demo-agents 64]
                                         [--demo-steps 64] [--epochs 2] [--generations 5] [--max-steps 400] [--graph-chunk 8]
                                         [--device-encoder] [--keep-crashed] [--track Silverstone]
+                                        [--memory] [--memory-hidden 64] [--memory-epochs 2] [--no-carry]
 
 1. record: every living agent's frame while the expert drives (demonstrations.collect_demonstrations(images=True));
 2. train: binary cross-entropy of the reconstruction plus the KL term, Adam 2e-4 (train_vae.py);
 3. generations: sample, one batched rollout (camera -> act -> step -> score, in graph chunks, until nobody is alive), tell
    (worldmodel.WorldModelRacers).  The reference evaluates its 30 candidates one after another.
 --frame-size is the encoder's image size, a multiple of 16 up to 128; the camera renders at it, there is no resize.
+
+With --memory the racer is the reference's Vision + Memory + Controller: between 2 and 3 the expert drives again, the latents come from
+the device encoder (worldmodel.collect_latents), the GRU dynamics model is trained on them with the reference's recipe
+(worldmodel.train_memory), and every candidate's controller reads [mu | h_top] (okenv_memory_act with --device-encoder).
 """
 import argparse
 import os
@@ -43,6 +48,13 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device-encoder", action="store_true")
     ap.add_argument("--keep-crashed", action="store_true", help="act for crashed candidates too (skip_crashed = 0)")
+    ap.add_argument("--memory", action="store_true", help="train the GRU dynamics model and feed the controllers [mu | h_top]")
+    ap.add_argument("--memory-hidden", type=int, default=64,
+                    help="the memory's width H.  The solver keeps a full covariance over a controller's parameters: H = 64 gives 1 697 of them; "
+                         "the reference's H = 512 gives 8 865, a 629 MB matrix -- the limit the reference's Readme names")
+    ap.add_argument("--memory-layers", type=int, default=wm.MEMORY_LAYERS)
+    ap.add_argument("--memory-epochs", type=int, default=2)
+    ap.add_argument("--no-carry", action="store_true", help="the reference as written: the hidden state starts from zero at every act")
     a = ap.parse_args(argv)
     torch.manual_seed(a.seed)
     # 1. frames
@@ -58,12 +70,25 @@ def main(argv=None):
     t0 = time.perf_counter()
     losses = wm.train_vae(model, frames, epochs=a.epochs, seed=a.seed)
     print("trained %d epochs in %.1f s: loss per frame %s" % (a.epochs, time.perf_counter() - t0, " ".join("%.5g" % v for v in losses)))
+    memory = memory_stats = memory_losses = None
+    if a.memory:  # 2b. the memory: the expert drives again, the latents come from the device encoder
+        model.eval()
+        sd = model.enc.state_dict()
+        venv.enable_world_racers(wm.world_config_from_state_dict(sd, a.frame_size), wm.world_params_from_state_dict(sd, a.frame_size).to(device))
+        venv.set_world_controllers(torch.zeros(a.demo_agents, venv.env.world_num_params()[1], device=device))
+        latents, actions, alive = wm.collect_latents(venv, a.demo_steps, drive=lambda v: v.expert_act())
+        memory = wm.GRUDynamics(a.latent, a.memory_hidden, a.memory_layers).to(device)
+        t0 = time.perf_counter()
+        memory_losses, memory_stats = wm.train_memory(memory, latents, actions, alive, epochs=a.memory_epochs, seed=a.seed)
+        print("trained the memory (H = %d, %d layers) %d epochs in %.1f s: loss %s"
+              % (a.memory_hidden, a.memory_layers, a.memory_epochs, time.perf_counter() - t0, " ".join("%.5g" % v for v in memory_losses)))
     venv.close()
     # 3. generations
     racers = wm.WorldModelRacers(a.track, a.population, model.enc, seed=a.seed, encoder="device" if a.device_encoder else "torch",
-                                 max_steps=a.max_steps, graph_chunk=a.graph_chunk, skip_crashed=not a.keep_crashed)
+                                 max_steps=a.max_steps, graph_chunk=a.graph_chunk, skip_crashed=not a.keep_crashed, memory=memory,
+                                 memory_stats=memory_stats, carry=not a.no_carry)
     first = None
-    if a.device_encoder:  # the first frames, both ways: the device's mu against the PyTorch module's
+    if a.device_encoder and not a.memory:  # the first frames, both ways: the device's mu against the PyTorch module's
         racers.venv.reset()
         frame = racers.venv.camera()
         racers.set_params(racers.solver.sample())
@@ -74,16 +99,19 @@ def main(argv=None):
         alive = ~racers.venv.done
         print("first step: max |device - PyTorch module| = %.4g on mu (up to %.3g in size)"
               % (float((first["mu"] - first["mu_torch"])[alive].abs().max()), float(first["mu_torch"].abs().max())))
-    best, means = [], [racers.solver.mean.copy()]
+    best, means, fitnesses, all_steps = [], [racers.solver.mean.copy()], [], []
     for g in range(a.generations):
         t0 = time.perf_counter()
         top, steps = racers.run_generation()
         dt = time.perf_counter() - t0
         best.append(top)
+        fitnesses.append(racers.fitness.copy())
+        all_steps.append(steps)
         means.append(racers.solver.mean.copy())
         print("generation %d: %d candidates, %d steps with the %s in %.3f s; best fitness %.3f, mean %.3f"
               % (g, a.population, steps, "device encoder" if a.device_encoder else "PyTorch encoder", dt, top, float(racers.fitness.mean())))
-    out = {"model": model, "config": racers.config, "first": first, "best": best, "fitness": racers.fitness, "means": means, "losses": losses}
+    out = {"model": model, "config": racers.config, "first": first, "best": best, "fitness": racers.fitness, "means": means, "losses": losses,
+           "memory": memory, "memory_stats": memory_stats, "memory_losses": memory_losses, "fitnesses": fitnesses, "steps": all_steps}
     print("fitness finite %s" % bool(torch.isfinite(torch.as_tensor(racers.fitness)).all()))
     racers.venv.close()
     return out

@@ -1219,6 +1219,87 @@ OKENV_API int okenv_world_act_host(const okenv_world_config *config, const float
 OKENV_API int okenv_world_score_host(const float *cx, const float *cy, const float *w_left, const float *w_right, int32_t num_points, int32_t n,
                                      const float *x, const float *y, const uint8_t *crashed, const uint8_t *timed_out, float *fitness);
 
+/* ---- World-model racers' memory -----------------------------------------------------------------------------
+ * The "M" of WorldModelVaeRnn's Vision + Memory + Controller: train_rnn.py's GRUDynamics (a stacked GRU on [z | a] with a linear head
+ * that predicts the next latent) and main.cpp's CmaEsAgent::runVaeRnn, whose controllers read [z_t | h_top].  It attaches to a handle
+ * that has okenv_world_create's racers and reuses their encoder, list and score; okenv_world_act itself is unchanged.  Every agent
+ * carries a hidden state [layers][hidden] in the handle, from act to act.  The rule is written out in include/okenv_memory.h
+ * (ok_memory_*), with its deliberate departures: the sums run in blocks of 64, the latent is mu, and `carry` chooses between the reference as
+ * written (0: every act starts from a zero state) and the memory its Readme describes (1).  Two parameter vectors: the network's, shared
+ * (ok_memory_offsets: torch's state_dict order of GRUDynamics, then z_mean, z_std, a_mean, a_std), and the controllers',
+ * [N][ok_controller_num_params(latent + hidden, ctrl_hidden, 1)].  Every value must be finite and every std > 0. */
+typedef struct okenv_memory_config {
+    int32_t hidden;      /* H: multiple of 16, 16 .. 512                        (the reference: 512)         */
+    int32_t layers;      /* L: 1 .. 4                                           (3)                          */
+    int32_t ctrl_hidden; /* the controller's: even, 2 .. 64                     (16)                         */
+    int32_t carry;       /* 1: the hidden state persists from act to act; 0: every act starts from zero      */
+    float   throttle;    /* the constant throttle_delta; finite                 (100)                        */
+    float   steer_scale; /* steering_delta per unit of the output; finite       (5)                          */
+} okenv_memory_config;
+
+/* What an act can leave behind for the caller, device pointers (okenv_memory_act_host: host pointers), each may be NULL */
+typedef struct okenv_memory_record {
+    float   *mu;         /* [N][Z]     the encoder's mu                                 */
+    float   *hidden;     /* [N][H]     the top layer's hidden state after the act       */
+    float   *prediction; /* [N][Z]     the head's next latent, denormalised             */
+    float   *state;      /* [N][Z + H] mu, h_top: the controller's input                */
+    float   *out;        /* [N]        the controller's output                          */
+    float   *action;     /* [N][2]     throttle_delta, steering_delta                   */
+    uint8_t *alive;      /* [N]        1 where the agent was not crashed                */
+} okenv_memory_record;
+
+/* LDS bytes of the largest memory kernel for the shape (`world` supplies the latent width): a pure host function.  0 for a NULL config
+ * or a shape outside the limits.  Always inside 160 KB. */
+OKENV_API int64_t okenv_memory_lds_bytes(const okenv_world_config *world, const okenv_memory_config *config);
+/* What names the kernels' paths for the shape: a pure host function.  plan [8]: the column blocks of a layer (32 hidden units a
+ * workgroup), the live column tiles of the last block (1 or 2), the K blocks of layer 0's input chain (64 k's a block) and the k's of the
+ * last one, the K blocks of a chain over the hidden width and the k's of the last one, whether the Whh pass runs (carry), and the layer
+ * kernel's launches. */
+OKENV_API int okenv_memory_plan(const okenv_world_config *world, const okenv_memory_config *config, int32_t *plan);
+/* Device bytes okenv_memory_create allocates for N agents (the network vector, its packed matrices, controllers, inputs, both hidden
+ * buffers). */
+OKENV_API int64_t okenv_memory_workspace_bytes(const okenv_world_config *world, const okenv_memory_config *config, int32_t num_agents);
+/* Attaches the memory to the handle's racers (replaces an earlier one: its parameters are forgotten) and zeroes every hidden state.  All
+ * device memory is allocated here.  OKENV_ERR_STATE before okenv_world_create; a later okenv_world_create detaches the memory.
+ * OKENV_ERR_INVALID for NULL arguments, a shape outside the limits, a carry other than 0 or 1 or a non-finite throttle or steer_scale. */
+OKENV_API int okenv_memory_create(okenv_t h, const okenv_memory_config *config);
+/* Floats of the network vector and of ONE agent's controller. */
+OKENV_API int okenv_memory_num_params(okenv_t h, int32_t *network, int32_t *controller);
+/* New parameters from a host or device pointer: `which` OKENV_MEMORY_NETWORK (the kernels' own copy of the matrices is made behind it
+ * on the stream) or OKENV_MEMORY_CONTROLLERS ([N][controller], one copy on the stream).  No synchronisation, so the values are not
+ * looked at: okenv_memory_act_host is where a non-finite value or a std <= 0 is refused. */
+#define OKENV_MEMORY_NETWORK 0
+#define OKENV_MEMORY_CONTROLLERS 1
+OKENV_API int okenv_memory_set_params(okenv_t h, int32_t which, const float *params);
+/* The parameters, in the same order, to a host or device pointer; synchronises. */
+OKENV_API int okenv_memory_get_params(okenv_t h, int32_t which, float *params);
+/* Zeroes every agent's hidden state: one kernel on the handle's stream, capturable. */
+OKENV_API int okenv_memory_reset(okenv_t h);
+/* Every agent's hidden state [N][layers][hidden] from / to a host or device pointer, for tests and checkpoints.  set: a copy on the
+ * stream, no synchronisation; get synchronises. */
+OKENV_API int okenv_memory_set_hidden(okenv_t h, const float *hidden);
+OKENV_API int okenv_memory_get_hidden(okenv_t h, float *hidden);
+/* Acts from frames as okenv_world_act does (same frames, same refusals): reads OKENV_F_THROTTLE / OKENV_F_STEER as the action of the
+ * step before, advances the hidden states, writes OKENV_F_THROTTLE, OKENV_F_STEER and the record (rec may be NULL), for every agent, or
+ * with the racers' skip_crashed for those not crashed (a crashed agent keeps its hidden state).  Kernels on the handle's stream only, no
+ * synchronisation, no allocation: capturable beside okenv_step, okenv_render_views and okenv_world_score.  OKENV_ERR_STATE before
+ * okenv_memory_create, before the racers' encoder is set or before both okenv_memory_set_params. */
+OKENV_API int okenv_memory_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_memory_record *rec);
+/* okenv_memory_act's kernels one by one, for measurement: only those named in `stages`, in their order (each reads what the one before
+ * left in the handle's buffers on an earlier call).  Refusals as okenv_memory_act's. */
+#define OKENV_MEMORY_STAGE_ENCODER 1u /* okenv_world_act's list, convolutions and latent kernels */
+#define OKENV_MEMORY_STAGE_INPUT 2u
+#define OKENV_MEMORY_STAGE_LAYER0 4u /* LAYER0 << l: layer l */
+#define OKENV_MEMORY_STAGE_HEAD 64u
+OKENV_API int okenv_debug_memory_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_memory_record *rec, uint32_t stages);
+/* The same rule on host arrays, no GPU needed: frames [n][S][S][4]; crashed [n] or NULL; hidden [n][layers][hidden], throttle and
+ * steer [n] in and out (the stored action in, the new one out); rec: HOST pointers or NULL.  world: the racers' config (its shape and
+ * skip_crashed; its hidden, throttle and steer_scale are not read).  With skip_crashed everything of a crashed agent is left as it is.
+ * Refuses a network vector with a non-finite value or a std <= 0. */
+OKENV_API int okenv_memory_act_host(const okenv_world_config *world, const okenv_memory_config *config, const float *encoder, const float *network,
+                                    const float *controllers, int32_t n, const uint8_t *frames, const uint8_t *crashed, float *hidden,
+                                    float *throttle, float *steer, const okenv_memory_record *rec);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.

@@ -110,6 +110,9 @@ SYMBOLS = [
     "okenv_world_set_params", "okenv_world_get_params", "okenv_world_act", "okenv_world_set_lane_widths", "okenv_world_score_begin",
     "okenv_world_score", "okenv_world_fitness", "okenv_world_fitness_device", "okenv_debug_world_stages", "okenv_world_act_host",
     "okenv_world_score_host",
+    "okenv_memory_lds_bytes", "okenv_memory_plan", "okenv_memory_workspace_bytes", "okenv_memory_create", "okenv_memory_num_params",
+    "okenv_memory_set_params", "okenv_memory_get_params", "okenv_memory_reset", "okenv_memory_set_hidden", "okenv_memory_get_hidden",
+    "okenv_memory_act", "okenv_debug_memory_stages", "okenv_memory_act_host",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -733,6 +736,95 @@ def world_score_host(cx, cy, w_left, w_right, x, y, crashed, timed_out, fitness)
     return fitness
 
 
+# the world-model racers' memory (include/okenv.h)
+MEMORY_NETWORK, MEMORY_CONTROLLERS = 0, 1
+MEMORY_VECTORS = {"network": MEMORY_NETWORK, "controllers": MEMORY_CONTROLLERS}
+MEMORY_STAGE_ENCODER, MEMORY_STAGE_INPUT, MEMORY_STAGE_LAYER0, MEMORY_STAGE_HEAD = 1, 2, 4, 64  # LAYER0 << l: layer l
+MEMORY_COLS, MEMORY_CHUNK, MEMORY_ROWS = 32, 64, 128  # hidden units and list slots per workgroup, k's per K block (ok_memory.h)
+MEMORY_RECORD = ("mu", "hidden", "prediction", "state", "out", "action", "alive")
+
+
+class OkenvMemoryConfig(C.Structure):
+    _fields_ = [("hidden", C.c_int32), ("layers", C.c_int32), ("ctrl_hidden", C.c_int32), ("carry", C.c_int32), ("throttle", C.c_float),
+                ("steer_scale", C.c_float)]
+
+
+class OkenvMemoryRecord(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in MEMORY_RECORD]
+
+
+def memory_config(hidden=512, layers=3, ctrl_hidden=16, carry=1, throttle=100.0, steer_scale=5.0):
+    """okenv_memory_config with the reference's shape and controls as defaults (WorldModelVaeRnn: train_rnn.py's defaults, main.cpp);
+    carry=0 is the reference as written (every act starts from a zero hidden state)."""
+    return OkenvMemoryConfig(int(hidden), int(layers), int(ctrl_hidden), int(carry), float(throttle), float(steer_scale))
+
+
+def memory_layout(world, cfg):
+    """ok_memory_offsets: where every piece of the network vector begins, as (name, offset, shape) in order: the state-dict keys of
+    worldmodel.GRUDynamics, then the statistics z_mean, z_std, a_mean, a_std.  The last entry's end is the vector's length."""
+    Z, H = world.latent, cfg.hidden
+    pieces = []
+    for l in range(cfg.layers):
+        pieces += [("gru.weight_ih_l%d" % l, (3 * H, Z + 2 if l == 0 else H)), ("gru.weight_hh_l%d" % l, (3 * H, H)),
+                   ("gru.bias_ih_l%d" % l, (3 * H,)), ("gru.bias_hh_l%d" % l, (3 * H,))]
+    pieces += [("head.weight", (Z, H)), ("head.bias", (Z,)), ("z_mean", (Z,)), ("z_std", (Z,)), ("a_mean", (2,)), ("a_std", (2,))]
+    out, at = [], 0
+    for name, shape in pieces:
+        out.append((name, at, shape))
+        at += int(np.prod(shape))
+    return out
+
+
+def memory_num_params(world, cfg):
+    """(floats of the network vector, floats of one agent's controller: ok_controller_num_params(latent + hidden, ctrl_hidden, 1))."""
+    name, at, shape = memory_layout(world, cfg)[-1]
+    i, h = world.latent + cfg.hidden, cfg.ctrl_hidden
+    return at + int(np.prod(shape)), h * i + h + (h // 2) * h + h // 2 + h // 2 + 1
+
+
+def memory_lds_bytes(world, cfg):
+    """okenv_memory_lds_bytes: the layer kernel's LDS, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_memory_lds_bytes(C.byref(world), C.byref(cfg)))
+
+
+def memory_plan(world, cfg):
+    """okenv_memory_plan: (column blocks of a layer, live column tiles of the last, K blocks of layer 0's input, k's of the last, K blocks
+    of a chain over the hidden width, k's of the last, carry, layers).  No GPU needed."""
+    out = (C.c_int32 * 8)()
+    check(load().okenv_memory_plan(C.byref(world), C.byref(cfg), out))
+    return tuple(int(v) for v in out)
+
+
+def memory_workspace_bytes(world, cfg, num_agents):
+    """okenv_memory_workspace_bytes: device bytes okenv_memory_create allocates for num_agents; 0 for a refused shape."""
+    return int(load().okenv_memory_workspace_bytes(C.byref(world), C.byref(cfg), int(num_agents)))
+
+
+def memory_act_host(world, cfg, encoder, network, controllers, frames, hidden, throttle, steer, crashed=None, into=None):
+    """okenv_memory_act_host on numpy arrays: frames [n][S][S][4] uint8, hidden [n][L][H], throttle and steer [n] (the stored action) ->
+    dict of the record's members (capi.MEMORY_RECORD) plus "hidden_state" [n][L][H], "throttle" and "steer" [n], the new ones; the
+    arguments are not written.  into: such a dict to write into (with skip_crashed the entries of crashed agents keep what it holds;
+    its hidden_state, throttle and steer are then the inputs too).  No GPU needed."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    encoder, network, controllers = (np.ascontiguousarray(v, np.float32) for v in (encoder, network, controllers))
+    n, Z, H, L = frames.shape[0], world.latent, cfg.hidden, cfg.layers
+    nn, nc = memory_num_params(world, cfg)
+    assert frames.shape == (n, world.image_size, world.image_size, 4) and encoder.size == world_num_params(world)[0]
+    assert network.size == nn and controllers.size == n * nc
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, np.uint8)
+    if into is None:
+        out = dict(mu=np.zeros((n, Z), np.float32), hidden=np.zeros((n, H), np.float32), prediction=np.zeros((n, Z), np.float32),
+                   state=np.zeros((n, Z + H), np.float32), out=np.zeros(n, np.float32), action=np.zeros((n, 2), np.float32),
+                   alive=np.zeros(n, np.uint8), hidden_state=np.array(hidden, np.float32).reshape(n, L, H),
+                   throttle=np.array(throttle, np.float32).reshape(n), steer=np.array(steer, np.float32).reshape(n))
+    else:
+        out = into
+    rec = fill_pointers(OkenvMemoryRecord(), {k: out.get(k) for k in MEMORY_RECORD}, "record")
+    check(load().okenv_memory_act_host(C.byref(world), C.byref(cfg), ptr(encoder), ptr(network), ptr(controllers), n, ptr(frames), ptr(crashed),
+                                       ptr(out["hidden_state"]), ptr(out["throttle"]), ptr(out["steer"]), C.byref(rec)))
+    return out
+
+
 # guided cost learning (include/okenv.h)
 GCL_POLICY,GCL_VALUE, GCL_COST = 0, 1, 2
 GCL_NETWORKS = {"policy": GCL_POLICY, "value": GCL_VALUE, "cost": GCL_COST}
@@ -1142,6 +1234,22 @@ def load(build_if_missing=True):
     L.okenv_debug_world_stages.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvWorldRecord), C.c_uint32]
     L.okenv_world_act_host.argtypes = [C.POINTER(OkenvWorldConfig), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.okenv_world_score_host.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    wc, mc = C.POINTER(OkenvWorldConfig), C.POINTER(OkenvMemoryConfig)
+    L.okenv_memory_lds_bytes.argtypes = [wc, mc]
+    L.okenv_memory_lds_bytes.restype = C.c_int64
+    L.okenv_memory_plan.argtypes = [wc, mc, vp]
+    L.okenv_memory_workspace_bytes.argtypes = [wc, mc, i32]
+    L.okenv_memory_workspace_bytes.restype = C.c_int64
+    L.okenv_memory_create.argtypes = [vp, mc]
+    L.okenv_memory_num_params.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.okenv_memory_set_params.argtypes = [vp, i32, vp]
+    L.okenv_memory_get_params.argtypes = [vp, i32, vp]
+    L.okenv_memory_reset.argtypes = [vp]
+    L.okenv_memory_set_hidden.argtypes = [vp, vp]
+    L.okenv_memory_get_hidden.argtypes = [vp, vp]
+    L.okenv_memory_act.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvMemoryRecord)]
+    L.okenv_debug_memory_stages.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvMemoryRecord), C.c_uint32]
+    L.okenv_memory_act_host.argtypes = [wc, mc, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(OkenvMemoryRecord)]
     _lib = L
     return L
 

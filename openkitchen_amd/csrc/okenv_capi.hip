@@ -36,6 +36,7 @@
 #include "ok_bev.h"
 #include "ok_cnn.h"
 #include "ok_world.h"
+#include "ok_memory.h"
 #include "ok_expert.h"
 
 namespace
@@ -601,6 +602,12 @@ struct okenv
     float                  *d_world_ws{nullptr}, *d_world_widths{nullptr};
     size_t                  world_ws_cap{0};
     bool                    world_widths{false};
+    // The racers' memory (okenv_memory_create): the network vector in torch's order in mem_drv.d; one workspace for everything else
+    // (okMemoryPlaces: packed matrices, controllers, mu, x0 and the two hidden buffers), allocated at create
+    OkDriver                mem_drv;
+    okenv_memory_config     mem{};
+    float                  *d_mem_ws{nullptr};
+    size_t                  mem_ws_cap{0};
 };
 
 struct okenv_track
@@ -1476,7 +1483,8 @@ const DriverKind kActorDriver{&okenv::actor_drv, "okenv_actor_", "every attached
     kFlowDriver{&okenv::flow_drv, "okenv_flow_", "the policy needs its parameters", "the policy needs its parameters", true},
     kBevDriver{&okenv::bev_drv, "okenv_bev_", "the encoder needs its parameters", "the encoder needs its parameters", true},
     kCnnDriver{&okenv::cnn_drv, "okenv_cnn_", "the policy needs its parameters", "the policy needs its parameters", true},
-    kWorldDriver{&okenv::world_drv, "okenv_world_", "the encoder and the controllers need their parameters", "the vector needs its parameters", true};
+    kWorldDriver{&okenv::world_drv, "okenv_world_", "the encoder and the controllers need their parameters", "the vector needs its parameters", true},
+    kMemoryDriver{&okenv::mem_drv, "okenv_memory_", "the network and the controllers need their parameters", "the vector needs its parameters", true};
 
 int driverRefuses(okenv *h, const int code, const DriverKind &k, const char *entry, const std::string &why)
 {
@@ -1726,6 +1734,8 @@ int cnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const oke
 
 // okenv_world_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_WORLD_STAGE_*), in their order, on the stream.  Every
 // grid is sized for all N agents; workgroups past the list's end leave at once.
+int worldKernels(okenv *h, const uint8_t *frames, const okenv_world_record *rec, unsigned stages);
+
 int worldAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_world_record *rec, const unsigned stages)
 {
     const char *missing = nullptr;
@@ -1741,6 +1751,12 @@ int worldAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const o
     }
     if (const int rc = actBegin(h, kWorldDriver, 3U, missing))
         return rc;
+    return worldKernels(h, frames, rec, stages);
+}
+
+// ... and its launches, which okenv_memory_act shares up to the head
+int worldKernels(okenv *h, const uint8_t *frames, const okenv_world_record *rec, const unsigned stages)
+{
     const ok_world_shape  s  = okWorldShape(h->world);
     const ok_world_layout at = ok_world_offsets(s);
     const size_t          N  = static_cast<size_t>(h->shape.N);
@@ -1807,6 +1823,111 @@ int worldAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const o
         if (rec != nullptr)
             p.rec = *rec;
         return actLaunch(h, okWorldHeadKernel, kWorldHeadSlots, 64 * kWorldHeadSlots, 0, p);
+    }
+    return OKENV_OK;
+}
+
+ok_memory_shape memoryShape(const okenv *h)
+{
+    return okMemoryShape(h->world, h->mem);
+}
+
+// okenv_memory_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_MEMORY_STAGE_*), in their order, on the stream.  The
+// encoder is okenv_world_act's own launches (worldAct without its head); every grid behind it is sized for all N agents as well.
+int memoryAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_memory_record *rec, const unsigned stages)
+{
+    const char *missing = nullptr;
+    if (h != nullptr && h->mem_drv.ok)
+    {
+        const int S = h->world.image_size;
+        if (!h->world_drv.ok || !h->world_drv.set[0])
+            return driverRefuses(h, OKENV_ERR_STATE, kMemoryDriver, "act", "call okenv_world_set_params first (the encoder needs its parameters)");
+        if (!frames)
+            missing = "NULL argument";
+        else if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
+            missing = "frame_bytes is not num_agents x image_size x image_size x 4";
+        else if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
+            missing = "frames must be 4-byte aligned";
+    }
+    if (const int rc = actBegin(h, kMemoryDriver, 3U, missing))
+        return rc;
+    const ok_world_shape   w   = okWorldShape(h->world);
+    const ok_memory_shape  s   = memoryShape(h);
+    const ok_world_layout  wat = ok_world_offsets(w);
+    const ok_memory_layout at  = ok_memory_offsets(s);
+    const size_t           N   = static_cast<size_t>(h->shape.N);
+    const OkWorldPlaces    wpl = okWorldPlaces(w, N);
+    const OkMemoryPlaces   pl  = okMemoryPlaces(s, N);
+    float                 *ws = h->d_mem_ws, *net = h->mem_drv.d;
+    const int             *list = reinterpret_cast<const int *>(h->d_world_ws + wpl.list), *count = reinterpret_cast<const int *>(h->d_world_ws + wpl.count);
+    if ((stages & OKENV_MEMORY_STAGE_ENCODER) != 0U)
+    {
+        // (the racers' own controllers are not read: only their encoder must be set)
+        if (const int rc = worldKernels(h, frames, nullptr, ~static_cast<unsigned>(OKENV_WORLD_STAGE_HEAD)))
+            return rc;
+    }
+    const int LH = s.L * s.H;
+    if ((stages & OKENV_MEMORY_STAGE_INPUT) != 0U)
+    {
+        OkMemoryInputJob j{};
+        j.st       = h->st;
+        j.enc_bias = h->world_drv.d + wat.mb;
+        j.part     = h->d_world_ws + wpl.part;
+        j.z_mean   = net + at.z_mean;
+        j.z_std    = net + at.z_std;
+        j.a_mean   = net + at.a_mean;
+        j.a_std    = net + at.a_std;
+        j.mu       = ws + pl.mu;
+        j.x0       = ws + pl.x0;
+        j.list     = list;
+        j.count    = count;
+        j.Z        = s.Z;
+        j.P        = ok_world_side(w, 3) * ok_world_side(w, 3);
+        const size_t threads = N * static_cast<size_t>(s.Z + OK_MEMORY_ACTIONS);
+        hipLaunchKernelGGL(okMemoryInputKernel, dim3(static_cast<unsigned>((threads + 255U) / 256U)), dim3(256), 0, h->stream, j);
+        OK_HIP(h, hipGetLastError());
+    }
+    for (int l = 0; l < s.L; ++l)
+    {
+        if ((stages & (OKENV_MEMORY_STAGE_LAYER0 << l)) == 0U)
+            continue;
+        OkMemoryLayerJob j{};
+        j.x       = l == 0 ? ws + pl.x0 : ws + pl.fresh + static_cast<size_t>(l - 1) * s.H;
+        j.x_pitch = l == 0 ? okMemoryPitch(s) : LH;
+        j.Kin     = okMemoryKin(s, l);
+        j.hidden  = ws + pl.hidden + static_cast<size_t>(l) * s.H;
+        j.fresh   = ws + pl.fresh + static_cast<size_t>(l) * s.H;
+        j.wih     = ws + pl.ih[l];
+        j.whh     = ws + pl.hh[l];
+        j.tail    = l == 0 ? net + at.wih[0] : nullptr;
+        j.bih     = net + at.bih[l];
+        j.bhh     = net + at.bhh[l];
+        j.list    = list;
+        j.count   = count;
+        j.H       = s.H;
+        j.LH      = LH;
+        j.carry   = s.carry;
+        const dim3 grid(static_cast<unsigned>((N + kMemRows - 1) / kMemRows), static_cast<unsigned>((s.H + kMemCols - 1) / kMemCols));
+        hipLaunchKernelGGL(okMemoryLayerKernel, grid, dim3(kMemThreads), okMemoryLdsBytes(s), h->stream, j);
+        OK_HIP(h, hipGetLastError());
+    }
+    if ((stages & OKENV_MEMORY_STAGE_HEAD) != 0U)
+    {
+        OkMemoryHeadParams p{};
+        p.st          = h->st;
+        p.s           = s;
+        p.net         = net;
+        p.ctrl        = ws + pl.ctrl;
+        p.mu          = ws + pl.mu;
+        p.fresh       = ws + pl.fresh;
+        p.hidden      = ws + pl.hidden;
+        p.list        = list;
+        p.count       = count;
+        p.throttle    = h->mem.throttle;
+        p.steer_scale = h->mem.steer_scale;
+        if (rec != nullptr)
+            p.rec = *rec;
+        return actLaunch(h, okMemoryHeadKernel, kMemHeadSlots, 64 * kMemHeadSlots, 0, p);
     }
     return OKENV_OK;
 }
@@ -4766,6 +4887,7 @@ extern "C"
         if (const char *why = okWorldCheckConfig(config))
             return driverRefuses(h, OKENV_ERR_INVALID, kWorldDriver, "create", why);
         const ok_world_shape s = okWorldShape(*config);
+        h->mem_drv.ok          = false; // (a memory belongs to the racers it was created on: okenv_memory_create attaches a new one)
         // (the conv kernels' 16.5 KB and their row table fit the default limit; the latent kernel, up to 32.1 KB, has the limit raised)
         if (const int rc = driverCreateFlat(h, kWorldDriver, static_cast<size_t>(ok_world_offsets(s).total), kernelOf(okWorldLatentKernel)))
             return rc;
@@ -4924,6 +5046,174 @@ extern "C"
         if (!cx || !cy || !w_left || !w_right || num_points < 1 || n < 0 || !x || !y || !crashed || !timed_out || !fitness)
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_world_score_host: bad argument");
         okWorldScoreHost(cx, cy, w_left, w_right, num_points, n, x, y, crashed, timed_out, fitness);
+        return OKENV_OK;
+    }
+
+    // ---- The racers' memory (ok_memory.h) -----------------------------------------------------------------------------------------
+
+    int64_t okenv_memory_lds_bytes(const okenv_world_config *world, const okenv_memory_config *config)
+    {
+        return okMemoryCheckConfig(world, config) == nullptr ? static_cast<int64_t>(okMemoryLdsBytes(okMemoryShape(*world, *config))) : 0;
+    }
+
+    int okenv_memory_plan(const okenv_world_config *world, const okenv_memory_config *config, int32_t *plan)
+    {
+        if (const char *why = okMemoryCheckConfig(world, config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_memory_plan: ") + why);
+        if (!plan)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_plan: bad argument");
+        okMemoryPlan(okMemoryShape(*world, *config), plan);
+        return OKENV_OK;
+    }
+
+    int64_t okenv_memory_workspace_bytes(const okenv_world_config *world, const okenv_memory_config *config, int32_t num_agents)
+    {
+        if (okMemoryCheckConfig(world, config) != nullptr || num_agents < 1)
+            return 0;
+        const ok_memory_shape s = okMemoryShape(*world, *config);
+        return static_cast<int64_t>(sizeof(float) * (okMemoryPlaces(s, static_cast<size_t>(num_agents)).words + static_cast<size_t>(ok_memory_offsets(s).total)));
+    }
+
+    int okenv_memory_create(okenv_t h, const okenv_memory_config *config)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kMemoryDriver, "create", kGateHandle))
+            return rc;
+        if (!h->world_drv.ok)
+            return driverRefuses(h, OKENV_ERR_STATE, kMemoryDriver, "create", "call okenv_world_create first");
+        if (const char *why = okMemoryCheckConfig(&h->world, config))
+            return driverRefuses(h, OKENV_ERR_INVALID, kMemoryDriver, "create", why);
+        const ok_memory_shape s = okMemoryShape(h->world, *config);
+        if (const int rc = driverCreateFlat(h, kMemoryDriver, static_cast<size_t>(ok_memory_offsets(s).total), kernelOf(okMemoryLayerKernel)))
+            return rc;
+        h->mem_drv.ok     = false; // (until the workspace stands)
+        h->mem_drv.set[1] = false;
+        const OkMemoryPlaces pl = okMemoryPlaces(s, static_cast<size_t>(h->shape.N));
+        if (pl.words > h->mem_ws_cap)
+        {
+            h->mem_ws_cap = 0; // (a failed allocation leaves none)
+            if (const int rc = regrow(h, {fresh(h->d_mem_ws, pl.words)}))
+                return rc;
+            h->mem_ws_cap = pl.words;
+        }
+        OK_HIP(h, hipMemsetAsync(h->d_mem_ws + pl.hidden, 0, sizeof(float) * static_cast<size_t>(h->shape.N) * s.L * s.H, h->stream));
+        h->mem        = *config;
+        h->mem_drv.ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_memory_num_params(okenv_t h, int32_t *network, int32_t *controller)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kMemoryDriver, "num_params", kGateArgFirst | kGateCreated, network != nullptr && controller != nullptr))
+            return rc;
+        const ok_memory_shape s = memoryShape(h);
+        *network                = ok_memory_offsets(s).total;
+        *controller             = ok_memory_controller_params(s);
+        return OKENV_OK;
+    }
+
+    int okenv_memory_set_params(okenv_t h, int32_t which, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kMemoryDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
+            return rc;
+        if (which != OKENV_MEMORY_NETWORK && which != OKENV_MEMORY_CONTROLLERS)
+            return driverRefuses(h, OKENV_ERR_INVALID, kMemoryDriver, "set_params", "which must be OKENV_MEMORY_NETWORK or OKENV_MEMORY_CONTROLLERS");
+        const ok_memory_shape  s  = memoryShape(h);
+        const OkMemoryPlaces   pl = okMemoryPlaces(s, static_cast<size_t>(h->shape.N));
+        const ok_memory_layout at = ok_memory_offsets(s);
+        if (which == OKENV_MEMORY_CONTROLLERS)
+            return driverSet(h, kMemoryDriver, {vectorOf(h->d_mem_ws + pl.ctrl, params, h->shape.N * ok_memory_controller_params(s), 1)});
+        if (const int rc = driverSet(h, kMemoryDriver, {vectorOf(h->mem_drv.d, params, at.total)}))
+            return rc;
+        for (int m = 0; m < 2 * s.L; ++m)
+        {
+            const int       l = m / 2;
+            OkMemoryPackJob j{};
+            j.cols   = 3 * s.H;
+            j.K      = m % 2 == 0 ? okMemoryKin(s, l) : s.H;
+            j.stride = m % 2 == 0 ? ok_memory_in(s, l) : s.H;
+            j.src    = h->mem_drv.d + (m % 2 == 0 ? at.wih[l] : at.whh[l]);
+            j.dst    = h->d_mem_ws + (m % 2 == 0 ? pl.ih[l] : pl.hh[l]);
+            hipLaunchKernelGGL(okMemoryPackKernel, dim3(static_cast<unsigned>((j.cols * j.K + 255) / 256)), dim3(256), 0, h->stream, j);
+            OK_HIP(h, hipGetLastError());
+        }
+        return OKENV_OK;
+    }
+
+    int okenv_memory_get_params(okenv_t h, int32_t which, float *params)
+    {
+        OK_QUIESCE(h);
+        const bool controllers = which == OKENV_MEMORY_CONTROLLERS;
+        if (const int rc = driverGate(h, kMemoryDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, controllers ? 2U : 1U))
+            return rc;
+        if (which != OKENV_MEMORY_NETWORK && !controllers)
+            return driverRefuses(h, OKENV_ERR_INVALID, kMemoryDriver, "get_params", "which must be OKENV_MEMORY_NETWORK or OKENV_MEMORY_CONTROLLERS");
+        const ok_memory_shape s = memoryShape(h);
+        if (controllers)
+            return driverGet(h, {vectorOf(h->d_mem_ws + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).ctrl, params,
+                                          h->shape.N * ok_memory_controller_params(s))});
+        return driverGet(h, {vectorOf(h->mem_drv.d, params, ok_memory_offsets(s).total)});
+    }
+
+    int okenv_memory_reset(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kMemoryDriver, "reset", kGateHandle | kGateCreated))
+            return rc;
+        OK_HIP(h, hipSetDevice(h->device));
+        const ok_memory_shape s     = memoryShape(h);
+        const long            words = static_cast<long>(h->shape.N) * s.L * s.H;
+        hipLaunchKernelGGL(okMemoryResetKernel, dim3(static_cast<unsigned>((words + 255) / 256)), dim3(256), 0, h->stream,
+                           h->d_mem_ws + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).hidden, words);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_memory_set_hidden(okenv_t h, const float *hidden)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kMemoryDriver, "set_hidden", kGateArgFirst | kGateCreated, hidden != nullptr))
+            return rc;
+        OK_HIP(h, hipSetDevice(h->device));
+        const ok_memory_shape s = memoryShape(h);
+        return copyAny(h, h->d_mem_ws + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).hidden, hidden,
+                       sizeof(float) * static_cast<size_t>(h->shape.N) * s.L * s.H);
+    }
+
+    int okenv_memory_get_hidden(okenv_t h, float *hidden)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kMemoryDriver, "get_hidden", kGateArgFirst | kGateCreated, hidden != nullptr))
+            return rc;
+        const ok_memory_shape s = memoryShape(h);
+        return driverGet(h, {vectorOf(h->d_mem_ws + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).hidden, hidden, h->shape.N * s.L * s.H)});
+    }
+
+    int okenv_memory_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_memory_record *rec)
+    {
+        OK_QUIESCE(h);
+        return memoryAct(h, frames, frame_bytes, rec, ~0U);
+    }
+
+    int okenv_debug_memory_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_memory_record *rec, uint32_t stages)
+    {
+        OK_QUIESCE(h);
+        return memoryAct(h, frames, frame_bytes, rec, stages);
+    }
+
+    int okenv_memory_act_host(const okenv_world_config *world, const okenv_memory_config *config, const float *encoder, const float *network,
+                              const float *controllers, int32_t n, const uint8_t *frames, const uint8_t *crashed, float *hidden, float *throttle,
+                              float *steer, const okenv_memory_record *rec)
+    {
+        if (const char *why = okMemoryCheckConfig(world, config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_memory_act_host: ") + why);
+        if (!encoder || !network || !controllers || n < 0 || !frames || !hidden || !throttle || !steer)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_act_host: bad argument");
+        if (ok_memory_params_bad(okMemoryShape(*world, *config), network))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_act_host: the network vector holds a non-finite value or a std that is not > 0");
+        okMemoryActHost(*world, *config, encoder, network, controllers, n, frames, crashed, hidden, throttle, steer, rec != nullptr ? *rec : okenv_memory_record{});
         return OKENV_OK;
     }
 

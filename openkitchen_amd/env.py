@@ -1015,6 +1015,66 @@ class BatchedEnvironment:
         capi.check(self._L.okenv_world_fitness_device(self._h, C.byref(p)), self._h)
         return int(p.value)
 
+    # ---- the racers' memory (include/okenv.h) ---------------------------------------------------------------
+    def memory_create(self, config=None, **members):
+        """Attaches the memory (the reference's GRUDynamics and one [mu | h_top] controller per agent) to the handle's world-model
+        racers and zeroes every hidden state; config: a capi.memory_config(...), or its members by name.  Returns (floats of the
+        network vector, floats of one agent's controller)."""
+        if config is None:
+            config = capi.memory_config(**members)
+        capi.check(self._L.okenv_memory_create(self._h, C.byref(config)), self._h)
+        self.memory_config = config
+        return self.memory_num_params()
+
+    def memory_num_params(self):
+        return self._count("okenv_memory_num_params", outs=2)
+
+    def _memory_floats(self, which):
+        nn, nc = self.memory_num_params()
+        return nn if capi.MEMORY_VECTORS[which] == capi.MEMORY_NETWORK else self.N * nc
+
+    def memory_set_params(self, which, params):
+        """New parameters, which: "network" (the shared vector, capi.memory_layout) or "controllers" ([N, controller]), from a float32
+        numpy array or a device tensor; waits for the stream only when it was handed a numpy array."""
+        self._set_params("okenv_memory_set_params", (params,), (self._memory_floats(which),), capi.MEMORY_VECTORS[which])
+
+    def memory_get_params(self, which, out=None):
+        """The vector `which` as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
+        return self._get_state("okenv_memory_get_params", {"params": self._memory_floats(which)}, None if out is None else {"params": out},
+                               lead=(capi.MEMORY_VECTORS[which],))["params"]
+
+    def memory_reset(self):
+        """Zeroes every agent's hidden state: one kernel on the handle's stream."""
+        capi.check(self._L.okenv_memory_reset(self._h), self._h)
+
+    def _memory_hidden_floats(self):
+        return self.N * self.memory_config.layers * self.memory_config.hidden
+
+    def memory_set_hidden(self, hidden):
+        """Every agent's hidden state [N, layers, hidden] from a float32 numpy array or a device tensor."""
+        self._set_params("okenv_memory_set_hidden", (hidden,), (self._memory_hidden_floats(),))
+
+    def memory_get_hidden(self, out=None):
+        """Every agent's hidden state as a float32 numpy array [N, layers, hidden], or copied into the device tensor `out`.
+        Synchronises."""
+        got = self._get_state("okenv_memory_get_hidden", {"params": self._memory_hidden_floats()}, None if out is None else {"params": out})["params"]
+        return got.reshape(self.N, self.memory_config.layers, self.memory_config.hidden) if out is None else got
+
+    def memory_act(self, frames, record=None, stages=None):
+        """Every agent's action from its frame, its hidden state and its own controller, enqueued on the handle's stream without a
+        synchronisation (with the racers' skip_crashed nothing of a crashed agent is touched).  frames: as world_act's.  record: None,
+        or a dict of device tensors / addresses under capi.MEMORY_RECORD ("mu" [N,Z], "hidden" [N,H], "prediction" [N,Z], "state"
+        [N,Z+H], "out" [N], "action" [N,2] float32, "alive" [N] uint8), each optional.  stages: None, or a mask of
+        capi.MEMORY_STAGE_* -- only those kernels (okenv_debug_memory_stages)."""
+        S, Z, H = self.world_config.image_size, self.world_config.latent, self.memory_config.hidden
+        sizes = record and {"mu": self.N * Z * 4, "hidden": self.N * H * 4, "prediction": self.N * Z * 4, "state": self.N * (Z + H) * 4,
+                            "out": self.N * 4, "action": self.N * 8, "alive": self.N}
+        if stages is None:
+            self._act("okenv_memory_act", capi.OkenvMemoryRecord, record, sizes, capi.ptr(frames), self.N * S * S * 4)
+        else:
+            rec = None if record is None else C.byref(capi.fill_pointers(capi.OkenvMemoryRecord(), record, "record", sizes))
+            capi.check(self._L.okenv_debug_memory_stages(self._h, capi.ptr(frames), self.N * S * S * 4, rec, int(stages)), self._h)
+
     # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) -------------------------------------------------------
     def gcl_create(self, **config):
         """Attaches a GCL object (policy R -> H1 -> H2 -> 2 with log_std, value R -> H1 -> H2 -> 1, cost R + 2 -> C1 -> C2 -> 1) to the
