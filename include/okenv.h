@@ -1300,6 +1300,126 @@ OKENV_API int okenv_memory_act_host(const okenv_world_config *world, const okenv
                                     const float *controllers, int32_t n, const uint8_t *frames, const uint8_t *crashed, float *hidden,
                                     float *throttle, float *steer, const okenv_memory_record *rec);
 
+/* ---- Deep-Q image racers ------------------------------------------------------------------------------------
+ * RLRacers/DQN_CNN (CNN.hpp, DQCNNAgent.hpp, dq_cnn_racer_sim.cpp) for every agent of the handle: from the camera's RGBA8 frames
+ * (okenv_render_views, rendered at image_size x image_size) one grey plane, three PADDED convolutions with ReLU, the flatten, fc1 with
+ * ReLU, fc2 to num_actions Q-values, the greedy or epsilon-greedy choice of the shared-network actors and their action table; and the
+ * ring of frame transitions with its push and its batch gather.  The temporal-difference update stays in PyTorch
+ * (openkitchen_amd/dqn_cnn.py).  The rule is written out in include/okenv_qcnn.h (ok_qcnn_*); all matrix work runs on the f32-input
+ * matrix cores.  The parameter vector is torch's parameters() order for the reference module (ok_qcnn_offsets); every weight must be
+ * finite. */
+typedef struct okenv_qcnn_config {
+    int32_t  image_size;         /* S: 16 .. 128                                         (on this camera: 96)         */
+    int32_t  kernel[3];          /* 1 .. 8                                               (8, 4, 3)                    */
+    int32_t  stride[3];          /* 1 .. 4, at most the kernel                           (4, 2, 1)                    */
+    int32_t  padding[3];         /* 0 .. 3, below the kernel                             (2, 1, 1)                    */
+    int32_t  channels[3];        /* multiples of 16, 16 .. 128; ONE input channel        (32, 64, 64)                 */
+    int32_t  hidden;             /* H: multiple of 16, 16 .. 512                         (512)                        */
+    int32_t  num_actions;        /* A: 2 .. 8                                            (5)                          */
+    int32_t  mode;               /* OKENV_ACTOR_GREEDY | OKENV_ACTOR_EPS_GREEDY                                       */
+    float    epsilon;            /* [0, 1]; read by OKENV_ACTOR_EPS_GREEDY only                                       */
+    uint32_t seed, agent_base;   /* key of the draws (okenv_actor_params'); global id of the handle's agent 0         */
+    float    action_table[8][2]; /* (throttle_delta, steering_delta) per action index (DQCNNAgent::kActionMap); finite */
+} okenv_qcnn_config;
+
+/* What an act can leave behind for the caller, device pointers, each may be NULL */
+typedef struct okenv_qcnn_record {
+    float   *q;      /* [N][A] the Q-values                            */
+    int64_t *action; /* [N]    the chosen index                        */
+    float   *value;  /* [N]    q of the chosen action                  */
+    uint8_t *alive;  /* [N]    1 where the agent was not crashed       */
+} okenv_qcnn_record;
+
+/* The frame ring's fields, capacity C: fp32 grey planes, what the learner's network consumes */
+typedef struct okenv_qcnn_ring {
+    float   *state;      /* [C][S][S] */
+    float   *next_state; /* [C][S][S] */
+    int64_t *action;     /* [C]       */
+    float   *reward;     /* [C]       */
+    float   *done;       /* [C] 1.0f or 0.0f */
+} okenv_qcnn_ring;
+
+/* Where okenv_qcnn_batch leaves a batch of B positions: each pointer may be NULL */
+typedef struct okenv_qcnn_batch_out {
+    float   *state;      /* [B][S][S] */
+    float   *next_state; /* [B][S][S] */
+    int64_t *action;     /* [B]       */
+    float   *reward;     /* [B]       */
+    float   *done;       /* [B]       */
+    int32_t *index;      /* [B] the slot each position was read from */
+} okenv_qcnn_batch_out;
+
+#define OKENV_QCNN_BATCH_UNIFORM 0    /* slot ok_dqn_sample(seed, q, draw, size): the lidar ring's draw                        */
+#define OKENV_QCNN_BATCH_SEQUENTIAL 1 /* push rank first + ((start + q) mod size): the reference's walk, wrapping at the end  */
+
+/* LDS bytes of the larger of the two act kernels for the shape: a pure host function.  A shape is accepted only if this fits 160 KB.
+ * 0 for a NULL config or a shape outside the rule's limits. */
+OKENV_API int64_t okenv_qcnn_lds_bytes(const okenv_qcnn_config *config);
+/* What names the kernels' paths for the shape: a pure host function.  plan [3]: the tiles of 16 hidden units a wave of the head kernel
+ * owns (1 .. 4); what sizes the conv kernel's first LDS region (0: the grey plane inside its border, 1: layer 1's output inside its
+ * border); whether the push and the gather move planes as 16-byte vectors (1: S S is a multiple of 4) or float by float (0). */
+OKENV_API int okenv_qcnn_plan(const okenv_qcnn_config *config, int32_t *plan);
+/* Attaches a Q-network to the handle (replaces an earlier one: its parameters are forgotten).  All device memory of the act is
+ * allocated here.  OKENV_ERR_INVALID for NULL arguments, a shape outside the limits above or the LDS budget, an unknown mode, epsilon
+ * outside [0, 1] or a non-finite entry of the action table. */
+OKENV_API int okenv_qcnn_create(okenv_t h, const okenv_qcnn_config *config);
+OKENV_API int okenv_qcnn_num_params(okenv_t h, int32_t *num_params);
+/* New parameters from a host or device pointer (a device pointer is a device-to-device copy on the handle's stream); the kernels' own
+ * copy of the weights is made behind it on the stream.  No synchronisation. */
+OKENV_API int okenv_qcnn_set_params(okenv_t h, const float *params);
+/* The parameters, in the same order, to a host or device pointer; synchronises. */
+OKENV_API int okenv_qcnn_get_params(okenv_t h, float *params);
+OKENV_API int okenv_qcnn_set_epsilon(okenv_t h, float epsilon);
+/* A device word that is added to the draw index of every later okenv_qcnn_act (NULL: none); see okenv_actor_act. */
+OKENV_API int okenv_qcnn_set_draw_offset(okenv_t h, const uint32_t *device_word);
+/* Acts for every agent, crashed ones included, from frames (device, [N][S][S][4] uint8, frame_bytes = N S S 4 in all; 16-byte
+ * aligned where S S is a multiple of 4, else 4-byte): writes OKENV_F_THROTTLE, OKENV_F_STEER and the record (rec may be NULL).  The
+ * draw index and its device word are exactly okenv_actor_act's.  Two kernels on the handle's stream, no synchronisation, no
+ * allocation: capturable beside okenv_step and okenv_render_views.  OKENV_ERR_STATE before okenv_qcnn_create or okenv_qcnn_set_params;
+ * OKENV_ERR_INVALID for NULL frames or another frame_bytes. */
+OKENV_API int okenv_qcnn_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_qcnn_record *rec);
+/* okenv_qcnn_act's kernels one by one, for measurement: only those named in `stages`, in their order (the head reads what the conv
+ * kernel left in the handle's buffer on an earlier call).  OKENV_QCNN_STAGE_HEAD_32 runs the head with 32 agents a workgroup instead of
+ * the act's 16: the tiling that was measured and not chosen.  Refusals as okenv_qcnn_act's. */
+#define OKENV_QCNN_STAGE_CONV 1u       /* grey, layers 0, 1 and 2 */
+#define OKENV_QCNN_STAGE_HEAD 2u       /* fc1, fc2, the choice, the action fields and the record */
+#define OKENV_QCNN_STAGE_HEAD_32 4u    /* the same with 32 agents a workgroup */
+OKENV_API int okenv_debug_qcnn_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_qcnn_record *rec, uint32_t stages);
+/* Attaches the frame ring of `capacity` transitions (replaces an earlier one, whose memory is freed: a captured okenv_qcnn_push must
+ * not be replayed afterwards).  flags: 0 or OKENV_REPLAY_PUSH_ALL.  OKENV_ERR_STATE before okenv_qcnn_create (the planes have the
+ * network's size; a later okenv_qcnn_create with another image_size drops the ring).  Synchronises. */
+OKENV_API int okenv_qcnn_ring_create(okenv_t h, int32_t capacity, uint32_t flags);
+OKENV_API int okenv_qcnn_ring_reset(okenv_t h);
+/* (transitions in the ring, transitions ever pushed); each pointer may be NULL; synchronises */
+OKENV_API int okenv_qcnn_ring_size(okenv_t h, int64_t *size, int64_t *pushed);
+/* The ring's fields, all `capacity` slots, to host or device pointers (each may be NULL); synchronises */
+OKENV_API int okenv_qcnn_ring_get(okenv_t h, const okenv_qcnn_ring *out);
+/* Appends the transitions of the step that has just run.  rec: what the preceding okenv_qcnn_act recorded (action; alive unless the
+ * ring has OKENV_REPLAY_PUSH_ALL); frames: what that act saw; next_frames: the camera after the step; reward [N] on the device, or
+ * NULL: the clearance rule (ok_dqn_reward).  Selection and rank are okenv_replay_push's.  Three kernels on the handle's stream, no
+ * synchronisation, no allocation. */
+OKENV_API int okenv_qcnn_push(okenv_t h, const okenv_qcnn_record *rec, const uint8_t *frames, const uint8_t *next_frames, int64_t frame_bytes,
+                              const float *reward);
+/* B positions of the ring into dense device arrays: mode OKENV_QCNN_BATCH_UNIFORM (start_or_draw: the draw index; the seed is the
+ * config's) or _SEQUENTIAL (start_or_draw: the walk's start).  The ring's size is read on the device; an empty ring gives zeros.  One
+ * kernel on the handle's stream, no synchronisation. */
+OKENV_API int okenv_qcnn_batch(okenv_t h, int32_t B, int32_t mode, int64_t start_or_draw, const okenv_qcnn_batch_out *out);
+/* The same rules on host arrays, no GPU needed.  act: frames [n][S][S][4]; crashed [n] or NULL; q [n][A], the others [n]; every
+ * output may be NULL. */
+OKENV_API int okenv_qcnn_act_host(const okenv_qcnn_config *config, const float *params, int32_t n, const uint8_t *frames, const uint8_t *crashed,
+                                  uint32_t draw_index, float *throttle, float *steer, float *q, int64_t *action, float *value, uint8_t *alive);
+/* One push on host arrays: ring [capacity] slots of image_size^2 planes and its counter; action, alive, crashed [n]; reward [n] or
+ * NULL with dist [n][num_rays]. */
+OKENV_API int okenv_qcnn_push_host(const okenv_qcnn_ring *ring, int32_t capacity, int32_t image_size, uint64_t *pushed, uint32_t flags, int32_t n,
+                                   const int64_t *action, const uint8_t *alive, const uint8_t *frames, const uint8_t *next_frames,
+                                   const uint8_t *crashed, const float *reward, const float *dist, int32_t num_rays);
+OKENV_API int okenv_qcnn_batch_host(const okenv_qcnn_ring *ring, int32_t capacity, int32_t image_size, uint64_t pushed, uint32_t seed, int32_t B,
+                                    int32_t mode, int64_t start_or_draw, const okenv_qcnn_batch_out *out);
+/* Test hooks on host arrays: the grey planes [n][S][S] of frames [n][S][S][4]; and the network on grey planes [n][S][S] to q [n][A]
+ * (the forward of okenv_qcnn_act_host behind its grey). */
+OKENV_API int okenv_debug_qcnn_grey_host(int32_t image_size, int32_t n, const uint8_t *frames, float *planes);
+OKENV_API int okenv_debug_qcnn_forward_planes_host(const okenv_qcnn_config *config, const float *params, int32_t n, const float *planes, float *q);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.

@@ -113,6 +113,10 @@ SYMBOLS = [
     "okenv_memory_lds_bytes", "okenv_memory_plan", "okenv_memory_workspace_bytes", "okenv_memory_create", "okenv_memory_num_params",
     "okenv_memory_set_params", "okenv_memory_get_params", "okenv_memory_reset", "okenv_memory_set_hidden", "okenv_memory_get_hidden",
     "okenv_memory_act", "okenv_debug_memory_stages", "okenv_memory_act_host",
+    "okenv_qcnn_lds_bytes", "okenv_qcnn_plan", "okenv_qcnn_create", "okenv_qcnn_num_params", "okenv_qcnn_set_params", "okenv_qcnn_get_params",
+    "okenv_qcnn_set_epsilon", "okenv_qcnn_set_draw_offset", "okenv_qcnn_act", "okenv_debug_qcnn_stages", "okenv_qcnn_ring_create",
+    "okenv_qcnn_ring_reset", "okenv_qcnn_ring_size", "okenv_qcnn_ring_get", "okenv_qcnn_push", "okenv_qcnn_batch", "okenv_qcnn_act_host",
+    "okenv_qcnn_push_host", "okenv_qcnn_batch_host", "okenv_debug_qcnn_grey_host", "okenv_debug_qcnn_forward_planes_host",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -635,6 +639,167 @@ def cnn_act_host(cfg, params, frames, crashed=None):
     out = dict(throttle=np.empty(n, np.float32), steer=np.empty(n, np.float32), out=np.empty(n, np.float32), alive=np.empty(n, np.uint8))
     check(load().okenv_cnn_act_host(C.byref(cfg), ptr(params), n, ptr(frames), ptr(crashed), ptr(out["throttle"]), ptr(out["steer"]),
                                     ptr(out["out"]), ptr(out["alive"])))
+    return out
+
+
+# Deep-Q image racers (include/okenv.h)
+QCNN_LDS_BUDGET = 160 * 1024
+QCNN_STAGE_CONV, QCNN_STAGE_HEAD, QCNN_STAGE_HEAD_32 = 1, 2, 4
+QCNN_AGENTS = 16  # agents per workgroup of the head kernel (ok_qcnn.h: kQcnnAgents)
+QCNN_BATCH_UNIFORM, QCNN_BATCH_SEQUENTIAL = 0, 1
+QCNN_BATCH_MODES = {"uniform": QCNN_BATCH_UNIFORM, "sequential": QCNN_BATCH_SEQUENTIAL}
+# DQCNNAgent::kActionMap: (throttle_delta, steering_delta) per action index (kVelocity 60, kSteeringDelta 5 degrees)
+QCNN_ACTION_MAP = ((60.0, 0.0), (30.0, 5.0), (30.0, -5.0), (30.0, 2.5), (30.0, -2.5))
+
+
+class OkenvQcnnConfig(C.Structure):
+    _fields_ = [("image_size", C.c_int32), ("kernel", C.c_int32 * 3), ("stride", C.c_int32 * 3), ("padding", C.c_int32 * 3),
+                ("channels", C.c_int32 * 3), ("hidden", C.c_int32), ("num_actions", C.c_int32), ("mode", C.c_int32), ("epsilon", C.c_float),
+                ("seed", C.c_uint32), ("agent_base", C.c_uint32), ("action_table", (C.c_float * 2) * 8)]
+
+
+class OkenvQcnnRecord(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("action", C.c_void_p), ("value", C.c_void_p), ("alive", C.c_void_p)]
+
+
+class OkenvQcnnRing(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("next_state", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p)]
+
+
+class OkenvQcnnBatchOut(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("next_state", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p),
+                ("index", C.c_void_p)]
+
+
+def qcnn_config(image_size=96, kernel=(8, 4, 3), stride=(4, 2, 1), padding=(2, 1, 1), channels=(32, 64, 64), hidden=512, num_actions=5,
+                mode="greedy", epsilon=0.0, seed=0, agent_base=0, action_table=QCNN_ACTION_MAP):
+    """okenv_qcnn_config with the reference's layers, action count and action table as defaults (RLRacers/DQN_CNN: CNN.hpp,
+    DQCNNAgent.hpp); mode: "greedy", "eps_greedy" or the number."""
+    cfg = OkenvQcnnConfig(int(image_size), (C.c_int32 * 3)(*map(int, kernel)), (C.c_int32 * 3)(*map(int, stride)),
+                          (C.c_int32 * 3)(*map(int, padding)), (C.c_int32 * 3)(*map(int, channels)), int(hidden), int(num_actions),
+                          ACTOR_MODES.get(mode, mode), float(epsilon), int(seed) & 0xFFFFFFFF, int(agent_base) & 0xFFFFFFFF)
+    for i, (thr, steer) in enumerate(action_table):
+        cfg.action_table[i][0], cfg.action_table[i][1] = float(thr), float(steer)
+    return cfg
+
+
+def qcnn_sides(cfg):
+    """ok_qcnn_side: the sides of the three padded convolutions' outputs (torch's flooring; 0 where the kernel does not fit)."""
+    side, out = cfg.image_size, []
+    for k, s, p in zip(cfg.kernel, cfg.stride, cfg.padding):
+        side = 0 if side + 2 * p < k or s < 1 else (side + 2 * p - k) // s + 1
+        out.append(side)
+    return tuple(out)
+
+
+def qcnn_layout(cfg):
+    """ok_qcnn_offsets: where every piece of the parameter vector begins, as (name, offset, shape) in order; the names are the
+    state-dict keys of the reference's CNN.  The last entry's end is the vector's length."""
+    k, c, H, A = list(cfg.kernel), list(cfg.channels), cfg.hidden, cfg.num_actions
+    F = c[2] * qcnn_sides(cfg)[2] ** 2
+    pieces = []
+    for l, cin in enumerate([1] + c[:2]):
+        pieces += [("conv%d.weight" % (l + 1), (c[l], cin, k[l], k[l])), ("conv%d.bias" % (l + 1), (c[l],))]
+    pieces += [("fc1.weight", (H, F)), ("fc1.bias", (H,)), ("fc2.weight", (A, H)), ("fc2.bias", (A,))]
+    out, at = [], 0
+    for name, shape in pieces:
+        out.append((name, at, shape))
+        at += int(np.prod(shape))
+    return out
+
+
+def qcnn_num_params(cfg):
+    """Floats of the Q-network's parameter vector."""
+    name, at, shape = qcnn_layout(cfg)[-1]
+    return at + int(np.prod(shape))
+
+
+def qcnn_lds_bytes(cfg):
+    """okenv_qcnn_lds_bytes: the larger act kernel's LDS for the shape, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_qcnn_lds_bytes(C.byref(cfg)))
+
+
+def qcnn_plan(cfg):
+    """okenv_qcnn_plan: (tiles of 16 hidden units per wave of the head kernel, what sizes the conv kernel's first LDS region, whether
+    planes move as 16-byte vectors), the kernels' paths.  No GPU needed."""
+    out = (C.c_int32 * 3)()
+    check(load().okenv_qcnn_plan(C.byref(cfg), out))
+    return tuple(int(v) for v in out)
+
+
+def qcnn_act_host(cfg, params, frames, crashed=None, draw_index=0):
+    """okenv_qcnn_act_host on numpy arrays: frames [n][S][S][4] uint8 -> dict(throttle, steer, value [n] float32, q [n][A] float32,
+    action [n] int64, alive [n] uint8).  No GPU needed."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    params = np.ascontiguousarray(params, np.float32)
+    n = frames.shape[0]
+    assert frames.shape == (n, cfg.image_size, cfg.image_size, 4) and params.size == qcnn_num_params(cfg)
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, np.uint8)
+    out = dict(throttle=np.empty(n, np.float32), steer=np.empty(n, np.float32), q=np.empty((n, cfg.num_actions), np.float32),
+               action=np.empty(n, np.int64), value=np.empty(n, np.float32), alive=np.empty(n, np.uint8))
+    check(load().okenv_qcnn_act_host(C.byref(cfg), ptr(params), n, ptr(frames), ptr(crashed), int(draw_index) & 0xFFFFFFFF, ptr(out["throttle"]),
+                                     ptr(out["steer"]), ptr(out["q"]), ptr(out["action"]), ptr(out["value"]), ptr(out["alive"])))
+    return out
+
+
+def qcnn_ring(capacity, image_size):
+    """An empty host-side frame ring: dict of zeroed numpy arrays (state, next_state [C][S][S]; action int64, reward, done [C]), its
+    "pushed" count, "capacity" and "image_size"."""
+    C_, S = int(capacity), int(image_size)
+    return dict(state=np.zeros((C_, S, S), np.float32), next_state=np.zeros((C_, S, S), np.float32), action=np.zeros(C_, np.int64),
+                reward=np.zeros(C_, np.float32), done=np.zeros(C_, np.float32), pushed=0, capacity=C_, image_size=S)
+
+
+def _qcnn_ring_struct(ring):
+    return fill_pointers(OkenvQcnnRing(), {k: ring[k] for k in ("state", "next_state", "action", "reward", "done")}, "ring")
+
+
+def qcnn_push_host(ring, action, alive, frames, next_frames, crashed, reward=None, dist=None, push_all=False):
+    """One push on host arrays, no GPU needed (okenv_qcnn_push_host): `ring` (qcnn_ring(...)) is updated in place, "pushed" included."""
+    S = ring["image_size"]
+    frames, next_frames = np.ascontiguousarray(frames, np.uint8), np.ascontiguousarray(next_frames, np.uint8)
+    n = frames.shape[0]
+    assert frames.shape == next_frames.shape == (n, S, S, 4)
+    action = np.ascontiguousarray(action, np.int64)
+    alive = None if alive is None else np.ascontiguousarray(alive, np.uint8)
+    crashed = np.ascontiguousarray(crashed, np.uint8)
+    reward = None if reward is None else np.ascontiguousarray(reward, np.float32)
+    dist = None if dist is None else np.ascontiguousarray(dist, np.float32)
+    pushed = C.c_uint64(ring["pushed"])
+    check(load().okenv_qcnn_push_host(C.byref(_qcnn_ring_struct(ring)), ring["capacity"], S, C.byref(pushed), REPLAY_PUSH_ALL if push_all else 0, n,
+                                      ptr(action), ptr(alive), ptr(frames), ptr(next_frames), ptr(crashed), ptr(reward), ptr(dist),
+                                      0 if dist is None else dist.shape[1]))
+    ring["pushed"] = int(pushed.value)
+    return ring
+
+
+def qcnn_batch_host(ring, B, mode="sequential", start_or_draw=0, seed=0):
+    """B positions of a host-side ring (okenv_qcnn_batch_host): dict(state, next_state [B][S][S], action, reward, done, index [B])."""
+    S, B = ring["image_size"], int(B)
+    out = dict(state=np.full((B, S, S), -7.0, np.float32), next_state=np.full((B, S, S), -7.0, np.float32), action=np.full(B, -7, np.int64),
+               reward=np.full(B, -7.0, np.float32), done=np.full(B, -7.0, np.float32), index=np.full(B, -7, np.int32))
+    check(load().okenv_qcnn_batch_host(C.byref(_qcnn_ring_struct(ring)), ring["capacity"], S, int(ring["pushed"]), int(seed) & 0xFFFFFFFF, B,
+                                       QCNN_BATCH_MODES.get(mode, mode), int(start_or_draw), C.byref(fill_pointers(OkenvQcnnBatchOut(), out, "batch"))))
+    return out
+
+
+def qcnn_grey_host(frames):
+    """The rule's grey planes [n][S][S] float32 of frames [n][S][S][4] uint8 (a test hook).  No GPU needed."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, S = frames.shape[0], frames.shape[1]
+    assert frames.shape == (n, S, S, 4)
+    out = np.empty((n, S, S), np.float32)
+    check(load().okenv_debug_qcnn_grey_host(S, n, ptr(frames), ptr(out)))
+    return out
+
+
+def qcnn_forward_planes_host(cfg, params, planes):
+    """The network of okenv_qcnn_act_host on grey planes [n][S][S] float32 -> q [n][A] (a test hook).  No GPU needed."""
+    planes, params = np.ascontiguousarray(planes, np.float32), np.ascontiguousarray(params, np.float32)
+    n = planes.shape[0]
+    assert planes.shape == (n, cfg.image_size, cfg.image_size) and params.size == qcnn_num_params(cfg)
+    out = np.empty((n, cfg.num_actions), np.float32)
+    check(load().okenv_debug_qcnn_forward_planes_host(C.byref(cfg), ptr(params), n, ptr(planes), ptr(out)))
     return out
 
 
@@ -1250,6 +1415,29 @@ def load(build_if_missing=True):
     L.okenv_memory_act.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvMemoryRecord)]
     L.okenv_debug_memory_stages.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvMemoryRecord), C.c_uint32]
     L.okenv_memory_act_host.argtypes = [wc, mc, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(OkenvMemoryRecord)]
+    qc, i64 = C.POINTER(OkenvQcnnConfig), C.c_int64
+    L.okenv_qcnn_lds_bytes.argtypes = [qc]
+    L.okenv_qcnn_lds_bytes.restype = C.c_int64
+    L.okenv_qcnn_plan.argtypes = [qc, vp]
+    L.okenv_qcnn_create.argtypes = [vp, qc]
+    L.okenv_qcnn_num_params.argtypes = [vp, C.POINTER(i32)]
+    L.okenv_qcnn_set_params.argtypes = [vp, vp]
+    L.okenv_qcnn_get_params.argtypes = [vp, vp]
+    L.okenv_qcnn_set_epsilon.argtypes = [vp, C.c_float]
+    L.okenv_qcnn_set_draw_offset.argtypes = [vp, vp]
+    L.okenv_qcnn_act.argtypes = [vp, vp, i64, C.POINTER(OkenvQcnnRecord)]
+    L.okenv_debug_qcnn_stages.argtypes = [vp, vp, i64, C.POINTER(OkenvQcnnRecord), C.c_uint32]
+    L.okenv_qcnn_ring_create.argtypes = [vp, i32, C.c_uint32]
+    L.okenv_qcnn_ring_reset.argtypes = [vp]
+    L.okenv_qcnn_ring_size.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.okenv_qcnn_ring_get.argtypes = [vp, C.POINTER(OkenvQcnnRing)]
+    L.okenv_qcnn_push.argtypes = [vp, C.POINTER(OkenvQcnnRecord), vp, vp, i64, vp]
+    L.okenv_qcnn_batch.argtypes = [vp, i32, i32, i64, C.POINTER(OkenvQcnnBatchOut)]
+    L.okenv_qcnn_act_host.argtypes = [qc, vp, i32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.okenv_qcnn_push_host.argtypes = [C.POINTER(OkenvQcnnRing), i32, i32, C.POINTER(C.c_uint64), C.c_uint32, i32, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.okenv_qcnn_batch_host.argtypes = [C.POINTER(OkenvQcnnRing), i32, i32, C.c_uint64, C.c_uint32, i32, i32, i64, C.POINTER(OkenvQcnnBatchOut)]
+    L.okenv_debug_qcnn_grey_host.argtypes = [i32, i32, vp, vp]
+    L.okenv_debug_qcnn_forward_planes_host.argtypes = [qc, vp, i32, vp, vp]
     _lib = L
     return L
 

@@ -37,6 +37,7 @@
 #include "ok_cnn.h"
 #include "ok_world.h"
 #include "ok_memory.h"
+#include "ok_qcnn.h"
 #include "ok_expert.h"
 
 namespace
@@ -608,6 +609,16 @@ struct okenv
     okenv_memory_config     mem{};
     float                  *d_mem_ws{nullptr};
     size_t                  mem_ws_cap{0};
+    // Deep-Q image racers (okenv_qcnn_create, okenv_qcnn_ring_create): the parameter vector in torch's order; the kernels' copy of the
+    // weights and the features that pass from the conv kernel to the head, both allocated at create; the frame ring (its planes have
+    // the network's image_size) and the push's slot of every agent
+    OkDriver                qcnn_drv;
+    okenv_qcnn_config       qcnn{};
+    float                  *d_qcnn_pack{nullptr}, *d_qcnn_feat{nullptr};
+    size_t                  qcnn_pack_cap{0}, qcnn_feat_cap{0};
+    OkRing                  qcnn_ring{sizeof(int64_t)};
+    int32_t                 qcnn_ring_side{0};
+    long long              *d_qcnn_slots{nullptr};
 };
 
 struct okenv_track
@@ -1484,7 +1495,8 @@ const DriverKind kActorDriver{&okenv::actor_drv, "okenv_actor_", "every attached
     kBevDriver{&okenv::bev_drv, "okenv_bev_", "the encoder needs its parameters", "the encoder needs its parameters", true},
     kCnnDriver{&okenv::cnn_drv, "okenv_cnn_", "the policy needs its parameters", "the policy needs its parameters", true},
     kWorldDriver{&okenv::world_drv, "okenv_world_", "the encoder and the controllers need their parameters", "the vector needs its parameters", true},
-    kMemoryDriver{&okenv::mem_drv, "okenv_memory_", "the network and the controllers need their parameters", "the vector needs its parameters", true};
+    kMemoryDriver{&okenv::mem_drv, "okenv_memory_", "the network and the controllers need their parameters", "the vector needs its parameters", true},
+    kQcnnDriver{&okenv::qcnn_drv, "okenv_qcnn_", "the network needs its parameters", "the network needs its parameters", true};
 
 int driverRefuses(okenv *h, const int code, const DriverKind &k, const char *entry, const std::string &why)
 {
@@ -1729,6 +1741,58 @@ int cnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const oke
         void (*const heads[kCnnMaxColTiles])(OkCnnActParams) = {okCnnHeadKernel<1>, okCnnHeadKernel<2>, okCnnHeadKernel<3>, okCnnHeadKernel<4>};
         return actLaunch(h, heads[pl.ct - 1], kCnnAgents, kCnnThreads, sizeof(float) * static_cast<size_t>(pl.head_end), p);
     }
+    return OKENV_OK;
+}
+
+// What okenv_qcnn_act and okenv_qcnn_push refuse in their frames: nullptr when they are as the kernels need them
+const char *qcnnFramesMissing(const okenv *h, const void *frames, const int64_t frame_bytes)
+{
+    const int S = h->qcnn.image_size;
+    if (!frames)
+        return "NULL argument";
+    if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
+        return "frame_bytes is not num_agents x image_size x image_size x 4";
+    if (reinterpret_cast<uintptr_t>(frames) % (okQcnnPlaces(okQcnnShape(h->qcnn)).vec != 0 ? 16U : 4U) != 0U)
+        return "frames must be 16-byte aligned (4-byte where image_size x image_size is no multiple of 4)";
+    return nullptr;
+}
+
+template <int RT>
+int qcnnHead(okenv *h, const OkQcnnPlaces &pl, const OkQcnnActParams &p)
+{
+    void (*const heads[kQcnnMaxColTiles])(OkQcnnActParams) = {okQcnnHeadKernel<1, RT>, okQcnnHeadKernel<2, RT>, okQcnnHeadKernel<3, RT>, okQcnnHeadKernel<4, RT>};
+    const size_t lds = sizeof(float) * static_cast<size_t>(kQcnnAgents * RT * (pl.ldt + pl.ldh));
+    return actLaunch(h, heads[pl.ct - 1], kQcnnAgents * RT, kQcnnThreads, lds, p);
+}
+
+// okenv_qcnn_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_QCNN_STAGE_*), in their order, on the stream
+int qcnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_qcnn_record *rec, const unsigned stages)
+{
+    const char *missing = h != nullptr && h->qcnn_drv.ok ? qcnnFramesMissing(h, frames, frame_bytes) : nullptr;
+    if (const int rc = actBegin(h, kQcnnDriver, 1U, missing))
+        return rc;
+    const ok_qcnn_shape s  = okQcnnShape(h->qcnn);
+    const OkQcnnPlaces  pl = okQcnnPlaces(s);
+    OkQcnnActParams     p{};
+    p.st     = h->st;
+    p.N      = h->shape.N;
+    p.s      = s;
+    p.frames = frames;
+    p.params = h->qcnn_drv.d;
+    p.pack   = h->d_qcnn_pack;
+    p.feat   = h->d_qcnn_feat;
+    p.draw   = actDrawWords(h, h->qcnn_drv.draw_offset);
+    p.cfg    = h->qcnn;
+    if (rec != nullptr)
+        p.rec = *rec;
+    if ((stages & OKENV_QCNN_STAGE_CONV) != 0U)
+        if (const int rc = actLaunch(h, okQcnnConvKernel, 1, kQcnnThreads, sizeof(float) * static_cast<size_t>(pl.conv_end), p))
+            return rc;
+    if ((stages & OKENV_QCNN_STAGE_HEAD) != 0U)
+        if (const int rc = qcnnHead<1>(h, pl, p))
+            return rc;
+    if ((stages & OKENV_QCNN_STAGE_HEAD_32) != 0U)
+        return qcnnHead<2>(h, pl, p);
     return OKENV_OK;
 }
 
@@ -5214,6 +5278,339 @@ extern "C"
         if (ok_memory_params_bad(okMemoryShape(*world, *config), network))
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_act_host: the network vector holds a non-finite value or a std that is not > 0");
         okMemoryActHost(*world, *config, encoder, network, controllers, n, frames, crashed, hidden, throttle, steer, rec != nullptr ? *rec : okenv_memory_record{});
+        return OKENV_OK;
+    }
+
+    // ---- Deep-Q image racers (ok_qcnn.h) ---------------------------------------------------------------------------------------------
+
+    int64_t okenv_qcnn_lds_bytes(const okenv_qcnn_config *config)
+    {
+        return config != nullptr ? static_cast<int64_t>(okQcnnLdsBytes(okQcnnShape(*config))) : 0;
+    }
+
+    int okenv_qcnn_plan(const okenv_qcnn_config *config, int32_t *plan)
+    {
+        if (const char *why = okQcnnCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_qcnn_plan: ") + why);
+        if (!plan)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_qcnn_plan: bad argument");
+        const OkQcnnPlaces pl = okQcnnPlaces(okQcnnShape(*config));
+        plan[0] = pl.ct;
+        plan[1] = pl.region;
+        plan[2] = pl.vec;
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_create(okenv_t h, const okenv_qcnn_config *config)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kQcnnDriver, "create", kGateHandle))
+            return rc;
+        if (const char *why = okQcnnCheckConfig(config))
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "create", why);
+        const ok_qcnn_shape s = okQcnnShape(*config);
+        if (const int rc = driverCreateFlat(h, kQcnnDriver, static_cast<size_t>(ok_qcnn_offsets(s).total), kernelOf(okQcnnConvKernel)))
+            return rc;
+        h->qcnn_drv.ok = false; // (until the kernels' own buffers stand)
+        if (const int rc = raiseLdsLimit(h, {kernelOf(okQcnnHeadKernel<1, 1>), kernelOf(okQcnnHeadKernel<2, 1>), kernelOf(okQcnnHeadKernel<3, 1>),
+                                             kernelOf(okQcnnHeadKernel<4, 1>), kernelOf(okQcnnHeadKernel<1, 2>), kernelOf(okQcnnHeadKernel<2, 2>),
+                                             kernelOf(okQcnnHeadKernel<3, 2>), kernelOf(okQcnnHeadKernel<4, 2>)}))
+            return rc;
+        const size_t pack = static_cast<size_t>(okQcnnPlaces(s).pack_total), feat = static_cast<size_t>(h->shape.N) * ok_qcnn_features(s);
+        if (pack > h->qcnn_pack_cap || feat > h->qcnn_feat_cap)
+        {
+            const size_t np = std::max(pack, h->qcnn_pack_cap), nf = std::max(feat, h->qcnn_feat_cap);
+            h->qcnn_pack_cap = h->qcnn_feat_cap = 0; // (a failed allocation leaves none of them)
+            if (const int rc = regrow(h, {fresh(h->d_qcnn_pack, np), fresh(h->d_qcnn_feat, nf)}))
+                return rc;
+            h->qcnn_pack_cap = np, h->qcnn_feat_cap = nf;
+        }
+        if (h->qcnn_ring.ok && h->qcnn_ring_side != config->image_size)
+            h->qcnn_ring.ok = false; // (its planes had the earlier network's size)
+        h->qcnn        = *config;
+        h->qcnn_drv.ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_num_params(okenv_t h, int32_t *num_params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kQcnnDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
+            return rc;
+        *num_params = ok_qcnn_offsets(okQcnnShape(h->qcnn)).total;
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_set_params(okenv_t h, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kQcnnDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
+            return rc;
+        const ok_qcnn_shape s = okQcnnShape(h->qcnn);
+        if (const int rc = driverSet(h, kQcnnDriver, {vectorOf(h->qcnn_drv.d, params, ok_qcnn_offsets(s).total)}))
+            return rc;
+        OkQcnnPackParams p{};
+        p.s      = s;
+        p.params = h->qcnn_drv.d;
+        p.pack   = h->d_qcnn_pack;
+        const unsigned blocks = static_cast<unsigned>((okQcnnPlaces(s).pack_total + 255) / 256);
+        hipLaunchKernelGGL(okQcnnPackKernel, dim3(blocks), dim3(256), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_get_params(okenv_t h, float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kQcnnDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
+            return rc;
+        return driverGet(h, {vectorOf(h->qcnn_drv.d, params, ok_qcnn_offsets(okQcnnShape(h->qcnn)).total)});
+    }
+
+    int okenv_qcnn_set_epsilon(okenv_t h, float epsilon)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kQcnnDriver, "set_epsilon", kGateCreated))
+            return rc;
+        if (!(epsilon >= 0.F && epsilon <= 1.F))
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "set_epsilon", "epsilon outside [0, 1]");
+        h->qcnn.epsilon = epsilon;
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_set_draw_offset(okenv_t h, const uint32_t *device_word)
+    {
+        OK_QUIESCE(h);
+        return driverSetDrawOffset(h, kQcnnDriver, device_word);
+    }
+
+    int okenv_qcnn_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_qcnn_record *rec)
+    {
+        OK_QUIESCE(h);
+        return qcnnAct(h, frames, frame_bytes, rec, OKENV_QCNN_STAGE_CONV | OKENV_QCNN_STAGE_HEAD);
+    }
+
+    int okenv_debug_qcnn_stages(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_qcnn_record *rec, uint32_t stages)
+    {
+        OK_QUIESCE(h);
+        return qcnnAct(h, frames, frame_bytes, rec, stages);
+    }
+
+    int okenv_qcnn_ring_create(okenv_t h, int32_t capacity, uint32_t flags)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kQcnnDriver, "ring_create", kGateHandle | kGateCreated))
+            return rc;
+        if (const char *why = okReplayCheckCreate(capacity, flags))
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "ring_create", why);
+        OkRing &r = h->qcnn_ring;
+        OK_HIP(h, hipSetDevice(h->device));
+        r.ok = false;
+        const size_t C = static_cast<size_t>(capacity), px = static_cast<size_t>(h->qcnn.image_size) * static_cast<size_t>(h->qcnn.image_size);
+        const size_t blocks = (static_cast<size_t>(h->shape.N) + kReplayThreads - 1U) / kReplayThreads;
+        // (the wait: nobody is still working in an earlier ring)
+        int rc = regrow(h, {fresh(r.state, C * px), fresh(r.next_state, C * px), fresh(r.action, C * r.action_bytes), fresh(r.reward, C), fresh(r.done, C)});
+        if (rc != OKENV_OK || (rc = devEnsure(h, &r.d_words, 2)) != OKENV_OK || (rc = devEnsure(h, &r.d_counts, blocks)) != OKENV_OK ||
+            (rc = devEnsure(h, &h->d_qcnn_slots, static_cast<size_t>(h->shape.N))) != OKENV_OK)
+            return rc;
+        OK_HIP(h, hipMemsetAsync(r.d_words, 0, 2U * sizeof(uint64_t), h->stream));
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        r.capacity        = capacity;
+        r.flags           = flags;
+        r.ok              = true;
+        h->qcnn_ring_side = h->qcnn.image_size;
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_ring_reset(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->qcnn_ring.ok)
+            return driverRefuses(h, OKENV_ERR_STATE, kQcnnDriver, "ring_reset", "call okenv_qcnn_ring_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        OK_HIP(h, hipMemsetAsync(h->qcnn_ring.d_words, 0, 2U * sizeof(uint64_t), h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_ring_size(okenv_t h, int64_t *size, int64_t *pushed)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->qcnn_ring.ok)
+            return driverRefuses(h, OKENV_ERR_STATE, kQcnnDriver, "ring_size", "call okenv_qcnn_ring_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        uint64_t word = 0;
+        OK_HIP(h, hipMemcpyAsync(&word, h->qcnn_ring.d_words, sizeof(word), hipMemcpyDeviceToHost, h->stream));
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        if (size)
+            *size = static_cast<int64_t>(ok_dqn_size(word, static_cast<uint64_t>(h->qcnn_ring.capacity)));
+        if (pushed)
+            *pushed = static_cast<int64_t>(word);
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_ring_get(okenv_t h, const okenv_qcnn_ring *out)
+    {
+        OK_QUIESCE(h);
+        if (!h || !out)
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "ring_get", "NULL argument");
+        const OkRing &r = h->qcnn_ring;
+        if (!r.ok)
+            return driverRefuses(h, OKENV_ERR_STATE, kQcnnDriver, "ring_get", "call okenv_qcnn_ring_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        const size_t C = static_cast<size_t>(r.capacity), px = static_cast<size_t>(h->qcnn_ring_side) * static_cast<size_t>(h->qcnn_ring_side);
+        void *const       dst[5]   = {out->state, out->next_state, out->action, out->reward, out->done};
+        const void *const src[5]   = {r.state, r.next_state, r.action, r.reward, r.done};
+        const size_t      bytes[5] = {C * px * sizeof(float), C * px * sizeof(float), C * r.action_bytes, C * sizeof(float), C * sizeof(float)};
+        for (int i = 0; i < 5; ++i)
+            if (dst[i] != nullptr)
+                if (const int rc = copyAny(h, dst[i], src[i], bytes[i]))
+                    return rc;
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_push(okenv_t h, const okenv_qcnn_record *rec, const uint8_t *frames, const uint8_t *next_frames, int64_t frame_bytes,
+                        const float *reward)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "push", "NULL handle");
+        const OkRing &r = h->qcnn_ring;
+        if (!h->qcnn_drv.ok || !r.ok)
+            return driverRefuses(h, OKENV_ERR_STATE, kQcnnDriver, "push", "call okenv_qcnn_ring_create first");
+        if (!rec || !rec->action)
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "push", "the record needs action");
+        if (!rec->alive && (r.flags & OKENV_REPLAY_PUSH_ALL) == 0U)
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "push", "the record needs alive (or create the ring with OKENV_REPLAY_PUSH_ALL)");
+        for (const uint8_t *f : {frames, next_frames})
+            if (const char *missing = qcnnFramesMissing(h, f, frame_bytes))
+                return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "push", missing);
+        OK_HIP(h, hipSetDevice(h->device));
+        OkQcnnPushParams p{};
+        p.N           = h->shape.N;
+        p.R           = h->shape.R;
+        p.S           = h->qcnn.image_size;
+        p.flags       = r.flags;
+        p.capacity    = static_cast<uint64_t>(r.capacity);
+        p.ring        = okenv_qcnn_ring{r.state, r.next_state, reinterpret_cast<int64_t *>(r.action), r.reward, r.done};
+        p.pushed      = r.d_words;
+        p.snapshot    = r.d_words + 1;
+        p.counts      = r.d_counts;
+        p.slots       = h->d_qcnn_slots;
+        p.rec         = *rec;
+        p.frames      = frames;
+        p.next_frames = next_frames;
+        p.crashed     = h->st.crashed;
+        p.dist        = h->st.dist;
+        p.reward      = reward;
+        const unsigned blocks = static_cast<unsigned>((h->shape.N + kReplayThreads - 1) / kReplayThreads);
+        hipLaunchKernelGGL(okReplayCountKernel<OkQcnnPushParams>, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        hipLaunchKernelGGL(okQcnnRankKernel, dim3(blocks), dim3(kReplayThreads), 0, h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        const bool     vec    = okQcnnPlaces(okQcnnShape(h->qcnn)).vec != 0;
+        const unsigned pieces = static_cast<unsigned>((p.S * p.S / (vec ? 4 : 1) + kQcnnCopyThreads - 1) / kQcnnCopyThreads);
+        hipLaunchKernelGGL(vec ? okQcnnFramesKernel<true> : okQcnnFramesKernel<false>, dim3(static_cast<unsigned>(p.N), pieces), dim3(kQcnnCopyThreads), 0,
+                           h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_batch(okenv_t h, int32_t B, int32_t mode, int64_t start_or_draw, const okenv_qcnn_batch_out *out)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "batch", "NULL handle");
+        const OkRing &r = h->qcnn_ring;
+        if (!h->qcnn_drv.ok || !r.ok)
+            return driverRefuses(h, OKENV_ERR_STATE, kQcnnDriver, "batch", "call okenv_qcnn_ring_create first");
+        if (!out || B < 1 || start_or_draw < 0 || (mode != OKENV_QCNN_BATCH_UNIFORM && mode != OKENV_QCNN_BATCH_SEQUENTIAL))
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "batch", "out must not be NULL, B at least 1, start_or_draw at least 0, mode OKENV_QCNN_BATCH_UNIFORM or _SEQUENTIAL");
+        const bool vec = okQcnnPlaces(okQcnnShape(h->qcnn)).vec != 0;
+        if (vec && (reinterpret_cast<uintptr_t>(out->state) % 16U != 0U || reinterpret_cast<uintptr_t>(out->next_state) % 16U != 0U))
+            return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "batch", "state and next_state must be 16-byte aligned");
+        OK_HIP(h, hipSetDevice(h->device));
+        OkQcnnBatchParams p{};
+        p.S             = h->qcnn.image_size;
+        p.B             = B;
+        p.mode          = mode;
+        p.seed          = h->qcnn.seed;
+        p.capacity      = static_cast<uint64_t>(r.capacity);
+        p.start_or_draw = static_cast<uint64_t>(start_or_draw);
+        p.pushed        = r.d_words;
+        p.ring          = okenv_qcnn_ring{r.state, r.next_state, reinterpret_cast<int64_t *>(r.action), r.reward, r.done};
+        p.out           = *out;
+        const unsigned pieces = static_cast<unsigned>((p.S * p.S / (vec ? 4 : 1) + kQcnnCopyThreads - 1) / kQcnnCopyThreads);
+        hipLaunchKernelGGL(vec ? okQcnnBatchKernel<true> : okQcnnBatchKernel<false>, dim3(static_cast<unsigned>(B), pieces), dim3(kQcnnCopyThreads), 0,
+                           h->stream, p);
+        OK_HIP(h, hipGetLastError());
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_act_host(const okenv_qcnn_config *config, const float *params, int32_t n, const uint8_t *frames, const uint8_t *crashed,
+                            uint32_t draw_index, float *throttle, float *steer, float *q, int64_t *action, float *value, uint8_t *alive)
+    {
+        if (const char *why = okQcnnCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_qcnn_act_host: ") + why);
+        if (!params || n < 0 || !frames)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_qcnn_act_host: bad argument");
+        okQcnnActHost(*config, params, n, frames, crashed, draw_index, throttle, steer, q, action, value, alive);
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_push_host(const okenv_qcnn_ring *ring, int32_t capacity, int32_t image_size, uint64_t *pushed, uint32_t flags, int32_t n,
+                             const int64_t *action, const uint8_t *alive, const uint8_t *frames, const uint8_t *next_frames, const uint8_t *crashed,
+                             const float *reward, const float *dist, int32_t num_rays)
+    {
+        if (const char *why = okReplayCheckCreate(capacity, flags))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_qcnn_push_host: ") + why);
+        if (!okReplayRingComplete(ring) || !pushed)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_qcnn_push_host: the ring needs every field and its counter");
+        if (image_size < OK_CNN_MIN_SIDE || image_size > OK_CNN_MAX_SIDE || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_qcnn_push_host: image_size 16 .. 128 and n >= 0");
+        if (!action || !frames || !next_frames || !crashed)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_qcnn_push_host: action, frames, next_frames and crashed are required");
+        if (!alive && (flags & OKENV_REPLAY_PUSH_ALL) == 0U)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_qcnn_push_host: alive is required (or pass OKENV_REPLAY_PUSH_ALL)");
+        if (!reward && (!dist || num_rays < 1))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_qcnn_push_host: without reward, dist and num_rays >= 1 are required");
+        ok_qcnn_push(okQcnnRing(*ring), static_cast<uint64_t>(capacity), image_size, pushed, flags, n, action, alive, frames, next_frames, crashed, reward,
+                     dist, num_rays);
+        return OKENV_OK;
+    }
+
+    int okenv_qcnn_batch_host(const okenv_qcnn_ring *ring, int32_t capacity, int32_t image_size, uint64_t pushed, uint32_t seed, int32_t B, int32_t mode,
+                              int64_t start_or_draw, const okenv_qcnn_batch_out *out)
+    {
+        if (!okReplayRingComplete(ring) || !out || capacity < 1 || B < 1 || start_or_draw < 0 || image_size < OK_CNN_MIN_SIDE ||
+            image_size > OK_CNN_MAX_SIDE || (mode != OKENV_QCNN_BATCH_UNIFORM && mode != OKENV_QCNN_BATCH_SEQUENTIAL))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_qcnn_batch_host: bad argument");
+        const ok_qcnn_batch_out o{out->state, out->next_state, out->action, out->reward, out->done, out->index};
+        ok_qcnn_batch(okQcnnRing(*ring), static_cast<uint64_t>(capacity), image_size, pushed, seed, B, mode, static_cast<uint64_t>(start_or_draw), o);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_qcnn_grey_host(int32_t image_size, int32_t n, const uint8_t *frames, float *planes)
+    {
+        if (image_size < 1 || n < 0 || !frames || !planes)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_qcnn_grey_host: bad argument");
+        const size_t px = static_cast<size_t>(image_size) * static_cast<size_t>(image_size);
+        for (int a = 0; a < n; ++a)
+            ok_qcnn_grey_plane(image_size, frames + static_cast<size_t>(a) * px * 4U, planes + static_cast<size_t>(a) * px);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_qcnn_forward_planes_host(const okenv_qcnn_config *config, const float *params, int32_t n, const float *planes, float *q)
+    {
+        if (const char *why = okQcnnCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_debug_qcnn_forward_planes_host: ") + why);
+        if (!params || n < 0 || !planes || !q)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_qcnn_forward_planes_host: bad argument");
+        const ok_qcnn_shape s  = okQcnnShape(*config);
+        const size_t        px = static_cast<size_t>(s.S) * static_cast<size_t>(s.S);
+        std::vector<float>  work(static_cast<size_t>(ok_qcnn_work_floats(s)));
+        for (int a = 0; a < n; ++a)
+            ok_qcnn_forward_plane(s, params, planes + static_cast<size_t>(a) * px, work.data(), q + static_cast<size_t>(a) * s.A);
         return OKENV_OK;
     }
 

@@ -946,6 +946,91 @@ class BatchedEnvironment:
             rec = None if record is None else C.byref(capi.fill_pointers(capi.OkenvCnnRecord(), record, "record", sizes))
             capi.check(self._L.okenv_debug_cnn_stages(self._h, capi.ptr(frames), self.N * S * S * 4, rec, int(stages)), self._h)
 
+    # ---- Deep-Q image racers (include/okenv.h) --------------------------------------------------------------
+    def qcnn_create(self, config=None, **members):
+        """Attaches the reference's image Q-network (RLRacers/DQN_CNN: CNN.hpp) to the handle; config: a capi.qcnn_config(...), or
+        its members as keywords.  Returns the floats of the parameter vector.  A frame ring of another image_size is dropped."""
+        if config is None:
+            config = capi.qcnn_config(**members)
+        capi.check(self._L.okenv_qcnn_create(self._h, C.byref(config)), self._h)
+        self.qcnn_config = config
+        return self.qcnn_num_params()
+
+    def qcnn_num_params(self):
+        return self._count("okenv_qcnn_num_params")
+
+    def qcnn_set_params(self, params):
+        """New parameters (the network's, in torch's parameters() order: capi.qcnn_layout) from a float32 numpy array or a device
+        tensor / address (a device-to-device copy on the handle's stream)."""
+        self._set_params("okenv_qcnn_set_params", (params,), (self.qcnn_num_params(),))
+
+    def qcnn_get_params(self, out=None):
+        """The parameter vector as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
+        return self._get_state("okenv_qcnn_get_params", {"params": self.qcnn_num_params()}, None if out is None else {"params": out})["params"]
+
+    def qcnn_set_epsilon(self, epsilon):
+        capi.check(self._L.okenv_qcnn_set_epsilon(self._h, float(epsilon)), self._h)
+        self.qcnn_config.epsilon = float(epsilon)
+
+    def qcnn_set_draw_offset(self, word=None):
+        """A device uint32 word (tensor or address) added to the draw index of every later qcnn_act; None removes it."""
+        self._set_draw_offset("okenv_qcnn_set_draw_offset", word)
+
+    def _qcnn_frame_bytes(self):
+        return self.N * self.qcnn_config.image_size ** 2 * 4
+
+    def qcnn_act(self, frames, record=None, stages=None):
+        """The Q-network's greedy or epsilon-greedy action of every agent from `frames`, a device uint8 tensor / address
+        [N][S][S][4], enqueued on the handle's stream without a synchronisation.  record: None, or a dict of device tensors /
+        addresses under "q" [N,A] float32, "action" [N] int64, "value" [N] float32 and "alive" [N] uint8, each optional.  stages: None
+        for the act, or a sum of capi.QCNN_STAGE_* to run only those kernels (okenv_debug_qcnn_stages, for measurement)."""
+        A = self.qcnn_config.num_actions
+        sizes = record and {"q": self.N * A * 4, "action": self.N * 8, "value": self.N * 4, "alive": self.N}
+        if stages is None:
+            self._act("okenv_qcnn_act", capi.OkenvQcnnRecord, record, sizes, capi.ptr(frames), self._qcnn_frame_bytes())
+        else:
+            rec = None if record is None else C.byref(capi.fill_pointers(capi.OkenvQcnnRecord(), record, "record", sizes))
+            capi.check(self._L.okenv_debug_qcnn_stages(self._h, capi.ptr(frames), self._qcnn_frame_bytes(), rec, int(stages)), self._h)
+
+    def qcnn_ring_create(self, capacity, push_all=False):
+        """Attaches the frame ring of `capacity` transitions (state, next_state [C,S,S] float32 grey planes, action, reward, done [C]);
+        an earlier one is dropped and its memory freed: a HIP graph that captured qcnn_push before this call must not be replayed."""
+        capi.check(self._L.okenv_qcnn_ring_create(self._h, int(capacity), capi.REPLAY_PUSH_ALL if push_all else 0), self._h)
+        self.qcnn_ring_capacity = int(capacity)
+
+    def qcnn_ring_reset(self):
+        capi.check(self._L.okenv_qcnn_ring_reset(self._h), self._h)
+
+    def qcnn_ring_size(self):
+        """(transitions in the ring, transitions ever pushed); waits for the stream."""
+        size, pushed = C.c_int64(), C.c_int64()
+        capi.check(self._L.okenv_qcnn_ring_size(self._h, C.byref(size), C.byref(pushed)), self._h)
+        return size.value, pushed.value
+
+    def qcnn_ring_get(self, out=None):
+        """The ring's fields, all `capacity` slots: numpy arrays, or copied into the device tensors of the dict `out`.  Synchronises."""
+        if out is None:
+            out = {k: v for k, v in capi.qcnn_ring(self.qcnn_ring_capacity, self.qcnn_config.image_size).items() if isinstance(v, np.ndarray)}
+        capi.check(self._L.okenv_qcnn_ring_get(self._h, C.byref(capi.fill_pointers(capi.OkenvQcnnRing(), out, "ring"))), self._h)
+        return out
+
+    def qcnn_push(self, record, frames, next_frames, reward=None):
+        """Appends the transitions of the step that has just run: `record` is the dict the preceding qcnn_act was given ("action" and,
+        unless push_all, "alive"), `frames` what that act saw, `next_frames` the camera after the step; reward: None (the clearance
+        rule) or a device float32 tensor [N].  Three kernels on the handle's stream, no synchronisation."""
+        rec = capi.fill_pointers(capi.OkenvQcnnRecord(), {k: v for k, v in record.items() if k in ("action", "alive")}, "record")
+        capi.check(self._L.okenv_qcnn_push(self._h, C.byref(rec), capi.ptr(frames), capi.ptr(next_frames), self._qcnn_frame_bytes(), capi.ptr(reward)),
+                   self._h)
+
+    def qcnn_batch(self, B, out, mode="sequential", start_or_draw=0):
+        """B positions of the ring into the device tensors of the dict `out` ("state", "next_state" [B,S,S] float32, "action" [B]
+        int64, "reward", "done" [B] float32, "index" [B] int32, each optional): mode "uniform" (start_or_draw: the draw index) or
+        "sequential" (the walk's start).  One kernel on the handle's stream, no synchronisation."""
+        S = self.qcnn_config.image_size
+        sizes = {"state": B * S * S * 4, "next_state": B * S * S * 4, "action": B * 8, "reward": B * 4, "done": B * 4, "index": B * 4}
+        o = capi.fill_pointers(capi.OkenvQcnnBatchOut(), out, "batch", sizes)
+        capi.check(self._L.okenv_qcnn_batch(self._h, int(B), capi.QCNN_BATCH_MODES.get(mode, mode), int(start_or_draw), C.byref(o)), self._h)
+
     # ---- world-model racers (include/okenv.h, DESIGN.md section 27) --------------------------------------------------------------
     def world_create(self, config=None, **members):
         """Attaches the world-model racers (the reference's conv-VAE encoder and one controller per agent) to the handle; config: a
@@ -1120,6 +1205,7 @@ class BatchedEnvironment:
         E = int(state.shape[0])
         assert state.is_contiguous() and action.is_contiguous() and state.numel() == E * self.R and action.numel() == E * 2
         capi.check(self._L.okenv_gcl_set_expert(self._h, capi.ptr(state), capi.ptr(action), E), self._h)
+        self._gcl_bank_inputs = (state, action)  # alive until the next hand-over: the copies are only enqueued
 
     def gcl_cost(self, state, squashed, out):
         """out[s] = cost([state_s | squashed_s]) for the M rows of device tensors state [M,R], squashed [M,2]; out [M] float32."""

@@ -615,6 +615,65 @@ class VectorEnvironment:
             raise ValueError("image_act(frames) needs a contiguous uint8 tensor of shape (%d, %d, %d, 4) on %s" % (self.num_envs, S, S, self.device))
         self.env.cnn_act(frames, record)
 
+    # ---- Deep-Q image racers (include/okenv.h) ---------------------------------------------------------------
+    def enable_image_dqn(self, config, params, capacity=None, push_all=False):
+        """Attaches the reference's image Q-network (RLRacers/DQN_CNN) as a device driver and, with `capacity`, its frame ring.
+        config: a capi.qcnn_config(...) or a dict of its members (seed and agent_base default to the environment's); params: the flat
+        vector dqn_cnn.qcnn_params_from_state_dict makes, a float32 numpy array or a tensor.  set_image_dqn_params hands new
+        parameters over after an update."""
+        if isinstance(config, dict):
+            config = capi.qcnn_config(**dict({"seed": self.seed, "agent_base": self.agent_base}, **config))
+        self._qcnn_flat = self._attach_flat("qcnn", config, params)  # alive until the next hand-over: a tensor's copy is asynchronous
+        self.qcnn_config = config
+        self._qcnn_graphs = {}  # a captured launch carries the old shape, vector and ring
+        if capacity is not None:
+            self.env.qcnn_ring_create(capacity, push_all)
+            self.qcnn_push_all = bool(push_all)
+
+    def set_image_dqn_params(self, params):
+        """New parameters of the attached Q-network: a device tensor is copied device to device on the environment's stream."""
+        if torch.is_tensor(params):
+            params = params.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        self.env.qcnn_set_params(params)
+        self._qcnn_flat = params
+
+    def set_image_dqn_epsilon(self, epsilon):
+        self.env.qcnn_set_epsilon(epsilon)
+        self._qcnn_graphs = {}  # a captured launch carries the old value
+
+    def _check_qcnn_frames(self, what, frames):
+        S = self.qcnn_config.image_size
+        if (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.device != self.device
+                or tuple(frames.shape) != (self.num_envs, S, S, 4)):
+            raise ValueError("%s needs a contiguous uint8 tensor of shape (%d, %d, %d, 4) on %s" % (what, self.num_envs, S, S, self.device))
+
+    def image_dqn_act(self, frames, record=None):
+        """The Q-network's action of every agent from `frames`, a contiguous uint8 tensor [N, S, S, 4] on this device (camera()'s,
+        rendered at the network's image_size), written into `throttle` / `steering`: two kernels on the environment's stream, no
+        synchronisation, usable inside capture(body).  record: optional dict of device tensors ("q" [N,A], "value" [N] float32,
+        "action" [N] int64, "alive" [N] uint8) that receive the sample."""
+        self._check_qcnn_frames("image_dqn_act(frames)", frames)
+        self.env.qcnn_act(frames, record)
+
+    def image_dqn_push(self, record, frames, next_frames, reward=None):
+        """Appends the transitions of the step that has just run to the frame ring: `record` as the preceding image_dqn_act filled it,
+        `frames` what it saw, `next_frames` the camera after the step; reward: None for the clearance reward, or a device float32
+        tensor [N].  Usable inside capture(body)."""
+        self._check_qcnn_frames("image_dqn_push(frames)", frames)
+        self._check_qcnn_frames("image_dqn_push(next_frames)", next_frames)
+        self.env.qcnn_push(record, frames, next_frames, reward)
+
+    def image_dqn_batch(self, B, mode="sequential", start_or_draw=0, out=None):
+        """B positions of the frame ring as a dict of device tensors (state, next_state [B,S,S]; action int64, reward, done, index
+        int32 [B]); `out`: such a dict to fill in place."""
+        S = self.qcnn_config.image_size
+        if out is None:
+            f = dict(dtype=torch.float32, device=self.device)
+            out = dict(state=torch.empty((B, S, S), **f), next_state=torch.empty((B, S, S), **f), action=torch.empty(B, dtype=torch.int64, device=self.device),
+                       reward=torch.empty(B, **f), done=torch.empty(B, **f), index=torch.empty(B, dtype=torch.int32, device=self.device))
+        self.env.qcnn_batch(B, out, mode, start_or_draw)
+        return out
+
     # ---- world-model racers (include/okenv.h, DESIGN.md section 27) ------------------------------------------------------------------
     def enable_world_racers(self, config, encoder_params, controllers=None):
         """Attaches the reference's world-model racers (WorldModelVaeRnn: the conv-VAE encoder, one controller per agent) as a device
