@@ -37,7 +37,8 @@ PATHS = {
     "l4": (16, 2, 1, 48, 8, 64, 4),
     "z128": (3, 2, 2, 64, 2, 32, 2),
 }
-COUNTS = (1, 17, 33)  # agents: a partial row tile, a full one and a partial one, several
+COUNTS = (1, 17, 33)  # agents: a partial row tile, a full one and a partial one, several (every wave and a second and third row workgroup
+#                       of the layer kernel: tests/_population_cases.py's MEMORY_COUNTS, in tests/test_gpu_image_populations.py)
 
 
 def shape_of(name):

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _memory_numpy as mirror
+import _population_cases as P
 import _world_numpy as wmirror
 
 f32 = np.float32
@@ -215,8 +216,38 @@ def test_skip_crashed_leaves_crashed_agents_alone(capi):
     assert same(got["hidden_state"][[1, 3]], hidden[[1, 3]]) and same(got["throttle"][[1, 3]], thr[[1, 3]]) and same(got["steer"][[1, 3]], steer[[1, 3]])
 
 
+@pytest.mark.parametrize("pattern", P.HOST_PATTERNS)
+def test_skip_crashed_host_entry_at_a_population_pattern(capi, pattern):
+    """The host entry with skip_crashed at 129 agents under a crashed pattern of tests/_population_cases.py, which
+    tests/test_gpu_image_populations.py takes as the truth for the device: against the mirror, bit for bit as everywhere in this file,
+    at the agents on both sides of every wave's edge (the mirror is slow); for every other agent what needs no mirror."""
+    name, N = "h16", P.HOST_N
+    w, mem, Z, H, L, h = mirror.shape_of(name)
+    enc, net, ctrl, frames, hidden, thr, steer = drawn(name, 6, N)
+    crashed = P.crashed(pattern, N)
+    sizes = {"mu": (N, Z), "hidden": (N, H), "prediction": (N, Z), "state": (N, Z + H), "out": (N,), "action": (N, 2)}
+    into = {k: np.full(s, 77, f32) for k, s in sizes.items()}
+    into.update(alive=np.full(N, 77, np.uint8), hidden_state=hidden.copy(), throttle=thr.copy(), steer=steer.copy())
+    got = capi.memory_act_host(*configs(capi, name, world_more=dict(skip_crashed=1)), enc, net, ctrl, frames, None, None, None, crashed, into=into)
+    at = [a for a in P.HOST_MIRRORED if not crashed[a]]
+    assert len(at) >= 3 and any(crashed[a] for a in P.HOST_MIRRORED)
+    want = mirror.act(name, 1, enc, net, ctrl[at], frames[at], hidden[at], thr[at], steer[at])
+    for k in KEYS:
+        assert same(got[k][at], want[k]), "%s %s: differ by up to %.3g" % (pattern, k, float(np.abs(got[k][at] - want[k]).max()))
+    gone = crashed != 0
+    n_alive = int((~gone).sum())
+    for k in capi.MEMORY_RECORD:
+        assert (got[k][gone] == 77).all(), k  # crashed agents untouched
+        assert np.isfinite(got[k][~gone]).all() and (got[k][~gone].reshape(n_alive, -1) != 77).all(), k
+    assert same(got["hidden_state"][gone], hidden[gone]) and same(got["throttle"][gone], thr[gone]) and same(got["steer"][gone], steer[gone])
+    assert np.isfinite(got["hidden_state"]).all() and (got["hidden_state"][~gone] != hidden[~gone]).any(axis=(1, 2)).all()
+    assert (got["throttle"][~gone] == 100.0).all() and (got["steer"][~gone] != steer[~gone]).all()
+    assert len(set(got["out"][~gone].tolist())) == n_alive
+
+
 def test_plan_functions_equal_the_mirror(capi):
     L_ = capi.load()
+    assert P.MEMORY_ROWS == capi.MEMORY_ROWS == mirror.ROWS and P.MEMORY_WAVE_ROWS * 8 == P.MEMORY_ROWS
     for name in mirror.SHAPES:
         w, mem, Z, H, L, h = mirror.shape_of(name)
         for carry in (0, 1):

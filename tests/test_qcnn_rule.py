@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import _population_cases as P
 import _qcnn_numpy as mirror
 
 f32 = np.float32
@@ -226,6 +227,40 @@ def test_push_host_equals_the_mirror(capi, capacity, push_all, with_reward):
     if not with_reward:
         assert set(np.unique(got["reward"][got["done"] == 1.0])) <= {f32(-200.0)} and -200.0 < got["reward"][got["done"] == 0.0].min()
         assert got["reward"].max() <= 200.0
+
+
+@pytest.mark.parametrize("case", range(len(P.RING_CASES)), ids=["%s-%d-%s-%d" % c for c in P.RING_CASES])
+def test_push_host_equals_the_mirror_at_the_population_cases(capi, case):
+    """The (N, selection, capacity) cases tests/test_gpu_image_populations.py holds the device to (tests/_population_cases.py), three
+    pushes each, field by field and `pushed`.  The mirror pushes the transitions one by one, which is the rule's "as if": of n > C
+    selected agents the last C survive because the earlier ones are overwritten."""
+    name, N, selection, capacity = P.RING_CASES[case]
+    shape = mirror.SHAPES[name]
+    S, A = shape["image_size"], shape["num_actions"]
+    got, want = capi.qcnn_ring(capacity, S), mirror.ring(capacity, S)
+    for r in (got, want):
+        for k in ("state", "next_state", "reward", "done"):
+            r[k].fill(-7.0)
+        r["action"].fill(-7)
+    expected = 0
+    for push in range(P.RING_PUSHES):
+        x = P.ring_inputs(S, A, N, selection, push, 3)
+        push_all = x["alive"] is None
+        expected += N if push_all else int(x["alive"].sum())
+        kw = dict(reward=x["reward"] if case % 2 else None, dist=x["dist"], push_all=push_all)
+        capi.qcnn_push_host(got, x["action"], x["alive"], x["frames"], x["next_frames"], x["crashed"], **kw)
+        mirror.push(want, x["action"], x["alive"], x["frames"], x["next_frames"], x["crashed"], **kw)
+        assert got["pushed"] == want["pushed"] == expected
+        for k in ("state", "next_state", "action", "reward", "done"):
+            assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), (push, k)
+    if expected < capacity:  # slots no transition reached keep their sentinel
+        assert (got["state"][expected:] == -7.0).all() and (got["action"][expected:] == -7).all()
+    assert (expected == 0) == (selection == "nobody")
+
+
+def test_population_constants_are_the_kernels(capi):
+    assert P.HEAD_AGENTS == capi.QCNN_AGENTS == capi.CNN_AGENTS == mirror.AGENTS
+    assert P.LIST_THREADS == P.REPLAY_THREADS == 4 * P.WAVE and P.LIST_THREADS % P.HEAD_AGENTS == 0 and P.HEAD_AGENTS % P.HEAD_SLOTS == 0
 
 
 @pytest.mark.parametrize("B", [1, 32, 50])

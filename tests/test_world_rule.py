@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _oracle as O
+import _population_cases as P
 import _world_numpy as mirror
 
 f32 = np.float32
@@ -165,6 +166,32 @@ def test_skip_crashed_leaves_crashed_agents_alone(capi):
         assert L.okenv_world_act_host(C.byref(c), *bad) == INVALID, at
     assert L.okenv_world_act_host(C.byref(c), *(args[:2] + [-1] + args[3:])) == INVALID
     assert L.okenv_world_act_host(None, *args) == INVALID
+
+
+@pytest.mark.parametrize("pattern", P.HOST_PATTERNS)
+def test_skip_crashed_host_entry_at_a_population_pattern(capi, pattern):
+    """The host entry with skip_crashed at 129 agents under a crashed pattern of tests/_population_cases.py, which
+    tests/test_gpu_image_populations.py takes as the truth for the device: against the mirror, bit for bit as everywhere in this file,
+    at the agents on both sides of every wave's edge (the mirror is slow); for every other agent what needs no mirror."""
+    cfg = mirror.SHAPES["tiny"]
+    N, Z = P.HOST_N, cfg["latent"]
+    enc, ctrl = mirror.draw_params(cfg, 6, N)
+    frames = mirror.draw_frames(16, 6, n=N)
+    rot = np.random.default_rng(6).uniform(-180.0, 180.0, N).astype(f32)
+    crashed = P.crashed(pattern, N)
+    into = dict(mu=np.full((N, Z), 77, f32), state=np.full((N, Z + 2), 77, f32), out=np.full(N, 77, f32), throttle=np.full(N, 77, f32),
+                steer=np.full(N, 77, f32), alive=np.full(N, 77, np.uint8))
+    got = capi.world_act_host(config(capi, "tiny", skip_crashed=1), enc, ctrl, frames, rot, crashed, into=into)
+    at = [a for a in P.HOST_MIRRORED if not crashed[a]]
+    assert len(at) >= 3 and any(crashed[a] for a in P.HOST_MIRRORED)
+    want = mirror.act(cfg, enc, ctrl[at], frames[at], rot[at])
+    for k in ("mu", "state", "out", "throttle", "steer"):
+        assert same(got[k][at], want[k]), "%s %s: differ by up to %.3g" % (pattern, k, float(np.abs(got[k][at] - want[k]).max()))
+    gone = crashed != 0
+    for k, v in got.items():
+        assert (v[gone] == 77).all(), k  # crashed agents untouched
+        assert np.isfinite(v[~gone]).all() and (v[~gone].reshape(int((~gone).sum()), -1) != 77).all(), k
+    assert (got["alive"][~gone] == 1).all() and len(set(got["out"][~gone].tolist())) == int((~gone).sum())
 
 
 @pytest.mark.parametrize("track", ["Austin", "Silverstone"])
