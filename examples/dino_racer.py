@@ -1,0 +1,100 @@
+"""The reference's image transformer driver (DinoControl/) for a whole population: demonstrations with bird's-eye frames from the
+device's potential-field expert, the 384-128-64-1 policy head trained on a FROZEN vision transformer's class token in PyTorch with the
+reference's recipe, and N agents driven by it at a constant throttle -- the forward once per step in PyTorch or, with
+--device-policy, in the device's act kernels.
+
+    python examples/dino_racer.py [--agents 32] [--demo-steps 32] [--epochs 3] [--steps 64] [--episodes 1] [--graph-chunk 8]
+                                  [--backbone file.pth] [--small] [--device-policy] [--track Austin]
+
+1. record: every living agent's frame and the expert's action (demonstrations.collect_demonstrations(images=True));
+2. train: the head only, weighted MSE (weight 5 where |label| > 0.1) against the expert's steering / 10, Adam 1e-4;
+3. hand over (--device-policy): the weights as one flat vector (dino.vit_params_from_state_dict -> enable_vit_policy);
+4. drive: `step`, `camera()`, the forward, throttle 100 and steering clamp(10 x output) (dino.drive), and the share of agents that
+   survive every episode.
+The camera renders at the network's own size (224 x 224, or 32 x 32 with --small): there is no resize.
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from openkitchen_amd import dino  # noqa: E402
+from openkitchen_amd.demonstrations import collect_demonstrations  # noqa: E402
+from openkitchen_amd.flow import demonstration_rows  # noqa: E402
+from openkitchen_amd.torch_env import VectorEnvironment  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--agents", type=int, default=32)
+    ap.add_argument("--demo-steps", type=int, default=32)
+    ap.add_argument("--epochs", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--episodes", type=int, default=1)
+    ap.add_argument("--graph-chunk", type=int, default=8)
+    ap.add_argument("--track", default="Austin")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--backbone", default=None, help="a state dict of timm's vit_small_patch8_224.dino (torch.save); without it the backbone is "
+                    "randomly initialised and frozen: a random-feature baseline, not the reference's pretrained features")
+    ap.add_argument("--small", action="store_true", help="a reduced network (32 x 32 frames, width 32, 2 blocks) for the tests")
+    ap.add_argument("--device-policy", action="store_true")
+    a = ap.parse_args(argv)
+    torch.manual_seed(a.seed)
+    shape = dict(dino.SMALL) if a.small else {}
+    heads = shape.get("heads", 6)
+    venv = VectorEnvironment(a.track, a.agents, auto_reset=False, randomize_lane=True, randomize_heading=True, seed=a.seed)
+    model = dino.ViT(**shape).to(venv.device).eval()
+    if a.backbone:
+        dino.load_backbone(model, torch.load(a.backbone, map_location=venv.device))
+    for p in model.backbone_parameters():
+        p.requires_grad_(False)
+    S = model.image_size
+    venv.enable_camera(width=S, height=S, fmt="rgba")
+    # 1. demonstrations (the steering clamp keeps the expert inside the policy's range of +-10 degrees)
+    venv.enable_expert("potfield", lookahead=2, goal_wrap=False, clamp_deg=dino.STEER_SCALE)
+    demos = collect_demonstrations(venv, a.demo_steps, images=True, seed=a.seed)
+    frames, actions = demonstration_rows(demos)
+    print("recorded %d frames of living agents out of %d" % (frames.shape[0], a.agents * a.demo_steps))
+    # 2. training
+    t0 = time.perf_counter()
+    losses = dino.train(model, frames, actions, epochs=a.epochs, seed=a.seed)
+    print("trained the head for %d epochs on a %s backbone in %.1f s: loss %s"
+          % (a.epochs, "given" if a.backbone else "random frozen", time.perf_counter() - t0, " ".join("%.4g" % v for v in losses)))
+    # 3. hand-over
+    sd = model.state_dict()
+    cfg = dino.vit_config_from_state_dict(sd, heads=heads)
+    if a.device_policy:
+        venv.enable_vit_policy(cfg, dino.vit_params_from_state_dict(sd, heads=heads))
+    # the first driven step, recorded: the PyTorch forward's output and, with --device-policy, the device's on the same frames
+    venv.reset()
+    venv.step()
+    frame = venv.camera()
+    with torch.no_grad():
+        out_torch = model(dino.frames_to_input(frame))[:, 0].contiguous()
+    first = {"out_torch": out_torch, "out": out_torch}
+    if a.device_policy:
+        first["out"] = torch.empty(a.agents, device=venv.device)
+        venv.vit_act({"output": first["out"]}, frames=frame)
+        print("first step: max |device - PyTorch forward| = %.4g on the output" % float((first["out"] - out_torch).abs().max()))
+    # 4. driving
+    survival = []
+    for episode in range(a.episodes):
+        t0 = time.perf_counter()
+        steps = dino.drive(venv, model, a.steps, graph_chunk=a.graph_chunk, policy="device" if a.device_policy else "torch")
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        survival.append(float((~venv.done).float().mean()))
+        print("episode %d: %d agents, %d steps with the %s in %.3f s (%.3g agent-steps/s); survival %.3f"
+              % (episode, a.agents, steps, "device policy" if a.device_policy else "PyTorch forward", dt, a.agents * steps / dt, survival[-1]))
+    out = {"model": model, "config": cfg, "first": first, "survival": survival, "losses": losses,
+           "throttle": venv.throttle.clone(), "steering": venv.steering.clone()}
+    print("actions finite %s" % bool(torch.isfinite(out["throttle"]).all() and torch.isfinite(out["steering"]).all()))
+    venv.close()
+    return out
+
+
+if __name__ == "__main__":
+    main()

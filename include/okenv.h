@@ -1420,6 +1420,64 @@ OKENV_API int okenv_qcnn_batch_host(const okenv_qcnn_ring *ring, int32_t capacit
 OKENV_API int okenv_debug_qcnn_grey_host(int32_t image_size, int32_t n, const uint8_t *frames, float *planes);
 OKENV_API int okenv_debug_qcnn_forward_planes_host(const okenv_qcnn_config *config, const float *params, int32_t n, const float *planes, float *q);
 
+/* ---- Image transformer driver --------------------------------------------------------------------------------
+ * DinoControl's frozen vision transformer (timm's vit_small_patch8_224.dino) and its 384-128-64-1 policy head, driven as
+ * main_dino_control.cpp:80-89 drives them, for every agent of the handle: from the camera's RGBA8 frames (okenv_render_views, rendered
+ * at image_size x image_size; the reference's bicubic resize is not part of the rule) the per-channel normalisation, the patch
+ * embedding, the class token and positional table, `depth` pre-norm blocks (attention, GELU feed-forward), the final LayerNorm of the
+ * class token and the head, to throttle_delta = throttle and steering_delta = clamp(output * steer_scale, +-steer_scale).  Inference
+ * only.  The rule is written out in include/okenv_vit.h (ok_vit_*); all matrix work runs on the f32-input matrix cores.  The parameter
+ * vector is torch's parameters() order of openkitchen_amd/dino.py's ViT (ok_vit_offsets); every weight must be finite. */
+typedef struct okenv_vit_config {
+    int32_t image_size;      /* S: a multiple of patch, (S / patch)^2 + 1 <= 1024 tokens   (the reference: 224)        */
+    int32_t patch;           /* 4, 8 or 16                                                 (8)                         */
+    int32_t dim;             /* D: multiple of 16, 16 .. 768                               (384)                       */
+    int32_t heads;           /* dim / heads a multiple of 16, at most 64                   (6)                         */
+    int32_t depth;           /* 1 .. 12                                                    (12)                        */
+    int32_t dim_feedforward; /* multiple of 16, 16 .. 4 dim                                (1536)                      */
+    int32_t head_hidden1;    /* multiples of 16, 16 .. 2048                                (128)                       */
+    int32_t head_hidden2;    /*                                                            (64)                        */
+    float   mean[3], std[3]; /* per channel, of pixel / 255; std > 0                       (ImageNet's)                */
+    float   ln_eps;          /* inside every LayerNorm's root; > 0                         (1e-6)                      */
+    float   throttle;        /* the constant throttle_delta; finite                        (100)                       */
+    float   steer_scale;     /* steering_delta per unit of the output and its clamp; >= 0  (10)                        */
+    int32_t agents_per_pass; /* agents whose activations the workspace holds; 0: as many as fit workspace_bytes, at least one */
+    int64_t workspace_bytes; /* read when agents_per_pass is 0; 0: 1 GiB                                               */
+} okenv_vit_config;
+
+/* What an act can leave behind for the caller, device pointers, each may be NULL */
+typedef struct okenv_vit_record {
+    float   *action;    /* [N][2] throttle_delta, steering_delta                  */
+    float   *output;    /* [N]    the head's output                               */
+    float   *embedding; /* [N][D] the class token behind the final LayerNorm      */
+    uint8_t *alive;     /* [N]    1 where the agent was not crashed               */
+} okenv_vit_record;
+
+/* LDS bytes of the largest of the act's kernels for the shape: a pure host function.  A shape is accepted only if this fits 160 KB.
+ * 0 for a NULL config or a shape outside the rule's limits. */
+OKENV_API int64_t okenv_vit_lds_bytes(const okenv_vit_config *config);
+/* Attaches a policy to the handle (replaces an earlier one: its parameters are forgotten).  All device memory, the activations'
+ * workspace included, is allocated here.  OKENV_ERR_INVALID for NULL arguments, a shape outside the limits above, an LDS plan
+ * beyond 160 KB, a workspace beyond the kernels' index range or non-finite constants. */
+OKENV_API int okenv_vit_create(okenv_t h, const okenv_vit_config *config);
+OKENV_API int okenv_vit_num_params(okenv_t h, int32_t *num_params);
+/* New parameters from a host or device pointer.  No synchronisation. */
+OKENV_API int okenv_vit_set_params(okenv_t h, const float *params);
+/* The parameters, in the same order, to a host or device pointer; synchronises. */
+OKENV_API int okenv_vit_get_params(okenv_t h, float *params);
+/* Acts for every agent, crashed ones included, from frames (device, 4-byte aligned, [N][S][S][4] uint8, frame_bytes = N S S 4 in
+ * all): writes OKENV_F_THROTTLE, OKENV_F_STEER and the record (rec may be NULL).  A fixed sequence of 2 + 7 depth kernels per pass on
+ * the handle's stream, no synchronisation, no allocation: capturable beside okenv_step and okenv_render_views.  OKENV_ERR_STATE before
+ * okenv_vit_create or okenv_vit_set_params; OKENV_ERR_INVALID for NULL frames or another frame_bytes. */
+OKENV_API int okenv_vit_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_vit_record *rec);
+/* The same rule on host arrays, no GPU needed: frames [n][S][S][4]; crashed [n] or NULL; every output may be NULL: throttle, steer,
+ * output [n], embedding [n][D], alive [n]. */
+OKENV_API int okenv_vit_act_host(const okenv_vit_config *config, const float *params, int32_t n, const uint8_t *frames, const uint8_t *crashed,
+                                 float *throttle, float *steer, float *output, float *embedding, uint8_t *alive);
+/* The attention piece alone (host pointers): qkv [seqs][T][3 heads dh] -> ctx [seqs][T][heads dh], on GPU `device` through the act's
+ * own kernel; device < 0 (OKENV_DEBUG_ON_HOST) evaluates ok_vit_attend on the host.  1 <= T <= 1024, dh a multiple of 16 up to 64. */
+OKENV_API int okenv_debug_vit_attend(int32_t device, int32_t seqs, int32_t T, int32_t heads, int32_t dh, const float *qkv, float *ctx);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.
@@ -1740,6 +1798,7 @@ enum okenv_debug_fn {
     OKENV_FN_EXPERT_NORMALIZE_ANGLE, /* ok_expert_normalize_angle_deg */
     OKENV_FN_SINCOS_PAIR,            /* ok_sincosf_pair(a, b): out0 and out1 hold 2 n floats, the sine and cosine of a[i] in
                                         out0[2 i], out0[2 i + 1], those of b[i] in out1[2 i], out1[2 i + 1] */
+    OKENV_FN_ERF,                    /* ok_erff */
     OKENV_NUM_DEBUG_FNS
 };
 #define OKENV_DEBUG_ON_HOST (-1)

@@ -591,6 +591,51 @@ OK_HD float ok_logf(const float x)
     return (float)r;
 }
 
+/* erf for the image transformer's GELU (okenv_vit.h), evaluated in fp64 with IEEE operations and explicit FMAs only and rounded once to
+ * fp32, as ok_tanhf and ok_expf are.  Four pieces in a = |x|, each the interpolant at the Chebyshev nodes of its interval
+ * (tools/fit_math.py prints the rows below and the error of the ROUNDED polynomials):
+ *     a <  1:       erf a = a G(a^2), G of degree 12                       (relative error 2^-55.8; G(0) = 2 / sqrt(pi))
+ *     1 <= a < 4:   erf a = H_c(a - c), c = 1.5, 2.5, 3.5, H_c of degree 17 (relative error 2^-54.2 each)
+ *     a >= 4:       1 (erf 4 = 1 - 1.5e-8 rounds to 1.0f; the first argument that gives 1.0f is about 3.8325, inside the last piece)
+ * all by Horner's rule in FMAs.  The branch points are 1, 2, 3 and 4.  The sign is put back at the end, so the function is odd in the
+ * bits; a < 1 covers +-0 (a G = +0, negated for -0) and the subnormals (one fp64 product, then the single rounding); +-inf give +-1; NaN
+ * fails every comparison and is returned as it came.  The fp64 value is within 2^-52 of erf, so the fp32 result is never more than one
+ * ulp from the rounded exact value (tests/test_erf_rule.py counts the arguments where it is not equal). */
+OK_HD float ok_erff(const float x)
+{
+    const double G[13] = {0x1.20dd750429b6dp+0, -0x1.812746b0379e6p-2, 0x1.ce2f21a042b30p-4, -0x1.b82ce31284e00p-6, 0x1.565bcd0dbaa38p-8,
+                          -0x1.c02db3dac435fp-11, 0x1.f9a321d5b8e1ep-14, -0x1.f4d1e3183f7aep-17, 0x1.b9df224ca4b97p-20, -0x1.5f1ecb6f0764cp-23,
+                          0x1.f7b4bf3b13964p-27, -0x1.389d4f2641625p-30, 0x1.05ffd737fb32ep-34};
+    const double H[3][18] = {
+        {0x1.eea5557137ae0p-1, 0x1.e723726b824a9p-4, -0x1.6d5a95d0a1b3ap-3, 0x1.1c2a02beb6a99p-3, -0x1.6d5a95d0a8e2dp-5, -0x1.e723726b75a2bp-7,
+         0x1.3ca3d72e94d2cp-6, -0x1.36d73a65ecb0ap-8, -0x1.35ae4fb43b234p-9, 0x1.c0380d88e655ap-10, -0x1.85b3d151e9cfdp-14, -0x1.0acf353ecb714p-12,
+         0x1.45cc7994de082p-14, 0x1.2d574ba32d17bp-16, -0x1.d70efbc5f9ed6p-17, 0x1.32b587a24f780p-21, 0x1.7c67db8e155e0p-20, -0x1.305d37a851c9dp-22},
+        {0x1.ffcaa8f4c9beap-1, 0x1.1d83170fbf6fcp-9, -0x1.64e3dcd3af2d3p-8, 0x1.119da0c46cc88p-7, -0x1.1a89b97cf1214p-7, 0x1.90e81283fccadp-8,
+         -0x1.6ecdbf63b4dcep-9, 0x1.1c610bc8e5f86p-11, 0x1.11551b52fb796p-12, -0x1.06717857ad0fap-12, 0x1.4a84c20123815p-14, 0x1.58bbca2bba994p-18,
+         -0x1.d88c48f8a82b3p-17, 0x1.3ad68181439ecp-18, 0x1.9f3af4d2b1565p-23, -0x1.595d63766c65ep-21, 0x1.495bf0556d5dep-23, 0x1.8353e53661806p-26},
+        {0x1.ffffe710d565ep-1, 0x1.6a597219a93d4p-18, -0x1.3d0e43d6734d9p-16, 0x1.62ccea63cb29ap-15, -0x1.1c07721adce45p-14, 0x1.586bafc9b36e3p-14,
+         -0x1.46153fb62cc1cp-14, 0x1.e827fafc968b1p-15, -0x1.1f63056912abap-15, 0x1.013525a7dacb3p-16, -0x1.3773e12d91261p-18, 0x1.dd8021aae75eap-22,
+         0x1.dc69f55490dbfp-22, -0x1.43f06e7cae34dp-22, 0x1.8ddc35b8e5308p-24, -0x1.83eccdb1df23fp-28, -0x1.343ba005050efp-27, 0x1.09106bf9376f0p-28}};
+    if (!(x == x)) return x;
+    const double a = __builtin_fabs((double)x);
+    double r;
+    if (a < 1.0) {
+        const double z = a * a;
+        double p = G[12];
+        for (int i = 11; i >= 0; --i) p = OK_FMA(p, z, G[i]);
+        r = a * p;
+    } else if (a < 4.0) {
+        const int piece = a < 2.0 ? 0 : (a < 3.0 ? 1 : 2);
+        const double t = a - (1.5 + (double)piece);
+        double p = H[piece][17];
+        for (int i = 16; i >= 0; --i) p = OK_FMA(p, t, H[piece][i]);
+        r = p;
+    } else {
+        r = 1.0;
+    }
+    return (float)(__builtin_signbit(x) ? -r : r);
+}
+
 /* ---- RLRacers: the shared-network actors -----------------------------------
  * updateAction of PPOAgent (RLRacers/PPO/PPOAgent.hpp:68-102 with Actor.hpp:20-27 and Critic.hpp), of the REINFORCE agent
  * (Reinforce/Policy.hpp:22-29; its Dropout is okenv_reinforce.h's, on top of this rule) and of DQAgent (Deep_Q_Learning/DQAgent.hpp:85-104, with one hidden layer): ONE

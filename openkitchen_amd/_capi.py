@@ -51,7 +51,7 @@ REINFORCE_SUM, REINFORCE_MEAN = 0, 1
 REINFORCE_REDUCE = {"sum": REINFORCE_SUM, "mean": REINFORCE_MEAN}
 REINFORCE_KERNELS = ("grad", "step")
 # okenv_debug_math (include/okenv.h): enum okenv_debug_fn in order, and the device number that means "evaluate on the host"
-DEBUG_FNS = ("sincos", "tanh", "exp", "log", "atan2", "normalize_angle", "expert_normalize_angle", "sincos_pair")
+DEBUG_FNS = ("sincos", "tanh", "exp", "log", "atan2", "normalize_angle", "expert_normalize_angle", "sincos_pair", "erf")
 DEBUG_ON_HOST = -1
 
 # every symbol include/okenv.h declares (tests/test_capi_symbols.py checks the library exports them all)
@@ -117,6 +117,8 @@ SYMBOLS = [
     "okenv_qcnn_set_epsilon", "okenv_qcnn_set_draw_offset", "okenv_qcnn_act", "okenv_debug_qcnn_stages", "okenv_qcnn_ring_create",
     "okenv_qcnn_ring_reset", "okenv_qcnn_ring_size", "okenv_qcnn_ring_get", "okenv_qcnn_push", "okenv_qcnn_batch", "okenv_qcnn_act_host",
     "okenv_qcnn_push_host", "okenv_qcnn_batch_host", "okenv_debug_qcnn_grey_host", "okenv_debug_qcnn_forward_planes_host",
+    "okenv_vit_lds_bytes", "okenv_vit_create", "okenv_vit_num_params", "okenv_vit_set_params", "okenv_vit_get_params", "okenv_vit_act",
+    "okenv_vit_act_host", "okenv_debug_vit_attend",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -793,6 +795,90 @@ def qcnn_grey_host(frames):
     return out
 
 
+# image transformer driver (include/okenv.h)
+VIT_LDS_BUDGET = 160 * 1024
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+class OkenvVitConfig(C.Structure):
+    _fields_ = [("image_size", C.c_int32), ("patch", C.c_int32), ("dim", C.c_int32), ("heads", C.c_int32), ("depth", C.c_int32),
+                ("dim_feedforward", C.c_int32), ("head_hidden1", C.c_int32), ("head_hidden2", C.c_int32), ("mean", C.c_float * 3),
+                ("std", C.c_float * 3), ("ln_eps", C.c_float), ("throttle", C.c_float), ("steer_scale", C.c_float),
+                ("agents_per_pass", C.c_int32), ("workspace_bytes", C.c_int64)]
+
+
+class OkenvVitRecord(C.Structure):
+    _fields_ = [("action", C.c_void_p), ("output", C.c_void_p), ("embedding", C.c_void_p), ("alive", C.c_void_p)]
+
+
+def vit_config(image_size=224, patch=8, dim=384, heads=6, depth=12, dim_feedforward=1536, head_hidden1=128, head_hidden2=64,
+               mean=IMAGENET_MEAN, std=IMAGENET_STD, ln_eps=1e-6, throttle=100.0, steer_scale=10.0, agents_per_pass=0, workspace_bytes=0):
+    """okenv_vit_config with the reference's shape and controls as defaults (DinoControl: timm's vit_small_patch8_224.dino, the
+    384-128-64-1 head, main_dino_control.cpp:80-89)."""
+    return OkenvVitConfig(int(image_size), int(patch), int(dim), int(heads), int(depth), int(dim_feedforward), int(head_hidden1),
+                          int(head_hidden2), (C.c_float * 3)(*map(float, mean)), (C.c_float * 3)(*map(float, std)), float(ln_eps),
+                          float(throttle), float(steer_scale), int(agents_per_pass), int(workspace_bytes))
+
+
+def vit_tokens(cfg):
+    return (cfg.image_size // cfg.patch) ** 2 + 1
+
+
+def vit_layout(cfg):
+    """ok_vit_offsets: where every piece of the parameter vector begins, as (name, offset, shape) in order; the names are timm's
+    state-dict keys with the head's behind them (openkitchen_amd/dino.py: DinoPolicy)."""
+    D, F, P, T = cfg.dim, cfg.dim_feedforward, cfg.patch, vit_tokens(cfg)
+    pieces = [("cls_token", (1, 1, D)), ("pos_embed", (1, T, D)), ("patch_embed.proj.weight", (D, 3, P, P)), ("patch_embed.proj.bias", (D,))]
+    for i in range(cfg.depth):
+        pre = "blocks.%d." % i
+        pieces += [(pre + "norm1.weight", (D,)), (pre + "norm1.bias", (D,)), (pre + "attn.qkv.weight", (3 * D, D)), (pre + "attn.qkv.bias", (3 * D,)),
+                   (pre + "attn.proj.weight", (D, D)), (pre + "attn.proj.bias", (D,)), (pre + "norm2.weight", (D,)), (pre + "norm2.bias", (D,)),
+                   (pre + "mlp.fc1.weight", (F, D)), (pre + "mlp.fc1.bias", (F,)), (pre + "mlp.fc2.weight", (D, F)), (pre + "mlp.fc2.bias", (D,))]
+    pieces += [("norm.weight", (D,)), ("norm.bias", (D,)), ("head.net.0.weight", (cfg.head_hidden1, D)), ("head.net.0.bias", (cfg.head_hidden1,)),
+               ("head.net.2.weight", (cfg.head_hidden2, cfg.head_hidden1)), ("head.net.2.bias", (cfg.head_hidden2,)),
+               ("head.output_layer.weight", (1, cfg.head_hidden2)), ("head.output_layer.bias", (1,))]
+    out, at = [], 0
+    for name, shape in pieces:
+        out.append((name, at, shape))
+        at += int(np.prod(shape))
+    return out
+
+
+def vit_num_params(cfg):
+    name, at, shape = vit_layout(cfg)[-1]
+    return at + int(np.prod(shape))
+
+
+def vit_lds_bytes(cfg):
+    """okenv_vit_lds_bytes: the largest LDS of the act's kernels for the shape, 0 outside the rule's limits.  No GPU needed."""
+    return int(load().okenv_vit_lds_bytes(C.byref(cfg)))
+
+
+def vit_act_host(cfg, params, frames, crashed=None):
+    """okenv_vit_act_host on numpy arrays: frames [n][S][S][4] uint8 -> dict(throttle, steer, output [n], embedding [n][D] float32,
+    alive [n]).  No GPU needed."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    params = np.ascontiguousarray(params, np.float32)
+    n = frames.shape[0]
+    assert frames.shape == (n, cfg.image_size, cfg.image_size, 4) and params.size == vit_num_params(cfg)
+    crashed = None if crashed is None else np.ascontiguousarray(crashed, np.uint8)
+    out = dict(throttle=np.empty(n, np.float32), steer=np.empty(n, np.float32), output=np.empty(n, np.float32),
+               embedding=np.empty((n, cfg.dim), np.float32), alive=np.empty(n, np.uint8))
+    check(load().okenv_vit_act_host(C.byref(cfg), ptr(params), n, ptr(frames), ptr(crashed), ptr(out["throttle"]), ptr(out["steer"]),
+                                    ptr(out["output"]), ptr(out["embedding"]), ptr(out["alive"])))
+    return out
+
+
+def debug_vit_attend(qkv, heads, device=DEBUG_ON_HOST):
+    """okenv_debug_vit_attend: qkv [seqs][T][3 heads dh] -> ctx [seqs][T][heads dh]; device < 0 evaluates the rule on the host."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    seqs, T, W = qkv.shape
+    D = W // 3
+    out = np.empty((seqs, T, D), np.float32)
+    check(load().okenv_debug_vit_attend(int(device), seqs, T, int(heads), D // int(heads), ptr(qkv), ptr(out)))
+    return out
+
+
 def qcnn_forward_planes_host(cfg, params, planes):
     """The network of okenv_qcnn_act_host on grey planes [n][S][S] float32 -> q [n][A] (a test hook).  No GPU needed."""
     planes, params = np.ascontiguousarray(planes, np.float32), np.ascontiguousarray(params, np.float32)
@@ -1438,6 +1524,15 @@ def load(build_if_missing=True):
     L.okenv_qcnn_batch_host.argtypes = [C.POINTER(OkenvQcnnRing), i32, i32, C.c_uint64, C.c_uint32, i32, i32, i64, C.POINTER(OkenvQcnnBatchOut)]
     L.okenv_debug_qcnn_grey_host.argtypes = [i32, i32, vp, vp]
     L.okenv_debug_qcnn_forward_planes_host.argtypes = [qc, vp, i32, vp, vp]
+    L.okenv_vit_lds_bytes.argtypes = [C.POINTER(OkenvVitConfig)]
+    L.okenv_vit_lds_bytes.restype = C.c_int64
+    L.okenv_vit_create.argtypes = [vp, C.POINTER(OkenvVitConfig)]
+    L.okenv_vit_num_params.argtypes = [vp, C.POINTER(i32)]
+    L.okenv_vit_set_params.argtypes = [vp, vp]
+    L.okenv_vit_get_params.argtypes = [vp, vp]
+    L.okenv_vit_act.argtypes = [vp, vp, i64, C.POINTER(OkenvVitRecord)]
+    L.okenv_vit_act_host.argtypes = [C.POINTER(OkenvVitConfig), vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.okenv_debug_vit_attend.argtypes = [i32, i32, i32, i32, i32, vp, vp]
     _lib = L
     return L
 

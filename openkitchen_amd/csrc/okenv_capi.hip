@@ -38,6 +38,7 @@
 #include "ok_world.h"
 #include "ok_memory.h"
 #include "ok_qcnn.h"
+#include "ok_vit.h"
 #include "ok_expert.h"
 
 namespace
@@ -619,6 +620,12 @@ struct okenv
     OkRing                  qcnn_ring{sizeof(int64_t)};
     int32_t                 qcnn_ring_side{0};
     long long              *d_qcnn_slots{nullptr};
+    // Image transformer driver (okenv_vit_create): the parameter vector in torch's order; the activations of the agents of one pass
+    // (vit_pass of them), allocated at create
+    OkDriver                vit_drv;
+    okenv_vit_config        vit{};
+    float                  *d_vit_work{nullptr};
+    size_t                  vit_work_cap{0}, vit_pass{0};
 };
 
 struct okenv_track
@@ -1496,7 +1503,8 @@ const DriverKind kActorDriver{&okenv::actor_drv, "okenv_actor_", "every attached
     kCnnDriver{&okenv::cnn_drv, "okenv_cnn_", "the policy needs its parameters", "the policy needs its parameters", true},
     kWorldDriver{&okenv::world_drv, "okenv_world_", "the encoder and the controllers need their parameters", "the vector needs its parameters", true},
     kMemoryDriver{&okenv::mem_drv, "okenv_memory_", "the network and the controllers need their parameters", "the vector needs its parameters", true},
-    kQcnnDriver{&okenv::qcnn_drv, "okenv_qcnn_", "the network needs its parameters", "the network needs its parameters", true};
+    kQcnnDriver{&okenv::qcnn_drv, "okenv_qcnn_", "the network needs its parameters", "the network needs its parameters", true},
+    kVitDriver{&okenv::vit_drv, "okenv_vit_", "the policy needs its parameters", "the policy needs its parameters", true};
 
 int driverRefuses(okenv *h, const int code, const DriverKind &k, const char *entry, const std::string &why)
 {
@@ -1793,6 +1801,81 @@ int qcnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const ok
             return rc;
     if ((stages & OKENV_QCNN_STAGE_HEAD_32) != 0U)
         return qcnnHead<2>(h, pl, p);
+    return OKENV_OK;
+}
+
+// One launch of the image transformer's linear kernel: the M x N outputs in tiles of 64 x 64
+template <int kSrc, int kEpi>
+void vitLinear(okenv *h, OkVitLinearParams p, const long M, const int K, const int N, const float *a, const long lda, const float *w, const float *bias,
+               float *out, const long ldo)
+{
+    p.M = M, p.K = K, p.N = N, p.a = a, p.lda = lda, p.w = w, p.bias = bias, p.out = out, p.ldo = ldo;
+    hipLaunchKernelGGL((okVitLinearKernel<kSrc, kEpi>), dim3(static_cast<unsigned>((M + kVitTile - 1) / kVitTile), static_cast<unsigned>((N + kVitTile - 1) / kVitTile)),
+                       dim3(kVitThreads), 0, h->stream, p);
+}
+
+// okenv_vit_act behind its OK_QUIESCE: the fixed launch sequence (ok_vit.h), once per pass of vit_pass agents, on the stream
+int vitAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_vit_record *rec)
+{
+    const char *missing = nullptr;
+    if (h != nullptr && h->vit_drv.ok)
+    {
+        const int S = h->vit.image_size;
+        if (!frames)
+            missing = "NULL argument";
+        else if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
+            missing = "frame_bytes is not num_agents x image_size x image_size x 4";
+        else if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
+            missing = "frames must be 4-byte aligned";
+    }
+    if (const int rc = actBegin(h, kVitDriver, 1U, missing))
+        return rc;
+    const ok_vit_shape  s  = okVitShape(h->vit);
+    const ok_vit_layout at = ok_vit_offsets(s);
+    const OkVitPlaces   pl = okVitPlaces(s);
+    const int           T = pl.T, D = s.D, F = s.ff;
+    const float        *prm = h->vit_drv.d;
+    const size_t        frame = static_cast<size_t>(s.S) * static_cast<size_t>(s.S) * 4U;
+    OkVitLinearParams   lp{};
+    lp.S = s.S, lp.P = s.P, lp.side = ok_vit_side(s), lp.T = T;
+    for (int c = 0; c < 3; ++c)
+        lp.mean[c] = h->vit.mean[c], lp.std[c] = h->vit.std[c];
+    lp.pos = prm + at.pos, lp.cls = prm + at.cls;
+    for (size_t a0 = 0; a0 < static_cast<size_t>(h->shape.N); a0 += h->vit_pass)
+    {
+        const size_t count = std::min(h->vit_pass, static_cast<size_t>(h->shape.N) - a0);
+        const long   M = static_cast<long>(count) * T;
+        float       *x = h->d_vit_work, *n = x + static_cast<size_t>(M) * D, *ctx = n + static_cast<size_t>(M) * D, *qkv = ctx + static_cast<size_t>(M) * D,
+              *hid = qkv + static_cast<size_t>(M) * 3U * D;
+        lp.frames = frames + a0 * frame;
+        vitLinear<kVitSrcPatch, kVitEpiPos>(h, lp, static_cast<long>(count) * (T - 1), ok_vit_patch_k(s), D, nullptr, 0, prm + at.pe_w, prm + at.pe_b, x, D);
+        OK_HIP(h, hipGetLastError());
+        const unsigned norm_blocks = static_cast<unsigned>((M + kVitNormRows - 1) / kVitNormRows);
+        OkVitAttendParams ap{};
+        ap.T = T, ap.D = D, ap.heads = s.heads, ap.dh = pl.dh, ap.qtiles = (T + kVitQueries - 1) / kVitQueries;
+        ap.scale = ok_lidar_scale(pl.dh), ap.qkv = qkv, ap.ctx = ctx;
+        for (int i = 0; i < s.depth; ++i)
+        {
+            const float *bp = prm + at.block0 + static_cast<size_t>(i) * at.block_stride;
+            hipLaunchKernelGGL(okVitNormKernel, dim3(norm_blocks), dim3(kVitThreads), 0, h->stream, M, D, x, bp + at.n1_g, bp + at.n1_b, h->vit.ln_eps, n);
+            vitLinear<kVitSrcPlain, kVitEpiNone>(h, lp, M, D, 3 * D, n, D, bp + at.qkv_w, bp + at.qkv_b, qkv, 3L * D);
+            hipLaunchKernelGGL(okVitAttendKernel, dim3(static_cast<unsigned>(count * s.heads * ap.qtiles)), dim3(kVitThreads),
+                               sizeof(float) * static_cast<size_t>(pl.attend), h->stream, ap);
+            vitLinear<kVitSrcPlain, kVitEpiResidual>(h, lp, M, D, D, ctx, D, bp + at.proj_w, bp + at.proj_b, x, D);
+            hipLaunchKernelGGL(okVitNormKernel, dim3(norm_blocks), dim3(kVitThreads), 0, h->stream, M, D, x, bp + at.n2_g, bp + at.n2_b, h->vit.ln_eps, n);
+            vitLinear<kVitSrcPlain, kVitEpiGelu>(h, lp, M, D, F, n, D, bp + at.fc1_w, bp + at.fc1_b, hid, F);
+            vitLinear<kVitSrcPlain, kVitEpiResidual>(h, lp, M, F, D, hid, F, bp + at.fc2_w, bp + at.fc2_b, x, D);
+            OK_HIP(h, hipGetLastError());
+        }
+        OkVitFinalParams fp{};
+        fp.st = h->st, fp.a0 = static_cast<long>(a0), fp.count = static_cast<int>(count), fp.s = s, fp.params = prm, fp.x = x;
+        fp.eps = h->vit.ln_eps, fp.throttle = h->vit.throttle, fp.steer_scale = h->vit.steer_scale;
+        if (rec != nullptr)
+            fp.rec = *rec;
+        hipLaunchKernelGGL(okVitFinalKernel, dim3(static_cast<unsigned>((count + kVitAgents - 1) / kVitAgents)), dim3(kLidarThreads),
+                           sizeof(float) * static_cast<size_t>(pl.final), h->stream, fp);
+        OK_HIP(h, hipGetLastError());
+    }
     return OKENV_OK;
 }
 
@@ -4729,6 +4812,117 @@ extern "C"
         return OKENV_OK;
     }
 
+    // ---- Image transformer driver (ok_vit.h) -----------------------------------------------------------------------------------
+
+    int64_t okenv_vit_lds_bytes(const okenv_vit_config *config)
+    {
+        return config != nullptr ? static_cast<int64_t>(okVitLdsBytes(okVitShape(*config))) : 0;
+    }
+
+    int okenv_vit_create(okenv_t h, const okenv_vit_config *config)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kVitDriver, "create", kGateHandle))
+            return rc;
+        if (const char *why = okVitCheckConfig(config))
+            return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "create", why);
+        const ok_vit_shape s = okVitShape(*config);
+        const size_t       pass = okVitAgentsPerPass(*config, static_cast<size_t>(h->shape.N));
+        if (const char *why = okVitWorkspaceBad(*config, pass))
+            return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "create", why);
+        if (const int rc = driverCreateFlat(h, kVitDriver, static_cast<size_t>(ok_vit_offsets(s).total), kernelOf(okVitAttendKernel)))
+            return rc;
+        h->vit_drv.ok = false; // (until the workspace stands)
+        if (const int rc = raiseLdsLimit(h, {kernelOf(okVitFinalKernel)}))
+            return rc;
+        const size_t floats = pass * ok_vit_agent_floats(s);
+        if (floats > h->vit_work_cap)
+        {
+            h->vit_work_cap = 0; // (a failed allocation leaves none)
+            if (const int rc = regrow(h, {fresh(h->d_vit_work, floats)}))
+                return rc;
+            h->vit_work_cap = floats;
+        }
+        h->vit        = *config;
+        h->vit_pass   = pass;
+        h->vit_drv.ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_vit_num_params(okenv_t h, int32_t *num_params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kVitDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
+            return rc;
+        *num_params = ok_vit_offsets(okVitShape(h->vit)).total;
+        return OKENV_OK;
+    }
+
+    int okenv_vit_set_params(okenv_t h, const float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kVitDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
+            return rc;
+        return driverSet(h, kVitDriver, {vectorOf(h->vit_drv.d, params, ok_vit_offsets(okVitShape(h->vit)).total)});
+    }
+
+    int okenv_vit_get_params(okenv_t h, float *params)
+    {
+        OK_QUIESCE(h);
+        if (const int rc = driverGate(h, kVitDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
+            return rc;
+        return driverGet(h, {vectorOf(h->vit_drv.d, params, ok_vit_offsets(okVitShape(h->vit)).total)});
+    }
+
+    int okenv_vit_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_vit_record *rec)
+    {
+        OK_QUIESCE(h);
+        return vitAct(h, frames, frame_bytes, rec);
+    }
+
+    int okenv_vit_act_host(const okenv_vit_config *config, const float *params, int32_t n, const uint8_t *frames, const uint8_t *crashed, float *throttle,
+                           float *steer, float *output, float *embedding, uint8_t *alive)
+    {
+        if (const char *why = okVitCheckConfig(config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_vit_act_host: ") + why);
+        if (!params || !frames || n < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_vit_act_host: bad argument");
+        okVitActHost(*config, params, n, frames, crashed, throttle, steer, output, embedding, alive);
+        return OKENV_OK;
+    }
+
+    int okenv_debug_vit_attend(int32_t device, int32_t seqs, int32_t T, int32_t heads, int32_t dh, const float *qkv, float *ctx)
+    {
+        if (!qkv || !ctx || seqs < 0 || T < 1 || T > OK_VIT_MAX_TOKENS || heads < 1 || heads > OK_VIT_MAX_DIM / 16 || dh < 16 || dh > OK_VIT_MAX_HEAD_DIM ||
+            dh % 16 != 0 || heads * dh > OK_VIT_MAX_DIM || seqs > 65536)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_debug_vit_attend: bad argument (T 1 .. 1024, dh a multiple of 16 up to 64, heads x dh up to 768)");
+        if (device < 0)
+        {
+            okVitAttendHost(seqs, T, heads, dh, qkv, ctx);
+            return OKENV_OK;
+        }
+        if (const int rc = debugNeedsDevice("okenv_debug_vit_attend"))
+            return rc;
+        if (seqs == 0)
+            return OKENV_OK;
+        OK_HIP(nullptr, hipSetDevice(device));
+        const size_t D = static_cast<size_t>(heads) * dh, nq = static_cast<size_t>(seqs) * T * 3U * D, nc = static_cast<size_t>(seqs) * T * D;
+        DebugBuffer  buf;
+        OK_HIP(nullptr, hipMalloc(reinterpret_cast<void **>(&buf.d), 4U * (nq + nc)));
+        float *dq = buf.d, *dc = dq + nq;
+        OK_HIP(nullptr, hipMemcpy(dq, qkv, 4U * nq, hipMemcpyHostToDevice));
+        if (const int rc = raiseLdsLimit(nullptr, {kernelOf(okVitAttendKernel)}))
+            return rc;
+        OkVitAttendParams ap{};
+        ap.T = T, ap.D = static_cast<int>(D), ap.heads = heads, ap.dh = dh, ap.qtiles = (T + kVitQueries - 1) / kVitQueries;
+        ap.scale = ok_lidar_scale(dh), ap.qkv = dq, ap.ctx = dc;
+        hipLaunchKernelGGL(okVitAttendKernel, dim3(static_cast<unsigned>(static_cast<size_t>(seqs) * heads * ap.qtiles)), dim3(kVitThreads),
+                           okVitAttendLdsBytes(T, dh), nullptr, ap);
+        OK_HIP(nullptr, hipGetLastError());
+        OK_HIP(nullptr, hipMemcpy(ctx, dc, 4U * nc, hipMemcpyDeviceToHost));
+        return OKENV_OK;
+    }
+
     // ---- Flow-matching driver (ok_flow.h) ----------------------------------------------------------------------------------------
 
     int64_t okenv_flow_lds_bytes(const okenv_flow_config *config)
@@ -6964,6 +7158,7 @@ extern "C"
         case OKENV_FN_ATAN2: return debugMath<OKENV_FN_ATAN2>(device, a, b, out0, out1, n);
         case OKENV_FN_NORMALIZE_ANGLE: return debugMath<OKENV_FN_NORMALIZE_ANGLE>(device, a, b, out0, out1, n);
         case OKENV_FN_SINCOS_PAIR: return debugMath<OKENV_FN_SINCOS_PAIR>(device, a, b, out0, out1, n);
+        case OKENV_FN_ERF: return debugMath<OKENV_FN_ERF>(device, a, b, out0, out1, n);
         default: return debugMath<OKENV_FN_EXPERT_NORMALIZE_ANGLE>(device, a, b, out0, out1, n);
         }
     }

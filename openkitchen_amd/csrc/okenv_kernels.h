@@ -2960,6 +2960,8 @@ __host__ __device__ inline void okDebugMathElement(const float *a, const float *
         out0[i] = ok_normalize_angle_deg(a[i]);
     else if (kFn == OKENV_FN_SINCOS_PAIR) // (out0 and out1 hold two floats per element: sine, cosine)
         ok_sincosf_pair(a[i], b[i], &out0[2U * i], &out0[2U * i + 1U], &out1[2U * i], &out1[2U * i + 1U]);
+    else if (kFn == OKENV_FN_ERF)
+        out0[i] = ok_erff(a[i]);
     else
         out0[i] = ok_expert_normalize_angle_deg(a[i]);
 }

@@ -946,6 +946,37 @@ class BatchedEnvironment:
             rec = None if record is None else C.byref(capi.fill_pointers(capi.OkenvCnnRecord(), record, "record", sizes))
             capi.check(self._L.okenv_debug_cnn_stages(self._h, capi.ptr(frames), self.N * S * S * 4, rec, int(stages)), self._h)
 
+    # ---- image transformer driver (include/okenv.h) ----------------------------------------------------------
+    def vit_create(self, config=None, **members):
+        """Attaches the image transformer policy (DinoControl's ViT and head) to the handle; config: a capi.vit_config(...), or its
+        members by name (the reference's shape and controls by default).  Returns the floats of its parameter vector."""
+        if config is None:
+            config = capi.vit_config(**members)
+        capi.check(self._L.okenv_vit_create(self._h, C.byref(config)), self._h)
+        self.vit_config = config
+        return self.vit_num_params()
+
+    def vit_num_params(self):
+        return self._count("okenv_vit_num_params")
+
+    def vit_set_params(self, params):
+        """New parameters (torch's parameters() order: capi.vit_layout) from a float32 numpy array or a device tensor.  Enqueued on
+        the handle's stream; the call waits for the stream when it was handed a numpy array (which may be a temporary), not for a
+        device tensor."""
+        self._set_params("okenv_vit_set_params", (params,), (self.vit_num_params(),))
+
+    def vit_get_params(self, out=None):
+        """The parameter vector as a float32 numpy array, or copied into the device tensor `out`.  Synchronises."""
+        return self._get_state("okenv_vit_get_params", {"params": self.vit_num_params()}, None if out is None else {"params": out})["params"]
+
+    def vit_act(self, frames, record=None):
+        """The policy's action of every agent from its frame, enqueued on the handle's stream without a synchronisation.  frames: a
+        device tensor / address of [N, S, S, 4] uint8.  record: None, or a dict of device tensors / addresses under "action" [N,2],
+        "output" [N], "embedding" [N,D] float32 and "alive" [N] uint8, each optional."""
+        S = self.vit_config.image_size
+        sizes = record and {"action": self.N * 8, "output": self.N * 4, "embedding": self.N * self.vit_config.dim * 4, "alive": self.N}
+        self._act("okenv_vit_act", capi.OkenvVitRecord, record, sizes, capi.ptr(frames), self.N * S * S * 4)
+
     # ---- Deep-Q image racers (include/okenv.h, DESIGN.md section 29) --------------------------------------------------------------
     def qcnn_create(self, config=None, **members):
         """Attaches the reference's image Q-network (RLRacers/DQN_CNN: CNN.hpp) to the handle; config: a capi.qcnn_config(...), or

@@ -615,6 +615,30 @@ class VectorEnvironment:
             raise ValueError("image_act(frames) needs a contiguous uint8 tensor of shape (%d, %d, %d, 4) on %s" % (self.num_envs, S, S, self.device))
         self.env.cnn_act(frames, record)
 
+    # ---- image transformer driver (include/okenv.h) -----------------------------------------------------------
+    def enable_vit_policy(self, config, params):
+        """Attaches DinoControl's vision transformer and head as a device driver.  config: a capi.vit_config(...) or a dict of its
+        members; params: the flat vector dino.vit_params_from_state_dict makes, a float32 numpy array or a tensor.  Call it again with
+        new params after training on."""
+        if isinstance(config, dict):
+            config = capi.vit_config(**config)
+        self._vit_flat = self._attach_flat("vit", config, params)  # alive until the next hand-over: a tensor's copy is asynchronous
+        self.vit_config = config
+        self._vit_graphs = {}  # a captured launch carries the old shape and vector
+
+    def vit_act(self, record=None, frames=None):
+        """The policy's action of every agent from `frames`, a contiguous uint8 tensor [N, S, S, 4] on this device (None: camera()'s,
+        rendered now; the camera must render at the policy's image_size), written into `throttle` / `steering`: a fixed sequence of
+        kernels on the environment's stream, no synchronisation, usable inside capture(body).  record: optional dict of device
+        tensors ("action" [N,2], "output" [N], "embedding" [N,D] float32, "alive" [N] uint8) that receive the sample."""
+        S = self.vit_config.image_size
+        if frames is None:
+            frames = self.camera()
+        if (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.device != self.device
+                or tuple(frames.shape) != (self.num_envs, S, S, 4)):
+            raise ValueError("vit_act(frames) needs a contiguous uint8 tensor of shape (%d, %d, %d, 4) on %s" % (self.num_envs, S, S, self.device))
+        self.env.vit_act(frames, record)
+
     # ---- Deep-Q image racers (include/okenv.h, DESIGN.md section 29) ---------------------------------------------------------------
     def enable_image_dqn(self, config, params, capacity=None, push_all=False):
         """Attaches the reference's image Q-network (RLRacers/DQN_CNN) as a device driver and, with `capacity`, its frame ring.

@@ -9,6 +9,8 @@ ROUNDED polynomial, evaluated exactly, is reported relative to the function valu
   cos r = 1 + z C(z),      C(z) = c1 + c2 z + ... + c6 z^5
   exp r - 1 = r + r^2 E(r), E(r) = e2 + e3 r + ... ,                |r| <= 0.3470 (ln 2 / 2 = 0.34657 plus slack)
   atan t = t + (t z) A(z), A(z) = a1 + a2 z + ... + a10 z^9,        z = t^2, |t| <= 0.4143 (tan(pi/8) = 0.41421 plus slack; ok_atan2f)
+  erf x = x G(z),          G(z) = g0 + g1 z + ... + g12 z^12,       z = x^2, |x| <= 1                                  (ok_erff)
+  erf x = H_c(x - c),      H_c(t) = h0 + h1 t + ... + h17 t^17,     c = 1.5, 2.5, 3.5, |t| <= 1/2: 1 <= x <= 4        (ok_erff)
 """
 import sys
 
@@ -88,6 +90,19 @@ def main():
     l1 = float(mp.log(2))
     l2 = float(mp.log(2) - mp.mpf(l1))
     print("ln 2: L1 = %s (%r), L2 = %s (%r); 1/ln2 = %r" % (l1.hex(), l1, l2.hex(), l2, float(1 / mp.log(2))))
+    # erf: the odd piece on [0, 1] (relative error: erf x ~ x there) and three pieces of width 1 up to 4 (erf >= 0.84: absolute error)
+    G = lambda z: mp.erf(mp.sqrt(z)) / mp.sqrt(z) if z > 0 else 2 / mp.sqrt(mp.pi)  # noqa: E731
+    c = to_double(cheb_fit(G, mp.mpf("1e-30"), mp.mpf(1), 13))
+    err = max_rel_err(lambda x: x * horner(c, x * x), mp.erf, mp.mpf("1e-6"), mp.mpf(1))
+    print("erf, |x| <= 1: 13 coefficients, max relative error: %s = 2^%.1f" % (mp.nstr(err, 3), float(mp.log(err, 2))))
+    print("    {" + ", ".join(v.hex() for v in c) + "}")
+    for centre in ("1.5", "2.5", "3.5"):
+        m = mp.mpf(centre)
+        c = to_double(cheb_fit(lambda t: mp.erf(m + t), -mp.mpf("0.5"), mp.mpf("0.5"), 18))
+        err = max_rel_err(lambda x: horner(c, x - m), mp.erf, m - mp.mpf("0.5"), m + mp.mpf("0.5"))
+        print("erf, |x - %s| <= 1/2: 18 coefficients, max relative error: %s = 2^%.1f" % (centre, mp.nstr(err, 3), float(mp.log(err, 2))))
+        print("    {" + ", ".join(v.hex() for v in c) + "}")
+    print("2/sqrt(pi) = %s" % float(2 / mp.sqrt(mp.pi)).hex())
 
 
 if __name__ == "__main__":
