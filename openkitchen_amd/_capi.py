@@ -567,7 +567,7 @@ def bev_encode_host(cfg, params, frames):
 # behavioural-cloning image policy (include/okenv.h)
 CNN_LDS_BUDGET = 160 * 1024
 CNN_STAGE_CONV, CNN_STAGE_HEAD = 1, 2
-CNN_AGENTS = 16  # agents per workgroup of the head kernel (ok_cnn.h: kCnnAgents)
+CNN_AGENTS = 16  # agents per workgroup of the head kernel (ok_conv.h: kConvAgents)
 
 
 class OkenvCnnConfig(C.Structure):
@@ -647,7 +647,7 @@ def cnn_act_host(cfg, params, frames, crashed=None):
 # Deep-Q image racers (include/okenv.h)
 QCNN_LDS_BUDGET = 160 * 1024
 QCNN_STAGE_CONV, QCNN_STAGE_HEAD, QCNN_STAGE_HEAD_32 = 1, 2, 4
-QCNN_AGENTS = 16  # agents per workgroup of the head kernel (ok_qcnn.h: kQcnnAgents)
+QCNN_AGENTS = 16  # agents per workgroup of the head kernel (ok_conv.h: kConvAgents)
 QCNN_BATCH_UNIFORM, QCNN_BATCH_SEQUENTIAL = 0, 1
 QCNN_BATCH_MODES = {"uniform": QCNN_BATCH_UNIFORM, "sequential": QCNN_BATCH_SEQUENTIAL}
 # DQCNNAgent::kActionMap: (throttle_delta, steering_delta) per action index (kVelocity 60, kSteeringDelta 5 degrees)

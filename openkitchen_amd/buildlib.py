@@ -21,19 +21,16 @@ CXX_SOURCES = [
     os.path.join(CSRC, "facade", "Environment.cpp"),
     os.path.join(CSRC, "facade", "Visualizer.cpp"),
 ]
-HEADERS = [
-    os.path.join(CSRC, "ok_raycast.h"), os.path.join(CSRC, "ok_grid.h"), os.path.join(CSRC, "ok_render.h"), os.path.join(CSRC, "ok_expert.h"),
-    os.path.join(CSRC, "ok_actor.h"), os.path.join(CSRC, "ok_batch.h"), os.path.join(CSRC, "ok_learn.h"),
-    os.path.join(CSRC, "ok_dqn.h"), os.path.join(CSRC, "ok_ddpg.h"), os.path.join(CSRC, "ok_reinforce.h"), os.path.join(CSRC, "ok_gauss.h"), os.path.join(CSRC, "ok_lidar.h"), os.path.join(CSRC, "ok_flow.h"), os.path.join(CSRC, "ok_bev.h"), os.path.join(CSRC, "ok_cnn.h"), os.path.join(CSRC, "ok_world.h"), os.path.join(CSRC, "okenv_kernels.h"),
-    os.path.join(ROOT, "include", "okenv.h"), os.path.join(ROOT, "include", "okenv_math.h"),
-    os.path.join(ROOT, "include", "okenv_batch.h"), os.path.join(ROOT, "include", "okenv_learn.h"),
-    os.path.join(ROOT, "include", "okenv_dqn.h"), os.path.join(ROOT, "include", "okenv_ddpg.h"),
-    os.path.join(ROOT, "include", "okenv_reinforce.h"), os.path.join(ROOT, "include", "okenv_gauss.h"),
-    os.path.join(ROOT, "include", "okenv_lidar.h"), os.path.join(ROOT, "include", "okenv_flow.h"),
-    os.path.join(ROOT, "include", "okenv_bev.h"),
-    os.path.join(ROOT, "include", "okenv_cnn.h"),
-    os.path.join(ROOT, "include", "okenv_world.h"),
-]
+
+
+def headers():
+    """Every header on disk that a source may include: whatever is under csrc/ (the applications' too), the rule headers and the
+    facade's.  Listed, not named, so that a new header cannot be forgotten and leave a stale library standing."""
+    found = [os.path.join(d, f) for d, _, files in os.walk(CSRC) for f in files if f.endswith(".h")]
+    for d in (os.path.join(ROOT, "include"), os.path.join(ROOT, "include", "Environment")):
+        found += [os.path.join(d, f) for f in os.listdir(d) if f.endswith(".h")]
+    return sorted(found)
+
 
 # -ffp-contract=off: crash/done flags must be bit-exact against the CPU oracle, and FMA contraction changes
 # the cancellation-prone 2x2 determinants of the ray-segment test (SURVEY.md section 7, "FMA contraction").
@@ -56,9 +53,7 @@ def needs_build():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = sources() + HEADERS + [os.path.join(ROOT, "include", "Environment", f)
-                                  for f in os.listdir(os.path.join(ROOT, "include", "Environment")) if f.endswith(".h")]
-    return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
+    return any(os.path.exists(d) and os.path.getmtime(d) > t for d in sources() + headers())
 
 
 def build(force=False, verbose=False):

@@ -4,17 +4,18 @@
 // ok_cnn_hidden_at, ok_lidar_dot, ok_actor_argmax, ok_actor_eps_greedy, ok_qcnn_push, ok_qcnn_batch) and is shared with the host
 // entries below, so the device and the host agree bit for bit.
 //
-// These are NOT step kernels and add no step-kernel launch site.  All matrix work runs on v_mfma_f32_16x16x4_f32 with the accumulator
-// started from the bias, in ok_cnn.h's lane mapping and packed-weight layout.
+// These are NOT step kernels and add no step-kernel launch site.  The lane mapping, the packed-weight layout, the unit loop of a
+// convolution, the walk of layers 1 and 2 and fc1's GEMM are ok_conv.h's, shared with ok_cnn.h; what is this family's own:
 //   okQcnnPackKernel      at set_params: the four weight matrices in groups of 16 k's (layer 0: 16 taps a group, filler taps 0.0f)
+//   OkQcnnGreyTaps        layer 0's A operands: the grey plane, one float a tap
 //   okQcnnConvKernel      one frame per workgroup of 8 waves, every layer in LDS, channels last.  The grey plane and the outputs of
 //                         layers 0 and 1 lie INSIDE A BORDER OF +0.0f as wide as the next layer's padding: every tap of every
 //                         window is an ordinary in-range LDS read (the rule's ZERO TERMS).  Layer 2 writes the [N][F] features,
 //                         channels last, to global memory.
-//   okQcnnHeadKernel<CT,RT> 16 RT agents per workgroup of 8 waves: fc1 as a GEMM whose rows are agents, the features staged through
-//                         LDS 256 k's at a time, a wave owning CT tiles of 16 columns for RT row tiles; then fc2, the choice, the
-//                         action fields and the record, 8 lanes an agent (lane k: q_k).  The act runs RT = 1; RT = 2 (32 agents,
-//                         fc1.weight read half as often) was measured slower and is kept behind okenv_debug_qcnn_stages only.
+//   okQcnnHeadKernel<CT,RT> 16 RT agents per workgroup of 8 waves: fc1 (okConvFc1, a wave owning CT tiles of 16 columns for RT row
+//                         tiles); then fc2, the choice, the action fields and the record, 8 lanes an agent (lane k: q_k).  The act
+//                         runs RT = 1; RT = 2 (32 agents, fc1.weight read half as often) was measured slower and is kept behind
+//                         okenv_debug_qcnn_stages only.
 //   okReplayCountKernel<OkQcnnPushParams>, okQcnnRankKernel, okQcnnFramesKernel<Vec>
 //                         the push: ok_dqn.h's count, its rank piece (slot per agent, action / reward / done, the counter), then both
 //                         frames' grey planes into the survivors' slots, several workgroups a frame
@@ -28,19 +29,13 @@
 
 #include "../../include/okenv.h"
 #include "../../include/okenv_qcnn.h"
+#include "ok_conv.h"
 #include "ok_dqn.h"
 #include "ok_lidar.h"
 
 static_assert(OKENV_QCNN_BATCH_UNIFORM == OK_QCNN_BATCH_UNIFORM && OKENV_QCNN_BATCH_SEQUENTIAL == OK_QCNN_BATCH_SEQUENTIAL, "the ABI's modes are the rule's");
 
-constexpr int    kQcnnThreads     = 512; // 8 waves
-constexpr int    kQcnnWaves       = kQcnnThreads / 64;
-constexpr int    kQcnnRowBlock    = 2;   // row tiles a wave carries through one pass over a weight tile (the convolutions)
-constexpr int    kQcnnAgents      = 16;  // agents per workgroup of the head: the rows of one MFMA tile
-constexpr int    kQcnnChunk       = 256; // features the head stages at a time
-constexpr int    kQcnnMaxColTiles = OK_CNN_MAX_HIDDEN / 16 / kQcnnWaves; // 4
-constexpr int    kQcnnCopyThreads = 256;
-constexpr size_t kQcnnLdsBudget   = 160U * 1024U;
+constexpr int kQcnnCopyThreads = 256;
 
 __host__ __device__ inline ok_qcnn_shape okQcnnShape(const okenv_qcnn_config &c)
 {
@@ -68,14 +63,12 @@ __host__ __device__ inline int okQcnnGroups(const ok_qcnn_shape s, const int l)
 
 // The conv kernel's LDS, in floats: [p | q].  p: the grey plane inside its border, pin x pin floats, and behind layer 0 layer 1's
 // output inside its border, pad1^2 pixels of c1 + 1 floats.  q: layer 0's output inside its border, pad0^2 pixels of c0 + 1 floats
-// (odd: the 16 pixels of an MFMA tile start on different banks).  The head's: [tile | hid], 16 rows of kQcnnChunk + 4 and of H + 4.
-struct OkQcnnPlaces
+// (odd: the 16 pixels of an MFMA tile start on different banks).  The head's LDS and the pack's places are OkConvHeadPlaces'.
+struct OkQcnnPlaces : OkConvHeadPlaces
 {
     int side[3], pin, pad0, pad1, ld0, ld1, p, q, conv_end;
     int region; // what sizes p: 0 the grey plane, 1 layer 1's output
-    int ct, ldt, ldh, hid, head_end;
     int vec;    // the push and the gather move planes as 16-byte vectors
-    int pack[4], pack_total; // where each layer's packed weights begin, in floats (3: fc1)
 };
 
 __host__ __device__ inline OkQcnnPlaces okQcnnPlaces(const ok_qcnn_shape s)
@@ -93,19 +86,9 @@ __host__ __device__ inline OkQcnnPlaces okQcnnPlaces(const ok_qcnn_shape s)
     at.p        = 0;
     at.q        = at.p + okLidarMax(plane, out1);
     at.conv_end = at.q + at.pad0 * at.pad0 * at.ld0;
-    at.ct       = (s.H / 16 + kQcnnWaves - 1) / kQcnnWaves;
-    at.ldt      = kQcnnChunk + 4;
-    at.ldh      = s.H + 4;
-    at.hid      = kQcnnAgents * at.ldt;
-    at.head_end = at.hid + kQcnnAgents * at.ldh;
     at.vec      = (s.S * s.S) % 4 == 0 ? 1 : 0;
-    int o = 0;
-    for (int l = 0; l < 4; ++l)
-    {
-        at.pack[l] = o;
-        o += okQcnnGroups(s, l) * (l == 3 ? s.H : s.c[l]) * 16;
-    }
-    at.pack_total = o;
+    const int groups[4] = {okQcnnGroups(s, 0), okQcnnGroups(s, 1), okQcnnGroups(s, 2), okQcnnGroups(s, 3)}, cout[4] = {s.c[0], s.c[1], s.c[2], s.H};
+    okConvHeadPlaces(at, s.H, groups, cout);
     return at;
 }
 
@@ -119,9 +102,7 @@ inline size_t okQcnnLdsBytes(const ok_qcnn_shape s)
 
 // ---- the weights as the kernels read them ----------------------------------------------------------------------------------------------
 
-// ok_cnn.h's layout: a layer's B matrix [K][Cout] in groups of 16 k's, k the place in the rule's chain -- layer 0's k = tap
-// (tap = ty * k0 + tx), layers 1 and 2's k = tap * Cin + ch, fc1's k = (y * side_2 + x) * c2 + ch:
-// pack[((k / 16) * Cout + n) * 16 + (k % 4) * 4 + (k % 16) / 4].  Layer 0's filler taps are 0.0f.
+// okConvPack's layout; layer 0's k = tap (tap = ty * k0 + tx), its filler taps 0.0f
 struct OkQcnnPackParams
 {
     ok_qcnn_shape s;
@@ -132,153 +113,49 @@ struct OkQcnnPackParams
 __global__ __launch_bounds__(256) void okQcnnPackKernel(const OkQcnnPackParams p)
 {
     const ok_qcnn_layout at = ok_qcnn_offsets(p.s);
-    const OkQcnnPlaces   pl = okQcnnPlaces(p.s);
-    const int            e  = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    if (e >= pl.pack_total)
-        return;
-    const int l    = e >= pl.pack[3] ? 3 : (e >= pl.pack[2] ? 2 : (e >= pl.pack[1] ? 1 : 0));
-    const int base = l == 3 ? pl.pack[3] : (l == 2 ? pl.pack[2] : (l == 1 ? pl.pack[1] : 0)); // (no array indexed by l: it would live in scratch)
-    const int Cout = l == 3 ? p.s.H : (l == 2 ? p.s.c[2] : (l == 1 ? p.s.c[1] : p.s.c[0]));
-    const int idx = e - base, grp = idx / (Cout * 16), rem = idx - grp * Cout * 16, n = rem >> 4, g = (rem & 15) >> 2, q = rem & 3;
-    const int kk = grp * 16 + 4 * q + g;
-    float     v  = 0.F;
-    if (l == 0)
-    {
+    okConvPack(p.s, at, okQcnnPlaces(p.s), p.params, p.pack, [&](const int n, const int kk) {
         const int taps = p.s.k[0] * p.s.k[0];
-        if (kk < taps)
-            v = p.params[at.w[0] + n * taps + kk];
-    }
-    else if (l == 3)
-    {
-        const int c2 = p.s.c[2], P = pl.side[2] * pl.side[2], pos = kk / c2, ch = kk - pos * c2;
-        v = p.params[at.hw + n * (c2 * P) + ch * P + pos];
-    }
-    else
-    {
-        const int Cin = l == 2 ? p.s.c[1] : p.s.c[0], k = l == 2 ? p.s.k[2] : p.s.k[1], tap = kk / Cin, ch = kk - tap * Cin;
-        v = p.params[(l == 2 ? at.w[2] : at.w[1]) + (n * Cin + ch) * k * k + tap];
-    }
-    p.pack[e] = v;
+        return kk < taps ? p.params[at.w[0] + n * taps + kk] : 0.F;
+    });
 }
 
-// ---- the convolution piece -------------------------------------------------------------------------------------------------------------
+// ---- the convolutions ------------------------------------------------------------------------------------------------------------------
 
-// One convolution of a whole image: M output pixels, W to a row, times Cout channels.  The input lies in LDS INSIDE ITS BORDER: pixel
-// (y, x) of the bordered image at in + y * rs + x * ps, its channel ch at + ch; the output pixel (oy, ox) reads the bordered pixels
-// (stride oy + ty, stride ox + tx), all of them inside the bordered image.  The output pixel (oy, ox) goes to
-// out + ((oy + opad) * orow + ox + opad) * ldo + channel, LDS (inside the next layer's border) or global (opad = 0, orow = W).
-struct OkQcnnConvJob
+// Layer 0's A operands for okConv: one input channel, a k-step is four taps, lane group g reads tap 16 grp + 4 q + g; the filler taps
+// read the last tap against their 0.0f weight.
+struct OkQcnnGreyTaps
 {
-    int          in, ps, rs, k, stride, Cin, W, M, Cout;
-    const float *w, *bias; // packed weights of the layer, its bias
-    float       *out;
-    int          ldo, opad, orow;
+    const int last;
+    int       ty, tx; // this lane group's tap, four further every k-step
+
+    __device__ __forceinline__ OkQcnnGreyTaps(const OkConvJob &j, const int g) : last((j.k - 1) * (j.rs + j.ps)), ty(g / j.k), tx(g - ty * j.k) {}
+
+    __device__ __forceinline__ static int groups(const OkConvJob &j)
+    {
+        return (j.k * j.k + 15) >> 4;
+    }
+
+    __device__ __forceinline__ static int lane(const int)
+    {
+        return 0;
+    }
+
+    template <int RB>
+    __device__ __forceinline__ void load(const OkConvJob &j, const int (&abase)[RB], float (&a)[4][RB])
+    {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+        {
+            const int toff = ty >= j.k ? last : ty * j.rs + tx * j.ps;
+#pragma unroll
+            for (int m = 0; m < RB; ++m)
+                a[q][m] = ok_actor_lds[abase[m] + toff];
+            tx += 4;
+            while (tx >= j.k)
+                tx -= j.k, ++ty;
+        }
+    }
 };
-
-// A wave owns 16 columns and kQcnnRowBlock row tiles of 16 pixels at a time; ok_cnn.h's lane mapping.  Rows past M repeat the last
-// pixel and are not stored.  kFirst: layer 0 -- one input channel, a k-step is four taps, lane group g reads tap 16 grp + 4 q + g; the
-// filler taps read the last tap against their 0.0f weight.
-template <bool kFirst>
-__device__ __forceinline__ void okQcnnConv(const OkQcnnConvJob &j)
-{
-    constexpr int RB = kQcnnRowBlock;
-    const int lane = static_cast<int>(threadIdx.x) & 63, i = lane & 15, g = lane >> 4, wave = static_cast<int>(threadIdx.x) >> 6;
-    const int Nt = j.Cout >> 4, Mb = (j.M + 16 * RB - 1) / (16 * RB), units = Nt * Mb;
-    for (int u = wave; u < units; u += kQcnnWaves)
-    {
-        const int  mb = u / Nt, n0 = (u - mb * Nt) << 4;
-        int        abase[RB];
-        okLidarAcc acc[RB];
-#pragma unroll
-        for (int m = 0; m < RB; ++m)
-        {
-            const int row = okLidarMin((mb * RB + m) * 16 + i, j.M - 1), oy = row / j.W, ox = row - oy * j.W;
-            abase[m]      = j.in + j.stride * oy * j.rs + j.stride * ox * j.ps + (kFirst ? 0 : g);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                acc[m][r] = j.bias[n0 + i];
-        }
-        const float4 *wp = reinterpret_cast<const float4 *>(j.w) + (n0 + i) * 4 + g;
-        const int     gstride = j.Cout * 4; // float4's between groups
-        if constexpr (kFirst)
-        {
-            const int groups = (j.k * j.k + 15) >> 4, last = (j.k - 1) * (j.rs + j.ps);
-            int       ty = g / j.k, tx = g - ty * j.k; // this lane group's tap, four further every k-step
-            for (int grp = 0; grp < groups; ++grp)
-            {
-                const float4 bv = wp[grp * gstride];
-                float        a[4][RB];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-                    const int toff = ty >= j.k ? last : ty * j.rs + tx * j.ps;
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        a[q][m] = ok_actor_lds[abase[m] + toff];
-                    tx += 4;
-                    while (tx >= j.k)
-                        tx -= j.k, ++ty;
-                }
-                const float b[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q][m], b[q], acc[m], 0, 0, 0);
-                }
-            }
-        }
-        else
-        {
-            // group grp = (tap (ty, tx), channels c0 .. c0 + 15)
-            const int groups = j.k * j.k * (j.Cin >> 4);
-            int       ty = 0, tx = 0, c0 = 0;
-            for (int grp = 0; grp < groups; ++grp)
-            {
-                const float4 bv   = wp[grp * gstride];
-                const int    toff = ty * j.rs + tx * j.ps + c0;
-                float        a[4][RB];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        a[q][m] = ok_actor_lds[abase[m] + toff + 4 * q];
-                }
-                const float b[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q][m], b[q], acc[m], 0, 0, 0);
-                }
-                c0 += 16;
-                if (c0 == j.Cin)
-                {
-                    c0 = 0;
-                    if (++tx == j.k)
-                        tx = 0, ++ty;
-                }
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < RB; ++m)
-        {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-            {
-                const int row = (mb * RB + m) * 16 + 4 * g + r;
-                if (row < j.M)
-                {
-                    const int oy = row / j.W, ox = row - oy * j.W;
-                    j.out[static_cast<long>((oy + j.opad) * j.orow + ox + j.opad) * j.ldo + n0 + i] = ok_lidar_relu(acc[m][r]);
-                }
-            }
-        }
-    }
-}
 
 struct OkQcnnActParams
 {
@@ -293,7 +170,7 @@ struct OkQcnnActParams
     okenv_qcnn_record rec;
 };
 
-__global__ __launch_bounds__(kQcnnThreads) void okQcnnConvKernel(const OkQcnnActParams p)
+__global__ __launch_bounds__(kConvThreads) void okQcnnConvKernel(const OkQcnnActParams p)
 {
     const ok_qcnn_shape  sh = p.s;
     const ok_qcnn_layout at = ok_qcnn_offsets(sh);
@@ -303,7 +180,7 @@ __global__ __launch_bounds__(kQcnnThreads) void okQcnnConvKernel(const OkQcnnAct
 
     // the grey plane inside its border, and +0.0f all over layer 0's place (its border stays)
     const uint32_t *frame = reinterpret_cast<const uint32_t *>(p.frames) + n * static_cast<size_t>(S * S);
-    for (int e = tid; e < pl.pin * pl.pin; e += kQcnnThreads)
+    for (int e = tid; e < pl.pin * pl.pin; e += kConvThreads)
     {
         const int y = e / pl.pin - sh.p[0], x = e - (y + sh.p[0]) * pl.pin - sh.p[0];
         float     v = 0.F;
@@ -315,21 +192,21 @@ __global__ __launch_bounds__(kQcnnThreads) void okQcnnConvKernel(const OkQcnnAct
         ok_actor_lds[pl.p + e] = v;
     }
     if (sh.p[1] > 0)
-        for (int e = tid; e < pl.pad0 * pl.pad0 * pl.ld0; e += kQcnnThreads)
+        for (int e = tid; e < pl.pad0 * pl.pad0 * pl.ld0; e += kConvThreads)
             ok_actor_lds[pl.q + e] = 0.F;
     __syncthreads();
 
-    OkQcnnConvJob j;
+    OkConvJob j;
     j.in = pl.p, j.ps = 1, j.rs = pl.pin, j.k = sh.k[0], j.stride = sh.s[0], j.Cin = 1, j.W = pl.side[0], j.M = pl.side[0] * pl.side[0], j.Cout = sh.c[0];
     j.w = p.pack + pl.pack[0], j.bias = p.params + at.b[0];
     j.out = ok_actor_lds + pl.q, j.ldo = pl.ld0, j.opad = sh.p[1], j.orow = pl.pad0;
-    okQcnnConv<true>(j);
+    okConv<OkQcnnGreyTaps>(j);
     __syncthreads();
 
     // (the grey plane is done with: +0.0f all over layer 1's place)
     if (sh.p[2] > 0)
     {
-        for (int e = tid; e < pl.pad1 * pl.pad1 * pl.ld1; e += kQcnnThreads)
+        for (int e = tid; e < pl.pad1 * pl.pad1 * pl.ld1; e += kConvThreads)
             ok_actor_lds[pl.p + e] = 0.F;
         __syncthreads();
     }
@@ -337,99 +214,28 @@ __global__ __launch_bounds__(kQcnnThreads) void okQcnnConvKernel(const OkQcnnAct
     j.M = pl.side[1] * pl.side[1], j.Cout = sh.c[1];
     j.w = p.pack + pl.pack[1], j.bias = p.params + at.b[1];
     j.out = ok_actor_lds + pl.p, j.ldo = pl.ld1, j.opad = sh.p[2], j.orow = pl.pad1;
-    okQcnnConv<false>(j);
+    okConv<OkConvWalk>(j);
     __syncthreads();
 
     j.in = pl.p, j.ps = pl.ld1, j.rs = pl.pad1 * pl.ld1, j.k = sh.k[2], j.stride = sh.s[2], j.Cin = sh.c[1], j.W = pl.side[2];
     j.M = pl.side[2] * pl.side[2], j.Cout = sh.c[2];
     j.w = p.pack + pl.pack[2], j.bias = p.params + at.b[2];
     j.out = p.feat + n * static_cast<size_t>(j.M * sh.c[2]), j.ldo = sh.c[2], j.opad = 0, j.orow = j.W;
-    okQcnnConv<false>(j);
+    okConv<OkConvWalk>(j);
 }
 
 // CT: tiles of 16 hidden units a wave owns; RT: row tiles of 16 agents a workgroup carries (fc1.weight is read once per workgroup): 1 in
 // the act, 2 for measurement ("The head's tiling")
 template <int CT, int RT>
-__global__ __launch_bounds__(kQcnnThreads) void okQcnnHeadKernel(const OkQcnnActParams p)
+__global__ __launch_bounds__(kConvThreads) void okQcnnHeadKernel(const OkQcnnActParams p)
 {
-    constexpr int        kAgents = kQcnnAgents * RT;
+    constexpr int        kAgents = kConvAgents * RT;
     const ok_qcnn_shape  sh = p.s;
     const ok_qcnn_layout at = ok_qcnn_offsets(sh);
     const OkQcnnPlaces   pl = okQcnnPlaces(sh);
-    const int            H = sh.H, A = sh.A, F = ok_qcnn_features(sh), Nt = H >> 4, tid = static_cast<int>(threadIdx.x);
-    const int            lane = tid & 63, i = lane & 15, g = lane >> 4, wave = tid >> 6;
+    const int            H = sh.H, A = sh.A, tid = static_cast<int>(threadIdx.x);
     const long           a0 = static_cast<long>(blockIdx.x) * kAgents;
-    float               *hid = ok_actor_lds + kAgents * pl.ldt; // (pl.hid when RT = 1)
-
-    okLidarAcc acc[RT][CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c)
-    {
-        const int t = okLidarMin(wave + kQcnnWaves * c, Nt - 1); // (a wave without a tile of its own repeats the last one and stores nothing)
-#pragma unroll
-        for (int m = 0; m < RT; ++m)
-        {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                acc[m][c][r] = p.params[at.hb + 16 * t + i];
-        }
-    }
-    const float4 *wp = reinterpret_cast<const float4 *>(p.pack + pl.pack[3]) + i * 4 + g;
-    const int     gstride = H * 4; // float4's between groups
-    for (int k0 = 0; k0 < F; k0 += kQcnnChunk)
-    {
-        const int kc = okLidarMin(kQcnnChunk, F - k0), kc4 = kc >> 2;
-        for (int e = tid; e < kAgents * kc4; e += kQcnnThreads)
-        {
-            const int    r = e / kc4, c4 = e - r * kc4;
-            const long   a = okLidarMin(static_cast<int>(a0) + r, p.N - 1); // (rows of a partial last workgroup repeat the last agent)
-            const float4 v = reinterpret_cast<const float4 *>(p.feat + a * F + k0)[c4];
-            *reinterpret_cast<float4 *>(ok_actor_lds + r * pl.ldt + 4 * c4) = v;
-        }
-        __syncthreads();
-        for (int grp = 0; grp < (kc >> 4); ++grp)
-        {
-            float a[RT][4];
-#pragma unroll
-            for (int m = 0; m < RT; ++m)
-            {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    a[m][q] = ok_actor_lds[(16 * m + i) * pl.ldt + 16 * grp + 4 * q + g];
-            }
-#pragma unroll
-            for (int c = 0; c < CT; ++c)
-            {
-                const int    t  = okLidarMin(wave + kQcnnWaves * c, Nt - 1);
-                const float4 bv = wp[((k0 >> 4) + grp) * gstride + t * 64];
-                const float  b[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-#pragma unroll
-                    for (int m = 0; m < RT; ++m)
-                        acc[m][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m][q], b[q], acc[m][c], 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int c = 0; c < CT; ++c)
-    {
-        const int t = wave + kQcnnWaves * c;
-        if (t < Nt)
-        {
-#pragma unroll
-            for (int m = 0; m < RT; ++m)
-            {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    hid[(16 * m + 4 * g + r) * pl.ldh + 16 * t + i] = ok_lidar_relu(acc[m][c][r]);
-            }
-        }
-    }
-    __syncthreads();
+    const float         *hid = okConvFc1<CT, RT>(p.feat, p.N, ok_qcnn_features(sh), H, a0, p.pack + pl.pack[3], p.params + at.hb, pl.ldt, pl.ldh);
 
     // fc2 and the choice: 8 lanes an agent, lane k holds q_k (whole waves leave here, so the shuffles below are complete)
     if (tid >= kAgents * OK_ACTOR_LANES)
@@ -636,7 +442,7 @@ inline const char *okQcnnCheckShape(const ok_qcnn_shape s)
         return "shape outside the limits (image_size 16 .. 128; kernel 1 .. 8; stride 1 .. 4 and at most the kernel; padding 0 .. 3 and below "
                "the kernel; every layer's side at least 1; channels multiples of 16 in 16 .. 128; at most 16384 features; hidden a multiple "
                "of 16 in 16 .. 512; 2 .. 8 actions)";
-    if (okQcnnLdsBytes(s) > kQcnnLdsBudget)
+    if (okQcnnLdsBytes(s) > kConvLdsBudget)
         return "the conv kernel's LDS (okenv_qcnn_lds_bytes) does not fit 160 KB";
     return nullptr;
 }

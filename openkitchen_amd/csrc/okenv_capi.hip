@@ -1742,12 +1742,12 @@ int cnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const oke
     if (rec != nullptr)
         p.rec = *rec;
     if ((stages & OKENV_CNN_STAGE_CONV) != 0U)
-        if (const int rc = actLaunch(h, okCnnConvKernel, 1, kCnnThreads, sizeof(float) * static_cast<size_t>(pl.conv_end), p))
+        if (const int rc = actLaunch(h, okCnnConvKernel, 1, kConvThreads, sizeof(float) * static_cast<size_t>(pl.conv_end), p))
             return rc;
     if ((stages & OKENV_CNN_STAGE_HEAD) != 0U)
     {
-        void (*const heads[kCnnMaxColTiles])(OkCnnActParams) = {okCnnHeadKernel<1>, okCnnHeadKernel<2>, okCnnHeadKernel<3>, okCnnHeadKernel<4>};
-        return actLaunch(h, heads[pl.ct - 1], kCnnAgents, kCnnThreads, sizeof(float) * static_cast<size_t>(pl.head_end), p);
+        void (*const heads[kConvMaxColTiles])(OkCnnActParams) = {okCnnHeadKernel<1>, okCnnHeadKernel<2>, okCnnHeadKernel<3>, okCnnHeadKernel<4>};
+        return actLaunch(h, heads[pl.ct - 1], kConvAgents, kConvThreads, sizeof(float) * static_cast<size_t>(pl.head_end), p);
     }
     return OKENV_OK;
 }
@@ -1768,9 +1768,9 @@ const char *qcnnFramesMissing(const okenv *h, const void *frames, const int64_t 
 template <int RT>
 int qcnnHead(okenv *h, const OkQcnnPlaces &pl, const OkQcnnActParams &p)
 {
-    void (*const heads[kQcnnMaxColTiles])(OkQcnnActParams) = {okQcnnHeadKernel<1, RT>, okQcnnHeadKernel<2, RT>, okQcnnHeadKernel<3, RT>, okQcnnHeadKernel<4, RT>};
-    const size_t lds = sizeof(float) * static_cast<size_t>(kQcnnAgents * RT * (pl.ldt + pl.ldh));
-    return actLaunch(h, heads[pl.ct - 1], kQcnnAgents * RT, kQcnnThreads, lds, p);
+    void (*const heads[kConvMaxColTiles])(OkQcnnActParams) = {okQcnnHeadKernel<1, RT>, okQcnnHeadKernel<2, RT>, okQcnnHeadKernel<3, RT>, okQcnnHeadKernel<4, RT>};
+    const size_t lds = sizeof(float) * static_cast<size_t>(kConvAgents * RT * (pl.ldt + pl.ldh));
+    return actLaunch(h, heads[pl.ct - 1], kConvAgents * RT, kConvThreads, lds, p);
 }
 
 // okenv_qcnn_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_QCNN_STAGE_*), in their order, on the stream
@@ -1794,7 +1794,7 @@ int qcnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const ok
     if (rec != nullptr)
         p.rec = *rec;
     if ((stages & OKENV_QCNN_STAGE_CONV) != 0U)
-        if (const int rc = actLaunch(h, okQcnnConvKernel, 1, kQcnnThreads, sizeof(float) * static_cast<size_t>(pl.conv_end), p))
+        if (const int rc = actLaunch(h, okQcnnConvKernel, 1, kConvThreads, sizeof(float) * static_cast<size_t>(pl.conv_end), p))
             return rc;
     if ((stages & OKENV_QCNN_STAGE_HEAD) != 0U)
         if (const int rc = qcnnHead<1>(h, pl, p))

@@ -10,7 +10,7 @@ MEMORY_ROWS = 128     # ok_memory.h: kMemRows, the list slots of a workgroup of 
 MEMORY_WAVE_ROWS = 16  # ok_memory.h: kMemRows / kMemWaves, the row tile of one of its 8 waves
 REPLAY_THREADS = 256  # ok_dqn.h: kReplayThreads, the agents of a workgroup of the ring's count and rank kernels
 HEAD_SLOTS = 4        # ok_world.h: kWorldHeadSlots, ok_memory.h: kMemHeadSlots, the list slots of a workgroup of the head kernels
-HEAD_AGENTS = 16      # ok_world.h: kWorldAgents, ok_qcnn.h: kQcnnAgents, ok_cnn.h: kCnnAgents, the agents of a workgroup of the MFMA heads
+HEAD_AGENTS = 16      # ok_world.h: kWorldAgents, ok_conv.h: kConvAgents, the agents of a workgroup of the MFMA heads
 
 
 def _flags(N, crashed):
