@@ -1,13 +1,18 @@
 """The reference's image transformer driver (DinoControl/) for a whole population: demonstrations with bird's-eye frames from the
 device's potential-field expert, the 384-128-64-1 policy head trained on a FROZEN vision transformer's class token in PyTorch with the
 reference's recipe, and N agents driven by it at a constant throttle -- the forward once per step in PyTorch or, with
---device-policy, in the device's act kernels.
+--device-policy, in the device's act kernels.  With --device-update the training runs on the device as well: the frozen backbone's
+embeddings are cached by the act's own kernels and the head is trained in the handle's parameter vector (dino.train_device), so that
+record, embed, train and drive all happen on the handle.
 
     python examples/dino_racer.py [--agents 32] [--demo-steps 32] [--epochs 3] [--steps 64] [--episodes 1] [--graph-chunk 8]
-                                  [--backbone file.pth] [--small] [--device-policy] [--track Austin]
+                                  [--backbone file.pth] [--small] [--device-policy] [--device-update [--val-split 0.1]]
+                                  [--track Austin]
 
 1. record: every living agent's frame and the expert's action (demonstrations.collect_demonstrations(images=True));
 2. train: the head only, weighted MSE (weight 5 where |label| > 0.1) against the expert's steering / 10, Adam 1e-4;
+   --device-update: the hand-over comes first, then dino.train_device trains the head on the device and prints the training and the
+   validation loss of every epoch; the trained head is copied back into the PyTorch module (dino.head_from_device);
 3. hand over (--device-policy): the weights as one flat vector (dino.vit_params_from_state_dict -> enable_vit_policy);
 4. drive: `step`, `camera()`, the forward, throttle 100 and steering clamp(10 x output) (dino.drive), and the share of agents that
    survive every episode.
@@ -41,7 +46,10 @@ def main(argv=None):
                     "randomly initialised and frozen: a random-feature baseline, not the reference's pretrained features")
     ap.add_argument("--small", action="store_true", help="a reduced network (32 x 32 frames, width 32, 2 blocks) for the tests")
     ap.add_argument("--device-policy", action="store_true")
+    ap.add_argument("--device-update", action="store_true", help="train the head on the device (implies --device-policy)")
+    ap.add_argument("--val-split", type=float, default=0.1, help="with --device-update: the share of the frames held out for validation")
     a = ap.parse_args(argv)
+    a.device_policy = a.device_policy or a.device_update
     torch.manual_seed(a.seed)
     shape = dict(dino.SMALL) if a.small else {}
     heads = shape.get("heads", 6)
@@ -60,13 +68,24 @@ def main(argv=None):
     print("recorded %d frames of living agents out of %d" % (frames.shape[0], a.agents * a.demo_steps))
     # 2. training
     t0 = time.perf_counter()
-    losses = dino.train(model, frames, actions, epochs=a.epochs, seed=a.seed)
-    print("trained the head for %d epochs on a %s backbone in %.1f s: loss %s"
-          % (a.epochs, "given" if a.backbone else "random frozen", time.perf_counter() - t0, " ".join("%.4g" % v for v in losses)))
+    val_losses = []
+    if a.device_update:
+        sd = model.state_dict()
+        cfg = dino.vit_config_from_state_dict(sd, heads=heads)
+        venv.enable_vit_policy(cfg, dino.vit_params_from_state_dict(sd, heads=heads))
+        losses, val_losses = dino.train_device(venv, frames, actions, epochs=a.epochs, seed=a.seed, val_split=a.val_split)
+        dino.head_from_device(venv, model)
+        print("trained the head on the device for %d epochs on a %s backbone in %.1f s: loss %s; validation loss %s"
+              % (a.epochs, "given" if a.backbone else "random frozen", time.perf_counter() - t0, " ".join("%.4g" % v for v in losses),
+                 " ".join("%.4g" % v for v in val_losses)))
+    else:
+        losses = dino.train(model, frames, actions, epochs=a.epochs, seed=a.seed)
+        print("trained the head for %d epochs on a %s backbone in %.1f s: loss %s"
+              % (a.epochs, "given" if a.backbone else "random frozen", time.perf_counter() - t0, " ".join("%.4g" % v for v in losses)))
     # 3. hand-over
     sd = model.state_dict()
     cfg = dino.vit_config_from_state_dict(sd, heads=heads)
-    if a.device_policy:
+    if a.device_policy and not a.device_update:
         venv.enable_vit_policy(cfg, dino.vit_params_from_state_dict(sd, heads=heads))
     # the first driven step, recorded: the PyTorch forward's output and, with --device-policy, the device's on the same frames
     venv.reset()
@@ -89,7 +108,7 @@ def main(argv=None):
         survival.append(float((~venv.done).float().mean()))
         print("episode %d: %d agents, %d steps with the %s in %.3f s (%.3g agent-steps/s); survival %.3f"
               % (episode, a.agents, steps, "device policy" if a.device_policy else "PyTorch forward", dt, a.agents * steps / dt, survival[-1]))
-    out = {"model": model, "config": cfg, "first": first, "survival": survival, "losses": losses,
+    out = {"model": model, "config": cfg, "first": first, "survival": survival, "losses": losses, "val_losses": val_losses,
            "throttle": venv.throttle.clone(), "steering": venv.steering.clone()}
     print("actions finite %s" % bool(torch.isfinite(out["throttle"]).all() and torch.isfinite(out["steering"]).all()))
     venv.close()

@@ -1478,6 +1478,69 @@ OKENV_API int okenv_vit_act_host(const okenv_vit_config *config, const float *pa
  * own kernel; device < 0 (OKENV_DEBUG_ON_HOST) evaluates ok_vit_attend on the host.  1 <= T <= 1024, dh a multiple of 16 up to 64. */
 OKENV_API int okenv_debug_vit_attend(int32_t device, int32_t seqs, int32_t T, int32_t heads, int32_t dh, const float *qkv, float *ctx);
 
+/* ---- The image transformer driver's training: cached embeddings, head update -----------------------------------
+ * DinoControl's recipe (train_dino_control.py): the backbone is frozen, so its embeddings are computed once (okenv_vit_embed) and the
+ * head alone is trained on them with a weighted squared error against steering / steer_scale and Adam, one step per minibatch, in place
+ * in the parameters okenv_vit_act reads.  The rule, with its summation order, is written out in include/okenv_vithead.h
+ * (ok_vithead_*); every contraction of the update runs on the f32-input matrix cores. */
+
+/* The frozen backbone over m frames (device, 4-byte aligned, [m][S][S][4] uint8, frame_bytes = m S S 4 in all; m is any positive
+ * number, not the population): the final LayerNorm of every frame's class token to embedding [m][D] (device), bit for bit what
+ * okenv_vit_act records.  Runs in passes of the act's agents_per_pass through the act's own workspace and kernels, and touches no
+ * agent field.  No synchronisation, no allocation: capturable.  OKENV_ERR_STATE before okenv_vit_create or okenv_vit_set_params;
+ * OKENV_ERR_INVALID for NULL arguments, m < 1 or another frame_bytes. */
+OKENV_API int okenv_vit_embed(okenv_t h, const uint8_t *frames, int32_t m, int64_t frame_bytes, float *embedding);
+
+typedef struct okenv_vit_head_params {
+    float lr;        /* > 0                                        (the reference: 1e-4) */
+    float beta1;     /* [0, 1), torch: 0.9                                               */
+    float beta2;     /* [0, 1), torch: 0.999                                             */
+    float eps;       /* > 0, torch: 1e-8                                                 */
+    float weight;    /* of a sample whose |label| > threshold; > 0 (5)                   */
+    float threshold; /* >= 0                                       (0.1)                 */
+} okenv_vit_head_params;
+
+/* The head's parameters [W1 | b1 | W2 | b2 | w3 | b3] (the tail of the driver's parameter vector) and Adam's moments, each
+ * dim * hidden1 + hidden1 + hidden2 * hidden1 + hidden2 + hidden2 + 1 floats (57 601 at the reference shape); t: steps taken so far. */
+typedef struct okenv_vit_head_state {
+    float  *params, *m, *v;
+    int64_t t;
+} okenv_vit_head_state;
+
+/* Where an update reports: device pointers (host pointers for okenv_vit_head_update_host), each may be NULL (skipped). */
+typedef struct okenv_vit_head_output {
+    float *loss; /* [epochs * ceil(M / B)]  per minibatch, from before its step         */
+    float *grad; /* the last minibatch's gradient, in the head's parameter order        */
+} okenv_vit_head_output;
+
+/* LDS bytes of the update's forward kernel for a head dim -> hidden1 -> hidden2 -> 1: a pure host function.  A head is trained only
+ * if this fits 160 KB.  0 for widths outside okenv_vit_config's limits. */
+OKENV_API int64_t okenv_vit_head_lds_bytes(int32_t dim, int32_t hidden1, int32_t hidden2);
+/* Attaches Adam state (m = v = 0, t = 0) for the head of the handle's policy; okenv_vit_create drops it again.  OKENV_ERR_STATE
+ * before okenv_vit_create or okenv_vit_set_params; OKENV_ERR_INVALID for NULL arguments, lr <= 0, a beta outside [0, 1), eps <= 0,
+ * weight <= 0, threshold < 0 (or NaN), a config whose steer_scale is 0, an LDS plan beyond 160 KB. */
+OKENV_API int okenv_vit_head_learner_create(okenv_t h, const okenv_vit_head_params *params);
+/* m = v = 0, t = 0 again.  (okenv_vit_set_params leaves the moments alone.) */
+OKENV_API int okenv_vit_head_learner_reset(okenv_t h);
+/* The head's parameters and Adam's moments to host or device pointers (each may be NULL), and t; synchronises. */
+OKENV_API int okenv_vit_head_learner_get_state(okenv_t h, okenv_vit_head_state *out);
+/* Enqueues every minibatch of every epoch on the handle's stream, two kernels each: no synchronisation, and no allocation after the
+ * first call of a given min(B, M).  embedding [M][D], steer [M]: device; `order` is a device array [epochs][M] of int32 sample indices
+ * or NULL (sequential).  Steps the head's slice of the handle's parameter vector in place: the next okenv_vit_act on the stream acts
+ * with the new head and okenv_vit_get_params returns it.  The step number advances per enqueued minibatch.
+ * OKENV_ERR_STATE before okenv_vit_head_learner_create; OKENV_ERR_INVALID for a NULL handle, embedding or steer, M, B or epochs < 1,
+ * epochs * M >= 2^31. */
+OKENV_API int okenv_vit_head_update(okenv_t h, const float *embedding, const float *steer, int32_t M, int32_t B, int32_t epochs, const int32_t *order,
+                                    const okenv_vit_head_output *out);
+/* The loss of every minibatch of one sequential pass with no update, to loss [ceil(M / B)] (device): the validation loop. */
+OKENV_API int okenv_vit_head_eval(okenv_t h, const float *embedding, const float *steer, int32_t M, int32_t B, float *loss);
+/* The same rule on host arrays, no GPU needed.  okenv_vit_act_host gives the embedding on the host. */
+OKENV_API int okenv_vit_head_update_host(const okenv_vit_head_params *params, int32_t dim, int32_t hidden1, int32_t hidden2, float steer_scale,
+                                         okenv_vit_head_state *state, const float *embedding, const float *steer, int32_t M, int32_t B, int32_t epochs,
+                                         const int32_t *order, const okenv_vit_head_output *out);
+OKENV_API int okenv_vit_head_eval_host(const okenv_vit_head_params *params, int32_t dim, int32_t hidden1, int32_t hidden2, float steer_scale,
+                                       const float *head, const float *embedding, const float *steer, int32_t M, int32_t B, float *loss);
+
 /* ---- zero-copy access for device-side callers ------------------------ */
 
 /* Device address and size of one library-owned struct-of-arrays field (okenv_field), valid for the handle's lifetime.

@@ -119,6 +119,8 @@ SYMBOLS = [
     "okenv_qcnn_push_host", "okenv_qcnn_batch_host", "okenv_debug_qcnn_grey_host", "okenv_debug_qcnn_forward_planes_host",
     "okenv_vit_lds_bytes", "okenv_vit_create", "okenv_vit_num_params", "okenv_vit_set_params", "okenv_vit_get_params", "okenv_vit_act",
     "okenv_vit_act_host", "okenv_debug_vit_attend",
+    "okenv_vit_embed", "okenv_vit_head_lds_bytes", "okenv_vit_head_learner_create", "okenv_vit_head_learner_reset",
+    "okenv_vit_head_learner_get_state", "okenv_vit_head_update", "okenv_vit_head_eval", "okenv_vit_head_update_host", "okenv_vit_head_eval_host",
 ]
 
 # enum okenv_step_form / okenv_step_form_attr of include/okenv.h, in order (tests/test_step_form_table.py keeps them in step)
@@ -879,6 +881,75 @@ def debug_vit_attend(qkv, heads, device=DEBUG_ON_HOST):
     return out
 
 
+# the image transformer driver's training (include/okenv.h)
+VIT_HEAD_CHUNK = 64
+
+
+class OkenvVitHeadParams(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight", C.c_float), ("threshold", C.c_float)]
+
+
+class OkenvVitHeadState(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("t", C.c_int64)]
+
+
+class OkenvVitHeadOutput(C.Structure):
+    _fields_ = [("loss", C.c_void_p), ("grad", C.c_void_p)]
+
+
+def vit_head_params(lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight=5.0, threshold=0.1):
+    """okenv_vit_head_params with the reference's values as defaults (train_dino_control.py)."""
+    return OkenvVitHeadParams(float(lr), float(beta1), float(beta2), float(eps), float(weight), float(threshold))
+
+
+def vit_head_num_params(D, H1, H2):
+    return H1 * D + H1 + H2 * H1 + H2 + H2 + 1
+
+
+def vit_head_offset(cfg):
+    """Where the head begins in the driver's parameter vector (vit_layout's head.net.0.weight)."""
+    return vit_num_params(cfg) - vit_head_num_params(cfg.dim, cfg.head_hidden1, cfg.head_hidden2)
+
+
+def vit_head_lds_bytes(D, H1, H2):
+    """okenv_vit_head_lds_bytes: the LDS of the update's forward kernel, 0 outside the limits.  No GPU needed."""
+    return int(load().okenv_vit_head_lds_bytes(int(D), int(H1), int(H2)))
+
+
+def vit_head_update_host(params, shape, steer_scale, state, embedding, steer, B, epochs=1, order=None, want=("loss", "grad")):
+    """The head's update on host arrays, no GPU needed (okenv_vit_head_update_host).  params: vit_head_params(...); shape: (D, H1, H2);
+    state: dict of float32 numpy arrays "params", "m", "v" (the head's slice) and the int "t" -- copied, the new state is returned;
+    embedding [M, D], steer [M]; order: None or int32 [epochs, M].  Returns (new state, outputs): "loss" holds one value per
+    minibatch, "grad" the last minibatch's gradient."""
+    D, H1, H2 = (int(v) for v in shape)
+    embedding = None if embedding is None else np.ascontiguousarray(embedding, np.float32)
+    steer = None if steer is None else np.ascontiguousarray(steer, np.float32)
+    M = int(steer.shape[0]) if steer is not None else 0
+    new = {k: np.array(v, dtype=np.float32, copy=True).ravel() for k, v in state.items() if k != "t" and v is not None}
+    st = fill_pointers(OkenvVitHeadState(), new, "vit head state")
+    st.t = int(state.get("t", 0))
+    steps = int(epochs) * ((M + int(B) - 1) // int(B)) if M > 0 and B > 0 and epochs > 0 else 0
+    sizes = {"loss": steps, "grad": vit_head_num_params(D, H1, H2)}
+    outs = {k: np.zeros(sizes[k], dtype=np.float32) for k in want}
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.int32)
+    check(load().okenv_vit_head_update_host(C.byref(params) if params is not None else None, D, H1, H2, float(steer_scale), C.byref(st), ptr(embedding),
+                                            ptr(steer), M, int(B), int(epochs), ptr(order),
+                                            C.byref(fill_pointers(OkenvVitHeadOutput(), {k: v for k, v in outs.items() if v.size}, "vit head output"))))
+    new["t"] = int(st.t)
+    return new, outs
+
+
+def vit_head_eval_host(params, shape, steer_scale, head, embedding, steer, B):
+    """okenv_vit_head_eval_host: the loss of every minibatch of one sequential pass, float32 [ceil(M / B)].  No GPU needed."""
+    D, H1, H2 = (int(v) for v in shape)
+    head, embedding, steer = (np.ascontiguousarray(a, np.float32) for a in (head, embedding, steer))
+    M = int(steer.shape[0])
+    loss = np.zeros((M + int(B) - 1) // int(B) if M > 0 and B > 0 else 0, np.float32)
+    check(load().okenv_vit_head_eval_host(C.byref(params), D, H1, H2, float(steer_scale), ptr(head), ptr(embedding), ptr(steer), M, int(B), ptr(loss)))
+    return loss
+
+
 def qcnn_forward_planes_host(cfg, params, planes):
     """The network of okenv_qcnn_act_host on grey planes [n][S][S] float32 -> q [n][A] (a test hook).  No GPU needed."""
     planes, params = np.ascontiguousarray(planes, np.float32), np.ascontiguousarray(params, np.float32)
@@ -1533,6 +1604,17 @@ def load(build_if_missing=True):
     L.okenv_vit_act.argtypes = [vp, vp, i64, C.POINTER(OkenvVitRecord)]
     L.okenv_vit_act_host.argtypes = [C.POINTER(OkenvVitConfig), vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.okenv_debug_vit_attend.argtypes = [i32, i32, i32, i32, i32, vp, vp]
+    L.okenv_vit_embed.argtypes = [vp, vp, i32, i64, vp]
+    L.okenv_vit_head_lds_bytes.argtypes = [i32, i32, i32]
+    L.okenv_vit_head_lds_bytes.restype = C.c_int64
+    L.okenv_vit_head_learner_create.argtypes = [vp, C.POINTER(OkenvVitHeadParams)]
+    L.okenv_vit_head_learner_reset.argtypes = [vp]
+    L.okenv_vit_head_learner_get_state.argtypes = [vp, C.POINTER(OkenvVitHeadState)]
+    L.okenv_vit_head_update.argtypes = [vp, vp, vp, i32, i32, i32, vp, C.POINTER(OkenvVitHeadOutput)]
+    L.okenv_vit_head_eval.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.okenv_vit_head_update_host.argtypes = [C.POINTER(OkenvVitHeadParams), i32, i32, i32, C.c_float, C.POINTER(OkenvVitHeadState), vp, vp, i32, i32, i32, vp,
+                                             C.POINTER(OkenvVitHeadOutput)]
+    L.okenv_vit_head_eval_host.argtypes = [C.POINTER(OkenvVitHeadParams), i32, i32, i32, C.c_float, vp, vp, vp, i32, i32, vp]
     _lib = L
     return L
 

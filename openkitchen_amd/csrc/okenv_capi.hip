@@ -39,6 +39,7 @@
 #include "ok_memory.h"
 #include "ok_qcnn.h"
 #include "ok_vit.h"
+#include "ok_vithead.h"
 #include "ok_expert.h"
 
 namespace
@@ -626,6 +627,14 @@ struct okenv
     okenv_vit_config        vit{};
     float                  *d_vit_work{nullptr};
     size_t                  vit_work_cap{0}, vit_pass{0};
+    // ... and its head's learner (okenv_vit_head_learner_create): Adam's moments [m | v] of the head's parameters, the step number, the
+    // scratch of a minibatch's rows
+    bool                    vit_head_ok{false};
+    okenv_vit_head_params   vit_head{};
+    int64_t                 vit_head_t{0};
+    float                  *d_vit_head_mv{nullptr};
+    size_t                  vit_head_cap{0};
+    OkUpdateScratch         vit_head_scratch;
 };
 
 struct okenv_track
@@ -1814,6 +1823,146 @@ void vitLinear(okenv *h, OkVitLinearParams p, const long M, const int K, const i
                        dim3(kVitThreads), 0, h->stream, p);
 }
 
+// The backbone of one pass: the frames of `count` sequences (at most vit_pass) through the patch embedding and the blocks, into the
+// workspace's x [count][T][D]; 1 + 7 depth launches on the stream
+int vitBackbone(okenv *h, const uint8_t *frames, const size_t count)
+{
+    const ok_vit_shape  s  = okVitShape(h->vit);
+    const ok_vit_layout at = ok_vit_offsets(s);
+    const OkVitPlaces   pl = okVitPlaces(s);
+    const int           T = pl.T, D = s.D, F = s.ff;
+    const float        *prm = h->vit_drv.d;
+    OkVitLinearParams   lp{};
+    lp.S = s.S, lp.P = s.P, lp.side = ok_vit_side(s), lp.T = T;
+    for (int c = 0; c < 3; ++c)
+        lp.mean[c] = h->vit.mean[c], lp.std[c] = h->vit.std[c];
+    lp.pos = prm + at.pos, lp.cls = prm + at.cls;
+    const long M = static_cast<long>(count) * T;
+    float     *x = h->d_vit_work, *n = x + static_cast<size_t>(M) * D, *ctx = n + static_cast<size_t>(M) * D, *qkv = ctx + static_cast<size_t>(M) * D,
+          *hid = qkv + static_cast<size_t>(M) * 3U * D;
+    lp.frames = frames;
+    vitLinear<kVitSrcPatch, kVitEpiPos>(h, lp, static_cast<long>(count) * (T - 1), ok_vit_patch_k(s), D, nullptr, 0, prm + at.pe_w, prm + at.pe_b, x, D);
+    OK_HIP(h, hipGetLastError());
+    const unsigned norm_blocks = static_cast<unsigned>((M + kVitNormRows - 1) / kVitNormRows);
+    OkVitAttendParams ap{};
+    ap.T = T, ap.D = D, ap.heads = s.heads, ap.dh = pl.dh, ap.qtiles = (T + kVitQueries - 1) / kVitQueries;
+    ap.scale = ok_lidar_scale(pl.dh), ap.qkv = qkv, ap.ctx = ctx;
+    for (int i = 0; i < s.depth; ++i)
+    {
+        const float *bp = prm + at.block0 + static_cast<size_t>(i) * at.block_stride;
+        hipLaunchKernelGGL(okVitNormKernel, dim3(norm_blocks), dim3(kVitThreads), 0, h->stream, M, D, x, bp + at.n1_g, bp + at.n1_b, h->vit.ln_eps, n);
+        vitLinear<kVitSrcPlain, kVitEpiNone>(h, lp, M, D, 3 * D, n, D, bp + at.qkv_w, bp + at.qkv_b, qkv, 3L * D);
+        hipLaunchKernelGGL(okVitAttendKernel, dim3(static_cast<unsigned>(count * s.heads * ap.qtiles)), dim3(kVitThreads),
+                           sizeof(float) * static_cast<size_t>(pl.attend), h->stream, ap);
+        vitLinear<kVitSrcPlain, kVitEpiResidual>(h, lp, M, D, D, ctx, D, bp + at.proj_w, bp + at.proj_b, x, D);
+        hipLaunchKernelGGL(okVitNormKernel, dim3(norm_blocks), dim3(kVitThreads), 0, h->stream, M, D, x, bp + at.n2_g, bp + at.n2_b, h->vit.ln_eps, n);
+        vitLinear<kVitSrcPlain, kVitEpiGelu>(h, lp, M, D, F, n, D, bp + at.fc1_w, bp + at.fc1_b, hid, F);
+        vitLinear<kVitSrcPlain, kVitEpiResidual>(h, lp, M, F, D, hid, F, bp + at.fc2_w, bp + at.fc2_b, x, D);
+        OK_HIP(h, hipGetLastError());
+    }
+    return OKENV_OK;
+}
+
+// okenv_vit_embed behind its OK_QUIESCE: the backbone over m frames in passes of vit_pass, the class tokens' LayerNorm behind each
+int vitEmbed(okenv *h, const uint8_t *frames, const int32_t m, const int64_t frame_bytes, float *embedding)
+{
+    if (const int rc = driverGate(h, kVitDriver, "embed", kGateHandle | kGateCreated | kGateSet, true, 1U))
+        return rc;
+    const ok_vit_shape s = okVitShape(h->vit);
+    const size_t       frame = static_cast<size_t>(s.S) * static_cast<size_t>(s.S) * 4U;
+    if (!frames || !embedding)
+        return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "embed", "NULL argument");
+    if (m < 1 || frame_bytes != static_cast<int64_t>(m) * static_cast<int64_t>(frame))
+        return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "embed", "m must be at least 1 and frame_bytes m x image_size x image_size x 4");
+    if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
+        return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "embed", "frames must be 4-byte aligned");
+    OK_HIP(h, hipSetDevice(h->device));
+    const ok_vit_layout at = ok_vit_offsets(s);
+    const int           T = ok_vit_tokens(s), D = s.D;
+    for (size_t a0 = 0; a0 < static_cast<size_t>(m); a0 += h->vit_pass)
+    {
+        const size_t count = std::min(h->vit_pass, static_cast<size_t>(m) - a0);
+        if (const int rc = vitBackbone(h, frames + a0 * frame, count))
+            return rc;
+        hipLaunchKernelGGL(okVitEmbedKernel, dim3(static_cast<unsigned>((count + kVitNormRows - 1) / kVitNormRows)), dim3(kVitThreads), 0, h->stream,
+                           static_cast<int>(count), D, static_cast<long>(T) * D, h->d_vit_work, h->vit_drv.d + at.norm_g, h->vit_drv.d + at.norm_b, h->vit.ln_eps,
+                           embedding + a0 * D);
+        OK_HIP(h, hipGetLastError());
+    }
+    return OKENV_OK;
+}
+
+// The head's slice of the handle's parameter vector, and Adam's moments k = 0 (m), 1 (v)
+float *vitHeadParams(const okenv *h)
+{
+    return h->vit_drv.d + ok_vit_offsets(okVitShape(h->vit)).hw0;
+}
+
+int vitHeadTotal(const okenv *h)
+{
+    return ok_vithead_offsets(h->vit.dim, h->vit.head_hidden1, h->vit.head_hidden2).total;
+}
+
+float *vitHeadMoment(const okenv *h, const int k)
+{
+    return h->d_vit_head_mv + static_cast<size_t>(k) * h->vit_head_cap;
+}
+
+// okenv_vit_head_update (update == true: `epochs` passes in `order`, a step per minibatch) and okenv_vit_head_eval (one sequential pass, the
+// losses only) behind their OK_QUIESCE: two launches per minibatch on the stream
+int vitHeadRun(okenv *h, const char *entry, const bool update, const float *embedding, const float *steer, const int32_t M, const int32_t B, const int32_t epochs,
+               const int32_t *order, float *loss, float *grad)
+{
+    if (!h)
+        return fail(h, OKENV_ERR_INVALID, std::string(entry) + ": NULL handle");
+    if (!h->vit_drv.ok || !h->vit_head_ok)
+        return fail(h, OKENV_ERR_STATE, std::string(entry) + ": call okenv_vit_head_learner_create first");
+    if (const char *why = okVitHeadCheckCall(embedding, steer, M, B, epochs))
+        return fail(h, OKENV_ERR_INVALID, std::string(entry) + ": " + why);
+    OK_HIP(h, hipSetDevice(h->device));
+    const int    D = h->vit.dim, H1 = h->vit.head_hidden1, H2 = h->vit.head_hidden2, slices = okLearnMinibatches(M, B);
+    const size_t qp_max = (static_cast<size_t>(std::min(B, M)) + OK_VITHEAD_CHUNK - 1U) / OK_VITHEAD_CHUNK * OK_VITHEAD_CHUNK;
+    if (const int rc = growScratch(h, h->vit_head_scratch, sizeof(float) * okVitHeadScratchFloats(D, H1, H2, qp_max)))
+        return rc;
+    const okenv_learner_params lp = okVitHeadAdam(h->vit_head);
+    OkVitHeadForwardParams     f{};
+    f.D = D, f.H1 = H1, f.H2 = H2, f.M = M, f.head = vitHeadParams(h), f.embedding = embedding, f.steer = steer;
+    f.steer_scale = h->vit.steer_scale, f.weight = h->vit_head.weight, f.threshold = h->vit_head.threshold;
+    f.out = okVitHeadScratchAt(reinterpret_cast<float *>(h->vit_head_scratch.part), D, H1, H2, qp_max);
+    OkVitHeadGradParams g{};
+    g.D = D, g.H1 = H1, g.H2 = H2, g.in = f.out, g.head = vitHeadParams(h), g.m = vitHeadMoment(h, 0), g.v = vitHeadMoment(h, 1);
+    const int    units = okVitHeadUnits(D, H1, H2);
+    const size_t lds = okVitHeadLdsBytes(D, H1, H2);
+    for (int e = 0; e < epochs; ++e)
+        for (int k = 0; k < slices; ++k)
+        {
+            f.base  = static_cast<long>(k) * B;
+            f.Bk    = static_cast<int>(std::min<long>(B, M - f.base));
+            f.order = order != nullptr ? order + static_cast<size_t>(e) * M : nullptr;
+            g.Bk    = f.Bk;
+            g.chunks = (f.Bk + OK_VITHEAD_CHUNK - 1) / OK_VITHEAD_CHUNK;
+            g.loss   = loss != nullptr ? loss + static_cast<size_t>(e) * slices + k : nullptr;
+            hipLaunchKernelGGL(okVitHeadForwardKernel, dim3(static_cast<unsigned>(g.chunks * (OK_VITHEAD_CHUNK / kVitHeadRows))), dim3(kLidarThreads), lds, h->stream, f);
+            OK_HIP(h, hipGetLastError());
+            if (update)
+            {
+                g.first_unit = 0;
+                g.adam       = okLearnAdamConsts(lp, h->vit_head_t + 1);
+                g.grad       = (e + 1 == epochs && k + 1 == slices) ? grad : nullptr;
+                hipLaunchKernelGGL(okVitHeadGradKernel<true>, dim3(static_cast<unsigned>((units + kLidarWaves - 1) / kLidarWaves)), dim3(kLidarThreads), 0, h->stream, g);
+                OK_HIP(h, hipGetLastError());
+                h->vit_head_t += 1; // (the step number advances once the step's kernels are enqueued, as in okenv_ppo_update)
+            }
+            else if (loss != nullptr)
+            {
+                g.first_unit = units - 1;
+                hipLaunchKernelGGL(okVitHeadGradKernel<false>, dim3(1), dim3(64), 0, h->stream, g);
+                OK_HIP(h, hipGetLastError());
+            }
+        }
+    return OKENV_OK;
+}
+
 // okenv_vit_act behind its OK_QUIESCE: the fixed launch sequence (ok_vit.h), once per pass of vit_pass agents, on the stream
 int vitAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_vit_record *rec)
 {
@@ -1831,42 +1980,15 @@ int vitAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const oke
     if (const int rc = actBegin(h, kVitDriver, 1U, missing))
         return rc;
     const ok_vit_shape  s  = okVitShape(h->vit);
-    const ok_vit_layout at = ok_vit_offsets(s);
     const OkVitPlaces   pl = okVitPlaces(s);
-    const int           T = pl.T, D = s.D, F = s.ff;
     const float        *prm = h->vit_drv.d;
     const size_t        frame = static_cast<size_t>(s.S) * static_cast<size_t>(s.S) * 4U;
-    OkVitLinearParams   lp{};
-    lp.S = s.S, lp.P = s.P, lp.side = ok_vit_side(s), lp.T = T;
-    for (int c = 0; c < 3; ++c)
-        lp.mean[c] = h->vit.mean[c], lp.std[c] = h->vit.std[c];
-    lp.pos = prm + at.pos, lp.cls = prm + at.cls;
     for (size_t a0 = 0; a0 < static_cast<size_t>(h->shape.N); a0 += h->vit_pass)
     {
         const size_t count = std::min(h->vit_pass, static_cast<size_t>(h->shape.N) - a0);
-        const long   M = static_cast<long>(count) * T;
-        float       *x = h->d_vit_work, *n = x + static_cast<size_t>(M) * D, *ctx = n + static_cast<size_t>(M) * D, *qkv = ctx + static_cast<size_t>(M) * D,
-              *hid = qkv + static_cast<size_t>(M) * 3U * D;
-        lp.frames = frames + a0 * frame;
-        vitLinear<kVitSrcPatch, kVitEpiPos>(h, lp, static_cast<long>(count) * (T - 1), ok_vit_patch_k(s), D, nullptr, 0, prm + at.pe_w, prm + at.pe_b, x, D);
-        OK_HIP(h, hipGetLastError());
-        const unsigned norm_blocks = static_cast<unsigned>((M + kVitNormRows - 1) / kVitNormRows);
-        OkVitAttendParams ap{};
-        ap.T = T, ap.D = D, ap.heads = s.heads, ap.dh = pl.dh, ap.qtiles = (T + kVitQueries - 1) / kVitQueries;
-        ap.scale = ok_lidar_scale(pl.dh), ap.qkv = qkv, ap.ctx = ctx;
-        for (int i = 0; i < s.depth; ++i)
-        {
-            const float *bp = prm + at.block0 + static_cast<size_t>(i) * at.block_stride;
-            hipLaunchKernelGGL(okVitNormKernel, dim3(norm_blocks), dim3(kVitThreads), 0, h->stream, M, D, x, bp + at.n1_g, bp + at.n1_b, h->vit.ln_eps, n);
-            vitLinear<kVitSrcPlain, kVitEpiNone>(h, lp, M, D, 3 * D, n, D, bp + at.qkv_w, bp + at.qkv_b, qkv, 3L * D);
-            hipLaunchKernelGGL(okVitAttendKernel, dim3(static_cast<unsigned>(count * s.heads * ap.qtiles)), dim3(kVitThreads),
-                               sizeof(float) * static_cast<size_t>(pl.attend), h->stream, ap);
-            vitLinear<kVitSrcPlain, kVitEpiResidual>(h, lp, M, D, D, ctx, D, bp + at.proj_w, bp + at.proj_b, x, D);
-            hipLaunchKernelGGL(okVitNormKernel, dim3(norm_blocks), dim3(kVitThreads), 0, h->stream, M, D, x, bp + at.n2_g, bp + at.n2_b, h->vit.ln_eps, n);
-            vitLinear<kVitSrcPlain, kVitEpiGelu>(h, lp, M, D, F, n, D, bp + at.fc1_w, bp + at.fc1_b, hid, F);
-            vitLinear<kVitSrcPlain, kVitEpiResidual>(h, lp, M, F, D, hid, F, bp + at.fc2_w, bp + at.fc2_b, x, D);
-            OK_HIP(h, hipGetLastError());
-        }
+        float       *x = h->d_vit_work;
+        if (const int rc = vitBackbone(h, frames + a0 * frame, count))
+            return rc;
         OkVitFinalParams fp{};
         fp.st = h->st, fp.a0 = static_cast<long>(a0), fp.count = static_cast<int>(count), fp.s = s, fp.params = prm, fp.x = x;
         fp.eps = h->vit.ln_eps, fp.throttle = h->vit.throttle, fp.steer_scale = h->vit.steer_scale;
@@ -2517,7 +2639,7 @@ extern "C"
             (void)hipEventDestroy(e.stop);
         }
         for (OkUpdateScratch *u : {&h->batch_scratch, &h->learn_scratch, &h->dqn_scratch, &h->ddpg_scratch, &h->reinforce_scratch, &h->gauss_scratch, &h->gcl_scratch[0],
-                                   &h->gcl_scratch[1], &h->gcl_scratch[2], &h->gcl_adv_scratch})
+                                   &h->gcl_scratch[1], &h->gcl_scratch[2], &h->gcl_adv_scratch, &h->vit_head_scratch})
             for (hipEvent_t e : u->log.events)
                 (void)hipEventDestroy(e);
         if (h->own_stream && h->stream)
@@ -4830,6 +4952,7 @@ extern "C"
         const size_t       pass = okVitAgentsPerPass(*config, static_cast<size_t>(h->shape.N));
         if (const char *why = okVitWorkspaceBad(*config, pass))
             return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "create", why);
+        h->vit_head_ok = false; // (the head's learner belongs to the policy that goes)
         if (const int rc = driverCreateFlat(h, kVitDriver, static_cast<size_t>(ok_vit_offsets(s).total), kernelOf(okVitAttendKernel)))
             return rc;
         h->vit_drv.ok = false; // (until the workspace stands)
@@ -4920,6 +5043,122 @@ extern "C"
                            okVitAttendLdsBytes(T, dh), nullptr, ap);
         OK_HIP(nullptr, hipGetLastError());
         OK_HIP(nullptr, hipMemcpy(ctx, dc, 4U * nc, hipMemcpyDeviceToHost));
+        return OKENV_OK;
+    }
+
+    // ---- The image transformer driver's training (ok_vithead.h) ---------------------------------------------------------------------
+
+    int okenv_vit_embed(okenv_t h, const uint8_t *frames, int32_t m, int64_t frame_bytes, float *embedding)
+    {
+        OK_QUIESCE(h);
+        return vitEmbed(h, frames, m, frame_bytes, embedding);
+    }
+
+    int64_t okenv_vit_head_lds_bytes(int32_t dim, int32_t hidden1, int32_t hidden2)
+    {
+        return static_cast<int64_t>(okVitHeadLdsBytes(dim, hidden1, hidden2));
+    }
+
+    int okenv_vit_head_learner_create(okenv_t h, const okenv_vit_head_params *params)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_vit_head_learner_create: NULL handle");
+        if (const char *why = okVitHeadCheckParams(params))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_vit_head_learner_create: ") + why);
+        if (!h->vit_drv.ok || !h->vit_drv.set[0])
+            return fail(h, OKENV_ERR_STATE, "okenv_vit_head_learner_create: needs a policy that has its parameters (okenv_vit_create, okenv_vit_set_params)");
+        if (const char *why = okVitHeadCheckShape(h->vit.dim, h->vit.head_hidden1, h->vit.head_hidden2, h->vit.steer_scale))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_vit_head_learner_create: ") + why);
+        OK_HIP(h, hipSetDevice(h->device));
+        h->vit_head_ok = false;
+        const size_t total = static_cast<size_t>(vitHeadTotal(h));
+        if (total > h->vit_head_cap)
+        {
+            h->vit_head_cap = 0; // (a failed allocation leaves none)
+            if (const int rc = regrow(h, {fresh(h->d_vit_head_mv, 2U * total)}))
+                return rc;
+            h->vit_head_cap = total;
+        }
+        if (const int rc = raiseLdsLimit(h, {kernelOf(okVitHeadForwardKernel)}))
+            return rc;
+        OK_HIP(h, hipMemsetAsync(h->d_vit_head_mv, 0, 2U * h->vit_head_cap * sizeof(float), h->stream));
+        h->vit_head    = *params;
+        h->vit_head_t  = 0;
+        h->vit_head_ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_vit_head_learner_reset(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->vit_drv.ok || !h->vit_head_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_vit_head_learner_reset: call okenv_vit_head_learner_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        OK_HIP(h, hipMemsetAsync(h->d_vit_head_mv, 0, 2U * h->vit_head_cap * sizeof(float), h->stream));
+        h->vit_head_t = 0;
+        return OKENV_OK;
+    }
+
+    int okenv_vit_head_learner_get_state(okenv_t h, okenv_vit_head_state *out)
+    {
+        OK_QUIESCE(h);
+        if (!h || !out)
+            return fail(h, OKENV_ERR_INVALID, "okenv_vit_head_learner_get_state: NULL argument");
+        if (!h->vit_drv.ok || !h->vit_head_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_vit_head_learner_get_state: call okenv_vit_head_learner_create first");
+        const int n = vitHeadTotal(h);
+        if (const int rc = driverGet(h, {vectorOf(vitHeadParams(h), out->params, n), vectorOf(vitHeadMoment(h, 0), out->m, n), vectorOf(vitHeadMoment(h, 1), out->v, n)}))
+            return rc;
+        out->t = h->vit_head_t;
+        return OKENV_OK;
+    }
+
+    int okenv_vit_head_update(okenv_t h, const float *embedding, const float *steer, int32_t M, int32_t B, int32_t epochs, const int32_t *order,
+                              const okenv_vit_head_output *out)
+    {
+        OK_QUIESCE(h);
+        return vitHeadRun(h, "okenv_vit_head_update", true, embedding, steer, M, B, epochs, order, out != nullptr ? out->loss : nullptr,
+                          out != nullptr ? out->grad : nullptr);
+    }
+
+    int okenv_vit_head_eval(okenv_t h, const float *embedding, const float *steer, int32_t M, int32_t B, float *loss)
+    {
+        OK_QUIESCE(h);
+        if (h != nullptr && h->vit_head_ok && loss == nullptr)
+            return fail(h, OKENV_ERR_INVALID, "okenv_vit_head_eval: NULL argument");
+        return vitHeadRun(h, "okenv_vit_head_eval", false, embedding, steer, M, B, 1, nullptr, loss, nullptr);
+    }
+
+    int okenv_vit_head_update_host(const okenv_vit_head_params *params, int32_t dim, int32_t hidden1, int32_t hidden2, float steer_scale,
+                                   okenv_vit_head_state *state, const float *embedding, const float *steer, int32_t M, int32_t B, int32_t epochs,
+                                   const int32_t *order, const okenv_vit_head_output *out)
+    {
+        if (const char *why = okVitHeadCheckParams(params))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_vit_head_update_host: ") + why);
+        if (const char *why = okVitHeadCheckShape(dim, hidden1, hidden2, steer_scale))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_vit_head_update_host: ") + why);
+        if (const char *why = okVitHeadCheckCall(embedding, steer, M, B, epochs))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_vit_head_update_host: ") + why);
+        if (state == nullptr || state->params == nullptr || state->m == nullptr || state->v == nullptr || state->t < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_vit_head_update_host: state is NULL, lacks a parameter or moment vector (NULL argument), or t < 0");
+        const okenv_vit_head_output none{};
+        okVitHeadUpdateHost(*params, dim, hidden1, hidden2, steer_scale, *state, embedding, steer, M, B, epochs, order, out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    int okenv_vit_head_eval_host(const okenv_vit_head_params *params, int32_t dim, int32_t hidden1, int32_t hidden2, float steer_scale, const float *head,
+                                 const float *embedding, const float *steer, int32_t M, int32_t B, float *loss)
+    {
+        if (const char *why = okVitHeadCheckParams(params))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_vit_head_eval_host: ") + why);
+        if (const char *why = okVitHeadCheckShape(dim, hidden1, hidden2, steer_scale))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_vit_head_eval_host: ") + why);
+        if (const char *why = okVitHeadCheckCall(embedding, steer, M, B, 1))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_vit_head_eval_host: ") + why);
+        if (head == nullptr || loss == nullptr)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_vit_head_eval_host: NULL argument");
+        okVitHeadEvalHost(*params, dim, hidden1, hidden2, steer_scale, head, embedding, steer, M, B, loss);
         return OKENV_OK;
     }
 

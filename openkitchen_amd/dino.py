@@ -2,8 +2,9 @@
 vit_small_patch8_224.dino) and the 384-128-64-1 policy head as PyTorch modules written anew with timm's parameter names, the hand-over
 of their weights to the device act (okenv_vit_*) and the driving loop of main_dino_control.cpp for N agents.
 
-timm is not needed: a checkpoint of timm's model loads into ViT by name (load_backbone).  Training stays in PyTorch and trains the head
-only.  The forward, once per environment step, runs in PyTorch or, handed over, as the device act (drive(policy="device")).
+timm is not needed: a checkpoint of timm's model loads into ViT by name (load_backbone).  Training trains the head only: in PyTorch
+(train), or on the device driver's own parameter vector (train_device: okenv_vit_embed and okenv_vit_head_update, DESIGN.md section
+31).  The forward, once per environment step, runs in PyTorch or, handed over, as the device act (drive(policy="device")).
 """
 import torch
 from torch import nn
@@ -175,6 +176,60 @@ def train(model, frames, actions, epochs=1, batch=64, lr=1e-4, seed=0, steer_sca
     return losses
 
 
+def epoch_means(losses, M, batch):
+    """Per-minibatch mean losses [epochs * ceil(M / batch)] (a tensor) -> the mean loss of every epoch as train forms it: each
+    minibatch's loss times its size, summed, over M."""
+    K = (M + batch - 1) // batch
+    sizes = torch.full((K,), float(batch), device=losses.device)
+    sizes[-1] = float(M - (K - 1) * batch)
+    return [float(v) for v in (losses.reshape(-1, K) * sizes).sum(dim=1) / M]
+
+
+def train_device(venv, frames, actions, epochs=1, batch=64, lr=1e-4, seed=0, val_split=0.0, embed_chunk=256):
+    """train's recipe on the device driver venv.enable_vit_policy attached: frames [M, S, S, 4] uint8 and actions [M, 2] on the device.
+    The frozen backbone's embeddings are computed once (venv.vit_embed, `embed_chunk` frames a call), then the head alone is trained in
+    the handle's parameter vector (venv.vit_head_update: a fresh Adam of `lr`, the weighted squared error against steering /
+    steer_scale), in the orders train draws (torch.randperm of the same generator).  The next venv.vit_act acts with the new head.
+    val_split > 0 keeps the last floor(M val_split) samples out of the training and evaluates them behind every epoch
+    (venv.vit_head_eval).  Returns the mean loss of every epoch, formed as train forms it; with val_split > 0 the pair (training
+    losses, validation losses)."""
+    assert getattr(venv, "vit_config", None) is not None, "call venv.enable_vit_policy(config, params) first"
+    total = int(frames.shape[0])
+    held = int(total * float(val_split))
+    M = total - held
+    assert M >= 1 and epochs >= 1 and batch >= 1
+    emb = torch.empty((total, venv.vit_config.dim), dtype=torch.float32, device=venv.device)
+    for at in range(0, total, embed_chunk):
+        venv.vit_embed(frames[at:at + embed_chunk], out=emb[at:at + embed_chunk])
+    steer = actions[:, 1].to(torch.float32).contiguous()
+    venv.enable_vit_head_learner(lr=lr)
+    gen = torch.Generator(device=frames.device).manual_seed(seed)
+    order = torch.stack([torch.randperm(M, device=frames.device, generator=gen) for _ in range(epochs)]).to(torch.int32)
+    if held == 0:
+        return epoch_means(venv.vit_head_update(emb[:M], steer[:M], batch, epochs, order), M, batch)
+    losses, val = [], []
+    for e in range(epochs):
+        losses.append(venv.vit_head_update(emb[:M], steer[:M], batch, 1, order[e:e + 1]))
+        val.append(venv.vit_head_eval(emb[M:], steer[M:], batch))
+    return epoch_means(torch.cat(losses), M, batch), epoch_means(torch.cat(val), held, batch)
+
+
+def head_from_device(venv, model):
+    """Copies the head the device holds (trained by train_device) into model.head, so that the PyTorch module follows the driver."""
+    cfg = venv.vit_config
+    flat = torch.empty(capi.vit_num_params(cfg), dtype=torch.float32, device=venv.device)
+    venv.env.vit_get_params(out=flat)
+    own = dict(model.named_parameters())
+    with torch.no_grad():
+        for name, at, shape in capi.vit_layout(cfg):
+            if name.startswith("head."):
+                n = 1
+                for s in shape:
+                    n *= int(s)
+                own[name].copy_(flat[at:at + n].reshape(shape))
+    return model
+
+
 def drive(venv, model, steps, policy="torch", graph_chunk=0, throttle=THROTTLE, steer_scale=STEER_SCALE, mean=capi.IMAGENET_MEAN, std=capi.IMAGENET_STD):
     """The loop of main_dino_control.cpp for every agent: `step`, the agents' frames (venv.camera()), the forward, the action (the
     constant throttle, the clamped steer_scale times the output), `steps` times; the environment's auto-reset stands in for
@@ -235,4 +290,4 @@ def drive(venv, model, steps, policy="torch", graph_chunk=0, throttle=THROTTLE, 
 
 
 __all__ = ["ViT", "PolicyHead", "load_backbone", "vit_config_from_state_dict", "vit_params_from_state_dict", "frames_to_input", "weighted_mse", "train",
-           "drive", "THROTTLE", "STEER_SCALE", "SMALL"]
+           "train_device", "epoch_means", "head_from_device", "drive", "THROTTLE", "STEER_SCALE", "SMALL"]

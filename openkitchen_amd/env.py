@@ -977,6 +977,44 @@ class BatchedEnvironment:
         sizes = record and {"action": self.N * 8, "output": self.N * 4, "embedding": self.N * self.vit_config.dim * 4, "alive": self.N}
         self._act("okenv_vit_act", capi.OkenvVitRecord, record, sizes, capi.ptr(frames), self.N * S * S * 4)
 
+    # ---- the image transformer driver's training (include/okenv.h) -------------------------------------------
+    def vit_embed(self, frames, m, out):
+        """The frozen backbone over m frames (any m >= 1, not the population): frames a device tensor / address of [m, S, S, 4] uint8,
+        out one of [m, D] float32.  Enqueued in passes of the act's agents_per_pass, no synchronisation; touches no agent field."""
+        S = self.vit_config.image_size
+        capi.check(self._L.okenv_vit_embed(self._h, capi.ptr(frames), int(m), int(m) * S * S * 4, capi.ptr(out)), self._h)
+
+    def vit_head_num_params(self):
+        c = self.vit_config
+        return capi.vit_head_num_params(c.dim, c.head_hidden1, c.head_hidden2)
+
+    def vit_head_learner_create(self, params=None, **members):
+        """Adam for the policy's head (capi.vit_head_params: the reference's lr 1e-4, weight 5, threshold 0.1): moments zeroed, t = 0."""
+        if params is None:
+            params = capi.vit_head_params(**members)
+        capi.check(self._L.okenv_vit_head_learner_create(self._h, C.byref(params)), self._h)
+
+    def vit_head_learner_reset(self):
+        capi.check(self._L.okenv_vit_head_learner_reset(self._h), self._h)
+
+    def vit_head_state(self, out=None):
+        """The head's parameters, Adam's two moments ("params", "m", "v") and the int t: float32 numpy arrays, or copied into the
+        device tensors of the dict `out` (any subset).  Synchronises."""
+        return self._get_state("okenv_vit_head_learner_get_state", dict.fromkeys(("params", "m", "v"), self.vit_head_num_params()), out,
+                               capi.OkenvVitHeadState)
+
+    def vit_head_update(self, embedding, steer, M, B, epochs=1, order=None, out=None):
+        """okenv_vit_head_update: enqueues every minibatch of every epoch on the handle's stream (two kernels each), no synchronisation.
+        embedding [M, D], steer [M]: device tensors / addresses, float32; order: None or a device int32 tensor [epochs, M]; out: None
+        or a dict under "loss" (float32, one per minibatch) and "grad" (the last minibatch's)."""
+        go = capi.fill_pointers(capi.OkenvVitHeadOutput(), out or {}, "vit head output")
+        capi.check(self._L.okenv_vit_head_update(self._h, capi.ptr(embedding), capi.ptr(steer), int(M), int(B), int(epochs), capi.ptr(order), C.byref(go)),
+                   self._h)
+
+    def vit_head_eval(self, embedding, steer, M, B, loss):
+        """okenv_vit_head_eval: the loss of every minibatch of one sequential pass into the device tensor loss [ceil(M / B)], no update."""
+        capi.check(self._L.okenv_vit_head_eval(self._h, capi.ptr(embedding), capi.ptr(steer), int(M), int(B), capi.ptr(loss)), self._h)
+
     # ---- Deep-Q image racers (include/okenv.h, DESIGN.md section 29) --------------------------------------------------------------
     def qcnn_create(self, config=None, **members):
         """Attaches the reference's image Q-network (RLRacers/DQN_CNN: CNN.hpp) to the handle; config: a capi.qcnn_config(...), or

@@ -639,6 +639,56 @@ class VectorEnvironment:
             raise ValueError("vit_act(frames) needs a contiguous uint8 tensor of shape (%d, %d, %d, 4) on %s" % (self.num_envs, S, S, self.device))
         self.env.vit_act(frames, record)
 
+    # ---- the image transformer driver's training (include/okenv.h) -------------------------------------------
+    def vit_embed(self, frames, out=None):
+        """The frozen backbone's embedding [m, D] float32 of m frames, any m >= 1: `frames` a contiguous uint8 tensor [m, S, S, 4] on
+        this device.  Runs in passes through the act's workspace on the environment's stream, no synchronisation, and touches no
+        agent.  `out`: a contiguous float32 tensor to fill in place; otherwise a new tensor."""
+        S, D = self.vit_config.image_size, self.vit_config.dim
+        if (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.device != self.device
+                or frames.dim() != 4 or frames.shape[0] < 1 or tuple(frames.shape[1:]) != (S, S, 4)):
+            raise ValueError("vit_embed(frames) needs a contiguous uint8 tensor of shape (m, %d, %d, 4) on %s" % (S, S, self.device))
+        m = int(frames.shape[0])
+        if out is None:
+            out = torch.empty((m, D), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (m, D) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("vit_embed(out=...) needs a contiguous float32 tensor of shape (%d, %d) on %s" % (m, D, self.device))
+        self.env.vit_embed(frames, m, out)
+        return out
+
+    def enable_vit_head_learner(self, **params):
+        """Adam for the head of the policy enable_vit_policy attached (capi.vit_head_params: lr, beta1, beta2, eps, weight, threshold;
+        the reference's by default).  enable_vit_policy drops it again."""
+        self.env.vit_head_learner_create(**params)
+
+    def _vit_head_data(self, embedding, steer):
+        D = self.vit_config.dim
+        for name, t, tail in (("embedding", embedding, (D,)), ("steer", steer, ())):
+            if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device
+                    or tuple(t.shape[1:]) != tail or t.shape[0] != embedding.shape[0] or t.shape[0] < 1):
+                raise ValueError("%s must be a contiguous float32 tensor of shape (M%s) on %s" % (name, ", %d" % D if tail else "", self.device))
+        return int(embedding.shape[0])
+
+    def vit_head_update(self, embedding, steer, batch, epochs, order=None, grad=None):
+        """Trains the head on cached embeddings [M, D] and recorded steering deltas [M] (float32 tensors on this device): every minibatch
+        of `epochs` passes, two kernels each on the environment's stream, no synchronisation.  order: None (sequential) or an int32
+        tensor [epochs, M] of sample indices.  The next vit_act acts with the new head.  Returns the minibatches' losses, a float32
+        tensor [epochs * ceil(M / batch)] on the device; grad: an optional float32 tensor for the last minibatch's gradient."""
+        M = self._vit_head_data(embedding, steer)
+        if order is not None and (not torch.is_tensor(order) or order.dtype != torch.int32 or not order.is_contiguous() or order.device != self.device
+                                  or order.numel() != int(epochs) * M):
+            raise ValueError("order must be a contiguous int32 tensor of shape (%d, %d) on %s" % (int(epochs), M, self.device))
+        loss = torch.empty(max(int(epochs), 0) * ((M + int(batch) - 1) // max(int(batch), 1)), dtype=torch.float32, device=self.device)
+        self.env.vit_head_update(embedding, steer, M, batch, epochs, order, {"loss": loss if loss.numel() else None, "grad": grad})
+        return loss
+
+    def vit_head_eval(self, embedding, steer, batch):
+        """The loss of every minibatch of one sequential pass with no update: a float32 tensor [ceil(M / batch)] on the device."""
+        M = self._vit_head_data(embedding, steer)
+        loss = torch.empty((M + int(batch) - 1) // max(int(batch), 1), dtype=torch.float32, device=self.device)
+        self.env.vit_head_eval(embedding, steer, M, batch, loss)
+        return loss
+
     # ---- Deep-Q image racers (include/okenv.h, DESIGN.md section 29) ---------------------------------------------------------------
     def enable_image_dqn(self, config, params, capacity=None, push_all=False):
         """Attaches the reference's image Q-network (RLRacers/DQN_CNN) as a device driver and, with `capacity`, its frame ring.
