@@ -4,9 +4,11 @@
 // device and the host entry agree bit for bit.
 //
 // These are NOT step kernels and add no step-kernel launch site.  Every convolution is an implicit GEMM on v_mfma_f32_16x16x4_f32
-// (okBevConv): rows are output pixels of a tile, columns output channels, k runs over (tap row, tap column, input channel) with the
-// channel innermost, A comes from an activation tile in LDS, B from the weights as okBevPackKernel laid them out at set_params, and
-// the accumulator starts from the bias -- the rule's chain, four terms an instruction.
+// (ok_conv.h's okConv, with the next group's operands prefetched): rows are output pixels of a tile, columns output channels, k runs
+// over (tap row, tap column, input channel) with the channel innermost, A comes from an activation tile in LDS, B from the weights as
+// okBevPackKernel laid them out at set_params, and the accumulator starts from the bias -- the rule's chain, four terms an
+// instruction.  The lane mapping, the packed-weight layout, the unit loop and the walk of layers 1 and 2 are ok_conv.h's; this
+// family's own are layer 0's planar loader (OkBevPlanarTaps) and the store of a tile that may reach past the image (OkBevTileStore).
 //   okBevFrontKernel<T>  one T x T tile of layer 1's output of one frame per workgroup of 4 waves: the frame's patch as floats in LDS
 //                        (planar), layer 0 on it into an LDS tile (channels last) with its halo recomputed, layer 1 from that tile to
 //                        global memory (channels last).  Layer 0's output never leaves the CU.
@@ -22,6 +24,7 @@
 
 #include "../../include/okenv.h"
 #include "../../include/okenv_bev.h"
+#include "ok_conv.h"
 #include "ok_lidar.h"
 
 constexpr int    kBevThreads   = 256; // 4 waves
@@ -114,10 +117,7 @@ inline size_t okBevLdsBytes(const ok_bev_shape s)
 
 // ---- the weights as the conv kernels read them ---------------------------------------------------------------------------------------
 
-// Layer l's B matrix [K][Cout], k = tap * Cin' + ch (tap = ty * k + tx; Cin' = Cin, layer 0: 4), in groups of 16 k's:
-// pack[((k / 16) * Cout + n) * 16 + (k % 4) * 4 + (k % 16) / 4] = weight[n][ch][ty][tx] -- the four floats a lane (column n, k-lane
-// g = k % 4) feeds to the four instructions of a group lie side by side, one 16-byte load, and a wave's 64 loads are 1 KB in a row.
-// Layer 0's alpha slot and filler taps are 0.0f.
+// ok_conv.h's layout; k = tap * Cin' + ch (tap = ty * k + tx; Cin' = Cin, layer 0: 4), layer 0's alpha slot and filler taps 0.0f
 struct OkBevPackParams
 {
     ok_bev_shape s;
@@ -134,10 +134,9 @@ __global__ __launch_bounds__(kBevThreads) void okBevPackKernel(const OkBevPackPa
         return;
     const int  l = e >= pl.pack[2] ? 2 : (e >= pl.pack[1] ? 1 : 0);
     const auto of = [l](const int *v) { return l == 2 ? v[2] : (l == 1 ? v[1] : v[0]); }; // (no array indexed by l: it would live in scratch)
-    const int  Cout = of(p.s.c), k = of(p.s.k), taps = k * k, idx = e - of(pl.pack);
-    const int grp = idx / (Cout * 16), rem = idx - grp * Cout * 16, n = rem >> 4, g = (rem & 15) >> 2, q = rem & 3;
-    const int kk = grp * 16 + 4 * q + g;
-    float     v  = 0.F;
+    const int  k = of(p.s.k), taps = k * k;
+    const auto [n, kk] = okConvPackAt(e - of(pl.pack), of(p.s.c));
+    float      v       = 0.F;
     if (l == 0)
     {
         const int tap = kk >> 2, ch = kk & 3;
@@ -145,175 +144,64 @@ __global__ __launch_bounds__(kBevThreads) void okBevPackKernel(const OkBevPackPa
             v = p.params[at.w[0] + (n * 3 + ch) * taps + tap];
     }
     else
-    {
-        const int Cin = l == 2 ? p.s.c[1] : p.s.c[0], tap = kk / Cin, ch = kk - tap * Cin;
-        v = p.params[of(at.w) + (n * Cin + ch) * taps + tap];
-    }
+        v = p.params[of(at.w) + okConvWeightAt(n, kk, l == 2 ? p.s.c[1] : p.s.c[0], taps)];
     p.pack[e] = v;
 }
 
-// ---- the convolution piece -------------------------------------------------------------------------------------------------------------
+// ---- the convolutions ------------------------------------------------------------------------------------------------------------------
 
-// One convolution of the workgroup's tile: M output pixels, W to a row, times Cout channels.  Input pixel (y, x) of the region the tile
-// needs lies in LDS at in + y * rs + x * ps, channel ch at + ch (kFirst: + ch * cs, planar); the output pixel (oy, ox) reads the input
-// pixels (2 oy + ty, 2 ox + tx).  Output pixel (oy, ox), image position (gy0 + oy, gx0 + ox) of `side`, goes to
-// out + oy * ors + ox * ops + channel, LDS or global; outside the image nothing is stored, or 0.0f (zero_outside: the next layer's
-// padding).
-struct OkBevConvJob
+// Layer 0's A operands for okConv: the patch is planar, three planes of rs x rs floats; a k-step is one tap, lane group g reads plane g
+// (3: the blue plane against the alpha slot's 0.0f); the filler taps read the last tap.
+struct OkBevPlanarTaps
 {
-    int          in, ps, rs, cs, k, Cin, W, M, Cout;
-    const float *w, *bias; // packed weights of the layer, its bias
-    float       *out;
-    long         ops, ors;
-    int          gy0, gx0, side;
-    bool         zero_outside;
+    int s = 0; // the group's first k-step
+
+    __device__ __forceinline__ OkBevPlanarTaps(const OkConvJob &, const int) {}
+
+    __device__ __forceinline__ static int groups(const OkConvJob &j)
+    {
+        return (j.k * j.k + 3) >> 2;
+    }
+
+    __device__ __forceinline__ static int lane(const OkConvJob &j, const int g)
+    {
+        return okLidarMin(g, 2) * j.rs * j.rs;
+    }
+
+    template <int RB>
+    __device__ __forceinline__ void load(const OkConvJob &j, const int (&abase)[RB], float (&a)[4][RB], const bool first = false)
+    {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+        {
+            const int tap = okLidarMin((first ? 0 : s) + q, j.k * j.k - 1), ty = j.k == 3 ? tap / 3 : tap / 5; // (divisions by constants: k is 3 or 5)
+            const int toff = ty * j.rs + (tap - ty * j.k) * j.ps;
+#pragma unroll
+            for (int m = 0; m < RB; ++m)
+                a[q][m] = ok_actor_lds[abase[m] + toff];
+        }
+        s += 4;
+    }
 };
 
-// A wave owns 16 columns and RB row tiles of 16 pixels at a time: RB independent accumulator chains.  Lane l holds A[row l & 15][k = l >> 4]
-// and B[k = l >> 4][col l & 15]; accumulator register r is D[row 4 (l >> 4) + r][col l & 15] (ok_lidar.h).  Rows past M repeat the last
-// pixel and are not stored.  kFirst: layer 0 -- a k-step is one tap, lane group 3 reads the blue plane against the alpha slot's 0.0f,
-// the filler taps read the last tap.
-template <int RB, bool kFirst>
-__device__ __forceinline__ void okBevConv(const OkBevConvJob &j)
+// The store of a tile: output pixel (oy, ox), image position (gy0 + oy, gx0 + ox) of `side`, goes to out + oy * ors + ox * ops + channel,
+// LDS or global; outside the image nothing is stored, or 0.0f (zero_outside: the next layer's padding)
+struct OkBevTileStore
 {
-    const int lane = static_cast<int>(threadIdx.x) & 63, i = lane & 15, g = lane >> 4, wave = static_cast<int>(threadIdx.x) >> 6;
-    const int Nt = j.Cout >> 4, Mb = (j.M + 16 * RB - 1) / (16 * RB), units = Nt * Mb;
-    for (int u = wave; u < units; u += kBevWaves)
+    float *out;
+    long   ops, ors;
+    int    gy0, gx0, side;
+    bool   zero_outside;
+
+    __device__ __forceinline__ void put(const int oy, const int ox, const int n0, const int i, const float v) const
     {
-        const int  mb = u / Nt, n0 = (u - mb * Nt) << 4;
-        int        abase[RB];
-        okLidarAcc acc[RB];
-#pragma unroll
-        for (int m = 0; m < RB; ++m)
-        {
-            const int row = okLidarMin((mb * RB + m) * 16 + i, j.M - 1), oy = row / j.W, ox = row - oy * j.W;
-            abase[m]      = j.in + 2 * oy * j.rs + 2 * ox * j.ps + (kFirst ? okLidarMin(g, 2) * j.cs : g);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                acc[m][r] = j.bias[n0 + i];
-        }
-        const float4 *wp = reinterpret_cast<const float4 *>(j.w) + (n0 + i) * 4 + g;
-        const int     gstride = j.Cout * 4; // float4's between groups
-        if constexpr (kFirst)
-        {
-            const int taps = j.k * j.k, groups = (taps + 3) >> 2;
-            const auto tapoff = [&j, taps](const int s) // (divisions by constants: k is 3 or 5)
-            {
-                const int tap = okLidarMin(s, taps - 1), ty = j.k == 3 ? tap / 3 : tap / 5;
-                return ty * j.rs + (tap - ty * j.k) * j.ps;
-            };
-            // as below: the next group's operands are loaded before this group's instructions are issued
-            float  a[4][RB];
-            float4 bv = wp[0];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-            {
-                const int toff = tapoff(q);
-#pragma unroll
-                for (int m = 0; m < RB; ++m)
-                    a[q][m] = ok_actor_lds[abase[m] + toff];
-            }
-            for (int grp = 0; grp < groups; ++grp)
-            {
-                const int    next = grp + 1 < groups ? grp + 1 : grp; // (the last group loads itself again: every load goes out)
-                const float4 bn   = wp[next * gstride];
-                float        an[4][RB];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-                    const int toff = tapoff(4 * next + q);
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        an[q][m] = ok_actor_lds[abase[m] + toff];
-                }
-                const float b[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q][m], b[q], acc[m], 0, 0, 0);
-                }
-                bv = bn;
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        a[q][m] = an[q][m];
-                }
-            }
-        }
-        else
-        {
-            // group grp = (tap (ty, tx), channels c0 .. c0 + 15); the next group's operands are loaded before this group's
-            // instructions are issued, so that the LDS's latency passes behind them (two waves a SIMD do not hide it)
-            const int groups = j.k * j.k * (j.Cin >> 4);
-            int       ty = 0, tx = 0, c0 = 0;
-            float     a[4][RB];
-            float4    bv = wp[0];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-            {
-#pragma unroll
-                for (int m = 0; m < RB; ++m)
-                    a[q][m] = ok_actor_lds[abase[m] + 4 * q];
-            }
-            for (int grp = 0; grp < groups; ++grp)
-            {
-                c0 += 16;
-                if (c0 == j.Cin)
-                {
-                    c0 = 0;
-                    if (++tx == j.k)
-                        tx = 0, ++ty;
-                }
-                const int  next = grp + 1 < groups ? grp + 1 : grp; // (the last group loads itself again: every load goes out)
-                const int  noff = grp + 1 < groups ? ty * j.rs + tx * j.ps + c0 : 0;
-                const float4 bn = wp[next * gstride];
-                float      an[4][RB];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        an[q][m] = ok_actor_lds[abase[m] + noff + 4 * q];
-                }
-                const float b[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q][m], b[q], acc[m], 0, 0, 0);
-                }
-                bv = bn;
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-#pragma unroll
-                    for (int m = 0; m < RB; ++m)
-                        a[q][m] = an[q][m];
-                }
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < RB; ++m)
-        {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-            {
-                const int row = (mb * RB + m) * 16 + 4 * g + r;
-                if (row >= j.M)
-                    continue;
-                const int  oy = row / j.W, ox = row - oy * j.W, gy = j.gy0 + oy, gx = j.gx0 + ox;
-                const bool inside = gy >= 0 && gy < j.side && gx >= 0 && gx < j.side;
-                if (inside || j.zero_outside)
-                    j.out[oy * j.ors + ox * j.ops + n0 + i] = inside ? ok_lidar_relu(acc[m][r]) : 0.F;
-            }
-        }
+        const int  gy = gy0 + oy, gx = gx0 + ox; // (0 <= gy < side as one unsigned compare, and no branch between the two: the stores of a
+                                                 // row tile stay under one mask)
+        const bool inside = (static_cast<unsigned>(gy) < static_cast<unsigned>(side)) & (static_cast<unsigned>(gx) < static_cast<unsigned>(side));
+        if (inside || zero_outside)
+            out[oy * ors + ox * ops + n0 + i] = inside ? v : 0.F;
     }
-}
+};
 
 struct OkBevEncodeParams
 {
@@ -349,20 +237,21 @@ __global__ __launch_bounds__(kBevThreads) void okBevFrontKernel(const OkBevEncod
     }
     __syncthreads();
 
-    OkBevConvJob j;
-    j.in = 0, j.ps = 1, j.rs = pl.p0, j.cs = pl.plane0, j.k = sh.k[0], j.Cin = 4, j.W = pl.p1, j.M = pl.p1 * pl.p1, j.Cout = sh.c[0];
+    OkConvJob      j;
+    OkBevTileStore to;
+    j.in = 0, j.ps = 1, j.rs = pl.p0, j.k = sh.k[0], j.stride = 2, j.Cin = 4, j.W = pl.p1, j.M = pl.p1 * pl.p1, j.Cout = sh.c[0];
     j.w = p.pack + pl.pack[0], j.bias = p.params + at.b[0];
-    j.out = ok_actor_lds + pl.tile1, j.ops = pl.ldc1, j.ors = pl.ldr1;
-    j.gy0 = y0, j.gx0 = x0, j.side = side0, j.zero_outside = true;
-    okBevConv<4, true>(j);
+    to.out = ok_actor_lds + pl.tile1, to.ops = pl.ldc1, to.ors = pl.ldr1;
+    to.gy0 = y0, to.gx0 = x0, to.side = side0, to.zero_outside = true;
+    okConv<OkBevPlanarTaps, 4, kBevWaves, true>(j, to);
     __syncthreads();
 
-    j.in = pl.tile1, j.ps = pl.ldc1, j.rs = pl.ldr1, j.cs = 0, j.k = sh.k[1], j.Cin = sh.c[0], j.W = T, j.M = T * T, j.Cout = sh.c[1];
+    j.in = pl.tile1, j.ps = pl.ldc1, j.rs = pl.ldr1, j.k = sh.k[1], j.Cin = sh.c[0], j.W = T, j.M = T * T, j.Cout = sh.c[1];
     j.w = p.pack + pl.pack[1], j.bias = p.params + at.b[1];
-    j.ops = sh.c[1], j.ors = static_cast<long>(side1) * sh.c[1];
-    j.out = p.act1 + (static_cast<size_t>(n) * side1 * side1 + static_cast<size_t>(y1) * side1 + x1) * sh.c[1];
-    j.gy0 = y1, j.gx0 = x1, j.side = side1, j.zero_outside = false;
-    okBevConv<T * T / 16, false>(j);
+    to.ops = sh.c[1], to.ors = static_cast<long>(side1) * sh.c[1];
+    to.out = p.act1 + (static_cast<size_t>(n) * side1 * side1 + static_cast<size_t>(y1) * side1 + x1) * sh.c[1];
+    to.gy0 = y1, to.gx0 = x1, to.side = side1, to.zero_outside = false;
+    okConv<OkConvWalk, T * T / 16, kBevWaves, true>(j, to);
 }
 
 template <int T>
@@ -388,13 +277,14 @@ __global__ __launch_bounds__(kBevThreads) void okBevBackKernel(const OkBevEncode
     }
     __syncthreads();
 
-    OkBevConvJob j;
-    j.in = 0, j.ps = pl.ldc2, j.rs = pl.ldr2, j.cs = 0, j.k = sh.k[2], j.Cin = c1, j.W = T, j.M = T * T, j.Cout = sh.c[2];
+    OkConvJob      j;
+    OkBevTileStore to;
+    j.in = 0, j.ps = pl.ldc2, j.rs = pl.ldr2, j.k = sh.k[2], j.stride = 2, j.Cin = c1, j.W = T, j.M = T * T, j.Cout = sh.c[2];
     j.w = p.pack + pl.pack[2], j.bias = p.params + at.b[2];
-    j.ops = sh.c[2], j.ors = static_cast<long>(side2) * sh.c[2];
-    j.out = p.act2 + (static_cast<size_t>(n) * side2 * side2 + static_cast<size_t>(y2) * side2 + x2) * sh.c[2];
-    j.gy0 = y2, j.gx0 = x2, j.side = side2, j.zero_outside = false;
-    okBevConv<T * T / 16, false>(j);
+    to.ops = sh.c[2], to.ors = static_cast<long>(side2) * sh.c[2];
+    to.out = p.act2 + (static_cast<size_t>(n) * side2 * side2 + static_cast<size_t>(y2) * side2 + x2) * sh.c[2];
+    to.gy0 = y2, to.gx0 = x2, to.side = side2, to.zero_outside = false;
+    okConv<OkConvWalk, T * T / 16, kBevWaves, true>(j, to);
 }
 
 constexpr int kBevPoolBatch = 8; // loads a thread issues before it adds the first of them

@@ -4,7 +4,7 @@
 // okCnnActHost below, so the device and the host entry agree bit for bit.
 //
 // These are NOT step kernels and add no step-kernel launch site.  The lane mapping, the packed-weight layout, the unit loop of a
-// convolution, the walk of layers 1 and 2 and the hidden layer's GEMM are ok_conv.h's, shared with ok_qcnn.h; what is this family's own:
+// convolution, the walk of layers 1 and 2 and the hidden layer's GEMM are ok_conv.h's; what is this family's own:
 //   okCnnPackKernel     at set_params: the four weight matrices in groups of 16 k's (layer 0: 4 k's a tap, R, G, B and an alpha slot)
 //   OkCnnRgbaTaps       layer 0's A operands: a frame's bytes through the table of ok_bev_pixel
 //   okCnnConvKernel     one frame per workgroup of 8 waves.  The frame's bytes, layer 0's output and layer 1's output live in LDS
@@ -115,15 +115,17 @@ struct OkCnnRgbaTaps
         return (j.k * j.k + 3) >> 2;
     }
 
-    __device__ __forceinline__ static int lane(const int)
+    __device__ __forceinline__ static int lane(const OkConvJob &, const int)
     {
         return 0;
     }
 
     template <int RB>
-    __device__ __forceinline__ void load(const OkConvJob &j, const int (&abase)[RB], float (&a)[4][RB])
+    __device__ __forceinline__ void load(const OkConvJob &j, const int (&abase)[RB], float (&a)[4][RB], const bool first = false)
     {
         const uint32_t *words = reinterpret_cast<const uint32_t *>(ok_actor_lds);
+        if (first)
+            ty = 0, tx = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
         {
@@ -166,25 +168,26 @@ __global__ __launch_bounds__(kConvThreads) void okCnnConvKernel(const OkCnnActPa
         words[e] = frame[e];
     __syncthreads();
 
-    OkConvJob j;
+    OkConvJob      j;
+    OkConvBordered to;
     j.in = pl.p, j.ps = 1, j.rs = S, j.k = sh.k[0], j.stride = sh.s[0], j.Cin = 4, j.W = pl.side[0], j.M = pl.side[0] * pl.side[0], j.Cout = sh.c[0];
     j.w = p.pack + pl.pack[0], j.bias = p.params + at.b[0];
-    j.out = ok_actor_lds + pl.q, j.ldo = pl.ld0, j.opad = 0, j.orow = j.W; // (no layer pads: no border anywhere)
-    okConv<OkCnnRgbaTaps>(j);
+    to.out = ok_actor_lds + pl.q, to.ldo = pl.ld0, to.opad = 0, to.orow = j.W; // (no layer pads: no border anywhere)
+    okConv<OkCnnRgbaTaps, kConvRowBlock, kConvWaves, false>(j, to);
     __syncthreads();
 
     j.in = pl.q, j.ps = pl.ld0, j.rs = pl.side[0] * pl.ld0, j.k = sh.k[1], j.stride = sh.s[1], j.Cin = sh.c[0], j.W = pl.side[1];
     j.M = pl.side[1] * pl.side[1], j.Cout = sh.c[1];
     j.w = p.pack + pl.pack[1], j.bias = p.params + at.b[1];
-    j.out = ok_actor_lds + pl.p, j.ldo = pl.ld1, j.orow = j.W;
-    okConv<OkConvWalk>(j);
+    to.out = ok_actor_lds + pl.p, to.ldo = pl.ld1, to.orow = j.W;
+    okConv<OkConvWalk, kConvRowBlock, kConvWaves, false>(j, to);
     __syncthreads();
 
     j.in = pl.p, j.ps = pl.ld1, j.rs = pl.side[1] * pl.ld1, j.k = sh.k[2], j.stride = sh.s[2], j.Cin = sh.c[1], j.W = pl.side[2];
     j.M = pl.side[2] * pl.side[2], j.Cout = sh.c[2];
     j.w = p.pack + pl.pack[2], j.bias = p.params + at.b[2];
-    j.out = p.feat + n * static_cast<size_t>(j.M * sh.c[2]), j.ldo = sh.c[2], j.orow = j.W;
-    okConv<OkConvWalk>(j);
+    to.out = p.feat + n * static_cast<size_t>(j.M * sh.c[2]), to.ldo = sh.c[2], to.orow = j.W;
+    okConv<OkConvWalk, kConvRowBlock, kConvWaves, false>(j, to);
 }
 
 template <int CT>

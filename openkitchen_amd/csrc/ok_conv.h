@@ -1,11 +1,14 @@
-// ok_conv.h -- what the image policy (ok_cnn.h) and the image Q-network (ok_qcnn.h, section 29) share on the device:
-// three convolutions of one frame in LDS and a hidden layer over 16 agents, all of it on v_mfma_f32_16x16x4_f32 with the accumulator
-// started from the bias, so that every chain is the rule's.  Rows are output pixels (the convolutions) or agents (the hidden layer),
-// columns output channels, k runs over the rule's chain, four terms an instruction; B comes from the packed weights.
-//   okConvPack     the packed-weight layout, a family supplying layer 0's value
-//   okConvMfma     the 4 x RB instructions of one group of 16 k's
-//   okConv<Taps>   one convolution of a whole image; Taps fetches a group's A operands: OkConvWalk for layers 1 and 2, a family's own
-//                  loader for layer 0
+// ok_conv.h -- what the image encoders share on the device: the flow driver's (ok_bev.h), the image policy
+// (ok_cnn.h, section 26), the image Q-network (ok_qcnn.h, section 29) and the world model's encoder and memory (ok_world.h, ok_memory.h,
+// sections 27 and 28).  All of it runs on v_mfma_f32_16x16x4_f32 with the accumulator started from the bias, so that every chain is
+// the rule's.  Rows are output pixels (the convolutions) or agents (the hidden layer), columns output channels, k runs over the rule's
+// chain, four terms an instruction; B comes from the packed weights.
+//   okConvPackAt, okConvWeightAt  the packed-weight layout: from an element of a pack to its column and place in the chain, and from
+//                  there into a conv weight
+//   okConvPack     a four-layer pack (three convolutions and a hidden layer), a family supplying layer 0's value
+//   okConvMfma     the 4 x RB instructions of one group of 16 k's: the only place that names the instruction
+//   okConv<Taps, RB, Waves, Prefetch>  one convolution of an image in LDS; Taps fetches a group's A operands: OkConvWalk for layers 1
+//                  and 2, a family's own loader for layer 0; the caller's store says where an output pixel goes
 //   okConvFc1      the hidden layer as a GEMM whose rows are agents, into LDS
 // Nothing here knows which family calls it.
 #ifndef OK_CONV_H
@@ -49,12 +52,32 @@ __host__ __device__ inline void okConvHeadPlaces(OkConvHeadPlaces &at, const int
 
 // ---- the weights as the kernels read them ----------------------------------------------------------------------------------------------
 
-// A layer's B matrix [K][Cout] in groups of 16 k's, k the place in the rule's chain: layer 0's as its family says, layers 1 and 2's
-// k = tap * Cin + ch (tap = ty * k + tx), the hidden layer's k = (y * side_2 + x) * c2 + ch:
+// A layer's B matrix [K][Cout] in groups of 16 k's, k the place in the rule's chain:
 // pack[((k / 16) * Cout + n) * 16 + (k % 4) * 4 + (k % 16) / 4] -- the four floats a lane (column n, k-lane g = k % 4) feeds to the four
-// instructions of a group lie side by side, one 16-byte load, and a wave's 64 loads are 1 KB in a row.
-// Element blockIdx.x * 256 + threadIdx.x of the pack; layer0(n, k) is layer 0's B[k][n].  Shape, Layout and Places are a family's
-// ok_*_shape, ok_*_layout and Ok*Places.
+// instructions of a group lie side by side, one 16-byte load, and a wave's 64 loads are 1 KB in a row.  Every pack kernel walks its
+// pack's elements and asks these two where an element comes from.
+struct OkConvPackAt
+{
+    int n, kk; // column, place in the chain
+};
+
+// Element idx of a layer's pack of Cout columns
+__host__ __device__ inline OkConvPackAt okConvPackAt(const int idx, const int Cout)
+{
+    const int grp = idx / (Cout * 16), rem = idx - grp * Cout * 16, g = (rem & 15) >> 2, q = rem & 3;
+    return {rem >> 4, grp * 16 + 4 * q + g};
+}
+
+// Where a conv weight [n][Cin][taps] holds column n's k = tap * Cin + ch (tap = ty * k + tx)
+__host__ __device__ inline int okConvWeightAt(const int n, const int kk, const int Cin, const int taps)
+{
+    const int tap = kk / Cin, ch = kk - tap * Cin;
+    return (n * Cin + ch) * taps + tap;
+}
+
+// Three convolutions and a hidden layer: layer 0's k as its family says, layers 1 and 2's as okConvWeightAt's, the hidden layer's
+// k = (y * side_2 + x) * c2 + ch.  Element blockIdx.x * 256 + threadIdx.x of the pack; layer0(n, k) is layer 0's B[k][n].  Shape, Layout
+// and Places are a family's ok_*_shape, ok_*_layout and Ok*Places.
 template <class Shape, class Layout, class Places, class Layer0>
 __device__ __forceinline__ void okConvPack(const Shape &s, const Layout &at, const Places &pl, const float *params, float *pack, const Layer0 layer0)
 {
@@ -64,9 +87,8 @@ __device__ __forceinline__ void okConvPack(const Shape &s, const Layout &at, con
     const int l    = e >= pl.pack[3] ? 3 : (e >= pl.pack[2] ? 2 : (e >= pl.pack[1] ? 1 : 0));
     const int base = l == 3 ? pl.pack[3] : (l == 2 ? pl.pack[2] : (l == 1 ? pl.pack[1] : 0)); // (no array indexed by l: it would live in scratch)
     const int Cout = l == 3 ? s.H : (l == 2 ? s.c[2] : (l == 1 ? s.c[1] : s.c[0]));
-    const int idx = e - base, grp = idx / (Cout * 16), rem = idx - grp * Cout * 16, n = rem >> 4, g = (rem & 15) >> 2, q = rem & 3;
-    const int kk = grp * 16 + 4 * q + g;
-    float     v;
+    const auto [n, kk] = okConvPackAt(e - base, Cout);
+    float      v;
     if (l == 0)
         v = layer0(n, kk);
     else if (l == 3)
@@ -76,8 +98,8 @@ __device__ __forceinline__ void okConvPack(const Shape &s, const Layout &at, con
     }
     else
     {
-        const int Cin = l == 2 ? s.c[1] : s.c[0], k = l == 2 ? s.k[2] : s.k[1], tap = kk / Cin, ch = kk - tap * Cin;
-        v = params[(l == 2 ? at.w[2] : at.w[1]) + (n * Cin + ch) * k * k + tap];
+        const int k = l == 2 ? s.k[2] : s.k[1];
+        v = params[(l == 2 ? at.w[2] : at.w[1]) + okConvWeightAt(n, kk, l == 2 ? s.c[1] : s.c[0], k * k)];
     }
     pack[e] = v;
 }
@@ -98,17 +120,36 @@ __device__ __forceinline__ void okConvMfma(const float (&a)[4][RB], const float4
     }
 }
 
-// One convolution of a whole image: M output pixels, W to a row, times Cout channels.  Input pixel (y, x) lies in LDS at
-// in + y * rs + x * ps, its channel ch at + ch (a border the rule pads with is part of the image: +0.0f in LDS); the output pixel
-// (oy, ox) reads the input pixels (stride oy + ty, stride ox + tx), all of them inside the input.  The output pixel (oy, ox) goes to
-// out + ((oy + opad) * orow + ox + opad) * ldo + channel: LDS, inside a border of opad pixels in rows of orow, or global (opad = 0,
-// orow = W).
+// ... on one row tile
+__device__ __forceinline__ void okConvMfma(const float (&a)[4], const float4 bv, okLidarAcc &acc)
+{
+    const float b[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], b[q], acc, 0, 0, 0);
+}
+
+// One convolution of an image in LDS: M output pixels, W to a row, times Cout channels.  Input pixel (y, x) lies at
+// in + y * rs + x * ps, its channel ch at + ch unless the Taps say otherwise (a border the rule pads with is part of the image: +0.0f
+// in LDS); the output pixel (oy, ox) reads the input pixels (stride oy + ty, stride ox + tx), all of them inside the input.  Where an
+// output pixel goes, the caller's store says.
 struct OkConvJob
 {
     int          in, ps, rs, k, stride, Cin, W, M, Cout;
     const float *w, *bias; // packed weights of the layer, its bias
-    float       *out;
-    int          ldo, opad, orow;
+};
+
+// The store of a whole image: pixel (oy, ox) goes to out + ((oy + opad) * orow + ox + opad) * ldo + channel n0 + i -- LDS, inside a
+// border of opad pixels in rows of orow, or global (opad = 0, orow = W)
+struct OkConvBordered
+{
+    float *out;
+    int    ldo, opad, orow;
+
+    __device__ __forceinline__ void put(const int oy, const int ox, const int n0, const int i, const float v) const
+    {
+        out[static_cast<long>((oy + opad) * orow + ox + opad) * ldo + n0 + i] = v;
+    }
 };
 
 // Layers 1 and 2's A operands: group grp = (tap (ty, tx), channels c0 .. c0 + 15), lane group g reads channel c0 + 4 q + g
@@ -123,15 +164,15 @@ struct OkConvWalk
         return j.k * j.k * (j.Cin >> 4);
     }
 
-    __device__ __forceinline__ static int lane(const int g)
+    __device__ __forceinline__ static int lane(const OkConvJob &, const int g)
     {
         return g;
     }
 
     template <int RB>
-    __device__ __forceinline__ void load(const OkConvJob &j, const int (&abase)[RB], float (&a)[4][RB])
+    __device__ __forceinline__ void load(const OkConvJob &j, const int (&abase)[RB], float (&a)[4][RB], const bool first = false)
     {
-        const int off = ty * j.rs + tx * j.ps + c0;
+        const int off = first ? 0 : ty * j.rs + tx * j.ps + c0;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
         {
@@ -149,18 +190,24 @@ struct OkConvWalk
     }
 };
 
-// A wave owns 16 columns and kConvRowBlock row tiles of 16 pixels at a time.  Lane l holds A[row l & 15][k = l >> 4] and
-// B[k = l >> 4][col l & 15]; accumulator register r is D[row 4 (l >> 4) + r][col l & 15] (ok_lidar.h).  Rows past M repeat the last
-// pixel and are not stored.  Taps(j, g) starts a unit's chain for lane group g; groups(j) is the chain's length in groups of 16 k's;
-// lane(g) is where lane group g's first k lies behind a window's first pixel (kept in abase, out of the walk); load(j, abase, a) fills
-// a[q][m], the lane's A operand of the group's instruction q on row tile m, from the window at abase[m], and moves on to the next group.
-template <class Taps>
-__device__ __forceinline__ void okConv(const OkConvJob &j)
+// A workgroup of Waves waves; a wave owns 16 columns and RB row tiles of 16 pixels at a time: RB independent accumulator chains.
+// Lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; accumulator register r is D[row 4 (l >> 4) + r][col l & 15]
+// (ok_lidar.h).  Rows past M repeat the last pixel and are not stored.  Taps(j, g) starts a unit's chain for lane group g; groups(j) is
+// the chain's length in groups of 16 k's; lane(j, g) is where lane group g's first k lies behind a window's first pixel (kept in abase,
+// out of the walk); load(j, abase, a) fills a[q][m], the lane's A operand of the group's instruction q on row tile m, from the window
+// at abase[m], and moves on to the next group; load(j, abase, a, true) fetches the unit's first group instead, wherever the walk stands,
+// and is the unit's last load.  to.put(oy, ox, n0, i, v) stores channel n0 + i of an output pixel (apart: n0 is the wave's, i the
+// lane's, and a store adds them in that order to the pixel's place).
+// Prefetch: the next group's operands are loaded before this group's instructions are issued, so that the LDS's latency passes behind
+// them where the waves of a SIMD are too few to hide it; the last group loads the first one again, so that every load goes out -- as
+// an offset of 0 chosen in place of the walk's, which the compiler makes a branch that keeps the loads in front of the instructions
+// (resetting the walk instead cost the flow encoder 3 %, docs/HISTORY.md section 46).
+template <class Taps, int RB, int Waves, bool Prefetch, class Store>
+__device__ __forceinline__ void okConv(const OkConvJob &j, const Store &to)
 {
-    constexpr int RB = kConvRowBlock;
     const int lane = static_cast<int>(threadIdx.x) & 63, i = lane & 15, g = lane >> 4, wave = static_cast<int>(threadIdx.x) >> 6;
     const int Nt = j.Cout >> 4, Mb = (j.M + 16 * RB - 1) / (16 * RB), units = Nt * Mb, groups = Taps::groups(j);
-    for (int u = wave; u < units; u += kConvWaves)
+    for (int u = wave; u < units; u += Waves)
     {
         const int  mb = u / Nt, n0 = (u - mb * Nt) << 4;
         int        abase[RB];
@@ -169,7 +216,7 @@ __device__ __forceinline__ void okConv(const OkConvJob &j)
         for (int m = 0; m < RB; ++m)
         {
             const int row = okLidarMin((mb * RB + m) * 16 + i, j.M - 1), oy = row / j.W, ox = row - oy * j.W;
-            abase[m]      = j.in + j.stride * oy * j.rs + j.stride * ox * j.ps + Taps::lane(g);
+            abase[m]      = j.in + j.stride * oy * j.rs + j.stride * ox * j.ps + Taps::lane(j, g);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 acc[m][r] = j.bias[n0 + i];
@@ -177,12 +224,37 @@ __device__ __forceinline__ void okConv(const OkConvJob &j)
         const float4 *wp = reinterpret_cast<const float4 *>(j.w) + (n0 + i) * 4 + g;
         const int     gstride = j.Cout * 4; // float4's between groups
         Taps          taps(j, g);
-        for (int grp = 0; grp < groups; ++grp)
+        if constexpr (Prefetch)
         {
-            const float4 bv = wp[grp * gstride];
-            float        a[4][RB];
+            float  a[4][RB];
+            float4 bv = wp[0];
             taps.load(j, abase, a);
-            okConvMfma(a, bv, acc);
+            for (int grp = 0; grp < groups; ++grp)
+            {
+                const int    next = grp + 1 < groups ? grp + 1 : 0;
+                const float4 bn   = wp[next * gstride];
+                float        an[4][RB];
+                taps.load(j, abase, an, next == 0);
+                okConvMfma(a, bv, acc);
+                bv = bn;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                {
+#pragma unroll
+                    for (int m = 0; m < RB; ++m)
+                        a[q][m] = an[q][m];
+                }
+            }
+        }
+        else
+        {
+            for (int grp = 0; grp < groups; ++grp)
+            {
+                const float4 bv = wp[grp * gstride];
+                float        a[4][RB];
+                taps.load(j, abase, a);
+                okConvMfma(a, bv, acc);
+            }
         }
 #pragma unroll
         for (int m = 0; m < RB; ++m)
@@ -194,7 +266,7 @@ __device__ __forceinline__ void okConv(const OkConvJob &j)
                 if (row < j.M)
                 {
                     const int oy = row / j.W, ox = row - oy * j.W;
-                    j.out[static_cast<long>((oy + j.opad) * j.orow + ox + j.opad) * j.ldo + n0 + i] = ok_lidar_relu(acc[m][r]);
+                    to.put(oy, ox, n0, i, ok_lidar_relu(acc[m][r]));
                 }
             }
         }

@@ -126,8 +126,7 @@ inline void okMemoryPlan(const ok_memory_shape s, int32_t *plan)
 
 // ---- the weights as the layer kernel reads them ------------------------------------------------------------------------------------------
 
-// One matrix [cols][stride], of which the first K columns are packed: B [K][cols] in groups of 16 k's,
-// pack[((k / 16) * cols + n) * 16 + (k % 4) * 4 + (k % 16) / 4]  (ok_bev.h's 16-k layout)
+// One matrix [cols][stride], of which the first K columns are packed: B [K][cols] in ok_conv.h's layout
 struct OkMemoryPackJob
 {
     const float *src;
@@ -140,8 +139,8 @@ __global__ __launch_bounds__(256) void okMemoryPackKernel(const OkMemoryPackJob 
     const int e = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
     if (e >= j.cols * j.K)
         return;
-    const int grp = e / (j.cols * 16), rem = e - grp * j.cols * 16, n = rem >> 4, g = (rem & 15) >> 2, q = rem & 3;
-    j.dst[e] = j.src[n * j.stride + grp * 16 + 4 * q + g];
+    const auto [n, kk] = okConvPackAt(e, j.cols);
+    j.dst[e]           = j.src[n * j.stride + kk];
 }
 
 // ---- the state --------------------------------------------------------------------------------------------------------------------------
@@ -264,13 +263,7 @@ __device__ __forceinline__ void okMemoryPass(const OkMemoryLayerJob &j, const in
                 {
 #pragma unroll
                     for (int gate = 0; gate < 3; ++gate)
-                    {
-                        const float4 bv    = W[((grp * 3 + gate) * kMemCols + 16 * t + i) * 4 + g];
-                        const float  bq[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            part[t][gate] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], bq[q], part[t][gate], 0, 0, 0);
-                    }
+                        okConvMfma(a, W[((grp * 3 + gate) * kMemCols + 16 * t + i) * 4 + g], part[t][gate]);
                 }
             }
         }

@@ -5,7 +5,7 @@
 // entries below, so the device and the host agree bit for bit.
 //
 // These are NOT step kernels and add no step-kernel launch site.  The lane mapping, the packed-weight layout, the unit loop of a
-// convolution, the walk of layers 1 and 2 and fc1's GEMM are ok_conv.h's, shared with ok_cnn.h; what is this family's own:
+// convolution, the walk of layers 1 and 2 and fc1's GEMM are ok_conv.h's; what is this family's own:
 //   okQcnnPackKernel      at set_params: the four weight matrices in groups of 16 k's (layer 0: 16 taps a group, filler taps 0.0f)
 //   OkQcnnGreyTaps        layer 0's A operands: the grey plane, one float a tap
 //   okQcnnConvKernel      one frame per workgroup of 8 waves, every layer in LDS, channels last.  The grey plane and the outputs of
@@ -125,24 +125,26 @@ __global__ __launch_bounds__(256) void okQcnnPackKernel(const OkQcnnPackParams p
 // read the last tap against their 0.0f weight.
 struct OkQcnnGreyTaps
 {
-    const int last;
+    const int g, last;
     int       ty, tx; // this lane group's tap, four further every k-step
 
-    __device__ __forceinline__ OkQcnnGreyTaps(const OkConvJob &j, const int g) : last((j.k - 1) * (j.rs + j.ps)), ty(g / j.k), tx(g - ty * j.k) {}
+    __device__ __forceinline__ OkQcnnGreyTaps(const OkConvJob &j, const int g_) : g(g_), last((j.k - 1) * (j.rs + j.ps)), ty(g / j.k), tx(g - ty * j.k) {}
 
     __device__ __forceinline__ static int groups(const OkConvJob &j)
     {
         return (j.k * j.k + 15) >> 4;
     }
 
-    __device__ __forceinline__ static int lane(const int)
+    __device__ __forceinline__ static int lane(const OkConvJob &, const int)
     {
         return 0;
     }
 
     template <int RB>
-    __device__ __forceinline__ void load(const OkConvJob &j, const int (&abase)[RB], float (&a)[4][RB])
+    __device__ __forceinline__ void load(const OkConvJob &j, const int (&abase)[RB], float (&a)[4][RB], const bool first = false)
     {
+        if (first)
+            ty = g / j.k, tx = g - ty * j.k;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
         {
@@ -196,11 +198,12 @@ __global__ __launch_bounds__(kConvThreads) void okQcnnConvKernel(const OkQcnnAct
             ok_actor_lds[pl.q + e] = 0.F;
     __syncthreads();
 
-    OkConvJob j;
+    OkConvJob      j;
+    OkConvBordered to;
     j.in = pl.p, j.ps = 1, j.rs = pl.pin, j.k = sh.k[0], j.stride = sh.s[0], j.Cin = 1, j.W = pl.side[0], j.M = pl.side[0] * pl.side[0], j.Cout = sh.c[0];
     j.w = p.pack + pl.pack[0], j.bias = p.params + at.b[0];
-    j.out = ok_actor_lds + pl.q, j.ldo = pl.ld0, j.opad = sh.p[1], j.orow = pl.pad0;
-    okConv<OkQcnnGreyTaps>(j);
+    to.out = ok_actor_lds + pl.q, to.ldo = pl.ld0, to.opad = sh.p[1], to.orow = pl.pad0;
+    okConv<OkQcnnGreyTaps, kConvRowBlock, kConvWaves, false>(j, to);
     __syncthreads();
 
     // (the grey plane is done with: +0.0f all over layer 1's place)
@@ -213,15 +216,15 @@ __global__ __launch_bounds__(kConvThreads) void okQcnnConvKernel(const OkQcnnAct
     j.in = pl.q, j.ps = pl.ld0, j.rs = pl.pad0 * pl.ld0, j.k = sh.k[1], j.stride = sh.s[1], j.Cin = sh.c[0], j.W = pl.side[1];
     j.M = pl.side[1] * pl.side[1], j.Cout = sh.c[1];
     j.w = p.pack + pl.pack[1], j.bias = p.params + at.b[1];
-    j.out = ok_actor_lds + pl.p, j.ldo = pl.ld1, j.opad = sh.p[2], j.orow = pl.pad1;
-    okConv<OkConvWalk>(j);
+    to.out = ok_actor_lds + pl.p, to.ldo = pl.ld1, to.opad = sh.p[2], to.orow = pl.pad1;
+    okConv<OkConvWalk, kConvRowBlock, kConvWaves, false>(j, to);
     __syncthreads();
 
     j.in = pl.p, j.ps = pl.ld1, j.rs = pl.pad1 * pl.ld1, j.k = sh.k[2], j.stride = sh.s[2], j.Cin = sh.c[1], j.W = pl.side[2];
     j.M = pl.side[2] * pl.side[2], j.Cout = sh.c[2];
     j.w = p.pack + pl.pack[2], j.bias = p.params + at.b[2];
-    j.out = p.feat + n * static_cast<size_t>(j.M * sh.c[2]), j.ldo = sh.c[2], j.opad = 0, j.orow = j.W;
-    okConv<OkConvWalk>(j);
+    to.out = p.feat + n * static_cast<size_t>(j.M * sh.c[2]), to.ldo = sh.c[2], to.opad = 0, to.orow = j.W;
+    okConv<OkConvWalk, kConvRowBlock, kConvWaves, false>(j, to);
 }
 
 // CT: tiles of 16 hidden units a wave owns; RT: row tiles of 16 agents a workgroup carries (fc1.weight is read once per workgroup): 1 in

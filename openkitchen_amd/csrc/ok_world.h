@@ -5,7 +5,7 @@
 //
 // These are NOT step kernels and add no step-kernel launch site.  All matrix work runs on v_mfma_f32_16x16x4_f32 with the accumulator
 // started from the bias (the latent's partial chains: from +0.0f), k in the rule's order, four terms an instruction; B comes from the
-// weights as okWorldPackKernel laid them out at set_params (ok_bev.h's 16-k layout).
+// weights as okWorldPackKernel laid them out at set_params (ok_conv.h's layout and group step).
 //   okWorldListKernel       the agents an act works for, in ascending order, and their number: all of them, or (skip_crashed) those not
 //                           crashed.  Everything behind it works on list slots, so a crashed agent costs nothing.
 //   okWorldConvKernel<F>    one convolution as an implicit GEMM whose rows are the output pixels of ALL listed frames, one after the other
@@ -26,6 +26,7 @@
 
 #include "../../include/okenv.h"
 #include "../../include/okenv_world.h"
+#include "ok_conv.h"
 #include "ok_lidar.h"
 #include "okenv_kernels.h"
 
@@ -119,9 +120,8 @@ inline void okWorldPlan(const ok_world_shape s, int32_t *plan)
 
 // ---- the weights as the kernels read them ----------------------------------------------------------------------------------------------
 
-// A matrix's B [K][Cout] in groups of 16 k's, k the place in the rule's chain: the convolutions' k = tap * Cin' + ch (tap = 4 ty + tx;
-// Cin' = Cin, layer 0: 4), fc_mu's k = p * c3 + ch:  pack[((k / 16) * Cout + n) * 16 + (k % 4) * 4 + (k % 16) / 4]  (ok_bev.h).  Layer 0's
-// alpha slot is 0.0f.
+// ok_conv.h's layout, k the place in the rule's chain: the convolutions' k = tap * Cin' + ch (tap = 4 ty + tx; Cin' = Cin, layer 0: 4),
+// fc_mu's k = p * c3 + ch.  Layer 0's alpha slot is 0.0f.
 struct OkWorldPackParams
 {
     ok_world_shape s;
@@ -140,9 +140,8 @@ __global__ __launch_bounds__(256) void okWorldPackKernel(const OkWorldPackParams
     const int l    = e >= pl.pack[4] ? 4 : (e >= pl.pack[3] ? 3 : (e >= pl.pack[2] ? 2 : (e >= pl.pack[1] ? 1 : 0)));
     const int base = l == 4 ? pl.pack[4] : (l == 3 ? pl.pack[3] : (l == 2 ? pl.pack[2] : (l == 1 ? pl.pack[1] : 0)));
     const int Cout = l == 4 ? p.s.Z : (l == 3 ? p.s.c[3] : (l == 2 ? p.s.c[2] : (l == 1 ? p.s.c[1] : p.s.c[0])));
-    const int idx = e - base, grp = idx / (Cout * 16), rem = idx - grp * Cout * 16, n = rem >> 4, g = (rem & 15) >> 2, q = rem & 3;
-    const int kk = grp * 16 + 4 * q + g;
-    float     v  = 0.F;
+    const auto [n, kk] = okConvPackAt(e - base, Cout);
+    float      v       = 0.F;
     if (l == 0)
     {
         const int tap = kk >> 2, ch = kk & 3;
@@ -156,8 +155,8 @@ __global__ __launch_bounds__(256) void okWorldPackKernel(const OkWorldPackParams
     }
     else
     {
-        const int Cin = l == 3 ? p.s.c[2] : (l == 2 ? p.s.c[1] : p.s.c[0]), tap = kk / Cin, ch = kk - tap * Cin;
-        v = p.params[(l == 3 ? at.w[3] : (l == 2 ? at.w[2] : at.w[1])) + (n * Cin + ch) * 16 + tap];
+        const int Cin = l == 3 ? p.s.c[2] : (l == 2 ? p.s.c[1] : p.s.c[0]);
+        v = p.params[(l == 3 ? at.w[3] : (l == 2 ? at.w[2] : at.w[1])) + okConvWeightAt(n, kk, Cin, 16)];
     }
     p.pack[e] = v;
 }
@@ -297,14 +296,7 @@ __global__ __launch_bounds__(kWorldThreads) void okWorldConvKernel(const OkWorld
                         for (int m = 0; m < RB; ++m)
                             a[q][m] = ok_actor_lds[(16 * m + i) * kWorldLda + 16 * grp + 4 * q + g];
                     }
-                    const float bq[4] = {bv[grp].x, bv[grp].y, bv[grp].z, bv[grp].w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                    {
-#pragma unroll
-                        for (int m = 0; m < RB; ++m)
-                            acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q][m], bq[q], acc[m], 0, 0, 0);
-                    }
+                    okConvMfma(a, bv[grp], acc);
                 }
             }
         }
@@ -367,10 +359,7 @@ __global__ __launch_bounds__(kWorldThreads) void okWorldLatentKernel(const OkWor
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             a[q] = ok_actor_lds[i * lda + 16 * grp + 4 * q + g];
-        const float bq[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], bq[q], acc, 0, 0, 0);
+        okConvMfma(a, bv, acc);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r)

@@ -1682,18 +1682,30 @@ int actLaunch(okenv *h, void (*kernel)(Params), const int agents, const unsigned
     return OKENV_OK;
 }
 
+// What an entry refuses in its frames argument, `count` RGBA8 frames of image_size x image_size pixels: nullptr when they are as the
+// kernels need them.  align: 4, or 16 for kernels that move a frame as 16-byte vectors wherever its pixels are a multiple of 4
+const char *framesMissing(const void *frames, const int64_t frame_bytes, const int64_t count, const int image_size, const unsigned align)
+{
+    const int px = image_size * image_size;
+    if (!frames)
+        return "NULL argument";
+    if (frame_bytes != count * px * 4)
+        return "frame_bytes is not num_agents x image_size x image_size x 4";
+    if (align == 4U)
+        return reinterpret_cast<uintptr_t>(frames) % 4U != 0U ? "frames must be 4-byte aligned" : nullptr;
+    if (reinterpret_cast<uintptr_t>(frames) % (px % 4 == 0 ? 16U : 4U) != 0U)
+        return "frames must be 16-byte aligned (4-byte where image_size x image_size is no multiple of 4)";
+    return nullptr;
+}
+
 // okenv_bev_encode behind its OK_QUIESCE: the kernels named in `stages` (OKENV_BEV_STAGE_*), in their order, on the stream
 int bevEncode(okenv *h, const uint8_t *frames, const int64_t frame_bytes, float *out, const unsigned stages)
 {
     if (const int rc = driverGate(h, kBevDriver, "encode", kGateHandle | kGateCreated | kGateSet, true, 1U))
         return rc;
     const ok_bev_shape s = okBevShape(h->bev);
-    if (!frames || !out)
-        return driverRefuses(h, OKENV_ERR_INVALID, kBevDriver, "encode", "NULL argument");
-    if (frame_bytes != static_cast<int64_t>(h->shape.N) * s.S * s.S * 4)
-        return driverRefuses(h, OKENV_ERR_INVALID, kBevDriver, "encode", "frame_bytes is not num_agents x image_size x image_size x 4");
-    if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
-        return driverRefuses(h, OKENV_ERR_INVALID, kBevDriver, "encode", "frames must be 4-byte aligned");
+    if (const char *why = !out ? "NULL argument" : framesMissing(frames, frame_bytes, h->shape.N, s.S, 4U))
+        return driverRefuses(h, OKENV_ERR_INVALID, kBevDriver, "encode", why);
     OK_HIP(h, hipSetDevice(h->device));
     const OkBevPlaces pl = okBevPlaces(s);
     OkBevEncodeParams p{};
@@ -1723,17 +1735,7 @@ int bevEncode(okenv *h, const uint8_t *frames, const int64_t frame_bytes, float 
 // okenv_cnn_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_CNN_STAGE_*), in their order, on the stream
 int cnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_cnn_record *rec, const unsigned stages)
 {
-    const char *missing = nullptr;
-    if (h != nullptr && h->cnn_drv.ok)
-    {
-        const int S = h->cnn.image_size;
-        if (!frames)
-            missing = "NULL argument";
-        else if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
-            missing = "frame_bytes is not num_agents x image_size x image_size x 4";
-        else if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
-            missing = "frames must be 4-byte aligned";
-    }
+    const char *missing = h != nullptr && h->cnn_drv.ok ? framesMissing(frames, frame_bytes, h->shape.N, h->cnn.image_size, 4U) : nullptr;
     if (const int rc = actBegin(h, kCnnDriver, 1U, missing))
         return rc;
     const ok_cnn_shape s  = okCnnShape(h->cnn);
@@ -1764,14 +1766,7 @@ int cnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const oke
 // What okenv_qcnn_act and okenv_qcnn_push refuse in their frames: nullptr when they are as the kernels need them
 const char *qcnnFramesMissing(const okenv *h, const void *frames, const int64_t frame_bytes)
 {
-    const int S = h->qcnn.image_size;
-    if (!frames)
-        return "NULL argument";
-    if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
-        return "frame_bytes is not num_agents x image_size x image_size x 4";
-    if (reinterpret_cast<uintptr_t>(frames) % (okQcnnPlaces(okQcnnShape(h->qcnn)).vec != 0 ? 16U : 4U) != 0U)
-        return "frames must be 16-byte aligned (4-byte where image_size x image_size is no multiple of 4)";
-    return nullptr;
+    return framesMissing(frames, frame_bytes, h->shape.N, h->qcnn.image_size, 16U); // (OkQcnnPlaces' vec)
 }
 
 template <int RT>
@@ -1872,10 +1867,10 @@ int vitEmbed(okenv *h, const uint8_t *frames, const int32_t m, const int64_t fra
     const size_t       frame = static_cast<size_t>(s.S) * static_cast<size_t>(s.S) * 4U;
     if (!frames || !embedding)
         return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "embed", "NULL argument");
-    if (m < 1 || frame_bytes != static_cast<int64_t>(m) * static_cast<int64_t>(frame))
+    if (m < 1 || frame_bytes != static_cast<int64_t>(m) * static_cast<int64_t>(frame)) // (its own text: the frames are m, not num_agents)
         return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "embed", "m must be at least 1 and frame_bytes m x image_size x image_size x 4");
-    if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
-        return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "embed", "frames must be 4-byte aligned");
+    if (const char *why = framesMissing(frames, frame_bytes, m, s.S, 4U))
+        return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "embed", why);
     OK_HIP(h, hipSetDevice(h->device));
     const ok_vit_layout at = ok_vit_offsets(s);
     const int           T = ok_vit_tokens(s), D = s.D;
@@ -1966,17 +1961,7 @@ int vitHeadRun(okenv *h, const char *entry, const bool update, const float *embe
 // okenv_vit_act behind its OK_QUIESCE: the fixed launch sequence (ok_vit.h), once per pass of vit_pass agents, on the stream
 int vitAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_vit_record *rec)
 {
-    const char *missing = nullptr;
-    if (h != nullptr && h->vit_drv.ok)
-    {
-        const int S = h->vit.image_size;
-        if (!frames)
-            missing = "NULL argument";
-        else if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
-            missing = "frame_bytes is not num_agents x image_size x image_size x 4";
-        else if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
-            missing = "frames must be 4-byte aligned";
-    }
+    const char *missing = h != nullptr && h->vit_drv.ok ? framesMissing(frames, frame_bytes, h->shape.N, h->vit.image_size, 4U) : nullptr;
     if (const int rc = actBegin(h, kVitDriver, 1U, missing))
         return rc;
     const ok_vit_shape  s  = okVitShape(h->vit);
@@ -2007,17 +1992,7 @@ int worldKernels(okenv *h, const uint8_t *frames, const okenv_world_record *rec,
 
 int worldAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_world_record *rec, const unsigned stages)
 {
-    const char *missing = nullptr;
-    if (h != nullptr && h->world_drv.ok)
-    {
-        const int S = h->world.image_size;
-        if (!frames)
-            missing = "NULL argument";
-        else if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
-            missing = "frame_bytes is not num_agents x image_size x image_size x 4";
-        else if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
-            missing = "frames must be 4-byte aligned";
-    }
+    const char *missing = h != nullptr && h->world_drv.ok ? framesMissing(frames, frame_bytes, h->shape.N, h->world.image_size, 4U) : nullptr;
     if (const int rc = actBegin(h, kWorldDriver, 3U, missing))
         return rc;
     return worldKernels(h, frames, rec, stages);
@@ -2108,15 +2083,9 @@ int memoryAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const 
     const char *missing = nullptr;
     if (h != nullptr && h->mem_drv.ok)
     {
-        const int S = h->world.image_size;
         if (!h->world_drv.ok || !h->world_drv.set[0])
             return driverRefuses(h, OKENV_ERR_STATE, kMemoryDriver, "act", "call okenv_world_set_params first (the encoder needs its parameters)");
-        if (!frames)
-            missing = "NULL argument";
-        else if (frame_bytes != static_cast<int64_t>(h->shape.N) * S * S * 4)
-            missing = "frame_bytes is not num_agents x image_size x image_size x 4";
-        else if (reinterpret_cast<uintptr_t>(frames) % 4U != 0U)
-            missing = "frames must be 4-byte aligned";
+        missing = framesMissing(frames, frame_bytes, h->shape.N, h->world.image_size, 4U);
     }
     if (const int rc = actBegin(h, kMemoryDriver, 3U, missing))
         return rc;
