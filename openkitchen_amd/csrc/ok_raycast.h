@@ -494,12 +494,13 @@ OKRC_HD void okCellRefPoint(const OkGridGeom &g, const int ix, const int iy, con
 // F point registered in the cell can lie from a point of the cell, ok_grid.h).
 OKRC_HD int okChiPairClass(const OkPoint a, const OkPoint b, const float rx, const float ry, const float ox, const float oy, const float t12, const float t34)
 {
-    const float sx = b.x - a.x, sy = b.y - a.y;
-    const float d1 = sx * (ry - a.y) - sy * (rx - a.x);
-    const float d2 = sx * (oy - a.y) - sy * (ox - a.x);
-    const float wx = ox - rx, wy = oy - ry;
-    const float d3 = wx * (a.y - ry) - wy * (a.x - rx);
-    const float d4 = wx * (b.y - ry) - wy * (b.x - rx);
+    // (okUnpaired on the differences of y coordinates and on the products they enter: plain VALU, no packed pairs; same bits)
+    const float sx = b.x - a.x, sy = okUnpaired(b.y - a.y);
+    const float d1 = sx * okUnpaired(ry - a.y) - okUnpaired(sy * (rx - a.x));
+    const float d2 = sx * okUnpaired(oy - a.y) - okUnpaired(sy * (ox - a.x));
+    const float wx = ox - rx, wy = okUnpaired(oy - ry);
+    const float d3 = wx * okUnpaired(a.y - ry) - okUnpaired(wy * (a.x - rx));
+    const float d4 = wx * okUnpaired(b.y - ry) - okUnpaired(wy * (b.x - rx));
     const bool  c12 = __builtin_fabsf(d1) > t12 && __builtin_fabsf(d2) > t12; // both signs are the true ones
     const bool  c34 = __builtin_fabsf(d3) > t34 && __builtin_fabsf(d4) > t34;
     const bool  opp12 = (d1 > 0.F) != (d2 > 0.F), opp34 = (d3 > 0.F) != (d4 > 0.F);
@@ -508,6 +509,66 @@ OKRC_HD int okChiPairClass(const OkPoint a, const OkPoint b, const float rx, con
     if (c12 && c34) // (opp12 && opp34)
         return 1;
     return 2;
+}
+
+// The cell of a ray origin (the origin test's, and the arithmetic the walk's set-up repeats for its start cell).  `cell` is 0 for
+// an origin outside the grid box (a NaN pose included), so hdr[cell] can always be read.
+struct OkOriginCell
+{
+    int  ix, iy, cell;
+    bool inside;
+};
+OKRC_HD bool okInsideBox(const OkGridGeom &g, const float ox, const float oy)
+{
+    return ox >= g.x0 && ox <= g.x1 && oy >= g.y0 && oy <= g.y1; // (false for NaN poses)
+}
+OKRC_HD OkOriginCell okOriginCellOf(const OkGridGeom &g, const float ox, const float oy)
+{
+    OkOriginCell oc;
+    oc.inside = okInsideBox(g, ox, oy);
+    int ix    = (int)__builtin_floorf((ox - g.x0) * g.inv_cell);
+    int iy    = (int)__builtin_floorf(okUnpaired(okUnpaired(oy - g.y0) * g.inv_cell));
+    oc.ix     = ix < 0 ? 0 : (ix >= g.nx ? g.nx - 1 : ix);
+    oc.iy     = iy < 0 ? 0 : (iy >= g.ny ? g.ny - 1 : iy);
+    oc.cell   = oc.inside ? oc.iy * g.nx + oc.ix : 0;
+    return oc;
+}
+
+// A cell's header by ONE 8-byte load: read as two words, the code generator may fetch w0 first and brk by a later, dependent
+// load where brk is first used.  (Headers are 8-byte aligned.)
+OKRC_HD OkCellHdr okLoadHdr(const OkCellHdr *h)
+{
+    unsigned long long u;
+    __builtin_memcpy(&u, __builtin_assume_aligned(h, 8), 8);
+    return {static_cast<uint32_t>(u), static_cast<uint32_t>(u >> 32)};
+}
+
+// ---- the square around an origin inside which the origin test's answer stands ---------------------------------------------------
+// chi is a function of the position alone and flips only across F, so the answer holds at every point the origin can reach along
+// a straight line that meets no F segment.  The F segments registered in the origin's cell are kept off by their bounding boxes
+// (okPairBoxDist), all others lie outside the cell (okCellBorderDist).  Both are distances along the axes, so what they clear is
+// the open SQUARE of that half-width around the origin: a point of it is separated from each box by one axis and lies in the
+// cell, and so does the whole line to it.  The step loop therefore compares the LARGER of the two coordinate differences
+// (okOriginMoved) with the half-width: the test is repeated when the origin has left the square, not the diamond |dx| + |dy| < r
+// inside it.  okClearSlack shortens the half-width for the rounding here and in that comparison.
+OKRC_HD float okPairBoxDist(const OkPoint a, const OkPoint b, const float ox, const float oy)
+{ // Chebyshev distance to the segment's bounding box
+    const float bx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(a.x, b.x) - ox, ox - __builtin_fmaxf(a.x, b.x)), 0.F);
+    const float by = __builtin_fmaxf(__builtin_fmaxf(okUnpaired(__builtin_fminf(a.y, b.y) - oy), okUnpaired(oy - __builtin_fmaxf(a.y, b.y))), 0.F);
+    return __builtin_fmaxf(bx, by);
+}
+OKRC_HD float okCellBorderDist(const OkGridGeom &g, const int ix, const int iy, const float ox, const float oy)
+{ // (the cell's corners in the walk's own arithmetic)
+    const float cx0 = g.x0 + static_cast<float>(ix) * g.cell, cy0 = okUnpaired(g.y0 + okUnpaired(static_cast<float>(iy) * g.cell));
+    return __builtin_fminf(__builtin_fminf(ox - cx0, (cx0 + g.cell) - ox), __builtin_fminf(okUnpaired(oy - cy0), okUnpaired(okUnpaired(cy0 + g.cell) - oy)));
+}
+OKRC_HD float okClearSlack(const float near)
+{
+    return 0.99F * near - 1.0e-3F;
+}
+OKRC_HD float okOriginMoved(const float ox, const float oy, const float from_x, const float from_y)
+{ // (a NaN pose gives NaN, which fails "moved < half-width")
+    return __builtin_fmaxf(__builtin_fabsf(ox - from_x), __builtin_fabsf(okUnpaired(oy - from_y)));
 }
 
 // The test as one thread makes it (the CPU tests; the kernels deal the pairs to the lanes of the agent's group: okenv_kernels.h,
@@ -545,6 +606,29 @@ OKRC_HD int okOriginChiScalar(const OkPolyView &front, const float ox, const flo
     return static_cast<int>(parity);
 }
 
+// The half-width that goes with the test, as one thread forms it: the arithmetic okOriginChiGroup runs per pair, the minimum taken
+// in slot order instead of across lanes (a minimum of floats does not depend on the order).  0 for an origin in a cell that is not
+// certifiable; an origin outside the grid box stays uncertified at least until it has covered the distance back to the box.
+OKRC_HD float okOriginClearScalar(const OkPolyView &front, const float ox, const float oy)
+{
+    const OkGridGeom  &g  = front.g;
+    const OkOriginCell oc = okOriginCellOf(g, ox, oy);
+    if (!oc.inside)
+        return okClearSlack(__builtin_fmaxf(__builtin_fmaxf(g.x0 - ox, ox - g.x1), __builtin_fmaxf(g.y0 - oy, oy - g.y1)));
+    const OkCellHdr hc    = okLoadHdr(&front.hdr[oc.cell]);
+    const uint32_t  flags = (hc.w0 >> OKFB_HDR_SHIFT_RC) & 15U;
+    if ((flags & OKFB_RC_CERT) == 0U)
+        return 0.F;
+    const uint32_t k0 = hc.w0 & OKPOLY_IDX_MASK;
+    const uint32_t n8 = (((hc.w0 >> OKPOLY_IDX_BITS) & OKPOLY_N_MASK) + 7U) & ~7U;
+    const uint32_t nf = hc.w0 >> OKFB_HDR_NF_SHIFT;
+    float          near = okCellBorderDist(g, oc.ix, oc.iy, ox, oy);
+    for (uint32_t j = 0; j + 1U < nf; ++j)
+        if (((hc.brk >> (n8 - 2U - j)) & 1U) == 0U)
+            near = __builtin_fminf(near, okPairBoxDist(front.slots[k0 + j], front.slots[k0 + j + 1U], ox, oy));
+    return okClearSlack(near);
+}
+
 // What a walk over part of a ray reports.
 struct OkIntervalResult
 {
@@ -559,6 +643,15 @@ struct alignas(16) OkVec4 // 16-byte aligned load unit (ds_read_b128): two conse
 {
     float x, y, z, w;
 };
+
+// Keeps the instruction scheduler from moving what precedes it below what follows (a load that must be ISSUED early).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define OKRC_PIN_ISSUE() __builtin_amdgcn_sched_barrier(0)
+#define OKRC_WAIT_LDS() __builtin_amdgcn_s_waitcnt(0xC07F) // lgkmcnt(0), the other counters left alone
+#else
+#define OKRC_PIN_ISSUE() ((void)0)
+#define OKRC_WAIT_LDS() ((void)0)
+#endif
 
 // median of three; one v_med3_f32 on the GPU
 OKRC_HD float okMed3(const float a, const float b, const float c)
@@ -628,7 +721,14 @@ OKRC_HD uint32_t okShiftInSign(const uint32_t acc, const float d)
 // three 24 px cells; the first of them is the neighbour's last.)  Must be false for the walk that starts a ray.
 // min_t0: a first hit already known from elsewhere (the front image's, when this walk covers the back image): the walk starts
 // with it, so it ends as soon as the cells up to that parameter are covered and reports min(min_t0, what it finds).
-template <bool kCount, bool kAmb = false>
+//
+// kOrigin / from_origin: the walk that STARTS a ray (t_a = 0, skip_unowned_start false) may be told that the origin lies inside the
+// grid box -- for every lane that walks, one ballot per wave, so the branch is the wave's and not the lane's.  The slab clip is
+// then left out: it could only yield t_in = 0, so the start cell is the origin's (ox + 0 * rdx is ox), and its t_out only repeats
+// what the steps-left counters decide (the box ends where the grid does: x1 = x0 + nx * cell in ok_grid.h), so t_out stays at the
+// sensor range and the walk leaves by code 3 where the clip would have ended it by code 1.  Same cells or a superset (where a few
+// ulps put the clip's t_out before the last cell's own exit), hence the same bits.  from_origin = false is the generic path.
+template <bool kCount, bool kAmb = false, bool kOrigin = false>
 OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
                                                const float       ox,
                                                const float       oy,
@@ -641,42 +741,57 @@ OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
                                                uint32_t         *points,
                                                unsigned long long *prof = nullptr,
                                                const bool        skip_unowned_start = false,
-                                               const float       min_t0 = OK_SENSOR_RANGE)
+                                               const float       min_t0 = OK_SENSOR_RANGE,
+                                               const bool        from_origin = false)
 {
     const OkGridGeom &g = v.g;
     OKRC_PROF_BEGIN();
-    // ---- set-up: slab clip of [t_a, range] against the grid box (same arithmetic as OkWalk::init) ----
+    // (okUnpaired on the y side of the set-up: plain VALU, no packed pairs and none of their hazard waits; same bits.  The barriers
+    // stand outside the selects: a select's arm cannot be evaluated speculatively through one and would become a branch.)
     const bool  par_x  = __builtin_fabsf(rdx) < 1e-30F;
     const bool  par_y  = __builtin_fabsf(rdy) < 1e-30F;
     const float inv_dx = par_x ? 0.0F : okRcpApprox(rdx);
     const float inv_dy = par_y ? 0.0F : okRcpApprox(rdy);
-    const float tax = (g.x0 - ox) * inv_dx, tbx = (g.x1 - ox) * inv_dx;
-    const float tay = (g.y0 - oy) * inv_dy, tby = (g.y1 - oy) * inv_dy;
-    float       t_in  = t_a;
-    float       t_out = OK_SENSOR_RANGE;
-    t_in              = par_x ? t_in : __builtin_fmaxf(t_in, __builtin_fminf(tax, tbx));
-    t_out             = par_x ? t_out : __builtin_fminf(t_out, __builtin_fmaxf(tax, tbx));
-    t_in              = par_y ? t_in : __builtin_fmaxf(t_in, __builtin_fminf(tay, tby));
-    t_out             = par_y ? t_out : __builtin_fminf(t_out, __builtin_fmaxf(tay, tby));
-    const bool in_x   = !par_x || (ox >= g.x0 && ox <= g.x1);
-    const bool in_y   = !par_y || (oy >= g.y0 && oy <= g.y1);
-    if (!(in_x && in_y && (t_in <= t_out))) // the interval misses the grid box (also rejects NaN poses)
-        return {min_t0, OK_SENSOR_RANGE, true, false};
-    const float px = ox + t_in * rdx;
-    const float py = oy + t_in * rdy;
-    int         ix = (int)__builtin_floorf((px - g.x0) * g.inv_cell);
-    int         iy = (int)__builtin_floorf((py - g.y0) * g.inv_cell);
-    ix             = ix < 0 ? 0 : (ix >= g.nx ? g.nx - 1 : ix);
-    iy             = iy < 0 ? 0 : (iy >= g.ny ? g.ny - 1 : iy);
+    float       t_out  = OK_SENSOR_RANGE;
+    float       px = ox, py = oy;
+    if (!(kOrigin && from_origin))
+    {
+        // ---- slab clip of [t_a, range] against the grid box (same arithmetic as OkWalk::init) ----
+        const float tax = (g.x0 - ox) * inv_dx, tbx = (g.x1 - ox) * inv_dx;
+        const float tay = okUnpaired(okUnpaired(g.y0 - oy) * inv_dy), tby = okUnpaired(okUnpaired(g.y1 - oy) * inv_dy);
+        float       t_in = t_a;
+        t_in             = par_x ? t_in : __builtin_fmaxf(t_in, __builtin_fminf(tax, tbx));
+        t_out            = par_x ? t_out : __builtin_fminf(t_out, __builtin_fmaxf(tax, tbx));
+        t_in             = par_y ? t_in : __builtin_fmaxf(t_in, __builtin_fminf(tay, tby));
+        t_out            = par_y ? t_out : __builtin_fminf(t_out, __builtin_fmaxf(tay, tby));
+        const bool in_x  = !par_x || (ox >= g.x0 && ox <= g.x1);
+        const bool in_y  = !par_y || (oy >= g.y0 && oy <= g.y1);
+        if (!(in_x && in_y && (t_in <= t_out))) // the interval misses the grid box (also rejects NaN poses)
+            return {min_t0, OK_SENSOR_RANGE, true, false};
+        px = ox + t_in * rdx;
+        py = okUnpaired(oy + okUnpaired(t_in * rdy));
+    }
+    int ix = (int)__builtin_floorf((px - g.x0) * g.inv_cell);
+    int iy = (int)__builtin_floorf(okUnpaired(okUnpaired(py - g.y0) * g.inv_cell));
+    ix     = ix < 0 ? 0 : (ix >= g.nx ? g.nx - 1 : ix);
+    iy     = iy < 0 ? 0 : (iy >= g.ny ? g.ny - 1 : iy);
+    int cell = iy * g.nx + ix; // linear cell index
+    OkCellHdr h_next;
+    if (kOrigin)
+    { // (a walk that starts a ray never steps over its start cell: the header is requested here, under the rest of the set-up)
+        h_next = v.hdr[cell];
+        OKRC_PIN_ISSUE();
+    }
     const bool  fwd_x = rdx >= 0.0F, fwd_y = rdy >= 0.0F;
     const float bx    = g.x0 + (float)(ix + (fwd_x ? 1 : 0)) * g.cell;
-    const float by    = g.y0 + (float)(iy + (fwd_y ? 1 : 0)) * g.cell;
-    float       tmax_x = par_x ? OKRC_INF : (bx - ox) * inv_dx;
-    float       tmax_y = par_y ? OKRC_INF : (by - oy) * inv_dy;
-    const float tdel_x = par_x ? OKRC_INF : g.cell * __builtin_fabsf(inv_dx);
-    const float tdel_y = par_y ? OKRC_INF : g.cell * __builtin_fabsf(inv_dy);
+    const float by    = okUnpaired(g.y0 + okUnpaired((float)(iy + (fwd_y ? 1 : 0)) * g.cell));
+    const float tmx = (bx - ox) * inv_dx, tmy = okUnpaired(okUnpaired(by - oy) * inv_dy);
+    const float tdx = g.cell * __builtin_fabsf(inv_dx), tdy = okUnpaired(g.cell * __builtin_fabsf(inv_dy));
+    float       tmax_x = par_x ? OKRC_INF : tmx;
+    float       tmax_y = par_y ? OKRC_INF : tmy;
+    const float tdel_x = par_x ? OKRC_INF : tdx;
+    const float tdel_y = par_y ? OKRC_INF : tdy;
     // linear cell index, its increments, and the steps left before the walk leaves the grid on either axis
-    int       cell   = iy * g.nx + ix;
     const int lin_x  = fwd_x ? 1 : -1;
     const int lin_y  = fwd_y ? g.nx : -g.nx;
     int       left_x = fwd_x ? g.nx - 1 - ix : ix;
@@ -698,7 +813,6 @@ OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
     // Every loop-carried quantity is a plain register value (no lane masks carried around the loop).
     float     t_exit, tnx, tny;
     int       cell_n, leave;
-    OkCellHdr h_next;
 #define OKRC_ENTER_CELL()                                                                                              \
     do                                                                                                                 \
     {                                                                                                                  \
@@ -711,8 +825,8 @@ OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
         cell_n = cell + (go_x ? lin_x : lin_y);                                                                        \
         cell_n = cell_n < 0 ? 0 : (cell_n > last_cell ? last_cell : cell_n);                                           \
         h_next = v.hdr[cell_n];                                                                                        \
-        leave  = (left_x | left_y) >= 0 ? 0 : 3;                                                                       \
-        leave  = (t_exit >= t_b) ? 2 : leave;                                                                          \
+        leave  = (t_exit >= t_b) ? 2 : 0;                                                                              \
+        leave  = (left_x | left_y) >= 0 ? leave : 3; /* (beyond the grid there is nothing: conclusive whatever t_b) */  \
         leave  = (t_out <= t_exit) ? 1 : leave;                                                                        \
     } while (0)
 
@@ -737,68 +851,76 @@ OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
             tmax_y = go_x ? tmax_y : tmax_y + tdel_y;
         }
     }
-    OkCellHdr hc = v.hdr[cell];
-    OKRC_ENTER_CELL();
-    if (kCount)
-        *cells += 1;
+    // The start cell's header travels as "the next cell's": every cell, the first included, takes its header from h_next at the
+    // top of the loop and requests its successor's right away, so the only wait for a header is for one requested a whole cell
+    // (or, at the start, a whole set-up) earlier, and nothing waits for the request just made.
+    if (!kOrigin)
+        h_next = v.hdr[cell];
     OKRC_PROF(0);
-    // One pass per chunk of <= 32 slots (almost every cell is a single chunk; a cell's chain of chunks is finite by
-    // construction of the image).  The walk visits at most nx + ny cells: the explicit bound on cell steps makes
-    // termination unconditional.
+    // The walk visits at most nx + ny cells: the explicit bound on cell steps makes termination unconditional.
     int guard = g.nx + g.ny + 2;
     while (true)
     {
-        const uint32_t k0 = hc.w0 & OKPOLY_IDX_MASK;
-        const uint32_t n  = (hc.w0 >> OKPOLY_IDX_BITS) & OKPOLY_N_MASK;
+        OkCellHdr hc = h_next;
+        OKRC_ENTER_CELL();
         if (kCount)
-            *points += n;
-        // Point loop.  After it, bit (n8 - 1 - j) of `skip` tells that the pair (slot k0+j-1, slot k0+j) lies clearly on one
-        // side of the ray (n8 = n rounded up to 8); the header's break bits use the same positions.
-        uint32_t skip = 0U;
-        float    sp   = 0.F;
-        OKRC_PROF(1);
-        for (uint32_t i = 0; i < n; i += 8)
+            *cells += 1;
+        // One pass per chunk of <= 32 slots (almost every cell is a single chunk; a cell's chain of chunks is finite by
+        // construction of the image).
+        while (true)
         {
-            const OkVec4 *q  = reinterpret_cast<const OkVec4 *>(v.slots + k0 + i); // k0 + i is even, the slot array 16-byte aligned
-            const OkVec4  q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-            const float   s0 = __builtin_fmaf(q0.x, rdy, __builtin_fmaf(q0.y, neg_dx, -c_ray));
-            const float   s1 = __builtin_fmaf(q0.z, rdy, __builtin_fmaf(q0.w, neg_dx, -c_ray));
-            const float   s2 = __builtin_fmaf(q1.x, rdy, __builtin_fmaf(q1.y, neg_dx, -c_ray));
-            const float   s3 = __builtin_fmaf(q1.z, rdy, __builtin_fmaf(q1.w, neg_dx, -c_ray));
-            const float   s4 = __builtin_fmaf(q2.x, rdy, __builtin_fmaf(q2.y, neg_dx, -c_ray));
-            const float   s5 = __builtin_fmaf(q2.z, rdy, __builtin_fmaf(q2.w, neg_dx, -c_ray));
-            const float   s6 = __builtin_fmaf(q3.x, rdy, __builtin_fmaf(q3.y, neg_dx, -c_ray));
-            const float   s7 = __builtin_fmaf(q3.z, rdy, __builtin_fmaf(q3.w, neg_dx, -c_ray));
-            skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(sp, s0, 0.F)));
-            skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s0, s1, 0.F)));
-            skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s1, s2, 0.F)));
-            skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s2, s3, 0.F)));
-            skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s3, s4, 0.F)));
-            skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s4, s5, 0.F)));
-            skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s5, s6, 0.F)));
-            skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s6, s7, 0.F)));
-            sp               = s7;
-        }
-        // Exact tests of the surviving segments, all lanes of a wave together: the long test stays out of the point
-        // loop, and a wave runs it max-over-lanes(survivors) times per chunk (typically 2: the inner and the outer
-        // boundary).
-        uint32_t       cand = ~(skip | hc.brk);
-        const uint32_t top  = k0 + ((n + 7U) & ~7U) - 2U; // bit b <-> pair (slot top - b, slot top - b + 1)
-        OKRC_PROF(2);
-        while (cand != 0U)
-        { // highest bit first = ascending slots, the order of the reference's sweep inside a run (it decides which of
-          // two hits at t = +0 / -0 is kept)
-            const uint32_t z = static_cast<uint32_t>(__builtin_clz(cand));
-            cand &= ~(0x80000000U >> z);
+            const uint32_t k0 = hc.w0 & OKPOLY_IDX_MASK;
+            const uint32_t n  = (hc.w0 >> OKPOLY_IDX_BITS) & OKPOLY_N_MASK;
             if (kCount)
-                *tests += 1;
-            min_t = okExactSlot<kAmb>(v, top - (31U - z), ox, oy, rdx, rdy, min_t, &amb);
-        }
-        OKRC_PROF(3);
-        if (((hc.w0 >> (OKPOLY_IDX_BITS + 6)) & 1U) != 0U)
-        { // the cell continues in another chunk: its header sits right behind this chunk's slots
+                *points += n;
+            // Point loop.  After it, bit (n8 - 1 - j) of `skip` tells that the pair (slot k0+j-1, slot k0+j) lies clearly on one
+            // side of the ray (n8 = n rounded up to 8); the header's break bits use the same positions.
+            uint32_t skip = 0U;
+            float    sp   = 0.F;
+            OKRC_PROF(1);
+            for (uint32_t i = 0; i < n; i += 8)
+            {
+                const OkVec4 *q  = reinterpret_cast<const OkVec4 *>(v.slots + k0 + i); // k0 + i is even, the slot array 16-byte aligned
+                const OkVec4  q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+                const float   s0 = __builtin_fmaf(q0.x, rdy, __builtin_fmaf(q0.y, neg_dx, -c_ray));
+                const float   s1 = __builtin_fmaf(q0.z, rdy, __builtin_fmaf(q0.w, neg_dx, -c_ray));
+                const float   s2 = __builtin_fmaf(q1.x, rdy, __builtin_fmaf(q1.y, neg_dx, -c_ray));
+                const float   s3 = __builtin_fmaf(q1.z, rdy, __builtin_fmaf(q1.w, neg_dx, -c_ray));
+                const float   s4 = __builtin_fmaf(q2.x, rdy, __builtin_fmaf(q2.y, neg_dx, -c_ray));
+                const float   s5 = __builtin_fmaf(q2.z, rdy, __builtin_fmaf(q2.w, neg_dx, -c_ray));
+                const float   s6 = __builtin_fmaf(q3.x, rdy, __builtin_fmaf(q3.y, neg_dx, -c_ray));
+                const float   s7 = __builtin_fmaf(q3.z, rdy, __builtin_fmaf(q3.w, neg_dx, -c_ray));
+                skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(sp, s0, 0.F)));
+                skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s0, s1, 0.F)));
+                skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s1, s2, 0.F)));
+                skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s2, s3, 0.F)));
+                skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s3, s4, 0.F)));
+                skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s4, s5, 0.F)));
+                skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s5, s6, 0.F)));
+                skip             = okShiftInSign(skip, tol - __builtin_fabsf(okMed3(s6, s7, 0.F)));
+                sp               = s7;
+            }
+            // Exact tests of the surviving segments, all lanes of a wave together: the long test stays out of the point
+            // loop, and a wave runs it max-over-lanes(survivors) times per chunk (typically 2: the inner and the outer
+            // boundary).
+            uint32_t       cand = ~(skip | hc.brk);
+            const uint32_t top  = k0 + ((n + 7U) & ~7U) - 2U; // bit b <-> pair (slot top - b, slot top - b + 1)
+            OKRC_PROF(2);
+            while (cand != 0U)
+            { // highest bit first = ascending slots, the order of the reference's sweep inside a run (it decides which of
+              // two hits at t = +0 / -0 is kept)
+                const uint32_t z = static_cast<uint32_t>(__builtin_clz(cand));
+                cand &= ~(0x80000000U >> z);
+                if (kCount)
+                    *tests += 1;
+                min_t = okExactSlot<kAmb>(v, top - (31U - z), ox, oy, rdx, rdy, min_t, &amb);
+            }
+            OKRC_PROF(3);
+            if (((hc.w0 >> (OKPOLY_IDX_BITS + 6)) & 1U) == 0U)
+                break;
+            // the cell continues in another chunk: its header sits right behind this chunk's slots
             hc = *reinterpret_cast<const OkCellHdr *>(&v.slots[k0 + n]);
-            continue;
+            OKRC_WAIT_LDS(); // (waited for here, where it is rare, so that the chunk loop's head need not wait for h_next as well)
         }
         // leave the cell
         leave = (min_t <= t_exit) ? 1 : leave; // first hit inside the covered part
@@ -807,10 +929,6 @@ OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
         cell   = cell_n;
         tmax_x = tnx;
         tmax_y = tny;
-        hc     = h_next;
-        OKRC_ENTER_CELL();
-        if (kCount)
-            *cells += 1;
         OKRC_PROF(4);
     }
 #undef OKRC_ENTER_CELL

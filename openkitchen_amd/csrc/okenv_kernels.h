@@ -871,48 +871,52 @@ __device__ __forceinline__ OkPolyView okSetupView(const OkStepParams &p, unsigne
 // thread makes it.)  Here the pairs of the origin cell's front chunk are dealt to the G lanes of the agent's group, lane r taking
 // pairs r, r + G, ...; the classes are the scalar test's, their parity and "any pair that cannot be told" come together by two
 // ballots.  Every lane of the group returns the same answer.
-// *clear: a radius around the origin inside which the answer cannot change -- chi is a function of the position alone and flips
-// only across F, so it holds wherever no F segment can be reached: a lower bound of the distance to the F segments registered
-// in the cell (each by its bounding box) and to the cell's own border (every other F segment lies beyond that).  The step loop
-// repeats the test only when the origin has left that circle (an agent moves 1.6 px per step at most).
-__device__ __forceinline__ bool okOriginChiGroup(const OkPolyView &front, const float ox, const float oy, const int r, const int G, const float t12,
-                                                 const float t34, float *clear)
+// *clear: the half-width of the square around the origin inside which the answer cannot change (ok_raycast.h, above okPairBoxDist,
+// has the argument and okOriginClearScalar the same arithmetic as one thread runs it).  The step loop repeats the test only when
+// the origin has left that square (okOriginMoved; an agent moves 1.6 px per step at most).
+// oc, hc: the origin's cell and its header (hdr[oc.cell], by okLoadHdr: one load for both words), formed where the test is due --
+// formed once per step for the test and for phase 1's set-up they cost the headline kernel 16 more spilled SGPRs (docs/HISTORY.md
+// section 47).
+__device__ __forceinline__ bool okOriginChiGroup(const OkPolyView &front, const float ox, const float oy, const OkOriginCell &oc, const OkCellHdr hc,
+                                                 const int r, const int G, const float t12, const float t34, float *clear)
 {
     const OkGridGeom &g      = front.g;
-    const bool        inside = ox >= g.x0 && ox <= g.x1 && oy >= g.y0 && oy <= g.y1; // (false for NaN poses)
-    int               ix     = (int)__builtin_floorf((ox - g.x0) * g.inv_cell);
-    int               iy     = (int)__builtin_floorf((oy - g.y0) * g.inv_cell);
-    ix                       = ix < 0 ? 0 : (ix >= g.nx ? g.nx - 1 : ix);
-    iy                       = iy < 0 ? 0 : (iy >= g.ny ? g.ny - 1 : iy);
-    const OkCellHdr hc       = front.hdr[inside ? iy * g.nx + ix : 0];
-    const uint32_t  flags    = (hc.w0 >> OKFB_HDR_SHIFT_RC) & 15U;
-    const bool      usable   = inside && (flags & OKFB_RC_CERT) != 0U;
-    float           rx, ry;
-    okCellRefPoint(g, ix, iy, (flags >> 2) & 3U, &rx, &ry);
-    const uint32_t k0 = hc.w0 & OKPOLY_IDX_MASK;
-    const uint32_t n8 = (((hc.w0 >> OKPOLY_IDX_BITS) & OKPOLY_N_MASK) + 7U) & ~7U;
-    const uint32_t n  = usable ? (hc.w0 >> OKFB_HDR_NF_SHIFT) : 0U; // the slots of the cell's F segments: the first of its chunk
-    bool           amb = false, odd = false;
-    // distance to the cell's border (the cell's corners in the walk's own arithmetic)
-    const float cx0 = g.x0 + static_cast<float>(ix) * g.cell, cy0 = g.y0 + static_cast<float>(iy) * g.cell;
-    float       near = __builtin_fminf(__builtin_fminf(ox - cx0, (cx0 + g.cell) - ox), __builtin_fminf(oy - cy0, (cy0 + g.cell) - oy));
-    for (uint32_t j = static_cast<uint32_t>(r); j + 1U < n; j += static_cast<uint32_t>(G))
+    const uint32_t    flags  = (hc.w0 >> OKFB_HDR_SHIFT_RC) & 15U;
+    const bool        usable = oc.inside && (flags & OKFB_RC_CERT) != 0U;
+    const uint32_t    k0     = hc.w0 & OKPOLY_IDX_MASK;
+    const uint32_t    n8     = (((hc.w0 >> OKPOLY_IDX_BITS) & OKPOLY_N_MASK) + 7U) & ~7U;
+    const uint32_t    n      = usable ? (hc.w0 >> OKFB_HDR_NF_SHIFT) : 0U; // the slots of the cell's F segments: the first of its chunk
+    // The lane's first pair is asked for as soon as k0 is known: its LDS round trip runs under the arithmetic up to the loop.  (A
+    // lane without a pair reads the chunk's first two slots: in bounds, not looked at.)
+    uint32_t       j  = static_cast<uint32_t>(r);
+    const uint32_t j0 = j + 1U < n ? j : 0U;
+    OkPoint        pa = front.slots[k0 + j0], pb = front.slots[k0 + j0 + 1U];
+    float          rx, ry;
+    okCellRefPoint(g, oc.ix, oc.iy, (flags >> 2) & 3U, &rx, &ry);
+    bool  amb = false, odd = false;
+    float near = okCellBorderDist(g, oc.ix, oc.iy, ox, oy);
+    while (j + 1U < n)
     {
-        if ((hc.brk >> (n8 - 2U - j)) & 1U) // no segment joins slots j and j + 1
-            continue;
-        const OkPoint pa = front.slots[k0 + j], pb = front.slots[k0 + j + 1U];
-        const int     cls = okChiPairClass(pa, pb, rx, ry, ox, oy, t12, t34);
-        amb               = amb || cls == 2;
-        odd               = odd != (cls == 1);
-        // Chebyshev distance to the segment's bounding box: never more than the distance to the segment
-        const float bx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(pa.x, pb.x) - ox, ox - __builtin_fmaxf(pa.x, pb.x)), 0.F);
-        const float by = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(pa.y, pb.y) - oy, oy - __builtin_fmaxf(pa.y, pb.y)), 0.F);
-        near           = __builtin_fminf(near, __builtin_fmaxf(bx, by));
+        const bool    joined = ((hc.brk >> (n8 - 2U - j)) & 1U) == 0U; // a segment joins slots j and j + 1
+        const OkPoint qa = pa, qb = pb;
+        j += static_cast<uint32_t>(G);
+        if (j + 1U < n)
+        { // (groups narrower than the chunk: the next pair, under this one's arithmetic)
+            pa = front.slots[k0 + j];
+            pb = front.slots[k0 + j + 1U];
+        }
+        if (joined)
+        {
+            const int cls = okChiPairClass(qa, qb, rx, ry, ox, oy, t12, t34);
+            amb           = amb || cls == 2;
+            odd           = odd != (cls == 1);
+            near          = __builtin_fminf(near, okPairBoxDist(qa, qb, ox, oy));
+        }
     }
     near = okGroupMin(near, G);
     // (an origin outside the grid box stays uncertified at least until it has covered the distance back to the box)
     const float outside = __builtin_fmaxf(__builtin_fmaxf(g.x0 - ox, ox - g.x1), __builtin_fmaxf(g.y0 - oy, oy - g.y1));
-    *clear              = usable ? 0.99F * near - 1.0e-3F : (inside ? 0.F : 0.99F * outside - 1.0e-3F); // (slack: rounding here and in the later comparison)
+    *clear              = usable ? okClearSlack(near) : (oc.inside ? 0.F : okClearSlack(outside));
     unsigned long long b_amb = __ballot(amb), b_odd = __ballot(odd);
     if (G < 64)
     {
@@ -1536,12 +1540,14 @@ __global__ void __launch_bounds__(1024) okStepCoopKernel(const OkStepParams p_in
             // be a ray's first hit?  (one answer per agent; its rays' front walks report ambiguous rejections in amb_ray)
             bool cert = false, amb_ray = false;
             if (fb)
-            { // (the answer of the last test stands while the origin stays inside the circle that test cleared; a re-placed agent
+            { // (the answer of the last test stands while the origin stays inside the square that test cleared; a re-placed agent
               // is far outside it, a NaN pose fails the comparison)
-                const float moved = __builtin_fabsf(ox - cert_ox) + __builtin_fabsf(okUnpaired(oy - cert_oy));
+                const float moved = okOriginMoved(ox, oy, cert_ox, cert_oy);
                 if (!(moved < cert_clear))
                 {
-                    cert_state = okOriginChiGroup(view, ox, oy, r, G, p.fb_t12, p.fb_t34, &cert_clear);
+                    const OkOriginCell oc   = okOriginCellOf(view.g, ox, oy);
+                    const OkCellHdr    hc_o = okLoadHdr(&view.hdr[oc.cell]);
+                    cert_state = okOriginChiGroup(view, ox, oy, oc, hc_o, r, G, p.fb_t12, p.fb_t34, &cert_clear);
                     cert_ox    = ox;
                     cert_oy    = oy;
                 }
@@ -1597,8 +1603,11 @@ __global__ void __launch_bounds__(1024) okStepCoopKernel(const OkStepParams p_in
             }
             else if (casts && phase1_range > 0.F)
             {
-                const OkIntervalResult r1 =
-                    ok_cast_poly_interval<false, kAmbW>(view, ox, oy, rdx, rdy, 0.F, phase1_range, nullptr, nullptr, nullptr OK_WPROF(0));
+                // (every walking lane's origin inside the grid box -- one ballot, and with one agent per wave one origin: the walk
+                // starts in the origin's cell without the slab clip, ok_raycast.h)
+                const bool             in_box = __ballot(!okInsideBox(view.g, ox, oy)) == 0ULL;
+                const OkIntervalResult r1     = ok_cast_poly_interval<false, kAmbW, true>(view, ox, oy, rdx, rdy, 0.F, phase1_range, nullptr, nullptr, nullptr OK_WPROF(0),
+                                                                                          false, OK_SENSOR_RANGE, in_box);
                 min_t      = r1.min_t;
                 unfinished = !r1.conclusive;
                 t_reached  = r1.t_reached;
@@ -2078,11 +2087,12 @@ __global__ void __launch_bounds__(kPolicy == kPolicyQ ? 576 : 512) okStepTailKer
         OK_TSTAMP(1);
         bool cert = false;
         if (fb)
-        { // (cooperative kernel: the answer of the last origin test stands while the origin stays inside the circle it cleared)
-            const float moved = __builtin_fabsf(ox - cert_ox) + __builtin_fabsf(oy - cert_oy);
+        { // (cooperative kernel: the answer of the last origin test stands while the origin stays inside the square it cleared)
+            const float moved = okOriginMoved(ox, oy, cert_ox, cert_oy);
             if (!(moved < cert_clear))
             {
-                cert_state = okOriginChiGroup(view, ox, oy, lane, 64, p.fb_t12, p.fb_t34, &cert_clear);
+                const OkOriginCell oc = okOriginCellOf(view.g, ox, oy);
+                cert_state = okOriginChiGroup(view, ox, oy, oc, okLoadHdr(&view.hdr[oc.cell]), lane, 64, p.fb_t12, p.fb_t34, &cert_clear);
                 cert_ox    = ox;
                 cert_oy    = oy;
             }
