@@ -653,6 +653,14 @@ struct alignas(16) OkVec4 // 16-byte aligned load unit (ds_read_b128): two conse
 #define OKRC_WAIT_LDS() ((void)0)
 #endif
 
+// How many lanes of the wave, among those that execute this, satisfy `pred` (kVote walks): a ballot and a population count on the
+// GPU -- inside a divergent loop the ballot holds the lanes still in it.  On the host there is no wave: the caller's value stands.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define OKRC_WAVE_COUNT(pred, host_value) __builtin_popcountll(__builtin_amdgcn_ballot_w64(pred))
+#else
+#define OKRC_WAVE_COUNT(pred, host_value) (host_value)
+#endif
+
 // median of three; one v_med3_f32 on the GPU
 OKRC_HD float okMed3(const float a, const float b, const float c)
 {
@@ -728,7 +736,32 @@ OKRC_HD uint32_t okShiftInSign(const uint32_t acc, const float d)
 // what the steps-left counters decide (the box ends where the grid does: x1 = x0 + nx * cell in ok_grid.h), so t_out stays at the
 // sensor range and the walk leaves by code 3 where the clip would have ended it by code 1.  Same cells or a superset (where a few
 // ulps put the clip's t_out before the last cell's own exit), hence the same bits.  from_origin = false is the generic path.
-template <bool kCount, bool kAmb = false, bool kOrigin = false>
+//
+// kVote (> 0, the walk that STARTS a ray only): the wave ends the walk itself.  The lanes of a wave run the cell loop in lock
+// step, so its last iterations cost the wave what the first did while a handful of lanes still walk -- rays that whoever continues
+// them (the kernels' phase 2) would cut over all 64 lanes for almost nothing.  So at the end of every cell iteration the wave counts
+// the lanes that would go on plus the lanes that have left this walk inconclusively so far (leave == 2) -- which is the lanes that
+// entered the loop less those that have left it conclusively (codes 1 and 3), so one ballot per iteration keeps the count
+// (`vote_left`; inside the divergent loop only the lanes still walking execute, each of them has executed every earlier
+// iteration, so each one's copy is the wave's count; lanes that do not cast never enter).  When that count is at most
+// kVote, the rays that would have to be continued anyway plus these fit the continuation well, and every lane still walking takes
+// leave = 2: the existing "interval's end reached, not conclusive" exit with t_reached = t_exit, as if t_b had been this cell's
+// exit.  No new exit code and no new contract: a walk over [0, t_b] may end at ANY cell's exit already (whichever cell t_b falls
+// into), the cells up to t_reached are processed and a hit beyond it is only a candidate (min-combined by the caller).  The
+// continuation starts at t_reached with skip_unowned_start set, and that rule decides about the cell containing t_reached however
+// small t_reached is -- an origin right at a cell's border leaves its cell after a fraction of a pixel, or at t_exit = 0:
+//   * t_reached = 0 (the caller sets the flag for t_reached > 0 only): the continuation is a walk from the origin, start cell looked at;
+//   * the point at t_reached falls into the cell just left: the ray entered it at or before 0.  More than kOwnEps before t_reached:
+//     stepped over, rightly, this walk has processed it.  Otherwise (a t_reached below kOwnEps with the origin on the entry border
+//     as well, a corner) it is looked at a second time, which changes no bit;
+//   * it falls into a cell further on: the ray enters that one at t_reached to rounding, far less than kOwnEps before it: looked at.
+// The rule never steps over a cell the ray entered within kOwnEps of t_a, so a tiny t_reached can only make it look twice.
+// kVoteOnly: the vote alone ends the walk.  t_b is not looked at (callers pass +inf), so no lane leaves with code 2 before the
+// vote passes, nobody is ever pending and the count is simply the lanes that go on -- the mask the loop's own exit test forms.
+// With several agents in a wave the vote is the wave's, across agents, as the continuation's dealing is.  On the host the count comes
+// from the caller (OKRC_WAVE_COUNT): vote_host_cells = c > 0 stands for a wave whose other lanes keep the sum above kVote for
+// c - 1 iterations and are gone in the c-th, so the walk is cut after its c-th cell at the latest; 0: the vote never passes.
+template <bool kCount, bool kAmb = false, bool kOrigin = false, int kVote = 0, bool kVoteOnly = false>
 OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
                                                const float       ox,
                                                const float       oy,
@@ -742,7 +775,8 @@ OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
                                                unsigned long long *prof = nullptr,
                                                const bool        skip_unowned_start = false,
                                                const float       min_t0 = OK_SENSOR_RANGE,
-                                               const bool        from_origin = false)
+                                               const bool        from_origin = false,
+                                               const int         vote_host_cells = 0)
 {
     const OkGridGeom &g = v.g;
     OKRC_PROF_BEGIN();
@@ -825,7 +859,7 @@ OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
         cell_n = cell + (go_x ? lin_x : lin_y);                                                                        \
         cell_n = cell_n < 0 ? 0 : (cell_n > last_cell ? last_cell : cell_n);                                           \
         h_next = v.hdr[cell_n];                                                                                        \
-        leave  = (t_exit >= t_b) ? 2 : 0;                                                                              \
+        leave  = (!kVoteOnly && t_exit >= t_b) ? 2 : 0;                                                                \
         leave  = (left_x | left_y) >= 0 ? leave : 3; /* (beyond the grid there is nothing: conclusive whatever t_b) */  \
         leave  = (t_out <= t_exit) ? 1 : leave;                                                                        \
     } while (0)
@@ -859,6 +893,7 @@ OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
     OKRC_PROF(0);
     // The walk visits at most nx + ny cells: the explicit bound on cell steps makes termination unconditional.
     int guard = g.nx + g.ny + 2;
+    int vote_left = (kVote > 0 && !kVoteOnly) ? OKRC_WAVE_COUNT(true, kVote + 1) : 0; // kVote: lanes of the wave in this walk, less those that have left it conclusively
     while (true)
     {
         OkCellHdr hc = h_next;
@@ -924,6 +959,19 @@ OKRC_HD OkIntervalResult ok_cast_poly_interval(const OkPolyView &v,
         }
         // leave the cell
         leave = (min_t <= t_exit) ? 1 : leave; // first hit inside the covered part
+        if (kVote > 0 && kVoteOnly)
+        { // the wave's vote (see above), nobody pending: the lanes that would go on are the count -- the mask the loop's own exit
+          // test forms, so the vote costs a population count and a compare, and t_b's compare is gone
+          // (host: g.nx + g.ny + 3 - guard cells done so far; nobody else is left from the vote_host_cells-th on)
+            const int walking = OKRC_WAVE_COUNT(leave == 0, (vote_host_cells > 0 && g.nx + g.ny + 3 - guard >= vote_host_cells) ? 0 : kVote + 1);
+            leave             = (walking <= kVote && leave == 0) ? 2 : leave;
+        }
+        else if (kVote > 0)
+        { // ... with an interval's end as well.  Lanes that would go on + lanes that have left inconclusively = the lanes that
+          // entered less those that have left conclusively (codes 1 and 3: bit 0 of leave), so one ballot keeps the count
+            vote_left -= OKRC_WAVE_COUNT((leave & 1) != 0, (vote_host_cells > 0 && g.nx + g.ny + 3 - guard >= vote_host_cells) ? vote_left : 0);
+            leave = (vote_left <= kVote && leave == 0) ? 2 : leave;
+        }
         if (leave != 0 || --guard <= 0)
             break;
         cell   = cell_n;

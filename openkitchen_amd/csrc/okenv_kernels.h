@@ -1203,6 +1203,24 @@ __global__ void __launch_bounds__(1024) okStepKernel(const OkStepParams p)
 #define OKENV_PRIO_STEP 1
 #endif
 constexpr int kMaxSplit = OKENV_MAX_SPLIT; // intervals a pending ray is cut into at most
+// Phase 1 ends by the wave's vote (ok_raycast.h, kVote) once (lanes still walking + rays already pending) <= a threshold; 0: at its
+// range only.  Compile-time constants like OKENV_PRIO: the headline kernel has no register for another argument.  Results cannot
+// depend on them (where phase 1 ends only moves cells between the two phases).  Measured per fan width (docs/HISTORY.md section 48):
+//   one agent per wave (the kG == 64 forms)   the vote at 16 or the range, whichever comes first
+//   the other forms (several agents per wave)  the vote alone at 12: phase1_range > 0 then only says that there is a phase 1,
+//                                              the walk has no interval's end to compare with and no pending count to keep
+#if !defined(OKENV_VOTE)
+#define OKENV_VOTE 16
+#endif
+#if !defined(OKENV_VOTE_ONLY)
+#define OKENV_VOTE_ONLY 0
+#endif
+#if !defined(OKENV_VOTE_NARROW)
+#define OKENV_VOTE_NARROW 12
+#endif
+#if !defined(OKENV_VOTE_NARROW_ONLY)
+#define OKENV_VOTE_NARROW_ONLY 1
+#endif
 
 template <int kPolicy, bool kPacked = false, bool kResident = false, bool kDirect = false, int kG = 0, bool kDriver = false>
 __global__ void __launch_bounds__(1024) okStepCoopKernel(const OkStepParams p_in, const uint32_t off_coop, const float phase1_range)
@@ -1606,7 +1624,9 @@ __global__ void __launch_bounds__(1024) okStepCoopKernel(const OkStepParams p_in
                 // (every walking lane's origin inside the grid box -- one ballot, and with one agent per wave one origin: the walk
                 // starts in the origin's cell without the slab clip, ok_raycast.h)
                 const bool             in_box = __ballot(!okInsideBox(view.g, ox, oy)) == 0ULL;
-                const OkIntervalResult r1     = ok_cast_poly_interval<false, kAmbW, true>(view, ox, oy, rdx, rdy, 0.F, phase1_range, nullptr, nullptr, nullptr OK_WPROF(0),
+                constexpr int          kVote     = kG == 64 ? OKENV_VOTE : OKENV_VOTE_NARROW;
+                constexpr bool         kVoteOnly = kVote > 0 && (kG == 64 ? OKENV_VOTE_ONLY : OKENV_VOTE_NARROW_ONLY) != 0;
+                const OkIntervalResult r1     = ok_cast_poly_interval<false, kAmbW, true, kVote, kVoteOnly>(view, ox, oy, rdx, rdy, 0.F, kVoteOnly ? OKRC_INF : phase1_range, nullptr, nullptr, nullptr OK_WPROF(0),
                                                                                           false, OK_SENSOR_RANGE, in_box);
                 min_t      = r1.min_t;
                 unfinished = !r1.conclusive;
