@@ -1,7 +1,8 @@
 """Float64 mirror of the image transformer driver's rule (include/okenv_vit.h), in numpy: the same network on the same flat parameter
 vector, every sum in double precision and in numpy's order.  It pins WHAT is computed (parameter order, pre-norm, the qkv split, GELU,
 eps, the class token, the input's normalisation, the clamp); the fp32 summation orders are pinned by the device-against-host tests.
-Behind it a restatement of the device's LDS plan and workspace (openkitchen_amd/csrc/ok_vit.h)."""
+Behind it a restatement of the device's LDS plan, workspace and launch geometry (openkitchen_amd/csrc/ok_vit.h and the launches in
+okenv_capi.hip), and the path each of the later shapes exists for (PATHS)."""
 import math
 
 import numpy as np
@@ -15,11 +16,23 @@ SHAPES = {
     "long_rows": dict(image_size=224, patch=8, dim=16, heads=1, depth=1, dim_feedforward=16, head_hidden1=16, head_hidden2=16),  # T 785
     "reference_width": dict(image_size=32, patch=8, dim=384, heads=6, depth=1, dim_feedforward=1536, head_hidden1=128, head_hidden2=64),  # K 384, K 1536
     "reference_depth": dict(image_size=24, patch=8, dim=384, heads=6, depth=12, dim_feedforward=1536, head_hidden1=128, head_hidden2=64),  # 12 blocks, T 10
+    # the paths the seven above never select; what each one reaches is in PATHS below and asserted by the tests that use it
+    "dh32": dict(image_size=16, patch=8, dim=64, heads=2, depth=1, dim_feedforward=64, head_hidden1=16, head_hidden2=16),
+    "dh48": dict(image_size=16, patch=8, dim=96, heads=2, depth=2, dim_feedforward=48, head_hidden1=16, head_hidden2=16),
+    "patch16": dict(image_size=32, patch=16, dim=16, heads=1, depth=1, dim_feedforward=16, head_hidden1=16, head_hidden2=16),
+    "grid_2d": dict(image_size=32, patch=8, dim=80, heads=5, depth=2, dim_feedforward=208, head_hidden1=16, head_hidden2=16),
+    "wide_head": dict(image_size=16, patch=8, dim=16, heads=1, depth=1, dim_feedforward=16, head_hidden1=2048, head_hidden2=16),
+    "head2_wider": dict(image_size=16, patch=8, dim=32, heads=2, depth=1, dim_feedforward=32, head_hidden1=16, head_hidden2=48),
+    "most_tokens": dict(image_size=124, patch=4, dim=64, heads=1, depth=1, dim_feedforward=16, head_hidden1=16, head_hidden2=16),
 }
-TOKENS = {"tiny": 5, "ten_tokens": 10, "second_tile": 17, "patch4_dh64": 17, "long_rows": 785, "reference_width": 17, "reference_depth": 10}
+TOKENS = {"tiny": 5, "ten_tokens": 10, "second_tile": 17, "patch4_dh64": 17, "long_rows": 785, "reference_width": 17, "reference_depth": 10,
+          "dh32": 5, "dh48": 5, "patch16": 5, "grid_2d": 17, "wide_head": 5, "head2_wider": 5, "most_tokens": 962}
+NEW_SHAPES = ("dh32", "dh48", "patch16", "grid_2d", "wide_head", "head2_wider", "most_tokens")
 
 # ok_vit.h's constants
 QUERIES, AGENTS, PAD, TILE, KBLOCK = 16, 16, 4, 64, 16
+THREADS, LANES = 256, 8       # kVitThreads; OK_ACTOR_LANES: the lanes of a LayerNorm row
+NORM_ROWS = THREADS // LANES  # kVitNormRows: the rows of a workgroup of okVitNormKernel and okVitEmbedKernel
 LDS_BUDGET = 160 * 1024
 DEFAULT_WORKSPACE = 1 << 30
 
@@ -53,6 +66,53 @@ def lds_bytes(s):
     attend = QUERIES * (s["dim"] // s["heads"] + PAD + Tp + PAD)
     final = AGENTS * (s["dim"] + s["head_hidden1"] + s["head_hidden2"] + 3 * PAD)
     return 4 * max(attend, final, 2 * TILE * (KBLOCK + 4))
+
+
+def linear_launch(rows, K, N):
+    """One launch of okVitLinearKernel (vitLinear) of rows x K by K x N: its grid of 64 x 64 tiles, the ctiles of every column workgroup,
+    the rows of the last row workgroup and how many of its four waves hold a row."""
+    gx, gy = -(-rows // TILE), -(-N // TILE)
+    last_rows = rows - (gx - 1) * TILE
+    return dict(K=K, grid=(gx, gy), ctiles=[min(TILE // 16, (N - y * TILE) // 16) for y in range(gy)], last_rows=last_rows, last_live_waves=-(-last_rows // 16))
+
+
+def geometry(s, count):
+    """The launch geometry of one pass of `count` agents (vitBackbone, vitAct and vitEmbed in okenv_capi.hip) restated: every linear
+    launch, the attention launch's workgroups, its dynamic LDS and the waves of its context phase, the workgroups of the norm, final
+    and embed kernels and the final kernel's dynamic LDS."""
+    T, D, F = tokens(s), s["dim"], s["dim_feedforward"]
+    dh, M = D // s["heads"], count * T
+    return dict(patch=linear_launch(count * (T - 1), 3 * s["patch"] ** 2, D), qkv=linear_launch(M, D, 3 * D), proj=linear_launch(M, D, D),
+                fc1=linear_launch(M, D, F), fc2=linear_launch(M, F, D),
+                attend_blocks=count * s["heads"] * (-(-T // QUERIES)), attend_lds=4 * QUERIES * (dh + PAD + -(-T // 16) * 16 + PAD), context_waves=dh // 16,
+                norm_blocks=-(-M // NORM_ROWS), final_blocks=-(-count // AGENTS), embed_blocks=-(-count // NORM_ROWS),
+                final_lds=4 * AGENTS * (D + s["head_hidden1"] + s["head_hidden2"] + 3 * PAD), final_last_agents=count - (-(-count // AGENTS) - 1) * AGENTS)
+
+
+LINEARS = ("patch", "qkv", "proj", "fc1", "fc2")
+# name: (the agents of the act case, the path the shape exists for as a predicate on (shape, geometry(shape, agents)))
+PATHS = {
+    "dh32": (2, lambda s, g: g["context_waves"] == 2 and s["heads"] == 2),  # the context on two waves, the second head starts at column 32
+    "dh48": (2, lambda s, g: g["context_waves"] == 3 and s["heads"] == 2 and s["dim_feedforward"] < s["dim"]),  # three waves, a head at column 48
+    # K 768 of the patch embedding's launch, the decode at P 16.  (geometry's K is held to the code elsewhere: test_launch_geometry_restated
+    # has it equal the parameter layout's weight shape, test_plan_restated pins ok_vit_patch_k and the K vitBackbone passes to the source.)
+    "patch16": (2, lambda s, g: s["patch"] == 16 and g["patch"]["K"] == 768),
+    # several workgroups in x and in y in every linear launch; a short last column workgroup behind full ones; a last row workgroup of
+    # 25 rows: wave 0 full, wave 1 partial, waves 2 and 3 dead
+    "grid_2d": (9, lambda s, g: all(min(g[k]["grid"]) > 1 for k in LINEARS) and g["patch"]["grid"] == (3, 2) and g["qkv"]["grid"] == (3, 4)
+                and g["qkv"]["ctiles"] == [4, 4, 4, 3] and g["fc1"]["ctiles"] == [4, 4, 4, 1] and g["proj"]["ctiles"] == g["fc2"]["ctiles"] == [4, 1]
+                and g["qkv"]["last_rows"] == 25 and g["qkv"]["last_live_waves"] == 2),
+    # okLidarLinear over 128 column tiles from the final kernel, its LDS the shape's largest; two workgroups, the second with one agent
+    "wide_head": (17, lambda s, g: s["head_hidden1"] == 2048 and g["final_lds"] == lds_bytes(s) == 133888 and g["final_blocks"] == 2 and g["final_last_agents"] == 1),
+    "head2_wider": (2, lambda s, g: s["head_hidden2"] > s["head_hidden1"]),
+    "most_tokens": (1, lambda s, g: g["attend_lds"] == lds_bytes(s) == 67072 > 65536 and g["context_waves"] == 4),  # above 64 KB of dynamic LDS
+}
+
+
+def reaches(name, agents=None):
+    """The shape's predicate at its case's population (or at `agents`)."""
+    n, path = PATHS[name]
+    return path(SHAPES[name], geometry(SHAPES[name], n if agents is None else agents))
 
 
 def agent_floats(s):

@@ -7,7 +7,10 @@ import numpy as np
 f32, f64 = np.float32, np.float64
 U = 2.0 ** -24
 CHUNK = 64
-SHAPES = [(16, 16, 16), (48, 32, 16), (384, 128, 64)]  # (D, H1, H2): the smallest; a partial 64-column block; the reference
+# (D, H1, H2): the smallest; a partial 64-column block; the reference; H2 > H1: a d1 chain longer than its row and more column tiles in
+# layer 3 than in layer 2; the widest layer the LDS takes: 8 strides of the forward kernel's row loops, 387 gradient units; the widest
+# embedding: 49 column tiles of layer 1.  ((16, 16, 2048) needs 265 KB of LDS and is refused.)
+SHAPES = [(16, 16, 16), (48, 32, 16), (384, 128, 64), (32, 16, 48), (16, 2048, 16), (768, 16, 16)]
 LDS_BUDGET = 160 * 1024
 
 
@@ -174,7 +177,9 @@ GEOMETRIES = [("less_than_a_tile", 13, 5, 1, False),  # B no multiple of 4, last
               ("second_chunk_of_one", 65, 65, 1, False),
               ("reference_batch", 600, 512, 1, False),  # a partial minibatch of 88: one full chunk and 24 positions
               ("batch_beyond_M", 13, 20, 1, False),
-              ("two_epochs_permuted", 13, 5, 2, True)]  # an order with a repeated and an out-of-range index
+              ("two_epochs_permuted", 13, 5, 2, True),  # an order with a repeated and an out-of-range index
+              ("whole_chunk_then_one", 65, 64, 1, False),  # a minibatch of exactly one chunk (no filler term), then one of a single position
+              ("permuted_across_chunks", 150, 70, 2, True)]  # minibatches of 70, 70 and 10: the order read past a chunk and in later minibatches
 
 
 def random_head(shape, rng, scale=1.0):

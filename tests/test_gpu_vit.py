@@ -1,8 +1,8 @@
 """The image transformer driver on the device (okenv_vit_*; openkitchen_amd/csrc/ok_vit.h): the attention kernel alone and the whole
 act bit-equal to the host entries that share their rule, at every shape of tests/_vit_numpy.py, on frames the camera rendered and on
 random bytes, with crashed agents among them; populations that fill less than a row tile, share a tile between agents and take several
-passes; parameters from host and device pointers; the order of calls and the refusals; step + camera + act captured in a graph; the
-output against the PyTorch module."""
+passes; the paths a shape and a pass select in the launch geometry (mirror.PATHS, mirror.geometry); parameters from host and device
+pointers; the order of calls and the refusals; step + camera + act captured in a graph; the output against the PyTorch module."""
 import ctypes as C
 
 import numpy as np
@@ -25,14 +25,11 @@ SHAPE_LIMITS = ("shape outside the limits (patch 4, 8 or 16; image_size a multip
                 "to 2048)")
 
 
-@pytest.mark.parametrize("dh", [16, 64])
-@pytest.mark.parametrize("T", [1, 15, 16, 17, 785])
-def test_attend_device_equals_host(gpu, T, dh):
-    """One key; one short of a tile; a tile; one key and one query past it; the reference's row of 49 key tiles and one key.  Two heads
-    and two sequences, uniform data and scores spread over 2^+-20, where most of a softmax row underflows."""
+def attend_case(gpu, T, dh, heads, seqs):
+    """Uniform data and scores spread over 2^+-20, where most of a softmax row underflows: the device against the host entry bit for
+    bit, the host entry against the float64 mirror."""
     capi = gpu.capi
     rng = np.random.default_rng(1000 * T + dh)
-    heads, seqs = 2, 2
     uniform = rng.uniform(-1.0, 1.0, (seqs, T, 3 * heads * dh)).astype(f32)
     spread = uniform.copy()
     spread[..., :2 * heads * dh] *= np.exp2(rng.uniform(-20.0, 20.0, (seqs, T, 1))).astype(f32)  # q and k rows scaled, v as it was
@@ -49,12 +46,32 @@ def test_attend_device_equals_host(gpu, T, dh):
         assert float((under > 0.5).mean()) > 0.25
 
 
+@pytest.mark.parametrize("dh", [16, 64])
+@pytest.mark.parametrize("T", [1, 15, 16, 17, 785])
+def test_attend_device_equals_host(gpu, T, dh):
+    """One key; one short of a tile; a tile; one key and one query past it; the reference's row of 49 key tiles and one key.  Two heads
+    and two sequences."""
+    attend_case(gpu, T, dh, 2, 2)
+
+
+@pytest.mark.parametrize("T,dh,heads,seqs", [(17, 32, 3, 3), (40, 48, 3, 3), (1024, 64, 1, 1), (1009, 48, 1, 1)])
+def test_attend_device_equals_host_other_heads(gpu, T, dh, heads, seqs):
+    """The context phase on two and on three waves, heads that start at multiples of 32 and of 48, score chains of two and three
+    groups, the unit decode with three heads and three sequences of two and three query tiles; the largest plan (64 key tiles, no dead
+    key, 16 x (68 + 1028) x 4 = 70 144 B of LDS); 1009 keys at dh 48: 15 dead keys in the last tile."""
+    dead = -(-T // 16) * 16 - T
+    assert (dh // 16, dead) == {17: (2, 15), 40: (3, 8), 1024: (4, 0), 1009: (3, 15)}[T]
+    assert 4 * mirror.QUERIES * (dh + T + dead + 2 * mirror.PAD) <= mirror.LDS_BUDGET
+    attend_case(gpu, T, dh, heads, seqs)
+
+
 def act_case(gpu, name, N, agents_per_pass=0, lifecycle=False):
     capi = gpu.capi
     shape = mirror.SHAPES[name]
     cfg = capi.vit_config(throttle=80.0, steer_scale=7.0, agents_per_pass=agents_per_pass, **shape)
     S, D = shape["image_size"], shape["dim"]
     assert capi.vit_tokens(cfg) == mirror.TOKENS[name] and capi.vit_lds_bytes(cfg) == mirror.lds_bytes(shape) <= capi.VIT_LDS_BUDGET
+    assert (name in mirror.PATHS) == (name in mirror.NEW_SHAPES) and (name not in mirror.PATHS or (mirror.PATHS[name][0] == N and mirror.reaches(name))), name
     params = mirror.random_params(capi, cfg, np.random.default_rng(N), scale=2.0)
     venv = driven_population(gpu, N, S)
     dev, L, h = venv.env, venv.env._L, venv.env._h
@@ -192,9 +209,32 @@ def test_act_device_equals_host_in_three_passes(gpu):
     act_case(gpu, "tiny", 5, agents_per_pass=2)
 
 
-@pytest.mark.parametrize("name", [n for n in mirror.SHAPES if n != "tiny"])
+@pytest.mark.parametrize("N,per_pass", [(40, 24), (41, 20)])
+def test_act_device_equals_host_in_later_passes(gpu, N, per_pass):
+    """40 agents in passes of 24: the first pass has a full and a half workgroup of the final kernel, the second starts at a0 = 24 with
+    one full workgroup.  41 in passes of 20: the second pass starts at a0 = 20 and has a second workgroup itself, which reads the
+    pass's rows from b0 = 16 on and stores at a0 + b0; the third is a single agent at a0 = 40."""
+    shape = mirror.SHAPES["tiny"]
+    assert mirror.agents_per_pass(shape, N, per_pass) == per_pass
+    blocks = [mirror.geometry(shape, min(per_pass, N - a0))["final_blocks"] for a0 in range(0, N, per_pass)]
+    assert blocks == {(40, 24): [2, 1], (41, 20): [2, 2, 1]}[N, per_pass]
+    act_case(gpu, "tiny", N, agents_per_pass=per_pass)
+
+
+@pytest.mark.parametrize("name", [n for n in mirror.SHAPES if n != "tiny" and n not in mirror.NEW_SHAPES])
 def test_act_device_equals_host_other_shapes(gpu, name):
     act_case(gpu, name, 2)
+
+
+@pytest.mark.parametrize("name", mirror.NEW_SHAPES)
+def test_act_device_equals_host_paths(gpu, name):
+    """The shapes that select what the seven above never do (mirror.PATHS names it and the population it needs, act_case asserts it
+    first): the context phase on two and three waves; patch 16; every linear launch with several workgroups in x and y, short last
+    column workgroups and dead upper waves; the head 2048 wide at 17 agents; a second hidden layer wider than the first; the attention
+    kernel launched from the act above 64 KB of dynamic LDS."""
+    if name == "most_tokens":
+        assert mirror.geometry(mirror.SHAPES[name], 1)["attend_lds"] > 65536
+    act_case(gpu, name, mirror.PATHS[name][0])
 
 
 def test_workspace_bytes_sets_the_pass(gpu):

@@ -1,7 +1,8 @@
 """The image transformer driver's training on the device (okenv_vit_embed, okenv_vit_head_*; openkitchen_amd/csrc/ok_vithead.h): the
 head's update and eval bit-equal to the host entries that share their rule at every head shape and launch geometry of
-tests/_vithead_numpy.py, the embed against the host act's embedding over several passes and a partial one, the act after an update, the
-order of calls, and a second okenv_vit_create dropping the learner."""
+tests/_vithead_numpy.py, the embed against the host act's embedding over several passes and a partial one and in passes of a whole
+population (one, two and three workgroups of its last kernel), the act after an update, the order of calls, and a second
+okenv_vit_create dropping the learner."""
 import ctypes as C
 
 import numpy as np
@@ -67,9 +68,9 @@ def test_update_and_eval_equal_the_host_entries(gpu, shape, geometry):
         assert same(before.cpu().numpy()[:1], out["loss"][:1])
 
 
-def embed_case(gpu, N=3, agents_per_pass=2):
+def embed_case(gpu, N=3, agents_per_pass=2, name="tiny"):
     capi = gpu.capi
-    shape = V_.SHAPES["tiny"]
+    shape = V_.SHAPES[name]
     cfg = capi.vit_config(agents_per_pass=agents_per_pass, **shape)
     venv = driven_population(gpu, N, shape["image_size"])
     params = V_.random_params(capi, cfg, np.random.default_rng(N), scale=2.0)
@@ -102,6 +103,42 @@ def test_embed_equals_the_host_over_several_passes(gpu):
     venv.vit_act(rec, frames=frames)
     assert same(venv.vit_embed(frames).cpu().numpy(), rec["embedding"].cpu().numpy())
     assert float(venv.throttle.min()) == cfg.throttle  # (the act did write them)
+
+
+@pytest.mark.parametrize("name,N,ms", [("tiny", 40, (1, 31, 32, 33, 40, 41, 100)), ("ten_tokens", 35, (71,)), ("tiny", 70, (65, 70))],
+                         ids=["tiny-40", "ten_tokens-35", "tiny-70"])
+def test_embed_equals_the_host_in_passes_of_the_population(gpu, name, N, ms):
+    """The default pass holds the whole population.  tiny at 40 agents: m = 1 and 31 fill part of okVitEmbedKernel's first workgroup,
+    32 all of it, 33 and 40 a second one (one row; a wave of eight), 41 is a pass of 40 and one of 1, 100 two of 40 and one of 20.
+    ten_tokens at 35 agents, two blocks: m = 71 is passes of 35, 35 and 1.  tiny at 70 agents: m = 65 and 70 reach a third workgroup,
+    the first whose rows no other workgroup's stride could cover (one row; six)."""
+    capi = gpu.capi
+    venv, cfg, params = embed_case(gpu, N, 0, name)
+    S, D = cfg.image_size, cfg.dim
+    shape = V_.SHAPES[name]
+    assert V_.agents_per_pass(shape, N) == N
+    counts = {m: [min(N, m - a0) for a0 in range(0, m, N)] for m in ms}
+    blocks = {m: [V_.geometry(shape, c)["embed_blocks"] for c in counts[m]] for m in ms}
+    if N == 40:
+        assert [counts[m] for m in ms] == [[1], [31], [32], [33], [40], [40, 1], [40, 40, 20]]
+        assert [blocks[m] for m in ms] == [[1], [1], [1], [2], [2], [2, 1], [2, 2, 1]]
+    elif N == 70:
+        assert [counts[m] for m in ms] == [[65], [70]] and [blocks[m] for m in ms] == [[3], [3]]
+    else:
+        assert counts[71] == [35, 35, 1] and blocks[71] == [2, 2, 1] and cfg.depth == 2
+    venv.enable_vit_policy(cfg, params)
+    torch.manual_seed(N)
+    for m in ms:
+        frames = torch.randint(0, 256, (m, S, S, 4), dtype=torch.uint8, device="cuda")
+        out = torch.full((m + 1, D), -7.0, device="cuda")
+        got = venv.vit_embed(frames, out=out[:m])
+        torch.cuda.synchronize()
+        want = capi.vit_act_host(cfg, params, frames.cpu().numpy())["embedding"]
+        got = got.cpu().numpy()
+        assert same(got, want), "m %d: %d of %d rows differ, the first %d" % (m, int((got != want).any(axis=1).sum()), m, int((got != want).any(axis=1).argmax()))
+        assert float(out[m].min()) == float(out[m].max()) == -7.0 and np.isfinite(want).all() and np.abs(want).max() > 0
+        assert len({row.tobytes() for row in want}) == m  # (every frame has an embedding of its own: a row taken from another frame shows)
+    venv.close()
 
 
 def test_act_after_update_acts_with_the_new_head(gpu):

@@ -26,6 +26,14 @@ HOST_MEASURED = {
     "long_rows": (4.405e-07, 3.898e-08),
     "reference_width": (2.097e-06, 1.319e-07),
     "reference_depth": (3.233e-06, 7.693e-08),
+    # the shapes of mirror.PATHS, by the same recipe
+    "dh32": (6.884e-07, 2.470e-08),
+    "dh48": (8.904e-07, 3.398e-08),
+    "patch16": (4.856e-07, 3.358e-08),
+    "grid_2d": (9.732e-07, 7.990e-08),
+    "wide_head": (4.631e-07, 1.183e-07),
+    "head2_wider": (5.137e-07, 2.672e-08),
+    "most_tokens": (5.110e-07, 1.229e-08),
 }
 
 
@@ -64,7 +72,7 @@ def test_mirror_equals_dino_vit(capi, name):
 def test_host_entry_against_the_mirror(capi, name):
     shape = mirror.SHAPES[name]
     cfg = capi.vit_config(**shape)
-    assert capi.vit_tokens(cfg) == mirror.TOKENS[name]
+    assert capi.vit_tokens(cfg) == mirror.TOKENS[name] and (name in mirror.PATHS) == (name in mirror.NEW_SHAPES) and (name not in mirror.PATHS or mirror.reaches(name))
     worst_emb = worst_out = 0.0
     for seed in range(4):
         rng = np.random.default_rng(seed)
@@ -204,17 +212,90 @@ def test_plan_restated(capi):
     constant = lambda name: int(re.search(r"constexpr int %s\s*=\s*(\d+);" % name, kernel).group(1))  # noqa: E731
     assert (constant("kVitTile"), constant("kVitKBlock"), constant("kVitQueries"), constant("kVitAgents")) == (mirror.TILE, mirror.KBLOCK, mirror.QUERIES, mirror.AGENTS)
     assert "kVitDefaultWorkspace = static_cast<size_t>(1) << 30" in kernel
+    # ... and the launch geometry's: 256 threads, 8 lanes a LayerNorm row, so 32 rows a workgroup of the norm and embed kernels
+    math_h = open(os.path.join(ROOT, "include", "okenv_math.h")).read()
+    assert constant("kVitThreads") == mirror.THREADS and int(re.search(r"#define OK_ACTOR_LANES\s+(\d+)", math_h).group(1)) == mirror.LANES
+    assert "constexpr int kVitNormRows = kVitThreads / OK_ACTOR_LANES;" in kernel and mirror.NORM_ROWS == mirror.THREADS // mirror.LANES == 32
+    head = open(os.path.join(ROOT, "openkitchen_amd", "csrc", "ok_vithead.h")).read()
+    assert "r_raw = static_cast<long>(blockIdx.x) * kVitNormRows + static_cast<int>(threadIdx.x) / OK_ACTOR_LANES;" in head
+    # ... and what mirror.geometry restates of the launches themselves: every grid, the rows, K and columns of the five linear launches,
+    # the ctiles of a column workgroup, the waves of the context phase, the K of the patch embedding
+    launches = " ".join(open(os.path.join(ROOT, "openkitchen_amd", "csrc", "okenv_capi.hip")).read().split())
+    u = "dim3(static_cast<unsigned>(%s))"
+    for text in ("(okVitLinearKernel<kSrc, kEpi>), dim3(static_cast<unsigned>((M + kVitTile - 1) / kVitTile), static_cast<unsigned>((N + kVitTile - 1) / kVitTile)), "
+                 "dim3(kVitThreads), 0,",
+                 "const long M = static_cast<long>(count) * T;",
+                 "const unsigned norm_blocks = static_cast<unsigned>((M + kVitNormRows - 1) / kVitNormRows);",
+                 "okVitNormKernel, dim3(norm_blocks), dim3(kVitThreads), 0,",
+                 "ap.qtiles = (T + kVitQueries - 1) / kVitQueries;",
+                 "okVitAttendKernel, " + u % "count * s.heads * ap.qtiles" + ", dim3(kVitThreads), sizeof(float) * static_cast<size_t>(pl.attend),",
+                 "okVitEmbedKernel, " + u % "(count + kVitNormRows - 1) / kVitNormRows" + ", dim3(kVitThreads), 0,",
+                 "okVitFinalKernel, " + u % "(count + kVitAgents - 1) / kVitAgents" + ", dim3(kLidarThreads), sizeof(float) * static_cast<size_t>(pl.final),",
+                 "vitLinear<kVitSrcPatch, kVitEpiPos>(h, lp, static_cast<long>(count) * (T - 1), ok_vit_patch_k(s), D,",
+                 "vitLinear<kVitSrcPlain, kVitEpiNone>(h, lp, M, D, 3 * D,",
+                 "vitLinear<kVitSrcPlain, kVitEpiResidual>(h, lp, M, D, D,",
+                 "vitLinear<kVitSrcPlain, kVitEpiGelu>(h, lp, M, D, F,",
+                 "vitLinear<kVitSrcPlain, kVitEpiResidual>(h, lp, M, F, D,"):
+        assert text in launches, text
+    assert "const int ctiles = okLidarMin(kVitTile / 16, (p.N - n0) >> 4);" in " ".join(kernel.split()) and "if (wave < dh / 16)" in kernel
+    rule = " ".join(open(os.path.join(ROOT, "include", "okenv_vit.h")).read().split())
+    assert "OK_HDI int ok_vit_patch_k(const ok_vit_shape s) { return 3 * s.P * s.P; }" in rule
+
+
+# (rows of an agent, K, columns) of the five linear launches, from the parameter layout's own weight shapes (columns x K)
+LINEAR_WEIGHTS = {"patch": "patch_embed.proj.weight", "qkv": "blocks.0.attn.qkv.weight", "proj": "blocks.0.attn.proj.weight", "fc1": "blocks.0.mlp.fc1.weight",
+                  "fc2": "blocks.0.mlp.fc2.weight"}
+LINEAR_SIZES = {"patch": lambda T, D, F: (T - 1, D), "qkv": lambda T, D, F: (T, 3 * D), "proj": lambda T, D, F: (T, D), "fc1": lambda T, D, F: (T, F),
+                "fc2": lambda T, D, F: (T, D)}
+
+
+@pytest.mark.parametrize("name", list(mirror.SHAPES))
+def test_launch_geometry_restated(capi, name):
+    """mirror.geometry at every shape of the table: the LDS plan against okenv_vit_lds_bytes, the grids against a count of the tiles
+    one by one, the figures the shapes were chosen for, and each new shape's predicate."""
+    shape = mirror.SHAPES[name]
+    T, D, F = mirror.tokens(shape), shape["dim"], shape["dim_feedforward"]
+    assert not mirror.shape_bad(shape) and T == mirror.TOKENS[name]
+    weights = {n: w for n, _, w in capi.vit_layout(capi.vit_config(**shape))}
+    for agents in (1, 2, 9, 17, 33, 40):
+        g = mirror.geometry(shape, agents)
+        assert capi.vit_lds_bytes(capi.vit_config(**shape)) == mirror.lds_bytes(shape) == max(g["attend_lds"], g["final_lds"], 10240)
+        for k in mirror.LINEARS:
+            rows, N = LINEAR_SIZES[k](T, D, F)
+            rows *= agents
+            assert (N, g[k]["K"]) == (weights[LINEAR_WEIGHTS[k]][0], int(np.prod(weights[LINEAR_WEIGHTS[k]][1:])))
+            tiles = {(m // 64, n // 64) for m in range(0, rows, 16) for n in range(0, N, 16)}  # the workgroup of every 16 x 16 tile of the output
+            assert g[k]["grid"] == (max(x for x, _ in tiles) + 1, max(y for _, y in tiles) + 1)
+            assert g[k]["ctiles"] == [sum(1 for n in range(0, N, 16) if n // 64 == y) for y in range(g[k]["grid"][1])]
+            assert g[k]["last_rows"] == sum(1 for m in range(rows) if m // 64 == g[k]["grid"][0] - 1) and g[k]["last_live_waves"] == -(-g[k]["last_rows"] // 16)
+        assert g["attend_blocks"] == agents * shape["heads"] * len(range(0, T, 16)) and g["context_waves"] * 16 * shape["heads"] == D
+        assert g["norm_blocks"] == len(range(0, agents * T, 32)) and g["final_blocks"] == len(range(0, agents, 16)) and g["embed_blocks"] == len(range(0, agents, 32))
+        assert g["final_last_agents"] == len(range(range(0, agents, 16)[-1], agents))  # the agents from the last workgroup's first on
+    assert (name in mirror.PATHS) == (name in mirror.NEW_SHAPES)
+    if name in mirror.PATHS:
+        assert mirror.reaches(name), name
+        assert mirror.lds_bytes(shape) == {"wide_head": 133888, "most_tokens": 67072}.get(name, 10240)
+    if name == "grid_2d":
+        g = mirror.geometry(shape, 9)
+        assert 9 * (T - 1) == 144 and g["patch"]["grid"][0] == 3 and 9 * T == 153 and g["qkv"]["grid"][0] == 3 and g["qkv"]["last_rows"] == 25
+        assert (g["proj"]["ctiles"], g["qkv"]["ctiles"], g["fc1"]["ctiles"]) == ([4, 1], [4, 4, 4, 3], [4, 4, 4, 1])
+    if name == "wide_head":
+        g = mirror.geometry(shape, 17)
+        assert g["final_blocks"] == 2 and g["final_last_agents"] == 17 - (g["final_blocks"] - 1) * mirror.AGENTS == 1
+    if name == "reference_width":  # several column workgroups on 34 rows: one row workgroup, which is why grid_2d exists
+        assert mirror.geometry(shape, 2)["qkv"]["grid"] == (1, 18)
 
 
 def test_host_forward_stays_inside_its_work_space(tmp_path):
     """The host forward as a stand-alone program under AddressSanitizer and UBSan (tests/cpp/vit_host_check.cpp), on parameters, a frame
     and a work space of exactly the counted sizes: the small shapes of the table and corners of the limits -- a feed-forward narrower
     than the width, one token besides the class token, the widest head."""
+    assert mirror.reaches("dh48") and mirror.reaches("patch16")  # (a feed-forward narrower than the width; K 768 of the patch embedding)
     exe = str(tmp_path / "vit_host_check")
     subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
                     "-g", "-O1", "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tests", "cpp", "vit_host_check.cpp")], check=True)
     keys = ("image_size", "patch", "dim", "heads", "depth", "dim_feedforward", "head_hidden1", "head_hidden2")
-    shapes = [tuple(mirror.SHAPES[name][k] for k in keys) for name in ("tiny", "ten_tokens", "second_tile", "patch4_dh64")]
+    shapes = [tuple(mirror.SHAPES[name][k] for k in keys) for name in ("tiny", "ten_tokens", "second_tile", "patch4_dh64", "dh48", "patch16")]
     shapes += [(16, 16, 64, 4, 2, 16, 16, 2048), (4, 4, 16, 1, 1, 64, 2048, 16), (48, 16, 128, 2, 1, 48, 32, 32)]
     assert any(ff < D for S, P, D, heads, depth, ff, h1, h2 in shapes)
     r = subprocess.run([exe] + [str(v) for shape in shapes for v in shape], capture_output=True, text=True, timeout=600,
