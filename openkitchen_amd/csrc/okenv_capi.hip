@@ -407,6 +407,13 @@ struct OkUpdateScratch
     OkEventLog log;
 };
 
+// A device buffer of the handle that grows and never shrinks (growBuffers): the pointer and its room in floats
+struct OkBuffer
+{
+    float *d{nullptr};
+    size_t cap{0};
+};
+
 // What a family that attaches a network keeps in the handle beside its configuration ("The drivers' life cycle on the host"):
 // the shared entries reach it through the family's DriverKind
 struct OkDriver
@@ -577,8 +584,8 @@ struct okenv
     okenv_gcl_config        gcl{};
     okenv_learner_params    gcl_learner{}, gcl_cost_learner{};
     int64_t                 gcl_t{0}, gcl_cost_t{0};
-    float                  *d_gcl_bank{nullptr}; // [state rows | action rows]
-    int32_t                 gcl_bank_rows{0}, gcl_bank_cap{0};
+    OkBuffer                gcl_bank; // [state rows | action rows]
+    int32_t                 gcl_bank_rows{0};
     OkUpdateScratch         gcl_scratch[3], gcl_adv_scratch;
     // Lidar transformer driver (okenv_lidar_create): the parameter vector in torch's order with the positional table behind it
     OkDriver                lidar_drv;
@@ -590,34 +597,30 @@ struct okenv
     // and the two layers' outputs that pass through global memory, all allocated at create
     OkDriver                bev_drv;
     okenv_bev_config        bev{};
-    float                  *d_bev_pack{nullptr}, *d_bev_act1{nullptr}, *d_bev_act2{nullptr};
-    size_t                  bev_pack_cap{0}, bev_act1_cap{0}, bev_act2_cap{0};
+    OkBuffer                bev_pack, bev_act1, bev_act2;
     // Behavioural-cloning image policy (okenv_cnn_create): the parameter vector in torch's order; the kernels' copy of the weights and
     // the features that pass from the conv kernel to the head, both allocated at create
     OkDriver                cnn_drv;
     okenv_cnn_config        cnn{};
-    float                  *d_cnn_pack{nullptr}, *d_cnn_feat{nullptr};
-    size_t                  cnn_pack_cap{0}, cnn_feat_cap{0};
+    OkBuffer                cnn_pack, cnn_feat;
     // World-model racers (okenv_world_create): the encoder vector in torch's order in world_drv.d; one workspace for everything else
     // (okWorldPlaces: packed weights, controllers, activations, partial latents, fitness, list), allocated at create; the lane widths
     OkDriver                world_drv;
     okenv_world_config      world{};
-    float                  *d_world_ws{nullptr}, *d_world_widths{nullptr};
-    size_t                  world_ws_cap{0};
+    OkBuffer                world_ws;
+    float                  *d_world_widths{nullptr};
     bool                    world_widths{false};
     // The racers' memory (okenv_memory_create): the network vector in torch's order in mem_drv.d; one workspace for everything else
     // (okMemoryPlaces: packed matrices, controllers, mu, x0 and the two hidden buffers), allocated at create
     OkDriver                mem_drv;
     okenv_memory_config     mem{};
-    float                  *d_mem_ws{nullptr};
-    size_t                  mem_ws_cap{0};
+    OkBuffer                mem_ws;
     // Deep-Q image racers (okenv_qcnn_create, okenv_qcnn_ring_create): the parameter vector in torch's order; the kernels' copy of the
     // weights and the features that pass from the conv kernel to the head, both allocated at create; the frame ring (its planes have
     // the network's image_size) and the push's slot of every agent
     OkDriver                qcnn_drv;
     okenv_qcnn_config       qcnn{};
-    float                  *d_qcnn_pack{nullptr}, *d_qcnn_feat{nullptr};
-    size_t                  qcnn_pack_cap{0}, qcnn_feat_cap{0};
+    OkBuffer                qcnn_pack, qcnn_feat;
     OkRing                  qcnn_ring{sizeof(int64_t)};
     int32_t                 qcnn_ring_side{0};
     long long              *d_qcnn_slots{nullptr};
@@ -625,15 +628,14 @@ struct okenv
     // (vit_pass of them), allocated at create
     OkDriver                vit_drv;
     okenv_vit_config        vit{};
-    float                  *d_vit_work{nullptr};
-    size_t                  vit_work_cap{0}, vit_pass{0};
+    OkBuffer                vit_work;
+    size_t                  vit_pass{0};
     // ... and its head's learner (okenv_vit_head_learner_create): Adam's moments [m | v] of the head's parameters, the step number, the
     // scratch of a minibatch's rows
     bool                    vit_head_ok{false};
     okenv_vit_head_params   vit_head{};
     int64_t                 vit_head_t{0};
-    float                  *d_vit_head_mv{nullptr};
-    size_t                  vit_head_cap{0};
+    OkBuffer                vit_head_mv;
     OkUpdateScratch         vit_head_scratch;
 };
 
@@ -1273,7 +1275,7 @@ OkFresh fresh(T *&slot, const size_t count)
     return OkFresh{reinterpret_cast<void **>(&slot), std::max<size_t>(count, 1) * sizeof(T)};
 }
 
-int regrow(okenv *h, const std::initializer_list<OkFresh> buffers)
+int regrow(okenv *h, const std::vector<OkFresh> &buffers)
 {
     OK_HIP(h, hipStreamSynchronize(h->stream));
     for (const OkFresh &b : buffers)
@@ -1290,6 +1292,40 @@ int regrow(okenv *h, const std::initializer_list<OkFresh> buffers)
             return rc;
         *b.slot = p;
     }
+    return OKENV_OK;
+}
+
+// Buffers of the handle that grow and never shrink (OkBuffer; a driver's vector), brought to what a call needs.  Nothing happens when
+// every need fits its room.  Otherwise all of them are replaced through regrow -- its wait for the stream, its zeroed memory -- each
+// with the larger of its need and its room; the rooms are zero while the allocation is under way, so that a failed one leaves none.
+struct OkGrow
+{
+    float **slot;
+    size_t *cap;
+    size_t  need; // floats
+};
+
+OkGrow grown(OkBuffer &b, const size_t need)
+{
+    return OkGrow{&b.d, &b.cap, need};
+}
+
+int growBuffers(okenv *h, const std::initializer_list<OkGrow> buffers)
+{
+    if (std::all_of(buffers.begin(), buffers.end(), [](const OkGrow &b) { return b.need <= *b.cap; }))
+        return OKENV_OK;
+    std::vector<OkGrow>  all(buffers);
+    std::vector<OkFresh> anew;
+    for (OkGrow &b : all)
+    {
+        b.need = std::max(b.need, *b.cap);
+        *b.cap = 0;
+        anew.push_back(fresh(*b.slot, b.need));
+    }
+    if (const int rc = regrow(h, anew))
+        return rc;
+    for (const OkGrow &b : all)
+        *b.cap = b.need;
     return OKENV_OK;
 }
 
@@ -1493,27 +1529,96 @@ int gclNumParams(const okenv *h, const int which)
 // ---- the drivers' life cycle, behind the exported functions' OK_QUIESCE ("The drivers' life cycle on the host") ---------------
 
 // Which family an exported entry works on: its record in the handle, the prefix of its entries' names (for the messages), who "needs its
-// parameters" in act's refusal and in get's, and whether num_params and set_params look at their pointer before the state (the two
-// families that came last do, and refuse a NULL out pointer of num_params; the others write nothing through one)
+// parameters" in act's refusal and in get's, and whether num_params and set_params look at their pointer before the state (the
+// families that came after the first four do, and refuse a NULL out pointer of num_params; the others write nothing through one).
+// The flat-vector families (one vector in torch's order that grows on demand: lidar, flow and the six image families) describe
+// themselves further, and their shared entries below (flatNumParams, flatSetParams, flatGetParams, actBeginFrames) read nothing else.
 struct DriverKind
 {
     OkDriver okenv::*drv;
     const char      *prefix;
     const char      *act_needs, *get_needs;
     bool             argument_first;
+    int (*total)(const okenv *h);      // the floats of vector 0 as the stored config stands
+    int (*repack)(okenv *h);           // nullptr, or: enqueues the kernels that rebuild the conv / GRU kernels' copy of the weights behind an upload
+    int (*image_size)(const okenv *h); // nullptr, or: the side of the frames the act takes
+    // world and memory: vector 1, [N][controller] inside the workspace, with set flag 1
+    int (*controller)(const okenv *h);     // nullptr, or: the floats of one agent's controller
+    float *(*controllers)(const okenv *h); // ... where the agents' controllers begin
+    const char *which;                     // ... and the two names of `which`, for the refusal
 };
+
+// The kernels' copy of a conv family's weights (cnn, qcnn, bev, world): one thread per float of the pack, behind the upload on the stream
+template <class Params, class Shape>
+int packLaunch(okenv *h, void (*kernel)(Params), const Shape &s, const float *params, float *pack, const int pack_total)
+{
+    Params p{};
+    p.s      = s;
+    p.params = params;
+    p.pack   = pack;
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((pack_total + 255) / 256)), dim3(256), 0, h->stream, p);
+    OK_HIP(h, hipGetLastError());
+    return OKENV_OK;
+}
+
+ok_memory_shape memoryShape(const okenv *h)
+{
+    return okMemoryShape(h->world, h->mem);
+}
+
+int memoryRepack(okenv *h); // (beside okenv_memory_act's launches)
+
+static_assert(kBevThreads == 256 && OKENV_WORLD_ENCODER == 0 && OKENV_WORLD_CONTROLLERS == 1 && OKENV_MEMORY_NETWORK == 0 && OKENV_MEMORY_CONTROLLERS == 1,
+              "packLaunch's block and the shared entries' `which`");
+
 const DriverKind kActorDriver{&okenv::actor_drv, "okenv_actor_", "every attached network needs its parameters", nullptr, false},
     kDdpgDriver{&okenv::ddpg_drv, "okenv_ddpg_", "the actor needs its parameters", "both networks need their parameters", false},
     kGaussDriver{&okenv::gauss_drv, "okenv_gauss_", "the actor needs its parameters", "the actor needs its parameters", false},
     kGclDriver{&okenv::gcl_drv, "okenv_gcl_", "the policy needs its parameters", "the network needs its parameters", false},
-    kLidarDriver{&okenv::lidar_drv, "okenv_lidar_", "the policy needs its parameters", "the policy needs its parameters", true},
-    kFlowDriver{&okenv::flow_drv, "okenv_flow_", "the policy needs its parameters", "the policy needs its parameters", true},
-    kBevDriver{&okenv::bev_drv, "okenv_bev_", "the encoder needs its parameters", "the encoder needs its parameters", true},
-    kCnnDriver{&okenv::cnn_drv, "okenv_cnn_", "the policy needs its parameters", "the policy needs its parameters", true},
-    kWorldDriver{&okenv::world_drv, "okenv_world_", "the encoder and the controllers need their parameters", "the vector needs its parameters", true},
-    kMemoryDriver{&okenv::mem_drv, "okenv_memory_", "the network and the controllers need their parameters", "the vector needs its parameters", true},
-    kQcnnDriver{&okenv::qcnn_drv, "okenv_qcnn_", "the network needs its parameters", "the network needs its parameters", true},
-    kVitDriver{&okenv::vit_drv, "okenv_vit_", "the policy needs its parameters", "the policy needs its parameters", true};
+    kLidarDriver{&okenv::lidar_drv, "okenv_lidar_", "the policy needs its parameters", "the policy needs its parameters", true,
+                 [](const okenv *h) { return ok_lidar_offsets(okLidarShape(h->lidar)).total; }},
+    kFlowDriver{&okenv::flow_drv, "okenv_flow_", "the policy needs its parameters", "the policy needs its parameters", true,
+                [](const okenv *h) { return ok_flow_offsets(okFlowShape(h->flow)).total; }},
+    kBevDriver{&okenv::bev_drv, "okenv_bev_", "the encoder needs its parameters", "the encoder needs its parameters", true,
+               [](const okenv *h) { return ok_bev_offsets(okBevShape(h->bev)).total; },
+               [](okenv *h) {
+                   const ok_bev_shape s = okBevShape(h->bev);
+                   return packLaunch(h, okBevPackKernel, s, h->bev_drv.d, h->bev_pack.d, okBevPlaces(s).pack_total);
+               },
+               nullptr}, // (okenv_bev_encode checks its frames itself, behind its output)
+    kCnnDriver{&okenv::cnn_drv, "okenv_cnn_", "the policy needs its parameters", "the policy needs its parameters", true,
+               [](const okenv *h) { return ok_cnn_offsets(okCnnShape(h->cnn)).total; },
+               [](okenv *h) {
+                   const ok_cnn_shape s = okCnnShape(h->cnn);
+                   return packLaunch(h, okCnnPackKernel, s, h->cnn_drv.d, h->cnn_pack.d, okCnnPlaces(s).pack_total);
+               },
+               [](const okenv *h) { return h->cnn.image_size; }},
+    kWorldDriver{&okenv::world_drv, "okenv_world_", "the encoder and the controllers need their parameters", "the vector needs its parameters", true,
+                 [](const okenv *h) { return ok_world_offsets(okWorldShape(h->world)).total; },
+                 [](okenv *h) {
+                     const ok_world_shape s = okWorldShape(h->world);
+                     return packLaunch(h, okWorldPackKernel, s, h->world_drv.d, h->world_ws.d, okWorldPlaces(s, static_cast<size_t>(h->shape.N)).pack_total);
+                 },
+                 [](const okenv *h) { return h->world.image_size; },
+                 [](const okenv *h) { return ok_world_controller_params(okWorldShape(h->world)); },
+                 [](const okenv *h) { return h->world_ws.d + okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).ctrl; },
+                 "OKENV_WORLD_ENCODER or OKENV_WORLD_CONTROLLERS"},
+    kMemoryDriver{&okenv::mem_drv, "okenv_memory_", "the network and the controllers need their parameters", "the vector needs its parameters", true,
+                  [](const okenv *h) { return ok_memory_offsets(memoryShape(h)).total; },
+                  memoryRepack,
+                  [](const okenv *h) { return h->world.image_size; }, // (the racers' frames)
+                  [](const okenv *h) { return ok_memory_controller_params(memoryShape(h)); },
+                  [](const okenv *h) { return h->mem_ws.d + okMemoryPlaces(memoryShape(h), static_cast<size_t>(h->shape.N)).ctrl; },
+                  "OKENV_MEMORY_NETWORK or OKENV_MEMORY_CONTROLLERS"},
+    kQcnnDriver{&okenv::qcnn_drv, "okenv_qcnn_", "the network needs its parameters", "the network needs its parameters", true,
+                [](const okenv *h) { return ok_qcnn_offsets(okQcnnShape(h->qcnn)).total; },
+                [](okenv *h) {
+                    const ok_qcnn_shape s = okQcnnShape(h->qcnn);
+                    return packLaunch(h, okQcnnPackKernel, s, h->qcnn_drv.d, h->qcnn_pack.d, okQcnnPlaces(s).pack_total);
+                },
+                [](const okenv *h) { return h->qcnn.image_size; }},
+    kVitDriver{&okenv::vit_drv, "okenv_vit_", "the policy needs its parameters", "the policy needs its parameters", true,
+               [](const okenv *h) { return ok_vit_offsets(okVitShape(h->vit)).total; }, nullptr, [](const okenv *h) { return h->vit.image_size; }};
 
 int driverRefuses(okenv *h, const int code, const DriverKind &k, const char *entry, const std::string &why)
 {
@@ -1578,25 +1683,23 @@ int driverCreateFixed(okenv *h, const DriverKind &k, const size_t cap, const siz
     return OKENV_OK;
 }
 
-// okenv_*_create of the families whose one vector grows on demand, behind their gate and config check: detached before the allocation,
-// so that a failed one leaves the driver so; the room is kept when it suffices, and the parameters are forgotten either way
-int driverCreateFlat(okenv *h, const DriverKind &k, const size_t total, const void *kernel)
+// okenv_*_create of the flat-vector families, behind their gate, config check and own refusals: detached and the parameters forgotten
+// before anything is allocated, so that a failure leaves the driver so; the vector's room is kept when it suffices; the kernels' LDS
+// limits; then the family's other buffers (`buffers`: as one group, growBuffers).  The driver stays detached: the caller resets what
+// depends on the network, stores its config and only then says that the driver is created.
+int driverCreateFlat(okenv *h, const DriverKind &k, const size_t total, const std::initializer_list<const void *> kernels,
+                     const std::initializer_list<OkGrow> buffers = {})
 {
     OK_HIP(h, hipSetDevice(h->device));
     OkDriver &d = h->*k.drv;
     d.ok        = false;
-    d.set[0]    = false;
-    if (total > d.cap)
-    {
-        d.cap = 0;
-        if (const int rc = regrow(h, {fresh(d.d, total)}))
-            return rc;
-        d.cap = total;
-    }
-    if (const int rc = raiseLdsLimit(h, {kernel}))
+    for (bool &set : d.set)
+        set = false;
+    if (const int rc = growBuffers(h, {OkGrow{&d.d, &d.cap, total}}))
         return rc;
-    d.ok = true;
-    return OKENV_OK;
+    if (const int rc = raiseLdsLimit(h, kernels))
+        return rc;
+    return growBuffers(h, buffers);
 }
 
 // One parameter vector of a set or get: where it lies on the device, the caller's pointer (host or device; nullptr: not this one), its
@@ -1638,6 +1741,51 @@ int driverGet(okenv *h, const std::initializer_list<OkVector> vectors)
                 return rc;
     OK_HIP(h, hipStreamSynchronize(h->stream));
     return OKENV_OK;
+}
+
+// okenv_*_num_params / _set_params / _get_params of the flat-vector families behind their OK_QUIESCE, from the family's description.
+// which: 0 for vector 0 (the only one of most families), 1 for the controllers of a family that has them; an entry without a `which`
+// passes 0.  controller: the second out pointer of such a family's num_params.
+int flatNumParams(okenv *h, const DriverKind &k, int32_t *vector0, int32_t *controller = nullptr)
+{
+    const bool argument = vector0 != nullptr && (k.controller == nullptr || controller != nullptr);
+    if (const int rc = driverGate(h, k, "num_params", kGateArgFirst | kGateCreated, argument))
+        return rc;
+    *vector0 = k.total(h);
+    if (k.controller != nullptr)
+        *controller = k.controller(h);
+    return OKENV_OK;
+}
+
+bool flatWhichBad(const DriverKind &k, const int32_t which)
+{
+    return which != 0 && (which != 1 || k.controller == nullptr);
+}
+
+int flatSetParams(okenv *h, const DriverKind &k, const int32_t which, const float *params)
+{
+    if (const int rc = driverGate(h, k, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
+        return rc;
+    if (flatWhichBad(k, which))
+        return driverRefuses(h, OKENV_ERR_INVALID, k, "set_params", std::string("which must be ") + k.which);
+    if (which == 1)
+        return driverSet(h, k, {vectorOf(k.controllers(h), params, h->shape.N * k.controller(h), 1)});
+    if (const int rc = driverSet(h, k, {vectorOf((h->*k.drv).d, params, k.total(h))}))
+        return rc;
+    return k.repack != nullptr ? k.repack(h) : OKENV_OK;
+}
+
+// (the gate, which asks for the vector's own set flag, comes before a bad `which`, which asks for flag 0)
+int flatGetParams(okenv *h, const DriverKind &k, const int32_t which, float *params)
+{
+    const bool controllers = which == 1 && k.controller != nullptr;
+    if (const int rc = driverGate(h, k, "get_params", kGateArgFirst | kGateStored, params != nullptr, controllers ? 2U : 1U))
+        return rc;
+    if (flatWhichBad(k, which))
+        return driverRefuses(h, OKENV_ERR_INVALID, k, "get_params", std::string("which must be ") + k.which);
+    if (controllers)
+        return driverGet(h, {vectorOf(k.controllers(h), params, h->shape.N * k.controller(h))});
+    return driverGet(h, {vectorOf((h->*k.drv).d, params, k.total(h))});
 }
 
 int driverSetDrawOffset(okenv *h, const DriverKind &k, const uint32_t *device_word)
@@ -1698,6 +1846,14 @@ const char *framesMissing(const void *frames, const int64_t frame_bytes, const i
     return nullptr;
 }
 
+// actBegin of the families that act on one frame per agent: what framesMissing says of them is the entry's last refusal, and they are looked
+// at only once the driver is created (before that the state is all an act reports)
+int actBeginFrames(okenv *h, const DriverKind &k, const unsigned need, const void *frames, const int64_t frame_bytes, const unsigned align = 4U)
+{
+    const bool created = h != nullptr && (h->*k.drv).ok;
+    return actBegin(h, k, need, created ? framesMissing(frames, frame_bytes, h->shape.N, k.image_size(h), align) : nullptr);
+}
+
 // okenv_bev_encode behind its OK_QUIESCE: the kernels named in `stages` (OKENV_BEV_STAGE_*), in their order, on the stream
 int bevEncode(okenv *h, const uint8_t *frames, const int64_t frame_bytes, float *out, const unsigned stages)
 {
@@ -1713,9 +1869,9 @@ int bevEncode(okenv *h, const uint8_t *frames, const int64_t frame_bytes, float 
     p.s      = s;
     p.frames = frames;
     p.params = h->bev_drv.d;
-    p.pack   = h->d_bev_pack;
-    p.act1   = h->d_bev_act1;
-    p.act2   = h->d_bev_act2;
+    p.pack   = h->bev_pack.d;
+    p.act1   = h->bev_act1.d;
+    p.act2   = h->bev_act2.d;
     p.out    = out;
     const auto tiles = [](const int side, const int t) { return static_cast<unsigned>((side + t - 1) / t); };
     const unsigned N = static_cast<unsigned>(h->shape.N), ta = tiles(ok_bev_side(s, 1), pl.ta), tb = tiles(ok_bev_side(s, 2), pl.tb);
@@ -1735,8 +1891,7 @@ int bevEncode(okenv *h, const uint8_t *frames, const int64_t frame_bytes, float 
 // okenv_cnn_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_CNN_STAGE_*), in their order, on the stream
 int cnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_cnn_record *rec, const unsigned stages)
 {
-    const char *missing = h != nullptr && h->cnn_drv.ok ? framesMissing(frames, frame_bytes, h->shape.N, h->cnn.image_size, 4U) : nullptr;
-    if (const int rc = actBegin(h, kCnnDriver, 1U, missing))
+    if (const int rc = actBeginFrames(h, kCnnDriver, 1U, frames, frame_bytes))
         return rc;
     const ok_cnn_shape s  = okCnnShape(h->cnn);
     const OkCnnPlaces  pl = okCnnPlaces(s);
@@ -1746,8 +1901,8 @@ int cnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const oke
     p.s           = s;
     p.frames      = frames;
     p.params      = h->cnn_drv.d;
-    p.pack        = h->d_cnn_pack;
-    p.feat        = h->d_cnn_feat;
+    p.pack        = h->cnn_pack.d;
+    p.feat        = h->cnn_feat.d;
     p.throttle    = h->cnn.throttle;
     p.steer_scale = h->cnn.steer_scale;
     if (rec != nullptr)
@@ -1780,8 +1935,7 @@ int qcnnHead(okenv *h, const OkQcnnPlaces &pl, const OkQcnnActParams &p)
 // okenv_qcnn_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_QCNN_STAGE_*), in their order, on the stream
 int qcnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_qcnn_record *rec, const unsigned stages)
 {
-    const char *missing = h != nullptr && h->qcnn_drv.ok ? qcnnFramesMissing(h, frames, frame_bytes) : nullptr;
-    if (const int rc = actBegin(h, kQcnnDriver, 1U, missing))
+    if (const int rc = actBeginFrames(h, kQcnnDriver, 1U, frames, frame_bytes, 16U)) // (as qcnnFramesMissing)
         return rc;
     const ok_qcnn_shape s  = okQcnnShape(h->qcnn);
     const OkQcnnPlaces  pl = okQcnnPlaces(s);
@@ -1791,8 +1945,8 @@ int qcnnAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const ok
     p.s      = s;
     p.frames = frames;
     p.params = h->qcnn_drv.d;
-    p.pack   = h->d_qcnn_pack;
-    p.feat   = h->d_qcnn_feat;
+    p.pack   = h->qcnn_pack.d;
+    p.feat   = h->qcnn_feat.d;
     p.draw   = actDrawWords(h, h->qcnn_drv.draw_offset);
     p.cfg    = h->qcnn;
     if (rec != nullptr)
@@ -1833,7 +1987,7 @@ int vitBackbone(okenv *h, const uint8_t *frames, const size_t count)
         lp.mean[c] = h->vit.mean[c], lp.std[c] = h->vit.std[c];
     lp.pos = prm + at.pos, lp.cls = prm + at.cls;
     const long M = static_cast<long>(count) * T;
-    float     *x = h->d_vit_work, *n = x + static_cast<size_t>(M) * D, *ctx = n + static_cast<size_t>(M) * D, *qkv = ctx + static_cast<size_t>(M) * D,
+    float     *x = h->vit_work.d, *n = x + static_cast<size_t>(M) * D, *ctx = n + static_cast<size_t>(M) * D, *qkv = ctx + static_cast<size_t>(M) * D,
           *hid = qkv + static_cast<size_t>(M) * 3U * D;
     lp.frames = frames;
     vitLinear<kVitSrcPatch, kVitEpiPos>(h, lp, static_cast<long>(count) * (T - 1), ok_vit_patch_k(s), D, nullptr, 0, prm + at.pe_w, prm + at.pe_b, x, D);
@@ -1880,7 +2034,7 @@ int vitEmbed(okenv *h, const uint8_t *frames, const int32_t m, const int64_t fra
         if (const int rc = vitBackbone(h, frames + a0 * frame, count))
             return rc;
         hipLaunchKernelGGL(okVitEmbedKernel, dim3(static_cast<unsigned>((count + kVitNormRows - 1) / kVitNormRows)), dim3(kVitThreads), 0, h->stream,
-                           static_cast<int>(count), D, static_cast<long>(T) * D, h->d_vit_work, h->vit_drv.d + at.norm_g, h->vit_drv.d + at.norm_b, h->vit.ln_eps,
+                           static_cast<int>(count), D, static_cast<long>(T) * D, h->vit_work.d, h->vit_drv.d + at.norm_g, h->vit_drv.d + at.norm_b, h->vit.ln_eps,
                            embedding + a0 * D);
         OK_HIP(h, hipGetLastError());
     }
@@ -1900,7 +2054,7 @@ int vitHeadTotal(const okenv *h)
 
 float *vitHeadMoment(const okenv *h, const int k)
 {
-    return h->d_vit_head_mv + static_cast<size_t>(k) * h->vit_head_cap;
+    return h->vit_head_mv.d + static_cast<size_t>(k) * (h->vit_head_mv.cap / 2U);
 }
 
 // okenv_vit_head_update (update == true: `epochs` passes in `order`, a step per minibatch) and okenv_vit_head_eval (one sequential pass, the
@@ -1961,8 +2115,7 @@ int vitHeadRun(okenv *h, const char *entry, const bool update, const float *embe
 // okenv_vit_act behind its OK_QUIESCE: the fixed launch sequence (ok_vit.h), once per pass of vit_pass agents, on the stream
 int vitAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_vit_record *rec)
 {
-    const char *missing = h != nullptr && h->vit_drv.ok ? framesMissing(frames, frame_bytes, h->shape.N, h->vit.image_size, 4U) : nullptr;
-    if (const int rc = actBegin(h, kVitDriver, 1U, missing))
+    if (const int rc = actBeginFrames(h, kVitDriver, 1U, frames, frame_bytes))
         return rc;
     const ok_vit_shape  s  = okVitShape(h->vit);
     const OkVitPlaces   pl = okVitPlaces(s);
@@ -1971,7 +2124,7 @@ int vitAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const oke
     for (size_t a0 = 0; a0 < static_cast<size_t>(h->shape.N); a0 += h->vit_pass)
     {
         const size_t count = std::min(h->vit_pass, static_cast<size_t>(h->shape.N) - a0);
-        float       *x = h->d_vit_work;
+        float       *x = h->vit_work.d;
         if (const int rc = vitBackbone(h, frames + a0 * frame, count))
             return rc;
         OkVitFinalParams fp{};
@@ -1992,8 +2145,7 @@ int worldKernels(okenv *h, const uint8_t *frames, const okenv_world_record *rec,
 
 int worldAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_world_record *rec, const unsigned stages)
 {
-    const char *missing = h != nullptr && h->world_drv.ok ? framesMissing(frames, frame_bytes, h->shape.N, h->world.image_size, 4U) : nullptr;
-    if (const int rc = actBegin(h, kWorldDriver, 3U, missing))
+    if (const int rc = actBeginFrames(h, kWorldDriver, 3U, frames, frame_bytes))
         return rc;
     return worldKernels(h, frames, rec, stages);
 }
@@ -2005,7 +2157,7 @@ int worldKernels(okenv *h, const uint8_t *frames, const okenv_world_record *rec,
     const ok_world_layout at = ok_world_offsets(s);
     const size_t          N  = static_cast<size_t>(h->shape.N);
     const OkWorldPlaces   pl = okWorldPlaces(s, N);
-    float                *ws = h->d_world_ws;
+    float                *ws = h->world_ws.d;
     int                  *list = reinterpret_cast<int *>(ws + pl.list), *count = reinterpret_cast<int *>(ws + pl.count);
     if ((stages & OKENV_WORLD_STAGE_LIST) != 0U)
     {
@@ -2071,23 +2223,13 @@ int worldKernels(okenv *h, const uint8_t *frames, const okenv_world_record *rec,
     return OKENV_OK;
 }
 
-ok_memory_shape memoryShape(const okenv *h)
-{
-    return okMemoryShape(h->world, h->mem);
-}
-
 // okenv_memory_act behind its OK_QUIESCE: the kernels named in `stages` (OKENV_MEMORY_STAGE_*), in their order, on the stream.  The
 // encoder is okenv_world_act's own launches (worldAct without its head); every grid behind it is sized for all N agents as well.
 int memoryAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const okenv_memory_record *rec, const unsigned stages)
 {
-    const char *missing = nullptr;
-    if (h != nullptr && h->mem_drv.ok)
-    {
-        if (!h->world_drv.ok || !h->world_drv.set[0])
-            return driverRefuses(h, OKENV_ERR_STATE, kMemoryDriver, "act", "call okenv_world_set_params first (the encoder needs its parameters)");
-        missing = framesMissing(frames, frame_bytes, h->shape.N, h->world.image_size, 4U);
-    }
-    if (const int rc = actBegin(h, kMemoryDriver, 3U, missing))
+    if (h != nullptr && h->mem_drv.ok && (!h->world_drv.ok || !h->world_drv.set[0]))
+        return driverRefuses(h, OKENV_ERR_STATE, kMemoryDriver, "act", "call okenv_world_set_params first (the encoder needs its parameters)");
+    if (const int rc = actBeginFrames(h, kMemoryDriver, 3U, frames, frame_bytes))
         return rc;
     const ok_world_shape   w   = okWorldShape(h->world);
     const ok_memory_shape  s   = memoryShape(h);
@@ -2096,8 +2238,8 @@ int memoryAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const 
     const size_t           N   = static_cast<size_t>(h->shape.N);
     const OkWorldPlaces    wpl = okWorldPlaces(w, N);
     const OkMemoryPlaces   pl  = okMemoryPlaces(s, N);
-    float                 *ws = h->d_mem_ws, *net = h->mem_drv.d;
-    const int             *list = reinterpret_cast<const int *>(h->d_world_ws + wpl.list), *count = reinterpret_cast<const int *>(h->d_world_ws + wpl.count);
+    float                 *ws = h->mem_ws.d, *net = h->mem_drv.d;
+    const int             *list = reinterpret_cast<const int *>(h->world_ws.d + wpl.list), *count = reinterpret_cast<const int *>(h->world_ws.d + wpl.count);
     if ((stages & OKENV_MEMORY_STAGE_ENCODER) != 0U)
     {
         // (the racers' own controllers are not read: only their encoder must be set)
@@ -2110,7 +2252,7 @@ int memoryAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const 
         OkMemoryInputJob j{};
         j.st       = h->st;
         j.enc_bias = h->world_drv.d + wat.mb;
-        j.part     = h->d_world_ws + wpl.part;
+        j.part     = h->world_ws.d + wpl.part;
         j.z_mean   = net + at.z_mean;
         j.z_std    = net + at.z_std;
         j.a_mean   = net + at.a_mean;
@@ -2166,6 +2308,27 @@ int memoryAct(okenv *h, const uint8_t *frames, const int64_t frame_bytes, const 
         if (rec != nullptr)
             p.rec = *rec;
         return actLaunch(h, okMemoryHeadKernel, kMemHeadSlots, 64 * kMemHeadSlots, 0, p);
+    }
+    return OKENV_OK;
+}
+
+// The layer kernel's copy of the GRU matrices behind an upload of the network: one launch per matrix on the stream
+int memoryRepack(okenv *h)
+{
+    const ok_memory_shape  s  = memoryShape(h);
+    const OkMemoryPlaces   pl = okMemoryPlaces(s, static_cast<size_t>(h->shape.N));
+    const ok_memory_layout at = ok_memory_offsets(s);
+    for (int m = 0; m < 2 * s.L; ++m)
+    {
+        const int       l = m / 2;
+        OkMemoryPackJob j{};
+        j.cols   = 3 * s.H;
+        j.K      = m % 2 == 0 ? okMemoryKin(s, l) : s.H;
+        j.stride = m % 2 == 0 ? ok_memory_in(s, l) : s.H;
+        j.src    = h->mem_drv.d + (m % 2 == 0 ? at.wih[l] : at.whh[l]);
+        j.dst    = h->mem_ws.d + (m % 2 == 0 ? pl.ih[l] : pl.hh[l]);
+        hipLaunchKernelGGL(okMemoryPackKernel, dim3(static_cast<unsigned>((j.cols * j.K + 255) / 256)), dim3(256), 0, h->stream, j);
+        OK_HIP(h, hipGetLastError());
     }
     return OKENV_OK;
 }
@@ -4494,16 +4657,13 @@ extern "C"
             return fail(h, OKENV_ERR_INVALID, "okenv_gcl_set_expert: NULL argument or an empty bank");
         OK_HIP(h, hipSetDevice(h->device));
         const size_t R = static_cast<size_t>(h->shape.R), rows = static_cast<size_t>(E);
-        if (E > h->gcl_bank_cap)
-        {
-            h->gcl_bank_cap = h->gcl_bank_rows = 0;
-            if (const int rc = regrow(h, {fresh(h->d_gcl_bank, rows * (R + 2U))}))
-                return rc;
-            h->gcl_bank_cap = E;
-        }
-        if (const int rc = copyAny(h, h->d_gcl_bank, state, sizeof(float) * rows * R))
+        if (rows * (R + 2U) > h->gcl_bank.cap)
+            h->gcl_bank_rows = 0; // (a failed allocation leaves no bank)
+        if (const int rc = growBuffers(h, {grown(h->gcl_bank, rows * (R + 2U))}))
             return rc;
-        if (const int rc = copyAny(h, h->d_gcl_bank + rows * R, action, sizeof(float) * rows * 2U))
+        if (const int rc = copyAny(h, h->gcl_bank.d, state, sizeof(float) * rows * R))
+            return rc;
+        if (const int rc = copyAny(h, h->gcl_bank.d + rows * R, action, sizeof(float) * rows * 2U))
             return rc;
         h->gcl_bank_rows = E;
         return OKENV_OK;
@@ -4578,8 +4738,8 @@ extern "C"
         p.cols        = p.P + 1;
         p.state       = batch->state;
         p.squashed    = batch->squashed;
-        p.bank_state  = h->d_gcl_bank;
-        p.bank_action = h->d_gcl_bank + static_cast<size_t>(h->gcl_bank_rows) * static_cast<size_t>(p.R);
+        p.bank_state  = h->gcl_bank.d;
+        p.bank_action = h->gcl_bank.d + static_cast<size_t>(h->gcl_bank_rows) * static_cast<size_t>(p.R);
         p.E           = h->gcl_bank_rows;
         p.Me          = Me;
         p.Ce          = (Me + OK_LEARN_CHUNK - 1) / OK_LEARN_CHUNK;
@@ -4805,35 +4965,29 @@ extern "C"
             return driverRefuses(h, OKENV_ERR_INVALID, kLidarDriver, "create", why);
         if (config->num_points != h->shape.R)
             return fail(h, OKENV_ERR_INVALID, "okenv_lidar_create: num_points must equal the handle's ray count");
-        if (const int rc = driverCreateFlat(h, kLidarDriver, static_cast<size_t>(ok_lidar_offsets(okLidarShape(*config)).total), kernelOf(okLidarActKernel)))
+        if (const int rc = driverCreateFlat(h, kLidarDriver, static_cast<size_t>(ok_lidar_offsets(okLidarShape(*config)).total), {kernelOf(okLidarActKernel)}))
             return rc;
-        h->lidar = *config;
+        h->lidar        = *config;
+        h->lidar_drv.ok = true;
         return OKENV_OK;
     }
 
     int okenv_lidar_num_params(okenv_t h, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kLidarDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
-            return rc;
-        *num_params = ok_lidar_offsets(okLidarShape(h->lidar)).total;
-        return OKENV_OK;
+        return flatNumParams(h, kLidarDriver, num_params);
     }
 
     int okenv_lidar_set_params(okenv_t h, const float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kLidarDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
-            return rc;
-        return driverSet(h, kLidarDriver, {vectorOf(h->lidar_drv.d, params, ok_lidar_offsets(okLidarShape(h->lidar)).total)});
+        return flatSetParams(h, kLidarDriver, 0, params);
     }
 
     int okenv_lidar_get_params(okenv_t h, float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kLidarDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
-            return rc;
-        return driverGet(h, {vectorOf(h->lidar_drv.d, params, ok_lidar_offsets(okLidarShape(h->lidar)).total)});
+        return flatGetParams(h, kLidarDriver, 0, params);
     }
 
     int okenv_lidar_act(okenv_t h, const okenv_lidar_record *rec)
@@ -4922,19 +5076,9 @@ extern "C"
         if (const char *why = okVitWorkspaceBad(*config, pass))
             return driverRefuses(h, OKENV_ERR_INVALID, kVitDriver, "create", why);
         h->vit_head_ok = false; // (the head's learner belongs to the policy that goes)
-        if (const int rc = driverCreateFlat(h, kVitDriver, static_cast<size_t>(ok_vit_offsets(s).total), kernelOf(okVitAttendKernel)))
+        if (const int rc = driverCreateFlat(h, kVitDriver, static_cast<size_t>(ok_vit_offsets(s).total), {kernelOf(okVitAttendKernel), kernelOf(okVitFinalKernel)},
+                                            {grown(h->vit_work, pass * ok_vit_agent_floats(s))}))
             return rc;
-        h->vit_drv.ok = false; // (until the workspace stands)
-        if (const int rc = raiseLdsLimit(h, {kernelOf(okVitFinalKernel)}))
-            return rc;
-        const size_t floats = pass * ok_vit_agent_floats(s);
-        if (floats > h->vit_work_cap)
-        {
-            h->vit_work_cap = 0; // (a failed allocation leaves none)
-            if (const int rc = regrow(h, {fresh(h->d_vit_work, floats)}))
-                return rc;
-            h->vit_work_cap = floats;
-        }
         h->vit        = *config;
         h->vit_pass   = pass;
         h->vit_drv.ok = true;
@@ -4944,26 +5088,19 @@ extern "C"
     int okenv_vit_num_params(okenv_t h, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kVitDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
-            return rc;
-        *num_params = ok_vit_offsets(okVitShape(h->vit)).total;
-        return OKENV_OK;
+        return flatNumParams(h, kVitDriver, num_params);
     }
 
     int okenv_vit_set_params(okenv_t h, const float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kVitDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
-            return rc;
-        return driverSet(h, kVitDriver, {vectorOf(h->vit_drv.d, params, ok_vit_offsets(okVitShape(h->vit)).total)});
+        return flatSetParams(h, kVitDriver, 0, params);
     }
 
     int okenv_vit_get_params(okenv_t h, float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kVitDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
-            return rc;
-        return driverGet(h, {vectorOf(h->vit_drv.d, params, ok_vit_offsets(okVitShape(h->vit)).total)});
+        return flatGetParams(h, kVitDriver, 0, params);
     }
 
     int okenv_vit_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_vit_record *rec)
@@ -5041,17 +5178,11 @@ extern "C"
             return fail(h, OKENV_ERR_INVALID, std::string("okenv_vit_head_learner_create: ") + why);
         OK_HIP(h, hipSetDevice(h->device));
         h->vit_head_ok = false;
-        const size_t total = static_cast<size_t>(vitHeadTotal(h));
-        if (total > h->vit_head_cap)
-        {
-            h->vit_head_cap = 0; // (a failed allocation leaves none)
-            if (const int rc = regrow(h, {fresh(h->d_vit_head_mv, 2U * total)}))
-                return rc;
-            h->vit_head_cap = total;
-        }
+        if (const int rc = growBuffers(h, {grown(h->vit_head_mv, 2U * static_cast<size_t>(vitHeadTotal(h)))})) // [m | v], each half the room
+            return rc;
         if (const int rc = raiseLdsLimit(h, {kernelOf(okVitHeadForwardKernel)}))
             return rc;
-        OK_HIP(h, hipMemsetAsync(h->d_vit_head_mv, 0, 2U * h->vit_head_cap * sizeof(float), h->stream));
+        OK_HIP(h, hipMemsetAsync(h->vit_head_mv.d, 0, h->vit_head_mv.cap * sizeof(float), h->stream));
         h->vit_head    = *params;
         h->vit_head_t  = 0;
         h->vit_head_ok = true;
@@ -5064,7 +5195,7 @@ extern "C"
         if (!h || !h->vit_drv.ok || !h->vit_head_ok)
             return fail(h, OKENV_ERR_STATE, "okenv_vit_head_learner_reset: call okenv_vit_head_learner_create first");
         OK_HIP(h, hipSetDevice(h->device));
-        OK_HIP(h, hipMemsetAsync(h->d_vit_head_mv, 0, 2U * h->vit_head_cap * sizeof(float), h->stream));
+        OK_HIP(h, hipMemsetAsync(h->vit_head_mv.d, 0, h->vit_head_mv.cap * sizeof(float), h->stream));
         h->vit_head_t = 0;
         return OKENV_OK;
     }
@@ -5145,35 +5276,29 @@ extern "C"
             return rc;
         if (const char *why = okFlowCheckConfig(config))
             return driverRefuses(h, OKENV_ERR_INVALID, kFlowDriver, "create", why);
-        if (const int rc = driverCreateFlat(h, kFlowDriver, static_cast<size_t>(ok_flow_offsets(okFlowShape(*config)).total), kernelOf(okFlowActKernel)))
+        if (const int rc = driverCreateFlat(h, kFlowDriver, static_cast<size_t>(ok_flow_offsets(okFlowShape(*config)).total), {kernelOf(okFlowActKernel)}))
             return rc;
-        h->flow = *config;
+        h->flow        = *config;
+        h->flow_drv.ok = true;
         return OKENV_OK;
     }
 
     int okenv_flow_num_params(okenv_t h, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kFlowDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
-            return rc;
-        *num_params = ok_flow_offsets(okFlowShape(h->flow)).total;
-        return OKENV_OK;
+        return flatNumParams(h, kFlowDriver, num_params);
     }
 
     int okenv_flow_set_params(okenv_t h, const float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kFlowDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
-            return rc;
-        return driverSet(h, kFlowDriver, {vectorOf(h->flow_drv.d, params, ok_flow_offsets(okFlowShape(h->flow)).total)});
+        return flatSetParams(h, kFlowDriver, 0, params);
     }
 
     int okenv_flow_get_params(okenv_t h, float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kFlowDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
-            return rc;
-        return driverGet(h, {vectorOf(h->flow_drv.d, params, ok_flow_offsets(okFlowShape(h->flow)).total)});
+        return flatGetParams(h, kFlowDriver, 0, params);
     }
 
     int okenv_flow_set_draw_offset(okenv_t h, const uint32_t *device_word)
@@ -5245,18 +5370,10 @@ extern "C"
         if (const char *why = okCnnCheckConfig(config))
             return driverRefuses(h, OKENV_ERR_INVALID, kCnnDriver, "create", why);
         const ok_cnn_shape s = okCnnShape(*config);
-        if (const int rc = driverCreateFlat(h, kCnnDriver, static_cast<size_t>(ok_cnn_offsets(s).total), kernelOf(okCnnConvKernel)))
+        if (const int rc = driverCreateFlat(h, kCnnDriver, static_cast<size_t>(ok_cnn_offsets(s).total), {kernelOf(okCnnConvKernel)},
+                                            {grown(h->cnn_pack, static_cast<size_t>(okCnnPlaces(s).pack_total)),
+                                             grown(h->cnn_feat, static_cast<size_t>(h->shape.N) * ok_cnn_features(s))}))
             return rc;
-        h->cnn_drv.ok = false; // (until the kernels' own buffers stand)
-        const size_t pack = static_cast<size_t>(okCnnPlaces(s).pack_total), feat = static_cast<size_t>(h->shape.N) * ok_cnn_features(s);
-        if (pack > h->cnn_pack_cap || feat > h->cnn_feat_cap)
-        {
-            const size_t np = std::max(pack, h->cnn_pack_cap), nf = std::max(feat, h->cnn_feat_cap);
-            h->cnn_pack_cap = h->cnn_feat_cap = 0; // (a failed allocation leaves none of them)
-            if (const int rc = regrow(h, {fresh(h->d_cnn_pack, np), fresh(h->d_cnn_feat, nf)}))
-                return rc;
-            h->cnn_pack_cap = np, h->cnn_feat_cap = nf;
-        }
         h->cnn        = *config;
         h->cnn_drv.ok = true;
         return OKENV_OK;
@@ -5265,36 +5382,19 @@ extern "C"
     int okenv_cnn_num_params(okenv_t h, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kCnnDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
-            return rc;
-        *num_params = ok_cnn_offsets(okCnnShape(h->cnn)).total;
-        return OKENV_OK;
+        return flatNumParams(h, kCnnDriver, num_params);
     }
 
     int okenv_cnn_set_params(okenv_t h, const float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kCnnDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
-            return rc;
-        const ok_cnn_shape s = okCnnShape(h->cnn);
-        if (const int rc = driverSet(h, kCnnDriver, {vectorOf(h->cnn_drv.d, params, ok_cnn_offsets(s).total)}))
-            return rc;
-        OkCnnPackParams p{};
-        p.s      = s;
-        p.params = h->cnn_drv.d;
-        p.pack   = h->d_cnn_pack;
-        const unsigned blocks = static_cast<unsigned>((okCnnPlaces(s).pack_total + 255) / 256);
-        hipLaunchKernelGGL(okCnnPackKernel, dim3(blocks), dim3(256), 0, h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return flatSetParams(h, kCnnDriver, 0, params);
     }
 
     int okenv_cnn_get_params(okenv_t h, float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kCnnDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
-            return rc;
-        return driverGet(h, {vectorOf(h->cnn_drv.d, params, ok_cnn_offsets(okCnnShape(h->cnn)).total)});
+        return flatGetParams(h, kCnnDriver, 0, params);
     }
 
     int okenv_cnn_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_cnn_record *rec)
@@ -5354,20 +5454,12 @@ extern "C"
             return driverRefuses(h, OKENV_ERR_INVALID, kWorldDriver, "create", why);
         const ok_world_shape s = okWorldShape(*config);
         h->mem_drv.ok          = false; // (a memory belongs to the racers it was created on: okenv_memory_create attaches a new one)
+        const OkWorldPlaces  pl = okWorldPlaces(s, static_cast<size_t>(h->shape.N));
         // (the conv kernels' 16.5 KB and their row table fit the default limit; the latent kernel, up to 32.1 KB, has the limit raised)
-        if (const int rc = driverCreateFlat(h, kWorldDriver, static_cast<size_t>(ok_world_offsets(s).total), kernelOf(okWorldLatentKernel)))
+        if (const int rc = driverCreateFlat(h, kWorldDriver, static_cast<size_t>(ok_world_offsets(s).total), {kernelOf(okWorldLatentKernel)},
+                                            {grown(h->world_ws, pl.words)}))
             return rc;
-        h->world_drv.ok     = false; // (until the workspace stands)
-        h->world_drv.set[1] = false;
-        const OkWorldPlaces pl = okWorldPlaces(s, static_cast<size_t>(h->shape.N));
-        if (pl.words > h->world_ws_cap)
-        {
-            h->world_ws_cap = 0; // (a failed allocation leaves none)
-            if (const int rc = regrow(h, {fresh(h->d_world_ws, pl.words)}))
-                return rc;
-            h->world_ws_cap = pl.words;
-        }
-        OK_HIP(h, hipMemsetAsync(h->d_world_ws + pl.fitness, 0, sizeof(float) * static_cast<size_t>(h->shape.N), h->stream));
+        OK_HIP(h, hipMemsetAsync(h->world_ws.d + pl.fitness, 0, sizeof(float) * static_cast<size_t>(h->shape.N), h->stream));
         h->world        = *config;
         h->world_drv.ok = true;
         return OKENV_OK;
@@ -5376,49 +5468,19 @@ extern "C"
     int okenv_world_num_params(okenv_t h, int32_t *encoder, int32_t *controller)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kWorldDriver, "num_params", kGateArgFirst | kGateCreated, encoder != nullptr && controller != nullptr))
-            return rc;
-        const ok_world_shape s = okWorldShape(h->world);
-        *encoder               = ok_world_offsets(s).total;
-        *controller            = ok_world_controller_params(s);
-        return OKENV_OK;
+        return flatNumParams(h, kWorldDriver, encoder, controller);
     }
 
     int okenv_world_set_params(okenv_t h, int32_t which, const float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kWorldDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
-            return rc;
-        if (which != OKENV_WORLD_ENCODER && which != OKENV_WORLD_CONTROLLERS)
-            return driverRefuses(h, OKENV_ERR_INVALID, kWorldDriver, "set_params", "which must be OKENV_WORLD_ENCODER or OKENV_WORLD_CONTROLLERS");
-        const ok_world_shape s  = okWorldShape(h->world);
-        const OkWorldPlaces  pl = okWorldPlaces(s, static_cast<size_t>(h->shape.N));
-        if (which == OKENV_WORLD_CONTROLLERS)
-            return driverSet(h, kWorldDriver, {vectorOf(h->d_world_ws + pl.ctrl, params, h->shape.N * ok_world_controller_params(s), 1)});
-        if (const int rc = driverSet(h, kWorldDriver, {vectorOf(h->world_drv.d, params, ok_world_offsets(s).total)}))
-            return rc;
-        OkWorldPackParams p{};
-        p.s      = s;
-        p.params = h->world_drv.d;
-        p.pack   = h->d_world_ws;
-        hipLaunchKernelGGL(okWorldPackKernel, dim3(static_cast<unsigned>((pl.pack_total + 255) / 256)), dim3(256), 0, h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return flatSetParams(h, kWorldDriver, which, params);
     }
 
     int okenv_world_get_params(okenv_t h, int32_t which, float *params)
     {
         OK_QUIESCE(h);
-        const bool controllers = which == OKENV_WORLD_CONTROLLERS;
-        if (const int rc = driverGate(h, kWorldDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, controllers ? 2U : 1U))
-            return rc;
-        if (which != OKENV_WORLD_ENCODER && !controllers)
-            return driverRefuses(h, OKENV_ERR_INVALID, kWorldDriver, "get_params", "which must be OKENV_WORLD_ENCODER or OKENV_WORLD_CONTROLLERS");
-        const ok_world_shape s = okWorldShape(h->world);
-        if (controllers)
-            return driverGet(h, {vectorOf(h->d_world_ws + okWorldPlaces(s, static_cast<size_t>(h->shape.N)).ctrl, params,
-                                          h->shape.N * ok_world_controller_params(s))});
-        return driverGet(h, {vectorOf(h->world_drv.d, params, ok_world_offsets(s).total)});
+        return flatGetParams(h, kWorldDriver, which, params);
     }
 
     int okenv_world_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_world_record *rec)
@@ -5457,7 +5519,7 @@ extern "C"
         if (const int rc = driverGate(h, kWorldDriver, "score_begin", kGateHandle | kGateCreated))
             return rc;
         const size_t at = okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).fitness;
-        OK_HIP(h, hipMemsetAsync(h->d_world_ws + at, 0, sizeof(float) * static_cast<size_t>(h->shape.N), h->stream));
+        OK_HIP(h, hipMemsetAsync(h->world_ws.d + at, 0, sizeof(float) * static_cast<size_t>(h->shape.N), h->stream));
         return OKENV_OK;
     }
 
@@ -5471,7 +5533,7 @@ extern "C"
         OK_HIP(h, hipSetDevice(h->device));
         const size_t at = okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).fitness;
         hipLaunchKernelGGL(okWorldScoreKernel, dim3((h->shape.N + 255) / 256), dim3(256), 0, h->stream, h->st, h->shape.N, h->d_cx, h->d_cy,
-                           h->d_world_widths, h->d_world_widths + h->P, h->P, h->d_world_ws + at);
+                           h->d_world_widths, h->d_world_widths + h->P, h->P, h->world_ws.d + at);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -5482,7 +5544,7 @@ extern "C"
         if (const int rc = driverGate(h, kWorldDriver, "fitness", kGateArgFirst | kGateCreated, out != nullptr))
             return rc;
         const size_t at = okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).fitness;
-        return driverGet(h, {vectorOf(h->d_world_ws + at, out, h->shape.N)});
+        return driverGet(h, {vectorOf(h->world_ws.d + at, out, h->shape.N)});
     }
 
     int okenv_world_fitness_device(okenv_t h, float **ptr)
@@ -5490,7 +5552,7 @@ extern "C"
         OK_QUIESCE(h);
         if (const int rc = driverGate(h, kWorldDriver, "fitness_device", kGateArgFirst | kGateCreated, ptr != nullptr))
             return rc;
-        *ptr = h->d_world_ws + okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).fitness;
+        *ptr = h->world_ws.d + okWorldPlaces(okWorldShape(h->world), static_cast<size_t>(h->shape.N)).fitness;
         return OKENV_OK;
     }
 
@@ -5550,19 +5612,11 @@ extern "C"
         if (const char *why = okMemoryCheckConfig(&h->world, config))
             return driverRefuses(h, OKENV_ERR_INVALID, kMemoryDriver, "create", why);
         const ok_memory_shape s = okMemoryShape(h->world, *config);
-        if (const int rc = driverCreateFlat(h, kMemoryDriver, static_cast<size_t>(ok_memory_offsets(s).total), kernelOf(okMemoryLayerKernel)))
-            return rc;
-        h->mem_drv.ok     = false; // (until the workspace stands)
-        h->mem_drv.set[1] = false;
         const OkMemoryPlaces pl = okMemoryPlaces(s, static_cast<size_t>(h->shape.N));
-        if (pl.words > h->mem_ws_cap)
-        {
-            h->mem_ws_cap = 0; // (a failed allocation leaves none)
-            if (const int rc = regrow(h, {fresh(h->d_mem_ws, pl.words)}))
-                return rc;
-            h->mem_ws_cap = pl.words;
-        }
-        OK_HIP(h, hipMemsetAsync(h->d_mem_ws + pl.hidden, 0, sizeof(float) * static_cast<size_t>(h->shape.N) * s.L * s.H, h->stream));
+        if (const int rc = driverCreateFlat(h, kMemoryDriver, static_cast<size_t>(ok_memory_offsets(s).total), {kernelOf(okMemoryLayerKernel)},
+                                            {grown(h->mem_ws, pl.words)}))
+            return rc;
+        OK_HIP(h, hipMemsetAsync(h->mem_ws.d + pl.hidden, 0, sizeof(float) * static_cast<size_t>(h->shape.N) * s.L * s.H, h->stream));
         h->mem        = *config;
         h->mem_drv.ok = true;
         return OKENV_OK;
@@ -5571,56 +5625,19 @@ extern "C"
     int okenv_memory_num_params(okenv_t h, int32_t *network, int32_t *controller)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kMemoryDriver, "num_params", kGateArgFirst | kGateCreated, network != nullptr && controller != nullptr))
-            return rc;
-        const ok_memory_shape s = memoryShape(h);
-        *network                = ok_memory_offsets(s).total;
-        *controller             = ok_memory_controller_params(s);
-        return OKENV_OK;
+        return flatNumParams(h, kMemoryDriver, network, controller);
     }
 
     int okenv_memory_set_params(okenv_t h, int32_t which, const float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kMemoryDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
-            return rc;
-        if (which != OKENV_MEMORY_NETWORK && which != OKENV_MEMORY_CONTROLLERS)
-            return driverRefuses(h, OKENV_ERR_INVALID, kMemoryDriver, "set_params", "which must be OKENV_MEMORY_NETWORK or OKENV_MEMORY_CONTROLLERS");
-        const ok_memory_shape  s  = memoryShape(h);
-        const OkMemoryPlaces   pl = okMemoryPlaces(s, static_cast<size_t>(h->shape.N));
-        const ok_memory_layout at = ok_memory_offsets(s);
-        if (which == OKENV_MEMORY_CONTROLLERS)
-            return driverSet(h, kMemoryDriver, {vectorOf(h->d_mem_ws + pl.ctrl, params, h->shape.N * ok_memory_controller_params(s), 1)});
-        if (const int rc = driverSet(h, kMemoryDriver, {vectorOf(h->mem_drv.d, params, at.total)}))
-            return rc;
-        for (int m = 0; m < 2 * s.L; ++m)
-        {
-            const int       l = m / 2;
-            OkMemoryPackJob j{};
-            j.cols   = 3 * s.H;
-            j.K      = m % 2 == 0 ? okMemoryKin(s, l) : s.H;
-            j.stride = m % 2 == 0 ? ok_memory_in(s, l) : s.H;
-            j.src    = h->mem_drv.d + (m % 2 == 0 ? at.wih[l] : at.whh[l]);
-            j.dst    = h->d_mem_ws + (m % 2 == 0 ? pl.ih[l] : pl.hh[l]);
-            hipLaunchKernelGGL(okMemoryPackKernel, dim3(static_cast<unsigned>((j.cols * j.K + 255) / 256)), dim3(256), 0, h->stream, j);
-            OK_HIP(h, hipGetLastError());
-        }
-        return OKENV_OK;
+        return flatSetParams(h, kMemoryDriver, which, params);
     }
 
     int okenv_memory_get_params(okenv_t h, int32_t which, float *params)
     {
         OK_QUIESCE(h);
-        const bool controllers = which == OKENV_MEMORY_CONTROLLERS;
-        if (const int rc = driverGate(h, kMemoryDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, controllers ? 2U : 1U))
-            return rc;
-        if (which != OKENV_MEMORY_NETWORK && !controllers)
-            return driverRefuses(h, OKENV_ERR_INVALID, kMemoryDriver, "get_params", "which must be OKENV_MEMORY_NETWORK or OKENV_MEMORY_CONTROLLERS");
-        const ok_memory_shape s = memoryShape(h);
-        if (controllers)
-            return driverGet(h, {vectorOf(h->d_mem_ws + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).ctrl, params,
-                                          h->shape.N * ok_memory_controller_params(s))});
-        return driverGet(h, {vectorOf(h->mem_drv.d, params, ok_memory_offsets(s).total)});
+        return flatGetParams(h, kMemoryDriver, which, params);
     }
 
     int okenv_memory_reset(okenv_t h)
@@ -5632,7 +5649,7 @@ extern "C"
         const ok_memory_shape s     = memoryShape(h);
         const long            words = static_cast<long>(h->shape.N) * s.L * s.H;
         hipLaunchKernelGGL(okMemoryResetKernel, dim3(static_cast<unsigned>((words + 255) / 256)), dim3(256), 0, h->stream,
-                           h->d_mem_ws + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).hidden, words);
+                           h->mem_ws.d + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).hidden, words);
         OK_HIP(h, hipGetLastError());
         return OKENV_OK;
     }
@@ -5644,7 +5661,7 @@ extern "C"
             return rc;
         OK_HIP(h, hipSetDevice(h->device));
         const ok_memory_shape s = memoryShape(h);
-        return copyAny(h, h->d_mem_ws + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).hidden, hidden,
+        return copyAny(h, h->mem_ws.d + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).hidden, hidden,
                        sizeof(float) * static_cast<size_t>(h->shape.N) * s.L * s.H);
     }
 
@@ -5654,7 +5671,7 @@ extern "C"
         if (const int rc = driverGate(h, kMemoryDriver, "get_hidden", kGateArgFirst | kGateCreated, hidden != nullptr))
             return rc;
         const ok_memory_shape s = memoryShape(h);
-        return driverGet(h, {vectorOf(h->d_mem_ws + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).hidden, hidden, h->shape.N * s.L * s.H)});
+        return driverGet(h, {vectorOf(h->mem_ws.d + okMemoryPlaces(s, static_cast<size_t>(h->shape.N)).hidden, hidden, h->shape.N * s.L * s.H)});
     }
 
     int okenv_memory_act(okenv_t h, const uint8_t *frames, int64_t frame_bytes, const okenv_memory_record *rec)
@@ -5711,22 +5728,13 @@ extern "C"
         if (const char *why = okQcnnCheckConfig(config))
             return driverRefuses(h, OKENV_ERR_INVALID, kQcnnDriver, "create", why);
         const ok_qcnn_shape s = okQcnnShape(*config);
-        if (const int rc = driverCreateFlat(h, kQcnnDriver, static_cast<size_t>(ok_qcnn_offsets(s).total), kernelOf(okQcnnConvKernel)))
+        if (const int rc = driverCreateFlat(h, kQcnnDriver, static_cast<size_t>(ok_qcnn_offsets(s).total),
+                                            {kernelOf(okQcnnConvKernel), kernelOf(okQcnnHeadKernel<1, 1>), kernelOf(okQcnnHeadKernel<2, 1>),
+                                             kernelOf(okQcnnHeadKernel<3, 1>), kernelOf(okQcnnHeadKernel<4, 1>), kernelOf(okQcnnHeadKernel<1, 2>),
+                                             kernelOf(okQcnnHeadKernel<2, 2>), kernelOf(okQcnnHeadKernel<3, 2>), kernelOf(okQcnnHeadKernel<4, 2>)},
+                                            {grown(h->qcnn_pack, static_cast<size_t>(okQcnnPlaces(s).pack_total)),
+                                             grown(h->qcnn_feat, static_cast<size_t>(h->shape.N) * ok_qcnn_features(s))}))
             return rc;
-        h->qcnn_drv.ok = false; // (until the kernels' own buffers stand)
-        if (const int rc = raiseLdsLimit(h, {kernelOf(okQcnnHeadKernel<1, 1>), kernelOf(okQcnnHeadKernel<2, 1>), kernelOf(okQcnnHeadKernel<3, 1>),
-                                             kernelOf(okQcnnHeadKernel<4, 1>), kernelOf(okQcnnHeadKernel<1, 2>), kernelOf(okQcnnHeadKernel<2, 2>),
-                                             kernelOf(okQcnnHeadKernel<3, 2>), kernelOf(okQcnnHeadKernel<4, 2>)}))
-            return rc;
-        const size_t pack = static_cast<size_t>(okQcnnPlaces(s).pack_total), feat = static_cast<size_t>(h->shape.N) * ok_qcnn_features(s);
-        if (pack > h->qcnn_pack_cap || feat > h->qcnn_feat_cap)
-        {
-            const size_t np = std::max(pack, h->qcnn_pack_cap), nf = std::max(feat, h->qcnn_feat_cap);
-            h->qcnn_pack_cap = h->qcnn_feat_cap = 0; // (a failed allocation leaves none of them)
-            if (const int rc = regrow(h, {fresh(h->d_qcnn_pack, np), fresh(h->d_qcnn_feat, nf)}))
-                return rc;
-            h->qcnn_pack_cap = np, h->qcnn_feat_cap = nf;
-        }
         if (h->qcnn_ring.ok && h->qcnn_ring_side != config->image_size)
             h->qcnn_ring.ok = false; // (its planes had the earlier network's size)
         h->qcnn        = *config;
@@ -5737,36 +5745,19 @@ extern "C"
     int okenv_qcnn_num_params(okenv_t h, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kQcnnDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
-            return rc;
-        *num_params = ok_qcnn_offsets(okQcnnShape(h->qcnn)).total;
-        return OKENV_OK;
+        return flatNumParams(h, kQcnnDriver, num_params);
     }
 
     int okenv_qcnn_set_params(okenv_t h, const float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kQcnnDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
-            return rc;
-        const ok_qcnn_shape s = okQcnnShape(h->qcnn);
-        if (const int rc = driverSet(h, kQcnnDriver, {vectorOf(h->qcnn_drv.d, params, ok_qcnn_offsets(s).total)}))
-            return rc;
-        OkQcnnPackParams p{};
-        p.s      = s;
-        p.params = h->qcnn_drv.d;
-        p.pack   = h->d_qcnn_pack;
-        const unsigned blocks = static_cast<unsigned>((okQcnnPlaces(s).pack_total + 255) / 256);
-        hipLaunchKernelGGL(okQcnnPackKernel, dim3(blocks), dim3(256), 0, h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return flatSetParams(h, kQcnnDriver, 0, params);
     }
 
     int okenv_qcnn_get_params(okenv_t h, float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kQcnnDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
-            return rc;
-        return driverGet(h, {vectorOf(h->qcnn_drv.d, params, ok_qcnn_offsets(okQcnnShape(h->qcnn)).total)});
+        return flatGetParams(h, kQcnnDriver, 0, params);
     }
 
     int okenv_qcnn_set_epsilon(okenv_t h, float epsilon)
@@ -6043,21 +6034,12 @@ extern "C"
         if (const char *why = okBevCheckConfig(config))
             return driverRefuses(h, OKENV_ERR_INVALID, kBevDriver, "create", why);
         const ok_bev_shape s = okBevShape(*config);
-        if (const int rc = driverCreateFlat(h, kBevDriver, static_cast<size_t>(ok_bev_offsets(s).total), kernelOf(okBevFrontKernel<8>)))
-            return rc;
-        h->bev_drv.ok = false; // (until the kernels' own buffers stand)
-        if (const int rc = raiseLdsLimit(h, {kernelOf(okBevFrontKernel<4>), kernelOf(okBevBackKernel<8>), kernelOf(okBevBackKernel<4>)}))
-            return rc;
         const size_t N = static_cast<size_t>(h->shape.N), side1 = static_cast<size_t>(ok_bev_side(s, 1)), side2 = static_cast<size_t>(ok_bev_side(s, 2));
-        const size_t pack = static_cast<size_t>(okBevPlaces(s).pack_total), act1 = N * side1 * side1 * s.c[1], act2 = N * side2 * side2 * s.c[2];
-        if (pack > h->bev_pack_cap || act1 > h->bev_act1_cap || act2 > h->bev_act2_cap)
-        {
-            const size_t np = std::max(pack, h->bev_pack_cap), n1 = std::max(act1, h->bev_act1_cap), n2 = std::max(act2, h->bev_act2_cap);
-            h->bev_pack_cap = h->bev_act1_cap = h->bev_act2_cap = 0; // (a failed allocation leaves none of them)
-            if (const int rc = regrow(h, {fresh(h->d_bev_pack, np), fresh(h->d_bev_act1, n1), fresh(h->d_bev_act2, n2)}))
-                return rc;
-            h->bev_pack_cap = np, h->bev_act1_cap = n1, h->bev_act2_cap = n2;
-        }
+        if (const int rc = driverCreateFlat(h, kBevDriver, static_cast<size_t>(ok_bev_offsets(s).total),
+                                            {kernelOf(okBevFrontKernel<8>), kernelOf(okBevFrontKernel<4>), kernelOf(okBevBackKernel<8>), kernelOf(okBevBackKernel<4>)},
+                                            {grown(h->bev_pack, static_cast<size_t>(okBevPlaces(s).pack_total)), grown(h->bev_act1, N * side1 * side1 * s.c[1]),
+                                             grown(h->bev_act2, N * side2 * side2 * s.c[2])}))
+            return rc;
         h->bev        = *config;
         h->bev_drv.ok = true;
         return OKENV_OK;
@@ -6066,37 +6048,19 @@ extern "C"
     int okenv_bev_num_params(okenv_t h, int32_t *num_params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kBevDriver, "num_params", kGateArgFirst | kGateCreated, num_params != nullptr))
-            return rc;
-        *num_params = ok_bev_offsets(okBevShape(h->bev)).total;
-        return OKENV_OK;
+        return flatNumParams(h, kBevDriver, num_params);
     }
 
     int okenv_bev_set_params(okenv_t h, const float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kBevDriver, "set_params", kGateArgFirst | kGateCreated, params != nullptr))
-            return rc;
-        const ok_bev_shape s = okBevShape(h->bev);
-        if (const int rc = driverSet(h, kBevDriver, {vectorOf(h->bev_drv.d, params, ok_bev_offsets(s).total)}))
-            return rc;
-        // the conv kernels' copy of the weights, behind the upload on the stream
-        OkBevPackParams p{};
-        p.s      = s;
-        p.params = h->bev_drv.d;
-        p.pack   = h->d_bev_pack;
-        const unsigned blocks = static_cast<unsigned>((okBevPlaces(s).pack_total + kBevThreads - 1) / kBevThreads);
-        hipLaunchKernelGGL(okBevPackKernel, dim3(blocks), dim3(kBevThreads), 0, h->stream, p);
-        OK_HIP(h, hipGetLastError());
-        return OKENV_OK;
+        return flatSetParams(h, kBevDriver, 0, params);
     }
 
     int okenv_bev_get_params(okenv_t h, float *params)
     {
         OK_QUIESCE(h);
-        if (const int rc = driverGate(h, kBevDriver, "get_params", kGateArgFirst | kGateStored, params != nullptr, 1U))
-            return rc;
-        return driverGet(h, {vectorOf(h->bev_drv.d, params, ok_bev_offsets(okBevShape(h->bev)).total)});
+        return flatGetParams(h, kBevDriver, 0, params);
     }
 
     int okenv_bev_encode(okenv_t h, const uint8_t *frames, int64_t frame_bytes, float *out)
