@@ -6,7 +6,7 @@ to the lane centre -- with the encoder's forward once per step in PyTorch or, wi
     python examples/worldmodel_racer.py [--population 256] [--frame-size 128] [--base-ch 64] [--latent 32] [--demo-agents 64]
                                         [--demo-steps 64] [--epochs 2] [--generations 5] [--max-steps 400] [--graph-chunk 8]
                                         [--device-encoder] [--keep-crashed] [--track Silverstone]
-                                        [--memory] [--memory-hidden 64] [--memory-epochs 2] [--no-carry]
+                                        [--memory] [--memory-hidden 64] [--memory-epochs 2] [--no-carry] [--device-update]
 
 1. record: every living agent's frame while the expert drives (demonstrations.collect_demonstrations(images=True));
 2. train: binary cross-entropy of the reconstruction plus the KL term, Adam 2e-4 (train_vae.py);
@@ -16,7 +16,8 @@ to the lane centre -- with the encoder's forward once per step in PyTorch or, wi
 
 With --memory the racer is the reference's Vision + Memory + Controller: between 2 and 3 the expert drives again, the latents come from
 the device encoder (worldmodel.collect_latents), the GRU dynamics model is trained on them with the reference's recipe
-(worldmodel.train_memory), and every candidate's controller reads [mu | h_top] (okenv_memory_act with --device-encoder).
+(worldmodel.train_memory, or with --device-update on the device: worldmodel.train_memory_device, okenv_memory_update), and every
+candidate's controller reads [mu | h_top] (okenv_memory_act with --device-encoder).
 """
 import argparse
 import os
@@ -55,6 +56,7 @@ def main(argv=None):
     ap.add_argument("--memory-layers", type=int, default=wm.MEMORY_LAYERS)
     ap.add_argument("--memory-epochs", type=int, default=2)
     ap.add_argument("--no-carry", action="store_true", help="the reference as written: the hidden state starts from zero at every act")
+    ap.add_argument("--device-update", action="store_true", help="train the memory on the device (okenv_memory_update) instead of in PyTorch")
     a = ap.parse_args(argv)
     torch.manual_seed(a.seed)
     # 1. frames
@@ -79,14 +81,19 @@ def main(argv=None):
         latents, actions, alive = wm.collect_latents(venv, a.demo_steps, drive=lambda v: v.expert_act())
         memory = wm.GRUDynamics(a.latent, a.memory_hidden, a.memory_layers).to(device)
         t0 = time.perf_counter()
-        memory_losses, memory_stats = wm.train_memory(memory, latents, actions, alive, epochs=a.memory_epochs, seed=a.seed)
-        print("trained the memory (H = %d, %d layers) %d epochs in %.1f s: loss %s"
-              % (a.memory_hidden, a.memory_layers, a.memory_epochs, time.perf_counter() - t0, " ".join("%.5g" % v for v in memory_losses)))
+        if a.device_update:  # the same recipe in the device's kernels; the trained vector carries its statistics
+            memory_losses, memory_stats, memory = wm.train_memory_device(venv, memory, latents, actions, alive, epochs=a.memory_epochs, seed=a.seed,
+                                                                         carry=not a.no_carry)
+        else:
+            memory_losses, memory_stats = wm.train_memory(memory, latents, actions, alive, epochs=a.memory_epochs, seed=a.seed)
+        print("trained the memory (H = %d, %d layers) %d epochs %s in %.1f s: loss %s"
+              % (a.memory_hidden, a.memory_layers, a.memory_epochs, "on the device" if a.device_update else "in PyTorch", time.perf_counter() - t0,
+                 " ".join("%.5g" % v for v in memory_losses)))
     venv.close()
     # 3. generations
     racers = wm.WorldModelRacers(a.track, a.population, model.enc, seed=a.seed, encoder="device" if a.device_encoder else "torch",
                                  max_steps=a.max_steps, graph_chunk=a.graph_chunk, skip_crashed=not a.keep_crashed, memory=memory,
-                                 memory_stats=memory_stats, carry=not a.no_carry)
+                                 memory_stats=memory_stats, carry=not a.no_carry, memory_shape=(a.memory_hidden, a.memory_layers))
     first = None
     if a.device_encoder and not a.memory:  # the first frames, both ways: the device's mu against the PyTorch module's
         racers.venv.reset()

@@ -1300,6 +1300,75 @@ OKENV_API int okenv_memory_act_host(const okenv_world_config *world, const okenv
                                     const float *controllers, int32_t n, const uint8_t *frames, const uint8_t *crashed, float *hidden,
                                     float *throttle, float *steer, const okenv_memory_record *rec);
 
+/* ---- The memory's training ------------------------------------------------------------------------------------
+ * train_rnn.py's recipe for the network of okenv_memory_create on the device: windows of seq_len steps over recorded latents and
+ * actions, teacher forcing, mean squared error on the normalised next latent, backpropagation through time, clipping by the global
+ * norm, AdamW.  The rule is written out in include/okenv_memtrain.h (ok_memtrain_*); every contraction runs on the f32-input matrix
+ * cores.  The statistics at the network vector's end are not trained. */
+typedef struct okenv_memory_learner_config {
+    float   lr;           /* > 0; the rate of a minibatch without a schedule     (the reference: 1e-3) */
+    float   beta1;        /* [0, 1), torch: 0.9                                                         */
+    float   beta2;        /* [0, 1), torch: 0.999                                                       */
+    float   eps;          /* > 0, torch: 1e-8                                                           */
+    float   weight_decay; /* >= 0, AdamW's                                       (1e-4)                 */
+    float   clip_grad;    /* >= 0, the global norm's limit; 0: no clipping       (1.0)                  */
+    int32_t seq_len;      /* S: steps of a window, 1 .. 16                       (5)                    */
+    int32_t max_batch;    /* the most windows a minibatch may hold               (256)                  */
+} okenv_memory_learner_config;
+
+/* The network vector (all of it, statistics included) and Adam's moments of its trainable prefix (the vector without its last
+ * 2 Z + 4 floats); t: steps taken so far. */
+typedef struct okenv_memory_learner_state {
+    float  *params, *m, *v;
+    int64_t t;
+} okenv_memory_learner_state;
+
+/* Where an update reports: device pointers (host pointers for okenv_memory_update_host), each may be NULL (skipped). */
+typedef struct okenv_memory_learner_output {
+    float *loss; /* [epochs * ceil(M / B)]  per minibatch, from before its step                        */
+    float *norm; /* [epochs * ceil(M / B)]  the gradient's global norm before clipping                 */
+    float *grad; /* the last minibatch's gradient after clipping, [trainable prefix]                   */
+} okenv_memory_learner_output;
+
+/* Device bytes okenv_memory_learner_create allocates, and the LDS bytes of its largest kernel (0: the kernels keep their operands in
+ * registers): pure host functions.  0 for a NULL or refused argument. */
+OKENV_API int64_t okenv_memory_learner_workspace_bytes(const okenv_world_config *world, const okenv_memory_config *config,
+                                                       const okenv_memory_learner_config *learner);
+OKENV_API int64_t okenv_memory_learner_lds_bytes(const okenv_world_config *world, const okenv_memory_config *config);
+/* Attaches the learner (m = v = 0, t = 0) to the handle's memory; all its device memory is allocated here.  A later
+ * okenv_memory_create or okenv_world_create drops it.  OKENV_ERR_STATE before okenv_memory_create or before the network's parameters
+ * are set; OKENV_ERR_INVALID for NULL arguments or values outside the ranges above. */
+OKENV_API int okenv_memory_learner_create(okenv_t h, const okenv_memory_learner_config *config);
+/* m = v = 0, t = 0 again. */
+OKENV_API int okenv_memory_learner_reset(okenv_t h);
+/* The network vector and Adam's moments to host or device pointers (each may be NULL), and t; synchronises. */
+OKENV_API int okenv_memory_learner_get_state(okenv_t h, okenv_memory_learner_state *out);
+/* Enqueues every minibatch of every epoch on the handle's stream: no synchronisation, no allocation, capturable (the step number lives
+ * on the device, so a replay takes the steps that follow).  latent [rows][Z], action [rows][2], start [M] (int32 rows): device; `order`
+ * a device array [epochs][M] of int32 window indices or NULL (sequential); lr_schedule a HOST array [epochs * ceil(M / B)] or NULL (the
+ * config's lr).  Step s of window w reads row start[w] + s * stride, and its target is the row a stride further; rows and indices
+ * outside their range count as the nearest valid one.  Steps the handle's network vector in place and renews the act's copy of its
+ * matrices: the next okenv_memory_act on the stream acts with the new network, okenv_memory_get_params returns it.  No agent field and
+ * no hidden state is touched.  OKENV_ERR_STATE before okenv_memory_learner_create; OKENV_ERR_INVALID for a NULL handle or array, rows,
+ * M, B or epochs < 1, B above max_batch (where M is above it too), epochs * M >= 2^31. */
+OKENV_API int okenv_memory_update(okenv_t h, const float *latent, const float *action, int32_t rows, const int32_t *start, int32_t M, int32_t stride,
+                                  int32_t B, int32_t epochs, const int32_t *order, const float *lr_schedule, const okenv_memory_learner_output *out);
+/* The loss of every minibatch of one sequential pass with no step, to loss [ceil(M / B)] (device): the validation loop. */
+OKENV_API int okenv_memory_eval(okenv_t h, const float *latent, const float *action, int32_t rows, const int32_t *start, int32_t M, int32_t stride, int32_t B,
+                                float *loss);
+/* The same rule on host arrays, no GPU needed.  Refuse a network vector with a non-finite value or a std <= 0. */
+OKENV_API int okenv_memory_update_host(const okenv_world_config *world, const okenv_memory_config *config, const okenv_memory_learner_config *learner,
+                                       okenv_memory_learner_state *state, const float *latent, const float *action, int32_t rows, const int32_t *start,
+                                       int32_t M, int32_t stride, int32_t B, int32_t epochs, const int32_t *order, const float *lr_schedule,
+                                       const okenv_memory_learner_output *out);
+OKENV_API int okenv_memory_eval_host(const okenv_world_config *world, const okenv_memory_config *config, const okenv_memory_learner_config *learner,
+                                     const float *network, const float *latent, const float *action, int32_t rows, const int32_t *start, int32_t M,
+                                     int32_t stride, int32_t B, float *loss);
+/* The update's forward of ONE window on the host, for tests: hidden [seq_len][layers][hidden] and zn [seq_len][Z], the hidden states
+ * behind every step and the head's normalised predictions. */
+OKENV_API int okenv_memory_window_host(const okenv_world_config *world, const okenv_memory_config *config, const float *network, const float *latent,
+                                       const float *action, int32_t rows, int32_t start, int32_t stride, int32_t seq_len, float *hidden, float *zn);
+
 /* ---- Deep-Q image racers ------------------------------------------------------------------------------------
  * RLRacers/DQN_CNN (CNN.hpp, DQCNNAgent.hpp, dq_cnn_racer_sim.cpp) for every agent of the handle: from the camera's RGBA8 frames
  * (okenv_render_views, rendered at image_size x image_size) one grey plane, three PADDED convolutions with ReLU, the flatten, fc1 with

@@ -113,6 +113,9 @@ SYMBOLS = [
     "okenv_memory_lds_bytes", "okenv_memory_plan", "okenv_memory_workspace_bytes", "okenv_memory_create", "okenv_memory_num_params",
     "okenv_memory_set_params", "okenv_memory_get_params", "okenv_memory_reset", "okenv_memory_set_hidden", "okenv_memory_get_hidden",
     "okenv_memory_act", "okenv_debug_memory_stages", "okenv_memory_act_host",
+    "okenv_memory_learner_workspace_bytes", "okenv_memory_learner_lds_bytes", "okenv_memory_learner_create", "okenv_memory_learner_reset",
+    "okenv_memory_learner_get_state", "okenv_memory_update", "okenv_memory_eval", "okenv_memory_update_host", "okenv_memory_eval_host",
+    "okenv_memory_window_host",
     "okenv_qcnn_lds_bytes", "okenv_qcnn_plan", "okenv_qcnn_create", "okenv_qcnn_num_params", "okenv_qcnn_set_params", "okenv_qcnn_get_params",
     "okenv_qcnn_set_epsilon", "okenv_qcnn_set_draw_offset", "okenv_qcnn_act", "okenv_debug_qcnn_stages", "okenv_qcnn_ring_create",
     "okenv_qcnn_ring_reset", "okenv_qcnn_ring_size", "okenv_qcnn_ring_get", "okenv_qcnn_push", "okenv_qcnn_batch", "okenv_qcnn_act_host",
@@ -1147,6 +1150,93 @@ def memory_act_host(world, cfg, encoder, network, controllers, frames, hidden, t
     return out
 
 
+# the memory's training (include/okenv.h)
+MEMORY_TRAIN_BLOCK, MEMORY_TRAIN_MAX_SEQ = 64, 16
+
+
+class OkenvMemoryLearnerConfig(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("clip_grad", C.c_float),
+                ("seq_len", C.c_int32), ("max_batch", C.c_int32)]
+
+
+class OkenvMemoryLearnerState(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("t", C.c_int64)]
+
+
+class OkenvMemoryLearnerOutput(C.Structure):
+    _fields_ = [("loss", C.c_void_p), ("norm", C.c_void_p), ("grad", C.c_void_p)]
+
+
+def memory_learner_config(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-4, clip_grad=1.0, seq_len=5, max_batch=256):
+    """okenv_memory_learner_config with train_rnn.py's values as defaults."""
+    return OkenvMemoryLearnerConfig(float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), float(clip_grad), int(seq_len), int(max_batch))
+
+
+def memory_trainable(world, cfg):
+    """Floats of the trainable prefix of the network vector: everything in front of the statistics."""
+    return memory_num_params(world, cfg)[0] - (2 * world.latent + 4)
+
+
+def memory_learner_workspace_bytes(world, cfg, learner):
+    """okenv_memory_learner_workspace_bytes: device bytes okenv_memory_learner_create allocates; 0 for a refused argument.  No GPU needed."""
+    return int(load().okenv_memory_learner_workspace_bytes(C.byref(world), C.byref(cfg), C.byref(learner)))
+
+
+def memory_learner_lds_bytes(world, cfg):
+    """okenv_memory_learner_lds_bytes: the LDS of the learner's largest kernel.  No GPU needed."""
+    return int(load().okenv_memory_learner_lds_bytes(C.byref(world), C.byref(cfg)))
+
+
+def _memory_windows_args(world, latent, action, start):
+    latent = None if latent is None else np.ascontiguousarray(latent, np.float32).reshape(-1, world.latent)
+    action = None if action is None else np.ascontiguousarray(action, np.float32).reshape(-1, 2)
+    start = None if start is None else np.ascontiguousarray(start, np.int32).ravel()
+    return latent, action, start, (int(latent.shape[0]) if latent is not None else 0), (int(start.size) if start is not None else 0)
+
+
+def memory_update_host(world, cfg, learner, state, latent, action, start, B, stride=1, epochs=1, order=None, lr_schedule=None, want=("loss", "norm", "grad")):
+    """The memory's update on host arrays, no GPU needed (okenv_memory_update_host).  state: dict of float32 numpy arrays "params" (the
+    whole network vector), "m", "v" (its trainable prefix) and the int "t" -- copied, the new state is returned; latent [rows, Z],
+    action [rows, 2], start [M] int32; order: None or int32 [epochs, M]; lr_schedule: None or float32 [epochs * ceil(M / B)].  Returns
+    (new state, outputs): "loss" and "norm" hold one value per minibatch, "grad" the last minibatch's clipped gradient."""
+    latent, action, start, rows, M = _memory_windows_args(world, latent, action, start)
+    new = {k: np.array(v, dtype=np.float32, copy=True).ravel() for k, v in state.items() if k != "t" and v is not None}
+    st = fill_pointers(OkenvMemoryLearnerState(), new, "memory learner state")
+    st.t = int(state.get("t", 0))
+    steps = int(epochs) * ((M + int(B) - 1) // int(B)) if M > 0 and B > 0 and epochs > 0 else 0
+    sizes = {"loss": steps, "norm": steps, "grad": memory_trainable(world, cfg)}
+    outs = {k: np.zeros(sizes[k], dtype=np.float32) for k in want}
+    order = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+    lr_schedule = None if lr_schedule is None else np.ascontiguousarray(lr_schedule, dtype=np.float32)
+    assert lr_schedule is None or lr_schedule.size == steps
+    check(load().okenv_memory_update_host(C.byref(world), C.byref(cfg), C.byref(learner) if learner is not None else None, C.byref(st), ptr(latent), ptr(action),
+                                          rows, ptr(start), M, int(stride), int(B), int(epochs), ptr(order), ptr(lr_schedule),
+                                          C.byref(fill_pointers(OkenvMemoryLearnerOutput(), {k: v for k, v in outs.items() if v.size}, "memory learner output"))))
+    new["t"] = int(st.t)
+    return new, outs
+
+
+def memory_eval_host(world, cfg, learner, network, latent, action, start, B, stride=1):
+    """okenv_memory_eval_host: the loss of every minibatch of one sequential pass, float32 [ceil(M / B)].  No GPU needed."""
+    latent, action, start, rows, M = _memory_windows_args(world, latent, action, start)
+    network = np.ascontiguousarray(network, np.float32)
+    loss = np.zeros((M + int(B) - 1) // int(B) if M > 0 and B > 0 else 0, np.float32)
+    check(load().okenv_memory_eval_host(C.byref(world), C.byref(cfg), C.byref(learner), ptr(network), ptr(latent), ptr(action), rows, ptr(start), M, int(stride),
+                                        int(B), ptr(loss)))
+    return loss
+
+
+def memory_window_host(world, cfg, network, latent, action, start, seq_len, stride=1):
+    """okenv_memory_window_host: the update's forward of one window -> (hidden [S, L, H], zn [S, Z]).  No GPU needed."""
+    latent, action, _, rows, _ = _memory_windows_args(world, latent, action, None)
+    network = np.ascontiguousarray(network, np.float32)
+    hidden = np.zeros((int(seq_len), cfg.layers, cfg.hidden), np.float32)
+    zn = np.zeros((int(seq_len), world.latent), np.float32)
+    check(load().okenv_memory_window_host(C.byref(world), C.byref(cfg), ptr(network), ptr(latent), ptr(action), rows, int(start), int(stride), int(seq_len),
+                                          ptr(hidden), ptr(zn)))
+    return hidden, zn
+
+
 # guided cost learning (include/okenv.h)
 GCL_POLICY,GCL_VALUE, GCL_COST = 0, 1, 2
 GCL_NETWORKS = {"policy": GCL_POLICY, "value": GCL_VALUE, "cost": GCL_COST}
@@ -1572,6 +1662,20 @@ def load(build_if_missing=True):
     L.okenv_memory_act.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvMemoryRecord)]
     L.okenv_debug_memory_stages.argtypes = [vp, vp, C.c_int64, C.POINTER(OkenvMemoryRecord), C.c_uint32]
     L.okenv_memory_act_host.argtypes = [wc, mc, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(OkenvMemoryRecord)]
+    lc = C.POINTER(OkenvMemoryLearnerConfig)
+    L.okenv_memory_learner_workspace_bytes.argtypes = [wc, mc, lc]
+    L.okenv_memory_learner_workspace_bytes.restype = C.c_int64
+    L.okenv_memory_learner_lds_bytes.argtypes = [wc, mc]
+    L.okenv_memory_learner_lds_bytes.restype = C.c_int64
+    L.okenv_memory_learner_create.argtypes = [vp, lc]
+    L.okenv_memory_learner_reset.argtypes = [vp]
+    L.okenv_memory_learner_get_state.argtypes = [vp, C.POINTER(OkenvMemoryLearnerState)]
+    L.okenv_memory_update.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, C.POINTER(OkenvMemoryLearnerOutput)]
+    L.okenv_memory_eval.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp]
+    L.okenv_memory_update_host.argtypes = [wc, mc, lc, C.POINTER(OkenvMemoryLearnerState), vp, vp, i32, vp, i32, i32, i32, i32, vp, vp,
+                                           C.POINTER(OkenvMemoryLearnerOutput)]
+    L.okenv_memory_eval_host.argtypes = [wc, mc, lc, vp, vp, vp, i32, vp, i32, i32, i32, vp]
+    L.okenv_memory_window_host.argtypes = [wc, mc, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     qc, i64 = C.POINTER(OkenvQcnnConfig), C.c_int64
     L.okenv_qcnn_lds_bytes.argtypes = [qc]
     L.okenv_qcnn_lds_bytes.restype = C.c_int64

@@ -37,6 +37,7 @@
 #include "ok_cnn.h"
 #include "ok_world.h"
 #include "ok_memory.h"
+#include "ok_memtrain.h"
 #include "ok_qcnn.h"
 #include "ok_vit.h"
 #include "ok_vithead.h"
@@ -615,6 +616,11 @@ struct okenv
     OkDriver                mem_drv;
     okenv_memory_config     mem{};
     OkBuffer                mem_ws;
+    // ... and its learner (okenv_memory_learner_create): Adam's moments, the step number and every buffer of a minibatch in one
+    // workspace (okMemTrainPlaces), allocated at create
+    bool                        mem_learn_ok{false};
+    okenv_memory_learner_config mem_learn{};
+    OkBuffer                    mem_learn_ws;
     // Deep-Q image racers (okenv_qcnn_create, okenv_qcnn_ring_create): the parameter vector in torch's order; the kernels' copy of the
     // weights and the features that pass from the conv kernel to the head, both allocated at create; the frame ring (its planes have
     // the network's image_size) and the push's slot of every agent
@@ -2331,6 +2337,191 @@ int memoryRepack(okenv *h)
         OK_HIP(h, hipGetLastError());
     }
     return OKENV_OK;
+}
+
+// One job of the product kernel as a list of one
+int memTrainProduct(okenv *h, const OkMemTrainGemm &job)
+{
+    OkMemTrainGemmJobs js{};
+    js.count  = 1;
+    js.job[0] = job;
+    hipLaunchKernelGGL(okMemTrainGemmKernel, dim3(static_cast<unsigned>((okMemTrainTiles(job) + kMemTrainWaves - 1) / kMemTrainWaves), 1U), dim3(kMemTrainThreads), 0,
+                       h->stream, js);
+    OK_HIP(h, hipGetLastError());
+    return OKENV_OK;
+}
+
+// okenv_memory_update (update == true: `epochs` passes in `order`, a step per minibatch) and okenv_memory_eval (one sequential pass, the
+// losses only) behind their OK_QUIESCE: the launches of ok_memtrain.h on the stream
+int memoryLearnRun(okenv *h, const char *entry, const bool update, const float *latent, const float *action, const int32_t rows, const int32_t *start,
+                   const int32_t M, const int32_t stride, const int32_t B, const int32_t epochs, const int32_t *order, const float *lr_schedule, float *loss,
+                   float *norm, float *grad_out)
+{
+    if (!h)
+        return fail(h, OKENV_ERR_INVALID, std::string(entry) + ": NULL handle");
+    if (!h->mem_drv.ok || !h->mem_learn_ok)
+        return fail(h, OKENV_ERR_STATE, std::string(entry) + ": call okenv_memory_learner_create first");
+    if (const char *why = okMemTrainCheckCall(latent, action, rows, start, M, B, epochs))
+        return fail(h, OKENV_ERR_INVALID, std::string(entry) + ": " + why);
+    const okenv_memory_learner_config &c = h->mem_learn;
+    if (std::min(B, M) > c.max_batch)
+        return fail(h, OKENV_ERR_INVALID, std::string(entry) + ": a minibatch of min(B, M) windows is beyond the learner's max_batch");
+    OK_HIP(h, hipSetDevice(h->device));
+    const ok_memory_shape  s  = memoryShape(h);
+    const ok_memory_layout at = ok_memory_offsets(s);
+    const int              Z = s.Z, H = s.H, H3 = 3 * s.H, S = c.seq_len, Bmax = c.max_batch, in0 = Z + OK_MEMORY_ACTIONS, T = ok_memtrain_trainable(s);
+    const OkMemTrainPlaces pl = okMemTrainPlaces(s, S, Bmax);
+    float                 *ws = h->mem_learn_ws.d, *net = h->mem_drv.d, *g = ws + pl.grad;
+    long long             *t_dev = reinterpret_cast<long long *>(ws + pl.scalars + kMemTrainStepAt);
+    ok_learn_adam_consts  *adam_dev = reinterpret_cast<ok_learn_adam_consts *>(ws + pl.scalars + kMemTrainConstsAt);
+    const int              slices = okLearnMinibatches(M, B);
+    const auto blocks = [](const long n) { return dim3(static_cast<unsigned>((n + 255) / 256)); };
+    for (int e = 0; e < epochs; ++e)
+        for (int k = 0; k < slices; ++k)
+        {
+            const long   base = static_cast<long>(k) * B;
+            const int    Bk = static_cast<int>(std::min<long>(B, M - base)), P = Bk * S;
+            const size_t at_step = static_cast<size_t>(e) * slices + k;
+            const float  count = static_cast<float>(Bk * S * Z);
+            // a layer's rows: h_prev of position p at hp + p H, its h' at hp + (Bk + p) H
+            const auto hp = [&](const int l) { return ws + pl.h[l] + static_cast<size_t>(Bmax - Bk) * H; };
+            OkMemTrainGatherJob gj{};
+            gj.latent = latent, gj.action = action, gj.net = net, gj.start = start;
+            gj.order = order != nullptr ? order + static_cast<size_t>(e) * M : nullptr;
+            gj.x0 = ws + pl.x0, gj.y = ws + pl.y, gj.base = base, gj.rows = rows, gj.M = M, gj.stride = stride, gj.Bk = Bk, gj.S = S, gj.Z = Z, gj.at = at;
+            hipLaunchKernelGGL(okMemTrainGatherKernel, blocks(static_cast<long>(P) * (2 * Z + OK_MEMORY_ACTIONS)), dim3(256), 0, h->stream, gj);
+            OK_HIP(h, hipGetLastError());
+            // ---- forward, layer by layer
+            for (int l = 0; l < s.L; ++l)
+            {
+                const int      in = ok_memory_in(s, l);
+                OkMemTrainGemm gi{};
+                gi.a = l == 0 ? ws + pl.x0 : hp(l - 1) + static_cast<size_t>(Bk) * H, gi.a_rs = l == 0 ? in0 : H, gi.a_cs = 1;
+                gi.b = net + at.wih[l], gi.b_rs = 1, gi.b_cs = in, gi.bias = net + at.bih[l];
+                gi.c = ws + pl.gi, gi.c_rs = H3, gi.M = P, gi.N = H3, gi.K = okMemoryKin(s, l);
+                if (const int rc = memTrainProduct(h, gi))
+                    return rc;
+                for (int st = 0; st < S; ++st)
+                {
+                    const size_t   row = static_cast<size_t>(st) * Bk;
+                    OkMemTrainGemm gh{};
+                    gh.a = hp(l) + row * H, gh.a_rs = H, gh.a_cs = 1;
+                    gh.b = net + at.whh[l], gh.b_rs = 1, gh.b_cs = H, gh.bias = net + at.bhh[l];
+                    gh.c = ws + pl.gh, gh.c_rs = H3, gh.M = Bk, gh.N = H3, gh.K = H;
+                    if (const int rc = memTrainProduct(h, gh))
+                        return rc;
+                    OkMemTrainGateJob gt{};
+                    gt.gi = ws + pl.gi + row * H3, gt.gh = ws + pl.gh;
+                    gt.xa = l == 0 ? ws + pl.x0 + row * in0 : nullptr, gt.tail = l == 0 ? net + at.wih[0] : nullptr;
+                    gt.h_prev = hp(l) + row * H, gt.h = hp(l) + (row + Bk) * H;
+                    gt.r = ws + pl.r[l] + row * H, gt.u = ws + pl.u[l] + row * H, gt.n = ws + pl.n[l] + row * H, gt.ghn = ws + pl.ghn[l] + row * H;
+                    gt.Bk = Bk, gt.H = H, gt.Z = Z;
+                    hipLaunchKernelGGL(okMemTrainGateKernel, blocks(static_cast<long>(Bk) * H), dim3(256), 0, h->stream, gt);
+                    OK_HIP(h, hipGetLastError());
+                }
+            }
+            const float   *top = hp(s.L - 1) + static_cast<size_t>(Bk) * H;
+            OkMemTrainGemm hd{};
+            hd.a = top, hd.a_rs = H, hd.a_cs = 1, hd.b = net + at.hw, hd.b_rs = 1, hd.b_cs = H, hd.bias = net + at.hb;
+            hd.c = ws + pl.zn, hd.c_rs = Z, hd.M = P, hd.N = Z, hd.K = H;
+            if (const int rc = memTrainProduct(h, hd))
+                return rc;
+            hipLaunchKernelGGL(okMemTrainSeedKernel, blocks(static_cast<long>(P) * Z), dim3(256), 0, h->stream, ws + pl.zn, ws + pl.y, ws + pl.tt,
+                               static_cast<long>(P) * Z);
+            OK_HIP(h, hipGetLastError());
+            OkMemTrainGemmJobs sums{};
+            OkMemTrainGemm    &lj = sums.job[sums.count++]; // the loss column: the terms against 1.0f
+            lj.a = ws + pl.tt, lj.a_rs = 1, lj.a_cs = Z, lj.b = ws + pl.tt, lj.c = ws + pl.lossj, lj.c_ones = ws + pl.lossj, lj.M = Z, lj.N = 0, lj.K = P;
+            float *loss_at = loss != nullptr ? loss + at_step : ws + pl.scalars + kMemTrainLossAt;
+            if (update)
+            {
+                // ---- backward, top layer first, in a layer from the last step down
+                OkMemTrainGemm dn{};
+                dn.a = ws + pl.zn, dn.a_rs = Z, dn.a_cs = 1, dn.b = net + at.hw, dn.b_rs = H, dn.b_cs = 1;
+                dn.c = ws + pl.down, dn.c_rs = H, dn.M = P, dn.N = H, dn.K = Z;
+                if (const int rc = memTrainProduct(h, dn))
+                    return rc;
+                for (int l = s.L - 1; l >= 0; --l)
+                {
+                    for (int st = S - 1; st >= 0; --st)
+                    {
+                        const size_t      row = static_cast<size_t>(st) * Bk;
+                        OkMemTrainCellJob cj{};
+                        cj.down = ws + pl.down + row * H, cj.back = ws + pl.back, cj.keep = ws + pl.keep;
+                        cj.r = ws + pl.r[l] + row * H, cj.u = ws + pl.u[l] + row * H, cj.n = ws + pl.n[l] + row * H, cj.ghn = ws + pl.ghn[l] + row * H;
+                        cj.h_prev = hp(l) + row * H, cj.dgi = ws + pl.dgi[l] + row * H3, cj.dgh = ws + pl.dgh[l] + row * H3;
+                        cj.Bk = Bk, cj.H = H, cj.last = st == S - 1 ? 1 : 0;
+                        hipLaunchKernelGGL(okMemTrainCellKernel, blocks(static_cast<long>(Bk) * H), dim3(256), 0, h->stream, cj);
+                        OK_HIP(h, hipGetLastError());
+                        if (st > 0)
+                        {
+                            OkMemTrainGemm bk{};
+                            bk.a = cj.dgh, bk.a_rs = H3, bk.a_cs = 1, bk.b = net + at.whh[l], bk.b_rs = H, bk.b_cs = 1;
+                            bk.c = ws + pl.back, bk.c_rs = H, bk.M = Bk, bk.N = H, bk.K = H3;
+                            if (const int rc = memTrainProduct(h, bk))
+                                return rc;
+                        }
+                    }
+                    if (l > 0)
+                    {
+                        OkMemTrainGemm dx{};
+                        dx.a = ws + pl.dgi[l], dx.a_rs = H3, dx.a_cs = 1, dx.b = net + at.wih[l], dx.b_rs = H, dx.b_cs = 1;
+                        dx.c = ws + pl.down, dx.c_rs = H, dx.M = P, dx.N = H, dx.K = H3;
+                        if (const int rc = memTrainProduct(h, dx))
+                            return rc;
+                    }
+                }
+                // ---- the parameter sums over the positions: one launch
+                for (int l = 0; l < s.L; ++l)
+                {
+                    const int       in = ok_memory_in(s, l);
+                    OkMemTrainGemm &wi = sums.job[sums.count++];
+                    wi.a = ws + pl.dgi[l], wi.a_rs = 1, wi.a_cs = H3;
+                    wi.b = l == 0 ? ws + pl.x0 : hp(l - 1) + static_cast<size_t>(Bk) * H, wi.b_rs = l == 0 ? in0 : H, wi.b_cs = 1;
+                    wi.c = g + at.wih[l], wi.c_rs = in, wi.c_ones = g + at.bih[l], wi.M = H3, wi.N = in, wi.K = P, wi.div = count;
+                    OkMemTrainGemm &wh = sums.job[sums.count++];
+                    wh.a = ws + pl.dgh[l], wh.a_rs = 1, wh.a_cs = H3, wh.b = hp(l), wh.b_rs = H, wh.b_cs = 1;
+                    wh.c = g + at.whh[l], wh.c_rs = H, wh.c_ones = g + at.bhh[l], wh.M = H3, wh.N = H, wh.K = P, wh.div = count;
+                }
+                OkMemTrainGemm &hw = sums.job[sums.count++];
+                hw.a = ws + pl.zn, hw.a_rs = 1, hw.a_cs = Z, hw.b = top, hw.b_rs = H, hw.b_cs = 1;
+                hw.c = g + at.hw, hw.c_rs = H, hw.c_ones = g + at.hb, hw.M = Z, hw.N = H, hw.K = P, hw.div = count;
+            }
+            int tiles = 0;
+            for (int i = 0; i < sums.count; ++i)
+                tiles = std::max(tiles, okMemTrainTiles(sums.job[i]));
+            hipLaunchKernelGGL(okMemTrainGemmKernel, dim3(static_cast<unsigned>((tiles + kMemTrainWaves - 1) / kMemTrainWaves), static_cast<unsigned>(sums.count)),
+                               dim3(kMemTrainThreads), 0, h->stream, sums);
+            OK_HIP(h, hipGetLastError());
+            hipLaunchKernelGGL(okMemTrainLossKernel, dim3(1), dim3(64), 0, h->stream, ws + pl.lossj, Z, count, loss_at);
+            OK_HIP(h, hipGetLastError());
+            if (!update)
+                continue;
+            // ---- the norm, level by level, then the step
+            int    left = (T + OK_MEMTRAIN_BLOCK - 1) / OK_MEMTRAIN_BLOCK;
+            float *from = ws + pl.sum_a, *to = ws + pl.sum_b;
+            hipLaunchKernelGGL(okMemTrainSquareKernel, blocks(left), dim3(256), 0, h->stream, g, T, from);
+            OK_HIP(h, hipGetLastError());
+            while (left > 1)
+            {
+                const int next = (left + OK_MEMTRAIN_BLOCK - 1) / OK_MEMTRAIN_BLOCK;
+                hipLaunchKernelGGL(okMemTrainSumKernel, blocks(next), dim3(256), 0, h->stream, from, left, to);
+                OK_HIP(h, hipGetLastError());
+                std::swap(from, to);
+                left = next;
+            }
+            const float lr = lr_schedule != nullptr ? lr_schedule[at_step] : c.lr;
+            hipLaunchKernelGGL(okMemTrainTickKernel, dim3(1), dim3(64), 0, h->stream, t_dev, adam_dev, okMemTrainConsts(c), lr);
+            OK_HIP(h, hipGetLastError());
+            OkMemTrainStepJob sj{};
+            sj.params = net, sj.m = ws + pl.m, sj.v = ws + pl.v, sj.grad = g, sj.total = from, sj.adam = adam_dev;
+            sj.norm_out = norm != nullptr ? norm + at_step : nullptr;
+            sj.grad_out = (e + 1 == epochs && k + 1 == slices) ? grad_out : nullptr;
+            sj.clip_grad = c.clip_grad, sj.decay = ok_memtrain_decay(lr, c.weight_decay), sj.T = T;
+            hipLaunchKernelGGL(okMemTrainStepKernel, blocks(T), dim3(256), 0, h->stream, sj);
+            OK_HIP(h, hipGetLastError());
+        }
+    return update ? memoryRepack(h) : OKENV_OK; // (the act's copy of the matrices follows the last step; the training reads the vector itself)
 }
 
 // ---- the replay rings' entries, behind the exported functions' OK_QUIESCE ---------------------------------------------------------
@@ -5454,6 +5645,7 @@ extern "C"
             return driverRefuses(h, OKENV_ERR_INVALID, kWorldDriver, "create", why);
         const ok_world_shape s = okWorldShape(*config);
         h->mem_drv.ok          = false; // (a memory belongs to the racers it was created on: okenv_memory_create attaches a new one)
+        h->mem_learn_ok        = false; // (and a learner to its memory)
         const OkWorldPlaces  pl = okWorldPlaces(s, static_cast<size_t>(h->shape.N));
         // (the conv kernels' 16.5 KB and their row table fit the default limit; the latent kernel, up to 32.1 KB, has the limit raised)
         if (const int rc = driverCreateFlat(h, kWorldDriver, static_cast<size_t>(ok_world_offsets(s).total), {kernelOf(okWorldLatentKernel)},
@@ -5613,6 +5805,7 @@ extern "C"
             return driverRefuses(h, OKENV_ERR_INVALID, kMemoryDriver, "create", why);
         const ok_memory_shape s = okMemoryShape(h->world, *config);
         const OkMemoryPlaces pl = okMemoryPlaces(s, static_cast<size_t>(h->shape.N));
+        h->mem_learn_ok         = false; // (the learner belongs to the memory that goes)
         if (const int rc = driverCreateFlat(h, kMemoryDriver, static_cast<size_t>(ok_memory_offsets(s).total), {kernelOf(okMemoryLayerKernel)},
                                             {grown(h->mem_ws, pl.words)}))
             return rc;
@@ -5697,6 +5890,151 @@ extern "C"
         if (ok_memory_params_bad(okMemoryShape(*world, *config), network))
             return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_act_host: the network vector holds a non-finite value or a std that is not > 0");
         okMemoryActHost(*world, *config, encoder, network, controllers, n, frames, crashed, hidden, throttle, steer, rec != nullptr ? *rec : okenv_memory_record{});
+        return OKENV_OK;
+    }
+
+    // ---- The memory's training (ok_memtrain.h) ------------------------------------------------------------------------------------
+
+    int64_t okenv_memory_learner_workspace_bytes(const okenv_world_config *world, const okenv_memory_config *config, const okenv_memory_learner_config *learner)
+    {
+        if (okMemoryCheckConfig(world, config) != nullptr || okMemTrainCheckConfig(learner) != nullptr)
+            return 0;
+        return static_cast<int64_t>(sizeof(float) * okMemTrainPlaces(okMemoryShape(*world, *config), learner->seq_len, learner->max_batch).words);
+    }
+
+    int64_t okenv_memory_learner_lds_bytes(const okenv_world_config *world, const okenv_memory_config *config)
+    {
+        return okMemoryCheckConfig(world, config) == nullptr ? static_cast<int64_t>(okMemTrainLdsBytes(okMemoryShape(*world, *config))) : 0;
+    }
+
+    int okenv_memory_learner_create(okenv_t h, const okenv_memory_learner_config *config)
+    {
+        OK_QUIESCE(h);
+        if (!h)
+            return fail(h, OKENV_ERR_INVALID, "okenv_memory_learner_create: NULL handle");
+        if (const char *why = okMemTrainCheckConfig(config))
+            return fail(h, OKENV_ERR_INVALID, std::string("okenv_memory_learner_create: ") + why);
+        if (!h->mem_drv.ok || !h->mem_drv.set[0])
+            return fail(h, OKENV_ERR_STATE, "okenv_memory_learner_create: needs a memory whose network has its parameters (okenv_memory_create, okenv_memory_set_params)");
+        OK_HIP(h, hipSetDevice(h->device));
+        h->mem_learn_ok = false;
+        const OkMemTrainPlaces pl = okMemTrainPlaces(memoryShape(h), config->seq_len, config->max_batch);
+        if (okMemTrainLdsBytes(memoryShape(h)) > kLidarLdsBudget)
+            return fail(h, OKENV_ERR_INVALID, "okenv_memory_learner_create: the kernels' LDS (okenv_memory_learner_lds_bytes) does not fit 160 KB");
+        if (const int rc = growBuffers(h, {grown(h->mem_learn_ws, pl.words)}))
+            return rc;
+        // (everything: the moments, the step number, and the rows of zeros in front of every layer's hidden states)
+        OK_HIP(h, hipMemsetAsync(h->mem_learn_ws.d, 0, h->mem_learn_ws.cap * sizeof(float), h->stream));
+        h->mem_learn    = *config;
+        h->mem_learn_ok = true;
+        return OKENV_OK;
+    }
+
+    int okenv_memory_learner_reset(okenv_t h)
+    {
+        OK_QUIESCE(h);
+        if (!h || !h->mem_drv.ok || !h->mem_learn_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_memory_learner_reset: call okenv_memory_learner_create first");
+        OK_HIP(h, hipSetDevice(h->device));
+        const OkMemTrainPlaces pl = okMemTrainPlaces(memoryShape(h), h->mem_learn.seq_len, h->mem_learn.max_batch);
+        // [scalars | m | v] lie together at the workspace's start
+        OK_HIP(h, hipMemsetAsync(h->mem_learn_ws.d, 0, sizeof(float) * pl.grad, h->stream));
+        return OKENV_OK;
+    }
+
+    int okenv_memory_learner_get_state(okenv_t h, okenv_memory_learner_state *out)
+    {
+        OK_QUIESCE(h);
+        if (!h || !out)
+            return fail(h, OKENV_ERR_INVALID, "okenv_memory_learner_get_state: NULL argument");
+        if (!h->mem_drv.ok || !h->mem_learn_ok)
+            return fail(h, OKENV_ERR_STATE, "okenv_memory_learner_get_state: call okenv_memory_learner_create first");
+        const ok_memory_shape  s  = memoryShape(h);
+        const OkMemTrainPlaces pl = okMemTrainPlaces(s, h->mem_learn.seq_len, h->mem_learn.max_batch);
+        const int              T = ok_memtrain_trainable(s);
+        float                 *ws = h->mem_learn_ws.d;
+        if (const int rc = driverGet(h, {vectorOf(h->mem_drv.d, out->params, ok_memory_offsets(s).total), vectorOf(ws + pl.m, out->m, T), vectorOf(ws + pl.v, out->v, T)}))
+            return rc;
+        long long t = 0;
+        OK_HIP(h, hipMemcpyAsync(&t, ws + pl.scalars + kMemTrainStepAt, sizeof(t), hipMemcpyDeviceToHost, h->stream));
+        OK_HIP(h, hipStreamSynchronize(h->stream));
+        out->t = static_cast<int64_t>(t);
+        return OKENV_OK;
+    }
+
+    int okenv_memory_update(okenv_t h, const float *latent, const float *action, int32_t rows, const int32_t *start, int32_t M, int32_t stride, int32_t B,
+                            int32_t epochs, const int32_t *order, const float *lr_schedule, const okenv_memory_learner_output *out)
+    {
+        OK_QUIESCE(h);
+        return memoryLearnRun(h, "okenv_memory_update", true, latent, action, rows, start, M, stride, B, epochs, order, lr_schedule,
+                              out != nullptr ? out->loss : nullptr, out != nullptr ? out->norm : nullptr, out != nullptr ? out->grad : nullptr);
+    }
+
+    int okenv_memory_eval(okenv_t h, const float *latent, const float *action, int32_t rows, const int32_t *start, int32_t M, int32_t stride, int32_t B, float *loss)
+    {
+        OK_QUIESCE(h);
+        if (h != nullptr && h->mem_learn_ok && loss == nullptr)
+            return fail(h, OKENV_ERR_INVALID, "okenv_memory_eval: NULL argument");
+        return memoryLearnRun(h, "okenv_memory_eval", false, latent, action, rows, start, M, stride, B, 1, nullptr, nullptr, loss, nullptr, nullptr);
+    }
+
+    int okenv_memory_update_host(const okenv_world_config *world, const okenv_memory_config *config, const okenv_memory_learner_config *learner,
+                                 okenv_memory_learner_state *state, const float *latent, const float *action, int32_t rows, const int32_t *start, int32_t M,
+                                 int32_t stride, int32_t B, int32_t epochs, const int32_t *order, const float *lr_schedule, const okenv_memory_learner_output *out)
+    {
+        if (const char *why = okMemoryCheckConfig(world, config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_memory_update_host: ") + why);
+        if (const char *why = okMemTrainCheckConfig(learner))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_memory_update_host: ") + why);
+        if (const char *why = okMemTrainCheckCall(latent, action, rows, start, M, B, epochs))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_memory_update_host: ") + why);
+        if (std::min(B, M) > learner->max_batch)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_update_host: a minibatch of min(B, M) windows is beyond the learner's max_batch");
+        if (!state || !state->params || !state->m || !state->v || state->t < 0)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_update_host: state is NULL, lacks a parameter or moment vector (NULL argument), or t < 0");
+        const ok_memory_shape s = okMemoryShape(*world, *config);
+        if (ok_memory_params_bad(s, state->params))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_update_host: the network vector holds a non-finite value or a std that is not > 0");
+        const okenv_memory_learner_output none{};
+        okMemTrainUpdateHost(*learner, s, *state, latent, action, rows, start, M, stride, B, epochs, order, lr_schedule, out != nullptr ? *out : none);
+        return OKENV_OK;
+    }
+
+    int okenv_memory_eval_host(const okenv_world_config *world, const okenv_memory_config *config, const okenv_memory_learner_config *learner, const float *network,
+                               const float *latent, const float *action, int32_t rows, const int32_t *start, int32_t M, int32_t stride, int32_t B, float *loss)
+    {
+        if (const char *why = okMemoryCheckConfig(world, config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_memory_eval_host: ") + why);
+        if (const char *why = okMemTrainCheckConfig(learner))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_memory_eval_host: ") + why);
+        if (const char *why = okMemTrainCheckCall(latent, action, rows, start, M, B, 1))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_memory_eval_host: ") + why);
+        if (!network || !loss)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_eval_host: NULL argument");
+        const ok_memory_shape s = okMemoryShape(*world, *config);
+        if (ok_memory_params_bad(s, network))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_eval_host: the network vector holds a non-finite value or a std that is not > 0");
+        okMemTrainEvalHost(s, learner->seq_len, network, latent, action, rows, start, M, stride, B, loss);
+        return OKENV_OK;
+    }
+
+    int okenv_memory_window_host(const okenv_world_config *world, const okenv_memory_config *config, const float *network, const float *latent, const float *action,
+                                 int32_t rows, int32_t start, int32_t stride, int32_t seq_len, float *hidden, float *zn)
+    {
+        if (const char *why = okMemoryCheckConfig(world, config))
+            return fail(nullptr, OKENV_ERR_INVALID, std::string("okenv_memory_window_host: ") + why);
+        if (!network || !latent || !action || rows < 1 || seq_len < 1 || seq_len > OK_MEMTRAIN_MAX_SEQ || !hidden || !zn)
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_window_host: bad argument");
+        const ok_memory_shape s = okMemoryShape(*world, *config);
+        if (ok_memory_params_bad(s, network))
+            return fail(nullptr, OKENV_ERR_INVALID, "okenv_memory_window_host: the network vector holds a non-finite value or a std that is not > 0");
+        OkMemTrainSaved sv;
+        okMemTrainForwardHost(s, network, latent, action, rows, stride, seq_len, std::vector<int>{start}, sv);
+        for (int st = 0; st < seq_len; ++st)
+            for (int l = 0; l < s.L; ++l)
+                std::copy(sv.h.begin() + (static_cast<long>(l) * seq_len + st) * s.H, sv.h.begin() + (static_cast<long>(l) * seq_len + st + 1) * s.H,
+                          hidden + (static_cast<long>(st) * s.L + l) * s.H);
+        std::copy(sv.zn.begin(), sv.zn.end(), zn);
         return OKENV_OK;
     }
 

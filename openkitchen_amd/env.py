@@ -1229,6 +1229,41 @@ class BatchedEnvironment:
             rec = None if record is None else C.byref(capi.fill_pointers(capi.OkenvMemoryRecord(), record, "record", sizes))
             capi.check(self._L.okenv_debug_memory_stages(self._h, capi.ptr(frames), self.N * S * S * 4, rec, int(stages)), self._h)
 
+    # ---- the memory's training (include/okenv.h) ------------------------------------------------------
+    def memory_learner_create(self, config=None, **members):
+        """AdamW, clipping and the workspace of windows for the memory's network (capi.memory_learner_config: train_rnn.py's values):
+        moments zeroed, t = 0.  memory_create drops it again."""
+        if config is None:
+            config = capi.memory_learner_config(**members)
+        capi.check(self._L.okenv_memory_learner_create(self._h, C.byref(config)), self._h)
+        self.memory_learner_config = config
+
+    def memory_learner_reset(self):
+        capi.check(self._L.okenv_memory_learner_reset(self._h), self._h)
+
+    def memory_learner_state(self, out=None):
+        """The network vector, Adam's two moments of its trainable prefix ("params", "m", "v") and the int t: float32 numpy arrays, or
+        copied into the device tensors of the dict `out` (any subset).  Synchronises."""
+        T = capi.memory_trainable(self.world_config, self.memory_config)
+        return self._get_state("okenv_memory_learner_get_state", {"params": self.memory_num_params()[0], "m": T, "v": T}, out, capi.OkenvMemoryLearnerState)
+
+    def memory_update(self, latent, action, rows, start, M, B, stride=1, epochs=1, order=None, lr_schedule=None, out=None):
+        """okenv_memory_update: enqueues every minibatch of every epoch on the handle's stream, no synchronisation.  latent [rows, Z],
+        action [rows, 2] float32 and start [M] int32: device tensors / addresses; order: None or a device int32 tensor [epochs, M];
+        lr_schedule: None or a HOST float32 numpy array, one rate per minibatch; out: None or a dict under "loss", "norm" (float32,
+        one per minibatch) and "grad" (the last minibatch's clipped gradient)."""
+        go = capi.fill_pointers(capi.OkenvMemoryLearnerOutput(), out or {}, "memory learner output")
+        if lr_schedule is not None:
+            lr_schedule = np.ascontiguousarray(lr_schedule, np.float32)
+            assert lr_schedule.size == int(epochs) * ((int(M) + int(B) - 1) // int(B)), "one rate per minibatch"
+        capi.check(self._L.okenv_memory_update(self._h, capi.ptr(latent), capi.ptr(action), int(rows), capi.ptr(start), int(M), int(stride), int(B), int(epochs),
+                                               capi.ptr(order), capi.ptr(lr_schedule), C.byref(go)), self._h)
+
+    def memory_eval(self, latent, action, rows, start, M, B, loss, stride=1):
+        """okenv_memory_eval: the loss of every minibatch of one sequential pass into the device tensor loss [ceil(M / B)], no step."""
+        capi.check(self._L.okenv_memory_eval(self._h, capi.ptr(latent), capi.ptr(action), int(rows), capi.ptr(start), int(M), int(stride), int(B),
+                                             capi.ptr(loss)), self._h)
+
     # ---- guided cost learning (include/okenv.h, DESIGN.md section 21) -------------------------------------------------------
     def gcl_create(self, **config):
         """Attaches a GCL object (policy R -> H1 -> H2 -> 2 with log_std, value R -> H1 -> H2 -> 1, cost R + 2 -> C1 -> C2 -> 1) to the

@@ -689,6 +689,51 @@ class VectorEnvironment:
         self.env.vit_head_eval(embedding, steer, M, batch, loss)
         return loss
 
+    # ---- the memory's training (include/okenv.h) -----------------------------------------------------------
+    def enable_memory_learner(self, **config):
+        """AdamW and clipping for the network of the memory attached to this environment's handle (capi.memory_learner_config: lr, beta1,
+        beta2, eps, weight_decay, clip_grad, seq_len, max_batch; train_rnn.py's by default).  A new memory drops it again."""
+        self.env.memory_learner_create(**config)
+
+    def _memory_data(self, latent, action, start):
+        Z = self.env.world_config.latent
+        for name, t, dtype, tail in (("latent", latent, torch.float32, Z), ("action", action, torch.float32, 2), ("start", start, torch.int32, None)):
+            if (not torch.is_tensor(t) or t.dtype != dtype or not t.is_contiguous() or t.device != self.device or t.numel() < 1
+                    or (tail is not None and t.shape[-1] != tail)):
+                raise ValueError("%s must be a contiguous %s tensor%s on %s" % (name, dtype, "" if tail is None else " whose last dimension is %d" % tail, self.device))
+        rows = latent.numel() // Z
+        if action.numel() != 2 * rows:
+            raise ValueError("latent and action must hold the same rows")
+        return rows, int(start.numel())
+
+    def memory_update(self, latent, action, start, batch, stride=1, epochs=1, order=None, lr_schedule=None, grad=None):
+        """Trains the memory's network on windows of recorded latents [.., Z] and actions [.., 2] (float32 tensors on this device, the
+        same leading dimensions, read as flat rows): window w begins at row start[w] (int32 tensor [M]) and steps by `stride` rows.
+        Every minibatch of `epochs` passes is enqueued on the environment's stream, no synchronisation.  order: None (sequential) or an
+        int32 tensor [epochs, M] of window indices; lr_schedule: None or a host array, one rate per minibatch.  The next memory_act acts
+        with the new network.  Returns (losses, norms), float32 tensors [epochs * ceil(M / batch)] on the device; grad: an optional
+        float32 tensor for the last minibatch's clipped gradient."""
+        rows, M = self._memory_data(latent, action, start)
+        if order is not None and (not torch.is_tensor(order) or order.dtype != torch.int32 or not order.is_contiguous() or order.device != self.device
+                                  or order.numel() != int(epochs) * M):
+            raise ValueError("order must be a contiguous int32 tensor of shape (%d, %d) on %s" % (int(epochs), M, self.device))
+        steps = max(int(epochs), 0) * ((M + int(batch) - 1) // max(int(batch), 1))
+        loss, norm = (torch.empty(steps, dtype=torch.float32, device=self.device) for _ in range(2))
+        self.env.memory_update(latent, action, rows, start, M, batch, stride, epochs, order, lr_schedule,
+                               {"loss": loss if steps else None, "norm": norm if steps else None, "grad": grad})
+        return loss, norm
+
+    def memory_eval(self, latent, action, start, batch, stride=1):
+        """The loss of every minibatch of one sequential pass with no step: a float32 tensor [ceil(M / batch)] on the device."""
+        rows, M = self._memory_data(latent, action, start)
+        loss = torch.empty((M + int(batch) - 1) // max(int(batch), 1), dtype=torch.float32, device=self.device)
+        self.env.memory_eval(latent, action, rows, start, M, batch, loss, stride)
+        return loss
+
+    def memory_learner_state(self, out=None):
+        """The network vector, Adam's moments and t (env.memory_learner_state).  Synchronises."""
+        return self.env.memory_learner_state(out)
+
     # ---- Deep-Q image racers (include/okenv.h, DESIGN.md section 29) ---------------------------------------------------------------
     def enable_image_dqn(self, config, params, capacity=None, push_all=False):
         """Attaches the reference's image Q-network (RLRacers/DQN_CNN) as a device driver and, with `capacity`, its frame ring.

@@ -252,6 +252,62 @@ def train_memory(model, latents, actions, alive, epochs=1, batch=64, lr=1e-3, we
     return losses, {k: v.detach().cpu() for k, v in stats.items()}
 
 
+def memory_window_starts(alive, seq_len=SEQ_LEN):
+    """The flat first rows t0 * N + n of memory_windows' windows, in its order, as an int32 tensor [M], without materialising them: with
+    row stride N, step s of window w is row start[w] + s * N of latents.reshape(T * N, Z)."""
+    T, N = alive.shape
+    if T <= seq_len:
+        return torch.zeros(0, dtype=torch.int32, device=alive.device)
+    ok = torch.stack([alive[k:T - seq_len + k] for k in range(seq_len + 1)]).all(0)
+    t0, n = ok.nonzero(as_tuple=True)
+    return (t0 * N + n).to(torch.int32)
+
+
+def memory_from_params(vector, latent, hidden, layers):
+    """A GRUDynamics and the statistics (train_memory's form) from a network vector (capi.memory_layout): the inverse of
+    memory_params_from_state_dict."""
+    model = GRUDynamics(latent=latent, hidden=hidden, layers=layers)
+    flat = torch.as_tensor(vector).detach().to(dtype=torch.float32, device="cpu").reshape(-1)
+    sd, stats = {}, {}
+    for name, at, shape in capi.memory_layout(capi.world_config(latent=latent), capi.memory_config(hidden=hidden, layers=layers)):
+        piece = flat[at:at + int(np.prod(shape))].reshape(tuple(shape)).clone()
+        (stats if name in STATS else sd)[name] = piece
+    model.load_state_dict(sd)
+    return model.eval(), stats
+
+
+def train_memory_device(venv, model, latents, actions, alive, epochs=1, batch=64, lr=1e-3, weight_decay=1e-4, seq_len=SEQ_LEN, seed=0, ctrl_hidden=HIDDEN,
+                        carry=True):
+    """train_memory's recipe on the device (okenv_memory_update): venv has its world racers enabled; model, a
+    GRUDynamics, supplies the shape and the initial weights and is not changed.  The statistics come from the training windows as
+    train_memory forms them and are written with the initial weights; the epochs' orders come from torch.randperm with train_memory's
+    generator; the cosine schedule is a host array.  Attaches a memory of the model's shape and its learner to venv's handle.  Returns
+    (the mean loss of every epoch, the statistics as a dict of CPU tensors, the trained network vector, a float32 device tensor)."""
+    z, a = memory_windows(latents, actions, alive, seq_len)
+    assert z.shape[0] > 0, "no window of %d steps inside one agent's life" % (seq_len + 1)
+    stats = {"z_mean": z.mean((0, 1)), "z_std": z.std((0, 1)).clamp_min(1e-6), "a_mean": a.mean((0, 1)), "a_std": a.std((0, 1)).clamp_min(1e-6)}
+    stats = {k: v.detach().cpu() for k, v in stats.items()}
+    start = memory_window_starts(alive, seq_len)
+    M, N = int(start.numel()), int(alive.shape[1])
+    steps_per_epoch = -(-M // batch)
+    sd = model.state_dict()
+    env = venv.env
+    env.memory_create(memory_config_from_state_dict(sd, ctrl_hidden=ctrl_hidden, carry=carry))
+    flat = memory_params_from_state_dict(sd, stats).to(venv.device)
+    env.memory_set_params("network", flat)
+    venv.enable_memory_learner(lr=lr, weight_decay=weight_decay, seq_len=seq_len, max_batch=min(batch, M))
+    gen = torch.Generator(device=latents.device).manual_seed(seed)
+    order = torch.stack([torch.randperm(M, device=latents.device, generator=gen) for _ in range(epochs)]).to(torch.int32).contiguous()
+    total = max(1, epochs * steps_per_epoch)  # CosineAnnealingLR with eta_min 0: the rate of step i
+    schedule = np.array([lr * 0.5 * (1.0 + np.cos(np.pi * i / total)) for i in range(epochs * steps_per_epoch)], np.float32)
+    loss, _ = venv.memory_update(latents.contiguous(), actions.contiguous(), start, batch, stride=N, epochs=epochs, order=order, lr_schedule=schedule)
+    sizes = torch.tensor([min(batch, M - k * batch) for k in range(steps_per_epoch)], dtype=torch.float32, device=loss.device)
+    losses = ((loss.reshape(epochs, steps_per_epoch) * sizes).sum(1) / M).tolist()
+    vector = torch.empty_like(flat)
+    env.memory_get_params("network", vector)
+    return losses, stats, vector
+
+
 class WorldModelRacers:
     """main.cpp:284-369 for `population` candidates at once, after cmaes.CmaEsRacers.  encoder_model: an Encoder (eval mode is set
     here).  encoder="device": okenv_world_act, no PyTorch op in the iteration; "torch": the module behind frames_to_input plus
@@ -264,7 +320,7 @@ class WorldModelRacers:
     RAYS = (-70.0, -30.0, 0.0, 30.0, 70.0)  # the agents still cast rays for the collision check's neighbourhood; nobody reads them
 
     def __init__(self, track, population, encoder_model, device=0, seed=0, encoder="device", hidden=HIDDEN, sigma=0.5, reset_randomly=False,
-                 max_steps=1000, graph_chunk=8, skip_crashed=True, memory=None, memory_stats=None, carry=True):
+                 max_steps=1000, graph_chunk=8, skip_crashed=True, memory=None, memory_stats=None, carry=True, memory_shape=None):
         assert encoder in ("device", "torch"), 'encoder is "device" or "torch"'
         self.encoder, self.max_steps, self.graph_chunk = encoder, int(max_steps), int(graph_chunk)
         self.venv = VectorEnvironment(track, population, ray_angles_deg=np.array(self.RAYS, dtype=np.float32), device=device,
@@ -279,6 +335,9 @@ class WorldModelRacers:
         self._encoder_flat = world_params_from_state_dict(sd, S).to(self.venv.device)
         env.world_set_params("encoder", self._encoder_flat)
         env.world_set_lane_widths(self.venv.track.wl, self.venv.track.wr)
+        if torch.is_tensor(memory):  # train_memory_device's network vector, with memory_shape = (hidden, layers): its statistics are inside
+            assert memory_shape is not None, "a network vector needs memory_shape=(hidden, layers)"
+            memory, memory_stats = memory_from_params(memory, self.config.latent, *memory_shape)
         self.memory, self.carry = memory, bool(carry)
         width = self.config.latent + 2
         if memory is not None:
@@ -384,5 +443,6 @@ class WorldModelRacers:
 
 __all__ = ["Encoder", "Decoder", "VAE", "fold_batchnorm", "world_config_from_state_dict", "world_params_from_state_dict", "frames_to_input",
            "train_vae", "WorldModelRacers", "THROTTLE", "STEER_SCALE", "Z_DIM", "HIDDEN", "GRUDynamics", "memory_config_from_state_dict",
-           "memory_params_from_state_dict", "identity_stats", "collect_latents", "memory_windows", "train_memory", "MEMORY_HIDDEN",
+           "memory_params_from_state_dict", "identity_stats", "collect_latents", "memory_windows", "train_memory", "memory_window_starts",
+           "memory_from_params", "train_memory_device", "MEMORY_HIDDEN",
            "MEMORY_LAYERS", "SEQ_LEN"]
