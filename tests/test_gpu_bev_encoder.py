@@ -136,22 +136,62 @@ def encode_case(gpu, name, N):
 def test_encode_device_equals_host(gpu, name, N):
     """Layer sides below a tile (8 / 4 / 2: tiles of 4) and not a multiple of one (20 / 10 / 5: tiles of 8, partial at every edge), one
     16-column tile, k = 5 on every layer; one frame, two, and seventeen with crashed agents among them."""
+    assert mirror.reaches(name, N)
     encode_case(gpu, name, N)
 
 
 def test_encode_device_equals_host_reference_shape(gpu):
+    assert mirror.reaches("reference")
     encode_case(gpu, "reference", 3)
 
 
 def test_encode_device_equals_host_mixed_shape(gpu):
     """Mixed kernels, the widest channel count against the narrowest, the widest projection, sides 12 / 6 / 3: tiles of 8, then of 4."""
+    assert mirror.reaches("mixed")
     encode_case(gpu, "mixed", 5)
 
 
 def test_encode_device_equals_host_front_tile_limited_by_the_lds(gpu):
     """The one path the four shapes above do not reach: the front kernel on tiles of 4 because 128 channels with k1 = 5 leave no room for
     a tile of 8, the back kernel on tiles of 8."""
+    assert mirror.reaches("front4_back8")
     encode_case(gpu, "front4_back8", 2)
+
+
+def path_case(gpu, name):
+    """A shape that exists for one path of the two conv kernels, at the frames its predicate names: the predicate first (mirror.REACHES,
+    restated from the kernels' prose and held to the source in tests/test_bev_encoder_rule.py), so that an edit to the shape cannot
+    leave the path unnoticed."""
+    N = mirror.REACHES[name][0]
+    assert name in mirror.NEW_SHAPES and mirror.reaches(name, N), (name, mirror.geometry(mirror.SHAPES[name], N))
+    encode_case(gpu, name, N)
+
+
+def test_encode_device_equals_host_front_tiles_of_4_with_a_partial_one(gpu):
+    """The front kernel at T = 4 (one row tile a unit of layer 1) with a partial last tile: layer 1 is 10 wide, three tiles a side of
+    4, 4 and 2, the last one's stores guarded at the right and bottom edge; tile (1, 1) reads no padding.  The back kernel on one
+    tile of 8 of which 5 x 5 are stored."""
+    path_case(gpu, "front4_ragged")
+
+
+def test_encode_device_equals_host_back_tiles_of_4_several_a_frame(gpu):
+    """The back kernel at T = 4 -- okConv<OkConvWalk, 1, 4, true>, one row tile a unit -- with several tiles a frame: 128 channels
+    under k2 = 5 leave no room for a tile of 8 (186 656 B), layer 2 is 5 wide, so two tiles a side of 4 and 1: origins other than
+    (0, 0), a patch that starts inside the image (at row 6 of layer 1's 10), the guarded store at the right and bottom edge.  Three
+    frames: twelve workgroups, the frame of one its index over four."""
+    path_case(gpu, "back4_tiles")
+
+
+def test_encode_device_equals_host_tiles_of_8_with_a_partial_last(gpu):
+    """Both kernels at T = 8 with a partial tile behind full ones: the front 3 x 3 tiles of 8, 8 and 4, of which tile (1, 1) reads no
+    padding in its patch of layer 0's output or of the frame; the back 2 x 2 tiles of 8 and 2."""
+    path_case(gpu, "back8_ragged")
+
+
+def test_encode_device_equals_host_tiles_of_4_in_both_kernels(gpu):
+    """Both kernels at T = 4 with several tiles: 128 channels under k = 5 in front of layer 1 and of layer 2; 3 x 3 tiles in front (4,
+    4, 2), 2 x 2 behind (4, 1); k0 = 5, seven groups of layer 0 with three filler taps; 32 channels pooled, 48 projected."""
+    path_case(gpu, "both4_tiles")
 
 
 def flow_policy(seed, frame_size):

@@ -146,22 +146,69 @@ def act_case(gpu, name, N):
 def test_act_device_equals_host(gpu, name, N):
     """Row counts that are no multiple of 16 (49 and 25; 9 and 1), frame rows no window reaches, one 16-column tile; one frame, two,
     and seventeen -- one full and one partial row tile of the head -- with crashed agents among them."""
+    assert mirror.reaches(name, N)
     act_case(gpu, name, N)
 
 
 def test_act_device_equals_host_wide_shape(gpu):
     """Stride 1 on the frame, a pointwise layer, stride = kernel, 64 / 16 / 128 channels, 512 hidden units (four column tiles a wave),
     F = 4608 (18 chunks of the head), layer 1's output larger than the frame."""
+    assert mirror.reaches("wide")
     act_case(gpu, "wide", 5)
 
 
 def test_act_device_equals_host_reference_shape(gpu):
+    assert mirror.reaches("reference")
     act_case(gpu, "reference", 3)
 
 
 def test_act_device_equals_host_three_column_tiles(gpu):
     """The head kernel's one form the four shapes above do not reach: 20 column tiles on 8 waves, three a wave, the last on four waves."""
+    assert mirror.reaches("three_tiles")
     act_case(gpu, "three_tiles", 2)
+
+
+def path_case(gpu, name):
+    """A shape that exists for one path of the kernels, at the population its predicate names: the predicate first (mirror.REACHES,
+    restated from the kernels' prose and held to the source in tests/test_cnn_rule.py), so that an edit to the shape cannot leave
+    the path unnoticed."""
+    N = mirror.REACHES[name][0]
+    assert name in mirror.NEW_SHAPES and mirror.reaches(name, N), (name, mirror.geometry(mirror.SHAPES[name], N))
+    act_case(gpu, name, N)
+
+
+def test_act_device_equals_host_ragged_chunk(gpu):
+    """okConvFc1's chunk loop with a partial chunk behind a full one: F = 400, the second chunk 144 features in 9 groups (kc4 = 36 in
+    the staging split, weight groups 16 .. 24).  17 agents: two head workgroups, the second with one agent, whose 16 staged rows all
+    repeat agent 16 through both chunks.  Nine head tiles: CT = 2 with the second tile on wave 0 alone.  Layer 0 with k0 = 3, nine
+    taps and three fillers on the last tap, under stride 3 (frame row and column 21 unread); a pointwise layer 2."""
+    path_case(gpu, "ragged_chunk")
+
+
+def test_act_device_equals_host_one_group_tail(gpu):
+    """F = 784: three whole chunks and a last one of a single group (kc4 = 4: a staged row is four float4's).  k0 = 1: one tap and
+    three fillers, the stay-on-the-last-tap rule from the first advance on.  128 channels into layer 1: the walk's channel wrap after
+    eight groups, 32 groups a chain.  289 rows of layer 0: ten row blocks, one live row in the last.  Eight head tiles on eight waves
+    exactly.  154 500 B of LDS, the most of any case."""
+    path_case(gpu, "one_group_tail")
+
+
+def test_act_device_equals_host_wide_inputs(gpu):
+    """k0 = 7: 13 groups, three fillers.  128 columns out of layer 1 and 128 channels into layer 2.  F = 288: a tail chunk of two
+    groups.  17 head tiles: CT = 3 with the third tile on wave 0 alone."""
+    path_case(gpu, "wide_inputs")
+
+
+def test_act_device_equals_host_long_chains(gpu):
+    """k0 = 6: nine groups and no filler.  Layer 1 with k = 8: 64 taps behind layer 0, 128 groups a chain.  Layer 2 with stride 4 under
+    k = 4 onto a single position, 128 columns.  F = 128: one partial chunk of eight groups.  24 head tiles: CT = 3 exactly."""
+    path_case(gpu, "long_chains")
+
+
+def test_act_device_equals_host_four_tiles_one_wave(gpu):
+    """25 head tiles: CT = 4 with the fourth tile on wave 0 alone, at 17 agents in two workgroups.  k0 = 2: one group, no filler.
+    Stride 4 in layer 1."""
+    path_case(gpu, "four_tiles_one_wave")
 
 
 def image_policy(seed, S):
